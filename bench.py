@@ -35,6 +35,10 @@ roofline         : dominant kernel symbol by time; achieved = sum(algorithmic by
                    profiles/pmc_*.json ONLY when those files were produced from the same kernel sources (sha256 stamp).
 cpu_baseline     : the CPU oracle (oracle/, a port of the reference's int32 CPU forward) timed on the host cores for a bounded
                    sample of the same workload, rank 0 at N = 1 only; `c1` = BASELINE config 1 (ResNet-18, bs 1) timed the same way.
+
+--dump-outputs DIR: after the headline region, rank 0 writes the logits of its LAST timed step (what the caller of the path receives: the
+                   gathered [N * bs, classes] block at N > 1) as DIR/logits.npy, float32.  Inputs and parameters are seeded, so two builds run
+                   with the same arguments can be compared output for output.
 """
 import argparse
 import hashlib
@@ -53,6 +57,7 @@ OPS_PER_IMG = {'resnet50': 8.178368512e9, 'resnet18': 3.628146688e9, 'mobilenet_
 STRUCT_BYTES_PER_IMG = {'resnet50': 93444000.0, 'resnet18': 20830112.0, 'mobilenet_v2': 20602656.0, 'mobilenet_v1': 28911520.0}
 PRETTY = {'resnet50': 'ResNet-50', 'resnet18': 'ResNet-18', 'mobilenet_v2': 'MobileNet-V2', 'mobilenet_v1': 'MobileNet-V1'}
 MIN_TIMED_S = 0.2              # below this the two-deep pipeline's fill / drain is a visible share of the timed region
+DUMP_MAX_BYTES = 64 * 10 ** 6  # --dump-outputs writes at most this much
 
 
 def csrc_sha256():
@@ -78,6 +83,18 @@ def stamped_json(name, stamp):
     if d.get('csrc_sha256') != stamp:
         return None, f'profiles/{name} was measured on other kernel sources (stamp mismatch): dropped'
     return d, None
+
+
+def dump_outputs(out_dir, logits):
+    """--dump-outputs: `logits` as <out_dir>/logits.npy (float32).  A block over DUMP_MAX_BYTES keeps a fixed, seeded sample of its rows
+    (in order): the same rows on every run with the same arguments."""
+    import numpy as np
+    a = np.ascontiguousarray(logits, dtype=np.float32)
+    keep = max(1, DUMP_MAX_BYTES // max(1, a[0].nbytes))
+    if a.shape[0] > keep:
+        a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, 'logits.npy'), a)
 
 
 def cpu_baseline(spec, params, x_np, x_fl, ref_logits, budget_s=12.0):
@@ -152,7 +169,10 @@ def main():
     ap.add_argument('--hw', type=int, default=224, help=argparse.SUPPRESS)
     ap.add_argument('--autotune', action='store_true', help='measured tile selection (f8_net_autotune) instead of the planner heuristics; '
                     'measured: re-tiles ~12 launches, gain within run-to-run noise, so off by default')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write the logits of the last timed step as DIR/logits.npy (float32)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(launch_ranks(args.gpus))
 
@@ -273,6 +293,8 @@ def main():
 
     if dry:
         dt, last = timed(pipe_mode, args.steps, args.warmup)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, last['full'].cpu().numpy())
         selfcheck = f8dist.verify_gather(last['local'], last['full'], BS, args.steps, last['dt_own'])
         # every rank's gathered logits must hold every rank's shard, in rank order (the stub forward is a function of the images alone)
         full = f8dist.ShardedForward(lambda t: net.run(t, out=torch.empty((BS, spec.num_classes))), spec.num_classes)(x)
@@ -311,6 +333,8 @@ def main():
     # (3) the headline: W warm-up steps, then EXACTLY K timed steps
     dt, last = timed(pipe_mode, args.steps, args.warmup)
     logits, x_last = last['local'], last['x']
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last['full'].cpu().numpy())
     # N > 1: the first multi-GPU launch verifies itself: the ranks RCCL really connected, each rank's own rate, and every rank's
     # gathered block against a checksum its owner computed
     selfcheck = f8dist.verify_gather(last['local'], last['full'], BS, args.steps, last['dt_own']) if world > 1 else None

@@ -61,6 +61,12 @@ def float_key(int_key: str) -> str:
     return '.'.join(parts)
 
 
+def _sqrt(x):
+    """Correctly rounded float32 square root.  torch.sqrt (and `** 0.5`) of a CPU float32 tensor goes through MKL's vector math, whose code
+    path, and with it the last bit, depends on the host CPU; a square root taken in float64 and rounded to float32 is exact on every host."""
+    return torch.sqrt(x.double()).to(x.dtype)
+
+
 def fix_quant(x, wl, fl, align_dim, signed):
     """fix_quant_ops.py:64-87 (non-floating): round(x * 2^fl), clamp, / 2^fl."""
     expand = x.dim() - align_dim - 1
@@ -84,7 +90,7 @@ def fraclen_gridsearch(x, wl, align_dim, signed):
     errs = []
     for fl in range(wl + 1 - int(signed)):
         res = fix_quant(x, wl, torch.ones(x.shape[align_dim]) * fl * 1.0, align_dim, signed)
-        errs.append(torch.mean((x - res) ** 2) ** 0.5)
+        errs.append(_sqrt(torch.mean((x - res) ** 2)))
     return torch.argmin(torch.tensor(errs)) * 1.0
 
 
@@ -95,7 +101,7 @@ def _weight_metric(w, metric):
     if metric == 'mae':
         return torch.mean(torch.abs(w), axis=dims)
     if metric == 'rms':
-        return torch.mean(w ** 2, axis=dims) ** 0.5
+        return _sqrt(torch.mean(w ** 2, axis=dims))
     raise NotImplementedError(metric)
 
 
@@ -180,7 +186,7 @@ class _Layer:
         else:
             weight_scale = 1.0
         weight = weight * weight_scale
-        bn_std = torch.sqrt(self.bn_var + self.cfg.bn_eps)
+        bn_std = _sqrt(self.bn_var + self.cfg.bn_eps)
         if self.groups == 1:
             return (self.bn_w / bn_std)[:, None, None, None] * weight * self.fix_scaling[(...,) + (None, None)] / \
                 self.following.fix_scaling[(...,) + (None, None, None)]
@@ -201,7 +207,7 @@ class _Layer:
     @property
     def float_bias(self):
         if not self.linear:
-            bn_std = torch.sqrt(self.bn_var + self.cfg.bn_eps)
+            bn_std = _sqrt(self.bn_var + self.cfg.bn_eps)
             return (self.bn_b - self.bn_w / bn_std * self.bn_mean) / self.following.fix_scaling
         weight = self.weight * 1.0
         w_wl, _ = self.weight_format

@@ -191,6 +191,26 @@ def test_bench_dry_run_dist_world2():
     assert r3.returncode != 0 and 'WORLD_SIZE' in (r3.stderr + r3.stdout)
 
 
+def test_bench_dump_outputs_gathered_and_repeatable(tmp_path):
+    """`bench.py --dump-outputs DIR`: rank 0 writes the gathered logits of the last timed step as DIR/logits.npy (float32), and two runs with
+    the same arguments write the same array (seeded inputs: two builds compare output for output)."""
+    import subprocess
+    env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get('PYTHONPATH', ''))
+    for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
+        env.pop(k, None)
+    got = []
+    for run in ('a', 'b'):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--dry-run-dist', '--bs', '2',
+                            '--hw', '32', '--arch', 'resnet18', '--dump-outputs', str(tmp_path / run)], env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert sorted(os.listdir(tmp_path / run)) == ['logits.npy']
+        got.append(np.load(tmp_path / run / 'logits.npy'))
+    a, b = got
+    assert a.dtype == np.float32 and a.shape == (4, 1000)
+    assert np.array_equal(a, b)
+    assert not np.array_equal(a[:2], a[2:])          # both ranks' blocks, each from its own input batch
+
+
 def _verify_worker(rank, world, port, corrupt, q):
     os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
     import torch
