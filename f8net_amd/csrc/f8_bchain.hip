@@ -499,18 +499,19 @@ bool bchain_supported(int C, int H, int W) { return bchain_rows(C, H, W) > 0; }
 bool bchain_ds_supported(int C, int H, int W) { return bchain_rows(C, H, W) > 0 && C >= 128; }
 int bchain_tiles_per_img(int C, int H, int W) { const int r = bchain_rows(C, H, W); return r ? (H + r - 1) / r : 0; }
 
-// 0 = generic instance, 1 = constant formats + float-converter requantisation, 2 = constant formats + integer requantisation (f8_chain.hip: chain_fast)
-int bchain_fast(const BChainArgs& a) {
+// 0 = generic instance, 1 = constant formats + float-converter requantisation, 2 = constant formats + integer requantisation (f8_chain.hip: chain_fast);
+// ds = the chain opens with a stage-opening block, q8 = q[0] is an output form
+int bchain_fast(const BChainArgs& a, bool ds, bool q8) {
     bool f16 = true;
     for (int k = 0; k < a.nblk; ++k) {
         const BChainBlk& B = a.blk[k];
         if (!(B.relu_a && B.relu1 && B.n1 > 0 && B.n1 <= 30 && B.lo1 == 0)) return 0;
         f16 = f16 && B.n1 <= kRequantU8MaxShift;
-        if (k == 0 && a.x8in) continue;                      // opening block: its input arrives as int8, its join shifts either operand
+        if (k == 0 && ds) continue;                          // opening block: its input arrives as int8, its join shifts either operand
         if (!(B.nq > 0 && B.nq <= 30 && B.loq == 0 && B.res_shl == 0)) return 0;
         f16 = f16 && B.nq <= kRequantU8MaxShift;
     }
-    if (a.q[0].ptr) {
+    if (q8) {
         if (!(a.q[0].n > 0 && a.q[0].n <= 30 && a.q[0].lo == 0)) return 0;
         f16 = f16 && a.q[0].n <= kRequantU8MaxShift;
     }
@@ -569,11 +570,9 @@ int bchain_kernel_name(char* buf, size_t cap, int C, int H, int W, bool ds, int 
     const int nbuf = C == 64 ? BChPair<F8_BCH_S0>::nbuf : (C == 128 ? BChPair<F8_BCH_S1>::nbuf : BChPair<F8_BCH_S2>::nbuf);
     return snprintf(buf, cap, "f8::bchain_kernel<%d, %d, %d, %d, %d, %d, %d, %s, %d>", C, W, H, bchain_rows(C), nb, nbuf, fast, ds ? "true" : "false", F8_BCH_NW);
 }
-hipError_t launch_bchain(const BChainArgs& a, int C, int H, int W, hipStream_t s, char* launched, size_t cap) {
+hipError_t launch_bchain(const BChainArgs& a, int fast, int C, int H, int W, hipStream_t s) {     // fast: bchain_fast, bound with the plan (see launch_chain)
     if (a.nblk < 1 || a.nblk > kBChainMaxBlocks) return hipErrorInvalidValue;
-    const int fast = bchain_fast(a);
     const bool ds = a.x8in != nullptr;
-    if (launched) bchain_kernel_name(launched, cap, C, H, W, ds, fast);      // the instance that runs (see launch_chain)
     if (ds ? !(a.x8sc && a.wsc && a.bsc && bchain_ds_supported(C, H, W)) : !a.xr) return hipErrorInvalidValue;
 #define F8_BCH(...) (fast == 1 ? launch_bchain_t<__VA_ARGS__, 1, false>(a, s) : fast == 2 ? launch_bchain_t<__VA_ARGS__, 2, false>(a, s) : launch_bchain_t<__VA_ARGS__, 0, false>(a, s))
 #define F8_BCHD(...) (fast == 1 ? launch_bchain_t<__VA_ARGS__, 1, true>(a, s) : fast == 2 ? launch_bchain_t<__VA_ARGS__, 2, true>(a, s) : launch_bchain_t<__VA_ARGS__, 0, true>(a, s))

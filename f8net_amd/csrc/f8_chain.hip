@@ -1017,16 +1017,17 @@ static hipError_t launch_chain_t(const ChainArgs& a, hipStream_t s) {
 #define F8_CH_S2 2, 4
 #endif
 // FAST instance (see chain_kernel): 0 = generic, 1 = constant formats + float-converter requantisation, 2 = constant formats + integer requantisation
-// (option requant_float = 0, accumulators the planner cannot bound, or a shift beyond the converter form's 16)
-int chain_fast(const ChainArgs& a) {
+// (option requant_float = 0, accumulators the planner cannot bound, or a shift beyond the converter form's 16).  Decided once per plan (f8_net.cpp binds
+// it at finalize), so it reads plan facts, not pointers: bit k of `shortcut_blocks` = block k joins a shortcut conv (wsc), q8 = q[0] is an output form
+int chain_fast(const ChainArgs& a, unsigned shortcut_blocks, bool q8) {
     bool f16 = true;
     for (int k = 0; k < a.nblk; ++k) {
         const ChainBlk& B = a.blk[k];
         if (!(B.relu_a && B.relu_b && B.relu1 && B.n1 > 0 && B.n2 > 0 && B.nq > 0 && B.n1 <= 30 && B.n2 <= 30 && B.nq <= 30 && B.lo1 == 0 && B.lo2 == 0 && B.loq == 0)) return 0;
-        if (B.wsc == nullptr && B.res_shl != 0) return 0;
+        if (!(shortcut_blocks >> k & 1u) && B.res_shl != 0) return 0;
         f16 = f16 && B.n1 <= kRequantU8MaxShift && B.n2 <= kRequantU8MaxShift && B.nq <= kRequantU8MaxShift;
     }
-    if (a.q[0].ptr) {
+    if (q8) {
         if (!(a.q[0].n > 0 && a.q[0].n <= 30 && a.q[0].lo == 0)) return 0;
         f16 = f16 && a.q[0].n <= kRequantU8MaxShift;
     }
@@ -1055,12 +1056,9 @@ int chain_kernel_name(char* buf, size_t cap, int C, int MID, int H, int W, int c
                     chain_nw(C, MID, H, W, cin0, tail));
 }
 
-// `launched` (optional): receives the symbol of the instance that was started — the planner names a step before the run's arguments exist and
-// guesses `fast` from its bounds (1 or 2); chain_fast may still pick the generic instance (0): the executor corrects Step::kernel from here
-hipError_t launch_chain(const ChainArgs& a, int C, int MID, int H, int W, int cin0, hipStream_t s, char* launched, size_t cap) {
+// fast: the instance chain_fast chose when the plan was bound; chain_kernel_name(..., fast) names the symbol started here
+hipError_t launch_chain(const ChainArgs& a, int fast, int C, int MID, int H, int W, int cin0, hipStream_t s) {
     if (a.nblk < 1 || a.nblk > kChainMaxBlocks) return hipErrorInvalidValue;
-    const int fast = chain_fast(a);
-    if (launched) chain_kernel_name(launched, cap, C, MID, H, W, cin0, a.tail != 0, fast);
     if (cchain_supported(C, MID, H, W, cin0, a.tail != 0)) return launch_cchain(a, fast, s);
 #define F8_CHAIN_INST(...) (fast == 1 ? launch_chain_t<__VA_ARGS__, 1, F8_CHAIN_ROT>(a, s) : fast == 2 ? launch_chain_t<__VA_ARGS__, 2, F8_CHAIN_ROT>(a, s) : launch_chain_t<__VA_ARGS__, 0, F8_CHAIN_ROT>(a, s))
 #define F8_CHAIN_ROT false

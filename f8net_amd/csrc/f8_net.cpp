@@ -21,6 +21,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <variant>
 #include <string>
 #include <mutex>
 #include <vector>
@@ -59,7 +60,7 @@ struct Form {
 struct Tensor {
     int C = 0, H = 0, W = 0, Cs = 0, fl = 0;
     int prod = -1;
-    mutable int64_t amax = -2;         // tensor_amax(), cached (-2: not computed yet)
+    int64_t amax = -2;                 // tensor_amax(), cached (-2: not computed yet)
     std::vector<int> consumers;        // node ids
     std::vector<Form> forms;
     std::string label;
@@ -70,8 +71,8 @@ struct Node {
     int kind; int a = -1, b = -1; int out = -1;
     f8_conv_desc cd{};                 // conv / linear (as 1x1 conv)
     std::vector<int8_t> w; std::vector<int32_t> bias;   // raw OIHW int8 + bias
-    mutable int acc_ok = -1;           // conv_acc_bounded(), cached
-    mutable int64_t acc_max = -2;      // conv_acc_max(), cached (-2: not computed yet)
+    int acc_ok = -1;                   // conv_acc_bounded(), cached
+    int64_t acc_max = -2;              // conv_acc_max(), cached (-2: not computed yet)
     int relu = 0;                      // add
     int pk = 0, pstride = 0, ppad = 0; // maxpool
     int shift = 0;                     // avgpool
@@ -120,9 +121,13 @@ struct Step {
     bool dense = false;
     bool raw_input = false;            // S_INPUT: its work is done by the stem launch (S_STEMPOOL with the same flag) unless the run's input is uint8 NHWC
     std::string name;
-    mutable std::string kernel;        // device symbol as rocprofv3 prints it; chain steps: corrected by the first run from the instance the launcher really started
+    std::string kernel;                // device symbol as rocprofv3 prints it (chain steps: of the instance bind_step chose)
     double bytes_per_img = 0, bytes_const = 0, ops_per_img = 0;
     double valu_per_img = 0;           // ESSENTIAL vector lane-operations per image (f8_net_launch_valu): what the reference's semantics need once the MFMAs are done
+    // the launcher's arguments as far as the plan decides them (bind_step); run_step copies them and adds what the run decides
+    std::variant<std::monostate, ConvArgs, StemPoolArgs, FusedArgs, ChainArgs, BChainArgs, IRArgs, DwArgs, AddArgs, PoolArgs, AvgArgs, OutArgs> args;
+    // S_CHAIN / S_BCHAIN: the instance (chain_fast / bchain_fast), its geometry, workgroups per image and resident per CU, the 7x7 cluster form (f8_cchain.hip)
+    int fast = 0, C = 0, MID = 0, H = 0, W = 0, cin0 = 0, tiles = 0, wg_per_cu = 1; bool cluster = false;
 };
 
 }  // namespace
@@ -158,7 +163,6 @@ struct f8_net {
     // pipelined submission (f8_net_set_pipelined): fork dependency = the event recorded at the PREVIOUS run's entry
     int pipelined = 0; hipEvent_t start_ev[4] = {nullptr, nullptr, nullptr, nullptr}; int start_idx = 0; int pipe_count = 0; hipStream_t prev_stream = nullptr;
     int alt_idx = 0;                   // pipelined == 2: internal stream / arena copy of the next run
-    int chunk_off = 0;                 // image offset inside the arena while a chunk group runs (run_steps)
     // hipGraph of one whole run (both sub-batch streams), replayed while (input, output, N, stream) stay the same
     hipGraphExec_t g_exec = nullptr; const void* g_in = nullptr; void* g_out = nullptr; int g_N = 0; hipStream_t g_stream = nullptr; int g_warm = 0;
 };
@@ -197,7 +201,7 @@ int new_tensor(f8_net* net, int C, int H, int W, int fl, int prod) {
 // the limit, a net that is not keeps the integer form (generic kernel instances).  Cached per node.
 constexpr int64_t kAccLimit = (int64_t(1) << 31) - (int64_t(1) << 16) - 1;
 // max over the output channels of  sum |w| * max |x| + |b|  (-1: no weights to look at)
-static int64_t conv_acc_max(const Node& nd) {
+static int64_t conv_acc_max(Node& nd) {
     if (nd.acc_max != -2) return nd.acc_max;
     int64_t m = -1;
     if (nd.cd.cout > 0 && !nd.w.empty() && nd.w.size() % (size_t)nd.cd.cout == 0) {
@@ -214,7 +218,7 @@ static int64_t conv_acc_max(const Node& nd) {
     nd.acc_max = m;
     return m;
 }
-static bool conv_acc_bounded(const Node& nd) {
+static bool conv_acc_bounded(Node& nd) {
     if (nd.acc_ok >= 0) return nd.acc_ok != 0;
     const int64_t m = conv_acc_max(nd);
     nd.acc_ok = (m >= 0 && m <= kAccLimit) ? 1 : 0;
@@ -225,13 +229,13 @@ static bool conv_acc_bounded(const Node& nd) {
 // shifted sum of its operands' — which makes the int32 residual STREAM of a ResNet stage a bounded quantity: real nets sit at 2^20 .. 2^27.  -1 =
 // unknown or beyond 2^40 (the network input, pooled sums).  The chain launches requantise the stream through the float converter only below
 // kAccLimit (ChainArgs::stream_ok); beyond it `v + 2^(n-1)` may wrap as the reference's int32 add does, and the integer instances run.
-static int64_t tensor_amax(const f8_net* net, int t, int depth = 0) {
+static int64_t tensor_amax(f8_net* net, int t, int depth = 0) {
     if (t < 0 || t >= (int)net->tensors.size() || depth > 256) return -1;
-    const Tensor& T = net->tensors[t];
+    Tensor& T = net->tensors[t];
     if (T.amax != -2) return T.amax;
     int64_t m = -1;
     if (T.prod >= 0) {
-        const Node& nd = net->nodes[T.prod];
+        Node& nd = net->nodes[T.prod];
         if (nd.kind == N_CONV) m = conv_acc_max(nd);
         else if (nd.kind == N_MAXPOOL) m = tensor_amax(net, nd.a, depth + 1);
         else if (nd.kind == N_ADD) {
@@ -245,7 +249,7 @@ static int64_t tensor_amax(const f8_net* net, int t, int depth = 0) {
     T.amax = m;
     return m;
 }
-static bool stream_bounded(const f8_net* net, int t) { const int64_t m = tensor_amax(net, t); return m >= 0 && m <= kAccLimit; }
+static bool stream_bounded(f8_net* net, int t) { const int64_t m = tensor_amax(net, t); return m >= 0 && m <= kAccLimit; }
 
 // shift / clamp of a consumer's int_op_only_fix_quant; validates what the reference asserts
 int consumer_format(const Tensor& src, const f8_conv_desc& d, int* n, const char* who) {
@@ -269,8 +273,8 @@ void make_magic(uint32_t d, uint32_t* magic, int32_t* sh1, int32_t* sh2) {
 
 int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
 
-void set_q(QuantOut& q, char* ptr, const Form& f) {
-    q.ptr = (int8_t*)ptr; q.n = f.n;
+void set_q(QuantOut& q, const Form& f) {      // the format of an int8 output (its pointer: run_step)
+    q.n = f.n;
     q.lo = f.sgn ? -127 : 0; q.hi = f.sgn ? 127 : 255;
     q.bias_xor = f.sgn ? 0u : 0x80808080u;      // unsigned int8 tensors are stored biased (x ^ 0x80)
 }
@@ -793,7 +797,7 @@ static void select_outputs(f8_net* net, int t, OutSel* o, std::vector<int>* extr
 //   1/4 v_xor_b32; the ReLU in front of it is the clamp's lower bound); a joined int32 value: align-add + clamp / ReLU = 2; a max-pooled conv value: 1.
 // Addressing, lane swaps, exec masks, halo code, tile padding and recompute are NOT in it: they are what the ratio shows.
 static double out_forms8(const Step& st) { return (double)((st.out.f8[0] >= 0) + (st.out.f8[1] >= 0)); }
-static void label_conv_step(f8_net* net, Step& st, const Node& nd) {
+static void label_conv_step(f8_net* net, Step& st, Node& nd) {
     auto& ND = net->nodes;
     const f8_conv_desc& d = nd.cd;
     const Tensor& s = net->tensors[nd.a];
@@ -1540,17 +1544,7 @@ static int emit_steps(f8_net* net, int max_batch) {
                     st.ops_per_img = ops; st.bytes_per_img = b; st.bytes_const = wbytes;
                     st.valu_per_img = (double)ch.size() * px * o.C * (3.0 + 2.0 + 3.0) - 3.0 * px * o.C + 3.0 * px * o.Cs * out_forms8(st);   // per block: first conv's int8, join, the next block's int8 input; the last block's are the output forms
                     st.name = "basic_chain_x" + std::to_string(ch.size()) + (ds ? "_ds:" : ":") + tname(net, f1.out) + ".." + tname(net, nd.out);
-                    char kb[160];
-                    // the instance's arithmetic as launch_bchain picks it (bchain_fast): the float converter only for values the planner bounds
-                    bool bounded = true;
-                    for (size_t k = 0; k < ch.size(); ++k) {
-                        const Node& hk = ND[ch[k]];
-                        const Node& c1 = ND[hk.bds_a >= 0 ? hk.bds_a : hk.bb_a];
-                        bounded = bounded && conv_acc_bounded(c1) && stream_bounded(net, ND[hk.fused_add].out) && (k > 0 || hk.bds_a >= 0 || stream_bounded(net, c1.a));
-                    }
-                    bchain_kernel_name(kb, sizeof kb, o.C, o.H, o.W, ds, (opt.requant_float && bounded) ? 1 : 2);   // the name comes from f8_bchain.hip, next to the launcher
-                    st.kernel = kb;
-                    break;
+                    break;                                       // (kernel: bind_step)
                 }
                 if (nd.chain_into == i) {
                     // ---- stage chain: nd is the host conv of its LAST block
@@ -1602,23 +1596,7 @@ static int emit_steps(f8_net* net, int max_batch) {
                     }
                     const Node& a0 = tail ? ND[hf.dual] : ND[ds ? hf.fbd_a : hf.fb_a];
                     st.name = "stage_chain_x" + std::to_string(ch.size()) + (tail ? "_tail" : (ds ? "_ds" : "")) + (nd.pool >= 0 ? "+avgpool:" : ":") + tname(net, a0.out) + ".." + tname(net, nd.out);
-                    char kb[160];
-                    const int C = o.C, MID = tail ? a0.cd.cin : a0.cd.cout;
-                    int cR = 4, cW = 1;
-                    chain_shape(C, MID, o.H, o.W, tail ? hf.cd.cin : a0.cd.cin, tail, &cR, &cW);
-                    // the instance's arithmetic as launch_chain picks it (chain_fast): the float converter only for values the planner bounds
-                    bool bounded = true;
-                    for (size_t k = 0; k < ch.size(); ++k) {
-                        const Node& hh = ND[ch[k]];
-                        bounded = bounded && stream_bounded(net, ND[hh.fused_add].out);
-                        if (hh.tail) continue;
-                        const bool hds = hh.fbd_a >= 0;
-                        const Node& na = ND[hds ? hh.fbd_a : hh.fb_a]; const Node& nb = ND[hds ? hh.fbd_b : hh.fb_b];
-                        bounded = bounded && conv_acc_bounded(na) && conv_acc_bounded(nb) && (k > 0 || hds || stream_bounded(net, na.a));
-                    }
-                    chain_kernel_name(kb, sizeof kb, C, MID, o.H, o.W, tail ? hf.cd.cin : a0.cd.cin, tail, (opt.requant_float && bounded) ? 1 : 2);   // the name comes from f8_chain.hip, next to the launcher
-                    st.kernel = kb;
-                    break;
+                    break;                                       // (kernel: bind_step)
                 }
                 if (nd.fbd_a >= 0) {
                     // ---- fused stage-opening block (DS): nd is the shortcut conv, nd.dual the block's last body conv
@@ -2086,6 +2064,285 @@ static int layout_arena(f8_net* net, int max_batch) {
     return F8_OK;
 }
 
+// ------------------------------------------------------------------------------ bind
+// Fills st.args with every launch argument the plan decides: geometry, magic divisors, consumer formats, ReLU flags, join shifts, the bounds
+// of the float requantisation, output formats; for the chain launches also the instance (chain_fast / bchain_fast) and its symbol.  Weight
+// pointers are set once the weights are on the device (f8_net_upload binds again).  What a run decides is run_step's.
+static int bind_step(f8_net* net, Step& st) {
+    auto& T = net->tensors; auto& ND = net->nodes;
+    Node& nd = ND[st.node];
+    int rc = F8_OK;
+    auto W8 = [&](size_t off) { return net->d_w ? (const int8_t*)(net->d_w + off) : nullptr; };
+    auto B32 = [&](size_t off) { return (const int32_t*)W8(off); };
+    // the int8 input format of conv c: shift from its source tensor, clamp bounds, storage bias (unsigned formats are stored x ^ 0x80)
+    auto fmt = [&](const Node& c, int32_t* n, int32_t* lo = nullptr, int32_t* hi = nullptr, uint32_t* x_or = nullptr) {
+        int v = 0;
+        const int r = consumer_format(T[c.a], c.cd, &v, "finalize");
+        if (!rc) rc = r;
+        *n = v;
+        if (lo) { *lo = c.cd.input_signed ? -127 : 0; *hi = c.cd.input_signed ? 127 : 255; *x_or = c.cd.input_signed ? 0u : 0x80808080u; }
+    };
+    auto out_formats = [&](QuantOut q[2]) {
+        if (st.out.t < 0 || st.dense) return;
+        for (int k = 0; k < 2; ++k) if (st.out.f8[k] >= 0) set_q(q[k], T[st.out.t].forms[st.out.f8[k]]);
+    };
+    const bool q8 = st.out.t >= 0 && !st.dense && st.out.f8[0] >= 0;
+    const int rq_int = !net->opt.requant_float;
+    switch (st.kind) {
+        case S_INPUT: break;                              // (the input launch is the run's: run_step)
+        case S_CONV: {
+            const Tensor& sT = T[st.src_t]; const Form& sF = sT.forms[st.src_f];
+            const Tensor& oT = T[nd.out];
+            const f8_conv_desc& d = nd.cd;
+            ConvArgs a{};
+            a.w = W8(nd.w_off); a.w_bytes = (uint32_t)((size_t)nd.coutP * nd.ktot);
+            a.bias = B32(nd.b_off);
+            a.PQ = oT.H * oT.W; a.Q = oT.W;
+            make_magic((uint32_t)a.PQ, &a.mPQ, &a.s1PQ, &a.s2PQ);
+            make_magic((uint32_t)a.Q, &a.mQ, &a.s1Q, &a.s2Q);
+            a.stride = d.stride; a.kh = d.kernel; a.CK = nd.ck; a.ktot = nd.ktot; a.coutP = nd.coutP;
+            a.ncc = nd.ncc;
+            if (nd.ncc > 0) { a.rowcls = (const uint8_t*)W8(nd.rc_off); a.colcls = (const uint8_t*)W8(nd.cc_off); }
+            if (nd.stem) {
+                a.sN = (int)sF.bytes_per_img; a.sP = d.stride * sF.Wp * 4; a.sQ = d.stride * 4;
+                a.origin = 0; a.H = sF.Hp; a.W = sF.Wp; a.pad = 0; a.kw = 1;
+                a.tapH = sF.Wp * 4; a.tapW = 0;
+            } else {
+                a.sN = sT.H * sT.W * sT.Cs; a.sP = d.stride * sT.W * sT.Cs; a.sQ = d.stride * sT.Cs;
+                a.origin = -(d.pad * sT.W + d.pad) * sT.Cs; a.H = sT.H; a.W = sT.W; a.pad = d.pad; a.kw = d.kernel;
+                a.tapH = sT.W * sT.Cs; a.tapW = sT.Cs;
+            }
+            a.relu0 = st.relu0; a.deep_nk = net->opt.deep_nk; a.no_fast = net->opt.wstat_fast ? 0 : 1;
+            if (st.res_t >= 0 || nd.dual >= 0) { a.acc_shl = st.acc_shl; a.res_shl = st.res_shl; a.relu1 = st.relu1; }
+            if (nd.dual >= 0) {
+                const Node& g = ND[nd.dual];
+                const Tensor& s2 = T[st.src2_t];
+                a.w2 = W8(g.w_off); a.w2_bytes = (uint32_t)((size_t)g.coutP * g.ktot);
+                a.bias2 = B32(g.b_off);
+                a.sN2 = s2.H * s2.W * s2.Cs; a.sP2 = g.cd.stride * s2.W * s2.Cs; a.sQ2 = g.cd.stride * s2.Cs; a.ktot2 = g.ktot;
+            }
+            // the kernels that read the fragment-order weight image (run_step picks the launcher in the same order)
+            const bool frag = st.dense || nd.pool >= 0 || nd.s2w;
+            if (frag || nd.wstat || nd.wreg) a.w = W8(nd.wf_off);
+            if (!frag && nd.wstat && nd.dual >= 0) a.w2 = W8(ND[nd.dual].wf_off);
+            out_formats(a.q); st.args = a; break;
+        }
+        case S_HEAD2: case S_STEMPOOL: {
+            const bool h2 = st.kind == S_HEAD2;
+            Node& hc = h2 ? ND[nd.h2_head] : nd;          // the head conv
+            const Tensor& sT = T[st.src_t]; const Form& sF = sT.forms[st.src_f];
+            StemPoolArgs a{};
+            a.w = W8(hc.w_off); a.w_bytes = (uint32_t)((size_t)hc.coutP * hc.ktot);
+            a.bias = B32(hc.b_off);
+            a.Hp = sF.Hp; a.Wp = sF.Wp; a.org = sF.pad - hc.cd.pad;
+            a.raw_kind = -1;
+            if (h2) {
+                Node& hb = ND[nd.h2_dw];
+                const Tensor& oT = T[nd.out];
+                a.h2 = 1;
+                a.wd = W8(hb.w_off); a.bd = B32(hb.cc_off);
+                a.w1 = W8(nd.w_off); a.b1 = B32(nd.b_off);
+                fmt(hb, &a.na); fmt(nd, &a.nb);
+                a.Pc = oT.H; a.Qc = oT.W; a.P = oT.H; a.Q = oT.W;
+                a.relu0 = 1;
+                a.acc_ok = conv_acc_bounded(hc) && conv_acc_bounded(hb) && conv_acc_bounded(nd); a.rq_int = rq_int || !a.acc_ok;
+                a.rC = sT.C; a.rH = sT.H; a.rW = sT.W; a.xor8 = sF.sgn ? 0u : 0x80808080u;
+            } else {
+                const Tensor& cT = T[nd.out]; const Tensor& oT = T[ND[nd.sp_pool].out];
+                a.Pc = cT.H; a.Qc = cT.W; a.P = oT.H; a.Q = oT.W;
+                a.relu0 = st.relu0; a.rows = net->opt.stem_rows;
+                a.acc_ok = conv_acc_bounded(nd); a.rq_int = rq_int;
+            }
+            out_formats(a.q); st.args = a; break;
+        }
+        case S_FUSED: {
+            const bool ds = nd.fbd_a >= 0;                // stage-opening block: nd = shortcut conv, nd.dual = body.4
+            const Node& na = ND[ds ? nd.fbd_a : nd.fb_a]; const Node& nb = ND[ds ? nd.fbd_b : nd.fb_b]; const Node& ng = ds ? ND[nd.dual] : nd;
+            const Tensor& x = T[st.src_t];
+            FusedArgs a{};
+            a.w0 = W8(na.w_off); a.w0_bytes = (uint32_t)((size_t)na.coutP * na.ktot);
+            a.w2 = W8(nb.w_off); a.w2_bytes = (uint32_t)((size_t)nb.coutP * nb.ktot);
+            a.w4 = W8(ng.w_off); a.w4_bytes = (uint32_t)((size_t)ng.coutP * ng.ktot);
+            a.b0 = B32(na.b_off); a.b2 = B32(nb.b_off); a.b4 = B32(ng.b_off);
+            if (ds) {
+                a.wsc = W8(nd.w_off); a.wsc_bytes = (uint32_t)((size_t)nd.coutP * nd.ktot); a.bsc = B32(nd.b_off);
+                a.COUT = nd.cd.cout; a.stride2 = nd.fbd_s2 ? 1 : 0; a.stg = net->opt.opener_stg;
+            }
+            a.H = x.H; a.W = x.W; a.C = na.cd.cin; a.MID = na.cd.cout; a.R = nd.fb_R;
+            a.tiles_per_img = (ds && nd.fbd_s2) ? (x.H / 2) / nd.fb_R : (x.H + nd.fb_R - 1) / nd.fb_R;
+            fmt(nb, &a.n1, &a.lo1, &a.hi1, &a.xor1);
+            fmt(ng, &a.n2, &a.lo2, &a.hi2, &a.xor2);
+            a.relu_a = na.cd.relu; a.relu_b = nb.cd.relu;
+            a.acc_shl = st.acc_shl; a.res_shl = st.res_shl; a.relu1 = st.relu1;
+            out_formats(a.q); st.args = a; break;
+        }
+        case S_P12: {
+            Node& na = ND[nd.p12_a];
+            const Tensor& x = T[st.src_t];
+            FusedArgs a{};
+            const size_t w0 = nd.p12_s2 ? na.w_off : na.wf_off, w2 = nd.p12_s2 ? nd.w_off : nd.wf_off;   // f8_p12.hip reads fragment order
+            a.w0 = W8(w0); a.w0_bytes = (uint32_t)((size_t)na.coutP * na.ktot);
+            a.w2 = W8(w2); a.w2_bytes = (uint32_t)((size_t)nd.coutP * nd.ktot);
+            a.b0 = B32(na.b_off); a.b2 = B32(nd.b_off);
+            a.H = x.H; a.W = x.W; a.C = na.cd.cin; a.MID = na.cd.cout;
+            fmt(nd, &a.n1, &a.lo1, &a.hi1, &a.xor1);
+            a.relu_a = na.cd.relu; a.relu_b = nd.cd.relu;
+            out_formats(a.q);
+            if (nd.p12_s2) {                              // body.0 + body.2 of a stride-2 opening block on f8_opener.hip (P12); q[0] = mid2
+                a.COUT = 4 * na.cd.cout; a.R = nd.fb_R;
+                a.tiles_per_img = (x.H / 2 + nd.fb_R - 1) / nd.fb_R;
+                a.n2 = a.q[0].n; a.lo2 = a.q[0].lo; a.hi2 = a.q[0].hi; a.xor2 = a.q[0].bias_xor;      // mid2's one form = body.4's input format
+                a.stride2 = 1; a.p12only = 1; a.acc_ok = conv_acc_bounded(na) && conv_acc_bounded(nd); a.rq_int = rq_int;
+            }
+            st.args = a; break;
+        }
+        case S_CHAIN: {
+            const std::vector<int>& ch = nd.chain;
+            ChainArgs a{};
+            a.nblk = (int)ch.size();
+            unsigned shortcut_blocks = 0;
+            for (int k = 0; k < a.nblk; ++k) {
+                Node& hh = ND[ch[k]];
+                ChainBlk& B = a.blk[k];
+                if (hh.tail) {                                  // only the join of a stride-2 opening block: shortcut (hh) + body.4 (its dual)
+                    const Node& g4 = ND[hh.dual];
+                    B.w4 = W8(g4.wf_off); B.b4 = B32(g4.b_off);
+                    B.wsc = W8(hh.wf_off); B.bsc = B32(hh.b_off);
+                    B.nq = B.n1 = B.n2 = 1; B.hiq = B.hi1 = B.hi2 = 255; B.xorq = B.xor1 = B.xor2 = 0x80808080u;     // (unused: no body.0 / body.2 here)
+                    B.relu_a = B.relu_b = 1; B.relu1 = ND[hh.fused_add].relu;
+                    a.acc_ok = 1; a.stream_ok = stream_bounded(net, ND[hh.fused_add].out) ? 1 : 0; a.rq_int = rq_int;
+                    const int dfl = T[hh.out].fl - T[g4.out].fl;             // (shortcut << acc_shl) + (body.4 << res_shl)
+                    B.acc_shl = dfl < 0 ? -dfl : 0; B.res_shl = dfl > 0 ? dfl : 0;
+                    shortcut_blocks |= 1u << k;
+                    continue;
+                }
+                const bool hds = hh.fbd_a >= 0;
+                Node& na = ND[hds ? hh.fbd_a : hh.fb_a]; Node& nb = ND[hds ? hh.fbd_b : hh.fb_b];
+                const Node& ng = hds ? ND[hh.dual] : hh;
+                B.w0 = W8(na.wf_off); B.w2 = W8(nb.wf_off); B.w4 = W8(ng.wf_off);
+                B.b0 = B32(na.b_off); B.b2 = B32(nb.b_off); B.b4 = B32(ng.b_off);
+                if (hds) { B.wsc = W8(hh.wf_off); B.bsc = B32(hh.b_off); shortcut_blocks |= 1u << k; }
+                fmt(na, &B.nq, &B.loq, &B.hiq, &B.xorq);
+                fmt(nb, &B.n1, &B.lo1, &B.hi1, &B.xor1);
+                fmt(ng, &B.n2, &B.lo2, &B.hi2, &B.xor2);
+                B.relu_a = na.cd.relu; B.relu_b = nb.cd.relu; B.relu1 = ND[hh.fused_add].relu;
+                if (k == 0) { a.acc_ok = 1; a.rq_int = rq_int; a.stream_ok = (hds || stream_bounded(net, na.a)) ? 1 : 0; }   // identity first block: the stream it reads
+                a.acc_ok = a.acc_ok && conv_acc_bounded(na) && conv_acc_bounded(nb);
+                a.stream_ok = a.stream_ok && stream_bounded(net, ND[hh.fused_add].out);
+                // identity: (body.4 << acc_shl) + (block input << res_shl); opening block: (shortcut << acc_shl) + (body.4 << res_shl)
+                const int dfl = T[hh.out].fl - (hds ? T[ng.out].fl : T[na.a].fl);
+                B.acc_shl = dfl < 0 ? -dfl : 0; B.res_shl = dfl > 0 ? dfl : 0;
+            }
+            const Node& hf = ND[ch[0]];
+            const bool tail = hf.tail, ds = hf.fbd_a >= 0 || tail;
+            const Node& a0 = tail ? ND[hf.dual] : ND[ds ? hf.fbd_a : hf.fb_a];
+            const Tensor& oT = T[ND[nd.fused_add].out];      // the stage's output map (st.out.t: the pooled tensor when the pool runs in the launch)
+            a.tail = tail ? 1 : 0;
+            a.pool = nd.pool >= 0 ? 1 : 0;
+            st.C = oT.C; st.MID = tail ? a0.cd.cin : a0.cd.cout; st.H = oT.H; st.W = oT.W; st.cin0 = tail ? hf.cd.cin : a0.cd.cin;
+            chain_shape(st.C, st.MID, st.H, st.W, st.cin0, tail, &a.R, &st.wg_per_cu);
+            st.tiles = (st.H + a.R - 1) / a.R;
+            st.cluster = (!ds || tail) && cchain_supported(st.C, st.MID, st.H, st.W, st.cin0, tail);   // the 7x7 stage: clusters of eight workgroups
+            out_formats(a.q);
+            st.fast = chain_fast(a, shortcut_blocks, q8);
+            char kb[160];
+            chain_kernel_name(kb, sizeof kb, st.C, st.MID, st.H, st.W, st.cin0, tail, st.fast);
+            st.kernel = kb;
+            st.args = a; break;
+        }
+        case S_BCHAIN: {
+            const std::vector<int>& ch = nd.bchain;
+            BChainArgs a{};
+            a.nblk = (int)ch.size();
+            const bool ds = ND[ch[0]].bds_a >= 0;
+            for (int k = 0; k < a.nblk; ++k) {
+                const Node& hk = ND[ch[k]];
+                const bool hds = hk.bds_a >= 0;                 // opening block: hk = its shortcut conv
+                const Node& c2 = hds ? ND[hk.bds_b] : hk; Node& c1 = ND[hds ? hk.bds_a : hk.bb_a];
+                BChainBlk& B = a.blk[k];
+                B.wa = W8(c1.wf_off); B.wb = W8(c2.wf_off);
+                B.ba = B32(c1.b_off); B.bb = B32(c2.b_off);
+                fmt(c1, &B.nq, &B.loq, &B.hiq, &B.xorq);
+                fmt(c2, &B.n1, &B.lo1, &B.hi1, &B.xor1);
+                B.relu_a = c1.cd.relu; B.relu1 = ND[hk.fused_add].relu;
+                if (k == 0) { a.acc_ok = 1; a.rq_int = rq_int; a.stream_ok = (hds || stream_bounded(net, c1.a)) ? 1 : 0; }   // identity first block: the stream it reads
+                a.acc_ok = a.acc_ok && conv_acc_bounded(c1);
+                a.stream_ok = a.stream_ok && stream_bounded(net, ND[hk.fused_add].out);
+                // identity: (second conv << acc_shl) + (block input << res_shl); opening block: (second conv << acc_shl) + (shortcut << res_shl)
+                const int dfl = T[c2.out].fl - (hds ? T[hk.out].fl : T[c1.a].fl);
+                B.acc_shl = dfl < 0 ? -dfl : 0; B.res_shl = dfl > 0 ? dfl : 0;
+                if (hds) { a.wsc = W8(hk.wf_off); a.bsc = B32(hk.b_off); }
+            }
+            const Tensor& x = T[st.out.t];
+            st.C = x.C; st.H = x.H; st.W = x.W;
+            st.tiles = bchain_tiles_per_img(x.C, x.H, x.W);
+            out_formats(a.q);
+            st.fast = bchain_fast(a, ds, q8);
+            char kb[160];
+            bchain_kernel_name(kb, sizeof kb, st.C, st.H, st.W, ds, st.fast);
+            st.kernel = kb;
+            st.args = a; break;
+        }
+        case S_IR: {
+            Node& na = ND[nd.ir_a]; Node& nb = ND[nd.ir_b];
+            const Tensor& x = T[st.src_t];
+            const Tensor& oT = T[nd.out];
+            IRArgs a{};
+            a.w0 = W8(na.w_off); a.b0 = B32(na.b_off);
+            a.wd4 = W8(nb.rc_off); a.bd4 = B32(nb.cc_off);
+            a.w4 = W8(nd.w_off); a.b4 = B32(nd.b_off);
+            a.H = x.H; a.W = x.W; a.Ho = oT.H; a.Wo = oT.W; a.stride = nb.cd.stride; a.R = nd.ir_R; a.G = nd.ir_G;
+            a.tiles_per_img = oT.H / nd.ir_R; a.E32 = na.coutP;
+            fmt(nb, &a.n1, &a.lo1, &a.hi1, &a.xor1);
+            fmt(nd, &a.n2, &a.lo2, &a.hi2, &a.xor2);
+            a.relu_a = na.cd.relu; a.relu_b = nb.cd.relu; a.relu0 = st.relu0;
+            a.acc_ok = conv_acc_bounded(na) && conv_acc_bounded(nb); a.rq_int = rq_int;
+            a.acc_shl = st.acc_shl; a.res_shl = st.res_shl; a.relu1 = st.relu1;
+            make_magic((uint32_t)x.W, &a.mW, &a.s1W, &a.s2W);
+            make_magic((uint32_t)(x.H * x.W), &a.mHW, &a.s1HW, &a.s2HW);
+            make_magic((uint32_t)oT.W, &a.mWo, &a.s1Wo, &a.s2Wo);
+            make_magic((uint32_t)(nd.ir_R * oT.W), &a.mRWo, &a.s1RWo, &a.s2RWo);
+            out_formats(a.q); st.args = a; break;
+        }
+        case S_DW: {
+            const Tensor& sT = T[st.src_t];
+            const Tensor& oT = T[nd.out];
+            DwArgs a{};
+            a.w = W8(nd.w_off); a.bias = B32(nd.b_off);
+            a.w4 = W8(nd.rc_off); a.bias4 = B32(nd.cc_off);
+            a.H = sT.H; a.W = sT.W; a.P = oT.H; a.Q = oT.W; a.Cs = sT.Cs; a.stride = nd.cd.stride; a.pad = nd.cd.pad;
+            a.in_signed = nd.cd.input_signed; a.relu0 = st.relu0; a.use_dot4 = net->opt.dw_dot4; a.use_mma = net->opt.dw_mma; a.acc_ok = conv_acc_bounded(nd); a.rq_int = rq_int;
+            out_formats(a.q); st.args = a; break;
+        }
+        case S_ADD: case S_REQUANT: {
+            AddArgs a{};
+            a.Cs = T[st.src_t].Cs; a.a_shl = st.acc_shl; a.b_shl = st.res_shl; a.relu = st.relu1;
+            out_formats(a.q); st.args = a; break;
+        }
+        case S_MAXPOOL: {
+            const Tensor& sT = T[st.src_t]; const Form& sF = sT.forms[st.src_f];
+            const Tensor& oT = T[nd.out];
+            PoolArgs a{};
+            a.in_is_i8 = sF.kind == FORM_I8; a.in_signed = sF.sgn;
+            a.H = sT.H; a.W = sT.W; a.P = oT.H; a.Q = oT.W; a.Cs = sT.Cs; a.k = nd.pk; a.stride = nd.pstride; a.pad = nd.ppad;
+            out_formats(a.q); st.args = a; break;
+        }
+        case S_AVGPOOL: {
+            const Tensor& sT = T[st.src_t];
+            AvgArgs a{};
+            a.HW = sT.H * sT.W; a.Cs = sT.Cs;
+            out_formats(a.q); st.args = a; break;
+        }
+        case S_OUTPUT: {
+            const Tensor& sT = T[st.src_t];
+            OutArgs a{};
+            a.C = sT.C; a.HW = sT.H * sT.W; a.Cs = sT.Cs; a.as_float = net->out_float;
+            st.args = a; break;
+        }
+    }
+    return rc;
+}
+
 int f8_net_finalize(f8_net* net, int max_batch) {
     if (!net) return fail(F8_ERR_INVALID, "f8_net_finalize: null net");
     if (net->finalized) return fail(F8_ERR_STATE, "f8_net_finalize: already finalized");
@@ -2105,6 +2362,8 @@ int f8_net_finalize(f8_net* net, int max_batch) {
     int rc = emit_steps(net, max_batch);            // 3:  the launches, packed weights, algorithmic bytes / ops
     if (rc) return rc;
     if ((rc = layout_arena(net, max_batch))) return rc;   // 4: lifetimes, first-fit arena
+    for (Step& st : net->steps)                           // 5: the launch arguments the plan decides
+        if ((rc = bind_step(net, st))) return rc;
     net->max_batch = max_batch;
     net->finalized = true;
     return F8_OK;
@@ -2189,6 +2448,7 @@ int f8_net_upload(f8_net* net) {
         return hip_fail(e, "hipMemcpy(weights)");
     if ((e = hipMalloc((void**)&net->d_err, 256)) != hipSuccess) return hip_fail(e, "hipMalloc(error words)");
     if ((e = hipMemset(net->d_err, 0, 256)) != hipSuccess) return hip_fail(e, "hipMemset(error words)");
+    for (Step& st : net->steps) (void)bind_step(net, st);     // again, now with the weight pointers (the plan part cannot fail twice)
     for (const Step& st : net->steps)
         if ((st.kind == S_CHAIN || st.kind == S_BCHAIN) && !net->d_chain) {
             size_t xchg = kChainXchgBytes;
@@ -2215,30 +2475,55 @@ int f8_net_upload(f8_net* net) {
     return F8_OK;
 }
 
-// Runs one launch for images [n0, n0 + N) of the batch.  Every sub-batch works in its OWN copy of the arena
-// (index `part`): the arena packs tensors by lifetime assuming the steps of one batch run in order, so two
-// sub-batches that are at different steps at the same time must not share it (a later, larger tensor of the
-// sub-batch that is ahead would overlap an earlier tensor the other one is still reading).
-static int run_step(f8_net* net, const Step& st, const int32_t* input, void* output, int n0, int N, int part, hipStream_t s) {
-    auto& T = net->tensors;
+// Image groups (clusters, in the 7x7 cluster form) a chain launch over N images starts.  Every workgroup of a chain launch must be
+// resident: a device with fewer slots than one image has tiles (or than one cluster needs) cannot run it — 0, after fail().
+static int chain_launch_groups(const f8_net* net, const Step& st, int N) {
+    const int slots = (net->num_cu > 0 ? std::min(net->num_cu, 256) : 256) * st.wg_per_cu;
+    if (slots < st.tiles) {
+        fail(F8_ERR_STATE, "f8_net_run: a stage-chain launch needs %d co-resident workgroups per image, the device has %d compute units (plan with fuse_chain = 0 / fuse_bchain = 0)", st.tiles, net->num_cu);
+        return 0;
+    }
+    if (!st.cluster) return chain_groups(N, slots / st.tiles);
+    const int ng = cchain_clusters(N, slots);
+    if (ng < 1) fail(F8_ERR_STATE, "f8_net_run: the 7x7 stage-chain launch needs 8 co-resident workgroups, the device has %d compute units (plan with fuse_chain7 = 0)", net->num_cu);
+    return ng;
+}
+
+// Runs one launch for images [n0, n0 + N) of the batch; c0 = the chunk's first image inside the arena (for_each_launch).  Every
+// sub-batch works in its OWN copy of the arena (index `part`): the arena packs tensors by lifetime assuming the steps of one batch
+// run in order, so two sub-batches that are at different steps at the same time must not share it (a later, larger tensor of the
+// sub-batch that is ahead would overlap an earlier tensor the other one is still reading).  The launch's arguments are st.args
+// (bind_step) plus what this run decides: arena and caller pointers, the batch, the chain scratch.
+static int run_step(const f8_net* net, const Step& st, const int32_t* input, void* output, int n0, int N, int c0, int part, hipStream_t s) {
+    const auto& T = net->tensors;
     char* A = net->d_arena + (size_t)part * net->arena_stride;
-    auto fp = [&](const Form& F) -> char* { return A + F.off + (size_t)net->chunk_off * F.bytes_per_img; };
+    auto fp = [&](const Form& F) -> char* { return A + F.off + (size_t)c0 * F.bytes_per_img; };
     const Node& nd = net->nodes[st.node];
     auto fill_out = [&](int32_t** out32, QuantOut q[2]) {
-        *out32 = nullptr; q[0].ptr = q[1].ptr = nullptr; q[0].n = q[1].n = 0; q[0].lo = q[1].lo = 0; q[0].hi = q[1].hi = 0;
         if (st.out.t < 0 || st.dense) return;
         const Tensor& o = T[st.out.t];
         if (st.out.f32 >= 0) *out32 = (int32_t*)fp(o.forms[st.out.f32]);
-        for (int k = 0; k < 2; ++k) if (st.out.f8[k] >= 0) set_q(q[k], fp(o.forms[st.out.f8[k]]), o.forms[st.out.f8[k]]);
+        for (int k = 0; k < 2; ++k) if (st.out.f8[k] >= 0) q[k].ptr = (int8_t*)fp(o.forms[st.out.f8[k]]);
+    };
+    char* const chain = net->d_chain ? net->d_chain + (size_t)part * net->chain_stride : nullptr;
+    const uint32_t* chain_err = chain ? (const uint32_t*)chain + kChainErrWord : nullptr;
+    auto chain_scratch = [&](auto& a) {
+        if (!chain) return fail(F8_ERR_STATE, "f8_net_run: chain scratch missing");
+        a.sync = (uint32_t*)chain;
+        a.err = a.sync + kChainErrWord; a.err_host = net->h_err_dev; a.epoch = net->epoch;
+        a.xchg = (int8_t*)(chain + 4096);
+        a.timeout_ticks = (uint32_t)std::min<long long>((long long)net->opt.chain_timeout_ms * 100000ll, 0x7fffffffll);
+        return (int)F8_OK;
     };
     hipError_t e = hipSuccess;
     switch (st.kind) {
         case S_INPUT: {
-            const Tensor& o = T[st.out.t];
             if (st.raw_input && !(net->in_u8 && net->in_u8_nhwc)) break;       // the stem launch reads the caller's buffer
-            InArgs a{}; a.x = input + (size_t)n0 * o.C * o.H * o.W; a.N = N; a.C = o.C; a.H = o.H; a.W = o.W;
-            if (net->in_f32) { a.xf = net->in_f32 + (size_t)n0 * o.C * o.H * o.W; a.scale = net->in_scale; a.qlo = net->in_lo; a.qhi = net->in_hi; }
-            if (net->in_u8) { a.xu8 = net->in_u8 + (size_t)n0 * o.C * o.H * o.W; a.u8_nhwc = net->in_u8_nhwc; memcpy(a.lut, net->in_lut, sizeof a.lut); }
+            const Tensor& o = T[st.out.t];
+            const size_t img = (size_t)o.C * o.H * o.W;
+            InArgs a{}; a.x = input + (size_t)n0 * img; a.N = N; a.C = o.C; a.H = o.H; a.W = o.W;
+            if (net->in_f32) { a.xf = net->in_f32 + (size_t)n0 * img; a.scale = net->in_scale; a.qlo = net->in_lo; a.qhi = net->in_hi; }
+            if (net->in_u8) { a.xu8 = net->in_u8 + (size_t)n0 * img; a.u8_nhwc = net->in_u8_nhwc; memcpy(a.lut, net->in_lut, sizeof a.lut); }
             for (auto& F : o.forms) {
                 if (F.kind == FORM_I8) { if (F.n == 0) { a.out8 = (int8_t*)fp(F); a.Cs8 = o.Cs; if (!F.sgn) a.xor8 = 0x80808080u; } }
                 else if (F.kind == FORM_I32) { a.out32 = (int32_t*)fp(F); a.Cs32 = o.Cs; }
@@ -2252,98 +2537,29 @@ static int run_step(f8_net* net, const Step& st, const int32_t* input, void* out
             break;
         }
         case S_CONV: {
-            const Tensor& sT = T[st.src_t]; const Form& sF = sT.forms[st.src_f];
-            const Tensor& oT = T[nd.out];
-            const f8_conv_desc& d = nd.cd;
-            ConvArgs a{};
-            a.x = (const int8_t*)fp(sF); a.x_bytes = (uint32_t)(sF.bytes_per_img * N);
-            a.w = (const int8_t*)(net->d_w + nd.w_off); a.w_bytes = (uint32_t)((size_t)nd.coutP * nd.ktot);
-            a.bias = (const int32_t*)(net->d_w + nd.b_off);
-            a.PQ = oT.H * oT.W; a.Q = oT.W; a.M = N * a.PQ;
-            make_magic((uint32_t)a.PQ, &a.mPQ, &a.s1PQ, &a.s2PQ);
-            make_magic((uint32_t)a.Q, &a.mQ, &a.s1Q, &a.s2Q);
-            a.stride = d.stride; a.kh = d.kernel; a.CK = nd.ck; a.ktot = nd.ktot; a.coutP = nd.coutP;
-            a.ncc = nd.ncc;
-            if (nd.ncc > 0) { a.rowcls = (const uint8_t*)(net->d_w + nd.rc_off); a.colcls = (const uint8_t*)(net->d_w + nd.cc_off); }
-            if (nd.stem) {
-                a.sN = (int)sF.bytes_per_img; a.sP = d.stride * sF.Wp * 4; a.sQ = d.stride * 4;
-                a.origin = 0; a.H = sF.Hp; a.W = sF.Wp; a.pad = 0; a.kw = 1;
-                a.tapH = sF.Wp * 4; a.tapW = 0;
-            } else {
-                a.sN = sT.H * sT.W * sT.Cs; a.sP = d.stride * sT.W * sT.Cs; a.sQ = d.stride * sT.Cs;
-                a.origin = -(d.pad * sT.W + d.pad) * sT.Cs; a.H = sT.H; a.W = sT.W; a.pad = d.pad; a.kw = d.kernel;
-                a.tapH = sT.W * sT.Cs; a.tapW = sT.Cs;
-            }
-            a.relu0 = st.relu0; a.deep_nk = net->opt.deep_nk; a.no_fast = net->opt.wstat_fast ? 0 : 1;
-            if (st.res_t >= 0) { a.res = (const int32_t*)fp(T[st.res_t].forms[st.res_f]); a.acc_shl = st.acc_shl; a.res_shl = st.res_shl; a.relu1 = st.relu1; }
-            if (nd.dual >= 0) {
-                const Node& g = net->nodes[nd.dual];
-                const Tensor& s2 = T[st.src2_t]; const Form& F2 = s2.forms[st.src2_f];
-                a.x2 = (const int8_t*)fp(F2); a.x2_bytes = (uint32_t)(F2.bytes_per_img * N);
-                a.w2 = (const int8_t*)(net->d_w + g.w_off); a.w2_bytes = (uint32_t)((size_t)g.coutP * g.ktot);
-                a.bias2 = (const int32_t*)(net->d_w + g.b_off);
-                a.sN2 = s2.H * s2.W * s2.Cs; a.sP2 = g.cd.stride * s2.W * s2.Cs; a.sQ2 = g.cd.stride * s2.Cs; a.ktot2 = g.ktot;
-                a.acc_shl = st.acc_shl; a.res_shl = st.res_shl; a.relu1 = st.relu1;
-            }
+            const Form& sF = T[st.src_t].forms[st.src_f];
+            ConvArgs a = std::get<ConvArgs>(st.args);
+            a.x = (const int8_t*)fp(sF); a.x_bytes = (uint32_t)(sF.bytes_per_img * N); a.M = N * a.PQ;
+            if (st.res_t >= 0) a.res = (const int32_t*)fp(T[st.res_t].forms[st.res_f]);
+            if (nd.dual >= 0) { const Form& F2 = T[st.src2_t].forms[st.src2_f]; a.x2 = (const int8_t*)fp(F2); a.x2_bytes = (uint32_t)(F2.bytes_per_img * N); }
             fill_out(&a.out32, a.q);
             if (st.dense) {
-                a.w = (const int8_t*)(net->d_w + nd.wf_off);
-                e = launch_fc_dense(a, (char*)output + (size_t)n0 * oT.C * 4, oT.C, net->out_float, net->d_chain ? (const uint32_t*)(net->d_chain + (size_t)part * net->chain_stride + kChainErrWord * 4) : nullptr, net->epoch, s);
-            } else if (nd.pool >= 0) { a.w = (const int8_t*)(net->d_w + nd.wf_off); e = launch_conv1x1_pool(a, s); }
-            else if (nd.s2w) { a.w = (const int8_t*)(net->d_w + nd.wf_off); e = launch_conv3x3s2_wreg(a, s); }
-            else if (nd.wstat) {
-                a.w = (const int8_t*)(net->d_w + nd.wf_off);
-                if (nd.dual >= 0) a.w2 = (const int8_t*)(net->d_w + net->nodes[nd.dual].wf_off);
-                e = launch_conv1x1_wstat(a, net->num_cu, s);
-            } else if (nd.wreg) { a.w = (const int8_t*)(net->d_w + nd.wf_off); e = launch_conv1x1_wreg(a, s); }
-            else e = nd.p3_R > 0 ? launch_conv3x3_patch(a, d.cin, s) : launch_conv(a, nd.tile, s);
+                const int C = T[nd.out].C;
+                e = launch_fc_dense(a, (char*)output + (size_t)n0 * C * 4, C, net->out_float, chain_err, net->epoch, s);
+            } else if (nd.pool >= 0) e = launch_conv1x1_pool(a, s);
+            else if (nd.s2w) e = launch_conv3x3s2_wreg(a, s);
+            else if (nd.wstat) e = launch_conv1x1_wstat(a, net->num_cu, s);
+            else if (nd.wreg) e = launch_conv1x1_wreg(a, s);
+            else e = nd.p3_R > 0 ? launch_conv3x3_patch(a, nd.cd.cin, s) : launch_conv(a, nd.tile, s);
             break;
         }
-        case S_HEAD2: {
-            const Node& hh = net->nodes[nd.h2_head]; const Node& hb = net->nodes[nd.h2_dw];
+        case S_HEAD2: case S_STEMPOOL: {
             const Tensor& sT = T[st.src_t]; const Form& sF = sT.forms[st.src_f];
-            const Tensor& oT = T[nd.out];
-            StemPoolArgs a{};
-            a.h2 = 1;
-            a.x = (const int8_t*)fp(sF); a.x_bytes = (uint32_t)(sF.bytes_per_img * N);
-            a.w = (const int8_t*)(net->d_w + hh.w_off); a.w_bytes = (uint32_t)((size_t)hh.coutP * hh.ktot);
-            a.bias = (const int32_t*)(net->d_w + hh.b_off);
-            a.wd = (const int8_t*)(net->d_w + hb.w_off); a.bd = (const int32_t*)(net->d_w + hb.cc_off);
-            a.w1 = (const int8_t*)(net->d_w + nd.w_off); a.b1 = (const int32_t*)(net->d_w + nd.b_off);
-            { int v = 0; consumer_format(T[hb.a], hb.cd, &v, "run"); a.na = v; consumer_format(T[nd.a], nd.cd, &v, "run"); a.nb = v; }
-            a.N = N; a.Hp = sF.Hp; a.Wp = sF.Wp; a.org = sF.pad - hh.cd.pad;
-            a.Pc = oT.H; a.Qc = oT.W; a.P = oT.H; a.Q = oT.W;
-            a.relu0 = 1; a.grid_div = net->opt.stem_grid_div;
-            a.acc_ok = conv_acc_bounded(hh) && conv_acc_bounded(hb) && conv_acc_bounded(nd); a.rq_int = !net->opt.requant_float || !a.acc_ok;
-            a.rC = sT.C; a.rH = sT.H; a.rW = sT.W; a.xor8 = sF.sgn ? 0u : 0x80808080u;
-            a.raw_kind = -1;
-            if (st.raw_input && !(net->in_u8 && net->in_u8_nhwc)) {
-                const size_t img = (size_t)sT.C * sT.H * sT.W;
-                if (net->in_u8) { a.raw_kind = 2; a.xu8 = net->in_u8 + (size_t)n0 * img; memcpy(a.lut, net->in_lut, sizeof a.lut); }
-                else if (net->in_f32) { a.raw_kind = 1; a.xf = net->in_f32 + (size_t)n0 * img; a.scale = net->in_scale; a.qlo = net->in_lo; a.qhi = net->in_hi; }
-                else {
-                    a.raw_kind = 0; a.xi = input + (size_t)n0 * img;
-                    if (net->opt.check_input_range) { a.err = net->d_err; a.chk_lo = sF.sgn ? -127 : 0; a.chk_hi = sF.sgn ? 127 : 255; }
-                }
-            }
-            fill_out(&a.out32, a.q);
-            e = launch_stem_pool(a, s);
-            break;
-        }
-        case S_STEMPOOL: {
-            const Node& pl = net->nodes[nd.sp_pool];
-            const Tensor& sT = T[st.src_t]; const Form& sF = sT.forms[st.src_f];
-            const Tensor& cT = T[nd.out]; const Tensor& oT = T[pl.out];
-            StemPoolArgs a{};
-            a.x = (const int8_t*)fp(sF); a.x_bytes = (uint32_t)(sF.bytes_per_img * N);
-            a.w = (const int8_t*)(net->d_w + nd.w_off); a.w_bytes = (uint32_t)((size_t)nd.coutP * nd.ktot);
-            a.bias = (const int32_t*)(net->d_w + nd.b_off);
-            a.N = N; a.Hp = sF.Hp; a.Wp = sF.Wp; a.org = sF.pad - nd.cd.pad;
-            a.Pc = cT.H; a.Qc = cT.W; a.P = oT.H; a.Q = oT.W;
-            a.relu0 = st.relu0; a.wpc = net->opt.stem_wpc; a.rows = net->opt.stem_rows; a.grid_div = net->opt.stem_grid_div;
-            a.acc_ok = conv_acc_bounded(nd); a.rq_int = !net->opt.requant_float;
-            a.raw_kind = -1;
-            if (st.raw_input && !(net->in_u8 && net->in_u8_nhwc)) {
+            StemPoolArgs a = std::get<StemPoolArgs>(st.args);
+            a.x = (const int8_t*)fp(sF); a.x_bytes = (uint32_t)(sF.bytes_per_img * N); a.N = N;
+            if (st.kind == S_STEMPOOL) a.wpc = net->opt.stem_wpc;
+            a.grid_div = net->opt.stem_grid_div;
+            if (st.raw_input && !(net->in_u8 && net->in_u8_nhwc)) {      // the raw network input, read by this launch (the input step launches nothing)
                 const size_t img = (size_t)sT.C * sT.H * sT.W;
                 a.rC = sT.C; a.rH = sT.H; a.rW = sT.W; a.xor8 = sF.sgn ? 0u : 0x80808080u;
                 if (net->in_u8) { a.raw_kind = 2; a.xu8 = net->in_u8 + (size_t)n0 * img; memcpy(a.lut, net->in_lut, sizeof a.lut); }
@@ -2357,290 +2573,84 @@ static int run_step(f8_net* net, const Step& st, const int32_t* input, void* out
             e = launch_stem_pool(a, s);
             break;
         }
-        case S_FUSED: {
-            if (nd.fbd_a >= 0) {      // stage-opening block: nd = shortcut conv, nd.dual = body.4
-                const Node& na = net->nodes[nd.fbd_a]; const Node& nb = net->nodes[nd.fbd_b]; const Node& ng = net->nodes[nd.dual];
-                const Tensor& x = T[st.src_t]; const Form& xF = x.forms[st.src_f];
-                FusedArgs a{};
-                a.x8 = (const int8_t*)fp(xF); a.x_bytes = (uint32_t)(xF.bytes_per_img * N);
-                a.w0 = (const int8_t*)(net->d_w + na.w_off); a.w0_bytes = (uint32_t)((size_t)na.coutP * na.ktot);
-                a.w2 = (const int8_t*)(net->d_w + nb.w_off); a.w2_bytes = (uint32_t)((size_t)nb.coutP * nb.ktot);
-                a.w4 = (const int8_t*)(net->d_w + ng.w_off); a.w4_bytes = (uint32_t)((size_t)ng.coutP * ng.ktot);
-                a.wsc = (const int8_t*)(net->d_w + nd.w_off); a.wsc_bytes = (uint32_t)((size_t)nd.coutP * nd.ktot);
-                a.b0 = (const int32_t*)(net->d_w + na.b_off); a.b2 = (const int32_t*)(net->d_w + nb.b_off);
-                a.b4 = (const int32_t*)(net->d_w + ng.b_off); a.bsc = (const int32_t*)(net->d_w + nd.b_off);
-                a.N = N; a.H = x.H; a.W = x.W; a.C = na.cd.cin; a.MID = na.cd.cout; a.COUT = nd.cd.cout; a.R = nd.fb_R;
-                a.tiles_per_img = nd.fbd_s2 ? (x.H / 2) / nd.fb_R : (x.H + nd.fb_R - 1) / nd.fb_R;
-                a.stride2 = nd.fbd_s2 ? 1 : 0; a.stg = net->opt.opener_stg;
-                auto fmt = [&](const Node& cons, const Tensor& src, int32_t* n, int32_t* lo, int32_t* hi, uint32_t* x_or) {
-                    int nn = 0; consumer_format(src, cons.cd, &nn, "run");
-                    *n = nn; *lo = cons.cd.input_signed ? -127 : 0; *hi = cons.cd.input_signed ? 127 : 255;
-                    *x_or = cons.cd.input_signed ? 0u : 0x80808080u;
-                };
-                fmt(nb, T[nb.a], &a.n1, &a.lo1, &a.hi1, &a.xor1);
-                fmt(ng, T[ng.a], &a.n2, &a.lo2, &a.hi2, &a.xor2);
-                a.relu_a = na.cd.relu; a.relu_b = nb.cd.relu;
-                a.acc_shl = st.acc_shl; a.res_shl = st.res_shl; a.relu1 = st.relu1;
-                fill_out(&a.out32, a.q);
-                e = nd.fbd_s2 ? launch_fused_opener(a, s) : launch_fused_bottleneck(a, s);
-                break;
-            }
-            const Node& na = net->nodes[nd.fb_a]; const Node& nb = net->nodes[nd.fb_b];
-            const Tensor& x = T[st.src_t]; const Form& xF = x.forms[st.src_f];
-            FusedArgs a{};
-            a.x8 = (const int8_t*)fp(xF); a.x_bytes = (uint32_t)(xF.bytes_per_img * N);
-            a.xr = (const int32_t*)fp(T[st.res_t].forms[st.res_f]);
-            a.w0 = (const int8_t*)(net->d_w + na.w_off); a.w0_bytes = (uint32_t)((size_t)na.coutP * na.ktot);
-            a.w2 = (const int8_t*)(net->d_w + nb.w_off); a.w2_bytes = (uint32_t)((size_t)nb.coutP * nb.ktot);
-            a.w4 = (const int8_t*)(net->d_w + nd.w_off); a.w4_bytes = (uint32_t)((size_t)nd.coutP * nd.ktot);
-            a.b0 = (const int32_t*)(net->d_w + na.b_off); a.b2 = (const int32_t*)(net->d_w + nb.b_off); a.b4 = (const int32_t*)(net->d_w + nd.b_off);
-            a.N = N; a.H = x.H; a.W = x.W; a.C = na.cd.cin; a.MID = na.cd.cout; a.R = nd.fb_R;
-            a.tiles_per_img = (x.H + nd.fb_R - 1) / nd.fb_R;
-            auto fmt = [&](const Node& cons, const Tensor& src, int32_t* n, int32_t* lo, int32_t* hi, uint32_t* x_or) {
-                int nn = 0; consumer_format(src, cons.cd, &nn, "run");
-                *n = nn; *lo = cons.cd.input_signed ? -127 : 0; *hi = cons.cd.input_signed ? 127 : 255;
-                *x_or = cons.cd.input_signed ? 0u : 0x80808080u;
-            };
-            fmt(nb, T[nb.a], &a.n1, &a.lo1, &a.hi1, &a.xor1);
-            fmt(nd, T[nd.a], &a.n2, &a.lo2, &a.hi2, &a.xor2);
-            a.relu_a = na.cd.relu; a.relu_b = nb.cd.relu;
-            a.acc_shl = st.acc_shl; a.res_shl = st.res_shl; a.relu1 = st.relu1;
+        case S_FUSED: case S_P12: {
+            const Form& xF = T[st.src_t].forms[st.src_f];
+            FusedArgs a = std::get<FusedArgs>(st.args);
+            a.x8 = (const int8_t*)fp(xF); a.x_bytes = (uint32_t)(xF.bytes_per_img * N); a.N = N;
+            if (st.kind == S_FUSED && nd.fbd_a < 0) a.xr = (const int32_t*)fp(T[st.res_t].forms[st.res_f]);
             fill_out(&a.out32, a.q);
-            e = launch_fused_bottleneck(a, s);
+            if (st.kind == S_P12) e = nd.p12_s2 ? launch_fused_opener(a, s) : launch_fused_p12(a, s);
+            else e = (nd.fbd_a >= 0 && nd.fbd_s2) ? launch_fused_opener(a, s) : launch_fused_bottleneck(a, s);
             break;
         }
         case S_CHAIN: {
-            const std::vector<int>& ch = nd.chain;
-            ChainArgs a{};
-            a.nblk = (int)ch.size();
-            auto fmt = [&](const Node& cons, const Tensor& src, int32_t* n, int32_t* lo, int32_t* hi, uint32_t* x_or) {
-                int nn = 0; consumer_format(src, cons.cd, &nn, "run");
-                *n = nn; *lo = cons.cd.input_signed ? -127 : 0; *hi = cons.cd.input_signed ? 127 : 255;
-                *x_or = cons.cd.input_signed ? 0u : 0x80808080u;
-            };
-            for (int k = 0; k < a.nblk; ++k) {
-                const Node& hh = net->nodes[ch[k]];
-                ChainBlk& B = a.blk[k];
-                if (hh.tail) {                                  // only the join of a stride-2 opening block: shortcut (hh) + body.4 (its dual)
-                    const Node& g4 = net->nodes[hh.dual];
-                    B.w4 = (const int8_t*)(net->d_w + g4.wf_off); B.b4 = (const int32_t*)(net->d_w + g4.b_off);
-                    B.wsc = (const int8_t*)(net->d_w + hh.wf_off); B.bsc = (const int32_t*)(net->d_w + hh.b_off);
-                    B.nq = B.n1 = B.n2 = 1; B.hiq = B.hi1 = B.hi2 = 255; B.xorq = B.xor1 = B.xor2 = 0x80808080u;     // (unused: no body.0 / body.2 here)
-                    B.relu_a = B.relu_b = 1; B.relu1 = net->nodes[hh.fused_add].relu;
-                    a.acc_ok = 1; a.stream_ok = stream_bounded(net, net->nodes[hh.fused_add].out) ? 1 : 0; a.rq_int = !net->opt.requant_float;
-                    const int dfl = T[hh.out].fl - T[g4.out].fl;             // (shortcut << acc_shl) + (body.4 << res_shl)
-                    B.acc_shl = dfl < 0 ? -dfl : 0; B.res_shl = dfl > 0 ? dfl : 0;
-                    continue;
-                }
-                const bool hds = hh.fbd_a >= 0;
-                const Node& na = net->nodes[hds ? hh.fbd_a : hh.fb_a]; const Node& nb = net->nodes[hds ? hh.fbd_b : hh.fb_b];
-                const Node& ng = hds ? net->nodes[hh.dual] : hh;
-                B.w0 = (const int8_t*)(net->d_w + na.wf_off); B.w2 = (const int8_t*)(net->d_w + nb.wf_off); B.w4 = (const int8_t*)(net->d_w + ng.wf_off);
-                B.b0 = (const int32_t*)(net->d_w + na.b_off); B.b2 = (const int32_t*)(net->d_w + nb.b_off); B.b4 = (const int32_t*)(net->d_w + ng.b_off);
-                if (hds) { B.wsc = (const int8_t*)(net->d_w + hh.wf_off); B.bsc = (const int32_t*)(net->d_w + hh.b_off); }
-                const Tensor& xin = T[na.a];
-                fmt(na, xin, &B.nq, &B.loq, &B.hiq, &B.xorq);
-                fmt(nb, T[nb.a], &B.n1, &B.lo1, &B.hi1, &B.xor1);
-                fmt(ng, T[ng.a], &B.n2, &B.lo2, &B.hi2, &B.xor2);
-                B.relu_a = na.cd.relu; B.relu_b = nb.cd.relu; B.relu1 = net->nodes[hh.fused_add].relu;
-                if (k == 0) { a.acc_ok = 1; a.rq_int = !net->opt.requant_float; a.stream_ok = (hds || stream_bounded(net, na.a)) ? 1 : 0; }   // identity first block: the stream it reads
-                a.acc_ok = a.acc_ok && conv_acc_bounded(na) && conv_acc_bounded(nb);
-                a.stream_ok = a.stream_ok && stream_bounded(net, net->nodes[hh.fused_add].out);
-                // identity: (body.4 << acc_shl) + (block input << res_shl); opening block: (shortcut << acc_shl) + (body.4 << res_shl)
-                const int dfl = T[hh.out].fl - (hds ? T[ng.out].fl : xin.fl);
-                B.acc_shl = dfl < 0 ? -dfl : 0; B.res_shl = dfl > 0 ? dfl : 0;
-            }
-            const Node& hf = net->nodes[ch[0]];
-            const bool tail = hf.tail, ds = hf.fbd_a >= 0 || tail;
-            const Tensor& x = T[st.src_t]; const Form& xF = x.forms[st.src_f];
-            if (ds) a.x8in = (const int8_t*)fp(xF); else a.xr = (const int32_t*)fp(xF);
-            if (tail) { a.tail = 1; a.m2in = (const int8_t*)fp(T[st.src2_t].forms[st.src2_f]); }
-            const Node& a0 = tail ? net->nodes[hf.dual] : net->nodes[ds ? hf.fbd_a : hf.fb_a];
-            const Tensor& oT = T[net->nodes[nd.fused_add].out];      // the stage's output map (st.out.t: the pooled tensor when the pool runs in the launch)
-            const int C = oT.C, MID = tail ? a0.cd.cin : a0.cd.cout;
-            a.pool = nd.pool >= 0 ? 1 : 0;
-            int wg_per_cu = 1;
-            chain_shape(C, MID, oT.H, oT.W, tail ? hf.cd.cin : a0.cd.cin, tail, &a.R, &wg_per_cu);
-            const int tiles = (oT.H + a.R - 1) / a.R;
-            const int slots = (net->num_cu > 0 ? std::min(net->num_cu, 256) : 256) * wg_per_cu;
-            // every workgroup of a chain launch must be resident: a device with fewer slots than one image has tiles cannot run it
-            if (slots < tiles)
-                return fail(F8_ERR_STATE, "f8_net_run: a stage-chain launch needs %d co-resident workgroups per image, the device has %d compute units (plan with fuse_chain = 0 / fuse_bchain = 0)", tiles, net->num_cu);
-            a.N = N; a.NG = chain_groups(N, slots / tiles);
-            if ((!ds || tail) && cchain_supported(C, MID, oT.H, oT.W, tail ? hf.cd.cin : a0.cd.cin, tail)) {      // the 7x7 stage: clusters of eight workgroups, four images per cluster and round
-                a.NG = cchain_clusters(N, slots);
-                if (a.NG < 1) return fail(F8_ERR_STATE, "f8_net_run: the 7x7 stage-chain launch needs 8 co-resident workgroups, the device has %d compute units (plan with fuse_chain7 = 0)", net->num_cu);
-            }
+            ChainArgs a = std::get<ChainArgs>(st.args);
+            const Form& xF = T[st.src_t].forms[st.src_f];
+            if (a.tail || net->nodes[nd.chain[0]].fbd_a >= 0) a.x8in = (const int8_t*)fp(xF); else a.xr = (const int32_t*)fp(xF);
+            if (a.tail) a.m2in = (const int8_t*)fp(T[st.src2_t].forms[st.src2_f]);
+            a.N = N;
+            if ((a.NG = chain_launch_groups(net, st, N)) < 1) return F8_ERR_STATE;
             fill_out(&a.out32, a.q);
-            if (!net->d_chain) return fail(F8_ERR_STATE, "f8_net_run: chain scratch missing");
-            a.sync = (uint32_t*)(net->d_chain + (size_t)part * net->chain_stride);
-            a.err = a.sync + kChainErrWord; a.err_host = net->h_err_dev; a.epoch = net->epoch;
-            a.xchg = (int8_t*)(net->d_chain + (size_t)part * net->chain_stride + 4096);
-            a.timeout_ticks = (uint32_t)std::min<long long>((long long)net->opt.chain_timeout_ms * 100000ll, 0x7fffffffll);
-            char kb[160] = "";
-            e = launch_chain(a, C, MID, oT.H, oT.W, tail ? hf.cd.cin : a0.cd.cin, s, kb, sizeof kb);
-            if (kb[0] && st.kernel != kb) st.kernel = kb;
+            if (const int rc = chain_scratch(a)) return rc;
+            e = launch_chain(a, st.fast, st.C, st.MID, st.H, st.W, st.cin0, s);
             break;
         }
         case S_BCHAIN: {
-            const std::vector<int>& ch = nd.bchain;
-            BChainArgs a{};
-            a.nblk = (int)ch.size();
-            auto fmt = [&](const Node& cons, const Tensor& src, int32_t* n, int32_t* lo, int32_t* hi, uint32_t* x_or) {
-                int nn = 0; consumer_format(src, cons.cd, &nn, "run");
-                *n = nn; *lo = cons.cd.input_signed ? -127 : 0; *hi = cons.cd.input_signed ? 127 : 255;
-                *x_or = cons.cd.input_signed ? 0u : 0x80808080u;
-            };
-            const bool ds = net->nodes[ch[0]].bds_a >= 0;
-            for (int k = 0; k < a.nblk; ++k) {
-                const Node& hk = net->nodes[ch[k]];
-                const bool hds = hk.bds_a >= 0;                 // opening block: hk = its shortcut conv
-                const Node& c2 = hds ? net->nodes[hk.bds_b] : hk; const Node& c1 = net->nodes[hds ? hk.bds_a : hk.bb_a];
-                BChainBlk& B = a.blk[k];
-                B.wa = (const int8_t*)(net->d_w + c1.wf_off); B.wb = (const int8_t*)(net->d_w + c2.wf_off);
-                B.ba = (const int32_t*)(net->d_w + c1.b_off); B.bb = (const int32_t*)(net->d_w + c2.b_off);
-                const Tensor& xin = T[c1.a];
-                fmt(c1, xin, &B.nq, &B.loq, &B.hiq, &B.xorq);
-                fmt(c2, T[c2.a], &B.n1, &B.lo1, &B.hi1, &B.xor1);
-                B.relu_a = c1.cd.relu; B.relu1 = net->nodes[hk.fused_add].relu;
-                if (k == 0) { a.acc_ok = 1; a.rq_int = !net->opt.requant_float; a.stream_ok = (hds || stream_bounded(net, c1.a)) ? 1 : 0; }   // identity first block: the stream it reads
-                a.acc_ok = a.acc_ok && conv_acc_bounded(c1);
-                a.stream_ok = a.stream_ok && stream_bounded(net, net->nodes[hk.fused_add].out);
-                // identity: (second conv << acc_shl) + (block input << res_shl); opening block: (second conv << acc_shl) + (shortcut << res_shl)
-                const int dfl = T[c2.out].fl - (hds ? T[hk.out].fl : xin.fl);
-                B.acc_shl = dfl < 0 ? -dfl : 0; B.res_shl = dfl > 0 ? dfl : 0;
-                if (hds) { a.wsc = (const int8_t*)(net->d_w + hk.wf_off); a.bsc = (const int32_t*)(net->d_w + hk.b_off); }
-            }
+            BChainArgs a = std::get<BChainArgs>(st.args);
             const Tensor& xs = T[st.src_t];
-            if (ds) { a.x8in = (const int8_t*)fp(xs.forms[st.src_f]); a.x8sc = (const int8_t*)fp(xs.forms[st.res_f]); }
+            if (net->nodes[nd.bchain[0]].bds_a >= 0) { a.x8in = (const int8_t*)fp(xs.forms[st.src_f]); a.x8sc = (const int8_t*)fp(xs.forms[st.res_f]); }
             else a.xr = (const int32_t*)fp(xs.forms[st.src_f]);
-            const Tensor& x = T[st.out.t];
-            const int tiles = bchain_tiles_per_img(x.C, x.H, x.W);
-            // every workgroup of a chain launch must be resident (one per CU): a device with fewer CUs than one image has tiles cannot run it
-            if ((net->num_cu > 0 ? std::min(net->num_cu, 256) : 256) < tiles)
-                return fail(F8_ERR_STATE, "f8_net_run: a stage-chain launch needs %d co-resident workgroups per image, the device has %d compute units (plan with fuse_chain = 0 / fuse_bchain = 0)", tiles, net->num_cu);
-            a.N = N; a.NG = chain_groups(N, (net->num_cu > 0 ? std::min(net->num_cu, 256) : 256) / tiles);
+            a.N = N;
+            if ((a.NG = chain_launch_groups(net, st, N)) < 1) return F8_ERR_STATE;
             fill_out(&a.out32, a.q);
-            if (!net->d_chain) return fail(F8_ERR_STATE, "f8_net_run: chain scratch missing");
-            a.sync = (uint32_t*)(net->d_chain + (size_t)part * net->chain_stride);
-            a.err = a.sync + kChainErrWord; a.err_host = net->h_err_dev; a.epoch = net->epoch;
-            a.xchg = (int8_t*)(net->d_chain + (size_t)part * net->chain_stride + 4096);
-            a.timeout_ticks = (uint32_t)std::min<long long>((long long)net->opt.chain_timeout_ms * 100000ll, 0x7fffffffll);
-            char kb[160] = "";
-            e = launch_bchain(a, x.C, x.H, x.W, s, kb, sizeof kb);
-            if (kb[0] && st.kernel != kb) st.kernel = kb;
-            break;
-        }
-        case S_P12: {
-            const Node& na = net->nodes[nd.p12_a];
-            const Tensor& x = T[st.src_t]; const Form& xF = x.forms[st.src_f];
-            if (nd.p12_s2) {                                    // body.0 + body.2 of a stride-2 opening block on f8_opener.hip (P12); q[0] = mid2
-                FusedArgs a{};
-                a.x8 = (const int8_t*)fp(xF); a.x_bytes = (uint32_t)(xF.bytes_per_img * N);
-                a.w0 = (const int8_t*)(net->d_w + na.w_off); a.w0_bytes = (uint32_t)((size_t)na.coutP * na.ktot);
-                a.w2 = (const int8_t*)(net->d_w + nd.w_off); a.w2_bytes = (uint32_t)((size_t)nd.coutP * nd.ktot);
-                a.b0 = (const int32_t*)(net->d_w + na.b_off); a.b2 = (const int32_t*)(net->d_w + nd.b_off);
-                a.N = N; a.H = x.H; a.W = x.W; a.C = na.cd.cin; a.MID = na.cd.cout; a.COUT = 4 * na.cd.cout; a.R = nd.fb_R;
-                a.tiles_per_img = (x.H / 2 + nd.fb_R - 1) / nd.fb_R;
-                { int nn = 0; consumer_format(T[nd.a], nd.cd, &nn, "run"); a.n1 = nn; a.lo1 = nd.cd.input_signed ? -127 : 0; a.hi1 = nd.cd.input_signed ? 127 : 255;
-                  a.xor1 = nd.cd.input_signed ? 0u : 0x80808080u; }
-                a.relu_a = na.cd.relu; a.relu_b = nd.cd.relu;
-                fill_out(&a.out32, a.q);
-                a.n2 = a.q[0].n; a.lo2 = a.q[0].lo; a.hi2 = a.q[0].hi; a.xor2 = a.q[0].bias_xor;      // mid2's one form = body.4's input format
-                a.stride2 = 1; a.p12only = 1; a.acc_ok = conv_acc_bounded(na) && conv_acc_bounded(nd); a.rq_int = !net->opt.requant_float;
-                e = launch_fused_opener(a, s);
-                break;
-            }
-            FusedArgs a{};
-            a.x8 = (const int8_t*)fp(xF); a.x_bytes = (uint32_t)(xF.bytes_per_img * N);
-            a.w0 = (const int8_t*)(net->d_w + na.wf_off); a.w0_bytes = (uint32_t)((size_t)na.coutP * na.ktot);     // fragment order
-            a.w2 = (const int8_t*)(net->d_w + nd.wf_off); a.w2_bytes = (uint32_t)((size_t)nd.coutP * nd.ktot);
-            a.b0 = (const int32_t*)(net->d_w + na.b_off); a.b2 = (const int32_t*)(net->d_w + nd.b_off);
-            a.N = N; a.H = x.H; a.W = x.W; a.C = na.cd.cin; a.MID = na.cd.cout;
-            { int nn = 0; consumer_format(T[nd.a], nd.cd, &nn, "run"); a.n1 = nn; a.lo1 = nd.cd.input_signed ? -127 : 0; a.hi1 = nd.cd.input_signed ? 127 : 255;
-              a.xor1 = nd.cd.input_signed ? 0u : 0x80808080u; }
-            a.relu_a = na.cd.relu; a.relu_b = nd.cd.relu;
-            fill_out(&a.out32, a.q);
-            e = launch_fused_p12(a, s);
+            if (const int rc = chain_scratch(a)) return rc;
+            e = launch_bchain(a, st.fast, st.C, st.H, st.W, s);
             break;
         }
         case S_IR: {
-            const Node& na = net->nodes[nd.ir_a]; const Node& nb = net->nodes[nd.ir_b];
-            const Tensor& x = T[st.src_t]; const Form& xF = x.forms[st.src_f];
-            const Tensor& oT = T[nd.out];
-            IRArgs a{};
-            a.x8 = (const int8_t*)fp(xF);
+            const Tensor& x = T[st.src_t];
+            IRArgs a = std::get<IRArgs>(st.args);
+            a.x8 = (const int8_t*)fp(x.forms[st.src_f]); a.N = N;
             if (st.res_t >= 0) a.xr = (const int32_t*)fp(T[st.res_t].forms[st.res_f]);
-            a.w0 = (const int8_t*)(net->d_w + na.w_off); a.b0 = (const int32_t*)(net->d_w + na.b_off);
-            a.wd4 = (const int8_t*)(net->d_w + nb.rc_off); a.bd4 = (const int32_t*)(net->d_w + nb.cc_off);
-            a.w4 = (const int8_t*)(net->d_w + nd.w_off); a.b4 = (const int32_t*)(net->d_w + nd.b_off);
-            a.N = N; a.H = x.H; a.W = x.W; a.Ho = oT.H; a.Wo = oT.W; a.stride = nb.cd.stride; a.R = nd.ir_R; a.G = nd.ir_G;
-            a.tiles_per_img = oT.H / nd.ir_R; a.E32 = na.coutP;
-            auto fmt = [&](const Node& cons, const Tensor& src, int32_t* n, int32_t* lo, int32_t* hi, uint32_t* x_or) {
-                int nn = 0; consumer_format(src, cons.cd, &nn, "run");
-                *n = nn; *lo = cons.cd.input_signed ? -127 : 0; *hi = cons.cd.input_signed ? 127 : 255;
-                *x_or = cons.cd.input_signed ? 0u : 0x80808080u;
-            };
-            fmt(nb, T[nb.a], &a.n1, &a.lo1, &a.hi1, &a.xor1);
-            fmt(nd, T[nd.a], &a.n2, &a.lo2, &a.hi2, &a.xor2);
-            a.relu_a = na.cd.relu; a.relu_b = nb.cd.relu; a.relu0 = st.relu0;
-            a.acc_ok = conv_acc_bounded(na) && conv_acc_bounded(nb); a.rq_int = !net->opt.requant_float;
-            a.acc_shl = st.acc_shl; a.res_shl = st.res_shl; a.relu1 = st.relu1;
-            make_magic((uint32_t)x.W, &a.mW, &a.s1W, &a.s2W);
-            make_magic((uint32_t)(x.H * x.W), &a.mHW, &a.s1HW, &a.s2HW);
-            make_magic((uint32_t)oT.W, &a.mWo, &a.s1Wo, &a.s2Wo);
-            make_magic((uint32_t)(nd.ir_R * oT.W), &a.mRWo, &a.s1RWo, &a.s2RWo);
             fill_out(&a.out32, a.q);
             e = launch_fused_ir(a, x.Cs, nd.coutP, s);
             break;
         }
         case S_DW: {
-            const Tensor& sT = T[st.src_t]; const Form& sF = sT.forms[st.src_f];
-            const Tensor& oT = T[nd.out];
-            DwArgs a{};
-            a.x = (const int8_t*)fp(sF); a.w = (const int8_t*)(net->d_w + nd.w_off); a.bias = (const int32_t*)(net->d_w + nd.b_off);
-            a.w4 = (const int8_t*)(net->d_w + nd.rc_off); a.bias4 = (const int32_t*)(net->d_w + nd.cc_off);
-            a.N = N; a.H = sT.H; a.W = sT.W; a.P = oT.H; a.Q = oT.W; a.Cs = sT.Cs; a.stride = nd.cd.stride; a.pad = nd.cd.pad;
-            a.in_signed = nd.cd.input_signed; a.relu0 = st.relu0; a.use_dot4 = net->opt.dw_dot4; a.use_mma = net->opt.dw_mma; a.acc_ok = conv_acc_bounded(nd); a.rq_int = !net->opt.requant_float;
+            DwArgs a = std::get<DwArgs>(st.args);
+            a.x = (const int8_t*)fp(T[st.src_t].forms[st.src_f]); a.N = N;
             fill_out(&a.out32, a.q);
             e = launch_dwconv(a, s);
             break;
         }
         case S_ADD: case S_REQUANT: {
             const Tensor& sT = T[st.src_t];
-            AddArgs a{};
+            AddArgs a = std::get<AddArgs>(st.args);
             a.a = (const int32_t*)fp(sT.forms[st.src_f]);
-            a.b = st.kind == S_ADD ? (const int32_t*)fp(T[st.res_t].forms[st.res_f]) : nullptr;
-            a.M = N * sT.H * sT.W; a.Cs = sT.Cs; a.a_shl = st.acc_shl; a.b_shl = st.res_shl; a.relu = st.relu1;
+            if (st.kind == S_ADD) a.b = (const int32_t*)fp(T[st.res_t].forms[st.res_f]);
+            a.M = N * sT.H * sT.W;
             fill_out(&a.out32, a.q);
             e = launch_add(a, s);
             break;
         }
         case S_MAXPOOL: {
-            const Tensor& sT = T[st.src_t]; const Form& sF = sT.forms[st.src_f];
-            const Tensor& oT = T[nd.out];
-            PoolArgs a{};
-            a.x = fp(sF); a.in_is_i8 = sF.kind == FORM_I8; a.in_signed = sF.sgn;
-            if (a.in_is_i8) { a.q[0].bias_xor = 0; }
-            a.N = N; a.H = sT.H; a.W = sT.W; a.P = oT.H; a.Q = oT.W; a.Cs = sT.Cs; a.k = nd.pk; a.stride = nd.pstride; a.pad = nd.ppad;
+            PoolArgs a = std::get<PoolArgs>(st.args);
+            a.x = fp(T[st.src_t].forms[st.src_f]); a.N = N;
             fill_out(&a.out32, a.q);
             e = launch_maxpool(a, s);
             break;
         }
         case S_AVGPOOL: {
-            const Tensor& sT = T[st.src_t];
-            AvgArgs a{};
-            a.x = (const int32_t*)fp(sT.forms[st.src_f]); a.N = N; a.HW = sT.H * sT.W; a.Cs = sT.Cs;
+            AvgArgs a = std::get<AvgArgs>(st.args);
+            a.x = (const int32_t*)fp(T[st.src_t].forms[st.src_f]); a.N = N;
             fill_out(&a.out32, a.q);
             e = launch_avgpool(a, s);
             break;
         }
         case S_OUTPUT: {
-            const Tensor& sT = T[st.src_t];
-            OutArgs a{};
-            a.x = (const int32_t*)fp(sT.forms[st.src_f]); a.N = N; a.C = sT.C; a.HW = sT.H * sT.W; a.Cs = sT.Cs;
-            a.out = (char*)output + (size_t)n0 * sT.C * sT.H * sT.W * 4; a.as_float = net->out_float;
-            a.err = net->d_chain ? (const uint32_t*)(net->d_chain + (size_t)part * net->chain_stride + kChainErrWord * 4) : nullptr; a.epoch = net->epoch;
+            OutArgs a = std::get<OutArgs>(st.args);
+            a.x = (const int32_t*)fp(T[st.src_t].forms[st.src_f]); a.N = N;
+            a.out = (char*)output + (size_t)n0 * a.C * a.HW * 4; a.err = chain_err; a.epoch = net->epoch;
             e = launch_output(a, s);
             break;
         }
@@ -2679,11 +2689,11 @@ int f8_net_autotune(f8_net* net, int N, void* stream) {
             if (nd.dual >= 0 && !(t.bn == 64 || (t.bn == 128 && t.bm == 128))) continue;     // dual-GEMM instances
             if (t.bm == 64 && t.bn == 32) continue;
             nd.tile = t;
-            if (run_step(net, st, nullptr, nullptr, 0, n_launch, 0, s) != F8_OK) { (void)hipGetLastError(); continue; }   // no instance
+            if (run_step(net, st, nullptr, nullptr, 0, n_launch, 0, 0, s) != F8_OK) { (void)hipGetLastError(); continue; }   // no instance
             float ms_min = 1e30f;
             for (int rep = 0; rep < 3; ++rep) {
                 (void)hipEventRecord(e0, s);
-                for (int k = 0; k < 4; ++k) (void)run_step(net, st, nullptr, nullptr, 0, n_launch, 0, s);
+                for (int k = 0; k < 4; ++k) (void)run_step(net, st, nullptr, nullptr, 0, n_launch, 0, 0, s);
                 (void)hipEventRecord(e1, s);
                 if (hipEventSynchronize(e1) != hipSuccess) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); return fail(F8_ERR_HIP, "f8_net_autotune: sync"); }
                 float ms = 0.f; (void)hipEventElapsedTime(&ms, e0, e1);
@@ -2784,13 +2794,8 @@ static int for_each_launch(const f8_net* net, int N, F&& f) {
     return F8_OK;
 }
 // all launches of one run for images [n0, n0 + N) of the network input, on stream s, in arena copy `part`
-static int run_steps(f8_net* net, const int32_t* input, void* output, int n0, int N, int part, hipStream_t s) {
-    const int rc = for_each_launch(net, N, [&](int k, int c0, int cn) {
-        net->chunk_off = c0;
-        return run_step(net, net->steps[k], input, output, n0, cn, part, s);
-    });
-    net->chunk_off = 0;
-    return rc;
+static int run_steps(const f8_net* net, const int32_t* input, void* output, int n0, int N, int part, hipStream_t s) {
+    return for_each_launch(net, N, [&](int k, int c0, int cn) { return run_step(net, net->steps[k], input, output, n0, cn, c0, part, s); });
 }
 
 static int run_common(f8_net* net, const int32_t* input, void* output, int N, void* stream, float* ms, int cap) {
@@ -2844,12 +2849,10 @@ static int run_common(f8_net* net, const int32_t* input, void* output, int N, vo
         for (int p = 0; p < parts; ++p) {
             (void)hipEventRecord(net->events[pos++], s);
             rc = for_each_launch(net, cut[p + 1] - cut[p], [&](int k, int c0, int cn) {
-                net->chunk_off = c0;
-                const int r = run_step(net, net->steps[k], input, output, cut[p], cn, p, s);
+                const int r = run_step(net, net->steps[k], input, output, cut[p], cn, c0, p, s);
                 (void)hipEventRecord(net->events[pos++], s);
                 return r;
             });
-            net->chunk_off = 0;
             if (rc) return rc;
         }
         hipError_t e = hipStreamSynchronize(s);
@@ -3004,9 +3007,7 @@ static int run_common(f8_net* net, const int32_t* input, void* output, int N, vo
         for (int p = 0; p < parts; ++p) {
             if (t >= plan[p].size()) continue;
             const Launch& L = plan[p][t];
-            net->chunk_off = L.c0;
-            rc = run_step(net, net->steps[L.k], input, output, cut[p], L.cn, p, net->aux[p]);
-            net->chunk_off = 0;
+            rc = run_step(net, net->steps[L.k], input, output, cut[p], L.cn, L.c0, p, net->aux[p]);
             if (rc) {
                 if (capturing) { hipGraph_t g = nullptr; (void)hipStreamEndCapture(s, &g); if (g) (void)hipGraphDestroy(g); }
                 return rc;

@@ -288,6 +288,7 @@ int f8_net_launch_info(const f8_net* net, int i, int N, char* name, size_t name_
  * saturate-pack, 1/4 merge, 1/4 bias flip), 2 per joined int32 value (fix_resnet.py:40-54: align-add + clamp / ReLU), 1 per max-pooled value.
  * The profile tooling divides the counters' vector instructions x 64 lanes by it (profiles/rocprof_*_valu.md: issued / essential). */
 int f8_net_launch_valu(const f8_net* net, int i, int N, double* essential_lane_ops);
+/* The device symbol (as rocprofv3 prints it) launch i starts.  Final once f8_net_finalize returns; only f8_net_autotune can still change it. */
 int f8_net_launch_kernel(const f8_net* net, int i, char* buf, size_t cap);
 
 /* Attach a label (e.g. the state_dict key) to the node that produced tensor `t`. */

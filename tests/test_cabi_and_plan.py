@@ -329,6 +329,43 @@ def test_planner_bounds_the_residual_stream_before_it_plans_the_float_requantisa
     assert len(ks) == 3 and all(re.search(r', 1, (false|true), 8>$', k) for k in ks), ks       # stage 0 reads the max-pooled head output: bounded through the pool node
 
 
+def test_planned_chain_instance_is_the_one_the_launcher_runs():
+    """The chain instance (f8_chain.hip chain_fast) is chosen once, when f8_net_finalize binds the launch arguments, and launch_kernel names it.
+    A 14x14 chain of three identity blocks whose joins shift the residual left (block 0: body.4 at fraclen 12 against the stream's 9) has no
+    constant-format instance: the generic one (0) runs — the planner used to name 2 there.  With body.4 shifting left instead it is 2 (1 under
+    requant_float = 1, the stream being a conv's output: bounded).  Fraclens as tests/test_gpu_chain.py's 'res_shifts_left' / 'acc_shifts_left' stages."""
+    C, MID, HW = 1024, 256, 14
+
+    def kernel(variant, options):
+        net = F8Net()
+        for k, v in options.items():
+            net.set_option(k, v)
+        r = net.input(64, HW, HW, 8)
+        w = synth.rand_normal_int(10, 'stem', (C, 64, 1, 1), 30.0).clip(-127, 127).astype(np.int32)
+        r = net.conv(r, w, np.zeros(C, np.int32), stride=1, pad=0, groups=1, weight_fl=1, input_fl=8, input_signed=False, relu=True)   # a stream of fraclen 9 the planner bounds
+        for b in range(3):
+            if variant == 'acc_shifts_left':
+                fls = [(4, 7), (3, 6), (3, 5 + b % 2)]
+            else:
+                fls = [(4, 7), (4, 7), (min(5 + b, 7), 7)]
+            xin = r
+            for j, (cin, cout, k) in enumerate(((C, MID, 1), (MID, MID, 3), (MID, C, 1))):
+                w = synth.rand_normal_int(11, f'{variant}{b}{j}w', (cout, cin, k, k), 30.0).clip(-127, 127).astype(np.int32)
+                bias = synth.rand_normal_int(12, f'{variant}{b}{j}b', (cout,), 2.0 ** sum(fls[j])).astype(np.int32)
+                r = net.conv(r, w, bias, stride=1, pad=k // 2, groups=1, weight_fl=fls[j][1], input_fl=fls[j][0], input_signed=False,
+                             quant_input=True, relu=j < 2)
+            r = net.add(r, xin, relu=True)
+        net.output(r, as_float=False)
+        net.finalize(4)
+        assert 'stage_chain_x3:' in net.describe(), net.describe()
+        ks = [net.launch_kernel(i) for i in range(net.num_launches) if '::chain_kernel<' in net.launch_kernel(i)]
+        assert len(ks) == 1, ks
+        return re.search(r'<1024, 256, 14, 14, 4, 1024, \d+, \d+, (\d), ', ks[0]).group(1)
+
+    assert kernel('res_shifts_left', {}) == '0' and kernel('res_shifts_left', {'requant_float': 1}) == '0'
+    assert kernel('acc_shifts_left', {}) == '2' and kernel('acc_shifts_left', {'requant_float': 1}) == '1'
+
+
 def test_essential_vector_work_per_launch_follows_the_reference_semantics():
     """f8_net_launch_valu (VERDICT r5 #1b): 3 lane-operations per int8 value a launch produces (in HBM or only in LDS), 2 per joined int32 value, 1 per
     max-pooled conv value — checked by hand for the stage-0 chain and the head of ResNet-50 and as a whole-net total; scales with N."""

@@ -165,8 +165,10 @@ def _run_stage_chain(dev, cfg, variant, tail, options=None, big_bias=False):
     net.finalize(N)
     plan = net.describe()
     assert f'stage_chain_x{nblk}' in plan, plan
+    planned = [net.launch_kernel(i) for i in range(net.num_launches)]
     got = net.run(_t(x, dev)).cpu().numpy()
     net.check()
+    assert [net.launch_kernel(i) for i in range(net.num_launches)] == planned     # the planned symbols are the ones the run started
 
     w, fl = x, x_fl
     for b in blocks:
