@@ -167,23 +167,24 @@ __global__ void __launch_bounds__(256, S == 1 ? 4 : 3) dwconv3x3_mma_kernel(cons
     }
 }
 
-// int8 outputs only, pad 1, stride 1 / 2, whole 32-channel tiles, strips that fill their lanes: output width >= 28 (measured: 14-wide maps,
-// 14 of 32 lanes live, are 10 - 15 % SLOWER than the v_dot4 kernel: 17.7 -> 20.0 us; 112 / 56 / 28-wide ones 41 -> 26, 43 -> 27, 27 -> 19 us)
-bool dwconv_mma_supported(const DwArgs& a) {
-    return !a.out32 && a.w && a.bias4 && a.pad == 1 && (a.stride == 1 || a.stride == 2) && (a.Cs & 31) == 0 && (a.Q >= DW_SW || a.Q == 14) &&
-           (a.stride == 1 ? (a.P == a.H && a.Q == a.W) : (a.H == 2 * a.P && a.W == 2 * a.Q)) &&
-           (size_t)a.N * a.H * a.W * a.Cs < 0x7fffffffull;
-}
-
-hipError_t launch_dwconv_mma(const DwArgs& a0, hipStream_t s) {
-    DwArgs a = a0; a.bias = a0.bias4;                               // bias + 128 * sum(w) for unsigned inputs
+// The instance for N images: FQ | SUBS << 2, or -1 where there is none.  int8 outputs only, pad 1, stride 1 / 2, whole 32-channel tiles,
+// 32-bit element indices, strips that fill their lanes: output width >= 28 (measured: 14-wide maps, 14 of 32 lanes live, are 10 - 15 %
+// SLOWER than the v_dot4 kernel: 17.7 -> 20.0 us; 112 / 56 / 28-wide ones 41 -> 26, 43 -> 27, 27 -> 19 us), or the two-sub-row form at 14.
+int dwconv_mma_inst(const DwArgs& a, bool out32, int nq, int N) {
+    if (!(!out32 && a.pad == 1 && (a.stride == 1 || a.stride == 2) && (a.Cs & 31) == 0 && (a.Q >= DW_SW || a.Q == 14) &&
+          (a.stride == 1 ? (a.P == a.H && a.Q == a.W) : (a.H == 2 * a.P && a.W == 2 * a.Q)) && (size_t)N * a.H * a.W * a.Cs < 0x7fffffffull)) return -1;
     int fq = a.relu0 != 0 ? ((a.acc_ok != 0 && !a.rq_int) ? 1 : 2) : 0;      // 1: float converter; 2: integer form of the same requantisation
-    for (int k = 0; k < 2; ++k) {
-        if (!a.q[k].ptr) continue;
+    for (int k = 0; k < nq; ++k) {
         if (!(a.q[k].n > 0 && a.q[k].n <= 30 && a.q[k].lo == 0 && a.q[k].hi == 255 && a.q[k].bias_xor == 0x80808080u)) fq = 0;
         else if (fq == 1 && a.q[k].n > kRequantU8MaxShift) fq = 2;
     }
-    const int subs = a.Q >= DW_SW ? 1 : 2, vw = subs == 2 ? 14 : DW_SW;
+    return fq | (a.Q >= DW_SW ? 1 : 2) << 2;
+}
+
+hipError_t launch_dwconv_mma(const DwArgs& a0, int inst, hipStream_t s) {
+    if (a0.out32 || !a0.w || !a0.bias4) return hipErrorInvalidValue;
+    DwArgs a = a0; a.bias = a0.bias4;                               // bias + 128 * sum(w) for unsigned inputs
+    const int fq = inst & 3, subs = inst >> 2, vw = subs == 2 ? 14 : DW_SW;
     a.band = DW_BAND;
     long long items = (long long)a.N * ((a.P + a.band - 1) / a.band) * ((a.Q + vw - 1) / vw) * (a.Cs >> 5);
     if (items < 4096 && a.P > 8) { a.band = 8; items = (long long)a.N * ((a.P + a.band - 1) / a.band) * ((a.Q + vw - 1) / vw) * (a.Cs >> 5); }   // < 4 waves per SIMD

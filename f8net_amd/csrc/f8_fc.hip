@@ -67,6 +67,8 @@ static hipError_t launch_fc_t(const ConvArgs& a, void* out, int classes, int as_
     return hipGetLastError();
 }
 
+int fc_dense_kernel_name(char* buf, size_t cap, const ConvArgs& a) { return snprintf(buf, cap, "f8::fc_dense_kernel<%d>", a.CK); }
+
 hipError_t launch_fc_dense(const ConvArgs& a, void* out, int classes, int as_float, const uint32_t* err, uint32_t epoch, hipStream_t s) {
     if (a.CK == 512) return launch_fc_t<512>(a, out, classes, as_float, err, epoch, s);
     if (a.CK == 1024) return launch_fc_t<1024>(a, out, classes, as_float, err, epoch, s);

@@ -942,6 +942,11 @@ hipError_t launch_fused_bottleneck(const FusedArgs& a, hipStream_t s) {
     return hipErrorInvalidValue;
 }
 
+int fused_bottleneck_kernel_name(char* buf, size_t cap, const FusedArgs& a) {      // COUT > 0: the DS variant (its wsc is set once the weights are uploaded)
+    const bool ds = a.COUT > 0;
+    return snprintf(buf, cap, "f8::fused_bottleneck_kernel<%d, %d, %d, %d, %d, %s>", a.C, a.MID, a.W, a.R, ds ? a.COUT : a.C, ds ? "true" : "false");
+}
+
 // stage-opening bottleneck at unchanged resolution (1x1 -> 3x3 -> [1x1 + 1x1 shortcut]): the ResNet-50 stage-0 shape
 bool fused_ds_supported(int C, int MID, int COUT, int H, int W, int* R) {
     if (C == 64 && MID == 64 && COUT == 256 && W == 56 && H % 2 == 0) { *R = 2; return true; }

@@ -106,8 +106,6 @@ struct ConvArgs {
     const int32_t* bias2;                  // [coutP]
     int32_t sN2, sP2, sQ2, ktot2;          // input byte strides of x2 (per image / output row / output col), its K
     void* trace;                           // tuning builds (F8_TRACE) only; nullptr otherwise
-    int32_t deep_nk;                       // Options::deep_nk (ring depth rule of launch_conv_t)
-    int32_t no_fast;                       // !Options::wstat_fast
 };
 
 // Depthwise 3x3 (groups == C), NHWC int8 in, VALU.
@@ -120,8 +118,6 @@ struct DwArgs {
     int32_t relu0;
     int32_t* out32;
     QuantOut q[2];
-    int32_t use_dot4;                      // Options::dw_dot4
-    int32_t use_mma;                       // Options::dw_mma
     int32_t band;                          // f8_dwmma.hip: output rows per wave (set by its launcher)
     int32_t acc_ok;                        // every accumulator is provably below 2^31 - 2^16 in magnitude (planner: conv_acc_bounded): the
                                            // float requantisation (requant_u8x4, f8_device.h) equals the wrapping integer one
@@ -182,7 +178,6 @@ struct FusedArgs {
     int32_t* out32; QuantOut q[2];
     void* trace;                           // tuning builds (F8_TRACE) only
     int32_t stride2;                       // stage-opening block with a stride-2 3x3 (f8_opener.hip): H, W are the INPUT map
-    int32_t stg;                           // Options::opener_stg
     int32_t acc_ok, rq_int;                // P12: both convs' accumulators bounded (conv_acc_bounded) / Options::requant_float == 0 (see DwArgs)
     int32_t p12only;                       // f8_opener.hip: body.0 + body.2 only, q[0] = body.2's output (NHWC int8, MID channels); the join runs as the
                                            // first block of the stage's chain launch (ChainArgs::tail)
@@ -290,7 +285,6 @@ struct StemPoolArgs {
     int32_t* out32;                        // pooled int32 (I32T, 64 channels) or nullptr
     QuantOut q[2];                         // pooled int8 NHWC (64 channels) in up to two formats
     int32_t wpc;                           // Options::stem_wpc
-    int32_t rows;                          // Options::stem_rows: the row-walking kernel where it has an instance
     int32_t grid_div;                      // Options::stem_grid_div: that kernel runs on 1 / grid_div of the CUs (0 = by output form)
     // h2 != 0: the MobileNet-V2 head instead (3x3 / 2 conv 3 -> 32 ReLU, depthwise 3x3 ReLU, 1x1 32 -> <= 32): w / bias = the head conv
     // ([32][3][32 B], single class), wd / bd = depthwise ([9][32] tap-major, bias + 128 sum(w)), w1 / b1 = the 1x1 ([32][32]); na / nb =
@@ -317,17 +311,29 @@ inline bool dyn_lds_opted_in(unsigned long long* done, int* dev_out) {
 
 struct ConvTile { int bm, bn, bk; };
 
+// Instances and their names.  A launch family whose launcher chooses between template instances on more than geometry has one
+// *_inst function next to its dispatch: f8_net.cpp bind_step calls it once, when the plan is bound, and keeps the value in Step::inst
+// (each family defines its bits); the launcher takes that value and only dispatches on it.  *_kernel_name builds the symbol the launcher
+// then starts, as rocprofv3 prints it (bench.py joins its live timings with the counter files of profiles/ on that string), next to the
+// instantiation; the families whose template argument is the run's raw-input kind are named without their arguments.  nq: the step's
+// int8 output forms, q[0 .. nq - 1]; out32 / res: it writes an int32 form / joins an int32 residual operand.
+
 // Tile choice for a conv; returns false if no kernel instance fits (ck % bk).
 bool pick_conv_tile(int M, int coutP, int ck, bool has_res, bool bk128, ConvTile* t);
 int  conv_grid(const ConvTile& t, int M, int coutP);
 
-hipError_t launch_conv(const ConvArgs& a, const ConvTile& t, hipStream_t s);
+int conv_inst(const ConvArgs& a, const ConvTile& t, bool res, bool dual, int deep_nk);   // ring depth (Options::deep_nk), residual, dual GEMM
+int conv_kernel_name(char* buf, size_t cap, const ConvArgs& a, const ConvTile& t, int inst);
+hipError_t launch_conv(const ConvArgs& a, const ConvTile& t, int inst, hipStream_t s);
 hipError_t launch_fused_bottleneck(const FusedArgs& a, hipStream_t s);
+int fused_bottleneck_kernel_name(char* buf, size_t cap, const FusedArgs& a);
 bool fused_bottleneck_supported(int C, int MID, int H, int W, int imgs_per_launch, int stage_mask, int* R);
 bool fused_ds_supported(int C, int MID, int COUT, int H, int W, int* R);
 // stage-opening block with a stride-2 3x3 (f8_opener.hip); H, W = input map
 bool fused_opener_supported(int C, int MID, int COUT, int H, int W, int* R);
-hipError_t launch_fused_opener(const FusedArgs& a, hipStream_t s);
+int fused_opener_inst(const FusedArgs& a, bool stg);            // full block: STG (Options::opener_stg); P12 form (p12only): FQ
+int fused_opener_kernel_name(char* buf, size_t cap, const FusedArgs& a, int inst);
+hipError_t launch_fused_opener(const FusedArgs& a, int inst, hipStream_t s);
 // all consecutive bottleneck blocks of a stage in one launch, residual stream in registers (f8_chain.hip).  cin0 != C: the first
 // block is the stage-opening block at unchanged resolution (1x1 shortcut conv from cin0 channels).
 bool chain_supported(int C, int MID, int H, int W, int cin0);
@@ -335,7 +341,7 @@ bool chain_tail_supported(int C, int MID, int H, int W, int cin0);   // ... a st
 int chain_max_blocks(int C, int MID, int H, int W, int cin0, bool tail);
 // rows per tile (4, or 2: the two-workgroups-per-CU instance of tuning builds, -DF8_CH_R2_S0=1) and resident workgroups per CU of the instance that runs the shape
 void chain_shape(int C, int MID, int H, int W, int cin0, bool tail, int* R, int* wg_per_cu);
-hipError_t launch_chain(const ChainArgs& a, int fast, int C, int MID, int H, int W, int cin0, hipStream_t s);   // fast: chain_fast
+hipError_t launch_chain(const ChainArgs& a, int fast, int C, int MID, int H, int W, int cin0, hipStream_t s);   // fast: chain_fast (the chain's inst)
 int chain_kernel_name(char* buf, size_t cap, int C, int MID, int H, int W, int cin0, bool tail, int fast);   // the symbol launch_chain starts (f8_chain.hip)
 // the identity blocks of a 7x7 bottleneck stage over clusters of eight workgroups (f8_cchain.hip): reached through chain_supported / launch_chain
 bool cchain_supported(int C, int MID, int H, int W, int cin0, bool tail);   // tail: the join of the stride-2 opening block as the first block (cin0 = its input channels)
@@ -354,39 +360,60 @@ int bchain_kernel_name(char* buf, size_t cap, int C, int H, int W, bool ds, int 
 // 1x1 -> 3x3 of a 7x7 bottleneck block in one launch (f8_p12.hip); FusedArgs: x8, w0 / b0, w2 / b2, requant 1, q[] = the int8 outputs
 bool fused_p12_supported(int C, int MID, int H, int W);
 hipError_t launch_fused_p12(const FusedArgs& a, hipStream_t s);
+int fused_p12_kernel_name(char* buf, size_t cap, const FusedArgs& a);
 // 1x1 conv with the weights streamed into registers (f8_wreg.hip); ConvArgs::w = the fragment-order image of the weights
 bool conv1x1_wreg_supported(int ck, int coutP);
 hipError_t launch_conv1x1_wreg(const ConvArgs& a, hipStream_t s);
+int conv1x1_wreg_kernel_name(char* buf, size_t cap, const ConvArgs& a);
 // classifier: integer linear + int32 -> float32 / int32 [N][classes] into the caller's buffer (f8_fc.hip); ConvArgs::w = fragment order
 bool fc_dense_supported(int ck, int coutP);
 hipError_t launch_fc_dense(const ConvArgs& a, void* out, int classes, int as_float, const uint32_t* err, uint32_t epoch, hipStream_t s);   // err / epoch: the run's chain error word and tag (logits poisoned when the word carries the tag) or nullptr
+int fc_dense_kernel_name(char* buf, size_t cap, const ConvArgs& a);
 // 3x3 / stride 2 / pad 1 with the input patch in LDS and the weights streamed into registers (f8_s2conv.hip); ConvArgs::w = fragment order
 bool conv3x3s2_wreg_supported(int ck, int HO, int WO, int coutP);
 hipError_t launch_conv3x3s2_wreg(const ConvArgs& a, hipStream_t s);
+int conv3x3s2_wreg_kernel_name(char* buf, size_t cap, const ConvArgs& a);
 // weight-stationary 1x1 conv / dual GEMM / residual join (f8_wstat.hip); ConvArgs::w (and w2) = fragment-order images
 bool conv1x1_wstat_supported(int k0, int k1, int coutP, bool has_res);
 int conv1x1_wstat_waves(int k0, int k1);
-bool conv1x1_wstat_fast(const ConvArgs& a);
-hipError_t launch_conv1x1_wstat(const ConvArgs& a, int num_cu, hipStream_t s);
+int conv1x1_wstat_inst(const ConvArgs& a, bool res, bool out32, int nq, bool fast);   // fast: Options::wstat_fast
+int conv1x1_wstat_kernel_name(char* buf, size_t cap, const ConvArgs& a, int inst);
+hipError_t launch_conv1x1_wstat(const ConvArgs& a, int inst, int num_cu, hipStream_t s);
 // MobileNet-V2 inverted residual (f8_ir.hip): instance for the padded channel pair + a tile (R rows or G whole images) that fits LDS
 bool fused_ir_config(int cinS, int coutS, int H, int W, int stride, int* R, int* G);
-hipError_t launch_fused_ir(const IRArgs& a, int cinS, int coutS, hipStream_t s);
+int fused_ir_inst(const IRArgs& a, int coutS);
+int fused_ir_kernel_name(char* buf, size_t cap, int cinS, int coutS, int inst);
+hipError_t launch_fused_ir(const IRArgs& a, int cinS, int coutS, int inst, hipStream_t s);
 // 3x3 / stride 1 / pad 1 with the input patch resident in LDS (f8_conv3x3.hip); config = false: no instance
 bool conv3x3_patch_config(int cin, int H, int W, int coutP, int* R, int* IMGS, int* BN);
 hipError_t launch_conv3x3_patch(const ConvArgs& a, int cin, hipStream_t s);
+int conv3x3_patch_kernel_name(char* buf, size_t cap, int cin, int W, bool res);
 bool head2_supported(int H, int W);
-bool dwconv_mma_supported(const DwArgs& a);
-hipError_t launch_dwconv_mma(const DwArgs& a, hipStream_t s);
+int dwconv_mma_inst(const DwArgs& a, bool out32, int nq, int N);   // f8_dwmma.hip: FQ | sub-rows << 2, or -1 (no instance for N images)
+hipError_t launch_dwconv_mma(const DwArgs& a, int inst, hipStream_t s);
 bool stem_pool_supported(int cin, int cout, int k, int stride, int pad, int pool_k, int pool_s, int pool_p, int P, int Q, int rows, int H, int W);
-hipError_t launch_stem_pool(const StemPoolArgs& a, hipStream_t s);
-hipError_t launch_dwconv(const DwArgs& a, hipStream_t s);
-hipError_t launch_maxpool(const PoolArgs& a, hipStream_t s);
+int stem_pool_inst(const StemPoolArgs& a, bool rows, bool raw);    // 0 tile kernel, 1 row-walking kernel, 2 MobileNet-V2 head; raw: the plan reads the raw input
+const char* stem_pool_kernel_name(int inst);
+hipError_t launch_stem_pool(const StemPoolArgs& a, int inst, hipStream_t s);
+// mma / dot4: Options::dw_mma / dw_dot4; max_batch: the largest N a launch may cover (the MMA kernel's 32-bit index bound)
+int dwconv_inst(const DwArgs& a, bool out32, int nq, bool mma, bool dot4, int max_batch);
+int dwconv_kernel_name(char* buf, size_t cap, const DwArgs& a, int inst);
+hipError_t launch_dwconv(const DwArgs& a, int inst, hipStream_t s);
+int maxpool_inst(const PoolArgs& a);
+const char* maxpool_kernel_name(int inst);
+hipError_t launch_maxpool(const PoolArgs& a, int inst, hipStream_t s);
+const char* avgpool_kernel_name();
 hipError_t launch_avgpool(const AvgArgs& a, hipStream_t s);
 // last 1x1 conv (+ residual join) + average pool in one launch (f8_pool.hip); ConvArgs::w = fragment order, out32 / q[] = the POOLED forms [N][coutP]
 bool conv1x1_pool_supported(int ck, int coutP, int pq);
 hipError_t launch_conv1x1_pool(const ConvArgs& a, hipStream_t s);
+int conv1x1_pool_kernel_name(char* buf, size_t cap, const ConvArgs& a, bool res);
+const char* add_kernel_name();
 hipError_t launch_add(const AddArgs& a, hipStream_t s);
-hipError_t launch_input(const InArgs& a, hipStream_t s);
+int input_inst(int C, int W, bool stem_only);                      // 1: input_stem4_kernel (the input's only form is the stem's NHWC4 copy), 0: input_kernel
+const char* input_kernel_name(int inst);
+hipError_t launch_input(const InArgs& a, int inst, hipStream_t s);
+const char* output_kernel_name();
 hipError_t launch_output(const OutArgs& a, hipStream_t s);
 hipError_t launch_quantize_input(const float* x, int32_t* y, size_t n, float scale, int lo, int hi, hipStream_t s);
 struct TopkKs { int k[8]; };                // the k list travels by value in the kernel arguments

@@ -470,15 +470,23 @@ static hipError_t launch_ir_t(const IRArgs& a, int lds, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t launch_fused_ir(const IRArgs& a0, int cinS, int coutS, hipStream_t s) {
+// FQ: ReLU + right shift into unsigned 8-bit after the expand AND the depthwise conv (the VALU depthwise path keeps its general epilogue)
+// 1: through the float converter (bounded accumulators, shifts <= 16); 2: the integer form (option requant_float = 0, or where 1 is not provably exact)
+int fused_ir_inst(const IRArgs& a, int coutS) {
+    const bool fqf = a.relu_a && a.relu_b && a.n1 > 0 && a.n2 > 0 && a.n1 <= 30 && a.n2 <= 30 && a.lo1 == 0 && a.lo2 == 0 && a.hi1 == 255 && a.hi2 == 255 &&
+                     a.xor1 == 0x80808080u && a.xor2 == 0x80808080u && coutS <= 96;
+    return !fqf ? 0 : ((a.rq_int || !a.acc_ok || a.n1 > kRequantU8MaxShift || a.n2 > kRequantU8MaxShift) ? 2 : 1);
+}
+
+int fused_ir_kernel_name(char* buf, size_t cap, int cinS, int coutS, int inst) {
+    return snprintf(buf, cap, "f8::fused_ir_kernel<%d, %d, %d, %s, %d>", cinS, coutS, inst, coutS <= 96 ? "true" : "false", ir_nw(cinS, coutS));
+}
+
+hipError_t launch_fused_ir(const IRArgs& a0, int cinS, int coutS, int inst, hipStream_t s) {
     IRArgs a = a0;
     int lds = 0;
     if (!ir_layout(cinS, coutS, a.H, a.W, a.stride, a.R, a.G, &a, &lds)) return hipErrorInvalidValue;
-    // FQ: ReLU + right shift into unsigned 8-bit after the expand AND the depthwise conv (the VALU depthwise path keeps its general epilogue)
-    // 1: through the float converter (bounded accumulators, shifts <= 16); 2: the integer form (option requant_float = 0, or where 1 is not provably exact)
-    const bool fqf = a.relu_a && a.relu_b && a.n1 > 0 && a.n2 > 0 && a.n1 <= 30 && a.n2 <= 30 && a.lo1 == 0 && a.lo2 == 0 && a.hi1 == 255 && a.hi2 == 255 &&
-                     a.xor1 == 0x80808080u && a.xor2 == 0x80808080u && coutS <= 96;
-    const int fq = !fqf ? 0 : ((a.rq_int || !a.acc_ok || a.n1 > kRequantU8MaxShift || a.n2 > kRequantU8MaxShift) ? 2 : 1);
+    const int fq = inst;
 #define F8_IR(C_, O_) if (cinS == C_ && coutS == O_) return fq == 1 ? launch_ir_t<C_, O_, 1>(a, lds, s) : fq == 2 ? launch_ir_t<C_, O_, 2>(a, lds, s) : launch_ir_t<C_, O_, 0>(a, lds, s);
     F8_IR(32, 32) F8_IR(32, 64) F8_IR(64, 64) F8_IR(64, 96) F8_IR(96, 96) F8_IR(96, 160) F8_IR(160, 160) F8_IR(160, 320)
 #undef F8_IR

@@ -910,11 +910,36 @@ bool pick_conv_tile(int M, int coutP, int ck, bool has_res, bool bk128, ConvTile
     return true;
 }
 
-// K loops of at least ConvArgs::deep_nk (Options::deep_nk, default 7) steps get the deepest ring that fits 64 KB of static LDS (else 2
-// slots).  Measured (ResNet-50, bs 128, A/B/A/B): threshold 16 -> 64.0-64.5 k, 7 -> 64.7-64.9 k, 5 -> 65.2 k img/s; 7 takes in the
-// 7-step stem (80 -> 75 us) and the 9-step 3x3s without touching the 4-step residual-carrying 1x1s.
 int conv_grid(const ConvTile& t, int M, int coutP) {
     return ((M + t.bm - 1) / t.bm) * ((coutP + t.bn - 1) / t.bn);
+}
+
+// Ring depth of conv_igemm_kernel: kConvStages slots, or the deepest ring that fits 64 KB of static LDS for long K loops.
+#ifdef F8_FORCE_STAGES
+constexpr int kConvStages = F8_FORCE_STAGES;
+#else
+// measured on ResNet-50 (profiles/): ring depth 2/3/4 = 49.9k/49.5k/48.5k img/s for the one-tile-per-workgroup
+// kernel — bound by per-workgroup instruction issue and start-up, not by steady-state latency, so the
+// smaller LDS footprint (more resident workgroups) wins there
+constexpr int kConvStages = 2;
+#endif
+constexpr int conv_deep_stages(int bm, int bn, int bk) { return 4 * (bm + bn) * bk <= 65536 ? 4 : (3 * (bm + bn) * bk <= 65536 ? 3 : 2); }
+constexpr int conv_wpx(int bm, int bn) { return bm == 128 && bn <= 64 ? 4 : 2; }     // waves along the pixels (the F8_CASE table of launch_conv)
+enum { kConvDeep = 1, kConvRes = 2, kConvDual = 4 };
+
+// Long K loops (3x3 of the late stages: 36-72 steps of ~64-256 MFMA cycles against an ~800-cycle DMA round trip) want a deeper ring,
+// short ones the smaller LDS footprint: K loops of at least Options::deep_nk (default 7) steps get the deep ring.  Measured (ResNet-50,
+// bs 128, A/B/A/B): threshold 16 -> 64.0-64.5 k, 7 -> 64.7-64.9 k, 5 -> 65.2 k img/s; 7 takes in the 7-step stem (80 -> 75 us) and the
+// 9-step 3x3s without touching the 4-step residual-carrying 1x1s.
+int conv_inst(const ConvArgs& a, const ConvTile& t, bool res, bool dual, int deep_nk) {
+    const bool deep = conv_deep_stages(t.bm, t.bn, t.bk) > kConvStages && (a.ktot + a.ktot2) / t.bk >= deep_nk;
+    return (deep ? kConvDeep : 0) | (res ? kConvRes : 0) | (dual ? kConvDual : 0);
+}
+
+int conv_kernel_name(char* buf, size_t cap, const ConvArgs& a, const ConvTile& t, int inst) {
+    const int wpx = conv_wpx(t.bm, t.bn), dual = inst & kConvDual;
+    return snprintf(buf, cap, "f8::conv_igemm_kernel<%d, %d, %d, %d, %d, %s, %s, %d, %s>", t.bm, t.bn, t.bk, wpx, 4 / wpx, a.pad > 0 ? "true" : "false",
+                    (inst & kConvRes) || dual ? "true" : "false", inst & kConvDeep ? conv_deep_stages(t.bm, t.bn, t.bk) : kConvStages, dual ? "true" : "false");
 }
 
 static int g_num_cu = 0;
@@ -928,23 +953,11 @@ static int num_cus() {
 }
 
 template <int BM, int BN, int BK, int WPX, int WCO>
-static hipError_t launch_conv_t(const ConvArgs& a, int grid, hipStream_t s) {
-#ifdef F8_FORCE_STAGES
-    constexpr int ST = F8_FORCE_STAGES;
-#else
-    // measured on ResNet-50 (profiles/): ring depth 2/3/4 = 49.9k/49.5k/48.5k img/s for the one-tile-per-workgroup
-    // kernel — bound by per-workgroup instruction issue and start-up, not by steady-state latency, so the
-    // smaller LDS footprint (more resident workgroups) wins there
-    constexpr int ST = 2;
-#endif
-    constexpr int TILE = (BM + BN) * BK;
-    static_assert(ST * TILE <= 65536, "static LDS");
-    const bool pad = a.pad > 0, res = a.res != nullptr;
-    // long K loops (3x3 of the late stages: 36-72 steps of ~64-256 MFMA cycles against an ~800-cycle DMA round
-    // trip) want a deeper ring; short ones want the smaller LDS footprint
-    const int deep_nk = a.deep_nk > 0 ? a.deep_nk : 7;
-    constexpr int DST = (4 * TILE <= 65536) ? 4 : ((3 * TILE <= 65536) ? 3 : 2);
-    const bool deep = (DST > ST) && ((a.ktot + a.ktot2) / BK >= deep_nk);
+static hipError_t launch_conv_t(const ConvArgs& a, int inst, int grid, hipStream_t s) {
+    constexpr int ST = kConvStages, DST = conv_deep_stages(BM, BN, BK);
+    static_assert(ST * (BM + BN) * BK <= 65536, "static LDS");
+    const bool pad = a.pad > 0, res = inst & kConvRes, deep = inst & kConvDeep;
+    if (res != (a.res != nullptr) || ((inst & kConvDual) != 0) != (a.x2 != nullptr)) return hipErrorInvalidValue;
     if (a.x2) {   // dual GEMM (downsample join): 1x1 / no padding; 64-wide cout tiles, or 128x128 for the wide late stages
         if constexpr (BK == 64 && (BN == 64 || (BN == 128 && BM == 128))) {
             if (pad || res) return hipErrorInvalidValue;
@@ -969,7 +982,7 @@ static int g_trace_launch = 0;
 static void* g_trace_buf = nullptr;
 #endif
 
-hipError_t launch_conv(const ConvArgs& a0, const ConvTile& t, hipStream_t s) {
+hipError_t launch_conv(const ConvArgs& a0, const ConvTile& t, int inst, hipStream_t s) {
     ConvArgs a = a0;
     const int grid = conv_grid(t, a.M, a.coutP);
 #ifdef F8_TRACE
@@ -998,7 +1011,7 @@ hipError_t launch_conv(const ConvArgs& a0, const ConvTile& t, hipStream_t s) {
     } } dump{tracing, grid, s};
 #endif
 #define F8_CASE(BM_, BN_, BK_, WPX_, WCO_) \
-    if (t.bm == BM_ && t.bn == BN_ && t.bk == BK_) return launch_conv_t<BM_, BN_, BK_, WPX_, WCO_>(a, grid, s);
+    if (t.bm == BM_ && t.bn == BN_ && t.bk == BK_) return launch_conv_t<BM_, BN_, BK_, WPX_, WCO_>(a, inst, grid, s);
     F8_CASE(128, 128, 128, 2, 2)
     F8_CASE(128, 64, 128, 4, 1)
     F8_CASE(64, 128, 128, 2, 2)
@@ -1017,10 +1030,25 @@ hipError_t launch_conv(const ConvArgs& a0, const ConvTile& t, hipStream_t s) {
     return hipErrorInvalidValue;
 }
 
-hipError_t launch_dwconv(const DwArgs& a, hipStream_t s) {
-    // dot4 kernel: int8 outputs only, stride 1 / 2, pad 1, channel stride a multiple of 16 (always: Cs % 32 == 0)
-    if (a.use_mma && dwconv_mma_supported(a)) return launch_dwconv_mma(a, s);
-    if (a.use_dot4 && !a.out32 && a.w4 && a.pad == 1 && (a.stride == 1 || a.stride == 2)) {
+// Depthwise 3x3: the matrix-core kernel (f8_dwmma.hip) where it has an instance, else the v_dot4 kernel (int8 outputs only, stride 1 / 2,
+// pad 1, channel stride a multiple of 16: always, Cs % 32 == 0), else the generic one.  inst: kind | dwconv_mma_inst << 2.
+enum { kDwGeneric = 0, kDwDot4 = 1, kDwMma = 2 };
+int dwconv_inst(const DwArgs& a, bool out32, int nq, bool mma, bool dot4, int max_batch) {
+    const int m = mma ? dwconv_mma_inst(a, out32, nq, max_batch) : -1;
+    if (m >= 0) return kDwMma | m << 2;
+    return dot4 && !out32 && a.pad == 1 && (a.stride == 1 || a.stride == 2) ? kDwDot4 : kDwGeneric;
+}
+
+int dwconv_kernel_name(char* buf, size_t cap, const DwArgs& a, int inst) {
+    if ((inst & 3) == kDwMma) return snprintf(buf, cap, "f8::dwconv3x3_mma_kernel<%d, %d, %d>", a.stride, (inst >> 2) & 3, inst >> 4);
+    if ((inst & 3) == kDwDot4) return snprintf(buf, cap, "f8::dwconv3x3_dot4_kernel<%d, 2>", a.stride);
+    return snprintf(buf, cap, "f8::dwconv3x3_kernel<%s>", a.in_signed ? "true" : "false");
+}
+
+hipError_t launch_dwconv(const DwArgs& a, int inst, hipStream_t s) {
+    if ((inst & 3) == kDwMma) return launch_dwconv_mma(a, inst >> 2, s);
+    if ((inst & 3) == kDwDot4) {
+        if (a.out32 || !a.w4 || a.pad != 1 || (a.stride != 1 && a.stride != 2)) return hipErrorInvalidValue;
         const size_t work = (size_t)a.N * a.P * ((a.Q + 1) / 2) * (a.Cs >> 4);
         const unsigned grid = (unsigned)((work + 255) / 256);
         DwArgs b = a; b.w = a.w4; b.bias = a.bias4;
@@ -1033,8 +1061,10 @@ hipError_t launch_dwconv(const DwArgs& a, hipStream_t s) {
     else hipLaunchKernelGGL(dwconv3x3_kernel<false>, dim3(grid_for(work)), dim3(256), 0, s, a);
     return hipGetLastError();
 }
-hipError_t launch_maxpool(const PoolArgs& a, hipStream_t s) {
-    if (a.in_is_i8 && (a.Cs & 15) == 0 && a.pad < a.k) {     // every window holds at least one in-image tap (pad < k)
+int maxpool_inst(const PoolArgs& a) { return a.in_is_i8 && (a.Cs & 15) == 0 && a.pad < a.k; }     // every window holds at least one in-image tap (pad < k)
+const char* maxpool_kernel_name(int inst) { return inst ? "f8::maxpool_i8x16_kernel" : "f8::maxpool_kernel"; }
+hipError_t launch_maxpool(const PoolArgs& a, int inst, hipStream_t s) {
+    if (inst) {
         hipLaunchKernelGGL(maxpool_i8x16_kernel, dim3(grid_for((size_t)a.N * a.P * a.Q * (a.Cs >> 4), 256, 1 << 20)), dim3(256), 0, s, a);
         return hipGetLastError();
     }
@@ -1042,17 +1072,23 @@ hipError_t launch_maxpool(const PoolArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(maxpool_kernel, dim3(grid_for(work)), dim3(256), 0, s, a);
     return hipGetLastError();
 }
+const char* avgpool_kernel_name() { return "f8::avgpool_kernel"; }
 hipError_t launch_avgpool(const AvgArgs& a, hipStream_t s) {
     const size_t work = (size_t)a.N * (a.Cs >> 2) * 8;
     hipLaunchKernelGGL(avgpool_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, s, a);
     return hipGetLastError();
 }
+const char* add_kernel_name() { return "f8::add_kernel"; }
 hipError_t launch_add(const AddArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(add_kernel, dim3(grid_for((size_t)a.M * (a.Cs >> 2))), dim3(256), 0, s, a);
     return hipGetLastError();
 }
-hipError_t launch_input(const InArgs& a, hipStream_t s) {
-    if (a.stem && !a.out8 && !a.out32 && (a.W & 3) == 0 && a.C <= 4) {
+int input_inst(int C, int W, bool stem_only) { return stem_only && (W & 3) == 0 && C <= 4; }
+// input_stem4_kernel's first template argument is the kind of the run's input (int32, fp32, uint8 planes or pixels): named without arguments
+const char* input_kernel_name(int inst) { return inst ? "f8::input_stem4_kernel" : "f8::input_kernel"; }
+hipError_t launch_input(const InArgs& a, int inst, hipStream_t s) {
+    if (inst) {
+        if (!a.stem || a.out8 || a.out32) return hipErrorInvalidValue;
         const dim3 grid(grid_for((size_t)a.N * a.H * (a.W >> 2), 256, 1 << 20));
         const int kind = a.xu8 ? (a.u8_nhwc ? 3 : 2) : a.xf ? 1 : 0;
 #define F8_IN(K, CT) hipLaunchKernelGGL((input_stem4_kernel<K, CT>), grid, dim3(256), 0, s, a)
@@ -1072,6 +1108,7 @@ hipError_t launch_topk_correct(const float* logits, const int64_t* target, int N
     hipLaunchKernelGGL(topk_correct_kernel, dim3((N + 3) / 4), dim3(256), 0, s, logits, target, N, C, ks, nk, correct);
     return hipGetLastError();
 }
+const char* output_kernel_name() { return "f8::output_kernel"; }
 hipError_t launch_output(const OutArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(output_kernel, dim3(grid_for((size_t)a.N * a.C * a.HW)), dim3(256), 0, s, a);
     return hipGetLastError();

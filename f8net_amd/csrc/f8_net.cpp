@@ -121,13 +121,14 @@ struct Step {
     bool dense = false;
     bool raw_input = false;            // S_INPUT: its work is done by the stem launch (S_STEMPOOL with the same flag) unless the run's input is uint8 NHWC
     std::string name;
-    std::string kernel;                // device symbol as rocprofv3 prints it (chain steps: of the instance bind_step chose)
+    std::string kernel;                // device symbol as rocprofv3 prints it: of the instance bind_step chose (the launch family's *_kernel_name)
     double bytes_per_img = 0, bytes_const = 0, ops_per_img = 0;
     double valu_per_img = 0;           // ESSENTIAL vector lane-operations per image (f8_net_launch_valu): what the reference's semantics need once the MFMAs are done
     // the launcher's arguments as far as the plan decides them (bind_step); run_step copies them and adds what the run decides
     std::variant<std::monostate, ConvArgs, StemPoolArgs, FusedArgs, ChainArgs, BChainArgs, IRArgs, DwArgs, AddArgs, PoolArgs, AvgArgs, OutArgs> args;
-    // S_CHAIN / S_BCHAIN: the instance (chain_fast / bchain_fast), its geometry, workgroups per image and resident per CU, the 7x7 cluster form (f8_cchain.hip)
-    int fast = 0, C = 0, MID = 0, H = 0, W = 0, cin0 = 0, tiles = 0, wg_per_cu = 1; bool cluster = false;
+    int inst = 0;                      // the instance the launcher starts (the family's *_inst, f8_internal.h; bind_step)
+    // S_CHAIN / S_BCHAIN: geometry, workgroups per image and resident per CU, the 7x7 cluster form (f8_cchain.hip)
+    int C = 0, MID = 0, H = 0, W = 0, cin0 = 0, tiles = 0, wg_per_cu = 1; bool cluster = false;
 };
 
 }  // namespace
@@ -797,10 +798,14 @@ static void select_outputs(f8_net* net, int t, OutSel* o, std::vector<int>* extr
 //   1/4 v_xor_b32; the ReLU in front of it is the clamp's lower bound); a joined int32 value: align-add + clamp / ReLU = 2; a max-pooled conv value: 1.
 // Addressing, lane swaps, exec masks, halo code, tile padding and recompute are NOT in it: they are what the ratio shows.
 static double out_forms8(const Step& st) { return (double)((st.out.f8[0] >= 0) + (st.out.f8[1] >= 0)); }
-static void label_conv_step(f8_net* net, Step& st, Node& nd) {
+static bool only_stem_form(const Tensor& o) {           // the network input's one form is the stem's haloed NHWC4 copy
+    bool only = !o.forms.empty();
+    for (auto& F : o.forms) only = only && F.kind == FORM_STEM;
+    return only;
+}
+static void label_conv_step(f8_net* net, Step& st, Node& nd) {          // the layer label (the kernel's name: bind_step)
     auto& ND = net->nodes;
     const f8_conv_desc& d = nd.cd;
-    const Tensor& s = net->tensors[nd.a];
     char buf[160];
     if (nd.depthwise) snprintf(buf, sizeof buf, "dwconv3x3s%d:%s", d.stride, tname(net, nd.out).c_str());
     else snprintf(buf, sizeof buf, "conv%dx%ds%d_t%dx%dx%d%s%s:%s", d.kernel, d.kernel, d.stride, nd.tile.bm, nd.tile.bn,
@@ -809,30 +814,6 @@ static void label_conv_step(f8_net* net, Step& st, Node& nd) {
     if (nd.p3_R > 0) snprintf(buf, sizeof buf, "conv3x3s1_patch_R%dx%d_bn%d%s:%s", nd.p3_R, nd.p3_imgs, nd.p3_bn, st.res_t >= 0 ? "_res" : "",
                               tname(net, nd.out).c_str());
     st.name = buf;
-    if (nd.depthwise) {
-        const Tensor& od = net->tensors[nd.out];         // keep in sync with launch_dwconv / dwconv_mma_supported / launch_dwconv_mma (FQ)
-        int fq = d.relu ? ((conv_acc_bounded(nd) && net->opt.requant_float) ? 1 : 2) : 0;
-        int n8 = 0;
-        for (int k = 0; k < 2; ++k) if (st.out.f8[k] >= 0) { const Form& F = od.forms[st.out.f8[k]]; ++n8; if (!(F.n > 0 && F.n <= 30 && !F.sgn)) fq = 0; else if (fq == 1 && F.n > 16) fq = 2; }
-        const bool mma = net->opt.dw_mma && st.out.f32 < 0 && n8 > 0 && d.pad == 1 && (d.stride == 1 || d.stride == 2) && (od.W >= 28 || od.W == 14) &&
-                         (d.stride == 1 ? (od.H == s.H && od.W == s.W) : (s.H == 2 * od.H && s.W == 2 * od.W));
-        if (mma) snprintf(buf, sizeof buf, "f8::dwconv3x3_mma_kernel<%d, %d, %d>", d.stride, fq, od.W >= 28 ? 1 : 2);
-        else snprintf(buf, sizeof buf, "f8::dwconv3x3_dot4_kernel<%d, 2>", d.stride);
-    }
-    else if (nd.p3_R > 0) snprintf(buf, sizeof buf, "f8::conv3x3_patch_kernel<%d, %d, %d, %d, %d, %d, %s>", d.cin, s.W, nd.p3_R, nd.p3_imgs, nd.p3_bn,
-                                   d.cin == 64 ? 64 : (nd.p3_bn == 128 ? 128 : 256), st.res_t >= 0 ? "true" : "false");   // keep in sync with launch_conv3x3_patch
-    else {
-        const int wpx = (nd.tile.bm == 128 && nd.tile.bn <= 64) ? 4 : 2, wco = 4 / wpx;
-        // keep in sync with launch_conv_t (f8_kernels.hip)
-        const int tile_b = (nd.tile.bm + nd.tile.bn) * nd.tile.bk;
-        const int dst = (4 * tile_b <= 65536) ? 4 : ((3 * tile_b <= 65536) ? 3 : 2);
-        const int ksteps = (nd.ktot + (nd.dual >= 0 ? ND[nd.dual].ktot : 0)) / nd.tile.bk;
-        const int stages = (dst > 2 && ksteps >= net->opt.deep_nk) ? dst : 2;    // ring depth rule of launch_conv_t
-        snprintf(buf, sizeof buf, "f8::conv_igemm_kernel<%d, %d, %d, %d, %d, %s, %s, %d, %s>", nd.tile.bm, nd.tile.bn, nd.tile.bk, wpx, wco,
-                 (d.pad > 0 && !nd.stem) ? "true" : "false", (st.res_t >= 0 || nd.dual >= 0) ? "true" : "false", stages,
-                 nd.dual >= 0 ? "true" : "false");
-    }
-    st.kernel = buf;
 }
 
 // ================================================================================================================================
@@ -1434,7 +1415,7 @@ static int emit_steps(f8_net* net, int max_batch) {
             Step st; st.kind = S_REQUANT; st.node = T[t].prod;
             st.src_t = t; st.src_f = find_form(T[t], FORM_I32, 0, 0);
             st.out.t = t; st.out.f8[0] = f;
-            st.name = "requant:" + tname(net, t); st.kernel = "f8::add_kernel";
+            st.name = "requant:" + tname(net, t);
             const double e = (double)T[t].H * T[t].W * T[t].Cs;
             st.bytes_per_img = e * 5;
             net->steps.push_back(st);
@@ -1462,7 +1443,7 @@ static int emit_steps(f8_net* net, int max_batch) {
                     if (o.forms[f].kind == FORM_I8 && o.forms[f].n != 0) extra.push_back((int)f);
                 if (!extra.empty()) add_form(o, FORM_I32, 0, 0);
                 st.out.t = nd.out;
-                st.name = "input"; st.kernel = "f8::input_kernel";     // refined below once the forms are known
+                st.name = "input";
                 double b = (double)o.C * o.H * o.W * 4;
                 for (auto& F : o.forms) b += (double)o.H * o.W * (F.kind == FORM_I32 ? o.Cs * 4 : (F.kind == FORM_STEM ? 4 : o.Cs));
                 st.bytes_per_img = b;
@@ -1486,7 +1467,6 @@ static int emit_steps(f8_net* net, int max_batch) {
                     st.bytes_per_img = (double)s.H * s.W * 4 + cpx * o.Cs * ((st.out.f8[0] >= 0) + (st.out.f8[1] >= 0));
                     st.bytes_const = 32.0 * 100 + 32.0 * 13 + 32.0 * 36;
                     st.name = "head3x3s2+dw3x3+1x1:" + tname(net, hh.out) + "+" + tname(net, hb.out) + "+" + tname(net, nd.out);
-                    st.kernel = "f8::stem_rows_kernel";
                     break;
                 }
                 if (nd.sp_pool >= 0 && nd.stem) {
@@ -1506,7 +1486,6 @@ static int emit_steps(f8_net* net, int max_batch) {
                     st.bytes_per_img = (double)s.H * s.W * 4 + (double)o.H * o.W * o.Cs * ((st.out.f32 >= 0 ? 4 : 0) + (st.out.f8[0] >= 0) + (st.out.f8[1] >= 0));
                     st.bytes_const = (double)nd.coutP * (nd.ktot + 4);
                     st.name = "stem7x7s2+maxpool3x3s2:" + tname(net, nd.out) + "+" + tname(net, pl.out);
-                    st.kernel = (opt.stem_rows && T[pl.out].W >= 2 && T[pl.out].W <= 56 && s.W == 4 * T[pl.out].W && s.H == 4 * T[pl.out].H) ? "f8::stem_rows_kernel" : "f8::stem_pool_kernel";    // keep in sync with launch_stem_pool
                     break;
                 }
                 if (nd.bchain_into == i) {
@@ -1544,7 +1523,7 @@ static int emit_steps(f8_net* net, int max_batch) {
                     st.ops_per_img = ops; st.bytes_per_img = b; st.bytes_const = wbytes;
                     st.valu_per_img = (double)ch.size() * px * o.C * (3.0 + 2.0 + 3.0) - 3.0 * px * o.C + 3.0 * px * o.Cs * out_forms8(st);   // per block: first conv's int8, join, the next block's int8 input; the last block's are the output forms
                     st.name = "basic_chain_x" + std::to_string(ch.size()) + (ds ? "_ds:" : ":") + tname(net, f1.out) + ".." + tname(net, nd.out);
-                    break;                                       // (kernel: bind_step)
+                    break;
                 }
                 if (nd.chain_into == i) {
                     // ---- stage chain: nd is the host conv of its LAST block
@@ -1596,7 +1575,7 @@ static int emit_steps(f8_net* net, int max_batch) {
                     }
                     const Node& a0 = tail ? ND[hf.dual] : ND[ds ? hf.fbd_a : hf.fb_a];
                     st.name = "stage_chain_x" + std::to_string(ch.size()) + (tail ? "_tail" : (ds ? "_ds" : "")) + (nd.pool >= 0 ? "+avgpool:" : ":") + tname(net, a0.out) + ".." + tname(net, nd.out);
-                    break;                                       // (kernel: bind_step)
+                    break;
                 }
                 if (nd.fbd_a >= 0) {
                     // ---- fused stage-opening block (DS): nd is the shortcut conv, nd.dual the block's last body conv
@@ -1629,11 +1608,6 @@ static int emit_steps(f8_net* net, int max_batch) {
                                      (double)nd.coutP * (nd.ktot + 4);
                     st.name = std::string(nd.fbd_s2 ? "fused_opener_s2_R" : "fused_bottleneck_ds_R") + std::to_string(nd.fb_R) + ":" + tname(net, na.out) + "+" +
                               tname(net, nb.out) + "+" + tname(net, ng.out) + "+" + tname(net, nd.out);
-                    char kb[160];
-                    if (nd.fbd_s2) snprintf(kb, sizeof kb, "f8::fused_opener_kernel<%d, %d, %d, %d, %d, %s>", na.cd.cin, na.cd.cout, x.W, nd.fb_R, nd.cd.cout,
-                                            (opt.opener_stg && st.out.f8[0] >= 0) ? "true" : "false");
-                    else snprintf(kb, sizeof kb, "f8::fused_bottleneck_kernel<%d, %d, %d, %d, %d, true>", na.cd.cin, na.cd.cout, x.W, nd.fb_R, nd.cd.cout);
-                    st.kernel = kb;
                     break;
                 }
                 if (nd.p12_a >= 0) {
@@ -1660,10 +1634,6 @@ static int emit_steps(f8_net* net, int max_batch) {
                     st.bytes_per_img = b;
                     st.bytes_const = (double)na.coutP * (na.ktot + 4) + (double)nd.coutP * (nd.ktot + 4);
                     st.name = std::string(nd.p12_s2 ? "fused_opener_s2_p12_R" + std::to_string(nd.fb_R) + ":" : "fused_p12:") + tname(net, na.out) + "+" + tname(net, nd.out);
-                    char kb[96];
-                    if (nd.p12_s2) snprintf(kb, sizeof kb, "f8::fused_opener_kernel<%d, %d, %d, %d, %d, false, true, %d>", na.cd.cin, na.cd.cout, x.W, nd.fb_R, 4 * na.cd.cout, opt.requant_float ? 1 : 2);
-                    else snprintf(kb, sizeof kb, "f8::fused_p12_kernel<%d, %d>", na.cd.cin, na.cd.cout);
-                    st.kernel = kb;
                     break;
                 }
                 if (nd.ir_a >= 0) {
@@ -1700,14 +1670,6 @@ static int emit_steps(f8_net* net, int max_batch) {
                     char kb[200];
                     snprintf(kb, sizeof kb, "fused_ir_s%d_%s:", nb.cd.stride, nd.ir_G > 1 ? ("G" + std::to_string(nd.ir_G)).c_str() : ("R" + std::to_string(nd.ir_R)).c_str());
                     st.name = std::string(kb) + tname(net, na.out) + "+" + tname(net, nb.out) + "+" + tname(net, nd.out);
-                    {   // keep in sync with launch_fused_ir (FQ) and f8_ir.hip (P2MMA)
-                        int n1 = 0, n2 = 0;
-                        consumer_format(T[nb.a], nb.cd, &n1, "finalize"); consumer_format(T[nd.a], nd.cd, &n2, "finalize");
-                        const bool fqf = na.cd.relu && nb.cd.relu && !nb.cd.input_signed && !nd.cd.input_signed && n1 > 0 && n2 > 0 && n1 <= 30 && n2 <= 30 && nd.coutP <= 96;
-                        const int fq = !fqf ? 0 : ((opt.requant_float && n1 <= 16 && n2 <= 16 && conv_acc_bounded(na) && conv_acc_bounded(nb)) ? 1 : 2);
-                        snprintf(kb, sizeof kb, "f8::fused_ir_kernel<%d, %d, %d, %s, %d>", x.Cs, nd.coutP, fq, nd.coutP <= 96 ? "true" : "false", nd.coutP <= 96 ? 8 : 4);
-                    }
-                    st.kernel = kb;
                     break;
                 }
                 if (nd.fb_a >= 0) {
@@ -1738,9 +1700,6 @@ static int emit_steps(f8_net* net, int max_batch) {
                     st.bytes_per_img = b;
                     st.bytes_const = (double)na.coutP * (na.ktot + 4) + (double)nb.coutP * (nb.ktot + 4) + (double)nd.coutP * (nd.ktot + 4);
                     st.name = "fused_bottleneck_R" + std::to_string(nd.fb_R) + ":" + tname(net, na.out) + "+" + tname(net, nb.out) + "+" + tname(net, nd.out);
-                    char kb[160];
-                    snprintf(kb, sizeof kb, "f8::fused_bottleneck_kernel<%d, %d, %d, %d, %d, false>", na.cd.cin, na.cd.cout, x.W, nd.fb_R, na.cd.cin);
-                    st.kernel = kb;
                     break;
                 }
                 Tensor& s = T[nd.a];
@@ -1809,9 +1768,6 @@ static int emit_steps(f8_net* net, int max_batch) {
                 if (st.dense) {                          // the classifier: logits straight into the caller's buffer (f8_fc.hip)
                     pack_frag_weights(net, nd);
                     st.name = "linear_dense:" + tname(net, nd.out);
-                    char kb[64];
-                    snprintf(kb, sizeof kb, "f8::fc_dense_kernel<%d>", nd.ck);
-                    st.kernel = kb;
                 }
                 // 1x1 convs (plain, with the residual join, or as the dual GEMM of a stage-opening block) whose weight slice per wave
                 // fits the register file: weight-stationary kernel, when a launch gives every workgroup a few pixel tiles to walk
@@ -1819,9 +1775,6 @@ static int emit_steps(f8_net* net, int max_batch) {
                     pack_frag_weights(net, nd);
                     const size_t colon = st.name.find(':');
                     st.name = std::string(st.res_t >= 0 ? "conv1x1_res+avgpool" : "conv1x1+avgpool") + (colon == std::string::npos ? ":" + tname(net, nd.out) : st.name.substr(colon));
-                    char kb[96];
-                    snprintf(kb, sizeof kb, "f8::conv1x1_pool_kernel<%d, %s>", nd.ck, st.res_t >= 0 ? "true" : "false");
-                    st.kernel = kb;
                 } else
                 if (opt.wstat && !nd.depthwise && !nd.stem && d.kernel == 1 && d.pad == 0 && d.groups == 1 && !st.dense) {
                     const int k1 = nd.dual >= 0 ? ND[nd.dual].ktot : 0;
@@ -1839,12 +1792,6 @@ static int emit_steps(f8_net* net, int max_batch) {
                             const size_t colon = st.name.find(':');
                             st.name = std::string(nd.dual >= 0 ? "conv1x1_wstat_dual" : has_res ? "conv1x1_wstat_res" : "conv1x1_wstat") +
                                       (colon == std::string::npos ? ":" + tname(net, nd.out) : st.name.substr(colon));
-                            char kb[144];
-                            bool fast = opt.wstat_fast && (!st.relu0 || (nd.dual < 0 && !has_res && st.out.f32 < 0));      // keep in sync with conv1x1_wstat_fast
-                            for (int k = 0; k < 2; ++k) if (st.out.f8[k] >= 0 && T[st.out.t].forms[st.out.f8[k]].n <= 0) fast = false;
-                            snprintf(kb, sizeof kb, "f8::conv1x1_wstat_kernel<%d, %d, %d, %s, %s, %d, %s>", nd.ck, k1, conv1x1_wstat_waves(nd.ck, k1), has_res ? "true" : "false",
-                                     st.out.f32 >= 0 ? "true" : "false", (st.out.f8[0] >= 0 ? 1 : 0) + (st.out.f8[1] >= 0 ? 1 : 0), fast ? "true" : "false");
-                            st.kernel = kb;
                         }
                     }
                 }
@@ -1855,9 +1802,6 @@ static int emit_steps(f8_net* net, int max_batch) {
                     nd.s2w = true;
                     pack_frag_weights(net, nd);
                     st.name = "conv3x3s2_wreg:" + tname(net, nd.out);
-                    char kb[96];
-                    snprintf(kb, sizeof kb, "f8::conv3x3s2_wreg_kernel<%d, %d, %d, %d>", nd.ck, T[nd.out].H, T[nd.out].W, nd.coutP);
-                    st.kernel = kb;
                 }
                 // late, weight-heavy 1x1 convs with int8 outputs only: weights straight to registers (f8_wreg.hip)
                 if (nd.pool < 0 && !nd.wstat && opt.wreg && !nd.depthwise && !nd.stem && d.kernel == 1 && d.stride == 1 && d.pad == 0 && d.groups == 1 && nd.fused_add < 0 &&
@@ -1865,9 +1809,6 @@ static int emit_steps(f8_net* net, int max_batch) {
                     nd.wreg = true;
                     pack_frag_weights(net, nd);
                     st.name = "conv1x1s1_wreg:" + tname(net, nd.out);
-                    char kb[96];
-                    snprintf(kb, sizeof kb, "f8::conv1x1_wreg_kernel<%d, %d>", nd.ck, nd.coutP);
-                    st.kernel = kb;
                 }
                 break;
             }
@@ -1879,7 +1820,7 @@ static int emit_steps(f8_net* net, int max_batch) {
                 st.acc_shl = dfl < 0 ? -dfl : 0; st.res_shl = dfl > 0 ? dfl : 0;
                 st.relu1 = nd.relu;
                 select_outputs(net, nd.out, &st.out, &extra);
-                st.name = "add:" + tname(net, nd.out); st.kernel = "f8::add_kernel";
+                st.name = "add:" + tname(net, nd.out);
                 const double e = (double)T[nd.out].H * T[nd.out].W * T[nd.out].Cs;
                 st.bytes_per_img = e * 8 + (st.out.f32 >= 0 ? e * 4 : 0) + (st.out.f8[0] >= 0 ? e : 0) + (st.out.f8[1] >= 0 ? e : 0);
                 break;
@@ -1893,7 +1834,6 @@ static int emit_steps(f8_net* net, int max_batch) {
                 if (o.forms.empty()) add_form(o, FORM_I32, 0, 0);
                 select_outputs(net, nd.out, &st.out, &extra);
                 st.name = std::string(i8 ? "maxpool_i8:" : "maxpool_i32:") + tname(net, nd.out);
-                st.kernel = (i8 && (s.Cs & 15) == 0 && nd.ppad < nd.pk) ? "f8::maxpool_i8x16_kernel" : "f8::maxpool_kernel";   // keep in sync with launch_maxpool
                 const double ei = (double)s.H * s.W * s.Cs, eo = (double)o.H * o.W * o.Cs;
                 st.bytes_per_img = ei * (i8 ? 1 : 4) + (st.out.f32 >= 0 ? eo * 4 : 0) + (st.out.f8[0] >= 0 ? eo : 0) + (st.out.f8[1] >= 0 ? eo : 0);
                 break;
@@ -1904,7 +1844,7 @@ static int emit_steps(f8_net* net, int max_batch) {
                 st.src_t = nd.a; st.src_f = find_form(s, FORM_I32, 0, 0);
                 if (o.forms.empty()) add_form(o, FORM_I32, 0, 0);
                 select_outputs(net, nd.out, &st.out, &extra);
-                st.name = "avgpool_sum:" + tname(net, nd.out); st.kernel = "f8::avgpool_kernel";
+                st.name = "avgpool_sum:" + tname(net, nd.out);
                 st.bytes_per_img = (double)s.H * s.W * s.Cs * 4 + (double)o.Cs * 5;
                 break;
             }
@@ -1915,19 +1855,16 @@ static int emit_steps(f8_net* net, int max_batch) {
     if (!T[net->out_t].dense_out) {
         Step st; st.kind = S_OUTPUT; st.node = T[net->out_t].prod;
         st.src_t = net->out_t; st.src_f = find_form(T[net->out_t], FORM_I32, 0, 0);
-        st.name = "output:" + tname(net, net->out_t); st.kernel = "f8::output_kernel";
+        st.name = "output:" + tname(net, net->out_t);
         st.bytes_per_img = (double)T[net->out_t].H * T[net->out_t].W * (T[net->out_t].Cs + T[net->out_t].C) * 4;
         net->steps.push_back(st);
     }
 
     for (auto& st : net->steps)
-        if (st.kind == S_INPUT) {      // keep in sync with launch_input
+        if (st.kind == S_INPUT) {
             const Tensor& o = T[st.out.t];
-            bool only_stem = !o.forms.empty();
-            for (auto& F : o.forms) only_stem = only_stem && F.kind == FORM_STEM;
-            if (only_stem && (o.W & 3) == 0 && o.C <= 4) st.kernel = "f8::input_stem4_kernel";
             // the fused stem launch can read the raw input itself: the input step then launches nothing (run_step)
-            if (only_stem && o.C == 3 && net->opt.fuse_input) {
+            if (only_stem_form(o) && o.C == 3 && net->opt.fuse_input) {
                 Step* stem = nullptr; int users = 0;
                 for (auto& s2 : net->steps) if (s2.src_t == st.out.t) { ++users; if (s2.kind == S_STEMPOOL || s2.kind == S_HEAD2) stem = &s2; }
                 if (stem && users == 1) {
@@ -2066,8 +2003,8 @@ static int layout_arena(f8_net* net, int max_batch) {
 
 // ------------------------------------------------------------------------------ bind
 // Fills st.args with every launch argument the plan decides: geometry, magic divisors, consumer formats, ReLU flags, join shifts, the bounds
-// of the float requantisation, output formats; for the chain launches also the instance (chain_fast / bchain_fast) and its symbol.  Weight
-// pointers are set once the weights are on the device (f8_net_upload binds again).  What a run decides is run_step's.
+// of the float requantisation, output formats; chooses the instance the launcher starts (st.inst: the family's *_inst, f8_internal.h) and
+// names it (st.kernel).  Weight pointers are set once the weights are on the device (f8_net_upload binds again).  What a run decides is run_step's.
 static int bind_step(f8_net* net, Step& st) {
     auto& T = net->tensors; auto& ND = net->nodes;
     Node& nd = ND[st.node];
@@ -2086,10 +2023,18 @@ static int bind_step(f8_net* net, Step& st) {
         if (st.out.t < 0 || st.dense) return;
         for (int k = 0; k < 2; ++k) if (st.out.f8[k] >= 0) set_q(q[k], T[st.out.t].forms[st.out.f8[k]]);
     };
-    const bool q8 = st.out.t >= 0 && !st.dense && st.out.f8[0] >= 0;
+    const int nq = (st.out.t >= 0 && !st.dense) ? (st.out.f8[0] >= 0) + (st.out.f8[1] >= 0) : 0;   // int8 output forms: q[0 .. nq - 1] (select_outputs)
+    const bool res = st.res_t >= 0, out32 = st.out.f32 >= 0;
     const int rq_int = !net->opt.requant_float;
+    const Options& opt = net->opt;
+    char kb[192] = "";
     switch (st.kind) {
-        case S_INPUT: break;                              // (the input launch is the run's: run_step)
+        case S_INPUT: {                                   // (its arguments are the run's: run_step)
+            const Tensor& o = T[st.out.t];
+            st.inst = input_inst(o.C, o.W, only_stem_form(o));
+            snprintf(kb, sizeof kb, "%s", input_kernel_name(st.inst));
+            break;
+        }
         case S_CONV: {
             const Tensor& sT = T[st.src_t]; const Form& sF = sT.forms[st.src_f];
             const Tensor& oT = T[nd.out];
@@ -2112,7 +2057,7 @@ static int bind_step(f8_net* net, Step& st) {
                 a.origin = -(d.pad * sT.W + d.pad) * sT.Cs; a.H = sT.H; a.W = sT.W; a.pad = d.pad; a.kw = d.kernel;
                 a.tapH = sT.W * sT.Cs; a.tapW = sT.Cs;
             }
-            a.relu0 = st.relu0; a.deep_nk = net->opt.deep_nk; a.no_fast = net->opt.wstat_fast ? 0 : 1;
+            a.relu0 = st.relu0;
             if (st.res_t >= 0 || nd.dual >= 0) { a.acc_shl = st.acc_shl; a.res_shl = st.res_shl; a.relu1 = st.relu1; }
             if (nd.dual >= 0) {
                 const Node& g = ND[nd.dual];
@@ -2121,11 +2066,19 @@ static int bind_step(f8_net* net, Step& st) {
                 a.bias2 = B32(g.b_off);
                 a.sN2 = s2.H * s2.W * s2.Cs; a.sP2 = g.cd.stride * s2.W * s2.Cs; a.sQ2 = g.cd.stride * s2.Cs; a.ktot2 = g.ktot;
             }
-            // the kernels that read the fragment-order weight image (run_step picks the launcher in the same order)
+            // the kernels that read the fragment-order weight image
             const bool frag = st.dense || nd.pool >= 0 || nd.s2w;
             if (frag || nd.wstat || nd.wreg) a.w = W8(nd.wf_off);
             if (!frag && nd.wstat && nd.dual >= 0) a.w2 = W8(ND[nd.dual].wf_off);
-            out_formats(a.q); st.args = a; break;
+            out_formats(a.q);
+            if (st.dense) fc_dense_kernel_name(kb, sizeof kb, a);           // (run_step: the same order)
+            else if (nd.pool >= 0) conv1x1_pool_kernel_name(kb, sizeof kb, a, res);
+            else if (nd.s2w) conv3x3s2_wreg_kernel_name(kb, sizeof kb, a);
+            else if (nd.wstat) conv1x1_wstat_kernel_name(kb, sizeof kb, a, st.inst = conv1x1_wstat_inst(a, res, out32, nq, opt.wstat_fast));
+            else if (nd.wreg) conv1x1_wreg_kernel_name(kb, sizeof kb, a);
+            else if (nd.p3_R > 0) conv3x3_patch_kernel_name(kb, sizeof kb, d.cin, a.W, res);
+            else conv_kernel_name(kb, sizeof kb, a, nd.tile, st.inst = conv_inst(a, nd.tile, res, nd.dual >= 0, opt.deep_nk));
+            st.args = a; break;
         }
         case S_HEAD2: case S_STEMPOOL: {
             const bool h2 = st.kind == S_HEAD2;
@@ -2150,9 +2103,12 @@ static int bind_step(f8_net* net, Step& st) {
             } else {
                 const Tensor& cT = T[nd.out]; const Tensor& oT = T[ND[nd.sp_pool].out];
                 a.Pc = cT.H; a.Qc = cT.W; a.P = oT.H; a.Q = oT.W;
-                a.relu0 = st.relu0; a.rows = net->opt.stem_rows;
+                a.relu0 = st.relu0;
                 a.acc_ok = conv_acc_bounded(nd); a.rq_int = rq_int;
             }
+            StemPoolArgs g = a; g.rH = sT.H; g.rW = sT.W;      // (the raw input's sides: run_step binds them where the launch reads it)
+            st.inst = stem_pool_inst(g, opt.stem_rows, st.raw_input);
+            snprintf(kb, sizeof kb, "%s", stem_pool_kernel_name(st.inst));
             out_formats(a.q); st.args = a; break;
         }
         case S_FUSED: {
@@ -2166,7 +2122,7 @@ static int bind_step(f8_net* net, Step& st) {
             a.b0 = B32(na.b_off); a.b2 = B32(nb.b_off); a.b4 = B32(ng.b_off);
             if (ds) {
                 a.wsc = W8(nd.w_off); a.wsc_bytes = (uint32_t)((size_t)nd.coutP * nd.ktot); a.bsc = B32(nd.b_off);
-                a.COUT = nd.cd.cout; a.stride2 = nd.fbd_s2 ? 1 : 0; a.stg = net->opt.opener_stg;
+                a.COUT = nd.cd.cout; a.stride2 = nd.fbd_s2 ? 1 : 0;
             }
             a.H = x.H; a.W = x.W; a.C = na.cd.cin; a.MID = na.cd.cout; a.R = nd.fb_R;
             a.tiles_per_img = (ds && nd.fbd_s2) ? (x.H / 2) / nd.fb_R : (x.H + nd.fb_R - 1) / nd.fb_R;
@@ -2174,7 +2130,10 @@ static int bind_step(f8_net* net, Step& st) {
             fmt(ng, &a.n2, &a.lo2, &a.hi2, &a.xor2);
             a.relu_a = na.cd.relu; a.relu_b = nb.cd.relu;
             a.acc_shl = st.acc_shl; a.res_shl = st.res_shl; a.relu1 = st.relu1;
-            out_formats(a.q); st.args = a; break;
+            out_formats(a.q);
+            if (ds && nd.fbd_s2) fused_opener_kernel_name(kb, sizeof kb, a, st.inst = fused_opener_inst(a, opt.opener_stg));
+            else fused_bottleneck_kernel_name(kb, sizeof kb, a);
+            st.args = a; break;
         }
         case S_P12: {
             Node& na = ND[nd.p12_a];
@@ -2193,7 +2152,8 @@ static int bind_step(f8_net* net, Step& st) {
                 a.tiles_per_img = (x.H / 2 + nd.fb_R - 1) / nd.fb_R;
                 a.n2 = a.q[0].n; a.lo2 = a.q[0].lo; a.hi2 = a.q[0].hi; a.xor2 = a.q[0].bias_xor;      // mid2's one form = body.4's input format
                 a.stride2 = 1; a.p12only = 1; a.acc_ok = conv_acc_bounded(na) && conv_acc_bounded(nd); a.rq_int = rq_int;
-            }
+                fused_opener_kernel_name(kb, sizeof kb, a, st.inst = fused_opener_inst(a, opt.opener_stg));
+            } else fused_p12_kernel_name(kb, sizeof kb, a);
             st.args = a; break;
         }
         case S_CHAIN: {
@@ -2244,10 +2204,8 @@ static int bind_step(f8_net* net, Step& st) {
             st.tiles = (st.H + a.R - 1) / a.R;
             st.cluster = (!ds || tail) && cchain_supported(st.C, st.MID, st.H, st.W, st.cin0, tail);   // the 7x7 stage: clusters of eight workgroups
             out_formats(a.q);
-            st.fast = chain_fast(a, shortcut_blocks, q8);
-            char kb[160];
-            chain_kernel_name(kb, sizeof kb, st.C, st.MID, st.H, st.W, st.cin0, tail, st.fast);
-            st.kernel = kb;
+            st.inst = chain_fast(a, shortcut_blocks, nq > 0);
+            chain_kernel_name(kb, sizeof kb, st.C, st.MID, st.H, st.W, st.cin0, tail, st.inst);
             st.args = a; break;
         }
         case S_BCHAIN: {
@@ -2277,10 +2235,8 @@ static int bind_step(f8_net* net, Step& st) {
             st.C = x.C; st.H = x.H; st.W = x.W;
             st.tiles = bchain_tiles_per_img(x.C, x.H, x.W);
             out_formats(a.q);
-            st.fast = bchain_fast(a, ds, q8);
-            char kb[160];
-            bchain_kernel_name(kb, sizeof kb, st.C, st.H, st.W, ds, st.fast);
-            st.kernel = kb;
+            st.inst = bchain_fast(a, ds, nq > 0);
+            bchain_kernel_name(kb, sizeof kb, st.C, st.H, st.W, ds, st.inst);
             st.args = a; break;
         }
         case S_IR: {
@@ -2302,6 +2258,7 @@ static int bind_step(f8_net* net, Step& st) {
             make_magic((uint32_t)(x.H * x.W), &a.mHW, &a.s1HW, &a.s2HW);
             make_magic((uint32_t)oT.W, &a.mWo, &a.s1Wo, &a.s2Wo);
             make_magic((uint32_t)(nd.ir_R * oT.W), &a.mRWo, &a.s1RWo, &a.s2RWo);
+            fused_ir_kernel_name(kb, sizeof kb, x.Cs, nd.coutP, st.inst = fused_ir_inst(a, nd.coutP));
             out_formats(a.q); st.args = a; break;
         }
         case S_DW: {
@@ -2311,12 +2268,16 @@ static int bind_step(f8_net* net, Step& st) {
             a.w = W8(nd.w_off); a.bias = B32(nd.b_off);
             a.w4 = W8(nd.rc_off); a.bias4 = B32(nd.cc_off);
             a.H = sT.H; a.W = sT.W; a.P = oT.H; a.Q = oT.W; a.Cs = sT.Cs; a.stride = nd.cd.stride; a.pad = nd.cd.pad;
-            a.in_signed = nd.cd.input_signed; a.relu0 = st.relu0; a.use_dot4 = net->opt.dw_dot4; a.use_mma = net->opt.dw_mma; a.acc_ok = conv_acc_bounded(nd); a.rq_int = rq_int;
-            out_formats(a.q); st.args = a; break;
+            a.in_signed = nd.cd.input_signed; a.relu0 = st.relu0; a.acc_ok = conv_acc_bounded(nd); a.rq_int = rq_int;
+            out_formats(a.q);
+            st.inst = dwconv_inst(a, out32, nq, opt.dw_mma, opt.dw_dot4, net->max_batch);     // (the MMA kernel's index bound at the largest launch)
+            dwconv_kernel_name(kb, sizeof kb, a, st.inst);
+            st.args = a; break;
         }
         case S_ADD: case S_REQUANT: {
             AddArgs a{};
             a.Cs = T[st.src_t].Cs; a.a_shl = st.acc_shl; a.b_shl = st.res_shl; a.relu = st.relu1;
+            snprintf(kb, sizeof kb, "%s", add_kernel_name());
             out_formats(a.q); st.args = a; break;
         }
         case S_MAXPOOL: {
@@ -2325,21 +2286,25 @@ static int bind_step(f8_net* net, Step& st) {
             PoolArgs a{};
             a.in_is_i8 = sF.kind == FORM_I8; a.in_signed = sF.sgn;
             a.H = sT.H; a.W = sT.W; a.P = oT.H; a.Q = oT.W; a.Cs = sT.Cs; a.k = nd.pk; a.stride = nd.pstride; a.pad = nd.ppad;
+            snprintf(kb, sizeof kb, "%s", maxpool_kernel_name(st.inst = maxpool_inst(a)));
             out_formats(a.q); st.args = a; break;
         }
         case S_AVGPOOL: {
             const Tensor& sT = T[st.src_t];
             AvgArgs a{};
             a.HW = sT.H * sT.W; a.Cs = sT.Cs;
+            snprintf(kb, sizeof kb, "%s", avgpool_kernel_name());
             out_formats(a.q); st.args = a; break;
         }
         case S_OUTPUT: {
             const Tensor& sT = T[st.src_t];
             OutArgs a{};
             a.C = sT.C; a.HW = sT.H * sT.W; a.Cs = sT.Cs; a.as_float = net->out_float;
+            snprintf(kb, sizeof kb, "%s", output_kernel_name());
             st.args = a; break;
         }
     }
+    st.kernel = kb;
     return rc;
 }
 
@@ -2362,9 +2327,9 @@ int f8_net_finalize(f8_net* net, int max_batch) {
     int rc = emit_steps(net, max_batch);            // 3:  the launches, packed weights, algorithmic bytes / ops
     if (rc) return rc;
     if ((rc = layout_arena(net, max_batch))) return rc;   // 4: lifetimes, first-fit arena
-    for (Step& st : net->steps)                           // 5: the launch arguments the plan decides
-        if ((rc = bind_step(net, st))) return rc;
     net->max_batch = max_batch;
+    for (Step& st : net->steps)                           // 5: the launch arguments the plan decides, the instances
+        if ((rc = bind_step(net, st))) return rc;
     net->finalized = true;
     return F8_OK;
 }
@@ -2533,7 +2498,7 @@ static int run_step(const f8_net* net, const Step& st, const int32_t* input, voi
                     a.err = net->d_err; a.chk_lo = F.sgn ? -127 : 0; a.chk_hi = F.sgn ? 127 : 255;
                 }
             }
-            e = launch_input(a, s);
+            e = launch_input(a, st.inst, s);
             break;
         }
         case S_CONV: {
@@ -2548,9 +2513,9 @@ static int run_step(const f8_net* net, const Step& st, const int32_t* input, voi
                 e = launch_fc_dense(a, (char*)output + (size_t)n0 * C * 4, C, net->out_float, chain_err, net->epoch, s);
             } else if (nd.pool >= 0) e = launch_conv1x1_pool(a, s);
             else if (nd.s2w) e = launch_conv3x3s2_wreg(a, s);
-            else if (nd.wstat) e = launch_conv1x1_wstat(a, net->num_cu, s);
+            else if (nd.wstat) e = launch_conv1x1_wstat(a, st.inst, net->num_cu, s);
             else if (nd.wreg) e = launch_conv1x1_wreg(a, s);
-            else e = nd.p3_R > 0 ? launch_conv3x3_patch(a, nd.cd.cin, s) : launch_conv(a, nd.tile, s);
+            else e = nd.p3_R > 0 ? launch_conv3x3_patch(a, nd.cd.cin, s) : launch_conv(a, nd.tile, st.inst, s);
             break;
         }
         case S_HEAD2: case S_STEMPOOL: {
@@ -2570,7 +2535,7 @@ static int run_step(const f8_net* net, const Step& st, const int32_t* input, voi
                 }
             }
             fill_out(&a.out32, a.q);
-            e = launch_stem_pool(a, s);
+            e = launch_stem_pool(a, st.inst, s);
             break;
         }
         case S_FUSED: case S_P12: {
@@ -2579,8 +2544,8 @@ static int run_step(const f8_net* net, const Step& st, const int32_t* input, voi
             a.x8 = (const int8_t*)fp(xF); a.x_bytes = (uint32_t)(xF.bytes_per_img * N); a.N = N;
             if (st.kind == S_FUSED && nd.fbd_a < 0) a.xr = (const int32_t*)fp(T[st.res_t].forms[st.res_f]);
             fill_out(&a.out32, a.q);
-            if (st.kind == S_P12) e = nd.p12_s2 ? launch_fused_opener(a, s) : launch_fused_p12(a, s);
-            else e = (nd.fbd_a >= 0 && nd.fbd_s2) ? launch_fused_opener(a, s) : launch_fused_bottleneck(a, s);
+            if (st.kind == S_P12) e = nd.p12_s2 ? launch_fused_opener(a, st.inst, s) : launch_fused_p12(a, s);
+            else e = (nd.fbd_a >= 0 && nd.fbd_s2) ? launch_fused_opener(a, st.inst, s) : launch_fused_bottleneck(a, s);
             break;
         }
         case S_CHAIN: {
@@ -2592,7 +2557,7 @@ static int run_step(const f8_net* net, const Step& st, const int32_t* input, voi
             if ((a.NG = chain_launch_groups(net, st, N)) < 1) return F8_ERR_STATE;
             fill_out(&a.out32, a.q);
             if (const int rc = chain_scratch(a)) return rc;
-            e = launch_chain(a, st.fast, st.C, st.MID, st.H, st.W, st.cin0, s);
+            e = launch_chain(a, st.inst, st.C, st.MID, st.H, st.W, st.cin0, s);
             break;
         }
         case S_BCHAIN: {
@@ -2604,7 +2569,7 @@ static int run_step(const f8_net* net, const Step& st, const int32_t* input, voi
             if ((a.NG = chain_launch_groups(net, st, N)) < 1) return F8_ERR_STATE;
             fill_out(&a.out32, a.q);
             if (const int rc = chain_scratch(a)) return rc;
-            e = launch_bchain(a, st.fast, st.C, st.H, st.W, s);
+            e = launch_bchain(a, st.inst, st.C, st.H, st.W, s);
             break;
         }
         case S_IR: {
@@ -2613,14 +2578,14 @@ static int run_step(const f8_net* net, const Step& st, const int32_t* input, voi
             a.x8 = (const int8_t*)fp(x.forms[st.src_f]); a.N = N;
             if (st.res_t >= 0) a.xr = (const int32_t*)fp(T[st.res_t].forms[st.res_f]);
             fill_out(&a.out32, a.q);
-            e = launch_fused_ir(a, x.Cs, nd.coutP, s);
+            e = launch_fused_ir(a, x.Cs, nd.coutP, st.inst, s);
             break;
         }
         case S_DW: {
             DwArgs a = std::get<DwArgs>(st.args);
             a.x = (const int8_t*)fp(T[st.src_t].forms[st.src_f]); a.N = N;
             fill_out(&a.out32, a.q);
-            e = launch_dwconv(a, s);
+            e = launch_dwconv(a, st.inst, s);
             break;
         }
         case S_ADD: case S_REQUANT: {
@@ -2637,7 +2602,7 @@ static int run_step(const f8_net* net, const Step& st, const int32_t* input, voi
             PoolArgs a = std::get<PoolArgs>(st.args);
             a.x = fp(T[st.src_t].forms[st.src_f]); a.N = N;
             fill_out(&a.out32, a.q);
-            e = launch_maxpool(a, s);
+            e = launch_maxpool(a, st.inst, s);
             break;
         }
         case S_AVGPOOL: {
@@ -2680,7 +2645,7 @@ int f8_net_autotune(f8_net* net, int N, void* stream) {
     for (auto& st : net->steps) {
         if (st.kind != S_CONV) continue;
         Node& nd = net->nodes[st.node];
-        if (nd.p3_R > 0 || nd.wreg || nd.wstat || nd.s2w || st.dense) continue;
+        if (nd.p3_R > 0 || nd.wreg || nd.wstat || nd.s2w || st.dense || nd.pool >= 0) continue;     // (conv_igemm_kernel steps only)
         const ConvTile keep = nd.tile;
         ConvTile best = keep; float best_ms = 1e30f;
         for (int c = 0; c < 4; ++c) {
@@ -2689,6 +2654,7 @@ int f8_net_autotune(f8_net* net, int N, void* stream) {
             if (nd.dual >= 0 && !(t.bn == 64 || (t.bn == 128 && t.bm == 128))) continue;     // dual-GEMM instances
             if (t.bm == 64 && t.bn == 32) continue;
             nd.tile = t;
+            (void)bind_step(net, st);                                  // the instance follows the tile (ring depth)
             if (run_step(net, st, nullptr, nullptr, 0, n_launch, 0, 0, s) != F8_OK) { (void)hipGetLastError(); continue; }   // no instance
             float ms_min = 1e30f;
             for (int rep = 0; rep < 3; ++rep) {
@@ -2703,6 +2669,7 @@ int f8_net_autotune(f8_net* net, int N, void* stream) {
             if (ms_min * bias < best_ms) { best_ms = ms_min * bias; best = t; }
         }
         nd.tile = best;
+        (void)bind_step(net, st);
         if (best.bm != keep.bm || best.bn != keep.bn) { ++changed; label_conv_step(net, st, nd); }
     }
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);

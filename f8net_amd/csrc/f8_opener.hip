@@ -528,22 +528,32 @@ static hipError_t launch_opener_t(const FusedArgs& a, hipStream_t s) {
 #endif
 }
 
-hipError_t launch_fused_opener(const FusedArgs& a, hipStream_t s) {
-    const int stg = a.stg;
-    if (a.C == 256 && a.MID == 128 && a.COUT == 512 && a.W == 56 && a.R == 4) {
-        if (a.p12only) {
-            if (!(a.q[0].ptr && !a.q[1].ptr && !a.out32)) return hipErrorInvalidValue;
-            // FQ: ReLU -> unsigned 8-bit right shifts after both convs (1: float converter where it is provably exact, 2: integer form)
-            const bool fqf = a.relu_a && a.relu_b && a.n1 > 0 && a.n2 > 0 && a.n1 <= 30 && a.n2 <= 30 && a.lo1 == 0 && a.lo2 == 0 && a.hi1 == 255 && a.hi2 == 255 &&
-                             a.xor1 == 0x80808080u && a.xor2 == 0x80808080u;
+// The full block: STG (int8 output staged through LDS, Options::opener_stg).  The P12 form (p12only): FQ, ReLU -> unsigned 8-bit right shifts
+// after both convs (1: float converter where it is provably exact, 2: integer form, 0: the general epilogues).
+int fused_opener_inst(const FusedArgs& a, bool stg) {
+    if (!a.p12only) return stg ? 1 : 0;
+    const bool fqf = a.relu_a && a.relu_b && a.n1 > 0 && a.n2 > 0 && a.n1 <= 30 && a.n2 <= 30 && a.lo1 == 0 && a.lo2 == 0 && a.hi1 == 255 && a.hi2 == 255 &&
+                     a.xor1 == 0x80808080u && a.xor2 == 0x80808080u;
 #ifndef F8_OPENER_FQ
 #define F8_OPENER_FQ 1             // 0 (tuning builds): the general epilogues
 #endif
-            const int fq = (!fqf || !F8_OPENER_FQ) ? 0 : ((a.rq_int || !a.acc_ok || a.n1 > kRequantU8MaxShift || a.n2 > kRequantU8MaxShift) ? 2 : 1);
+    return (!fqf || !F8_OPENER_FQ) ? 0 : ((a.rq_int || !a.acc_ok || a.n1 > kRequantU8MaxShift || a.n2 > kRequantU8MaxShift) ? 2 : 1);
+}
+
+int fused_opener_kernel_name(char* buf, size_t cap, const FusedArgs& a, int inst) {
+    return snprintf(buf, cap, "f8::fused_opener_kernel<%d, %d, %d, %d, %d, %s, %s, %d>", a.C, a.MID, a.W, a.R, a.COUT, !a.p12only && inst ? "true" : "false",
+                    a.p12only ? "true" : "false", a.p12only ? inst : 0);
+}
+
+hipError_t launch_fused_opener(const FusedArgs& a, int inst, hipStream_t s) {
+    if (a.C == 256 && a.MID == 128 && a.COUT == 512 && a.W == 56 && a.R == 4) {
+        if (a.p12only) {
+            if (!(a.q[0].ptr && !a.q[1].ptr && !a.out32)) return hipErrorInvalidValue;
+            const int fq = inst;
             return fq == 1 ? launch_opener_t<256, 128, 56, 4, 512, false, true, 1>(a, s) : fq == 2 ? launch_opener_t<256, 128, 56, 4, 512, false, true, 2>(a, s)
                                                                                                : launch_opener_t<256, 128, 56, 4, 512, false, true, 0>(a, s);
         }
-        return stg ? launch_opener_t<256, 128, 56, 4, 512, true>(a, s) : launch_opener_t<256, 128, 56, 4, 512, false>(a, s);
+        return inst ? launch_opener_t<256, 128, 56, 4, 512, true>(a, s) : launch_opener_t<256, 128, 56, 4, 512, false>(a, s);
     }
     return hipErrorInvalidValue;
 }

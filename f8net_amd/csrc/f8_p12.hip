@@ -288,6 +288,8 @@ fused_p12_kernel(const FusedArgs a) {
 
 bool fused_p12_supported(int C, int MID, int H, int W) { return C == 2048 && MID == 512 && H == 7 && W == 7; }
 
+int fused_p12_kernel_name(char* buf, size_t cap, const FusedArgs& a) { return snprintf(buf, cap, "f8::fused_p12_kernel<%d, %d>", a.C, a.MID); }
+
 hipError_t launch_fused_p12(const FusedArgs& a, hipStream_t s) {
     if (!fused_p12_supported(a.C, a.MID, a.H, a.W)) return hipErrorInvalidValue;
     using Cfg = P12Cfg<2048, 512>;

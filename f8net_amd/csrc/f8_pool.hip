@@ -145,6 +145,10 @@ static hipError_t launch_pool_t(const ConvArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
+int conv1x1_pool_kernel_name(char* buf, size_t cap, const ConvArgs& a, bool res) {
+    return snprintf(buf, cap, "f8::conv1x1_pool_kernel<%d, %s>", a.CK, res ? "true" : "false");
+}
+
 hipError_t launch_conv1x1_pool(const ConvArgs& a, hipStream_t s) {
     if (!conv1x1_pool_supported(a.CK, a.coutP, a.PQ) || a.M % a.PQ) return hipErrorInvalidValue;
     const bool res = a.res != nullptr;

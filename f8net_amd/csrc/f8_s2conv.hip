@@ -201,6 +201,10 @@ static hipError_t launch_s2_t(const ConvArgs& a, int N, hipStream_t s) {
     return hipGetLastError();
 }
 
+int conv3x3s2_wreg_kernel_name(char* buf, size_t cap, const ConvArgs& a) {
+    return snprintf(buf, cap, "f8::conv3x3s2_wreg_kernel<%d, %d, %d, %d>", a.CK, a.PQ / a.Q, a.Q, a.coutP);
+}
+
 hipError_t launch_conv3x3s2_wreg(const ConvArgs& a, hipStream_t s) {
     const int HO = a.PQ / a.Q, N = a.M / a.PQ;
     if (a.out32 || a.res || a.x2) return hipErrorInvalidValue;

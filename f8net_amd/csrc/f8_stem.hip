@@ -702,11 +702,17 @@ __global__ void __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3, 3))
 }
 
 // instances of the row-walking kernel: pooled width <= 56 (two strips), any height; a haloed form must carry 5 halo pixels
-static bool stem_rows_ok(const StemPoolArgs& a) {
+static bool stem_rows_ok(const StemPoolArgs& a, bool raw) {
     if (a.Q < 2 || a.Q > 2 * SW || a.P < 1 || a.Qc != 2 * a.Q || a.Pc != 2 * a.P) return false;
-    if (a.raw_kind < 0) return a.org == 2 && a.Wp % 4 == 0;
+    if (!raw) return a.org == 2 && a.Wp % 4 == 0;
     return a.rW == 2 * a.Qc && a.rH == 2 * a.Pc;
 }
+
+// 2: the MobileNet-V2 head; 1: the row-walking kernel (Options::stem_rows) where it has an instance for the form the plan reads (raw: the
+// raw network input, whose sides rW, rH the plan binds; a run that reads the haloed copy instead has one too: stem_rows_ok); 0: the tile kernel
+int stem_pool_inst(const StemPoolArgs& a, bool rows, bool raw) { return a.h2 ? 2 : (rows && stem_rows_ok(a, raw)) ? 1 : 0; }
+// both kernels' first template argument is the kind of the run's raw input (int32, fp32, uint8, or -1: the haloed form): named without arguments
+const char* stem_pool_kernel_name(int inst) { return inst ? "f8::stem_rows_kernel" : "f8::stem_pool_kernel"; }
 
 bool stem_pool_supported(int cin, int cout, int k, int stride, int pad, int pool_k, int pool_s, int pool_p, int P, int Q, int rows, int H, int W) {
     if (!(cin <= 4 && cout == 64 && k == 7 && stride == 2 && pad == 3 && pool_k == 3 && pool_s == 2 && pool_p == 1 && P > 0 && Q > 0)) return false;
@@ -726,8 +732,9 @@ static int device_cus() {
     return cus[dev];
 }
 
-hipError_t launch_stem_pool(const StemPoolArgs& a, hipStream_t s) {
-    if (a.h2) {
+hipError_t launch_stem_pool(const StemPoolArgs& a, int inst, hipStream_t s) {
+    if ((inst == 2) != (a.h2 != 0)) return hipErrorInvalidValue;
+    if (inst == 2) {
         if (!head2_supported(a.rH, a.rW) || a.P != a.rH / 2 || a.Q != a.rW / 2 || a.Pc != a.P || a.Qc != a.Q || a.na < 1 || a.nb < 1 || a.na > kRequantU8MaxShift || a.nb > kRequantU8MaxShift || (!a.acc_ok && !a.rq_int) || a.out32 ||
             (a.raw_kind < 0 && !(a.org == 4 && a.Wp % 4 == 0))) return hipErrorInvalidValue;
         const int lds_bytes = 2 * RB_ROWS * (a.rW + 8) * 4 + 512 + 1536;
@@ -744,7 +751,8 @@ hipError_t launch_stem_pool(const StemPoolArgs& a, hipStream_t s) {
         }
         return hipGetLastError();
     }
-    if (a.rows && stem_rows_ok(a)) {
+    if (inst == 1) {
+        if (!stem_rows_ok(a, a.raw_kind >= 0)) return hipErrorInvalidValue;
         const int lds_bytes = 2 * RB_ROWS * (4 * a.Q + 8) * 4 + 512 + 1536;   // 67 KB at 224 x 224: patches, biases, the u8 table
         const int ncu2 = device_cus();
         const int ntiles = a.N * ((a.P + RB - 1) / RB);

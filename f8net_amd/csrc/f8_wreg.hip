@@ -130,6 +130,8 @@ __global__ void __launch_bounds__(512) conv1x1_wreg_kernel(const ConvArgs a) {
 // 1x1 / stride 1 / no padding, K = cin bytes, int8 outputs only: the instances
 bool conv1x1_wreg_supported(int ck, int coutP) { return (ck == 512 && coutP == 256) || (ck == 1024 && coutP == 512); }
 
+int conv1x1_wreg_kernel_name(char* buf, size_t cap, const ConvArgs& a) { return snprintf(buf, cap, "f8::conv1x1_wreg_kernel<%d, %d>", a.CK, a.coutP); }
+
 hipError_t launch_conv1x1_wreg(const ConvArgs& a, hipStream_t s) {
     const int grid = (a.M + 63) / 64;
     if (a.CK == 512 && a.coutP == 256) { hipLaunchKernelGGL((conv1x1_wreg_kernel<512, 256>), dim3(grid), dim3(512), 0, s, a); return hipGetLastError(); }

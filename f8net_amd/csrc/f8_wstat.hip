@@ -431,29 +431,38 @@ static hipError_t launch_wstat_o(const ConvArgs& a, int num_cu, hipStream_t s) {
     if (nq == 2) return launch_wstat_t<K0, K1, NW, RES, false, 2, FAST>(a, num_cu, s);
     return hipErrorInvalidValue;
 }
+enum { kWstatFast = 1, kWstatRes = 2, kWstatOut32 = 4 };      // | nq << 3
 // FAST epilogue: every int8 output shifts right (the usual case: 4-operation requantisation) and the ReLU behind the conv is either
 // absent or can ride in the clamp's lower bound (no int32 output, no join: requant is monotonic and maps 0 to 0, so
-// requant(max(v, 0)) = max(requant(v), 0))
-bool conv1x1_wstat_fast(const ConvArgs& a) {
-    if (a.no_fast) return false;
-    for (int k = 0; k < 2; ++k) if (a.q[k].ptr && a.q[k].n <= 0) return false;
-    const bool join = a.res != nullptr || a.x2 != nullptr;
-    return !a.relu0 || (!join && !a.out32);
-}
-template <int K0, int K1, int NW, bool RES>
-static hipError_t launch_wstat_f(const ConvArgs& a, int num_cu, hipStream_t s) {
-    return conv1x1_wstat_fast(a) ? launch_wstat_o<K0, K1, NW, RES, true>(a, num_cu, s) : launch_wstat_o<K0, K1, NW, RES, false>(a, num_cu, s);
+// requant(max(v, 0)) = max(requant(v), 0)); fast = 0 (Options::wstat_fast): always the general epilogue
+int conv1x1_wstat_inst(const ConvArgs& a, bool res, bool out32, int nq, bool fast) {
+    for (int k = 0; k < nq; ++k) if (a.q[k].n <= 0) fast = false;
+    const bool join = res || a.ktot2 > 0;
+    fast = fast && (!a.relu0 || (!join && !out32));
+    return (fast ? kWstatFast : 0) | (res ? kWstatRes : 0) | (out32 ? kWstatOut32 : 0) | nq << 3;
 }
 
-hipError_t launch_conv1x1_wstat(const ConvArgs& a, int num_cu, hipStream_t s) {
+int conv1x1_wstat_kernel_name(char* buf, size_t cap, const ConvArgs& a, int inst) {
+    return snprintf(buf, cap, "f8::conv1x1_wstat_kernel<%d, %d, %d, %s, %s, %d, %s>", a.CK, a.ktot2, conv1x1_wstat_waves(a.CK, a.ktot2), inst & kWstatRes ? "true" : "false",
+                    inst & kWstatOut32 ? "true" : "false", inst >> 3, inst & kWstatFast ? "true" : "false");
+}
+
+template <int K0, int K1, int NW, bool RES>
+static hipError_t launch_wstat_f(const ConvArgs& a, int inst, int num_cu, hipStream_t s) {
+    return inst & kWstatFast ? launch_wstat_o<K0, K1, NW, RES, true>(a, num_cu, s) : launch_wstat_o<K0, K1, NW, RES, false>(a, num_cu, s);
+}
+
+hipError_t launch_conv1x1_wstat(const ConvArgs& a, int inst, int num_cu, hipStream_t s) {
     const bool res = a.res != nullptr;
     const int k1 = a.x2 ? a.ktot2 : 0;
+    if (res != ((inst & kWstatRes) != 0) || (a.out32 != nullptr) != ((inst & kWstatOut32) != 0) || (a.q[0].ptr ? 1 : 0) + (a.q[1].ptr ? 1 : 0) != inst >> 3)
+        return hipErrorInvalidValue;
     if (num_cu <= 0) num_cu = 256;
-    if (k1 == 0 && !res && a.CK == 512) return launch_wstat_f<512, 0, 8, false>(a, num_cu, s);
-    if (k1 == 0 && !res && a.CK == 1024) return launch_wstat_f<1024, 0, 8, false>(a, num_cu, s);
-    if (k1 == 0 && res && a.CK == 512) return launch_wstat_f<512, 0, 8, true>(a, num_cu, s);
-    if (a.CK == 512 && k1 == 256) return launch_wstat_f<512, 256, 8, false>(a, num_cu, s);
-    if (a.CK == 1024 && k1 == 512) return launch_wstat_f<1024, 512, 4, false>(a, num_cu, s);
+    if (k1 == 0 && !res && a.CK == 512) return launch_wstat_f<512, 0, 8, false>(a, inst, num_cu, s);
+    if (k1 == 0 && !res && a.CK == 1024) return launch_wstat_f<1024, 0, 8, false>(a, inst, num_cu, s);
+    if (k1 == 0 && res && a.CK == 512) return launch_wstat_f<512, 0, 8, true>(a, inst, num_cu, s);
+    if (a.CK == 512 && k1 == 256) return launch_wstat_f<512, 256, 8, false>(a, inst, num_cu, s);
+    if (a.CK == 1024 && k1 == 512) return launch_wstat_f<1024, 512, 4, false>(a, inst, num_cu, s);
     return hipErrorInvalidValue;
 }
 

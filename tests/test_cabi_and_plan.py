@@ -278,6 +278,9 @@ def test_tail_chain_is_planned_only_for_an_input_map_of_exactly_twice_the_output
     assert '_tail:' not in plan, plan
 
 
+RUN_TIME_KIND_KERNELS = ('f8::input_stem4_kernel', 'f8::stem_rows_kernel', 'f8::stem_pool_kernel')
+
+
 def test_every_planned_kernel_name_is_a_symbol_of_the_library():
     """`launch_kernel(i)` is the device symbol as rocprofv3 prints it: bench.py joins its live timings with the stamped counter files of profiles/ on that
     string.  A template parameter added to a kernel without its name string following (round 4: bchain_kernel's wave count) silently detaches the
@@ -298,9 +301,32 @@ def test_every_planned_kernel_name_is_a_symbol_of_the_library():
                 k = net.launch_kernel(i)
                 if not k:
                     continue
-                # a name without template arguments stands for a family whose instance is picked at run time (input / output kernels)
-                ok = k in have if '<' in k else any(h == k or h.startswith(k + '<') for h in have)
+                # named without template arguments: the families whose first template argument is the kind of the run's raw input
+                ok = k in have or (k in RUN_TIME_KIND_KERNELS and any(h.startswith(k + '<') for h in have))
                 assert ok, f'{arch} {opts}: launch {i} ({net.launch_info(i, 128)[0]}) names {k!r}, which the library does not define'
+
+
+def test_planned_kernel_is_the_instance_the_launcher_selects():
+    """Every launch's instance is selected once, by its family's *_inst function when the plan is bound, and named by the *_kernel_name next to
+    the dispatch.  Two cases where the planner's own copy of the launchers' rules used to name another instance than the one that ran: the
+    depthwise convs with both fast kernels off run the generic kernel, and the P12 form of the stride-2 opener runs its integer instance (2) under
+    requant_float = 1 when an accumulator it requantises cannot be bounded."""
+    mv2 = topology.get('mobilenet_v2')
+    net = build_net(mv2, synth.reference_params(mv2), max_batch=8, hw=224, options={'dw_dot4': 0, 'dw_mma': 0})
+    dw = [net.launch_kernel(i) for i in range(net.num_launches) if net.launch_info(i, 1)[0].startswith('dwconv3x3')]
+    assert dw and all(re.fullmatch(r'f8::dwconv3x3_kernel<(true|false)>', k) for k in dw), dw
+    r50 = topology.get('resnet50', normalize=True)
+    p = synth.reference_params(r50)
+    def opener_p12(params):
+        net = build_net(r50, params, max_batch=8, hw=224, options={'requant_float': 1})
+        ks = [net.launch_kernel(i) for i in range(net.num_launches) if net.launch_info(i, 1)[0].startswith('fused_opener_s2_p12')]
+        assert len(ks) == 1, ks
+        return ks[0]
+    assert opener_p12(p) == 'f8::fused_opener_kernel<256, 128, 56, 4, 512, false, true, 1>'
+    for conv in ('body.0', 'body.2'):
+        q = {k: (v.copy() if hasattr(v, 'copy') else v) for k, v in p.items()}
+        q[f'stage_1_layer_0.{conv}.bias'][5] = 2 ** 31 - 2 ** 18      # (see the test below) that conv's accumulators are no longer bounded
+        assert opener_p12(q) == 'f8::fused_opener_kernel<256, 128, 56, 4, 512, false, true, 2>', conv
 
 
 def test_planner_bounds_the_residual_stream_before_it_plans_the_float_requantisation():

@@ -1,6 +1,7 @@
 """GPU parity, whole networks: fused HIP plan vs golden fixtures captured from the reference, vs the
 CPU oracle on fresh seeds, and vs our own op-level path.  Bit-exact (integer arithmetic)."""
 import os
+import re
 
 import numpy as np
 import pytest
@@ -241,6 +242,21 @@ def test_autotuned_plan_is_bit_identical(dev, golden_dir):
     before = net.describe()
     changed = net.autotune(4, dev)
     assert changed >= 0 and (changed == 0) == (net.describe() == before)
+    # the instance (and its name) follows the tile autotune chose: every conv..._t{bm}x{bn}x{bk} launch names conv_igemm_kernel<bm, bn, bk, ...>
+    # (ResNet-50 has none at this batch: MobileNet-V1 has fourteen)
+    v1 = topology.get('mobilenet_v1')
+    p1 = synth.make_params(v1, seed=1234)
+    x1, _ = synth.make_input(v1, p1, 4, 224, seed=7)
+    x1 = torch.from_numpy(x1).to(dev)
+    n1 = build_net(v1, p1, max_batch=4, hw=224)
+    want = n1.run(x1).cpu().numpy()
+    assert n1.autotune(4, dev) >= 0
+    np.testing.assert_array_equal(n1.run(x1).cpu().numpy(), want)
+    for n in (net, n1):
+        tiled = [(i, m) for i in range(n.num_launches) for m in [re.match(r'conv\w*_t(\d+)x(\d+)x(\d+)', n.launch_info(i, 1)[0])] if m]
+        assert tiled or n is net
+        for i, m in tiled:
+            assert n.launch_kernel(i).startswith('f8::conv_igemm_kernel<%s, %s, %s,' % m.groups()), (i, n.launch_info(i, 1)[0], n.launch_kernel(i))
     np.testing.assert_array_equal(net.run(torch.from_numpy(x).to(dev)).cpu().numpy(), g['s1234_hw224_n1/logits'])
 
 
