@@ -34,6 +34,7 @@ struct Options {
     int fuse_p12 = 1;            // 7x7 identity blocks: body.0 + body.2 in one launch, split over a workgroup pair per image (f8_p12.hip)
     int fuse_head2 = 1;          // MobileNet-V2 head (3x3 / 2 conv, depthwise 3x3, 1x1) as one row-walking launch (f8_stem.hip, H2)
     int fuse_ir = 1;             // MobileNet-V2 inverted residual (expand -> depthwise -> project) in one launch: 1 = where it wins, 2 = always
+    int fuse_irchain = 0;        // runs of >= 2 consecutive stride-1 inverted residuals on a small map in ONE launch, one workgroup per image (f8_irchain.hip)
     int patch3x3 = 1;            // LDS-patch 3x3 kernel
     int dual_wide = 2048;        // dual-GEMM joins with at least this many couts use the 128x128 tile
     int deep_nk = 7;             // K loops of at least this many steps use the deepest DMA ring
@@ -272,6 +273,34 @@ struct IRArgs {
     uint32_t mW, mHW, mWo, mRWo; int32_t s1W, s2W, s1HW, s2HW, s1Wo, s2Wo, s1RWo, s2RWo;
 };
 
+// One launch for a run of consecutive stride-1 inverted-residual blocks on one map, one workgroup per image (f8_irchain.hip): the int8 block
+// inputs and the int32 stream between the blocks stay in LDS.  Weights as IRArgs (the fused_ir images), channel counts padded to 32.
+struct IRChainBlk {
+    const int8_t* w0; const int32_t* b0;   // expand  [E32][cin], offset-corrected bias [E32]
+    const int8_t* wd4; const int32_t* bd4; // depthwise: dot4 image [E32/4][36 B], bias (+128*sum(w) for unsigned inputs) [E32]
+    const int8_t* w4; const int32_t* b4;   // project [cout][E32], offset-corrected bias [cout]
+    int32_t cin, cout, E32;
+    int32_t n1, lo1, hi1; uint32_t xor1;   // requant expand output -> depthwise input format
+    int32_t n2, lo2, hi2; uint32_t xor2;   // requant depthwise output -> project input format
+    int32_t relu_a, relu_b, relu0;         // ReLU after expand / depthwise / project
+    int32_t res;                           // the block joins its input (int32 stream): (acc << acc_shl) + (stream << res_shl), clamp, ReLU relu1
+    int32_t acc_shl, res_shl, relu1;
+    int32_t nq, loq, hiq; uint32_t xorq;   // requant block output -> the NEXT block's expand input format (all blocks but the last)
+    int32_t keep;                          // the next block joins this block's output: it stays in LDS as int32
+};
+constexpr int kIRChainMaxBlocks = 8;
+struct IRChainArgs {
+    IRChainBlk blk[kIRChainMaxBlocks]; int32_t nblk;
+    int32_t acc_ok;                        // expand / depthwise accumulators of every block bounded (see DwArgs::acc_ok)
+    int32_t rq_int;                        // Options::requant_float == 0: integer requantisation only
+    const int8_t* x8;                      // first block's input, int8 NHWC [N*H*W][blk[0].cin] in its expand conv's input format
+    const int32_t* xr;                     // ... int32 I32T, when blk[0].res
+    int32_t N, H, W;
+    int32_t* out32; QuantOut q[2];         // forms of the last block's output
+    uint32_t mW; int32_t s1W, s2W;         // magic numbers (fast_div) for / W
+    int32_t xp, off_strm, off_patch, off_mid2, off_w;   // LDS layout (filled by launch_irchain)
+};
+
 // ResNet head in one launch: 7x7/2 conv + ReLU + requant (unsigned 8-bit) + 3x3/2 max-pool (f8_stem.hip).
 struct StemPoolArgs {
     int32_t acc_ok;                        // conv accumulators bounded (see DwArgs::acc_ok)
@@ -384,6 +413,12 @@ bool fused_ir_config(int cinS, int coutS, int H, int W, int stride, int* R, int*
 int fused_ir_inst(const IRArgs& a, int coutS);
 int fused_ir_kernel_name(char* buf, size_t cap, int cinS, int coutS, int inst);
 hipError_t launch_fused_ir(const IRArgs& a, int cinS, int coutS, int inst, hipStream_t s);
+// a run of stride-1 inverted residuals in one launch (f8_irchain.hip): H x W map, the largest padded block input / output and the widest int32
+// stream a later block joins (keep_max; 0: none)
+bool irchain_supported(int H, int W, int cin_max, int cout_max, int keep_max);
+int irchain_inst(const IRChainArgs& a);                            // FQ (as fused_ir_inst) | register shape << 2
+int irchain_kernel_name(char* buf, size_t cap, int inst);
+hipError_t launch_irchain(const IRChainArgs& a, int inst, hipStream_t s);
 // 3x3 / stride 1 / pad 1 with the input patch resident in LDS (f8_conv3x3.hip); config = false: no instance
 bool conv3x3_patch_config(int cin, int H, int W, int coutP, int* R, int* IMGS, int* BN);
 hipError_t launch_conv3x3_patch(const ConvArgs& a, int cin, hipStream_t s);

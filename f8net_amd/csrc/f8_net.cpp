@@ -100,6 +100,9 @@ struct Node {
     bool tail = false;                   // shortcut conv (dual GEMM host) of such a block: its join runs as the FIRST block of a chain launch (ChainArgs::tail)
     int h2_head = -1, h2_dw = -1;        // 1x1 conv that ends the MobileNet-V2 head launch (f8_stem.hip, H2): its 3x3 / 2 head conv and its depthwise conv
     int ir_a = -1, ir_b = -1, ir_R = 0, ir_G = 0;   // project conv of a fused inverted-residual block: its expand / depthwise convs, tile
+    int irc_a = -1, irc_b = -1;          // project conv of a block that runs inside an inverted-residual chain launch (f8_irchain.hip): expand / depthwise
+    int irc_into = -1;                   // ... the project conv of the chain's LAST block
+    std::vector<int> irchain;            // project conv of the last block of such a chain: the project convs of all its blocks, in order
     int dual = -1;                     // 1x1 conv hosting a join whose other operand is ANOTHER 1x1 conv (node id): one dual-GEMM launch
     int dual_host = -1;                // ... and that other conv: the node that carries it
     int p3_R = 0, p3_imgs = 0, p3_bn = 0;   // 3x3 conv on the LDS-patch kernel (p3_R > 0): rows / images per tile, cout tile
@@ -109,7 +112,7 @@ struct Node {
     size_t rc_off = 0, cc_off = 0; int ncc = 0;      // border-class tables (0 = single class)
     ConvTile tile{};
 };
-enum StepKind { S_INPUT, S_CONV, S_DW, S_ADD, S_MAXPOOL, S_AVGPOOL, S_REQUANT, S_OUTPUT, S_FUSED, S_STEMPOOL, S_IR, S_P12, S_CHAIN, S_BCHAIN, S_HEAD2 };
+enum StepKind { S_INPUT, S_CONV, S_DW, S_ADD, S_MAXPOOL, S_AVGPOOL, S_REQUANT, S_OUTPUT, S_FUSED, S_STEMPOOL, S_IR, S_P12, S_CHAIN, S_BCHAIN, S_HEAD2, S_IRCHAIN };
 struct OutSel { int t = -1; int f32 = -1; int f8[2] = {-1, -1}; };
 struct Step {
     int kind; int node;
@@ -125,7 +128,7 @@ struct Step {
     double bytes_per_img = 0, bytes_const = 0, ops_per_img = 0;
     double valu_per_img = 0;           // ESSENTIAL vector lane-operations per image (f8_net_launch_valu): what the reference's semantics need once the MFMAs are done
     // the launcher's arguments as far as the plan decides them (bind_step); run_step copies them and adds what the run decides
-    std::variant<std::monostate, ConvArgs, StemPoolArgs, FusedArgs, ChainArgs, BChainArgs, IRArgs, DwArgs, AddArgs, PoolArgs, AvgArgs, OutArgs> args;
+    std::variant<std::monostate, ConvArgs, StemPoolArgs, FusedArgs, ChainArgs, BChainArgs, IRArgs, IRChainArgs, DwArgs, AddArgs, PoolArgs, AvgArgs, OutArgs> args;
     int inst = 0;                      // the instance the launcher starts (the family's *_inst, f8_internal.h; bind_step)
     // S_CHAIN / S_BCHAIN: geometry, workgroups per image and resident per CU, the 7x7 cluster form (f8_cchain.hip)
     int C = 0, MID = 0, H = 0, W = 0, cin0 = 0, tiles = 0, wg_per_cu = 1; bool cluster = false;
@@ -295,6 +298,7 @@ static const OptKey kOptKeys[] = {
     {"fuse_stem", "F8_FUSE_STEM", &Options::fuse_stem, 0, 1, true},
     {"fuse_input", "F8_FUSE_INPUT", &Options::fuse_input, 0, 1, true},
     {"fuse_ir", "F8_FUSE_IR", &Options::fuse_ir, 0, 2, true},
+    {"fuse_irchain", "F8_FUSE_IRCHAIN", &Options::fuse_irchain, 0, 1, true},
     {"fuse_head2", "F8_FUSE_HEAD2", &Options::fuse_head2, 0, 1, true},
     {"fuse_p12", "F8_FUSE_P12", &Options::fuse_p12, 0, 1, true},
     {"fuse_chain", "F8_FUSE_CHAIN", &Options::fuse_chain, 0, 1, true},
@@ -1215,6 +1219,102 @@ static void plan_inverted_residuals(f8_net* net, int max_batch) {
 
 }
 
+// pass 1e2
+static void plan_inverted_residual_chains(f8_net* net) {
+    auto& T = net->tensors;
+    auto& ND = net->nodes;
+    const int nn = (int)ND.size();
+    const Options& opt = net->opt;
+    // ---- 1e2. runs of >= 2 consecutive STRIDE-1 inverted residuals on one map  ->  ONE launch, one workgroup per image (f8_irchain.hip): the
+    //           block outputs between them exist in no form at all (int8 block input and int32 stream in LDS).  Its own matcher: a block pass 1e
+    //           left as three launches (the 7x7 maps under fuse_ir = 1) is taken as well, and 1e's marks of a chained block are undone.
+    if (!opt.fuse_irchain) return;
+    // the stride-1 block whose project conv is c: expand a0 -> depthwise b -> c [+ join with a0's input]; out = the block output
+    struct Blk { int a0, b, c, out; bool res; };
+    auto match = [&](int ci, Blk* k) -> bool {
+        const Node& c = ND[ci];
+        if (c.kind != N_CONV || c.cd.groups != 1 || c.cd.kernel != 1 || c.cd.stride != 1 || c.cd.pad != 0 || !c.cd.quant_input ||
+            (c.absorbed_by >= 0) || c.fb_a >= 0 || c.fbd_a >= 0 || c.dual >= 0 || c.dual_host >= 0 || c.chain_into >= 0 || c.bchain_into >= 0 ||
+            c.p12_a >= 0 || c.bb_a >= 0 || c.h2_head >= 0) return false;
+        const Tensor& tb = T[c.a];
+        if (tb.prod < 0 || tb.consumers.size() != 1 || c.a == net->out_t) return false;
+        const int bi = tb.prod;
+        const Node& b = ND[bi];
+        if (b.kind != N_CONV || b.cd.groups == 1 || b.cd.groups != b.cd.cin || b.cd.cout != b.cd.cin || b.cd.kernel != 3 || b.cd.pad != 1 || b.cd.stride != 1 ||
+            !b.cd.quant_input || b.fused_add >= 0 || (b.absorbed_by >= 0 && b.absorbed_by != ci)) return false;
+        const Tensor& ta = T[b.a];
+        if (ta.prod < 0 || ta.consumers.size() != 1 || b.a == net->out_t) return false;
+        const int ai = ta.prod;
+        const Node& a0 = ND[ai];
+        if (a0.kind != N_CONV || a0.cd.groups != 1 || a0.cd.kernel != 1 || a0.cd.stride != 1 || a0.cd.pad != 0 || !a0.cd.quant_input || a0.fused_add >= 0 ||
+            (a0.absorbed_by >= 0 && a0.absorbed_by != ci) || a0.dual >= 0 || a0.dual_host >= 0 || a0.ir_a >= 0 || a0.fb_a >= 0 || a0.fbd_a >= 0) return false;
+        if (T[a0.a].prod < 0 || ND[T[a0.a].prod].kind == N_INPUT) return false;      // the network input has its own layouts
+        k->a0 = ai; k->b = bi; k->c = ci; k->res = false; k->out = c.out;
+        if (c.fused_add >= 0) {                                   // a residual join must be with the block input
+            const Node& ad = ND[c.fused_add];
+            const int other = (ad.a == c.out) ? ad.b : ad.a;
+            if (other != a0.a || T[c.out].consumers.size() != 1 || c.out == net->out_t) return false;
+            k->res = true; k->out = ad.out;
+        }
+        const Tensor& x = T[a0.a];
+        return T[k->out].H == x.H && T[k->out].W == x.W;
+    };
+    // the widest block input / output and the widest int32 stream a block of the run joins: what irchain_supported checks
+    auto fits = [&](const std::vector<Blk>& run) {
+        const Tensor& x = T[ND[run[0].a0].a];
+        int cin_max = 0, cout_max = 0, keep_max = 0;
+        for (const Blk& k : run) {
+            const int ci = T[ND[k.a0].a].Cs, co = round_up(ND[k.c].cd.cout, 32);
+            cin_max = std::max(cin_max, ci); cout_max = std::max(cout_max, co);
+            if (k.res) keep_max = std::max(keep_max, ci);
+        }
+        return (int)run.size() <= kIRChainMaxBlocks && irchain_supported(x.H, x.W, cin_max, cout_max, keep_max);
+    };
+    std::vector<char> used(nn, 0);
+    for (int i = 0; i < nn; ++i) {
+        Blk k0;
+        if (used[i] || !match(i, &k0)) continue;
+        std::vector<Blk> run{k0};
+        if (!fits(run)) continue;
+        for (;;) {                                                // extend: the block output's only readers are the next block's expand conv and its join
+            const Blk& last = run.back();
+            if (last.out == net->out_t) break;
+            const Tensor& o = T[last.out];
+            int nxt = -1, joins = 0, others = 0;
+            for (int u : o.consumers) {
+                const Node& un = ND[u];
+                if (un.kind == N_CONV && un.cd.groups == 1 && un.cd.kernel == 1) { if (nxt < 0) nxt = u; else ++others; }
+                else if (un.kind == N_ADD) ++joins;
+                else ++others;
+            }
+            if (nxt < 0 || others) break;
+            // the next block: the project conv that consumes nxt's expand -> depthwise chain
+            const Tensor& e1 = T[ND[nxt].out];
+            if (e1.consumers.size() != 1) break;
+            const Tensor& e2 = T[ND[e1.consumers[0]].out];
+            if (e2.consumers.size() != 1) break;
+            Blk kn;
+            if (!match(e2.consumers[0], &kn) || kn.a0 != nxt || ND[kn.a0].a != last.out) break;
+            if (joins != (kn.res ? 1 : 0)) break;
+            if (kn.res && ND[ND[kn.c].fused_add].fused_into != kn.c) break;
+            run.push_back(kn);
+            if (!fits(run)) { run.pop_back(); break; }
+        }
+        if (run.size() < 2) continue;
+        const int host = run.back().c;
+        std::vector<int> hosts;
+        for (const Blk& k : run) {
+            Node& c = ND[k.c];
+            used[k.c] = 1;
+            c.ir_a = c.ir_b = -1; c.ir_R = c.ir_G = 0;            // (pass 1e's marks)
+            c.irc_a = k.a0; c.irc_b = k.b; c.irc_into = host;
+            ND[k.a0].absorbed_by = k.c; ND[k.b].absorbed_by = k.c;
+            hosts.push_back(k.c);
+        }
+        ND[host].irchain = hosts;
+    }
+}
+
 // pass 1h
 static void plan_mobilenet_v2_head(f8_net* net, int max_batch) {
     auto& T = net->tensors;
@@ -1229,7 +1329,7 @@ static void plan_mobilenet_v2_head(f8_net* net, int max_batch) {
     for (int i = 0; opt.fuse_head2 && opt.fuse_stem && i < nn; ++i) {
         Node& c = ND[i];
         if (c.kind != N_CONV || c.cd.groups != 1 || c.cd.kernel != 1 || c.cd.stride != 1 || c.cd.pad != 0 || c.cd.relu || !c.cd.quant_input ||
-            c.cd.input_signed || c.fused_add >= 0 || c.absorbed_by >= 0 || c.ir_a >= 0 || c.dual >= 0 || c.dual_host >= 0 || c.out == net->out_t) continue;
+            c.cd.input_signed || c.fused_add >= 0 || c.absorbed_by >= 0 || c.ir_a >= 0 || c.irc_a >= 0 || c.dual >= 0 || c.dual_host >= 0 || c.out == net->out_t) continue;
         if (c.cd.cin != 32 || round_up(c.cd.cout, 32) != 32) continue;
         const Tensor& tb = T[c.a];
         if (tb.consumers.size() != 1 || c.a == net->out_t) continue;
@@ -1280,7 +1380,7 @@ static void plan_last_conv_and_pool(f8_net* net, int max_batch) {
             continue;
         }
         if (c.kind != N_CONV || c.absorbed_by >= 0 || c.dual >= 0 || c.dual_host >= 0 || c.fb_a >= 0 || c.fbd_a >= 0 || c.chain_into >= 0 || c.bchain_into >= 0 ||
-            c.ir_a >= 0 || c.p12_a >= 0 || c.bb_a >= 0 || c.h2_head >= 0 || c.cd.groups != 1 || c.cd.kernel != 1 || c.cd.stride != 1 || c.cd.pad != 0 || !c.cd.quant_input) continue;
+            c.ir_a >= 0 || c.irc_a >= 0 || c.p12_a >= 0 || c.bb_a >= 0 || c.h2_head >= 0 || c.cd.groups != 1 || c.cd.kernel != 1 || c.cd.stride != 1 || c.cd.pad != 0 || !c.cd.quant_input) continue;
         if ((c.fused_add >= 0 ? ND[c.fused_add].out : c.out) != p.a) continue;
         if (c.fused_add < 0 && T[c.out].consumers.size() != 1) continue;
         const int ckp = round_up(c.cd.cin, 32), coutP = round_up(c.cd.cout, 32);
@@ -1330,6 +1430,16 @@ static void plan_tensor_forms(f8_net* net, int max_batch) {
                     break;
                 }
                 if (nd.absorbed_by >= 0 && ND[nd.absorbed_by].bb_a == i) break;            // first conv of a chained BasicBlock: its int8 input is made in the launch
+                {   // inverted-residual chain (f8_irchain.hip): only the first block's input exists in HBM (int8, and int32 when it joins it)
+                    const int ich = nd.irc_a >= 0 ? i : (nd.absorbed_by >= 0 && ND[nd.absorbed_by].irc_a >= 0 ? nd.absorbed_by : -1);
+                    if (ich >= 0) {
+                        const Node& hc = ND[ich];
+                        const bool first = ND[hc.irc_into].irchain[0] == ich;
+                        if (i == hc.irc_a && first) { add_form(s, FORM_I8, n, nd.cd.input_signed ? 1 : 0); break; }   // expand conv of the first block
+                        if (i == ich && first && nd.fused_add >= 0) add_form(T[ND[hc.irc_a].a], FORM_I32, 0, 0);
+                        break;
+                    }
+                }
                 {   // stage chain (f8_chain.hip): the tensors between its blocks exist in no form at all; an identity first block
                     // reads only the int32 form of the stage input (its int8 copy is made in the launch)
                     const int host = nd.absorbed_by >= 0 && ND[nd.absorbed_by].fb_a == i ? nd.absorbed_by : -1;   // nd = body.0 of an identity block
@@ -1427,6 +1537,7 @@ static int emit_steps(f8_net* net, int max_batch) {
         if (nd.kind == N_CONV && (nd.absorbed_by >= 0 || nd.dual_host >= 0)) continue;
         if (nd.kind == N_CONV && nd.chain_into >= 0 && nd.chain_into != i) continue;      // runs inside the chain launch of a later block
         if (nd.kind == N_CONV && nd.bchain_into >= 0 && nd.bchain_into != i) continue;
+        if (nd.kind == N_CONV && nd.irc_into >= 0 && nd.irc_into != i) continue;       // runs inside the inverted-residual chain launch of a later block
         if (nd.kind == N_MAXPOOL && nd.sp_conv >= 0) continue;
         if (nd.kind == N_AVGPOOL && nd.pool_host >= 0) continue;     // runs in its conv's launch
         Step st; st.node = i;
@@ -1634,6 +1745,49 @@ static int emit_steps(f8_net* net, int max_batch) {
                     st.bytes_per_img = b;
                     st.bytes_const = (double)na.coutP * (na.ktot + 4) + (double)nd.coutP * (nd.ktot + 4);
                     st.name = std::string(nd.p12_s2 ? "fused_opener_s2_p12_R" + std::to_string(nd.fb_R) + ":" : "fused_p12:") + tname(net, na.out) + "+" + tname(net, nd.out);
+                    break;
+                }
+                if (nd.irc_into == i) {
+                    // ---- inverted-residual chain: nd is the project conv of its LAST block
+                    const std::vector<int> ch = nd.irchain;
+                    const Node& f = ND[ch[0]];
+                    Node& fa = ND[f.irc_a];
+                    Tensor& x = T[fa.a];
+                    st.kind = S_IRCHAIN;
+                    st.src_t = fa.a;
+                    int n0 = 0; consumer_format(x, fa.cd, &n0, "finalize");
+                    st.src_f = find_form(x, FORM_I8, n0, fa.cd.input_signed ? 1 : 0);
+                    if (f.fused_add >= 0) { st.res_t = fa.a; st.res_f = find_form(x, FORM_I32, 0, 0); }
+                    const double px = (double)x.H * x.W;
+                    double ops = 0, wbytes = 0, valu = 0;
+                    std::string blocks;
+                    for (size_t k = 0; k < ch.size(); ++k) {
+                        Node& c = ND[ch[k]]; Node& na = ND[c.irc_a]; Node& nb = ND[c.irc_b];
+                        pack_conv_weights(net, na, T[na.a], T[na.out]);
+                        nb.depthwise = true;
+                        pack_dw_weights(net, nb, T[nb.a]);
+                        pack_conv_weights(net, c, T[c.a], T[c.out]);
+                        ops += 2.0 * px * ((double)na.cd.cin * na.cd.cout + 9.0 * nb.cd.cout + (double)c.cd.cin * c.cd.cout);
+                        wbytes += (double)na.coutP * (na.ktot + 4) + (double)T[nb.a].Cs * 13 + (double)c.coutP * (c.ktot + 4);
+                        const int bo = c.fused_add >= 0 ? ND[c.fused_add].out : c.out;
+                        valu += 3.0 * px * (na.cd.cout + nb.cd.cout) + (c.fused_add >= 0 ? 2.0 * px * T[bo].C : 0.0) + (k + 1 < ch.size() ? 3.0 * px * T[bo].Cs : 0.0);
+                        const std::string& lb = T[bo].label;
+                        blocks += (k ? "+" : "") + (lb.empty() ? tname(net, bo) : lb.substr(0, lb.find('.')));
+                    }
+                    if (nd.fused_add >= 0) {
+                        const Node& ad = ND[nd.fused_add];
+                        st.relu1 = ad.relu;
+                        out_t = ad.out;
+                    }
+                    st.relu0 = nd.cd.relu;
+                    select_outputs(net, out_t, &st.out, &extra);
+                    Tensor& o = T[out_t];
+                    double b = px * x.Cs + (st.res_t >= 0 ? px * x.Cs * 4 : 0);
+                    if (st.out.f32 >= 0) b += px * o.Cs * 4;
+                    for (int k = 0; k < 2; ++k) if (st.out.f8[k] >= 0) b += px * o.Cs;
+                    st.ops_per_img = ops; st.bytes_per_img = b; st.bytes_const = wbytes;
+                    st.valu_per_img = valu + 3.0 * px * o.Cs * out_forms8(st);
+                    st.name = "ir_chain_x" + std::to_string(ch.size()) + ":" + blocks;
                     break;
                 }
                 if (nd.ir_a >= 0) {
@@ -2261,6 +2415,40 @@ static int bind_step(f8_net* net, Step& st) {
             fused_ir_kernel_name(kb, sizeof kb, x.Cs, nd.coutP, st.inst = fused_ir_inst(a, nd.coutP));
             out_formats(a.q); st.args = a; break;
         }
+        case S_IRCHAIN: {
+            const std::vector<int>& ch = nd.irchain;
+            const Tensor& x = T[st.src_t];
+            IRChainArgs a{};
+            a.nblk = (int)ch.size();
+            a.acc_ok = 1; a.rq_int = rq_int;
+            for (int k = 0; k < a.nblk; ++k) {
+                const Node& c = ND[ch[k]]; Node& na = ND[c.irc_a]; Node& nb = ND[c.irc_b];
+                IRChainBlk& B = a.blk[k];
+                B.w0 = W8(na.w_off); B.b0 = B32(na.b_off);
+                B.wd4 = W8(nb.rc_off); B.bd4 = B32(nb.cc_off);
+                B.w4 = W8(c.w_off); B.b4 = B32(c.b_off);
+                B.cin = T[na.a].Cs; B.cout = c.coutP; B.E32 = na.coutP;
+                fmt(nb, &B.n1, &B.lo1, &B.hi1, &B.xor1);
+                fmt(c, &B.n2, &B.lo2, &B.hi2, &B.xor2);
+                B.relu_a = na.cd.relu; B.relu_b = nb.cd.relu; B.relu0 = c.cd.relu;
+                if (c.fused_add >= 0) {
+                    const int dfl = T[c.out].fl - T[na.a].fl;     // (project << acc_shl) + (block input << res_shl)
+                    B.res = 1; B.acc_shl = dfl < 0 ? -dfl : 0; B.res_shl = dfl > 0 ? dfl : 0; B.relu1 = ND[c.fused_add].relu;
+                }
+                if (k + 1 < a.nblk) {
+                    const Node& nc = ND[ch[k + 1]];
+                    fmt(ND[nc.irc_a], &B.nq, &B.loq, &B.hiq, &B.xorq);
+                    B.keep = nc.fused_add >= 0;
+                }
+                a.acc_ok = a.acc_ok && conv_acc_bounded(na) && conv_acc_bounded(nb);
+            }
+            a.H = x.H; a.W = x.W;
+            make_magic((uint32_t)x.W, &a.mW, &a.s1W, &a.s2W);
+            out_formats(a.q);
+            st.inst = irchain_inst(a);
+            irchain_kernel_name(kb, sizeof kb, st.inst);
+            st.args = a; break;
+        }
         case S_DW: {
             const Tensor& sT = T[st.src_t];
             const Tensor& oT = T[nd.out];
@@ -2321,6 +2509,7 @@ int f8_net_finalize(f8_net* net, int max_batch) {
     plan_stage_chains(net, max_batch);              // 1f: all consecutive bottleneck blocks of a stage in one launch
     plan_basic_block_chains(net, max_batch);        // 1g: the same for BasicBlocks
     plan_inverted_residuals(net, max_batch);        // 1e: MobileNet-V2 inverted residuals
+    plan_inverted_residual_chains(net);             // 1e2: runs of stride-1 inverted residuals in one launch (option fuse_irchain)
     plan_mobilenet_v2_head(net, max_batch);         // 1h: MobileNet-V2 head conv + depthwise + 1x1
     plan_last_conv_and_pool(net, max_batch);        // 1i: the last 1x1 conv + the average pool
     plan_tensor_forms(net, max_batch);              // 2:  which forms of each tensor exist in HBM
@@ -2579,6 +2768,14 @@ static int run_step(const f8_net* net, const Step& st, const int32_t* input, voi
             if (st.res_t >= 0) a.xr = (const int32_t*)fp(T[st.res_t].forms[st.res_f]);
             fill_out(&a.out32, a.q);
             e = launch_fused_ir(a, x.Cs, nd.coutP, st.inst, s);
+            break;
+        }
+        case S_IRCHAIN: {
+            IRChainArgs a = std::get<IRChainArgs>(st.args);
+            a.x8 = (const int8_t*)fp(T[st.src_t].forms[st.src_f]); a.N = N;
+            if (st.res_t >= 0) a.xr = (const int32_t*)fp(T[st.res_t].forms[st.res_f]);
+            fill_out(&a.out32, a.q);
+            e = launch_irchain(a, st.inst, s);
             break;
         }
         case S_DW: {
