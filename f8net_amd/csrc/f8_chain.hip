@@ -41,7 +41,18 @@ template <int C, int MID, int W, int H, int R, int CIN0, bool BROT_ = false, boo
 struct ChainCfg {
     static constexpr bool BROT = BROT_, ALIAS = ALIAS_;
     static constexpr int BSLOTS = BROT ? 2 : kChainMaxBlocks;
+#ifdef F8_CH_ABL_NORAG          // tuning build (results invalid): an ablation of the UNSTACKED form (run it with F8_CHAIN_STACK=0) — no ragged last
+                                // tile, a 14x14 image runs 3 tiles of 4 rows, rows 12-13 are not computed; the host still sizes the groups for 4 tiles
+    static constexpr int T = H / R;
+#else
     static constexpr int T = (H + R - 1) / R;                  // tiles (workgroups) per image
+#endif
+    // STACKABLE: H rows are not whole tiles but 2H are (14x14, R = 4: 3.5 tiles per image, 7 per pair).  With ChainArgs::stack = 2 a tile column
+    // is an image PAIR — in NHWC row 0 of image n + 1 follows row H - 1 of image n, so a pair is one contiguous 2H-row map — and T2 tiles cover it.
+    // The 3x3 must not read across the seam between the two images: lanes of row H - 1 take their bottom taps, lanes of row H their top taps, from
+    // ZPAD, three patch entries of biased zero at the end of LDS (the tile that spans the seam holds both rows; every other tile's lanes never point there)
+    static constexpr bool STACKABLE = H % R != 0 && (2 * H) % R == 0;
+    static constexpr int T2 = STACKABLE ? 2 * H / R : T;       // tiles per image pair
     static constexpr int PX = R * W, NPT = (PX + 31) / 32, ROWS = NPT * 32;
     static constexpr int PW = W + 2, PR = R + 2;
     // LDS rows are PADDED by 16 bytes instead of XOR-swizzled: the 16 lanes of a ds_read_b128 service group read consecutive rows
@@ -56,9 +67,11 @@ struct ChainCfg {
     static constexpr int BIAS_BYTES = (BSLOTS * BIAS_INTS + (CIN0 != C ? C : 0)) * 4;   // + bsc of the stage-opening block
     static constexpr int MISC_BYTES = 256;
     static_assert(!ALIAS || XIN_BYTES <= PATCH_BYTES, "ALIAS: the shortcut's operand fits the patch");
-    static constexpr int LDS_BYTES = X8_BYTES + PATCH_BYTES + MID2_BYTES + (ALIAS ? 0 : XIN_BYTES) + BIAS_BYTES + MISC_BYTES;
+    static constexpr int ZPAD_BYTES = STACKABLE ? 3 * MS : 0;
+    static constexpr int ZPAD_OFF = X8_BYTES + PATCH_BYTES + MID2_BYTES + (ALIAS ? 0 : XIN_BYTES) + BIAS_BYTES + MISC_BYTES;
+    static constexpr int LDS_BYTES = ZPAD_OFF + ZPAD_BYTES;
     static constexpr int ROWB = W * MID;                       // one exchanged row of mid1
-    static_assert(LDS_BYTES <= 160 * 1024, "LDS");
+    static_assert(LDS_BYTES <= 160 * 1024 && ZPAD_OFF % 16 == 0, "LDS");
     static_assert(X8_BYTES < 65536 + 4096 && PATCH_BYTES < 65536 && MID2_BYTES < 65536, "immediate offsets");
     static_assert(ROWB / 16 <= 256 && (size_t)512 * 4 * ROWB <= kChainXchgBytes, "one 16-byte piece of a halo row per thread of a half workgroup");
 };
@@ -154,6 +167,7 @@ chain_kernel(const ChainArgs a) {
 #endif
     constexpr int PG_ = NW / (MID / 32), NPW_ = ((R * W + 31) / 32 + PG_ - 1) / PG_;
     constexpr bool SPLIT = F8_CH_SPLIT != 0 && EARLY && PG_ >= 2 && T * R == H && W <= NPW_ * 32 && (R - 1) * W >= NPW_ * 32;
+    static_assert(!(Cfg::STACKABLE && SPLIT), "the seam's tap bases live in the plain EARLY tap order");
     static_assert(NB <= CM && CM % NB == 0 && NK1 % NB == 0, "a batch of K steps stays inside one 3x3 tap / one weight tile");
     static_assert(!DS0 || KS % NB == 0, "stage-opening block: whole batches");
     static_assert(!ROT || (NK1 % 8 == 0 && CM == 8), "rotation: groups of 8 K steps (256 bytes of a row), whole taps");
@@ -220,11 +234,20 @@ chain_kernel(const ChainArgs a) {
     if constexpr (DS0) for (int i = tid; i < C; i += NT) bias_lds[BSLOTS * BIAS_INTS + i] = a.blk[0].bsc[i];
     __syncthreads();
     const int L = __builtin_amdgcn_readfirstlane(misc[0]);
-    const int grp = L / T, ti = L - grp * T;
+    // STACK (Cfg::STACKABLE instances, ChainArgs::stack = 2): the tile column is an image pair, HS = 2H rows, T2 tiles; n below counts pairs
+    constexpr bool STACKABLE = Cfg::STACKABLE && !ROT;          // (a K-rotated tuning instance keeps one image per column)
+    const bool stk2 = STACKABLE && a.stack == 2;
+    const int TC = stk2 ? Cfg::T2 : T, HS = stk2 ? 2 * H : H;
+    const int grp = L / TC, ti = L - grp * TC;
     const int p0 = ti * R;
-    const int rows = (H - p0) < R ? (H - p0) : R;
-    const int npx = rows * W;
-    const bool has_up = ti > 0, has_dn = ti < T - 1;
+    // pairs of the launch; an odd N leaves ONE image in the last pair: the tiles below its row H - 1 have no rows there and stop one pair early
+    // (they still count themselves out at the end), the tile that spans the seam runs as the ragged last tile of an unstacked image
+    const int n_end = !stk2 ? a.N : ((a.N & 1) && p0 >= H ? a.N / 2 : (a.N + 1) / 2);
+    // (the seam tile of an odd N's last pair is ragged: HS != H, 2 n + 1 == N, p0 == (H / R) R — tested from values that are live anyway)
+    auto ragged = [&](int n) { return STACKABLE && HS != H && 2 * n + 1 == a.N && p0 == (H / R) * R; };
+    const int rows0 = (HS - p0) < R ? (HS - p0) : R;
+    const int npx0 = rows0 * W;
+    const bool has_up = ti > 0, has_dn0 = ti < TC - 1;
     const int rot = ROT ? __builtin_amdgcn_readfirstlane(L * 5 + wave * 3) : 0;
 
     unsigned* const flags = a.sync + 16;
@@ -305,14 +328,20 @@ chain_kernel(const ChainArgs a) {
     auto in_issue = [&](int n, bool live) {     // !live: zeros (every register is (re)defined here on every path: nothing stays live through the blocks)
         if constexpr (DS0) {
             int tq0 = tid; asm volatile("" : "+v"(tq0));
-            const int mt0 = (n * H + p0) * W;
+            const int mt0 = (n * HS + p0) * W;
+            const int npx = ragged(n) ? (H - p0) * W : npx0;  // (an odd N's last pair holds one image)
 #pragma unroll
             for (int k = 0; k < NXI; ++k) {
                 const int idx = tq0 + k * NT, row = idx / CHX, c16 = idx % CHX;
                 vin[k] = v4i{0, 0, 0, 0};
                 if constexpr (TAIL) {       // the shortcut's operand: pixels (2 (p0 + r), 2 c) of the block input (2H x 2W, CIN0 channels)
                     const int pr = row / W, pc = row - pr * W;
-                    if (live && row < npx) vin[k] = *(const v4i*)(a.x8in + ((size_t)(n * 2 * H + 2 * (p0 + pr)) * (2 * W) + 2 * pc) * CIN0 + c16 * 16);
+                    if constexpr (STACKABLE) {  // stacked row -> (image, its row): pairs are contiguous, so the global row is n HS + p0 + r
+                        const int g = mt0 / W + pr, img = g / H, y = g - img * H;
+                        if (live && row < npx) vin[k] = *(const v4i*)(a.x8in + ((size_t)(img * 2 * H + 2 * y) * (2 * W) + 2 * pc) * CIN0 + c16 * 16);
+                    } else {
+                        if (live && row < npx) vin[k] = *(const v4i*)(a.x8in + ((size_t)(n * 2 * H + 2 * (p0 + pr)) * (2 * W) + 2 * pc) * CIN0 + c16 * 16);
+                    }
                 } else {
                     if (live && row < npx) vin[k] = *(const v4i*)(a.x8in + (size_t)(mt0 + row) * CIN0 + c16 * 16);
                 }
@@ -337,10 +366,13 @@ chain_kernel(const ChainArgs a) {
 #ifndef F8_CH_PREFETCH
 #define F8_CH_PREFETCH 1          // 0 (tuning builds): the input tile is requested at the top of its own round
 #endif
-    if (F8_CH_PREFETCH) in_issue(grp < a.N ? grp : 0, grp < a.N);
+    if (F8_CH_PREFETCH) in_issue(grp < n_end ? grp : 0, grp < n_end);
 
-    for (int n = grp; n < a.N; n += a.NG) {
-        const int m_tile = (n * H + p0) * W;                    // global pixel index of the tile's first pixel
+    for (int n = grp; n < n_end; n += a.NG) {
+        const int m_tile = (n * HS + p0) * W;                   // global pixel index of the tile's first pixel
+        const bool rag = ragged(n);              // an odd N's last pair: the seam tile is the image's ragged last tile
+        const int rows = rag ? H - p0 : rows0, npx = rag ? (H - p0) * W : npx0;
+        const bool has_dn = has_dn0 && !rag;
         if (!F8_CH_PREFETCH) in_issue(n, true);
 
         // =====================================================================================
@@ -469,6 +501,7 @@ chain_kernel(const ChainArgs a) {
                         } else {
                             for (int o = tq_ * 16; o < Cfg::PATCH_BYTES; o += NT * 16) *(v4i*)(patch + o) = zv;
                         }
+                        if constexpr (STACKABLE) { if (tq_ < Cfg::ZPAD_BYTES / 16) *(v4i*)(lds + Cfg::ZPAD_OFF + tq_ * 16) = zv; }   // the seam's taps
                     }
                     v16i acc[NPW];
 #pragma unroll
@@ -641,6 +674,20 @@ chain_kernel(const ChainArgs a) {
                     unsigned bpb2[NPW], bpb3[NPW];
 #pragma unroll
                     for (int j = 0; j < NPW; ++j) { bpb2[j] = bpb[j] + (unsigned)(ord ? 2 * PW * MS : 0); bpb3[j] = bpb[j] + (unsigned)(ord ? 0 : 2 * PW * MS); }
+                    // STACKABLE: the top / bottom tap rows' own bases — a lane on the seam's second / first image row reads the zero pad there
+                    // (chosen once per block here: the K loop gains no instruction)
+                    unsigned bpbt[NPW], bpbb[NPW];
+#pragma unroll
+                    for (int j = 0; j < NPW; ++j) {
+                        bpbt[j] = bpb[j]; bpbb[j] = bpb[j];
+                        if constexpr (STACKABLE) {
+                            const int pix = p12_pix[j], srow = p0 + (pix < npx ? pix : npx - 1) / W;
+                            const unsigned zo = (unsigned)(Cfg::ZPAD_OFF - Cfg::X8_BYTES + lh * 16);
+                            // (row H exists in pairs only; row H - 1 of a lone image has the border's zero row below it: the pad holds the same bytes)
+                            if (srow == H) bpbt[j] = zo;
+                            if (srow == H - 1) bpbb[j] = zo - (unsigned)(2 * PW * MS);
+                        }
+                    }
                     auto rd = [&](v4i (&xf)[NPW], auto gc) {
                         constexpr int G = decltype(gc)::value, TAP0 = G / CM, CI = G % CM;
                         if constexpr (SPLIT) {
@@ -661,7 +708,7 @@ chain_kernel(const ChainArgs a) {
                                 for (int j = 0; j < NPW; ++j) xf[j] = *(const v4i*)(patch + bpb[j] + eo);
                             } else {
 #pragma unroll
-                                for (int j = 0; j < NPW; ++j) xf[j] = *(const v4i*)(patch + bpb[j] + ((TAP / 3) * PW + TAP % 3) * MS + CI * 32);
+                                for (int j = 0; j < NPW; ++j) xf[j] = *(const v4i*)(patch + (TAP < 3 ? bpbt[j] : TAP < 6 ? bpb[j] : bpbb[j]) + ((TAP / 3) * PW + TAP % 3) * MS + CI * 32);
                             }
                         }
                     };
@@ -888,7 +935,7 @@ chain_kernel(const ChainArgs a) {
             for (int b = DS0 ? 1 : 0; b < a.nblk; ++b) block(b, std::integral_constant<int, 0>{}, std::integral_constant<int, 2>{});
         }
 
-        if (F8_CH_PREFETCH) in_issue(n + a.NG < a.N ? n + a.NG : n, n + a.NG < a.N);   // the next image's input tile: ahead of the output stores in the memory queue
+        if (F8_CH_PREFETCH) in_issue(n + a.NG < n_end ? n + a.NG : n, n + a.NG < n_end);   // the next image's input tile: ahead of the output stores in the memory queue
         // ---- the int8 copy of the stage output: LDS rows -> whole NHWC rows in HBM
         if (a.q[0].ptr) {
             constexpr int CH = C / 16;
@@ -971,7 +1018,9 @@ static hipError_t launch_chain_t(const ChainArgs& a, hipStream_t s) {
         if (e != hipSuccess) return e;
         if (attr_dev >= 0) attr_done |= 1ull << attr_dev;
     }
-    const int grid = a.NG * Cfg::T;
+    const bool stk2 = a.stack == 2;
+    if (stk2 && (!Cfg::STACKABLE || ROT)) return hipErrorInvalidValue;
+    const int grid = a.NG * (stk2 ? Cfg::T2 : Cfg::T);
     if (grid < 1 || grid > (R < 4 ? 512 : 256)) return hipErrorInvalidValue;
 #ifdef F8_TRACE
     static unsigned long long* tbuf = nullptr; static int count = 0;
@@ -1046,6 +1095,13 @@ static bool chain_rot(int H, bool tail) {
 #else
     (void)H; (void)tail; return false;
 #endif
+}
+// ChainArgs::stack = 2 is a launch argument of the instance, not an instance of its own: the symbol is the same with and without it
+bool chain_stackable(int C, int MID, int H, int W, int cin0, bool tail) {
+    if (cchain_supported(C, MID, H, W, cin0, tail) || chain_rot(H, tail)) return false;
+    int R = 4, wg = 1;
+    chain_shape(C, MID, H, W, cin0, tail, &R, &wg);
+    return H % R != 0 && (2 * H) % R == 0;
 }
 int chain_kernel_name(char* buf, size_t cap, int C, int MID, int H, int W, int cin0, bool tail, int fast) {
     if (cchain_supported(C, MID, H, W, cin0, tail)) return cchain_kernel_name(buf, cap, fast);

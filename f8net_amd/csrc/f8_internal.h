@@ -31,6 +31,7 @@ struct Options {
     int fuse_pool = 1;           // the network's last 1x1 conv (+ residual join) and the average pool behind it in one launch (f8_pool.hip)
     int fuse_tail = 1;           // ... and the JOIN of a stride-2 stage-opening block as the first block of its stage's chain (its body.0 + body.2 on f8_opener.hip, P12)
     int chain_timeout_ms = 10000; // bound of its halo-exchange spins (another process holding the CUs for longer: sticky error word, logits poisoned, f8_net_check)
+    int chain_stack = 1;         // stage chains whose H rows are not whole tiles but 2H are (14x14): image pairs as one 2H-row map, 7 tiles per pair instead of 8
     int fuse_p12 = 1;            // 7x7 identity blocks: body.0 + body.2 in one launch, split over a workgroup pair per image (f8_p12.hip)
     int fuse_head2 = 1;          // MobileNet-V2 head (3x3 / 2 conv, depthwise 3x3, 1x1) as one row-walking launch (f8_stem.hip, H2)
     int fuse_ir = 1;             // MobileNet-V2 inverted residual (expand -> depthwise -> project) in one launch: 1 = where it wins, 2 = always
@@ -221,6 +222,7 @@ struct ChainArgs {
     void* trace;
     int32_t R;                             // rows per tile of the instance to launch (chain_shape)
     int32_t pool;                          // f8_cchain.hip only: out32 / q[] are forms of the AVERAGE POOL behind the last block ([N][C]: FXQAvgPool2d's wrapping int32 sum over the map)
+    int32_t stack;                         // images per tile column: 2 = image pairs tiled as one 2H-row map (instances with H % R != 0 == 2H % R: chain_stackable); 0 / 1 = one image
 };
 constexpr int kChainSyncWords = 16 + 512;   // [0] ticket, [1] workgroups out, [16 + workgroup] halo flags (up to two workgroups per CU)
 constexpr int kChainErrWord = 1000;          // the sticky error word, inside the first 4096 bytes of the scratch
@@ -370,6 +372,7 @@ bool chain_tail_supported(int C, int MID, int H, int W, int cin0);   // ... a st
 int chain_max_blocks(int C, int MID, int H, int W, int cin0, bool tail);
 // rows per tile (4, or 2: the two-workgroups-per-CU instance of tuning builds, -DF8_CH_R2_S0=1) and resident workgroups per CU of the instance that runs the shape
 void chain_shape(int C, int MID, int H, int W, int cin0, bool tail, int* R, int* wg_per_cu);
+bool chain_stackable(int C, int MID, int H, int W, int cin0, bool tail);   // the instance can tile image pairs as one 2H-row map (ChainArgs::stack = 2)
 hipError_t launch_chain(const ChainArgs& a, int fast, int C, int MID, int H, int W, int cin0, hipStream_t s);   // fast: chain_fast (the chain's inst)
 int chain_kernel_name(char* buf, size_t cap, int C, int MID, int H, int W, int cin0, bool tail, int fast);   // the symbol launch_chain starts (f8_chain.hip)
 // the identity blocks of a 7x7 bottleneck stage over clusters of eight workgroups (f8_cchain.hip): reached through chain_supported / launch_chain

@@ -307,6 +307,7 @@ static const OptKey kOptKeys[] = {
     {"fuse_pool", "F8_FUSE_POOL", &Options::fuse_pool, 0, 1, true},
     {"fuse_bchain", "F8_FUSE_BCHAIN", &Options::fuse_bchain, 0, 2, true},
     {"chain_timeout_ms", "F8_CHAIN_TIMEOUT_MS", &Options::chain_timeout_ms, 0, 1 << 20, false},
+    {"chain_stack", "F8_CHAIN_STACK", &Options::chain_stack, 0, 1, true},
     {"wreg", "F8_WREG", &Options::wreg, 0, 1, true},
     {"s2wreg", "F8_S2WREG", &Options::s2wreg, 0, 1, true},
     {"wstat", "F8_WSTAT", &Options::wstat, 0, 1, true},
@@ -2355,8 +2356,11 @@ static int bind_step(f8_net* net, Step& st) {
             a.pool = nd.pool >= 0 ? 1 : 0;
             st.C = oT.C; st.MID = tail ? a0.cd.cin : a0.cd.cout; st.H = oT.H; st.W = oT.W; st.cin0 = tail ? hf.cd.cin : a0.cd.cin;
             chain_shape(st.C, st.MID, st.H, st.W, st.cin0, tail, &a.R, &st.wg_per_cu);
-            st.tiles = (st.H + a.R - 1) / a.R;
             st.cluster = (!ds || tail) && cchain_supported(st.C, st.MID, st.H, st.W, st.cin0, tail);   // the 7x7 stage: clusters of eight workgroups
+            // option chain_stack: a map whose H rows are not whole tiles but 2H are (14x14) is tiled by image PAIRS — 7 tiles per pair instead of 8
+            // (f8_chain.hip ChainCfg::STACKABLE); st.tiles then counts the tiles of a pair (chain_launch_groups: a device with fewer slots runs unstacked)
+            a.stack = (net->opt.chain_stack && !st.cluster && chain_stackable(st.C, st.MID, st.H, st.W, st.cin0, tail)) ? 2 : 1;
+            st.tiles = (a.stack * st.H + a.R - 1) / a.R;
             out_formats(a.q);
             st.inst = chain_fast(a, shortcut_blocks, nq > 0);
             chain_kernel_name(kb, sizeof kb, st.C, st.MID, st.H, st.W, st.cin0, tail, st.inst);
@@ -2629,18 +2633,42 @@ int f8_net_upload(f8_net* net) {
     return F8_OK;
 }
 
-// Image groups (clusters, in the 7x7 cluster form) a chain launch over N images starts.  Every workgroup of a chain launch must be
-// resident: a device with fewer slots than one image has tiles (or than one cluster needs) cannot run it — 0, after fail().
-static int chain_launch_groups(const f8_net* net, const Step& st, int N) {
-    const int slots = (net->num_cu > 0 ? std::min(net->num_cu, 256) : 256) * st.wg_per_cu;
-    if (slots < st.tiles) {
-        fail(F8_ERR_STATE, "f8_net_run: a stage-chain launch needs %d co-resident workgroups per image, the device has %d compute units (plan with fuse_chain = 0 / fuse_bchain = 0)", st.tiles, net->num_cu);
-        return 0;
+// Geometry of a chain launch (S_CHAIN / S_BCHAIN) over N images on num_cu compute units (0: 256 assumed).  *stack: ChainArgs::stack as bound
+// (2 = tile columns of image pairs), set back to 1 where the slots do not hold a pair's tiles; *tiles: workgroups per tile column.  Returns the
+// image groups (clusters, in the 7x7 cluster form) resident at once, 0 where the slots do not hold one column (one cluster): every workgroup
+// of a chain launch must be resident.
+static int chain_geometry(const Step& st, int N, int num_cu, int32_t* stack, int* tiles) {
+    const int slots = (num_cu > 0 ? std::min(num_cu, 256) : 256) * st.wg_per_cu;
+    *tiles = st.tiles;
+    if (*stack == 2 && slots < st.tiles) {
+        const int R = std::get<ChainArgs>(st.args).R;
+        *stack = 1; *tiles = (st.H + R - 1) / R;
     }
-    if (!st.cluster) return chain_groups(N, slots / st.tiles);
-    const int ng = cchain_clusters(N, slots);
-    if (ng < 1) fail(F8_ERR_STATE, "f8_net_run: the 7x7 stage-chain launch needs 8 co-resident workgroups, the device has %d compute units (plan with fuse_chain7 = 0)", net->num_cu);
-    return ng;
+    if (slots < *tiles) return 0;
+    if (st.cluster) return cchain_clusters(N, slots);
+    return chain_groups(*stack == 2 ? (N + 1) / 2 : N, slots / *tiles);
+}
+
+static int chain_launch_groups(const f8_net* net, const Step& st, int N, int32_t* stack) {
+    int tiles = 0;
+    const int ng = chain_geometry(st, N, net->num_cu, stack, &tiles);
+    if (ng >= 1) return ng;
+    if (st.cluster) fail(F8_ERR_STATE, "f8_net_run: the 7x7 stage-chain launch needs 8 co-resident workgroups, the device has %d compute units (plan with fuse_chain7 = 0)", net->num_cu);
+    else fail(F8_ERR_STATE, "f8_net_run: a stage-chain launch needs %d co-resident workgroups per image, the device has %d compute units (plan with fuse_chain = 0 / fuse_bchain = 0)", tiles, net->num_cu);
+    return 0;
+}
+
+int f8_net_launch_grid(const f8_net* net, int i, int N, int num_cu, int* tiles, int* groups, int* grid, int* stack) {
+    if (!net || !net->finalized) return fail(F8_ERR_STATE, "f8_net_launch_grid: not finalized");
+    if (i < 0 || i >= (int)net->steps.size() || N < 1 || !tiles || !groups || !grid || !stack) return fail(F8_ERR_INVALID, "f8_net_launch_grid: index / batch / null pointer");
+    const Step& st = net->steps[i];
+    *tiles = *groups = *grid = *stack = 0;
+    if (st.kind != S_CHAIN && st.kind != S_BCHAIN) return F8_OK;
+    int32_t sk = st.kind == S_CHAIN ? std::get<ChainArgs>(st.args).stack : 1;
+    *groups = chain_geometry(st, N, num_cu, &sk, tiles);
+    *stack = sk < 1 ? 1 : sk;
+    *grid = *groups * (st.cluster ? 8 : *tiles);
+    return F8_OK;
 }
 
 // Runs one launch for images [n0, n0 + N) of the batch; c0 = the chunk's first image inside the arena (for_each_launch).  Every
@@ -2743,7 +2771,7 @@ static int run_step(const f8_net* net, const Step& st, const int32_t* input, voi
             if (a.tail || net->nodes[nd.chain[0]].fbd_a >= 0) a.x8in = (const int8_t*)fp(xF); else a.xr = (const int32_t*)fp(xF);
             if (a.tail) a.m2in = (const int8_t*)fp(T[st.src2_t].forms[st.src2_f]);
             a.N = N;
-            if ((a.NG = chain_launch_groups(net, st, N)) < 1) return F8_ERR_STATE;
+            if ((a.NG = chain_launch_groups(net, st, N, &a.stack)) < 1) return F8_ERR_STATE;
             fill_out(&a.out32, a.q);
             if (const int rc = chain_scratch(a)) return rc;
             e = launch_chain(a, st.inst, st.C, st.MID, st.H, st.W, st.cin0, s);
@@ -2755,7 +2783,7 @@ static int run_step(const f8_net* net, const Step& st, const int32_t* input, voi
             if (net->nodes[nd.bchain[0]].bds_a >= 0) { a.x8in = (const int8_t*)fp(xs.forms[st.src_f]); a.x8sc = (const int8_t*)fp(xs.forms[st.res_f]); }
             else a.xr = (const int32_t*)fp(xs.forms[st.src_f]);
             a.N = N;
-            if ((a.NG = chain_launch_groups(net, st, N)) < 1) return F8_ERR_STATE;
+            { int32_t one = 1; if ((a.NG = chain_launch_groups(net, st, N, &one)) < 1) return F8_ERR_STATE; }
             fill_out(&a.out32, a.q);
             if (const int rc = chain_scratch(a)) return rc;
             e = launch_bchain(a, st.inst, st.C, st.H, st.W, s);

@@ -144,6 +144,13 @@ class F8Net:
         check(self._L.f8_net_launch_kernel(self._h, i, buf, 256))
         return buf.value.decode()
 
+    def launch_grid(self, i, N, num_cu=0):
+        """Stage-chain geometry of planned launch i for N images on num_cu compute units (0: 256), f8_net_launch_grid:
+        (workgroups per tile column, groups, grid, images per tile column); zeros for other launches."""
+        v = [ctypes.c_int(0) for _ in range(4)]
+        check(self._L.f8_net_launch_grid(self._h, i, int(N), int(num_cu), *[ctypes.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
     # ---- execution (torch = device memory + stream plumbing) ---------------------------------
     def upload(self):
         check(self._L.f8_net_upload(self._h))
