@@ -86,9 +86,6 @@ struct Node {
     int pool = -1, pool_host = -1;       // 1x1 conv (hosting its residual join or not) <-> the average pool behind it, one launch (f8_pool.hip)
     int fbd_a = -1, fbd_b = -1;          // shortcut conv hosting a fused stage-opening block (DS): body.0 / body.2 (body.4 = `dual`)
     bool fbd_s2 = false;                 // ... whose 3x3 and shortcut have stride 2 (f8_opener.hip)
-    bool wreg = false;                   // 1x1 conv on conv1x1_wreg_kernel (f8_wreg.hip)
-    bool s2w = false;                    // 3x3 / stride 2 conv on conv3x3s2_wreg_kernel (f8_s2conv.hip)
-    bool wstat = false;                  // 1x1 conv / dual GEMM / residual join on conv1x1_wstat_kernel (f8_wstat.hip)
     int chain_into = -1;                 // host conv of a bottleneck block that runs inside a stage-chain launch: the host of the chain's LAST block
     std::vector<int> chain;              // host of the last block of a chain: the hosts of all its blocks, in order (f8_chain.hip)
     int bb_a = -1;                       // second 3x3 of a BasicBlock identity block that runs in a bchain launch: its first 3x3
@@ -113,9 +110,15 @@ struct Node {
     ConvTile tile{};
 };
 enum StepKind { S_INPUT, S_CONV, S_DW, S_ADD, S_MAXPOOL, S_AVGPOOL, S_REQUANT, S_OUTPUT, S_FUSED, S_STEMPOOL, S_IR, S_P12, S_CHAIN, S_BCHAIN, S_HEAD2, S_IRCHAIN };
+// The kernel of a step whose kind has several, chosen once by the step's emitter (pass 3); bind_step, run_step and f8_net_autotune switch on it.
+//   S_CONV:  conv_igemm (f8_kernels.hip), the LDS-patch 3x3 (f8_conv3x3.hip), conv1x1_wreg (f8_wreg.hip), conv1x1_wstat (f8_wstat.hip),
+//            conv3x3s2_wreg (f8_s2conv.hip), the 1x1 conv + average pool (f8_pool.hip), the classifier fc_dense (f8_fc.hip)
+//   S_FUSED: fused_bottleneck (identity or DS, f8_fused.hip) or the stride-2 opener (f8_opener.hip);  S_P12: fused_p12 (f8_p12.hip) or the opener
+enum Variant { V_NONE, V_IGEMM, V_PATCH3X3, V_WREG, V_WSTAT, V_S2WREG, V_POOL, V_FC, V_BOTTLENECK, V_P12, V_OPENER };
 struct OutSel { int t = -1; int f32 = -1; int f8[2] = {-1, -1}; };
 struct Step {
     int kind; int node;
+    Variant variant = V_NONE;
     int src_t = -1, src_f = -1;        // main input tensor / form
     int res_t = -1, res_f = -1;        // residual (conv) or second operand (add)
     int src2_t = -1, src2_f = -1;      // dual GEMM: input of the second conv
@@ -640,7 +643,7 @@ int f8_net_set_label(f8_net* net, int t, const char* label) {
 }
 
 // ------------------------------------------------------------------------------ planner
-static void pack_conv_weights(f8_net* net, Node& nd, const Tensor& src, const Tensor& dst) {
+static void pack_conv_weights(f8_net* net, Node& nd) {
     // Packed layout: [coutP][taps][CK] int8, K-contiguous per output channel, zero padded.
     // Generic: tap = (r,s), CK = Cs(src) channels.  Stem (cin <= 4, source = network input held as
     // haloed NHWC4): one "tap" per kernel ROW, CK = 32 bytes = 8 pixels x 4 channels of which
@@ -651,6 +654,7 @@ static void pack_conv_weights(f8_net* net, Node& nd, const Tensor& src, const Te
     // rows and columns are classified by their in-image tap mask and the table is
     // bias[rowclass * ncc + colclass][cout].  Signed inputs / unpadded convs have one class.
     const f8_conv_desc& d = nd.cd;
+    const Tensor& src = net->tensors[nd.a]; const Tensor& dst = net->tensors[nd.out];
     const int k = d.kernel;
     nd.coutP = round_up(d.cout, 32);
     if (nd.stem) { nd.ck = 32; nd.ktot = k * 32; }
@@ -737,13 +741,14 @@ static void pack_frag_weights(f8_net* net, Node& nd) {
                 memcpy(dst + (((size_t)t * steps + s) * 64 + l) * 16, src + (size_t)(t * 32 + (l & 31)) * nd.ktot + s * 32 + (l >> 5) * 16, 16);
 }
 
-static void pack_dw_weights(f8_net* net, Node& nd, const Tensor& src) {
+static void pack_dw_weights(f8_net* net, Node& nd) {
     // Two images of the depthwise weights:
     //  (1) [9][Cs] tap-major + plain bias            — scalar kernel (int32 outputs, fallback)
     //  (2) [Cs/4][9] dwords for the dot4 kernel: per 4-channel quad, dword e (0..3) = taps 0..3 of channel e,
     //      dword 4+e = taps 4..7 of channel e, dword 8 = tap 8 of the 4 channels; bias + 128 * sum(w) when the
     //      input is unsigned (stored biased; out-of-image taps are replaced by the biased zero in the kernel).
     const f8_conv_desc& d = nd.cd;
+    const Tensor& src = net->tensors[nd.a];
     nd.coutP = src.Cs; nd.ck = 0; nd.ktot = 0;
     nd.w_off = round_up_z(net->wblob.size(), 256);
     nd.b_off = round_up_z(nd.w_off + (size_t)9 * src.Cs, 256);
@@ -796,7 +801,6 @@ static void select_outputs(f8_net* net, int t, OutSel* o, std::vector<int>* extr
         }
 }
 
-// Name (layer key + kernel variant) and device symbol (as rocprofv3 prints it) of a conv step; depends on the tile.
 // Essential vector work of a launch (VERDICT r5 #1b: the counters' SQ_INSTS_VALU x 64 divided by this = issued / essential): per value of the
 // reference's semantics, with the cheapest exact integer forms of f8_device.h —
 //   an int8 value produced (in HBM or only in LDS): round-half-even shift + clamp + pack = 3 (v_bfe_u32, v_add3_u32, 1/2 v_ashr_pk_u8_i32, 1/4 v_perm_b32,
@@ -808,16 +812,24 @@ static bool only_stem_form(const Tensor& o) {           // the network input's o
     for (auto& F : o.forms) only = only && F.kind == FORM_STEM;
     return only;
 }
-static void label_conv_step(f8_net* net, Step& st, Node& nd) {          // the layer label (the kernel's name: bind_step)
-    auto& ND = net->nodes;
+// Name of a conv step: the kernel (its variant; the tile of conv_igemm) + the layer key.  (The device symbol, Step::kernel: bind_step.)
+static void label_conv_step(f8_net* net, Step& st, const Node& nd) {
     const f8_conv_desc& d = nd.cd;
+    const bool res = st.res_t >= 0;
+    const std::string key = nd.dual >= 0 ? tname(net, net->nodes[nd.dual].out) + "+" + tname(net, nd.out) : tname(net, nd.out);
     char buf[160];
-    if (nd.depthwise) snprintf(buf, sizeof buf, "dwconv3x3s%d:%s", d.stride, tname(net, nd.out).c_str());
-    else snprintf(buf, sizeof buf, "conv%dx%ds%d_t%dx%dx%d%s%s:%s", d.kernel, d.kernel, d.stride, nd.tile.bm, nd.tile.bn,
-                  nd.tile.bk, nd.stem ? "_stem" : "", st.res_t >= 0 ? "_res" : (nd.dual >= 0 ? "_dual" : ""),
-                  (nd.dual >= 0 ? tname(net, ND[nd.dual].out) + "+" + tname(net, nd.out) : tname(net, nd.out)).c_str());
-    if (nd.p3_R > 0) snprintf(buf, sizeof buf, "conv3x3s1_patch_R%dx%d_bn%d%s:%s", nd.p3_R, nd.p3_imgs, nd.p3_bn, st.res_t >= 0 ? "_res" : "",
-                              tname(net, nd.out).c_str());
+    switch (st.variant) {
+        case V_FC: st.name = "linear_dense:" + key; return;
+        case V_POOL: st.name = (res ? "conv1x1_res+avgpool:" : "conv1x1+avgpool:") + key; return;
+        case V_WSTAT: st.name = (nd.dual >= 0 ? "conv1x1_wstat_dual:" : res ? "conv1x1_wstat_res:" : "conv1x1_wstat:") + key; return;
+        case V_S2WREG: st.name = "conv3x3s2_wreg:" + key; return;
+        case V_WREG: st.name = "conv1x1s1_wreg:" + key; return;
+        case V_PATCH3X3: snprintf(buf, sizeof buf, "conv3x3s1_patch_R%dx%d_bn%d%s:%s", nd.p3_R, nd.p3_imgs, nd.p3_bn, res ? "_res" : "", key.c_str()); break;
+        default:
+            if (nd.depthwise) snprintf(buf, sizeof buf, "dwconv3x3s%d:%s", d.stride, key.c_str());
+            else snprintf(buf, sizeof buf, "conv%dx%ds%d_t%dx%dx%d%s%s:%s", d.kernel, d.kernel, d.stride, nd.tile.bm, nd.tile.bn,
+                          nd.tile.bk, nd.stem ? "_stem" : "", res ? "_res" : (nd.dual >= 0 ? "_dual" : ""), key.c_str());
+    }
     st.name = buf;
 }
 
@@ -844,13 +856,10 @@ static int bchain_pos(const f8_net* net, int host) {
 }
 
 // pass 1
-static void plan_residual_joins(f8_net* net, int max_batch) {
+static void plan_residual_joins(f8_net* net) {
     auto& T = net->tensors;
     auto& ND = net->nodes;
     const int nn = (int)ND.size();
-    const Options& opt = net->opt;
-    const int fuse_blocks = opt.fuse_blocks;
-    (void)T; (void)nn; (void)opt; (void)fuse_blocks; (void)max_batch;
     // ---- 1. residual fusion: an add rides in the epilogue of the LATER of its two producers when
     //         that producer is an MFMA conv nobody else reads and the other operand is already there.
     for (int i = 0; i < nn; ++i) {
@@ -876,7 +885,6 @@ static void plan_bottleneck_blocks(f8_net* net, int max_batch) {
     const int nn = (int)ND.size();
     const Options& opt = net->opt;
     const int fuse_blocks = opt.fuse_blocks;
-    (void)T; (void)nn; (void)opt; (void)fuse_blocks; (void)max_batch;
     // ---- 1b. whole-block fusion: 1x1(ReLU) -> 3x3 pad 1 (ReLU) -> 1x1 + residual with the block input,
     //          all stride 1, intermediates read by nobody else  ->  one launch (f8_fused.hip)
     for (int i = 0; fuse_blocks && i < nn; ++i) {
@@ -913,13 +921,11 @@ static void plan_bottleneck_blocks(f8_net* net, int max_batch) {
 }
 
 // pass 1c
-static void plan_dual_gemm_joins(f8_net* net, int max_batch) {
+static void plan_dual_gemm_joins(f8_net* net) {
     auto& T = net->tensors;
     auto& ND = net->nodes;
     const int nn = (int)ND.size();
     const Options& opt = net->opt;
-    const int fuse_blocks = opt.fuse_blocks;
-    (void)T; (void)nn; (void)opt; (void)fuse_blocks; (void)max_batch;
     // ---- 1c. downsample join: the add's two operands are both 1x1 / pad 0 convs (body.4 and the shortcut) and the
     //          earlier one feeds nothing else  ->  one dual-GEMM launch, its int32 result never touches HBM
     for (int i = 0; opt.fuse_dual && i < nn; ++i) {
@@ -939,13 +945,12 @@ static void plan_dual_gemm_joins(f8_net* net, int max_batch) {
 }
 
 // pass 1d
-static void plan_stage_opening_blocks(f8_net* net, int max_batch) {
+static void plan_stage_opening_blocks(f8_net* net) {
     auto& T = net->tensors;
     auto& ND = net->nodes;
     const int nn = (int)ND.size();
     const Options& opt = net->opt;
     const int fuse_blocks = opt.fuse_blocks;
-    (void)T; (void)nn; (void)opt; (void)fuse_blocks; (void)max_batch;
     // ---- 1d. stage-opening bottleneck at unchanged resolution: body.0 -> body.2 -> [body.4 + shortcut] in ONE launch
     for (int i = 0; fuse_blocks && i < nn; ++i) {
         Node& h = ND[i];
@@ -979,13 +984,12 @@ static void plan_stage_opening_blocks(f8_net* net, int max_batch) {
 }
 
 // pass 1f
-static void plan_stage_chains(f8_net* net, int max_batch) {
+static void plan_stage_chains(f8_net* net) {
     auto& T = net->tensors;
     auto& ND = net->nodes;
     const int nn = (int)ND.size();
     const Options& opt = net->opt;
     const int fuse_blocks = opt.fuse_blocks;
-    (void)T; (void)nn; (void)opt; (void)fuse_blocks; (void)max_batch;
     // ---- 1f. stage chains: consecutive bottleneck blocks at one resolution whose block-to-block tensors are read by nobody else
     //          -> ONE launch for all of them, the int32 residual stream stays in registers (f8_chain.hip).  A chain may start with
     //          the stage-opening block at unchanged resolution (1d) and continues through identity blocks (1b).
@@ -1077,13 +1081,12 @@ static void plan_stage_chains(f8_net* net, int max_batch) {
 }
 
 // pass 1g
-static void plan_basic_block_chains(f8_net* net, int max_batch) {
+static void plan_basic_block_chains(f8_net* net) {
     auto& T = net->tensors;
     auto& ND = net->nodes;
     const int nn = (int)ND.size();
     const Options& opt = net->opt;
     const int fuse_blocks = opt.fuse_blocks;
-    (void)T; (void)nn; (void)opt; (void)fuse_blocks; (void)max_batch;
     // ---- 1g. BasicBlock identity blocks (3x3 ReLU -> 3x3 + residual with the block input, all stride 1) -> f8_bchain.hip: ONE launch for
     //          the consecutive ones of a stage, the int32 stream in registers (a single block is a chain of one: both convs in one
     //          launch, `mid` only in LDS)
@@ -1172,13 +1175,11 @@ static void plan_basic_block_chains(f8_net* net, int max_batch) {
 }
 
 // pass 1e
-static void plan_inverted_residuals(f8_net* net, int max_batch) {
+static void plan_inverted_residuals(f8_net* net) {
     auto& T = net->tensors;
     auto& ND = net->nodes;
     const int nn = (int)ND.size();
     const Options& opt = net->opt;
-    const int fuse_blocks = opt.fuse_blocks;
-    (void)T; (void)nn; (void)opt; (void)fuse_blocks; (void)max_batch;
     // ---- 1e. MobileNet-V2 inverted residual: 1x1 expand (ReLU) -> depthwise 3x3 (ReLU) -> 1x1 project [+ residual with the
     //          block input], intermediates read by nobody else  ->  one launch (f8_ir.hip), the expanded tensors stay in LDS
     for (int i = 0; opt.fuse_ir && i < nn; ++i) {
@@ -1317,13 +1318,11 @@ static void plan_inverted_residual_chains(f8_net* net) {
 }
 
 // pass 1h
-static void plan_mobilenet_v2_head(f8_net* net, int max_batch) {
+static void plan_mobilenet_v2_head(f8_net* net) {
     auto& T = net->tensors;
     auto& ND = net->nodes;
     const int nn = (int)ND.size();
     const Options& opt = net->opt;
-    const int fuse_blocks = opt.fuse_blocks;
-    (void)T; (void)nn; (void)opt; (void)fuse_blocks; (void)max_batch;
     // ---- 1h. MobileNet-V2 head: network input -> 3x3 / 2 conv (cin <= 4 -> 32, ReLU) -> depthwise 3x3 (ReLU) -> 1x1 (32 -> <= 32), each read
     //          by nobody else  ->  ONE row-walking launch (f8_stem.hip, stem_rows_kernel<KIND, true>): the three convs hand their rows to
     //          each other in registers, the launch reads the caller's buffer itself
@@ -1358,13 +1357,11 @@ static void plan_mobilenet_v2_head(f8_net* net, int max_batch) {
 }
 
 // pass 1i
-static void plan_last_conv_and_pool(f8_net* net, int max_batch) {
+static void plan_last_conv_and_pool(f8_net* net) {
     auto& T = net->tensors;
     auto& ND = net->nodes;
     const int nn = (int)ND.size();
     const Options& opt = net->opt;
-    const int fuse_blocks = opt.fuse_blocks;
-    (void)T; (void)nn; (void)opt; (void)fuse_blocks; (void)max_batch;
     // ---- 1i. the network's last 1x1 conv (hosting its residual join, or a plain conv + ReLU) and the average pool behind it: ONE launch that sums the map's
     //          pixels in the epilogue (f8_pool.hip); the conv's int32 result — read by nobody but the pool — never exists
     for (int i = 0; opt.fuse_pool && i < nn; ++i) {
@@ -1392,13 +1389,11 @@ static void plan_last_conv_and_pool(f8_net* net, int max_batch) {
 }
 
 // pass 2
-static void plan_tensor_forms(f8_net* net, int max_batch) {
+static void plan_tensor_forms(f8_net* net) {
     auto& T = net->tensors;
     auto& ND = net->nodes;
     const int nn = (int)ND.size();
     const Options& opt = net->opt;
-    const int fuse_blocks = opt.fuse_blocks;
-    (void)T; (void)nn; (void)opt; (void)fuse_blocks; (void)max_batch;
     // ---- 2. which forms does each tensor need?  (reverse order: consumers before producers)
     {
         Tensor& O = T[net->out_t];
@@ -1462,8 +1457,7 @@ static void plan_tensor_forms(f8_net* net, int max_batch) {
                 nd.stem = !nd.depthwise && nd.cd.cin <= 4 && ND[s.prod].kind == N_INPUT && nd.cd.kernel <= 8 &&
                           s.consumers.size() == 1 && nd.a != net->out_t && n == 0;
                 if (nd.stem) {
-                    const int P = T[nd.out].H, Q = T[nd.out].W;
-                    (void)P;
+                    const int Q = T[nd.out].W;
                     const int f = add_form(s, FORM_STEM, 0, 0);
                     Form& F = s.forms[f];
                     F.sgn = nd.cd.input_signed ? 1 : 0;
@@ -1511,29 +1505,490 @@ static void plan_tensor_forms(f8_net* net, int max_batch) {
 
 }
 
-// pass 3
-static int emit_steps(f8_net* net, int max_batch) {
+// pass 3: the launches in node order, one emitter per launch family.  Each fills one Step: its input / output forms, the packed weights, the
+// algorithmic bytes / ops / essential vector work, the name.  The weight image assigns offsets in call order: every emitter packs its convs in
+// role order (block_convs), the order the plans were made with.
+
+// The convs of a block by role, from its host node (node ids, -1: the block has none) — body.0 / body.2 / body.4 and the shortcut:
+//   bottleneck identity block (fb_a): body.0, body.2, host = body.4;  stage-opening block (fbd_a: DS / stride-2 opener): body.0, body.2, host.dual =
+//   body.4, host = shortcut;  its join alone (tail, the first block of a chain): host.dual = body.4, host = shortcut;  BasicBlock (bb_a): first 3x3 =
+//   body.0, host = body.2;  opening BasicBlock (bds_a): body.0, body.2, host = shortcut;  inverted residual (ir_a; irc_a in a chain): expand =
+//   body.0, depthwise = body.2, host = project (body.4)
+struct BlockConvs { int b0 = -1, b2 = -1, b4 = -1, sc = -1; };
+static BlockConvs block_convs(const f8_net* net, int host) {
+    const Node& h = net->nodes[host];
+    BlockConvs r;
+    if (h.tail) { r.b4 = h.dual; r.sc = host; }
+    else if (h.fbd_a >= 0) { r.b0 = h.fbd_a; r.b2 = h.fbd_b; r.b4 = h.dual; r.sc = host; }
+    else if (h.bds_a >= 0) { r.b0 = h.bds_a; r.b2 = h.bds_b; r.sc = host; }
+    else if (h.fb_a >= 0) { r.b0 = h.fb_a; r.b2 = h.fb_b; r.b4 = host; }
+    else if (h.bb_a >= 0) { r.b0 = h.bb_a; r.b2 = host; }
+    else if (h.irc_a >= 0) { r.b0 = h.irc_a; r.b2 = h.irc_b; r.b4 = host; }
+    else if (h.ir_a >= 0) { r.b0 = h.ir_a; r.b2 = h.ir_b; r.b4 = host; }
+    return r;
+}
+// conv c's input: the tensor (*t) and its form in c's int8 consumer format (*f; pass 2 made it)
+static int conv_input_i8(const f8_net* net, const Node& c, int* t, int* f) {
+    int n = 0;
+    if (const int rc = consumer_format(net->tensors[c.a], c.cd, &n, "finalize")) return rc;
+    *t = c.a; *f = find_form(net->tensors[c.a], FORM_I8, n, c.cd.input_signed ? 1 : 0);
+    return F8_OK;
+}
+// a residual join (a << acc_shl) + (b << res_shl): dfl = fraclen of a - fraclen of b, the operand with the smaller fraclen shifts left
+static void join_shifts(int dfl, int32_t* acc_shl, int32_t* res_shl) { *acc_shl = dfl < 0 ? -dfl : 0; *res_shl = dfl > 0 ? dfl : 0; }
+// the tensor a conv's launch writes: the output of the residual join it hosts (the step applies its ReLU), else its own
+static int join_output(const f8_net* net, const Node& c, Step& st) {
+    if (c.fused_add < 0) return c.out;
+    st.relu1 = net->nodes[c.fused_add].relu;
+    return net->nodes[c.fused_add].out;
+}
+// bytes of a conv's packed weights + bias (depthwise: 9 taps + 4 bytes of bias per channel)
+static double weight_bytes(const f8_net* net, const Node& c) {
+    return c.depthwise ? (double)net->tensors[c.a].Cs * 13 : (double)c.coutP * (c.ktot + 4);
+}
+// multiply-adds x 2 of a conv per image
+static double conv_ops(const f8_net* net, const Node& c) {
+    const Tensor& o = net->tensors[c.out];
+    return 2.0 * o.H * o.W * c.cd.cout * (c.cd.cin / c.cd.groups) * c.cd.kernel * c.cd.kernel;
+}
+// bytes per image a step writes: its output forms over px pixels of map o
+static double out_bytes(const Step& st, const Tensor& o, double px) { return px * o.Cs * ((st.out.f32 >= 0 ? 4 : 0) + out_forms8(st)); }
+// packs a block's convs in role order (frag: also in MFMA-fragment order) and adds their ops / weight bytes to the step
+static void pack_block(f8_net* net, const BlockConvs& r, bool frag, Step& st) {
+    for (int c : {r.b0, r.b2, r.b4, r.sc}) {
+        if (c < 0) continue;
+        Node& n = net->nodes[c];
+        if (n.depthwise) pack_dw_weights(net, n); else pack_conv_weights(net, n);
+        if (frag) pack_frag_weights(net, n);
+        st.ops_per_img += conv_ops(net, n); st.bytes_const += weight_bytes(net, n);
+    }
+}
+// "body.0+body.2+..." of a block's output tensors, role order
+static std::string block_names(const f8_net* net, const BlockConvs& r) {
+    std::string s;
+    for (int c : {r.b0, r.b2, r.b4, r.sc}) if (c >= 0) s += (s.empty() ? "" : "+") + tname(net, net->nodes[c].out);
+    return s;
+}
+
+static int emit_input(f8_net* net, int i, Step& st, std::vector<int>* extra) {
+    Tensor& o = net->tensors[net->nodes[i].out];
+    st.kind = S_INPUT;
+    if (o.forms.empty()) add_form(o, FORM_I32, 0, 0);
+    // int8 formats that need a real shift (quant_input=1 on the network input) go through the
+    // int32 form + a stand-alone requant; the n == 0 format is a plain narrowing in the input kernel
+    for (size_t f = 0; f < o.forms.size(); ++f)
+        if (o.forms[f].kind == FORM_I8 && o.forms[f].n != 0) extra->push_back((int)f);
+    if (!extra->empty()) add_form(o, FORM_I32, 0, 0);
+    st.out.t = net->nodes[i].out;
+    st.name = "input";
+    double b = (double)o.C * o.H * o.W * 4;
+    for (auto& F : o.forms) b += (double)o.H * o.W * (F.kind == FORM_I32 ? o.Cs * 4 : (F.kind == FORM_STEM ? 4 : o.Cs));
+    st.bytes_per_img = b;
+    return F8_OK;
+}
+
+// MobileNet-V2 head: 3x3 / 2 conv + depthwise 3x3 + this 1x1 in one launch
+static int emit_head2(f8_net* net, int i, Step& st, std::vector<int>* extra) {
+    auto& T = net->tensors; auto& ND = net->nodes;
+    Node& nd = ND[i]; Node& hh = ND[nd.h2_head]; Node& hb = ND[nd.h2_dw];
+    const Tensor& s = T[hh.a];
+    st.kind = S_HEAD2;
+    st.src_t = hh.a; st.src_f = find_form(s, FORM_STEM, 0, 0);
+    pack_conv_weights(net, hh);
+    pack_dw_weights(net, hb);
+    pack_conv_weights(net, nd);
+    select_outputs(net, nd.out, &st.out, extra);
+    const Tensor& o = T[nd.out];
+    const double cpx = (double)o.H * o.W;
+    st.ops_per_img = 2.0 * cpx * (32.0 * hh.cd.cin * 9 + 32.0 * 9 + 32.0 * nd.cd.cout);
+    st.valu_per_img = 3.0 * cpx * (32.0 + 32.0 + o.Cs * out_forms8(st));
+    st.bytes_per_img = (double)s.H * s.W * 4 + out_bytes(st, o, cpx);      // (int8 outputs only: pass 1h)
+    st.bytes_const = 32.0 * 100 + 32.0 * 13 + 32.0 * 36;
+    st.name = "head3x3s2+dw3x3+1x1:" + tname(net, hh.out) + "+" + tname(net, hb.out) + "+" + tname(net, nd.out);
+    return F8_OK;
+}
+
+// ResNet head: stem conv + max-pool in one launch
+static int emit_stem_pool(f8_net* net, int i, Step& st, std::vector<int>* extra) {
     auto& T = net->tensors;
-    auto& ND = net->nodes;
-    const int nn = (int)ND.size();
+    Node& nd = net->nodes[i];
+    const Node& pl = net->nodes[nd.sp_pool];
+    const Tensor& s = T[nd.a]; const Tensor& o = T[pl.out];
+    st.kind = S_STEMPOOL;
+    st.src_t = nd.a; st.src_f = find_form(s, FORM_STEM, 0, 0);
+    st.relu0 = nd.cd.relu;
+    pack_conv_weights(net, nd);
+    select_outputs(net, pl.out, &st.out, extra);
+    const double cpx = (double)T[nd.out].H * T[nd.out].W, opx = (double)o.H * o.W;
+    st.ops_per_img = conv_ops(net, nd);
+    st.valu_per_img = cpx * nd.cd.cout + 3.0 * opx * o.Cs * out_forms8(st);      // one max per conv value; the requantisation runs on the pooled ones
+    st.bytes_per_img = (double)s.H * s.W * 4 + out_bytes(st, o, opx);
+    st.bytes_const = weight_bytes(net, nd);
+    st.name = "stem7x7s2+maxpool3x3s2:" + tname(net, nd.out) + "+" + tname(net, pl.out);
+    return F8_OK;
+}
+
+// BasicBlock chain: node i is the second conv of its LAST block
+static int emit_bchain(f8_net* net, int i, Step& st, std::vector<int>* extra) {
+    auto& T = net->tensors; auto& ND = net->nodes;
+    const Node& nd = ND[i];
+    const std::vector<int>& ch = nd.bchain;
+    const BlockConvs r0 = block_convs(net, ch[0]);
+    const bool ds = r0.sc >= 0;                  // the chain starts with the stage-opening block: ch[0] is its shortcut conv
+    const Node& f1 = ND[r0.b0];
+    const Tensor& x = T[f1.a];
+    st.kind = S_BCHAIN;
+    if (!ds) { st.src_t = f1.a; st.src_f = find_form(x, FORM_I32, 0, 0); }
+    else if (int rc = conv_input_i8(net, f1, &st.src_t, &st.src_f)) return rc;      // its two convs over the block input may read
+    else if ((rc = conv_input_i8(net, ND[r0.sc], &st.res_t, &st.res_f))) return rc;  // different int8 forms of it
+    for (int h : ch) pack_block(net, block_convs(net, h), true, st);
+    const int out_t = ND[nd.fused_add].out;
+    select_outputs(net, out_t, &st.out, extra);
+    const Tensor& o = T[out_t];
+    const double px = (double)o.H * o.W;
+    st.bytes_per_img = (ds ? (double)x.H * x.W * x.Cs + (st.res_f != st.src_f ? px * x.Cs : 0) : px * x.Cs * 4) + out_bytes(st, o, px);
+    st.valu_per_img = (double)ch.size() * px * o.C * (3.0 + 2.0 + 3.0) - 3.0 * px * o.C + 3.0 * px * o.Cs * out_forms8(st);   // per block: first conv's int8, join, the next block's int8 input; the last block's are the output forms
+    st.name = "basic_chain_x" + std::to_string(ch.size()) + (ds ? "_ds:" : ":") + tname(net, f1.out) + ".." + tname(net, nd.out);
+    return F8_OK;
+}
+
+// stage chain: node i is the host conv of its LAST block
+static int emit_chain(f8_net* net, int i, Step& st, std::vector<int>* extra) {
+    auto& T = net->tensors; auto& ND = net->nodes;
+    const Node& nd = ND[i];
+    const std::vector<int>& ch = nd.chain;
+    const BlockConvs r0 = block_convs(net, ch[0]);
+    const bool tail = r0.b0 < 0;                 // first block = the join of a stride-2 opening block (its body.0 + body.2: the S_P12 step in front)
+    const bool ds = r0.sc >= 0;                  // ... or a stage-opening block: the chain reads an int8 form of the stage input
+    const Node& a0 = ND[tail ? r0.b4 : r0.b0];
+    const Tensor& x = T[ND[ds ? r0.sc : r0.b0].a];
+    st.kind = S_CHAIN;
+    if (!ds) { st.src_t = a0.a; st.src_f = find_form(x, FORM_I32, 0, 0); }
+    else if (int rc = conv_input_i8(net, ND[tail ? r0.sc : r0.b0], &st.src_t, &st.src_f)) return rc;    // tail: the shortcut's int8 form
+    else if (tail && (rc = conv_input_i8(net, a0, &st.src2_t, &st.src2_f))) return rc;                  // mid2 in body.4's format
+    for (int h : ch) pack_block(net, block_convs(net, h), true, st);
+    int out_t = ND[nd.fused_add].out;
+    const Tensor& o = T[out_t];                  // the stage's output map (geometry of the chain)
+    if (nd.pool >= 0) {                          // ... summed over its pixels in the launch (1i): the step's outputs are the POOLED tensor's forms
+        out_t = ND[nd.pool].out;
+        if (T[out_t].forms.empty()) add_form(T[out_t], FORM_I32, 0, 0);
+    }
+    select_outputs(net, out_t, &st.out, extra);
+    const double px = (double)o.H * o.W, opx = nd.pool >= 0 ? 1.0 : px;
+    st.bytes_per_img = (tail ? px * (x.Cs + T[st.src2_t].Cs) : px * x.Cs * (ds ? 1 : 4)) + out_bytes(st, o, opx);   // the stage input, once (tail: the shortcut's pixels + mid2)
+    // per block: body.0's and body.2's int8 outputs (the TAIL join has none), the join, the next block's int8 input (last block: the output forms)
+    const double mid = (double)(tail ? a0.cd.cin : a0.cd.cout);
+    st.valu_per_img = px * ((double)(ch.size() - (tail ? 1 : 0)) * 2.0 * mid * 3.0 + (double)ch.size() * o.C * 2.0 + (double)(ch.size() - 1) * o.C * 3.0) +
+                      opx * 3.0 * o.Cs * out_forms8(st) + (nd.pool >= 0 ? px * o.C : 0.0);
+    st.name = "stage_chain_x" + std::to_string(ch.size()) + (tail ? "_tail" : (ds ? "_ds" : "")) + (nd.pool >= 0 ? "+avgpool:" : ":") + tname(net, a0.out) + ".." + tname(net, nd.out);
+    return F8_OK;
+}
+
+// fused bottleneck block (node i = body.4), or fused stage-opening block: DS, or the stride-2 opener (node i = the shortcut conv, i.dual = body.4)
+static int emit_fused(f8_net* net, int i, Step& st, std::vector<int>* extra) {
+    auto& T = net->tensors; auto& ND = net->nodes;
+    const Node& nd = ND[i];
+    const BlockConvs r = block_convs(net, i);
+    const Node& na = ND[r.b0]; const Node& nb = ND[r.b2]; const Node& ng = ND[r.b4];
+    const bool ds = r.sc >= 0;
+    const Tensor& x = T[na.a];                   // (DS: body.0 and the shortcut read one int8 form of it, pass 1d)
+    st.kind = S_FUSED;
+    st.variant = nd.fbd_s2 ? V_OPENER : V_BOTTLENECK;
+    if (const int rc = conv_input_i8(net, na, &st.src_t, &st.src_f)) return rc;
+    pack_block(net, r, false, st);
+    if (!ds) { st.res_t = na.a; st.res_f = find_form(x, FORM_I32, 0, 0); }
+    join_shifts(T[nd.out].fl - (ds ? T[ng.out].fl : x.fl), &st.acc_shl, &st.res_shl);     // DS: > 0: body.4's result shifts left
+    const int out_t = join_output(net, nd, st);
+    select_outputs(net, out_t, &st.out, extra);
+    const Tensor& o = T[out_t];
+    const double px = (double)x.H * x.W, pxo = (double)o.H * o.W;   // stride-2 opener: body.0 runs on the input map
+    st.valu_per_img = 3.0 * (px * na.cd.cout + pxo * nb.cd.cout) + pxo * o.C * 2.0 + 3.0 * pxo * o.Cs * out_forms8(st);
+    st.bytes_per_img = px * x.Cs * (ds ? 1 : 1 + 4) + out_bytes(st, o, pxo);                // int8 input (identity: + int32 residual), once each
+    st.name = std::string(!ds ? "fused_bottleneck_R" : nd.fbd_s2 ? "fused_opener_s2_R" : "fused_bottleneck_ds_R") + std::to_string(nd.fb_R) + ":" +
+              block_names(net, r);
+    return F8_OK;
+}
+
+// 1x1 -> 3x3 of a 7x7 bottleneck block in one launch (node i = the 3x3), or body.0 + body.2 of a stride-2 opening block whose join opens its chain
+static int emit_p12(f8_net* net, int i, Step& st, std::vector<int>* extra) {
+    auto& T = net->tensors;
+    Node& nd = net->nodes[i]; Node& na = net->nodes[nd.p12_a];
+    const Tensor& x = T[na.a];
+    st.kind = S_P12;
+    st.variant = nd.p12_s2 ? V_OPENER : V_P12;
+    if (const int rc = conv_input_i8(net, na, &st.src_t, &st.src_f)) return rc;
+    pack_conv_weights(net, na);
+    pack_conv_weights(net, nd);
+    if (st.variant == V_P12) { pack_frag_weights(net, na); pack_frag_weights(net, nd); }      // f8_opener.hip streams the plain [cout][K] images
+    st.relu0 = nd.cd.relu;
+    select_outputs(net, nd.out, &st.out, extra);
+    if (st.out.f32 >= 0) return fail(F8_ERR_UNSUPPORTED, "finalize: the fused 1x1 -> 3x3 launch writes int8 forms only");
+    if (st.variant == V_OPENER && (st.out.f8[0] < 0 || st.out.f8[1] >= 0)) return fail(F8_ERR_UNSUPPORTED, "finalize: the stride-2 1x1 -> 3x3 launch writes exactly one int8 form");
+    const Tensor& o = T[nd.out];
+    const double px = (double)x.H * x.W, pxo = (double)o.H * o.W;
+    st.ops_per_img = conv_ops(net, na) + conv_ops(net, nd);
+    st.valu_per_img = 3.0 * (px * na.cd.cout + pxo * o.Cs * out_forms8(st));
+    st.bytes_per_img = px * x.Cs + out_bytes(st, o, pxo);
+    st.bytes_const = weight_bytes(net, na) + weight_bytes(net, nd);
+    st.name = std::string(st.variant == V_OPENER ? "fused_opener_s2_p12_R" + std::to_string(nd.fb_R) + ":" : "fused_p12:") + tname(net, na.out) + "+" + tname(net, nd.out);
+    return F8_OK;
+}
+
+// inverted-residual chain: node i is the project conv of its LAST block
+static int emit_irchain(f8_net* net, int i, Step& st, std::vector<int>* extra) {
+    auto& T = net->tensors; auto& ND = net->nodes;
+    const Node& nd = ND[i];
+    const std::vector<int>& ch = nd.irchain;
+    const Node& fa = ND[block_convs(net, ch[0]).b0];
+    const Tensor& x = T[fa.a];
+    st.kind = S_IRCHAIN;
+    if (const int rc = conv_input_i8(net, fa, &st.src_t, &st.src_f)) return rc;
+    if (ND[ch[0]].fused_add >= 0) { st.res_t = fa.a; st.res_f = find_form(x, FORM_I32, 0, 0); }
+    const double px = (double)x.H * x.W;
+    double valu = 0;
+    std::string blocks;
+    for (size_t k = 0; k < ch.size(); ++k) {
+        const Node& c = ND[ch[k]];
+        const BlockConvs r = block_convs(net, ch[k]);
+        pack_block(net, r, false, st);
+        const int bo = c.fused_add >= 0 ? ND[c.fused_add].out : c.out;
+        valu += 3.0 * px * (ND[r.b0].cd.cout + ND[r.b2].cd.cout) + (c.fused_add >= 0 ? 2.0 * px * T[bo].C : 0.0) + (k + 1 < ch.size() ? 3.0 * px * T[bo].Cs : 0.0);
+        const std::string& lb = T[bo].label;
+        blocks += (k ? "+" : "") + (lb.empty() ? tname(net, bo) : lb.substr(0, lb.find('.')));
+    }
+    const int out_t = join_output(net, nd, st);
+    st.relu0 = nd.cd.relu;
+    select_outputs(net, out_t, &st.out, extra);
+    const Tensor& o = T[out_t];
+    st.bytes_per_img = px * x.Cs + (st.res_t >= 0 ? px * x.Cs * 4 : 0) + out_bytes(st, o, px);
+    st.valu_per_img = valu + 3.0 * px * o.Cs * out_forms8(st);
+    st.name = "ir_chain_x" + std::to_string(ch.size()) + ":" + blocks;
+    return F8_OK;
+}
+
+// fused inverted residual: node i is the project conv
+static int emit_ir(f8_net* net, int i, Step& st, std::vector<int>* extra) {
+    auto& T = net->tensors; auto& ND = net->nodes;
+    const Node& nd = ND[i];
+    const BlockConvs r = block_convs(net, i);
+    const Node& na = ND[r.b0]; const Node& nb = ND[r.b2];
+    const Tensor& x = T[na.a];
+    st.kind = S_IR;
+    if (const int rc = conv_input_i8(net, na, &st.src_t, &st.src_f)) return rc;
+    pack_block(net, r, false, st);
+    st.relu0 = nd.cd.relu;
+    const int out_t = join_output(net, nd, st);
+    if (nd.fused_add >= 0) {
+        st.res_t = na.a; st.res_f = find_form(x, FORM_I32, 0, 0);
+        join_shifts(T[nd.out].fl - x.fl, &st.acc_shl, &st.res_shl);
+    }
+    select_outputs(net, out_t, &st.out, extra);
+    const Tensor& o = T[out_t];
+    const double px = (double)x.H * x.W, pxo = (double)o.H * o.W;
+    st.valu_per_img = 3.0 * (px * na.cd.cout + pxo * nb.cd.cout) + (st.res_t >= 0 ? 2.0 * pxo * o.C : 0.0) + 3.0 * pxo * o.Cs * out_forms8(st);
+    st.bytes_per_img = px * x.Cs + (st.res_t >= 0 ? px * x.Cs * 4 : 0) + out_bytes(st, o, pxo);
+    char kb[200];
+    snprintf(kb, sizeof kb, "fused_ir_s%d_%s:", nb.cd.stride, nd.ir_G > 1 ? ("G" + std::to_string(nd.ir_G)).c_str() : ("R" + std::to_string(nd.ir_R)).c_str());
+    st.name = kb + block_names(net, r);
+    return F8_OK;
+}
+
+// The kernel of a plain conv step (not depthwise), once its inputs and outputs are known; the first that applies, in this order.
+static Variant conv_variant(const f8_net* net, const Node& nd, const Step& st, int max_batch) {
     const Options& opt = net->opt;
-    const int fuse_blocks = opt.fuse_blocks;
-    (void)T; (void)nn; (void)opt; (void)fuse_blocks; (void)max_batch;
-    // ---- 3. emit steps in node order
-    net->steps.clear();
-    auto emit_requants = [&](int t, const std::vector<int>& extra) {
-        for (int f : extra) {
-            Step st; st.kind = S_REQUANT; st.node = T[t].prod;
-            st.src_t = t; st.src_f = find_form(T[t], FORM_I32, 0, 0);
-            st.out.t = t; st.out.f8[0] = f;
-            st.name = "requant:" + tname(net, t);
-            const double e = (double)T[t].H * T[t].W * T[t].Cs;
-            st.bytes_per_img = e * 5;
-            net->steps.push_back(st);
+    const f8_conv_desc& d = nd.cd;
+    const Tensor& s = net->tensors[nd.a]; const Tensor& o = net->tensors[nd.out];
+    if (st.dense) return V_FC;                   // the classifier: logits straight into the caller's buffer (f8_fc.hip)
+    if (nd.pool >= 0) return V_POOL;             // ... and the average pool behind the last 1x1 conv (1i)
+    const bool plain = !nd.stem && d.groups == 1;
+    // the stride-2 3x3 of a late stage-opening block, int8 outputs only: input patch in LDS, weights straight to registers
+    if (opt.s2wreg && plain && d.kernel == 3 && d.stride == 2 && d.pad == 1 && nd.fused_add < 0 && nd.dual < 0 && st.out.f32 < 0 && nd.ck == d.cin &&
+        s.H == 2 * o.H && s.W == 2 * o.W && conv3x3s2_wreg_supported(nd.ck, o.H, o.W, nd.coutP)) return V_S2WREG;
+    // 1x1 convs (plain, with the residual join, or as the dual GEMM of a stage-opening block) whose weight slice per wave
+    // fits the register file: weight-stationary kernel, when a launch gives every workgroup a few pixel tiles to walk
+    if (opt.wstat && plain && d.kernel == 1 && d.pad == 0) {
+        const Node* g = nd.dual >= 0 ? &net->nodes[nd.dual] : nullptr;
+        const int k1 = g ? g->ktot : 0;
+        if ((!g || (g->cd.kernel == 1 && g->cd.pad == 0 && g->cd.groups == 1)) && conv1x1_wstat_supported(nd.ck, k1, nd.coutP, st.res_t >= 0)) {
+            const int imgs = opt.whole_batch_launches ? max_batch : std::max(1, max_batch / opt.split);
+            const long tiles = ((long)imgs * ((long)o.H * o.W) + 31) / 32;
+            const int ngroups = nd.coutP / (32 * conv1x1_wstat_waves(nd.ck, k1));
+            const int cus = net->num_cu > 0 ? net->num_cu : 256;
+            if (tiles >= (long)opt.wstat_min_tiles * std::max(1, cus / ngroups)) return V_WSTAT;
         }
-    };
-    for (int i = 0; i < nn; ++i) {
-        Node& nd = ND[i];
+    }
+    // late, weight-heavy 1x1 convs with int8 outputs only: weights straight to registers (f8_wreg.hip)
+    if (opt.wreg && plain && d.kernel == 1 && d.stride == 1 && d.pad == 0 && nd.fused_add < 0 && nd.dual < 0 && st.out.f32 < 0 &&
+        conv1x1_wreg_supported(nd.ck, nd.coutP)) return V_WREG;
+    return nd.p3_R > 0 ? V_PATCH3X3 : V_IGEMM;
+}
+// the conv kernels that read the weights in MFMA-fragment order (pack_frag_weights)
+static bool reads_frag_weights(Variant v) { return v == V_FC || v == V_POOL || v == V_WSTAT || v == V_S2WREG || v == V_WREG; }
+
+// a conv / linear / depthwise conv of its own, with its residual join or dual GEMM and the average pool behind it
+static int emit_conv(f8_net* net, int i, int max_batch, Step& st, std::vector<int>* extra) {
+    auto& T = net->tensors; auto& ND = net->nodes;
+    const Options& opt = net->opt;
+    Node& nd = ND[i];
+    const f8_conv_desc& d = nd.cd;
+    const Tensor& s = T[nd.a];
+    st.kind = nd.depthwise ? S_DW : S_CONV;
+    if (nd.stem) { st.src_t = nd.a; st.src_f = find_form(s, FORM_STEM, 0, 0); }
+    else if (const int rc = conv_input_i8(net, nd, &st.src_t, &st.src_f)) return rc;
+    st.relu0 = d.relu;
+    if (nd.depthwise) pack_dw_weights(net, nd);
+    else {
+        pack_conv_weights(net, nd);
+        const int M1 = T[nd.out].H * T[nd.out].W;
+        if (!pick_conv_tile(M1 * max_batch, nd.coutP, nd.ck, nd.fused_add >= 0, opt.bk128 != 0, &nd.tile))
+            return fail(F8_ERR_UNSUPPORTED, "finalize: no conv kernel instance for ck=%d coutP=%d", nd.ck, nd.coutP);
+        if (nd.dual >= 0) {       // the dual-GEMM instances: 128x64 / 64x64, or 128x128 where many cout tiles re-read X
+            const int wide = opt.dual_wide;   // measured: 7x7x2048 join 67 -> 52 us; 14x14x1024 and 28x28x512 are slower with the wide tile
+            nd.tile.bk = 64;
+            if (nd.coutP >= wide && nd.tile.bm == 128) nd.tile.bn = 128; else nd.tile.bn = 64;
+        }
+        if (!nd.stem && d.groups == 1 && d.kernel == 3 && d.stride == 1 && d.pad == 1 && nd.ck == d.cin && opt.patch3x3 &&
+            !conv3x3_patch_config(d.cin, s.H, s.W, nd.coutP, &nd.p3_R, &nd.p3_imgs, &nd.p3_bn)) nd.p3_R = 0;
+    }
+    int out_t = join_output(net, nd, st);
+    if (nd.fused_add >= 0) {
+        const Node& ad = ND[nd.fused_add];
+        const int other = (ad.a == nd.out) ? ad.b : ad.a;
+        if (nd.dual >= 0) {
+            if (const int rc = conv_input_i8(net, ND[nd.dual], &st.src2_t, &st.src2_f)) return rc;
+            pack_conv_weights(net, ND[nd.dual]);
+        } else {
+            st.res_t = other; st.res_f = find_form(T[other], FORM_I32, 0, 0);
+        }
+        join_shifts(T[nd.out].fl - T[other].fl, &st.acc_shl, &st.res_shl);     // > 0: the residual shifts left
+    }
+    if (nd.pool >= 0) {                          // ... and the average pool: the step's outputs are the POOLED tensor's forms
+        out_t = ND[nd.pool].out;
+        if (T[out_t].forms.empty()) add_form(T[out_t], FORM_I32, 0, 0);
+    }
+    const Tensor& o = T[out_t];
+    if (o.dense_out) { st.dense = true; st.out.t = out_t; }
+    else select_outputs(net, out_t, &st.out, extra);
+    if (!nd.depthwise) st.variant = conv_variant(net, nd, st, max_batch);
+    const Node* g = nd.dual >= 0 ? &ND[nd.dual] : nullptr;
+    const double opix = (double)T[nd.out].H * T[nd.out].W, outpix = nd.pool >= 0 ? 1.0 : opix;
+    st.ops_per_img = conv_ops(net, nd) + (g ? conv_ops(net, *g) : 0.0);
+    double b = (double)s.H * s.W * (nd.stem ? 4 : s.Cs);            // input once
+    if (st.res_t >= 0) b += opix * o.Cs * 4;
+    if (g) b += (double)T[g->a].H * T[g->a].W * T[g->a].Cs;
+    if (st.dense) b += (double)d.cout * 4;
+    st.bytes_per_img = b + out_bytes(st, o, outpix);
+    st.valu_per_img = ((st.res_t >= 0 || g) ? 2.0 * opix * o.C : 0.0) + (nd.pool >= 0 ? opix * o.C : 0.0) + 3.0 * outpix * o.Cs * out_forms8(st) + (nd.depthwise ? 9.0 * opix * d.cout / 4.0 : 0.0);   // (a VALU depthwise conv: one v_dot4 per four taps)
+    st.bytes_const = weight_bytes(net, nd) + (g ? weight_bytes(net, *g) : 0.0);
+    label_conv_step(net, st, nd);
+    if (reads_frag_weights(st.variant)) pack_frag_weights(net, nd);
+    if (st.variant == V_WSTAT && g) pack_frag_weights(net, ND[nd.dual]);
+    return F8_OK;
+}
+
+// the launch of conv node i: the families are tried in this order, which decides between marks that hold at once (chain_into with fb_a, ...)
+static int emit_conv_family(f8_net* net, int i, int max_batch, Step& st, std::vector<int>* extra) {
+    const Node& nd = net->nodes[i];
+    if (nd.h2_head >= 0) return emit_head2(net, i, st, extra);
+    if (nd.sp_pool >= 0 && nd.stem) return emit_stem_pool(net, i, st, extra);
+    if (nd.bchain_into == i) return emit_bchain(net, i, st, extra);
+    if (nd.chain_into == i) return emit_chain(net, i, st, extra);
+    if (nd.fbd_a >= 0) return emit_fused(net, i, st, extra);
+    if (nd.p12_a >= 0) return emit_p12(net, i, st, extra);
+    if (nd.irc_into == i) return emit_irchain(net, i, st, extra);
+    if (nd.ir_a >= 0) return emit_ir(net, i, st, extra);
+    if (nd.fb_a >= 0) return emit_fused(net, i, st, extra);
+    return emit_conv(net, i, max_batch, st, extra);
+}
+
+static int emit_add(f8_net* net, int i, Step& st, std::vector<int>* extra) {
+    auto& T = net->tensors;
+    const Node& nd = net->nodes[i];
+    st.kind = S_ADD;
+    st.src_t = nd.a; st.src_f = find_form(T[nd.a], FORM_I32, 0, 0);
+    st.res_t = nd.b; st.res_f = find_form(T[nd.b], FORM_I32, 0, 0);
+    join_shifts(T[nd.a].fl - T[nd.b].fl, &st.acc_shl, &st.res_shl);
+    st.relu1 = nd.relu;
+    select_outputs(net, nd.out, &st.out, extra);
+    st.name = "add:" + tname(net, nd.out);
+    const Tensor& o = T[nd.out];
+    st.bytes_per_img = (double)o.H * o.W * o.Cs * 8 + out_bytes(st, o, (double)o.H * o.W);
+    return F8_OK;
+}
+
+static int emit_maxpool(f8_net* net, int i, Step& st, std::vector<int>* extra) {
+    auto& T = net->tensors;
+    const Node& nd = net->nodes[i];
+    const Tensor& s = T[nd.a]; Tensor& o = T[nd.out];
+    st.kind = S_MAXPOOL;
+    st.src_t = nd.a;
+    const bool i8 = (o.forms.size() == 1 && o.forms[0].kind == FORM_I8);
+    st.src_f = i8 ? find_form(s, FORM_I8, o.forms[0].n, o.forms[0].sgn) : find_form(s, FORM_I32, 0, 0);
+    if (o.forms.empty()) add_form(o, FORM_I32, 0, 0);
+    select_outputs(net, nd.out, &st.out, extra);
+    st.name = std::string(i8 ? "maxpool_i8:" : "maxpool_i32:") + tname(net, nd.out);
+    st.bytes_per_img = (double)s.H * s.W * s.Cs * (i8 ? 1 : 4) + out_bytes(st, o, (double)o.H * o.W);
+    return F8_OK;
+}
+
+static int emit_avgpool(f8_net* net, int i, Step& st, std::vector<int>* extra) {
+    auto& T = net->tensors;
+    const Node& nd = net->nodes[i];
+    const Tensor& s = T[nd.a]; Tensor& o = T[nd.out];
+    st.kind = S_AVGPOOL;
+    st.src_t = nd.a; st.src_f = find_form(s, FORM_I32, 0, 0);
+    if (o.forms.empty()) add_form(o, FORM_I32, 0, 0);
+    select_outputs(net, nd.out, &st.out, extra);
+    st.name = "avgpool_sum:" + tname(net, nd.out);
+    st.bytes_per_img = (double)s.H * s.W * s.Cs * 4 + (double)o.Cs * 5;
+    return F8_OK;
+}
+
+// the int8 forms of tensor t beyond the two its producer writes: stand-alone requants of its int32 form
+static void emit_requants(f8_net* net, int t, const std::vector<int>& extra) {
+    for (int f : extra) {
+        const Tensor& x = net->tensors[t];
+        Step st; st.kind = S_REQUANT; st.node = x.prod;
+        st.src_t = t; st.src_f = find_form(x, FORM_I32, 0, 0);
+        st.out.t = t; st.out.f8[0] = f;
+        st.name = "requant:" + tname(net, t);
+        st.bytes_per_img = (double)x.H * x.W * x.Cs * 5;
+        net->steps.push_back(st);
+    }
+}
+
+// the network output's launch, unless the classifier writes the caller's buffer itself
+static void emit_output(f8_net* net) {
+    const Tensor& x = net->tensors[net->out_t];
+    if (x.dense_out) return;
+    Step st; st.kind = S_OUTPUT; st.node = x.prod;
+    st.src_t = net->out_t; st.src_f = find_form(x, FORM_I32, 0, 0);
+    st.name = "output:" + tname(net, net->out_t);
+    st.bytes_per_img = (double)x.H * x.W * (x.Cs + x.C) * 4;
+    net->steps.push_back(st);
+}
+
+// the fused stem launch can read the raw input itself: the input step then launches nothing (run_step)
+static void let_stem_read_input(f8_net* net) {
+    for (auto& st : net->steps) {
+        if (st.kind != S_INPUT) continue;
+        const Tensor& o = net->tensors[st.out.t];
+        if (!only_stem_form(o) || o.C != 3 || !net->opt.fuse_input) continue;
+        Step* stem = nullptr; int users = 0;
+        for (auto& s2 : net->steps) if (s2.src_t == st.out.t) { ++users; if (s2.kind == S_STEMPOOL || s2.kind == S_HEAD2) stem = &s2; }
+        if (stem && users == 1) {
+            st.raw_input = stem->raw_input = true;
+            stem->bytes_per_img += (double)o.C * o.H * o.W * 4 - (double)o.H * o.W * 4;      // int32 planes instead of the NHWC4 copy
+            st.bytes_per_img = 0;
+            st.name = "input(read by the stem launch)";
+        }
+    }
+}
+
+static int emit_steps(f8_net* net, int max_batch) {
+    net->steps.clear();
+    for (int i = 0; i < (int)net->nodes.size(); ++i) {
+        const Node& nd = net->nodes[i];
         if (nd.kind == N_ADD && nd.fused_into >= 0) continue;
         if (nd.kind == N_CONV && (nd.absorbed_by >= 0 || nd.dual_host >= 0)) continue;
         if (nd.kind == N_CONV && nd.chain_into >= 0 && nd.chain_into != i) continue;      // runs inside the chain launch of a later block
@@ -1543,504 +1998,26 @@ static int emit_steps(f8_net* net, int max_batch) {
         if (nd.kind == N_AVGPOOL && nd.pool_host >= 0) continue;     // runs in its conv's launch
         Step st; st.node = i;
         std::vector<int> extra;
-        int out_t = nd.out;
+        int rc = F8_OK;
         switch (nd.kind) {
-            case N_INPUT: {
-                st.kind = S_INPUT;
-                Tensor& o = T[nd.out];
-                if (o.forms.empty()) add_form(o, FORM_I32, 0, 0);
-                // int8 formats that need a real shift (quant_input=1 on the network input) go through the
-                // int32 form + a stand-alone requant; the n == 0 format is a plain narrowing in the input kernel
-                for (size_t f = 0; f < o.forms.size(); ++f)
-                    if (o.forms[f].kind == FORM_I8 && o.forms[f].n != 0) extra.push_back((int)f);
-                if (!extra.empty()) add_form(o, FORM_I32, 0, 0);
-                st.out.t = nd.out;
-                st.name = "input";
-                double b = (double)o.C * o.H * o.W * 4;
-                for (auto& F : o.forms) b += (double)o.H * o.W * (F.kind == FORM_I32 ? o.Cs * 4 : (F.kind == FORM_STEM ? 4 : o.Cs));
-                st.bytes_per_img = b;
-                break;
-            }
-            case N_CONV: case N_LINEAR: {
-                if (nd.h2_head >= 0) {
-                    // ---- MobileNet-V2 head: 3x3 / 2 conv + depthwise 3x3 + this 1x1 in one launch
-                    Node& hh = ND[nd.h2_head]; Node& hb = ND[nd.h2_dw];
-                    Tensor& s = T[hh.a];
-                    st.kind = S_HEAD2;
-                    st.src_t = hh.a; st.src_f = find_form(s, FORM_STEM, 0, 0);
-                    pack_conv_weights(net, hh, s, T[hh.out]);
-                    pack_dw_weights(net, hb, T[hb.a]);
-                    pack_conv_weights(net, nd, T[nd.a], T[nd.out]);
-                    select_outputs(net, out_t, &st.out, &extra);
-                    Tensor& o = T[out_t];
-                    const double cpx = (double)o.H * o.W;
-                    st.ops_per_img = 2.0 * cpx * (32.0 * hh.cd.cin * 9 + 32.0 * 9 + 32.0 * nd.cd.cout);
-                    st.valu_per_img = 3.0 * cpx * (32.0 + 32.0 + o.Cs * out_forms8(st));
-                    st.bytes_per_img = (double)s.H * s.W * 4 + cpx * o.Cs * ((st.out.f8[0] >= 0) + (st.out.f8[1] >= 0));
-                    st.bytes_const = 32.0 * 100 + 32.0 * 13 + 32.0 * 36;
-                    st.name = "head3x3s2+dw3x3+1x1:" + tname(net, hh.out) + "+" + tname(net, hb.out) + "+" + tname(net, nd.out);
-                    break;
-                }
-                if (nd.sp_pool >= 0 && nd.stem) {
-                    // ---- ResNet head: stem conv + max-pool in one launch
-                    const Node& pl = ND[nd.sp_pool];
-                    Tensor& s = T[nd.a]; Tensor& o = T[pl.out];
-                    st.kind = S_STEMPOOL;
-                    st.src_t = nd.a; st.src_f = find_form(s, FORM_STEM, 0, 0);
-                    st.relu0 = nd.cd.relu;
-                    pack_conv_weights(net, nd, s, T[nd.out]);
-                    out_t = pl.out;
-                    select_outputs(net, out_t, &st.out, &extra);
-                    const f8_conv_desc& d = nd.cd;
-                    const double cpx = (double)T[nd.out].H * T[nd.out].W;
-                    st.ops_per_img = 2.0 * cpx * d.cout * d.cin * d.kernel * d.kernel;
-                    st.valu_per_img = cpx * d.cout + 3.0 * (double)o.H * o.W * o.Cs * out_forms8(st);      // one max per conv value; the requantisation runs on the pooled ones
-                    st.bytes_per_img = (double)s.H * s.W * 4 + (double)o.H * o.W * o.Cs * ((st.out.f32 >= 0 ? 4 : 0) + (st.out.f8[0] >= 0) + (st.out.f8[1] >= 0));
-                    st.bytes_const = (double)nd.coutP * (nd.ktot + 4);
-                    st.name = "stem7x7s2+maxpool3x3s2:" + tname(net, nd.out) + "+" + tname(net, pl.out);
-                    break;
-                }
-                if (nd.bchain_into == i) {
-                    // ---- BasicBlock chain: nd is the second conv of its LAST block
-                    const std::vector<int> ch = nd.bchain;
-                    Node& f2 = ND[ch[0]];
-                    const bool ds = f2.bds_a >= 0;               // the chain starts with the stage-opening block: f2 is its shortcut conv
-                    Node& f1 = ND[ds ? f2.bds_a : f2.bb_a];
-                    Tensor& x = T[f1.a];
-                    st.kind = S_BCHAIN;
-                    st.src_t = f1.a;
-                    if (ds) {
-                        int n0 = 0; consumer_format(x, f1.cd, &n0, "finalize"); st.src_f = find_form(x, FORM_I8, n0, f1.cd.input_signed ? 1 : 0);
-                        int n1 = 0; consumer_format(x, f2.cd, &n1, "finalize"); st.res_t = f1.a; st.res_f = find_form(x, FORM_I8, n1, f2.cd.input_signed ? 1 : 0);
-                    } else st.src_f = find_form(x, FORM_I32, 0, 0);
-                    double ops = 0, wbytes = 0;
-                    for (int hi : ch) {
-                        const bool hds = ND[hi].bds_a >= 0;
-                        Node* cv[3] = {&ND[hds ? ND[hi].bds_a : ND[hi].bb_a], hds ? &ND[ND[hi].bds_b] : &ND[hi], hds ? &ND[hi] : nullptr};
-                        for (Node* c : cv) {
-                            if (!c) continue;
-                            pack_conv_weights(net, *c, T[c->a], T[c->out]);
-                            pack_frag_weights(net, *c);
-                            ops += 2.0 * T[c->out].H * T[c->out].W * (double)c->cd.kernel * c->cd.kernel * c->cd.cin * c->cd.cout;
-                            wbytes += (double)c->coutP * (c->ktot + 4);
-                        }
-                    }
-                    out_t = ND[nd.fused_add].out;
-                    select_outputs(net, out_t, &st.out, &extra);
-                    Tensor& o = T[out_t];
-                    const double px = (double)o.H * o.W;
-                    double b = ds ? (double)x.H * x.W * x.Cs + (st.res_f != st.src_f ? px * x.Cs : 0) : px * x.Cs * 4;
-                    if (st.out.f32 >= 0) b += px * o.Cs * 4;
-                    for (int k = 0; k < 2; ++k) if (st.out.f8[k] >= 0) b += px * o.Cs;
-                    st.ops_per_img = ops; st.bytes_per_img = b; st.bytes_const = wbytes;
-                    st.valu_per_img = (double)ch.size() * px * o.C * (3.0 + 2.0 + 3.0) - 3.0 * px * o.C + 3.0 * px * o.Cs * out_forms8(st);   // per block: first conv's int8, join, the next block's int8 input; the last block's are the output forms
-                    st.name = "basic_chain_x" + std::to_string(ch.size()) + (ds ? "_ds:" : ":") + tname(net, f1.out) + ".." + tname(net, nd.out);
-                    break;
-                }
-                if (nd.chain_into == i) {
-                    // ---- stage chain: nd is the host conv of its LAST block
-                    const std::vector<int> ch = nd.chain;
-                    Node& hf = ND[ch[0]];
-                    const bool tail = hf.tail;                  // first block = the join of a stride-2 opening block (its body.0 + body.2: the S_P12 step in front)
-                    const bool ds = hf.fbd_a >= 0 || tail;
-                    Tensor& x = T[ds ? hf.a : ND[hf.fb_a].a];
-                    st.kind = S_CHAIN;
-                    st.src_t = ds ? hf.a : ND[hf.fb_a].a;
-                    if (tail) {
-                        int n0 = 0; consumer_format(x, hf.cd, &n0, "finalize"); st.src_f = find_form(x, FORM_I8, n0, hf.cd.input_signed ? 1 : 0);      // the shortcut's int8 form
-                        const Node& g0 = ND[hf.dual];
-                        int n2 = 0; consumer_format(T[g0.a], g0.cd, &n2, "finalize");
-                        st.src2_t = g0.a; st.src2_f = find_form(T[g0.a], FORM_I8, n2, g0.cd.input_signed ? 1 : 0);                                      // mid2 in body.4's format
-                    }
-                    else if (ds) { int n0 = 0; consumer_format(x, ND[hf.fbd_a].cd, &n0, "finalize"); st.src_f = find_form(x, FORM_I8, n0, ND[hf.fbd_a].cd.input_signed ? 1 : 0); }
-                    else st.src_f = find_form(x, FORM_I32, 0, 0);
-                    double ops = 0, wbytes = 0;
-                    for (int hi : ch) {
-                        Node& hh = ND[hi];
-                        const bool hds = hh.fbd_a >= 0, htl = hh.tail;
-                        Node* cv[4] = {htl ? nullptr : &ND[hds ? hh.fbd_a : hh.fb_a], htl ? nullptr : &ND[hds ? hh.fbd_b : hh.fb_b], (hds || htl) ? &ND[hh.dual] : &hh, (hds || htl) ? &hh : nullptr};
-                        for (Node* c : cv) {
-                            if (!c) continue;
-                            pack_conv_weights(net, *c, T[c->a], T[c->out]);
-                            pack_frag_weights(net, *c);
-                            const double px = (double)T[c->out].H * T[c->out].W;
-                            ops += 2.0 * px * c->cd.cin * c->cd.cout * c->cd.kernel * c->cd.kernel;
-                            wbytes += (double)c->coutP * (c->ktot + 4);
-                        }
-                    }
-                    out_t = ND[nd.fused_add].out;
-                    Tensor& o = T[out_t];                        // the stage's output map (geometry of the chain)
-                    if (nd.pool >= 0) {                          // ... summed over its pixels in the launch (1i): the step's outputs are the POOLED tensor's forms
-                        out_t = ND[nd.pool].out;
-                        if (T[out_t].forms.empty()) add_form(T[out_t], FORM_I32, 0, 0);
-                    }
-                    select_outputs(net, out_t, &st.out, &extra);
-                    const double px = (double)o.H * o.W, opx = nd.pool >= 0 ? 1.0 : px;
-                    double b = tail ? px * (x.Cs + T[st.src2_t].Cs) : px * x.Cs * (ds ? 1 : 4);   // the stage input, once (tail: the shortcut's pixels + mid2)
-                    if (st.out.f32 >= 0) b += opx * o.Cs * 4;
-                    for (int k = 0; k < 2; ++k) if (st.out.f8[k] >= 0) b += opx * o.Cs;
-                    st.ops_per_img = ops; st.bytes_per_img = b; st.bytes_const = wbytes;
-                    {   // per block: body.0's and body.2's int8 outputs (the TAIL join has none), the join, the next block's int8 input (last block: the output forms)
-                        const double mid = (double)(tail ? ND[hf.dual].cd.cin : ND[ds ? hf.fbd_a : hf.fb_a].cd.cout);
-                        st.valu_per_img = px * ((double)(ch.size() - (tail ? 1 : 0)) * 2.0 * mid * 3.0 + (double)ch.size() * o.C * 2.0 + (double)(ch.size() - 1) * o.C * 3.0) +
-                                          opx * 3.0 * o.Cs * out_forms8(st) + (nd.pool >= 0 ? px * o.C : 0.0);
-                    }
-                    const Node& a0 = tail ? ND[hf.dual] : ND[ds ? hf.fbd_a : hf.fb_a];
-                    st.name = "stage_chain_x" + std::to_string(ch.size()) + (tail ? "_tail" : (ds ? "_ds" : "")) + (nd.pool >= 0 ? "+avgpool:" : ":") + tname(net, a0.out) + ".." + tname(net, nd.out);
-                    break;
-                }
-                if (nd.fbd_a >= 0) {
-                    // ---- fused stage-opening block (DS): nd is the shortcut conv, nd.dual the block's last body conv
-                    Node& na = ND[nd.fbd_a]; Node& nb = ND[nd.fbd_b]; Node& ng = ND[nd.dual];
-                    Tensor& x = T[nd.a];
-                    st.kind = S_FUSED;
-                    st.src_t = nd.a;
-                    int n0 = 0; consumer_format(x, na.cd, &n0, "finalize");
-                    st.src_f = find_form(x, FORM_I8, n0, na.cd.input_signed ? 1 : 0);
-                    pack_conv_weights(net, na, x, T[na.out]);
-                    pack_conv_weights(net, nb, T[nb.a], T[nb.out]);
-                    pack_conv_weights(net, ng, T[ng.a], T[ng.out]);
-                    pack_conv_weights(net, nd, x, T[nd.out]);
-                    const Node& ad = ND[nd.fused_add];
-                    const int dfl = T[nd.out].fl - T[ng.out].fl;          // > 0: body.4's result shifts left
-                    st.acc_shl = dfl < 0 ? -dfl : 0; st.res_shl = dfl > 0 ? dfl : 0;
-                    st.relu1 = ad.relu;
-                    out_t = ad.out;
-                    select_outputs(net, out_t, &st.out, &extra);
-                    Tensor& o = T[out_t];
-                    const double px = (double)x.H * x.W, pxo = (double)o.H * o.W;   // stride-2 opener: body.0 runs on the input map
-                    st.ops_per_img = 2.0 * (px * (double)na.cd.cin * na.cd.cout + pxo * (9.0 * nb.cd.cin * nb.cd.cout + (double)ng.cd.cin * ng.cd.cout +
-                                                                                         (double)nd.cd.cin * nd.cd.cout));
-                    st.valu_per_img = 3.0 * (px * na.cd.cout + pxo * nb.cd.cout) + pxo * o.C * 2.0 + 3.0 * pxo * o.Cs * out_forms8(st);
-                    double b = px * x.Cs;                                           // int8 input once
-                    if (st.out.f32 >= 0) b += pxo * o.Cs * 4;
-                    for (int k = 0; k < 2; ++k) if (st.out.f8[k] >= 0) b += pxo * o.Cs;
-                    st.bytes_per_img = b;
-                    st.bytes_const = (double)na.coutP * (na.ktot + 4) + (double)nb.coutP * (nb.ktot + 4) + (double)ng.coutP * (ng.ktot + 4) +
-                                     (double)nd.coutP * (nd.ktot + 4);
-                    st.name = std::string(nd.fbd_s2 ? "fused_opener_s2_R" : "fused_bottleneck_ds_R") + std::to_string(nd.fb_R) + ":" + tname(net, na.out) + "+" +
-                              tname(net, nb.out) + "+" + tname(net, ng.out) + "+" + tname(net, nd.out);
-                    break;
-                }
-                if (nd.p12_a >= 0) {
-                    // ---- 1x1 -> 3x3 of a 7x7 bottleneck block in one launch: nd is the 3x3
-                    Node& na = ND[nd.p12_a];
-                    Tensor& x = T[na.a];
-                    st.kind = S_P12;
-                    st.src_t = na.a;
-                    int n0 = 0; consumer_format(x, na.cd, &n0, "finalize");
-                    st.src_f = find_form(x, FORM_I8, n0, na.cd.input_signed ? 1 : 0);
-                    pack_conv_weights(net, na, x, T[na.out]);
-                    pack_conv_weights(net, nd, T[nd.a], T[nd.out]);
-                    if (!nd.p12_s2) { pack_frag_weights(net, na); pack_frag_weights(net, nd); }      // f8_opener.hip streams the plain [cout][K] images
-                    st.relu0 = nd.cd.relu;
-                    select_outputs(net, out_t, &st.out, &extra);
-                    if (st.out.f32 >= 0) return fail(F8_ERR_UNSUPPORTED, "finalize: the fused 1x1 -> 3x3 launch writes int8 forms only");
-                    if (nd.p12_s2 && (st.out.f8[0] < 0 || st.out.f8[1] >= 0)) return fail(F8_ERR_UNSUPPORTED, "finalize: the stride-2 1x1 -> 3x3 launch writes exactly one int8 form");
-                    Tensor& o = T[out_t];
-                    const double px = (double)x.H * x.W, pxo = (double)o.H * o.W;
-                    st.ops_per_img = 2.0 * (px * (double)na.cd.cin * na.cd.cout + pxo * 9.0 * nd.cd.cin * nd.cd.cout);
-                    st.valu_per_img = 3.0 * (px * na.cd.cout + pxo * o.Cs * out_forms8(st));
-                    double b = px * x.Cs;
-                    for (int k = 0; k < 2; ++k) if (st.out.f8[k] >= 0) b += pxo * o.Cs;
-                    st.bytes_per_img = b;
-                    st.bytes_const = (double)na.coutP * (na.ktot + 4) + (double)nd.coutP * (nd.ktot + 4);
-                    st.name = std::string(nd.p12_s2 ? "fused_opener_s2_p12_R" + std::to_string(nd.fb_R) + ":" : "fused_p12:") + tname(net, na.out) + "+" + tname(net, nd.out);
-                    break;
-                }
-                if (nd.irc_into == i) {
-                    // ---- inverted-residual chain: nd is the project conv of its LAST block
-                    const std::vector<int> ch = nd.irchain;
-                    const Node& f = ND[ch[0]];
-                    Node& fa = ND[f.irc_a];
-                    Tensor& x = T[fa.a];
-                    st.kind = S_IRCHAIN;
-                    st.src_t = fa.a;
-                    int n0 = 0; consumer_format(x, fa.cd, &n0, "finalize");
-                    st.src_f = find_form(x, FORM_I8, n0, fa.cd.input_signed ? 1 : 0);
-                    if (f.fused_add >= 0) { st.res_t = fa.a; st.res_f = find_form(x, FORM_I32, 0, 0); }
-                    const double px = (double)x.H * x.W;
-                    double ops = 0, wbytes = 0, valu = 0;
-                    std::string blocks;
-                    for (size_t k = 0; k < ch.size(); ++k) {
-                        Node& c = ND[ch[k]]; Node& na = ND[c.irc_a]; Node& nb = ND[c.irc_b];
-                        pack_conv_weights(net, na, T[na.a], T[na.out]);
-                        nb.depthwise = true;
-                        pack_dw_weights(net, nb, T[nb.a]);
-                        pack_conv_weights(net, c, T[c.a], T[c.out]);
-                        ops += 2.0 * px * ((double)na.cd.cin * na.cd.cout + 9.0 * nb.cd.cout + (double)c.cd.cin * c.cd.cout);
-                        wbytes += (double)na.coutP * (na.ktot + 4) + (double)T[nb.a].Cs * 13 + (double)c.coutP * (c.ktot + 4);
-                        const int bo = c.fused_add >= 0 ? ND[c.fused_add].out : c.out;
-                        valu += 3.0 * px * (na.cd.cout + nb.cd.cout) + (c.fused_add >= 0 ? 2.0 * px * T[bo].C : 0.0) + (k + 1 < ch.size() ? 3.0 * px * T[bo].Cs : 0.0);
-                        const std::string& lb = T[bo].label;
-                        blocks += (k ? "+" : "") + (lb.empty() ? tname(net, bo) : lb.substr(0, lb.find('.')));
-                    }
-                    if (nd.fused_add >= 0) {
-                        const Node& ad = ND[nd.fused_add];
-                        st.relu1 = ad.relu;
-                        out_t = ad.out;
-                    }
-                    st.relu0 = nd.cd.relu;
-                    select_outputs(net, out_t, &st.out, &extra);
-                    Tensor& o = T[out_t];
-                    double b = px * x.Cs + (st.res_t >= 0 ? px * x.Cs * 4 : 0);
-                    if (st.out.f32 >= 0) b += px * o.Cs * 4;
-                    for (int k = 0; k < 2; ++k) if (st.out.f8[k] >= 0) b += px * o.Cs;
-                    st.ops_per_img = ops; st.bytes_per_img = b; st.bytes_const = wbytes;
-                    st.valu_per_img = valu + 3.0 * px * o.Cs * out_forms8(st);
-                    st.name = "ir_chain_x" + std::to_string(ch.size()) + ":" + blocks;
-                    break;
-                }
-                if (nd.ir_a >= 0) {
-                    // ---- fused inverted residual: nd is the project conv
-                    Node& na = ND[nd.ir_a]; Node& nb = ND[nd.ir_b];
-                    Tensor& x = T[na.a];
-                    st.kind = S_IR;
-                    st.src_t = na.a;
-                    int n0 = 0; consumer_format(x, na.cd, &n0, "finalize");
-                    st.src_f = find_form(x, FORM_I8, n0, na.cd.input_signed ? 1 : 0);
-                    pack_conv_weights(net, na, x, T[na.out]);
-                    nb.depthwise = true;
-                    pack_dw_weights(net, nb, T[nb.a]);
-                    pack_conv_weights(net, nd, T[nd.a], T[nd.out]);
-                    st.relu0 = nd.cd.relu;
-                    if (nd.fused_add >= 0) {
-                        const Node& ad = ND[nd.fused_add];
-                        st.res_t = na.a; st.res_f = find_form(x, FORM_I32, 0, 0);
-                        const int dfl = T[nd.out].fl - x.fl;
-                        st.acc_shl = dfl < 0 ? -dfl : 0; st.res_shl = dfl > 0 ? dfl : 0;
-                        st.relu1 = ad.relu;
-                        out_t = ad.out;
-                    }
-                    select_outputs(net, out_t, &st.out, &extra);
-                    Tensor& o = T[out_t];
-                    const double px = (double)x.H * x.W, pxo = (double)o.H * o.W;
-                    st.ops_per_img = 2.0 * (px * na.cd.cin * na.cd.cout + pxo * 9.0 * nb.cd.cout + pxo * (double)nd.cd.cin * nd.cd.cout);
-                    st.valu_per_img = 3.0 * (px * na.cd.cout + pxo * nb.cd.cout) + (st.res_t >= 0 ? 2.0 * pxo * o.C : 0.0) + 3.0 * pxo * o.Cs * out_forms8(st);
-                    double b = px * x.Cs + (st.res_t >= 0 ? px * x.Cs * 4 : 0);
-                    if (st.out.f32 >= 0) b += pxo * o.Cs * 4;
-                    for (int k = 0; k < 2; ++k) if (st.out.f8[k] >= 0) b += pxo * o.Cs;
-                    st.bytes_per_img = b;
-                    st.bytes_const = (double)na.coutP * (na.ktot + 4) + (double)T[nb.a].Cs * 13 + (double)nd.coutP * (nd.ktot + 4);
-                    char kb[200];
-                    snprintf(kb, sizeof kb, "fused_ir_s%d_%s:", nb.cd.stride, nd.ir_G > 1 ? ("G" + std::to_string(nd.ir_G)).c_str() : ("R" + std::to_string(nd.ir_R)).c_str());
-                    st.name = std::string(kb) + tname(net, na.out) + "+" + tname(net, nb.out) + "+" + tname(net, nd.out);
-                    break;
-                }
-                if (nd.fb_a >= 0) {
-                    // ---- fused bottleneck block: nd is its last conv
-                    Node& na = ND[nd.fb_a]; Node& nb = ND[nd.fb_b];
-                    Tensor& x = T[na.a];
-                    st.kind = S_FUSED;
-                    st.src_t = na.a;
-                    int n0 = 0; consumer_format(x, na.cd, &n0, "finalize");
-                    st.src_f = find_form(x, FORM_I8, n0, na.cd.input_signed ? 1 : 0);
-                    pack_conv_weights(net, na, x, T[na.out]);
-                    pack_conv_weights(net, nb, T[nb.a], T[nb.out]);
-                    pack_conv_weights(net, nd, T[nd.a], T[nd.out]);
-                    const Node& ad = ND[nd.fused_add];
-                    st.res_t = na.a; st.res_f = find_form(x, FORM_I32, 0, 0);
-                    const int dfl = T[nd.out].fl - x.fl;
-                    st.acc_shl = dfl < 0 ? -dfl : 0; st.res_shl = dfl > 0 ? dfl : 0;
-                    st.relu1 = ad.relu;
-                    out_t = ad.out;
-                    select_outputs(net, out_t, &st.out, &extra);
-                    Tensor& o = T[out_t];
-                    const double px = (double)x.H * x.W;
-                    st.ops_per_img = 2.0 * px * ((double)na.cd.cin * na.cd.cout + 9.0 * nb.cd.cin * nb.cd.cout + (double)nd.cd.cin * nd.cd.cout);
-                    st.valu_per_img = px * (3.0 * (na.cd.cout + nb.cd.cout) + 2.0 * o.C + 3.0 * o.Cs * out_forms8(st));
-                    double b = px * x.Cs * (1 + 4);                                 // int8 input + int32 residual, once each
-                    if (st.out.f32 >= 0) b += px * o.Cs * 4;
-                    for (int k = 0; k < 2; ++k) if (st.out.f8[k] >= 0) b += px * o.Cs;
-                    st.bytes_per_img = b;
-                    st.bytes_const = (double)na.coutP * (na.ktot + 4) + (double)nb.coutP * (nb.ktot + 4) + (double)nd.coutP * (nd.ktot + 4);
-                    st.name = "fused_bottleneck_R" + std::to_string(nd.fb_R) + ":" + tname(net, na.out) + "+" + tname(net, nb.out) + "+" + tname(net, nd.out);
-                    break;
-                }
-                Tensor& s = T[nd.a];
-                st.kind = nd.depthwise ? S_DW : S_CONV;
-                st.src_t = nd.a;
-                int n = 0; consumer_format(s, nd.cd, &n, "finalize");
-                st.src_f = nd.stem ? find_form(s, FORM_STEM, 0, 0) : find_form(s, FORM_I8, n, nd.cd.input_signed ? 1 : 0);
-                st.relu0 = nd.cd.relu;
-                if (nd.depthwise) pack_dw_weights(net, nd, s);
-                else {
-                    pack_conv_weights(net, nd, s, T[nd.out]);
-                    const int M1 = T[nd.out].H * T[nd.out].W;
-                    if (!pick_conv_tile(M1 * max_batch, nd.coutP, nd.ck, nd.fused_add >= 0, opt.bk128 != 0, &nd.tile))
-                        return fail(F8_ERR_UNSUPPORTED, "finalize: no conv kernel instance for ck=%d coutP=%d", nd.ck, nd.coutP);
-                    if (nd.dual >= 0) {       // the dual-GEMM instances: 128x64 / 64x64, or 128x128 where many cout tiles re-read X
-                        const int wide = opt.dual_wide;   // measured: 7x7x2048 join 67 -> 52 us; 14x14x1024 and 28x28x512 are slower with the wide tile
-                        nd.tile.bk = 64;
-                        if (nd.coutP >= wide && nd.tile.bm == 128) nd.tile.bn = 128; else nd.tile.bn = 64;
-                    }
-                    if (!nd.stem && nd.cd.groups == 1 && nd.cd.kernel == 3 && nd.cd.stride == 1 && nd.cd.pad == 1 && nd.ck == nd.cd.cin && opt.patch3x3 &&
-                        !conv3x3_patch_config(nd.cd.cin, s.H, s.W, nd.coutP, &nd.p3_R, &nd.p3_imgs, &nd.p3_bn)) nd.p3_R = 0;
-                }
-                if (nd.fused_add >= 0) {
-                    const Node& ad = ND[nd.fused_add];
-                    const int other = (ad.a == nd.out) ? ad.b : ad.a;
-                    if (nd.dual >= 0) {
-                        Node& g = ND[nd.dual];
-                        Tensor& s2 = T[g.a];
-                        int n2 = 0; consumer_format(s2, g.cd, &n2, "finalize");
-                        st.src2_t = g.a; st.src2_f = find_form(s2, FORM_I8, n2, g.cd.input_signed ? 1 : 0);
-                        pack_conv_weights(net, g, s2, T[g.out]);
-                    } else {
-                        st.res_t = other; st.res_f = find_form(T[other], FORM_I32, 0, 0);
-                    }
-                    const int dfl = T[nd.out].fl - T[other].fl;     // >0: residual shifts left
-                    st.acc_shl = dfl < 0 ? -dfl : 0; st.res_shl = dfl > 0 ? dfl : 0;
-                    st.relu1 = ad.relu;
-                    out_t = ad.out;
-                }
-                if (nd.pool >= 0) {                      // ... and the average pool: the step's outputs are the POOLED tensor's forms
-                    out_t = ND[nd.pool].out;
-                    if (T[out_t].forms.empty()) add_form(T[out_t], FORM_I32, 0, 0);
-                }
-                Tensor& o = T[out_t];
-                if (o.dense_out) { st.dense = true; st.out.t = out_t; }
-                else select_outputs(net, out_t, &st.out, &extra);
-                const f8_conv_desc& d = nd.cd;
-                const double opix = (double)T[nd.out].H * T[nd.out].W;
-                st.ops_per_img = 2.0 * opix * d.cout * (d.cin / d.groups) * d.kernel * d.kernel;
-                double b = (double)s.H * s.W * (nd.stem ? 4 : s.Cs);            // input once
-                if (st.res_t >= 0) b += opix * o.Cs * 4;
-                if (nd.dual >= 0) {
-                    const Node& g = ND[nd.dual];
-                    b += (double)T[g.a].H * T[g.a].W * T[g.a].Cs;
-                    st.ops_per_img += 2.0 * opix * g.cd.cout * g.cd.cin;
-                }
-                if (st.dense) b += (double)d.cout * 4;
-                const double outpix = nd.pool >= 0 ? 1.0 : opix;
-                if (st.out.f32 >= 0) b += outpix * o.Cs * 4;
-                for (int k = 0; k < 2; ++k) if (st.out.f8[k] >= 0) b += outpix * o.Cs;
-                st.bytes_per_img = b;
-                st.valu_per_img = ((st.res_t >= 0 || nd.dual >= 0) ? 2.0 * opix * o.C : 0.0) + (nd.pool >= 0 ? opix * o.C : 0.0) + 3.0 * outpix * o.Cs * out_forms8(st) + (nd.depthwise ? 9.0 * opix * d.cout / 4.0 : 0.0);   // (a VALU depthwise conv: one v_dot4 per four taps)
-                st.bytes_const = nd.depthwise ? (double)s.Cs * 13 : (double)nd.coutP * (nd.ktot + 4);
-                if (nd.dual >= 0) st.bytes_const += (double)ND[nd.dual].coutP * (ND[nd.dual].ktot + 4);
-                label_conv_step(net, st, nd);
-                if (st.dense) {                          // the classifier: logits straight into the caller's buffer (f8_fc.hip)
-                    pack_frag_weights(net, nd);
-                    st.name = "linear_dense:" + tname(net, nd.out);
-                }
-                // 1x1 convs (plain, with the residual join, or as the dual GEMM of a stage-opening block) whose weight slice per wave
-                // fits the register file: weight-stationary kernel, when a launch gives every workgroup a few pixel tiles to walk
-                if (nd.pool >= 0) {
-                    pack_frag_weights(net, nd);
-                    const size_t colon = st.name.find(':');
-                    st.name = std::string(st.res_t >= 0 ? "conv1x1_res+avgpool" : "conv1x1+avgpool") + (colon == std::string::npos ? ":" + tname(net, nd.out) : st.name.substr(colon));
-                } else
-                if (opt.wstat && !nd.depthwise && !nd.stem && d.kernel == 1 && d.pad == 0 && d.groups == 1 && !st.dense) {
-                    const int k1 = nd.dual >= 0 ? ND[nd.dual].ktot : 0;
-                    const bool has_res = nd.dual < 0 && st.res_t >= 0;
-                    const bool g_ok = nd.dual < 0 || (ND[nd.dual].cd.kernel == 1 && ND[nd.dual].cd.pad == 0 && ND[nd.dual].cd.groups == 1);
-                    if (g_ok && conv1x1_wstat_supported(nd.ck, k1, nd.coutP, has_res)) {
-                        const int imgs = opt.whole_batch_launches ? max_batch : std::max(1, max_batch / opt.split);
-                        const long tiles = ((long)imgs * (long)opix + 31) / 32;
-                        const int ngroups = nd.coutP / (32 * conv1x1_wstat_waves(nd.ck, k1));
-                        const int cus = net->num_cu > 0 ? net->num_cu : 256;
-                        if (tiles >= (long)opt.wstat_min_tiles * std::max(1, cus / ngroups)) {
-                            nd.wstat = true;
-                            pack_frag_weights(net, nd);
-                            if (nd.dual >= 0) pack_frag_weights(net, ND[nd.dual]);
-                            const size_t colon = st.name.find(':');
-                            st.name = std::string(nd.dual >= 0 ? "conv1x1_wstat_dual" : has_res ? "conv1x1_wstat_res" : "conv1x1_wstat") +
-                                      (colon == std::string::npos ? ":" + tname(net, nd.out) : st.name.substr(colon));
-                        }
-                    }
-                }
-                // the stride-2 3x3 of a late stage-opening block, int8 outputs only: input patch in LDS, weights straight to registers
-                if (nd.pool < 0 && opt.s2wreg && !nd.depthwise && !nd.stem && d.kernel == 3 && d.stride == 2 && d.pad == 1 && d.groups == 1 && nd.fused_add < 0 &&
-                    nd.dual < 0 && st.out.f32 < 0 && !st.dense && nd.ck == d.cin && s.H == 2 * T[nd.out].H && s.W == 2 * T[nd.out].W &&
-                    conv3x3s2_wreg_supported(nd.ck, T[nd.out].H, T[nd.out].W, nd.coutP)) {
-                    nd.s2w = true;
-                    pack_frag_weights(net, nd);
-                    st.name = "conv3x3s2_wreg:" + tname(net, nd.out);
-                }
-                // late, weight-heavy 1x1 convs with int8 outputs only: weights straight to registers (f8_wreg.hip)
-                if (nd.pool < 0 && !nd.wstat && opt.wreg && !nd.depthwise && !nd.stem && d.kernel == 1 && d.stride == 1 && d.pad == 0 && d.groups == 1 && nd.fused_add < 0 &&
-                    nd.dual < 0 && st.out.f32 < 0 && !st.dense && conv1x1_wreg_supported(nd.ck, nd.coutP)) {
-                    nd.wreg = true;
-                    pack_frag_weights(net, nd);
-                    st.name = "conv1x1s1_wreg:" + tname(net, nd.out);
-                }
-                break;
-            }
-            case N_ADD: {
-                st.kind = S_ADD;
-                st.src_t = nd.a; st.src_f = find_form(T[nd.a], FORM_I32, 0, 0);
-                st.res_t = nd.b; st.res_f = find_form(T[nd.b], FORM_I32, 0, 0);
-                const int dfl = T[nd.a].fl - T[nd.b].fl;
-                st.acc_shl = dfl < 0 ? -dfl : 0; st.res_shl = dfl > 0 ? dfl : 0;
-                st.relu1 = nd.relu;
-                select_outputs(net, nd.out, &st.out, &extra);
-                st.name = "add:" + tname(net, nd.out);
-                const double e = (double)T[nd.out].H * T[nd.out].W * T[nd.out].Cs;
-                st.bytes_per_img = e * 8 + (st.out.f32 >= 0 ? e * 4 : 0) + (st.out.f8[0] >= 0 ? e : 0) + (st.out.f8[1] >= 0 ? e : 0);
-                break;
-            }
-            case N_MAXPOOL: {
-                st.kind = S_MAXPOOL;
-                Tensor& s = T[nd.a]; Tensor& o = T[nd.out];
-                st.src_t = nd.a;
-                const bool i8 = (o.forms.size() == 1 && o.forms[0].kind == FORM_I8);
-                st.src_f = i8 ? find_form(s, FORM_I8, o.forms[0].n, o.forms[0].sgn) : find_form(s, FORM_I32, 0, 0);
-                if (o.forms.empty()) add_form(o, FORM_I32, 0, 0);
-                select_outputs(net, nd.out, &st.out, &extra);
-                st.name = std::string(i8 ? "maxpool_i8:" : "maxpool_i32:") + tname(net, nd.out);
-                const double ei = (double)s.H * s.W * s.Cs, eo = (double)o.H * o.W * o.Cs;
-                st.bytes_per_img = ei * (i8 ? 1 : 4) + (st.out.f32 >= 0 ? eo * 4 : 0) + (st.out.f8[0] >= 0 ? eo : 0) + (st.out.f8[1] >= 0 ? eo : 0);
-                break;
-            }
-            case N_AVGPOOL: {
-                st.kind = S_AVGPOOL;
-                Tensor& s = T[nd.a]; Tensor& o = T[nd.out];
-                st.src_t = nd.a; st.src_f = find_form(s, FORM_I32, 0, 0);
-                if (o.forms.empty()) add_form(o, FORM_I32, 0, 0);
-                select_outputs(net, nd.out, &st.out, &extra);
-                st.name = "avgpool_sum:" + tname(net, nd.out);
-                st.bytes_per_img = (double)s.H * s.W * s.Cs * 4 + (double)o.Cs * 5;
-                break;
-            }
+            case N_INPUT: rc = emit_input(net, i, st, &extra); break;
+            case N_CONV: case N_LINEAR: rc = emit_conv_family(net, i, max_batch, st, &extra); break;
+            case N_ADD: rc = emit_add(net, i, st, &extra); break;
+            case N_MAXPOOL: rc = emit_maxpool(net, i, st, &extra); break;
+            case N_AVGPOOL: rc = emit_avgpool(net, i, st, &extra); break;
         }
+        if (rc) return rc;
         net->steps.push_back(st);
-        emit_requants(st.out.t, extra);
+        emit_requants(net, st.out.t, extra);
     }
-    if (!T[net->out_t].dense_out) {
-        Step st; st.kind = S_OUTPUT; st.node = T[net->out_t].prod;
-        st.src_t = net->out_t; st.src_f = find_form(T[net->out_t], FORM_I32, 0, 0);
-        st.name = "output:" + tname(net, net->out_t);
-        st.bytes_per_img = (double)T[net->out_t].H * T[net->out_t].W * (T[net->out_t].Cs + T[net->out_t].C) * 4;
-        net->steps.push_back(st);
-    }
-
-    for (auto& st : net->steps)
-        if (st.kind == S_INPUT) {
-            const Tensor& o = T[st.out.t];
-            // the fused stem launch can read the raw input itself: the input step then launches nothing (run_step)
-            if (only_stem_form(o) && o.C == 3 && net->opt.fuse_input) {
-                Step* stem = nullptr; int users = 0;
-                for (auto& s2 : net->steps) if (s2.src_t == st.out.t) { ++users; if (s2.kind == S_STEMPOOL || s2.kind == S_HEAD2) stem = &s2; }
-                if (stem && users == 1) {
-                    st.raw_input = stem->raw_input = true;
-                    stem->bytes_per_img += (double)o.C * o.H * o.W * 4 - (double)o.H * o.W * 4;      // int32 planes instead of the NHWC4 copy
-                    st.bytes_per_img = 0;
-                    st.name = "input(read by the stem launch)";
-                }
-            }
-        }
+    emit_output(net);
+    let_stem_read_input(net);
     return F8_OK;
 }
 
 // pass 4
 static int layout_arena(f8_net* net, int max_batch) {
     auto& T = net->tensors;
-    auto& ND = net->nodes;
-    const int nn = (int)ND.size();
-    const Options& opt = net->opt;
-    const int fuse_blocks = opt.fuse_blocks;
-    (void)T; (void)nn; (void)opt; (void)fuse_blocks; (void)max_batch;
     // ---- 4. lifetimes and arena layout (first-fit over a free list; in-place residual update)
     auto touch = [&](int t, int f, int step) {
         if (t < 0 || f < 0) return;
@@ -2222,17 +2199,18 @@ static int bind_step(f8_net* net, Step& st) {
                 a.sN2 = s2.H * s2.W * s2.Cs; a.sP2 = g.cd.stride * s2.W * s2.Cs; a.sQ2 = g.cd.stride * s2.Cs; a.ktot2 = g.ktot;
             }
             // the kernels that read the fragment-order weight image
-            const bool frag = st.dense || nd.pool >= 0 || nd.s2w;
-            if (frag || nd.wstat || nd.wreg) a.w = W8(nd.wf_off);
-            if (!frag && nd.wstat && nd.dual >= 0) a.w2 = W8(ND[nd.dual].wf_off);
+            if (reads_frag_weights(st.variant)) a.w = W8(nd.wf_off);
+            if (st.variant == V_WSTAT && nd.dual >= 0) a.w2 = W8(ND[nd.dual].wf_off);
             out_formats(a.q);
-            if (st.dense) fc_dense_kernel_name(kb, sizeof kb, a);           // (run_step: the same order)
-            else if (nd.pool >= 0) conv1x1_pool_kernel_name(kb, sizeof kb, a, res);
-            else if (nd.s2w) conv3x3s2_wreg_kernel_name(kb, sizeof kb, a);
-            else if (nd.wstat) conv1x1_wstat_kernel_name(kb, sizeof kb, a, st.inst = conv1x1_wstat_inst(a, res, out32, nq, opt.wstat_fast));
-            else if (nd.wreg) conv1x1_wreg_kernel_name(kb, sizeof kb, a);
-            else if (nd.p3_R > 0) conv3x3_patch_kernel_name(kb, sizeof kb, d.cin, a.W, res);
-            else conv_kernel_name(kb, sizeof kb, a, nd.tile, st.inst = conv_inst(a, nd.tile, res, nd.dual >= 0, opt.deep_nk));
+            switch (st.variant) {                         // (run_step: the same cases)
+                case V_FC: fc_dense_kernel_name(kb, sizeof kb, a); break;
+                case V_POOL: conv1x1_pool_kernel_name(kb, sizeof kb, a, res); break;
+                case V_S2WREG: conv3x3s2_wreg_kernel_name(kb, sizeof kb, a); break;
+                case V_WSTAT: conv1x1_wstat_kernel_name(kb, sizeof kb, a, st.inst = conv1x1_wstat_inst(a, res, out32, nq, opt.wstat_fast)); break;
+                case V_WREG: conv1x1_wreg_kernel_name(kb, sizeof kb, a); break;
+                case V_PATCH3X3: conv3x3_patch_kernel_name(kb, sizeof kb, d.cin, a.W, res); break;
+                default: conv_kernel_name(kb, sizeof kb, a, nd.tile, st.inst = conv_inst(a, nd.tile, res, nd.dual >= 0, opt.deep_nk));   // V_IGEMM
+            }
             st.args = a; break;
         }
         case S_HEAD2: case S_STEMPOOL: {
@@ -2267,8 +2245,9 @@ static int bind_step(f8_net* net, Step& st) {
             out_formats(a.q); st.args = a; break;
         }
         case S_FUSED: {
-            const bool ds = nd.fbd_a >= 0;                // stage-opening block: nd = shortcut conv, nd.dual = body.4
-            const Node& na = ND[ds ? nd.fbd_a : nd.fb_a]; const Node& nb = ND[ds ? nd.fbd_b : nd.fb_b]; const Node& ng = ds ? ND[nd.dual] : nd;
+            const BlockConvs r = block_convs(net, st.node);
+            const bool ds = r.sc >= 0, opener = st.variant == V_OPENER;     // stage-opening block: nd = shortcut conv, nd.dual = body.4
+            const Node& na = ND[r.b0]; const Node& nb = ND[r.b2]; const Node& ng = ND[r.b4];
             const Tensor& x = T[st.src_t];
             FusedArgs a{};
             a.w0 = W8(na.w_off); a.w0_bytes = (uint32_t)((size_t)na.coutP * na.ktot);
@@ -2277,16 +2256,16 @@ static int bind_step(f8_net* net, Step& st) {
             a.b0 = B32(na.b_off); a.b2 = B32(nb.b_off); a.b4 = B32(ng.b_off);
             if (ds) {
                 a.wsc = W8(nd.w_off); a.wsc_bytes = (uint32_t)((size_t)nd.coutP * nd.ktot); a.bsc = B32(nd.b_off);
-                a.COUT = nd.cd.cout; a.stride2 = nd.fbd_s2 ? 1 : 0;
+                a.COUT = nd.cd.cout; a.stride2 = opener ? 1 : 0;
             }
             a.H = x.H; a.W = x.W; a.C = na.cd.cin; a.MID = na.cd.cout; a.R = nd.fb_R;
-            a.tiles_per_img = (ds && nd.fbd_s2) ? (x.H / 2) / nd.fb_R : (x.H + nd.fb_R - 1) / nd.fb_R;
+            a.tiles_per_img = opener ? (x.H / 2) / nd.fb_R : (x.H + nd.fb_R - 1) / nd.fb_R;
             fmt(nb, &a.n1, &a.lo1, &a.hi1, &a.xor1);
             fmt(ng, &a.n2, &a.lo2, &a.hi2, &a.xor2);
             a.relu_a = na.cd.relu; a.relu_b = nb.cd.relu;
             a.acc_shl = st.acc_shl; a.res_shl = st.res_shl; a.relu1 = st.relu1;
             out_formats(a.q);
-            if (ds && nd.fbd_s2) fused_opener_kernel_name(kb, sizeof kb, a, st.inst = fused_opener_inst(a, opt.opener_stg));
+            if (opener) fused_opener_kernel_name(kb, sizeof kb, a, st.inst = fused_opener_inst(a, opt.opener_stg));
             else fused_bottleneck_kernel_name(kb, sizeof kb, a);
             st.args = a; break;
         }
@@ -2294,7 +2273,8 @@ static int bind_step(f8_net* net, Step& st) {
             Node& na = ND[nd.p12_a];
             const Tensor& x = T[st.src_t];
             FusedArgs a{};
-            const size_t w0 = nd.p12_s2 ? na.w_off : na.wf_off, w2 = nd.p12_s2 ? nd.w_off : nd.wf_off;   // f8_p12.hip reads fragment order
+            const bool opener = st.variant == V_OPENER;
+            const size_t w0 = opener ? na.w_off : na.wf_off, w2 = opener ? nd.w_off : nd.wf_off;   // f8_p12.hip reads fragment order
             a.w0 = W8(w0); a.w0_bytes = (uint32_t)((size_t)na.coutP * na.ktot);
             a.w2 = W8(w2); a.w2_bytes = (uint32_t)((size_t)nd.coutP * nd.ktot);
             a.b0 = B32(na.b_off); a.b2 = B32(nd.b_off);
@@ -2302,7 +2282,7 @@ static int bind_step(f8_net* net, Step& st) {
             fmt(nd, &a.n1, &a.lo1, &a.hi1, &a.xor1);
             a.relu_a = na.cd.relu; a.relu_b = nd.cd.relu;
             out_formats(a.q);
-            if (nd.p12_s2) {                              // body.0 + body.2 of a stride-2 opening block on f8_opener.hip (P12); q[0] = mid2
+            if (opener) {                                 // body.0 + body.2 of a stride-2 opening block on f8_opener.hip (P12); q[0] = mid2
                 a.COUT = 4 * na.cd.cout; a.R = nd.fb_R;
                 a.tiles_per_img = (x.H / 2 + nd.fb_R - 1) / nd.fb_R;
                 a.n2 = a.q[0].n; a.lo2 = a.q[0].lo; a.hi2 = a.q[0].hi; a.xor2 = a.q[0].bias_xor;      // mid2's one form = body.4's input format
@@ -2317,40 +2297,36 @@ static int bind_step(f8_net* net, Step& st) {
             a.nblk = (int)ch.size();
             unsigned shortcut_blocks = 0;
             for (int k = 0; k < a.nblk; ++k) {
-                Node& hh = ND[ch[k]];
+                const Node& hh = ND[ch[k]];
+                const BlockConvs r = block_convs(net, ch[k]);
+                const Node& ng = ND[r.b4];
                 ChainBlk& B = a.blk[k];
-                if (hh.tail) {                                  // only the join of a stride-2 opening block: shortcut (hh) + body.4 (its dual)
-                    const Node& g4 = ND[hh.dual];
-                    B.w4 = W8(g4.wf_off); B.b4 = B32(g4.b_off);
-                    B.wsc = W8(hh.wf_off); B.bsc = B32(hh.b_off);
+                B.w4 = W8(ng.wf_off); B.b4 = B32(ng.b_off);
+                if (r.sc >= 0) { B.wsc = W8(hh.wf_off); B.bsc = B32(hh.b_off); shortcut_blocks |= 1u << k; }
+                B.relu1 = ND[hh.fused_add].relu;
+                // identity: (body.4 << acc_shl) + (block input << res_shl); opening block: (shortcut << acc_shl) + (body.4 << res_shl)
+                join_shifts(T[hh.out].fl - (r.sc >= 0 ? T[ng.out].fl : T[ND[r.b0].a].fl), &B.acc_shl, &B.res_shl);
+                if (r.b0 < 0) {                                 // only the join of a stride-2 opening block (tail: always the first block)
                     B.nq = B.n1 = B.n2 = 1; B.hiq = B.hi1 = B.hi2 = 255; B.xorq = B.xor1 = B.xor2 = 0x80808080u;     // (unused: no body.0 / body.2 here)
-                    B.relu_a = B.relu_b = 1; B.relu1 = ND[hh.fused_add].relu;
+                    B.relu_a = B.relu_b = 1;
                     a.acc_ok = 1; a.stream_ok = stream_bounded(net, ND[hh.fused_add].out) ? 1 : 0; a.rq_int = rq_int;
-                    const int dfl = T[hh.out].fl - T[g4.out].fl;             // (shortcut << acc_shl) + (body.4 << res_shl)
-                    B.acc_shl = dfl < 0 ? -dfl : 0; B.res_shl = dfl > 0 ? dfl : 0;
-                    shortcut_blocks |= 1u << k;
                     continue;
                 }
-                const bool hds = hh.fbd_a >= 0;
-                Node& na = ND[hds ? hh.fbd_a : hh.fb_a]; Node& nb = ND[hds ? hh.fbd_b : hh.fb_b];
-                const Node& ng = hds ? ND[hh.dual] : hh;
-                B.w0 = W8(na.wf_off); B.w2 = W8(nb.wf_off); B.w4 = W8(ng.wf_off);
-                B.b0 = B32(na.b_off); B.b2 = B32(nb.b_off); B.b4 = B32(ng.b_off);
-                if (hds) { B.wsc = W8(hh.wf_off); B.bsc = B32(hh.b_off); shortcut_blocks |= 1u << k; }
+                Node& na = ND[r.b0]; Node& nb = ND[r.b2];
+                B.w0 = W8(na.wf_off); B.w2 = W8(nb.wf_off);
+                B.b0 = B32(na.b_off); B.b2 = B32(nb.b_off);
                 fmt(na, &B.nq, &B.loq, &B.hiq, &B.xorq);
                 fmt(nb, &B.n1, &B.lo1, &B.hi1, &B.xor1);
                 fmt(ng, &B.n2, &B.lo2, &B.hi2, &B.xor2);
-                B.relu_a = na.cd.relu; B.relu_b = nb.cd.relu; B.relu1 = ND[hh.fused_add].relu;
-                if (k == 0) { a.acc_ok = 1; a.rq_int = rq_int; a.stream_ok = (hds || stream_bounded(net, na.a)) ? 1 : 0; }   // identity first block: the stream it reads
+                B.relu_a = na.cd.relu; B.relu_b = nb.cd.relu;
+                if (k == 0) { a.acc_ok = 1; a.rq_int = rq_int; a.stream_ok = (r.sc >= 0 || stream_bounded(net, na.a)) ? 1 : 0; }   // identity first block: the stream it reads
                 a.acc_ok = a.acc_ok && conv_acc_bounded(na) && conv_acc_bounded(nb);
                 a.stream_ok = a.stream_ok && stream_bounded(net, ND[hh.fused_add].out);
-                // identity: (body.4 << acc_shl) + (block input << res_shl); opening block: (shortcut << acc_shl) + (body.4 << res_shl)
-                const int dfl = T[hh.out].fl - (hds ? T[ng.out].fl : T[na.a].fl);
-                B.acc_shl = dfl < 0 ? -dfl : 0; B.res_shl = dfl > 0 ? dfl : 0;
             }
             const Node& hf = ND[ch[0]];
-            const bool tail = hf.tail, ds = hf.fbd_a >= 0 || tail;
-            const Node& a0 = tail ? ND[hf.dual] : ND[ds ? hf.fbd_a : hf.fb_a];
+            const BlockConvs r0 = block_convs(net, ch[0]);
+            const bool tail = r0.b0 < 0, ds = r0.sc >= 0;
+            const Node& a0 = ND[tail ? r0.b4 : r0.b0];
             const Tensor& oT = T[ND[nd.fused_add].out];      // the stage's output map (st.out.t: the pooled tensor when the pool runs in the launch)
             a.tail = tail ? 1 : 0;
             a.pool = nd.pool >= 0 ? 1 : 0;
@@ -2370,11 +2346,12 @@ static int bind_step(f8_net* net, Step& st) {
             const std::vector<int>& ch = nd.bchain;
             BChainArgs a{};
             a.nblk = (int)ch.size();
-            const bool ds = ND[ch[0]].bds_a >= 0;
+            const bool ds = block_convs(net, ch[0]).sc >= 0;
             for (int k = 0; k < a.nblk; ++k) {
                 const Node& hk = ND[ch[k]];
-                const bool hds = hk.bds_a >= 0;                 // opening block: hk = its shortcut conv
-                const Node& c2 = hds ? ND[hk.bds_b] : hk; Node& c1 = ND[hds ? hk.bds_a : hk.bb_a];
+                const BlockConvs r = block_convs(net, ch[k]);
+                const bool hds = r.sc >= 0;                     // opening block: hk = its shortcut conv
+                Node& c1 = ND[r.b0]; const Node& c2 = ND[r.b2];
                 BChainBlk& B = a.blk[k];
                 B.wa = W8(c1.wf_off); B.wb = W8(c2.wf_off);
                 B.ba = B32(c1.b_off); B.bb = B32(c2.b_off);
@@ -2385,8 +2362,7 @@ static int bind_step(f8_net* net, Step& st) {
                 a.acc_ok = a.acc_ok && conv_acc_bounded(c1);
                 a.stream_ok = a.stream_ok && stream_bounded(net, ND[hk.fused_add].out);
                 // identity: (second conv << acc_shl) + (block input << res_shl); opening block: (second conv << acc_shl) + (shortcut << res_shl)
-                const int dfl = T[c2.out].fl - (hds ? T[hk.out].fl : T[c1.a].fl);
-                B.acc_shl = dfl < 0 ? -dfl : 0; B.res_shl = dfl > 0 ? dfl : 0;
+                join_shifts(T[c2.out].fl - (hds ? T[hk.out].fl : T[c1.a].fl), &B.acc_shl, &B.res_shl);
                 if (hds) { a.wsc = W8(hk.wf_off); a.bsc = B32(hk.b_off); }
             }
             const Tensor& x = T[st.out.t];
@@ -2398,7 +2374,8 @@ static int bind_step(f8_net* net, Step& st) {
             st.args = a; break;
         }
         case S_IR: {
-            Node& na = ND[nd.ir_a]; Node& nb = ND[nd.ir_b];
+            const BlockConvs r = block_convs(net, st.node);
+            Node& na = ND[r.b0]; Node& nb = ND[r.b2];
             const Tensor& x = T[st.src_t];
             const Tensor& oT = T[nd.out];
             IRArgs a{};
@@ -2426,7 +2403,8 @@ static int bind_step(f8_net* net, Step& st) {
             a.nblk = (int)ch.size();
             a.acc_ok = 1; a.rq_int = rq_int;
             for (int k = 0; k < a.nblk; ++k) {
-                const Node& c = ND[ch[k]]; Node& na = ND[c.irc_a]; Node& nb = ND[c.irc_b];
+                const BlockConvs r = block_convs(net, ch[k]);
+                const Node& c = ND[ch[k]]; Node& na = ND[r.b0]; Node& nb = ND[r.b2];
                 IRChainBlk& B = a.blk[k];
                 B.w0 = W8(na.w_off); B.b0 = B32(na.b_off);
                 B.wd4 = W8(nb.rc_off); B.bd4 = B32(nb.cc_off);
@@ -2435,14 +2413,13 @@ static int bind_step(f8_net* net, Step& st) {
                 fmt(nb, &B.n1, &B.lo1, &B.hi1, &B.xor1);
                 fmt(c, &B.n2, &B.lo2, &B.hi2, &B.xor2);
                 B.relu_a = na.cd.relu; B.relu_b = nb.cd.relu; B.relu0 = c.cd.relu;
-                if (c.fused_add >= 0) {
-                    const int dfl = T[c.out].fl - T[na.a].fl;     // (project << acc_shl) + (block input << res_shl)
-                    B.res = 1; B.acc_shl = dfl < 0 ? -dfl : 0; B.res_shl = dfl > 0 ? dfl : 0; B.relu1 = ND[c.fused_add].relu;
+                if (c.fused_add >= 0) {                         // (project << acc_shl) + (block input << res_shl)
+                    B.res = 1; B.relu1 = ND[c.fused_add].relu;
+                    join_shifts(T[c.out].fl - T[na.a].fl, &B.acc_shl, &B.res_shl);
                 }
                 if (k + 1 < a.nblk) {
-                    const Node& nc = ND[ch[k + 1]];
-                    fmt(ND[nc.irc_a], &B.nq, &B.loq, &B.hiq, &B.xorq);
-                    B.keep = nc.fused_add >= 0;
+                    fmt(ND[block_convs(net, ch[k + 1]).b0], &B.nq, &B.loq, &B.hiq, &B.xorq);
+                    B.keep = ND[ch[k + 1]].fused_add >= 0;
                 }
                 a.acc_ok = a.acc_ok && conv_acc_bounded(na) && conv_acc_bounded(nb);
             }
@@ -2506,17 +2483,17 @@ int f8_net_finalize(f8_net* net, int max_batch) {
     if (max_batch < 1) return fail(F8_ERR_INVALID, "f8_net_finalize: max_batch < 1");
     if (net->out_t < 0) return fail(F8_ERR_STATE, "f8_net_finalize: no output marked");
     if (net->nodes.empty() || net->nodes[0].kind != N_INPUT) return fail(F8_ERR_STATE, "f8_net_finalize: first node must be the input");
-    plan_residual_joins(net, max_batch);            // 1:  a residual add rides in the epilogue of the later of its two producers
+    plan_residual_joins(net);                       // 1:  a residual add rides in the epilogue of the later of its two producers
     plan_bottleneck_blocks(net, max_batch);         // 1b: bottleneck identity blocks (one launch, or body.0 + body.2 on the 7x7 maps)
-    plan_dual_gemm_joins(net, max_batch);           // 1c: body.4 || shortcut of a stage-opening block as one dual GEMM
-    plan_stage_opening_blocks(net, max_batch);      // 1d: whole stage-opening blocks (same resolution / stride 2)
-    plan_stage_chains(net, max_batch);              // 1f: all consecutive bottleneck blocks of a stage in one launch
-    plan_basic_block_chains(net, max_batch);        // 1g: the same for BasicBlocks
-    plan_inverted_residuals(net, max_batch);        // 1e: MobileNet-V2 inverted residuals
+    plan_dual_gemm_joins(net);                      // 1c: body.4 || shortcut of a stage-opening block as one dual GEMM
+    plan_stage_opening_blocks(net);                 // 1d: whole stage-opening blocks (same resolution / stride 2)
+    plan_stage_chains(net);                         // 1f: all consecutive bottleneck blocks of a stage in one launch
+    plan_basic_block_chains(net);                   // 1g: the same for BasicBlocks
+    plan_inverted_residuals(net);                   // 1e: MobileNet-V2 inverted residuals
     plan_inverted_residual_chains(net);             // 1e2: runs of stride-1 inverted residuals in one launch (option fuse_irchain)
-    plan_mobilenet_v2_head(net, max_batch);         // 1h: MobileNet-V2 head conv + depthwise + 1x1
-    plan_last_conv_and_pool(net, max_batch);        // 1i: the last 1x1 conv + the average pool
-    plan_tensor_forms(net, max_batch);              // 2:  which forms of each tensor exist in HBM
+    plan_mobilenet_v2_head(net);                    // 1h: MobileNet-V2 head conv + depthwise + 1x1
+    plan_last_conv_and_pool(net);                   // 1i: the last 1x1 conv + the average pool
+    plan_tensor_forms(net);                         // 2:  which forms of each tensor exist in HBM
     int rc = emit_steps(net, max_batch);            // 3:  the launches, packed weights, algorithmic bytes / ops
     if (rc) return rc;
     if ((rc = layout_arena(net, max_batch))) return rc;   // 4: lifetimes, first-fit arena
@@ -2723,16 +2700,18 @@ static int run_step(const f8_net* net, const Step& st, const int32_t* input, voi
             ConvArgs a = std::get<ConvArgs>(st.args);
             a.x = (const int8_t*)fp(sF); a.x_bytes = (uint32_t)(sF.bytes_per_img * N); a.M = N * a.PQ;
             if (st.res_t >= 0) a.res = (const int32_t*)fp(T[st.res_t].forms[st.res_f]);
-            if (nd.dual >= 0) { const Form& F2 = T[st.src2_t].forms[st.src2_f]; a.x2 = (const int8_t*)fp(F2); a.x2_bytes = (uint32_t)(F2.bytes_per_img * N); }
+            if (st.src2_t >= 0) { const Form& F2 = T[st.src2_t].forms[st.src2_f]; a.x2 = (const int8_t*)fp(F2); a.x2_bytes = (uint32_t)(F2.bytes_per_img * N); }
             fill_out(&a.out32, a.q);
-            if (st.dense) {
-                const int C = T[nd.out].C;
-                e = launch_fc_dense(a, (char*)output + (size_t)n0 * C * 4, C, net->out_float, chain_err, net->epoch, s);
-            } else if (nd.pool >= 0) e = launch_conv1x1_pool(a, s);
-            else if (nd.s2w) e = launch_conv3x3s2_wreg(a, s);
-            else if (nd.wstat) e = launch_conv1x1_wstat(a, st.inst, net->num_cu, s);
-            else if (nd.wreg) e = launch_conv1x1_wreg(a, s);
-            else e = nd.p3_R > 0 ? launch_conv3x3_patch(a, nd.cd.cin, s) : launch_conv(a, nd.tile, st.inst, s);
+            const int C = T[nd.out].C;
+            switch (st.variant) {
+                case V_FC: e = launch_fc_dense(a, (char*)output + (size_t)n0 * C * 4, C, net->out_float, chain_err, net->epoch, s); break;
+                case V_POOL: e = launch_conv1x1_pool(a, s); break;
+                case V_S2WREG: e = launch_conv3x3s2_wreg(a, s); break;
+                case V_WSTAT: e = launch_conv1x1_wstat(a, st.inst, net->num_cu, s); break;
+                case V_WREG: e = launch_conv1x1_wreg(a, s); break;
+                case V_PATCH3X3: e = launch_conv3x3_patch(a, nd.cd.cin, s); break;
+                default: e = launch_conv(a, nd.tile, st.inst, s);      // V_IGEMM
+            }
             break;
         }
         case S_HEAD2: case S_STEMPOOL: {
@@ -2759,16 +2738,15 @@ static int run_step(const f8_net* net, const Step& st, const int32_t* input, voi
             const Form& xF = T[st.src_t].forms[st.src_f];
             FusedArgs a = std::get<FusedArgs>(st.args);
             a.x8 = (const int8_t*)fp(xF); a.x_bytes = (uint32_t)(xF.bytes_per_img * N); a.N = N;
-            if (st.kind == S_FUSED && nd.fbd_a < 0) a.xr = (const int32_t*)fp(T[st.res_t].forms[st.res_f]);
+            if (st.res_t >= 0) a.xr = (const int32_t*)fp(T[st.res_t].forms[st.res_f]);     // identity block: its int32 input
             fill_out(&a.out32, a.q);
-            if (st.kind == S_P12) e = nd.p12_s2 ? launch_fused_opener(a, st.inst, s) : launch_fused_p12(a, s);
-            else e = (nd.fbd_a >= 0 && nd.fbd_s2) ? launch_fused_opener(a, st.inst, s) : launch_fused_bottleneck(a, s);
+            e = st.variant == V_OPENER ? launch_fused_opener(a, st.inst, s) : st.variant == V_P12 ? launch_fused_p12(a, s) : launch_fused_bottleneck(a, s);
             break;
         }
         case S_CHAIN: {
             ChainArgs a = std::get<ChainArgs>(st.args);
             const Form& xF = T[st.src_t].forms[st.src_f];
-            if (a.tail || net->nodes[nd.chain[0]].fbd_a >= 0) a.x8in = (const int8_t*)fp(xF); else a.xr = (const int32_t*)fp(xF);
+            if (xF.kind == FORM_I8) a.x8in = (const int8_t*)fp(xF); else a.xr = (const int32_t*)fp(xF);     // (an identity first block reads the int32 stream)
             if (a.tail) a.m2in = (const int8_t*)fp(T[st.src2_t].forms[st.src2_f]);
             a.N = N;
             if ((a.NG = chain_launch_groups(net, st, N, &a.stack)) < 1) return F8_ERR_STATE;
@@ -2780,7 +2758,7 @@ static int run_step(const f8_net* net, const Step& st, const int32_t* input, voi
         case S_BCHAIN: {
             BChainArgs a = std::get<BChainArgs>(st.args);
             const Tensor& xs = T[st.src_t];
-            if (net->nodes[nd.bchain[0]].bds_a >= 0) { a.x8in = (const int8_t*)fp(xs.forms[st.src_f]); a.x8sc = (const int8_t*)fp(xs.forms[st.res_f]); }
+            if (st.res_t >= 0) { a.x8in = (const int8_t*)fp(xs.forms[st.src_f]); a.x8sc = (const int8_t*)fp(xs.forms[st.res_f]); }     // opening block: two int8 forms
             else a.xr = (const int32_t*)fp(xs.forms[st.src_f]);
             a.N = N;
             { int32_t one = 1; if ((a.NG = chain_launch_groups(net, st, N, &one)) < 1) return F8_ERR_STATE; }
@@ -2868,9 +2846,8 @@ int f8_net_autotune(f8_net* net, int N, void* stream) {
     static const int cand_bm[4] = {128, 128, 64, 64}, cand_bn[4] = {128, 64, 128, 64};
     int changed = 0;
     for (auto& st : net->steps) {
-        if (st.kind != S_CONV) continue;
+        if (st.variant != V_IGEMM) continue;                       // (conv_igemm_kernel steps only)
         Node& nd = net->nodes[st.node];
-        if (nd.p3_R > 0 || nd.wreg || nd.wstat || nd.s2w || st.dense || nd.pool >= 0) continue;     // (conv_igemm_kernel steps only)
         const ConvTile keep = nd.tile;
         ConvTile best = keep; float best_ms = 1e30f;
         for (int c = 0; c < 4; ++c) {
@@ -2939,8 +2916,10 @@ static int step_chunk(const f8_net* net, int i) {        // nominal images per c
     const Step& st = net->steps[i];
     if (st.kind != S_FUSED) return 0;                    // (chunking the stage-opening convs as well: -3 %, more launches than locality)
     const Node& nd = net->nodes[st.node];
+    const BlockConvs r = block_convs(net, st.node);
+    const bool opener = st.variant == V_OPENER;
     const Options& o = net->opt;
-    if (nd.fbd_a >= 0 && !(nd.fbd_s2 ? o.chunk_opener : o.chunk_ds)) return 0;
+    if (r.sc >= 0 && !(opener ? o.chunk_opener : o.chunk_ds)) return 0;
     const Tensor& x = net->tensors[st.src_t];
     if (x.W != x.H || !(x.W == 56 || x.W == 28 || x.W == 14)) return 0;
     int chunk = x.W == 56 ? o.chunk56 : (x.W == 28 ? o.chunk28 : o.chunk14);
@@ -2949,9 +2928,9 @@ static int step_chunk(const f8_net* net, int i) {        // nominal images per c
         size_t per_img = (size_t)x.H * x.W * x.Cs * 4;
         if (st.out.t >= 0) { const Tensor& y = net->tensors[st.out.t]; per_img = std::max(per_img, (size_t)y.H * y.W * y.Cs * 4); }
         const int cache = (int)std::min<size_t>(((size_t)o.chunk_budget_mb << 20) / std::max<size_t>(per_img, 1), 1 << 20) / gran * gran;
-        const int mid = net->nodes[nd.fbd_a >= 0 ? nd.fbd_a : nd.fb_a].cd.cout;
-        const int tiles = std::max(1, (nd.fbd_s2 ? x.H / 2 : x.H) / std::max(1, nd.fb_R));        // workgroups per image
-        const int slots = (net->num_cu > 0 ? net->num_cu : 256) * ((nd.fbd_s2 || mid > 128) ? 1 : 2);
+        const int mid = net->nodes[r.b0].cd.cout;
+        const int tiles = std::max(1, (opener ? x.H / 2 : x.H) / std::max(1, nd.fb_R));        // workgroups per image
+        const int slots = (net->num_cu > 0 ? net->num_cu : 256) * ((opener || mid > 128) ? 1 : 2);
         const int fill = ((slots * 85 / 100 + tiles - 1) / tiles + gran - 1) / gran * gran;
         chunk = std::max(cache, fill);
     }
