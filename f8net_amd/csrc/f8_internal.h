@@ -25,6 +25,8 @@ struct Options {
     int s2wreg = 1;              // stride-2 3x3 convs of the stage-2 / stage-3 openers on conv3x3s2_wreg_kernel (f8_s2conv.hip)
     int wreg = 1;                // late 1x1 convs on conv1x1_wreg_kernel (weights straight to registers, f8_wreg.hip)
     int fuse_bchain = 2;         // consecutive BasicBlock identity blocks of a stage in ONE launch (f8_bchain.hip); 2: with the stage-opening block in front of them
+    int fuse_bchain7 = 0;        // ... and those of a 7x7 x 512 stage over clusters of eight workgroups, the pool behind them summed in the launch (f8_bcchain.hip);
+                                 // 2: with the JOIN of the stage-opening block in front of them (its stride-2 body.0 stays a launch of its own)
     int fuse_chain = 1;          // all consecutive bottleneck blocks of a stage in ONE launch, int32 residual stream in registers (f8_chain.hip)
                                  // with the same number of rounds (224): groups that finish a round early free their CUs for the next batch's launches
     int fuse_chain7 = 1;         // ... and the identity blocks of a 7x7 bottleneck stage over clusters of eight workgroups (f8_cchain.hip); 0: fused_p12 + the residual-carrying 1x1
@@ -255,6 +257,21 @@ struct BChainArgs {
     void* trace;
 };
 
+// One launch for consecutive BasicBlocks of a 7x7 x 512 stage over clusters of eight workgroups (f8_bcchain.hip; option fuse_bchain7).  Blocks as
+// BChainArgs.  tail != 0: blk[0] is only the JOIN of the stage-opening block (its wb / bb = body.2, acc_shl / res_shl: (body.2 << acc_shl) +
+// (shortcut << res_shl)); body.0 ran in an earlier launch.
+struct BCChainArgs {
+    BChainBlk blk[kBChainMaxBlocks]; int32_t nblk;
+    const int32_t* xr;                     // identity first block: the stage's int32 stream (I32T)
+    const int8_t* m0in;                    // tail: body.0's output [N*7*7][512] in body.2's int8 input format
+    const int8_t* x8sc;                    // tail: the block input [N][14][14][256] in the shortcut's int8 format
+    const int8_t* wsc; const int32_t* bsc; // tail: shortcut conv, fragment order / offset-corrected bias
+    int32_t tail, pool;                    // pool: out32 / q[] are forms of the AVERAGE POOL behind the last block ([N][512], FXQAvgPool2d's wrapping sum)
+    int32_t N, NG;                         // images; clusters resident at once (grid = 8 NG)
+    int32_t* out32; QuantOut q[2];
+    uint32_t* sync; uint32_t* err; uint32_t* err_host; uint32_t epoch; int8_t* xchg; uint32_t timeout_ticks;   // as ChainArgs
+};
+
 // One launch for a MobileNet-V2 inverted-residual block: 1x1 expand -> depthwise 3x3 -> 1x1 project [+ int32 residual] (f8_ir.hip).
 struct IRArgs {
     int32_t acc_ok;                        // expand / depthwise accumulators bounded (see DwArgs::acc_ok)
@@ -382,6 +399,12 @@ int cchain_clusters(int N, int slots);                           // clusters (Ch
 int cchain_kernel_name(char* buf, size_t cap, int fast);
 int chain_fast(const ChainArgs& a, unsigned shortcut_blocks, bool q8);   // f8_chain.hip: 0 = generic instance, 1 = float-converter requantisation, 2 = integer
 hipError_t launch_cchain(const ChainArgs& a, int fast, hipStream_t s);
+// consecutive BasicBlocks of a 7x7 x 512 stage over clusters of eight workgroups (f8_bcchain.hip): geometry and clusters as the 7x7 cluster chain (cchain_clusters)
+bool bcchain_supported(int C, int H, int W, bool opener);       // opener: the join of the stride-2 opening block first
+size_t bcchain_xchg_bytes();
+int bcchain_inst(const BCChainArgs& a, bool q8);                 // 2: integer ReLU / unsigned / right-shift instance, 0: any format
+int bcchain_kernel_name(char* buf, size_t cap, int inst);
+hipError_t launch_bcchain(const BCChainArgs& a, int inst, hipStream_t s);
 // consecutive BasicBlock identity blocks of a stage in one launch (f8_bchain.hip)
 bool bchain_supported(int C, int H, int W);
 bool bchain_ds_supported(int C, int H, int W);

@@ -92,6 +92,8 @@ struct Node {
     int bds_a = -1, bds_b = -1;          // 1x1 / 2 shortcut conv of a stage-opening BasicBlock that opens a bchain launch: its 3x3 / 2 and its second 3x3
     int bchain_into = -1;                // ... the host (second conv) of the chain's LAST block
     std::vector<int> bchain;             // host of the last block of a BasicBlock chain: the hosts of all its blocks (f8_bchain.hip)
+    bool bcc = false;                    // ... which runs over clusters of eight workgroups (a 7x7 x 512 stage, option fuse_bchain7: f8_bcchain.hip)
+    bool btail = false;                  // shortcut conv of a stride-2 opening BasicBlock whose JOIN opens such a launch (bds_b = its second 3x3; its 3x3 / 2 runs alone)
     int p12_a = -1;                      // 3x3 conv hosting "1x1 -> 3x3 in one launch" (f8_p12.hip): its 1x1 producer
     bool p12_s2 = false;                 // ... the 3x3 has stride 2: body.0 + body.2 of a stage-opening block on f8_opener.hip (P12); the block's join opens the stage's chain
     bool tail = false;                   // shortcut conv (dual GEMM host) of such a block: its join runs as the FIRST block of a chain launch (ChainArgs::tail)
@@ -131,7 +133,7 @@ struct Step {
     double bytes_per_img = 0, bytes_const = 0, ops_per_img = 0;
     double valu_per_img = 0;           // ESSENTIAL vector lane-operations per image (f8_net_launch_valu): what the reference's semantics need once the MFMAs are done
     // the launcher's arguments as far as the plan decides them (bind_step); run_step copies them and adds what the run decides
-    std::variant<std::monostate, ConvArgs, StemPoolArgs, FusedArgs, ChainArgs, BChainArgs, IRArgs, IRChainArgs, DwArgs, AddArgs, PoolArgs, AvgArgs, OutArgs> args;
+    std::variant<std::monostate, ConvArgs, StemPoolArgs, FusedArgs, ChainArgs, BChainArgs, BCChainArgs, IRArgs, IRChainArgs, DwArgs, AddArgs, PoolArgs, AvgArgs, OutArgs> args;
     int inst = 0;                      // the instance the launcher starts (the family's *_inst, f8_internal.h; bind_step)
     // S_CHAIN / S_BCHAIN: geometry, workgroups per image and resident per CU, the 7x7 cluster form (f8_cchain.hip)
     int C = 0, MID = 0, H = 0, W = 0, cin0 = 0, tiles = 0, wg_per_cu = 1; bool cluster = false;
@@ -309,6 +311,7 @@ static const OptKey kOptKeys[] = {
     {"fuse_chain7", "F8_FUSE_CHAIN7", &Options::fuse_chain7, 0, 1, true},
     {"fuse_pool", "F8_FUSE_POOL", &Options::fuse_pool, 0, 1, true},
     {"fuse_bchain", "F8_FUSE_BCHAIN", &Options::fuse_bchain, 0, 2, true},
+    {"fuse_bchain7", "F8_FUSE_BCHAIN7", &Options::fuse_bchain7, 0, 2, true},
     {"chain_timeout_ms", "F8_CHAIN_TIMEOUT_MS", &Options::chain_timeout_ms, 0, 1 << 20, false},
     {"chain_stack", "F8_CHAIN_STACK", &Options::chain_stack, 0, 1, true},
     {"wreg", "F8_WREG", &Options::wreg, 0, 1, true},
@@ -1089,8 +1092,10 @@ static void plan_basic_block_chains(f8_net* net) {
     const int fuse_blocks = opt.fuse_blocks;
     // ---- 1g. BasicBlock identity blocks (3x3 ReLU -> 3x3 + residual with the block input, all stride 1) -> f8_bchain.hip: ONE launch for
     //          the consecutive ones of a stage, the int32 stream in registers (a single block is a chain of one: both convs in one
-    //          launch, `mid` only in LDS)
-    if (opt.fuse_bchain && fuse_blocks) {
+    //          launch, `mid` only in LDS).  Option fuse_bchain7: the 7x7 x 512 stage the same way over clusters of eight workgroups (f8_bcchain.hip);
+    //          value 2 puts the JOIN of the stage-opening block in front (its stride-2 body.0 stays a launch of its own)
+    if ((opt.fuse_bchain || opt.fuse_bchain7) && fuse_blocks) {
+        auto cluster7 = [&](int cc, const Tensor& t) { return opt.fuse_bchain7 && bcchain_supported(cc, t.H, t.W, false); };
         auto bblock = [&](int i, int* in_t, int* out_t, int* C) -> bool {
             const Node& c2 = ND[i];
             if (c2.kind != N_CONV || c2.fused_add < 0 || c2.bchain_into >= 0 || c2.fb_a >= 0 || c2.fbd_a >= 0 || c2.dual >= 0 || c2.dual_host >= 0 ||
@@ -1106,7 +1111,7 @@ static void plan_basic_block_chains(f8_net* net) {
             const int cc = c1.cd.cin;
             if (c1.cd.cout != cc || c2.cd.cin != cc || c2.cd.cout != cc || cc % 32) return false;
             if (ND[T[c1.a].prod].kind == N_INPUT) return false;
-            if (!bchain_supported(cc, T[c1.a].H, T[c1.a].W)) return false;
+            if (cluster7(cc, T[c1.a]) ? false : !(opt.fuse_bchain && bchain_supported(cc, T[c1.a].H, T[c1.a].W))) return false;
             *in_t = c1.a; *out_t = ad.out; *C = cc;
             return true;
         };
@@ -1130,6 +1135,8 @@ static void plan_basic_block_chains(f8_net* net) {
                 hosts.push_back(next); cur_out = nout;
             }
             const int lastn = hosts.back();
+            const bool bcc = cluster7(C, T[in_t]);
+            ND[lastn].bcc = bcc;
             for (int h : hosts) {
                 Node& c2 = ND[h]; Node& c1 = ND[T[c2.a].prod];
                 c2.bchain_into = lastn; c2.bb_a = T[c2.a].prod;
@@ -1138,7 +1145,7 @@ static void plan_basic_block_chains(f8_net* net) {
             // the stage-opening block in front of them (3x3 / 2 ReLU -> 3x3, 1x1 / 2 shortcut, join) joins the launch when the chain is
             // the only reader of its output (its two convs over the block input may read different int8 forms of it)
             [&] {
-                if (opt.fuse_bchain < 2 || (int)hosts.size() >= kBChainMaxBlocks || in_t == net->out_t) return;
+                if ((bcc ? opt.fuse_bchain7 : opt.fuse_bchain) < 2 || (int)hosts.size() >= kBChainMaxBlocks || in_t == net->out_t) return;
                 const Tensor& y = T[in_t];
                 const int c1f = T[ND[i].a].prod, adf = ND[i].fused_add;
                 if (y.consumers.size() != 2 || !((y.consumers[0] == c1f && y.consumers[1] == adf) || (y.consumers[0] == adf && y.consumers[1] == c1f))) return;
@@ -1164,6 +1171,13 @@ static void plan_basic_block_chains(f8_net* net) {
                 if (b0.cd.cin * 2 != C || h.cd.cin * 2 != C || b0.cd.cout != C || g.cd.cin != C || g.cd.cout != C || h.cd.cout != C) return;
                 int na = 0, nh = 0;
                 if (consumer_format(x, b0.cd, &na, "finalize") || consumer_format(x, h.cd, &nh, "finalize")) return;
+                if (bcc) {                                           // only the join (body.2 + shortcut) joins the cluster launch; body.0 writes its 7x7 int8 output
+                    if (!bcchain_supported(C, y.H, y.W, true)) return;
+                    h.btail = true; h.bds_b = gi; h.bchain_into = lastn;
+                    g.absorbed_by = hi; g.no_classes = true;
+                    hosts.insert(hosts.begin(), hi);
+                    return;
+                }
                 if (!bchain_ds_supported(C, y.H, y.W)) return;
                 h.bds_a = bi; h.bds_b = gi; h.bchain_into = lastn;
                 b0.absorbed_by = hi; g.absorbed_by = hi; b0.no_classes = true; g.no_classes = true;
@@ -1372,6 +1386,10 @@ static void plan_last_conv_and_pool(f8_net* net) {
         int ci = t.prod;
         if (ND[ci].kind == N_ADD) { if (ND[ci].fused_into < 0) continue; ci = ND[ci].fused_into; }
         Node& c = ND[ci];
+        if (c.kind == N_CONV && c.bchain_into == ci && c.bcc && c.fused_add >= 0 && ND[c.fused_add].out == p.a && p.out != net->out_t) {
+            c.pool = i; p.pool_host = ci;                         // the last block of a 7x7 BasicBlock cluster chain: the same (f8_bcchain.hip)
+            continue;
+        }
         if (c.kind == N_CONV && c.chain_into == ci && c.fused_add >= 0 && ND[c.fused_add].out == p.a && p.out != net->out_t &&
             cchain_supported(c.cd.cout, c.cd.cin, t.H, t.W, c.cd.cout, false)) {      // (geometry: a chain's last block is an identity block)
             c.pool = i; p.pool_host = ci;                         // the last block of a 7x7 cluster chain: the pool is summed from its stream registers (f8_cchain.hip)
@@ -1416,7 +1434,10 @@ static void plan_tensor_forms(f8_net* net) {
                 if ((nd.absorbed_by >= 0 && ND[nd.absorbed_by].fbd_b == i) || (nd.dual_host >= 0 && ND[nd.dual_host].fbd_a >= 0)) break;   // DS: in LDS
                 if (nd.p12_a >= 0) break;                    // the 1x1's output lives in LDS inside the launch
                 if (nd.h2_head >= 0 || (nd.absorbed_by >= 0 && ND[nd.absorbed_by].h2_dw == i)) break;   // 1x1 / depthwise of the MobileNet-V2 head launch: rows in registers
-                if (nd.absorbed_by >= 0 && ND[nd.absorbed_by].bds_b == i) break;   // second 3x3 of the opening block of a bchain launch: `mid` lives in LDS
+                if (nd.absorbed_by >= 0 && ND[nd.absorbed_by].bds_b == i) {        // second 3x3 of the opening block of a bchain launch: `mid` lives in LDS
+                    if (ND[nd.absorbed_by].btail) add_form(s, FORM_I8, n, nd.cd.input_signed ? 1 : 0);   // (cluster launch: body.0's int8 output in HBM)
+                    break;
+                }
                                                                  // (its 3x3 / 2 and its shortcut conv each ask for their int8 form of the block input below)
                 if (nd.bb_a >= 0) {                          // second conv of a chained BasicBlock: its source (`mid`) lives in LDS
                     if (bchain_pos(net, i) == 0) {
@@ -1468,7 +1489,7 @@ static void plan_tensor_forms(f8_net* net) {
                 } else {
                     add_form(s, FORM_I8, n, nd.cd.input_signed ? 1 : 0);
                 }
-                if (nd.fused_add >= 0 && nd.dual < 0 && nd.bds_a < 0) {
+                if (nd.fused_add >= 0 && nd.dual < 0 && nd.bds_a < 0 && !nd.btail) {
                     const Node& ad = ND[nd.fused_add];
                     const int other = (ad.a == nd.out) ? ad.b : ad.a;
                     add_form(T[other], FORM_I32, 0, 0);
@@ -1520,6 +1541,7 @@ static BlockConvs block_convs(const f8_net* net, int host) {
     BlockConvs r;
     if (h.tail) { r.b4 = h.dual; r.sc = host; }
     else if (h.fbd_a >= 0) { r.b0 = h.fbd_a; r.b2 = h.fbd_b; r.b4 = h.dual; r.sc = host; }
+    else if (h.btail) { r.b2 = h.bds_b; r.sc = host; }
     else if (h.bds_a >= 0) { r.b0 = h.bds_a; r.b2 = h.bds_b; r.sc = host; }
     else if (h.fb_a >= 0) { r.b0 = h.fb_a; r.b2 = h.fb_b; r.b4 = host; }
     else if (h.bb_a >= 0) { r.b0 = h.bb_a; r.b2 = host; }
@@ -1649,6 +1671,36 @@ static int emit_bchain(f8_net* net, int i, Step& st, std::vector<int>* extra) {
     st.bytes_per_img = (ds ? (double)x.H * x.W * x.Cs + (st.res_f != st.src_f ? px * x.Cs : 0) : px * x.Cs * 4) + out_bytes(st, o, px);
     st.valu_per_img = (double)ch.size() * px * o.C * (3.0 + 2.0 + 3.0) - 3.0 * px * o.C + 3.0 * px * o.Cs * out_forms8(st);   // per block: first conv's int8, join, the next block's int8 input; the last block's are the output forms
     st.name = "basic_chain_x" + std::to_string(ch.size()) + (ds ? "_ds:" : ":") + tname(net, f1.out) + ".." + tname(net, nd.out);
+    return F8_OK;
+}
+
+// BasicBlocks of a 7x7 x 512 stage over clusters of eight workgroups (f8_bcchain.hip): node i is the second conv of the LAST block; the first
+// block may be the JOIN of the stage-opening block (its shortcut conv hosts it, its body.0 ran in the launch before)
+static int emit_bcchain(f8_net* net, int i, Step& st, std::vector<int>* extra) {
+    auto& T = net->tensors; auto& ND = net->nodes;
+    const Node& nd = ND[i];
+    const std::vector<int>& ch = nd.bchain;
+    const BlockConvs r0 = block_convs(net, ch[0]);
+    const bool tail = r0.sc >= 0;
+    st.kind = S_BCHAIN;
+    st.cluster = true;
+    const Node& f1 = ND[tail ? r0.b2 : r0.b0];
+    if (!tail) { st.src_t = f1.a; st.src_f = find_form(T[f1.a], FORM_I32, 0, 0); }
+    else if (int rc = conv_input_i8(net, f1, &st.src_t, &st.src_f)) return rc;          // body.0's output in body.2's format
+    else if ((rc = conv_input_i8(net, ND[r0.sc], &st.res_t, &st.res_f))) return rc;     // the block input in the shortcut's format
+    for (int h : ch) pack_block(net, block_convs(net, h), true, st);
+    const Tensor& o = T[ND[nd.fused_add].out];               // the stage's output map
+    int out_t = ND[nd.fused_add].out;
+    if (nd.pool >= 0) {                                      // ... summed over its pixels in the launch (1i): the step's outputs are the POOLED tensor's forms
+        out_t = ND[nd.pool].out;
+        if (T[out_t].forms.empty()) add_form(T[out_t], FORM_I32, 0, 0);
+    }
+    select_outputs(net, out_t, &st.out, extra);
+    const double px = (double)o.H * o.W, opx = nd.pool >= 0 ? 1.0 : px, n = (double)ch.size();
+    st.bytes_per_img = (tail ? px * (T[st.src_t].Cs + T[st.res_t].Cs) : px * o.Cs * 4) + out_bytes(st, o, opx);   // (tail: mid0 + the shortcut's pixels)
+    // per block: the first conv's int8 output (the TAIL join has none), the join, the next block's int8 input; the last block's are the output forms
+    st.valu_per_img = px * ((n - (tail ? 1 : 0)) * o.C * 3.0 + n * o.C * 2.0 + (n - 1) * o.C * 3.0) + opx * 3.0 * o.Cs * out_forms8(st) + (nd.pool >= 0 ? px * o.C : 0.0);
+    st.name = "basic_cluster_chain_x" + std::to_string(ch.size()) + (tail ? "_ds:" : ":") + tname(net, f1.out) + ".." + tname(net, nd.out) + (nd.pool >= 0 ? "+avgpool" : "");
     return F8_OK;
 }
 
@@ -1891,7 +1943,7 @@ static int emit_conv_family(f8_net* net, int i, int max_batch, Step& st, std::ve
     const Node& nd = net->nodes[i];
     if (nd.h2_head >= 0) return emit_head2(net, i, st, extra);
     if (nd.sp_pool >= 0 && nd.stem) return emit_stem_pool(net, i, st, extra);
-    if (nd.bchain_into == i) return emit_bchain(net, i, st, extra);
+    if (nd.bchain_into == i) return nd.bcc ? emit_bcchain(net, i, st, extra) : emit_bchain(net, i, st, extra);
     if (nd.chain_into == i) return emit_chain(net, i, st, extra);
     if (nd.fbd_a >= 0) return emit_fused(net, i, st, extra);
     if (nd.p12_a >= 0) return emit_p12(net, i, st, extra);
@@ -2342,7 +2394,39 @@ static int bind_step(f8_net* net, Step& st) {
             chain_kernel_name(kb, sizeof kb, st.C, st.MID, st.H, st.W, st.cin0, tail, st.inst);
             st.args = a; break;
         }
-        case S_BCHAIN: {
+        case S_BCHAIN: if (st.cluster) {
+            const std::vector<int>& ch = nd.bchain;
+            BCChainArgs a{};
+            a.nblk = (int)ch.size();
+            for (int k = 0; k < a.nblk; ++k) {
+                const Node& hk = ND[ch[k]];
+                const BlockConvs r = block_convs(net, ch[k]);
+                const Node& c2 = ND[r.b2];
+                BChainBlk& B = a.blk[k];
+                B.wb = W8(c2.wf_off); B.bb = B32(c2.b_off);
+                fmt(c2, &B.n1, &B.lo1, &B.hi1, &B.xor1);
+                B.relu1 = ND[hk.fused_add].relu;
+                if (r.sc >= 0) {                                // the opening block's join: (body.2 << acc_shl) + (shortcut << res_shl)
+                    a.tail = 1; a.wsc = W8(hk.wf_off); a.bsc = B32(hk.b_off);
+                    B.relu_a = ND[T[c2.a].prod].cd.relu;        // (body.0's ReLU: mid0's format)
+                    join_shifts(T[c2.out].fl - T[hk.out].fl, &B.acc_shl, &B.res_shl);
+                    continue;
+                }
+                Node& c1 = ND[r.b0];
+                B.wa = W8(c1.wf_off); B.ba = B32(c1.b_off);
+                fmt(c1, &B.nq, &B.loq, &B.hiq, &B.xorq);
+                B.relu_a = c1.cd.relu;
+                join_shifts(T[c2.out].fl - T[c1.a].fl, &B.acc_shl, &B.res_shl);
+            }
+            a.pool = nd.pool >= 0 ? 1 : 0;
+            const Tensor& x = T[ND[nd.fused_add].out];
+            st.C = x.C; st.H = x.H; st.W = x.W;
+            st.tiles = 8;                                       // the workgroups of one cluster
+            out_formats(a.q);
+            st.inst = bcchain_inst(a, nq > 0);                  // (requant_float = 1: the integer instance, as the 7x7 bottleneck chain)
+            bcchain_kernel_name(kb, sizeof kb, st.inst);
+            st.args = a; break;
+        } else {
             const std::vector<int>& ch = nd.bchain;
             BChainArgs a{};
             a.nblk = (int)ch.size();
@@ -2591,7 +2675,7 @@ int f8_net_upload(f8_net* net) {
                 if (c7.kind == S_CHAIN) {
                     const Tensor& o7 = net->tensors[net->nodes[net->nodes[c7.node].fused_add].out];   // the stage's map (c7.out.t: the pooled tensor when the pool runs in the launch)
                     if (cchain_supported(o7.C, net->nodes[c7.node].cd.cin, o7.H, o7.W, o7.C, false)) xchg = std::max(xchg, cchain_xchg_bytes());   // (geometry; the last host is an identity block's body.4)
-                }
+                } else if (c7.kind == S_BCHAIN && c7.cluster) xchg = std::max(xchg, bcchain_xchg_bytes());
             net->chain_stride = round_up_z(4096 + xchg, 4096);
             if ((e = hipMalloc((void**)&net->d_chain, net->chain_stride * parts_cap)) != hipSuccess) return hip_fail(e, "hipMalloc(chain scratch)");
             if ((e = hipMemset(net->d_chain, 0, net->chain_stride * parts_cap)) != hipSuccess) return hip_fail(e, "hipMemset(chain scratch)");
@@ -2630,7 +2714,8 @@ static int chain_launch_groups(const f8_net* net, const Step& st, int N, int32_t
     int tiles = 0;
     const int ng = chain_geometry(st, N, net->num_cu, stack, &tiles);
     if (ng >= 1) return ng;
-    if (st.cluster) fail(F8_ERR_STATE, "f8_net_run: the 7x7 stage-chain launch needs 8 co-resident workgroups, the device has %d compute units (plan with fuse_chain7 = 0)", net->num_cu);
+    if (st.cluster) fail(F8_ERR_STATE, "f8_net_run: the 7x7 stage-chain launch needs 8 co-resident workgroups, the device has %d compute units (plan with %s = 0)", net->num_cu,
+                         st.kind == S_BCHAIN ? "fuse_bchain7" : "fuse_chain7");
     else fail(F8_ERR_STATE, "f8_net_run: a stage-chain launch needs %d co-resident workgroups per image, the device has %d compute units (plan with fuse_chain = 0 / fuse_bchain = 0)", tiles, net->num_cu);
     return 0;
 }
@@ -2755,7 +2840,18 @@ static int run_step(const f8_net* net, const Step& st, const int32_t* input, voi
             e = launch_chain(a, st.inst, st.C, st.MID, st.H, st.W, st.cin0, s);
             break;
         }
-        case S_BCHAIN: {
+        case S_BCHAIN: if (st.cluster) {
+            BCChainArgs a = std::get<BCChainArgs>(st.args);
+            const Tensor& xs = T[st.src_t];
+            if (st.res_t >= 0) { a.m0in = (const int8_t*)fp(xs.forms[st.src_f]); a.x8sc = (const int8_t*)fp(T[st.res_t].forms[st.res_f]); }   // the opening block's join
+            else a.xr = (const int32_t*)fp(xs.forms[st.src_f]);
+            a.N = N;
+            { int32_t one = 1; if ((a.NG = chain_launch_groups(net, st, N, &one)) < 1) return F8_ERR_STATE; }
+            fill_out(&a.out32, a.q);
+            if (const int rc = chain_scratch(a)) return rc;
+            e = launch_bcchain(a, st.inst, s);
+            break;
+        } else {
             BChainArgs a = std::get<BChainArgs>(st.args);
             const Tensor& xs = T[st.src_t];
             if (st.res_t >= 0) { a.x8in = (const int8_t*)fp(xs.forms[st.src_f]); a.x8sc = (const int8_t*)fp(xs.forms[st.res_f]); }     // opening block: two int8 forms
