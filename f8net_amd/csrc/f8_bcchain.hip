@@ -18,15 +18,14 @@
 // The shortcut (K = 256, 8 steps) goes straight to the stream registers before the patch is loaded; mid0's patch is one LDS-DMA gather per
 // fragment (a lane's 16 channels of one pixel: a per-lane pixel offset).  At most one of the two shifts is non-zero; everything wraps mod 2^32.
 //
-// Exchange protocol: f8_cchain.hip's (write-through sc0 sc1 stores, drain, barrier, one flag per workgroup and exchange number; bounded polls,
-// the sticky error word with the run's epoch), copied rather than shared so that f8_cchain.hip keeps its code.  ONE buffer per exchanged tensor
+// Exchange protocol: f8_cchain.hip's, one flag per workgroup and exchange number (f8_chain_common.h).  ONE buffer per exchanged tensor
 // (x8, mid), each rewritten two exchanges later.  Why that is safe: a member publishes exchange e only after its LDS-DMA loads of exchange e - 1's
 // buffer have completed (the phase's K loop ends on vmcnt(0), publish() drains again), and a member writes a buffer for exchange e + 1 only after
 // it has seen every member's flag of exchange e.  So nobody overwrites x8 (mid) while a member may still be reading it.  The next image group's
 // stage input is one exchange behind the last block's PB, which read mid, not x8.
 //
 // requant_float = 1 plans run the integer instance (FAST = 2) here, as f8_cchain.hip: there is no float-converter instance of this kernel.
-#include "f8_device.h"
+#include "f8_chain_common.h"
 #include <algorithm>
 #include <cstdio>
 
@@ -49,36 +48,6 @@ struct BCCfg {
 };
 constexpr size_t kBCChainXchgBytes = (size_t)32 * BCCfg::XCL_BYTES;                     // 32 clusters = 256 workgroups
 
-// f8_cchain.hip cq_tile16: 16 accumulator values of one 32x32 tile -> this lane's 16 bytes of the consumer's B fragment
-template <int FAST>
-__device__ __forceinline__ v4i bcq_tile16(const v16i& y, int n, int lo, int hi, unsigned x_or) {
-    unsigned d[4];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        if constexpr (FAST == 2) d[g] = requant_u8x4_int(y[4 * g], y[4 * g + 1], y[4 * g + 2], y[4 * g + 3], n) ^ x_or;
-        else d[g] = pack4(requant1(y[4 * g], n, lo, hi), requant1(y[4 * g + 1], n, lo, hi), requant1(y[4 * g + 2], n, lo, hi), requant1(y[4 * g + 3], n, lo, hi)) ^ x_or;
-    }
-    auto s0 = __builtin_amdgcn_permlane32_swap(d[0], d[2], false, false);
-    auto s1 = __builtin_amdgcn_permlane32_swap(d[1], d[3], false, false);
-    const v4i o = {(int)s0[0], (int)s0[1], (int)s1[0], (int)s1[1]};
-    return o;
-}
-
-#define F8_LDS3(p) ((__attribute__((address_space(3))) void*)(p))
-
-// f8_cchain.hip mfma_operands_read (see there): nothing is scheduled across the end of an MFMA group, then wait states
-__device__ __forceinline__ void bc_mfma_operands_read() {
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_nop 7\n\ts_nop 7" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
-// barrier that leaves vector-memory operations (the LDS-DMA ring) in flight (f8_cchain.hip lds_barrier)
-__device__ __forceinline__ void bc_lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-
 // FAST: 0 = generic formats (signed, left shifts), 2 = ReLU everywhere, unsigned 8-bit formats with right shifts, the identity blocks' stream
 // unshifted, integer requantisation (v_ashr_pk_u8_i32) — bchain_fast's rule
 template <int FAST>
@@ -98,42 +67,24 @@ bcchain_kernel(const BCChainArgs a) {
     const int pp = wave & 3, kh = wave >> 2;                   // K loops: pixel-tile pair, K half
     const int jt = 2 * pp + kh;                                // the stream's pixel tile (7: the dummy)
 
-    if (tid == 0) misc[0] = (int)__hip_atomic_fetch_add(a.sync, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (tid == 0) misc[0] = (int)chain_ticket(a.cs);
     __syncthreads();
     const int L = __builtin_amdgcn_readfirstlane(misc[0]);
     const int cl = L >> 3, c = L & 7;                          // cluster, member
     const int ncl = (int)(gridDim.x >> 3);
     const int ngroups = (a.N + Cfg::IMG - 1) / Cfg::IMG;
     const int npix = a.N * Cfg::PXI;
-    unsigned* const flags = a.sync + 16;
-    const unsigned long long t_limit = (unsigned long long)a.timeout_ticks;
+    unsigned* const flags = chain_flags(a.cs);
+    const unsigned long long t_limit = (unsigned long long)a.cs.timeout_ticks;
     unsigned seq = 0;
 
-    const __amdgpu_buffer_rsrc_t rxc = __builtin_amdgcn_make_buffer_rsrc((void*)(a.xchg + (size_t)cl * Cfg::XCL_BYTES), 0, (unsigned)Cfg::XCL_BYTES, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rxc = __builtin_amdgcn_make_buffer_rsrc((void*)(a.cs.xchg + (size_t)cl * Cfg::XCL_BYTES), 0, (unsigned)Cfg::XCL_BYTES, 0x00020000);
     auto wrsrc = [](const int8_t* p) { return __builtin_amdgcn_make_buffer_rsrc((void*)p, 0, 0x7ffffff0, 0x00020000); };
 
-    // ---- exchange (f8_cchain.hip): every storing wave drains, barrier, one flag store; then the seven others' flags (bounded), barrier
-    auto publish = [&]() {
-        ++seq;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (tid == 0) __hip_atomic_store(flags + L, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    };
+    // ---- exchange (f8_chain_common.h): signal; then the seven others' flags (bounded), barrier
+    auto publish = [&]() { chain_signal(flags + L, ++seq); };
     auto wait_all = [&]() {
-        if (tid < Cfg::G && tid != c) {
-            unsigned* const f = flags + cl * Cfg::G + tid;
-            const unsigned long long t0 = wall_clock64();
-            bool ok = true;
-            while ((int)(__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - seq) < 0) {
-                __builtin_amdgcn_s_sleep(1);
-                if (wall_clock64() - t0 > t_limit) { ok = false; break; }
-                if ((__hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> 8) == a.epoch) break;   // another workgroup of THIS run gave up
-            }
-            if (!ok) {       // a member that never arrives: sticky error word, the launch runs on without waiting
-                __hip_atomic_store(a.err, (a.epoch << 8) | 0x80u | ((unsigned)seq & 0x3fu), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (a.err_host) __hip_atomic_store(a.err_host, (a.epoch << 8) | 0x80u | ((unsigned)seq & 0x3fu), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
-        }
+        if (tid < Cfg::G && tid != c) chain_wait_flag<0x80u, 1>(a.cs, flags + cl * Cfg::G + tid, seq, t_limit);
         __syncthreads();
     };
     // one exchanged tensor of the whole cluster (112 fragments) -> LDS [0, 112 KB): 14 LDS-DMA instructions per wave
@@ -150,7 +101,7 @@ bcchain_kernel(const BCChainArgs a) {
         *(v4i*)(lds + Cfg::OFF_ZERO + tid * 16) = zv;
     };
 
-    // ---- a 3x3, 512 -> 512 over the patch in LDS (f8_cchain.hip P2): y[i] = W . patch + bias for pixel tile jt, channel tiles 2 c + i
+    // ---- a 3x3, 512 -> 512 over the patch in LDS (the K loop: f8_cchain.hip P2's): y[i] = W . patch + bias for pixel tile jt, channel tiles 2 c + i
     auto conv3x3 = [&](const int8_t* w, const int* bias, v16i (&y)[2]) {
         const __amdgpu_buffer_rsrc_t rw = wrsrc(w);
         constexpr int NCH = 36, D = Cfg::D;
@@ -190,7 +141,7 @@ bcchain_kernel(const BCChainArgs a) {
             constexpr int Q = decltype(qc)::value, T = Q / 4;
             constexpr int younger = (Q + D - 2 < NCH - 1 ? Q + D - 2 : NCH - 1) - Q;
             wait_vmcnt<younger>();
-            bc_lds_barrier();
+            lds_barrier();
             if constexpr (Q + D - 1 < NCH) issue(Q + D - 1);
             if constexpr (Q % 4 == 0) tap_base(std::integral_constant<int, T>{});
             const char* const slot = ring + (Q % D) * Cfg::CH_BYTES;
@@ -204,7 +155,7 @@ bcchain_kernel(const BCChainArgs a) {
                 acc[1][1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, b1, acc[1][1], 0, 0, 0);
             }
         });
-        bc_mfma_operands_read();                        // (no vector instruction reads an accumulator inside the loop: one guard behind it)
+        mfma_operands_read();                        // (no vector instruction reads an accumulator inside the loop: one guard behind it)
         __syncthreads();                                // nobody reads the patch any more: its bytes carry the K halves' exchange
         // wave (pp, kh) keeps pixel tile 2 pp + kh: it gives away its sums for tile 2 pp + 1 - kh and takes the partner's (wave ^ 4) for tile 2 pp + kh
 #pragma unroll
@@ -271,7 +222,7 @@ bcchain_kernel(const BCChainArgs a) {
                 for (int k = 0; k < Cfg::KSC; ++k)
 #pragma unroll
                     for (int i = 0; i < 2; ++i) res[i] = __builtin_amdgcn_mfma_i32_32x32x32_i8(wa[i][k], xb[k], res[i], 0, 0, 0);
-                bc_mfma_operands_read();
+                mfma_operands_read();
             }
             if (tid < 64) bias_lds[64 + tid] = B.bb[c * 64 + tid];
             write_zeros(FAST ? 0x80808080u : B.xor1);
@@ -327,7 +278,7 @@ bcchain_kernel(const BCChainArgs a) {
                     for (int k = 0; k < 2; ++k)
                         if (a.q[k].ptr) {
                             const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc((void*)a.q[k].ptr, 0, tot, 0x00020000);
-                            __builtin_amdgcn_raw_buffer_store_b128(bcq_tile16<0>(res[i], a.q[k].n, a.q[k].lo, a.q[k].hi, a.q[k].bias_xor), rq, (unsigned)(mj * C + 16 * lh), ct * 32, 0);
+                            __builtin_amdgcn_raw_buffer_store_b128(quant_tile16<0>(res[i], a.q[k].n, a.q[k].lo, a.q[k].hi, a.q[k].bias_xor), rq, (unsigned)(mj * C + 16 * lh), ct * 32, 0);
                         }
                 }
                 return;
@@ -372,7 +323,7 @@ bcchain_kernel(const BCChainArgs a) {
             if (jt_ok) {
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
-                    const v4i o = bcq_tile16<FAST>(res[i], BN.nq, FAST ? 0 : BN.loq, FAST ? 255 : BN.hiq, FAST ? 0x80808080u : BN.xorq);
+                    const v4i o = quant_tile16<FAST>(res[i], BN.nq, FAST ? 0 : BN.loq, FAST ? 255 : BN.hiq, FAST ? 0x80808080u : BN.xorq);
                     __builtin_amdgcn_raw_buffer_store_b128(o, rxc, l16, Cfg::OFF_X8 + (jt * KK + c * 2 + i) * 1024, 17);
                 }
             }
@@ -403,7 +354,7 @@ bcchain_kernel(const BCChainArgs a) {
                         if constexpr (!FAST)
 #pragma unroll
                             for (int r = 0; r < 16; ++r) y[i][r] = max(y[i][r], floor0);
-                        const v4i o = bcq_tile16<FAST>(y[i], B.n1, FAST ? 0 : B.lo1, FAST ? 255 : B.hi1, FAST ? 0x80808080u : B.xor1);
+                        const v4i o = quant_tile16<FAST>(y[i], B.n1, FAST ? 0 : B.lo1, FAST ? 255 : B.hi1, FAST ? 0x80808080u : B.xor1);
                         __builtin_amdgcn_raw_buffer_store_b128(o, rxc, l16, Cfg::OFF_MID + (jt * KK + c * 2 + i) * 1024, 17);
                     }
                 }
@@ -432,16 +383,7 @@ bcchain_kernel(const BCChainArgs a) {
         }
         __syncthreads();                                        // the next group's loads overwrite the LDS the pool / the epilogue read
     }
-    // ---- re-arm ticket and flags for the next launch on this scratch (f8_cchain.hip): the last workgroup out zeroes them
-    if (tid == 0) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        misc[2] = (__hip_atomic_fetch_add(a.sync + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1u) ? 1 : 0;
-    }
-    __syncthreads();
-    if (misc[2]) {
-        for (int i = tid; i < (int)gridDim.x; i += 512) __hip_atomic_store(flags + i, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (tid == 0) { __hip_atomic_store(a.sync, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); __hip_atomic_store(a.sync + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-    }
+    chain_rearm<512>(a.cs, flags, misc + 2);
 }
 
 // identity blocks (or, opener: the join of the stage-opening block first) of a 7x7 x 512 BasicBlock stage

@@ -7,8 +7,8 @@
 // Same idea as f8_chain.hip (the bottleneck stages of ResNet-50): a workgroup owns a tile of R rows x full width of one image and
 // keeps the tile's int32 stream in REGISTERS from block to block; HBM sees the stage input once (int32) and the stage output once.
 // A BasicBlock has TWO 3x3 convolutions, so a tile swaps halo rows with its vertical neighbours twice per block (the int8 input of
-// the first conv, then `mid`), by the same placement-independent protocol (write-through stores, drain, barrier, flag; one lane
-// polls; sc0 sc1 loads; tickets; bounded spins).  Unlike the bottleneck chains the stream is small here (64 of 256 registers), which
+// the first conv, then `mid`), by the same placement-independent protocol (f8_chain_common.h; one lane polls each neighbour's flag,
+// sc0 sc1 loads).  Unlike the bottleneck chains the stream is small here (64 of 256 registers), which
 // leaves room for the overlap those kernels could not afford: the 3x3's K loop starts with its CENTRE-ROW taps, which read no halo
 // row, and the neighbours' rows are only waited for in front of the first tap that needs them — the exchange runs under a third of
 // the K loop.
@@ -17,7 +17,7 @@
 // instance) in BOTH convs, and owns the same tiles of the stream.  Weights travel L2 -> registers in MFMA-fragment order
 // (pack_frag_weights), B operands come from two LDS patches (rows padded by 16 bytes: one base register + immediates), no barrier
 // inside a K loop apart from the halo hand-over.
-#include "f8_device.h"
+#include "f8_chain_common.h"
 #include <cstdio>
 #include <cstdlib>
 
@@ -47,24 +47,6 @@ struct BChainCfg {
     static_assert(ROWB / 16 <= 256 && (size_t)256 * 4 * ROWB <= kChainXchgBytes, "one 16-byte piece of a halo row per thread of a half workgroup");
 };
 
-// FAST: 0 generic, 1 float-converter requantisation, 2 integer requantisation (f8_chain.hip: quant_tile16)
-template <int FAST, bool ACC = false, class Y>
-__device__ __forceinline__ v4i bquant_tile16(const Y& y, int n, int lo, int hi, unsigned x_or) {
-    unsigned d[4];
-    // FAST == 1: every requantised value is bounded by the planner (BChainArgs::acc_ok, ::stream_ok) -> the 3-operation float form; 2: integer form
-    const float sc = FAST == 1 ? requant_u8_scale(n) : 0.0f;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        if constexpr (FAST == 1) d[g] = requant_u8x4(y[4 * g], y[4 * g + 1], y[4 * g + 2], y[4 * g + 3], sc) ^ x_or;
-        else if constexpr (FAST == 2) d[g] = requant_u8x4_int(y[4 * g], y[4 * g + 1], y[4 * g + 2], y[4 * g + 3], n) ^ x_or;
-        else d[g] = pack4(requant1(y[4 * g], n, lo, hi), requant1(y[4 * g + 1], n, lo, hi), requant1(y[4 * g + 2], n, lo, hi), requant1(y[4 * g + 3], n, lo, hi)) ^ x_or;
-    }
-    auto s0 = __builtin_amdgcn_permlane32_swap(d[0], d[2], false, false);
-    auto s1 = __builtin_amdgcn_permlane32_swap(d[1], d[3], false, false);
-    const v4i o = {(int)s0[0], (int)s0[1], (int)s1[0], (int)s1[1]};
-    return o;
-}
-__device__ __forceinline__ int bopaque(int v) { asm volatile("" : "+s"(v)); return v; }
 
 // FAST: ReLU after the first conv and after the join, every int8 format of the chain unsigned with a right shift, the stream never shifted
 // DS: the chain starts with the stage-opening block (3x3 / 2 -> 3x3, 1x1 / 2 shortcut; C / 2 input channels at twice the resolution)
@@ -94,7 +76,7 @@ bchain_kernel(const BChainArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6) & (NW - 1);
     const int ct = wave & (CT - 1), pg = wave / CT;
 
-    if (tid == 0) { misc[0] = (int)__hip_atomic_fetch_add(a.sync, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); misc[1] = 0; }
+    if (tid == 0) { misc[0] = (int)chain_ticket(a.cs); misc[1] = 0; }
     for (int b = 0; b < a.nblk; ++b) {
         const BChainBlk& B = a.blk[b];
         for (int i = tid; i < 2 * C; i += NT) bias_lds[b * 2 * C + i] = i < C ? B.ba[i] : B.bb[i - C];
@@ -107,8 +89,8 @@ bchain_kernel(const BChainArgs a) {
     const int rows = (H - p0) < R ? (H - p0) : R;
     const int npx = rows * W;
     const bool has_up = ti > 0, has_dn = ti < T - 1;
-    unsigned* const flags = a.sync + 16;
-    const unsigned long long t_limit = (unsigned long long)a.timeout_ticks;
+    unsigned* const flags = chain_flags(a.cs);
+    const unsigned long long t_limit = (unsigned long long)a.cs.timeout_ticks;
 #ifdef F8_TRACE
     unsigned long long tt[8] = {}; unsigned long long t_prev = __builtin_readcyclecounter();
 #define F8_BT(i) do { const unsigned long long now_ = __builtin_readcyclecounter(); tt[i] += now_ - t_prev; t_prev = now_; } while (0)
@@ -133,7 +115,7 @@ bchain_kernel(const BChainArgs a) {
     // address pairs per stream and added two 64-bit vector adds per load)
     auto ldw = [](const int8_t* base, int soff, unsigned voff) {
         const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, 0x7ffffff0, 0x00020000);
-        return __builtin_amdgcn_raw_buffer_load_b128(r, voff, bopaque(soff), 0);
+        return __builtin_amdgcn_raw_buffer_load_b128(r, voff, opaque(soff), 0);
     };
 #else
     auto ldw = [](const int8_t* base, int soff, unsigned voff) { const int q = (int)(size_t)base + soff + (int)voff; const v4i r = {q, q, q, q}; return r; };
@@ -158,7 +140,7 @@ bchain_kernel(const BChainArgs a) {
 #endif
             ++seq;
             constexpr int RCH = ROWB / 16, CPE = C / 16;
-            const __amdgpu_buffer_rsrc_t rxc = __builtin_amdgcn_make_buffer_rsrc((void*)a.xchg, 0, (unsigned)kChainXchgBytes, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rxc = __builtin_amdgcn_make_buffer_rsrc((void*)a.cs.xchg, 0, (unsigned)kChainXchgBytes, 0x00020000);
             const int side = tid / (NT / 2), idx = tid % (NT / 2);
             const bool mine = idx < RCH && (side == 0 ? has_up : has_dn);
             if (mine) {
@@ -167,9 +149,7 @@ bchain_kernel(const BChainArgs a) {
                 const v4i v = *(const v4i*)(patch + ent * CS + c16 * 16);
                 __builtin_amdgcn_raw_buffer_store_b128(v, rxc, (unsigned)(((L * 2 + (int)(seq & 1u)) * 2 + side) * ROWB + idx * 16), 0, 17);   // sc0 sc1
             }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            if (tid == 0) __hip_atomic_store(flags + L, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            chain_signal(flags + L, seq);
 #ifdef F8_TRACE
             tt[4] += __builtin_readcyclecounter() - tp0;
 #endif
@@ -183,26 +163,11 @@ bchain_kernel(const BChainArgs a) {
 #endif
             constexpr int RCH = ROWB / 16, CPE = C / 16;
             int t2 = tid; asm volatile("" : "+v"(t2));
-            if ((t2 == 0 && has_up) || (t2 == NT / 2 && has_dn)) {
-                unsigned* const f = flags + (t2 == 0 ? L - 1 : L + 1);
-                const unsigned long long t0 = wall_clock64();
-                bool ok = true;
-                // a neighbour that never arrives: the sticky error word is set and the launch runs on WITHOUT waiting any more, here and in
-                // every other workgroup (they see the word in their own polls) — no second exit from the block loop (f8_chain.hip)
-                while ((int)(__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - seq) < 0) {
-                    __builtin_amdgcn_s_sleep(1);
-                    if (wall_clock64() - t0 > t_limit) { ok = false; break; }
-                    if ((__hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> 8) == a.epoch) break;   // another tile of THIS run gave up
-                }
-                if (!ok) {
-                    __hip_atomic_store(a.err, (a.epoch << 8) | 0x80u | ((unsigned)seq & 0x3fu), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (a.err_host) __hip_atomic_store(a.err_host, (a.epoch << 8) | 0x80u | ((unsigned)seq & 0x3fu), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                }
-            }
+            if ((t2 == 0 && has_up) || (t2 == NT / 2 && has_dn)) chain_wait_flag<0x80u, 1>(a.cs, flags + (t2 == 0 ? L - 1 : L + 1), seq, t_limit);   // (a time-out runs on)
             __syncthreads();
             const int side = t2 / (NT / 2), idx = t2 % (NT / 2);
             if (idx < RCH && (side == 0 ? has_up : has_dn)) {
-                const __amdgpu_buffer_rsrc_t rxc = __builtin_amdgcn_make_buffer_rsrc((void*)a.xchg, 0, (unsigned)kChainXchgBytes, 0x00020000);
+                const __amdgpu_buffer_rsrc_t rxc = __builtin_amdgcn_make_buffer_rsrc((void*)a.cs.xchg, 0, (unsigned)kChainXchgBytes, 0x00020000);
                 const int nb_wg = side == 0 ? L - 1 : L + 1;
                 const v4i v = __builtin_amdgcn_raw_buffer_load_b128(rxc, (unsigned)(((nb_wg * 2 + (int)(seq & 1u)) * 2 + (1 - side)) * ROWB + idx * 16), 0, 17);
                 const int col = idx / CPE, c16 = idx % CPE;
@@ -301,7 +266,7 @@ bchain_kernel(const BChainArgs a) {
 #pragma unroll
             for (int j = 0; j < NPW; ++j) {
                 const int pix = bpix[j], pr = pix / W, pc = pix - pr * W;
-                const v4i o = bquant_tile16<FAST>(res[j], B0.nq, FAST ? 0 : B0.loq, FAST ? 255 : B0.hiq, FAST ? 0x80808080u : B0.xorq);
+                const v4i o = quant_tile16<FAST>(res[j], B0.nq, FAST ? 0 : B0.loq, FAST ? 255 : B0.hiq, FAST ? 0x80808080u : B0.xorq);
                 if (pix < npx) *(v4i*)(patchX + ((pr + 1) * PW + pc + 1) * CS + ct * 32 + lh * 16) = o;
             }
             __syncthreads();
@@ -402,7 +367,7 @@ bchain_kernel(const BChainArgs a) {
 #pragma unroll
                         for (int r = 0; r < 16; ++r) acc[j][r] = max(acc[j][r], floor0);
                     }
-                    const v4i o = bquant_tile16<FAST, true>(acc[j], n1, lo1, hi1, xor1);
+                    const v4i o = quant_tile16<FAST, true>(acc[j], n1, lo1, hi1, xor1);
                     if (pix < npx) *(v4i*)(patchM + ((pr + 1) * PW + pc + 1) * CS + ct * 32 + lh * 16) = o;
                 } }
             }
@@ -425,11 +390,11 @@ bchain_kernel(const BChainArgs a) {
                         else res[j][r] = max((int)(((unsigned)acc[j][r] << acc_shl) + ((unsigned)res[j][r] << res_shl)), FAST ? 0 : floor1);
                     }
                     if (!last || a.q[0].ptr) {
-                        const v4i o = bquant_tile16<FAST>(res[j], nq, loq, hiq, xorq);
+                        const v4i o = quant_tile16<FAST>(res[j], nq, loq, hiq, xorq);
                         if (pix < npx) *(v4i*)(patchX + ((pr + 1) * PW + pc + 1) * CS + ct * 32 + lh * 16) = o;
                     }
                     if (last && pix < npx) {
-                        const int m = bopaque(m_tile) + pix;
+                        const int m = opaque(m_tile) + pix;
                         const unsigned tot = (unsigned)(((a.N * H * W + 31) & ~31) * C);
                         if (a.out32) {
                             const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc((void*)a.out32, 0, tot * 4u, 0x00020000);
@@ -442,7 +407,7 @@ bchain_kernel(const BChainArgs a) {
                         }
                         if (a.q[1].ptr) {
                             const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc((void*)a.q[1].ptr, 0, tot, 0x00020000);
-                            __builtin_amdgcn_raw_buffer_store_b128(bquant_tile16<false>(res[j], a.q[1].n, a.q[1].lo, a.q[1].hi, a.q[1].bias_xor), rq,
+                            __builtin_amdgcn_raw_buffer_store_b128(quant_tile16<false>(res[j], a.q[1].n, a.q[1].lo, a.q[1].hi, a.q[1].bias_xor), rq,
                                                                    (unsigned)(m * C + 16 * lh), ct * 32, 0);
                         }
                     }
@@ -466,19 +431,7 @@ bchain_kernel(const BChainArgs a) {
         __syncthreads();
         F8_BT(3);
     }
-    // ---- re-arm the ticket and the flags for the NEXT launch on this scratch (f8_chain.hip).  A workgroup counts itself out once ITS flag stores have been performed (lane 0 issued
-    //      them: its vmcnt(0)) and its last poll has returned; the last one out sees every other workgroup past its last access of the words
-    //      and zeroes them; the kernel boundary orders the zeroes before the next launch.  Every workgroup gets here — a timed-out wait sets the
-    //      error word and runs on — and the words are zeroed once at allocation (f8_net.cpp), so the first launch starts clean.
-    if (tid == 0) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        misc[2] = (__hip_atomic_fetch_add(a.sync + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1u) ? 1 : 0;
-    }
-    __syncthreads();
-    if (misc[2]) {
-        if (tid < (int)gridDim.x) __hip_atomic_store(flags + tid, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (tid == 0) { __hip_atomic_store(a.sync, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); __hip_atomic_store(a.sync + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-    }
+    chain_rearm<NT>(a.cs, flags, misc + 2);
 #ifdef F8_TRACE
     if (a.trace && tid == 0) {
         unsigned long long* tp = (unsigned long long*)a.trace + (size_t)blockIdx.x * 8;

@@ -19,10 +19,10 @@
 // The price: every phase needs ALL channels of its input, so the cluster exchanges its int8 activations three times per block through
 // memory — x8 (448 KB), mid1 and mid2 (112 KB each), written by their producers in MFMA-B-FRAGMENT order ([pixel tile][K32 step][lane][16 B]:
 // what a lane holds after the epilogue's two permlane swaps IS its 16 bytes of the consumer's B fragment), so every exchange store and load is a
-// contiguous 1 KB per wave instruction and the consumers' LDS images are straight LDS-DMA copies.  Protocol: f8_chain.hip's (write-through
-// stores, drain, barrier, one flag per workgroup and exchange number; consumers poll the seven others' flags, bounded; agent-scope loads) —
-// placement-independent: a workgroup's place is a ticket, the eight members of a cluster are consecutive tickets, so the set of started
-// workgroups is a prefix of the logical grid and only the cluster whose last member has not started yet waits.
+// contiguous 1 KB per wave instruction and the consumers' LDS images are straight LDS-DMA copies.  Protocol: f8_chain_common.h's, one flag
+// per workgroup and exchange number, consumers poll the seven others' flags — placement-independent: a workgroup's place is a ticket, the
+// eight members of a cluster are consecutive tickets, so the set of started workgroups is a prefix of the logical grid and only the
+// cluster whose last member has not started yet waits.
 //
 // Phases of a block on one workgroup (512 threads = 8 waves, 2 per SIMD, 256 registers each):
 //   P1: operands through an LDS ring of D1 = 3 chunks (a chunk = 4 K32 steps: 7 x8 fragments + 2 weight fragments each, LDS-DMA, no registers
@@ -33,7 +33,7 @@
 //       wave roles, K cut by half a tap's channels; epilogue -> mid2 -> exchange;
 //   P3: mid2 of the whole cluster in LDS, the wave's 16 W4 fragments and its bias in registers; per pixel tile 16 MFMAs, then the join with the
 //       stream registers, ReLU, requantisation -> x8' -> exchange (or, after the last block, the stage's output forms).
-#include "f8_device.h"
+#include "f8_chain_common.h"
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -60,26 +60,6 @@ struct CCfg {
 };
 constexpr size_t kCChainXchgBytes = (size_t)32 * CCfg::XCL_BYTES;                        // 32 clusters = 256 workgroups
 
-// 16 accumulator values of one 32x32 tile (this lane: one pixel, channels 8g + 4 lh + e) -> this lane's 16 bytes of the consumer's fragment
-// (f8_chain.hip quant_tile16: FAST 0 = any format, 1 = float converter, 2 = integer v_ashr_pk_u8_i32)
-template <int FAST>
-__device__ __forceinline__ v4i cq_tile16(const v16i& y, int n, int lo, int hi, unsigned x_or) {
-    unsigned d[4];
-    const float sc = FAST == 1 ? requant_u8_scale(n) : 0.0f;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        if constexpr (FAST == 1) d[g] = requant_u8x4(y[4 * g], y[4 * g + 1], y[4 * g + 2], y[4 * g + 3], sc) ^ x_or;
-        else if constexpr (FAST == 2) d[g] = requant_u8x4_int(y[4 * g], y[4 * g + 1], y[4 * g + 2], y[4 * g + 3], n) ^ x_or;
-        else d[g] = pack4(requant1(y[4 * g], n, lo, hi), requant1(y[4 * g + 1], n, lo, hi), requant1(y[4 * g + 2], n, lo, hi), requant1(y[4 * g + 3], n, lo, hi)) ^ x_or;
-    }
-    auto s0 = __builtin_amdgcn_permlane32_swap(d[0], d[2], false, false);
-    auto s1 = __builtin_amdgcn_permlane32_swap(d[1], d[3], false, false);
-    const v4i o = {(int)s0[0], (int)s0[1], (int)s1[0], (int)s1[1]};
-    return o;
-}
-
-#define F8_LDS3(p) ((__attribute__((address_space(3))) void*)(p))
-
 // (tuning builds that study the float-converter instance: which requantisation site runs which arithmetic — 0: the instance's own)
 #ifndef F8_CC_Q_TAIL
 #define F8_CC_Q_TAIL 0
@@ -94,40 +74,6 @@ __device__ __forceinline__ v4i cq_tile16(const v16i& y, int n, int lo, int hi, u
 #define F8_CC_Q_P3 0
 #endif
 #define F8_CC_QI(fast, ov) ((fast) == 1 && (ov) != 0 ? (ov) : (fast))
-
-// Found with this kernel (round 6).  In the TAIL phase seven independent MFMAs (one per pixel tile) end a K step and the epilogue's vector code follows.
-// Left to itself the scheduler moved that code up INTO the last step: the float-converter instance (FAST = 1) read the first tile's accumulators one MFMA
-// + `s_nop 6` behind the MFMA that writes them, and wrote `v_cvt_f32_i32 v114, ...` in the slot after `v_mfma ..., v[114:117], ...` (a dying B operand, reused
-// at once).  That build returned a few pixels of a tile DIFFERENT FROM RUN TO RUN (tests/test_gpu_chain.py, requant_float=1 on the 7x7 TAIL chain; the
-// integer instance, scheduled differently, was exact); with the vector code kept behind the MFMAs it is bit-exact (every variant of this guard, 0 to 16
-// wait states).  The mechanism is NOT isolated: tools/ubench/ubench_mfma_hazard.hip (profiles/ubench_mfma_hazard_r06.txt) shows the hardware interlocks a
-// vector write to SrcA / SrcB right behind the MFMA (never a wrong result, with or without a backlog of MFMAs), and that a vector read of a result needs
-// 9 .. 16 wait states directly behind its MFMA, 3 .. 4 with one independent MFMA in between, none with two — the compiler's `s_nop 6` satisfies that.  What
-// is known is the cure: nothing is scheduled across the end of an MFMA group (an `asm volatile` alone does not stop the machine scheduler — the first
-// version of this guard left the instructions where they were), plus wait states.
-#ifndef F8_CC_WAR_NOPS
-#define F8_CC_WAR_NOPS 16
-#endif
-__device__ __forceinline__ void mfma_operands_read() {
-#ifdef F8_CC_NO_GUARD       // (tuning / demonstration builds: the schedule the compiler picks by itself)
-    return;
-#endif
-    __builtin_amdgcn_sched_barrier(0);
-    if constexpr (F8_CC_WAR_NOPS >= 16) asm volatile("s_nop 7\n\ts_nop 7" ::: "memory");
-    else if constexpr (F8_CC_WAR_NOPS >= 8) asm volatile("s_nop 7" ::: "memory");
-    else if constexpr (F8_CC_WAR_NOPS >= 4) asm volatile("s_nop 3" ::: "memory");
-    else if constexpr (F8_CC_WAR_NOPS >= 2) asm volatile("s_nop 1" ::: "memory");
-    else if constexpr (F8_CC_WAR_NOPS >= 1) asm volatile("s_nop 0" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
-
-// barrier that leaves vector-memory operations (the LDS-DMA ring) in flight: __syncthreads() drains them (s_waitcnt vmcnt(0) in front of every s_barrier —
-// each ring stage then exposes its whole latency); LDS accesses are complete, and no memory access moves across it
-__device__ __forceinline__ void lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
 
 // FAST as in chain_kernel: 0 = generic formats, 1 / 2 = ReLU everywhere, unsigned 8-bit formats with right shifts, the stream unshifted;
 // requantisation through the float converter (1: bounded values, shifts <= 16) or in integer operations (2: the default plan)
@@ -150,15 +96,15 @@ cchain_kernel(const ChainArgs a) {
     const unsigned l16 = (unsigned)(lane * 16);
     const int pp = wave & 3, kh = wave >> 2;                   // P1 / P2 role: pixel-tile pair, K half
 
-    if (tid == 0) misc[0] = (int)__hip_atomic_fetch_add(a.sync, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (tid == 0) misc[0] = (int)chain_ticket(a.cs);
     __syncthreads();
     const int L = __builtin_amdgcn_readfirstlane(misc[0]);
     const int cl = L >> 3, c = L & 7;                          // cluster, member
     const int ncl = (int)(gridDim.x >> 3);
     const int ngroups = (a.N + Cfg::IMG - 1) / Cfg::IMG;
     const int npix = a.N * Cfg::PXI;
-    unsigned* const flags = a.sync + 16;
-    const unsigned long long t_limit = (unsigned long long)a.timeout_ticks;
+    unsigned* const flags = chain_flags(a.cs);
+    const unsigned long long t_limit = (unsigned long long)a.cs.timeout_ticks;
     unsigned seq = 0;
 #ifdef F8_TRACE
     unsigned tt[12] = {}; unsigned t_prev = (unsigned)__builtin_readcyclecounter();
@@ -167,31 +113,13 @@ cchain_kernel(const ChainArgs a) {
 #define F8_CT(i)
 #endif
 
-    const __amdgpu_buffer_rsrc_t rxc = __builtin_amdgcn_make_buffer_rsrc((void*)(a.xchg + (size_t)cl * Cfg::XCL_BYTES), 0, (unsigned)Cfg::XCL_BYTES, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rxc = __builtin_amdgcn_make_buffer_rsrc((void*)(a.cs.xchg + (size_t)cl * Cfg::XCL_BYTES), 0, (unsigned)Cfg::XCL_BYTES, 0x00020000);
     auto wrsrc = [](const int8_t* p) { return __builtin_amdgcn_make_buffer_rsrc((void*)p, 0, 0x7ffffff0, 0x00020000); };
 
-    // ---- exchange: every storing wave drains, barrier, one flag store; then the seven others' flags (bounded), barrier
-    auto publish = [&]() {
-        ++seq;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (tid == 0) __hip_atomic_store(flags + L, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    };
+    // ---- exchange (f8_chain_common.h): signal; then the seven others' flags (bounded), barrier
+    auto publish = [&]() { chain_signal(flags + L, ++seq); };
     auto wait_all = [&]() {
-        if (tid < Cfg::G && tid != c) {
-            unsigned* const f = flags + cl * Cfg::G + tid;
-            const unsigned long long t0 = wall_clock64();
-            bool ok = true;
-            while ((int)(__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - seq) < 0) {
-                __builtin_amdgcn_s_sleep(1);
-                if (wall_clock64() - t0 > t_limit) { ok = false; break; }
-                if ((__hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> 8) == a.epoch) break;   // another workgroup of THIS run gave up
-            }
-            if (!ok) {       // a member that never arrives: sticky error word, the launch runs on without waiting (f8_chain.hip)
-                __hip_atomic_store(a.err, (a.epoch << 8) | 0x80u | ((unsigned)seq & 0x3fu), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (a.err_host) __hip_atomic_store(a.err_host, (a.epoch << 8) | 0x80u | ((unsigned)seq & 0x3fu), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
-        }
+        if (tid < Cfg::G && tid != c) chain_wait_flag<0x80u, 1>(a.cs, flags + cl * Cfg::G + tid, seq, t_limit);
         __syncthreads();
     };
     // the whole cluster's mid1 / mid2 (112 fragments) -> LDS [0, 112 KB): 14 LDS-DMA instructions per wave
@@ -294,7 +222,7 @@ cchain_kernel(const ChainArgs a) {
             for (int j = 0; j < NPT; ++j) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) res[j][r] = max(res[j][r], floor1);
-                const v4i o = cq_tile16<F8_CC_QI(FAST, F8_CC_Q_TAIL)>(res[j], B1.nq, FAST ? 0 : B1.loq, FAST ? 255 : B1.hiq, FAST ? 0x80808080u : B1.xorq);
+                const v4i o = quant_tile16<F8_CC_QI(FAST, F8_CC_Q_TAIL)>(res[j], B1.nq, FAST ? 0 : B1.loq, FAST ? 255 : B1.hiq, FAST ? 0x80808080u : B1.xorq);
                 __builtin_amdgcn_raw_buffer_store_b128(o, rxc, l16, (j * NK1 + ct) * 1024, 17);
             }
             publish();
@@ -315,7 +243,7 @@ cchain_kernel(const ChainArgs a) {
             }
 #pragma unroll
             for (int j = 0; j < NPT; ++j) {
-                const v4i o = cq_tile16<FAST>(res[j], B0.nq, FAST ? 0 : B0.loq, FAST ? 255 : B0.hiq, FAST ? 0x80808080u : B0.xorq);
+                const v4i o = quant_tile16<FAST>(res[j], B0.nq, FAST ? 0 : B0.loq, FAST ? 255 : B0.hiq, FAST ? 0x80808080u : B0.xorq);
                 __builtin_amdgcn_raw_buffer_store_b128(o, rxc, l16, (j * NK1 + ct) * 1024, 17);
             }
             publish();
@@ -422,7 +350,7 @@ cchain_kernel(const ChainArgs a) {
                         }
                     }
                     const int j = pp * 2 + jj;
-                    const v4i o = cq_tile16<F8_CC_QI(FAST, F8_CC_Q_P1)>(y, n1, lo1, hi1, xor1);
+                    const v4i o = quant_tile16<F8_CC_QI(FAST, F8_CC_Q_P1)>(y, n1, lo1, hi1, xor1);
                     if (j < NPT) __builtin_amdgcn_raw_buffer_store_b128(o, rxc, l16, Cfg::OFF_M1 + (j * KK + ctm) * 1024, 17);
                 }
                 publish();
@@ -522,7 +450,7 @@ cchain_kernel(const ChainArgs a) {
                         }
                     }
                     const int j = pp * 2 + jj;
-                    const v4i o = cq_tile16<F8_CC_QI(FAST, F8_CC_Q_P2)>(y, n2, lo2, hi2, xor2);
+                    const v4i o = quant_tile16<F8_CC_QI(FAST, F8_CC_Q_P2)>(y, n2, lo2, hi2, xor2);
                     if (j < NPT) __builtin_amdgcn_raw_buffer_store_b128(o, rxc, l16, Cfg::OFF_M2 + (j * KK + ctm) * 1024, 17);
                 }
                 publish();
@@ -566,7 +494,7 @@ cchain_kernel(const ChainArgs a) {
                         else rr[r] = max((int)(((unsigned)acc[r] << acc_shl) + ((unsigned)rr[r] << res_shl)), floor1);
                     }
                     if (!last) {
-                        const v4i o = cq_tile16<F8_CC_QI(FAST, F8_CC_Q_P3)>(rr, nq, loq, hiq, xorq);
+                        const v4i o = quant_tile16<F8_CC_QI(FAST, F8_CC_Q_P3)>(rr, nq, loq, hiq, xorq);
                         __builtin_amdgcn_raw_buffer_store_b128(o, rxc, l16, (J * NK1 + ct) * 1024, 17);
                     } else if (!a.pool) {
                         const int p = J * 32 + l31, m = m0 + p;
@@ -585,7 +513,7 @@ cchain_kernel(const ChainArgs a) {
                             for (int k = 0; k < 2; ++k)
                                 if (a.q[k].ptr) {
                                     const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc((void*)a.q[k].ptr, 0, tot, 0x00020000);
-                                    __builtin_amdgcn_raw_buffer_store_b128(cq_tile16<0>(rr, a.q[k].n, a.q[k].lo, a.q[k].hi, a.q[k].bias_xor), rq, (unsigned)(m * C + 16 * lh), ct * 32, 0);
+                                    __builtin_amdgcn_raw_buffer_store_b128(quant_tile16<0>(rr, a.q[k].n, a.q[k].lo, a.q[k].hi, a.q[k].bias_xor), rq, (unsigned)(m * C + 16 * lh), ct * 32, 0);
                                 }
                         }
                     }
@@ -639,16 +567,7 @@ cchain_kernel(const ChainArgs a) {
             }
         }
     }
-    // ---- re-arm ticket and flags for the next launch on this scratch (f8_chain.hip): the last workgroup out zeroes them
-    if (tid == 0) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        misc[2] = (__hip_atomic_fetch_add(a.sync + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1u) ? 1 : 0;
-    }
-    __syncthreads();
-    if (misc[2]) {
-        for (int i = tid; i < (int)gridDim.x; i += 512) __hip_atomic_store(flags + i, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (tid == 0) { __hip_atomic_store(a.sync, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); __hip_atomic_store(a.sync + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-    }
+    chain_rearm<512>(a.cs, flags, misc + 2);
 #ifdef F8_TRACE
     if (a.trace && lane == 0) {
         unsigned* tp = (unsigned*)a.trace + ((size_t)blockIdx.x * 8 + wave) * 16;
@@ -708,7 +627,7 @@ static hipError_t launch_cchain_t(const ChainArgs& a, hipStream_t s) {
 }
 
 // fast: chain_fast(a) (f8_chain.hip).  There is NO float-converter instance (1) of this kernel in the library: it was built, and its TAIL form returned a few wrong pixels in
-// a third of the runs of a 130-image batch (tools/soak_chain7.py; tools/study_float_instance.sh on -DF8_CC_FLOAT_INSTANCE builds) — with the scheduling guard above in place
+// a third of the runs of a 130-image batch (tools/soak_chain7.py; tools/study_float_instance.sh on -DF8_CC_FLOAT_INSTANCE builds) — with the scheduling guard (mfma_operands_read, f8_chain_common.h) in place
 // and the integer instance beside it exact in every run, soak and suite.  Isolated to ONE site: with the float arithmetic everywhere EXCEPT the requantisation of the
 // freshly joined stream at the end of the TAIL phase (-DF8_CC_Q_TAIL=2) 0 of 300 runs differ, with it ONLY there 56 of 150; not the MODE write (same rate without
 // s_setreg), not cured by wait states around the lane swaps; cause unknown.  The integer form is exact for every value the float form takes, so plans with

@@ -14,9 +14,8 @@
 //                          -> clamp, ReLU -> stream' (registers) -> requant -> x8' (LDS)
 //
 // The 3x3 needs one row of mid1 above and below the tile: vertically adjacent tiles of an image run on different CUs at the same
-// time and swap those rows (3.5 KB each) through global memory once per block:
-//   producer: write-through (sc0 sc1) stores -> every storing wave drains -> barrier -> one lane stores the flag (relaxed, agent);
-//   consumer: one lane polls the neighbour's flag (relaxed) -> barrier -> sc0 sc1 loads
+// time and swap those rows (3.5 KB each) through global memory once per block, by the protocol of f8_chain_common.h: write-through
+// (sc0 sc1) stores, drain, barrier, one flag; one lane polls the neighbour's flag, barrier, sc0 sc1 loads
 // (cdna_hip_programming.md Guideline 16, form {sc0 sc1 stores and loads on both sides}); nothing depends on placement or dispatch
 // order: a workgroup's place in the grid is a TICKET it draws when it starts, so the set of started workgroups is always a prefix of
 // the logical grid, the tiles of one image are consecutive tickets, and a group whose last member has not started yet is the only
@@ -26,7 +25,7 @@
 // channel tiles [w CT/8, (w+1) CT/8) of the stream for all pixel tiles.  No barrier inside a K loop: B operands are read-only LDS,
 // A operands rotate through NBUF register batches of NB K-steps; every (workgroup, wave) walks K in a rotated order (integer sums
 // are exact in any order) so that the workgroups do not all ask the L2 for the same kilobyte at the same moment (f8_p12.hip).
-#include "f8_device.h"
+#include "f8_chain_common.h"
 #include <cstdio>
 #include <cstdlib>
 
@@ -75,33 +74,6 @@ struct ChainCfg {
     static_assert(X8_BYTES < 65536 + 4096 && PATCH_BYTES < 65536 && MID2_BYTES < 65536, "immediate offsets");
     static_assert(ROWB / 16 <= 256 && (size_t)512 * 4 * ROWB <= kChainXchgBytes, "one 16-byte piece of a halo row per thread of a half workgroup");
 };
-
-// 16 accumulator values of one 32x32 tile (this lane: one pixel, channels 8g + 4 lh + e) -> this lane's 16 bytes of the int8 row:
-// channels [16 lh, 16 lh + 16) of the tile (two v_permlane32_swap put a lane's four dwords side by side).
-// FAST: unsigned 8-bit behind a ReLU with a right shift; otherwise either direction, any clamp.  FAST == 1: through the float converter
-// (requant_u8x4, 3 operations per value, f8_device.h) — planned only where every shift is 1 .. 16 and the planner has BOUNDED every value that is
-// requantised: the conv accumulators (ChainArgs::acc_ok) and, since round 4, the int32 stream itself (ChainArgs::stream_ok: the stream of a chain
-// that starts with a stage-opening block is a sum of bounded accumulators — the 4-operation wrap-exact float form round 3 used for it cost the
-// 56x56 launch 6.5 %); FAST == 2: the INTEGER form (requant_u8x4_int: v_bfe_u32, v_add3_u32, v_ashr_pk_u8_i32 — no float instruction; exact for
-// every int32, the reference's wrap included, and any shift): option requant_float = 0, or anything unbounded.
-template <int FAST, bool ACC = false>
-__device__ __forceinline__ v4i quant_tile16(const v16i& y, int n, int lo, int hi, unsigned x_or) {
-    unsigned d[4];
-    const float sc = FAST == 1 ? requant_u8_scale(n) : 0.0f;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        if constexpr (FAST == 1) d[g] = requant_u8x4(y[4 * g], y[4 * g + 1], y[4 * g + 2], y[4 * g + 3], sc) ^ x_or;
-        else if constexpr (FAST == 2) d[g] = requant_u8x4_int(y[4 * g], y[4 * g + 1], y[4 * g + 2], y[4 * g + 3], n) ^ x_or;
-        else d[g] = pack4(requant1(y[4 * g], n, lo, hi), requant1(y[4 * g + 1], n, lo, hi), requant1(y[4 * g + 2], n, lo, hi), requant1(y[4 * g + 3], n, lo, hi)) ^ x_or;
-    }
-    auto s0 = __builtin_amdgcn_permlane32_swap(d[0], d[2], false, false);
-    auto s1 = __builtin_amdgcn_permlane32_swap(d[1], d[3], false, false);
-    const v4i o = {(int)s0[0], (int)s0[1], (int)s1[0], (int)s1[1]};
-    return o;
-}
-
-// a scalar the optimiser may not look through (keeps run-time rotated addresses from being precomputed for every unrolled step)
-__device__ __forceinline__ int opaque(int v) { asm volatile("" : "+s"(v)); return v; }
 
 // FAST: every block has ReLU after body.0 / body.2 / the join, every int8 format of the chain is unsigned with a right shift, and the
 // stream itself is never shifted (res_shl == 0) — true for the real fraclen tables; the generic instance takes everything else.
@@ -206,7 +178,7 @@ chain_kernel(const ChainArgs a) {
     (void)p12x; (void)p12m; (void)p12i; (void)p12_pix
 
     // ---- place in the logical grid: a ticket
-    if (tid == 0) { misc[0] = (int)__hip_atomic_fetch_add(a.sync, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); misc[1] = 0; }
+    if (tid == 0) { misc[0] = (int)chain_ticket(a.cs); misc[1] = 0; }
     // ---- biases of every block: once per workgroup, into LDS (a global bias load at the head of a phase costs its whole latency)
     constexpr int NBI = (BIAS_INTS + NT - 1) / NT;               // bias words per thread and block
     auto bias_fetch = [&](int b, int (&v)[NBI]) {               // BROT: block b's b0 | b2 | b4 -> registers (the tail block has no b0 / b2)
@@ -250,8 +222,8 @@ chain_kernel(const ChainArgs a) {
     const bool has_up = ti > 0, has_dn0 = ti < TC - 1;
     const int rot = ROT ? __builtin_amdgcn_readfirstlane(L * 5 + wave * 3) : 0;
 
-    unsigned* const flags = a.sync + 16;
-    const unsigned long long t_limit = (unsigned long long)a.timeout_ticks;
+    unsigned* const flags = chain_flags(a.cs);
+    const unsigned long long t_limit = (unsigned long long)a.cs.timeout_ticks;
 #ifdef F8_TRACE
     unsigned long long tt[16] = {}; unsigned long long t_prev = __builtin_readcyclecounter();
 #define F8_CT(i) do { const unsigned long long now_ = __builtin_readcyclecounter(); tt[i] += now_ - t_prev; t_prev = now_; } while (0)
@@ -543,7 +515,7 @@ chain_kernel(const ChainArgs a) {
                     if constexpr (!F8_CH_BFILL) __syncthreads();     // the (whole-patch) zero fill is complete
                     F8_CT(8);
                     const int floor0 = relu_a ? 0 : INT32_MIN;
-                    const __amdgpu_buffer_rsrc_t rxp = __builtin_amdgcn_make_buffer_rsrc((void*)a.xchg, 0, (unsigned)kChainXchgBytes, 0x00020000);
+                    const __amdgpu_buffer_rsrc_t rxp = __builtin_amdgcn_make_buffer_rsrc((void*)a.cs.xchg, 0, (unsigned)kChainXchgBytes, 0x00020000);
                     const unsigned pub0 = (unsigned)((L * 2 + (int)(seq & 1u)) * 2 * ROWB + mt * 32 + lh * 16);   // this block's parity, side 0 (my top row)
 #pragma unroll
                     for (int j = 0; j < NPW; ++j) {
@@ -565,14 +537,14 @@ chain_kernel(const ChainArgs a) {
                 }
                 F8_CT(1);
                 __syncthreads();                                // the patch interior is complete (EARLY: and every halo store has been performed)
-                if constexpr (EARLY) { if (tid == 0) __hip_atomic_store(flags + L, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+                if constexpr (EARLY) { if (tid == 0) chain_flag(flags + L, seq); }
                 F8_CT(9);
 
                 // ============================ halo rows: publish mine (EARLY: done above), fetch the neighbours' (EARLY: inside body.2's K loop)
                 static_assert(NW == 8 || EARLY || T == 1, "the 4-wave instances publish their halo rows from P1's epilogue");
                 if constexpr (T > 1 && !EARLY) {
                     constexpr int RCH = ROWB / 16, CPE = MID / 16;              // 16-byte pieces per row / per patch entry
-                    const __amdgpu_buffer_rsrc_t rxc = __builtin_amdgcn_make_buffer_rsrc((void*)a.xchg, 0, (unsigned)kChainXchgBytes, 0x00020000);
+                    const __amdgpu_buffer_rsrc_t rxc = __builtin_amdgcn_make_buffer_rsrc((void*)a.cs.xchg, 0, (unsigned)kChainXchgBytes, 0x00020000);
                     int th = tid; asm volatile("" : "+v"(th));                   // re-derived per block, not hoisted and spilled
                     const int side = th >> 8, idx = th & 255;                   // threads 0..255: top row / upper neighbour; 256..511: bottom / lower
                     const bool mine = idx < RCH && (side == 0 ? has_up : has_dn);
@@ -583,10 +555,8 @@ chain_kernel(const ChainArgs a) {
                         const v4i v = *(const v4i*)(patch + ent * MS + c16 * 16);
                         __builtin_amdgcn_raw_buffer_store_b128(v, rxc, (unsigned)(((L * 2 + (int)par) * 2 + side) * ROWB + idx * 16), 0, F8_CH_HALO_AUX);   // sc0 sc1: write-through
                     }
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // every storing wave drains
                     F8_CT(10);
-                    __syncthreads();
-                    if (tid == 0) __hip_atomic_store(flags + L, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    chain_signal(flags + L, seq);
                     F8_CT(11);
                 }
                 // (Tried in round 4 and not kept: ONE wave per neighbour doing the whole hand-over — lane 0 polls, its 64 lanes fetch four pieces each — which
@@ -595,32 +565,16 @@ chain_kernel(const ChainArgs a) {
                   if constexpr (T > 1) {
                     constexpr int RCH = ROWB / 16, CPE = MID / 16;
                     constexpr int HT = NT / 2, PPT = (RCH + HT - 1) / HT;       // threads per side; 16-byte pieces of a row per thread (1 with 8 waves, 2 with 4)
-                    const __amdgpu_buffer_rsrc_t rxc = __builtin_amdgcn_make_buffer_rsrc((void*)a.xchg, 0, (unsigned)kChainXchgBytes, 0x00020000);
+                    const __amdgpu_buffer_rsrc_t rxc = __builtin_amdgcn_make_buffer_rsrc((void*)a.cs.xchg, 0, (unsigned)kChainXchgBytes, 0x00020000);
                     int th = tid; asm volatile("" : "+v"(th));
                     const int side = th / HT, idx0 = th & (HT - 1);             // first half of the workgroup: top row / upper neighbour; second half: bottom / lower
                     const bool side_ok = side == 0 ? has_up : has_dn;
                     const unsigned par = seq & 1u;
                     // one lane per neighbour polls its flag
                     if ((tid == 0 && has_up) || (tid == HT && has_dn)) {
-                        unsigned* const f = flags + (tid == 0 ? L - 1 : L + 1);
-                        const unsigned long long t0 = wall_clock64();
-                        bool ok = true;
-                        // A neighbour that never arrives: the error word is set (sticky; f8_net_check and the logits' poison report it) and the
-                        // launch RUNS ON without waiting any more — here and in every other workgroup, which see the word in their own polls.
-                        // (An early return from the middle of the block loop gave the loop a second exit and the opening-block instance a
-                        // second copy of the 112 stream registers at the loop header: 56 v_mov_b64 per block and its spills.)
-#ifdef F8_CH_ABL_NOPOLL         // tuning build (results invalid): the neighbours' rows are taken as they are
-                        if (false)
+#ifndef F8_CH_ABL_NOPOLL        // (tuning build, results invalid: without the wait the neighbours' rows are taken as they are)
+                        chain_wait_flag<0x40u, 2>(a.cs, flags + (tid == 0 ? L - 1 : L + 1), seq, t_limit);   // (a time-out runs on: f8_chain_common.h)
 #endif
-                        while ((int)(__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - seq) < 0) {
-                            __builtin_amdgcn_s_sleep(2);
-                            if (wall_clock64() - t0 > t_limit) { ok = false; break; }
-                            if ((__hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> 8) == a.epoch) break;   // another tile of THIS run gave up
-                        }
-                        if (!ok) {
-                            __hip_atomic_store(a.err, (a.epoch << 8) | 0x40u | ((unsigned)seq & 0x3fu), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            if (a.err_host) __hip_atomic_store(a.err_host, (a.epoch << 8) | 0x40u | ((unsigned)seq & 0x3fu), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                        }
                     }
                     F8_CT(12);
                     __syncthreads();
@@ -949,20 +903,7 @@ chain_kernel(const ChainArgs a) {
         __syncthreads();                                        // before the next image's tile overwrites x8 / xin
         F8_CT(5);
     }
-    // ---- re-arm the ticket and the flags for the NEXT launch on this scratch (round 4: the hipMemsetAsync node in front of every chain launch
-    //      was 3 x 5 us per step on the critical path).  A workgroup counts itself out once ITS flag stores have been performed (lane 0 issued
-    //      them: its vmcnt(0)) and its last poll has returned; the last one out sees every other workgroup past its last access of the words
-    //      and zeroes them; the kernel boundary orders the zeroes before the next launch.  Every workgroup gets here — a timed-out wait sets the
-    //      error word and runs on — and the words are zeroed once at allocation (f8_net.cpp), so the first launch starts clean.
-    if (tid == 0) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        misc[2] = (__hip_atomic_fetch_add(a.sync + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1u) ? 1 : 0;
-    }
-    __syncthreads();
-    if (misc[2]) {
-        for (int i = tid; i < (int)gridDim.x; i += NT) __hip_atomic_store(flags + i, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (tid == 0) { __hip_atomic_store(a.sync, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); __hip_atomic_store(a.sync + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-    }
+    chain_rearm<NT>(a.cs, flags, misc + 2);
 #ifdef F8_TRACE
     if (a.trace && (tid & 63) == 0) {
         unsigned long long* tp = (unsigned long long*)a.trace + ((size_t)blockIdx.x * 8 + wave) * 16;
@@ -1041,7 +982,7 @@ static hipError_t launch_chain_t(const ChainArgs& a, hipStream_t s) {
 
         fprintf(stderr, "[trace chain<%d,%d,%d>] grid %d, %d blocks, N %d: avg cycles per WG (whole launch): load %.0f | P1 %.0f | halo %.0f | P2 %.0f | P3 %.0f | out %.0f\n",
                 C, MID, W, grid, a.nblk, a.N, ph[0] / n, (ph[1] + ph[6] + ph[7] + ph[8]) / n, (ph[2] + ph[9] + ph[10] + ph[11] + ph[12]) / n, ph[3] / n, ph[4] / n, ph[5] / n);
-        fprintf(stderr, "    P1: P3-end barrier + zero fill + bias %.0f | K loop %.0f | barrier %.0f | epilogue %.0f    halo: barrier %.0f | publish + drain %.0f | barrier + flag %.0f | poll %.0f | fetch + barrier %.0f\n",
+        fprintf(stderr, "    P1: P3-end barrier + zero fill + bias %.0f | K loop %.0f | barrier %.0f | epilogue %.0f    halo: barrier %.0f | publish %.0f | drain + barrier + flag %.0f | poll %.0f | fetch + barrier %.0f\n",
                 ph[6] / n, ph[7] / n, ph[8] / n, ph[1] / n, ph[9] / n, ph[10] / n, ph[11] / n, ph[12] / n, ph[2] / n);
         for (int w = 0; w < 8; ++w)
             fprintf(stderr, "    wave %d: P1 wait+zero %.0f K %.0f bar %.0f epi %.0f | halo %.0f | P2 %.0f | P3 %.0f\n", w, pw[w][6] / n, pw[w][7] / n, pw[w][8] / n, pw[w][1] / n,

@@ -198,6 +198,18 @@ struct ChainBlk {
     int32_t relu_a, relu_b, relu1;         // ReLU after body.0 / body.2 / the join
     int32_t acc_shl, res_shl;              // residual join: (conv << acc_shl) + (other << res_shl)
 };
+// The stage-chain kernels' exchange scratch and error reporting (f8_chain_common.h holds the protocol that uses it)
+struct ChainSync {
+    uint32_t* sync;                        // [0] ticket, [1] workgroups out, [16 + workgroup] exchange flag; zeroed by the last workgroup out
+    uint32_t* err;                         // error word (a wait timed out): (epoch << 8) | code; read by f8_net_check
+    uint32_t* err_host;                    // the same word's mirror in host-visible (pinned, mapped) memory: f8_net_run reads it WITHOUT a synchronisation and
+                                           // refuses further runs until f8_net_check has collected the error (nullptr: no mirror)
+    uint32_t epoch;                        // this run's tag (1 .. 2^24 - 1): only an error of THIS run ends waits early / poisons the logits —
+                                           // a word left by an earlier run stays for f8_net_check to report and changes nothing else
+    int8_t* xchg;                          // exchanged data (f8_chain.hip: halo rows between vertically adjacent tiles, [workgroup][parity][side][W * MID])
+    uint32_t timeout_ticks;                // bound of every wait (100 MHz wall clock)
+};
+
 constexpr int kChainMaxBlocks = 6;
 struct ChainArgs {
     ChainBlk blk[kChainMaxBlocks]; int32_t nblk;
@@ -213,14 +225,7 @@ struct ChainArgs {
     const int8_t* m2in; int32_t tail;
     int32_t N, NG;                         // images; image groups resident at once (grid = NG * tiles per image)
     int32_t* out32; QuantOut q[2];         // forms of the last block's output
-    uint32_t* sync;                        // [0] ticket, [16 + workgroup] halo flag; zeroed before every launch
-    uint32_t* err;                         // error word (a halo spin timed out): (epoch << 8) | code; read by f8_net_check
-    uint32_t* err_host;                    // the same word's mirror in host-visible (pinned, mapped) memory: f8_net_run reads it WITHOUT a synchronisation and
-                                           // refuses further runs until f8_net_check has collected the error (nullptr: no mirror)
-    uint32_t epoch;                        // this run's tag (1 .. 2^24 - 1): only an error of THIS run ends waits early / poisons the logits —
-                                           // a word left by an earlier run stays for f8_net_check to report and changes nothing else
-    int8_t* xchg;                          // halo rows between vertically adjacent tiles: [workgroup][parity][side][W * MID]
-    uint32_t timeout_ticks;                // bound of every spin (100 MHz wall clock)
+    ChainSync cs;
     void* trace;
     int32_t R;                             // rows per tile of the instance to launch (chain_shape)
     int32_t pool;                          // f8_cchain.hip only: out32 / q[] are forms of the AVERAGE POOL behind the last block ([N][C]: FXQAvgPool2d's wrapping int32 sum over the map)
@@ -253,7 +258,7 @@ struct BChainArgs {
     const int8_t* wsc; const int32_t* bsc; // shortcut conv, fragment order / offset-corrected bias
     int32_t N, NG;
     int32_t* out32; QuantOut q[2];
-    uint32_t* sync; uint32_t* err; uint32_t* err_host; uint32_t epoch; int8_t* xchg; uint32_t timeout_ticks;   // as ChainArgs
+    ChainSync cs;
     void* trace;
 };
 
@@ -269,7 +274,7 @@ struct BCChainArgs {
     int32_t tail, pool;                    // pool: out32 / q[] are forms of the AVERAGE POOL behind the last block ([N][512], FXQAvgPool2d's wrapping sum)
     int32_t N, NG;                         // images; clusters resident at once (grid = 8 NG)
     int32_t* out32; QuantOut q[2];
-    uint32_t* sync; uint32_t* err; uint32_t* err_host; uint32_t epoch; int8_t* xchg; uint32_t timeout_ticks;   // as ChainArgs
+    ChainSync cs;
 };
 
 // One launch for a MobileNet-V2 inverted-residual block: 1x1 expand -> depthwise 3x3 -> 1x1 project [+ int32 residual] (f8_ir.hip).

@@ -2751,12 +2751,12 @@ static int run_step(const f8_net* net, const Step& st, const int32_t* input, voi
     };
     char* const chain = net->d_chain ? net->d_chain + (size_t)part * net->chain_stride : nullptr;
     const uint32_t* chain_err = chain ? (const uint32_t*)chain + kChainErrWord : nullptr;
-    auto chain_scratch = [&](auto& a) {
+    auto chain_scratch = [&](ChainSync& cs) {
         if (!chain) return fail(F8_ERR_STATE, "f8_net_run: chain scratch missing");
-        a.sync = (uint32_t*)chain;
-        a.err = a.sync + kChainErrWord; a.err_host = net->h_err_dev; a.epoch = net->epoch;
-        a.xchg = (int8_t*)(chain + 4096);
-        a.timeout_ticks = (uint32_t)std::min<long long>((long long)net->opt.chain_timeout_ms * 100000ll, 0x7fffffffll);
+        cs.sync = (uint32_t*)chain;
+        cs.err = cs.sync + kChainErrWord; cs.err_host = net->h_err_dev; cs.epoch = net->epoch;
+        cs.xchg = (int8_t*)(chain + 4096);
+        cs.timeout_ticks = (uint32_t)std::min<long long>((long long)net->opt.chain_timeout_ms * 100000ll, 0x7fffffffll);
         return (int)F8_OK;
     };
     hipError_t e = hipSuccess;
@@ -2836,7 +2836,7 @@ static int run_step(const f8_net* net, const Step& st, const int32_t* input, voi
             a.N = N;
             if ((a.NG = chain_launch_groups(net, st, N, &a.stack)) < 1) return F8_ERR_STATE;
             fill_out(&a.out32, a.q);
-            if (const int rc = chain_scratch(a)) return rc;
+            if (const int rc = chain_scratch(a.cs)) return rc;
             e = launch_chain(a, st.inst, st.C, st.MID, st.H, st.W, st.cin0, s);
             break;
         }
@@ -2848,7 +2848,7 @@ static int run_step(const f8_net* net, const Step& st, const int32_t* input, voi
             a.N = N;
             { int32_t one = 1; if ((a.NG = chain_launch_groups(net, st, N, &one)) < 1) return F8_ERR_STATE; }
             fill_out(&a.out32, a.q);
-            if (const int rc = chain_scratch(a)) return rc;
+            if (const int rc = chain_scratch(a.cs)) return rc;
             e = launch_bcchain(a, st.inst, s);
             break;
         } else {
@@ -2859,7 +2859,7 @@ static int run_step(const f8_net* net, const Step& st, const int32_t* input, voi
             a.N = N;
             { int32_t one = 1; if ((a.NG = chain_launch_groups(net, st, N, &one)) < 1) return F8_ERR_STATE; }
             fill_out(&a.out32, a.q);
-            if (const int rc = chain_scratch(a)) return rc;
+            if (const int rc = chain_scratch(a.cs)) return rc;
             e = launch_bchain(a, st.inst, st.C, st.H, st.W, s);
             break;
         }
