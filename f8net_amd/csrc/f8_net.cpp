@@ -66,6 +66,25 @@ struct Tensor {
     std::string label;
     bool dense_out = false;            // written straight to the caller's output buffer
 };
+// A fused block: the convs ONE launch (or one block of a chain launch) runs, by role — body.0 / body.2 / body.4 and the shortcut (node ids, -1: the
+// block has none).  It is recorded on its HOST, the conv at whose place in node order the launch is emitted and which is one of the roles itself; the
+// other convs are its members (Node::absorbed_by = the host; a dual GEMM's other conv: Node::dual_host).  A conv hosts at most one block and is a
+// member of at most one (set_block).
+//   B_BOTTLENECK    identity bottleneck: 1x1, 3x3, host = body.4 (f8_fused.hip; R = 0: only a chain launch can run it)
+//   B_OPENING       stage-opening bottleneck: 1x1, 3x3, body.4 = host.dual, host = shortcut (DS on f8_fused.hip; s2: the stride-2 opener, f8_opener.hip)
+//   B_JOIN          its join alone, the FIRST block of a stage chain (ChainArgs::tail): body.4 = host.dual, host = shortcut
+//   B_P12           1x1 -> 3x3 in one launch: 1x1, host = the 3x3 (f8_p12.hip; s2: body.0 + body.2 of a stride-2 opening block on f8_opener.hip, whose join opens the chain)
+//   B_BASIC         BasicBlock of a chain launch: first 3x3, host = the second 3x3
+//   B_BASIC_OPENING stage-opening BasicBlock that opens such a launch: 3x3 / 2, second 3x3, host = the 1x1 / 2 shortcut
+//   B_BASIC_JOIN    its join alone (the cluster launch; its 3x3 / 2 runs on its own): second 3x3, host = shortcut
+//   B_IR            inverted residual: expand, depthwise, host = project (alone: f8_ir.hip, tile R x G; in a chain launch: f8_irchain.hip)
+//   B_HEAD2         MobileNet-V2 head launch (f8_stem.hip, H2): 3x3 / 2 head conv, depthwise, host = the 1x1
+enum BlockKind { B_NONE, B_BOTTLENECK, B_OPENING, B_JOIN, B_P12, B_BASIC, B_BASIC_OPENING, B_BASIC_JOIN, B_IR, B_HEAD2 };
+struct Block { BlockKind kind = B_NONE; int b0 = -1, b2 = -1, b4 = -1, sc = -1; bool s2 = false; int R = 0, G = 0; };
+enum Role { R_NONE, R_B0, R_B2, R_B4, R_SC };
+// The chain launches: bottleneck stage (f8_chain.hip; the 7x7 stage over clusters, f8_cchain.hip), BasicBlocks (f8_bchain.hip), BasicBlocks of a 7x7 x 512
+// stage over clusters of eight workgroups (option fuse_bchain7, f8_bcchain.hip), inverted residuals (f8_irchain.hip).  Independent of the block kind.
+enum ChainKind { C_NONE, C_STAGE, C_BASIC, C_BASIC_CLUSTER, C_IR };
 enum NodeKind { N_INPUT, N_CONV, N_ADD, N_MAXPOOL, N_AVGPOOL, N_LINEAR };
 struct Node {
     int kind; int a = -1, b = -1; int out = -1;
@@ -80,28 +99,13 @@ struct Node {
     int fused_into = -1;               // add: conv node that carries it
     int fused_add = -1;                // conv: add node carried
     bool stem = false, depthwise = false;
-    int absorbed_by = -1;              // conv swallowed by a fused bottleneck launch (node id of its last conv)
-    int fb_a = -1, fb_b = -1, fb_R = 0;  // last conv of a fused bottleneck: its first two convs, rows per tile
+    int absorbed_by = -1;              // conv that runs inside a fused block hosted by ANOTHER conv (node id of that host; set_block)
+    Block blk;                         // the fused block this conv hosts (B_NONE: none)
     int sp_pool = -1, sp_conv = -1;      // stem conv <-> max-pool fused into one launch (f8_stem.hip)
     int pool = -1, pool_host = -1;       // 1x1 conv (hosting its residual join or not) <-> the average pool behind it, one launch (f8_pool.hip)
-    int fbd_a = -1, fbd_b = -1;          // shortcut conv hosting a fused stage-opening block (DS): body.0 / body.2 (body.4 = `dual`)
-    bool fbd_s2 = false;                 // ... whose 3x3 and shortcut have stride 2 (f8_opener.hip)
-    int chain_into = -1;                 // host conv of a bottleneck block that runs inside a stage-chain launch: the host of the chain's LAST block
-    std::vector<int> chain;              // host of the last block of a chain: the hosts of all its blocks, in order (f8_chain.hip)
-    int bb_a = -1;                       // second 3x3 of a BasicBlock identity block that runs in a bchain launch: its first 3x3
-    int bds_a = -1, bds_b = -1;          // 1x1 / 2 shortcut conv of a stage-opening BasicBlock that opens a bchain launch: its 3x3 / 2 and its second 3x3
-    int bchain_into = -1;                // ... the host (second conv) of the chain's LAST block
-    std::vector<int> bchain;             // host of the last block of a BasicBlock chain: the hosts of all its blocks (f8_bchain.hip)
-    bool bcc = false;                    // ... which runs over clusters of eight workgroups (a 7x7 x 512 stage, option fuse_bchain7: f8_bcchain.hip)
-    bool btail = false;                  // shortcut conv of a stride-2 opening BasicBlock whose JOIN opens such a launch (bds_b = its second 3x3; its 3x3 / 2 runs alone)
-    int p12_a = -1;                      // 3x3 conv hosting "1x1 -> 3x3 in one launch" (f8_p12.hip): its 1x1 producer
-    bool p12_s2 = false;                 // ... the 3x3 has stride 2: body.0 + body.2 of a stage-opening block on f8_opener.hip (P12); the block's join opens the stage's chain
-    bool tail = false;                   // shortcut conv (dual GEMM host) of such a block: its join runs as the FIRST block of a chain launch (ChainArgs::tail)
-    int h2_head = -1, h2_dw = -1;        // 1x1 conv that ends the MobileNet-V2 head launch (f8_stem.hip, H2): its 3x3 / 2 head conv and its depthwise conv
-    int ir_a = -1, ir_b = -1, ir_R = 0, ir_G = 0;   // project conv of a fused inverted-residual block: its expand / depthwise convs, tile
-    int irc_a = -1, irc_b = -1;          // project conv of a block that runs inside an inverted-residual chain launch (f8_irchain.hip): expand / depthwise
-    int irc_into = -1;                   // ... the project conv of the chain's LAST block
-    std::vector<int> irchain;            // project conv of the last block of such a chain: the project convs of all its blocks, in order
+    int chain_into = -1;               // host of a block that runs inside a chain launch: the host of the chain's LAST block
+    std::vector<int> chain;            // host of the last block of a chain: the hosts of all its blocks, in order
+    ChainKind chain_kind = C_NONE;     // ... and the launch it is
     int dual = -1;                     // 1x1 conv hosting a join whose other operand is ANOTHER 1x1 conv (node id): one dual-GEMM launch
     int dual_host = -1;                // ... and that other conv: the node that carries it
     int p3_R = 0, p3_imgs = 0, p3_bn = 0;   // 3x3 conv on the LDS-patch kernel (p3_R > 0): rows / images per tile, cout tile
@@ -146,6 +150,7 @@ struct f8_net {
     std::vector<Node> nodes;
     int out_t = -1, out_float = 0;
     bool finalized = false;
+    int plan_bug = -1;                 // planning: a conv that two fused blocks claimed (set_block); finalize fails on it
     int max_batch = 0;
     Options opt;                       // per-handle tuning (f8_net_set_option); seeded from the environment at create
     int device = -1;                   // HIP device the arena / weights live on (set by f8_net_upload)
@@ -837,12 +842,13 @@ static void label_conv_step(f8_net* net, Step& st, const Node& nd) {
 }
 
 // ================================================================================================================================
-// The planner: f8_net_finalize runs these passes in order.  Passes 1 .. 1i only MARK nodes (which launch hosts which conv);
+// The planner: f8_net_finalize runs these passes in order.  Passes 1 .. 1i only record which launch runs which conv — one Block per
+// fused block on its host conv (set_block), chain membership (set_chain), the pairwise links fused_add / dual / pool —;
 // pass 2 decides the forms each tensor needs in HBM, pass 3 emits the launches, pass 4 lays the arena out.  Round 5: one function per pass
 // (round 4: one 1100-line function).
 // ================================================================================================================================
 
-// position of a block (by its host conv) inside its stage chain / BasicBlock chain, -1: not chained
+// position of a block (by its host conv) inside its chain launch, -1: not chained
 static int chain_pos(const f8_net* net, int host) {
     const auto& ND = net->nodes;
     if (host < 0 || ND[host].chain_into < 0) return -1;
@@ -850,12 +856,48 @@ static int chain_pos(const f8_net* net, int host) {
     for (size_t k = 0; k < ch.size(); ++k) if (ch[k] == host) return (int)k;
     return -1;
 }
-static int bchain_pos(const f8_net* net, int host) {
-    const auto& ND = net->nodes;
-    if (host < 0 || ND[host].bchain_into < 0) return -1;
-    const std::vector<int>& ch = ND[ND[host].bchain_into].bchain;
-    for (size_t k = 0; k < ch.size(); ++k) if (ch[k] == host) return (int)k;
-    return -1;
+// the blocks hosted by `hosts`, in order, become one chain launch
+static void set_chain(f8_net* net, const std::vector<int>& hosts, ChainKind kind) {
+    Node& last = net->nodes[hosts.back()];
+    for (int h : hosts) net->nodes[h].chain_into = hosts.back();
+    last.chain = hosts; last.chain_kind = kind;
+}
+// Conv `host` becomes the host of block B and B's other convs its members.  The record's invariant — a conv hosts at most one block and is a member
+// of at most one — is checked here, once per block of every finalize: a pass that takes over what an earlier one marked releases it first.
+static void set_block(f8_net* net, int host, const Block& B) {
+    auto& ND = net->nodes;
+    if (ND[host].blk.kind != B_NONE && net->plan_bug < 0) net->plan_bug = host;
+    ND[host].blk = B;
+    for (int c : {B.b0, B.b2, B.b4, B.sc}) {
+        if (c < 0 || c == host || c == ND[host].dual) continue;      // (the other conv of the host's dual GEMM is linked by dual / dual_host)
+        if ((ND[c].absorbed_by >= 0 || ND[c].blk.kind != B_NONE) && net->plan_bug < 0) net->plan_bug = c;
+        ND[c].absorbed_by = host;
+    }
+}
+// ... and stops being one: its members are convs of their own again
+static void release_block(f8_net* net, int host) {
+    auto& ND = net->nodes;
+    const Block B = ND[host].blk;
+    for (int c : {B.b0, B.b2, B.b4, B.sc})
+        if (c >= 0 && ND[c].absorbed_by == host) { ND[c].absorbed_by = -1; ND[c].no_classes = false; }
+    ND[host].blk = Block{};
+}
+// Is conv i taken by a fused launch: does it host a block, is it a member of one, or is it in a chain?  (Hosting a dual GEMM — Node::dual — is
+// not in it: the stage-opening blocks are built on that link.)  `but`: hosting a block of that kind does not count, for a pass that takes over
+// what an earlier one marked.
+static bool claimed(const f8_net* net, int i, BlockKind but = B_NONE) {
+    const Node& n = net->nodes[i];
+    return n.absorbed_by >= 0 || n.dual_host >= 0 || n.chain_into >= 0 || (n.blk.kind != B_NONE && n.blk.kind != but);
+}
+// The role conv i plays in a fused block, and in whose (*host); R_NONE: in none
+static Role role_in_block(const f8_net* net, int i, int* host) {
+    const Node& n = net->nodes[i];
+    const int h = n.blk.kind != B_NONE ? i : (n.absorbed_by >= 0 ? n.absorbed_by : n.dual_host);
+    if (h < 0) return R_NONE;
+    const Block& B = net->nodes[h].blk;
+    const Role r = B.b0 == i ? R_B0 : B.b2 == i ? R_B2 : B.b4 == i ? R_B4 : B.sc == i ? R_SC : R_NONE;
+    if (r != R_NONE) *host = h;
+    return r;
 }
 
 // pass 1
@@ -913,12 +955,13 @@ static void plan_bottleneck_blocks(f8_net* net, int max_batch) {
         if (!fused_bottleneck_supported(C, MID, x.H, x.W, opt.whole_batch_launches ? max_batch : std::max(1, max_batch / opt.split), opt.fuse_stages, &R) && !chainable) {
             // no whole-block instance (the 7x7 maps of stage 3): body.0 + body.2 as one launch, the residual-carrying 1x1 stays
             if (opt.fuse_p12 && fused_p12_supported(C, MID, x.H, x.W) && a0.cd.relu && b.cd.relu && tb.consumers.size() == 1) {
-                a0.absorbed_by = tb.prod; b.p12_a = ta.prod; b.no_classes = true;
+                set_block(net, tb.prod, Block{B_P12, ta.prod, tb.prod});
+                b.no_classes = true;
             }
             continue;
         }
-        a0.absorbed_by = i; b.absorbed_by = i; b.no_classes = true;
-        c.fb_a = ta.prod; c.fb_b = tb.prod; c.fb_R = R;
+        set_block(net, i, Block{B_BOTTLENECK, ta.prod, tb.prod, i, -1, false, R});
+        b.no_classes = true;
     }
 
 }
@@ -933,13 +976,14 @@ static void plan_dual_gemm_joins(f8_net* net) {
     //          earlier one feeds nothing else  ->  one dual-GEMM launch, its int32 result never touches HBM
     for (int i = 0; opt.fuse_dual && i < nn; ++i) {
         Node& h = ND[i];
-        if (h.kind != N_CONV || h.fused_add < 0 || h.fb_a >= 0 || h.cd.groups != 1 || h.cd.kernel != 1 || h.cd.pad != 0) continue;
+        // (claimed(): after 1b a 1x1 conv that carries a join, h, can only host an identity bottleneck; one that carries none and feeds one add, g, only be absorbed)
+        if (h.kind != N_CONV || h.fused_add < 0 || claimed(net, i) || h.cd.groups != 1 || h.cd.kernel != 1 || h.cd.pad != 0) continue;
         if (h.cd.cin % 64 != 0 || round_up(h.cd.cout, 32) <= 32) continue;          // kernel instances: BK = 64, BN = 64
         const Node& ad = ND[h.fused_add];
         const int other = (ad.a == h.out) ? ad.b : ad.a;
         if (T[other].consumers.size() != 1 || other == net->out_t) continue;
         Node& g = ND[T[other].prod];
-        if (g.kind != N_CONV || g.fused_add >= 0 || g.absorbed_by >= 0 || g.fb_a >= 0 || g.cd.groups != 1 || g.cd.kernel != 1 || g.cd.pad != 0 ||
+        if (g.kind != N_CONV || g.fused_add >= 0 || claimed(net, T[other].prod) || g.cd.groups != 1 || g.cd.kernel != 1 || g.cd.pad != 0 ||
             g.cd.relu || g.cd.cin % 64 != 0 || g.cd.cout != h.cd.cout) continue;
         if (T[g.out].H != T[h.out].H || T[g.out].W != T[h.out].W) continue;
         h.dual = T[other].prod; g.dual_host = i;
@@ -964,13 +1008,14 @@ static void plan_stage_opening_blocks(f8_net* net) {
         const Tensor& tb = T[g.a];
         if (tb.consumers.size() != 1 || g.a == net->out_t) continue;
         Node& b = ND[tb.prod];
-        if (b.kind != N_CONV || b.fused_add >= 0 || b.absorbed_by >= 0 || b.cd.groups != 1 || b.cd.kernel != 3 || b.cd.stride != bs || b.cd.pad != 1 ||
+        // (claimed: b feeds g, which carries no join — a P12 host (1b) feeds the conv that carries the block's; a0 is a 1x1 conv that carries no join: no host)
+        if (b.kind != N_CONV || b.fused_add >= 0 || claimed(net, tb.prod) || b.cd.groups != 1 || b.cd.kernel != 3 || b.cd.stride != bs || b.cd.pad != 1 ||
             !b.cd.quant_input) continue;
         const Tensor& ta = T[b.a];
         if (ta.consumers.size() != 1 || b.a == net->out_t) continue;
         Node& a0 = ND[ta.prod];
-        if (a0.kind != N_CONV || a0.fused_add >= 0 || a0.absorbed_by >= 0 || a0.cd.groups != 1 || a0.cd.kernel != 1 || a0.cd.stride != 1 ||
-            a0.cd.pad != 0 || !a0.cd.quant_input || a0.a != h.a || a0.dual_host >= 0 || a0.dual >= 0) continue;
+        if (a0.kind != N_CONV || a0.fused_add >= 0 || claimed(net, ta.prod) || a0.cd.groups != 1 || a0.cd.kernel != 1 || a0.cd.stride != 1 ||
+            a0.cd.pad != 0 || !a0.cd.quant_input || a0.a != h.a || a0.dual >= 0) continue;
         const Tensor& x = T[h.a];
         int na = 0, nh = 0;
         if (consumer_format(x, a0.cd, &na, "finalize") || consumer_format(x, h.cd, &nh, "finalize")) continue;
@@ -980,8 +1025,8 @@ static void plan_stage_opening_blocks(f8_net* net) {
         int R = 0;
         if (bs == 1 ? !(opt.fuse_ds && fused_ds_supported(C, MID, h.cd.cout, x.H, x.W, &R))
                     : !(opt.fuse_opener && fused_opener_supported(C, MID, h.cd.cout, x.H, x.W, &R))) continue;
-        a0.absorbed_by = i; b.absorbed_by = i; b.no_classes = true;
-        h.fbd_a = ta.prod; h.fbd_b = tb.prod; h.fb_R = R; h.fbd_s2 = bs == 2;
+        set_block(net, i, Block{B_OPENING, ta.prod, tb.prod, h.dual, i, bs == 2, R});
+        b.no_classes = true;
     }
 
 }
@@ -1001,28 +1046,29 @@ static void plan_stage_chains(f8_net* net) {
         auto block_of = [&](int i, Blk* bk) -> bool {
             const Node& h = ND[i];
             if (h.kind != N_CONV || h.fused_add < 0 || h.chain_into >= 0) return false;
-            if (h.fb_a >= 0) {
-                const Node& a0 = ND[h.fb_a]; const Tensor& x = T[a0.a];
+            const Block& B = h.blk;                                // the blocks 1b and 1d marked are what a chain is made of
+            if (B.kind == B_BOTTLENECK) {
+                const Node& a0 = ND[B.b0]; const Tensor& x = T[a0.a];
                 *bk = Blk{i, a0.a, ND[h.fused_add].out, a0.cd.cin, a0.cd.cout, x.H, x.W, a0.cd.cin, false};
                 return true;
             }
-            if (h.fbd_a >= 0 && !h.fbd_s2) {
-                const Node& a0 = ND[h.fbd_a]; const Tensor& x = T[h.a];
+            if (B.kind == B_OPENING && !B.s2) {
+                const Node& a0 = ND[B.b0]; const Tensor& x = T[h.a];
                 *bk = Blk{i, h.a, ND[h.fused_add].out, h.cd.cout, a0.cd.cout, x.H, x.W, a0.cd.cin, true};
                 return true;
             }
-            if (h.fbd_a >= 0 && h.fbd_s2 && opt.fuse_tail) {
+            if (B.kind == B_OPENING && B.s2 && opt.fuse_tail) {
                 // stage-opening block with a stride-2 3x3 (1d fused it on f8_opener.hip): candidate for body.0 + body.2 there and the JOIN as the
                 // first block of the stage's chain (geometry of the chain = the block's OUTPUT map)
                 // chain_kernel<TAIL> addresses the shortcut's operand as [N][2H][2W][CIN0]: only an input map of exactly twice the output's sides
                 // (a 55x55 map also gives 28x28: the generic dual GEMM takes that one)
-                const Node& a0 = ND[h.fbd_a]; const Tensor& y = T[ND[h.fused_add].out]; const Tensor& x = T[h.a];
+                const Node& a0 = ND[B.b0]; const Tensor& y = T[ND[h.fused_add].out]; const Tensor& x = T[h.a];
                 if (x.H == 2 * y.H && x.W == 2 * y.W) {
                     *bk = Blk{i, h.a, ND[h.fused_add].out, h.cd.cout, a0.cd.cout, y.H, y.W, a0.cd.cin, true, true};
                     return true;
                 }
             }
-            if (h.dual >= 0 && h.fbd_a < 0 && h.cd.stride == 2 && h.cd.kernel == 1 && h.cd.quant_input && opt.fuse_tail) {
+            if (h.dual >= 0 && B.kind != B_OPENING && h.cd.stride == 2 && h.cd.kernel == 1 && h.cd.quant_input && opt.fuse_tail) {
                 // the same for an opening block whose convs run as separate launches (stages 2 / 3 of ResNet-50; stage 1 when body.0 and the shortcut
                 // read different int8 forms): the dual-GEMM join (1c) becomes the chain's first block, body.2's int8 output is its mid2
                 const Node& g = ND[h.dual]; const Tensor& y = T[ND[h.fused_add].out]; const Tensor& x = T[h.a]; const Tensor& m2 = T[g.a];
@@ -1053,32 +1099,27 @@ static void plan_stage_chains(f8_net* net) {
                 if (next < 0) break;
                 Blk nb; block_of(next, &nb);
                 if (nb.C != first.C || nb.MID != first.MID || nb.H != first.H || nb.W != first.W) break;
-                const int c0 = y.consumers[0], c1 = y.consumers[1], want0 = ND[next].fb_a, want1 = ND[next].fused_add;
+                const int c0 = y.consumers[0], c1 = y.consumers[1], want0 = ND[next].blk.b0, want1 = ND[next].fused_add;
                 if (!((c0 == want0 && c1 == want1) || (c0 == want1 && c1 == want0))) break;
                 hosts.push_back(next); cur = nb;
             }
             if (hosts.size() < 2) continue;
-            const int last = hosts.back();
-            for (int h : hosts) ND[h].chain_into = last;
-            ND[last].chain = hosts;
+            set_chain(net, hosts, C_STAGE);
             if (first.tail) {
                 // the opener becomes: [body.0 + body.2 on f8_opener.hip (P12), host = the 3x3, output = mid2 in body.4's int8 format] + [the chain's first block]
-                Node& h = ND[first.host];
-                if (h.fbd_a >= 0) {
-                    const int ia = h.fbd_a, ib = h.fbd_b;
-                    ND[ia].absorbed_by = ib; ND[ib].absorbed_by = -1; ND[ib].p12_a = ia; ND[ib].p12_s2 = true; ND[ib].fb_R = h.fb_R;
-                    h.fbd_a = h.fbd_b = -1; h.fbd_s2 = false;
+                const Block o = ND[first.host].blk;
+                if (o.kind == B_OPENING) {
+                    release_block(net, first.host);
+                    set_block(net, o.b2, Block{B_P12, o.b0, o.b2, -1, -1, true, o.R});
+                    ND[o.b2].no_classes = true;
                 }
-                h.tail = true;
+                set_block(net, first.host, Block{B_JOIN, -1, -1, ND[first.host].dual, first.host});
             }
         }
         // identity blocks that only the chain kernel could run and that did not end up in a chain: back to separate launches
         for (int i = 0; i < nn; ++i) {
-            Node& c = ND[i];
-            if (c.kind == N_CONV && c.fb_a >= 0 && c.fb_R == 0 && c.chain_into < 0) {
-                ND[c.fb_a].absorbed_by = -1; ND[c.fb_b].absorbed_by = -1; ND[c.fb_b].no_classes = false;
-                c.fb_a = c.fb_b = -1;
-            }
+            const Node& c = ND[i];
+            if (c.kind == N_CONV && c.blk.kind == B_BOTTLENECK && c.blk.R == 0 && c.chain_into < 0) release_block(net, i);
         }
     }
 }
@@ -1096,15 +1137,15 @@ static void plan_basic_block_chains(f8_net* net) {
     //          value 2 puts the JOIN of the stage-opening block in front (its stride-2 body.0 stays a launch of its own)
     if ((opt.fuse_bchain || opt.fuse_bchain7) && fuse_blocks) {
         auto cluster7 = [&](int cc, const Tensor& t) { return opt.fuse_bchain7 && bcchain_supported(cc, t.H, t.W, false); };
+        // (claimed(), here and below: the hosts so far carry a join — those of B_JOIN have `dual` —, or are a 3x3 that feeds a 1x1 conv (P12), which none of these does)
         auto bblock = [&](int i, int* in_t, int* out_t, int* C) -> bool {
             const Node& c2 = ND[i];
-            if (c2.kind != N_CONV || c2.fused_add < 0 || c2.bchain_into >= 0 || c2.fb_a >= 0 || c2.fbd_a >= 0 || c2.dual >= 0 || c2.dual_host >= 0 ||
-                c2.absorbed_by >= 0 || c2.cd.groups != 1 || c2.cd.kernel != 3 || c2.cd.stride != 1 || c2.cd.pad != 1 || c2.cd.relu || !c2.cd.quant_input) return false;
+            if (c2.kind != N_CONV || c2.fused_add < 0 || claimed(net, i) || c2.dual >= 0 || c2.cd.groups != 1 || c2.cd.kernel != 3 || c2.cd.stride != 1 || c2.cd.pad != 1 || c2.cd.relu || !c2.cd.quant_input) return false;
             const Tensor& tb = T[c2.a];
             if (tb.consumers.size() != 1 || c2.a == net->out_t) return false;
             const Node& c1 = ND[tb.prod];
-            if (c1.kind != N_CONV || c1.fused_add >= 0 || c1.absorbed_by >= 0 || c1.cd.groups != 1 || c1.cd.kernel != 3 || c1.cd.stride != 1 ||
-                c1.cd.pad != 1 || !c1.cd.quant_input || c1.dual >= 0 || c1.dual_host >= 0) return false;
+            if (c1.kind != N_CONV || c1.fused_add >= 0 || claimed(net, tb.prod) || c1.cd.groups != 1 || c1.cd.kernel != 3 || c1.cd.stride != 1 ||
+                c1.cd.pad != 1 || !c1.cd.quant_input || c1.dual >= 0) return false;
             const Node& ad = ND[c2.fused_add];
             const int other = (ad.a == c2.out) ? ad.b : ad.a;
             if (other != c1.a) return false;
@@ -1134,18 +1175,16 @@ static void plan_basic_block_chains(f8_net* net) {
                 if (!((k0 == w0 && k1 == w1) || (k0 == w1 && k1 == w0))) break;
                 hosts.push_back(next); cur_out = nout;
             }
-            const int lastn = hosts.back();
-            const bool bcc = cluster7(C, T[in_t]);
-            ND[lastn].bcc = bcc;
+            const bool cluster = cluster7(C, T[in_t]);
             for (int h : hosts) {
                 Node& c2 = ND[h]; Node& c1 = ND[T[c2.a].prod];
-                c2.bchain_into = lastn; c2.bb_a = T[c2.a].prod;
-                c1.absorbed_by = h; c1.no_classes = true; c2.no_classes = true;
+                set_block(net, h, Block{B_BASIC, T[c2.a].prod, h});
+                c1.no_classes = true; c2.no_classes = true;
             }
             // the stage-opening block in front of them (3x3 / 2 ReLU -> 3x3, 1x1 / 2 shortcut, join) joins the launch when the chain is
             // the only reader of its output (its two convs over the block input may read different int8 forms of it)
             [&] {
-                if ((bcc ? opt.fuse_bchain7 : opt.fuse_bchain) < 2 || (int)hosts.size() >= kBChainMaxBlocks || in_t == net->out_t) return;
+                if ((cluster ? opt.fuse_bchain7 : opt.fuse_bchain) < 2 || (int)hosts.size() >= kBChainMaxBlocks || in_t == net->out_t) return;
                 const Tensor& y = T[in_t];
                 const int c1f = T[ND[i].a].prod, adf = ND[i].fused_add;
                 if (y.consumers.size() != 2 || !((y.consumers[0] == c1f && y.consumers[1] == adf) || (y.consumers[0] == adf && y.consumers[1] == c1f))) return;
@@ -1153,37 +1192,36 @@ static void plan_basic_block_chains(f8_net* net) {
                 const Node& ad = ND[y.prod];
                 const int hi = ad.fused_into;
                 Node& h = ND[hi];
-                if (h.kind != N_CONV || h.fused_add != y.prod || h.bchain_into >= 0 || h.fb_a >= 0 || h.fbd_a >= 0 || h.dual >= 0 || h.dual_host >= 0 ||
-                    h.absorbed_by >= 0 || h.cd.groups != 1 || h.cd.kernel != 1 || h.cd.stride != 2 || h.cd.pad != 0 || h.cd.relu || !h.cd.quant_input) return;
+                if (h.kind != N_CONV || h.fused_add != y.prod || claimed(net, hi) || h.dual >= 0 || h.cd.groups != 1 || h.cd.kernel != 1 || h.cd.stride != 2 || h.cd.pad != 0 || h.cd.relu || !h.cd.quant_input) return;
                 const int other = (ad.a == h.out) ? ad.b : ad.a;
                 if (T[other].consumers.size() != 1 || other == net->out_t) return;
                 const int gi = T[other].prod;
                 Node& g = ND[gi];
-                if (g.kind != N_CONV || g.fused_add >= 0 || g.absorbed_by >= 0 || g.dual >= 0 || g.dual_host >= 0 || g.cd.groups != 1 || g.cd.kernel != 3 ||
+                if (g.kind != N_CONV || g.fused_add >= 0 || claimed(net, gi) || g.dual >= 0 || g.cd.groups != 1 || g.cd.kernel != 3 ||
                     g.cd.stride != 1 || g.cd.pad != 1 || g.cd.relu || !g.cd.quant_input) return;
                 if (T[g.a].consumers.size() != 1 || g.a == net->out_t) return;
                 const int bi = T[g.a].prod;
                 Node& b0 = ND[bi];
-                if (b0.kind != N_CONV || b0.fused_add >= 0 || b0.absorbed_by >= 0 || b0.dual >= 0 || b0.dual_host >= 0 || b0.cd.groups != 1 || b0.cd.kernel != 3 ||
+                if (b0.kind != N_CONV || b0.fused_add >= 0 || claimed(net, bi) || b0.dual >= 0 || b0.cd.groups != 1 || b0.cd.kernel != 3 ||
                     b0.cd.stride != 2 || b0.cd.pad != 1 || !b0.cd.quant_input || b0.a != h.a) return;
                 const Tensor& x = T[h.a];
                 if (ND[x.prod].kind == N_INPUT || x.H != 2 * y.H || x.W != 2 * y.W) return;
                 if (b0.cd.cin * 2 != C || h.cd.cin * 2 != C || b0.cd.cout != C || g.cd.cin != C || g.cd.cout != C || h.cd.cout != C) return;
                 int na = 0, nh = 0;
                 if (consumer_format(x, b0.cd, &na, "finalize") || consumer_format(x, h.cd, &nh, "finalize")) return;
-                if (bcc) {                                           // only the join (body.2 + shortcut) joins the cluster launch; body.0 writes its 7x7 int8 output
+                if (cluster) {                                           // only the join (body.2 + shortcut) joins the cluster launch; body.0 writes its 7x7 int8 output
                     if (!bcchain_supported(C, y.H, y.W, true)) return;
-                    h.btail = true; h.bds_b = gi; h.bchain_into = lastn;
-                    g.absorbed_by = hi; g.no_classes = true;
+                    set_block(net, hi, Block{B_BASIC_JOIN, -1, gi, -1, hi});
+                    g.no_classes = true;
                     hosts.insert(hosts.begin(), hi);
                     return;
                 }
                 if (!bchain_ds_supported(C, y.H, y.W)) return;
-                h.bds_a = bi; h.bds_b = gi; h.bchain_into = lastn;
-                b0.absorbed_by = hi; g.absorbed_by = hi; b0.no_classes = true; g.no_classes = true;
+                set_block(net, hi, Block{B_BASIC_OPENING, bi, gi, -1, hi});
+                b0.no_classes = true; g.no_classes = true;
                 hosts.insert(hosts.begin(), hi);
             }();
-            ND[lastn].bchain = hosts;
+            set_chain(net, hosts, cluster ? C_BASIC_CLUSTER : C_BASIC);
         }
     }
 }
@@ -1198,19 +1236,19 @@ static void plan_inverted_residuals(f8_net* net) {
     //          block input], intermediates read by nobody else  ->  one launch (f8_ir.hip), the expanded tensors stay in LDS
     for (int i = 0; opt.fuse_ir && i < nn; ++i) {
         Node& c = ND[i];
+        // (claimed(): of the hosts so far only an identity bottleneck's is a stride-1 1x1 conv without `dual`, as c and a0 are; depthwise convs are this pass's alone)
         if (c.kind != N_CONV || c.cd.groups != 1 || c.cd.kernel != 1 || c.cd.stride != 1 || c.cd.pad != 0 || !c.cd.quant_input ||
-            c.absorbed_by >= 0 || c.fb_a >= 0 || c.dual >= 0 || c.dual_host >= 0) continue;
+            claimed(net, i) || c.dual >= 0) continue;
         const Tensor& tb = T[c.a];
         if (tb.consumers.size() != 1 || c.a == net->out_t) continue;
         Node& b = ND[tb.prod];
         if (b.kind != N_CONV || b.cd.groups == 1 || b.cd.groups != b.cd.cin || b.cd.kernel != 3 || b.cd.pad != 1 || (b.cd.stride != 1 && b.cd.stride != 2) ||
-            !b.cd.quant_input || b.fused_add >= 0 || b.absorbed_by >= 0) continue;
+            !b.cd.quant_input || b.fused_add >= 0 || claimed(net, tb.prod)) continue;
         const Tensor& ta = T[b.a];
         if (ta.consumers.size() != 1 || b.a == net->out_t) continue;
         Node& a0 = ND[ta.prod];
         if (a0.kind != N_CONV || a0.cd.groups != 1 || a0.cd.kernel != 1 || a0.cd.stride != 1 || a0.cd.pad != 0 || a0.fused_add >= 0 ||
-            a0.absorbed_by >= 0 || a0.dual >= 0 || a0.dual_host >= 0 || !a0.cd.quant_input) continue;
-        if (a0.ir_a >= 0 || a0.fb_a >= 0 || a0.fbd_a >= 0) continue;   // already the host of another fused launch (chains of 1x1 / dw / 1x1 / dw ...)
+            claimed(net, ta.prod) || a0.dual >= 0 || !a0.cd.quant_input) continue;      // (a host too: chains of 1x1 / dw / 1x1 / dw ...)
         if (ND[T[a0.a].prod].kind == N_INPUT) continue;          // the network input has its own layouts
         if (c.fused_add >= 0) {                                   // a residual join must be with the block input
             const Node& ad = ND[c.fused_add];
@@ -1229,8 +1267,7 @@ static void plan_inverted_residuals(f8_net* net) {
             // images) stay three launches: 34 - 40 / 90 - 114.  fuse_ir = 2 fuses every block that has an instance.
             if (T[c.out].H * T[c.out].W < 128) continue;
         }
-        a0.absorbed_by = i; b.absorbed_by = i;
-        c.ir_a = ta.prod; c.ir_b = tb.prod; c.ir_R = R; c.ir_G = G;
+        set_block(net, i, Block{B_IR, ta.prod, tb.prod, i, -1, false, R, G});
     }
 
 }
@@ -1243,27 +1280,27 @@ static void plan_inverted_residual_chains(f8_net* net) {
     const Options& opt = net->opt;
     // ---- 1e2. runs of >= 2 consecutive STRIDE-1 inverted residuals on one map  ->  ONE launch, one workgroup per image (f8_irchain.hip): the
     //           block outputs between them exist in no form at all (int8 block input and int32 stream in LDS).  Its own matcher: a block pass 1e
-    //           left as three launches (the 7x7 maps under fuse_ir = 1) is taken as well, and 1e's marks of a chained block are undone.
+    //           left as three launches (the 7x7 maps under fuse_ir = 1) is taken as well, and the block 1e made of a chained one is released first.
     if (!opt.fuse_irchain) return;
     // the stride-1 block whose project conv is c: expand a0 -> depthwise b -> c [+ join with a0's input]; out = the block output
     struct Blk { int a0, b, c, out; bool res; };
     auto match = [&](int ci, Blk* k) -> bool {
         const Node& c = ND[ci];
         if (c.kind != N_CONV || c.cd.groups != 1 || c.cd.kernel != 1 || c.cd.stride != 1 || c.cd.pad != 0 || !c.cd.quant_input ||
-            (c.absorbed_by >= 0) || c.fb_a >= 0 || c.fbd_a >= 0 || c.dual >= 0 || c.dual_host >= 0 || c.chain_into >= 0 || c.bchain_into >= 0 ||
-            c.p12_a >= 0 || c.bb_a >= 0 || c.h2_head >= 0) return false;
+            claimed(net, ci, B_IR) || c.dual >= 0) return false;      // (the block 1e hosted here is taken over; one this pass chained already is claimed by its chain)
         const Tensor& tb = T[c.a];
         if (tb.prod < 0 || tb.consumers.size() != 1 || c.a == net->out_t) return false;
         const int bi = tb.prod;
         const Node& b = ND[bi];
         if (b.kind != N_CONV || b.cd.groups == 1 || b.cd.groups != b.cd.cin || b.cd.cout != b.cd.cin || b.cd.kernel != 3 || b.cd.pad != 1 || b.cd.stride != 1 ||
-            !b.cd.quant_input || b.fused_add >= 0 || (b.absorbed_by >= 0 && b.absorbed_by != ci)) return false;
+            !b.cd.quant_input || b.fused_add >= 0 || (b.absorbed_by >= 0 && b.absorbed_by != ci)) return false;      // (a member of c's own block: 1e)
         const Tensor& ta = T[b.a];
         if (ta.prod < 0 || ta.consumers.size() != 1 || b.a == net->out_t) return false;
         const int ai = ta.prod;
         const Node& a0 = ND[ai];
         if (a0.kind != N_CONV || a0.cd.groups != 1 || a0.cd.kernel != 1 || a0.cd.stride != 1 || a0.cd.pad != 0 || !a0.cd.quant_input || a0.fused_add >= 0 ||
-            (a0.absorbed_by >= 0 && a0.absorbed_by != ci) || a0.dual >= 0 || a0.dual_host >= 0 || a0.ir_a >= 0 || a0.fb_a >= 0 || a0.fbd_a >= 0) return false;
+            (a0.absorbed_by >= 0 && a0.absorbed_by != ci) || a0.dual >= 0 || a0.dual_host >= 0 || (a0.blk.kind != B_NONE && !(a0.blk.kind == B_IR && a0.chain_into >= 0))) return false;
+        // (not claimed(a0): the project conv of an inverted residual this pass CHAINED passes — that mark is the term this list never had; the other hosts are no stride-1 1x1 conv without a join)
         if (T[a0.a].prod < 0 || ND[T[a0.a].prod].kind == N_INPUT) return false;      // the network input has its own layouts
         k->a0 = ai; k->b = bi; k->c = ci; k->res = false; k->out = c.out;
         if (c.fused_add >= 0) {                                   // a residual join must be with the block input
@@ -1286,10 +1323,9 @@ static void plan_inverted_residual_chains(f8_net* net) {
         }
         return (int)run.size() <= kIRChainMaxBlocks && irchain_supported(x.H, x.W, cin_max, cout_max, keep_max);
     };
-    std::vector<char> used(nn, 0);
     for (int i = 0; i < nn; ++i) {
         Blk k0;
-        if (used[i] || !match(i, &k0)) continue;
+        if (!match(i, &k0)) continue;
         std::vector<Blk> run{k0};
         if (!fits(run)) continue;
         for (;;) {                                                // extend: the block output's only readers are the next block's expand conv and its join
@@ -1317,17 +1353,13 @@ static void plan_inverted_residual_chains(f8_net* net) {
             if (!fits(run)) { run.pop_back(); break; }
         }
         if (run.size() < 2) continue;
-        const int host = run.back().c;
         std::vector<int> hosts;
         for (const Blk& k : run) {
-            Node& c = ND[k.c];
-            used[k.c] = 1;
-            c.ir_a = c.ir_b = -1; c.ir_R = c.ir_G = 0;            // (pass 1e's marks)
-            c.irc_a = k.a0; c.irc_b = k.b; c.irc_into = host;
-            ND[k.a0].absorbed_by = k.c; ND[k.b].absorbed_by = k.c;
+            if (ND[k.c].blk.kind != B_NONE) release_block(net, k.c);      // (pass 1e's block: its tile is the stand-alone launch's)
+            set_block(net, k.c, Block{B_IR, k.a0, k.b, k.c});
             hosts.push_back(k.c);
         }
-        ND[host].irchain = hosts;
+        set_chain(net, hosts, C_IR);
     }
 }
 
@@ -1343,7 +1375,7 @@ static void plan_mobilenet_v2_head(f8_net* net) {
     for (int i = 0; opt.fuse_head2 && opt.fuse_stem && i < nn; ++i) {
         Node& c = ND[i];
         if (c.kind != N_CONV || c.cd.groups != 1 || c.cd.kernel != 1 || c.cd.stride != 1 || c.cd.pad != 0 || c.cd.relu || !c.cd.quant_input ||
-            c.cd.input_signed || c.fused_add >= 0 || c.absorbed_by >= 0 || c.ir_a >= 0 || c.irc_a >= 0 || c.dual >= 0 || c.dual_host >= 0 || c.out == net->out_t) continue;
+            c.cd.input_signed || c.fused_add >= 0 || claimed(net, i) || c.dual >= 0 || c.out == net->out_t) continue;      // (claimed: a stride-1 1x1 conv that carries no join and has no `dual` hosts only B_IR)
         if (c.cd.cin != 32 || round_up(c.cd.cout, 32) != 32) continue;
         const Tensor& tb = T[c.a];
         if (tb.consumers.size() != 1 || c.a == net->out_t) continue;
@@ -1364,8 +1396,7 @@ static void plan_mobilenet_v2_head(f8_net* net) {
         bool int8_readers = !T[c.out].consumers.empty() && T[c.out].consumers.size() <= 2;
         for (int u : T[c.out].consumers) if (ND[u].kind != N_CONV || !ND[u].cd.quant_input) int8_readers = false;
         if (!int8_readers) continue;
-        h.absorbed_by = i; b.absorbed_by = i;
-        c.h2_head = ta.prod; c.h2_dw = tb.prod;
+        set_block(net, i, Block{B_HEAD2, ta.prod, tb.prod, i});
     }
 
 }
@@ -1386,17 +1417,16 @@ static void plan_last_conv_and_pool(f8_net* net) {
         int ci = t.prod;
         if (ND[ci].kind == N_ADD) { if (ND[ci].fused_into < 0) continue; ci = ND[ci].fused_into; }
         Node& c = ND[ci];
-        if (c.kind == N_CONV && c.bchain_into == ci && c.bcc && c.fused_add >= 0 && ND[c.fused_add].out == p.a && p.out != net->out_t) {
+        if (c.kind == N_CONV && c.chain_into == ci && c.chain_kind == C_BASIC_CLUSTER && c.fused_add >= 0 && ND[c.fused_add].out == p.a && p.out != net->out_t) {
             c.pool = i; p.pool_host = ci;                         // the last block of a 7x7 BasicBlock cluster chain: the same (f8_bcchain.hip)
             continue;
         }
-        if (c.kind == N_CONV && c.chain_into == ci && c.fused_add >= 0 && ND[c.fused_add].out == p.a && p.out != net->out_t &&
+        if (c.kind == N_CONV && c.chain_into == ci && c.chain_kind == C_STAGE && c.fused_add >= 0 && ND[c.fused_add].out == p.a && p.out != net->out_t &&
             cchain_supported(c.cd.cout, c.cd.cin, t.H, t.W, c.cd.cout, false)) {      // (geometry: a chain's last block is an identity block)
             c.pool = i; p.pool_host = ci;                         // the last block of a 7x7 cluster chain: the pool is summed from its stream registers (f8_cchain.hip)
             continue;
         }
-        if (c.kind != N_CONV || c.absorbed_by >= 0 || c.dual >= 0 || c.dual_host >= 0 || c.fb_a >= 0 || c.fbd_a >= 0 || c.chain_into >= 0 || c.bchain_into >= 0 ||
-            c.ir_a >= 0 || c.irc_a >= 0 || c.p12_a >= 0 || c.bb_a >= 0 || c.h2_head >= 0 || c.cd.groups != 1 || c.cd.kernel != 1 || c.cd.stride != 1 || c.cd.pad != 0 || !c.cd.quant_input) continue;
+        if (c.kind != N_CONV || claimed(net, ci) || c.dual >= 0 || c.cd.groups != 1 || c.cd.kernel != 1 || c.cd.stride != 1 || c.cd.pad != 0 || !c.cd.quant_input) continue;
         if ((c.fused_add >= 0 ? ND[c.fused_add].out : c.out) != p.a) continue;
         if (c.fused_add < 0 && T[c.out].consumers.size() != 1) continue;
         const int ckp = round_up(c.cd.cin, 32), coutP = round_up(c.cd.cout, 32);
@@ -1431,50 +1461,36 @@ static void plan_tensor_forms(f8_net* net) {
                 int n = 0;
                 consumer_format(s, nd.cd, &n, "finalize");
                 nd.depthwise = nd.cd.groups != 1;
-                if ((nd.absorbed_by >= 0 && ND[nd.absorbed_by].fbd_b == i) || (nd.dual_host >= 0 && ND[nd.dual_host].fbd_a >= 0)) break;   // DS: in LDS
-                if (nd.p12_a >= 0) break;                    // the 1x1's output lives in LDS inside the launch
-                if (nd.h2_head >= 0 || (nd.absorbed_by >= 0 && ND[nd.absorbed_by].h2_dw == i)) break;   // 1x1 / depthwise of the MobileNet-V2 head launch: rows in registers
-                if (nd.absorbed_by >= 0 && ND[nd.absorbed_by].bds_b == i) {        // second 3x3 of the opening block of a bchain launch: `mid` lives in LDS
-                    if (ND[nd.absorbed_by].btail) add_form(s, FORM_I8, n, nd.cd.input_signed ? 1 : 0);   // (cluster launch: body.0's int8 output in HBM)
-                    break;
-                }
-                                                                 // (its 3x3 / 2 and its shortcut conv each ask for their int8 form of the block input below)
-                if (nd.bb_a >= 0) {                          // second conv of a chained BasicBlock: its source (`mid`) lives in LDS
-                    if (bchain_pos(net, i) == 0) {
-                        const Node& ad = ND[nd.fused_add];
-                        add_form(T[(ad.a == nd.out) ? ad.b : ad.a], FORM_I32, 0, 0);      // the stage's int32 stream: the chain's only input form
-                    }
-                    break;
-                }
-                if (nd.absorbed_by >= 0 && ND[nd.absorbed_by].bb_a == i) break;            // first conv of a chained BasicBlock: its int8 input is made in the launch
-                {   // inverted-residual chain (f8_irchain.hip): only the first block's input exists in HBM (int8, and int32 when it joins it)
-                    const int ich = nd.irc_a >= 0 ? i : (nd.absorbed_by >= 0 && ND[nd.absorbed_by].irc_a >= 0 ? nd.absorbed_by : -1);
-                    if (ich >= 0) {
-                        const Node& hc = ND[ich];
-                        const bool first = ND[hc.irc_into].irchain[0] == ich;
-                        if (i == hc.irc_a && first) { add_form(s, FORM_I8, n, nd.cd.input_signed ? 1 : 0); break; }   // expand conv of the first block
-                        if (i == ich && first && nd.fused_add >= 0) add_form(T[ND[hc.irc_a].a], FORM_I32, 0, 0);
+                // nd inside a fused block: does its source exist in HBM at all, and which form of the stream does the launch read?
+                int host = -1;
+                const Role role = role_in_block(net, i, &host);
+                const BlockKind bk = role != R_NONE ? ND[host].blk.kind : B_NONE;
+                const int pos = chain_pos(net, host);            // of its block in a chain launch: the tensors between a chain's blocks exist in no form at all
+                auto stream = [&]() -> Tensor& { const Node& ad = ND[nd.fused_add]; return T[(ad.a == nd.out) ? ad.b : ad.a]; };   // the other operand of nd's join
+                bool in_launch = true;                           // nd's source lives in LDS / registers inside the launch: no HBM form
+                switch (bk) {
+                    case B_OPENING: in_launch = role == R_B2 || role == R_B4; break;      // (body.0 and the shortcut read the block input)
+                    case B_P12: in_launch = role == R_B2; break;
+                    case B_HEAD2: in_launch = role != R_B0; break;
+                    case B_BASIC_JOIN:                           // (cluster launch: body.0's int8 output in HBM)
+                        if (role == R_B2) add_form(s, FORM_I8, n, nd.cd.input_signed ? 1 : 0);
+                        [[fallthrough]];
+                    case B_BASIC_OPENING: in_launch = role == R_B2; break;      // (its 3x3 / 2 and its shortcut conv each ask for their int8 form of the block input below)
+                    case B_BASIC:                                // the first conv's int8 input is made in the launch from the stage's int32 stream: the chain's only input form
+                        if (role == R_B2 && pos == 0) add_form(stream(), FORM_I32, 0, 0);
                         break;
-                    }
+                    case B_IR:                                   // in a chain (f8_irchain.hip) only the first block's input exists in HBM: int8, and int32 when it joins it
+                        in_launch = pos >= 0 || role != R_B0;    // (alone: the expand conv reads the block input from HBM)
+                        if (pos == 0 && role == R_B0) add_form(s, FORM_I8, n, nd.cd.input_signed ? 1 : 0);
+                        if (pos <= 0 && role == R_B4 && nd.fused_add >= 0) add_form(stream(), FORM_I32, 0, 0);
+                        break;
+                    case B_BOTTLENECK:                           // in a chain (f8_chain.hip) an identity first block reads only the int32 form of the stage input
+                        if (role == R_B0) { in_launch = pos >= 0; if (pos == 0) add_form(s, FORM_I32, 0, 0); }      // (alone: it reads the block input from HBM)
+                        if (role == R_B4 && pos <= 0) add_form(stream(), FORM_I32, 0, 0);
+                        break;
+                    default: in_launch = false;                  // a conv of its own; B_JOIN: the shortcut and body.4 read their int8 inputs from HBM
                 }
-                {   // stage chain (f8_chain.hip): the tensors between its blocks exist in no form at all; an identity first block
-                    // reads only the int32 form of the stage input (its int8 copy is made in the launch)
-                    const int host = nd.absorbed_by >= 0 && ND[nd.absorbed_by].fb_a == i ? nd.absorbed_by : -1;   // nd = body.0 of an identity block
-                    const int pos = chain_pos(net, host);
-                    if (pos > 0) break;
-                    if (pos == 0) { add_form(s, FORM_I32, 0, 0); break; }
-                }
-                if (nd.fb_a >= 0 || (nd.absorbed_by >= 0 && ND[nd.absorbed_by].fb_b == i) || nd.ir_a >= 0 ||
-                    (nd.absorbed_by >= 0 && ND[nd.absorbed_by].ir_b == i)) {
-                    // source lives in LDS inside the fused launch: no HBM form.  (The block's first conv
-                    // still reads the block input from HBM and falls through to the generic case.)
-                    if (nd.fused_add >= 0 && chain_pos(net, i) <= 0) {
-                        const Node& ad = ND[nd.fused_add];
-                        const int other = (ad.a == nd.out) ? ad.b : ad.a;
-                        add_form(T[other], FORM_I32, 0, 0);
-                    }
-                    break;
-                }
+                if (in_launch) break;
                 nd.stem = !nd.depthwise && nd.cd.cin <= 4 && ND[s.prod].kind == N_INPUT && nd.cd.kernel <= 8 &&
                           s.consumers.size() == 1 && nd.a != net->out_t && n == 0;
                 if (nd.stem) {
@@ -1482,18 +1498,14 @@ static void plan_tensor_forms(f8_net* net) {
                     const int f = add_form(s, FORM_STEM, 0, 0);
                     Form& F = s.forms[f];
                     F.sgn = nd.cd.input_signed ? 1 : 0;
-                    const bool h2 = nd.absorbed_by >= 0 && ND[nd.absorbed_by].h2_head == i;
+                    const bool h2 = bk == B_HEAD2;
                     F.pad = nd.cd.pad + (nd.sp_pool >= 0 ? 2 : 0) + (h2 ? 4 : 0);      // fused stem + pool: 2 more halo pixels keep every tile's patch in memory (head launch of MobileNet-V2: 5 in all)
                     F.Hp = s.H + 2 * F.pad;
                     F.Wp = round_up(std::max(s.W + 2 * F.pad, nd.cd.stride * (Q - 1) + 8), (nd.sp_pool >= 0 || h2) ? 4 : 2);
                 } else {
                     add_form(s, FORM_I8, n, nd.cd.input_signed ? 1 : 0);
                 }
-                if (nd.fused_add >= 0 && nd.dual < 0 && nd.bds_a < 0 && !nd.btail) {
-                    const Node& ad = ND[nd.fused_add];
-                    const int other = (ad.a == nd.out) ? ad.b : ad.a;
-                    add_form(T[other], FORM_I32, 0, 0);
-                }
+                if (nd.fused_add >= 0 && nd.dual < 0 && bk != B_BASIC_OPENING && bk != B_BASIC_JOIN) add_form(stream(), FORM_I32, 0, 0);
                 break;
             }
             case N_ADD:
@@ -1528,27 +1540,8 @@ static void plan_tensor_forms(f8_net* net) {
 
 // pass 3: the launches in node order, one emitter per launch family.  Each fills one Step: its input / output forms, the packed weights, the
 // algorithmic bytes / ops / essential vector work, the name.  The weight image assigns offsets in call order: every emitter packs its convs in
-// role order (block_convs), the order the plans were made with.
+// role order (Block), the order the plans were made with.
 
-// The convs of a block by role, from its host node (node ids, -1: the block has none) — body.0 / body.2 / body.4 and the shortcut:
-//   bottleneck identity block (fb_a): body.0, body.2, host = body.4;  stage-opening block (fbd_a: DS / stride-2 opener): body.0, body.2, host.dual =
-//   body.4, host = shortcut;  its join alone (tail, the first block of a chain): host.dual = body.4, host = shortcut;  BasicBlock (bb_a): first 3x3 =
-//   body.0, host = body.2;  opening BasicBlock (bds_a): body.0, body.2, host = shortcut;  inverted residual (ir_a; irc_a in a chain): expand =
-//   body.0, depthwise = body.2, host = project (body.4)
-struct BlockConvs { int b0 = -1, b2 = -1, b4 = -1, sc = -1; };
-static BlockConvs block_convs(const f8_net* net, int host) {
-    const Node& h = net->nodes[host];
-    BlockConvs r;
-    if (h.tail) { r.b4 = h.dual; r.sc = host; }
-    else if (h.fbd_a >= 0) { r.b0 = h.fbd_a; r.b2 = h.fbd_b; r.b4 = h.dual; r.sc = host; }
-    else if (h.btail) { r.b2 = h.bds_b; r.sc = host; }
-    else if (h.bds_a >= 0) { r.b0 = h.bds_a; r.b2 = h.bds_b; r.sc = host; }
-    else if (h.fb_a >= 0) { r.b0 = h.fb_a; r.b2 = h.fb_b; r.b4 = host; }
-    else if (h.bb_a >= 0) { r.b0 = h.bb_a; r.b2 = host; }
-    else if (h.irc_a >= 0) { r.b0 = h.irc_a; r.b2 = h.irc_b; r.b4 = host; }
-    else if (h.ir_a >= 0) { r.b0 = h.ir_a; r.b2 = h.ir_b; r.b4 = host; }
-    return r;
-}
 // conv c's input: the tensor (*t) and its form in c's int8 consumer format (*f; pass 2 made it)
 static int conv_input_i8(const f8_net* net, const Node& c, int* t, int* f) {
     int n = 0;
@@ -1576,7 +1569,7 @@ static double conv_ops(const f8_net* net, const Node& c) {
 // bytes per image a step writes: its output forms over px pixels of map o
 static double out_bytes(const Step& st, const Tensor& o, double px) { return px * o.Cs * ((st.out.f32 >= 0 ? 4 : 0) + out_forms8(st)); }
 // packs a block's convs in role order (frag: also in MFMA-fragment order) and adds their ops / weight bytes to the step
-static void pack_block(f8_net* net, const BlockConvs& r, bool frag, Step& st) {
+static void pack_block(f8_net* net, const Block& r, bool frag, Step& st) {
     for (int c : {r.b0, r.b2, r.b4, r.sc}) {
         if (c < 0) continue;
         Node& n = net->nodes[c];
@@ -1586,7 +1579,7 @@ static void pack_block(f8_net* net, const BlockConvs& r, bool frag, Step& st) {
     }
 }
 // "body.0+body.2+..." of a block's output tensors, role order
-static std::string block_names(const f8_net* net, const BlockConvs& r) {
+static std::string block_names(const f8_net* net, const Block& r) {
     std::string s;
     for (int c : {r.b0, r.b2, r.b4, r.sc}) if (c >= 0) s += (s.empty() ? "" : "+") + tname(net, net->nodes[c].out);
     return s;
@@ -1612,7 +1605,7 @@ static int emit_input(f8_net* net, int i, Step& st, std::vector<int>* extra) {
 // MobileNet-V2 head: 3x3 / 2 conv + depthwise 3x3 + this 1x1 in one launch
 static int emit_head2(f8_net* net, int i, Step& st, std::vector<int>* extra) {
     auto& T = net->tensors; auto& ND = net->nodes;
-    Node& nd = ND[i]; Node& hh = ND[nd.h2_head]; Node& hb = ND[nd.h2_dw];
+    Node& nd = ND[i]; Node& hh = ND[nd.blk.b0]; Node& hb = ND[nd.blk.b2];
     const Tensor& s = T[hh.a];
     st.kind = S_HEAD2;
     st.src_t = hh.a; st.src_f = find_form(s, FORM_STEM, 0, 0);
@@ -1654,8 +1647,8 @@ static int emit_stem_pool(f8_net* net, int i, Step& st, std::vector<int>* extra)
 static int emit_bchain(f8_net* net, int i, Step& st, std::vector<int>* extra) {
     auto& T = net->tensors; auto& ND = net->nodes;
     const Node& nd = ND[i];
-    const std::vector<int>& ch = nd.bchain;
-    const BlockConvs r0 = block_convs(net, ch[0]);
+    const std::vector<int>& ch = nd.chain;
+    const Block& r0 = ND[ch[0]].blk;
     const bool ds = r0.sc >= 0;                  // the chain starts with the stage-opening block: ch[0] is its shortcut conv
     const Node& f1 = ND[r0.b0];
     const Tensor& x = T[f1.a];
@@ -1663,7 +1656,7 @@ static int emit_bchain(f8_net* net, int i, Step& st, std::vector<int>* extra) {
     if (!ds) { st.src_t = f1.a; st.src_f = find_form(x, FORM_I32, 0, 0); }
     else if (int rc = conv_input_i8(net, f1, &st.src_t, &st.src_f)) return rc;      // its two convs over the block input may read
     else if ((rc = conv_input_i8(net, ND[r0.sc], &st.res_t, &st.res_f))) return rc;  // different int8 forms of it
-    for (int h : ch) pack_block(net, block_convs(net, h), true, st);
+    for (int h : ch) pack_block(net, ND[h].blk, true, st);
     const int out_t = ND[nd.fused_add].out;
     select_outputs(net, out_t, &st.out, extra);
     const Tensor& o = T[out_t];
@@ -1679,8 +1672,8 @@ static int emit_bchain(f8_net* net, int i, Step& st, std::vector<int>* extra) {
 static int emit_bcchain(f8_net* net, int i, Step& st, std::vector<int>* extra) {
     auto& T = net->tensors; auto& ND = net->nodes;
     const Node& nd = ND[i];
-    const std::vector<int>& ch = nd.bchain;
-    const BlockConvs r0 = block_convs(net, ch[0]);
+    const std::vector<int>& ch = nd.chain;
+    const Block& r0 = ND[ch[0]].blk;
     const bool tail = r0.sc >= 0;
     st.kind = S_BCHAIN;
     st.cluster = true;
@@ -1688,7 +1681,7 @@ static int emit_bcchain(f8_net* net, int i, Step& st, std::vector<int>* extra) {
     if (!tail) { st.src_t = f1.a; st.src_f = find_form(T[f1.a], FORM_I32, 0, 0); }
     else if (int rc = conv_input_i8(net, f1, &st.src_t, &st.src_f)) return rc;          // body.0's output in body.2's format
     else if ((rc = conv_input_i8(net, ND[r0.sc], &st.res_t, &st.res_f))) return rc;     // the block input in the shortcut's format
-    for (int h : ch) pack_block(net, block_convs(net, h), true, st);
+    for (int h : ch) pack_block(net, ND[h].blk, true, st);
     const Tensor& o = T[ND[nd.fused_add].out];               // the stage's output map
     int out_t = ND[nd.fused_add].out;
     if (nd.pool >= 0) {                                      // ... summed over its pixels in the launch (1i): the step's outputs are the POOLED tensor's forms
@@ -1709,7 +1702,7 @@ static int emit_chain(f8_net* net, int i, Step& st, std::vector<int>* extra) {
     auto& T = net->tensors; auto& ND = net->nodes;
     const Node& nd = ND[i];
     const std::vector<int>& ch = nd.chain;
-    const BlockConvs r0 = block_convs(net, ch[0]);
+    const Block& r0 = ND[ch[0]].blk;
     const bool tail = r0.b0 < 0;                 // first block = the join of a stride-2 opening block (its body.0 + body.2: the S_P12 step in front)
     const bool ds = r0.sc >= 0;                  // ... or a stage-opening block: the chain reads an int8 form of the stage input
     const Node& a0 = ND[tail ? r0.b4 : r0.b0];
@@ -1718,7 +1711,7 @@ static int emit_chain(f8_net* net, int i, Step& st, std::vector<int>* extra) {
     if (!ds) { st.src_t = a0.a; st.src_f = find_form(x, FORM_I32, 0, 0); }
     else if (int rc = conv_input_i8(net, ND[tail ? r0.sc : r0.b0], &st.src_t, &st.src_f)) return rc;    // tail: the shortcut's int8 form
     else if (tail && (rc = conv_input_i8(net, a0, &st.src2_t, &st.src2_f))) return rc;                  // mid2 in body.4's format
-    for (int h : ch) pack_block(net, block_convs(net, h), true, st);
+    for (int h : ch) pack_block(net, ND[h].blk, true, st);
     int out_t = ND[nd.fused_add].out;
     const Tensor& o = T[out_t];                  // the stage's output map (geometry of the chain)
     if (nd.pool >= 0) {                          // ... summed over its pixels in the launch (1i): the step's outputs are the POOLED tensor's forms
@@ -1740,12 +1733,12 @@ static int emit_chain(f8_net* net, int i, Step& st, std::vector<int>* extra) {
 static int emit_fused(f8_net* net, int i, Step& st, std::vector<int>* extra) {
     auto& T = net->tensors; auto& ND = net->nodes;
     const Node& nd = ND[i];
-    const BlockConvs r = block_convs(net, i);
+    const Block& r = nd.blk;
     const Node& na = ND[r.b0]; const Node& nb = ND[r.b2]; const Node& ng = ND[r.b4];
     const bool ds = r.sc >= 0;
     const Tensor& x = T[na.a];                   // (DS: body.0 and the shortcut read one int8 form of it, pass 1d)
     st.kind = S_FUSED;
-    st.variant = nd.fbd_s2 ? V_OPENER : V_BOTTLENECK;
+    st.variant = r.s2 ? V_OPENER : V_BOTTLENECK;
     if (const int rc = conv_input_i8(net, na, &st.src_t, &st.src_f)) return rc;
     pack_block(net, r, false, st);
     if (!ds) { st.res_t = na.a; st.res_f = find_form(x, FORM_I32, 0, 0); }
@@ -1756,7 +1749,7 @@ static int emit_fused(f8_net* net, int i, Step& st, std::vector<int>* extra) {
     const double px = (double)x.H * x.W, pxo = (double)o.H * o.W;   // stride-2 opener: body.0 runs on the input map
     st.valu_per_img = 3.0 * (px * na.cd.cout + pxo * nb.cd.cout) + pxo * o.C * 2.0 + 3.0 * pxo * o.Cs * out_forms8(st);
     st.bytes_per_img = px * x.Cs * (ds ? 1 : 1 + 4) + out_bytes(st, o, pxo);                // int8 input (identity: + int32 residual), once each
-    st.name = std::string(!ds ? "fused_bottleneck_R" : nd.fbd_s2 ? "fused_opener_s2_R" : "fused_bottleneck_ds_R") + std::to_string(nd.fb_R) + ":" +
+    st.name = std::string(!ds ? "fused_bottleneck_R" : r.s2 ? "fused_opener_s2_R" : "fused_bottleneck_ds_R") + std::to_string(r.R) + ":" +
               block_names(net, r);
     return F8_OK;
 }
@@ -1764,10 +1757,10 @@ static int emit_fused(f8_net* net, int i, Step& st, std::vector<int>* extra) {
 // 1x1 -> 3x3 of a 7x7 bottleneck block in one launch (node i = the 3x3), or body.0 + body.2 of a stride-2 opening block whose join opens its chain
 static int emit_p12(f8_net* net, int i, Step& st, std::vector<int>* extra) {
     auto& T = net->tensors;
-    Node& nd = net->nodes[i]; Node& na = net->nodes[nd.p12_a];
+    Node& nd = net->nodes[i]; Node& na = net->nodes[nd.blk.b0];
     const Tensor& x = T[na.a];
     st.kind = S_P12;
-    st.variant = nd.p12_s2 ? V_OPENER : V_P12;
+    st.variant = nd.blk.s2 ? V_OPENER : V_P12;
     if (const int rc = conv_input_i8(net, na, &st.src_t, &st.src_f)) return rc;
     pack_conv_weights(net, na);
     pack_conv_weights(net, nd);
@@ -1782,7 +1775,7 @@ static int emit_p12(f8_net* net, int i, Step& st, std::vector<int>* extra) {
     st.valu_per_img = 3.0 * (px * na.cd.cout + pxo * o.Cs * out_forms8(st));
     st.bytes_per_img = px * x.Cs + out_bytes(st, o, pxo);
     st.bytes_const = weight_bytes(net, na) + weight_bytes(net, nd);
-    st.name = std::string(st.variant == V_OPENER ? "fused_opener_s2_p12_R" + std::to_string(nd.fb_R) + ":" : "fused_p12:") + tname(net, na.out) + "+" + tname(net, nd.out);
+    st.name = std::string(st.variant == V_OPENER ? "fused_opener_s2_p12_R" + std::to_string(nd.blk.R) + ":" : "fused_p12:") + tname(net, na.out) + "+" + tname(net, nd.out);
     return F8_OK;
 }
 
@@ -1790,8 +1783,8 @@ static int emit_p12(f8_net* net, int i, Step& st, std::vector<int>* extra) {
 static int emit_irchain(f8_net* net, int i, Step& st, std::vector<int>* extra) {
     auto& T = net->tensors; auto& ND = net->nodes;
     const Node& nd = ND[i];
-    const std::vector<int>& ch = nd.irchain;
-    const Node& fa = ND[block_convs(net, ch[0]).b0];
+    const std::vector<int>& ch = nd.chain;
+    const Node& fa = ND[ND[ch[0]].blk.b0];
     const Tensor& x = T[fa.a];
     st.kind = S_IRCHAIN;
     if (const int rc = conv_input_i8(net, fa, &st.src_t, &st.src_f)) return rc;
@@ -1801,7 +1794,7 @@ static int emit_irchain(f8_net* net, int i, Step& st, std::vector<int>* extra) {
     std::string blocks;
     for (size_t k = 0; k < ch.size(); ++k) {
         const Node& c = ND[ch[k]];
-        const BlockConvs r = block_convs(net, ch[k]);
+        const Block& r = c.blk;
         pack_block(net, r, false, st);
         const int bo = c.fused_add >= 0 ? ND[c.fused_add].out : c.out;
         valu += 3.0 * px * (ND[r.b0].cd.cout + ND[r.b2].cd.cout) + (c.fused_add >= 0 ? 2.0 * px * T[bo].C : 0.0) + (k + 1 < ch.size() ? 3.0 * px * T[bo].Cs : 0.0);
@@ -1822,7 +1815,7 @@ static int emit_irchain(f8_net* net, int i, Step& st, std::vector<int>* extra) {
 static int emit_ir(f8_net* net, int i, Step& st, std::vector<int>* extra) {
     auto& T = net->tensors; auto& ND = net->nodes;
     const Node& nd = ND[i];
-    const BlockConvs r = block_convs(net, i);
+    const Block& r = nd.blk;
     const Node& na = ND[r.b0]; const Node& nb = ND[r.b2];
     const Tensor& x = T[na.a];
     st.kind = S_IR;
@@ -1840,7 +1833,7 @@ static int emit_ir(f8_net* net, int i, Step& st, std::vector<int>* extra) {
     st.valu_per_img = 3.0 * (px * na.cd.cout + pxo * nb.cd.cout) + (st.res_t >= 0 ? 2.0 * pxo * o.C : 0.0) + 3.0 * pxo * o.Cs * out_forms8(st);
     st.bytes_per_img = px * x.Cs + (st.res_t >= 0 ? px * x.Cs * 4 : 0) + out_bytes(st, o, pxo);
     char kb[200];
-    snprintf(kb, sizeof kb, "fused_ir_s%d_%s:", nb.cd.stride, nd.ir_G > 1 ? ("G" + std::to_string(nd.ir_G)).c_str() : ("R" + std::to_string(nd.ir_R)).c_str());
+    snprintf(kb, sizeof kb, "fused_ir_s%d_%s:", nb.cd.stride, r.G > 1 ? ("G" + std::to_string(r.G)).c_str() : ("R" + std::to_string(r.R)).c_str());
     st.name = kb + block_names(net, r);
     return F8_OK;
 }
@@ -1938,19 +1931,19 @@ static int emit_conv(f8_net* net, int i, int max_batch, Step& st, std::vector<in
     return F8_OK;
 }
 
-// the launch of conv node i: the families are tried in this order, which decides between marks that hold at once (chain_into with fb_a, ...)
+// the launch of conv node i: the chain whose last block it hosts, else the block it hosts, else a conv of its own
 static int emit_conv_family(f8_net* net, int i, int max_batch, Step& st, std::vector<int>* extra) {
+    static int (*const emit_chain_kind[])(f8_net*, int, Step&, std::vector<int>*) = {nullptr, emit_chain, emit_bchain, emit_bcchain, emit_irchain};   // by ChainKind
     const Node& nd = net->nodes[i];
-    if (nd.h2_head >= 0) return emit_head2(net, i, st, extra);
-    if (nd.sp_pool >= 0 && nd.stem) return emit_stem_pool(net, i, st, extra);
-    if (nd.bchain_into == i) return nd.bcc ? emit_bcchain(net, i, st, extra) : emit_bchain(net, i, st, extra);
-    if (nd.chain_into == i) return emit_chain(net, i, st, extra);
-    if (nd.fbd_a >= 0) return emit_fused(net, i, st, extra);
-    if (nd.p12_a >= 0) return emit_p12(net, i, st, extra);
-    if (nd.irc_into == i) return emit_irchain(net, i, st, extra);
-    if (nd.ir_a >= 0) return emit_ir(net, i, st, extra);
-    if (nd.fb_a >= 0) return emit_fused(net, i, st, extra);
-    return emit_conv(net, i, max_batch, st, extra);
+    if (nd.sp_pool >= 0 && nd.stem) return emit_stem_pool(net, i, st, extra);      // (the ResNet head: a pairwise link, no block)
+    if (nd.chain_into == i) return emit_chain_kind[nd.chain_kind](net, i, st, extra);
+    switch (nd.blk.kind) {
+        case B_HEAD2: return emit_head2(net, i, st, extra);
+        case B_BOTTLENECK: case B_OPENING: return emit_fused(net, i, st, extra);
+        case B_P12: return emit_p12(net, i, st, extra);
+        case B_IR: return emit_ir(net, i, st, extra);
+        default: return emit_conv(net, i, max_batch, st, extra);
+    }
 }
 
 static int emit_add(f8_net* net, int i, Step& st, std::vector<int>* extra) {
@@ -2044,8 +2037,6 @@ static int emit_steps(f8_net* net, int max_batch) {
         if (nd.kind == N_ADD && nd.fused_into >= 0) continue;
         if (nd.kind == N_CONV && (nd.absorbed_by >= 0 || nd.dual_host >= 0)) continue;
         if (nd.kind == N_CONV && nd.chain_into >= 0 && nd.chain_into != i) continue;      // runs inside the chain launch of a later block
-        if (nd.kind == N_CONV && nd.bchain_into >= 0 && nd.bchain_into != i) continue;
-        if (nd.kind == N_CONV && nd.irc_into >= 0 && nd.irc_into != i) continue;       // runs inside the inverted-residual chain launch of a later block
         if (nd.kind == N_MAXPOOL && nd.sp_conv >= 0) continue;
         if (nd.kind == N_AVGPOOL && nd.pool_host >= 0) continue;     // runs in its conv's launch
         Step st; st.node = i;
@@ -2267,7 +2258,7 @@ static int bind_step(f8_net* net, Step& st) {
         }
         case S_HEAD2: case S_STEMPOOL: {
             const bool h2 = st.kind == S_HEAD2;
-            Node& hc = h2 ? ND[nd.h2_head] : nd;          // the head conv
+            Node& hc = h2 ? ND[nd.blk.b0] : nd;           // the head conv
             const Tensor& sT = T[st.src_t]; const Form& sF = sT.forms[st.src_f];
             StemPoolArgs a{};
             a.w = W8(hc.w_off); a.w_bytes = (uint32_t)((size_t)hc.coutP * hc.ktot);
@@ -2275,7 +2266,7 @@ static int bind_step(f8_net* net, Step& st) {
             a.Hp = sF.Hp; a.Wp = sF.Wp; a.org = sF.pad - hc.cd.pad;
             a.raw_kind = -1;
             if (h2) {
-                Node& hb = ND[nd.h2_dw];
+                Node& hb = ND[nd.blk.b2];
                 const Tensor& oT = T[nd.out];
                 a.h2 = 1;
                 a.wd = W8(hb.w_off); a.bd = B32(hb.cc_off);
@@ -2297,7 +2288,7 @@ static int bind_step(f8_net* net, Step& st) {
             out_formats(a.q); st.args = a; break;
         }
         case S_FUSED: {
-            const BlockConvs r = block_convs(net, st.node);
+            const Block& r = nd.blk;
             const bool ds = r.sc >= 0, opener = st.variant == V_OPENER;     // stage-opening block: nd = shortcut conv, nd.dual = body.4
             const Node& na = ND[r.b0]; const Node& nb = ND[r.b2]; const Node& ng = ND[r.b4];
             const Tensor& x = T[st.src_t];
@@ -2310,8 +2301,8 @@ static int bind_step(f8_net* net, Step& st) {
                 a.wsc = W8(nd.w_off); a.wsc_bytes = (uint32_t)((size_t)nd.coutP * nd.ktot); a.bsc = B32(nd.b_off);
                 a.COUT = nd.cd.cout; a.stride2 = opener ? 1 : 0;
             }
-            a.H = x.H; a.W = x.W; a.C = na.cd.cin; a.MID = na.cd.cout; a.R = nd.fb_R;
-            a.tiles_per_img = opener ? (x.H / 2) / nd.fb_R : (x.H + nd.fb_R - 1) / nd.fb_R;
+            a.H = x.H; a.W = x.W; a.C = na.cd.cin; a.MID = na.cd.cout; a.R = r.R;
+            a.tiles_per_img = opener ? (x.H / 2) / r.R : (x.H + r.R - 1) / r.R;
             fmt(nb, &a.n1, &a.lo1, &a.hi1, &a.xor1);
             fmt(ng, &a.n2, &a.lo2, &a.hi2, &a.xor2);
             a.relu_a = na.cd.relu; a.relu_b = nb.cd.relu;
@@ -2322,7 +2313,7 @@ static int bind_step(f8_net* net, Step& st) {
             st.args = a; break;
         }
         case S_P12: {
-            Node& na = ND[nd.p12_a];
+            Node& na = ND[nd.blk.b0];
             const Tensor& x = T[st.src_t];
             FusedArgs a{};
             const bool opener = st.variant == V_OPENER;
@@ -2335,8 +2326,8 @@ static int bind_step(f8_net* net, Step& st) {
             a.relu_a = na.cd.relu; a.relu_b = nd.cd.relu;
             out_formats(a.q);
             if (opener) {                                 // body.0 + body.2 of a stride-2 opening block on f8_opener.hip (P12); q[0] = mid2
-                a.COUT = 4 * na.cd.cout; a.R = nd.fb_R;
-                a.tiles_per_img = (x.H / 2 + nd.fb_R - 1) / nd.fb_R;
+                a.COUT = 4 * na.cd.cout; a.R = nd.blk.R;
+                a.tiles_per_img = (x.H / 2 + a.R - 1) / a.R;
                 a.n2 = a.q[0].n; a.lo2 = a.q[0].lo; a.hi2 = a.q[0].hi; a.xor2 = a.q[0].bias_xor;      // mid2's one form = body.4's input format
                 a.stride2 = 1; a.p12only = 1; a.acc_ok = conv_acc_bounded(na) && conv_acc_bounded(nd); a.rq_int = rq_int;
                 fused_opener_kernel_name(kb, sizeof kb, a, st.inst = fused_opener_inst(a, opt.opener_stg));
@@ -2350,7 +2341,7 @@ static int bind_step(f8_net* net, Step& st) {
             unsigned shortcut_blocks = 0;
             for (int k = 0; k < a.nblk; ++k) {
                 const Node& hh = ND[ch[k]];
-                const BlockConvs r = block_convs(net, ch[k]);
+                const Block& r = ND[ch[k]].blk;
                 const Node& ng = ND[r.b4];
                 ChainBlk& B = a.blk[k];
                 B.w4 = W8(ng.wf_off); B.b4 = B32(ng.b_off);
@@ -2376,7 +2367,7 @@ static int bind_step(f8_net* net, Step& st) {
                 a.stream_ok = a.stream_ok && stream_bounded(net, ND[hh.fused_add].out);
             }
             const Node& hf = ND[ch[0]];
-            const BlockConvs r0 = block_convs(net, ch[0]);
+            const Block& r0 = ND[ch[0]].blk;
             const bool tail = r0.b0 < 0, ds = r0.sc >= 0;
             const Node& a0 = ND[tail ? r0.b4 : r0.b0];
             const Tensor& oT = T[ND[nd.fused_add].out];      // the stage's output map (st.out.t: the pooled tensor when the pool runs in the launch)
@@ -2395,12 +2386,12 @@ static int bind_step(f8_net* net, Step& st) {
             st.args = a; break;
         }
         case S_BCHAIN: if (st.cluster) {
-            const std::vector<int>& ch = nd.bchain;
+            const std::vector<int>& ch = nd.chain;
             BCChainArgs a{};
             a.nblk = (int)ch.size();
             for (int k = 0; k < a.nblk; ++k) {
                 const Node& hk = ND[ch[k]];
-                const BlockConvs r = block_convs(net, ch[k]);
+                const Block& r = ND[ch[k]].blk;
                 const Node& c2 = ND[r.b2];
                 BChainBlk& B = a.blk[k];
                 B.wb = W8(c2.wf_off); B.bb = B32(c2.b_off);
@@ -2427,13 +2418,13 @@ static int bind_step(f8_net* net, Step& st) {
             bcchain_kernel_name(kb, sizeof kb, st.inst);
             st.args = a; break;
         } else {
-            const std::vector<int>& ch = nd.bchain;
+            const std::vector<int>& ch = nd.chain;
             BChainArgs a{};
             a.nblk = (int)ch.size();
-            const bool ds = block_convs(net, ch[0]).sc >= 0;
+            const bool ds = ND[ch[0]].blk.sc >= 0;
             for (int k = 0; k < a.nblk; ++k) {
                 const Node& hk = ND[ch[k]];
-                const BlockConvs r = block_convs(net, ch[k]);
+                const Block& r = ND[ch[k]].blk;
                 const bool hds = r.sc >= 0;                     // opening block: hk = its shortcut conv
                 Node& c1 = ND[r.b0]; const Node& c2 = ND[r.b2];
                 BChainBlk& B = a.blk[k];
@@ -2458,7 +2449,7 @@ static int bind_step(f8_net* net, Step& st) {
             st.args = a; break;
         }
         case S_IR: {
-            const BlockConvs r = block_convs(net, st.node);
+            const Block& r = nd.blk;
             Node& na = ND[r.b0]; Node& nb = ND[r.b2];
             const Tensor& x = T[st.src_t];
             const Tensor& oT = T[nd.out];
@@ -2466,8 +2457,8 @@ static int bind_step(f8_net* net, Step& st) {
             a.w0 = W8(na.w_off); a.b0 = B32(na.b_off);
             a.wd4 = W8(nb.rc_off); a.bd4 = B32(nb.cc_off);
             a.w4 = W8(nd.w_off); a.b4 = B32(nd.b_off);
-            a.H = x.H; a.W = x.W; a.Ho = oT.H; a.Wo = oT.W; a.stride = nb.cd.stride; a.R = nd.ir_R; a.G = nd.ir_G;
-            a.tiles_per_img = oT.H / nd.ir_R; a.E32 = na.coutP;
+            a.H = x.H; a.W = x.W; a.Ho = oT.H; a.Wo = oT.W; a.stride = nb.cd.stride; a.R = r.R; a.G = r.G;
+            a.tiles_per_img = oT.H / r.R; a.E32 = na.coutP;
             fmt(nb, &a.n1, &a.lo1, &a.hi1, &a.xor1);
             fmt(nd, &a.n2, &a.lo2, &a.hi2, &a.xor2);
             a.relu_a = na.cd.relu; a.relu_b = nb.cd.relu; a.relu0 = st.relu0;
@@ -2476,18 +2467,18 @@ static int bind_step(f8_net* net, Step& st) {
             make_magic((uint32_t)x.W, &a.mW, &a.s1W, &a.s2W);
             make_magic((uint32_t)(x.H * x.W), &a.mHW, &a.s1HW, &a.s2HW);
             make_magic((uint32_t)oT.W, &a.mWo, &a.s1Wo, &a.s2Wo);
-            make_magic((uint32_t)(nd.ir_R * oT.W), &a.mRWo, &a.s1RWo, &a.s2RWo);
+            make_magic((uint32_t)(r.R * oT.W), &a.mRWo, &a.s1RWo, &a.s2RWo);
             fused_ir_kernel_name(kb, sizeof kb, x.Cs, nd.coutP, st.inst = fused_ir_inst(a, nd.coutP));
             out_formats(a.q); st.args = a; break;
         }
         case S_IRCHAIN: {
-            const std::vector<int>& ch = nd.irchain;
+            const std::vector<int>& ch = nd.chain;
             const Tensor& x = T[st.src_t];
             IRChainArgs a{};
             a.nblk = (int)ch.size();
             a.acc_ok = 1; a.rq_int = rq_int;
             for (int k = 0; k < a.nblk; ++k) {
-                const BlockConvs r = block_convs(net, ch[k]);
+                const Block& r = ND[ch[k]].blk;
                 const Node& c = ND[ch[k]]; Node& na = ND[r.b0]; Node& nb = ND[r.b2];
                 IRChainBlk& B = a.blk[k];
                 B.w0 = W8(na.w_off); B.b0 = B32(na.b_off);
@@ -2502,7 +2493,7 @@ static int bind_step(f8_net* net, Step& st) {
                     join_shifts(T[c.out].fl - T[na.a].fl, &B.acc_shl, &B.res_shl);
                 }
                 if (k + 1 < a.nblk) {
-                    fmt(ND[block_convs(net, ch[k + 1]).b0], &B.nq, &B.loq, &B.hiq, &B.xorq);
+                    fmt(ND[ND[ch[k + 1]].blk.b0], &B.nq, &B.loq, &B.hiq, &B.xorq);
                     B.keep = ND[ch[k + 1]].fused_add >= 0;
                 }
                 a.acc_ok = a.acc_ok && conv_acc_bounded(na) && conv_acc_bounded(nb);
@@ -2577,6 +2568,7 @@ int f8_net_finalize(f8_net* net, int max_batch) {
     plan_inverted_residual_chains(net);             // 1e2: runs of stride-1 inverted residuals in one launch (option fuse_irchain)
     plan_mobilenet_v2_head(net);                    // 1h: MobileNet-V2 head conv + depthwise + 1x1
     plan_last_conv_and_pool(net);                   // 1i: the last 1x1 conv + the average pool
+    if (net->plan_bug >= 0) return fail(F8_ERR_STATE, "f8_net_finalize: planner bug: two fused launches claim conv node %d", net->plan_bug);
     plan_tensor_forms(net);                         // 2:  which forms of each tensor exist in HBM
     int rc = emit_steps(net, max_batch);            // 3:  the launches, packed weights, algorithmic bytes / ops
     if (rc) return rc;
@@ -3012,7 +3004,7 @@ static int step_chunk(const f8_net* net, int i) {        // nominal images per c
     const Step& st = net->steps[i];
     if (st.kind != S_FUSED) return 0;                    // (chunking the stage-opening convs as well: -3 %, more launches than locality)
     const Node& nd = net->nodes[st.node];
-    const BlockConvs r = block_convs(net, st.node);
+    const Block& r = nd.blk;
     const bool opener = st.variant == V_OPENER;
     const Options& o = net->opt;
     if (r.sc >= 0 && !(opener ? o.chunk_opener : o.chunk_ds)) return 0;
@@ -3025,7 +3017,7 @@ static int step_chunk(const f8_net* net, int i) {        // nominal images per c
         if (st.out.t >= 0) { const Tensor& y = net->tensors[st.out.t]; per_img = std::max(per_img, (size_t)y.H * y.W * y.Cs * 4); }
         const int cache = (int)std::min<size_t>(((size_t)o.chunk_budget_mb << 20) / std::max<size_t>(per_img, 1), 1 << 20) / gran * gran;
         const int mid = net->nodes[r.b0].cd.cout;
-        const int tiles = std::max(1, (opener ? x.H / 2 : x.H) / std::max(1, nd.fb_R));        // workgroups per image
+        const int tiles = std::max(1, (opener ? x.H / 2 : x.H) / std::max(1, r.R));        // workgroups per image
         const int slots = (net->num_cu > 0 ? net->num_cu : 256) * ((opener || mid > 128) ? 1 : 2);
         const int fill = ((slots * 85 / 100 + tiles - 1) / tiles + gran - 1) / gran * gran;
         chunk = std::max(cache, fill);
