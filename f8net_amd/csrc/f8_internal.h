@@ -38,6 +38,7 @@ struct Options {
     int fuse_head2 = 1;          // MobileNet-V2 head (3x3 / 2 conv, depthwise 3x3, 1x1) as one row-walking launch (f8_stem.hip, H2)
     int fuse_ir = 1;             // MobileNet-V2 inverted residual (expand -> depthwise -> project) in one launch: 1 = where it wins, 2 = always
     int fuse_irchain = 0;        // runs of >= 2 consecutive stride-1 inverted residuals on a small map in ONE launch, one workgroup per image (f8_irchain.hip)
+    int fuse_dws = 0;            // MobileNet-V1 depthwise-separable block (depthwise 3x3 -> 1x1) in ONE launch, the depthwise result only in LDS (f8_dws.hip)
     int patch3x3 = 1;            // LDS-patch 3x3 kernel
     int dual_wide = 2048;        // dual-GEMM joins with at least this many couts use the 128x128 tile
     int deep_nk = 7;             // K loops of at least this many steps use the deepest DMA ring
@@ -325,6 +326,20 @@ struct IRChainArgs {
     int32_t xp, off_strm, off_patch, off_mid2, off_w;   // LDS layout (filled by launch_irchain)
 };
 
+// One launch for a depthwise-separable block: depthwise 3x3 / s, pad 1, ReLU -> 1x1 [ReLU] (f8_dws.hip); int8 outputs only.
+struct DwsArgs {
+    const int8_t* x;                       // block input, int8 NHWC [N][H][W][Cin] in the depthwise conv's input format
+    const int8_t* wd; const int32_t* bd;   // depthwise: [9][Cin] tap-major, bias (+ 128 * sum(w) for unsigned inputs) [Cin]
+    const int8_t* w1; const int32_t* b1;   // 1x1: fragment-order image (pack_frag_weights) [Cout][Cin], offset-corrected bias [Cout]
+    int32_t N, H, W, P, Q, Cin, Cout, stride;   // H, W: input map; P, Q: output map; channel counts padded to 32
+    int32_t R, tiles_per_img, px32;        // output rows per tile (dws_supported); tiles per image and the tile's padded pixel count (launch_dws)
+    int32_t in_signed;                     // the depthwise conv reads a signed format (zero padding = 0, else the biased zero)
+    int32_t n1, lo1, hi1; uint32_t xor1;   // requant depthwise output (behind its ReLU) -> the 1x1's input format
+    int32_t relu0;                         // ReLU after the 1x1
+    QuantOut q[2];
+    int32_t acc_ok, rq_int;                // both convs' accumulators bounded (conv_acc_bounded) / Options::requant_float == 0 (see DwArgs)
+};
+
 // ResNet head in one launch: 7x7/2 conv + ReLU + requant (unsigned 8-bit) + 3x3/2 max-pool (f8_stem.hip).
 struct StemPoolArgs {
     int32_t acc_ok;                        // conv accumulators bounded (see DwArgs::acc_ok)
@@ -450,6 +465,11 @@ bool irchain_supported(int H, int W, int cin_max, int cout_max, int keep_max);
 int irchain_inst(const IRChainArgs& a);                            // FQ (as fused_ir_inst) | register shape << 2
 int irchain_kernel_name(char* buf, size_t cap, int inst);
 hipError_t launch_irchain(const IRChainArgs& a, int inst, hipStream_t s);
+// depthwise-separable block in one launch (f8_dws.hip): padded channel counts, the block INPUT map, the largest N a launch may cover; *R = output rows per tile
+bool dws_supported(int cinS, int coutS, int H, int W, int stride, int imgs, int* R);
+int dws_inst(const DwsArgs& a, int nq);                            // FQ (0 any format, 1 float converter, 2 integer) | the walker's sub-rows << 2
+int dws_kernel_name(char* buf, size_t cap, const DwsArgs& a, int inst);
+hipError_t launch_dws(const DwsArgs& a, int inst, hipStream_t s);
 // 3x3 / stride 1 / pad 1 with the input patch resident in LDS (f8_conv3x3.hip); config = false: no instance
 bool conv3x3_patch_config(int cin, int H, int W, int coutP, int* R, int* IMGS, int* BN);
 hipError_t launch_conv3x3_patch(const ConvArgs& a, int cin, hipStream_t s);
