@@ -39,6 +39,7 @@ struct Options {
     int fuse_ir = 1;             // MobileNet-V2 inverted residual (expand -> depthwise -> project) in one launch: 1 = where it wins, 2 = always
     int fuse_irchain = 0;        // runs of >= 2 consecutive stride-1 inverted residuals on a small map in ONE launch, one workgroup per image (f8_irchain.hip)
     int fuse_dws = 0;            // MobileNet-V1 depthwise-separable block (depthwise 3x3 -> 1x1) in ONE launch, the depthwise result only in LDS (f8_dws.hip)
+    int fuse_dws7 = 0;           // ... the same for blocks whose OUTPUT map is 7 x 7, the average pool behind the last one summed in the launch (f8_dws7.hip)
     int patch3x3 = 1;            // LDS-patch 3x3 kernel
     int dual_wide = 2048;        // dual-GEMM joins with at least this many couts use the 128x128 tile
     int deep_nk = 7;             // K loops of at least this many steps use the deepest DMA ring
@@ -340,6 +341,23 @@ struct DwsArgs {
     int32_t acc_ok, rq_int;                // both convs' accumulators bounded (conv_acc_bounded) / Options::requant_float == 0 (see DwArgs)
 };
 
+// One launch for a depthwise-separable block whose OUTPUT map is 7 x 7 (f8_dws7.hip): as DwsArgs, the depthwise conv on v_dot4, I images per
+// workgroup, and optionally only the average pool of the block output written.
+struct Dws7Args {
+    const int8_t* x;                       // block input, int8 NHWC [N][H][W][Cin] in the depthwise conv's input format
+    const int8_t* wd4; const int32_t* bd4; // depthwise: dot4 image [Cin/4][36 B], bias (+ 128 * sum(w) for unsigned inputs) [Cin]
+    const int8_t* w1; const int32_t* b1;   // 1x1: fragment-order image (pack_frag_weights) [Cout][Cin], offset-corrected bias [Cout]
+    int32_t N, H, W, Cin, Cout, stride;    // H, W: input map (7 * stride); channel counts padded to 32
+    int32_t I, Z, px32;                    // images per workgroup (dws7_supported); slices of the output tiles and the mid tile's padded pixel count (launch_dws7)
+    int32_t in_signed;                     // the depthwise conv reads a signed format (zero padding = 0, else the biased zero)
+    int32_t n1, lo1, hi1; uint32_t xor1;   // requant depthwise output (behind its ReLU) -> the 1x1's input format
+    int32_t relu0;                         // ReLU after the 1x1
+    int32_t pool;                          // the outputs are the forms of the block output SUMMED over its 49 pixels: out32 (I32T, one pixel per image), q (int8 [N][Cout])
+    int32_t* out32;
+    QuantOut q[2];
+    int32_t acc_ok, rq_int;                // both convs' accumulators bounded (conv_acc_bounded) / Options::requant_float == 0 (see DwArgs)
+};
+
 // ResNet head in one launch: 7x7/2 conv + ReLU + requant (unsigned 8-bit) + 3x3/2 max-pool (f8_stem.hip).
 struct StemPoolArgs {
     int32_t acc_ok;                        // conv accumulators bounded (see DwArgs::acc_ok)
@@ -470,6 +488,12 @@ bool dws_supported(int cinS, int coutS, int H, int W, int stride, int imgs, int*
 int dws_inst(const DwsArgs& a, int nq);                            // FQ (0 any format, 1 float converter, 2 integer) | the walker's sub-rows << 2
 int dws_kernel_name(char* buf, size_t cap, const DwsArgs& a, int inst);
 hipError_t launch_dws(const DwsArgs& a, int inst, hipStream_t s);
+// ... whose output map is 7 x 7 (f8_dws7.hip): pool = the launch writes only the average pool of the block output; *I = images per workgroup
+bool dws7_supported(int cinS, int coutS, int H, int W, int stride, int imgs, bool pool, int* I);
+int dws7_slices(int groups, int nco, int cus);                     // Z: in how many slices the output tiles go over workgroups
+int dws7_inst(const Dws7Args& a, int nq);                          // FQ (0 any format, 1 float converter, 2 integer)
+int dws7_kernel_name(char* buf, size_t cap, const Dws7Args& a, int inst);
+hipError_t launch_dws7(const Dws7Args& a, int inst, int num_cu, hipStream_t s);
 // 3x3 / stride 1 / pad 1 with the input patch resident in LDS (f8_conv3x3.hip); config = false: no instance
 bool conv3x3_patch_config(int cin, int H, int W, int coutP, int* R, int* IMGS, int* BN);
 hipError_t launch_conv3x3_patch(const ConvArgs& a, int cin, hipStream_t s);

@@ -79,9 +79,10 @@ struct Tensor {
 //   B_BASIC_JOIN    its join alone (the cluster launch; its 3x3 / 2 runs on its own): second 3x3, host = shortcut
 //   B_IR            inverted residual: expand, depthwise, host = project (alone: f8_ir.hip, tile R x G; in a chain launch: f8_irchain.hip)
 //   B_HEAD2         MobileNet-V2 head launch (f8_stem.hip, H2): 3x3 / 2 head conv, depthwise, host = the 1x1
-//   B_DWS           depthwise-separable block (option fuse_dws, f8_dws.hip; R rows per tile): body.0 = the depthwise 3x3, host = the 1x1
+//   B_DWS           depthwise-separable block (option fuse_dws, f8_dws.hip; R rows per tile): body.0 = the depthwise 3x3, host = the 1x1;
+//                   I7 > 0: the form for a 7 x 7 output map (option fuse_dws7, f8_dws7.hip; I7 images per workgroup), the same block to every pass
 enum BlockKind { B_NONE, B_BOTTLENECK, B_OPENING, B_JOIN, B_P12, B_BASIC, B_BASIC_OPENING, B_BASIC_JOIN, B_IR, B_HEAD2, B_DWS };
-struct Block { BlockKind kind = B_NONE; int b0 = -1, b2 = -1, b4 = -1, sc = -1; bool s2 = false; int R = 0, G = 0; };
+struct Block { BlockKind kind = B_NONE; int b0 = -1, b2 = -1, b4 = -1, sc = -1; bool s2 = false; int R = 0, G = 0, I7 = 0; };
 enum Role { R_NONE, R_B0, R_B2, R_B4, R_SC };
 // The chain launches: bottleneck stage (f8_chain.hip; the 7x7 stage over clusters, f8_cchain.hip), BasicBlocks (f8_bchain.hip), BasicBlocks of a 7x7 x 512
 // stage over clusters of eight workgroups (option fuse_bchain7, f8_bcchain.hip), inverted residuals (f8_irchain.hip).  Independent of the block kind.
@@ -116,7 +117,7 @@ struct Node {
     size_t rc_off = 0, cc_off = 0; int ncc = 0;      // border-class tables (0 = single class)
     ConvTile tile{};
 };
-enum StepKind { S_INPUT, S_CONV, S_DW, S_ADD, S_MAXPOOL, S_AVGPOOL, S_REQUANT, S_OUTPUT, S_FUSED, S_STEMPOOL, S_IR, S_P12, S_CHAIN, S_BCHAIN, S_HEAD2, S_IRCHAIN, S_DWS };
+enum StepKind { S_INPUT, S_CONV, S_DW, S_ADD, S_MAXPOOL, S_AVGPOOL, S_REQUANT, S_OUTPUT, S_FUSED, S_STEMPOOL, S_IR, S_P12, S_CHAIN, S_BCHAIN, S_HEAD2, S_IRCHAIN, S_DWS, S_DWS7 };
 // The kernel of a step whose kind has several, chosen once by the step's emitter (pass 3); bind_step, run_step and f8_net_autotune switch on it.
 //   S_CONV:  conv_igemm (f8_kernels.hip), the LDS-patch 3x3 (f8_conv3x3.hip), conv1x1_wreg (f8_wreg.hip), conv1x1_wstat (f8_wstat.hip),
 //            conv3x3s2_wreg (f8_s2conv.hip), the 1x1 conv + average pool (f8_pool.hip), the classifier fc_dense (f8_fc.hip)
@@ -138,7 +139,7 @@ struct Step {
     double bytes_per_img = 0, bytes_const = 0, ops_per_img = 0;
     double valu_per_img = 0;           // ESSENTIAL vector lane-operations per image (f8_net_launch_valu): what the reference's semantics need once the MFMAs are done
     // the launcher's arguments as far as the plan decides them (bind_step); run_step copies them and adds what the run decides
-    std::variant<std::monostate, ConvArgs, StemPoolArgs, FusedArgs, ChainArgs, BChainArgs, BCChainArgs, IRArgs, IRChainArgs, DwsArgs, DwArgs, AddArgs, PoolArgs, AvgArgs, OutArgs> args;
+    std::variant<std::monostate, ConvArgs, StemPoolArgs, FusedArgs, ChainArgs, BChainArgs, BCChainArgs, IRArgs, IRChainArgs, DwsArgs, Dws7Args, DwArgs, AddArgs, PoolArgs, AvgArgs, OutArgs> args;
     int inst = 0;                      // the instance the launcher starts (the family's *_inst, f8_internal.h; bind_step)
     // S_CHAIN / S_BCHAIN: geometry, workgroups per image and resident per CU, the 7x7 cluster form (f8_cchain.hip)
     int C = 0, MID = 0, H = 0, W = 0, cin0 = 0, tiles = 0, wg_per_cu = 1; bool cluster = false;
@@ -311,6 +312,7 @@ static const OptKey kOptKeys[] = {
     {"fuse_ir", "F8_FUSE_IR", &Options::fuse_ir, 0, 2, true},
     {"fuse_irchain", "F8_FUSE_IRCHAIN", &Options::fuse_irchain, 0, 1, true},
     {"fuse_dws", "F8_FUSE_DWS", &Options::fuse_dws, 0, 1, true},
+    {"fuse_dws7", "F8_FUSE_DWS7", &Options::fuse_dws7, 0, 1, true},
     {"fuse_head2", "F8_FUSE_HEAD2", &Options::fuse_head2, 0, 1, true},
     {"fuse_p12", "F8_FUSE_P12", &Options::fuse_p12, 0, 1, true},
     {"fuse_chain", "F8_FUSE_CHAIN", &Options::fuse_chain, 0, 1, true},
@@ -1472,9 +1474,60 @@ static void plan_depthwise_separable(f8_net* net, int max_batch) {
         }
         if (!int8_readers || fmts.size() > 2) continue;
         int R = 0;
-        if (!dws_supported(x.Cs, round_up(c.cd.cout, 32), x.H, x.W, b.cd.stride, max_batch, &R)) continue;      // (7-wide maps: no matrix-core walker form)
+        if (!dws_supported(x.Cs, round_up(c.cd.cout, 32), x.H, x.W, b.cd.stride, max_batch, &R)) continue;      // (7-wide maps: no matrix-core walker form; pass 1k)
         if (tb.H * b.cd.stride != x.H || tb.W * b.cd.stride != x.W) continue;
         set_block(net, i, Block{B_DWS, bi, -1, i, -1, false, R});
+    }
+}
+
+// pass 1k
+static void plan_depthwise_separable_7x7(f8_net* net, int max_batch) {
+    auto& T = net->tensors;
+    auto& ND = net->nodes;
+    const int nn = (int)ND.size();
+    // ---- 1k. the same block on a 7 x 7 OUTPUT map (option fuse_dws7; f8_dws7.hip), which 1j's launch has no form for: 1j's conditions, and in addition
+    //          a block output whose only reader is the average pool, itself not the net output — the pool is then summed in the launch (pool / pool_host, as 1i)
+    //          and the block output exists in no form.  After 1j, so the last of the passes 1x: whatever an earlier one claimed stays claimed.
+    for (int i = 0; net->opt.fuse_dws7 && i < nn; ++i) {
+        Node& c = ND[i];
+        if (c.kind != N_CONV || c.cd.groups != 1 || c.cd.kernel != 1 || c.cd.stride != 1 || c.cd.pad != 0 || !c.cd.quant_input ||
+            c.fused_add >= 0 || c.dual >= 0 || c.pool >= 0 || claimed(net, i)) continue;
+        const Tensor& tb = T[c.a];
+        if (tb.prod < 0 || tb.consumers.size() != 1 || c.a == net->out_t) continue;
+        const int bi = tb.prod;
+        const Node& b = ND[bi];
+        if (b.kind != N_CONV || b.cd.groups == 1 || b.cd.groups != b.cd.cin || b.cd.cout != b.cd.cin || b.cd.kernel != 3 || b.cd.pad != 1 ||
+            (b.cd.stride != 1 && b.cd.stride != 2) || !b.cd.relu || !b.cd.quant_input || b.fused_add >= 0 || claimed(net, bi)) continue;
+        const Tensor& x = T[b.a];
+        if (x.prod < 0 || ND[x.prod].kind == N_INPUT || (b.cd.cin & 31)) continue;      // (the network input has its own layouts)
+        if (c.out == net->out_t || T[c.out].consumers.empty()) continue;                 // the net output is int32
+        // an inverted residual — expanding 1x1 (ReLU) -> depthwise -> 1x1 WITHOUT ReLU — is passes 1e / 1e2's to decide: the 7x7 ones that fuse_ir = 1
+        // leaves as three launches were measured there (1j never sees them: it has no 7-wide form)
+        const Node& xp = ND[x.prod];
+        if (!c.cd.relu && xp.kind == N_CONV && xp.cd.groups == 1 && xp.cd.kernel == 1 && xp.cd.relu && xp.cd.cout > xp.cd.cin && x.consumers.size() == 1) continue;
+        int pool = -1;
+        if (T[c.out].consumers.size() == 1 && ND[T[c.out].consumers[0]].kind == N_AVGPOOL) {
+            const int pi = T[c.out].consumers[0];
+            if (ND[pi].pool_host >= 0 || ND[pi].out == net->out_t) continue;             // (a pooled net output is int32 of the caller's: the pool stays a launch, and so does this conv's int32 result)
+            pool = pi;
+        }
+        bool int8_readers = true;
+        std::vector<std::pair<int, int>> fmts;
+        for (int u : T[c.out].consumers) {
+            if (pool >= 0) break;
+            const Node& un = ND[u];
+            int n = 0;
+            if ((un.kind != N_CONV && un.kind != N_LINEAR) || !un.cd.quant_input || consumer_format(T[c.out], un.cd, &n, "finalize") ||
+                (claimed(net, u) && !(un.absorbed_by >= 0 && ND[un.absorbed_by].blk.kind == B_DWS))) { int8_readers = false; break; }
+            const std::pair<int, int> f{n, un.cd.input_signed ? 1 : 0};
+            if (std::find(fmts.begin(), fmts.end(), f) == fmts.end()) fmts.push_back(f);
+        }
+        if (!int8_readers || fmts.size() > 2) continue;
+        int I = 0;
+        if (!dws7_supported(x.Cs, round_up(c.cd.cout, 32), x.H, x.W, b.cd.stride, max_batch, pool >= 0, &I)) continue;
+        if (tb.H * b.cd.stride != x.H || tb.W * b.cd.stride != x.W) continue;
+        set_block(net, i, Block{B_DWS, bi, -1, i, -1, false, 0, 0, I});
+        if (pool >= 0) { c.pool = pool; ND[pool].pool_host = i; }
     }
 }
 
@@ -1906,6 +1959,37 @@ static int emit_dws(f8_net* net, int i, Step& st, std::vector<int>* extra) {
     return F8_OK;
 }
 
+// ... on a 7 x 7 output map (1k), with the average pool behind it where the plan folds it in: the step's outputs are then the POOLED tensor's forms
+static int emit_dws7(f8_net* net, int i, Step& st, std::vector<int>* extra) {
+    auto& T = net->tensors; auto& ND = net->nodes;
+    Node& nd = ND[i];
+    const Block& r = nd.blk;
+    Node& nb = ND[r.b0];
+    const Tensor& x = T[nb.a];
+    st.kind = S_DWS7;
+    if (const int rc = conv_input_i8(net, nb, &st.src_t, &st.src_f)) return rc;
+    pack_dw_weights(net, nb);
+    pack_conv_weights(net, nd);
+    pack_frag_weights(net, nd);
+    st.relu0 = nd.cd.relu;
+    int out_t = nd.out;
+    if (nd.pool >= 0) {
+        out_t = ND[nd.pool].out;
+        if (T[out_t].forms.empty()) add_form(T[out_t], FORM_I32, 0, 0);
+    }
+    select_outputs(net, out_t, &st.out, extra);
+    if (nd.pool < 0 && (st.out.f32 >= 0 || st.out.f8[0] < 0)) return fail(F8_ERR_UNSUPPORTED, "finalize: the depthwise-separable launch writes int8 forms of the block output only");
+    const Tensor& o = T[out_t]; const Tensor& y = T[nd.out];
+    const double px = (double)x.H * x.W, pxo = (double)y.H * y.W, outpix = nd.pool >= 0 ? 1.0 : pxo;
+    st.ops_per_img = conv_ops(net, nb) + conv_ops(net, nd);
+    // the depthwise requantisation, one v_dot4 per four taps (a VALU depthwise conv, as emit_conv counts it), the pool's adds, the output forms
+    st.valu_per_img = 3.0 * pxo * nb.cd.cout + 9.0 * pxo * nb.cd.cout / 4.0 + (nd.pool >= 0 ? pxo * y.C : 0.0) + 3.0 * outpix * o.Cs * out_forms8(st);
+    st.bytes_per_img = px * x.Cs + out_bytes(st, o, outpix);
+    st.bytes_const = weight_bytes(net, nb) + weight_bytes(net, nd);
+    st.name = "fused_dws7:" + block_names(net, r) + (nd.pool >= 0 ? "+" + tname(net, out_t) : "");
+    return F8_OK;
+}
+
 // The kernel of a plain conv step (not depthwise), once its inputs and outputs are known; the first that applies, in this order.
 static Variant conv_variant(const f8_net* net, const Node& nd, const Step& st, int max_batch) {
     const Options& opt = net->opt;
@@ -2010,7 +2094,7 @@ static int emit_conv_family(f8_net* net, int i, int max_batch, Step& st, std::ve
         case B_BOTTLENECK: case B_OPENING: return emit_fused(net, i, st, extra);
         case B_P12: return emit_p12(net, i, st, extra);
         case B_IR: return emit_ir(net, i, st, extra);
-        case B_DWS: return emit_dws(net, i, st, extra);
+        case B_DWS: return nd.blk.I7 > 0 ? emit_dws7(net, i, st, extra) : emit_dws(net, i, st, extra);
         default: return emit_conv(net, i, max_batch, st, extra);
     }
 }
@@ -2590,6 +2674,22 @@ static int bind_step(f8_net* net, Step& st) {
             dws_kernel_name(kb, sizeof kb, a, st.inst = dws_inst(a, nq));
             st.args = a; break;
         }
+        case S_DWS7: {
+            Node& nb = ND[nd.blk.b0];
+            const Tensor& x = T[st.src_t];
+            Dws7Args a{};
+            a.wd4 = W8(nb.rc_off); a.bd4 = B32(nb.cc_off);        // the dot4 image; bias + 128 * sum(w) for unsigned inputs
+            a.w1 = W8(nd.wf_off); a.b1 = B32(nd.b_off);
+            a.H = x.H; a.W = x.W; a.Cin = x.Cs; a.Cout = nd.coutP; a.stride = nb.cd.stride; a.I = nd.blk.I7;
+            a.in_signed = nb.cd.input_signed;
+            fmt(nd, &a.n1, &a.lo1, &a.hi1, &a.xor1);
+            a.relu0 = st.relu0;
+            a.pool = nd.pool >= 0 ? 1 : 0;
+            a.acc_ok = conv_acc_bounded(nb) && conv_acc_bounded(nd); a.rq_int = rq_int;
+            out_formats(a.q);
+            dws7_kernel_name(kb, sizeof kb, a, st.inst = dws7_inst(a, nq));
+            st.args = a; break;
+        }
         case S_DW: {
             const Tensor& sT = T[st.src_t];
             const Tensor& oT = T[nd.out];
@@ -2654,6 +2754,7 @@ int f8_net_finalize(f8_net* net, int max_batch) {
     plan_mobilenet_v2_head(net);                    // 1h: MobileNet-V2 head conv + depthwise + 1x1
     plan_last_conv_and_pool(net);                   // 1i: the last 1x1 conv + the average pool
     plan_depthwise_separable(net, max_batch);       // 1j: MobileNet-V1 depthwise-separable blocks in one launch (option fuse_dws)
+    plan_depthwise_separable_7x7(net, max_batch);   // 1k: ... those on 7 x 7 output maps, and the average pool behind the last (option fuse_dws7)
     if (net->plan_bug >= 0) return fail(F8_ERR_STATE, "f8_net_finalize: planner bug: two fused launches claim conv node %d", net->plan_bug);
     plan_tensor_forms(net);                         // 2:  which forms of each tensor exist in HBM
     int rc = emit_steps(net, max_batch);            // 3:  the launches, packed weights, algorithmic bytes / ops
@@ -2963,6 +3064,13 @@ static int run_step(const f8_net* net, const Step& st, const int32_t* input, voi
             a.x = (const int8_t*)fp(T[st.src_t].forms[st.src_f]); a.N = N;
             { int32_t* none = nullptr; fill_out(&none, a.q); }
             e = launch_dws(a, st.inst, s);
+            break;
+        }
+        case S_DWS7: {
+            Dws7Args a = std::get<Dws7Args>(st.args);
+            a.x = (const int8_t*)fp(T[st.src_t].forms[st.src_f]); a.N = N;
+            fill_out(&a.out32, a.q);
+            e = launch_dws7(a, st.inst, net->num_cu, s);
             break;
         }
         case S_DW: {
