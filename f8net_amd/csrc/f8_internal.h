@@ -39,6 +39,7 @@ struct Options {
     int fuse_ir = 1;             // MobileNet-V2 inverted residual (expand -> depthwise -> project) in one launch: 1 = where it wins, 2 = always
     int fuse_irchain = 0;        // runs of >= 2 consecutive stride-1 inverted residuals on a small map in ONE launch, one workgroup per image (f8_irchain.hip)
     int fuse_dws = 0;            // MobileNet-V1 depthwise-separable block (depthwise 3x3 -> 1x1) in ONE launch, the depthwise result only in LDS (f8_dws.hip)
+    int fuse_head_dws = 0;       // MobileNet-V1 head + first depthwise-separable block (3x3 / 2 conv, depthwise 3x3, 1x1 to 32 / 64 channels [ReLU]) as one row-walking launch (f8_head_dws.hip)
     int fuse_dws7 = 0;           // ... the same for blocks whose OUTPUT map is 7 x 7, the average pool behind the last one summed in the launch (f8_dws7.hip)
     int patch3x3 = 1;            // LDS-patch 3x3 kernel
     int dual_wide = 2048;        // dual-GEMM joins with at least this many couts use the 128x128 tile
@@ -384,6 +385,9 @@ struct StemPoolArgs {
     uint32_t xor8;                         // 0x80808080 when the stem's input format is unsigned (stored biased)
     uint32_t* err; int32_t chk_lo, chk_hi; // raw_kind 0: values outside [chk_lo, chk_hi] set the sticky error word (err != nullptr)
     int16_t lut[3 * 256];
+    // h2 == 2: the MobileNet-V1 form of that head (f8_head_dws.hip, head_dws_kernel): the 1x1 has Cs = 32 or 64 output channels (w1 [Cs][32], b1 [Cs];
+    // Cs is also the channel stride of q[]) and carries a ReLU when relu1 is set
+    int32_t relu1, Cs;
 };
 
 // Dynamic LDS above 64 KB must be opted into per kernel AND per device (a process that drives several GPUs launches the same
@@ -502,9 +506,12 @@ bool head2_supported(int H, int W);
 int dwconv_mma_inst(const DwArgs& a, bool out32, int nq, int N);   // f8_dwmma.hip: FQ | sub-rows << 2, or -1 (no instance for N images)
 hipError_t launch_dwconv_mma(const DwArgs& a, int inst, hipStream_t s);
 bool stem_pool_supported(int cin, int cout, int k, int stride, int pad, int pool_k, int pool_s, int pool_p, int P, int Q, int rows, int H, int W);
-int stem_pool_inst(const StemPoolArgs& a, bool rows, bool raw);    // 0 tile kernel, 1 row-walking kernel, 2 MobileNet-V2 head; raw: the plan reads the raw input
+int stem_pool_inst(const StemPoolArgs& a, bool rows, bool raw);    // 0 tile kernel, 1 row-walking kernel, 2 MobileNet-V2 head, 3 MobileNet-V1 head + block (h2 == 2); raw: the plan reads the raw input
 const char* stem_pool_kernel_name(int inst);
 hipError_t launch_stem_pool(const StemPoolArgs& a, int inst, hipStream_t s);
+// instance 3 (f8_head_dws.hip): dispatched by launch_stem_pool
+const char* head_dws_kernel_name();
+hipError_t launch_head_dws(const StemPoolArgs& a, hipStream_t s);
 // mma / dot4: Options::dw_mma / dw_dot4; max_batch: the largest N a launch may cover (the MMA kernel's 32-bit index bound)
 int dwconv_inst(const DwArgs& a, bool out32, int nq, bool mma, bool dot4, int max_batch);
 int dwconv_kernel_name(char* buf, size_t cap, const DwArgs& a, int inst);

@@ -313,6 +313,7 @@ static const OptKey kOptKeys[] = {
     {"fuse_irchain", "F8_FUSE_IRCHAIN", &Options::fuse_irchain, 0, 1, true},
     {"fuse_dws", "F8_FUSE_DWS", &Options::fuse_dws, 0, 1, true},
     {"fuse_dws7", "F8_FUSE_DWS7", &Options::fuse_dws7, 0, 1, true},
+    {"fuse_head_dws", "F8_FUSE_HEAD_DWS", &Options::fuse_head_dws, 0, 1, true},
     {"fuse_head2", "F8_FUSE_HEAD2", &Options::fuse_head2, 0, 1, true},
     {"fuse_p12", "F8_FUSE_P12", &Options::fuse_p12, 0, 1, true},
     {"fuse_chain", "F8_FUSE_CHAIN", &Options::fuse_chain, 0, 1, true},
@@ -1367,6 +1368,9 @@ static void plan_inverted_residual_chains(f8_net* net) {
     }
 }
 
+// the 1x1 of a head launch (pass 1h) that only head_dws_kernel runs: more than one 32-channel output tile, or a ReLU
+static bool head_dws_form(const Node& c) { return c.cd.relu || round_up(c.cd.cout, 32) != 32; }
+
 // pass 1h
 static void plan_mobilenet_v2_head(f8_net* net) {
     auto& T = net->tensors;
@@ -1375,12 +1379,16 @@ static void plan_mobilenet_v2_head(f8_net* net) {
     const Options& opt = net->opt;
     // ---- 1h. MobileNet-V2 head: network input -> 3x3 / 2 conv (cin <= 4 -> 32, ReLU) -> depthwise 3x3 (ReLU) -> 1x1 (32 -> <= 32), each read
     //          by nobody else  ->  ONE row-walking launch (f8_stem.hip, stem_rows_kernel<KIND, true>): the three convs hand their rows to
-    //          each other in registers, the launch reads the caller's buffer itself
-    for (int i = 0; opt.fuse_head2 && opt.fuse_stem && i < nn; ++i) {
+    //          each other in registers, the launch reads the caller's buffer itself.  Option fuse_head_dws: the same position of MobileNet-V1 —
+    //          the 1x1 may have up to 64 output channels and / or a ReLU (f8_head_dws.hip, head_dws_kernel<KIND, NT>; bind_step picks the kernel
+    //          by those two properties); every other condition is the same.  Before 1j / 1k, which leave the claimed block 0 alone.
+    for (int i = 0; (opt.fuse_head2 || opt.fuse_head_dws) && opt.fuse_stem && i < nn; ++i) {
         Node& c = ND[i];
-        if (c.kind != N_CONV || c.cd.groups != 1 || c.cd.kernel != 1 || c.cd.stride != 1 || c.cd.pad != 0 || c.cd.relu || !c.cd.quant_input ||
+        if (c.kind != N_CONV || c.cd.groups != 1 || c.cd.kernel != 1 || c.cd.stride != 1 || c.cd.pad != 0 || !c.cd.quant_input ||
             c.cd.input_signed || c.fused_add >= 0 || claimed(net, i) || c.dual >= 0 || c.out == net->out_t) continue;      // (claimed: a stride-1 1x1 conv that carries no join and has no `dual` hosts only B_IR)
-        if (c.cd.cin != 32 || round_up(c.cd.cout, 32) != 32) continue;
+        if (c.cd.cin != 32) continue;
+        if (head_dws_form(c)) { if (!opt.fuse_head_dws || round_up(c.cd.cout, 32) > 64) continue; }      // MobileNet-V1's form
+        else if (!opt.fuse_head2) continue;                                                                // MobileNet-V2's: no ReLU, <= 32 couts
         const Tensor& tb = T[c.a];
         if (tb.consumers.size() != 1 || c.a == net->out_t) continue;
         Node& b = ND[tb.prod];
@@ -1714,7 +1722,7 @@ static int emit_head2(f8_net* net, int i, Step& st, std::vector<int>* extra) {
     st.ops_per_img = 2.0 * cpx * (32.0 * hh.cd.cin * 9 + 32.0 * 9 + 32.0 * nd.cd.cout);
     st.valu_per_img = 3.0 * cpx * (32.0 + 32.0 + o.Cs * out_forms8(st));
     st.bytes_per_img = (double)s.H * s.W * 4 + out_bytes(st, o, cpx);      // (int8 outputs only: pass 1h)
-    st.bytes_const = 32.0 * 100 + 32.0 * 13 + 32.0 * 36;
+    st.bytes_const = 32.0 * 100 + 32.0 * 13 + (double)o.Cs * 36;
     st.name = "head3x3s2+dw3x3+1x1:" + tname(net, hh.out) + "+" + tname(net, hb.out) + "+" + tname(net, nd.out);
     return F8_OK;
 }
@@ -2421,7 +2429,8 @@ static int bind_step(f8_net* net, Step& st) {
             if (h2) {
                 Node& hb = ND[nd.blk.b2];
                 const Tensor& oT = T[nd.out];
-                a.h2 = 1;
+                a.h2 = head_dws_form(nd) ? 2 : 1;         // 2: head_dws_kernel (pass 1h, option fuse_head_dws)
+                a.relu1 = nd.cd.relu ? 1 : 0; a.Cs = oT.Cs;
                 a.wd = W8(hb.w_off); a.bd = B32(hb.cc_off);
                 a.w1 = W8(nd.w_off); a.b1 = B32(nd.b_off);
                 fmt(hb, &a.na); fmt(nd, &a.nb);

@@ -710,9 +710,10 @@ static bool stem_rows_ok(const StemPoolArgs& a, bool raw) {
 
 // 2: the MobileNet-V2 head; 1: the row-walking kernel (Options::stem_rows) where it has an instance for the form the plan reads (raw: the
 // raw network input, whose sides rW, rH the plan binds; a run that reads the haloed copy instead has one too: stem_rows_ok); 0: the tile kernel
-int stem_pool_inst(const StemPoolArgs& a, bool rows, bool raw) { return a.h2 ? 2 : (rows && stem_rows_ok(a, raw)) ? 1 : 0; }
+// 3: the MobileNet-V1 head + first block (h2 == 2: f8_head_dws.hip)
+int stem_pool_inst(const StemPoolArgs& a, bool rows, bool raw) { return a.h2 == 2 ? 3 : a.h2 ? 2 : (rows && stem_rows_ok(a, raw)) ? 1 : 0; }
 // both kernels' first template argument is the kind of the run's raw input (int32, fp32, uint8, or -1: the haloed form): named without arguments
-const char* stem_pool_kernel_name(int inst) { return inst ? "f8::stem_rows_kernel" : "f8::stem_pool_kernel"; }
+const char* stem_pool_kernel_name(int inst) { return inst == 3 ? head_dws_kernel_name() : inst ? "f8::stem_rows_kernel" : "f8::stem_pool_kernel"; }
 
 bool stem_pool_supported(int cin, int cout, int k, int stride, int pad, int pool_k, int pool_s, int pool_p, int P, int Q, int rows, int H, int W) {
     if (!(cin <= 4 && cout == 64 && k == 7 && stride == 2 && pad == 3 && pool_k == 3 && pool_s == 2 && pool_p == 1 && P > 0 && Q > 0)) return false;
@@ -733,7 +734,8 @@ static int device_cus() {
 }
 
 hipError_t launch_stem_pool(const StemPoolArgs& a, int inst, hipStream_t s) {
-    if ((inst == 2) != (a.h2 != 0)) return hipErrorInvalidValue;
+    if ((inst == 2) != (a.h2 == 1) || (inst == 3) != (a.h2 == 2) || inst < 0 || inst > 3) return hipErrorInvalidValue;
+    if (inst == 3) return launch_head_dws(a, s);
     if (inst == 2) {
         if (!head2_supported(a.rH, a.rW) || a.P != a.rH / 2 || a.Q != a.rW / 2 || a.Pc != a.P || a.Qc != a.Q || a.na < 1 || a.nb < 1 || a.na > kRequantU8MaxShift || a.nb > kRequantU8MaxShift || (!a.acc_ok && !a.rq_int) || a.out32 ||
             (a.raw_kind < 0 && !(a.org == 4 && a.Wp % 4 == 0))) return hipErrorInvalidValue;
