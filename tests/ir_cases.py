@@ -34,11 +34,15 @@ class _Graph:
         self.taps = []
         self.raw = {}
 
-    def conv(self, t, w, b, *, stride=1, pad, groups, weight_fl, input_fl, input_signed, relu, label=None):
+    def conv(self, t, w, b, *, stride=1, pad, groups, weight_fl, input_fl, input_signed, relu, label=None, quant_input=True):
         o = self.net.conv(t, w, b, stride=stride, pad=pad, groups=groups, weight_fl=weight_fl, input_fl=input_fl, input_signed=input_signed,
-                          quant_input=True, relu=relu)
+                          quant_input=quant_input, relu=relu)
         x, fl = self.v[t]
-        xq = oracle.requant(x, input_fl, fl, input_signed)
+        if quant_input:
+            xq = oracle.requant(x, input_fl, fl, input_signed)
+        else:                                                    # the conv reads its input as it is: already 8 bits in its own format
+            assert fl == input_fl and x.min() >= (-127 if input_signed else 0) and x.max() <= (127 if input_signed else 255)
+            xq = x
         if label:
             self.taps.append((label, xq, input_signed))
         y = oracle.conv2d(xq, w, b, stride, pad, groups)
