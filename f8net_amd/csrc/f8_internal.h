@@ -67,6 +67,7 @@ struct Options {
     int requant_float = 0;       // 0 (default since round 5: BASELINE north_star — no FP32 multiply in any epilogue): integer shift / round-half-even /
                                  // clamp in every kernel; 1: ReLU -> unsigned 8-bit right shifts of values the planner can bound may run through the
                                  // float converter (v_cvt_f32_i32, v_mul_f32 by 2^-n, v_cvt_pk_u8_f32: exact where planned, f8_device.h)
+    int tap_tiled = 1;           // network outputs 1 .. leave on tap_kernel (f8_tap.hip: walks the I32T blocks, every loaded byte used); 0: on output_kernel like output 0
     int check_input_range = 1;   // int32 inputs that are NARROWED to the head's 8-bit format (no requant) are range-checked on the device; f8_net_check reports
 };
 void options_from_env(Options* o);                       // f8_net.cpp
@@ -532,6 +533,8 @@ const char* input_kernel_name(int inst);
 hipError_t launch_input(const InArgs& a, int inst, hipStream_t s);
 const char* output_kernel_name();
 hipError_t launch_output(const OutArgs& a, hipStream_t s);
+const char* tap_kernel_name(int as_float);                       // f8_tap.hip: the same conversion, one wave per 4 KB block of the I32T source
+hipError_t launch_tap(const OutArgs& a, hipStream_t s);
 hipError_t launch_quantize_input(const float* x, int32_t* y, size_t n, float scale, int lo, int hi, hipStream_t s);
 struct TopkKs { int k[8]; };                // the k list travels by value in the kernel arguments
 hipError_t launch_topk_correct(const float* logits, const int64_t* target, int N, int C, TopkKs ks, int nk, float* correct, hipStream_t s);

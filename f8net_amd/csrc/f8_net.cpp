@@ -133,6 +133,7 @@ struct Step {
     OutSel out;
     int acc_shl = 0, res_shl = 0, relu0 = 0, relu1 = 0;
     bool dense = false;
+    int out_k = 0;                     // S_OUTPUT: the network output it copies out (0: into the run's output_dev, k >= 1: into buffer k of f8_net_set_output_buffers)
     bool raw_input = false;            // S_INPUT: its work is done by the stem launch (S_STEMPOOL with the same flag) unless the run's input is uint8 NHWC
     std::string name;
     std::string kernel;                // device symbol as rocprofv3 prints it: of the instance bind_step chose (the launch family's *_kernel_name)
@@ -150,7 +151,11 @@ struct Step {
 struct f8_net {
     std::vector<Tensor> tensors;
     std::vector<Node> nodes;
-    int out_t = -1, out_float = 0;
+    struct Output { int t; int as_float; };
+    std::vector<Output> outs;          // the network outputs in the order of the f8_net_output calls; [0] is the one f8_net_run's output_dev receives
+    void* out_bufs[F8_MAX_OUTPUTS - 1] = {};   // caller buffers of outputs 1 .. (f8_net_set_output_buffers): one-shot, consumed by the next run ...
+    bool out_bufs_set = false;
+    void* run_bufs[F8_MAX_OUTPUTS - 1] = {};   // ... which keeps them here while it issues its launches
     bool finalized = false;
     int plan_bug = -1;                 // planning: a conv that two fused blocks claimed (set_block); finalize fails on it
     int max_batch = 0;
@@ -184,6 +189,13 @@ struct f8_net {
 };
 
 namespace {
+
+// index of tensor t among the network outputs, -1: none.  Every output exists in HBM as int32: no fused launch keeps it on chip.
+int output_index(const f8_net* net, int t) {
+    for (size_t k = 0; k < net->outs.size(); ++k) if (net->outs[k].t == t) return (int)k;
+    return -1;
+}
+bool is_output(const f8_net* net, int t) { return output_index(net, t) >= 0; }
 
 int add_form(Tensor& t, int kind, int n, int sgn) {
     for (size_t i = 0; i < t.forms.size(); ++i)
@@ -356,6 +368,7 @@ static const OptKey kOptKeys[] = {
     {"arena_copies", "F8_ARENA_COPIES", &Options::arena_copies, 0, 4, true},
     {"shared_streams", "F8_SHARED_STREAMS", &Options::shared_streams, 0, 1, true},
     {"whole_batch_launches", "F8_WHOLE_BATCH_LAUNCHES", &Options::whole_batch_launches, 0, 1, true},
+    {"tap_tiled", "F8_TAP_TILED", &Options::tap_tiled, 0, 1, true},
 };
 static const OptKey* find_opt(const char* key) {
     if (!key) return nullptr;
@@ -637,8 +650,33 @@ int f8_net_avgpool_sum(f8_net* net, int src, int shift) {
 int f8_net_output(f8_net* net, int src, int as_float) {
     int rc = check_t(net, src, "f8_net_output");
     if (rc) return rc;
-    if (net->out_t >= 0) return fail(F8_ERR_UNSUPPORTED, "f8_net_output: one output per net");
-    net->out_t = src; net->out_float = as_float ? 1 : 0;
+    if (is_output(net, src)) return fail(F8_ERR_INVALID, "f8_net_output: tensor %d is already output %d", src, output_index(net, src));
+    if ((int)net->outs.size() >= F8_MAX_OUTPUTS) return fail(F8_ERR_UNSUPPORTED, "f8_net_output: at most %d outputs per net", F8_MAX_OUTPUTS);
+    net->outs.push_back({src, as_float ? 1 : 0});
+    return (int)net->outs.size() - 1;
+}
+
+int f8_net_num_outputs(const f8_net* net) { return net ? (int)net->outs.size() : F8_ERR_INVALID; }
+
+int f8_net_output_info(const f8_net* net, int k, int* C, int* H, int* W, int* fraclen, int* as_float) {
+    if (!net) return fail(F8_ERR_INVALID, "f8_net_output_info: null net");
+    if (k < 0 || k >= (int)net->outs.size()) return fail(F8_ERR_INVALID, "f8_net_output_info: output %d of %d", k, (int)net->outs.size());
+    const Tensor& t = net->tensors[net->outs[k].t];
+    if (C) *C = t.C;
+    if (H) *H = t.H;
+    if (W) *W = t.W;
+    if (fraclen) *fraclen = t.fl;
+    if (as_float) *as_float = net->outs[k].as_float;
+    return F8_OK;
+}
+
+int f8_net_set_output_buffers(f8_net* net, void* const* bufs_dev, int n) {
+    if (!net) return fail(F8_ERR_INVALID, "f8_net_set_output_buffers: null net");
+    if (!net->finalized) return fail(F8_ERR_STATE, "f8_net_set_output_buffers: not finalized");
+    if (n != (int)net->outs.size() - 1) return fail(F8_ERR_INVALID, "f8_net_set_output_buffers: %d buffers for outputs 1 .. %d", n, (int)net->outs.size() - 1);
+    for (int k = 0; k < n; ++k) if (!bufs_dev || !bufs_dev[k]) return fail(F8_ERR_INVALID, "f8_net_set_output_buffers: null pointer");
+    for (int k = 0; k < n; ++k) net->out_bufs[k] = bufs_dev[k];
+    net->out_bufs_set = true;
     return F8_OK;
 }
 
@@ -920,7 +958,7 @@ static void plan_residual_joins(f8_net* net) {
             const int px = T[x].prod, py = T[y].prod;
             Node& cx = ND[px];
             if (cx.kind != N_CONV || cx.cd.groups != 1 || cx.fused_add >= 0) continue;
-            if (T[x].consumers.size() != 1 || x == net->out_t) continue;
+            if (T[x].consumers.size() != 1 || is_output(net, x)) continue;
             if (py > px) continue;     // other operand must exist before the conv runs
             ad.fused_into = px; cx.fused_add = i;
         }
@@ -941,11 +979,11 @@ static void plan_bottleneck_blocks(f8_net* net, int max_batch) {
         Node& c = ND[i];
         if (c.kind != N_CONV || c.fused_add < 0 || c.cd.groups != 1 || c.cd.kernel != 1 || c.cd.stride != 1 || c.cd.pad != 0 || c.cd.relu) continue;
         const Tensor& tb = T[c.a];
-        if (tb.consumers.size() != 1 || c.a == net->out_t || !c.cd.quant_input) continue;
+        if (tb.consumers.size() != 1 || is_output(net, c.a) || !c.cd.quant_input) continue;
         Node& b = ND[tb.prod];
         if (b.kind != N_CONV || b.fused_add >= 0 || b.cd.groups != 1 || b.cd.kernel != 3 || b.cd.stride != 1 || b.cd.pad != 1 || !b.cd.quant_input) continue;
         const Tensor& ta = T[b.a];
-        if (ta.consumers.size() != 1 || b.a == net->out_t) continue;
+        if (ta.consumers.size() != 1 || is_output(net, b.a)) continue;
         Node& a0 = ND[ta.prod];
         if (a0.kind != N_CONV || a0.fused_add >= 0 || a0.cd.groups != 1 || a0.cd.kernel != 1 || a0.cd.stride != 1 || a0.cd.pad != 0) continue;
         const Node& ad = ND[c.fused_add];
@@ -986,7 +1024,7 @@ static void plan_dual_gemm_joins(f8_net* net) {
         if (h.cd.cin % 64 != 0 || round_up(h.cd.cout, 32) <= 32) continue;          // kernel instances: BK = 64, BN = 64
         const Node& ad = ND[h.fused_add];
         const int other = (ad.a == h.out) ? ad.b : ad.a;
-        if (T[other].consumers.size() != 1 || other == net->out_t) continue;
+        if (T[other].consumers.size() != 1 || is_output(net, other)) continue;
         Node& g = ND[T[other].prod];
         if (g.kind != N_CONV || g.fused_add >= 0 || claimed(net, T[other].prod) || g.cd.groups != 1 || g.cd.kernel != 1 || g.cd.pad != 0 ||
             g.cd.relu || g.cd.cin % 64 != 0 || g.cd.cout != h.cd.cout) continue;
@@ -1011,13 +1049,13 @@ static void plan_stage_opening_blocks(f8_net* net) {
         Node& g = ND[h.dual];
         if (g.cd.stride != 1 || !g.cd.quant_input) continue;
         const Tensor& tb = T[g.a];
-        if (tb.consumers.size() != 1 || g.a == net->out_t) continue;
+        if (tb.consumers.size() != 1 || is_output(net, g.a)) continue;
         Node& b = ND[tb.prod];
         // (claimed: b feeds g, which carries no join — a P12 host (1b) feeds the conv that carries the block's; a0 is a 1x1 conv that carries no join: no host)
         if (b.kind != N_CONV || b.fused_add >= 0 || claimed(net, tb.prod) || b.cd.groups != 1 || b.cd.kernel != 3 || b.cd.stride != bs || b.cd.pad != 1 ||
             !b.cd.quant_input) continue;
         const Tensor& ta = T[b.a];
-        if (ta.consumers.size() != 1 || b.a == net->out_t) continue;
+        if (ta.consumers.size() != 1 || is_output(net, b.a)) continue;
         Node& a0 = ND[ta.prod];
         if (a0.kind != N_CONV || a0.fused_add >= 0 || claimed(net, ta.prod) || a0.cd.groups != 1 || a0.cd.kernel != 1 || a0.cd.stride != 1 ||
             a0.cd.pad != 0 || !a0.cd.quant_input || a0.a != h.a || a0.dual >= 0) continue;
@@ -1093,7 +1131,7 @@ static void plan_stage_chains(f8_net* net) {
             std::vector<int> hosts{first.host};
             Blk cur = first;
             const int max_blocks = chain_max_blocks(first.C, first.MID, first.H, first.W, first.cin0, first.tail);
-            while ((int)hosts.size() < max_blocks && cur.out_t != net->out_t) {
+            while ((int)hosts.size() < max_blocks && !is_output(net, cur.out_t)) {
                 const Tensor& y = T[cur.out_t];
                 if (y.consumers.size() != 2) break;
                 int next = -1;
@@ -1147,7 +1185,7 @@ static void plan_basic_block_chains(f8_net* net) {
             const Node& c2 = ND[i];
             if (c2.kind != N_CONV || c2.fused_add < 0 || claimed(net, i) || c2.dual >= 0 || c2.cd.groups != 1 || c2.cd.kernel != 3 || c2.cd.stride != 1 || c2.cd.pad != 1 || c2.cd.relu || !c2.cd.quant_input) return false;
             const Tensor& tb = T[c2.a];
-            if (tb.consumers.size() != 1 || c2.a == net->out_t) return false;
+            if (tb.consumers.size() != 1 || is_output(net, c2.a)) return false;
             const Node& c1 = ND[tb.prod];
             if (c1.kind != N_CONV || c1.fused_add >= 0 || claimed(net, tb.prod) || c1.cd.groups != 1 || c1.cd.kernel != 3 || c1.cd.stride != 1 ||
                 c1.cd.pad != 1 || !c1.cd.quant_input || c1.dual >= 0) return false;
@@ -1167,7 +1205,7 @@ static void plan_basic_block_chains(f8_net* net) {
             std::vector<int> hosts{i};
             const bool sgn0 = ND[T[ND[i].a].prod].cd.input_signed;
             int cur_out = out_t;
-            while ((int)hosts.size() < kBChainMaxBlocks && cur_out != net->out_t) {
+            while ((int)hosts.size() < kBChainMaxBlocks && !is_output(net, cur_out)) {
                 const Tensor& y = T[cur_out];
                 if (y.consumers.size() != 2) break;
                 int next = -1, nin = -1, nout = -1, nC = 0;
@@ -1189,7 +1227,7 @@ static void plan_basic_block_chains(f8_net* net) {
             // the stage-opening block in front of them (3x3 / 2 ReLU -> 3x3, 1x1 / 2 shortcut, join) joins the launch when the chain is
             // the only reader of its output (its two convs over the block input may read different int8 forms of it)
             [&] {
-                if ((cluster ? opt.fuse_bchain7 : opt.fuse_bchain) < 2 || (int)hosts.size() >= kBChainMaxBlocks || in_t == net->out_t) return;
+                if ((cluster ? opt.fuse_bchain7 : opt.fuse_bchain) < 2 || (int)hosts.size() >= kBChainMaxBlocks || is_output(net, in_t)) return;
                 const Tensor& y = T[in_t];
                 const int c1f = T[ND[i].a].prod, adf = ND[i].fused_add;
                 if (y.consumers.size() != 2 || !((y.consumers[0] == c1f && y.consumers[1] == adf) || (y.consumers[0] == adf && y.consumers[1] == c1f))) return;
@@ -1199,12 +1237,12 @@ static void plan_basic_block_chains(f8_net* net) {
                 Node& h = ND[hi];
                 if (h.kind != N_CONV || h.fused_add != y.prod || claimed(net, hi) || h.dual >= 0 || h.cd.groups != 1 || h.cd.kernel != 1 || h.cd.stride != 2 || h.cd.pad != 0 || h.cd.relu || !h.cd.quant_input) return;
                 const int other = (ad.a == h.out) ? ad.b : ad.a;
-                if (T[other].consumers.size() != 1 || other == net->out_t) return;
+                if (T[other].consumers.size() != 1 || is_output(net, other)) return;
                 const int gi = T[other].prod;
                 Node& g = ND[gi];
                 if (g.kind != N_CONV || g.fused_add >= 0 || claimed(net, gi) || g.dual >= 0 || g.cd.groups != 1 || g.cd.kernel != 3 ||
                     g.cd.stride != 1 || g.cd.pad != 1 || g.cd.relu || !g.cd.quant_input) return;
-                if (T[g.a].consumers.size() != 1 || g.a == net->out_t) return;
+                if (T[g.a].consumers.size() != 1 || is_output(net, g.a)) return;
                 const int bi = T[g.a].prod;
                 Node& b0 = ND[bi];
                 if (b0.kind != N_CONV || b0.fused_add >= 0 || claimed(net, bi) || b0.dual >= 0 || b0.cd.groups != 1 || b0.cd.kernel != 3 ||
@@ -1245,12 +1283,12 @@ static void plan_inverted_residuals(f8_net* net) {
         if (c.kind != N_CONV || c.cd.groups != 1 || c.cd.kernel != 1 || c.cd.stride != 1 || c.cd.pad != 0 || !c.cd.quant_input ||
             claimed(net, i) || c.dual >= 0) continue;
         const Tensor& tb = T[c.a];
-        if (tb.consumers.size() != 1 || c.a == net->out_t) continue;
+        if (tb.consumers.size() != 1 || is_output(net, c.a)) continue;
         Node& b = ND[tb.prod];
         if (b.kind != N_CONV || b.cd.groups == 1 || b.cd.groups != b.cd.cin || b.cd.kernel != 3 || b.cd.pad != 1 || (b.cd.stride != 1 && b.cd.stride != 2) ||
             !b.cd.quant_input || b.fused_add >= 0 || claimed(net, tb.prod)) continue;
         const Tensor& ta = T[b.a];
-        if (ta.consumers.size() != 1 || b.a == net->out_t) continue;
+        if (ta.consumers.size() != 1 || is_output(net, b.a)) continue;
         Node& a0 = ND[ta.prod];
         if (a0.kind != N_CONV || a0.cd.groups != 1 || a0.cd.kernel != 1 || a0.cd.stride != 1 || a0.cd.pad != 0 || a0.fused_add >= 0 ||
             claimed(net, ta.prod) || a0.dual >= 0 || !a0.cd.quant_input) continue;      // (a host too: chains of 1x1 / dw / 1x1 / dw ...)
@@ -1294,13 +1332,13 @@ static void plan_inverted_residual_chains(f8_net* net) {
         if (c.kind != N_CONV || c.cd.groups != 1 || c.cd.kernel != 1 || c.cd.stride != 1 || c.cd.pad != 0 || !c.cd.quant_input ||
             claimed(net, ci, B_IR) || c.dual >= 0) return false;      // (the block 1e hosted here is taken over; one this pass chained already is claimed by its chain)
         const Tensor& tb = T[c.a];
-        if (tb.prod < 0 || tb.consumers.size() != 1 || c.a == net->out_t) return false;
+        if (tb.prod < 0 || tb.consumers.size() != 1 || is_output(net, c.a)) return false;
         const int bi = tb.prod;
         const Node& b = ND[bi];
         if (b.kind != N_CONV || b.cd.groups == 1 || b.cd.groups != b.cd.cin || b.cd.cout != b.cd.cin || b.cd.kernel != 3 || b.cd.pad != 1 || b.cd.stride != 1 ||
             !b.cd.quant_input || b.fused_add >= 0 || (b.absorbed_by >= 0 && b.absorbed_by != ci)) return false;      // (a member of c's own block: 1e)
         const Tensor& ta = T[b.a];
-        if (ta.prod < 0 || ta.consumers.size() != 1 || b.a == net->out_t) return false;
+        if (ta.prod < 0 || ta.consumers.size() != 1 || is_output(net, b.a)) return false;
         const int ai = ta.prod;
         const Node& a0 = ND[ai];
         if (a0.kind != N_CONV || a0.cd.groups != 1 || a0.cd.kernel != 1 || a0.cd.stride != 1 || a0.cd.pad != 0 || !a0.cd.quant_input || a0.fused_add >= 0 ||
@@ -1311,7 +1349,7 @@ static void plan_inverted_residual_chains(f8_net* net) {
         if (c.fused_add >= 0) {                                   // a residual join must be with the block input
             const Node& ad = ND[c.fused_add];
             const int other = (ad.a == c.out) ? ad.b : ad.a;
-            if (other != a0.a || T[c.out].consumers.size() != 1 || c.out == net->out_t) return false;
+            if (other != a0.a || T[c.out].consumers.size() != 1 || is_output(net, c.out)) return false;
             k->res = true; k->out = ad.out;
         }
         const Tensor& x = T[a0.a];
@@ -1335,7 +1373,7 @@ static void plan_inverted_residual_chains(f8_net* net) {
         if (!fits(run)) continue;
         for (;;) {                                                // extend: the block output's only readers are the next block's expand conv and its join
             const Blk& last = run.back();
-            if (last.out == net->out_t) break;
+            if (is_output(net, last.out)) break;
             const Tensor& o = T[last.out];
             int nxt = -1, joins = 0, others = 0;
             for (int u : o.consumers) {
@@ -1385,20 +1423,20 @@ static void plan_mobilenet_v2_head(f8_net* net) {
     for (int i = 0; (opt.fuse_head2 || opt.fuse_head_dws) && opt.fuse_stem && i < nn; ++i) {
         Node& c = ND[i];
         if (c.kind != N_CONV || c.cd.groups != 1 || c.cd.kernel != 1 || c.cd.stride != 1 || c.cd.pad != 0 || !c.cd.quant_input ||
-            c.cd.input_signed || c.fused_add >= 0 || claimed(net, i) || c.dual >= 0 || c.out == net->out_t) continue;      // (claimed: a stride-1 1x1 conv that carries no join and has no `dual` hosts only B_IR)
+            c.cd.input_signed || c.fused_add >= 0 || claimed(net, i) || c.dual >= 0 || is_output(net, c.out)) continue;      // (claimed: a stride-1 1x1 conv that carries no join and has no `dual` hosts only B_IR)
         if (c.cd.cin != 32) continue;
         if (head_dws_form(c)) { if (!opt.fuse_head_dws || round_up(c.cd.cout, 32) > 64) continue; }      // MobileNet-V1's form
         else if (!opt.fuse_head2) continue;                                                                // MobileNet-V2's: no ReLU, <= 32 couts
         const Tensor& tb = T[c.a];
-        if (tb.consumers.size() != 1 || c.a == net->out_t) continue;
+        if (tb.consumers.size() != 1 || is_output(net, c.a)) continue;
         Node& b = ND[tb.prod];
         if (b.kind != N_CONV || b.cd.groups != b.cd.cin || b.cd.cin != 32 || b.cd.cout != 32 || b.cd.kernel != 3 || b.cd.stride != 1 || b.cd.pad != 1 ||
             !b.cd.relu || !b.cd.quant_input || b.cd.input_signed || b.fused_add >= 0 || b.absorbed_by >= 0) continue;
         const Tensor& ta = T[b.a];
-        if (ta.consumers.size() != 1 || b.a == net->out_t) continue;
+        if (ta.consumers.size() != 1 || is_output(net, b.a)) continue;
         Node& h = ND[ta.prod];
         if (h.kind != N_CONV || h.cd.groups != 1 || h.cd.kernel != 3 || h.cd.stride != 2 || h.cd.pad != 1 || h.cd.cin > 4 || h.cd.cout != 32 || !h.cd.relu ||
-            h.fused_add >= 0 || h.absorbed_by >= 0 || h.a == net->out_t) continue;
+            h.fused_add >= 0 || h.absorbed_by >= 0 || is_output(net, h.a)) continue;
         const Tensor& x = T[h.a];
         if (x.prod < 0 || ND[x.prod].kind != N_INPUT || x.consumers.size() != 1 || !(!h.cd.quant_input || x.fl == h.cd.input_fl)) continue;
         if (!head2_supported(x.H, x.W) || ta.H * 2 != x.H || ta.W * 2 != x.W) continue;
@@ -1423,17 +1461,17 @@ static void plan_last_conv_and_pool(f8_net* net) {
     //          pixels in the epilogue (f8_pool.hip); the conv's int32 result — read by nobody but the pool — never exists
     for (int i = 0; opt.fuse_pool && i < nn; ++i) {
         Node& p = ND[i];
-        if (p.kind != N_AVGPOOL || p.a == net->out_t || T[p.a].consumers.size() != 1) continue;
+        if (p.kind != N_AVGPOOL || is_output(net, p.a) || T[p.a].consumers.size() != 1) continue;
         const Tensor& t = T[p.a];
         if (t.prod < 0) continue;
         int ci = t.prod;
         if (ND[ci].kind == N_ADD) { if (ND[ci].fused_into < 0) continue; ci = ND[ci].fused_into; }
         Node& c = ND[ci];
-        if (c.kind == N_CONV && c.chain_into == ci && c.chain_kind == C_BASIC_CLUSTER && c.fused_add >= 0 && ND[c.fused_add].out == p.a && p.out != net->out_t) {
+        if (c.kind == N_CONV && c.chain_into == ci && c.chain_kind == C_BASIC_CLUSTER && c.fused_add >= 0 && ND[c.fused_add].out == p.a && !is_output(net, p.out)) {
             c.pool = i; p.pool_host = ci;                         // the last block of a 7x7 BasicBlock cluster chain: the same (f8_bcchain.hip)
             continue;
         }
-        if (c.kind == N_CONV && c.chain_into == ci && c.chain_kind == C_STAGE && c.fused_add >= 0 && ND[c.fused_add].out == p.a && p.out != net->out_t &&
+        if (c.kind == N_CONV && c.chain_into == ci && c.chain_kind == C_STAGE && c.fused_add >= 0 && ND[c.fused_add].out == p.a && !is_output(net, p.out) &&
             cchain_supported(c.cd.cout, c.cd.cin, t.H, t.W, c.cd.cout, false)) {      // (geometry: a chain's last block is an identity block)
             c.pool = i; p.pool_host = ci;                         // the last block of a 7x7 cluster chain: the pool is summed from its stream registers (f8_cchain.hip)
             continue;
@@ -1462,14 +1500,14 @@ static void plan_depthwise_separable(f8_net* net, int max_batch) {
         if (c.kind != N_CONV || c.cd.groups != 1 || c.cd.kernel != 1 || c.cd.stride != 1 || c.cd.pad != 0 || !c.cd.quant_input ||
             c.fused_add >= 0 || c.dual >= 0 || c.pool >= 0 || claimed(net, i)) continue;
         const Tensor& tb = T[c.a];
-        if (tb.prod < 0 || tb.consumers.size() != 1 || c.a == net->out_t) continue;
+        if (tb.prod < 0 || tb.consumers.size() != 1 || is_output(net, c.a)) continue;
         const int bi = tb.prod;
         const Node& b = ND[bi];
         if (b.kind != N_CONV || b.cd.groups == 1 || b.cd.groups != b.cd.cin || b.cd.cout != b.cd.cin || b.cd.kernel != 3 || b.cd.pad != 1 ||
             (b.cd.stride != 1 && b.cd.stride != 2) || !b.cd.relu || !b.cd.quant_input || b.fused_add >= 0 || claimed(net, bi)) continue;
         const Tensor& x = T[b.a];
         if (x.prod < 0 || ND[x.prod].kind == N_INPUT || (b.cd.cin & 31)) continue;      // (the network input has its own layouts)
-        if (c.out == net->out_t || T[c.out].consumers.empty()) continue;                 // the net output is int32
+        if (is_output(net, c.out) || T[c.out].consumers.empty()) continue;                 // the net output is int32
         bool int8_readers = true;
         std::vector<std::pair<int, int>> fmts;
         for (int u : T[c.out].consumers) {
@@ -1501,14 +1539,14 @@ static void plan_depthwise_separable_7x7(f8_net* net, int max_batch) {
         if (c.kind != N_CONV || c.cd.groups != 1 || c.cd.kernel != 1 || c.cd.stride != 1 || c.cd.pad != 0 || !c.cd.quant_input ||
             c.fused_add >= 0 || c.dual >= 0 || c.pool >= 0 || claimed(net, i)) continue;
         const Tensor& tb = T[c.a];
-        if (tb.prod < 0 || tb.consumers.size() != 1 || c.a == net->out_t) continue;
+        if (tb.prod < 0 || tb.consumers.size() != 1 || is_output(net, c.a)) continue;
         const int bi = tb.prod;
         const Node& b = ND[bi];
         if (b.kind != N_CONV || b.cd.groups == 1 || b.cd.groups != b.cd.cin || b.cd.cout != b.cd.cin || b.cd.kernel != 3 || b.cd.pad != 1 ||
             (b.cd.stride != 1 && b.cd.stride != 2) || !b.cd.relu || !b.cd.quant_input || b.fused_add >= 0 || claimed(net, bi)) continue;
         const Tensor& x = T[b.a];
         if (x.prod < 0 || ND[x.prod].kind == N_INPUT || (b.cd.cin & 31)) continue;      // (the network input has its own layouts)
-        if (c.out == net->out_t || T[c.out].consumers.empty()) continue;                 // the net output is int32
+        if (is_output(net, c.out) || T[c.out].consumers.empty()) continue;                 // the net output is int32
         // an inverted residual — expanding 1x1 (ReLU) -> depthwise -> 1x1 WITHOUT ReLU — is passes 1e / 1e2's to decide: the 7x7 ones that fuse_ir = 1
         // leaves as three launches were measured there (1j never sees them: it has no 7-wide form)
         const Node& xp = ND[x.prod];
@@ -1516,7 +1554,7 @@ static void plan_depthwise_separable_7x7(f8_net* net, int max_batch) {
         int pool = -1;
         if (T[c.out].consumers.size() == 1 && ND[T[c.out].consumers[0]].kind == N_AVGPOOL) {
             const int pi = T[c.out].consumers[0];
-            if (ND[pi].pool_host >= 0 || ND[pi].out == net->out_t) continue;             // (a pooled net output is int32 of the caller's: the pool stays a launch, and so does this conv's int32 result)
+            if (ND[pi].pool_host >= 0 || is_output(net, ND[pi].out)) continue;             // (a pooled net output is int32 of the caller's: the pool stays a launch, and so does this conv's int32 result)
             pool = pi;
         }
         bool int8_readers = true;
@@ -1547,14 +1585,16 @@ static void plan_tensor_forms(f8_net* net) {
     const Options& opt = net->opt;
     // ---- 2. which forms does each tensor need?  (reverse order: consumers before producers)
     {
-        Tensor& O = T[net->out_t];
+        const int out0 = net->outs[0].t;
+        Tensor& O = T[out0];
         const Node& p = ND[O.prod];
         // the classifier (a linear / 1x1 conv on a 1x1 map that nothing else reads) writes the caller's buffer itself: no int32 form
-        const Tensor& ps = T[p.a >= 0 ? p.a : net->out_t];
+        const Tensor& ps = T[p.a >= 0 ? p.a : out0];
         O.dense_out = opt.fuse_fc && (p.kind == N_LINEAR || p.kind == N_CONV) && p.cd.kernel == 1 && p.cd.stride == 1 && p.cd.pad == 0 && p.cd.groups == 1 &&
                       O.H == 1 && O.W == 1 && ps.H == 1 && ps.W == 1 && O.consumers.empty() && p.fused_add < 0 && p.absorbed_by < 0 && !p.cd.relu &&
                       fc_dense_supported(ps.Cs, round_up(p.cd.cout, 32));
         if (!O.dense_out) add_form(O, FORM_I32, 0, 0);
+        for (size_t k = 1; k < net->outs.size(); ++k) add_form(T[net->outs[k].t], FORM_I32, 0, 0);      // the copy-out launch reads the int32 form
     }
     for (int i = nn - 1; i >= 0; --i) {
         Node& nd = ND[i];
@@ -1596,7 +1636,7 @@ static void plan_tensor_forms(f8_net* net) {
                 }
                 if (in_launch) break;
                 nd.stem = !nd.depthwise && nd.cd.cin <= 4 && ND[s.prod].kind == N_INPUT && nd.cd.kernel <= 8 &&
-                          s.consumers.size() == 1 && nd.a != net->out_t && n == 0;
+                          s.consumers.size() == 1 && !is_output(net, nd.a) && n == 0;
                 if (nd.stem) {
                     const int Q = T[nd.out].W;
                     const int f = add_form(s, FORM_STEM, 0, 0);
@@ -1617,11 +1657,11 @@ static void plan_tensor_forms(f8_net* net) {
                 break;
             case N_MAXPOOL: {
                 Tensor& o = T[nd.out];
-                if (!o.forms.empty() && T[nd.a].consumers.size() == 1 && nd.a != net->out_t) {
+                if (!o.forms.empty() && T[nd.a].consumers.size() == 1 && !is_output(net, nd.a)) {
                     // ResNet head: 7x7/2 stem conv + this pool in one launch (the conv output never leaves LDS)
                     Node& c = ND[T[nd.a].prod];
                     if (c.kind == N_CONV && c.cd.groups == 1 && c.fused_add < 0 && ND[T[c.a].prod].kind == N_INPUT && T[c.a].consumers.size() == 1 &&
-                        c.a != net->out_t && (!c.cd.quant_input || T[c.a].fl == c.cd.input_fl) && opt.fuse_stem &&
+                        !is_output(net, c.a) && (!c.cd.quant_input || T[c.a].fl == c.cd.input_fl) && opt.fuse_stem &&
                         stem_pool_supported(c.cd.cin, c.cd.cout, c.cd.kernel, c.cd.stride, c.cd.pad, nd.pk, nd.pstride, nd.ppad, o.H, o.W, opt.stem_rows, T[c.a].H, T[c.a].W)) {
                         c.sp_pool = i; nd.sp_conv = T[nd.a].prod;
                         break;                                   // no HBM form of the conv output
@@ -2164,12 +2204,13 @@ static void emit_requants(f8_net* net, int t, const std::vector<int>& extra) {
 }
 
 // the network output's launch, unless the classifier writes the caller's buffer itself
-static void emit_output(f8_net* net) {
-    const Tensor& x = net->tensors[net->out_t];
+static void emit_output(f8_net* net, int k = 0) {
+    const int t = net->outs[k].t;
+    const Tensor& x = net->tensors[t];
     if (x.dense_out) return;
-    Step st; st.kind = S_OUTPUT; st.node = x.prod;
-    st.src_t = net->out_t; st.src_f = find_form(x, FORM_I32, 0, 0);
-    st.name = "output:" + tname(net, net->out_t);
+    Step st; st.kind = S_OUTPUT; st.node = x.prod; st.out_k = k;
+    st.src_t = t; st.src_f = find_form(x, FORM_I32, 0, 0);
+    st.name = (k ? "tap:" : "output:") + tname(net, t);
     st.bytes_per_img = (double)x.H * x.W * (x.Cs + x.C) * 4;
     net->steps.push_back(st);
 }
@@ -2193,6 +2234,7 @@ static void let_stem_read_input(f8_net* net) {
 
 static int emit_steps(f8_net* net, int max_batch) {
     net->steps.clear();
+    int taps = 0;
     for (int i = 0; i < (int)net->nodes.size(); ++i) {
         const Node& nd = net->nodes[i];
         if (nd.kind == N_ADD && nd.fused_into >= 0) continue;
@@ -2213,7 +2255,12 @@ static int emit_steps(f8_net* net, int max_batch) {
         if (rc) return rc;
         net->steps.push_back(st);
         emit_requants(net, st.out.t, extra);
+        // a further output leaves directly behind the launch that writes its int32 form: the form's lifetime ends here unless the net reads it
+        // again, and the arena reuses its space (at the end of the plan every tapped map would stay allocated through the whole run)
+        const int k = output_index(net, st.out.t);
+        if (k >= 1) { emit_output(net, k); ++taps; }
     }
+    if (taps != (int)net->outs.size() - 1) return fail(F8_ERR_UNSUPPORTED, "f8_net_finalize: an output tensor is written by no launch of the plan");
     emit_output(net);
     let_stem_read_input(net);
     return F8_OK;
@@ -2737,8 +2784,9 @@ static int bind_step(f8_net* net, Step& st) {
         case S_OUTPUT: {
             const Tensor& sT = T[st.src_t];
             OutArgs a{};
-            a.C = sT.C; a.HW = sT.H * sT.W; a.Cs = sT.Cs; a.as_float = net->out_float;
-            snprintf(kb, sizeof kb, "%s", output_kernel_name());
+            a.C = sT.C; a.HW = sT.H * sT.W; a.Cs = sT.Cs; a.as_float = net->outs[st.out_k].as_float;
+            st.inst = st.out_k >= 1 && opt.tap_tiled;      // output 0 stays on output_kernel (option tap_tiled, f8net.h)
+            snprintf(kb, sizeof kb, "%s", st.inst ? tap_kernel_name(a.as_float) : output_kernel_name());
             st.args = a; break;
         }
     }
@@ -2750,7 +2798,7 @@ int f8_net_finalize(f8_net* net, int max_batch) {
     if (!net) return fail(F8_ERR_INVALID, "f8_net_finalize: null net");
     if (net->finalized) return fail(F8_ERR_STATE, "f8_net_finalize: already finalized");
     if (max_batch < 1) return fail(F8_ERR_INVALID, "f8_net_finalize: max_batch < 1");
-    if (net->out_t < 0) return fail(F8_ERR_STATE, "f8_net_finalize: no output marked");
+    if (net->outs.empty()) return fail(F8_ERR_STATE, "f8_net_finalize: no output marked");
     if (net->nodes.empty() || net->nodes[0].kind != N_INPUT) return fail(F8_ERR_STATE, "f8_net_finalize: first node must be the input");
     plan_residual_joins(net);                       // 1:  a residual add rides in the epilogue of the later of its two producers
     plan_bottleneck_blocks(net, max_batch);         // 1b: bottleneck identity blocks (one launch, or body.0 + body.2 on the 7x7 maps)
@@ -2797,10 +2845,10 @@ size_t f8_net_describe(const f8_net* net, char* buf, size_t cap) {
 int f8_net_num_launches(const f8_net* net) { return (net && net->finalized) ? (int)net->steps.size() : F8_ERR_STATE; }
 size_t f8_net_arena_bytes(const f8_net* net) { return net ? net->arena_bytes : 0; }
 size_t f8_net_weight_bytes(const f8_net* net) { return net ? net->wblob.size() : 0; }
-int f8_net_output_fraclen(const f8_net* net) { return (net && net->out_t >= 0) ? net->tensors[net->out_t].fl : F8_ERR_STATE; }
+int f8_net_output_fraclen(const f8_net* net) { return (net && !net->outs.empty()) ? net->tensors[net->outs[0].t].fl : F8_ERR_STATE; }
 size_t f8_net_output_elems(const f8_net* net) {
-    if (!net || net->out_t < 0) return 0;
-    const Tensor& t = net->tensors[net->out_t];
+    if (!net || net->outs.empty()) return 0;
+    const Tensor& t = net->tensors[net->outs[0].t];
     return (size_t)t.C * t.H * t.W;
 }
 
@@ -2977,7 +3025,7 @@ static int run_step(const f8_net* net, const Step& st, const int32_t* input, voi
             fill_out(&a.out32, a.q);
             const int C = T[nd.out].C;
             switch (st.variant) {
-                case V_FC: e = launch_fc_dense(a, (char*)output + (size_t)n0 * C * 4, C, net->out_float, chain_err, net->epoch, s); break;
+                case V_FC: e = launch_fc_dense(a, (char*)output + (size_t)n0 * C * 4, C, net->outs[0].as_float, chain_err, net->epoch, s); break;
                 case V_POOL: e = launch_conv1x1_pool(a, s); break;
                 case V_S2WREG: e = launch_conv3x3s2_wreg(a, s); break;
                 case V_WSTAT: e = launch_conv1x1_wstat(a, st.inst, net->num_cu, s); break;
@@ -3116,8 +3164,9 @@ static int run_step(const f8_net* net, const Step& st, const int32_t* input, voi
         case S_OUTPUT: {
             OutArgs a = std::get<OutArgs>(st.args);
             a.x = (const int32_t*)fp(T[st.src_t].forms[st.src_f]); a.N = N;
-            a.out = (char*)output + (size_t)n0 * a.C * a.HW * 4; a.err = chain_err; a.epoch = net->epoch;
-            e = launch_output(a, s);
+            char* const buf = st.out_k ? (char*)net->run_bufs[st.out_k - 1] : (char*)output;
+            a.out = buf + (size_t)n0 * a.C * a.HW * 4; a.err = chain_err; a.epoch = net->epoch;
+            e = st.inst ? launch_tap(a, s) : launch_output(a, s);
             break;
         }
     }
@@ -3271,8 +3320,15 @@ static int run_common(f8_net* net, const int32_t* input, void* output, int N, vo
     // the one-shot event is consumed by THIS call whatever happens next: a run that fails validation must not leave it armed for a
     // later, unrelated run (by then the caller's event may be gone)
     hipEvent_t in_ready = nullptr;
-    if (net) { in_ready = net->input_ready; net->input_ready = nullptr; }
+    bool have_bufs = false;            // ... and so are the buffers of outputs 1 .. (f8_net_set_output_buffers)
+    if (net) {
+        in_ready = net->input_ready; net->input_ready = nullptr;
+        have_bufs = net->out_bufs_set; net->out_bufs_set = false;
+        if (have_bufs) memcpy(net->run_bufs, net->out_bufs, sizeof net->run_bufs);
+    }
     if (!net || !net->finalized) return fail(F8_ERR_STATE, "f8_net_run: not finalized");
+    if (net->outs.size() > 1 && !have_bufs)
+        return fail(F8_ERR_STATE, "f8_net_run: this net has %d outputs: hand over the buffers of outputs 1 .. with f8_net_set_output_buffers before every run", (int)net->outs.size());
     if (N < 1 || N > net->max_batch) return fail(F8_ERR_INVALID, "f8_net_run: N=%d outside [1,%d]", N, net->max_batch);
     if (!input || !output) return fail(F8_ERR_INVALID, "f8_net_run: null pointer");
     int rc = f8_net_upload(net);
@@ -3429,7 +3485,7 @@ static int run_common(f8_net* net, const int32_t* input, void* output, int N, vo
         if (gs != user_s) { (void)hipEventRecord(net->aux_ev[4], gs); (void)hipStreamWaitEvent(user_s, net->aux_ev[4], 0); }
         return F8_OK;
     };
-    if (use_graph && parts <= 3 && !net->in_f32 && !net->in_u8) {
+    if (use_graph && parts <= 3 && !net->in_f32 && !net->in_u8 && net->outs.size() == 1) {      // (the replay key knows one output buffer: a multi-output handle runs plain launches)
         const bool same = net->g_in == input && net->g_out == output && net->g_N == N && net->g_stream == user_s;
         if (same && net->g_exec) return graph_replay();
         if (!same) {

@@ -130,16 +130,18 @@ class IntModel(nn.Module):
         self._head_fl = None
         return super()._apply(fn, *args, **kwargs)
 
-    def plan(self, hw: int, max_batch: int, device=None):
+    def plan(self, hw: int, max_batch: int, device=None, taps=()):
         """The planned net for hw x hw inputs on `device` (a handle is bound to one device).  Re-planned when the batch
-        capacity grows or any parameter was edited in place since the plan was built."""
+        capacity grows or any parameter was edited in place since the plan was built.  taps: names of further outputs
+        (net.record_net); every tuple of names is a plan of its own."""
         dev = None if device is None else torch.device(device).index
-        key = (dev, hw)
+        taps = tuple(taps)
+        key = (dev, hw, taps) if taps else (dev, hw)
         ver = self._param_version()
         ent = self._plans.get(key)
         if ent is None or ent[0] != ver or ent[1].max_batch < max_batch:
             opts = {'whole_batch_launches': 1, 'arena_copies': self._depth, 'pipeline_depth': self._depth} if self._pipelined == 2 else None
-            net = build_net(self.spec, self.state_dict(), max_batch, hw, options=opts)
+            net = build_net(self.spec, self.state_dict(), max_batch, hw, options=opts, taps=taps)
             if self._pipelined:
                 net.set_pipelined(self._pipelined)
             ent = (ver, net)
@@ -169,10 +171,10 @@ class IntModel(nn.Module):
         for _, net in self._plans.values():
             net.set_pipelined(self._pipelined)
 
-    def _check_pipelined(self, out):
-        if self._pipelined and out is None:
-            raise ValueError('IntModel: pipelined mode needs a caller-owned, rotating `out=` buffer (a fresh allocation could recycle a block '
-                             'that an in-flight run still writes); see IntModel.set_pipelined')
+    def _check_pipelined(self, out, outs=()):
+        if self._pipelined and (out is None or outs is None):
+            raise ValueError('IntModel: pipelined mode needs caller-owned, rotating buffers — `out=`, and `outs=` for the taps of forward_features — '
+                             '(a fresh allocation could recycle a block that an in-flight run still writes); see IntModel.set_pipelined')
 
     def forward(self, x, out=None, input_ready=None):
         if not hasattr(x, 'output_fraclen'):
@@ -183,6 +185,29 @@ class IntModel(nn.Module):
         assert x.shape[2] == x.shape[3], 'square inputs'
         self._check_pipelined(out)
         return self.plan(int(x.shape[2]), int(x.shape[0]), x.device).run(x.contiguous(), out=out, input_ready=input_ready)
+
+    def forward_features(self, x, taps, out=None, outs=None, input_ready=None):
+        """`forward` that also returns intermediate tensors: (logits, {name: int32 tensor [N,C,H,W] tagged `.output_fraclen`}) for the names
+        in `taps` (net.record_net: block names — the stage outputs a detection or segmentation head consumes —, conv keys, 'head.maxpool',
+        'avgpool' = the embedding in front of the classifier).  One run; the plan is cached per (device, input size, taps).  outs: caller
+        buffers of the taps, in order (pipelined mode needs them, as it needs `out`)."""
+        if not hasattr(x, 'output_fraclen'):
+            raise ValueError('IntModel.forward_features: input must carry `output_fraclen` (fix_train.py:687,692)')
+        head_fl = self._head_fraclen()
+        if x.output_fraclen != head_fl:
+            raise ValueError(f'input output_fraclen {x.output_fraclen} != head.input_fraclen {head_fl}')
+        assert x.shape[2] == x.shape[3], 'square inputs'
+        taps = tuple(taps)
+        self._check_pipelined(out, outs if taps else ())
+        net = self.plan(int(x.shape[2]), int(x.shape[0]), x.device, taps=taps)
+        res = net.run(x.contiguous(), out=out, input_ready=input_ready, outs=outs)
+        if not taps:
+            return res, {}
+        feats = {}
+        for name, t, info in zip(taps, res[1:], net.outputs[1:]):
+            setattr(t, 'output_fraclen', info[3])
+            feats[name] = t
+        return res[0], feats
 
     def forward_f32(self, images, normalize=False, out=None, input_ready=None):
         """forward_loss's input quantisation (fix_train.py:683-692) fused into the input kernel: `images` is the

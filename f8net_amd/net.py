@@ -31,6 +31,9 @@ class F8Net:
         self.out_elems = 0
         self.out_float = True
         self.in_shape = None
+        self.outputs = []       # after finalize: (C, H, W, fraclen, as_float) of every output, in the order of the output() calls
+        self.tap_ids = {}       # record_net: name -> tensor id of everything `taps=` accepts
+        self.taps = ()          # record_net: the names marked as outputs 1 .., in that order
 
     def __del__(self):
         h, self._h = getattr(self, '_h', None), None
@@ -88,14 +91,25 @@ class F8Net:
         return t
 
     def output(self, src, as_float=True):
-        self.out_float = bool(as_float)
-        check(self._L.f8_net_output(self._h, src, int(self.out_float)))
+        """Marks tensor `src` as a network output (f8_net_output) and returns its index.  The first call names output 0, which the
+        run methods return as today; every further call adds an output that they return behind it, shaped [N, C, H, W]."""
+        k = check(self._L.f8_net_output(self._h, src, int(bool(as_float))))
+        if k == 0:
+            self.out_float = bool(as_float)
+        return k
 
     def finalize(self, max_batch):
         check(self._L.f8_net_finalize(self._h, int(max_batch)))
         self.max_batch = int(max_batch)
         self.out_elems = int(self._L.f8_net_output_elems(self._h))
+        self.outputs = [self.output_info(k) for k in range(check(self._L.f8_net_num_outputs(self._h)))]
         return self
+
+    def output_info(self, k):
+        """(C, H, W, fraclen, as_float) of output k (f8_net_output_info)."""
+        v = [ctypes.c_int(0) for _ in range(5)]
+        check(self._L.f8_net_output_info(self._h, int(k), *[ctypes.byref(x) for x in v]))
+        return tuple(x.value for x in v[:4]) + (bool(v[4].value),)
 
     # ---- introspection ----------------------------------------------------------------------
     def describe(self) -> str:
@@ -181,8 +195,31 @@ class F8Net:
         if ev is not None:
             check(self._L.f8_net_set_input_ready(self._h, ctypes.c_void_p(ev.cuda_event)))
 
-    def run(self, x, out=None, input_ready=None):
-        """x: int32 CUDA tensor [N,C,H,W] (reference input format).  Returns [N, out_elems].
+    def _output_buffers(self, N, device, outs):
+        """Hands the buffers of outputs 1 .. to the next run (f8_net_set_output_buffers; allocated when `outs` is None) and returns them
+        shaped [N, C, H, W].  A single-output net has none."""
+        import torch
+        extra = self.outputs[1:]
+        if not extra:
+            if outs:
+                raise ValueError('F8Net: outs= given, but the net has a single output')
+            return []
+        if outs is None:
+            outs = [torch.empty((N, C, H, W), dtype=torch.float32 if f else torch.int32, device=device) for C, H, W, _, f in extra]
+        if len(outs) != len(extra):
+            raise ValueError(f'F8Net: {len(outs)} buffers for outputs 1 .. {len(extra)}')
+        res = []
+        for o, (C, H, W, _, f) in zip(outs, extra):
+            if o.device != device or o.dtype != (torch.float32 if f else torch.int32) or not o.is_contiguous() or o.numel() != N * C * H * W:
+                raise ValueError(f'F8Net: an output buffer must be a contiguous {"float32" if f else "int32"} tensor of [{N},{C},{H},{W}] on {device}')
+            res.append(o.view(N, C, H, W))
+        ptrs = (ctypes.c_void_p * len(res))(*[o.data_ptr() for o in res])
+        check(self._L.f8_net_set_output_buffers(self._h, ptrs, len(res)))
+        return res
+
+    def run(self, x, out=None, input_ready=None, outs=None):
+        """x: int32 CUDA tensor [N,C,H,W] (reference input format).  Returns [N, out_elems]; a net with more than one output returns the
+        tuple (output 0, output 1, ...), the further ones shaped [N,C,H,W] (outs: their buffers, allocated when None).
         input_ready: torch.cuda.Event recorded behind the producer of `x` when that is another stream (pipelined callers)."""
         import torch
         self._check_input(x)
@@ -192,9 +229,10 @@ class F8Net:
                               device=x.device)
         stream = torch.cuda.current_stream(x.device).cuda_stream
         with torch.cuda.device(x.device):
+            outs = self._output_buffers(N, x.device, outs)      # (may raise: before the one-shot event is armed)
             self._input_ready(input_ready)
             check(self._L.f8_net_run(self._h, x.data_ptr(), out.data_ptr(), N, ctypes.c_void_p(stream)))
-        return out
+        return (out, *outs) if outs else out
 
     def check(self):
         """Synchronise the device and raise if a kernel of an earlier run reported a failure (f8_net_check)."""
@@ -216,7 +254,7 @@ class F8Net:
         mode = 2 if on in (2, 'alternate') else int(bool(on))
         check(self._L.f8_net_set_pipelined(self._h, mode))
 
-    def run_f32(self, images, normalize, out=None, input_ready=None):
+    def run_f32(self, images, normalize, out=None, input_ready=None, outs=None):
         """images: float32 CUDA tensor [N,C,H,W] as forward_loss receives them (fix_train.py:676-692); the input
         quantisation runs inside the input kernel.  normalize: FLAGS.normalize of the reference."""
         import torch
@@ -234,12 +272,13 @@ class F8Net:
                               device=images.device)
         stream = torch.cuda.current_stream(images.device).cuda_stream
         with torch.cuda.device(images.device):
+            outs = self._output_buffers(N, images.device, outs)
             self._input_ready(input_ready)
             check(self._L.f8_net_run_f32(self._h, images.data_ptr(), int(bool(normalize)), out.data_ptr(), N,
                                          ctypes.c_void_p(stream)))
-        return out
+        return (out, *outs) if outs else out
 
-    def run_u8(self, images, normalize=False, mean=None, std=None, nhwc=False, out=None, input_ready=None):
+    def run_u8(self, images, normalize=False, mean=None, std=None, nhwc=False, out=None, input_ready=None, outs=None):
         """images: uint8 CUDA tensor, NCHW [N,3,H,W] (or NHWC [N,H,W,3] with nhwc=True) as a decoder yields them; ToTensor /
         Normalize(mean, std) / the input quantisation of forward_loss are a table lookup inside the input kernel (f8_net_run_u8)."""
         import torch
@@ -260,12 +299,13 @@ class F8Net:
         s = (ctypes.c_float * 3)(*[float(v) for v in std]) if std is not None else None
         stream = torch.cuda.current_stream(images.device).cuda_stream
         with torch.cuda.device(images.device):
+            outs = self._output_buffers(N, images.device, outs)
             self._input_ready(input_ready)
             check(self._L.f8_net_run_u8(self._h, images.data_ptr(), int(bool(nhwc)), int(bool(normalize)), m, s, out.data_ptr(), N,
                                         ctypes.c_void_p(stream)))
-        return out
+        return (out, *outs) if outs else out
 
-    def run_profiled(self, x, out=None):
+    def run_profiled(self, x, out=None, outs=None):
         """Like run(); also returns per-launch milliseconds (HIP events on the launch stream)."""
         import torch
         self._check_input(x)
@@ -277,9 +317,10 @@ class F8Net:
         ms = (ctypes.c_float * n)()
         stream = torch.cuda.current_stream(x.device).cuda_stream
         with torch.cuda.device(x.device):
+            outs = self._output_buffers(N, x.device, outs)
             check(self._L.f8_net_run_profiled(self._h, x.data_ptr(), out.data_ptr(), N,
                                               ctypes.c_void_p(stream), ms, n))
-        return out, [float(v) for v in ms]
+        return ((out, *outs) if outs else out), [float(v) for v in ms]
 
 
 def _fl(params, key, name):
@@ -287,18 +328,26 @@ def _fl(params, key, name):
 
 
 def build_net(spec: topology.NetSpec, params: dict, max_batch: int, hw: int = 224,
-              input_fraclen=None, options=None) -> F8Net:
+              input_fraclen=None, options=None, taps=()) -> F8Net:
     """Record IntModel.forward for `spec` with exported parameters `params` (numpy or torch-cpu
     tensors keyed like the reference state_dict) and plan it for batches up to max_batch.
-    options: {key: value} for f8_net_set_option, applied before planning."""
-    net = record_net(spec, params, hw, input_fraclen)
+    options: {key: value} for f8_net_set_option, applied before planning.  taps: see record_net."""
+    net = record_net(spec, params, hw, input_fraclen, taps=taps)
     for k, v in (options or {}).items():
         net.set_option(k, v)
     return net.finalize(max_batch)
 
 
-def record_net(spec: topology.NetSpec, params: dict, hw: int = 224, input_fraclen=None) -> F8Net:
-    """The recording half of build_net: the graph is in the handle, not yet planned (set planning options, then finalize)."""
+def record_net(spec: topology.NetSpec, params: dict, hw: int = 224, input_fraclen=None, taps=()) -> F8Net:
+    """The recording half of build_net: the graph is in the handle, not yet planned (set planning options, then finalize).
+
+    taps: names of further tensors to return, marked as int32 outputs 1, 2, ... in the order given (output 0 stays the float
+    logits).  A name is a block name (`stage_1_layer_3`: the block's output tensor, whether or not the block ends in a join), a
+    conv key (`stage_1_layer_3.body.0`, `head.0`, `tail.0`), 'head.maxpool' or 'avgpool' (the pooled vector in front of the
+    classifier, at the last map's fraclen + 6).  A conv key names the tensor BEHIND that conv's ReLU, as a tensor id does everywhere
+    in the C ABI; the CPU oracle's `tap=` callback reports a conv before its in-place ReLU, so a comparison applies `oracle.relu`
+    where `ConvSpec.relu` is set.  An unknown name raises ValueError with the valid ones; the name -> tensor id map of everything
+    that can be tapped is kept as `net.tap_ids`, the names given as `net.taps`."""
     params = {k: (v.detach().cpu().numpy() if hasattr(v, 'detach') else np.asarray(v)) for k, v in params.items()}
     net = F8Net()
     head_in_fl = _fl(params, spec.head.key, 'input_fraclen')
@@ -308,16 +357,19 @@ def record_net(spec: topology.NetSpec, params: dict, hw: int = 224, input_fracle
         raise ValueError(f'network input fraclen {input_fraclen} != head.input_fraclen {head_in_fl}: the reference '
                          f'feeds the head conv head-format integers without requantising (fix_resnet.py:356-358)')
 
+    ids = net.tap_ids
+
     def conv(src, c: topology.ConvSpec, quant_input=True):
-        return net.conv(src, params[c.key + '.weight'], params[c.key + '.bias'], stride=c.stride, pad=c.pad,
-                        groups=c.groups, weight_fl=_fl(params, c.key, 'weight_fraclen'),
-                        input_fl=_fl(params, c.key, 'input_fraclen'), input_signed=c.signed_in,
-                        quant_input=quant_input, relu=c.relu, label=c.key)
+        ids[c.key] = net.conv(src, params[c.key + '.weight'], params[c.key + '.bias'], stride=c.stride, pad=c.pad,
+                              groups=c.groups, weight_fl=_fl(params, c.key, 'weight_fraclen'),
+                              input_fl=_fl(params, c.key, 'input_fraclen'), input_signed=c.signed_in,
+                              quant_input=quant_input, relu=c.relu, label=c.key)
+        return ids[c.key]
 
     t = net.input(3, hw, hw, input_fraclen)
     t = conv(t, spec.head, quant_input=False)                    # fix_resnet.py:356-358
     if spec.head_maxpool:
-        t = net.maxpool(t, 3, 2, 1, label='head.maxpool')        # fix_resnet.py:359
+        t = ids['head.maxpool'] = net.maxpool(t, 3, 2, 1, label='head.maxpool')        # fix_resnet.py:359
     for b in spec.blocks:                                        # IntBlock.forward, fix_resnet.py:26-77
         x = t
         r = x
@@ -328,12 +380,19 @@ def record_net(spec: topology.NetSpec, params: dict, hw: int = 224, input_fracle
             r = net.add(r, sx, relu=b.post_relu, label=b.name)
         elif b.residual:
             r = net.add(r, x, relu=b.post_relu, label=b.name)
-        t = r
+        t = ids[b.name] = r
     if spec.tail is not None:                                    # fix_mobilenet_v2.py:218-224
         t = conv(t, spec.tail)
-    t = net.avgpool_sum(t, AVGPOOL_SHIFT, label='avgpool')       # fix_quant_ops.py:126-134
+    t = ids['avgpool'] = net.avgpool_sum(t, AVGPOOL_SHIFT, label='avgpool')       # fix_quant_ops.py:126-134
     k = spec.fc_key
     t = net.linear(t, params[k + '.weight'], params[k + '.bias'], weight_fl=_fl(params, k, 'weight_fraclen'),
                    input_fl=_fl(params, k, 'input_fraclen'), input_signed=spec.fc_signed_in, label=k)
     net.output(t, as_float=True)                                 # `.float()`, fix_resnet.py:383
+    taps = tuple(taps)
+    unknown = [n for n in taps if n not in ids]
+    if unknown:
+        raise ValueError(f'record_net: unknown tap name(s) {unknown}; valid names: {", ".join(ids)}')
+    for n in taps:
+        net.output(ids[n], as_float=False)
+    net.taps = taps
     return net

@@ -14,6 +14,7 @@ the dispatcher.
     f8net::avgpool_sum(x)                            FXQAvgPool2d int branch          fix_quant_ops.py:126-134
     f8net::maxpool(x, k, stride, pad)                head max-pool                    fix_resnet.py:358-359
     f8net::net_forward(x, handle)                    IntModel.forward                 fix_resnet.py:352-383 (handle: register_net)
+    f8net::net_forward_taps(x, handle)               ... of a net with further outputs (F8Net.output called more than once): all of them
     f8net::net_forward_f32(images, handle, normalize)  forward_loss input quantisation + IntModel.forward, fix_train.py:683-692
 
 conv2d / linear plan a one-node net per (weight tensor, its in-place version, geometry, input shape, device) and cache it
@@ -41,6 +42,7 @@ _DEF.define('linear(Tensor x, Tensor weight, Tensor? bias, int weight_fl, int in
 _DEF.define('avgpool_sum(Tensor x) -> Tensor')
 _DEF.define('maxpool(Tensor x, int k, int stride, int pad) -> Tensor')
 _DEF.define('net_forward(Tensor x, int handle) -> Tensor')
+_DEF.define('net_forward_taps(Tensor x, int handle) -> Tensor[]')
 _DEF.define('net_forward_f32(Tensor images, int handle, bool normalize) -> Tensor')
 
 
@@ -245,6 +247,11 @@ def _net_forward(x, handle):
     return _nets[handle].run(x.contiguous())
 
 
+def _net_forward_taps(x, handle):
+    res = _nets[handle].run(x.contiguous())
+    return list(res) if isinstance(res, tuple) else [res]
+
+
 def _net_forward_f32(images, handle, normalize):
     return _nets[handle].run_f32(images.contiguous(), normalize)
 
@@ -252,7 +259,8 @@ def _net_forward_f32(images, handle, normalize):
 # ------------------------------------------------------------------------------------------ registration
 _CUDA = Library('f8net', 'IMPL', 'CUDA')
 for _n, _f in (('requant', _requant), ('relu_', _relu_), ('add_align_', _add_align_), ('conv2d', _conv2d), ('linear', _linear),
-               ('avgpool_sum', _avgpool_sum), ('maxpool', _maxpool), ('net_forward', _net_forward), ('net_forward_f32', _net_forward_f32)):
+               ('avgpool_sum', _avgpool_sum), ('maxpool', _maxpool), ('net_forward', _net_forward), ('net_forward_taps', _net_forward_taps),
+               ('net_forward_f32', _net_forward_f32)):
     _CUDA.impl(_n, _f)
 
 _META = Library('f8net', 'IMPL', 'Meta')
@@ -267,5 +275,7 @@ _META.impl('maxpool', lambda x, k, stride, pad: x.new_empty(
     (x.shape[0], x.shape[1], (x.shape[2] + 2 * pad - k) // stride + 1, (x.shape[3] + 2 * pad - k) // stride + 1)))
 _META.impl('net_forward', lambda x, handle: x.new_empty((x.shape[0], _nets[handle].out_elems),
                                                         dtype=torch.float32 if _nets[handle].out_float else torch.int32))
+_META.impl('net_forward_taps', lambda x, handle: [x.new_empty((x.shape[0], _nets[handle].out_elems), dtype=torch.float32 if _nets[handle].out_float else torch.int32)] + [
+    x.new_empty((x.shape[0], C, H, W), dtype=torch.float32 if f else torch.int32) for C, H, W, _, f in _nets[handle].outputs[1:]])
 _META.impl('net_forward_f32', lambda x, handle, normalize: x.new_empty((x.shape[0], _nets[handle].out_elems),
                                                                       dtype=torch.float32 if _nets[handle].out_float else torch.int32))

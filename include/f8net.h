@@ -143,9 +143,21 @@ int f8_net_avgpool_sum(f8_net* net, int src, int shift);
 int f8_net_linear(f8_net* net, int src, const f8_linear_desc* desc,
                   const int32_t* weight_host, const int32_t* bias_host);
 
-/* Marks `src` as the (single) network output.  as_float != 0: float32 (the `.float()` of
- * fix_resnet.py:383), else int32.  Layout NCHW [N,C,H,W] ([N,C] for pooled / linear results). */
+/* Marks `src` as a network output; may be called up to F8_MAX_OUTPUTS times before f8_net_finalize, on any tensor of the graph
+ * (a stage output for a detection head, the pooled vector in front of the classifier, any conv's result for a comparison with
+ * the reference).  Returns the output's index: 0 for the first call (the same value as F8_OK), 1, 2, ... for the next ones.
+ * F8_ERR_INVALID for a tensor that is an output already, F8_ERR_UNSUPPORTED for one output too many, F8_ERR_STATE after finalize.
+ * as_float != 0: float32 (the `.float()` of fix_resnet.py:383), else int32; every output has its own.  Layout NCHW [N,C,H,W]
+ * ([N,C] for pooled / linear results).  Output 0 is what the `output_dev` of the run entries receives; the others go to the
+ * buffers of f8_net_set_output_buffers.  Every output exists in device memory as int32: a fused launch that would keep the
+ * tensor on chip is cut there (a tap inside a stage chain makes two launches of it, an output on the pooled tensor keeps the
+ * pool out of the launch in front of it), and each further output adds one copy-out launch directly behind its producer. */
+#define F8_MAX_OUTPUTS 8
 int f8_net_output(f8_net* net, int src, int as_float);
+/* Number of outputs marked so far. */
+int f8_net_num_outputs(const f8_net* net);
+/* Shape, fraclen and element type of output k (0 <= k < f8_net_num_outputs); any out-pointer may be NULL. */
+int f8_net_output_info(const f8_net* net, int k, int* C, int* H, int* W, int* fraclen, int* as_float);
 
 /* Plans the graph for batches up to max_batch: fuses requant / ReLU / residual into producer
  * epilogues, picks kernels and tiles, packs weights (host side), lays out the arena.
@@ -157,8 +169,9 @@ size_t f8_net_describe(const f8_net* net, char* buf, size_t cap);
 int f8_net_num_launches(const f8_net* net);
 size_t f8_net_arena_bytes(const f8_net* net);
 size_t f8_net_weight_bytes(const f8_net* net);
+/* Fraclen of output 0. */
 int f8_net_output_fraclen(const f8_net* net);
-/* Output element count per image (C*H*W of the output tensor). */
+/* Element count per image of output 0 (C*H*W of the output tensor). */
 size_t f8_net_output_elems(const f8_net* net);
 
 /* Allocates device memory on the current device and uploads packed weights.  Implicit in the
@@ -219,6 +232,15 @@ int f8_net_set_pipelined(f8_net* net, int on);
  * One-shot: consumed by the next run. */
 int f8_net_set_input_ready(f8_net* net, void* event);
 
+/* Device buffers of outputs 1 .. n of a net with more than one output: bufs_dev[k - 1] receives output k, NCHW [N,C,H,W],
+ * int32 or float32 as its f8_net_output asked, as output_dev receives output 0.  n must be f8_net_num_outputs - 1
+ * (F8_ERR_INVALID otherwise, and for a NULL buffer; a single-output net accepts n == 0 with any bufs_dev, which changes nothing).  One-shot, like f8_net_set_input_ready: the next run — any of f8_net_run,
+ * _run_f32, _run_u8, _run_profiled — consumes the buffers, and a run of a multi-output net that was not given its buffers
+ * returns F8_ERR_STATE without issuing anything.  Under f8_net_set_pipelined the caller's promise covers these buffers too:
+ * one call of slack.  Option graph = 1: the replay key is (input, output, N, stream) and knows one output buffer, so a handle
+ * with more than one output does not capture and runs plain launches. */
+int f8_net_set_output_buffers(f8_net* net, void* const* bufs_dev, int n);
+
 /* Blocks until the device is idle and reports failures that happened INSIDE kernels of earlier runs of this handle: the
  * stage-chain launches (option fuse_chain) exchange halo rows between workgroups and bound every wait (chain_timeout_ms); a
  * workgroup whose neighbour never arrives stores (run tag << 8 | code) in an error word, the launch runs on without waiting, and THAT run's
@@ -252,7 +274,10 @@ int f8_net_check(f8_net* net);
  *               v_ashr_pk_u8_i32; no float instruction in any epilogue; 1: a ReLU -> unsigned-8-bit right shift (1..16) of a value the PLANNER
  *               CAN BOUND — conv accumulators, the int32 stream of a chain launch — runs through the float converter: v_cvt_f32_i32, v_mul_f32
  *               by 2^-n, v_cvt_pk_u8_f32: exact, compared with the reference's arithmetic over all 2^32 inputs on the device; anything
- *               unbounded takes the integer form by itself.  Same results either way, bit for bit)
+ *               unbounded takes the integer form by itself.  Same results either way, bit for bit),
+ *               tap_tiled (default 1: the copy-out launches of outputs 1 .. run f8::tap_kernel, f8_tap.hip — one wave per 4 KB block of the
+ *               int32 source, every loaded byte used; 0: f8::output_kernel, which walks the destination.  Output 0 always leaves through
+ *               output_kernel or the classifier itself.  Same values either way)
  *   scheduling: chunk56 / chunk28 / chunk14 (images per chunk of the fused blocks; -1 = derived from chunk_budget_mb, 0 = whole
  *               batch), chunk_budget_mb (memory-side cache a chunk's int32 stream may occupy), chunk_ds, chunk_opener,
  *               split_streams, graph, stagger, stagger_pipelined, stem_wpc, stem_grid_div (row-walking head on 1 / n of the CUs; 0 = by output form), check_device, check_input_range, pipeline_depth (2..4 runs in flight),

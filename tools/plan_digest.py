@@ -33,7 +33,7 @@ PLANNING = {
     'fuse_bchain7': (0, 2), 'chain_stack': (0, 1), 'wreg': (0, 1), 's2wreg': (0, 1), 'wstat': (0, 1), 'wstat_min_tiles': (0, 1 << 20),
     'wstat_fast': (0, 1), 'patch3x3': (0, 1), 'dual_wide': (0, 1 << 30), 'deep_nk': (1, 1 << 20), 'bk128': (0, 1), 'dw_dot4': (0, 1),
     'dw_mma': (0, 1), 'stem_rows': (0, 1), 'opener_stg': (0, 1), 'requant_float': (0, 1), 'arena_copies': (0, 4), 'shared_streams': (0, 1),
-    'whole_batch_launches': (0, 1),
+    'whole_batch_launches': (0, 1), 'tap_tiled': (0, 1),
 }
 
 

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Which kernels do the DEFAULT plans of the four nets reach?  Planning needs no GPU:
     python tools/reach.py            -> markdown table (kernel symbol x net / batch), used by DESIGN.md §4
-Batches 1 / 8 / 128 / 256 at 224x224; 128 and 256 also with `whole_batch_launches` (what bench.py plans under pipelining mode 2)."""
+Batches 1 / 8 / 128 / 256 at 224x224; 128 and 256 also with `whole_batch_launches` (what bench.py plans under pipelining mode 2); `t` = batch 128
+planned with further outputs (`taps=`: the last block of the last four stages and 'avgpool') — the only plans that reach `tap_kernel`."""
 import os
 import re
 import sys
@@ -11,7 +12,7 @@ from f8net_amd import synth, topology        # noqa: E402
 from f8net_amd.net import build_net          # noqa: E402
 
 NETS = ['resnet50', 'resnet18', 'mobilenet_v2', 'mobilenet_v1']
-CASES = [(1, 0), (8, 0), (128, 0), (128, 1), (256, 1)]
+CASES = [(1, 0, 0), (8, 0, 0), (128, 0, 0), (128, 1, 0), (256, 1, 0), (128, 0, 1)]      # batch, whole_batch_launches, taps
 
 
 def family(sym):
@@ -23,8 +24,11 @@ def main():
     for arch in NETS:
         spec = topology.get(arch, normalize=(arch == 'resnet50'))
         params = synth.reference_params(spec, seed=1234)
-        for bs, whole in CASES:
-            net = build_net(spec, params, max_batch=bs, hw=224, options={'whole_batch_launches': 1} if whole else None)
+        stages = {b.name.rsplit('_layer_', 1)[0]: b.name for b in spec.blocks}
+        for bs, whole, tapped in CASES:
+            net = build_net(spec, params, max_batch=bs, hw=224, options={'whole_batch_launches': 1} if whole else None,
+                            taps=list(stages.values())[-4:] + ['avgpool'] if tapped else ())
+            whole = 'w' if whole else ('t' if tapped else '')
             for i in range(net.num_launches):
                 k = net.launch_kernel(i)
                 if k:
@@ -38,8 +42,8 @@ def main():
         where = {}
         for _, v in inst:
             for arch, bs, whole in v:
-                where.setdefault(arch, set()).add(f'{bs}{"w" if whole else ""}')
-        txt = '; '.join(f'{a}: {", ".join(sorted(b, key=lambda x: (int(x.rstrip("w")), x)))}' for a, b in sorted(where.items()))
+                where.setdefault(arch, set()).add(f'{bs}{whole}')
+        txt = '; '.join(f'{a}: {", ".join(sorted(b, key=lambda x: (int(x.rstrip("wt")), x)))}' for a, b in sorted(where.items()))
         print(f'| `{f}` | {len(inst)} | {txt} |')
     if '-v' in sys.argv:
         for f in sorted(fams):
