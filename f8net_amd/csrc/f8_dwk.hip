@@ -1,0 +1,195 @@
+// f8_dwk.hip — general depthwise convolution (gfx950): square kernels 3 / 5 / 7, stride 1 / 2, any pad up to K / 2 — everything depthwise that
+// is not the 3x3 / pad 1 of f8_kernels.hip / f8_dwmma.hip, which keeps its own kernels.  VALU; a launch of its own (S_DW, f8_net.cpp).
+//
+// Both kernels work in the stored domain of the 3x3 kernels: NHWC int8 with channel stride Cs (a multiple of 32); unsigned tensors are stored
+// biased (x ^ 0x80); wrapping int32 accumulation; optional ReLU floor; up to two int8 forms (QuantOut) and / or the tiled int32 form.
+//
+//   dwconvk_kernel<SIGNED_IN>     K, stride, pad at run time; one thread = one output pixel x 4 channels; bytes extracted and multiplied one by
+//                                 one (unsigned inputs as unsigned bytes: out-of-image taps are skipped, plain bias).  Writes any form.  The
+//                                 correctness anchor, and what runs when a launch writes the int32 form or option dwk_dot4 is 0.
+//   dwconvk_dot4_kernel<K, S>     int8 forms only, on v_dot4_i32_i8.  One thread = 4 channels (one dword per tap) x DWK_PIX adjacent output pixels
+//                                 of one row.  A dot4 reduces over four ROWS of one input column: the thread walks the (DWK_PIX - 1) * S + K input
+//                                 columns of its pixels once, loads the K dwords of a column, byte-transposes rows 4g .. 4g + 3 into one dword per
+//                                 channel (8 v_perm_b32 per group of four rows; a last group of ONE row — K = 5 — is three shifts: its other three
+//                                 byte slots meet zero weights and may hold anything) and feeds each transposed column to every pixel whose window
+//                                 holds it — up to K of them at stride 1 —, 4 x ceil(K / 4) dot4 each.  Per output value of 4 channels at stride 1:
+//                                 K = 5: 40 dot4 + 22 transposing operations for 100 multiply-adds; K = 7: 56 + 40 for 196 (the 3x3 tap-raster kernel:
+//                                 8 + 8 + 4 for 36).  Out-of-image taps are the biased zero (a real 0 for signed inputs) and 128 * sum(w) sits in
+//                                 the bias, as in dwconv3x3_dot4_kernel.  Weights: pack_dwk_weights' image (f8_net.cpp),
+//                                 [Cs / 4][K columns][G = ceil(K / 4) row groups][4 channels] dwords, byte j of a dword = row 4g + j (0 beyond K).
+#include "f8_device.h"
+#include <algorithm>
+
+namespace f8 {
+
+namespace {
+constexpr int DWK_PIX = 4;                          // adjacent output pixels per thread of the dot4 kernel
+}
+
+template <bool SIGNED_IN>
+__global__ void __launch_bounds__(256) dwconvk_kernel(const DwArgs a) {
+    const int cgs = a.Cs >> 2;
+    const size_t total = (size_t)a.N * a.P * a.Q * cgs;
+    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
+         idx += (size_t)gridDim.x * blockDim.x) {
+        const int cg = (int)(idx % cgs);
+        size_t m = idx / cgs;
+        const int q = (int)(m % a.Q); m /= a.Q;
+        const int p = (int)(m % a.P);
+        const int n = (int)(m / a.P);
+        const int c = cg << 2;
+        int acc[4];
+        {
+            const v4i b = *(const v4i*)(a.bias + c);
+            acc[0] = b.x; acc[1] = b.y; acc[2] = b.z; acc[3] = b.w;
+        }
+        const int h0 = p * a.stride - a.pad, w0 = q * a.stride - a.pad;
+        const unsigned in_xor = SIGNED_IN ? 0u : 0x80808080u;   // unsigned tensors are stored biased
+        for (int r = 0; r < a.k; ++r) {
+            const int h = h0 + r;
+            if ((unsigned)h >= (unsigned)a.H) continue;
+            for (int s = 0; s < a.k; ++s) {
+                const int w = w0 + s;
+                if ((unsigned)w >= (unsigned)a.W) continue;
+                const unsigned xv = *(const unsigned*)(a.x + (((size_t)n * a.H + h) * a.W + w) * a.Cs + c) ^ in_xor;
+                const unsigned wv = *(const unsigned*)(a.w + (size_t)(r * a.k + s) * a.Cs + c);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int xe = SIGNED_IN ? (int)(signed char)(xv >> (8 * e)) : (int)((xv >> (8 * e)) & 0xffu);
+                    const int we = (int)(signed char)(wv >> (8 * e));
+                    acc[e] = (int)((unsigned)acc[e] + (unsigned)(xe * we));
+                }
+            }
+        }
+        if (a.relu0) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc[e] = max(acc[e], 0);
+        }
+        const int mo = (n * a.P + p) * a.Q + q;
+        const size_t o = (size_t)mo * a.Cs + c;
+        if (a.out32) { v4i v = {acc[0], acc[1], acc[2], acc[3]}; *(v4i*)(a.out32 + i32t_index(mo, c, a.Cs)) = v; }
+#pragma unroll
+        for (int k = 0; k < 2; ++k)
+            if (a.q[k].ptr)
+                *(unsigned*)(a.q[k].ptr + o) =
+                    pack4(requant1(acc[0], a.q[k].n, a.q[k].lo, a.q[k].hi), requant1(acc[1], a.q[k].n, a.q[k].lo, a.q[k].hi),
+                          requant1(acc[2], a.q[k].n, a.q[k].lo, a.q[k].hi), requant1(acc[3], a.q[k].n, a.q[k].lo, a.q[k].hi)) ^ a.q[k].bias_xor;
+    }
+}
+
+template <int K, int S>
+__global__ void __launch_bounds__(256) dwconvk_dot4_kernel(const DwArgs a) {
+    constexpr int PIX = DWK_PIX;
+    constexpr int NCOL = (PIX - 1) * S + K;          // input columns the thread's pixels read
+    constexpr int G = (K + 3) / 4;                   // groups of four rows
+    constexpr int LAST = K - 4 * (G - 1);            // rows of the last group: 3 (K = 3, 7) or 1 (K = 5)
+    static_assert(LAST == 1 || LAST == 3, "K is 3, 5 or 7");
+    const int cgs = a.Cs >> 2;                       // 4-channel quads
+    const int QS = (a.Q + PIX - 1) / PIX;
+    const size_t total = (size_t)a.N * a.P * QS * cgs;
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    const int cg = (int)(idx % cgs);
+    size_t st = idx / cgs;
+    const int qs = (int)(st % QS); st /= QS;
+    const int p = (int)(st % a.P);
+    const int n = (int)(st / a.P);
+    const int c = cg << 2, q0 = qs * PIX;
+    const unsigned padv = a.in_signed ? 0u : 0x80808080u;
+    const int h0 = p * S - a.pad, w0 = q0 * S - a.pad;
+    const unsigned* const wq = (const unsigned*)a.w + (size_t)cg * (K * G * 4);      // [column][group][channel]
+
+    int acc[PIX][4];
+    {
+        const v4i bv = *(const v4i*)(a.bias + c);
+#pragma unroll
+        for (int j = 0; j < PIX; ++j) { acc[j][0] = bv.x; acc[j][1] = bv.y; acc[j][2] = bv.z; acc[j][3] = bv.w; }
+    }
+    const int8_t* const xn = a.x + (size_t)n * a.H * a.W * a.Cs + c;
+#pragma unroll
+    for (int cc = 0; cc < NCOL; ++cc) {
+        const int w = w0 + cc;
+        const bool wok = (unsigned)w < (unsigned)a.W;
+        unsigned t[4 * G];                            // rows 0 .. K - 1 of this column, 4 channels each
+#pragma unroll
+        for (int r = 0; r < K; ++r) {
+            const int h = h0 + r;
+            unsigned v = padv;
+            if (wok && (unsigned)h < (unsigned)a.H) v = *(const unsigned*)(xn + ((size_t)h * a.W + w) * a.Cs);
+            t[r] = v;
+        }
+        unsigned col[G][4];                           // [row group][channel]: bytes = the group's four rows
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            if (g == G - 1 && LAST == 1) {            // one row: byte 0 is the row, the other slots meet zero weights
+                col[g][0] = t[4 * g]; col[g][1] = t[4 * g] >> 8; col[g][2] = t[4 * g] >> 16; col[g][3] = t[4 * g] >> 24;
+            } else {
+                const unsigned t0 = t[4 * g], t1 = t[4 * g + 1], t2 = t[4 * g + 2];
+                const unsigned t3 = (g == G - 1) ? t2 : t[4 * g + 3];                 // (three rows: slot 3 meets a zero weight)
+                const unsigned lo01 = __builtin_amdgcn_perm(t1, t0, 0x05010400u), hi01 = __builtin_amdgcn_perm(t1, t0, 0x07030602u);
+                const unsigned lo23 = __builtin_amdgcn_perm(t3, t2, 0x05010400u), hi23 = __builtin_amdgcn_perm(t3, t2, 0x07030602u);
+                col[g][0] = __builtin_amdgcn_perm(lo23, lo01, 0x05040100u); col[g][1] = __builtin_amdgcn_perm(lo23, lo01, 0x07060302u);
+                col[g][2] = __builtin_amdgcn_perm(hi23, hi01, 0x05040100u); col[g][3] = __builtin_amdgcn_perm(hi23, hi01, 0x07060302u);
+            }
+        }
+        // every pixel j whose window [j * S, j * S + K) holds column cc: kernel column s = cc - j * S
+#pragma unroll
+        for (int j = 0; j < PIX; ++j) {
+            const int s = cc - j * S;
+            if (s < 0 || s >= K) continue;
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                const v4i wv = *(const v4i*)(wq + (s * G + g) * 4);
+                acc[j][0] = __builtin_amdgcn_sdot4((int)col[g][0], wv.x, acc[j][0], false);
+                acc[j][1] = __builtin_amdgcn_sdot4((int)col[g][1], wv.y, acc[j][1], false);
+                acc[j][2] = __builtin_amdgcn_sdot4((int)col[g][2], wv.z, acc[j][2], false);
+                acc[j][3] = __builtin_amdgcn_sdot4((int)col[g][3], wv.w, acc[j][3], false);
+            }
+        }
+    }
+    const int floor0 = a.relu0 ? 0 : INT32_MIN;
+#pragma unroll
+    for (int j = 0; j < PIX; ++j) {
+        if (q0 + j >= a.Q) continue;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[j][e] = max(acc[j][e], floor0);
+        const size_t o = ((((size_t)n * a.P + p) * a.Q + q0 + j)) * a.Cs + c;
+#pragma unroll
+        for (int f = 0; f < 2; ++f)
+            if (a.q[f].ptr)
+                *(unsigned*)(a.q[f].ptr + o) =
+                    pack4(requant1(acc[j][0], a.q[f].n, a.q[f].lo, a.q[f].hi), requant1(acc[j][1], a.q[f].n, a.q[f].lo, a.q[f].hi),
+                          requant1(acc[j][2], a.q[f].n, a.q[f].lo, a.q[f].hi), requant1(acc[j][3], a.q[f].n, a.q[f].lo, a.q[f].hi)) ^ a.q[f].bias_xor;
+    }
+}
+
+// General depthwise: the v_dot4 kernel for int8-only launches (Options::dwk_dot4), else the generic one.
+int dwk_inst(const DwArgs& a, bool out32, bool dot4) {
+    return dot4 && !out32 && (a.k == 3 || a.k == 5 || a.k == 7) && (a.stride == 1 || a.stride == 2) ? 1 : 0;
+}
+
+int dwk_kernel_name(char* buf, size_t cap, const DwArgs& a, int inst) {
+    if (inst) return snprintf(buf, cap, "f8::dwconvk_dot4_kernel<%d, %d>", a.k, a.stride);
+    return snprintf(buf, cap, "f8::dwconvk_kernel<%s>", a.in_signed ? "true" : "false");
+}
+
+hipError_t launch_dwk(const DwArgs& a, int inst, hipStream_t s) {
+    if (a.k < 1 || a.pad < 0 || a.pad > a.k / 2) return hipErrorInvalidValue;
+    if (inst) {
+        if (a.out32 || !a.w4) return hipErrorInvalidValue;
+        const size_t work = (size_t)a.N * a.P * ((a.Q + DWK_PIX - 1) / DWK_PIX) * (a.Cs >> 2);
+        const unsigned grid = (unsigned)((work + 255) / 256);
+        DwArgs b = a; b.w = a.w4; b.bias = a.bias4;
+#define F8_DWK(K_, S_) if (a.k == K_ && a.stride == S_) { hipLaunchKernelGGL((dwconvk_dot4_kernel<K_, S_>), dim3(grid), dim3(256), 0, s, b); return hipGetLastError(); }
+        F8_DWK(3, 1) F8_DWK(3, 2) F8_DWK(5, 1) F8_DWK(5, 2) F8_DWK(7, 1) F8_DWK(7, 2)
+#undef F8_DWK
+        return hipErrorInvalidValue;
+    }
+    const size_t work = (size_t)a.N * a.P * a.Q * (a.Cs >> 2);
+    const unsigned grid = (unsigned)std::min<size_t>((work + 255) / 256, 256 * 8 * 4);      // (grid-stride loop)
+    if (a.in_signed) hipLaunchKernelGGL(dwconvk_kernel<true>, dim3(grid), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(dwconvk_kernel<false>, dim3(grid), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+}  // namespace f8

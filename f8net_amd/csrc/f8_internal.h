@@ -46,6 +46,7 @@ struct Options {
     int deep_nk = 7;             // K loops of at least this many steps use the deepest DMA ring
     int bk128 = 0;               // 128-byte K steps in conv_igemm_kernel
     int dw_dot4 = 1;             // v_dot4 depthwise kernel
+    int dwk_dot4 = 1;            // general depthwise (not 3x3 / pad 1): the v_dot4 kernel of f8_dwk.hip for int8-only launches (0: its generic kernel)
     int dw_mma = 1;              // depthwise 3x3 on the matrix cores (f8_dwmma.hip) where it has an instance (output width >= 14, int8 outputs)
     int stem_rows = 1;           // ResNet head: the row-walking kernel (pool in registers) where it has an instance, else the tile kernel
     int stem_grid_div = 0;       // row-walking head on 1 / n of the CUs; 0 = all of them when it writes int32 (write-bound), half otherwise
@@ -116,11 +117,13 @@ struct ConvArgs {
     void* trace;                           // tuning builds (F8_TRACE) only; nullptr otherwise
 };
 
-// Depthwise 3x3 (groups == C), NHWC int8 in, VALU.
+// Depthwise K x K (groups == C), NHWC int8 in, VALU.  3x3 / pad 1: the launchers of f8_kernels.hip / f8_dwmma.hip, which never read `k`;
+// every other accepted geometry (k 3 / 5 / 7, pad <= k / 2: "general depthwise"): f8_dwk.hip, with the images of pack_dwk_weights.
 struct DwArgs {
-    const int8_t* x; const int8_t* w;      // w: [9][Cs] tap-major
+    const int8_t* x; const int8_t* w;      // w: [k * k][Cs] tap-major
     const int32_t* bias;                   // [Cs]
-    const int8_t* w4; const int32_t* bias4; // dot4 kernel: [Cs/4][9] tap-transposed dwords, bias + 128*sum(w) for unsigned inputs
+    const int8_t* w4; const int32_t* bias4; // dot4 kernels, bias + 128*sum(w) for unsigned inputs.  3x3 / pad 1: [Cs/4][9] tap-transposed dwords;
+                                           // general: [Cs/4][k columns][ceil(k / 4) row groups][4 channels] dwords, byte j = row 4g + j (0 beyond k)
     int32_t N, H, W, P, Q, Cs, stride, pad;
     int32_t in_signed;
     int32_t relu0;
@@ -130,6 +133,7 @@ struct DwArgs {
     int32_t acc_ok;                        // every accumulator is provably below 2^31 - 2^16 in magnitude (planner: conv_acc_bounded): the
                                            // float requantisation (requant_u8x4, f8_device.h) equals the wrapping integer one
     int32_t rq_int;                        // Options::requant_float == 0: integer requantisation only
+    int32_t k;                             // kernel size; read by the general depthwise kernels only (f8_dwk.hip)
 };
 
 struct PoolArgs {                          // max-pool, NHWC
@@ -517,6 +521,11 @@ hipError_t launch_head_dws(const StemPoolArgs& a, hipStream_t s);
 int dwconv_inst(const DwArgs& a, bool out32, int nq, bool mma, bool dot4, int max_batch);
 int dwconv_kernel_name(char* buf, size_t cap, const DwArgs& a, int inst);
 hipError_t launch_dwconv(const DwArgs& a, int inst, hipStream_t s);
+// general depthwise (f8_dwk.hip): every accepted depthwise geometry but 3x3 / pad 1.  inst 1: dwconvk_dot4_kernel<k, stride> (int8 outputs only,
+// Options::dwk_dot4), 0: dwconvk_kernel<in_signed>
+int dwk_inst(const DwArgs& a, bool out32, bool dot4);
+int dwk_kernel_name(char* buf, size_t cap, const DwArgs& a, int inst);
+hipError_t launch_dwk(const DwArgs& a, int inst, hipStream_t s);
 int maxpool_inst(const PoolArgs& a);
 const char* maxpool_kernel_name(int inst);
 hipError_t launch_maxpool(const PoolArgs& a, int inst, hipStream_t s);

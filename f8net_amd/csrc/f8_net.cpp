@@ -347,6 +347,7 @@ static const OptKey kOptKeys[] = {
     {"bk128", "F8_BK128", &Options::bk128, 0, 1, true},
     {"dw_dot4", "F8_DW_DOT4", &Options::dw_dot4, 0, 1, true},
     {"dw_mma", "F8_DW_MMA", &Options::dw_mma, 0, 1, true},
+    {"dwk_dot4", "F8_DWK_DOT4", &Options::dwk_dot4, 0, 1, true},
     {"stem_wpc", "F8_STEM_WPC", &Options::stem_wpc, 1, 8, false},
     {"stem_rows", "F8_STEM_ROWS", &Options::stem_rows, 0, 1, true},
     {"stem_grid_div", "F8_STEM_GRID_DIV", &Options::stem_grid_div, 0, 32, false},
@@ -553,8 +554,9 @@ static int add_conv_node(f8_net* net, int src, const f8_conv_desc& d, const int3
     if (d.kernel < 1 || d.stride < 1 || d.pad < 0 || d.cout < 1) return fail(F8_ERR_INVALID, "%s: bad geometry", who);
     if (!(d.groups == 1 || (d.groups == d.cin && d.cout == d.cin)))
         return fail(F8_ERR_UNSUPPORTED, "%s: groups must be 1 or cin (depthwise)", who);
-    if (d.groups != 1 && !(d.kernel == 3 && d.pad == 1))
-        return fail(F8_ERR_UNSUPPORTED, "%s: depthwise is built for 3x3 pad 1", who);
+    if (d.groups != 1 && !((d.kernel == 3 || d.kernel == 5 || d.kernel == 7) && d.stride <= 2 && d.pad <= d.kernel / 2))
+        return fail(F8_ERR_UNSUPPORTED, "%s: depthwise is built for kernel 3, 5 or 7, stride 1 or 2, pad 0 .. kernel / 2 (got kernel %d, stride %d, pad %d)",
+                    who, d.kernel, d.stride, d.pad);
     if (d.weight_fl < 0 || d.weight_fl > 31) return fail(F8_ERR_INVALID, "%s: bad weight_fl", who);
     int n;
     rc = consumer_format(s, d, &n, who);
@@ -829,6 +831,45 @@ static void pack_dw_weights(f8_net* net, Node& nd) {
     }
 }
 
+// "General depthwise": every accepted depthwise conv that is not 3x3 / pad 1 (kernel 3 / 5 / 7, stride 1 / 2, pad 0 .. kernel / 2; add_conv_node).  No pass
+// of the planner fuses one (each matcher asks for kernel 3 and pad 1): always a launch of its own on the kernels of f8_dwk.hip.
+static bool dw_general(const f8_conv_desc& d) { return d.groups != 1 && !(d.kernel == 3 && d.pad == 1); }
+
+// The two weight images of a general depthwise conv, at offsets of their own (the 3x3 / pad 1 images are pack_dw_weights' and stay as they are):
+//  (1) [K * K][Cs] tap-major + plain bias                        — dwconvk_kernel
+//  (2) [Cs / 4][K columns][G = ceil(K / 4) row groups][4 channels] dwords for dwconvk_dot4_kernel: byte j of dword (quad, s, g, e) = the weight of
+//      channel 4 * quad + e at row 4 g + j, column s — 0 for the rows beyond K, whose slots of a dot4 may then hold any byte; bias + 128 * sum(w)
+//      when the input is unsigned (stored biased; the kernel replaces out-of-image taps by the biased zero).
+static void pack_dwk_weights(f8_net* net, Node& nd) {
+    const f8_conv_desc& d = nd.cd;
+    const Tensor& src = net->tensors[nd.a];
+    const int K = d.kernel, G = (K + 3) / 4;
+    nd.coutP = src.Cs; nd.ck = 0; nd.ktot = 0;
+    nd.w_off = round_up_z(net->wblob.size(), 256);
+    nd.b_off = round_up_z(nd.w_off + (size_t)K * K * src.Cs, 256);
+    nd.rc_off = round_up_z(nd.b_off + (size_t)src.Cs * 4, 256);                    // dot4 weights
+    nd.cc_off = round_up_z(nd.rc_off + (size_t)(src.Cs / 4) * K * G * 16, 256);    // dot4 bias
+    net->wblob.resize(nd.cc_off + (size_t)src.Cs * 4, 0);
+    int8_t* wp = (int8_t*)net->wblob.data() + nd.w_off;
+    int32_t* bp = (int32_t*)(net->wblob.data() + nd.b_off);
+    int8_t* w4 = (int8_t*)net->wblob.data() + nd.rc_off;
+    int32_t* b4 = (int32_t*)(net->wblob.data() + nd.cc_off);
+    for (int c = 0; c < d.cout; ++c) {
+        long long sum = 0;
+        for (int r = 0; r < K; ++r)
+            for (int s = 0; s < K; ++s) {
+                const int8_t v = nd.w[((size_t)c * K + r) * K + s];
+                wp[(size_t)(r * K + s) * src.Cs + c] = v;
+                sum += v;
+                w4[((((size_t)(c / 4) * K + s) * G + r / 4) * 4 + c % 4) * 4 + r % 4] = v;
+            }
+        bp[c] = nd.bias[c];
+        uint32_t b = (uint32_t)nd.bias[c];
+        if (!d.input_signed) b += (uint32_t)(128ll * sum);
+        b4[c] = (int32_t)b;
+    }
+}
+
 static std::string tname(const f8_net* net, int t) {
     const Tensor& T = net->tensors[t];
     if (!T.label.empty()) return T.label;
@@ -877,7 +918,7 @@ static void label_conv_step(f8_net* net, Step& st, const Node& nd) {
         case V_WREG: st.name = "conv1x1s1_wreg:" + key; return;
         case V_PATCH3X3: snprintf(buf, sizeof buf, "conv3x3s1_patch_R%dx%d_bn%d%s:%s", nd.p3_R, nd.p3_imgs, nd.p3_bn, res ? "_res" : "", key.c_str()); break;
         default:
-            if (nd.depthwise) snprintf(buf, sizeof buf, "dwconv3x3s%d:%s", d.stride, key.c_str());
+            if (nd.depthwise) snprintf(buf, sizeof buf, "dwconv%dx%ds%d:%s", d.kernel, d.kernel, d.stride, key.c_str());
             else snprintf(buf, sizeof buf, "conv%dx%ds%d_t%dx%dx%d%s%s:%s", d.kernel, d.kernel, d.stride, nd.tile.bm, nd.tile.bn,
                           nd.tile.bk, nd.stem ? "_stem" : "", res ? "_res" : (nd.dual >= 0 ? "_dual" : ""), key.c_str());
     }
@@ -1701,9 +1742,9 @@ static int join_output(const f8_net* net, const Node& c, Step& st) {
     st.relu1 = net->nodes[c.fused_add].relu;
     return net->nodes[c.fused_add].out;
 }
-// bytes of a conv's packed weights + bias (depthwise: 9 taps + 4 bytes of bias per channel)
+// bytes of a conv's packed weights + bias (depthwise: K * K taps + 4 bytes of bias per channel)
 static double weight_bytes(const f8_net* net, const Node& c) {
-    return c.depthwise ? (double)net->tensors[c.a].Cs * 13 : (double)c.coutP * (c.ktot + 4);
+    return c.depthwise ? (double)net->tensors[c.a].Cs * (c.cd.kernel * c.cd.kernel + 4) : (double)c.coutP * (c.ktot + 4);
 }
 // multiply-adds x 2 of a conv per image
 static double conv_ops(const f8_net* net, const Node& c) {
@@ -2081,7 +2122,7 @@ static int emit_conv(f8_net* net, int i, int max_batch, Step& st, std::vector<in
     if (nd.stem) { st.src_t = nd.a; st.src_f = find_form(s, FORM_STEM, 0, 0); }
     else if (const int rc = conv_input_i8(net, nd, &st.src_t, &st.src_f)) return rc;
     st.relu0 = d.relu;
-    if (nd.depthwise) pack_dw_weights(net, nd);
+    if (nd.depthwise) { if (dw_general(d)) pack_dwk_weights(net, nd); else pack_dw_weights(net, nd); }
     else {
         pack_conv_weights(net, nd);
         const int M1 = T[nd.out].H * T[nd.out].W;
@@ -2123,7 +2164,7 @@ static int emit_conv(f8_net* net, int i, int max_batch, Step& st, std::vector<in
     if (g) b += (double)T[g->a].H * T[g->a].W * T[g->a].Cs;
     if (st.dense) b += (double)d.cout * 4;
     st.bytes_per_img = b + out_bytes(st, o, outpix);
-    st.valu_per_img = ((st.res_t >= 0 || g) ? 2.0 * opix * o.C : 0.0) + (nd.pool >= 0 ? opix * o.C : 0.0) + 3.0 * outpix * o.Cs * out_forms8(st) + (nd.depthwise ? 9.0 * opix * d.cout / 4.0 : 0.0);   // (a VALU depthwise conv: one v_dot4 per four taps)
+    st.valu_per_img = ((st.res_t >= 0 || g) ? 2.0 * opix * o.C : 0.0) + (nd.pool >= 0 ? opix * o.C : 0.0) + 3.0 * outpix * o.Cs * out_forms8(st) + (nd.depthwise ? (double)(d.kernel * d.kernel) * opix * d.cout / 4.0 : 0.0);   // (a VALU depthwise conv: one v_dot4 per four taps)
     st.bytes_const = weight_bytes(net, nd) + (g ? weight_bytes(net, *g) : 0.0);
     label_conv_step(net, st, nd);
     if (reads_frag_weights(st.variant)) pack_frag_weights(net, nd);
@@ -2754,9 +2795,15 @@ static int bind_step(f8_net* net, Step& st) {
             a.w4 = W8(nd.rc_off); a.bias4 = B32(nd.cc_off);
             a.H = sT.H; a.W = sT.W; a.P = oT.H; a.Q = oT.W; a.Cs = sT.Cs; a.stride = nd.cd.stride; a.pad = nd.cd.pad;
             a.in_signed = nd.cd.input_signed; a.relu0 = st.relu0; a.acc_ok = conv_acc_bounded(nd); a.rq_int = rq_int;
+            a.k = nd.cd.kernel;
             out_formats(a.q);
-            st.inst = dwconv_inst(a, out32, nq, opt.dw_mma, opt.dw_dot4, net->max_batch);     // (the MMA kernel's index bound at the largest launch)
-            dwconv_kernel_name(kb, sizeof kb, a, st.inst);
+            if (dw_general(nd.cd)) {                                 // f8_dwk.hip: integer requantisation (requant1) whatever requant_float says
+                st.inst = dwk_inst(a, out32, opt.dwk_dot4);
+                dwk_kernel_name(kb, sizeof kb, a, st.inst);
+            } else {
+                st.inst = dwconv_inst(a, out32, nq, opt.dw_mma, opt.dw_dot4, net->max_batch);     // (the MMA kernel's index bound at the largest launch)
+                dwconv_kernel_name(kb, sizeof kb, a, st.inst);
+            }
             st.args = a; break;
         }
         case S_ADD: case S_REQUANT: {
@@ -3134,7 +3181,7 @@ static int run_step(const f8_net* net, const Step& st, const int32_t* input, voi
             DwArgs a = std::get<DwArgs>(st.args);
             a.x = (const int8_t*)fp(T[st.src_t].forms[st.src_f]); a.N = N;
             fill_out(&a.out32, a.q);
-            e = launch_dwconv(a, st.inst, s);
+            e = (a.k == 3 && a.pad == 1) ? launch_dwconv(a, st.inst, s) : launch_dwk(a, st.inst, s);      // (general depthwise: f8_dwk.hip)
             break;
         }
         case S_ADD: case S_REQUANT: {

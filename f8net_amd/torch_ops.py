@@ -164,7 +164,8 @@ def _conv2d(x, weight, bias, stride, pad, groups, weight_fl, input_fl, input_sig
     _i32(x, 'conv2d')
     x = x.contiguous()
     N, C, H, W = x.shape
-    key = ('conv', x.device.index, C, H, W, id(weight), None if bias is None else id(bias), stride, pad, groups, weight_fl, input_fl, bool(input_signed))
+    key = ('conv', x.device.index, C, H, W, id(weight), tuple(weight.shape), None if bias is None else id(bias), stride, pad, groups, weight_fl, input_fl,
+           bool(input_signed))
 
     def build(n):
         net = F8Net()

@@ -32,7 +32,7 @@ extern "C" {
 typedef enum f8_status {
     F8_OK = 0,
     F8_ERR_INVALID = -1,      /* argument the reference would assert on, or malformed graph */
-    F8_ERR_UNSUPPORTED = -2,  /* legal in the reference, not built here (e.g. groups not in {1, Cin}) */
+    F8_ERR_UNSUPPORTED = -2,  /* legal in the reference, not built here (e.g. groups not in {1, Cin}; a depthwise kernel of 9) */
     F8_ERR_HIP = -3,          /* HIP runtime error (message in f8_last_error) */
     F8_ERR_NOMEM = -4,
     F8_ERR_STATE = -5         /* call out of order (e.g. run before finalize) */
@@ -98,7 +98,8 @@ typedef struct f8_conv_desc {
     int32_t cin, cout;
     int32_t kernel;        /* square kernels: 1, 3, 7 in the reference nets */
     int32_t stride, pad;
-    int32_t groups;        /* 1 or cin (depthwise, cout == cin) — fix_quant_ops.py:373-390 */
+    int32_t groups;        /* 1 or cin (depthwise, cout == cin) — fix_quant_ops.py:373-390.  Depthwise: kernel 3, 5 or 7,
+                              stride 1 or 2, 0 <= pad <= kernel / 2; anything else depthwise is F8_ERR_UNSUPPORTED */
     int32_t weight_fl;     /* buffer `weight_fraclen` (fix_quant_ops.py:710) */
     int32_t input_fl;      /* buffer `input_fraclen`  (fix_quant_ops.py:711) */
     int32_t input_signed;  /* attr `input_symmetric`  (fix_quant_ops.py:709) */
@@ -268,13 +269,16 @@ int f8_net_check(f8_net* net);
  *               convs in one launch), wstat (weight-stationary 1x1 kernel: plain, dual-GEMM and residual-join instances) with
  *               wstat_min_tiles (pixel tiles per workgroup a launch must offer; 0 = always) and wstat_fast (0 = general epilogue), wreg (weights-streamed 1x1 kernel for the
  *               512 -> 256 / 1024 -> 512 reductions of smaller launches),
- *               patch3x3, dual_wide, deep_nk, bk128, dw_dot4, opener_stg, whole_batch_launches (hint: runs will use
+ *               patch3x3, dual_wide, deep_nk, bk128, dw_dot4, dwk_dot4 (default 1; depthwise convs other than 3x3 / pad 1 — kernel 3 / 5 / 7, stride 1 / 2,
+ *               pad 0 .. kernel / 2 —, always a launch of their own: 1 = a launch that writes int8 forms only runs f8::dwconvk_dot4_kernel<K, S>, f8_dwk.hip;
+ *               0 = f8::dwconvk_kernel, which a launch that writes an int32 form runs either way.  dw_mma and dw_dot4 govern 3x3 / pad 1 only), opener_stg, whole_batch_launches (hint: runs will use
  *               f8_net_set_pipelined(2)),
  *               requant_float (default 0: INTEGER shift / round-half-even / clamp in every kernel — fix_quant_ops.py:99-112 literally, on gfx950's
  *               v_ashr_pk_u8_i32; no float instruction in any epilogue; 1: a ReLU -> unsigned-8-bit right shift (1..16) of a value the PLANNER
  *               CAN BOUND — conv accumulators, the int32 stream of a chain launch — runs through the float converter: v_cvt_f32_i32, v_mul_f32
  *               by 2^-n, v_cvt_pk_u8_f32: exact, compared with the reference's arithmetic over all 2^32 inputs on the device; anything
- *               unbounded takes the integer form by itself.  Same results either way, bit for bit),
+ *               unbounded takes the integer form by itself.  Same results either way, bit for bit.  The general depthwise launches
+ *               (dwk_dot4) requantise in the integer form whatever this says: same kernels, same values),
  *               tap_tiled (default 1: the copy-out launches of outputs 1 .. run f8::tap_kernel, f8_tap.hip — one wave per 4 KB block of the
  *               int32 source, every loaded byte used; 0: f8::output_kernel, which walks the destination.  Output 0 always leaves through
  *               output_kernel or the classifier itself.  Same values either way)
