@@ -153,9 +153,8 @@ struct f8_net {
     std::vector<Node> nodes;
     struct Output { int t; int as_float; };
     std::vector<Output> outs;          // the network outputs in the order of the f8_net_output calls; [0] is the one f8_net_run's output_dev receives
-    void* out_bufs[F8_MAX_OUTPUTS - 1] = {};   // caller buffers of outputs 1 .. (f8_net_set_output_buffers): one-shot, consumed by the next run ...
+    void* out_bufs[F8_MAX_OUTPUTS - 1] = {};   // caller buffers of outputs 1 .. (f8_net_set_output_buffers): one-shot, consumed by the next run (begin_run)
     bool out_bufs_set = false;
-    void* run_bufs[F8_MAX_OUTPUTS - 1] = {};   // ... which keeps them here while it issues its launches
     bool finalized = false;
     int plan_bug = -1;                 // planning: a conv that two fused blocks claimed (set_block); finalize fails on it
     int max_batch = 0;
@@ -176,11 +175,9 @@ struct f8_net {
     uint32_t epoch = 0;                // tag of the run being issued (1 .. 2^24 - 1, f8_net_run): chain error words carry it (ChainArgs::epoch)
     char* d_chain = nullptr; size_t chain_stride = 0;   // per arena copy: sync words + halo exchange rows of the stage-chain launches
     hipEvent_t* events = nullptr; int n_events = 0;
-    bool aux_shared = false;           // aux[] belong to the per-device pool (run_common), not to this handle
+    bool aux_shared = false;           // aux[] belong to the per-device pool (ensure_aux), not to this handle
     hipStream_t aux[4] = {nullptr, nullptr, nullptr, nullptr}; hipEvent_t aux_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     hipEvent_t lag_ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    const float* in_f32 = nullptr; float in_scale = 0.f; int in_lo = 0, in_hi = 0;   // set by f8_net_run_f32 for the duration of the call
-    const uint8_t* in_u8 = nullptr; int in_u8_nhwc = 0; int16_t in_lut[3 * 256];       // set by f8_net_run_u8 for the duration of the call
     // pipelined submission (f8_net_set_pipelined): fork dependency = the event recorded at the PREVIOUS run's entry
     int pipelined = 0; hipEvent_t start_ev[4] = {nullptr, nullptr, nullptr, nullptr}; int start_idx = 0; int pipe_count = 0; hipStream_t prev_stream = nullptr;
     int alt_idx = 0;                   // pipelined == 2: internal stream / arena copy of the next run
@@ -3016,12 +3013,46 @@ int f8_net_launch_grid(const f8_net* net, int i, int N, int num_cu, int* tiles, 
     return F8_OK;
 }
 
+// What one run reads and writes: built on the stack by its entry point (begin_run) and read-only from there on; the handle keeps
+// nothing of a call but the cross-run state (the run tag, the pipelining ring, the graph cache).
+struct RunIO {
+    enum Kind { I32, F32, U8, U8_NHWC } kind = I32;
+    const void* in = nullptr;                  // the caller's images: NCHW planes of `kind`, U8_NHWC: pixels
+    float scale = 0.f; int lo = 0, hi = 0;     // F32: rint(x * scale) clamped to [lo, hi]
+    const int16_t* lut = nullptr;              // U8 / U8_NHWC: the 3 x 256 table on f8_net_run_u8's stack (launches copy it into their arguments)
+    void* out = nullptr;                       // output 0
+    void* bufs[F8_MAX_OUTPUTS - 1] = {}; bool have_bufs = false;   // outputs 1 .. (f8_net_set_output_buffers, consumed)
+    hipEvent_t in_ready = nullptr;             // the producer of `in` (f8_net_set_input_ready, consumed)
+};
+// Does the launch of step st read the caller's buffer in this run?  The input step does, unless the stem launch reads it itself
+// (raw_input) — which that launch cannot do for uint8 NHWC pixels: those go through the input step and the haloed form after all.
+static bool reads_raw_input(const Step& st, const RunIO& io) {
+    const bool stem_reads = st.raw_input && io.kind != RunIO::U8_NHWC;
+    return st.kind == S_INPUT ? !stem_reads : stem_reads;
+}
+// The caller's buffer from element `off` on, as the launch's arguments describe it.  sgn: sign of the 8-bit format an int32 input is
+// narrowed to without a requant (< 0: it is not) — values outside that format would wrap silently, so they are checked.
+extern "C++" template <class A>
+static void bind_raw_common(A& a, const f8_net* net, const RunIO& io, size_t off, int sgn) {
+    if (io.kind == RunIO::F32) { a.xf = (const float*)io.in + off; a.scale = io.scale; a.qlo = io.lo; a.qhi = io.hi; }
+    else if (io.kind != RunIO::I32) { a.xu8 = (const uint8_t*)io.in + off; memcpy(a.lut, io.lut, sizeof a.lut); }
+    else if (net->opt.check_input_range && sgn >= 0) { a.err = net->d_err; a.chk_lo = sgn ? -127 : 0; a.chk_hi = sgn ? 127 : 255; }
+}
+static void bind_raw_input(InArgs& a, const f8_net* net, const RunIO& io, size_t off, int sgn) {
+    a.u8_nhwc = io.kind == RunIO::U8_NHWC; if (io.kind == RunIO::I32) a.x = (const int32_t*)io.in + off;
+    bind_raw_common(a, net, io, off, sgn);
+}
+static void bind_raw_input(StemPoolArgs& a, const f8_net* net, const RunIO& io, size_t off, int sgn) {
+    a.raw_kind = io.kind == RunIO::I32 ? 0 : io.kind == RunIO::F32 ? 1 : 2; if (io.kind == RunIO::I32) a.xi = (const int32_t*)io.in + off;
+    bind_raw_common(a, net, io, off, sgn);
+}
+
 // Runs one launch for images [n0, n0 + N) of the batch; c0 = the chunk's first image inside the arena (for_each_launch).  Every
 // sub-batch works in its OWN copy of the arena (index `part`): the arena packs tensors by lifetime assuming the steps of one batch
 // run in order, so two sub-batches that are at different steps at the same time must not share it (a later, larger tensor of the
 // sub-batch that is ahead would overlap an earlier tensor the other one is still reading).  The launch's arguments are st.args
 // (bind_step) plus what this run decides: arena and caller pointers, the batch, the chain scratch.
-static int run_step(const f8_net* net, const Step& st, const int32_t* input, void* output, int n0, int N, int c0, int part, hipStream_t s) {
+static int run_step(const f8_net* net, const RunIO& io, const Step& st, int n0, int N, int c0, int part, hipStream_t s) {
     const auto& T = net->tensors;
     char* A = net->d_arena + (size_t)part * net->arena_stride;
     auto fp = [&](const Form& F) -> char* { return A + F.off + (size_t)c0 * F.bytes_per_img; };
@@ -3045,21 +3076,16 @@ static int run_step(const f8_net* net, const Step& st, const int32_t* input, voi
     hipError_t e = hipSuccess;
     switch (st.kind) {
         case S_INPUT: {
-            if (st.raw_input && !(net->in_u8 && net->in_u8_nhwc)) break;       // the stem launch reads the caller's buffer
+            if (!reads_raw_input(st, io)) break;                               // the stem launch reads the caller's buffer
             const Tensor& o = T[st.out.t];
-            const size_t img = (size_t)o.C * o.H * o.W;
-            InArgs a{}; a.x = input + (size_t)n0 * img; a.N = N; a.C = o.C; a.H = o.H; a.W = o.W;
-            if (net->in_f32) { a.xf = net->in_f32 + (size_t)n0 * img; a.scale = net->in_scale; a.qlo = net->in_lo; a.qhi = net->in_hi; }
-            if (net->in_u8) { a.xu8 = net->in_u8 + (size_t)n0 * img; a.u8_nhwc = net->in_u8_nhwc; memcpy(a.lut, net->in_lut, sizeof a.lut); }
+            InArgs a{}; a.N = N; a.C = o.C; a.H = o.H; a.W = o.W;
+            int narrow = -1;                                                   // sign of the head format (an 8-bit form without a requant)
             for (auto& F : o.forms) {
-                if (F.kind == FORM_I8) { if (F.n == 0) { a.out8 = (int8_t*)fp(F); a.Cs8 = o.Cs; if (!F.sgn) a.xor8 = 0x80808080u; } }
+                if (F.kind == FORM_I8) { if (F.n == 0) { a.out8 = (int8_t*)fp(F); a.Cs8 = o.Cs; if (!F.sgn) a.xor8 = 0x80808080u; narrow = F.sgn; } }
                 else if (F.kind == FORM_I32) { a.out32 = (int32_t*)fp(F); a.Cs32 = o.Cs; }
-                else { a.stem = (int8_t*)fp(F); a.Hp = F.Hp; a.Wp = F.Wp; a.pad = F.pad; if (!F.sgn) a.xor8 = 0x80808080u; }
-                // an int32 input that is narrowed to 8 bits without a requant (head format): values outside the format would wrap silently
-                if (net->opt.check_input_range && !net->in_f32 && !net->in_u8 && ((F.kind == FORM_I8 && F.n == 0) || F.kind == FORM_STEM)) {
-                    a.err = net->d_err; a.chk_lo = F.sgn ? -127 : 0; a.chk_hi = F.sgn ? 127 : 255;
-                }
+                else { a.stem = (int8_t*)fp(F); a.Hp = F.Hp; a.Wp = F.Wp; a.pad = F.pad; if (!F.sgn) a.xor8 = 0x80808080u; narrow = F.sgn; }
             }
+            bind_raw_input(a, net, io, (size_t)n0 * o.C * o.H * o.W, narrow);
             e = launch_input(a, st.inst, s);
             break;
         }
@@ -3072,7 +3098,7 @@ static int run_step(const f8_net* net, const Step& st, const int32_t* input, voi
             fill_out(&a.out32, a.q);
             const int C = T[nd.out].C;
             switch (st.variant) {
-                case V_FC: e = launch_fc_dense(a, (char*)output + (size_t)n0 * C * 4, C, net->outs[0].as_float, chain_err, net->epoch, s); break;
+                case V_FC: e = launch_fc_dense(a, (char*)io.out + (size_t)n0 * C * 4, C, net->outs[0].as_float, chain_err, net->epoch, s); break;
                 case V_POOL: e = launch_conv1x1_pool(a, s); break;
                 case V_S2WREG: e = launch_conv3x3s2_wreg(a, s); break;
                 case V_WSTAT: e = launch_conv1x1_wstat(a, st.inst, net->num_cu, s); break;
@@ -3088,15 +3114,9 @@ static int run_step(const f8_net* net, const Step& st, const int32_t* input, voi
             a.x = (const int8_t*)fp(sF); a.x_bytes = (uint32_t)(sF.bytes_per_img * N); a.N = N;
             if (st.kind == S_STEMPOOL) a.wpc = net->opt.stem_wpc;
             a.grid_div = net->opt.stem_grid_div;
-            if (st.raw_input && !(net->in_u8 && net->in_u8_nhwc)) {      // the raw network input, read by this launch (the input step launches nothing)
-                const size_t img = (size_t)sT.C * sT.H * sT.W;
+            if (reads_raw_input(st, io)) {                               // the raw network input, read by this launch (the input step launches nothing)
                 a.rC = sT.C; a.rH = sT.H; a.rW = sT.W; a.xor8 = sF.sgn ? 0u : 0x80808080u;
-                if (net->in_u8) { a.raw_kind = 2; a.xu8 = net->in_u8 + (size_t)n0 * img; memcpy(a.lut, net->in_lut, sizeof a.lut); }
-                else if (net->in_f32) { a.raw_kind = 1; a.xf = net->in_f32 + (size_t)n0 * img; a.scale = net->in_scale; a.qlo = net->in_lo; a.qhi = net->in_hi; }
-                else {
-                    a.raw_kind = 0; a.xi = input + (size_t)n0 * img;
-                    if (net->opt.check_input_range) { a.err = net->d_err; a.chk_lo = sF.sgn ? -127 : 0; a.chk_hi = sF.sgn ? 127 : 255; }
-                }
+                bind_raw_input(a, net, io, (size_t)n0 * sT.C * sT.H * sT.W, sF.sgn ? 1 : 0);
             }
             fill_out(&a.out32, a.q);
             e = launch_stem_pool(a, st.inst, s);
@@ -3211,7 +3231,7 @@ static int run_step(const f8_net* net, const Step& st, const int32_t* input, voi
         case S_OUTPUT: {
             OutArgs a = std::get<OutArgs>(st.args);
             a.x = (const int32_t*)fp(T[st.src_t].forms[st.src_f]); a.N = N;
-            char* const buf = st.out_k ? (char*)net->run_bufs[st.out_k - 1] : (char*)output;
+            char* const buf = st.out_k ? (char*)io.bufs[st.out_k - 1] : (char*)io.out;
             a.out = buf + (size_t)n0 * a.C * a.HW * 4; a.err = chain_err; a.epoch = net->epoch;
             e = st.inst ? launch_tap(a, s) : launch_output(a, s);
             break;
@@ -3221,7 +3241,23 @@ static int run_step(const f8_net* net, const Step& st, const int32_t* input, voi
     return F8_OK;
 }
 
-static int split_batch(const f8_net* net, int N, int cut[5]);
+// Cuts the batch into up to F8_SPLIT (default 2, max 4) equal sub-batches (the last takes the remainder), never more than arena
+// copies or images.  Returns the number of parts and their starts in cut[0..parts].
+static int split_batch(const f8_net* net, int N, int cut[5]) {
+    const int want = std::min(net->opt.split, net->n_copies > 0 ? net->n_copies : net->opt.split);
+    const int parts = std::min(want, N);
+    cut[0] = 0; cut[1] = N;
+    if (parts < 2) return 1;
+    for (int p = 0; p < parts; ++p) cut[p] = p * (N / parts);
+    cut[parts] = N;
+    return parts;
+}
+// The parts of one run: split_batch, except that pipelining mode 2 runs every batch unsplit (it overlaps whole runs instead).
+static int run_parts(const f8_net* net, int N, int cut[5]) {
+    const int parts = split_batch(net, N, cut);     // (cut[0] = 0)
+    if (net->pipelined == 2) cut[1] = N;
+    return net->pipelined == 2 ? 1 : parts;
+}
 
 // Measured tile choice: every implicit-GEMM conv step is timed on the device with each tile that has a kernel
 // instance (HIP events, best of a few repetitions, on garbage activations: integer kernels are data-independent in
@@ -3235,6 +3271,7 @@ int f8_net_autotune(f8_net* net, int N, void* stream) {
     int cut[5];
     (void)split_batch(net, N, cut);
     const int n_launch = cut[1] - cut[0];                      // images of one sub-batch launch
+    const RunIO io{};                                          // (a conv step reads and writes the arena only)
     hipEvent_t e0, e1;
     if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return fail(F8_ERR_HIP, "f8_net_autotune: events");
     static const int cand_bm[4] = {128, 128, 64, 64}, cand_bn[4] = {128, 64, 128, 64};
@@ -3251,11 +3288,11 @@ int f8_net_autotune(f8_net* net, int N, void* stream) {
             if (t.bm == 64 && t.bn == 32) continue;
             nd.tile = t;
             (void)bind_step(net, st);                                  // the instance follows the tile (ring depth)
-            if (run_step(net, st, nullptr, nullptr, 0, n_launch, 0, 0, s) != F8_OK) { (void)hipGetLastError(); continue; }   // no instance
+            if (run_step(net, io, st, 0, n_launch, 0, 0, s) != F8_OK) { (void)hipGetLastError(); continue; }   // no instance
             float ms_min = 1e30f;
             for (int rep = 0; rep < 3; ++rep) {
                 (void)hipEventRecord(e0, s);
-                for (int k = 0; k < 4; ++k) (void)run_step(net, st, nullptr, nullptr, 0, n_launch, 0, 0, s);
+                for (int k = 0; k < 4; ++k) (void)run_step(net, io, st, 0, n_launch, 0, 0, s);
                 (void)hipEventRecord(e1, s);
                 if (hipEventSynchronize(e1) != hipSuccess) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); return fail(F8_ERR_HIP, "f8_net_autotune: sync"); }
                 float ms = 0.f; (void)hipEventElapsedTime(&ms, e0, e1);
@@ -3270,22 +3307,6 @@ int f8_net_autotune(f8_net* net, int N, void* stream) {
     }
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     return changed;
-}
-
-// Cuts the batch into up to F8_SPLIT (default 2, max 4) sub-batches; every I32T form needs each cut at a
-// multiple of 32 pixels.  Returns the number of parts and their starts in cut[0..parts].
-static int split_batch(const f8_net* net, int N, int cut[5]) {
-    const int want = std::min(net->opt.split, net->n_copies > 0 ? net->n_copies : net->opt.split);   // never more parts than arena copies
-    cut[0] = 0; cut[1] = N;
-    if (want < 2 || N < 2) return 1;
-    const int gran = 1;
-    int parts = want;
-    while (parts > 1 && (N / parts) / gran * gran == 0) --parts;
-    if (parts < 2) return 1;
-    const int per = (N / parts) / gran * gran;
-    for (int p = 0; p < parts; ++p) cut[p] = p * per;
-    cut[parts] = N;
-    return parts;
 }
 
 // Chunked execution.  The fused bottleneck blocks of a stage run in chunks of images, block after block per chunk: a chunk's
@@ -3359,213 +3380,134 @@ static int for_each_launch(const f8_net* net, int N, F&& f) {
     return F8_OK;
 }
 // all launches of one run for images [n0, n0 + N) of the network input, on stream s, in arena copy `part`
-static int run_steps(const f8_net* net, const int32_t* input, void* output, int n0, int N, int part, hipStream_t s) {
-    return for_each_launch(net, N, [&](int k, int c0, int cn) { return run_step(net, net->steps[k], input, output, n0, cn, c0, part, s); });
+static int run_steps(const f8_net* net, const RunIO& io, int n0, int N, int part, hipStream_t s) {
+    return for_each_launch(net, N, [&](int k, int c0, int cn) { return run_step(net, io, net->steps[k], n0, cn, c0, part, s); });
 }
 
-static int run_common(f8_net* net, const int32_t* input, void* output, int N, void* stream, float* ms, int cap) {
-    // the one-shot event is consumed by THIS call whatever happens next: a run that fails validation must not leave it armed for a
-    // later, unrelated run (by then the caller's event may be gone)
-    hipEvent_t in_ready = nullptr;
-    bool have_bufs = false;            // ... and so are the buffers of outputs 1 .. (f8_net_set_output_buffers)
-    if (net) {
-        in_ready = net->input_ready; net->input_ready = nullptr;
-        have_bufs = net->out_bufs_set; net->out_bufs_set = false;
-        if (have_bufs) memcpy(net->run_bufs, net->out_bufs, sizeof net->run_bufs);
+// ---- the schedules of a run (run_common picks exactly one) ----
+
+// The internal streams and the fork / join events.  The streams are ONE set per device, shared by every handle of the process.
+// HIP maps streams onto a few hardware queues (GPU_MAX_HW_QUEUES, default 4) in creation order: the first handle's streams got a
+// queue each, a later handle's shared queues with them and its concurrent sub-batches / batches in flight serialised — measured,
+// ResNet-18 with three batches in flight: the handle created first 330 k img/s, every later one 308 k (all 332 k with
+// GPU_MAX_HW_QUEUES=16; tools/prof_intmodel.py).  Work of two handles on one stream is ordered, which costs nothing they would not
+// contend for anyway.  (hipGraph capture needs streams of its own: a capture must not see another handle's launches.)
+static int ensure_aux(f8_net* net) {
+    if (net->aux[0] && !(net->opt.graph && net->aux_shared)) return F8_OK;
+    if (net->aux[0]) {                               // `graph` was switched on after the pooled streams were taken: streams of its own
+        for (int k = 0; k < 4; ++k) { (void)hipStreamSynchronize(net->aux[k]); net->aux[k] = nullptr; }
+        net->aux_shared = false;
     }
-    if (!net || !net->finalized) return fail(F8_ERR_STATE, "f8_net_run: not finalized");
-    if (net->outs.size() > 1 && !have_bufs)
-        return fail(F8_ERR_STATE, "f8_net_run: this net has %d outputs: hand over the buffers of outputs 1 .. with f8_net_set_output_buffers before every run", (int)net->outs.size());
-    if (N < 1 || N > net->max_batch) return fail(F8_ERR_INVALID, "f8_net_run: N=%d outside [1,%d]", N, net->max_batch);
-    if (!input || !output) return fail(F8_ERR_INVALID, "f8_net_run: null pointer");
-    int rc = f8_net_upload(net);
-    if (rc) return rc;
-    if (net->opt.check_device) {       // the arena, the weights and the internal streams belong to the device of the upload
-        int dev = -1;
-        if (hipGetDevice(&dev) != hipSuccess || dev != net->device)
-            return fail(F8_ERR_STATE, "f8_net_run: current device %d, but this net lives on device %d (hipSetDevice before the call; one handle per device)", dev, net->device);
-    }
-    hipStream_t s = (hipStream_t)stream;
-    // this run's tag for the chain error words: a word an EARLIER run left behind (a transient halo time-out nobody collected with
-    // f8_net_check) neither cuts this run's waits short nor poisons its logits; it stays where it is for f8_net_check to report.
-    // (A replayed hipGraph carries the tag of its capture: there the word is sticky until f8_net_check, as it was before round 5.)
-    if (net->h_err) {
-        const uint32_t hw = *(volatile uint32_t*)net->h_err;
-        if (hw) return fail(F8_ERR_HIP, "f8_net_run: a stage-chain launch of an earlier run gave up waiting for a neighbouring tile (code 0x%x of run tag %u): the logits of that run are "
-                                        "poisoned (NaN / INT32_MIN); call f8_net_check to collect the error and re-arm the handle", hw & 0xffu, hw >> 8);
-    }
-    net->epoch = net->epoch % 0xffffffu + 1u;
-    if (in_ready) {                    // the producer of this run's input (f8_net_set_input_ready); every schedule forks from / runs on `s`
-        (void)hipStreamWaitEvent(s, in_ready, 0);
-    }
-    const int ns = (int)net->steps.size();
-    int cut[5];
-    int parts = split_batch(net, N, cut);
-    if (ms && net->pipelined == 2) { parts = 1; cut[0] = 0; cut[1] = N; }   // time the launches the alternating mode issues
-    if (ms) {
-        // profiled: the parts back to back on the caller's stream, one event after every launch; a step's time is the sum
-        // over its launches (parts x chunks)
-        if (cap < ns) return fail(F8_ERR_INVALID, "f8_net_run_profiled: ms capacity %d < %d launches", cap, ns);
-        std::vector<int> owner;                          // step index of every launch, in order
-        for (int p = 0; p < parts; ++p) {
-            owner.push_back(-1);                         // start marker of the part
-            (void)for_each_launch(net, cut[p + 1] - cut[p], [&](int k, int, int) { owner.push_back(k); return 0; });
-        }
-        const int ne = (int)owner.size();
-        if (net->n_events < ne) {
-            if (net->events) { for (int i = 0; i < net->n_events; ++i) (void)hipEventDestroy(net->events[i]); delete[] net->events; }
-            net->events = new hipEvent_t[ne]; net->n_events = ne;
-            for (int i = 0; i < ne; ++i) { hipError_t e = hipEventCreate(&net->events[i]); if (e != hipSuccess) return hip_fail(e, "hipEventCreate"); }
-        }
-        int pos = 0;
-        for (int p = 0; p < parts; ++p) {
-            (void)hipEventRecord(net->events[pos++], s);
-            rc = for_each_launch(net, cut[p + 1] - cut[p], [&](int k, int c0, int cn) {
-                const int r = run_step(net, net->steps[k], input, output, cut[p], cn, c0, p, s);
-                (void)hipEventRecord(net->events[pos++], s);
-                return r;
-            });
-            if (rc) return rc;
-        }
-        hipError_t e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return hip_fail(e, "f8_net_run_profiled: sync");
-        for (int i = 0; i < ns; ++i) ms[i] = 0.f;
-        for (int q = 1; q < ne; ++q) {
-            if (owner[q] < 0) continue;
-            float t = 0.f;
-            (void)hipEventElapsedTime(&t, net->events[q - 1], net->events[q]);
-            ms[owner[q]] += t;
-        }
-        // a step that launched nothing (the input step when the stem launch reads the caller's buffer) has no duration: the two
-        // events around it are ~5 us apart on their own
-        for (int i = 0; i < ns; ++i)
-            if (net->steps[i].kind == S_INPUT && net->steps[i].raw_input && !(net->in_u8 && net->in_u8_nhwc)) ms[i] = 0.f;
-        return F8_OK;
-    }
-    auto ensure_aux = [&]() -> int {
-        if (net->aux[0] && !(net->opt.graph && net->aux_shared)) return F8_OK;
-        if (net->aux[0]) {                               // `graph` was switched on after the pooled streams were taken: streams of its own
-            for (int k = 0; k < 4; ++k) { (void)hipStreamSynchronize(net->aux[k]); net->aux[k] = nullptr; }
-            net->aux_shared = false;
-        }
-        // The internal streams are ONE set per device, shared by every handle of the process.  HIP maps streams onto a few hardware
-        // queues (GPU_MAX_HW_QUEUES, default 4) in creation order: the first handle's streams got a queue each, a later handle's
-        // shared queues with them and its concurrent sub-batches / batches in flight serialised — measured, ResNet-18 with three
-        // batches in flight: the handle created first 330 k img/s, every later one 308 k (all 332 k with GPU_MAX_HW_QUEUES=16;
-        // tools/prof_intmodel.py).  Work of two handles on one stream is ordered, which costs nothing they would not contend for anyway.
-        // (hipGraph capture needs streams of its own: a capture must not see another handle's launches.)
-        static std::mutex pool_mu;
-        static hipStream_t pool[64][4] = {};
-        const int dv = net->device;
-        if (net->opt.shared_streams && !net->opt.graph && dv >= 0 && dv < 64) {
-            std::lock_guard<std::mutex> lk(pool_mu);
-            for (int k = 0; k < 4; ++k) {
-                if (!pool[dv][k]) {
-                    hipError_t e = hipStreamCreateWithFlags(&pool[dv][k], hipStreamNonBlocking);
-                    if (e != hipSuccess) { pool[dv][k] = nullptr; return hip_fail(e, "hipStreamCreate"); }
-                }
-            }
-            for (int k = 0; k < 4; ++k) net->aux[k] = pool[dv][k];
-            net->aux_shared = true;
-        } else
+    static std::mutex pool_mu;
+    static hipStream_t pool[64][4] = {};
+    const int dv = net->device;
+    if (net->opt.shared_streams && !net->opt.graph && dv >= 0 && dv < 64) {
+        std::lock_guard<std::mutex> lk(pool_mu);
         for (int k = 0; k < 4; ++k) {
-            hipError_t e = hipStreamCreateWithFlags(&net->aux[k], hipStreamNonBlocking);
-            if (e != hipSuccess) return hip_fail(e, "hipStreamCreate");
+            if (pool[dv][k]) continue;
+            hipError_t e = hipStreamCreateWithFlags(&pool[dv][k], hipStreamNonBlocking);
+            if (e != hipSuccess) { pool[dv][k] = nullptr; return hip_fail(e, "hipStreamCreate"); }
         }
-        for (int k = 0; k < 5; ++k) {
-            if (net->aux_ev[k]) continue;
-            hipError_t e = hipEventCreateWithFlags(&net->aux_ev[k], hipEventDisableTiming);
-            if (e != hipSuccess) return hip_fail(e, "hipEventCreate");
-        }
-        return F8_OK;
-    };
-    const int arena_copies = net->n_copies;
-    const int use_streams = net->opt.split_streams;
-    if (net->pipelined == 2 && arena_copies >= 2 && !use_streams)     // rocprofv3 runs: the same launches, alone on the caller's stream
-        return run_steps(net, input, output, 0, N, 0, s);
-    if (net->pipelined == 2 && arena_copies >= 2) {
-        // alternating whole batches: run i executes UNSPLIT on internal stream / arena copy i % 2, so that two consecutive
-        // runs are in flight together — the same occupancy as two concurrent sub-batches, but every launch covers the whole
-        // batch (twice the workgroups per launch: at 128 images the latency-bound launches of the late stages fill the chip).
-        // Fork: as in the lagged mode the stream waits for `s` as of the PREVIOUS run's entry (and, by stream order, for
-        // run i-2 on the same arena copy); join: `s` waits for this run.
-        // Options::pipeline_depth D (2..4, at most the arena copies): D runs in flight; the fork then lags D-1 entries.
-        if ((rc = ensure_aux())) return rc;
-        if (!net->start_ev[0])
-            for (int k = 0; k < 4; ++k) (void)hipEventCreateWithFlags(&net->start_ev[k], hipEventDisableTiming);
-        const int D = std::max(2, std::min(net->opt.pipeline_depth, arena_copies));
-        if (net->prev_stream != s) net->pipe_count = 0;
-        const int cur = net->start_idx, slot = net->alt_idx % D;
-        (void)hipEventRecord(net->start_ev[cur], s);
-        const int lagn = std::min(net->pipe_count, D - 1);
-        hipEvent_t dep = net->start_ev[(cur - lagn + 4) & 3];
-        (void)hipStreamWaitEvent(net->aux[slot], dep, 0);
-        if (in_ready) (void)hipStreamWaitEvent(net->aux[slot], in_ready, 0);   // the lagged dependency does not cover this run's input
-        net->start_idx = (cur + 1) & 3; ++net->pipe_count; net->prev_stream = s; net->alt_idx = (slot + 1) % D;
-        if ((rc = run_steps(net, input, output, 0, N, slot, net->aux[slot]))) return rc;
-        (void)hipEventRecord(net->aux_ev[1 + slot], net->aux[slot]);
-        (void)hipStreamWaitEvent(s, net->aux_ev[1 + slot], 0);
-        return F8_OK;
+        for (int k = 0; k < 4; ++k) net->aux[k] = pool[dv][k];
+        net->aux_shared = true;
+    } else
+    for (int k = 0; k < 4; ++k) {
+        hipError_t e = hipStreamCreateWithFlags(&net->aux[k], hipStreamNonBlocking);
+        if (e != hipSuccess) return hip_fail(e, "hipStreamCreate");
     }
-    if (parts == 1) return run_steps(net, input, output, 0, N, 0, s);
-    // F8_SPLIT_STREAMS=0: same launches, serialised on the caller's stream (used for rocprofv3 runs so
-    // that per-kernel durations are not inflated by the overlap of the two sub-batches)
-    if (!use_streams) {
-        for (int p = 0; p < parts; ++p)
-            if ((rc = run_steps(net, input, output, cut[p], cut[p + 1] - cut[p], p, s))) return rc;
-        return F8_OK;
+    for (int k = 0; k < 5; ++k) {
+        if (net->aux_ev[k]) continue;
+        hipError_t e = hipEventCreateWithFlags(&net->aux_ev[k], hipEventDisableTiming);
+        if (e != hipSuccess) return hip_fail(e, "hipEventCreate");
     }
-    // independent sub-batches on internal streams: while one is in a layer's tail / epilogue phase the
-    // others keep the CUs busy.  Fork from and join to the caller's stream with events (no host sync).
-    if ((rc = ensure_aux())) return rc;
-    // F8_GRAPH=1: the second call with the same (input, output, N, stream) captures the launches below into a hipGraph
-    // (the aux streams join the capture through the fork event); later calls replay it with one hipGraphLaunch.
-    // The legacy null stream cannot be captured: the graph then lives on an internal stream fenced by events.
-    const int use_graph = net->opt.graph;
-    bool capturing = false;
-    hipStream_t user_s = s;
-    auto graph_replay = [&]() -> int {
-        hipStream_t gs = user_s ? user_s : net->aux[3];
-        if (gs != user_s) { (void)hipEventRecord(net->aux_ev[0], user_s); (void)hipStreamWaitEvent(gs, net->aux_ev[0], 0); }
-        hipError_t e = hipGraphLaunch(net->g_exec, gs);
-        if (e != hipSuccess) return hip_fail(e, "hipGraphLaunch");
-        if (gs != user_s) { (void)hipEventRecord(net->aux_ev[4], gs); (void)hipStreamWaitEvent(user_s, net->aux_ev[4], 0); }
-        return F8_OK;
-    };
-    if (use_graph && parts <= 3 && !net->in_f32 && !net->in_u8 && net->outs.size() == 1) {      // (the replay key knows one output buffer: a multi-output handle runs plain launches)
-        const bool same = net->g_in == input && net->g_out == output && net->g_N == N && net->g_stream == user_s;
-        if (same && net->g_exec) return graph_replay();
-        if (!same) {
-            if (net->g_exec) { (void)hipGraphExecDestroy(net->g_exec); net->g_exec = nullptr; }
-            net->g_in = input; net->g_out = output; net->g_N = N; net->g_stream = user_s; net->g_warm = 0;
-        }
-        if (net->g_warm++ >= 1) {      // first call with a new key runs eagerly (one-time kernel attribute calls happen there)
-            s = user_s ? user_s : net->aux[3];
-            hipError_t e = hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed);
-            if (e != hipSuccess) return hip_fail(e, "hipStreamBeginCapture");
-            capturing = true;
-        }
+    return F8_OK;
+}
+// Lagged fork of a pipelined run: the n internal streams order themselves behind earlier runs on their arena copy by stream order;
+// towards the caller they only wait for the state of `s` at the entry of the run `lag` entries back (header contract) — fewer while
+// the ring is still filling or after the caller changed streams — and for this run's input, which that dependency does not cover.
+static void lagged_fork(f8_net* net, hipStream_t s, int lag, const hipStream_t* streams, int n, hipEvent_t in_ready) {
+    if (!net->start_ev[0]) for (int k = 0; k < 4; ++k) (void)hipEventCreateWithFlags(&net->start_ev[k], hipEventDisableTiming);
+    if (net->prev_stream != s) net->pipe_count = 0;
+    const int cur = net->start_idx;
+    (void)hipEventRecord(net->start_ev[cur], s);
+    hipEvent_t dep = net->start_ev[(cur - std::min(net->pipe_count, lag) + 4) & 3];
+    for (int k = 0; k < n; ++k) { (void)hipStreamWaitEvent(streams[k], dep, 0); if (in_ready) (void)hipStreamWaitEvent(streams[k], in_ready, 0); }
+    net->start_idx = (cur + 1) & 3; ++net->pipe_count; net->prev_stream = s;
+}
+// Profiled: the parts back to back on the caller's stream, one event after every launch; a step's time is the sum over its launches (parts x chunks).
+static int run_profiled_pass(f8_net* net, const RunIO& io, int parts, const int cut[5], hipStream_t s, float* ms, int cap) {
+    const int ns = (int)net->steps.size();
+    if (cap < ns) return fail(F8_ERR_INVALID, "f8_net_run_profiled: ms capacity %d < %d launches", cap, ns);
+    std::vector<int> owner;                          // step index of every launch, in order
+    for (int p = 0; p < parts; ++p) {
+        owner.push_back(-1);                         // start marker of the part
+        (void)for_each_launch(net, cut[p + 1] - cut[p], [&](int k, int, int) { owner.push_back(k); return 0; });
     }
-    if (net->pipelined && !capturing) {
-        // lagged fork: the sub-batch streams order themselves behind the previous run on the same arena copy by stream
-        // order; towards the caller they only wait for the state of `s` at the previous run's entry (header contract)
-        if (!net->start_ev[0])
-            for (int k = 0; k < 4; ++k) (void)hipEventCreateWithFlags(&net->start_ev[k], hipEventDisableTiming);
-        if (net->prev_stream != s) net->pipe_count = 0;
-        const int cur = net->start_idx;
-        (void)hipEventRecord(net->start_ev[cur], s);
-        hipEvent_t dep = net->start_ev[(cur - std::min(net->pipe_count, 1) + 4) & 3];
-        for (int k = 0; k < parts; ++k) { (void)hipStreamWaitEvent(net->aux[k], dep, 0); if (in_ready) (void)hipStreamWaitEvent(net->aux[k], in_ready, 0); }
-        net->start_idx = (cur + 1) & 3; ++net->pipe_count; net->prev_stream = s;
-    } else {
+    const int ne = (int)owner.size();
+    if (net->n_events < ne) {
+        if (net->events) { for (int i = 0; i < net->n_events; ++i) (void)hipEventDestroy(net->events[i]); delete[] net->events; }
+        net->events = new hipEvent_t[ne]; net->n_events = ne;
+        for (int i = 0; i < ne; ++i) { hipError_t e = hipEventCreate(&net->events[i]); if (e != hipSuccess) return hip_fail(e, "hipEventCreate"); }
+    }
+    int pos = 0;
+    for (int p = 0; p < parts; ++p) {
+        (void)hipEventRecord(net->events[pos++], s);
+        const int rc = for_each_launch(net, cut[p + 1] - cut[p], [&](int k, int c0, int cn) {
+            const int r = run_step(net, io, net->steps[k], cut[p], cn, c0, p, s);
+            (void)hipEventRecord(net->events[pos++], s);
+            return r;
+        });
+        if (rc) return rc;
+    }
+    hipError_t e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return hip_fail(e, "f8_net_run_profiled: sync");
+    for (int i = 0; i < ns; ++i) ms[i] = 0.f;
+    for (int q = 1; q < ne; ++q) {
+        if (owner[q] < 0) continue;
+        float t = 0.f;
+        (void)hipEventElapsedTime(&t, net->events[q - 1], net->events[q]);
+        ms[owner[q]] += t;
+    }
+    // an input step that launched nothing (the stem launch read the caller's buffer) has no duration: the two events around it are ~5 us apart on their own
+    for (int i = 0; i < ns; ++i)
+        if (net->steps[i].kind == S_INPUT && !reads_raw_input(net->steps[i], io)) ms[i] = 0.f;
+    return F8_OK;
+}
+// Alternating whole batches (pipelining mode 2): run i executes UNSPLIT on internal stream / arena copy i % D, so that consecutive
+// runs are in flight together — the same occupancy as concurrent sub-batches, but every launch covers the whole batch (twice the
+// workgroups per launch: at 128 images the latency-bound launches of the late stages fill the chip).  Options::pipeline_depth D
+// (2..4, at most the arena copies) runs are in flight: the fork lags D-1 entries (and, by stream order, run i-D on the same arena
+// copy); join: `s` waits for this run.
+static int run_alternating(f8_net* net, const RunIO& io, int N, hipStream_t s) {
+    if (const int rc = ensure_aux(net)) return rc;
+    const int D = std::max(2, std::min(net->opt.pipeline_depth, net->n_copies));
+    const int slot = net->alt_idx % D;
+    lagged_fork(net, s, D - 1, &net->aux[slot], 1, io.in_ready);
+    net->alt_idx = (slot + 1) % D;
+    if (const int rc = run_steps(net, io, 0, N, slot, net->aux[slot])) return rc;
+    (void)hipEventRecord(net->aux_ev[1 + slot], net->aux[slot]);
+    (void)hipStreamWaitEvent(s, net->aux_ev[1 + slot], 0);
+    return F8_OK;
+}
+// The parts one after the other on the caller's stream: a run of one part, and F8_SPLIT_STREAMS=0 (rocprofv3 runs: the same
+// launches, their durations not inflated by the overlap of the sub-batches).
+static int run_serial(const f8_net* net, const RunIO& io, int parts, const int cut[5], hipStream_t s) {
+    for (int p = 0; p < parts; ++p)
+        if (const int rc = run_steps(net, io, cut[p], cut[p + 1] - cut[p], p, s)) return rc;
+    return F8_OK;
+}
+// Independent sub-batches on the internal streams: while one is in a layer's tail / epilogue phase the others keep the CUs busy.
+// Fork from and join to `s` with events (no host sync); lagged: the fork of a pipelined run (lagged_fork).
+static int run_forked(f8_net* net, const RunIO& io, int parts, const int cut[5], hipStream_t s, bool lagged) {
+    if (lagged) lagged_fork(net, s, 1, net->aux, parts, io.in_ready);
+    else {
         (void)hipEventRecord(net->aux_ev[0], s);
         for (int k = 0; k < parts; ++k) (void)hipStreamWaitEvent(net->aux[k], net->aux_ev[0], 0);
         net->pipe_count = 0;
     }
     // optional stagger: sub-batch p starts only after sub-batch p-1 has finished its first `lag` launches, so that the
     // streams do not march through the memory-bound and the latency-bound layers in lock step
-    const int lag_env = net->opt.stagger, lag_pipe = net->opt.stagger_pipelined;
-    const int lag = lag_env >= 0 ? lag_env : (net->pipelined ? lag_pipe : 2);   // measured: lag 0/1/2/4/8 = 56.06/56.37/56.65/56.34/55.1 k img/s
+    const int lag = net->opt.stagger >= 0 ? net->opt.stagger : (net->pipelined ? net->opt.stagger_pipelined : 2);   // measured: lag 0/1/2/4/8 = 56.06/56.37/56.65/56.34/55.1 k img/s
     // the launches of every part (chunked where a part is larger than a chunk), submitted round-robin so that no stream's
     // queue starts late
     struct Launch { int k, c0, cn; };
@@ -3579,80 +3521,114 @@ static int run_common(f8_net* net, const int32_t* input, void* output, int N, vo
         for (int p = 0; p < parts; ++p) {
             if (t >= plan[p].size()) continue;
             const Launch& L = plan[p][t];
-            rc = run_step(net, net->steps[L.k], input, output, cut[p], L.cn, L.c0, p, net->aux[p]);
-            if (rc) {
-                if (capturing) { hipGraph_t g = nullptr; (void)hipStreamEndCapture(s, &g); if (g) (void)hipGraphDestroy(g); }
-                return rc;
-            }
+            if (const int rc = run_step(net, io, net->steps[L.k], cut[p], L.cn, L.c0, p, net->aux[p])) return rc;
             if (lag > 0 && (int)t == lag - 1 && p + 1 < parts) {
                 if (!net->lag_ev[p]) (void)hipEventCreateWithFlags(&net->lag_ev[p], hipEventDisableTiming);
                 (void)hipEventRecord(net->lag_ev[p], net->aux[p]);
                 (void)hipStreamWaitEvent(net->aux[p + 1], net->lag_ev[p], 0);
             }
         }
-    for (int k = 0; k < parts; ++k) {
-        (void)hipEventRecord(net->aux_ev[1 + k], net->aux[k]);
-        (void)hipStreamWaitEvent(s, net->aux_ev[1 + k], 0);
-    }
-    if (capturing) {
-        hipGraph_t g = nullptr;
-        hipError_t e = hipStreamEndCapture(s, &g);
-        if (e != hipSuccess) return hip_fail(e, "hipStreamEndCapture");
-        e = hipGraphInstantiate(&net->g_exec, g, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(g);
-        if (e != hipSuccess) { net->g_exec = nullptr; return hip_fail(e, "hipGraphInstantiate"); }
-        return graph_replay();
-    }
+    for (int k = 0; k < parts; ++k) { (void)hipEventRecord(net->aux_ev[1 + k], net->aux[k]); (void)hipStreamWaitEvent(s, net->aux_ev[1 + k], 0); }
     return F8_OK;
+}
+// F8_GRAPH=1 around run_forked: the second call with the same (input, output, N, stream) captures its launches into a hipGraph (the
+// internal streams join the capture through the fork event, which is why a captured run forks unlagged); later calls replay it with
+// one hipGraphLaunch.  The legacy null stream cannot be captured: the graph then lives on an internal stream fenced by events.
+static int graph_replay(const f8_net* net, hipStream_t user_s) {
+    hipStream_t gs = user_s ? user_s : net->aux[3];
+    if (gs != user_s) { (void)hipEventRecord(net->aux_ev[0], user_s); (void)hipStreamWaitEvent(gs, net->aux_ev[0], 0); }
+    hipError_t e = hipGraphLaunch(net->g_exec, gs);
+    if (e != hipSuccess) return hip_fail(e, "hipGraphLaunch");
+    if (gs != user_s) { (void)hipEventRecord(net->aux_ev[4], gs); (void)hipStreamWaitEvent(user_s, net->aux_ev[4], 0); }
+    return F8_OK;
+}
+static int run_graphed(f8_net* net, const RunIO& io, int N, int parts, const int cut[5], hipStream_t user_s) {
+    const bool same = net->g_in == io.in && net->g_out == io.out && net->g_N == N && net->g_stream == user_s;
+    if (same && net->g_exec) return graph_replay(net, user_s);
+    if (!same) {
+        if (net->g_exec) { (void)hipGraphExecDestroy(net->g_exec); net->g_exec = nullptr; }
+        net->g_in = io.in; net->g_out = io.out; net->g_N = N; net->g_stream = user_s; net->g_warm = 0;
+    }
+    if (net->g_warm++ < 1) return run_forked(net, io, parts, cut, user_s, net->pipelined != 0);   // a new key's first call runs eagerly (one-time kernel attribute calls happen there)
+    hipStream_t gs = user_s ? user_s : net->aux[3];
+    hipError_t e = hipStreamBeginCapture(gs, hipStreamCaptureModeRelaxed);
+    if (e != hipSuccess) return hip_fail(e, "hipStreamBeginCapture");
+    const int rc = run_forked(net, io, parts, cut, gs, false);
+    hipGraph_t g = nullptr;
+    e = hipStreamEndCapture(gs, &g);
+    if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
+    if (e != hipSuccess) return hip_fail(e, "hipStreamEndCapture");
+    e = hipGraphInstantiate(&net->g_exec, g, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(g);
+    if (e != hipSuccess) { net->g_exec = nullptr; return hip_fail(e, "hipGraphInstantiate"); }
+    return graph_replay(net, user_s);
+}
+// What every run does first, whatever its schedule: the checks, the upload, the run's tag, the wait for the input's producer.
+static int run_prologue(f8_net* net, const RunIO& io, int N, hipStream_t s) {
+    if (!net || !net->finalized) return fail(F8_ERR_STATE, "f8_net_run: not finalized");
+    if (net->outs.size() > 1 && !io.have_bufs)
+        return fail(F8_ERR_STATE, "f8_net_run: this net has %d outputs: hand over the buffers of outputs 1 .. with f8_net_set_output_buffers before every run", (int)net->outs.size());
+    if (N < 1 || N > net->max_batch) return fail(F8_ERR_INVALID, "f8_net_run: N=%d outside [1,%d]", N, net->max_batch);
+    if (!io.in || !io.out) return fail(F8_ERR_INVALID, "f8_net_run: null pointer");
+    if (const int rc = f8_net_upload(net)) return rc;
+    if (net->opt.check_device) {       // the arena, the weights and the internal streams belong to the device of the upload
+        int dev = -1;
+        if (hipGetDevice(&dev) != hipSuccess || dev != net->device)
+            return fail(F8_ERR_STATE, "f8_net_run: current device %d, but this net lives on device %d (hipSetDevice before the call; one handle per device)", dev, net->device);
+    }
+    // this run's tag for the chain error words: a word an EARLIER run left behind (a transient halo time-out nobody collected with
+    // f8_net_check) neither cuts this run's waits short nor poisons its logits; it stays where it is for f8_net_check to report.
+    // (A replayed hipGraph carries the tag of its capture: there the word is sticky until f8_net_check, as it was before round 5.)
+    if (net->h_err) {
+        const uint32_t hw = *(volatile uint32_t*)net->h_err;
+        if (hw) return fail(F8_ERR_HIP, "f8_net_run: a stage-chain launch of an earlier run gave up waiting for a neighbouring tile (code 0x%x of run tag %u): the logits of that run are "
+                                        "poisoned (NaN / INT32_MIN); call f8_net_check to collect the error and re-arm the handle", hw & 0xffu, hw >> 8);
+    }
+    net->epoch = net->epoch % 0xffffffu + 1u;
+    if (io.in_ready) (void)hipStreamWaitEvent(s, io.in_ready, 0);   // the producer of this run's input; every schedule forks from / runs on `s`
+    return F8_OK;
+}
+
+static int run_common(f8_net* net, const RunIO& io, int N, void* stream, float* ms, int cap) {
+    hipStream_t s = (hipStream_t)stream;
+    if (const int rc = run_prologue(net, io, N, s)) return rc;
+    int cut[5];
+    const int parts = run_parts(net, N, cut);
+    if (ms) return run_profiled_pass(net, io, parts, cut, s, ms, cap);
+    const bool streams = net->opt.split_streams != 0;
+    if (net->pipelined == 2 && net->n_copies >= 2 && streams) return run_alternating(net, io, N, s);
+    if (parts == 1 || !streams) return run_serial(net, io, parts, cut, s);
+    if (const int rc = ensure_aux(net)) return rc;
+    // (the replay key knows one int32 input and one output buffer: other runs issue plain launches)
+    if (net->opt.graph && parts <= 3 && io.kind == RunIO::I32 && net->outs.size() == 1) return run_graphed(net, io, N, parts, cut, s);
+    return run_forked(net, io, parts, cut, s, net->pipelined != 0);
 }
 
 int f8_net_num_parts(const f8_net* net, int N) {
     if (!net || !net->finalized) return fail(F8_ERR_STATE, "f8_net_num_parts: not finalized");
-    int cut[5];
-    const int parts = split_batch(net, N, cut);
-    return (net->pipelined == 2 && parts >= 2) ? 1 : parts;     // alternating whole batches: one launch set per run
+    int cut[5]; return run_parts(net, N, cut);
 }
 
 int f8_net_step_launches(const f8_net* net, int i, int N) {
     if (!net || !net->finalized) return fail(F8_ERR_STATE, "f8_net_step_launches: not finalized");
     if (i < 0 || i >= (int)net->steps.size()) return fail(F8_ERR_INVALID, "f8_net_step_launches: launch index out of range");
     int cut[5];
-    int parts = split_batch(net, N, cut);
-    if (net->pipelined == 2 && parts >= 2) { parts = 1; cut[0] = 0; cut[1] = N; }
+    const int parts = run_parts(net, N, cut);
     int n = 0;
     for (int p = 0; p < parts; ++p)
         (void)for_each_launch(net, cut[p + 1] - cut[p], [&](int k, int, int) { n += (k == i); return 0; });
     return n;
 }
 
-int f8_net_run(f8_net* net, const int32_t* input, void* output, int N, void* stream) {
-    return run_common(net, input, output, N, stream, nullptr, 0);
-}
-int f8_net_run_f32(f8_net* net, const float* images, int normalize, void* output, int N, void* stream) {
-    if (!net || !net->finalized) return fail(F8_ERR_STATE, "f8_net_run_f32: not finalized");
-    if (!images) return fail(F8_ERR_INVALID, "f8_net_run_f32: null pointer");
-    // the consumer format of the network input: fraclen of the input tensor, signedness of the conv(s) reading it
-    const Tensor& in = net->tensors[net->nodes[0].out];
-    int sgn = -1;
-    for (int c : in.consumers) {
-        const Node& nd = net->nodes[c];
-        if (nd.kind != N_CONV && nd.kind != N_LINEAR) return fail(F8_ERR_UNSUPPORTED, "f8_net_run_f32: the input must feed convolutions");
-        if (sgn >= 0 && sgn != (nd.cd.input_signed ? 1 : 0)) return fail(F8_ERR_UNSUPPORTED, "f8_net_run_f32: consumers disagree on signedness");
-        sgn = nd.cd.input_signed ? 1 : 0;
-    }
-    if (sgn < 0) return fail(F8_ERR_UNSUPPORTED, "f8_net_run_f32: the input has no consumer");
-    if (normalize) {
-        if (in.fl < 0 || in.fl > (sgn ? 7 : 8)) return fail(F8_ERR_INVALID, "f8_net_run_f32: input fraclen %d outside [0,%d]", in.fl, sgn ? 7 : 8);
-        net->in_scale = (float)(1 << in.fl); net->in_lo = sgn ? -127 : 0; net->in_hi = sgn ? 127 : 255;
-    } else {
-        if (in.fl != 8 || sgn) return fail(F8_ERR_INVALID, "f8_net_run_f32: normalize == 0 needs an unsigned input at fraclen 8 (fix_train.py:689-692), net has fl %d %s",
-                                           in.fl, sgn ? "signed" : "unsigned");
-        net->in_scale = 255.f; net->in_lo = 0; net->in_hi = 255;      // images are in [0,1] (asserted >= 0 by the reference); 8-bit storage
-    }
-    net->in_f32 = images;
-    const int rc = run_common(net, (const int32_t*)images, output, N, stream, nullptr, 0);
-    net->in_f32 = nullptr;
-    return rc;
+// ---- the run entries.  Each consumes the two one-shots (begin_run) before any check of its own: a call that fails for whatever
+// reason leaves nothing armed for a later, unrelated run (by then the caller's event or buffers may be gone) ----
+static RunIO begin_run(f8_net* net, const void* in, void* out) {
+    RunIO io; io.in = in; io.out = out;
+    if (!net) return io;
+    io.in_ready = net->input_ready; net->input_ready = nullptr;
+    io.have_bufs = net->out_bufs_set; net->out_bufs_set = false;
+    if (io.have_bufs) memcpy(io.bufs, net->out_bufs, sizeof io.bufs);
+    return io;
 }
 // sign of the network input's consumers (0 unsigned, 1 signed, < 0 status)
 static int input_sign(const f8_net* net, const char* who) {
@@ -3667,14 +3643,45 @@ static int input_sign(const f8_net* net, const char* who) {
     if (sgn < 0) return fail(F8_ERR_UNSUPPORTED, "%s: the input has no consumer", who);
     return sgn;
 }
+// the head format an image entry can quantise to: any 8-bit fraclen with `normalize`, the pixel values themselves (unsigned, fraclen 8) without
+static int check_input_format(const f8_net* net, int normalize, int sgn, const char* who) {
+    const int fl = net->tensors[net->nodes[0].out].fl;
+    if (normalize && (fl < 0 || fl > (sgn ? 7 : 8))) return fail(F8_ERR_INVALID, "%s: input fraclen %d outside [0,%d]", who, fl, sgn ? 7 : 8);
+    if (!normalize && (fl != 8 || sgn))
+        return fail(F8_ERR_INVALID, "%s: normalize == 0 needs an unsigned input at fraclen 8 (fix_train.py:689-692), net has fl %d %s", who, fl, sgn ? "signed" : "unsigned");
+    return F8_OK;
+}
 
+int f8_net_run(f8_net* net, const int32_t* input, void* output, int N, void* stream) {
+    return run_common(net, begin_run(net, input, output), N, stream, nullptr, 0);
+}
+int f8_net_run_profiled(f8_net* net, const int32_t* input, void* output, int N, void* stream, float* ms, int cap) {
+    const RunIO io = begin_run(net, input, output);
+    if (!ms) return fail(F8_ERR_INVALID, "f8_net_run_profiled: null ms");
+    return run_common(net, io, N, stream, ms, cap);
+}
+int f8_net_run_f32(f8_net* net, const float* images, int normalize, void* output, int N, void* stream) {
+    RunIO io = begin_run(net, images, output);
+    if (!net || !net->finalized) return fail(F8_ERR_STATE, "f8_net_run_f32: not finalized");
+    if (!images) return fail(F8_ERR_INVALID, "f8_net_run_f32: null pointer");
+    const int sgn = input_sign(net, "f8_net_run_f32");
+    if (sgn < 0) return sgn;
+    if (const int rc = check_input_format(net, normalize, sgn, "f8_net_run_f32")) return rc;
+    io.kind = RunIO::F32;              // (normalize == 0: images are in [0,1], asserted >= 0 by the reference; 8-bit storage)
+    io.scale = normalize ? (float)(1 << net->tensors[net->nodes[0].out].fl) : 255.f; io.lo = sgn ? -127 : 0; io.hi = sgn ? 127 : 255;
+    return run_common(net, io, N, stream, nullptr, 0);
+}
 int f8_net_run_u8(f8_net* net, const uint8_t* images, int nhwc, int normalize, const float* mean, const float* stdv, void* output, int N, void* stream) {
+    RunIO io = begin_run(net, images, output);
     if (!net || !net->finalized) return fail(F8_ERR_STATE, "f8_net_run_u8: not finalized");
     if (!images) return fail(F8_ERR_INVALID, "f8_net_run_u8: null pointer");
     const Tensor& in = net->tensors[net->nodes[0].out];
     if (in.C > 3 && normalize) return fail(F8_ERR_UNSUPPORTED, "f8_net_run_u8: mean / std are given for 3 channels");
     const int sgn = input_sign(net, "f8_net_run_u8");
     if (sgn < 0) return sgn;
+    if (normalize && (!mean || !stdv)) return fail(F8_ERR_INVALID, "f8_net_run_u8: normalize needs mean and std");
+    if (const int rc = check_input_format(net, normalize, sgn, "f8_net_run_u8")) return rc;
+    for (int c = 0; normalize && c < 3; ++c) if (!(stdv[c] != 0.f)) return fail(F8_ERR_INVALID, "f8_net_run_u8: std[%d] is zero", c);
     // The decoder-side pipeline of the reference, per pixel value k of channel c, in the float32 operations torch executes
     // (fix_train.py:299-329 transforms.ToTensor / Normalize, then :683-692):
     //   t = float(k) / 255                        ToTensor
@@ -3682,13 +3689,7 @@ int f8_net_run_u8(f8_net* net, const uint8_t* images, int nhwc, int normalize, c
     //   normalize != 0:  t = (t - mean[c]) / std[c];  x_int = clamp(round_half_even(t * 2^fl), +-127 or [0,255])   (fix_quant)
     // A uint8 has 256 values: the whole pipeline is a 3 x 256 table built here on the host (IEEE single precision, one
     // rounding per operation as in torch) and looked up inside the input kernel.
-    if (normalize) {
-        if (!mean || !stdv) return fail(F8_ERR_INVALID, "f8_net_run_u8: normalize needs mean and std");
-        if (in.fl < 0 || in.fl > (sgn ? 7 : 8)) return fail(F8_ERR_INVALID, "f8_net_run_u8: input fraclen %d outside [0,%d]", in.fl, sgn ? 7 : 8);
-        for (int c = 0; c < 3; ++c) if (!(stdv[c] != 0.f)) return fail(F8_ERR_INVALID, "f8_net_run_u8: std[%d] is zero", c);
-    } else if (in.fl != 8 || sgn) {
-        return fail(F8_ERR_INVALID, "f8_net_run_u8: normalize == 0 needs an unsigned input at fraclen 8 (fix_train.py:689-692), net has fl %d %s", in.fl, sgn ? "signed" : "unsigned");
-    }
+    int16_t lut[3 * 256];
     const float scale = (float)(1 << (normalize ? in.fl : 0));
     const float lo = sgn ? -127.f : 0.f, hi = sgn ? 127.f : 255.f;
     for (int c = 0; c < 3; ++c)
@@ -3704,17 +3705,10 @@ int f8_net_run_u8(f8_net* net, const uint8_t* images, int nhwc, int normalize, c
                 rr = rr < lo ? lo : (rr > hi ? hi : rr);
                 v = (int)rr;
             }
-            net->in_lut[c * 256 + k] = (int16_t)v;
+            lut[c * 256 + k] = (int16_t)v;
         }
-    net->in_u8 = images; net->in_u8_nhwc = nhwc ? 1 : 0;
-    const int rc = run_common(net, (const int32_t*)images, output, N, stream, nullptr, 0);
-    net->in_u8 = nullptr;
-    return rc;
-}
-
-int f8_net_run_profiled(f8_net* net, const int32_t* input, void* output, int N, void* stream, float* ms, int cap) {
-    if (!ms) return fail(F8_ERR_INVALID, "f8_net_run_profiled: null ms");
-    return run_common(net, input, output, N, stream, ms, cap);
+    io.kind = nhwc ? RunIO::U8_NHWC : RunIO::U8; io.lut = lut;
+    return run_common(net, io, N, stream, nullptr, 0);
 }
 
 }  // extern "C"

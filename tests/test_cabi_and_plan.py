@@ -411,3 +411,72 @@ def test_essential_vector_work_per_launch_follows_the_reference_semantics():
     assert net.get_option('err_mirror') == 0                     # read-only state key: no mirror before the upload
     with pytest.raises(Exception):
         net.set_option('err_mirror', 1)
+
+
+F8_ERR_INVALID, F8_ERR_UNSUPPORTED, F8_ERR_STATE = -1, -2, -5
+_PTR = ctypes.c_void_p(4096)              # stands for a device buffer: every call below fails before anything is dereferenced or uploaded
+
+
+def _head_net(input_fl, signed, C=3):
+    """input [C,8,8] at `input_fl` -> one 3x3 / 2 conv (a net's head) -> output, finalized for 2 images."""
+    net = F8Net()
+    t = net.input(C, 8, 8, input_fl)
+    w = np.ones((32, C, 3, 3), np.int32)
+    t = net.conv(t, w, None, stride=2, pad=1, groups=1, weight_fl=6, input_fl=4, input_signed=signed, quant_input=False, relu=True)
+    net.output(t, as_float=False)
+    net.finalize(2)
+    return net
+
+
+def _run_f32(net, normalize, images=_PTR):
+    return net._L.f8_net_run_f32(net._h, images, normalize, _PTR, 1, None)
+
+
+def _run_u8(net, normalize, mean=(0.5, 0.5, 0.5), std=(0.25, 0.25, 0.25), images=_PTR):
+    m = (ctypes.c_float * 3)(*mean) if mean is not None else None
+    s = (ctypes.c_float * 3)(*std) if std is not None else None
+    return net._L.f8_net_run_u8(net._h, images, 0, normalize, m, s, _PTR, 1, None)
+
+
+def _err(net):
+    return net._L.f8_last_error().decode()
+
+
+def test_image_entries_share_the_input_format_checks():
+    """f8_net_run_f32 and f8_net_run_u8: status and message of every check they make before the run proper, each under the entry's own name."""
+    signed, signed8 = _head_net(6, True), _head_net(8, True)
+    wide = _head_net(10, False)               # no 8-bit format has 10 fraction bits
+    for name, run in (('f8_net_run_f32', _run_f32), ('f8_net_run_u8', _run_u8)):
+        assert run(signed, 0) == F8_ERR_INVALID
+        assert _err(signed) == f'{name}: normalize == 0 needs an unsigned input at fraclen 8 (fix_train.py:689-692), net has fl 6 signed'
+        assert run(wide, 0) == F8_ERR_INVALID
+        assert _err(wide) == f'{name}: normalize == 0 needs an unsigned input at fraclen 8 (fix_train.py:689-692), net has fl 10 unsigned'
+        assert run(wide, 1) == F8_ERR_INVALID and _err(wide) == f'{name}: input fraclen 10 outside [0,8]'
+        assert run(signed8, 1) == F8_ERR_INVALID and _err(signed8) == f'{name}: input fraclen 8 outside [0,7]'
+        assert run(signed, 1, images=None) == F8_ERR_INVALID and _err(signed) == f'{name}: null pointer'
+        raw = F8Net()
+        raw.input(3, 8, 8, 6)
+        assert run(raw, 1) == F8_ERR_STATE and _err(raw) == f'{name}: not finalized'
+    # f8_net_run_u8's own: more than 3 channels comes first, then mean / std, then the range, then a zero std
+    assert _run_u8(signed, 1, mean=None) == F8_ERR_INVALID and _err(signed) == 'f8_net_run_u8: normalize needs mean and std'
+    assert _run_u8(wide, 1, std=None) == F8_ERR_INVALID and _err(wide) == 'f8_net_run_u8: normalize needs mean and std'
+    assert _run_u8(signed, 1, std=(0.25, 0.0, 0.25)) == F8_ERR_INVALID and _err(signed) == 'f8_net_run_u8: std[1] is zero'
+    assert _run_u8(wide, 1, std=(0.0, 0.25, 0.25)) == F8_ERR_INVALID and _err(wide) == 'f8_net_run_u8: input fraclen 10 outside [0,8]'
+    four = _head_net(6, True, C=4)
+    assert _run_u8(four, 1, mean=None) == F8_ERR_UNSUPPORTED and _err(four) == 'f8_net_run_u8: mean / std are given for 3 channels'
+    assert _run_u8(four, 0) == F8_ERR_INVALID and _err(four).startswith('f8_net_run_u8: normalize == 0 needs')
+
+
+def test_a_run_that_fails_its_own_checks_consumes_the_output_buffers():
+    """The one-shots (f8_net_set_output_buffers, f8_net_set_input_ready) are consumed by the next run entry whatever becomes of it: the
+    buffers handed over before an f8_net_run_f32 that fails its validation are not there for the run after it."""
+    from test_outputs_plan import _chain_of_convs
+    net, ts = _chain_of_convs(2)
+    net.output(ts[1]), net.output(ts[0])
+    net.finalize(2)
+    L, h = net._L, net._h
+    bufs = (ctypes.c_void_p * 1)(8192)
+    assert L.f8_net_set_output_buffers(h, bufs, 1) == 0
+    assert _run_f32(net, 0) == F8_ERR_INVALID and 'normalize == 0 needs' in _err(net)       # (a signed input at fraclen 6)
+    assert L.f8_net_run(h, _PTR, _PTR, 1, None) == F8_ERR_STATE
+    assert 'hand over the buffers of outputs 1 .. with f8_net_set_output_buffers before every run' in _err(net)

@@ -230,3 +230,46 @@ def test_uint8_entry_through_the_fused_heads(dev, arch, nhwc):
         img = torch.from_numpy(np.ascontiguousarray(u8.transpose(0, 2, 3, 1)) if nhwc else u8).to(dev)
         got = net.run_u8(img, nhwc=nhwc).cpu().numpy()
         np.testing.assert_array_equal(got, want)
+
+
+def test_one_handle_takes_every_input_kind_under_every_schedule(dev):
+    """One handle fed int32 values, fp32 images, uint8 planes and uint8 NHWC pixels in turn — with an image entry that fails its own
+    validation (its input-ready event armed) in between — without pipelining, with split runs in flight and with alternating whole
+    batches, at the handle's batch and at one image.  Nothing of a call may reach the next: an unsigned fraclen-8 head sees the pixel
+    values themselves, so every result is the oracle's logits for those integers."""
+    from f8net_amd import _lib
+    from f8net_amd.net import build_net
+    spec = topology.get('resnet18', num_classes=20)
+    params = synth.make_params(spec, seed=41)
+    net = build_net(spec, params, max_batch=3, hw=64)
+    u8 = synth.rand_uniform_int(43, 'kinds', (3, 3, 64, 64), 0, 255).astype(np.uint8)
+    want = oracle.net_forward(spec, params, u8.astype(np.int32), 8)
+    outs = [torch.empty((3, 20), dtype=torch.float32 if net.out_float else torch.int32, device=dev) for _ in range(2)]
+    for n in (3, 1):
+        ints = torch.from_numpy(u8[:n].astype(np.int32)).to(dev)
+        f32 = torch.from_numpy(u8[:n].astype(np.float32) / np.float32(255.0)).to(dev)
+        planes = torch.from_numpy(u8[:n]).to(dev)
+        pixels = torch.from_numpy(np.ascontiguousarray(u8[:n].transpose(0, 2, 3, 1))).to(dev)
+        torch.cuda.synchronize()
+        for mode in (0, 1, 2):
+            net.set_pipelined(mode)
+            got = []
+
+            def keep(run, *a, **kw):             # consecutive runs write alternating tensors; the copy is ordered behind the run
+                out = outs[len(got) % 2][:n]
+                got.append(run(*a, out=out, **kw).clone())
+
+            keep(net.run, ints)
+            keep(net.run_f32, f32, normalize=False)
+            keep(net.run_u8, planes)
+            keep(net.run_u8, pixels, nhwc=True)
+            ready = torch.cuda.Event()
+            ready.record()
+            net._input_ready(ready)
+            assert net._L.f8_net_run_f32(net._h, None, 0, outs[0].data_ptr(), n, None) == -1      # F8_ERR_INVALID: null images
+            assert _lib.lib().f8_last_error() == b'f8_net_run_f32: null pointer'
+            keep(net.run, ints)
+            torch.cuda.synchronize()
+            for k, g in enumerate(got):
+                np.testing.assert_array_equal(g.cpu().numpy(), want[:n], err_msg=f'N={n} pipelined={mode} run {k}')
+    net.check()
