@@ -38,6 +38,7 @@ struct Options {
     int fuse_head2 = 1;          // MobileNet-V2 head (3x3 / 2 conv, depthwise 3x3, 1x1) as one row-walking launch (f8_stem.hip, H2)
     int fuse_ir = 1;             // MobileNet-V2 inverted residual (expand -> depthwise -> project) in one launch: 1 = where it wins, 2 = always
     int fuse_irchain = 0;        // runs of >= 2 consecutive stride-1 inverted residuals on a small map in ONE launch, one workgroup per image (f8_irchain.hip)
+    int fuse_irk = 0;            // inverted residual around a depthwise 5x5 / 7x7 (pad K / 2) in ONE launch (f8_irk.hip); K = 3 stays fuse_ir's
     int fuse_dws = 0;            // MobileNet-V1 depthwise-separable block (depthwise 3x3 -> 1x1) in ONE launch, the depthwise result only in LDS (f8_dws.hip)
     int fuse_head_dws = 0;       // MobileNet-V1 head + first depthwise-separable block (3x3 / 2 conv, depthwise 3x3, 1x1 to 32 / 64 channels [ReLU]) as one row-walking launch (f8_head_dws.hip)
     int fuse_dws7 = 0;           // ... the same for blocks whose OUTPUT map is 7 x 7, the average pool behind the last one summed in the launch (f8_dws7.hip)
@@ -305,6 +306,26 @@ struct IRArgs {
     uint32_t mW, mHW, mWo, mRWo; int32_t s1W, s2W, s1HW, s2HW, s1Wo, s2Wo, s1RWo, s2RWo;
 };
 
+// One launch for an inverted-residual block around a depthwise K x K, K = 5 / 7, pad K / 2 (f8_irk.hip): IRArgs with run-time channel counts.
+struct IRKArgs {
+    const int8_t* x8;                      // block input, int8 NHWC [N*H*W][cin] in the expand conv's input format
+    const int32_t* xr;                     // block input, int32 I32T (residual operand) or nullptr
+    const int8_t* w0; const int32_t* b0;   // expand  [E32][cin], offset-corrected bias [E32]
+    const int8_t* wd4; const int32_t* bd4; // depthwise: pack_dwk_weights' dot4 image [E32/4][K][ceil(K/4)][4] dwords, bias (+128*sum(w) for unsigned inputs) [E32]
+    const int8_t* w4; const int32_t* b4;   // project [cout][E32], offset-corrected bias [cout]
+    int32_t K, cin, cout;                  // depthwise kernel size; channel counts padded to 32
+    int32_t N, H, W, Ho, Wo, stride, R, G, tiles_per_img, E32;   // R output rows per tile (tiles_per_img = ceil(Ho / R)) or G whole images (irk_config)
+    int32_t n1, lo1, hi1; uint32_t xor1;   // requant expand output -> depthwise input format (xor1 is also the patch's pad value)
+    int32_t n2, lo2, hi2; uint32_t xor2;   // requant depthwise output -> project input format
+    int32_t relu_a, relu_b, relu0;         // ReLU after expand / depthwise / project
+    int32_t acc_shl, res_shl, relu1;       // residual join
+    int32_t* out32; QuantOut q[2];
+    int32_t xp, off_patch, off_mid2, off_w;   // LDS layout (filled by launch_fused_irk)
+    int32_t QS;                            // P2 items per output row: ceil(Wo / 4)
+    // magic numbers (fast_div) for / W, / (H*W), / Wo, / (R*Wo), / QS, / (R*QS): [magic, sh1, sh2]
+    uint32_t mW, mHW, mWo, mRWo, mQS, mRQS; int32_t s1W, s2W, s1HW, s2HW, s1Wo, s2Wo, s1RWo, s2RWo, s1QS, s2QS, s1RQS, s2RQS;
+};
+
 // One launch for a run of consecutive stride-1 inverted-residual blocks on one map, one workgroup per image (f8_irchain.hip): the int8 block
 // inputs and the int32 stream between the blocks stay in LDS.  Weights as IRArgs (the fused_ir images), channel counts padded to 32.
 struct IRChainBlk {
@@ -486,6 +507,12 @@ bool fused_ir_config(int cinS, int coutS, int H, int W, int stride, int* R, int*
 int fused_ir_inst(const IRArgs& a, int coutS);
 int fused_ir_kernel_name(char* buf, size_t cap, int cinS, int coutS, int inst);
 hipError_t launch_fused_ir(const IRArgs& a, int cinS, int coutS, int inst, hipStream_t s);
+// inverted residual around a depthwise 5x5 / 7x7, pad K / 2 (f8_irk.hip): padded channel counts; the tile (R rows, or G whole images) that fits LDS
+bool irk_supported(int K, int cinS, int coutS);
+bool irk_config(int K, int cinS, int coutS, int H, int W, int stride, int* R, int* G);
+int irk_inst(const IRKArgs& a);                                    // 2: integer ReLU / unsigned / right-shift instance, 0: any format
+int irk_kernel_name(char* buf, size_t cap, int K, int coutS, int inst);
+hipError_t launch_fused_irk(const IRKArgs& a, int inst, hipStream_t s);
 // a run of stride-1 inverted residuals in one launch (f8_irchain.hip): H x W map, the largest padded block input / output and the widest int32
 // stream a later block joins (keep_max; 0: none)
 bool irchain_supported(int H, int W, int cin_max, int cout_max, int keep_max);

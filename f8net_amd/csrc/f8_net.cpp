@@ -78,10 +78,11 @@ struct Tensor {
 //   B_BASIC_OPENING stage-opening BasicBlock that opens such a launch: 3x3 / 2, second 3x3, host = the 1x1 / 2 shortcut
 //   B_BASIC_JOIN    its join alone (the cluster launch; its 3x3 / 2 runs on its own): second 3x3, host = shortcut
 //   B_IR            inverted residual: expand, depthwise, host = project (alone: f8_ir.hip, tile R x G; in a chain launch: f8_irchain.hip)
+//   B_IRK           inverted residual around a depthwise 5x5 / 7x7 (option fuse_irk, f8_irk.hip; tile R x G): expand, depthwise, host = project
 //   B_HEAD2         MobileNet-V2 head launch (f8_stem.hip, H2): 3x3 / 2 head conv, depthwise, host = the 1x1
 //   B_DWS           depthwise-separable block (option fuse_dws, f8_dws.hip; R rows per tile): body.0 = the depthwise 3x3, host = the 1x1;
 //                   I7 > 0: the form for a 7 x 7 output map (option fuse_dws7, f8_dws7.hip; I7 images per workgroup), the same block to every pass
-enum BlockKind { B_NONE, B_BOTTLENECK, B_OPENING, B_JOIN, B_P12, B_BASIC, B_BASIC_OPENING, B_BASIC_JOIN, B_IR, B_HEAD2, B_DWS };
+enum BlockKind { B_NONE, B_BOTTLENECK, B_OPENING, B_JOIN, B_P12, B_BASIC, B_BASIC_OPENING, B_BASIC_JOIN, B_IR, B_HEAD2, B_DWS, B_IRK };
 struct Block { BlockKind kind = B_NONE; int b0 = -1, b2 = -1, b4 = -1, sc = -1; bool s2 = false; int R = 0, G = 0, I7 = 0; };
 enum Role { R_NONE, R_B0, R_B2, R_B4, R_SC };
 // The chain launches: bottleneck stage (f8_chain.hip; the 7x7 stage over clusters, f8_cchain.hip), BasicBlocks (f8_bchain.hip), BasicBlocks of a 7x7 x 512
@@ -117,7 +118,7 @@ struct Node {
     size_t rc_off = 0, cc_off = 0; int ncc = 0;      // border-class tables (0 = single class)
     ConvTile tile{};
 };
-enum StepKind { S_INPUT, S_CONV, S_DW, S_ADD, S_MAXPOOL, S_AVGPOOL, S_REQUANT, S_OUTPUT, S_FUSED, S_STEMPOOL, S_IR, S_P12, S_CHAIN, S_BCHAIN, S_HEAD2, S_IRCHAIN, S_DWS, S_DWS7 };
+enum StepKind { S_INPUT, S_CONV, S_DW, S_ADD, S_MAXPOOL, S_AVGPOOL, S_REQUANT, S_OUTPUT, S_FUSED, S_STEMPOOL, S_IR, S_P12, S_CHAIN, S_BCHAIN, S_HEAD2, S_IRCHAIN, S_DWS, S_DWS7, S_IRK };
 // The kernel of a step whose kind has several, chosen once by the step's emitter (pass 3); bind_step, run_step and f8_net_autotune switch on it.
 //   S_CONV:  conv_igemm (f8_kernels.hip), the LDS-patch 3x3 (f8_conv3x3.hip), conv1x1_wreg (f8_wreg.hip), conv1x1_wstat (f8_wstat.hip),
 //            conv3x3s2_wreg (f8_s2conv.hip), the 1x1 conv + average pool (f8_pool.hip), the classifier fc_dense (f8_fc.hip)
@@ -140,7 +141,7 @@ struct Step {
     double bytes_per_img = 0, bytes_const = 0, ops_per_img = 0;
     double valu_per_img = 0;           // ESSENTIAL vector lane-operations per image (f8_net_launch_valu): what the reference's semantics need once the MFMAs are done
     // the launcher's arguments as far as the plan decides them (bind_step); run_step copies them and adds what the run decides
-    std::variant<std::monostate, ConvArgs, StemPoolArgs, FusedArgs, ChainArgs, BChainArgs, BCChainArgs, IRArgs, IRChainArgs, DwsArgs, Dws7Args, DwArgs, AddArgs, PoolArgs, AvgArgs, OutArgs> args;
+    std::variant<std::monostate, ConvArgs, StemPoolArgs, FusedArgs, ChainArgs, BChainArgs, BCChainArgs, IRArgs, IRKArgs, IRChainArgs, DwsArgs, Dws7Args, DwArgs, AddArgs, PoolArgs, AvgArgs, OutArgs> args;
     int inst = 0;                      // the instance the launcher starts (the family's *_inst, f8_internal.h; bind_step)
     // S_CHAIN / S_BCHAIN: geometry, workgroups per image and resident per CU, the 7x7 cluster form (f8_cchain.hip)
     int C = 0, MID = 0, H = 0, W = 0, cin0 = 0, tiles = 0, wg_per_cu = 1; bool cluster = false;
@@ -320,6 +321,7 @@ static const OptKey kOptKeys[] = {
     {"fuse_input", "F8_FUSE_INPUT", &Options::fuse_input, 0, 1, true},
     {"fuse_ir", "F8_FUSE_IR", &Options::fuse_ir, 0, 2, true},
     {"fuse_irchain", "F8_FUSE_IRCHAIN", &Options::fuse_irchain, 0, 1, true},
+    {"fuse_irk", "F8_FUSE_IRK", &Options::fuse_irk, 0, 1, true},
     {"fuse_dws", "F8_FUSE_DWS", &Options::fuse_dws, 0, 1, true},
     {"fuse_dws7", "F8_FUSE_DWS7", &Options::fuse_dws7, 0, 1, true},
     {"fuse_head_dws", "F8_FUSE_HEAD_DWS", &Options::fuse_head_dws, 0, 1, true},
@@ -828,8 +830,9 @@ static void pack_dw_weights(f8_net* net, Node& nd) {
     }
 }
 
-// "General depthwise": every accepted depthwise conv that is not 3x3 / pad 1 (kernel 3 / 5 / 7, stride 1 / 2, pad 0 .. kernel / 2; add_conv_node).  No pass
-// of the planner fuses one (each matcher asks for kernel 3 and pad 1): always a launch of its own on the kernels of f8_dwk.hip.
+// "General depthwise": every accepted depthwise conv that is not 3x3 / pad 1 (kernel 3 / 5 / 7, stride 1 / 2, pad 0 .. kernel / 2; add_conv_node).  One pass
+// of the planner fuses one — 1e3, option fuse_irk: kernel 5 / 7 with pad kernel / 2 inside an inverted residual —; every other matcher asks for kernel 3
+// and pad 1, so anywhere else it is a launch of its own on the kernels of f8_dwk.hip.
 static bool dw_general(const f8_conv_desc& d) { return d.groups != 1 && !(d.kernel == 3 && d.pad == 1); }
 
 // The two weight images of a general depthwise conv, at offsets of their own (the 3x3 / pad 1 images are pack_dw_weights' and stay as they are):
@@ -1353,6 +1356,42 @@ static void plan_inverted_residuals(f8_net* net) {
 
 }
 
+// pass 1e3
+static void plan_inverted_residuals_k(f8_net* net) {
+    auto& T = net->tensors;
+    auto& ND = net->nodes;
+    const int nn = (int)ND.size();
+    // ---- 1e3. (option fuse_irk) the inverted residual of MnasNet / ProxylessNAS / FBNet: 1x1 expand -> depthwise 5x5 or 7x7 / 1 or 2, pad K / 2 -> 1x1
+    //           project [+ residual with the block input], intermediates read by nobody else and no output  ->  one launch (f8_irk.hip).  1e's conditions
+    //           with the depthwise geometry exchanged; K = 3 / pad 1 stays 1e's (its choice to leave small maps unfused included), pad < K / 2 stays
+    //           three launches.  Any format: the launch has a generic instance.
+    for (int i = 0; net->opt.fuse_irk && i < nn; ++i) {
+        Node& c = ND[i];
+        if (c.kind != N_CONV || c.cd.groups != 1 || c.cd.kernel != 1 || c.cd.stride != 1 || c.cd.pad != 0 || !c.cd.quant_input ||
+            claimed(net, i) || c.dual >= 0) continue;
+        const Tensor& tb = T[c.a];
+        if (tb.prod < 0 || tb.consumers.size() != 1 || is_output(net, c.a)) continue;
+        Node& b = ND[tb.prod];
+        if (b.kind != N_CONV || b.cd.groups == 1 || b.cd.groups != b.cd.cin || b.cd.cout != b.cd.cin || (b.cd.kernel != 5 && b.cd.kernel != 7) ||
+            b.cd.pad != b.cd.kernel / 2 || (b.cd.stride != 1 && b.cd.stride != 2) || !b.cd.quant_input || b.fused_add >= 0 || claimed(net, tb.prod)) continue;
+        const Tensor& ta = T[b.a];
+        if (ta.prod < 0 || ta.consumers.size() != 1 || is_output(net, b.a)) continue;
+        Node& a0 = ND[ta.prod];
+        if (a0.kind != N_CONV || a0.cd.groups != 1 || a0.cd.kernel != 1 || a0.cd.stride != 1 || a0.cd.pad != 0 || a0.fused_add >= 0 ||
+            claimed(net, ta.prod) || a0.dual >= 0 || !a0.cd.quant_input) continue;
+        if (T[a0.a].prod < 0 || ND[T[a0.a].prod].kind == N_INPUT) continue;      // the network input has its own layouts
+        if (c.fused_add >= 0) {                                   // a residual join must be with the block input, at stride 1
+            const Node& ad = ND[c.fused_add];
+            const int other = (ad.a == c.out) ? ad.b : ad.a;
+            if (other != a0.a || b.cd.stride != 1) continue;
+        }
+        const Tensor& x = T[a0.a];
+        int R = 0, G = 0;
+        if (!irk_config(b.cd.kernel, x.Cs, round_up(c.cd.cout, 32), x.H, x.W, b.cd.stride, &R, &G)) continue;
+        set_block(net, i, Block{B_IRK, ta.prod, tb.prod, i, -1, false, R, G});
+    }
+}
+
 // pass 1e2
 static void plan_inverted_residual_chains(f8_net* net) {
     auto& T = net->tensors;
@@ -1665,6 +1704,10 @@ static void plan_tensor_forms(f8_net* net) {
                         in_launch = pos >= 0 || role != R_B0;    // (alone: the expand conv reads the block input from HBM)
                         if (pos == 0 && role == R_B0) add_form(s, FORM_I8, n, nd.cd.input_signed ? 1 : 0);
                         if (pos <= 0 && role == R_B4 && nd.fused_add >= 0) add_form(stream(), FORM_I32, 0, 0);
+                        break;
+                    case B_IRK:                                  // the expand conv reads the block input from HBM; a join reads its int32 form
+                        in_launch = role != R_B0;
+                        if (role == R_B4 && nd.fused_add >= 0) add_form(stream(), FORM_I32, 0, 0);
                         break;
                     case B_BOTTLENECK:                           // in a chain (f8_chain.hip) an identity first block reads only the int32 form of the stage input
                         if (role == R_B0) { in_launch = pos >= 0; if (pos == 0) add_form(s, FORM_I32, 0, 0); }      // (alone: it reads the block input from HBM)
@@ -2020,6 +2063,36 @@ static int emit_ir(f8_net* net, int i, Step& st, std::vector<int>* extra) {
     return F8_OK;
 }
 
+// fused inverted residual around a depthwise 5x5 / 7x7: node i is the project conv
+static int emit_irk(f8_net* net, int i, Step& st, std::vector<int>* extra) {
+    auto& T = net->tensors; auto& ND = net->nodes;
+    Node& nd = ND[i];
+    const Block& r = nd.blk;
+    Node& na = ND[r.b0]; Node& nb = ND[r.b2];
+    const Tensor& x = T[na.a];
+    st.kind = S_IRK;
+    if (const int rc = conv_input_i8(net, na, &st.src_t, &st.src_f)) return rc;
+    pack_conv_weights(net, na);
+    pack_dwk_weights(net, nb);
+    pack_conv_weights(net, nd);
+    for (const Node* n : {&na, &nb, &nd}) { st.ops_per_img += conv_ops(net, *n); st.bytes_const += weight_bytes(net, *n); }
+    st.relu0 = nd.cd.relu;
+    const int out_t = join_output(net, nd, st);
+    if (nd.fused_add >= 0) {
+        st.res_t = na.a; st.res_f = find_form(x, FORM_I32, 0, 0);
+        join_shifts(T[nd.out].fl - x.fl, &st.acc_shl, &st.res_shl);
+    }
+    select_outputs(net, out_t, &st.out, extra);
+    const Tensor& o = T[out_t];
+    const double px = (double)x.H * x.W, pxo = (double)o.H * o.W;
+    st.valu_per_img = 3.0 * (px * na.cd.cout + pxo * nb.cd.cout) + (st.res_t >= 0 ? 2.0 * pxo * o.C : 0.0) + 3.0 * pxo * o.Cs * out_forms8(st);
+    st.bytes_per_img = px * x.Cs + (st.res_t >= 0 ? px * x.Cs * 4 : 0) + out_bytes(st, o, pxo);
+    char kb[200];
+    snprintf(kb, sizeof kb, "fused_irk%d_s%d_%s:", nb.cd.kernel, nb.cd.stride, r.G > 1 ? ("G" + std::to_string(r.G)).c_str() : ("R" + std::to_string(r.R)).c_str());
+    st.name = kb + block_names(net, r);
+    return F8_OK;
+}
+
 // depthwise-separable block: node i is the 1x1 conv
 static int emit_dws(f8_net* net, int i, Step& st, std::vector<int>* extra) {
     auto& T = net->tensors; auto& ND = net->nodes;
@@ -2180,6 +2253,7 @@ static int emit_conv_family(f8_net* net, int i, int max_batch, Step& st, std::ve
         case B_BOTTLENECK: case B_OPENING: return emit_fused(net, i, st, extra);
         case B_P12: return emit_p12(net, i, st, extra);
         case B_IR: return emit_ir(net, i, st, extra);
+        case B_IRK: return emit_irk(net, i, st, extra);
         case B_DWS: return nd.blk.I7 > 0 ? emit_dws7(net, i, st, extra) : emit_dws(net, i, st, extra);
         default: return emit_conv(net, i, max_batch, st, extra);
     }
@@ -2718,6 +2792,32 @@ static int bind_step(f8_net* net, Step& st) {
             fused_ir_kernel_name(kb, sizeof kb, x.Cs, nd.coutP, st.inst = fused_ir_inst(a, nd.coutP));
             out_formats(a.q); st.args = a; break;
         }
+        case S_IRK: {
+            const Block& r = nd.blk;
+            Node& na = ND[r.b0]; Node& nb = ND[r.b2];
+            const Tensor& x = T[st.src_t];
+            const Tensor& oT = T[nd.out];
+            IRKArgs a{};
+            a.w0 = W8(na.w_off); a.b0 = B32(na.b_off);
+            a.wd4 = W8(nb.rc_off); a.bd4 = B32(nb.cc_off);         // pack_dwk_weights' dot4 image; bias + 128 * sum(w) for unsigned inputs
+            a.w4 = W8(nd.w_off); a.b4 = B32(nd.b_off);
+            a.K = nb.cd.kernel; a.cin = x.Cs; a.cout = nd.coutP;
+            a.H = x.H; a.W = x.W; a.Ho = oT.H; a.Wo = oT.W; a.stride = nb.cd.stride; a.R = r.R; a.G = r.G;
+            a.tiles_per_img = (oT.H + r.R - 1) / r.R; a.E32 = na.coutP;
+            a.QS = (oT.W + 3) / 4;
+            fmt(nb, &a.n1, &a.lo1, &a.hi1, &a.xor1);
+            fmt(nd, &a.n2, &a.lo2, &a.hi2, &a.xor2);
+            a.relu_a = na.cd.relu; a.relu_b = nb.cd.relu; a.relu0 = st.relu0;
+            a.acc_shl = st.acc_shl; a.res_shl = st.res_shl; a.relu1 = st.relu1;
+            make_magic((uint32_t)x.W, &a.mW, &a.s1W, &a.s2W);
+            make_magic((uint32_t)(x.H * x.W), &a.mHW, &a.s1HW, &a.s2HW);
+            make_magic((uint32_t)oT.W, &a.mWo, &a.s1Wo, &a.s2Wo);
+            make_magic((uint32_t)(r.R * oT.W), &a.mRWo, &a.s1RWo, &a.s2RWo);
+            make_magic((uint32_t)a.QS, &a.mQS, &a.s1QS, &a.s2QS);
+            make_magic((uint32_t)(r.R * a.QS), &a.mRQS, &a.s1RQS, &a.s2RQS);
+            irk_kernel_name(kb, sizeof kb, a.K, a.cout, st.inst = irk_inst(a));      // integer requantisation whatever requant_float says (as f8_dwk.hip)
+            out_formats(a.q); st.args = a; break;
+        }
         case S_IRCHAIN: {
             const std::vector<int>& ch = nd.chain;
             const Tensor& x = T[st.src_t];
@@ -2851,6 +2951,7 @@ int f8_net_finalize(f8_net* net, int max_batch) {
     plan_stage_chains(net);                         // 1f: all consecutive bottleneck blocks of a stage in one launch
     plan_basic_block_chains(net);                   // 1g: the same for BasicBlocks
     plan_inverted_residuals(net);                   // 1e: MobileNet-V2 inverted residuals
+    plan_inverted_residuals_k(net);                 // 1e3: inverted residuals around a depthwise 5x5 / 7x7 (option fuse_irk)
     plan_inverted_residual_chains(net);             // 1e2: runs of stride-1 inverted residuals in one launch (option fuse_irchain)
     plan_mobilenet_v2_head(net);                    // 1h: MobileNet-V2 head conv + depthwise + 1x1
     plan_last_conv_and_pool(net);                   // 1i: the last 1x1 conv + the average pool
@@ -3173,6 +3274,14 @@ static int run_step(const f8_net* net, const RunIO& io, const Step& st, int n0, 
             if (st.res_t >= 0) a.xr = (const int32_t*)fp(T[st.res_t].forms[st.res_f]);
             fill_out(&a.out32, a.q);
             e = launch_fused_ir(a, x.Cs, nd.coutP, st.inst, s);
+            break;
+        }
+        case S_IRK: {
+            IRKArgs a = std::get<IRKArgs>(st.args);
+            a.x8 = (const int8_t*)fp(T[st.src_t].forms[st.src_f]); a.N = N;
+            if (st.res_t >= 0) a.xr = (const int32_t*)fp(T[st.res_t].forms[st.res_f]);
+            fill_out(&a.out32, a.q);
+            e = launch_fused_irk(a, st.inst, s);
             break;
         }
         case S_IRCHAIN: {

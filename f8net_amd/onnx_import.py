@@ -142,8 +142,9 @@ class IntGraph:
         return sd
 
     # -- planning through the C ABI -----------------------------------------------------------------------------------
-    def build_net(self, max_batch, hw=None, input_fraclen=None):
-        """Record the graph through libf8net.so's builder and plan it (f8_net_finalize)."""
+    def build_net(self, max_batch, hw=None, input_fraclen=None, options=None):
+        """Record the graph through libf8net.so's builder and plan it (f8_net_finalize).
+        options: {key: value} for f8_net_set_option, applied before planning (as net.build_net's)."""
         from .net import F8Net
         V, layer = self.solve_fraclens(input_fraclen)
         net = F8Net()
@@ -170,6 +171,8 @@ class IntGraph:
             elif o.kind == 'avgpool':
                 ids[t] = net.avgpool_sum(ids[o.src], AVGPOOL_SHIFT)
         net.output(ids[self.output], as_float=self.output_float)
+        for k, v in (options or {}).items():
+            net.set_option(k, v)
         return net.finalize(max_batch)
 
 

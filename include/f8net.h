@@ -259,7 +259,7 @@ int f8_net_check(f8_net* net);
  * before f8_net_finalize (F8_ERR_STATE afterwards); scheduling keys may change between runs.
  *   planning  : split (1..4 concurrent sub-batches of a run), arena_copies (0 = split; more: that many whole runs in flight under
  *               f8_net_set_pipelined(2) with pipeline_depth), fuse_blocks, fuse_stages (bit mask, -1 = auto), fuse_dual,
- *               fuse_ds, fuse_opener, fuse_fc (the classifier writes the caller's logits buffer itself), fuse_stem, fuse_input (the fused stem launch reads the caller's NCHW buffer itself), fuse_ir (1 = where it wins, 2 = every block), fuse_irchain (off by default; 1: runs of >= 2 consecutive stride-1 MobileNet-V2 inverted residuals on a map of at most 256 pixels — the 14x14 and 7x7 runs at 224x224 — in ONE launch, one workgroup per image, nothing between the blocks in HBM, f8_irchain.hip), fuse_dws (off by default; 1: a MobileNet-V1 depthwise-separable block — depthwise 3x3 / 1 or 2, ReLU, 1x1 — whose output map is at least 28 or exactly 14 wide and whose readers all take int8 in ONE launch, the depthwise result only in LDS, f8_dws.hip; the blocks on 7-wide maps stay two launches: the matrix-core depthwise walker has no 7-wide form — see fuse_dws7), fuse_dws7 (off by default, independent of fuse_dws; 1: such a block whose OUTPUT map is exactly 7x7 — input 7x7 at stride 1 or 14x14 at stride 2 — in ONE launch, f8_dws7.hip: the depthwise conv on v_dot4, up to four images per workgroup, the output-channel tiles cut into slices over workgroups; where the block output's only reader is the average pool and the pooled tensor is not the network output the pool is summed in that launch and the block output never exists), fuse_head_dws (off by default; 1: the MobileNet-V1 head — network input -> 3x3 / 2 conv to 32 channels, ReLU -> depthwise 3x3 / 1, ReLU -> 1x1 to at most 64 channels, with or without ReLU, int8 readers in at most two formats, input sides multiples of 4, at most 224 wide — in ONE row-walking launch that reads the caller's buffer itself, f8_head_dws.hip; with fuse_dws the first depthwise-separable block belongs to this launch), fuse_chain (all consecutive bottleneck blocks of a stage in one launch, the int32 residual stream in registers; it takes precedence over fuse_stages and over the chunk56 / chunk28 / chunk14 keys for the stages it plans: set fuse_chain = 0 to get the per-block launches those keys govern), chain_stack (1: a 14x14 stage chain tiles image PAIRS as one 28-row map — 7 tiles of 4 rows per pair instead of 4 per image, zeros across the seam in the 3x3; same kernel symbol, 0: one image per tile column), fuse_tail (the join of a stride-2 stage-opening block opens that launch: its int32 output never exists), fuse_chain7 (the 7x7 bottleneck stage — that join, its identity blocks and the average pool behind them — as one launch over clusters of eight workgroups, f8_cchain.hip; 0: the dual-GEMM / fused_p12 / residual-join launches of rounds 3 - 5), fuse_pool (the network's last 1x1 conv, with its residual join, and the average pool behind it in one launch),
+ *               fuse_ds, fuse_opener, fuse_fc (the classifier writes the caller's logits buffer itself), fuse_stem, fuse_input (the fused stem launch reads the caller's NCHW buffer itself), fuse_ir (1 = where it wins, 2 = every block), fuse_irk (off by default; 1: an inverted residual around a depthwise 5x5 or 7x7 — stride-1 1x1 expand, depthwise / 1 or 2 with pad = kernel / 2, stride-1 1x1 project, optionally joined with the block input at stride 1; block input of at most 192 and output of at most 320 padded channels, intermediates read by nobody else and no output — in ONE launch, the expanded tensors only in LDS, f8_irk.hip; everything else, pad < kernel / 2 included, stays three launches, and 3x3 blocks stay fuse_ir's; integer requantisation whatever requant_float says), fuse_irchain (off by default; 1: runs of >= 2 consecutive stride-1 MobileNet-V2 inverted residuals on a map of at most 256 pixels — the 14x14 and 7x7 runs at 224x224 — in ONE launch, one workgroup per image, nothing between the blocks in HBM, f8_irchain.hip), fuse_dws (off by default; 1: a MobileNet-V1 depthwise-separable block — depthwise 3x3 / 1 or 2, ReLU, 1x1 — whose output map is at least 28 or exactly 14 wide and whose readers all take int8 in ONE launch, the depthwise result only in LDS, f8_dws.hip; the blocks on 7-wide maps stay two launches: the matrix-core depthwise walker has no 7-wide form — see fuse_dws7), fuse_dws7 (off by default, independent of fuse_dws; 1: such a block whose OUTPUT map is exactly 7x7 — input 7x7 at stride 1 or 14x14 at stride 2 — in ONE launch, f8_dws7.hip: the depthwise conv on v_dot4, up to four images per workgroup, the output-channel tiles cut into slices over workgroups; where the block output's only reader is the average pool and the pooled tensor is not the network output the pool is summed in that launch and the block output never exists), fuse_head_dws (off by default; 1: the MobileNet-V1 head — network input -> 3x3 / 2 conv to 32 channels, ReLU -> depthwise 3x3 / 1, ReLU -> 1x1 to at most 64 channels, with or without ReLU, int8 readers in at most two formats, input sides multiples of 4, at most 224 wide — in ONE row-walking launch that reads the caller's buffer itself, f8_head_dws.hip; with fuse_dws the first depthwise-separable block belongs to this launch), fuse_chain (all consecutive bottleneck blocks of a stage in one launch, the int32 residual stream in registers; it takes precedence over fuse_stages and over the chunk56 / chunk28 / chunk14 keys for the stages it plans: set fuse_chain = 0 to get the per-block launches those keys govern), chain_stack (1: a 14x14 stage chain tiles image PAIRS as one 28-row map — 7 tiles of 4 rows per pair instead of 4 per image, zeros across the seam in the 3x3; same kernel symbol, 0: one image per tile column), fuse_tail (the join of a stride-2 stage-opening block opens that launch: its int32 output never exists), fuse_chain7 (the 7x7 bottleneck stage — that join, its identity blocks and the average pool behind them — as one launch over clusters of eight workgroups, f8_cchain.hip; 0: the dual-GEMM / fused_p12 / residual-join launches of rounds 3 - 5), fuse_pool (the network's last 1x1 conv, with its residual join, and the average pool behind it in one launch),
  *               fuse_bchain (the same for BasicBlock stages: 1 = consecutive identity blocks, 2 = with the stage-opening block in front), fuse_bchain7 (off by
  *               default; the 7x7 x 512 BasicBlock stage of ResNet-18 / 34 over clusters of eight workgroups, f8_bcchain.hip: 1 = its consecutive identity blocks
  *               in one launch, 2 = with the JOIN of the stage-opening block in front — its stride-2 body.0 stays a launch of its own; an average pool that

@@ -35,6 +35,9 @@ PLANNING = {
     'dw_mma': (0, 1), 'stem_rows': (0, 1), 'opener_stg': (0, 1), 'requant_float': (0, 1), 'arena_copies': (0, 4), 'shared_streams': (0, 1),
     'whole_batch_launches': (0, 1), 'tap_tiled': (0, 1),
 }
+# keys added after the digest's matrix was fixed: each alone at every value, appended behind the matrix and only where the library under
+# test knows the key — so a parent library yields exactly its old lines and the lines of a new key are additions (never part of the random mixes)
+LATER = {'fuse_irk': (0, 1)}
 
 
 def option_sets(defaults):
@@ -85,6 +88,12 @@ def plan_lines(job):
     for k in PLANNING:
         probe.set_option(k, probe.get_option(k))                  # every key exists and is settable before finalize
     sets = option_sets({k: probe.get_option(k) for k in PLANNING})
+    for k, (lo, hi) in LATER.items():
+        try:
+            dflt = probe.get_option(k)
+        except F8Error:
+            continue                                              # an older library
+        sets += [(f'{k}={v}', {k: v}) for v in range(lo, hi + 1) if v != dflt]
     lines = []
     for name, opts in sets:
         if only and only not in name:

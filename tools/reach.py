@@ -2,7 +2,10 @@
 """Which kernels do the DEFAULT plans of the four nets reach?  Planning needs no GPU:
     python tools/reach.py            -> markdown table (kernel symbol x net / batch), used by DESIGN.md §4
 Batches 1 / 8 / 128 / 256 at 224x224; 128 and 256 also with `whole_batch_launches` (what bench.py plans under pipelining mode 2); `t` = batch 128
-planned with further outputs (`taps=`: the last block of the last four stages and 'avgpool') — the only plans that reach `tap_kernel`."""
+planned with further outputs (`taps=`: the last block of the last four stages and 'avgpool') — the only plans that reach `tap_kernel`.
+    python tools/reach.py --opt fuse_irk=1 [--opt key=value ..]   -> the same table with these planning options on top of the defaults
+(the fuse options that are off by default: fuse_irchain, fuse_dws, fuse_dws7, fuse_head_dws, fuse_bchain7, fuse_irk — `fuse_irk` reaches
+no kernel on these four nets: none of them has a depthwise 5x5 / 7x7)."""
 import os
 import re
 import sys
@@ -19,14 +22,24 @@ def family(sym):
     return re.sub(r'<.*', '', sym.replace('f8::', ''))
 
 
+def cli_options():
+    opts = {}
+    for i, a in enumerate(sys.argv):
+        if a == '--opt' and i + 1 < len(sys.argv):
+            k, v = sys.argv[i + 1].split('=')
+            opts[k] = int(v)
+    return opts
+
+
 def main():
     reach = {}
+    extra = cli_options()
     for arch in NETS:
         spec = topology.get(arch, normalize=(arch == 'resnet50'))
         params = synth.reference_params(spec, seed=1234)
         stages = {b.name.rsplit('_layer_', 1)[0]: b.name for b in spec.blocks}
         for bs, whole, tapped in CASES:
-            net = build_net(spec, params, max_batch=bs, hw=224, options={'whole_batch_launches': 1} if whole else None,
+            net = build_net(spec, params, max_batch=bs, hw=224, options=dict(extra, whole_batch_launches=1) if whole else (extra or None),
                             taps=list(stages.values())[-4:] + ['avgpool'] if tapped else ())
             whole = 'w' if whole else ('t' if tapped else '')
             for i in range(net.num_launches):
