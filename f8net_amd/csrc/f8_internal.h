@@ -69,6 +69,8 @@ struct Options {
     int requant_float = 0;       // 0 (default since round 5: BASELINE north_star — no FP32 multiply in any epilogue): integer shift / round-half-even /
                                  // clamp in every kernel; 1: ReLU -> unsigned 8-bit right shifts of values the planner can bound may run through the
                                  // float converter (v_cvt_f32_i32, v_mul_f32 by 2^-n, v_cvt_pk_u8_f32: exact where planned, f8_device.h)
+    int grouped = 0;             // grouped convs (1 < groups < cin): 0 = refused by f8_net_conv; 1 = accepted, on gconv3x3_kernel (f8_gconv.hip) where it applies and as the
+                                 // dense expansion (the plain conv kernels over block-diagonal weights) elsewhere; 2 = accepted, always the dense expansion
     int tap_tiled = 1;           // network outputs 1 .. leave on tap_kernel (f8_tap.hip: walks the I32T blocks, every loaded byte used); 0: on output_kernel like output 0
     int check_input_range = 1;   // int32 inputs that are NARROWED to the head's 8-bit format (no requant) are range-checked on the device; f8_net_check reports
 };
@@ -135,6 +137,23 @@ struct DwArgs {
                                            // float requantisation (requant_u8x4, f8_device.h) equals the wrapping integer one
     int32_t rq_int;                        // Options::requant_float == 0: integer requantisation only
     int32_t k;                             // kernel size; read by the general depthwise kernels only (f8_dwk.hip)
+};
+
+// Grouped 3x3 (f8_gconv.hip): cin == cout, cg = C / groups divides 32, stride 1 / 2, pad 0 / 1.  The kernel sees 32-channel slices only.
+struct GConvArgs {
+    const int8_t* x; uint32_t x_bytes;     // NHWC int8 [N][H][W][Cs]
+    const int8_t* w;                       // [Cs / 32 slices][9 taps][64 lanes][16 B]: block-diagonal 32 x 32 tap blocks in MFMA-fragment order (pack_gconv_weights)
+    const int32_t* bias;                   // [ncls][Cs] border-class bias table (as ConvArgs)
+    const uint8_t* rowcls; const uint8_t* colcls; int32_t ncc;   // class of output row p / col q; ncc = 0: single class
+    int32_t N, H, W, P, Q, Cs, stride, pad;
+    int32_t R, TW, G;                      // a workgroup's tile: R output rows x TW output columns of G images (gconv_tile; G > 1: whole images)
+    int32_t tiles_r, tiles_c;              // tiles per image
+    int32_t PR, PW;                        // its haloed input patch, pixels per image: (R - 1) stride + 3 rows of (TW - 1) stride + 3
+    // magic numbers (fast_div) for / (PR * PW), / PW, / (R * TW), / TW: [magic, sh1, sh2]
+    uint32_t mIPP, mPW, mRTW, mTW; int32_t s1IPP, s2IPP, s1PW, s2PW, s1RTW, s2RTW, s1TW, s2TW;
+    int32_t relu0;
+    int32_t* out32;
+    QuantOut q[2];
 };
 
 struct PoolArgs {                          // max-pool, NHWC
@@ -553,6 +572,10 @@ hipError_t launch_dwconv(const DwArgs& a, int inst, hipStream_t s);
 int dwk_inst(const DwArgs& a, bool out32, bool dot4);
 int dwk_kernel_name(char* buf, size_t cap, const DwArgs& a, int inst);
 hipError_t launch_dwk(const DwArgs& a, int inst, hipStream_t s);
+// grouped 3x3 on the slice-diagonal MFMA kernel (f8_gconv.hip): the tile of a P x Q output map (R rows x TW columns, or G whole images)
+void gconv_tile(int P, int Q, int stride, int* R, int* TW, int* G);
+int gconv_kernel_name(char* buf, size_t cap, const GConvArgs& a);
+hipError_t launch_gconv(const GConvArgs& a, hipStream_t s);
 int maxpool_inst(const PoolArgs& a);
 const char* maxpool_kernel_name(int inst);
 hipError_t launch_maxpool(const PoolArgs& a, int inst, hipStream_t s);

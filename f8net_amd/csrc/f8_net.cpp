@@ -101,7 +101,8 @@ struct Node {
     // planning
     int fused_into = -1;               // add: conv node that carries it
     int fused_add = -1;                // conv: add node carried
-    bool stem = false, depthwise = false;
+    bool stem = false, depthwise = false;   // depthwise: groups == cin == cout
+    bool grouped = false;              // 1 < groups < cin (option grouped): a launch of its own — gconv3x3_kernel (S_GCONV) or the dense expansion (S_CONV, gconv_kernel_applies)
     int absorbed_by = -1;              // conv that runs inside a fused block hosted by ANOTHER conv (node id of that host; set_block)
     Block blk;                         // the fused block this conv hosts (B_NONE: none)
     int sp_pool = -1, sp_conv = -1;      // stem conv <-> max-pool fused into one launch (f8_stem.hip)
@@ -118,7 +119,7 @@ struct Node {
     size_t rc_off = 0, cc_off = 0; int ncc = 0;      // border-class tables (0 = single class)
     ConvTile tile{};
 };
-enum StepKind { S_INPUT, S_CONV, S_DW, S_ADD, S_MAXPOOL, S_AVGPOOL, S_REQUANT, S_OUTPUT, S_FUSED, S_STEMPOOL, S_IR, S_P12, S_CHAIN, S_BCHAIN, S_HEAD2, S_IRCHAIN, S_DWS, S_DWS7, S_IRK };
+enum StepKind { S_INPUT, S_CONV, S_DW, S_ADD, S_MAXPOOL, S_AVGPOOL, S_REQUANT, S_OUTPUT, S_FUSED, S_STEMPOOL, S_IR, S_P12, S_CHAIN, S_BCHAIN, S_HEAD2, S_IRCHAIN, S_DWS, S_DWS7, S_IRK, S_GCONV };
 // The kernel of a step whose kind has several, chosen once by the step's emitter (pass 3); bind_step, run_step and f8_net_autotune switch on it.
 //   S_CONV:  conv_igemm (f8_kernels.hip), the LDS-patch 3x3 (f8_conv3x3.hip), conv1x1_wreg (f8_wreg.hip), conv1x1_wstat (f8_wstat.hip),
 //            conv3x3s2_wreg (f8_s2conv.hip), the 1x1 conv + average pool (f8_pool.hip), the classifier fc_dense (f8_fc.hip)
@@ -141,7 +142,7 @@ struct Step {
     double bytes_per_img = 0, bytes_const = 0, ops_per_img = 0;
     double valu_per_img = 0;           // ESSENTIAL vector lane-operations per image (f8_net_launch_valu): what the reference's semantics need once the MFMAs are done
     // the launcher's arguments as far as the plan decides them (bind_step); run_step copies them and adds what the run decides
-    std::variant<std::monostate, ConvArgs, StemPoolArgs, FusedArgs, ChainArgs, BChainArgs, BCChainArgs, IRArgs, IRKArgs, IRChainArgs, DwsArgs, Dws7Args, DwArgs, AddArgs, PoolArgs, AvgArgs, OutArgs> args;
+    std::variant<std::monostate, ConvArgs, StemPoolArgs, FusedArgs, ChainArgs, BChainArgs, BCChainArgs, IRArgs, IRKArgs, IRChainArgs, DwsArgs, Dws7Args, DwArgs, GConvArgs, AddArgs, PoolArgs, AvgArgs, OutArgs> args;
     int inst = 0;                      // the instance the launcher starts (the family's *_inst, f8_internal.h; bind_step)
     // S_CHAIN / S_BCHAIN: geometry, workgroups per image and resident per CU, the 7x7 cluster form (f8_cchain.hip)
     int C = 0, MID = 0, H = 0, W = 0, cin0 = 0, tiles = 0, wg_per_cu = 1; bool cluster = false;
@@ -369,6 +370,7 @@ static const OptKey kOptKeys[] = {
     {"shared_streams", "F8_SHARED_STREAMS", &Options::shared_streams, 0, 1, true},
     {"whole_batch_launches", "F8_WHOLE_BATCH_LAUNCHES", &Options::whole_batch_launches, 0, 1, true},
     {"tap_tiled", "F8_TAP_TILED", &Options::tap_tiled, 0, 1, true},
+    {"grouped", "F8_GROUPED", &Options::grouped, 0, 2, true},
 };
 static const OptKey* find_opt(const char* key) {
     if (!key) return nullptr;
@@ -551,9 +553,13 @@ static int add_conv_node(f8_net* net, int src, const f8_conv_desc& d, const int3
     const Tensor& s = net->tensors[src];
     if (d.cin != s.C) return fail(F8_ERR_INVALID, "%s: cin %d != source channels %d", who, d.cin, s.C);
     if (d.kernel < 1 || d.stride < 1 || d.pad < 0 || d.cout < 1) return fail(F8_ERR_INVALID, "%s: bad geometry", who);
-    if (!(d.groups == 1 || (d.groups == d.cin && d.cout == d.cin)))
+    // grouped convs (1 < groups < cin) are opt-in at the builder (option grouped): planned on f8_gconv.hip or as the dense expansion (emit_conv_family)
+    const bool grouped = d.groups > 1 && d.groups < d.cin && net->opt.grouped >= 1;
+    if (grouped) {
+        if (d.cin % d.groups || d.cout % d.groups) return fail(F8_ERR_INVALID, "%s: groups %d must divide cin %d and cout %d", who, d.groups, d.cin, d.cout);
+    } else if (!(d.groups == 1 || (d.groups == d.cin && d.cout == d.cin)))
         return fail(F8_ERR_UNSUPPORTED, "%s: groups must be 1 or cin (depthwise)", who);
-    if (d.groups != 1 && !((d.kernel == 3 || d.kernel == 5 || d.kernel == 7) && d.stride <= 2 && d.pad <= d.kernel / 2))
+    if (d.groups != 1 && !grouped && !((d.kernel == 3 || d.kernel == 5 || d.kernel == 7) && d.stride <= 2 && d.pad <= d.kernel / 2))
         return fail(F8_ERR_UNSUPPORTED, "%s: depthwise is built for kernel 3, 5 or 7, stride 1 or 2, pad 0 .. kernel / 2 (got kernel %d, stride %d, pad %d)",
                     who, d.kernel, d.stride, d.pad);
     if (d.weight_fl < 0 || d.weight_fl > 31) return fail(F8_ERR_INVALID, "%s: bad weight_fl", who);
@@ -695,6 +701,7 @@ int f8_net_set_label(f8_net* net, int t, const char* label) {
 }
 
 // ------------------------------------------------------------------------------ planner
+static void pack_conv_bias(f8_net* net, Node& nd, const std::vector<long long>& tapsum);
 static void pack_conv_weights(f8_net* net, Node& nd) {
     // Packed layout: [coutP][taps][CK] int8, K-contiguous per output channel, zero padded.
     // Generic: tap = (r,s), CK = Cs(src) channels.  Stem (cin <= 4, source = network input held as
@@ -705,9 +712,12 @@ static void pack_conv_weights(f8_net* net, Node& nd) {
     // corrected for taps outside; which taps are outside depends only on the output row / column, so
     // rows and columns are classified by their in-image tap mask and the table is
     // bias[rowclass * ncc + colclass][cout].  Signed inputs / unpadded convs have one class.
+    // A grouped conv (the dense expansion): raw weights [cout][cin / groups][k][k]; output channel o reads the input channels of ITS group only, every
+    // other weight of its row stays zero (block-diagonal), and its tap sums run over those cin / groups weights.
     const f8_conv_desc& d = nd.cd;
-    const Tensor& src = net->tensors[nd.a]; const Tensor& dst = net->tensors[nd.out];
+    const Tensor& src = net->tensors[nd.a];
     const int k = d.kernel;
+    const int cg = d.cin / d.groups, kg = d.cout / d.groups;
     nd.coutP = round_up(d.cout, 32);
     if (nd.stem) { nd.ck = 32; nd.ktot = k * 32; }
     else { nd.ck = src.Cs; nd.ktot = k * k * src.Cs; }
@@ -719,10 +729,11 @@ static void pack_conv_weights(f8_net* net, Node& nd) {
     {
         int8_t* wp = (int8_t*)net->wblob.data() + nd.w_off;
         for (int o = 0; o < d.cout; ++o)
-            for (int c = 0; c < d.cin; ++c)
+            for (int ci = 0; ci < cg; ++ci)
                 for (int r = 0; r < k; ++r)
                     for (int s = 0; s < k; ++s) {
-                        const int8_t v = nd.w[(((size_t)o * d.cin + c) * k + r) * k + s];
+                        const int8_t v = nd.w[(((size_t)o * cg + ci) * k + r) * k + s];
+                        const int c = (o / kg) * cg + ci;       // the input channel (groups == 1: ci)
                         tapsum[((size_t)o * k + r) * k + s] += v;
                         size_t idx;
                         if (nd.stem) idx = (size_t)o * nd.ktot + (size_t)r * 32 + (size_t)s * 4 + c;
@@ -730,6 +741,15 @@ static void pack_conv_weights(f8_net* net, Node& nd) {
                         wp[idx] = v;
                     }
     }
+    pack_conv_bias(net, nd, tapsum);
+}
+
+// The border-class bias table of a conv whose weights are packed (nd.coutP set): bias[rowclass * ncc + colclass][coutP] and the class of every output
+// row / column (pack_conv_weights); tapsum[cout][k][k] = the sum over the input channels of each tap's weights.
+static void pack_conv_bias(f8_net* net, Node& nd, const std::vector<long long>& tapsum) {
+    const f8_conv_desc& d = nd.cd;
+    const Tensor& src = net->tensors[nd.a]; const Tensor& dst = net->tensors[nd.out];
+    const int k = d.kernel;
     // classes
     std::vector<uint32_t> rmasks, cmasks;
     std::vector<uint8_t> rowcls(dst.H, 0), colcls(dst.W, 0);
@@ -833,7 +853,7 @@ static void pack_dw_weights(f8_net* net, Node& nd) {
 // "General depthwise": every accepted depthwise conv that is not 3x3 / pad 1 (kernel 3 / 5 / 7, stride 1 / 2, pad 0 .. kernel / 2; add_conv_node).  One pass
 // of the planner fuses one — 1e3, option fuse_irk: kernel 5 / 7 with pad kernel / 2 inside an inverted residual —; every other matcher asks for kernel 3
 // and pad 1, so anywhere else it is a launch of its own on the kernels of f8_dwk.hip.
-static bool dw_general(const f8_conv_desc& d) { return d.groups != 1 && !(d.kernel == 3 && d.pad == 1); }
+static bool dw_general(const f8_conv_desc& d) { return d.groups != 1 && d.groups == d.cin && !(d.kernel == 3 && d.pad == 1); }
 
 // The two weight images of a general depthwise conv, at offsets of their own (the 3x3 / pad 1 images are pack_dw_weights' and stay as they are):
 //  (1) [K * K][Cs] tap-major + plain bias                        — dwconvk_kernel
@@ -868,6 +888,32 @@ static void pack_dwk_weights(f8_net* net, Node& nd) {
         if (!d.input_signed) b += (uint32_t)(128ll * sum);
         b4[c] = (int32_t)b;
     }
+}
+
+// A grouped 3x3 on gconv3x3_kernel (f8_gconv.hip; gconv_kernel_applies: cin == cout, cg = cin / groups divides 32): per 32-channel slice t and tap, the
+// 32 x 32 block W[cout 32 t + i][cin 32 t + j] — zero wherever the two channels are not of one group, or beyond C — in MFMA-fragment order
+// [slice][tap][lane][16 B]: lane l = row (l & 31), input channels 32 t + 16 (l >> 5) .. + 15.  The bias table is pack_conv_weights' (the tap sums run over
+// the cg weights of the group).
+static void pack_gconv_weights(f8_net* net, Node& nd) {
+    const f8_conv_desc& d = nd.cd;
+    const Tensor& src = net->tensors[nd.a];
+    const int cg = d.cin / d.groups, nsl = src.Cs / 32;
+    nd.coutP = src.Cs; nd.ck = 32; nd.ktot = 9 * 32;
+    nd.w_off = round_up_z(net->wblob.size(), 256);
+    net->wblob.resize(nd.w_off + (size_t)nsl * 9 * 1024, 0);
+    std::vector<long long> tapsum((size_t)d.cout * 9, 0);
+    int8_t* wp = (int8_t*)net->wblob.data() + nd.w_off;
+    for (int o = 0; o < d.cout; ++o)
+        for (int ci = 0; ci < cg; ++ci) {
+            const int c = (o / cg) * cg + ci;                   // input channel: same group, hence same slice (cg divides 32)
+            const int lane = (o & 31) + 32 * ((c & 31) >> 4);
+            for (int t = 0; t < 9; ++t) {
+                const int8_t v = nd.w[((size_t)o * cg + ci) * 9 + t];
+                tapsum[(size_t)o * 9 + t] += v;
+                wp[(((size_t)(o >> 5) * 9 + t) * 64 + lane) * 16 + (c & 15)] = v;
+            }
+        }
+    pack_conv_bias(net, nd, tapsum);
 }
 
 static std::string tname(const f8_net* net, int t) {
@@ -919,6 +965,7 @@ static void label_conv_step(f8_net* net, Step& st, const Node& nd) {
         case V_PATCH3X3: snprintf(buf, sizeof buf, "conv3x3s1_patch_R%dx%d_bn%d%s:%s", nd.p3_R, nd.p3_imgs, nd.p3_bn, res ? "_res" : "", key.c_str()); break;
         default:
             if (nd.depthwise) snprintf(buf, sizeof buf, "dwconv%dx%ds%d:%s", d.kernel, d.kernel, d.stride, key.c_str());
+            else if (nd.grouped) snprintf(buf, sizeof buf, "gconv%dx%ds%d_dense:%s", d.kernel, d.kernel, d.stride, key.c_str());
             else snprintf(buf, sizeof buf, "conv%dx%ds%d_t%dx%dx%d%s%s:%s", d.kernel, d.kernel, d.stride, nd.tile.bm, nd.tile.bn,
                           nd.tile.bk, nd.stem ? "_stem" : "", res ? "_res" : (nd.dual >= 0 ? "_dual" : ""), key.c_str());
     }
@@ -1680,7 +1727,8 @@ static void plan_tensor_forms(f8_net* net) {
                 Tensor& s = T[nd.a];
                 int n = 0;
                 consumer_format(s, nd.cd, &n, "finalize");
-                nd.depthwise = nd.cd.groups != 1;
+                nd.depthwise = nd.cd.groups != 1 && nd.cd.groups == nd.cd.cin;
+                nd.grouped = nd.cd.groups != 1 && !nd.depthwise;      // (no matcher claims it: a launch of its own, its int8 input and its outputs in HBM)
                 // nd inside a fused block: does its source exist in HBM at all, and which form of the stream does the launch read?
                 int host = -1;
                 const Role role = role_in_block(net, i, &host);
@@ -1716,7 +1764,7 @@ static void plan_tensor_forms(f8_net* net) {
                     default: in_launch = false;                  // a conv of its own; B_JOIN: the shortcut and body.4 read their int8 inputs from HBM
                 }
                 if (in_launch) break;
-                nd.stem = !nd.depthwise && nd.cd.cin <= 4 && ND[s.prod].kind == N_INPUT && nd.cd.kernel <= 8 &&
+                nd.stem = !nd.depthwise && !nd.grouped && nd.cd.cin <= 4 && ND[s.prod].kind == N_INPUT && nd.cd.kernel <= 8 &&
                           s.consumers.size() == 1 && !is_output(net, nd.a) && n == 0;
                 if (nd.stem) {
                     const int Q = T[nd.out].W;
@@ -1782,8 +1830,9 @@ static int join_output(const f8_net* net, const Node& c, Step& st) {
     st.relu1 = net->nodes[c.fused_add].relu;
     return net->nodes[c.fused_add].out;
 }
-// bytes of a conv's packed weights + bias (depthwise: K * K taps + 4 bytes of bias per channel)
+// bytes of a conv's packed weights + bias (depthwise: K * K taps + 4 bytes of bias per channel; grouped: the weights of the groups, not the zeros between them)
 static double weight_bytes(const f8_net* net, const Node& c) {
+    if (c.grouped) return (double)c.cd.cout * ((c.cd.cin / c.cd.groups) * c.cd.kernel * c.cd.kernel + 4);
     return c.depthwise ? (double)net->tensors[c.a].Cs * (c.cd.kernel * c.cd.kernel + 4) : (double)c.coutP * (c.ktot + 4);
 }
 // multiply-adds x 2 of a conv per image
@@ -2242,6 +2291,35 @@ static int emit_conv(f8_net* net, int i, int max_batch, Step& st, std::vector<in
     return F8_OK;
 }
 
+// Which grouped convs run on gconv3x3_kernel (f8_gconv.hip) under option grouped = 1; every other accepted one — and all of them under grouped = 2 — is
+// the dense expansion: emit_conv's plain path over block-diagonal weights (pack_conv_weights), slower by cin / cg.  Measured on the seven grouped layers
+// of ResNeXt-50 32x4d at 128 images (profiles/gconv_r07.md): the kernel is 1.9x (128 x 56 x 56, cg 4: 51.3 against 98.7 us) to 8.1x (1024 x 14 x 14 / 2,
+// cg 32: 15.5 against 126.0 us) faster than the expansion, on every shape — none of its set is routed to the expansion.
+static bool gconv_kernel_applies(const Options& opt, const f8_conv_desc& d) {
+    const int cg = d.cin / d.groups;
+    return opt.grouped == 1 && d.kernel == 3 && (d.stride == 1 || d.stride == 2) && d.pad <= 1 && d.cin == d.cout && cg >= 2 && cg <= 32 && 32 % cg == 0;
+}
+// a grouped 3x3 on the slice-diagonal kernel: always a launch of its own, no join
+static int emit_gconv(f8_net* net, int i, Step& st, std::vector<int>* extra) {
+    auto& T = net->tensors;
+    Node& nd = net->nodes[i];
+    const f8_conv_desc& d = nd.cd;
+    const Tensor& s = T[nd.a]; const Tensor& o = T[nd.out];
+    st.kind = S_GCONV;
+    if (const int rc = conv_input_i8(net, nd, &st.src_t, &st.src_f)) return rc;
+    st.relu0 = d.relu;
+    pack_gconv_weights(net, nd);
+    select_outputs(net, nd.out, &st.out, extra);
+    const double opix = (double)o.H * o.W;
+    st.ops_per_img = conv_ops(net, nd);
+    st.bytes_per_img = (double)s.H * s.W * s.Cs + out_bytes(st, o, opix);
+    st.bytes_const = weight_bytes(net, nd);
+    st.valu_per_img = 3.0 * opix * o.Cs * out_forms8(st);
+    char buf[64]; snprintf(buf, sizeof buf, "gconv3x3s%d:", d.stride);
+    st.name = buf + tname(net, nd.out);
+    return F8_OK;
+}
+
 // the launch of conv node i: the chain whose last block it hosts, else the block it hosts, else a conv of its own
 static int emit_conv_family(f8_net* net, int i, int max_batch, Step& st, std::vector<int>* extra) {
     static int (*const emit_chain_kind[])(f8_net*, int, Step&, std::vector<int>*) = {nullptr, emit_chain, emit_bchain, emit_bcchain, emit_irchain};   // by ChainKind
@@ -2255,7 +2333,9 @@ static int emit_conv_family(f8_net* net, int i, int max_batch, Step& st, std::ve
         case B_IR: return emit_ir(net, i, st, extra);
         case B_IRK: return emit_irk(net, i, st, extra);
         case B_DWS: return nd.blk.I7 > 0 ? emit_dws7(net, i, st, extra) : emit_dws(net, i, st, extra);
-        default: return emit_conv(net, i, max_batch, st, extra);
+        default:
+            if (nd.grouped && gconv_kernel_applies(net->opt, nd.cd)) return emit_gconv(net, i, st, extra);
+            return emit_conv(net, i, max_batch, st, extra);
     }
 }
 
@@ -2903,6 +2983,25 @@ static int bind_step(f8_net* net, Step& st) {
             }
             st.args = a; break;
         }
+        case S_GCONV: {
+            const Tensor& sT = T[st.src_t];
+            const Tensor& oT = T[nd.out];
+            GConvArgs a{};
+            a.w = W8(nd.w_off); a.bias = B32(nd.b_off);
+            a.ncc = nd.ncc;
+            if (nd.ncc > 0) { a.rowcls = (const uint8_t*)W8(nd.rc_off); a.colcls = (const uint8_t*)W8(nd.cc_off); }
+            a.H = sT.H; a.W = sT.W; a.P = oT.H; a.Q = oT.W; a.Cs = sT.Cs; a.stride = nd.cd.stride; a.pad = nd.cd.pad;
+            gconv_tile(a.P, a.Q, a.stride, &a.R, &a.TW, &a.G);
+            a.tiles_r = (a.P + a.R - 1) / a.R; a.tiles_c = (a.Q + a.TW - 1) / a.TW;
+            a.PR = (a.R - 1) * a.stride + 3; a.PW = (a.TW - 1) * a.stride + 3;
+            make_magic((uint32_t)(a.PR * a.PW), &a.mIPP, &a.s1IPP, &a.s2IPP);
+            make_magic((uint32_t)a.PW, &a.mPW, &a.s1PW, &a.s2PW);
+            make_magic((uint32_t)(a.R * a.TW), &a.mRTW, &a.s1RTW, &a.s2RTW);
+            make_magic((uint32_t)a.TW, &a.mTW, &a.s1TW, &a.s2TW);
+            a.relu0 = st.relu0;
+            gconv_kernel_name(kb, sizeof kb, a);                  // integer requantisation whatever requant_float says (as f8_dwk.hip)
+            out_formats(a.q); st.args = a; break;
+        }
         case S_ADD: case S_REQUANT: {
             AddArgs a{};
             a.Cs = T[st.src_t].Cs; a.a_shl = st.acc_shl; a.b_shl = st.res_shl; a.relu = st.relu1;
@@ -3311,6 +3410,14 @@ static int run_step(const f8_net* net, const RunIO& io, const Step& st, int n0, 
             a.x = (const int8_t*)fp(T[st.src_t].forms[st.src_f]); a.N = N;
             fill_out(&a.out32, a.q);
             e = (a.k == 3 && a.pad == 1) ? launch_dwconv(a, st.inst, s) : launch_dwk(a, st.inst, s);      // (general depthwise: f8_dwk.hip)
+            break;
+        }
+        case S_GCONV: {
+            const Form& sF = T[st.src_t].forms[st.src_f];
+            GConvArgs a = std::get<GConvArgs>(st.args);
+            a.x = (const int8_t*)fp(sF); a.x_bytes = (uint32_t)(sF.bytes_per_img * N); a.N = N;
+            fill_out(&a.out32, a.q);
+            e = launch_gconv(a, s);
             break;
         }
         case S_ADD: case S_REQUANT: {

@@ -190,6 +190,8 @@ class _Layer:
         if self.groups == 1:
             return (self.bn_w / bn_std)[:, None, None, None] * weight * self.fix_scaling[(...,) + (None, None)] / \
                 self.following.fix_scaling[(...,) + (None, None, None)]
+        if weight.shape[1] != 1:                                # 1 < groups < in_channels: fix_quant_ops.py:386-390
+            raise NotImplementedError('Group-wise conv with groups != in_channels is not supported')
         return (self.bn_w / bn_std)[:, None, None, None] * weight * self.fix_scaling[(...,) + (None, None, None)] / \
             self.following.fix_scaling[(...,) + (None, None, None)]
 
@@ -246,7 +248,7 @@ def export_int_state(spec: topology.NetSpec, float_state: dict, cfg: ExportConfi
                the tail conv takes the last master; signed (`double_side`) inputs as in the topology table
       MBV1     fix_mobilenet_v1.py:53-80,204-230                         no masters
     """
-    resnet, mbv2, mbv1 = spec.arch.startswith('resnet'), spec.arch == 'mobilenet_v2', spec.arch == 'mobilenet_v1'
+    resnet, mbv2, mbv1 = spec.arch.startswith(('resnet', 'resnext')), spec.arch == 'mobilenet_v2', spec.arch == 'mobilenet_v1'
     if not (resnet or mbv2 or mbv1):
         raise NotImplementedError(f'export: {spec.arch}')
     layers: Dict[str, _Layer] = {}

@@ -6,6 +6,7 @@ fix_mobilenet_v2.py:207-241, fix_mobilenet_v1.py:120-147) through the C ABI; the
 into fused HIP launches.  torch is used for device memory and streams only.
 """
 import ctypes
+import os
 
 import numpy as np
 
@@ -17,6 +18,16 @@ AVGPOOL_SHIFT = 6   # FXQAvgPool2d(7).shiftnum = round(log2(49)), fix_quant_ops.
 
 def _np_i32(a):
     return np.ascontiguousarray(np.asarray(a), dtype=np.int32)
+
+
+def accept_grouped(net, convs, options=None):
+    """The raw builder refuses grouped convs (1 < groups < cin) unless the handle's option `grouped` says otherwise, and the option must be set
+    before the conv is added.  The high-level entry points call this before they record: a value the caller gave (options, or F8_GROUPED in the
+    environment) is applied as it is; with none, `grouped` becomes 1 when one of `convs` — (cin, groups) pairs — is grouped."""
+    if options and 'grouped' in options:
+        net.set_option('grouped', options['grouped'])
+    elif 'F8_GROUPED' not in os.environ and any(1 < g < cin for cin, g in convs):
+        net.set_option('grouped', 1)
 
 
 class F8Net:
@@ -332,14 +343,15 @@ def build_net(spec: topology.NetSpec, params: dict, max_batch: int, hw: int = 22
     """Record IntModel.forward for `spec` with exported parameters `params` (numpy or torch-cpu
     tensors keyed like the reference state_dict) and plan it for batches up to max_batch.
     options: {key: value} for f8_net_set_option, applied before planning.  taps: see record_net."""
-    net = record_net(spec, params, hw, input_fraclen, taps=taps)
+    net = record_net(spec, params, hw, input_fraclen, taps=taps, options=options)
     for k, v in (options or {}).items():
         net.set_option(k, v)
     return net.finalize(max_batch)
 
 
-def record_net(spec: topology.NetSpec, params: dict, hw: int = 224, input_fraclen=None, taps=()) -> F8Net:
+def record_net(spec: topology.NetSpec, params: dict, hw: int = 224, input_fraclen=None, taps=(), options=None) -> F8Net:
     """The recording half of build_net: the graph is in the handle, not yet planned (set planning options, then finalize).
+    options: only its `grouped` key is read here — grouped convs are accepted while they are recorded (accept_grouped).
 
     taps: names of further tensors to return, marked as int32 outputs 1, 2, ... in the order given (output 0 stays the float
     logits).  A name is a block name (`stage_1_layer_3`: the block's output tensor, whether or not the block ends in a join), a
@@ -350,6 +362,7 @@ def record_net(spec: topology.NetSpec, params: dict, hw: int = 224, input_fracle
     that can be tapped is kept as `net.tap_ids`, the names given as `net.taps`."""
     params = {k: (v.detach().cpu().numpy() if hasattr(v, 'detach') else np.asarray(v)) for k, v in params.items()}
     net = F8Net()
+    accept_grouped(net, [(c.cin, c.groups) for c in spec.convs()], options)
     head_in_fl = _fl(params, spec.head.key, 'input_fraclen')
     if input_fraclen is None:
         input_fraclen = head_in_fl if spec.normalize else 8     # fix_train.py:683-692

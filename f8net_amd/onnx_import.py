@@ -145,9 +145,10 @@ class IntGraph:
     def build_net(self, max_batch, hw=None, input_fraclen=None, options=None):
         """Record the graph through libf8net.so's builder and plan it (f8_net_finalize).
         options: {key: value} for f8_net_set_option, applied before planning (as net.build_net's)."""
-        from .net import F8Net
+        from .net import F8Net, accept_grouped
         V, layer = self.solve_fraclens(input_fraclen)
         net = F8Net()
+        accept_grouped(net, [(o.weight.shape[1] * o.groups, o.groups) for o in self.ops if o.kind == 'conv'], options)
         ids = {}
         for t, o in enumerate(self.ops):
             if o.kind == 'input':

@@ -96,6 +96,20 @@ def resnet(depth: int = 50, num_classes: int = 1000, normalize: bool = False) ->
                    num_classes, normalize=normalize)
 
 
+def resnext(depth: int = 50, groups: int = 32, width_per_group: int = 4, num_classes: int = 1000, normalize: bool = False) -> NetSpec:
+    """ResNeXt / Wide-ResNeXt: the bottleneck ResNet with a grouped 3x3 (body.2) of torchvision's width, mid = planes * width_per_group // 64 * groups.
+    The reference has no such net (its QAT path refuses these groups, fix_quant_ops.py:386-390); the integer graph is IntBlock's, keys as `resnet`."""
+    spec = resnet(depth, num_classes, normalize)
+    assert depth >= 50, 'ResNeXt is a bottleneck net'
+    for b in spec.blocks:
+        planes = b.body[2].cout // 4
+        mid = planes * width_per_group // 64 * groups
+        b.body[0].cout = b.body[1].cin = b.body[1].cout = b.body[2].cin = mid
+        b.body[1].groups = groups
+    spec.arch = f'resnext{depth}_{groups}x{width_per_group}d'
+    return spec
+
+
 def mobilenet_v2(num_classes: int = 1000, normalize: bool = False) -> NetSpec:
     """fix_mobilenet_v2.py:276-372 (block table :282-291), int_block :168-176."""
     setting = [[1, 16, 1, 1], [6, 24, 2, 2], [6, 32, 3, 2], [6, 64, 4, 2],
@@ -144,7 +158,12 @@ def mobilenet_v1(num_classes: int = 1000, normalize: bool = False) -> NetSpec:
                    num_classes, normalize=normalize)
 
 
+_RESNEXT = {'resnext50_32x4d': (50, 32, 4), 'resnext101_32x8d': (101, 32, 8), 'resnext101_64x4d': (101, 64, 4)}
+
+
 def get(arch: str, num_classes: int = 1000, normalize: bool = False) -> NetSpec:
+    if arch in _RESNEXT:
+        return resnext(*_RESNEXT[arch], num_classes, normalize)
     if arch.startswith('resnet'):
         return resnet(int(arch[len('resnet'):]), num_classes, normalize)
     if arch in ('mobilenet_v2', 'mbv2'):

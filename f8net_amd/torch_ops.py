@@ -31,7 +31,7 @@ from torch.library import Library
 
 from . import _lib
 from ._lib import check
-from .net import F8Net
+from .net import F8Net, accept_grouped
 
 _DEF = Library('f8net', 'DEF')
 _DEF.define('requant(Tensor x, int fl, int input_fl, bool signed) -> Tensor')
@@ -169,6 +169,7 @@ def _conv2d(x, weight, bias, stride, pad, groups, weight_fl, input_fl, input_sig
 
     def build(n):
         net = F8Net()
+        accept_grouped(net, [(C, groups)])
         t = net.input(C, H, W, input_fl)
         t = net.conv(t, _np(weight), _np(bias), stride=stride, pad=pad, groups=groups, weight_fl=weight_fl, input_fl=input_fl,
                      input_signed=input_signed, quant_input=False, relu=False)

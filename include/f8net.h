@@ -32,7 +32,7 @@ extern "C" {
 typedef enum f8_status {
     F8_OK = 0,
     F8_ERR_INVALID = -1,      /* argument the reference would assert on, or malformed graph */
-    F8_ERR_UNSUPPORTED = -2,  /* legal in the reference, not built here (e.g. groups not in {1, Cin}; a depthwise kernel of 9) */
+    F8_ERR_UNSUPPORTED = -2,  /* legal in the reference, not built here (e.g. 1 < groups < cin on a handle whose option `grouped` is 0, the default; a depthwise kernel of 9) */
     F8_ERR_HIP = -3,          /* HIP runtime error (message in f8_last_error) */
     F8_ERR_NOMEM = -4,
     F8_ERR_STATE = -5         /* call out of order (e.g. run before finalize) */
@@ -99,7 +99,10 @@ typedef struct f8_conv_desc {
     int32_t kernel;        /* square kernels: 1, 3, 7 in the reference nets */
     int32_t stride, pad;
     int32_t groups;        /* 1 or cin (depthwise, cout == cin) — fix_quant_ops.py:373-390.  Depthwise: kernel 3, 5 or 7,
-                              stride 1 or 2, 0 <= pad <= kernel / 2; anything else depthwise is F8_ERR_UNSUPPORTED */
+                              stride 1 or 2, 0 <= pad <= kernel / 2; anything else depthwise is F8_ERR_UNSUPPORTED.
+                              1 < groups < cin (grouped, the int nn.Conv2d of fix_quant_ops.py:680-714): F8_ERR_UNSUPPORTED unless the
+                              handle's option `grouped` is 1 or 2, set BEFORE this call; then any geometry a plain conv takes, and
+                              groups must divide cin and cout (F8_ERR_INVALID) */
     int32_t weight_fl;     /* buffer `weight_fraclen` (fix_quant_ops.py:710) */
     int32_t input_fl;      /* buffer `input_fraclen`  (fix_quant_ops.py:711) */
     int32_t input_signed;  /* attr `input_symmetric`  (fix_quant_ops.py:709) */
@@ -281,7 +284,12 @@ int f8_net_check(f8_net* net);
  *               (dwk_dot4) requantise in the integer form whatever this says: same kernels, same values),
  *               tap_tiled (default 1: the copy-out launches of outputs 1 .. run f8::tap_kernel, f8_tap.hip — one wave per 4 KB block of the
  *               int32 source, every loaded byte used; 0: f8::output_kernel, which walks the destination.  Output 0 always leaves through
- *               output_kernel or the classifier itself.  Same values either way)
+ *               output_kernel or the classifier itself.  Same values either way),
+ *               grouped (default 0: f8_net_conv refuses 1 < groups < cin with F8_ERR_UNSUPPORTED; 1: accepted — kernel 3, stride 1 / 2,
+ *               pad 0 / 1, cin == cout, cin / groups in {2, 4, 8, 16, 32} run f8::gconv3x3_kernel, f8_gconv.hip, plan token gconv3x3s{S}:,
+ *               every other grouped conv runs as the DENSE EXPANSION, the plain conv kernels over block-diagonal weights, plan token
+ *               gconv{k}x{k}s{S}_dense:; 2: accepted, always the dense expansion.  Set it before the f8_net_conv call that adds the
+ *               grouped conv.  Same values in both, bit for bit; depthwise convs keep their own rules and kernels whatever it says)
  *   scheduling: chunk56 / chunk28 / chunk14 (images per chunk of the fused blocks; -1 = derived from chunk_budget_mb, 0 = whole
  *               batch), chunk_budget_mb (memory-side cache a chunk's int32 stream may occupy), chunk_ds, chunk_opener,
  *               split_streams, graph, stagger, stagger_pipelined, stem_wpc, stem_grid_div (row-walking head on 1 / n of the CUs; 0 = by output form), check_device, check_input_range, pipeline_depth (2..4 runs in flight),

@@ -5,7 +5,9 @@ Batches 1 / 8 / 128 / 256 at 224x224; 128 and 256 also with `whole_batch_launche
 planned with further outputs (`taps=`: the last block of the last four stages and 'avgpool') — the only plans that reach `tap_kernel`.
     python tools/reach.py --opt fuse_irk=1 [--opt key=value ..]   -> the same table with these planning options on top of the defaults
 (the fuse options that are off by default: fuse_irchain, fuse_dws, fuse_dws7, fuse_head_dws, fuse_bchain7, fuse_irk — `fuse_irk` reaches
-no kernel on these four nets: none of them has a depthwise 5x5 / 7x7)."""
+no kernel on these four nets: none of them has a depthwise 5x5 / 7x7).
+    python tools/reach.py --net resnext50_32x4d [--net NAME ..]   -> the table over the four nets AND these (topology.get names; a net with
+grouped convs reaches `gconv3x3_kernel`: build_net sets `grouped = 1` by itself)."""
 import os
 import re
 import sys
@@ -31,10 +33,14 @@ def cli_options():
     return opts
 
 
+def cli_nets():
+    return [sys.argv[i + 1] for i, a in enumerate(sys.argv) if a == '--net' and i + 1 < len(sys.argv)]
+
+
 def main():
     reach = {}
     extra = cli_options()
-    for arch in NETS:
+    for arch in NETS + cli_nets():
         spec = topology.get(arch, normalize=(arch == 'resnet50'))
         params = synth.reference_params(spec, seed=1234)
         stages = {b.name.rsplit('_layer_', 1)[0]: b.name for b in spec.blocks}
