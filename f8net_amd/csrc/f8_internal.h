@@ -46,6 +46,7 @@ struct Options {
     int dual_wide = 2048;        // dual-GEMM joins with at least this many couts use the 128x128 tile
     int deep_nk = 7;             // K loops of at least this many steps use the deepest DMA ring
     int bk128 = 0;               // 128-byte K steps in conv_igemm_kernel
+    int igemm_tile = 0;          // tests and tuning: 1 .. 4 force conv_igemm_kernel's tile to 128x128 / 128x64 / 64x128 / 64x64 where f8_net_autotune would try it (bk stays)
     int dw_dot4 = 1;             // v_dot4 depthwise kernel
     int dwk_dot4 = 1;            // general depthwise (not 3x3 / pad 1): the v_dot4 kernel of f8_dwk.hip for int8-only launches (0: its generic kernel)
     int dw_mma = 1;              // depthwise 3x3 on the matrix cores (f8_dwmma.hip) where it has an instance (output width >= 14, int8 outputs)

@@ -345,6 +345,7 @@ static const OptKey kOptKeys[] = {
     {"dual_wide", "F8_DUAL_WIDE", &Options::dual_wide, 0, 1 << 30, true},
     {"deep_nk", "F8_DEEP_NK", &Options::deep_nk, 1, 1 << 20, true},
     {"bk128", "F8_BK128", &Options::bk128, 0, 1, true},
+    {"igemm_tile", "F8_IGEMM_TILE", &Options::igemm_tile, 0, 4, true},
     {"dw_dot4", "F8_DW_DOT4", &Options::dw_dot4, 0, 1, true},
     {"dw_mma", "F8_DW_MMA", &Options::dw_mma, 0, 1, true},
     {"dwk_dot4", "F8_DWK_DOT4", &Options::dwk_dot4, 0, 1, true},
@@ -2230,6 +2231,15 @@ static Variant conv_variant(const f8_net* net, const Node& nd, const Step& st, i
 // the conv kernels that read the weights in MFMA-fragment order (pack_frag_weights)
 static bool reads_frag_weights(Variant v) { return v == V_FC || v == V_POOL || v == V_WSTAT || v == V_S2WREG || v == V_WREG; }
 
+// The tiles f8_net_autotune times on a conv_igemm_kernel step and option igemm_tile (1 .. 4) forces, and which of them a node has an instance for.
+static const int kIgemmCandBm[4] = {128, 128, 64, 64}, kIgemmCandBn[4] = {128, 64, 128, 64};
+static bool igemm_tile_admissible(const Node& nd, const ConvTile& t) {
+    if (t.bn > 64 && nd.coutP <= 64) return false;
+    if (nd.dual >= 0 && !(t.bn == 64 || (t.bn == 128 && t.bm == 128))) return false;     // dual-GEMM instances
+    if (t.bm == 64 && t.bn == 32) return false;
+    return true;
+}
+
 // a conv / linear / depthwise conv of its own, with its residual join or dual GEMM and the average pool behind it
 static int emit_conv(f8_net* net, int i, int max_batch, Step& st, std::vector<int>* extra) {
     auto& T = net->tensors; auto& ND = net->nodes;
@@ -2251,6 +2261,10 @@ static int emit_conv(f8_net* net, int i, int max_batch, Step& st, std::vector<in
             const int wide = opt.dual_wide;   // measured: 7x7x2048 join 67 -> 52 us; 14x14x1024 and 28x28x512 are slower with the wide tile
             nd.tile.bk = 64;
             if (nd.coutP >= wide && nd.tile.bm == 128) nd.tile.bn = 128; else nd.tile.bn = 64;
+        }
+        if (opt.igemm_tile > 0) {     // tests and tuning: one of autotune's candidates where it is admissible (bk stays)
+            ConvTile t = nd.tile; t.bm = kIgemmCandBm[opt.igemm_tile - 1]; t.bn = kIgemmCandBn[opt.igemm_tile - 1];
+            if (igemm_tile_admissible(nd, t)) nd.tile = t;
         }
         if (!nd.stem && d.groups == 1 && d.kernel == 3 && d.stride == 1 && d.pad == 1 && nd.ck == d.cin && opt.patch3x3 &&
             !conv3x3_patch_config(d.cin, s.H, s.W, nd.coutP, &nd.p3_R, &nd.p3_imgs, &nd.p3_bn)) nd.p3_R = 0;
@@ -3490,7 +3504,6 @@ int f8_net_autotune(f8_net* net, int N, void* stream) {
     const RunIO io{};                                          // (a conv step reads and writes the arena only)
     hipEvent_t e0, e1;
     if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return fail(F8_ERR_HIP, "f8_net_autotune: events");
-    static const int cand_bm[4] = {128, 128, 64, 64}, cand_bn[4] = {128, 64, 128, 64};
     int changed = 0;
     for (auto& st : net->steps) {
         if (st.variant != V_IGEMM) continue;                       // (conv_igemm_kernel steps only)
@@ -3498,10 +3511,8 @@ int f8_net_autotune(f8_net* net, int N, void* stream) {
         const ConvTile keep = nd.tile;
         ConvTile best = keep; float best_ms = 1e30f;
         for (int c = 0; c < 4; ++c) {
-            ConvTile t = keep; t.bm = cand_bm[c]; t.bn = cand_bn[c];
-            if (t.bn > 64 && nd.coutP <= 64) continue;
-            if (nd.dual >= 0 && !(t.bn == 64 || (t.bn == 128 && t.bm == 128))) continue;     // dual-GEMM instances
-            if (t.bm == 64 && t.bn == 32) continue;
+            ConvTile t = keep; t.bm = kIgemmCandBm[c]; t.bn = kIgemmCandBn[c];
+            if (!igemm_tile_admissible(nd, t)) continue;
             nd.tile = t;
             (void)bind_step(net, st);                                  // the instance follows the tile (ring depth)
             if (run_step(net, io, st, 0, n_launch, 0, 0, s) != F8_OK) { (void)hipGetLastError(); continue; }   // no instance

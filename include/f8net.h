@@ -272,7 +272,9 @@ int f8_net_check(f8_net* net);
  *               convs in one launch), wstat (weight-stationary 1x1 kernel: plain, dual-GEMM and residual-join instances) with
  *               wstat_min_tiles (pixel tiles per workgroup a launch must offer; 0 = always) and wstat_fast (0 = general epilogue), wreg (weights-streamed 1x1 kernel for the
  *               512 -> 256 / 1024 -> 512 reductions of smaller launches),
- *               patch3x3, dual_wide, deep_nk, bk128, dw_dot4, dwk_dot4 (default 1; depthwise convs other than 3x3 / pad 1 — kernel 3 / 5 / 7, stride 1 / 2,
+ *               patch3x3, dual_wide, deep_nk, bk128, igemm_tile (default 0; tests and tuning: 1 .. 4 force f8::conv_igemm_kernel's tile to 128x128 / 128x64 /
+ *               64x128 / 64x64 where f8_net_autotune would try it — no 128-wide tile over at most 64 padded output channels, the dual-GEMM pair on
+ *               64-wide tiles or 128x128, never 64x32; the K step stays.  0 changes nothing.  Same values with every tile), dw_dot4, dwk_dot4 (default 1; depthwise convs other than 3x3 / pad 1 — kernel 3 / 5 / 7, stride 1 / 2,
  *               pad 0 .. kernel / 2 —, always a launch of their own: 1 = a launch that writes int8 forms only runs f8::dwconvk_dot4_kernel<K, S>, f8_dwk.hip;
  *               0 = f8::dwconvk_kernel, which a launch that writes an int32 form runs either way.  dw_mma and dw_dot4 govern 3x3 / pad 1 only), opener_stg, whole_batch_launches (hint: runs will use
  *               f8_net_set_pipelined(2)),
