@@ -1032,6 +1032,43 @@ static Role role_in_block(const f8_net* net, int i, int* host) {
     return r;
 }
 
+// ---- The vocabulary of the matchers (passes 1 .. 1k).  What the passes really differ in — quant_input, relu, fused_add, dual, claimed() — stays
+// written out where a pass tests it.  Every tensor has a producer (f8_net_input, add_conv_node and the other builders create it with one): no pass tests for that.
+// a plain conv (groups 1) of this kernel, stride and pad
+static bool plain_conv(const Node& n, int k, int s, int p) {
+    return n.kind == N_CONV && n.cd.groups == 1 && n.cd.kernel == k && n.cd.stride == s && n.cd.pad == p;
+}
+// a depthwise conv (groups == cin, more than one channel; add_conv_node then insists on cout == cin) of this kernel and pad, stride 1 (stride2: or 2)
+static bool depthwise_conv(const Node& n, int k, int p, bool stride2) {
+    return n.kind == N_CONV && n.cd.groups != 1 && n.cd.groups == n.cd.cin && n.cd.kernel == k && n.cd.pad == p &&
+           (n.cd.stride == 1 || (stride2 && n.cd.stride == 2));
+}
+// tensor t as a private intermediate: its producer node if exactly one node reads it and it is no network output, else -1
+static int private_producer(const f8_net* net, int t) {
+    const Tensor& x = net->tensors[t];
+    return x.consumers.size() == 1 && !is_output(net, t) ? x.prod : -1;
+}
+// conv c hosts a residual join (c.fused_add >= 0): the tensor on the join's other side
+static int join_other(const f8_net* net, const Node& c) {
+    const Node& ad = net->nodes[c.fused_add];
+    return ad.a == c.out ? ad.b : ad.a;
+}
+// Can a launch that writes int8 forms only produce tensor t (passes 1j / 1k): is every reader a conv of its own — or the member of a depthwise-separable
+// block — that requantises its input, in at most two formats between them?
+static bool int8_readers_only(const f8_net* net, int t) {
+    const auto& ND = net->nodes;
+    std::vector<std::pair<int, int>> fmts;
+    for (int u : net->tensors[t].consumers) {
+        const Node& un = ND[u];
+        int n = 0;
+        if ((un.kind != N_CONV && un.kind != N_LINEAR) || !un.cd.quant_input || consumer_format(net->tensors[t], un.cd, &n, "finalize") ||
+            (claimed(net, u) && !(un.absorbed_by >= 0 && ND[un.absorbed_by].blk.kind == B_DWS))) return false;
+        const std::pair<int, int> f{n, un.cd.input_signed ? 1 : 0};
+        if (std::find(fmts.begin(), fmts.end(), f) == fmts.end()) fmts.push_back(f);
+    }
+    return fmts.size() <= 2;
+}
+
 // pass 1
 static void plan_residual_joins(f8_net* net) {
     auto& T = net->tensors;
@@ -1046,13 +1083,12 @@ static void plan_residual_joins(f8_net* net) {
             const int x = pass == 0 ? ad.a : ad.b, y = pass == 0 ? ad.b : ad.a;
             const int px = T[x].prod, py = T[y].prod;
             Node& cx = ND[px];
-            if (cx.kind != N_CONV || cx.cd.groups != 1 || cx.fused_add >= 0) continue;
-            if (T[x].consumers.size() != 1 || is_output(net, x)) continue;
+            if (cx.kind != N_CONV || cx.cd.groups != 1 || cx.fused_add >= 0) continue;      // (any kernel, stride and pad)
+            if (private_producer(net, x) < 0) continue;
             if (py > px) continue;     // other operand must exist before the conv runs
             ad.fused_into = px; cx.fused_add = i;
         }
     }
-
 }
 
 // pass 1b
@@ -1066,18 +1102,18 @@ static void plan_bottleneck_blocks(f8_net* net, int max_batch) {
     //          all stride 1, intermediates read by nobody else  ->  one launch (f8_fused.hip)
     for (int i = 0; fuse_blocks && i < nn; ++i) {
         Node& c = ND[i];
-        if (c.kind != N_CONV || c.fused_add < 0 || c.cd.groups != 1 || c.cd.kernel != 1 || c.cd.stride != 1 || c.cd.pad != 0 || c.cd.relu) continue;
-        const Tensor& tb = T[c.a];
-        if (tb.consumers.size() != 1 || is_output(net, c.a) || !c.cd.quant_input) continue;
-        Node& b = ND[tb.prod];
-        if (b.kind != N_CONV || b.fused_add >= 0 || b.cd.groups != 1 || b.cd.kernel != 3 || b.cd.stride != 1 || b.cd.pad != 1 || !b.cd.quant_input) continue;
-        const Tensor& ta = T[b.a];
-        if (ta.consumers.size() != 1 || is_output(net, b.a)) continue;
-        Node& a0 = ND[ta.prod];
-        if (a0.kind != N_CONV || a0.fused_add >= 0 || a0.cd.groups != 1 || a0.cd.kernel != 1 || a0.cd.stride != 1 || a0.cd.pad != 0) continue;
-        const Node& ad = ND[c.fused_add];
-        const int other = (ad.a == c.out) ? ad.b : ad.a;
-        if (other != a0.a) continue;                          // residual operand must be the block input
+        if (!plain_conv(c, 1, 1, 0) || c.fused_add < 0 || c.cd.relu || !c.cd.quant_input) continue;
+        const int bi = private_producer(net, c.a);
+        if (bi < 0) continue;
+        Node& b = ND[bi];
+        if (!plain_conv(b, 3, 1, 1) || b.fused_add >= 0 || !b.cd.quant_input) continue;
+        const int ai = private_producer(net, b.a);
+        if (ai < 0) continue;
+        Node& a0 = ND[ai];
+        // (a0.cd.quant_input is deliberately not asked for: without it body.0 reads the shift-0 int8 form of the block input (consumer_format), an int8
+        //  form like any other to this launch; the chain launch asks for it, below)
+        if (!plain_conv(a0, 1, 1, 0) || a0.fused_add >= 0) continue;
+        if (join_other(net, c) != a0.a) continue;             // residual operand must be the block input
         const Tensor& x = T[a0.a];
         const int C = a0.cd.cin, MID = a0.cd.cout;
         if (c.cd.cout != C || b.cd.cin != MID || b.cd.cout != MID || c.cd.cin != MID) continue;
@@ -1086,16 +1122,15 @@ static void plan_bottleneck_blocks(f8_net* net, int max_batch) {
                                (opt.fuse_chain7 || !cchain_supported(C, MID, x.H, x.W, C, false));
         if (!fused_bottleneck_supported(C, MID, x.H, x.W, opt.whole_batch_launches ? max_batch : std::max(1, max_batch / opt.split), opt.fuse_stages, &R) && !chainable) {
             // no whole-block instance (the 7x7 maps of stage 3): body.0 + body.2 as one launch, the residual-carrying 1x1 stays
-            if (opt.fuse_p12 && fused_p12_supported(C, MID, x.H, x.W) && a0.cd.relu && b.cd.relu && tb.consumers.size() == 1) {
-                set_block(net, tb.prod, Block{B_P12, ta.prod, tb.prod});
+            if (opt.fuse_p12 && fused_p12_supported(C, MID, x.H, x.W) && a0.cd.relu && b.cd.relu) {
+                set_block(net, bi, Block{B_P12, ai, bi});
                 b.no_classes = true;
             }
             continue;
         }
-        set_block(net, i, Block{B_BOTTLENECK, ta.prod, tb.prod, i, -1, false, R});
+        set_block(net, i, Block{B_BOTTLENECK, ai, bi, i, -1, false, R});
         b.no_classes = true;
     }
-
 }
 
 // pass 1c
@@ -1109,18 +1144,16 @@ static void plan_dual_gemm_joins(f8_net* net) {
     for (int i = 0; opt.fuse_dual && i < nn; ++i) {
         Node& h = ND[i];
         // (claimed(): after 1b a 1x1 conv that carries a join, h, can only host an identity bottleneck; one that carries none and feeds one add, g, only be absorbed)
-        if (h.kind != N_CONV || h.fused_add < 0 || claimed(net, i) || h.cd.groups != 1 || h.cd.kernel != 1 || h.cd.pad != 0) continue;
+        // (h and g at ANY stride, deliberately: the shortcut of a stride-2 opening block is a 1x1 / 2; the two output maps are compared below)
+        if (!plain_conv(h, 1, h.cd.stride, 0) || h.fused_add < 0 || claimed(net, i)) continue;
         if (h.cd.cin % 64 != 0 || round_up(h.cd.cout, 32) <= 32) continue;          // kernel instances: BK = 64, BN = 64
-        const Node& ad = ND[h.fused_add];
-        const int other = (ad.a == h.out) ? ad.b : ad.a;
-        if (T[other].consumers.size() != 1 || is_output(net, other)) continue;
-        Node& g = ND[T[other].prod];
-        if (g.kind != N_CONV || g.fused_add >= 0 || claimed(net, T[other].prod) || g.cd.groups != 1 || g.cd.kernel != 1 || g.cd.pad != 0 ||
-            g.cd.relu || g.cd.cin % 64 != 0 || g.cd.cout != h.cd.cout) continue;
+        const int gi = private_producer(net, join_other(net, h));
+        if (gi < 0) continue;
+        Node& g = ND[gi];
+        if (!plain_conv(g, 1, g.cd.stride, 0) || g.fused_add >= 0 || claimed(net, gi) || g.cd.relu || g.cd.cin % 64 != 0 || g.cd.cout != h.cd.cout) continue;
         if (T[g.out].H != T[h.out].H || T[g.out].W != T[h.out].W) continue;
-        h.dual = T[other].prod; g.dual_host = i;
+        h.dual = gi; g.dual_host = i;
     }
-
 }
 
 // pass 1d
@@ -1137,17 +1170,15 @@ static void plan_stage_opening_blocks(f8_net* net) {
         const int bs = h.cd.stride;                            // stride of the shortcut = stride of the block's 3x3
         Node& g = ND[h.dual];
         if (g.cd.stride != 1 || !g.cd.quant_input) continue;
-        const Tensor& tb = T[g.a];
-        if (tb.consumers.size() != 1 || is_output(net, g.a)) continue;
-        Node& b = ND[tb.prod];
+        const int bi = private_producer(net, g.a);
+        if (bi < 0) continue;
+        Node& b = ND[bi];
         // (claimed: b feeds g, which carries no join — a P12 host (1b) feeds the conv that carries the block's; a0 is a 1x1 conv that carries no join: no host)
-        if (b.kind != N_CONV || b.fused_add >= 0 || claimed(net, tb.prod) || b.cd.groups != 1 || b.cd.kernel != 3 || b.cd.stride != bs || b.cd.pad != 1 ||
-            !b.cd.quant_input) continue;
-        const Tensor& ta = T[b.a];
-        if (ta.consumers.size() != 1 || is_output(net, b.a)) continue;
-        Node& a0 = ND[ta.prod];
-        if (a0.kind != N_CONV || a0.fused_add >= 0 || claimed(net, ta.prod) || a0.cd.groups != 1 || a0.cd.kernel != 1 || a0.cd.stride != 1 ||
-            a0.cd.pad != 0 || !a0.cd.quant_input || a0.a != h.a || a0.dual >= 0) continue;
+        if (!plain_conv(b, 3, bs, 1) || b.fused_add >= 0 || claimed(net, bi) || !b.cd.quant_input) continue;
+        const int ai = private_producer(net, b.a);
+        if (ai < 0) continue;
+        Node& a0 = ND[ai];
+        if (!plain_conv(a0, 1, 1, 0) || a0.fused_add >= 0 || claimed(net, ai) || !a0.cd.quant_input || a0.a != h.a || a0.dual >= 0) continue;
         const Tensor& x = T[h.a];
         int na = 0, nh = 0;
         if (consumer_format(x, a0.cd, &na, "finalize") || consumer_format(x, h.cd, &nh, "finalize")) continue;
@@ -1157,10 +1188,9 @@ static void plan_stage_opening_blocks(f8_net* net) {
         int R = 0;
         if (bs == 1 ? !(opt.fuse_ds && fused_ds_supported(C, MID, h.cd.cout, x.H, x.W, &R))
                     : !(opt.fuse_opener && fused_opener_supported(C, MID, h.cd.cout, x.H, x.W, &R))) continue;
-        set_block(net, i, Block{B_OPENING, ta.prod, tb.prod, h.dual, i, bs == 2, R});
+        set_block(net, i, Block{B_OPENING, ai, bi, h.dual, i, bs == 2, R});
         b.no_classes = true;
     }
-
 }
 
 // pass 1f
@@ -1200,11 +1230,11 @@ static void plan_stage_chains(f8_net* net) {
                     return true;
                 }
             }
-            if (h.dual >= 0 && B.kind != B_OPENING && h.cd.stride == 2 && h.cd.kernel == 1 && h.cd.quant_input && opt.fuse_tail) {
+            if (h.dual >= 0 && B.kind != B_OPENING && plain_conv(h, 1, 2, 0) && h.cd.quant_input && opt.fuse_tail) {
                 // the same for an opening block whose convs run as separate launches (stages 2 / 3 of ResNet-50; stage 1 when body.0 and the shortcut
                 // read different int8 forms): the dual-GEMM join (1c) becomes the chain's first block, body.2's int8 output is its mid2
                 const Node& g = ND[h.dual]; const Tensor& y = T[ND[h.fused_add].out]; const Tensor& x = T[h.a]; const Tensor& m2 = T[g.a];
-                if (g.cd.kernel == 1 && g.cd.stride == 1 && g.cd.quant_input && !g.cd.relu && !h.cd.relu && h.cd.pad == 0 && g.cd.pad == 0 &&
+                if (plain_conv(g, 1, 1, 0) && g.cd.quant_input && !g.cd.relu && !h.cd.relu &&      // (1c made the pair of plain 1x1 / pad 0 convs; the strides are asked here)
                     x.H == 2 * y.H && x.W == 2 * y.W && m2.H == y.H && m2.W == y.W) {
                     *bk = Blk{i, h.a, ND[h.fused_add].out, h.cd.cout, g.cd.cin, y.H, y.W, h.cd.cin, true, true};
                     return true;
@@ -1272,20 +1302,17 @@ static void plan_basic_block_chains(f8_net* net) {
         // (claimed(), here and below: the hosts so far carry a join — those of B_JOIN have `dual` —, or are a 3x3 that feeds a 1x1 conv (P12), which none of these does)
         auto bblock = [&](int i, int* in_t, int* out_t, int* C) -> bool {
             const Node& c2 = ND[i];
-            if (c2.kind != N_CONV || c2.fused_add < 0 || claimed(net, i) || c2.dual >= 0 || c2.cd.groups != 1 || c2.cd.kernel != 3 || c2.cd.stride != 1 || c2.cd.pad != 1 || c2.cd.relu || !c2.cd.quant_input) return false;
-            const Tensor& tb = T[c2.a];
-            if (tb.consumers.size() != 1 || is_output(net, c2.a)) return false;
-            const Node& c1 = ND[tb.prod];
-            if (c1.kind != N_CONV || c1.fused_add >= 0 || claimed(net, tb.prod) || c1.cd.groups != 1 || c1.cd.kernel != 3 || c1.cd.stride != 1 ||
-                c1.cd.pad != 1 || !c1.cd.quant_input || c1.dual >= 0) return false;
-            const Node& ad = ND[c2.fused_add];
-            const int other = (ad.a == c2.out) ? ad.b : ad.a;
-            if (other != c1.a) return false;
+            if (!plain_conv(c2, 3, 1, 1) || c2.fused_add < 0 || claimed(net, i) || c2.dual >= 0 || c2.cd.relu || !c2.cd.quant_input) return false;
+            const int c1i = private_producer(net, c2.a);
+            if (c1i < 0) return false;
+            const Node& c1 = ND[c1i];
+            if (!plain_conv(c1, 3, 1, 1) || c1.fused_add >= 0 || claimed(net, c1i) || !c1.cd.quant_input || c1.dual >= 0) return false;
+            if (join_other(net, c2) != c1.a) return false;
             const int cc = c1.cd.cin;
             if (c1.cd.cout != cc || c2.cd.cin != cc || c2.cd.cout != cc || cc % 32) return false;
             if (ND[T[c1.a].prod].kind == N_INPUT) return false;
             if (cluster7(cc, T[c1.a]) ? false : !(opt.fuse_bchain && bchain_supported(cc, T[c1.a].H, T[c1.a].W))) return false;
-            *in_t = c1.a; *out_t = ad.out; *C = cc;
+            *in_t = c1.a; *out_t = ND[c2.fused_add].out; *C = cc;
             return true;
         };
         for (int i = 0; i < nn; ++i) {
@@ -1320,22 +1347,18 @@ static void plan_basic_block_chains(f8_net* net) {
                 const Tensor& y = T[in_t];
                 const int c1f = T[ND[i].a].prod, adf = ND[i].fused_add;
                 if (y.consumers.size() != 2 || !((y.consumers[0] == c1f && y.consumers[1] == adf) || (y.consumers[0] == adf && y.consumers[1] == c1f))) return;
-                if (y.prod < 0 || ND[y.prod].kind != N_ADD || ND[y.prod].fused_into < 0) return;
-                const Node& ad = ND[y.prod];
-                const int hi = ad.fused_into;
+                if (ND[y.prod].kind != N_ADD || ND[y.prod].fused_into < 0) return;
+                const int hi = ND[y.prod].fused_into;
                 Node& h = ND[hi];
-                if (h.kind != N_CONV || h.fused_add != y.prod || claimed(net, hi) || h.dual >= 0 || h.cd.groups != 1 || h.cd.kernel != 1 || h.cd.stride != 2 || h.cd.pad != 0 || h.cd.relu || !h.cd.quant_input) return;
-                const int other = (ad.a == h.out) ? ad.b : ad.a;
-                if (T[other].consumers.size() != 1 || is_output(net, other)) return;
-                const int gi = T[other].prod;
+                if (!plain_conv(h, 1, 2, 0) || h.fused_add != y.prod || claimed(net, hi) || h.dual >= 0 || h.cd.relu || !h.cd.quant_input) return;
+                const int gi = private_producer(net, join_other(net, h));
+                if (gi < 0) return;
                 Node& g = ND[gi];
-                if (g.kind != N_CONV || g.fused_add >= 0 || claimed(net, gi) || g.dual >= 0 || g.cd.groups != 1 || g.cd.kernel != 3 ||
-                    g.cd.stride != 1 || g.cd.pad != 1 || g.cd.relu || !g.cd.quant_input) return;
-                if (T[g.a].consumers.size() != 1 || is_output(net, g.a)) return;
-                const int bi = T[g.a].prod;
+                if (!plain_conv(g, 3, 1, 1) || g.fused_add >= 0 || claimed(net, gi) || g.dual >= 0 || g.cd.relu || !g.cd.quant_input) return;
+                const int bi = private_producer(net, g.a);
+                if (bi < 0) return;
                 Node& b0 = ND[bi];
-                if (b0.kind != N_CONV || b0.fused_add >= 0 || claimed(net, bi) || b0.dual >= 0 || b0.cd.groups != 1 || b0.cd.kernel != 3 ||
-                    b0.cd.stride != 2 || b0.cd.pad != 1 || !b0.cd.quant_input || b0.a != h.a) return;
+                if (!plain_conv(b0, 3, 2, 1) || b0.fused_add >= 0 || claimed(net, bi) || b0.dual >= 0 || !b0.cd.quant_input || b0.a != h.a) return;
                 const Tensor& x = T[h.a];
                 if (ND[x.prod].kind == N_INPUT || x.H != 2 * y.H || x.W != 2 * y.W) return;
                 if (b0.cd.cin * 2 != C || h.cd.cin * 2 != C || b0.cd.cout != C || g.cd.cin != C || g.cd.cout != C || h.cd.cout != C) return;
@@ -1358,6 +1381,38 @@ static void plan_basic_block_chains(f8_net* net) {
     }
 }
 
+// The inverted residual that ends in project conv ci: 1x1 expand a0 -> depthwise b -> 1x1 project c [+ residual join with a0's input, res], every conv
+// requantising its input, the two intermediates private; out = the block output.  Passes 1e, 1e3 and 1e2 share it and differ in
+//   dw_ok    the depthwise geometry the pass's launch runs
+//   rechain  what counts as taken.  false: whatever claimed() says, of all three convs.  true (1e2): c may host the B_IR block 1e made and the members may
+//            be absorbed by c itself — 1e2 takes that block over —, and a0 may be the project conv of an inverted residual 1e2 CHAINED already (expand /
+//            depthwise / project / expand ...: a conv is one block's project and no other's expand).  For the members 1e2 reads absorbed_by, not claimed():
+//            a depthwise conv hosts nothing and has no dual, and a0's other marks are asked one by one.
+struct IRBlock { int a0, b, c, out; bool res; };
+static bool match_inverted_residual(const f8_net* net, int ci, bool (*dw_ok)(const Node&), bool rechain, IRBlock* k) {
+    const auto& T = net->tensors; const auto& ND = net->nodes;
+    const Node& c = ND[ci];
+    // (claimed(): of the hosts before 1e only an identity bottleneck's is a stride-1 1x1 conv without `dual`, as c and a0 are; depthwise convs are the passes 1e .. 1k's alone)
+    if (!plain_conv(c, 1, 1, 0) || !c.cd.quant_input || claimed(net, ci, rechain ? B_IR : B_NONE) || c.dual >= 0) return false;
+    auto member_taken = [&](int m) { return rechain ? (ND[m].absorbed_by >= 0 && ND[m].absorbed_by != ci) : claimed(net, m); };
+    const int bi = private_producer(net, c.a);
+    if (bi < 0) return false;
+    const Node& b = ND[bi];
+    if (!dw_ok(b) || !b.cd.quant_input || b.fused_add >= 0 || member_taken(bi)) return false;
+    const int ai = private_producer(net, b.a);
+    if (ai < 0) return false;
+    const Node& a0 = ND[ai];
+    if (!plain_conv(a0, 1, 1, 0) || !a0.cd.quant_input || a0.fused_add >= 0 || member_taken(ai) || a0.dual >= 0) return false;
+    if (rechain && (a0.dual_host >= 0 || (a0.blk.kind != B_NONE && !(a0.blk.kind == B_IR && a0.chain_into >= 0)))) return false;
+    if (ND[T[a0.a].prod].kind == N_INPUT) return false;         // the network input has its own layouts
+    *k = IRBlock{ai, bi, ci, c.out, false};
+    if (c.fused_add >= 0) {                                       // a residual join must be with the block input, at stride 1
+        if (join_other(net, c) != a0.a || b.cd.stride != 1) return false;
+        k->res = true; k->out = ND[c.fused_add].out;
+    }
+    return true;
+}
+
 // pass 1e
 static void plan_inverted_residuals(f8_net* net) {
     auto& T = net->tensors;
@@ -1367,29 +1422,11 @@ static void plan_inverted_residuals(f8_net* net) {
     // ---- 1e. MobileNet-V2 inverted residual: 1x1 expand (ReLU) -> depthwise 3x3 (ReLU) -> 1x1 project [+ residual with the
     //          block input], intermediates read by nobody else  ->  one launch (f8_ir.hip), the expanded tensors stay in LDS
     for (int i = 0; opt.fuse_ir && i < nn; ++i) {
-        Node& c = ND[i];
-        // (claimed(): of the hosts so far only an identity bottleneck's is a stride-1 1x1 conv without `dual`, as c and a0 are; depthwise convs are this pass's alone)
-        if (c.kind != N_CONV || c.cd.groups != 1 || c.cd.kernel != 1 || c.cd.stride != 1 || c.cd.pad != 0 || !c.cd.quant_input ||
-            claimed(net, i) || c.dual >= 0) continue;
-        const Tensor& tb = T[c.a];
-        if (tb.consumers.size() != 1 || is_output(net, c.a)) continue;
-        Node& b = ND[tb.prod];
-        if (b.kind != N_CONV || b.cd.groups == 1 || b.cd.groups != b.cd.cin || b.cd.kernel != 3 || b.cd.pad != 1 || (b.cd.stride != 1 && b.cd.stride != 2) ||
-            !b.cd.quant_input || b.fused_add >= 0 || claimed(net, tb.prod)) continue;
-        const Tensor& ta = T[b.a];
-        if (ta.consumers.size() != 1 || is_output(net, b.a)) continue;
-        Node& a0 = ND[ta.prod];
-        if (a0.kind != N_CONV || a0.cd.groups != 1 || a0.cd.kernel != 1 || a0.cd.stride != 1 || a0.cd.pad != 0 || a0.fused_add >= 0 ||
-            claimed(net, ta.prod) || a0.dual >= 0 || !a0.cd.quant_input) continue;      // (a host too: chains of 1x1 / dw / 1x1 / dw ...)
-        if (ND[T[a0.a].prod].kind == N_INPUT) continue;          // the network input has its own layouts
-        if (c.fused_add >= 0) {                                   // a residual join must be with the block input
-            const Node& ad = ND[c.fused_add];
-            const int other = (ad.a == c.out) ? ad.b : ad.a;
-            if (other != a0.a || b.cd.stride != 1) continue;
-        }
-        const Tensor& x = T[a0.a];
+        IRBlock k;
+        if (!match_inverted_residual(net, i, [](const Node& b) { return depthwise_conv(b, 3, 1, true); }, false, &k)) continue;
+        const Tensor& x = T[ND[k.a0].a];
         int R = 0, G = 0;
-        if (!fused_ir_config(x.Cs, round_up(c.cd.cout, 32), x.H, x.W, b.cd.stride, &R, &G)) continue;
+        if (!fused_ir_config(x.Cs, round_up(ND[i].cd.cout, 32), x.H, x.W, ND[k.b].cd.stride, &R, &G)) continue;
         if (opt.fuse_ir == 1) {
             // Where the fused launch wins (measured per block on MobileNet-V2 at 128 images, round 3 — after the depthwise phase moved to
             // the matrix cores and the requantisations to five operations; three launches / fused, us): stage 1 (112x112 / 2 and 56x56
@@ -1397,11 +1434,10 @@ static void plan_inverted_residuals(f8_net* net) {
             // 68 / 38.7; stages 3 - 4 (28x28 / 2, 14x14): 44 / 30.5, 48 / 34.4, 46 / 33.3, 45 / 30.5, 51 / 37.4 and, with 576 expanded
             // channels, 49.1 / 46.3 and 46.1 / 43.3.  The 7x7 blocks (960 channels = 15 chunks over 49 pixels, 64 workgroups for 128
             // images) stay three launches: 34 - 40 / 90 - 114.  fuse_ir = 2 fuses every block that has an instance.
-            if (T[c.out].H * T[c.out].W < 128) continue;
+            if (T[ND[i].out].H * T[ND[i].out].W < 128) continue;
         }
-        set_block(net, i, Block{B_IR, ta.prod, tb.prod, i, -1, false, R, G});
+        set_block(net, i, Block{B_IR, k.a0, k.b, i, -1, false, R, G});
     }
-
 }
 
 // pass 1e3
@@ -1414,29 +1450,13 @@ static void plan_inverted_residuals_k(f8_net* net) {
     //           with the depthwise geometry exchanged; K = 3 / pad 1 stays 1e's (its choice to leave small maps unfused included), pad < K / 2 stays
     //           three launches.  Any format: the launch has a generic instance.
     for (int i = 0; net->opt.fuse_irk && i < nn; ++i) {
-        Node& c = ND[i];
-        if (c.kind != N_CONV || c.cd.groups != 1 || c.cd.kernel != 1 || c.cd.stride != 1 || c.cd.pad != 0 || !c.cd.quant_input ||
-            claimed(net, i) || c.dual >= 0) continue;
-        const Tensor& tb = T[c.a];
-        if (tb.prod < 0 || tb.consumers.size() != 1 || is_output(net, c.a)) continue;
-        Node& b = ND[tb.prod];
-        if (b.kind != N_CONV || b.cd.groups == 1 || b.cd.groups != b.cd.cin || b.cd.cout != b.cd.cin || (b.cd.kernel != 5 && b.cd.kernel != 7) ||
-            b.cd.pad != b.cd.kernel / 2 || (b.cd.stride != 1 && b.cd.stride != 2) || !b.cd.quant_input || b.fused_add >= 0 || claimed(net, tb.prod)) continue;
-        const Tensor& ta = T[b.a];
-        if (ta.prod < 0 || ta.consumers.size() != 1 || is_output(net, b.a)) continue;
-        Node& a0 = ND[ta.prod];
-        if (a0.kind != N_CONV || a0.cd.groups != 1 || a0.cd.kernel != 1 || a0.cd.stride != 1 || a0.cd.pad != 0 || a0.fused_add >= 0 ||
-            claimed(net, ta.prod) || a0.dual >= 0 || !a0.cd.quant_input) continue;
-        if (T[a0.a].prod < 0 || ND[T[a0.a].prod].kind == N_INPUT) continue;      // the network input has its own layouts
-        if (c.fused_add >= 0) {                                   // a residual join must be with the block input, at stride 1
-            const Node& ad = ND[c.fused_add];
-            const int other = (ad.a == c.out) ? ad.b : ad.a;
-            if (other != a0.a || b.cd.stride != 1) continue;
-        }
-        const Tensor& x = T[a0.a];
+        IRBlock k;
+        if (!match_inverted_residual(net, i, [](const Node& b) { return (b.cd.kernel == 5 || b.cd.kernel == 7) && depthwise_conv(b, b.cd.kernel, b.cd.kernel / 2, true); },
+                                     false, &k)) continue;
+        const Tensor& x = T[ND[k.a0].a];
         int R = 0, G = 0;
-        if (!irk_config(b.cd.kernel, x.Cs, round_up(c.cd.cout, 32), x.H, x.W, b.cd.stride, &R, &G)) continue;
-        set_block(net, i, Block{B_IRK, ta.prod, tb.prod, i, -1, false, R, G});
+        if (!irk_config(ND[k.b].cd.kernel, x.Cs, round_up(ND[i].cd.cout, 32), x.H, x.W, ND[k.b].cd.stride, &R, &G)) continue;
+        set_block(net, i, Block{B_IRK, k.a0, k.b, i, -1, false, R, G});
     }
 }
 
@@ -1447,44 +1467,17 @@ static void plan_inverted_residual_chains(f8_net* net) {
     const int nn = (int)ND.size();
     const Options& opt = net->opt;
     // ---- 1e2. runs of >= 2 consecutive STRIDE-1 inverted residuals on one map  ->  ONE launch, one workgroup per image (f8_irchain.hip): the
-    //           block outputs between them exist in no form at all (int8 block input and int32 stream in LDS).  Its own matcher: a block pass 1e
+    //           block outputs between them exist in no form at all (int8 block input and int32 stream in LDS).  It matches for itself: a block pass 1e
     //           left as three launches (the 7x7 maps under fuse_ir = 1) is taken as well, and the block 1e made of a chained one is released first.
     if (!opt.fuse_irchain) return;
-    // the stride-1 block whose project conv is c: expand a0 -> depthwise b -> c [+ join with a0's input]; out = the block output
-    struct Blk { int a0, b, c, out; bool res; };
-    auto match = [&](int ci, Blk* k) -> bool {
-        const Node& c = ND[ci];
-        if (c.kind != N_CONV || c.cd.groups != 1 || c.cd.kernel != 1 || c.cd.stride != 1 || c.cd.pad != 0 || !c.cd.quant_input ||
-            claimed(net, ci, B_IR) || c.dual >= 0) return false;      // (the block 1e hosted here is taken over; one this pass chained already is claimed by its chain)
-        const Tensor& tb = T[c.a];
-        if (tb.prod < 0 || tb.consumers.size() != 1 || is_output(net, c.a)) return false;
-        const int bi = tb.prod;
-        const Node& b = ND[bi];
-        if (b.kind != N_CONV || b.cd.groups == 1 || b.cd.groups != b.cd.cin || b.cd.cout != b.cd.cin || b.cd.kernel != 3 || b.cd.pad != 1 || b.cd.stride != 1 ||
-            !b.cd.quant_input || b.fused_add >= 0 || (b.absorbed_by >= 0 && b.absorbed_by != ci)) return false;      // (a member of c's own block: 1e)
-        const Tensor& ta = T[b.a];
-        if (ta.prod < 0 || ta.consumers.size() != 1 || is_output(net, b.a)) return false;
-        const int ai = ta.prod;
-        const Node& a0 = ND[ai];
-        if (a0.kind != N_CONV || a0.cd.groups != 1 || a0.cd.kernel != 1 || a0.cd.stride != 1 || a0.cd.pad != 0 || !a0.cd.quant_input || a0.fused_add >= 0 ||
-            (a0.absorbed_by >= 0 && a0.absorbed_by != ci) || a0.dual >= 0 || a0.dual_host >= 0 || (a0.blk.kind != B_NONE && !(a0.blk.kind == B_IR && a0.chain_into >= 0))) return false;
-        // (not claimed(a0): the project conv of an inverted residual this pass CHAINED passes — that mark is the term this list never had; the other hosts are no stride-1 1x1 conv without a join)
-        if (T[a0.a].prod < 0 || ND[T[a0.a].prod].kind == N_INPUT) return false;      // the network input has its own layouts
-        k->a0 = ai; k->b = bi; k->c = ci; k->res = false; k->out = c.out;
-        if (c.fused_add >= 0) {                                   // a residual join must be with the block input
-            const Node& ad = ND[c.fused_add];
-            const int other = (ad.a == c.out) ? ad.b : ad.a;
-            if (other != a0.a || T[c.out].consumers.size() != 1 || is_output(net, c.out)) return false;
-            k->res = true; k->out = ad.out;
-        }
-        const Tensor& x = T[a0.a];
-        return T[k->out].H == x.H && T[k->out].W == x.W;
-    };
+    // the stride-1 block whose project conv is ci.  (Its map is the block input's: three stride-1 convs, 1x1 / pad 0 and 3x3 / pad 1.  A joined project
+    // conv's result is read by the join alone: pass 1, the only writer of fused_add, asked for that.)
+    auto match = [&](int ci, IRBlock* k) { return match_inverted_residual(net, ci, [](const Node& b) { return depthwise_conv(b, 3, 1, false); }, true, k); };
     // the widest block input / output and the widest int32 stream a block of the run joins: what irchain_supported checks
-    auto fits = [&](const std::vector<Blk>& run) {
+    auto fits = [&](const std::vector<IRBlock>& run) {
         const Tensor& x = T[ND[run[0].a0].a];
         int cin_max = 0, cout_max = 0, keep_max = 0;
-        for (const Blk& k : run) {
+        for (const IRBlock& k : run) {
             const int ci = T[ND[k.a0].a].Cs, co = round_up(ND[k.c].cd.cout, 32);
             cin_max = std::max(cin_max, ci); cout_max = std::max(cout_max, co);
             if (k.res) keep_max = std::max(keep_max, ci);
@@ -1492,12 +1485,12 @@ static void plan_inverted_residual_chains(f8_net* net) {
         return (int)run.size() <= kIRChainMaxBlocks && irchain_supported(x.H, x.W, cin_max, cout_max, keep_max);
     };
     for (int i = 0; i < nn; ++i) {
-        Blk k0;
+        IRBlock k0;
         if (!match(i, &k0)) continue;
-        std::vector<Blk> run{k0};
+        std::vector<IRBlock> run{k0};
         if (!fits(run)) continue;
         for (;;) {                                                // extend: the block output's only readers are the next block's expand conv and its join
-            const Blk& last = run.back();
+            const IRBlock& last = run.back();
             if (is_output(net, last.out)) break;
             const Tensor& o = T[last.out];
             int nxt = -1, joins = 0, others = 0;
@@ -1513,7 +1506,7 @@ static void plan_inverted_residual_chains(f8_net* net) {
             if (e1.consumers.size() != 1) break;
             const Tensor& e2 = T[ND[e1.consumers[0]].out];
             if (e2.consumers.size() != 1) break;
-            Blk kn;
+            IRBlock kn;
             if (!match(e2.consumers[0], &kn) || kn.a0 != nxt || ND[kn.a0].a != last.out) break;
             if (joins != (kn.res ? 1 : 0)) break;
             if (kn.res && ND[ND[kn.c].fused_add].fused_into != kn.c) break;
@@ -1522,7 +1515,7 @@ static void plan_inverted_residual_chains(f8_net* net) {
         }
         if (run.size() < 2) continue;
         std::vector<int> hosts;
-        for (const Blk& k : run) {
+        for (const IRBlock& k : run) {
             if (ND[k.c].blk.kind != B_NONE) release_block(net, k.c);      // (pass 1e's block: its tile is the stand-alone launch's)
             set_block(net, k.c, Block{B_IR, k.a0, k.b, k.c});
             hosts.push_back(k.c);
@@ -1547,33 +1540,34 @@ static void plan_mobilenet_v2_head(f8_net* net) {
     //          by those two properties); every other condition is the same.  Before 1j / 1k, which leave the claimed block 0 alone.
     for (int i = 0; (opt.fuse_head2 || opt.fuse_head_dws) && opt.fuse_stem && i < nn; ++i) {
         Node& c = ND[i];
-        if (c.kind != N_CONV || c.cd.groups != 1 || c.cd.kernel != 1 || c.cd.stride != 1 || c.cd.pad != 0 || !c.cd.quant_input ||
-            c.cd.input_signed || c.fused_add >= 0 || claimed(net, i) || c.dual >= 0 || is_output(net, c.out)) continue;      // (claimed: a stride-1 1x1 conv that carries no join and has no `dual` hosts only B_IR)
+        if (!plain_conv(c, 1, 1, 0) || !c.cd.quant_input || c.cd.input_signed || c.fused_add >= 0 || claimed(net, i) || c.dual >= 0 ||
+            is_output(net, c.out)) continue;      // (claimed: a stride-1 1x1 conv that carries no join and has no `dual` hosts only B_IR)
         if (c.cd.cin != 32) continue;
         if (head_dws_form(c)) { if (!opt.fuse_head_dws || round_up(c.cd.cout, 32) > 64) continue; }      // MobileNet-V1's form
         else if (!opt.fuse_head2) continue;                                                                // MobileNet-V2's: no ReLU, <= 32 couts
+        const int bi = private_producer(net, c.a);
+        if (bi < 0) continue;
         const Tensor& tb = T[c.a];
-        if (tb.consumers.size() != 1 || is_output(net, c.a)) continue;
-        Node& b = ND[tb.prod];
-        if (b.kind != N_CONV || b.cd.groups != b.cd.cin || b.cd.cin != 32 || b.cd.cout != 32 || b.cd.kernel != 3 || b.cd.stride != 1 || b.cd.pad != 1 ||
-            !b.cd.relu || !b.cd.quant_input || b.cd.input_signed || b.fused_add >= 0 || b.absorbed_by >= 0) continue;
+        Node& b = ND[bi];
+        // (b and h: absorbed_by is all of claimed() here — a depthwise conv hosts nothing and has no dual, and the one 3x3 / 2 host, a stride-2 P12's, reads
+        //  a 1x1 conv's output, not the network input.  32 channels: more than one, as depthwise_conv asks, and as many outputs, as add_conv_node does)
+        if (!depthwise_conv(b, 3, 1, false) || b.cd.cin != 32 || !b.cd.relu || !b.cd.quant_input || b.cd.input_signed || b.fused_add >= 0 || b.absorbed_by >= 0) continue;
+        const int hi = private_producer(net, b.a);
+        if (hi < 0) continue;
         const Tensor& ta = T[b.a];
-        if (ta.consumers.size() != 1 || is_output(net, b.a)) continue;
-        Node& h = ND[ta.prod];
-        if (h.kind != N_CONV || h.cd.groups != 1 || h.cd.kernel != 3 || h.cd.stride != 2 || h.cd.pad != 1 || h.cd.cin > 4 || h.cd.cout != 32 || !h.cd.relu ||
-            h.fused_add >= 0 || h.absorbed_by >= 0 || is_output(net, h.a)) continue;
+        Node& h = ND[hi];
+        if (!plain_conv(h, 3, 2, 1) || h.cd.cin > 4 || h.cd.cout != 32 || !h.cd.relu || h.fused_add >= 0 || h.absorbed_by >= 0 || is_output(net, h.a)) continue;
         const Tensor& x = T[h.a];
-        if (x.prod < 0 || ND[x.prod].kind != N_INPUT || x.consumers.size() != 1 || !(!h.cd.quant_input || x.fl == h.cd.input_fl)) continue;
+        if (ND[x.prod].kind != N_INPUT || x.consumers.size() != 1 || !(!h.cd.quant_input || x.fl == h.cd.input_fl)) continue;
         if (!head2_supported(x.H, x.W) || ta.H * 2 != x.H || ta.W * 2 != x.W) continue;
         int na = 0, nb2 = 0;
-        if (consumer_format(ta, b.cd, &na, "finalize") || consumer_format(tb, c.cd, &nb2, "finalize") || na < 1 || nb2 < 1 || na > 16 || nb2 > 16 ||
-            false) continue;   // 16: kRequantU8MaxShift (the launch's float-converter form; accumulators the planner cannot bound take its integer form: rq_int)
+        if (consumer_format(ta, b.cd, &na, "finalize") || consumer_format(tb, c.cd, &nb2, "finalize") || na < 1 || nb2 < 1 || na > 16 || nb2 > 16) continue;
+        // 16: kRequantU8MaxShift (the launch's float-converter form; accumulators the planner cannot bound take its integer form: rq_int)
         bool int8_readers = !T[c.out].consumers.empty() && T[c.out].consumers.size() <= 2;
         for (int u : T[c.out].consumers) if (ND[u].kind != N_CONV || !ND[u].cd.quant_input) int8_readers = false;
         if (!int8_readers) continue;
-        set_block(net, i, Block{B_HEAD2, ta.prod, tb.prod, i});
+        set_block(net, i, Block{B_HEAD2, hi, bi, i});
     }
-
 }
 
 // pass 1i
@@ -1586,10 +1580,10 @@ static void plan_last_conv_and_pool(f8_net* net) {
     //          pixels in the epilogue (f8_pool.hip); the conv's int32 result — read by nobody but the pool — never exists
     for (int i = 0; opt.fuse_pool && i < nn; ++i) {
         Node& p = ND[i];
-        if (p.kind != N_AVGPOOL || is_output(net, p.a) || T[p.a].consumers.size() != 1) continue;
+        if (p.kind != N_AVGPOOL) continue;
+        int ci = private_producer(net, p.a);
+        if (ci < 0) continue;
         const Tensor& t = T[p.a];
-        if (t.prod < 0) continue;
-        int ci = t.prod;
         if (ND[ci].kind == N_ADD) { if (ND[ci].fused_into < 0) continue; ci = ND[ci].fused_into; }
         Node& c = ND[ci];
         if (c.kind == N_CONV && c.chain_into == ci && c.chain_kind == C_BASIC_CLUSTER && c.fused_add >= 0 && ND[c.fused_add].out == p.a && !is_output(net, p.out)) {
@@ -1601,14 +1595,33 @@ static void plan_last_conv_and_pool(f8_net* net) {
             c.pool = i; p.pool_host = ci;                         // the last block of a 7x7 cluster chain: the pool is summed from its stream registers (f8_cchain.hip)
             continue;
         }
-        if (c.kind != N_CONV || claimed(net, ci) || c.dual >= 0 || c.cd.groups != 1 || c.cd.kernel != 1 || c.cd.stride != 1 || c.cd.pad != 0 || !c.cd.quant_input) continue;
+        if (!plain_conv(c, 1, 1, 0) || claimed(net, ci) || c.dual >= 0 || !c.cd.quant_input) continue;
         if ((c.fused_add >= 0 ? ND[c.fused_add].out : c.out) != p.a) continue;
         if (c.fused_add < 0 && T[c.out].consumers.size() != 1) continue;
         const int ckp = round_up(c.cd.cin, 32), coutP = round_up(c.cd.cout, 32);
         if (!conv1x1_pool_supported(ckp, coutP, t.H * t.W)) continue;
         c.pool = i; p.pool_host = ci;
     }
+}
 
+// The depthwise-separable block that ends in 1x1 conv ci (passes 1j and 1k): depthwise 3x3 / 1 or 2, pad 1, ReLU -> 1x1 [ReLU], both requantising their
+// input, neither taken or linked to anything else, the depthwise result private, the block input not the network's, the block output no network output
+// and read by somebody.  Returns the depthwise conv, -1: no such block.
+static int match_depthwise_separable(const f8_net* net, int ci) {
+    const auto& T = net->tensors; const auto& ND = net->nodes;
+    const Node& c = ND[ci];
+    if (!plain_conv(c, 1, 1, 0) || !c.cd.quant_input || c.fused_add >= 0 || c.dual >= 0 || c.pool >= 0 || claimed(net, ci)) return -1;
+    const int bi = private_producer(net, c.a);
+    if (bi < 0) return -1;
+    const Node& b = ND[bi];
+    if (!depthwise_conv(b, 3, 1, true) || !b.cd.relu || !b.cd.quant_input || b.fused_add >= 0 || claimed(net, bi)) return -1;
+    const Tensor& x = T[b.a];
+    if (ND[x.prod].kind == N_INPUT) return -1;                                        // the network input has its own layouts
+    // whole 32-channel slices of REAL channels: a 48-channel block input has a 64-channel form, which dws_supported / dws7_supported — asked with Cs — would take
+    if (b.cd.cin & 31) return -1;
+    if (is_output(net, c.out) || T[c.out].consumers.empty()) return -1;              // the net output is int32
+    if (T[c.a].H * b.cd.stride != x.H || T[c.a].W * b.cd.stride != x.W) return -1;   // (stride 2: an even map)
+    return bi;
 }
 
 // pass 1j
@@ -1617,36 +1630,15 @@ static void plan_depthwise_separable(f8_net* net, int max_batch) {
     auto& ND = net->nodes;
     const int nn = (int)ND.size();
     // ---- 1j. MobileNet-V1 depthwise-separable block (option fuse_dws): depthwise 3x3 / 1 or 2, pad 1 (ReLU) -> 1x1 [ReLU], the depthwise result read
-    //          by nobody else  ->  ONE launch (f8_dws.hip), the depthwise result only ever in LDS.  The last of the passes 1x: whatever an earlier one
+    //          by nobody else  ->  ONE launch (f8_dws.hip), the depthwise result only ever in LDS.  Behind every pass but 1k: whatever an earlier one
     //          claimed (MobileNet-V2's head and inverted residuals, the 1x1 + average pool) stays what it is.  The launch writes int8 forms only, so
     //          every reader of the block output must be a conv of its own (or another block of this kind) that requantises its input, in at most two formats.
     for (int i = 0; net->opt.fuse_dws && i < nn; ++i) {
-        Node& c = ND[i];
-        if (c.kind != N_CONV || c.cd.groups != 1 || c.cd.kernel != 1 || c.cd.stride != 1 || c.cd.pad != 0 || !c.cd.quant_input ||
-            c.fused_add >= 0 || c.dual >= 0 || c.pool >= 0 || claimed(net, i)) continue;
-        const Tensor& tb = T[c.a];
-        if (tb.prod < 0 || tb.consumers.size() != 1 || is_output(net, c.a)) continue;
-        const int bi = tb.prod;
-        const Node& b = ND[bi];
-        if (b.kind != N_CONV || b.cd.groups == 1 || b.cd.groups != b.cd.cin || b.cd.cout != b.cd.cin || b.cd.kernel != 3 || b.cd.pad != 1 ||
-            (b.cd.stride != 1 && b.cd.stride != 2) || !b.cd.relu || !b.cd.quant_input || b.fused_add >= 0 || claimed(net, bi)) continue;
-        const Tensor& x = T[b.a];
-        if (x.prod < 0 || ND[x.prod].kind == N_INPUT || (b.cd.cin & 31)) continue;      // (the network input has its own layouts)
-        if (is_output(net, c.out) || T[c.out].consumers.empty()) continue;                 // the net output is int32
-        bool int8_readers = true;
-        std::vector<std::pair<int, int>> fmts;
-        for (int u : T[c.out].consumers) {
-            const Node& un = ND[u];
-            int n = 0;
-            if ((un.kind != N_CONV && un.kind != N_LINEAR) || !un.cd.quant_input || consumer_format(T[c.out], un.cd, &n, "finalize") ||
-                (claimed(net, u) && !(un.absorbed_by >= 0 && ND[un.absorbed_by].blk.kind == B_DWS))) { int8_readers = false; break; }
-            const std::pair<int, int> f{n, un.cd.input_signed ? 1 : 0};
-            if (std::find(fmts.begin(), fmts.end(), f) == fmts.end()) fmts.push_back(f);
-        }
-        if (!int8_readers || fmts.size() > 2) continue;
+        const int bi = match_depthwise_separable(net, i);
+        if (bi < 0 || !int8_readers_only(net, ND[i].out)) continue;
+        const Tensor& x = T[ND[bi].a];
         int R = 0;
-        if (!dws_supported(x.Cs, round_up(c.cd.cout, 32), x.H, x.W, b.cd.stride, max_batch, &R)) continue;      // (7-wide maps: no matrix-core walker form; pass 1k)
-        if (tb.H * b.cd.stride != x.H || tb.W * b.cd.stride != x.W) continue;
+        if (!dws_supported(x.Cs, round_up(ND[i].cd.cout, 32), x.H, x.W, ND[bi].cd.stride, max_batch, &R)) continue;      // (7-wide maps: no matrix-core walker form; pass 1k)
         set_block(net, i, Block{B_DWS, bi, -1, i, -1, false, R});
     }
 }
@@ -1660,18 +1652,10 @@ static void plan_depthwise_separable_7x7(f8_net* net, int max_batch) {
     //          a block output whose only reader is the average pool, itself not the net output — the pool is then summed in the launch (pool / pool_host, as 1i)
     //          and the block output exists in no form.  After 1j, so the last of the passes 1x: whatever an earlier one claimed stays claimed.
     for (int i = 0; net->opt.fuse_dws7 && i < nn; ++i) {
+        const int bi = match_depthwise_separable(net, i);
+        if (bi < 0) continue;
         Node& c = ND[i];
-        if (c.kind != N_CONV || c.cd.groups != 1 || c.cd.kernel != 1 || c.cd.stride != 1 || c.cd.pad != 0 || !c.cd.quant_input ||
-            c.fused_add >= 0 || c.dual >= 0 || c.pool >= 0 || claimed(net, i)) continue;
-        const Tensor& tb = T[c.a];
-        if (tb.prod < 0 || tb.consumers.size() != 1 || is_output(net, c.a)) continue;
-        const int bi = tb.prod;
-        const Node& b = ND[bi];
-        if (b.kind != N_CONV || b.cd.groups == 1 || b.cd.groups != b.cd.cin || b.cd.cout != b.cd.cin || b.cd.kernel != 3 || b.cd.pad != 1 ||
-            (b.cd.stride != 1 && b.cd.stride != 2) || !b.cd.relu || !b.cd.quant_input || b.fused_add >= 0 || claimed(net, bi)) continue;
-        const Tensor& x = T[b.a];
-        if (x.prod < 0 || ND[x.prod].kind == N_INPUT || (b.cd.cin & 31)) continue;      // (the network input has its own layouts)
-        if (is_output(net, c.out) || T[c.out].consumers.empty()) continue;                 // the net output is int32
+        const Tensor& x = T[ND[bi].a];
         // an inverted residual — expanding 1x1 (ReLU) -> depthwise -> 1x1 WITHOUT ReLU — is passes 1e / 1e2's to decide: the 7x7 ones that fuse_ir = 1
         // leaves as three launches were measured there (1j never sees them: it has no 7-wide form)
         const Node& xp = ND[x.prod];
@@ -1682,21 +1666,9 @@ static void plan_depthwise_separable_7x7(f8_net* net, int max_batch) {
             if (ND[pi].pool_host >= 0 || is_output(net, ND[pi].out)) continue;             // (a pooled net output is int32 of the caller's: the pool stays a launch, and so does this conv's int32 result)
             pool = pi;
         }
-        bool int8_readers = true;
-        std::vector<std::pair<int, int>> fmts;
-        for (int u : T[c.out].consumers) {
-            if (pool >= 0) break;
-            const Node& un = ND[u];
-            int n = 0;
-            if ((un.kind != N_CONV && un.kind != N_LINEAR) || !un.cd.quant_input || consumer_format(T[c.out], un.cd, &n, "finalize") ||
-                (claimed(net, u) && !(un.absorbed_by >= 0 && ND[un.absorbed_by].blk.kind == B_DWS))) { int8_readers = false; break; }
-            const std::pair<int, int> f{n, un.cd.input_signed ? 1 : 0};
-            if (std::find(fmts.begin(), fmts.end(), f) == fmts.end()) fmts.push_back(f);
-        }
-        if (!int8_readers || fmts.size() > 2) continue;
+        if (pool < 0 && !int8_readers_only(net, c.out)) continue;
         int I = 0;
-        if (!dws7_supported(x.Cs, round_up(c.cd.cout, 32), x.H, x.W, b.cd.stride, max_batch, pool >= 0, &I)) continue;
-        if (tb.H * b.cd.stride != x.H || tb.W * b.cd.stride != x.W) continue;
+        if (!dws7_supported(x.Cs, round_up(c.cd.cout, 32), x.H, x.W, ND[bi].cd.stride, max_batch, pool >= 0, &I)) continue;
         set_block(net, i, Block{B_DWS, bi, -1, i, -1, false, 0, 0, I});
         if (pool >= 0) { c.pool = pool; ND[pool].pool_host = i; }
     }
@@ -1735,7 +1707,7 @@ static void plan_tensor_forms(f8_net* net) {
                 const Role role = role_in_block(net, i, &host);
                 const BlockKind bk = role != R_NONE ? ND[host].blk.kind : B_NONE;
                 const int pos = chain_pos(net, host);            // of its block in a chain launch: the tensors between a chain's blocks exist in no form at all
-                auto stream = [&]() -> Tensor& { const Node& ad = ND[nd.fused_add]; return T[(ad.a == nd.out) ? ad.b : ad.a]; };   // the other operand of nd's join
+                auto stream = [&]() -> Tensor& { return T[join_other(net, nd)]; };   // the other operand of nd's join
                 bool in_launch = true;                           // nd's source lives in LDS / registers inside the launch: no HBM form
                 switch (bk) {
                     case B_OPENING: in_launch = role == R_B2 || role == R_B4; break;      // (body.0 and the shortcut read the block input)
@@ -1809,7 +1781,6 @@ static void plan_tensor_forms(f8_net* net) {
             default: break;
         }
     }
-
 }
 
 // pass 3: the launches in node order, one emitter per launch family.  Each fills one Step: its input / output forms, the packed weights, the
@@ -1848,7 +1819,9 @@ static void pack_block(f8_net* net, const Block& r, bool frag, Step& st) {
     for (int c : {r.b0, r.b2, r.b4, r.sc}) {
         if (c < 0) continue;
         Node& n = net->nodes[c];
-        if (n.depthwise) pack_dw_weights(net, n); else pack_conv_weights(net, n);
+        if (!n.depthwise) pack_conv_weights(net, n);
+        else if (dw_general(n.cd)) pack_dwk_weights(net, n);      // (the 5x5 / 7x7 of a B_IRK block)
+        else pack_dw_weights(net, n);
         if (frag) pack_frag_weights(net, n);
         st.ops_per_img += conv_ops(net, n); st.bytes_const += weight_bytes(net, n);
     }
@@ -1858,6 +1831,15 @@ static std::string block_names(const f8_net* net, const Block& r) {
     std::string s;
     for (int c : {r.b0, r.b2, r.b4, r.sc}) if (c >= 0) s += (s.empty() ? "" : "+") + tname(net, net->nodes[c].out);
     return s;
+}
+
+// The tensor whose forms the launch hosted by conv c writes, t — or, where the plan folded the average pool behind it into the launch (c.pool; 1i, 1k), the
+// POOLED tensor: the launch sums the map's pixels, so the step's outputs are that tensor's forms (its int32 form if nobody asked for another)
+static int pooled_output(f8_net* net, const Node& c, int t) {
+    if (c.pool < 0) return t;
+    const int pt = net->nodes[c.pool].out;
+    if (net->tensors[pt].forms.empty()) add_form(net->tensors[pt], FORM_I32, 0, 0);
+    return pt;
 }
 
 static int emit_input(f8_net* net, int i, Step& st, std::vector<int>* extra) {
@@ -1958,12 +1940,7 @@ static int emit_bcchain(f8_net* net, int i, Step& st, std::vector<int>* extra) {
     else if ((rc = conv_input_i8(net, ND[r0.sc], &st.res_t, &st.res_f))) return rc;     // the block input in the shortcut's format
     for (int h : ch) pack_block(net, ND[h].blk, true, st);
     const Tensor& o = T[ND[nd.fused_add].out];               // the stage's output map
-    int out_t = ND[nd.fused_add].out;
-    if (nd.pool >= 0) {                                      // ... summed over its pixels in the launch (1i): the step's outputs are the POOLED tensor's forms
-        out_t = ND[nd.pool].out;
-        if (T[out_t].forms.empty()) add_form(T[out_t], FORM_I32, 0, 0);
-    }
-    select_outputs(net, out_t, &st.out, extra);
+    select_outputs(net, pooled_output(net, nd, ND[nd.fused_add].out), &st.out, extra);
     const double px = (double)o.H * o.W, opx = nd.pool >= 0 ? 1.0 : px, n = (double)ch.size();
     st.bytes_per_img = (tail ? px * (T[st.src_t].Cs + T[st.res_t].Cs) : px * o.Cs * 4) + out_bytes(st, o, opx);   // (tail: mid0 + the shortcut's pixels)
     // per block: the first conv's int8 output (the TAIL join has none), the join, the next block's int8 input; the last block's are the output forms
@@ -1987,13 +1964,8 @@ static int emit_chain(f8_net* net, int i, Step& st, std::vector<int>* extra) {
     else if (int rc = conv_input_i8(net, ND[tail ? r0.sc : r0.b0], &st.src_t, &st.src_f)) return rc;    // tail: the shortcut's int8 form
     else if (tail && (rc = conv_input_i8(net, a0, &st.src2_t, &st.src2_f))) return rc;                  // mid2 in body.4's format
     for (int h : ch) pack_block(net, ND[h].blk, true, st);
-    int out_t = ND[nd.fused_add].out;
-    const Tensor& o = T[out_t];                  // the stage's output map (geometry of the chain)
-    if (nd.pool >= 0) {                          // ... summed over its pixels in the launch (1i): the step's outputs are the POOLED tensor's forms
-        out_t = ND[nd.pool].out;
-        if (T[out_t].forms.empty()) add_form(T[out_t], FORM_I32, 0, 0);
-    }
-    select_outputs(net, out_t, &st.out, extra);
+    const Tensor& o = T[ND[nd.fused_add].out];   // the stage's output map (geometry of the chain)
+    select_outputs(net, pooled_output(net, nd, ND[nd.fused_add].out), &st.out, extra);
     const double px = (double)o.H * o.W, opx = nd.pool >= 0 ? 1.0 : px;
     st.bytes_per_img = (tail ? px * (x.Cs + T[st.src2_t].Cs) : px * x.Cs * (ds ? 1 : 4)) + out_bytes(st, o, opx);   // the stage input, once (tail: the shortcut's pixels + mid2)
     // per block: body.0's and body.2's int8 outputs (the TAIL join has none), the join, the next block's int8 input (last block: the output forms)
@@ -2086,14 +2058,14 @@ static int emit_irchain(f8_net* net, int i, Step& st, std::vector<int>* extra) {
     return F8_OK;
 }
 
-// fused inverted residual: node i is the project conv
+// fused inverted residual: node i is the project conv.  B_IR: around a depthwise 3x3 (f8_ir.hip); B_IRK: around a 5x5 / 7x7 (f8_irk.hip)
 static int emit_ir(f8_net* net, int i, Step& st, std::vector<int>* extra) {
     auto& T = net->tensors; auto& ND = net->nodes;
     const Node& nd = ND[i];
     const Block& r = nd.blk;
     const Node& na = ND[r.b0]; const Node& nb = ND[r.b2];
     const Tensor& x = T[na.a];
-    st.kind = S_IR;
+    st.kind = r.kind == B_IRK ? S_IRK : S_IR;
     if (const int rc = conv_input_i8(net, na, &st.src_t, &st.src_f)) return rc;
     pack_block(net, r, false, st);
     st.relu0 = nd.cd.relu;
@@ -2107,95 +2079,38 @@ static int emit_ir(f8_net* net, int i, Step& st, std::vector<int>* extra) {
     const double px = (double)x.H * x.W, pxo = (double)o.H * o.W;
     st.valu_per_img = 3.0 * (px * na.cd.cout + pxo * nb.cd.cout) + (st.res_t >= 0 ? 2.0 * pxo * o.C : 0.0) + 3.0 * pxo * o.Cs * out_forms8(st);
     st.bytes_per_img = px * x.Cs + (st.res_t >= 0 ? px * x.Cs * 4 : 0) + out_bytes(st, o, pxo);
-    char kb[200];
-    snprintf(kb, sizeof kb, "fused_ir_s%d_%s:", nb.cd.stride, r.G > 1 ? ("G" + std::to_string(r.G)).c_str() : ("R" + std::to_string(r.R)).c_str());
-    st.name = kb + block_names(net, r);
+    const std::string tile = r.G > 1 ? "G" + std::to_string(r.G) : "R" + std::to_string(r.R);
+    st.name = (st.kind == S_IRK ? "fused_irk" + std::to_string(nb.cd.kernel) : std::string("fused_ir")) + "_s" + std::to_string(nb.cd.stride) + "_" + tile + ":" + block_names(net, r);
     return F8_OK;
 }
 
-// fused inverted residual around a depthwise 5x5 / 7x7: node i is the project conv
-static int emit_irk(f8_net* net, int i, Step& st, std::vector<int>* extra) {
-    auto& T = net->tensors; auto& ND = net->nodes;
-    Node& nd = ND[i];
-    const Block& r = nd.blk;
-    Node& na = ND[r.b0]; Node& nb = ND[r.b2];
-    const Tensor& x = T[na.a];
-    st.kind = S_IRK;
-    if (const int rc = conv_input_i8(net, na, &st.src_t, &st.src_f)) return rc;
-    pack_conv_weights(net, na);
-    pack_dwk_weights(net, nb);
-    pack_conv_weights(net, nd);
-    for (const Node* n : {&na, &nb, &nd}) { st.ops_per_img += conv_ops(net, *n); st.bytes_const += weight_bytes(net, *n); }
-    st.relu0 = nd.cd.relu;
-    const int out_t = join_output(net, nd, st);
-    if (nd.fused_add >= 0) {
-        st.res_t = na.a; st.res_f = find_form(x, FORM_I32, 0, 0);
-        join_shifts(T[nd.out].fl - x.fl, &st.acc_shl, &st.res_shl);
-    }
-    select_outputs(net, out_t, &st.out, extra);
-    const Tensor& o = T[out_t];
-    const double px = (double)x.H * x.W, pxo = (double)o.H * o.W;
-    st.valu_per_img = 3.0 * (px * na.cd.cout + pxo * nb.cd.cout) + (st.res_t >= 0 ? 2.0 * pxo * o.C : 0.0) + 3.0 * pxo * o.Cs * out_forms8(st);
-    st.bytes_per_img = px * x.Cs + (st.res_t >= 0 ? px * x.Cs * 4 : 0) + out_bytes(st, o, pxo);
-    char kb[200];
-    snprintf(kb, sizeof kb, "fused_irk%d_s%d_%s:", nb.cd.kernel, nb.cd.stride, r.G > 1 ? ("G" + std::to_string(r.G)).c_str() : ("R" + std::to_string(r.R)).c_str());
-    st.name = kb + block_names(net, r);
-    return F8_OK;
-}
-
-// depthwise-separable block: node i is the 1x1 conv
+// depthwise-separable block: node i is the 1x1 conv.  On f8_dws.hip, or (Block::I7, 1k) on a 7 x 7 output map on f8_dws7.hip, with the average pool
+// behind it where the plan folds it in
 static int emit_dws(f8_net* net, int i, Step& st, std::vector<int>* extra) {
     auto& T = net->tensors; auto& ND = net->nodes;
     Node& nd = ND[i];
     const Block& r = nd.blk;
     Node& nb = ND[r.b0];
     const Tensor& x = T[nb.a];
-    st.kind = S_DWS;
+    const bool d7 = r.I7 > 0, pool = nd.pool >= 0;      // (pool: only 1k's blocks)
+    st.kind = d7 ? S_DWS7 : S_DWS;
     if (const int rc = conv_input_i8(net, nb, &st.src_t, &st.src_f)) return rc;
     pack_dw_weights(net, nb);
     pack_conv_weights(net, nd);
     pack_frag_weights(net, nd);
     st.relu0 = nd.cd.relu;
-    select_outputs(net, nd.out, &st.out, extra);
-    if (st.out.f32 >= 0 || st.out.f8[0] < 0) return fail(F8_ERR_UNSUPPORTED, "finalize: the depthwise-separable launch writes int8 forms only");
-    const Tensor& o = T[nd.out];
-    const double px = (double)x.H * x.W, pxo = (double)o.H * o.W;
-    st.ops_per_img = conv_ops(net, nb) + conv_ops(net, nd);
-    st.valu_per_img = 3.0 * pxo * (nb.cd.cout + o.Cs * out_forms8(st));      // both requantisations
-    st.bytes_per_img = px * x.Cs + out_bytes(st, o, pxo);
-    st.bytes_const = weight_bytes(net, nb) + weight_bytes(net, nd);
-    st.name = "fused_dws:" + block_names(net, r);
-    return F8_OK;
-}
-
-// ... on a 7 x 7 output map (1k), with the average pool behind it where the plan folds it in: the step's outputs are then the POOLED tensor's forms
-static int emit_dws7(f8_net* net, int i, Step& st, std::vector<int>* extra) {
-    auto& T = net->tensors; auto& ND = net->nodes;
-    Node& nd = ND[i];
-    const Block& r = nd.blk;
-    Node& nb = ND[r.b0];
-    const Tensor& x = T[nb.a];
-    st.kind = S_DWS7;
-    if (const int rc = conv_input_i8(net, nb, &st.src_t, &st.src_f)) return rc;
-    pack_dw_weights(net, nb);
-    pack_conv_weights(net, nd);
-    pack_frag_weights(net, nd);
-    st.relu0 = nd.cd.relu;
-    int out_t = nd.out;
-    if (nd.pool >= 0) {
-        out_t = ND[nd.pool].out;
-        if (T[out_t].forms.empty()) add_form(T[out_t], FORM_I32, 0, 0);
-    }
+    const int out_t = pooled_output(net, nd, nd.out);
     select_outputs(net, out_t, &st.out, extra);
-    if (nd.pool < 0 && (st.out.f32 >= 0 || st.out.f8[0] < 0)) return fail(F8_ERR_UNSUPPORTED, "finalize: the depthwise-separable launch writes int8 forms of the block output only");
+    if (!pool && (st.out.f32 >= 0 || st.out.f8[0] < 0)) return fail(F8_ERR_UNSUPPORTED, "finalize: the depthwise-separable launch writes int8 forms of the block output only");
     const Tensor& o = T[out_t]; const Tensor& y = T[nd.out];
-    const double px = (double)x.H * x.W, pxo = (double)y.H * y.W, outpix = nd.pool >= 0 ? 1.0 : pxo;
+    const double px = (double)x.H * x.W, pxo = (double)y.H * y.W, outpix = pool ? 1.0 : pxo;
     st.ops_per_img = conv_ops(net, nb) + conv_ops(net, nd);
-    // the depthwise requantisation, one v_dot4 per four taps (a VALU depthwise conv, as emit_conv counts it), the pool's adds, the output forms
-    st.valu_per_img = 3.0 * pxo * nb.cd.cout + 9.0 * pxo * nb.cd.cout / 4.0 + (nd.pool >= 0 ? pxo * y.C : 0.0) + 3.0 * outpix * o.Cs * out_forms8(st);
+    if (!d7) st.valu_per_img = 3.0 * pxo * (nb.cd.cout + o.Cs * out_forms8(st));      // both requantisations
+    // f8_dws7.hip: the depthwise requantisation, one v_dot4 per four taps (a VALU depthwise conv, as emit_conv counts it), the pool's adds, the output forms
+    else st.valu_per_img = 3.0 * pxo * nb.cd.cout + 9.0 * pxo * nb.cd.cout / 4.0 + (pool ? pxo * y.C : 0.0) + 3.0 * outpix * o.Cs * out_forms8(st);
     st.bytes_per_img = px * x.Cs + out_bytes(st, o, outpix);
     st.bytes_const = weight_bytes(net, nb) + weight_bytes(net, nd);
-    st.name = "fused_dws7:" + block_names(net, r) + (nd.pool >= 0 ? "+" + tname(net, out_t) : "");
+    st.name = (d7 ? "fused_dws7:" : "fused_dws:") + block_names(net, r) + (pool ? "+" + tname(net, out_t) : "");
     return F8_OK;
 }
 
@@ -2269,10 +2184,9 @@ static int emit_conv(f8_net* net, int i, int max_batch, Step& st, std::vector<in
         if (!nd.stem && d.groups == 1 && d.kernel == 3 && d.stride == 1 && d.pad == 1 && nd.ck == d.cin && opt.patch3x3 &&
             !conv3x3_patch_config(d.cin, s.H, s.W, nd.coutP, &nd.p3_R, &nd.p3_imgs, &nd.p3_bn)) nd.p3_R = 0;
     }
-    int out_t = join_output(net, nd, st);
+    const int join_t = join_output(net, nd, st);
     if (nd.fused_add >= 0) {
-        const Node& ad = ND[nd.fused_add];
-        const int other = (ad.a == nd.out) ? ad.b : ad.a;
+        const int other = join_other(net, nd);
         if (nd.dual >= 0) {
             if (const int rc = conv_input_i8(net, ND[nd.dual], &st.src2_t, &st.src2_f)) return rc;
             pack_conv_weights(net, ND[nd.dual]);
@@ -2281,10 +2195,7 @@ static int emit_conv(f8_net* net, int i, int max_batch, Step& st, std::vector<in
         }
         join_shifts(T[nd.out].fl - T[other].fl, &st.acc_shl, &st.res_shl);     // > 0: the residual shifts left
     }
-    if (nd.pool >= 0) {                          // ... and the average pool: the step's outputs are the POOLED tensor's forms
-        out_t = ND[nd.pool].out;
-        if (T[out_t].forms.empty()) add_form(T[out_t], FORM_I32, 0, 0);
-    }
+    const int out_t = pooled_output(net, nd, join_t);      // (... and the average pool, 1i)
     const Tensor& o = T[out_t];
     if (o.dense_out) { st.dense = true; st.out.t = out_t; }
     else select_outputs(net, out_t, &st.out, extra);
@@ -2344,9 +2255,8 @@ static int emit_conv_family(f8_net* net, int i, int max_batch, Step& st, std::ve
         case B_HEAD2: return emit_head2(net, i, st, extra);
         case B_BOTTLENECK: case B_OPENING: return emit_fused(net, i, st, extra);
         case B_P12: return emit_p12(net, i, st, extra);
-        case B_IR: return emit_ir(net, i, st, extra);
-        case B_IRK: return emit_irk(net, i, st, extra);
-        case B_DWS: return nd.blk.I7 > 0 ? emit_dws7(net, i, st, extra) : emit_dws(net, i, st, extra);
+        case B_IR: case B_IRK: return emit_ir(net, i, st, extra);
+        case B_DWS: return emit_dws(net, i, st, extra);
         default:
             if (nd.grouped && gconv_kernel_applies(net->opt, nd.cd)) return emit_gconv(net, i, st, extra);
             return emit_conv(net, i, max_batch, st, extra);
@@ -2616,6 +2526,41 @@ static int bind_step(f8_net* net, Step& st) {
     const bool res = st.res_t >= 0, out32 = st.out.f32 >= 0;
     const int rq_int = !net->opt.requant_float;
     const Options& opt = net->opt;
+    // What IRArgs and IRKArgs name alike (block hosted by nd: expand na -> depthwise nb -> project nd; map x -> oT): weights, geometry, formats, join, divisors
+    auto bind_ir_common = [&](auto& a, const Node& na, const Node& nb, const Tensor& x, const Tensor& oT) {
+        const Block& r = nd.blk;
+        a.w0 = W8(na.w_off); a.b0 = B32(na.b_off);
+        a.wd4 = W8(nb.rc_off); a.bd4 = B32(nb.cc_off);           // the depthwise conv's dot4 image; bias + 128 * sum(w) for unsigned inputs
+        a.w4 = W8(nd.w_off); a.b4 = B32(nd.b_off);
+        a.H = x.H; a.W = x.W; a.Ho = oT.H; a.Wo = oT.W; a.stride = nb.cd.stride; a.R = r.R; a.G = r.G; a.E32 = na.coutP;
+        fmt(nb, &a.n1, &a.lo1, &a.hi1, &a.xor1);
+        fmt(nd, &a.n2, &a.lo2, &a.hi2, &a.xor2);
+        a.relu_a = na.cd.relu; a.relu_b = nb.cd.relu; a.relu0 = st.relu0;
+        a.acc_shl = st.acc_shl; a.res_shl = st.res_shl; a.relu1 = st.relu1;
+        make_magic((uint32_t)x.W, &a.mW, &a.s1W, &a.s2W);
+        make_magic((uint32_t)(x.H * x.W), &a.mHW, &a.s1HW, &a.s2HW);
+        make_magic((uint32_t)oT.W, &a.mWo, &a.s1Wo, &a.s2Wo);
+        make_magic((uint32_t)(r.R * oT.W), &a.mRWo, &a.s1RWo, &a.s2RWo);
+        out_formats(a.q);
+    };
+    // ... DwsArgs and Dws7Args (depthwise nb -> 1x1 nd over block input x); the depthwise weights are each case's own image
+    auto bind_dws_common = [&](auto& a, Node& nb, const Tensor& x) {
+        a.w1 = W8(nd.wf_off); a.b1 = B32(nd.b_off);
+        a.H = x.H; a.W = x.W; a.Cin = x.Cs; a.Cout = nd.coutP; a.stride = nb.cd.stride;
+        a.in_signed = nb.cd.input_signed;
+        fmt(nd, &a.n1, &a.lo1, &a.hi1, &a.xor1);
+        a.relu0 = st.relu0;
+        a.acc_ok = conv_acc_bounded(nb) && conv_acc_bounded(nd); a.rq_int = rq_int;
+        out_formats(a.q);
+    };
+    // ... and one block of a BasicBlock chain, cluster launch or not, as far as it has a first conv (c1 -> c2, the join hosted by hk): not the opening block's join alone
+    auto bind_basic_block = [&](BChainBlk& B, const Node& hk, const Node& c1, const Node& c2) {
+        B.wa = W8(c1.wf_off); B.wb = W8(c2.wf_off);
+        B.ba = B32(c1.b_off); B.bb = B32(c2.b_off);
+        fmt(c1, &B.nq, &B.loq, &B.hiq, &B.xorq);
+        fmt(c2, &B.n1, &B.lo1, &B.hi1, &B.xor1);
+        B.relu_a = c1.cd.relu; B.relu1 = ND[hk.fused_add].relu;
+    };
     char kb[192] = "";
     switch (st.kind) {
         case S_INPUT: {                                   // (its arguments are the run's: run_step)
@@ -2806,23 +2751,20 @@ static int bind_step(f8_net* net, Step& st) {
             a.nblk = (int)ch.size();
             for (int k = 0; k < a.nblk; ++k) {
                 const Node& hk = ND[ch[k]];
-                const Block& r = ND[ch[k]].blk;
+                const Block& r = hk.blk;
                 const Node& c2 = ND[r.b2];
                 BChainBlk& B = a.blk[k];
-                B.wb = W8(c2.wf_off); B.bb = B32(c2.b_off);
-                fmt(c2, &B.n1, &B.lo1, &B.hi1, &B.xor1);
-                B.relu1 = ND[hk.fused_add].relu;
                 if (r.sc >= 0) {                                // the opening block's join: (body.2 << acc_shl) + (shortcut << res_shl)
+                    B.wb = W8(c2.wf_off); B.bb = B32(c2.b_off);
+                    fmt(c2, &B.n1, &B.lo1, &B.hi1, &B.xor1);
+                    B.relu1 = ND[hk.fused_add].relu;
                     a.tail = 1; a.wsc = W8(hk.wf_off); a.bsc = B32(hk.b_off);
                     B.relu_a = ND[T[c2.a].prod].cd.relu;        // (body.0's ReLU: mid0's format)
                     join_shifts(T[c2.out].fl - T[hk.out].fl, &B.acc_shl, &B.res_shl);
                     continue;
                 }
-                Node& c1 = ND[r.b0];
-                B.wa = W8(c1.wf_off); B.ba = B32(c1.b_off);
-                fmt(c1, &B.nq, &B.loq, &B.hiq, &B.xorq);
-                B.relu_a = c1.cd.relu;
-                join_shifts(T[c2.out].fl - T[c1.a].fl, &B.acc_shl, &B.res_shl);
+                bind_basic_block(B, hk, ND[r.b0], c2);
+                join_shifts(T[c2.out].fl - T[ND[r.b0].a].fl, &B.acc_shl, &B.res_shl);
             }
             a.pool = nd.pool >= 0 ? 1 : 0;
             const Tensor& x = T[ND[nd.fused_add].out];
@@ -2839,15 +2781,11 @@ static int bind_step(f8_net* net, Step& st) {
             const bool ds = ND[ch[0]].blk.sc >= 0;
             for (int k = 0; k < a.nblk; ++k) {
                 const Node& hk = ND[ch[k]];
-                const Block& r = ND[ch[k]].blk;
+                const Block& r = hk.blk;
                 const bool hds = r.sc >= 0;                     // opening block: hk = its shortcut conv
                 Node& c1 = ND[r.b0]; const Node& c2 = ND[r.b2];
                 BChainBlk& B = a.blk[k];
-                B.wa = W8(c1.wf_off); B.wb = W8(c2.wf_off);
-                B.ba = B32(c1.b_off); B.bb = B32(c2.b_off);
-                fmt(c1, &B.nq, &B.loq, &B.hiq, &B.xorq);
-                fmt(c2, &B.n1, &B.lo1, &B.hi1, &B.xor1);
-                B.relu_a = c1.cd.relu; B.relu1 = ND[hk.fused_add].relu;
+                bind_basic_block(B, hk, c1, c2);
                 if (k == 0) { a.acc_ok = 1; a.rq_int = rq_int; a.stream_ok = (hds || stream_bounded(net, c1.a)) ? 1 : 0; }   // identity first block: the stream it reads
                 a.acc_ok = a.acc_ok && conv_acc_bounded(c1);
                 a.stream_ok = a.stream_ok && stream_bounded(net, ND[hk.fused_add].out);
@@ -2864,53 +2802,28 @@ static int bind_step(f8_net* net, Step& st) {
             st.args = a; break;
         }
         case S_IR: {
-            const Block& r = nd.blk;
-            Node& na = ND[r.b0]; Node& nb = ND[r.b2];
+            Node& na = ND[nd.blk.b0]; Node& nb = ND[nd.blk.b2];
             const Tensor& x = T[st.src_t];
             const Tensor& oT = T[nd.out];
             IRArgs a{};
-            a.w0 = W8(na.w_off); a.b0 = B32(na.b_off);
-            a.wd4 = W8(nb.rc_off); a.bd4 = B32(nb.cc_off);
-            a.w4 = W8(nd.w_off); a.b4 = B32(nd.b_off);
-            a.H = x.H; a.W = x.W; a.Ho = oT.H; a.Wo = oT.W; a.stride = nb.cd.stride; a.R = r.R; a.G = r.G;
-            a.tiles_per_img = oT.H / r.R; a.E32 = na.coutP;
-            fmt(nb, &a.n1, &a.lo1, &a.hi1, &a.xor1);
-            fmt(nd, &a.n2, &a.lo2, &a.hi2, &a.xor2);
-            a.relu_a = na.cd.relu; a.relu_b = nb.cd.relu; a.relu0 = st.relu0;
+            bind_ir_common(a, na, nb, x, oT);
+            a.tiles_per_img = oT.H / a.R;
             a.acc_ok = conv_acc_bounded(na) && conv_acc_bounded(nb); a.rq_int = rq_int;
-            a.acc_shl = st.acc_shl; a.res_shl = st.res_shl; a.relu1 = st.relu1;
-            make_magic((uint32_t)x.W, &a.mW, &a.s1W, &a.s2W);
-            make_magic((uint32_t)(x.H * x.W), &a.mHW, &a.s1HW, &a.s2HW);
-            make_magic((uint32_t)oT.W, &a.mWo, &a.s1Wo, &a.s2Wo);
-            make_magic((uint32_t)(r.R * oT.W), &a.mRWo, &a.s1RWo, &a.s2RWo);
             fused_ir_kernel_name(kb, sizeof kb, x.Cs, nd.coutP, st.inst = fused_ir_inst(a, nd.coutP));
-            out_formats(a.q); st.args = a; break;
+            st.args = a; break;
         }
         case S_IRK: {
-            const Block& r = nd.blk;
-            Node& na = ND[r.b0]; Node& nb = ND[r.b2];
             const Tensor& x = T[st.src_t];
             const Tensor& oT = T[nd.out];
             IRKArgs a{};
-            a.w0 = W8(na.w_off); a.b0 = B32(na.b_off);
-            a.wd4 = W8(nb.rc_off); a.bd4 = B32(nb.cc_off);         // pack_dwk_weights' dot4 image; bias + 128 * sum(w) for unsigned inputs
-            a.w4 = W8(nd.w_off); a.b4 = B32(nd.b_off);
-            a.K = nb.cd.kernel; a.cin = x.Cs; a.cout = nd.coutP;
-            a.H = x.H; a.W = x.W; a.Ho = oT.H; a.Wo = oT.W; a.stride = nb.cd.stride; a.R = r.R; a.G = r.G;
-            a.tiles_per_img = (oT.H + r.R - 1) / r.R; a.E32 = na.coutP;
+            bind_ir_common(a, ND[nd.blk.b0], ND[nd.blk.b2], x, oT);      // (wd4: pack_dwk_weights' dot4 image)
+            a.K = ND[nd.blk.b2].cd.kernel; a.cin = x.Cs; a.cout = nd.coutP;
+            a.tiles_per_img = (oT.H + a.R - 1) / a.R;
             a.QS = (oT.W + 3) / 4;
-            fmt(nb, &a.n1, &a.lo1, &a.hi1, &a.xor1);
-            fmt(nd, &a.n2, &a.lo2, &a.hi2, &a.xor2);
-            a.relu_a = na.cd.relu; a.relu_b = nb.cd.relu; a.relu0 = st.relu0;
-            a.acc_shl = st.acc_shl; a.res_shl = st.res_shl; a.relu1 = st.relu1;
-            make_magic((uint32_t)x.W, &a.mW, &a.s1W, &a.s2W);
-            make_magic((uint32_t)(x.H * x.W), &a.mHW, &a.s1HW, &a.s2HW);
-            make_magic((uint32_t)oT.W, &a.mWo, &a.s1Wo, &a.s2Wo);
-            make_magic((uint32_t)(r.R * oT.W), &a.mRWo, &a.s1RWo, &a.s2RWo);
             make_magic((uint32_t)a.QS, &a.mQS, &a.s1QS, &a.s2QS);
-            make_magic((uint32_t)(r.R * a.QS), &a.mRQS, &a.s1RQS, &a.s2RQS);
+            make_magic((uint32_t)(a.R * a.QS), &a.mRQS, &a.s1RQS, &a.s2RQS);
             irk_kernel_name(kb, sizeof kb, a.K, a.cout, st.inst = irk_inst(a));      // integer requantisation whatever requant_float says (as f8_dwk.hip)
-            out_formats(a.q); st.args = a; break;
+            st.args = a; break;
         }
         case S_IRCHAIN: {
             const std::vector<int>& ch = nd.chain;
@@ -2948,33 +2861,21 @@ static int bind_step(f8_net* net, Step& st) {
         }
         case S_DWS: {
             Node& nb = ND[nd.blk.b0];
-            const Tensor& x = T[st.src_t];
             const Tensor& oT = T[nd.out];
             DwsArgs a{};
-            a.wd = W8(nb.w_off); a.bd = B32(nb.cc_off);           // bias + 128 * sum(w) for unsigned inputs
-            a.w1 = W8(nd.wf_off); a.b1 = B32(nd.b_off);
-            a.H = x.H; a.W = x.W; a.P = oT.H; a.Q = oT.W; a.Cin = x.Cs; a.Cout = nd.coutP; a.stride = nb.cd.stride; a.R = nd.blk.R;
-            a.in_signed = nb.cd.input_signed;
-            fmt(nd, &a.n1, &a.lo1, &a.hi1, &a.xor1);
-            a.relu0 = st.relu0;
-            a.acc_ok = conv_acc_bounded(nb) && conv_acc_bounded(nd); a.rq_int = rq_int;
-            out_formats(a.q);
+            a.wd = W8(nb.w_off); a.bd = B32(nb.cc_off);           // the tap-major image; bias + 128 * sum(w) for unsigned inputs
+            bind_dws_common(a, nb, T[st.src_t]);
+            a.P = oT.H; a.Q = oT.W; a.R = nd.blk.R;
             dws_kernel_name(kb, sizeof kb, a, st.inst = dws_inst(a, nq));
             st.args = a; break;
         }
         case S_DWS7: {
             Node& nb = ND[nd.blk.b0];
-            const Tensor& x = T[st.src_t];
             Dws7Args a{};
             a.wd4 = W8(nb.rc_off); a.bd4 = B32(nb.cc_off);        // the dot4 image; bias + 128 * sum(w) for unsigned inputs
-            a.w1 = W8(nd.wf_off); a.b1 = B32(nd.b_off);
-            a.H = x.H; a.W = x.W; a.Cin = x.Cs; a.Cout = nd.coutP; a.stride = nb.cd.stride; a.I = nd.blk.I7;
-            a.in_signed = nb.cd.input_signed;
-            fmt(nd, &a.n1, &a.lo1, &a.hi1, &a.xor1);
-            a.relu0 = st.relu0;
+            bind_dws_common(a, nb, T[st.src_t]);
+            a.I = nd.blk.I7;
             a.pool = nd.pool >= 0 ? 1 : 0;
-            a.acc_ok = conv_acc_bounded(nb) && conv_acc_bounded(nd); a.rq_int = rq_int;
-            out_formats(a.q);
             dws7_kernel_name(kb, sizeof kb, a, st.inst = dws7_inst(a, nq));
             st.args = a; break;
         }
@@ -3277,6 +3178,12 @@ static int run_step(const f8_net* net, const RunIO& io, const Step& st, int n0, 
         if (st.out.f32 >= 0) *out32 = (int32_t*)fp(o.forms[st.out.f32]);
         for (int k = 0; k < 2; ++k) if (st.out.f8[k] >= 0) q[k].ptr = (int8_t*)fp(o.forms[st.out.f8[k]]);
     };
+    // what a run adds to IRArgs, IRKArgs and IRChainArgs alike: the int8 block input, its int32 form where the (first) block joins, the output forms
+    auto ir_io = [&](auto& a) {
+        a.x8 = (const int8_t*)fp(T[st.src_t].forms[st.src_f]); a.N = N;
+        if (st.res_t >= 0) a.xr = (const int32_t*)fp(T[st.res_t].forms[st.res_f]);
+        fill_out(&a.out32, a.q);
+    };
     char* const chain = net->d_chain ? net->d_chain + (size_t)part * net->chain_stride : nullptr;
     const uint32_t* chain_err = chain ? (const uint32_t*)chain + kChainErrWord : nullptr;
     auto chain_scratch = [&](ChainSync& cs) {
@@ -3380,31 +3287,9 @@ static int run_step(const f8_net* net, const RunIO& io, const Step& st, int n0, 
             e = launch_bchain(a, st.inst, st.C, st.H, st.W, s);
             break;
         }
-        case S_IR: {
-            const Tensor& x = T[st.src_t];
-            IRArgs a = std::get<IRArgs>(st.args);
-            a.x8 = (const int8_t*)fp(x.forms[st.src_f]); a.N = N;
-            if (st.res_t >= 0) a.xr = (const int32_t*)fp(T[st.res_t].forms[st.res_f]);
-            fill_out(&a.out32, a.q);
-            e = launch_fused_ir(a, x.Cs, nd.coutP, st.inst, s);
-            break;
-        }
-        case S_IRK: {
-            IRKArgs a = std::get<IRKArgs>(st.args);
-            a.x8 = (const int8_t*)fp(T[st.src_t].forms[st.src_f]); a.N = N;
-            if (st.res_t >= 0) a.xr = (const int32_t*)fp(T[st.res_t].forms[st.res_f]);
-            fill_out(&a.out32, a.q);
-            e = launch_fused_irk(a, st.inst, s);
-            break;
-        }
-        case S_IRCHAIN: {
-            IRChainArgs a = std::get<IRChainArgs>(st.args);
-            a.x8 = (const int8_t*)fp(T[st.src_t].forms[st.src_f]); a.N = N;
-            if (st.res_t >= 0) a.xr = (const int32_t*)fp(T[st.res_t].forms[st.res_f]);
-            fill_out(&a.out32, a.q);
-            e = launch_irchain(a, st.inst, s);
-            break;
-        }
+        case S_IR: { IRArgs a = std::get<IRArgs>(st.args); ir_io(a); e = launch_fused_ir(a, T[st.src_t].Cs, nd.coutP, st.inst, s); break; }
+        case S_IRK: { IRKArgs a = std::get<IRKArgs>(st.args); ir_io(a); e = launch_fused_irk(a, st.inst, s); break; }
+        case S_IRCHAIN: { IRChainArgs a = std::get<IRChainArgs>(st.args); ir_io(a); e = launch_irchain(a, st.inst, s); break; }
         case S_DWS: {
             DwsArgs a = std::get<DwsArgs>(st.args);
             a.x = (const int8_t*)fp(T[st.src_t].forms[st.src_f]); a.N = N;

@@ -70,20 +70,21 @@ def test_64_chains_the_8x8_pair(mbv2):
     assert _chains(net) == ['ir_chain_x2:stage_2_layer_1+stage_2_layer_2', 'ir_chain_x6:' + '+'.join(CHAIN14), 'ir_chain_x3:' + '+'.join(CHAIN7)]
 
 
-def _graph(n_blocks, second_reader=None, output_at=None):
-    """A pre conv, then n_blocks residual inverted residuals (32 channels, E 96) on 6x6; second_reader = index of a block whose output a 1x1
-    also reads; output_at = index of the block whose output is the net output (the blocks after it are built too: nothing reads their result)."""
+def _graph(n_blocks, second_reader=None, output_at=None, hw=6, stride2_at=None):
+    """A pre conv, then n_blocks residual inverted residuals (32 channels, E 96) on hw x hw; second_reader = index of a block whose output a 1x1
+    also reads; output_at = index of the block whose output is the net output (the blocks after it are built too: nothing reads their result);
+    stride2_at = index of a block whose depthwise conv has stride 2 (and which therefore has no join)."""
     rng = np.random.default_rng(0)
     w = lambda *s: rng.integers(-20, 20, s).astype(np.int32)
     net = F8Net()
-    t = net.input(32, 6, 6, 5)
+    t = net.input(32, hw, hw, 5)
     t = net.conv(t, w(32, 32, 1, 1), None, stride=1, pad=0, groups=1, weight_fl=6, input_fl=5, input_signed=True, quant_input=True, relu=False)
     outs = []
     for i in range(n_blocks):
         e = net.conv(t, w(96, 32, 1, 1), None, stride=1, pad=0, groups=1, weight_fl=6, input_fl=4, input_signed=True, quant_input=True, relu=True)
-        d = net.conv(e, w(96, 1, 3, 3), None, stride=1, pad=1, groups=96, weight_fl=6, input_fl=6, input_signed=False, quant_input=True, relu=True)
+        d = net.conv(e, w(96, 1, 3, 3), None, stride=2 if i == stride2_at else 1, pad=1, groups=96, weight_fl=6, input_fl=6, input_signed=False, quant_input=True, relu=True)
         p = net.conv(d, w(32, 96, 1, 1), None, stride=1, pad=0, groups=1, weight_fl=6, input_fl=5, input_signed=False, quant_input=True, relu=False)
-        t = net.add(p, t)
+        t = p if i == stride2_at else net.add(p, t)
         outs.append(t)
     last = outs[-1]
     if second_reader is not None:
@@ -98,6 +99,13 @@ def test_graph_cut_at_a_second_reader():
     assert [c.split(':')[0] for c in _chains(_graph(5))] == ['ir_chain_x5']
     assert [c.split(':')[0] for c in _chains(_graph(5, second_reader=1))] == ['ir_chain_x2', 'ir_chain_x3']
     assert [c.split(':')[0] for c in _chains(_graph(5, second_reader=2))] == ['ir_chain_x3', 'ir_chain_x2']
+
+
+def test_a_stride_2_block_ends_the_run():
+    """The launch keeps ONE map in LDS: a stride-2 inverted residual is no block of a run — neither in its middle nor as its first —, the runs on
+    either side of it are (12x12, then 6x6)."""
+    assert [c.split(':')[0] for c in _chains(_graph(5, hw=12, stride2_at=2))] == ['ir_chain_x2', 'ir_chain_x2']
+    assert [c.split(':')[0] for c in _chains(_graph(3, hw=12, stride2_at=0))] == ['ir_chain_x2']
 
 
 def test_graph_cut_at_the_net_output():
