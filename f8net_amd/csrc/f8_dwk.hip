@@ -1,10 +1,11 @@
-// f8_dwk.hip — general depthwise convolution (gfx950): square kernels 3 / 5 / 7, stride 1 / 2, any pad up to K / 2 — everything depthwise that
-// is not the 3x3 / pad 1 of f8_kernels.hip / f8_dwmma.hip, which keeps its own kernels.  VALU; a launch of its own (S_DW, f8_net.cpp).
+// f8_dwk.hip — general depthwise convolution (gfx950): square kernels 3 / 5 / 7, stride 1 / 2, any pad up to K / 2, and the 3x3 at dilation d > 1
+// (pad up to d) — everything depthwise that is not the undilated 3x3 / pad 1 of f8_kernels.hip / f8_dwmma.hip, which keeps its own kernels.  VALU; a
+// launch of its own (S_DW, f8_net.cpp).
 //
-// Both kernels work in the stored domain of the 3x3 kernels: NHWC int8 with channel stride Cs (a multiple of 32); unsigned tensors are stored
+// All kernels work in the stored domain of the 3x3 kernels: NHWC int8 with channel stride Cs (a multiple of 32); unsigned tensors are stored
 // biased (x ^ 0x80); wrapping int32 accumulation; optional ReLU floor; up to two int8 forms (QuantOut) and / or the tiled int32 form.
 //
-//   dwconvk_kernel<SIGNED_IN>     K, stride, pad at run time; one thread = one output pixel x 4 channels; bytes extracted and multiplied one by
+//   dwconvk_kernel<SIGNED_IN>     K, stride, pad, dilation at run time; one thread = one output pixel x 4 channels; bytes extracted and multiplied one by
 //                                 one (unsigned inputs as unsigned bytes: out-of-image taps are skipped, plain bias).  Writes any form.  The
 //                                 correctness anchor, and what runs when a launch writes the int32 form or option dwk_dot4 is 0.
 //   dwconvk_dot4_kernel<K, S>     int8 forms only, on v_dot4_i32_i8.  One thread = 4 channels (one dword per tap) x DWK_PIX adjacent output pixels
@@ -17,6 +18,12 @@
 //                                 8 + 8 + 4 for 36).  Out-of-image taps are the biased zero (a real 0 for signed inputs) and 128 * sum(w) sits in
 //                                 the bias, as in dwconv3x3_dot4_kernel.  Weights: pack_dwk_weights' image (f8_net.cpp),
 //                                 [Cs / 4][K columns][G = ceil(K / 4) row groups][4 channels] dwords, byte j of a dword = row 4g + j (0 beyond K).
+//   dwconv3x3_dil_dot4_kernel     int8 forms only, 3x3 at run-time dilation d > 1, stride 1, on the same K = 3 weight image.  A dot4 reduces over the
+//                                 three rows h0, h0 + d, h0 + 2d of one input column (the fourth byte meets a zero weight).  Adjacent output pixels share
+//                                 no column under dilation, so a thread owns 4 channels x DWK_PIX output pixels q, q + d, q + 2d, q + 3d of one row — one
+//                                 residue class mod d — and walks the six columns q - pad, q - pad + d, .. q - pad + 5d once; each transposed column feeds
+//                                 up to three pixels: 18 loads, 48 v_perm_b32 and 48 dot4 for 4 x 4 output values (144 multiply-adds).  A row is cut into
+//                                 min(d, Q) residues x ceil(ceil(Q / d) / DWK_PIX) groups; pixels at or beyond Q are computed and not stored.
 #include "f8_device.h"
 #include <algorithm>
 
@@ -46,10 +53,10 @@ __global__ void __launch_bounds__(256) dwconvk_kernel(const DwArgs a) {
         const int h0 = p * a.stride - a.pad, w0 = q * a.stride - a.pad;
         const unsigned in_xor = SIGNED_IN ? 0u : 0x80808080u;   // unsigned tensors are stored biased
         for (int r = 0; r < a.k; ++r) {
-            const int h = h0 + r;
+            const int h = h0 + r * a.dil;
             if ((unsigned)h >= (unsigned)a.H) continue;
             for (int s = 0; s < a.k; ++s) {
-                const int w = w0 + s;
+                const int w = w0 + s * a.dil;
                 if ((unsigned)w >= (unsigned)a.W) continue;
                 const unsigned xv = *(const unsigned*)(a.x + (((size_t)n * a.H + h) * a.W + w) * a.Cs + c) ^ in_xor;
                 const unsigned wv = *(const unsigned*)(a.w + (size_t)(r * a.k + s) * a.Cs + c);
@@ -163,18 +170,106 @@ __global__ void __launch_bounds__(256) dwconvk_dot4_kernel(const DwArgs a) {
     }
 }
 
-// General depthwise: the v_dot4 kernel for int8-only launches (Options::dwk_dot4), else the generic one.
+// One thread = 4 channels x DWK_PIX output pixels of one row and one residue class mod dil: q = (DWK_PIX * g + j) * dil + res, j = 0 .. DWK_PIX - 1.
+__global__ void __launch_bounds__(256) dwconv3x3_dil_dot4_kernel(const DwArgs a) {
+    constexpr int PIX = DWK_PIX, NCOL = PIX + 2;     // the pixels' columns: q0 - pad + cc * dil
+    const int d = a.dil;
+    const int cgs = a.Cs >> 2;                       // 4-channel quads
+    const int DR = min(d, a.Q);                      // residue classes that hold a pixel
+    const int NG = ((a.Q + d - 1) / d + PIX - 1) / PIX;
+    const size_t total = (size_t)a.N * a.P * NG * DR * cgs;
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    const int cg = (int)(idx % cgs);
+    size_t st = idx / cgs;
+    const int res = (int)(st % DR); st /= DR;
+    const int g = (int)(st % NG); st /= NG;
+    const int p = (int)(st % a.P);
+    const int n = (int)(st / a.P);
+    const int c = cg << 2, q0 = g * PIX * d + res;
+    const unsigned padv = a.in_signed ? 0u : 0x80808080u;
+    const int h0 = p - a.pad, w0 = q0 - a.pad;
+    const unsigned* const wq = (const unsigned*)a.w + (size_t)cg * (3 * 4);          // [column][channel]: bytes = rows 0 .. 2, 0
+
+    int acc[PIX][4];
+    {
+        const v4i bv = *(const v4i*)(a.bias + c);
+#pragma unroll
+        for (int j = 0; j < PIX; ++j) { acc[j][0] = bv.x; acc[j][1] = bv.y; acc[j][2] = bv.z; acc[j][3] = bv.w; }
+    }
+    v4i wv[3];
+#pragma unroll
+    for (int s = 0; s < 3; ++s) wv[s] = *(const v4i*)(wq + s * 4);
+    const int8_t* const xn = a.x + (size_t)n * a.H * a.W * a.Cs + c;
+#pragma unroll
+    for (int cc = 0; cc < NCOL; ++cc) {
+        const int w = w0 + cc * d;
+        const bool wok = (unsigned)w < (unsigned)a.W;
+        unsigned t[3];                                // rows h0, h0 + d, h0 + 2d of this column, 4 channels each
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const int h = h0 + r * d;
+            unsigned v = padv;
+            if (wok && (unsigned)h < (unsigned)a.H) v = *(const unsigned*)(xn + ((size_t)h * a.W + w) * a.Cs);
+            t[r] = v;
+        }
+        // byte transpose: col[e] = rows 0, 1, 2 (and 2 again: slot 3 meets a zero weight) of channel e
+        const unsigned lo01 = __builtin_amdgcn_perm(t[1], t[0], 0x05010400u), hi01 = __builtin_amdgcn_perm(t[1], t[0], 0x07030602u);
+        const unsigned lo23 = __builtin_amdgcn_perm(t[2], t[2], 0x05010400u), hi23 = __builtin_amdgcn_perm(t[2], t[2], 0x07030602u);
+        const unsigned col0 = __builtin_amdgcn_perm(lo23, lo01, 0x05040100u), col1 = __builtin_amdgcn_perm(lo23, lo01, 0x07060302u);
+        const unsigned col2 = __builtin_amdgcn_perm(hi23, hi01, 0x05040100u), col3 = __builtin_amdgcn_perm(hi23, hi01, 0x07060302u);
+        // every pixel j whose window holds column cc: kernel column s = cc - j
+#pragma unroll
+        for (int j = 0; j < PIX; ++j) {
+            const int s = cc - j;
+            if (s < 0 || s >= 3) continue;
+            acc[j][0] = __builtin_amdgcn_sdot4((int)col0, wv[s].x, acc[j][0], false);
+            acc[j][1] = __builtin_amdgcn_sdot4((int)col1, wv[s].y, acc[j][1], false);
+            acc[j][2] = __builtin_amdgcn_sdot4((int)col2, wv[s].z, acc[j][2], false);
+            acc[j][3] = __builtin_amdgcn_sdot4((int)col3, wv[s].w, acc[j][3], false);
+        }
+    }
+    const int floor0 = a.relu0 ? 0 : INT32_MIN;
+#pragma unroll
+    for (int j = 0; j < PIX; ++j) {
+        const int q = q0 + j * d;
+        if (q >= a.Q) continue;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[j][e] = max(acc[j][e], floor0);
+        const size_t o = ((((size_t)n * a.P + p) * a.Q + q)) * a.Cs + c;
+#pragma unroll
+        for (int f = 0; f < 2; ++f)
+            if (a.q[f].ptr)
+                *(unsigned*)(a.q[f].ptr + o) =
+                    pack4(requant1(acc[j][0], a.q[f].n, a.q[f].lo, a.q[f].hi), requant1(acc[j][1], a.q[f].n, a.q[f].lo, a.q[f].hi),
+                          requant1(acc[j][2], a.q[f].n, a.q[f].lo, a.q[f].hi), requant1(acc[j][3], a.q[f].n, a.q[f].lo, a.q[f].hi)) ^ a.q[f].bias_xor;
+    }
+}
+
+// General depthwise: the v_dot4 kernels for int8-only launches (Options::dwk_dot4), else the generic one.  A dilated conv (3x3 only) has its dot4
+// kernel — instance 2 — at stride 1, exactly where dwconvk_dot4_kernel<3, 1> runs the undilated one.
 int dwk_inst(const DwArgs& a, bool out32, bool dot4) {
+    if (a.dil > 1) return dot4 && !out32 && a.k == 3 && a.stride == 1 ? 2 : 0;
     return dot4 && !out32 && (a.k == 3 || a.k == 5 || a.k == 7) && (a.stride == 1 || a.stride == 2) ? 1 : 0;
 }
 
 int dwk_kernel_name(char* buf, size_t cap, const DwArgs& a, int inst) {
+    if (inst == 2) return snprintf(buf, cap, "f8::dwconv3x3_dil_dot4_kernel");
     if (inst) return snprintf(buf, cap, "f8::dwconvk_dot4_kernel<%d, %d>", a.k, a.stride);
     return snprintf(buf, cap, "f8::dwconvk_kernel<%s>", a.in_signed ? "true" : "false");
 }
 
 hipError_t launch_dwk(const DwArgs& a, int inst, hipStream_t s) {
-    if (a.k < 1 || a.pad < 0 || a.pad > a.k / 2) return hipErrorInvalidValue;
+    if (a.k < 1 || a.dil < 1 || a.pad < 0 || a.pad > (a.dil > 1 ? a.dil : a.k / 2) || (a.dil > 1 && a.k != 3)) return hipErrorInvalidValue;
+    if ((inst == 2) != (a.dil > 1 && inst != 0)) return hipErrorInvalidValue;      // a dot4 instance: 2 for a dilated conv and only for one
+    if (inst == 2) {
+        if (a.out32 || !a.w4 || a.stride != 1) return hipErrorInvalidValue;
+        const int DR = std::min(a.dil, a.Q), NG = ((a.Q + a.dil - 1) / a.dil + DWK_PIX - 1) / DWK_PIX;
+        const size_t work = (size_t)a.N * a.P * NG * DR * (a.Cs >> 2);
+        DwArgs b = a; b.w = a.w4; b.bias = a.bias4;
+        hipLaunchKernelGGL(dwconv3x3_dil_dot4_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, s, b);
+        return hipGetLastError();
+    }
     if (inst) {
         if (a.out32 || !a.w4) return hipErrorInvalidValue;
         const size_t work = (size_t)a.N * a.P * ((a.Q + DWK_PIX - 1) / DWK_PIX) * (a.Cs >> 2);

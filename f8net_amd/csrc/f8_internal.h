@@ -119,10 +119,11 @@ struct ConvArgs {
     const int32_t* bias2;                  // [coutP]
     int32_t sN2, sP2, sQ2, ktot2;          // input byte strides of x2 (per image / output row / output col), its K
     void* trace;                           // tuning builds (F8_TRACE) only; nullptr otherwise
+    int32_t dil, kwd;                      // conv_igemm_kernel only: dilation (1: none) and kw * dil — its K loop steps the tap coordinates by dil and wraps the column at kwd
 };
 
 // Depthwise K x K (groups == C), NHWC int8 in, VALU.  3x3 / pad 1: the launchers of f8_kernels.hip / f8_dwmma.hip, which never read `k`;
-// every other accepted geometry (k 3 / 5 / 7, pad <= k / 2: "general depthwise"): f8_dwk.hip, with the images of pack_dwk_weights.
+// every other accepted geometry (k 3 / 5 / 7, pad <= k / 2; k 3 at dilation dil > 1, pad <= dil: "general depthwise"): f8_dwk.hip, with the images of pack_dwk_weights.
 struct DwArgs {
     const int8_t* x; const int8_t* w;      // w: [k * k][Cs] tap-major
     const int32_t* bias;                   // [Cs]
@@ -138,6 +139,7 @@ struct DwArgs {
                                            // float requantisation (requant_u8x4, f8_device.h) equals the wrapping integer one
     int32_t rq_int;                        // Options::requant_float == 0: integer requantisation only
     int32_t k;                             // kernel size; read by the general depthwise kernels only (f8_dwk.hip)
+    int32_t dil;                           // ... and the dilation (1: none; > 1 only with k == 3)
 };
 
 // Grouped 3x3 (f8_gconv.hip): cin == cout, cg = C / groups divides 32, stride 1 / 2, pad 0 / 1.  The kernel sees 32-channel slices only.
@@ -568,8 +570,8 @@ hipError_t launch_head_dws(const StemPoolArgs& a, hipStream_t s);
 int dwconv_inst(const DwArgs& a, bool out32, int nq, bool mma, bool dot4, int max_batch);
 int dwconv_kernel_name(char* buf, size_t cap, const DwArgs& a, int inst);
 hipError_t launch_dwconv(const DwArgs& a, int inst, hipStream_t s);
-// general depthwise (f8_dwk.hip): every accepted depthwise geometry but 3x3 / pad 1.  inst 1: dwconvk_dot4_kernel<k, stride> (int8 outputs only,
-// Options::dwk_dot4), 0: dwconvk_kernel<in_signed>
+// general depthwise (f8_dwk.hip): every accepted depthwise geometry but the undilated 3x3 / pad 1.  inst 1: dwconvk_dot4_kernel<k, stride> (int8 outputs only,
+// Options::dwk_dot4), 2: dwconv3x3_dil_dot4_kernel (the same, 3x3 at dilation > 1, stride 1), 0: dwconvk_kernel<in_signed>
 int dwk_inst(const DwArgs& a, bool out32, bool dot4);
 int dwk_kernel_name(char* buf, size_t cap, const DwArgs& a, int inst);
 hipError_t launch_dwk(const DwArgs& a, int inst, hipStream_t s);

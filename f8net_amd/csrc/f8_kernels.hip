@@ -239,7 +239,7 @@ __global__ void __launch_bounds__(256, BM * BN >= 128 * 128 ? (DUAL ? 2 : HAS_RE
 
     const int nk1 = a.ktot / BK;
     const int nk = nk1 + (DUAL ? a.ktot2 / BK : 0);
-    // K-step state of the NEXT stage to issue (wave-uniform): tap row/col, channel offset in the tap
+    // K-step state of the NEXT stage to issue (wave-uniform): tap row/col — in input pixels, i.e. pre-multiplied by the dilation —, channel offset in the tap
     int tr = 0, ts = 0, c0 = 0, kiss = 0;
 
     // Every thread issues exactly NLD DMA instructions per stage (waves without a slot for some
@@ -269,8 +269,8 @@ __global__ void __launch_bounds__(256, BM * BN >= 128 * 128 ? (DUAL ? 2 : HAS_RE
         ++kiss;
         c0 += BK;
         if (c0 == a.CK) {
-            c0 = 0; ++ts;
-            if (ts == a.kw) { ts = 0; ++tr; }
+            c0 = 0; ts += a.dil;
+            if (ts == a.kwd) { ts = 0; tr += a.dil; }
         }
     };
     // DUAL (two 1x1 convs: no tap state): STATELESS issue of global stage g.  The mutable captures of issue_stage end

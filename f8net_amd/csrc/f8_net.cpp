@@ -92,6 +92,7 @@ enum NodeKind { N_INPUT, N_CONV, N_ADD, N_MAXPOOL, N_AVGPOOL, N_LINEAR };
 struct Node {
     int kind; int a = -1, b = -1; int out = -1;
     f8_conv_desc cd{};                 // conv / linear (as 1x1 conv)
+    int dil = 1;                       // dilation (f8_net_conv_dilated; 1 for kernel 1).  > 1: a launch of its own on conv_igemm_kernel / f8_dwk.hip — every matcher refuses it
     std::vector<int8_t> w; std::vector<int32_t> bias;   // raw OIHW int8 + bias
     int acc_ok = -1;                   // conv_acc_bounded(), cached
     int64_t acc_max = -2;              // conv_acc_max(), cached (-2: not computed yet)
@@ -547,30 +548,41 @@ int f8_net_input(f8_net* net, int C, int H, int W, int fraclen) {
     return t;
 }
 
-static int add_conv_node(f8_net* net, int src, const f8_conv_desc& d, const int32_t* w, const int32_t* b,
+static int add_conv_node(f8_net* net, int src, const f8_conv_desc& d, int dil, const int32_t* w, const int32_t* b,
                          int kind, const char* who) {
     int rc = check_t(net, src, who);
     if (rc) return rc;
     const Tensor& s = net->tensors[src];
     if (d.cin != s.C) return fail(F8_ERR_INVALID, "%s: cin %d != source channels %d", who, d.cin, s.C);
     if (d.kernel < 1 || d.stride < 1 || d.pad < 0 || d.cout < 1) return fail(F8_ERR_INVALID, "%s: bad geometry", who);
+    if (dil < 1) return fail(F8_ERR_INVALID, "%s: dilation %d < 1 (kernel %d, stride %d, pad %d)", who, dil, d.kernel, d.stride, d.pad);
+    if (dil > 64) return fail(F8_ERR_UNSUPPORTED, "%s: dilation %d > 64 is not built (kernel %d, stride %d, pad %d)", who, dil, d.kernel, d.stride, d.pad);
+    if (d.kernel == 1) dil = 1;                   // a 1x1 has no second tap: the same conv
     // grouped convs (1 < groups < cin) are opt-in at the builder (option grouped): planned on f8_gconv.hip or as the dense expansion (emit_conv_family)
     const bool grouped = d.groups > 1 && d.groups < d.cin && net->opt.grouped >= 1;
     if (grouped) {
         if (d.cin % d.groups || d.cout % d.groups) return fail(F8_ERR_INVALID, "%s: groups %d must divide cin %d and cout %d", who, d.groups, d.cin, d.cout);
     } else if (!(d.groups == 1 || (d.groups == d.cin && d.cout == d.cin)))
         return fail(F8_ERR_UNSUPPORTED, "%s: groups must be 1 or cin (depthwise)", who);
-    if (d.groups != 1 && !grouped && !((d.kernel == 3 || d.kernel == 5 || d.kernel == 7) && d.stride <= 2 && d.pad <= d.kernel / 2))
+    if (d.groups != 1 && !grouped && dil == 1 && !((d.kernel == 3 || d.kernel == 5 || d.kernel == 7) && d.stride <= 2 && d.pad <= d.kernel / 2))
         return fail(F8_ERR_UNSUPPORTED, "%s: depthwise is built for kernel 3, 5 or 7, stride 1 or 2, pad 0 .. kernel / 2 (got kernel %d, stride %d, pad %d)",
                     who, d.kernel, d.stride, d.pad);
+    if (d.groups != 1 && !grouped && dil > 1 && !(d.kernel == 3 && d.stride <= 2 && d.pad <= dil))
+        return fail(F8_ERR_UNSUPPORTED, "%s: dilated depthwise is built for kernel 3, stride 1 or 2, pad 0 .. dilation (got kernel %d, stride %d, pad %d, dilation %d)",
+                    who, d.kernel, d.stride, d.pad, dil);
     if (d.weight_fl < 0 || d.weight_fl > 31) return fail(F8_ERR_INVALID, "%s: bad weight_fl", who);
     int n;
     rc = consumer_format(s, d, &n, who);
     if (rc) return rc;
-    const int P = (s.H + 2 * d.pad - d.kernel) / d.stride + 1, Q = (s.W + 2 * d.pad - d.kernel) / d.stride + 1;
-    if (P < 1 || Q < 1) return fail(F8_ERR_INVALID, "%s: kernel larger than padded input", who);
+    const int ext = dil * (d.kernel - 1) + 1;     // the kernel's extent on the input
+    if (s.H + 2 * d.pad < ext || s.W + 2 * d.pad < ext) {
+        if (dil == 1) return fail(F8_ERR_INVALID, "%s: kernel larger than padded input", who);
+        return fail(F8_ERR_INVALID, "%s: empty output: kernel %d at dilation %d spans %d pixels, the padded input is %d x %d (pad %d)", who, d.kernel, dil, ext,
+                    s.H + 2 * d.pad, s.W + 2 * d.pad, d.pad);
+    }
+    const int P = (s.H + 2 * d.pad - ext) / d.stride + 1, Q = (s.W + 2 * d.pad - ext) / d.stride + 1;
     if (!w) return fail(F8_ERR_INVALID, "%s: null weight", who);
-    Node nd; nd.kind = kind; nd.a = src; nd.cd = d;
+    Node nd; nd.kind = kind; nd.a = src; nd.cd = d; nd.dil = dil;
     const size_t wn = (size_t)d.cout * (d.cin / d.groups) * d.kernel * d.kernel;
     nd.w.resize(wn);
     for (size_t i = 0; i < wn; ++i) {
@@ -589,7 +601,12 @@ static int add_conv_node(f8_net* net, int src, const f8_conv_desc& d, const int3
 
 int f8_net_conv(f8_net* net, int src, const f8_conv_desc* desc, const int32_t* w, const int32_t* b) {
     if (!desc) return fail(F8_ERR_INVALID, "f8_net_conv: null desc");
-    return add_conv_node(net, src, *desc, w, b, N_CONV, "f8_net_conv");
+    return add_conv_node(net, src, *desc, 1, w, b, N_CONV, "f8_net_conv");
+}
+
+int f8_net_conv_dilated(f8_net* net, int src, const f8_conv_desc* desc, int dilation, const int32_t* w, const int32_t* b) {
+    if (!desc) return fail(F8_ERR_INVALID, "f8_net_conv_dilated: null desc");
+    return add_conv_node(net, src, *desc, dilation, w, b, N_CONV, "f8_net_conv_dilated");
 }
 
 int f8_net_linear(f8_net* net, int src, const f8_linear_desc* d, const int32_t* w, const int32_t* b) {
@@ -602,7 +619,7 @@ int f8_net_linear(f8_net* net, int src, const f8_linear_desc* d, const int32_t* 
     c.cin = d->in_features; c.cout = d->out_features; c.kernel = 1; c.stride = 1; c.pad = 0; c.groups = 1;
     c.weight_fl = d->weight_fl; c.input_fl = d->input_fl; c.input_signed = d->input_signed;
     c.quant_input = d->quant_input; c.relu = 0;
-    return add_conv_node(net, src, c, w, b, N_LINEAR, "f8_net_linear");
+    return add_conv_node(net, src, c, 1, w, b, N_LINEAR, "f8_net_linear");
 }
 
 int f8_net_add(f8_net* net, int a, int b, int relu) {
@@ -759,7 +776,7 @@ static void pack_conv_bias(f8_net* net, Node& nd, const std::vector<long long>& 
         auto classify = [&](int n_out, int n_in, std::vector<uint32_t>& masks, std::vector<uint8_t>& cls) {
             for (int p = 0; p < n_out; ++p) {
                 uint32_t mk = 0;
-                for (int r = 0; r < k; ++r) { const int h = p * d.stride - d.pad + r; if (h >= 0 && h < n_in) mk |= 1u << r; }
+                for (int r = 0; r < k; ++r) { const int h = p * d.stride - d.pad + r * nd.dil; if (h >= 0 && h < n_in) mk |= 1u << r; }
                 size_t id = 0;
                 while (id < masks.size() && masks[id] != mk) ++id;
                 if (id == masks.size()) masks.push_back(mk);
@@ -854,7 +871,7 @@ static void pack_dw_weights(f8_net* net, Node& nd) {
 // "General depthwise": every accepted depthwise conv that is not 3x3 / pad 1 (kernel 3 / 5 / 7, stride 1 / 2, pad 0 .. kernel / 2; add_conv_node).  One pass
 // of the planner fuses one — 1e3, option fuse_irk: kernel 5 / 7 with pad kernel / 2 inside an inverted residual —; every other matcher asks for kernel 3
 // and pad 1, so anywhere else it is a launch of its own on the kernels of f8_dwk.hip.
-static bool dw_general(const f8_conv_desc& d) { return d.groups != 1 && d.groups == d.cin && !(d.kernel == 3 && d.pad == 1); }
+static bool dw_general(const Node& n) { const f8_conv_desc& d = n.cd; return d.groups != 1 && d.groups == d.cin && !(d.kernel == 3 && d.pad == 1 && n.dil == 1); }
 
 // The two weight images of a general depthwise conv, at offsets of their own (the 3x3 / pad 1 images are pack_dw_weights' and stay as they are):
 //  (1) [K * K][Cs] tap-major + plain bias                        — dwconvk_kernel
@@ -956,7 +973,8 @@ static void label_conv_step(f8_net* net, Step& st, const Node& nd) {
     const f8_conv_desc& d = nd.cd;
     const bool res = st.res_t >= 0;
     const std::string key = nd.dual >= 0 ? tname(net, net->nodes[nd.dual].out) + "+" + tname(net, nd.out) : tname(net, nd.out);
-    char buf[160];
+    char buf[160], dl[16] = "";                  // d<D> behind the stride of a dilated conv
+    if (nd.dil > 1) snprintf(dl, sizeof dl, "d%d", nd.dil);
     switch (st.variant) {
         case V_FC: st.name = "linear_dense:" + key; return;
         case V_POOL: st.name = (res ? "conv1x1_res+avgpool:" : "conv1x1+avgpool:") + key; return;
@@ -965,9 +983,9 @@ static void label_conv_step(f8_net* net, Step& st, const Node& nd) {
         case V_WREG: st.name = "conv1x1s1_wreg:" + key; return;
         case V_PATCH3X3: snprintf(buf, sizeof buf, "conv3x3s1_patch_R%dx%d_bn%d%s:%s", nd.p3_R, nd.p3_imgs, nd.p3_bn, res ? "_res" : "", key.c_str()); break;
         default:
-            if (nd.depthwise) snprintf(buf, sizeof buf, "dwconv%dx%ds%d:%s", d.kernel, d.kernel, d.stride, key.c_str());
-            else if (nd.grouped) snprintf(buf, sizeof buf, "gconv%dx%ds%d_dense:%s", d.kernel, d.kernel, d.stride, key.c_str());
-            else snprintf(buf, sizeof buf, "conv%dx%ds%d_t%dx%dx%d%s%s:%s", d.kernel, d.kernel, d.stride, nd.tile.bm, nd.tile.bn,
+            if (nd.depthwise) snprintf(buf, sizeof buf, "dwconv%dx%ds%d%s:%s", d.kernel, d.kernel, d.stride, dl, key.c_str());
+            else if (nd.grouped) snprintf(buf, sizeof buf, "gconv%dx%ds%d%s_dense:%s", d.kernel, d.kernel, d.stride, dl, key.c_str());
+            else snprintf(buf, sizeof buf, "conv%dx%ds%d%s_t%dx%dx%d%s%s:%s", d.kernel, d.kernel, d.stride, dl, nd.tile.bm, nd.tile.bn,
                           nd.tile.bk, nd.stem ? "_stem" : "", res ? "_res" : (nd.dual >= 0 ? "_dual" : ""), key.c_str());
     }
     st.name = buf;
@@ -1034,13 +1052,13 @@ static Role role_in_block(const f8_net* net, int i, int* host) {
 
 // ---- The vocabulary of the matchers (passes 1 .. 1k).  What the passes really differ in — quant_input, relu, fused_add, dual, claimed() — stays
 // written out where a pass tests it.  Every tensor has a producer (f8_net_input, add_conv_node and the other builders create it with one): no pass tests for that.
-// a plain conv (groups 1) of this kernel, stride and pad
+// a plain conv (groups 1) of this kernel, stride and pad, undilated: a dilated conv joins no fused launch
 static bool plain_conv(const Node& n, int k, int s, int p) {
-    return n.kind == N_CONV && n.cd.groups == 1 && n.cd.kernel == k && n.cd.stride == s && n.cd.pad == p;
+    return n.kind == N_CONV && n.cd.groups == 1 && n.cd.kernel == k && n.dil == 1 && n.cd.stride == s && n.cd.pad == p;
 }
 // a depthwise conv (groups == cin, more than one channel; add_conv_node then insists on cout == cin) of this kernel and pad, stride 1 (stride2: or 2)
 static bool depthwise_conv(const Node& n, int k, int p, bool stride2) {
-    return n.kind == N_CONV && n.cd.groups != 1 && n.cd.groups == n.cd.cin && n.cd.kernel == k && n.cd.pad == p &&
+    return n.kind == N_CONV && n.cd.groups != 1 && n.cd.groups == n.cd.cin && n.cd.kernel == k && n.dil == 1 && n.cd.pad == p &&
            (n.cd.stride == 1 || (stride2 && n.cd.stride == 2));
 }
 // tensor t as a private intermediate: its producer node if exactly one node reads it and it is no network output, else -1
@@ -1737,7 +1755,7 @@ static void plan_tensor_forms(f8_net* net) {
                     default: in_launch = false;                  // a conv of its own; B_JOIN: the shortcut and body.4 read their int8 inputs from HBM
                 }
                 if (in_launch) break;
-                nd.stem = !nd.depthwise && !nd.grouped && nd.cd.cin <= 4 && ND[s.prod].kind == N_INPUT && nd.cd.kernel <= 8 &&
+                nd.stem = !nd.depthwise && !nd.grouped && nd.cd.cin <= 4 && ND[s.prod].kind == N_INPUT && nd.cd.kernel <= 8 && nd.dil == 1 &&
                           s.consumers.size() == 1 && !is_output(net, nd.a) && n == 0;
                 if (nd.stem) {
                     const int Q = T[nd.out].W;
@@ -1762,7 +1780,7 @@ static void plan_tensor_forms(f8_net* net) {
                 if (!o.forms.empty() && T[nd.a].consumers.size() == 1 && !is_output(net, nd.a)) {
                     // ResNet head: 7x7/2 stem conv + this pool in one launch (the conv output never leaves LDS)
                     Node& c = ND[T[nd.a].prod];
-                    if (c.kind == N_CONV && c.cd.groups == 1 && c.fused_add < 0 && ND[T[c.a].prod].kind == N_INPUT && T[c.a].consumers.size() == 1 &&
+                    if (c.kind == N_CONV && c.cd.groups == 1 && c.dil == 1 && c.fused_add < 0 && ND[T[c.a].prod].kind == N_INPUT && T[c.a].consumers.size() == 1 &&
                         !is_output(net, c.a) && (!c.cd.quant_input || T[c.a].fl == c.cd.input_fl) && opt.fuse_stem &&
                         stem_pool_supported(c.cd.cin, c.cd.cout, c.cd.kernel, c.cd.stride, c.cd.pad, nd.pk, nd.pstride, nd.ppad, o.H, o.W, opt.stem_rows, T[c.a].H, T[c.a].W)) {
                         c.sp_pool = i; nd.sp_conv = T[nd.a].prod;
@@ -1820,7 +1838,7 @@ static void pack_block(f8_net* net, const Block& r, bool frag, Step& st) {
         if (c < 0) continue;
         Node& n = net->nodes[c];
         if (!n.depthwise) pack_conv_weights(net, n);
-        else if (dw_general(n.cd)) pack_dwk_weights(net, n);      // (the 5x5 / 7x7 of a B_IRK block)
+        else if (dw_general(n)) pack_dwk_weights(net, n);      // (the 5x5 / 7x7 of a B_IRK block)
         else pack_dw_weights(net, n);
         if (frag) pack_frag_weights(net, n);
         st.ops_per_img += conv_ops(net, n); st.bytes_const += weight_bytes(net, n);
@@ -2122,6 +2140,7 @@ static Variant conv_variant(const f8_net* net, const Node& nd, const Step& st, i
     if (st.dense) return V_FC;                   // the classifier: logits straight into the caller's buffer (f8_fc.hip)
     if (nd.pool >= 0) return V_POOL;             // ... and the average pool behind the last 1x1 conv (1i)
     const bool plain = !nd.stem && d.groups == 1;
+    if (nd.dil > 1) return V_IGEMM;              // a dilated conv: conv_igemm_kernel walks its taps at any spacing, the LDS-patch / register-weight 3x3 kernels do not
     // the stride-2 3x3 of a late stage-opening block, int8 outputs only: input patch in LDS, weights straight to registers
     if (opt.s2wreg && plain && d.kernel == 3 && d.stride == 2 && d.pad == 1 && nd.fused_add < 0 && nd.dual < 0 && st.out.f32 < 0 && nd.ck == d.cin &&
         s.H == 2 * o.H && s.W == 2 * o.W && conv3x3s2_wreg_supported(nd.ck, o.H, o.W, nd.coutP)) return V_S2WREG;
@@ -2166,7 +2185,7 @@ static int emit_conv(f8_net* net, int i, int max_batch, Step& st, std::vector<in
     if (nd.stem) { st.src_t = nd.a; st.src_f = find_form(s, FORM_STEM, 0, 0); }
     else if (const int rc = conv_input_i8(net, nd, &st.src_t, &st.src_f)) return rc;
     st.relu0 = d.relu;
-    if (nd.depthwise) { if (dw_general(d)) pack_dwk_weights(net, nd); else pack_dw_weights(net, nd); }
+    if (nd.depthwise) { if (dw_general(nd)) pack_dwk_weights(net, nd); else pack_dw_weights(net, nd); }
     else {
         pack_conv_weights(net, nd);
         const int M1 = T[nd.out].H * T[nd.out].W;
@@ -2181,7 +2200,7 @@ static int emit_conv(f8_net* net, int i, int max_batch, Step& st, std::vector<in
             ConvTile t = nd.tile; t.bm = kIgemmCandBm[opt.igemm_tile - 1]; t.bn = kIgemmCandBn[opt.igemm_tile - 1];
             if (igemm_tile_admissible(nd, t)) nd.tile = t;
         }
-        if (!nd.stem && d.groups == 1 && d.kernel == 3 && d.stride == 1 && d.pad == 1 && nd.ck == d.cin && opt.patch3x3 &&
+        if (!nd.stem && d.groups == 1 && d.kernel == 3 && nd.dil == 1 && d.stride == 1 && d.pad == 1 && nd.ck == d.cin && opt.patch3x3 &&
             !conv3x3_patch_config(d.cin, s.H, s.W, nd.coutP, &nd.p3_R, &nd.p3_imgs, &nd.p3_bn)) nd.p3_R = 0;
     }
     const int join_t = join_output(net, nd, st);
@@ -2220,9 +2239,10 @@ static int emit_conv(f8_net* net, int i, int max_batch, Step& st, std::vector<in
 // the dense expansion: emit_conv's plain path over block-diagonal weights (pack_conv_weights), slower by cin / cg.  Measured on the seven grouped layers
 // of ResNeXt-50 32x4d at 128 images (profiles/gconv_r07.md): the kernel is 1.9x (128 x 56 x 56, cg 4: 51.3 against 98.7 us) to 8.1x (1024 x 14 x 14 / 2,
 // cg 32: 15.5 against 126.0 us) faster than the expansion, on every shape — none of its set is routed to the expansion.
-static bool gconv_kernel_applies(const Options& opt, const f8_conv_desc& d) {
+static bool gconv_kernel_applies(const Options& opt, const Node& n) {
+    const f8_conv_desc& d = n.cd;
     const int cg = d.cin / d.groups;
-    return opt.grouped == 1 && d.kernel == 3 && (d.stride == 1 || d.stride == 2) && d.pad <= 1 && d.cin == d.cout && cg >= 2 && cg <= 32 && 32 % cg == 0;
+    return opt.grouped == 1 && d.kernel == 3 && n.dil == 1 && (d.stride == 1 || d.stride == 2) && d.pad <= 1 && d.cin == d.cout && cg >= 2 && cg <= 32 && 32 % cg == 0;
 }
 // a grouped 3x3 on the slice-diagonal kernel: always a launch of its own, no join
 static int emit_gconv(f8_net* net, int i, Step& st, std::vector<int>* extra) {
@@ -2258,7 +2278,7 @@ static int emit_conv_family(f8_net* net, int i, int max_batch, Step& st, std::ve
         case B_IR: case B_IRK: return emit_ir(net, i, st, extra);
         case B_DWS: return emit_dws(net, i, st, extra);
         default:
-            if (nd.grouped && gconv_kernel_applies(net->opt, nd.cd)) return emit_gconv(net, i, st, extra);
+            if (nd.grouped && gconv_kernel_applies(net->opt, nd)) return emit_gconv(net, i, st, extra);
             return emit_conv(net, i, max_batch, st, extra);
     }
 }
@@ -2591,6 +2611,7 @@ static int bind_step(f8_net* net, Step& st) {
                 a.origin = -(d.pad * sT.W + d.pad) * sT.Cs; a.H = sT.H; a.W = sT.W; a.pad = d.pad; a.kw = d.kernel;
                 a.tapH = sT.W * sT.Cs; a.tapW = sT.Cs;
             }
+            a.dil = nd.stem ? 1 : nd.dil; a.kwd = a.kw * a.dil;     // (conv_igemm_kernel carries its tap coordinates pre-dilated; every other variant is undilated)
             a.relu0 = st.relu0;
             if (st.res_t >= 0 || nd.dual >= 0) { a.acc_shl = st.acc_shl; a.res_shl = st.res_shl; a.relu1 = st.relu1; }
             if (nd.dual >= 0) {
@@ -2887,9 +2908,9 @@ static int bind_step(f8_net* net, Step& st) {
             a.w4 = W8(nd.rc_off); a.bias4 = B32(nd.cc_off);
             a.H = sT.H; a.W = sT.W; a.P = oT.H; a.Q = oT.W; a.Cs = sT.Cs; a.stride = nd.cd.stride; a.pad = nd.cd.pad;
             a.in_signed = nd.cd.input_signed; a.relu0 = st.relu0; a.acc_ok = conv_acc_bounded(nd); a.rq_int = rq_int;
-            a.k = nd.cd.kernel;
+            a.k = nd.cd.kernel; a.dil = nd.dil;
             out_formats(a.q);
-            if (dw_general(nd.cd)) {                                 // f8_dwk.hip: integer requantisation (requant1) whatever requant_float says
+            if (dw_general(nd)) {                                 // f8_dwk.hip: integer requantisation (requant1) whatever requant_float says
                 st.inst = dwk_inst(a, out32, opt.dwk_dot4);
                 dwk_kernel_name(kb, sizeof kb, a, st.inst);
             } else {
@@ -3308,7 +3329,7 @@ static int run_step(const f8_net* net, const RunIO& io, const Step& st, int n0, 
             DwArgs a = std::get<DwArgs>(st.args);
             a.x = (const int8_t*)fp(T[st.src_t].forms[st.src_f]); a.N = N;
             fill_out(&a.out32, a.q);
-            e = (a.k == 3 && a.pad == 1) ? launch_dwconv(a, st.inst, s) : launch_dwk(a, st.inst, s);      // (general depthwise: f8_dwk.hip)
+            e = (a.k == 3 && a.pad == 1 && a.dil == 1) ? launch_dwconv(a, st.inst, s) : launch_dwk(a, st.inst, s);      // (general depthwise: f8_dwk.hip)
             break;
         }
         case S_GCONV: {

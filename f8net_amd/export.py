@@ -248,7 +248,7 @@ def export_int_state(spec: topology.NetSpec, float_state: dict, cfg: ExportConfi
                the tail conv takes the last master; signed (`double_side`) inputs as in the topology table
       MBV1     fix_mobilenet_v1.py:53-80,204-230                         no masters
     """
-    resnet, mbv2, mbv1 = spec.arch.startswith(('resnet', 'resnext')), spec.arch == 'mobilenet_v2', spec.arch == 'mobilenet_v1'
+    resnet, mbv2, mbv1 = spec.arch.startswith(('resnet', 'resnext')), spec.arch.startswith('mobilenet_v2'), spec.arch.startswith('mobilenet_v1')      # (with or without `_os16`: a dilated spec has the same layers and keys)
     if not (resnet or mbv2 or mbv1):
         raise NotImplementedError(f'export: {spec.arch}')
     layers: Dict[str, _Layer] = {}

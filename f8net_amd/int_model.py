@@ -27,7 +27,7 @@ from .ops import (F8Conv2d, F8Linear, F8MaxPool2d, FXQAvgPool2d, IntReLU, add_al
 
 def _conv_module(c: topology.ConvSpec) -> F8Conv2d:
     return F8Conv2d(c.cin, c.cout, c.k, stride=c.stride, padding=c.pad, groups=c.groups,
-                    input_symmetric=c.signed_in)
+                    input_symmetric=c.signed_in, dilation=c.dilation)
 
 
 class IntBlock(nn.Module):

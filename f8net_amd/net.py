@@ -57,7 +57,8 @@ class F8Net:
         return check(self._L.f8_net_input(self._h, C, H, W, fraclen))
 
     def conv(self, src, weight, bias, *, stride, pad, groups, weight_fl, input_fl, input_signed,
-             quant_input=True, relu=False, label=None):
+             quant_input=True, relu=False, label=None, dilation=1):
+        """dilation: the spacing of the kernel's taps (f8_net_conv_dilated); the weights stay the k x k real taps."""
         w = _np_i32(weight)
         cout, cin_g, k, k2 = w.shape
         assert k == k2
@@ -65,8 +66,12 @@ class F8Net:
                      weight_fl=int(weight_fl), input_fl=int(input_fl), input_signed=int(bool(input_signed)),
                      quant_input=int(bool(quant_input)), relu=int(bool(relu)))
         b = None if bias is None else _np_i32(bias)
-        t = check(self._L.f8_net_conv(self._h, src, ctypes.byref(d), w.ctypes.data,
-                                      None if b is None else b.ctypes.data))
+        if dilation != 1:
+            t = check(self._L.f8_net_conv_dilated(self._h, src, ctypes.byref(d), int(dilation), w.ctypes.data,
+                                                  None if b is None else b.ctypes.data))
+        else:
+            t = check(self._L.f8_net_conv(self._h, src, ctypes.byref(d), w.ctypes.data,
+                                          None if b is None else b.ctypes.data))
         if label:
             self._L.f8_net_set_label(self._h, t, label.encode())
         return t
@@ -376,7 +381,7 @@ def record_net(spec: topology.NetSpec, params: dict, hw: int = 224, input_fracle
         ids[c.key] = net.conv(src, params[c.key + '.weight'], params[c.key + '.bias'], stride=c.stride, pad=c.pad,
                               groups=c.groups, weight_fl=_fl(params, c.key, 'weight_fraclen'),
                               input_fl=_fl(params, c.key, 'input_fraclen'), input_signed=c.signed_in,
-                              quant_input=quant_input, relu=c.relu, label=c.key)
+                              quant_input=quant_input, relu=c.relu, label=c.key, dilation=c.dilation)
         return ids[c.key]
 
     t = net.input(3, hw, hw, input_fraclen)

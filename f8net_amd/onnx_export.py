@@ -42,7 +42,7 @@ def graph_from_params(spec: topology.NetSpec, params: dict, hw: int = 224) -> In
         ig.ops.append(IntOp('conv', src=src, weight=params[c.key + '.weight'].astype(np.int32),
                             bias=params[c.key + '.bias'].astype(np.int32), stride=c.stride, pad=c.pad, groups=c.groups,
                             kernel=c.k, shift=(fl[src] - i) if quant else None, signed=c.signed_in, relu=c.relu,
-                            key=c.key))
+                            key=c.key, dilation=c.dilation))
         fl[len(ig.ops) - 1] = i + w
         return len(ig.ops) - 1
 
@@ -153,7 +153,7 @@ def export_graph(ig: IntGraph) -> bytes:
                 inits[o.key + '.bias'] = o.bias
                 ins.append(o.key + '.bias')
             if o.kind == 'conv':
-                y = w.emit('Conv', ins, {'dilations': [1, 1], 'group': int(o.groups), 'kernel_shape': [o.kernel] * 2,
+                y = w.emit('Conv', ins, {'dilations': [int(o.dilation)] * 2, 'group': int(o.groups), 'kernel_shape': [o.kernel] * 2,
                                          'pads': [o.pad] * 4, 'strides': [o.stride] * 2})
             else:
                 y = w.emit('Gemm', ins, {'alpha': 1.0, 'beta': 1.0, 'transB': 1})

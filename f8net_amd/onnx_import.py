@@ -51,6 +51,7 @@ class IntOp:
     swap: bool = False             # add: the shifted operand is the Add's second input (`res += x << k`) — cosmetic
     key: str = ''                  # state_dict key of the layer ('head.0', 'stage_0_layer_0.body.0', ...)
     shape: tuple = None            # input: (C, H, W)
+    dilation: int = 1              # conv: spacing of the kernel's taps (ONNX `dilations`, both equal)
 
 
 @dataclass
@@ -160,7 +161,7 @@ class IntGraph:
                 i, w = layer[t]
                 ids[t] = net.conv(ids[o.src], o.weight, o.bias, stride=o.stride, pad=o.pad, groups=o.groups,
                                   weight_fl=w, input_fl=i, input_signed=o.signed, quant_input=o.shift is not None,
-                                  relu=o.relu, label=o.key)
+                                  relu=o.relu, label=o.key, dilation=o.dilation)
             elif o.kind == 'linear':
                 i, w = layer[t]
                 ids[t] = net.linear(ids[o.src], o.weight, o.bias, weight_fl=w, input_fl=i, input_signed=o.signed,
@@ -344,12 +345,13 @@ def import_graph(model, input_signed=False) -> IntGraph:
             b = init(nd.inputs[2], 'Conv bias')[1] if len(nd.inputs) > 2 else None
             k = a['kernel_shape']
             pads, st = a.get('pads', [0, 0, 0, 0]), a.get('strides', [1, 1])
-            if k[0] != k[1] or len(set(pads)) != 1 or st[0] != st[1] or any(d != 1 for d in a.get('dilations', [1, 1])):
-                raise OnnxImportError(f'Conv {wname}: only square kernels / symmetric pads / no dilation')
+            dil = list(a.get('dilations', [1, 1]))
+            if k[0] != k[1] or len(set(pads)) != 1 or st[0] != st[1] or len(set(dil)) != 1 or dil[0] < 1:
+                raise OnnxImportError(f'Conv {wname}: only square kernels / symmetric pads / equal dilations (got dilations {dil})')
             ig.ops.append(IntOp('conv', src=src, weight=np.array(w, np.int32),
                                 bias=None if b is None else np.array(b, np.int32), stride=st[0],
                                 pad=pads[0], groups=a.get('group', 1), kernel=k[0], shift=n, signed=signed,
-                                key=_layer_key(wname)))
+                                key=_layer_key(wname), dilation=int(dil[0])))
             if n is None:
                 ig.ops[-1].signed = ig.input_signed
             val[out] = ('T', len(ig.ops) - 1)
@@ -391,12 +393,19 @@ def import_graph(model, input_signed=False) -> IntGraph:
 
 
 def detect_arch(ig: IntGraph):
-    """Name of the topology table entry whose layer keys this graph carries, or None."""
+    """Name of the topology table entry whose layer keys this graph carries, or None.  A graph with dilated convs is the `_os16` / `_os8` form of
+    that entry (topology.dilate) whose strides, pads and dilations it has — or none."""
     from . import topology
     keys = sorted(ig.layer_keys())
+    geo = {o.key: (o.stride, o.pad, o.dilation) for o in ig.ops if o.kind == 'conv'}
     for arch in ('resnet18', 'resnet50', 'mobilenet_v1', 'mobilenet_v2'):
-        if sorted(topology.get(arch).layer_keys()) == keys:
+        if sorted(topology.get(arch).layer_keys()) != keys:
+            continue
+        if all(d == 1 for _, _, d in geo.values()):
             return arch
+        for name in (f'{arch}_os16', f'{arch}_os8'):
+            if all(geo[c.key] == (c.stride, c.pad, c.dilation) for c in topology.get(name).convs()):
+                return name
     return None
 
 

@@ -81,9 +81,9 @@ class F8Conv2d(nn.Conv2d):
     its in-place version, input shape, device): editing `weight` / `bias` in place re-plans on the next forward."""
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, groups=1,
-                 input_symmetric=False):
+                 input_symmetric=False, dilation=1):
         super().__init__(in_channels, out_channels, kernel_size, stride=stride, padding=padding,
-                         groups=groups, bias=True)
+                         dilation=dilation, groups=groups, bias=True)
         self.weight.requires_grad_(False)
         self.bias.requires_grad_(False)
         self.weight.data = torch.zeros(self.weight.shape, dtype=torch.int32)
@@ -98,7 +98,7 @@ class F8Conv2d(nn.Conv2d):
         _require_dev_i32(x, 'F8Conv2d')
         w_fl, in_fl = self._fl.get(self)
         return torch.ops.f8net.conv2d(x, self.weight, self.bias, self.stride[0], self.padding[0], self.groups, w_fl, in_fl,
-                                      self.input_symmetric)
+                                      self.input_symmetric, self.dilation[0])
 
 
 class F8Linear(nn.Linear):

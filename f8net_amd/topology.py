@@ -11,6 +11,7 @@ Key naming follows the reference's exported `IntModel.state_dict()`:
 `head.0`, `stage_{i}_layer_{j}.body.{0,2,4}` (ReLUs occupy odd indices),
 `stage_{i}_layer_{j}.shortcut.0`, `tail.0` (MobileNet-V2), `classifier.0`.
 """
+import copy
 from dataclasses import dataclass, field
 from typing import List, Optional
 
@@ -26,6 +27,7 @@ class ConvSpec:
     groups: int = 1
     signed_in: bool = False   # `input_symmetric` of the reference layer
     relu: bool = False        # an nn.ReLU directly follows this conv in the int graph
+    dilation: int = 1         # spacing of the kernel's taps (`dilate`)
 
 
 @dataclass
@@ -158,10 +160,42 @@ def mobilenet_v1(num_classes: int = 1000, normalize: bool = False) -> NetSpec:
                    num_classes, normalize=normalize)
 
 
+def dilate(spec: NetSpec, output_stride: int) -> NetSpec:
+    """`spec` as a dilated backbone of this output stride (8 or 16), by torchvision's `replace_stride_with_dilation` rule (resnet.py `_make_layer`;
+    DeepLab's MobileNet-V2 follows the same one): walking the blocks, a stride-2 block that would take the map beyond `output_stride` gets stride 1
+    on its conv and on its shortcut and keeps the PREVIOUS dilation on its own k > 1 conv; the running dilation then doubles, and every later k > 1
+    conv gets dilation = running with the padding that keeps the map (running * (k // 2)).  Weight shapes and keys do not change."""
+    if output_stride not in (8, 16):
+        raise ValueError(f'dilate: output_stride {output_stride} is not 8 or 16')
+    spec = copy.deepcopy(spec)
+    cur = spec.head.stride * (2 if spec.head_maxpool else 1)
+    running = 1
+    for b in spec.blocks:
+        convs = b.body + ([b.shortcut] if b.shortcut is not None else [])
+        d = running                                   # a converted block keeps the previous dilation
+        if any(c.stride == 2 for c in convs):
+            if cur * 2 > output_stride:
+                for c in convs:
+                    c.stride = 1
+                running *= 2
+            else:
+                cur *= 2
+        for c in b.body:
+            if c.k > 1 and d > 1:
+                c.dilation, c.pad = d, d * (c.k // 2)
+    spec.arch = f'{spec.arch}_os{output_stride}'
+    return spec
+
+
 _RESNEXT = {'resnext50_32x4d': (50, 32, 4), 'resnext101_32x8d': (101, 32, 8), 'resnext101_64x4d': (101, 64, 4)}
 
 
 def get(arch: str, num_classes: int = 1000, normalize: bool = False) -> NetSpec:
+    if '_os' in arch:                                 # 'resnet50_os16', 'resnet101_os8', 'mobilenet_v2_os16': the dilated backbones (`dilate`)
+        base, os_ = arch.rsplit('_os', 1)
+        if not os_.isdigit():
+            raise ValueError(f'unknown arch {arch!r}')
+        return dilate(get(base, num_classes, normalize), int(os_))
     if arch in _RESNEXT:
         return resnext(*_RESNEXT[arch], num_classes, normalize)
     if arch.startswith('resnet'):

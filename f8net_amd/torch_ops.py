@@ -9,7 +9,7 @@ the dispatcher.
     f8net::requant(x, fl, input_fl, signed)          int_op_only_fix_quant            fix_quant_ops.py:90-114
     f8net::relu_(x)                                  nn.ReLU(inplace) on int32        fix_resnet.py:39,77
     f8net::add_align_(res, x, res_fl, x_fl)          residual align-add-clamp         fix_resnet.py:40-54
-    f8net::conv2d(x, w, b, stride, pad, groups, weight_fl, input_fl, input_signed)    `layer_(res)`, int nn.Conv2d of int_conv :680-714
+    f8net::conv2d(x, w, b, stride, pad, groups, weight_fl, input_fl, input_signed, dilation=1)    `layer_(res)`, int nn.Conv2d of int_conv :680-714
     f8net::linear(x, w, b, weight_fl, input_fl, input_signed)                         `self.classifier(x)`, int_fc :1165-1195
     f8net::avgpool_sum(x)                            FXQAvgPool2d int branch          fix_quant_ops.py:126-134
     f8net::maxpool(x, k, stride, pad)                head max-pool                    fix_resnet.py:358-359
@@ -37,7 +37,7 @@ _DEF = Library('f8net', 'DEF')
 _DEF.define('requant(Tensor x, int fl, int input_fl, bool signed) -> Tensor')
 _DEF.define('relu_(Tensor(a!) x) -> Tensor(a!)')
 _DEF.define('add_align_(Tensor(a!) res, Tensor x, int res_fl, int x_fl) -> Tensor(a!)')
-_DEF.define('conv2d(Tensor x, Tensor weight, Tensor? bias, int stride, int pad, int groups, int weight_fl, int input_fl, bool input_signed) -> Tensor')
+_DEF.define('conv2d(Tensor x, Tensor weight, Tensor? bias, int stride, int pad, int groups, int weight_fl, int input_fl, bool input_signed, int dilation=1) -> Tensor')
 _DEF.define('linear(Tensor x, Tensor weight, Tensor? bias, int weight_fl, int input_fl, bool input_signed) -> Tensor')
 _DEF.define('avgpool_sum(Tensor x) -> Tensor')
 _DEF.define('maxpool(Tensor x, int k, int stride, int pad) -> Tensor')
@@ -160,25 +160,29 @@ def _np(t):
     return None if t is None else t.detach().cpu().numpy()
 
 
-def _conv2d(x, weight, bias, stride, pad, groups, weight_fl, input_fl, input_signed):
+def _conv_out(n, k, stride, pad, dilation):
+    return (n + 2 * pad - dilation * (k - 1) - 1) // stride + 1
+
+
+def _conv2d(x, weight, bias, stride, pad, groups, weight_fl, input_fl, input_signed, dilation=1):
     _i32(x, 'conv2d')
     x = x.contiguous()
     N, C, H, W = x.shape
     key = ('conv', x.device.index, C, H, W, id(weight), tuple(weight.shape), None if bias is None else id(bias), stride, pad, groups, weight_fl, input_fl,
-           bool(input_signed))
+           bool(input_signed), dilation)
 
     def build(n):
         net = F8Net()
         accept_grouped(net, [(C, groups)])
         t = net.input(C, H, W, input_fl)
         t = net.conv(t, _np(weight), _np(bias), stride=stride, pad=pad, groups=groups, weight_fl=weight_fl, input_fl=input_fl,
-                     input_signed=input_signed, quant_input=False, relu=False)
+                     input_signed=input_signed, quant_input=False, relu=False, dilation=dilation)
         net.output(t, as_float=False)
         return net.finalize(n)
 
     net = _plans.get(key, (weight, bias), N, build)
     k = weight.shape[2]
-    P, Q = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    P, Q = _conv_out(H, k, stride, pad, dilation), _conv_out(W, k, stride, pad, dilation)
     return net.run(x).view(N, weight.shape[0], P, Q)
 
 
@@ -269,8 +273,8 @@ _META = Library('f8net', 'IMPL', 'Meta')
 _META.impl('requant', lambda x, fl, input_fl, signed: torch.empty_like(x))
 _META.impl('relu_', lambda x: x)
 _META.impl('add_align_', lambda res, x, res_fl, x_fl: res)
-_META.impl('conv2d', lambda x, w, b, stride, pad, groups, wfl, ifl, sgn: x.new_empty(
-    (x.shape[0], w.shape[0], (x.shape[2] + 2 * pad - w.shape[2]) // stride + 1, (x.shape[3] + 2 * pad - w.shape[3]) // stride + 1)))
+_META.impl('conv2d', lambda x, w, b, stride, pad, groups, wfl, ifl, sgn, dilation=1: x.new_empty(
+    (x.shape[0], w.shape[0], _conv_out(x.shape[2], w.shape[2], stride, pad, dilation), _conv_out(x.shape[3], w.shape[3], stride, pad, dilation))))
 _META.impl('linear', lambda x, w, b, wfl, ifl, sgn: x.new_empty((x.shape[0], w.shape[0])))
 _META.impl('avgpool_sum', lambda x: x.new_empty((x.shape[0], x.shape[1])))
 _META.impl('maxpool', lambda x, k, stride, pad: x.new_empty(

@@ -131,6 +131,16 @@ int f8_net_input(f8_net* net, int C, int H, int W, int fraclen);
 int f8_net_conv(f8_net* net, int src, const f8_conv_desc* desc,
                 const int32_t* weight_host, const int32_t* bias_host);
 
+/* The same conv with `dilation` between its taps (int_conv passes dilation = self.conv.dilation into the int nn.Conv2d, fix_quant_ops.py:686):
+ * output size (H + 2 pad - dilation (kernel - 1) - 1) / stride + 1; weights as f8_net_conv ([cout, cin/groups, k, k], the k x k real taps).
+ * f8_net_conv is the dilation == 1 call of this function.  Accepted for 1 <= dilation <= 64: plain convs (groups == 1) of any geometry
+ * f8_net_conv takes (kernel == 1: dilation is normalised to 1), on conv_igemm_kernel, a launch of its own (conv3x3s1d2_t128x64x64[_res]:) that may
+ * carry the residual join; depthwise convs of kernel 3 with pad <= dilation, stride 1 / 2 (dwconv3x3s1d2:, f8_dwk.hip); grouped convs on a handle
+ * with option grouped >= 1, always as the dense expansion (gconv3x3s1d2_dense:).  A dilated conv joins no fused block or chain launch.
+ * F8_ERR_INVALID: dilation < 1, or an empty output; F8_ERR_UNSUPPORTED: dilation > 64, or a depthwise kernel of 5 / 7 with dilation > 1. */
+int f8_net_conv_dilated(f8_net* net, int src, const f8_conv_desc* desc, int dilation,
+                        const int32_t* weight_host, const int32_t* bias_host);
+
 /* Residual join of IntBlock.forward (fix_resnet.py:40-54 / :63-76) [+ post_relu :77]. */
 int f8_net_add(f8_net* net, int a, int b, int relu);
 
