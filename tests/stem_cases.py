@@ -1,0 +1,488 @@
+"""Case tables, graph builder and liveness helpers of the op-level tests of the fused head launches (f8_stem.hip: stem_pool_kernel<KIND>,
+stem_rows_kernel<KIND> and stem_rows_kernel<KIND, true>): tests/test_stem_plan.py (plan and liveness on the oracle, no GPU) and tests/test_gpu_stem.py
+(every case against the oracle on the device).  No test functions here.
+
+ResNet form ('resnet'):  input (cin <= 4) -> 7x7 / 2 / pad 3 conv to 64 (ReLU on or off) -> max-pool 3 / 2 / 1 -> readers, where output 0 is the
+aligned sum of one 32-output 1x1 reader per (fraclen, signed) — at most two int8 formats.  out32: 'add' — a 64-output 1x1 in the first reader's format
+joined with the pooled int32 tensor is output 1; 'out' — the pooled int32 tensor itself is output 1; 'only' — no int8 reader, the pooled tensor is
+output 0 (an add needs a second operand, which could only be a conv that reads the pooled tensor in an int8 format: f8_net_add refuses add(p, p)).
+H2 form ('h2'):  input -> 3x3 / 2 / pad 1 conv to 32 (ReLU) -> depthwise 3x3 (ReLU) -> 1x1 to cout (no ReLU) -> one or two 32-output 1x1 readers.
+
+The entry of a case says how its runs hand the images over, which is what selects the kernels' KIND:
+  i32  f8_net_run: int32 planes, read by the launch itself (KIND 0)          f32  f8_net_run_f32 (KIND 1): signed head format, fix_quant on the fly
+  u8   f8_net_run_u8, NCHW planes (KIND 2)                                    and the four that read the haloed NHWC4 copy (KIND -1):
+  halo  fuse_input = 0     nhwc  f8_net_run_u8(nhwc=True) on a default plan     cin1 / cin4  an input of 1 / 4 channels (f8_net_run)
+The expected plan token, kernel name and the wording of the input step are WRITTEN BY HAND per case (`kernel`: 'tile' | 'rows' | 'h2' | None — the
+unfused pair); nothing here asks the planner for them.
+
+Weights' sigma and biases are scaled as igemm_cases._sig does, so that the accumulators spread over about 2^shift * [0, 255]; where 8-bit weights
+cannot carry that (sigma below 1: one +-1 tap per output channel; shifts above 14: sigma stays at 60), the biases carry the rest.  Output channels
+3 .. 6 of every conv are made by hand: 3 and 4 sit beyond the clamps of every reader, 5 and 6 have zero weights and biases that are exact ties of the
+conv's first right shift above an even and an odd quotient."""
+import numpy as np
+
+from f8net_amd import synth
+from igemm_cases import _sig
+from ir_cases import _Graph, _b, _w
+from oracle import oracle
+
+TOKEN = {'resnet': 'stem7x7s2+maxpool3x3s2:', 'h2': 'head3x3s2+dw3x3+1x1:'}
+KERNEL = {'tile': 'f8::stem_pool_kernel', 'rows': 'f8::stem_rows_kernel', 'h2': 'f8::stem_rows_kernel'}
+RAW_WORDING = 'read by the stem launch'
+ENTRIES = ('i32', 'f32', 'u8', 'halo', 'nhwc', 'cin1', 'cin4')
+RAW_PLAN = {'i32': True, 'f32': True, 'u8': True, 'halo': False, 'nhwc': True, 'cin1': False, 'cin4': False}     # the plan's wording (nhwc: a raw plan whose run takes the haloed copy)
+KIND = {'i32': 0, 'f32': 1, 'u8': 2, 'halo': -1, 'nhwc': -1, 'cin1': -1, 'cin4': -1}                             # the template argument the run selects
+MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+INT32_LIM = 2 ** 31 - 2 ** 24                                    # biases stay this far inside int32: 147 products of 8 bits are below 2^23
+
+
+class Graph(_Graph):
+    """ir_cases._Graph with the max-pool the ResNet form needs."""
+
+    def maxpool(self, t, k=3, stride=2, pad=1):
+        o = self.net.maxpool(t, k, stride, pad)
+        self.v[o] = (oracle.maxpool(self.v[t][0], k, stride, pad), self.v[t][1])
+        return o
+
+
+# ---- entries: the format of the head input each one implies, and the images
+def _entry_format(entry, form):
+    """(x_fl, x_signed, normalize) an entry fixes; None for the int32 entries, whose case says it."""
+    if entry == 'f32':
+        return 6, True, True                                    # fix_quant: rint(x * 2^6) clamped to +-127
+    if entry == 'u8':                                           # tile kernel: the pixels themselves; row kernel: Normalize into signed 5; H2: into unsigned 8
+        return {'tile': (8, False, False), 'rows': (5, True, True), 'h2': (8, False, True), None: (8, False, False)}[form]
+    if entry == 'nhwc':
+        return 8, False, False
+    return None
+
+
+def make_data(name, case, n=None, seed=5):
+    """{'raw': what the entry hands to the run (int32 / float32 / uint8 NCHW), 'x': the head-format integers the graph is evaluated on}."""
+    c = case
+    n = n or c['N']
+    shape = (n, c['cin'], c['H'], c['W'])
+    lo, hi = (-127, 127) if c['x_signed'] else (0, 255)
+    if c['entry'] in ('u8', 'nhwc'):
+        pix = synth.rand_uniform_int(seed, f'px{name}', shape, 0, 255).astype(np.uint8)
+        pix[:, :, 1, 1], pix[:, :, 2, 5] = 0, 255                  # both ends in every plane
+        kw = dict(normalize=True, mean=MEAN, std=STD, head_in_fl=c['x_fl'], signed=c['x_signed']) if c['normalize'] else {}
+        x, fl = oracle.quantize_input_pixels(pix, **kw)
+        assert fl == c['x_fl']
+        return dict(raw=pix, x=x.astype(np.int32))
+    q = synth.rand_uniform_int(seed, f'x{name}', shape, lo, hi)
+    q[:, :, 1, 1], q[:, :, 2, 5] = lo, hi                          # both ends of the format in every plane
+    if c['entry'] != 'f32':
+        return dict(raw=q.astype(np.int32), x=q.astype(np.int32))
+    # fp32: exact multiples of 2^-fl, exact .5 ties above even and odd integers, and values beyond both clamps
+    f = q.astype(np.float64)
+    f[:, :, 0, 0::4] += 0.5                                     # ties (q even and odd, both signs)
+    f[:, :, 3, 1], f[:, :, 3, 2], f[:, :, 3, 3], f[:, :, 3, 4] = hi + 73.0, lo - 73.0, hi + 0.5, lo - 0.5
+    raw = (f / 2.0 ** c['x_fl']).astype(np.float32)
+    x, fl = oracle.quantize_input_normalized(raw, c['x_fl'])
+    assert fl == c['x_fl'] and c['x_signed']
+    return dict(raw=raw, x=x.astype(np.int32))
+
+
+# ---- weights and biases
+def _conv_params(seed, shape, rms_in, n, centre, hand=(), lim=INT32_LIM):
+    """Weights and biases of a conv whose accumulators spread with a sigma of about 80 * 2^n around centre * 2^n.  hand: [(channel, bias)] — channels
+    with zero weights and the bias given."""
+    cout, cg, k, _ = shape
+    K = cg * k * k
+    sig = _sig(K, rms_in, n)
+    if sig >= 1.0:
+        w = _w(seed, shape, sig)
+    else:                                                        # 8-bit weights cannot be that small: one tap of +-1 per output channel
+        pos = synth.rand_uniform_int(seed, f'tap{shape}', (cout,), 0, K - 1)
+        sgn = synth.rand_uniform_int(seed + 1000, f'sgn{shape}', (cout,), 0, 1) * 2 - 1
+        w = np.zeros((cout, K), np.int32)
+        w[np.arange(cout), pos] = sgn
+        w = w.reshape(shape)
+        sig = 1.0 / K ** 0.5
+    from_w = sig * K ** 0.5 * rms_in
+    if n >= 1 and from_w < 2.0 ** n:
+        # the products cannot move a value by one unit of the shift: every channel would be one constant.  Biases next to rounding boundaries
+        # (2j + 1) * 2^(n-1) instead, j over the 8-bit range (and below 0 for the ReLU) as far as int32 goes: the products decide the rounding
+        jmax = int((lim / 2.0 ** (n - 1) - 1) // 2)
+        j = synth.rand_uniform_int(seed + 1, f'j{cout}', (cout,), max(-60 if centre >= 0 else -127, -jmax - 1), min(255 if centre >= 0 else 127, jmax))
+        b = (2 * j + 1) * (1 << (n - 1)) + synth.rand_normal_int(seed + 2, f'b{cout}', (cout,), from_w)
+    else:
+        bsig = max(16.0 * 2.0 ** n, (max(0.0, (80.0 * 2.0 ** n) ** 2 - from_w ** 2)) ** 0.5)
+        b = np.clip(synth.rand_normal_int(seed + 1, f'b{cout}', (cout,), bsig) + int(centre * 2.0 ** n), -lim, lim).astype(np.int64)
+    for ch, v in hand:
+        w[ch] = 0
+        b[ch] = v
+    return w, b.astype(np.int32)
+
+
+def _ties(n):
+    """Biases that are exact ties of a right shift by n above an even and an odd quotient (inside unsigned and signed 8 bits)."""
+    if n < 1:
+        return []
+    q = 2 if n <= 28 else 0
+    return [(q << n) + (1 << (n - 1)), ((q + 1) << n) + (1 << (n - 1))]
+
+
+def _readers(g, t, cin, readers):
+    out = None
+    for i, (rfl, sgn) in enumerate(readers):
+        r = g.conv(t, _w(90 + i, (32, cin, 1, 1), 8.0), None, pad=0, groups=1, weight_fl=6, input_fl=rfl, input_signed=sgn, relu=False, label=f'reader{i}')
+        out = r if out is None else g.add(out, r)
+    return out
+
+
+def build_graph(case, x):
+    """Returns (graph, [output tensors], ids): ids names the tensors the liveness checks look at ('conv', 'pool' | 'head', 'dw', 'pw')."""
+    c = case
+    g = Graph(x, c['x_fl'])
+    for key, v in c['opts'].items():
+        g.net.set_option(key, v)
+    t0 = next(iter(g.v))
+    s = c['w_seed']
+    cin = c['cin']
+    rms_x = (127 if c['x_signed'] else 255) / 3.0 ** 0.5
+    ids, outs = {}, []
+    if c['form'] == 'resnet':
+        fl = c['x_fl'] + c['w_fl']
+        shifts = [fl - rfl for rfl, _ in c['readers']]
+        n = shifts[0] if shifts else c['shift']
+        nmax = max(shifts + [n, 0])
+        signed0 = bool(c['readers']) and c['readers'][0][1]
+        # the pooled value is the largest of nine: about 1.3 sigma above the conv's centre.  Unsigned readers: pooled values around 125 * 2^n
+        centre = -105.0 if (signed0 and not c["relu"]) else -20.0 if signed0 else 20.0
+        big = min(INT32_LIM, max(2 ** (nmax + 8) + 5, 2 ** 25 + 5 if c['out32'] else 0))
+        hand = [(3, big), (4, -big)] + list(zip((5, 6), _ties(n)))
+        w, b = _conv_params(s + 10, (64, cin, 7, 7), rms_x, n, centre, hand)
+        if c['bias_big']:                                         # next to 2^31: the planner cannot bound the accumulators (acc_ok = 0)
+            b[7], b[8] = 2 ** 31 - 50, -(2 ** 31) + 50
+        y = g.conv(t0, w, b, stride=2, pad=3, groups=1, weight_fl=c['w_fl'], input_fl=c['x_fl'], input_signed=c['x_signed'], relu=c['relu'], quant_input=False)
+        p = g.maxpool(y, 3, 2, 1)
+        ids.update(conv=y, pool=p)
+        if c['readers']:
+            outs.append(_readers(g, p, 64, c['readers']))
+        if c['out32'] == 'add':
+            rfl, sgn = c['readers'][0]
+            j = g.conv(p, _w(95, (64, 64, 1, 1), 8.0), None, pad=0, groups=1, weight_fl=6, input_fl=rfl, input_signed=sgn, relu=False)
+            outs.append(g.add(j, p))
+        elif c['out32'] in ('out', 'only'):
+            outs.append(p)
+    else:
+        na, nb = c['na'], c['nb']
+        pw_fl = c['pw_in_fl'] + c['pw_w_fl']
+        shifts = [pw_fl - rfl for rfl, _ in c['readers']]
+        n = shifts[0]
+        nmax = max(shifts + [0])
+        lim_a = INT32_LIM
+        wa, ba = _conv_params(s + 10, (32, cin, 3, 3), rms_x, na, 45.0, [(3, 300 << na), (4, -(300 << na))] + list(zip((5, 6), _ties(na))), lim_a)
+        wd, bd = _conv_params(s + 20, (32, 1, 3, 3), 110.0, nb, 45.0, [(3, 300 << nb), (4, -(300 << nb))] + list(zip((5, 6), _ties(nb))))
+        signed0 = c['readers'][0][1]
+        big = 2 ** (nmax + 8) + 5
+        hand = [(3, big), (4, -big)] + list(zip((5, 6), _ties(n)))
+        wp, bp = _conv_params(s + 30, (c['cout'], 32, 1, 1), 110.0, n, 0.0 if signed0 else 128.0, hand)
+        if c['bias_big'] == 'head':
+            ba[7], ba[8] = 2 ** 31 - 50, -(2 ** 31) + 50
+        if c['bias_big'] == 'dw':
+            bd[7], bd[8] = 2 ** 31 - 50, -(2 ** 31) + 50
+        h = g.conv(t0, wa, ba, stride=2, pad=1, groups=1, weight_fl=c['w_fl'], input_fl=c['x_fl'], input_signed=c['x_signed'], relu=True, quant_input=False)
+        d = g.conv(h, wd, bd, stride=1, pad=1, groups=32, weight_fl=c['dw_w_fl'], input_fl=c['dw_in_fl'], input_signed=False, relu=True, label='dw_in')
+        p = g.conv(d, wp, bp, pad=0, groups=1, weight_fl=c['pw_w_fl'], input_fl=c['pw_in_fl'], input_signed=False, relu=False, label='pw_in')
+        ids.update(head=h, dw=d, pw=p, wd=wd)
+        outs.append(_readers(g, p, c['cout'], c['readers']))
+    for o in outs:
+        g.net.output(o, as_float=False)
+    return g, outs, ids
+
+
+def plan(name, case, x=None, max_batch=None):
+    x = make_data(name, case)['x'] if x is None else x
+    g, outs, ids = build_graph(case, x)
+    g.net.finalize(max_batch or case['max_batch'])
+    return g, outs, ids
+
+
+def lines(net):
+    """[(plan token up to its colon, kernel name)] of every launch of the handle, in launch order."""
+    return [(net.launch_info(i, 1)[0].split(':')[0] + ':', net.launch_kernel(i)) for i in range(net.num_launches)]
+
+
+def expect(case):
+    """The hand-written expectation of a case: (token, kernel) of the head launch, or None where the head is not fused."""
+    return (TOKEN[case['form']], KERNEL[case['kernel']]) if case['kernel'] else None
+
+
+def head_lines(net):
+    return [ln for ln in lines(net) if ln[0] in TOKEN.values()]
+
+
+def head_launches(net, n):
+    """Kernel launches the head step issues per run of n images (sub-batches and chunks counted)."""
+    (i,) = [i for i in range(net.num_launches) if net.launch_info(i, 1)[0].split(':')[0] + ':' in TOKEN.values()]
+    return net.step_launches(i, n)
+
+
+def run_entry(net, case, data, dev, n=None, **kw):
+    """One run of the first n images through the case's entry; returns what the run method returns."""
+    import torch
+    raw = torch.from_numpy(np.ascontiguousarray(data['raw'][:n] if n else data['raw'])).to(dev)
+    e = case['entry']
+    if e == 'f32':
+        return net.run_f32(raw, True, **kw)
+    if e in ('u8', 'nhwc'):
+        norm = dict(normalize=True, mean=MEAN, std=STD) if case['normalize'] else dict(normalize=False)
+        if e == 'nhwc':
+            raw = raw.permute(0, 2, 3, 1).contiguous()
+        return net.run_u8(raw, nhwc=e == 'nhwc', **norm, **kw)
+    return net.run(raw, **kw)
+
+
+# ---- cases
+def _resnet(H, W, kernel, entry='i32', readers=((4, False),), shift=9, N=3, **kw):
+    """kernel: what the plan must launch, by hand.  w_fl: from the first reader's right shift (`shift`) unless given."""
+    d = dict(form='resnet', H=H, W=W, N=N, max_batch=None, entry=entry, cin=3, x_fl=8, x_signed=False, normalize=False, w_fl=None, relu=True,
+             readers=list(readers), out32=None, bias_big=False, opts={}, kernel=kernel, w_seed=0, shift=shift)
+    d.update(kw)
+    _finish(d, kernel)
+    if d['w_fl'] is None:
+        d['w_fl'] = shift + (d['readers'][0][0] if d['readers'] else 4) - d['x_fl']
+    assert d['w_fl'] >= 0, 'a larger reader fraclen makes room for the shift'
+    return d
+
+
+def _finish(d, form_kernel):
+    e = d['entry']
+    assert e in ENTRIES
+    fmt = _entry_format(e, form_kernel)
+    if fmt:
+        d['x_fl'], d['x_signed'], d['normalize'] = fmt
+    d['cin'] = {'cin1': 1, 'cin4': 4}.get(e, 3)
+    if e == 'halo':
+        d['opts'] = dict(d['opts'], fuse_input=0)
+    d['max_batch'] = d['max_batch'] or d['N']
+    d['raw_plan'] = RAW_PLAN[e] and d['kernel'] is not None
+    d['kind'] = KIND[e]
+
+
+def _h2(H, W, entry='i32', na=6, nb=6, cout=32, readers=((4, False),), shift=6, N=3, kernel='h2', **kw):
+    """Formats: the depthwise and the 1x1 read unsigned fraclen 8; the weights' fraclens make the shifts na, nb and the first reader's `shift`."""
+    d = dict(form='h2', H=H, W=W, N=N, max_batch=None, entry=entry, cin=3, x_fl=8, x_signed=False, normalize=False, na=na, nb=nb, cout=cout, dw_in_fl=8,
+             pw_in_fl=8, readers=list(readers), bias_big=None, opts={}, kernel=kernel, w_seed=0, relu=True, out32=None)
+    d.update(kw)
+    _finish(d, 'h2')
+    d['w_fl'] = na + d['dw_in_fl'] - d['x_fl']
+    d['dw_w_fl'] = nb + d['pw_in_fl'] - d['dw_in_fl']
+    d['pw_w_fl'] = shift + d['readers'][0][0] - d['pw_in_fl']
+    assert d['w_fl'] >= 0 and d['dw_w_fl'] >= 0 and d['pw_w_fl'] >= 0
+    return d
+
+
+# ================================================================================================================================================
+# Table A: every instance — three launch forms x (three raw entries + the haloed form, entered four ways).  Three images on a handle finalized for 3.
+# Tile kernel: stem_rows = 0, 28 x 32 -> pooled 7 x 8 (one tile per image).  Row kernel: 36 x 120 -> pooled 9 x 30 (two bands, two strips, the
+# second 2 columns wide).  H2: 32 x 60 -> 16 x 30 (two bands of 14 + 2 rows, two strips).
+TABLE_A = {}
+for _e in ENTRIES:
+    TABLE_A[f'a_tile_{_e}'] = _resnet(28, 32, 'tile', entry=_e, opts={'stem_rows': 0})
+    TABLE_A[f'a_rows_{_e}'] = _resnet(36, 120, 'rows', entry=_e)
+    TABLE_A[f'a_h2_{_e}'] = _h2(32, 60, entry=_e)
+# the twelve instances: (kernel, H2, KIND)
+INSTANCES = {(k, kind) for k in ('tile', 'rows', 'h2') for kind in (0, 1, 2, -1)}
+
+# ================================================================================================================================================
+# Table B: geometry.  Three images, reader shift 6 (x_fl 8, w_fl 2, reader at unsigned 4), integer requant.
+_G = dict(shift=6)
+TABLE_B = {}
+# row kernel: pooled (P, Q): one strip of four quarter-bands up to Q = 28, two strips of two half-bands above; sub-bands with no rows (P < 4 / P < 2),
+# ragged last bands; colO / colE at the last column of a strip 1, 2 and 28 columns wide
+for _P, _Q in ((1, 2), (2, 27), (3, 28), (7, 29), (8, 30), (9, 55), (15, 56), (25, 25)):
+    TABLE_B[f'b_rows_{_P}x{_Q}'] = _resnet(4 * _P, 4 * _Q, 'rows', **_G)
+# 20 x 24 (pooled 5 x 6: no tile-kernel instance) through each haloed entry: stem_rows_ok's org == 2 && Wp % 4 == 0
+for _e in ('halo', 'nhwc', 'cin1', 'cin4'):
+    TABLE_B[f'b_rows_5x6_{_e}'] = _resnet(20, 24, 'rows', entry=_e, **_G)
+# tile kernel: odd conv maps (13 x 15 inside the 15 x 17 region, behind the `inside` mask) — sides that are no multiple of 4, so the default plan
+# takes the tile kernel itself — and whole tiles under stem_rows = 0: 1 x 1, 2 x 2 and 1 x 2 tiles per image
+for _H, _W in ((25, 29), (26, 30), (27, 31)):
+    TABLE_B[f'b_tile_{_H}x{_W}'] = _resnet(_H, _W, 'tile', **_G)
+for _H, _W in ((28, 32), (56, 64), (28, 64)):
+    TABLE_B[f'b_tile_{_H}x{_W}'] = _resnet(_H, _W, 'tile', opts={'stem_rows': 0}, **_G)
+TABLE_B['b_unfused_70x70'] = _resnet(70, 70, None, **_G)           # conv 35 x 35, pool 18 x 18: neither kernel; the unfused pair
+# H2: output (H / 2, W / 2): one to four strips, the last one 2 (or 28) wide; one band, a ragged second band, three bands
+for _P, _Q in ((4, 4), (8, 28), (14, 30), (16, 56), (30, 58), (4, 84), (4, 112)):
+    TABLE_B[f'b_h2_{_P}x{_Q}'] = _h2(2 * _P, 2 * _Q)
+# 15 output rows are H = 30, which is no multiple of 4: head2_supported refuses it and the three convs run unfused (still against the oracle);
+# the four-strip map with a ragged second band is 16 x 86 (H = 32) instead
+TABLE_B['b_h2_15x86_unfused'] = _h2(30, 172, kernel=None)
+TABLE_B['b_h2_16x86'] = _h2(32, 172)
+TABLE_B['b_h2_wide_4x114_unfused'] = _h2(8, 228, kernel=None)     # W / 2 = 114 > 112: not fused
+
+# ================================================================================================================================================
+# Table C: epilogue and formats.  Row kernel at pooled 8 x 30 (32 x 120), H2 at 16 x 30 (32 x 60).
+_U, _S = (4, False), (4, True)
+
+
+def _epi(readers=(_U,), shift=9, **kw):
+    return _resnet(32, 120, 'rows', readers=readers, shift=shift, **kw)
+
+
+TABLE_C = {}
+for _rq in (0, 1):                                               # first / second branch of stem_quant16: float converter (requant_float 1, shift <= 16) / integer
+    TABLE_C[f'c_u_shift1_rq{_rq}'] = _epi([(7, False)], shift=1, opts={'requant_float': _rq})
+    TABLE_C[f'c_u_shift9_rq{_rq}'] = _epi(opts={'requant_float': _rq})
+    TABLE_C[f'c_u_shift16_rq{_rq}'] = _epi(shift=16, opts={'requant_float': _rq})
+    TABLE_C[f'c_h2_1_1_rq{_rq}'] = _h2(32, 60, na=1, nb=1, opts={'requant_float': _rq})
+    TABLE_C[f'c_h2_16_16_rq{_rq}'] = _h2(32, 60, na=16, nb=16, opts={'requant_float': _rq})
+    TABLE_C[f'c_h2_1_16_rq{_rq}'] = _h2(32, 60, na=1, nb=16, opts={'requant_float': _rq})
+    TABLE_C[f'c_h2_7_3_rq{_rq}'] = _h2(32, 60, na=7, nb=3, opts={'requant_float': _rq})
+TABLE_C.update({
+    'c_u_shift17': _epi(shift=17, opts={'requant_float': 1}),    # above kRequantU8MaxShift: the integer form whatever the option says
+    'c_u_shift30': _epi(shift=30, opts={'requant_float': 1}),
+    'c_s_behind_relu': _epi([_S]),                               # third branch: another right shift
+    'c_shift0': _epi([(8, False)], shift=0),                     # fourth branch: nothing to shift
+    'c_left_shift': _epi([(7, True)], x_fl=5, x_signed=True, w_fl=0, shift=-2),      # fraclen 5 -> 7: a left shift by 2
+    'c_two_formats': _epi([_U, (3, True)]),
+    'c_i32_only': _epi([], out32='only'),
+    'c_i32_u_add': _epi([_U], out32='add'),
+    'c_i32_u_s_out': _epi([_U, (3, True)], out32='out'),
+    'c_no_relu_s': _epi([_S], relu=False),
+    'c_no_relu_i32': _epi([_S], relu=False, out32='out'),
+    'c_signed_in_fl5': _epi(x_fl=5, x_signed=True),
+    'c_signed_in_fl7': _epi(x_fl=7, x_signed=True),
+    'c_unsigned_in_fl8': _epi(x_fl=8, x_signed=False, shift=7),
+    'c_bias_big_rq1': _epi(bias_big=True, opts={'requant_float': 1}),     # acc_ok = 0: the integer form although the option asks for the converter
+    'c_bias_big_rq0': _epi(bias_big=True),
+    'c_tile_two_formats_i32': _resnet(28, 32, 'tile', readers=[_U, (3, True)], out32='out', opts={'stem_rows': 0}),     # the tile kernel's own stores
+    'c_tile_no_relu_s': _resnet(28, 32, 'tile', readers=[_S], relu=False, opts={'stem_rows': 0}),
+    'c_h2_bias_big_head': _h2(32, 60, bias_big='head', opts={'requant_float': 1}),
+    'c_h2_bias_big_dw': _h2(32, 60, bias_big='dw', opts={'requant_float': 1}),
+    'c_h2_two_formats': _h2(32, 60, readers=[_U, (3, True)]),
+    'c_h2_signed_reader': _h2(32, 60, readers=[_S]),
+    'c_h2_cout8': _h2(32, 60, cout=8),
+    'c_h2_cout16': _h2(32, 60, cout=16),
+    'c_h2_cout24': _h2(32, 60, cout=24),
+    'c_h2_cout32': _h2(32, 60, cout=32),
+})
+CASES = dict(TABLE_A, **TABLE_B, **TABLE_C)
+
+# (w_seed: another draw of the weights where the first leaves a liveness condition of test_stem_plan.py unmet.  With channels 3 .. 6 made by hand
+#  the first draw, seed 0, meets every condition of every case: the search on the CPU oracle had nothing to change.)
+
+# ---- schedule cases (tests/test_gpu_stem.py).  split = 1: a run is ONE launch over all its images (by default a run is cut into two sub-batches, and
+# the tile counts below would be those of neither); stem_grid_div = 32: eight workgroups on 256 compute units
+ONE_LAUNCH = {'stem_grid_div': 32, 'split': 1}
+SCHED_ROWS = {'s_rows_9x60x8': dict(H=60, W=8, N=9, opts=ONE_LAUNCH),       # pooled 15 x 2: bands of 7 / 7 / 1, 27 band tiles: ntiles % 8 = 3
+              's_rows_8x56x120': dict(H=56, W=120, N=8, opts=ONE_LAUNCH),     # pooled 14 x 30: 16 tiles
+              's_rows_24x28x8': dict(H=28, W=8, N=24, opts=ONE_LAUNCH)}       # pooled 7 x 2: 24 tiles
+SCHED_H2 = dict(H=60, W=8, N=9, opts=ONE_LAUNCH)                            # 30 output rows: bands of 14 / 14 / 2, 27 band tiles
+RB, H2_RB, SW = 7, 14, 28
+
+
+def row_grid(cus, gdiv, ntiles):
+    """launch_stem_pool's grid of the row-walking kernels, written out by hand."""
+    return min(ntiles, (cus // gdiv + 7) // 8 * 8)
+
+
+# ---- liveness helpers (on the oracle's values alone)
+def reader_forms(case, g, t):
+    """[(label, int64 value the launch requantises, int8 value the reader sees, right shift, signed)] of the int8 forms the head launch writes."""
+    v, fl = g.v[t]
+    taps = [tp for tp in g.taps if tp[0].startswith('reader')]
+    assert len(taps) == len(case['readers'])
+    return [(label, v.astype(np.int64), xq, fl - rfl, sgn) for (rfl, sgn), (label, xq, s2) in zip(case['readers'], taps)]
+
+
+def tie_parities(v, n, lo, hi):
+    """(an exact tie of the right shift n above an even quotient exists, above an odd one), quotients inside [lo, hi)."""
+    tie = (v & ((1 << n) - 1)) == (1 << (n - 1))
+    q = v >> n
+    inside = tie & (q >= lo) & (q < hi)
+    return bool((inside & (q % 2 == 0)).any()), bool((inside & (q % 2 == 1)).any())
+
+
+def pool_windows(v):
+    """The 3 / 2 / 1 max-pool's windows over conv values v [N, C, Pc, Qc]: (win [N, C, P, Q, 9] with INT64_MIN outside the image, unique [N, C, P, Q]:
+    the maximum is attained once, pos [N, C, P, Q]: 3 * dr + dc of the maximum, padded copy of v: row / column i of v is i + 1 there)."""
+    N, C, Pc, Qc = v.shape
+    P, Q = (Pc - 1) // 2 + 1, (Qc - 1) // 2 + 1
+    NEG = np.iinfo(np.int64).min
+    vp = np.full((N, C, 2 * P + 2, 2 * Q + 2), NEG, np.int64)
+    vp[:, :, 1:1 + Pc, 1:1 + Qc] = v
+    win = np.stack([vp[:, :, dr:dr + 2 * P:2, dc:dc + 2 * Q:2] for dr in range(3) for dc in range(3)], -1)
+    mx = win.max(-1)
+    return win, (win == mx[..., None]).sum(-1) == 1, win.argmax(-1), vp
+
+
+def border_liveness(v):
+    """Problems (a list of strings, empty = live) of the pool's border windows on conv values v: per group of pooled outputs — row 0, column 0, the
+    corner, and the last row / column where the conv map is odd (a window that hangs over the far edge) — every in-image window position must be
+    the unique maximum of some output; and some output of row 0 / column 0 must have a strictly larger conv value in conv row 2 / column 2, just
+    outside its window (the value a wrong substitute for the padding would pick up)."""
+    win, uniq, pos, vp = pool_windows(v)
+    N, C, P, Q, _ = win.shape
+    NEG = np.iinfo(np.int64).min
+    groups = {'row0': (slice(0, 1), slice(None)), 'col0': (slice(None), slice(0, 1)), 'corner': (slice(0, 1), slice(0, 1))}
+    if v.shape[2] % 2:
+        groups['last_row'] = (slice(P - 1, P), slice(None))
+    if v.shape[3] % 2:
+        groups['last_col'] = (slice(None), slice(Q - 1, Q))
+    bad = []
+    for name, (ps, qs) in groups.items():
+        w, u, k = win[:, :, ps, qs], uniq[:, :, ps, qs], pos[:, :, ps, qs]
+        need = {i for i in range(9) if (w[..., i] != NEG).any()}
+        hit = set(np.unique(k[u]).tolist())
+        if need - hit:
+            bad.append(f'{name}: no unique maximum at window positions {sorted(need - hit)}')
+    mx = win.max(-1)
+    outside = False
+    if v.shape[2] > 2:                                           # conv row 2 = padded row 3, over the window's columns
+        below = np.stack([vp[:, :, 3, dc:dc + 2 * Q:2] for dc in range(3)], -1).max(-1)
+        outside |= bool((below > mx[:, :, 0, :]).any())
+    if v.shape[3] > 2:
+        right = np.stack([vp[:, :, dr:dr + 2 * P:2, 3] for dr in range(3)], -1).max(-1)
+        outside |= bool((right > mx[:, :, :, 0]).any())
+    if not outside:
+        bad.append('no border output has a larger conv value just outside its window')
+    return bad
+
+
+def pooled_hw(case):
+    """(P, Q) of what the head launch writes: the pooled map (conv 7 / 2 / 3, pool 3 / 2 / 1) or the H2 form's output."""
+    if case['form'] == 'h2':
+        return (case['H'] - 1) // 2 + 1, (case['W'] - 1) // 2 + 1
+    return tuple(((s - 1) // 2 + 1 - 1) // 2 + 1 for s in (case['H'], case['W']))
+
+
+def seams(case):
+    """(pooled columns, pooled rows) at which a new strip / tile / band / sub-band of the case's ResNet-form kernel starts (0 excluded), by hand from
+    the kernels: the tile kernel cuts at multiples of 8 columns and 7 rows; the row kernel at column 28 (two strips) and, per band of 7 rows, at the
+    starts of its 4 (one strip) or 2 sub-bands of ceil(rows / sub-bands) rows."""
+    P, Q = pooled_hw(case)
+    if case['kernel'] == 'tile':
+        return list(range(8, Q, 8)), list(range(7, P, 7))
+    cols = [SW] if Q > SW else []
+    nsb = 2 if Q > SW else 4
+    rows = []
+    for p0 in range(0, P, RB):
+        rp = min(RB, P - p0)
+        rps = -(-rp // nsb)
+        rows += [p0 + sb * rps for sb in range(nsb) if sb * rps < rp and p0 + sb * rps > 0]
+    return cols, rows
+
+
+def seam_liveness(case, v):
+    """Problems of the seams on conv values v: the maximum of some output in the last column (row) before a seam comes, uniquely, from the conv
+    column (row) it shares with the first output behind the seam, and the other way round."""
+    _, uniq, pos, _ = pool_windows(v)
+    cols, rows = seams(case)
+    bad = []
+    for q in cols:
+        if not (uniq & (pos % 3 == 2))[:, :, :, q - 1].any() or not (uniq & (pos % 3 == 0))[:, :, :, q].any():
+            bad.append(f'column seam {q}: no maximum from the shared conv column {2 * q - 1}')
+    for p in rows:
+        if not (uniq & (pos // 3 == 2))[:, :, p - 1, :].any() or not (uniq & (pos // 3 == 0))[:, :, p, :].any():
+            bad.append(f'row seam {p}: no maximum from the shared conv row {2 * p - 1}')
+    return bad
+
+
+def h2_seams(case):
+    Q = case['W'] // 2
+    return list(range(SW, Q, SW))

@@ -394,7 +394,8 @@ def test_handles_share_the_internal_streams_and_stay_independent(dev):
 def test_resnet_head_at_odd_sizes(dev, hw):
     """The row-walking head takes input sides that are multiples of 4 (ragged last band, one strip, lanes past the image); other sizes
     keep the tile kernel or the unfused pair: 56 -> pooled 14x14 (two bands), 100 -> 25x25 (3 bands + 4 rows), 120 -> 30x30 (two strips,
-    the second 2 columns wide), 70 -> conv 35x35, pool 18x18 (no fused head).  ResNet-18, bs 3, against the oracle; uint8 entry too."""
+    the second 2 columns wide), 70 -> conv 35x35, pool 18x18 (no fused head).  ResNet-18, bs 3, against the oracle; the uint8 entries (NCHW planes,
+    read by the head launch, and NHWC pixels, which take the haloed copy) too.  The op-level corners of the head are in tests/test_gpu_stem.py."""
     from f8net_amd.net import build_net
     spec = topology.get('resnet18', num_classes=16)
     params = synth.make_params(spec, seed=21)
@@ -408,6 +409,13 @@ def test_resnet_head_at_odd_sizes(dev, hw):
     assert np.array_equal(got, want)
     got1 = net.run(_t(x[:1], dev)).cpu().numpy()
     assert np.array_equal(got1, want[:1])
+    # uint8 entry: the unnormalised head reads the pixels themselves (ToTensor then `255 * x` rounded gives the pixel back), so the same images
+    # as uint8 planes — and as NHWC pixels, which go through the haloed copy — give the same logits
+    assert x_fl == 8 and x.min() >= 0 and x.max() <= 255
+    pix = torch.from_numpy(x.astype(np.uint8)).to(dev)
+    assert np.array_equal(net.run_u8(pix).cpu().numpy(), want)
+    assert np.array_equal(net.run_u8(pix.permute(0, 2, 3, 1).contiguous(), nhwc=True).cpu().numpy(), want)
+    net.check()
 
 
 def test_graph_switched_on_after_the_first_runs(dev):
