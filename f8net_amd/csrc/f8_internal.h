@@ -72,6 +72,7 @@ struct Options {
                                  // float converter (v_cvt_f32_i32, v_mul_f32 by 2^-n, v_cvt_pk_u8_f32: exact where planned, f8_device.h)
     int grouped = 0;             // grouped convs (1 < groups < cin): 0 = refused by f8_net_conv; 1 = accepted, on gconv3x3_kernel (f8_gconv.hip) where it applies and as the
                                  // dense expansion (the plain conv kernels over block-diagonal weights) elsewhere; 2 = accepted, always the dense expansion
+    int concat_i8 = 1;           // f8_net_concat: 1 = the byte-gather mode where it is exact (every source written in the output's int8 formats, f8_concat.hip); 0 = always the int32 mode
     int tap_tiled = 1;           // network outputs 1 .. leave on tap_kernel (f8_tap.hip: walks the I32T blocks, every loaded byte used); 0: on output_kernel like output 0
     int check_input_range = 1;   // int32 inputs that are NARROWED to the head's 8-bit format (no requant) are range-checked on the device; f8_net_check reports
 };
@@ -189,6 +190,18 @@ struct InArgs {                            // network input: int32 NCHW -> NHWC 
     int8_t* out8;  int32_t Cs8;            // NHWC int8 (Cs8-channel rows), or
     int8_t* stem;  int32_t Hp, Wp, pad;    // zero-haloed NHWC4 for the stem conv
     int32_t* out32; int32_t Cs32;
+};
+
+// Channel concatenation (f8_concat.hip; f8_net_concat): K sources of one map side by side along C.  Mode i8 (concat_i8_kernel): src[k][i] is source i
+// in the int8 format of output form k (NHWC, Cs_src[i]-byte rows), the launch copies bytes and only q[k].ptr / bias_xor are read.  Mode i32
+// (concat_i32_kernel): src[0][i] is source i's int32 form (I32T), shifted left by shl[i] (wrapping), clamped to +-(2^31 - 1); out32 and q[] as AddArgs.
+constexpr int kMaxConcat = 8;              // = F8_MAX_CONCAT (include/f8net.h)
+struct ConcatArgs {
+    const void* src[2][kMaxConcat];
+    int32_t C[kMaxConcat], Cs_src[kMaxConcat], off[kMaxConcat], shl[kMaxConcat];   // real / padded channels of source i, its first output channel, its alignment shift
+    int32_t K, M, Cs;                      // sources, pixels N * H * W, padded output channels (the real ones: off[K - 1] + C[K - 1])
+    int32_t* out32;
+    QuantOut q[2];
 };
 
 struct OutArgs {                           // NHWC int32 -> NCHW int32 / float32
@@ -592,6 +605,9 @@ const char* add_kernel_name();
 hipError_t launch_add(const AddArgs& a, hipStream_t s);
 int input_inst(int C, int W, bool stem_only);                      // 1: input_stem4_kernel (the input's only form is the stem's NHWC4 copy), 0: input_kernel
 const char* input_kernel_name(int inst);
+int concat_inst(const ConcatArgs& a, bool i8);                     // f8_concat.hip.  0: concat_i32_kernel, 1: concat_i8_kernel<true> (16-byte vectors), 2: concat_i8_kernel<false>
+const char* concat_kernel_name(int inst);
+hipError_t launch_concat(const ConcatArgs& a, int inst, hipStream_t s);
 hipError_t launch_input(const InArgs& a, int inst, hipStream_t s);
 const char* output_kernel_name();
 hipError_t launch_output(const OutArgs& a, hipStream_t s);

@@ -88,7 +88,7 @@ enum Role { R_NONE, R_B0, R_B2, R_B4, R_SC };
 // The chain launches: bottleneck stage (f8_chain.hip; the 7x7 stage over clusters, f8_cchain.hip), BasicBlocks (f8_bchain.hip), BasicBlocks of a 7x7 x 512
 // stage over clusters of eight workgroups (option fuse_bchain7, f8_bcchain.hip), inverted residuals (f8_irchain.hip).  Independent of the block kind.
 enum ChainKind { C_NONE, C_STAGE, C_BASIC, C_BASIC_CLUSTER, C_IR };
-enum NodeKind { N_INPUT, N_CONV, N_ADD, N_MAXPOOL, N_AVGPOOL, N_LINEAR };
+enum NodeKind { N_INPUT, N_CONV, N_ADD, N_MAXPOOL, N_AVGPOOL, N_LINEAR, N_CONCAT };
 struct Node {
     int kind; int a = -1, b = -1; int out = -1;
     f8_conv_desc cd{};                 // conv / linear (as 1x1 conv)
@@ -99,6 +99,8 @@ struct Node {
     int relu = 0;                      // add
     int pk = 0, pstride = 0, ppad = 0; // maxpool
     int shift = 0;                     // avgpool
+    std::vector<int> srcs;             // concat: the operands in channel order (tensor ids; a = srcs[0])
+    bool concat_i8 = false;            // concat, pass 2: the byte-gather mode (every source in the output's int8 formats); false: sources in int32
     // planning
     int fused_into = -1;               // add: conv node that carries it
     int fused_add = -1;                // conv: add node carried
@@ -120,7 +122,7 @@ struct Node {
     size_t rc_off = 0, cc_off = 0; int ncc = 0;      // border-class tables (0 = single class)
     ConvTile tile{};
 };
-enum StepKind { S_INPUT, S_CONV, S_DW, S_ADD, S_MAXPOOL, S_AVGPOOL, S_REQUANT, S_OUTPUT, S_FUSED, S_STEMPOOL, S_IR, S_P12, S_CHAIN, S_BCHAIN, S_HEAD2, S_IRCHAIN, S_DWS, S_DWS7, S_IRK, S_GCONV };
+enum StepKind { S_INPUT, S_CONV, S_DW, S_ADD, S_MAXPOOL, S_AVGPOOL, S_REQUANT, S_OUTPUT, S_FUSED, S_STEMPOOL, S_IR, S_P12, S_CHAIN, S_BCHAIN, S_HEAD2, S_IRCHAIN, S_DWS, S_DWS7, S_IRK, S_GCONV, S_CONCAT };
 // The kernel of a step whose kind has several, chosen once by the step's emitter (pass 3); bind_step, run_step and f8_net_autotune switch on it.
 //   S_CONV:  conv_igemm (f8_kernels.hip), the LDS-patch 3x3 (f8_conv3x3.hip), conv1x1_wreg (f8_wreg.hip), conv1x1_wstat (f8_wstat.hip),
 //            conv3x3s2_wreg (f8_s2conv.hip), the 1x1 conv + average pool (f8_pool.hip), the classifier fc_dense (f8_fc.hip)
@@ -133,6 +135,9 @@ struct Step {
     int src_t = -1, src_f = -1;        // main input tensor / form
     int res_t = -1, res_f = -1;        // residual (conv) or second operand (add)
     int src2_t = -1, src2_f = -1;      // dual GEMM: input of the second conv
+    // S_CONCAT reads K tensors and keeps them HERE, with src_t = res_t = src2_t = -1: code that asks what a step reads (lifetimes: layout_arena; users of the
+    // network input: let_stem_read_input) must look at cat_t as well as the three *_t above; step_chunk / for_each_launch index tensors[src_t] only for S_FUSED
+    std::vector<int> cat_t, cat_f[2];  // S_CONCAT: the source tensors and their forms — i8 mode: cat_f[k] = the sources in the format of output form out.f8[k]; i32 mode: cat_f[0] = their int32 forms
     OutSel out;
     int acc_shl = 0, res_shl = 0, relu0 = 0, relu1 = 0;
     bool dense = false;
@@ -143,7 +148,7 @@ struct Step {
     double bytes_per_img = 0, bytes_const = 0, ops_per_img = 0;
     double valu_per_img = 0;           // ESSENTIAL vector lane-operations per image (f8_net_launch_valu): what the reference's semantics need once the MFMAs are done
     // the launcher's arguments as far as the plan decides them (bind_step); run_step copies them and adds what the run decides
-    std::variant<std::monostate, ConvArgs, StemPoolArgs, FusedArgs, ChainArgs, BChainArgs, BCChainArgs, IRArgs, IRKArgs, IRChainArgs, DwsArgs, Dws7Args, DwArgs, GConvArgs, AddArgs, PoolArgs, AvgArgs, OutArgs> args;
+    std::variant<std::monostate, ConvArgs, StemPoolArgs, FusedArgs, ChainArgs, BChainArgs, BCChainArgs, IRArgs, IRKArgs, IRChainArgs, DwsArgs, Dws7Args, DwArgs, GConvArgs, AddArgs, PoolArgs, AvgArgs, OutArgs, ConcatArgs> args;
     int inst = 0;                      // the instance the launcher starts (the family's *_inst, f8_internal.h; bind_step)
     // S_CHAIN / S_BCHAIN: geometry, workgroups per image and resident per CU, the 7x7 cluster form (f8_cchain.hip)
     int C = 0, MID = 0, H = 0, W = 0, cin0 = 0, tiles = 0, wg_per_cu = 1; bool cluster = false;
@@ -271,6 +276,15 @@ static int64_t tensor_amax(f8_net* net, int t, int depth = 0) {
             const int sa = T.fl - net->tensors[nd.a].fl, sb = T.fl - net->tensors[nd.b].fl;      // out fraclen = the larger one (f8_net_add)
             constexpr int64_t cap = int64_t(1) << 40;       // the shifted operands stay below 2^41: no int64 overflow (an operand of 2^40 shifted by 31 would wrap)
             if (a >= 0 && b >= 0 && sa >= 0 && sb >= 0 && sa <= 31 && sb <= 31 && a <= (cap >> sa) && b <= (cap >> sb)) m = (a << sa) + (b << sb);
+        } else if (nd.kind == N_CONCAT) {                    // max over the operands of the aligned operand, under the same caps
+            constexpr int64_t cap = int64_t(1) << 40;
+            m = 0;
+            for (int x : nd.srcs) {
+                const int64_t a = tensor_amax(net, x, depth + 1);
+                const int sa = T.fl - net->tensors[x].fl;
+                if (a < 0 || sa < 0 || sa > 31 || a > (cap >> sa)) { m = -1; break; }
+                m = std::max(m, a << sa);
+            }
         }
     }
     if (m > (int64_t(1) << 40)) m = -1;
@@ -373,6 +387,7 @@ static const OptKey kOptKeys[] = {
     {"whole_batch_launches", "F8_WHOLE_BATCH_LAUNCHES", &Options::whole_batch_launches, 0, 1, true},
     {"tap_tiled", "F8_TAP_TILED", &Options::tap_tiled, 0, 1, true},
     {"grouped", "F8_GROUPED", &Options::grouped, 0, 2, true},
+    {"concat_i8", "F8_CONCAT_I8", &Options::concat_i8, 0, 1, true},
 };
 static const OptKey* find_opt(const char* key) {
     if (!key) return nullptr;
@@ -638,6 +653,32 @@ int f8_net_add(f8_net* net, int a, int b, int relu) {
     net->nodes[id].out = t;
     net->tensors[a].consumers.push_back(id);
     net->tensors[b].consumers.push_back(id);
+    return t;
+}
+
+static_assert(F8_MAX_CONCAT == kMaxConcat, "ConcatArgs holds F8_MAX_CONCAT sources");
+int f8_net_concat(f8_net* net, const int* srcs, int n) {
+    if (!net) return fail(F8_ERR_INVALID, "f8_net_concat: null net");
+    if (net->finalized) return fail(F8_ERR_STATE, "f8_net_concat: net already finalized");
+    if (!srcs || n < 2) return fail(F8_ERR_INVALID, "f8_net_concat: at least two operands (got %d)", srcs ? n : 0);
+    if (n > F8_MAX_CONCAT) return fail(F8_ERR_UNSUPPORTED, "f8_net_concat: at most %d operands (got %d)", F8_MAX_CONCAT, n);
+    int C = 0, fl = INT32_MIN, fl_min = INT32_MAX;
+    for (int i = 0; i < n; ++i) {
+        if (const int rc = check_t(net, srcs[i], "f8_net_concat")) return rc;
+        const Tensor &t = net->tensors[srcs[i]], &t0 = net->tensors[srcs[0]];
+        if (t.H != t0.H || t.W != t0.W) return fail(F8_ERR_INVALID, "f8_net_concat: operand %d is %d x %d, operand 0 is %d x %d", i, t.H, t.W, t0.H, t0.W);
+        C += t.C; fl = std::max(fl, t.fl); fl_min = std::min(fl_min, t.fl);
+    }
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < i; ++j)
+            if (srcs[i] == srcs[j]) return fail(F8_ERR_UNSUPPORTED, "f8_net_concat: operands must differ (tensor %d twice)", srcs[i]);
+    if (fl - fl_min > 31) return fail(F8_ERR_INVALID, "f8_net_concat: fraclen gap too large");
+    Node nd; nd.kind = N_CONCAT; nd.a = srcs[0]; nd.srcs.assign(srcs, srcs + n);
+    net->nodes.push_back(nd);
+    const int id = (int)net->nodes.size() - 1;
+    const int t = new_tensor(net, C, net->tensors[srcs[0]].H, net->tensors[srcs[0]].W, fl, id);
+    net->nodes[id].out = t;
+    for (int i = 0; i < n; ++i) net->tensors[srcs[i]].consumers.push_back(id);
     return t;
 }
 
@@ -1796,6 +1837,28 @@ static void plan_tensor_forms(f8_net* net) {
             case N_AVGPOOL:
                 if (nd.pool_host < 0) add_form(T[nd.a], FORM_I32, 0, 0);      // fused behind its conv (1i): the pool's input has no form
                 break;
+            case N_CONCAT: {
+                // Mode.  concat_i8: the output exists in one or two int8 forms and nothing else (no int32 reader, no network output), and
+                // requantising source i directly by n_i = n - (out.fl - fl_i) is the same function as aligning it and requantising by n: the aligned
+                // value neither wraps nor clamps (stream_bounded) and, for n > 0, the reference's `v + 2^(n-1)` stays below 2^31 on it.  Every source is
+                // then asked for the output's formats and the launch copies bytes.  Otherwise concat_i32: the sources' int32 forms, aligned in the launch.
+                Tensor& o = T[nd.out];
+                const int64_t amax = tensor_amax(net, nd.out);
+                int n8 = 0;
+                for (auto& F : o.forms) n8 += F.kind == FORM_I8;
+                bool i8 = opt.concat_i8 && n8 >= 1 && n8 <= 2 && (int)o.forms.size() == n8 && !is_output(net, nd.out) && stream_bounded(net, nd.out);
+                for (size_t f = 0; i8 && f < o.forms.size(); ++f) {
+                    const int n = o.forms[f].n;
+                    if (n > 0 && amax + (int64_t(1) << (n - 1)) > INT32_MAX) i8 = false;
+                    for (int x : nd.srcs) { const int ni = n - (o.fl - T[x].fl); if (ni < -31 || ni > 30) i8 = false; }
+                }
+                nd.concat_i8 = i8;
+                for (int x : nd.srcs) {
+                    if (!i8) { add_form(T[x], FORM_I32, 0, 0); continue; }
+                    for (size_t f = 0; f < o.forms.size(); ++f) add_form(T[x], FORM_I8, o.forms[f].n - (o.fl - T[x].fl), o.forms[f].sgn);
+                }
+                break;
+            }
             default: break;
         }
     }
@@ -2326,6 +2389,35 @@ static int emit_avgpool(f8_net* net, int i, Step& st, std::vector<int>* extra) {
     return F8_OK;
 }
 
+static int emit_concat(f8_net* net, int i, Step& st, std::vector<int>* extra) {
+    auto& T = net->tensors;
+    const Node& nd = net->nodes[i];
+    Tensor& o = T[nd.out];
+    st.kind = S_CONCAT;
+    st.cat_t = nd.srcs;
+    if (o.forms.empty()) add_form(o, FORM_I32, 0, 0);
+    select_outputs(net, nd.out, &st.out, extra);
+    const double px = (double)o.H * o.W;
+    if (nd.concat_i8) {                                   // (pass 2: one or two int8 forms and no other)
+        for (int k = 0; k < 2; ++k) {
+            if (st.out.f8[k] < 0) continue;
+            const Form& F = o.forms[st.out.f8[k]];
+            for (int x : nd.srcs) {
+                const int f = find_form(T[x], FORM_I8, F.n - (o.fl - T[x].fl), F.sgn);
+                if (f < 0) return fail(F8_ERR_STATE, "f8_net_finalize: planner bug: concat source t%d lacks the output's int8 form", x);
+                st.cat_f[k].push_back(f);
+            }
+        }
+        st.bytes_per_img = 2.0 * px * o.C * out_forms8(st);      // every real byte read once and written once, per form
+    } else {
+        for (int x : nd.srcs) st.cat_f[0].push_back(find_form(T[x], FORM_I32, 0, 0));
+        st.bytes_per_img = px * o.C * 4 + out_bytes(st, o, px);
+        st.valu_per_img = px * o.C * (2 + 3 * out_forms8(st));   // align + clamp per value, 3 per int8 value produced
+    }
+    st.name = (nd.concat_i8 ? "concat_i8:" : "concat_i32:") + tname(net, nd.out);
+    return F8_OK;
+}
+
 // the int8 forms of tensor t beyond the two its producer writes: stand-alone requants of its int32 form
 static void emit_requants(f8_net* net, int t, const std::vector<int>& extra) {
     for (int f : extra) {
@@ -2358,7 +2450,10 @@ static void let_stem_read_input(f8_net* net) {
         const Tensor& o = net->tensors[st.out.t];
         if (!only_stem_form(o) || o.C != 3 || !net->opt.fuse_input) continue;
         Step* stem = nullptr; int users = 0;
-        for (auto& s2 : net->steps) if (s2.src_t == st.out.t) { ++users; if (s2.kind == S_STEMPOOL || s2.kind == S_HEAD2) stem = &s2; }
+        for (auto& s2 : net->steps) {
+            if (s2.src_t == st.out.t) { ++users; if (s2.kind == S_STEMPOOL || s2.kind == S_HEAD2) stem = &s2; }
+            users += (int)std::count(s2.cat_t.begin(), s2.cat_t.end(), st.out.t);      // a concat that reads the input (it asks for another form: never reached today)
+        }
         if (stem && users == 1) {
             st.raw_input = stem->raw_input = true;
             stem->bytes_per_img += (double)o.C * o.H * o.W * 4 - (double)o.H * o.W * 4;      // int32 planes instead of the NHWC4 copy
@@ -2387,6 +2482,7 @@ static int emit_steps(f8_net* net, int max_batch) {
             case N_ADD: rc = emit_add(net, i, st, &extra); break;
             case N_MAXPOOL: rc = emit_maxpool(net, i, st, &extra); break;
             case N_AVGPOOL: rc = emit_avgpool(net, i, st, &extra); break;
+            case N_CONCAT: rc = emit_concat(net, i, st, &extra); break;
         }
         if (rc) return rc;
         net->steps.push_back(st);
@@ -2417,6 +2513,8 @@ static int layout_arena(f8_net* net, int max_batch) {
         touch(st.src_t, st.src_f, (int)si);
         touch(st.res_t, st.res_f, (int)si);
         touch(st.src2_t, st.src2_f, (int)si);
+        for (int k = 0; k < 2; ++k)
+            for (size_t j = 0; j < st.cat_f[k].size(); ++j) touch(st.cat_t[j], st.cat_f[k][j], (int)si);
         if (st.out.t >= 0 && !st.dense) {
             touch(st.out.t, st.out.f32, (int)si);
             touch(st.out.t, st.out.f8[0], (int)si);
@@ -2944,6 +3042,19 @@ static int bind_step(f8_net* net, Step& st) {
             snprintf(kb, sizeof kb, "%s", add_kernel_name());
             out_formats(a.q); st.args = a; break;
         }
+        case S_CONCAT: {
+            const Tensor& oT = T[nd.out];
+            ConcatArgs a{};
+            a.K = (int)st.cat_t.size(); a.Cs = oT.Cs;
+            int off = 0;
+            for (int i = 0; i < a.K; ++i) {
+                const Tensor& x = T[st.cat_t[i]];
+                a.C[i] = x.C; a.Cs_src[i] = x.Cs; a.off[i] = off; a.shl[i] = oT.fl - x.fl;
+                off += x.C;
+            }
+            snprintf(kb, sizeof kb, "%s", concat_kernel_name(st.inst = concat_inst(a, nd.concat_i8)));
+            out_formats(a.q); st.args = a; break;
+        }
         case S_MAXPOOL: {
             const Tensor& sT = T[st.src_t]; const Form& sF = sT.forms[st.src_f];
             const Tensor& oT = T[nd.out];
@@ -3348,6 +3459,16 @@ static int run_step(const f8_net* net, const RunIO& io, const Step& st, int n0, 
             a.M = N * sT.H * sT.W;
             fill_out(&a.out32, a.q);
             e = launch_add(a, s);
+            break;
+        }
+        case S_CONCAT: {
+            ConcatArgs a = std::get<ConcatArgs>(st.args);
+            for (int k = 0; k < 2; ++k)
+                for (size_t j = 0; j < st.cat_f[k].size(); ++j) a.src[k][j] = fp(T[st.cat_t[j]].forms[st.cat_f[k][j]]);
+            const Tensor& o = T[st.out.t];
+            a.M = N * o.H * o.W;
+            fill_out(&a.out32, a.q);
+            e = launch_concat(a, st.inst, s);
             break;
         }
         case S_MAXPOOL: {

@@ -94,6 +94,14 @@ class F8Net:
             self._L.f8_net_set_label(self._h, t, label.encode())
         return t
 
+    def concat(self, srcs, label=None):
+        """Channel concatenation of 2 .. 8 tensors of one map size, in order (f8_net_concat); fraclen = the largest operand fraclen."""
+        ids = (ctypes.c_int * len(srcs))(*[int(t) for t in srcs])
+        t = check(self._L.f8_net_concat(self._h, ids, len(srcs)))
+        if label:
+            self._L.f8_net_set_label(self._h, t, label.encode())
+        return t
+
     def maxpool(self, src, k=3, stride=2, pad=1, label=None):
         t = check(self._L.f8_net_maxpool(self._h, src, k, stride, pad))
         if label:

@@ -11,6 +11,7 @@ opset-11 vocabulary is written directly from the integer graph — per op the no
     residual join                  Pow/Cast/Mul, Add, Clip(-+2^31 as f32), Cast(i32) [, Relu, Cast]   (fix_resnet.py:40-54,77)
     head max-pool                  Cast(f32), MaxPool, Cast(i32)                     (fix_resnet.py:358-359)
     FXQAvgPool2d                   Cast(i64), ReduceSum(-1) x2, Cast(i32)            (fix_quant_ops.py:130-133)
+    channel concatenation          [Pow/Cast/Mul per operand at a smaller fraction length,] Concat(axis=1)
     x.view(x.size(0), -1)          Shape, Gather, Unsqueeze, Concat, Reshape         (fix_resnet.py:371)
     classifier                     Gemm(transB=1), Cast(f32)                         (fix_resnet.py:383)
 
@@ -162,6 +163,8 @@ def export_graph(ig: IntGraph) -> bytes:
             v = w.emit('Add', [name[o.src2], m] if o.swap else [m, name[o.src2]])   # `res += x`: res first
             v = w.emit('Clip', [v, w.const(-2147483647.0, np.float32), w.const(2147483647.0, np.float32)])
             y = w.cast(v, onnx_io.INT32)
+        elif o.kind == 'concat':                                     # torch.cat(dim=1); `x << k` as in the residual join
+            y = w.emit('Concat', [name[s] if k == 0 else w.emit('Mul', [name[s], w.pow2(k)]) for s, k in zip(o.srcs, o.shifts)], {'axis': 1})
         elif o.kind == 'maxpool':
             v = w.emit('MaxPool', [w.cast(name[o.src], onnx_io.FLOAT)],
                        {'ceil_mode': 0, 'dilations': [1, 1], 'kernel_shape': [o.kernel] * 2, 'pads': [o.pad] * 4,

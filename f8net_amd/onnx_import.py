@@ -36,7 +36,7 @@ class OnnxImportError(ValueError):
 
 @dataclass
 class IntOp:
-    kind: str                      # input | conv | linear | add | maxpool | avgpool
+    kind: str                      # input | conv | linear | add | maxpool | avgpool | concat
     src: int = -1                  # tensor id (index into IntGraph.ops)
     src2: int = -1                 # add: the operand that is NOT shifted
     weight: np.ndarray = None
@@ -52,6 +52,8 @@ class IntOp:
     key: str = ''                  # state_dict key of the layer ('head.0', 'stage_0_layer_0.body.0', ...)
     shape: tuple = None            # input: (C, H, W)
     dilation: int = 1              # conv: spacing of the kernel's taps (ONNX `dilations`, both equal)
+    srcs: list = None              # concat: the operands in channel order (tensor ids)
+    shifts: list = None            # concat: k_i of `srcs[i] << k_i`, the alignment to the largest fraclen (the smallest is 0)
 
 
 @dataclass
@@ -103,6 +105,9 @@ class IntGraph:
             elif o.kind == 'add':
                 eq(o.src2, o.src, o.shift)
                 eq(t, o.src2, 0)
+            elif o.kind == 'concat':
+                for s, k in zip(o.srcs, o.shifts):
+                    eq(t, s, k)
             elif o.kind == 'maxpool':
                 eq(t, o.src, 0)
             elif o.kind == 'avgpool':
@@ -168,6 +173,8 @@ class IntGraph:
                                     quant_input=o.shift is not None, label=o.key)
             elif o.kind == 'add':
                 ids[t] = net.add(ids[o.src], ids[o.src2], relu=o.relu)
+            elif o.kind == 'concat':                          # (the library aligns to the largest fraclen: V[t] = V[s] + k, min k = 0)
+                ids[t] = net.concat([ids[s] for s in o.srcs])
             elif o.kind == 'maxpool':
                 ids[t] = net.maxpool(ids[o.src], o.kernel, o.stride, o.pad)
             elif o.kind == 'avgpool':
@@ -294,6 +301,25 @@ def import_graph(model, input_signed=False) -> IntGraph:
                 ig.output_float = a['to'] == onnx_io.FLOAT
         elif op == 'Pow':
             val[out] = ('const', float(const(nd.inputs[0], 'Pow')) ** const(nd.inputs[1], 'Pow'))
+        elif op == 'Concat' and any(val.get(s, ('?',))[0] in ('T', 'mul') for s in nd.inputs):
+            # torch.cat(dim=1) of activations; an operand at a smaller fraction length arrives as Mul(x, 2^k), the alignment of the residual join
+            if a.get('axis') not in (1, -3):
+                raise OnnxImportError(f'Concat of activations along axis {a.get("axis")}: only the channel axis (1)')
+            srcs, shifts = [], []
+            for s in nd.inputs:
+                e = val.get(s, ('?',))
+                if e[0] == 'T':
+                    srcs.append(e[1])
+                    shifts.append(0)
+                elif e[0] == 'mul' and e[1][0] == 'T':
+                    srcs.append(e[1][1])
+                    shifts.append(_pow2(e[2], 'Concat operand scale'))
+                else:
+                    raise OnnxImportError(f'Concat operand {s!r} is neither a layer result nor one scaled by a power of two')
+            if min(shifts) != 0:
+                raise OnnxImportError('Concat: every operand is scaled (the result takes the largest operand fraction length)')
+            ig.ops.append(IntOp('concat', src=srcs[0], srcs=srcs, shifts=shifts))
+            val[out] = ('T', len(ig.ops) - 1)
         elif op in ('Shape', 'Gather', 'Unsqueeze', 'Concat'):
             val[out] = ('opaque',)                                 # the `x.view(x.size(0), -1)` plumbing before the FC
         elif op == 'Reshape':

@@ -144,6 +144,19 @@ int f8_net_conv_dilated(f8_net* net, int src, const f8_conv_desc* desc, int dila
 /* Residual join of IntBlock.forward (fix_resnet.py:40-54 / :63-76) [+ post_relu :77]. */
 int f8_net_add(f8_net* net, int a, int b, int relu);
 
+/* Channel concatenation (torch.cat(dim=1) of an ASPP head, an Inception module, a DenseNet block, a U-Net / FPN skip): out = concat(srcs[0] ..
+ * srcs[n - 1]) along C in operand order, 2 <= n <= F8_MAX_CONCAT operands of the same H and W.  out.C = sum of C_i; fraclen = the largest operand
+ * fraclen; an operand with a smaller one is aligned as the residual join aligns it (fix_resnet.py:40-54 with a zero partner): shifted left by the
+ * difference with the reference's int32 wrap, clamped to +-(2^31 - 1).  No ReLU, no rounding; a consumer with quant_input = 1 requantises the result
+ * from that fraclen as it does any tensor.  Returns the tensor id.  F8_ERR_INVALID: n < 2, a bad tensor id, operands of different H / W, fraclens more
+ * than 31 apart; F8_ERR_UNSUPPORTED: n > F8_MAX_CONCAT, the same tensor twice; F8_ERR_STATE after finalize.
+ * The plan runs it as one launch of f8_concat.hip, in one of two modes shown by its token: `concat_i8:` — the result is read in at most two int8
+ * formats and by nothing else, and its values are provably far enough from 2^31 — has every operand's producer write the result's formats and
+ * copies bytes; `concat_i32:` reads the operands' int32 forms and aligns in the launch (option concat_i8 = 0: always).  Same values either way.
+ * A tensor read by a concat exists in device memory: no fused block or chain launch keeps it on chip (it cuts a launch as an output tap does). */
+#define F8_MAX_CONCAT 8
+int f8_net_concat(f8_net* net, const int* srcs, int n);
+
 /* Head max-pool nn.MaxPool2d(k, stride, pad) via the float detour (fix_resnet.py:358-359) or
  * FXQMaxPool2d (fix_quant_ops.py:150-157); exact integer max. */
 int f8_net_maxpool(f8_net* net, int src, int kernel, int stride, int pad);
@@ -301,7 +314,10 @@ int f8_net_check(f8_net* net);
  *               pad 0 / 1, cin == cout, cin / groups in {2, 4, 8, 16, 32} run f8::gconv3x3_kernel, f8_gconv.hip, plan token gconv3x3s{S}:,
  *               every other grouped conv runs as the DENSE EXPANSION, the plain conv kernels over block-diagonal weights, plan token
  *               gconv{k}x{k}s{S}_dense:; 2: accepted, always the dense expansion.  Set it before the f8_net_conv call that adds the
- *               grouped conv.  Same values in both, bit for bit; depthwise convs keep their own rules and kernels whatever it says)
+ *               grouped conv.  Same values in both, bit for bit; depthwise convs keep their own rules and kernels whatever it says),
+ *               concat_i8 (default 1: a concat whose result is read in at most two int8 formats and by nothing else, with values the planner can
+ *               bound, runs f8::concat_i8_kernel on its operands' int8 forms, plan token concat_i8:; 0: every concat runs f8::concat_i32_kernel on
+ *               their int32 forms, token concat_i32:.  Same values either way, bit for bit)
  *   scheduling: chunk56 / chunk28 / chunk14 (images per chunk of the fused blocks; -1 = derived from chunk_budget_mb, 0 = whole
  *               batch), chunk_budget_mb (memory-side cache a chunk's int32 stream may occupy), chunk_ds, chunk_opener,
  *               split_streams, graph, stagger, stagger_pipelined, stem_wpc, stem_grid_div (row-walking head on 1 / n of the CUs; 0 = by output form), check_device, check_input_range, pipeline_depth (2..4 runs in flight),

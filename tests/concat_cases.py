@@ -1,0 +1,382 @@
+"""Case table, reference and graph builder of the tests of channel concatenation (f8_net_concat / `F8Net.concat`, f8_concat.hip):
+tests/test_concat_plan.py (acceptance, refusals, mode tokens, kernel symbols, forms, launch_info, fused nets, the ONNX round trip; no GPU) and
+tests/test_gpu_concat.py (every case on both legs, bit for bit on the device).  No test functions here.
+
+The reference.  `concat_align(xs, fls)`: the result's fraclen is the largest operand fraclen and operand i contributes what the residual join's
+alignment makes of it next to a zero partner, `oracle.add_align(zeros, x_i, out_fl, fl_i)` — shift left with the int32 wrap, clamp to
++-(2^31 - 1) — so nothing of that arithmetic is restated here; then `np.concatenate` along C.  `oracle/` stays as it is: `graph_forward` below walks
+an imported ONNX graph, handles `concat` itself and hands every other op kind to the oracle's op-level functions.
+
+Unless a builder says otherwise a case is  input (8 channels, 0 .. 255, fraclen 8) -> K 1x1 producer convs that read it as it is, couts C_i, weight
+fraclens chosen to give the stated output fraclens -> concat -> readers: one 32-output 1x1 conv per (input_fl, signed), summed (as dil_cases).
+
+The expected mode token and the ALIGNED flag of the kernel symbol of every case are WRITTEN BY HAND (the rule: DESIGN.md 4.5i); nothing here asks
+the planner for them."""
+import functools
+
+import numpy as np
+
+import dil_cases
+from dil_cases import FUSE_ALL  # noqa: F401  (the tests take it from here)
+from f8net_amd import synth
+from ir_cases import _b, _w
+from oracle import oracle
+
+X_FL = 8
+
+
+def concat_align(xs, fls):
+    """[(N, C_i, H, W) int32], [fraclen_i] -> (concatenation at the largest fraclen, that fraclen)."""
+    fl = max(fls)
+    parts = []
+    for x, f in zip(xs, fls):
+        y, got = oracle.add_align(np.zeros_like(x), x, fl, f)
+        assert got == fl
+        parts.append(y)
+    return np.concatenate(parts, axis=1), fl
+
+
+class _Graph(dil_cases._Graph):
+    """ir_cases._Graph (through dil_cases: `dilation=`, record=False) with concat and the two pools."""
+
+    def conv(self, t, w, b, *, dilation=1, pad, stride=1, **kw):
+        """A 3x3 at dilation d, pad d, stride 1 on a map of at most m + 1 pixels a side, m < d: the taps further than m from the centre only ever
+        meet padding, so the stuffed (2d + 1)-square kernel cropped to its central (2m + 1) square, at pad m, is the same conv (ASPP's d = 18 on a
+        6 x 6 map: 11 x 11 taps instead of 37 x 37 for the reference to walk)."""
+        x, fl = self.v[t]
+        d, m = dilation, max(x.shape[2], x.shape[3]) - 1
+        if not (d > 1 and w.shape[2] == 3 and pad == d and stride == 1 and m < d and kw['groups'] == 1 and kw.get('quant_input', True)):
+            return super().conv(t, w, b, dilation=dilation, pad=pad, stride=stride, **kw)
+        o = self._id(lambda: self.net.conv(t, w, b, stride=1, pad=pad, groups=1, weight_fl=kw['weight_fl'], input_fl=kw['input_fl'],
+                                           input_signed=kw['input_signed'], quant_input=True, relu=kw['relu'], dilation=d))
+        xq = oracle.requant(x, kw['input_fl'], fl, kw['input_signed'])
+        y = oracle.conv2d(xq, np.ascontiguousarray(dil_cases.stuffed(w, d)[:, :, d - m:d + m + 1, d - m:d + m + 1]), b, 1, m, 1)
+        self.raw[o] = y
+        self.v[o] = (oracle.relu(y) if kw['relu'] else y, kw['input_fl'] + kw['weight_fl'])
+        return o
+
+    def concat(self, ts, label=None):
+        o = self._id(lambda: self.net.concat(ts, label=label))
+        self.v[o] = concat_align([self.v[t][0] for t in ts], [self.v[t][1] for t in ts])
+        return o
+
+    def maxpool(self, t, k, stride, pad):
+        o = self._id(lambda: self.net.maxpool(t, k, stride, pad))
+        self.v[o] = (oracle.maxpool(self.v[t][0], k, stride, pad), self.v[t][1])
+        return o
+
+    def avgpool_sum(self, t, shift=oracle.AVGPOOL_SHIFT):
+        o = self._id(lambda: self.net.avgpool_sum(t, shift))
+        y = oracle.avgpool_sum(self.v[t][0])
+        self.v[o] = (y.reshape(y.shape[0], y.shape[1], 1, 1), self.v[t][1] + shift)
+        return o
+
+    def output(self, t, as_float=False):
+        if self.record:
+            self.net.output(t, as_float=as_float)
+
+
+def producer(g, t, k, cout, n, *, w_fl, relu, in_fl=X_FL, in_signed=False, quant_input=False, kernel=1, seed=0, dilation=1):
+    """Conv number k of a case: `cout` outputs from tensor t, scaled so that a right shift by n (the reader's, less the operand's alignment)
+    fills 8 bits: accumulators around 2^n x 100 where 8-bit weights can reach that."""
+    cin = g.v[t][0].shape[1]
+    taps = kernel * kernel
+    sig = float(np.clip(2.0 ** n * 100 / (128 * (cin * taps) ** 0.5), 0.4, 40.0))
+    w = _w(100 + 7 * k + seed, (cout, cin, kernel, kernel), sig)
+    b = _b(200 + 7 * k + seed, cout, 2.0 ** n * 20, 2.0 ** n * 40 if relu else 0.0)
+    return g.conv(t, w, b, pad=dilation * (kernel // 2), groups=1, weight_fl=w_fl, input_fl=in_fl, input_signed=in_signed, relu=relu,
+                  quant_input=quant_input, dilation=dilation)
+
+
+def readers(g, t, fmts):
+    """One 32-output 1x1 conv per (fraclen, signed) over tensor t, summed."""
+    out = None
+    C = g.v[t][0].shape[1]
+    for k, (fl, sgn) in enumerate(fmts):
+        r = g.conv(t, _w(90 + k, (32, C, 1, 1), 8.0), None, pad=0, groups=1, weight_fl=6, input_fl=fl, input_signed=sgn, relu=False, label=f'reader{k}')
+        out = r if out is None else g.add(out, r)
+    return out
+
+
+# ---- the builders.  Each returns (output tensor ids in output order, [concat tensor ids])
+def _plain(g, x0, c):
+    """K producers -> concat -> readers (or the concat itself as the output)."""
+    fmts = c['readers']
+    shift = (max(c['w_fl']) + X_FL) - (fmts[0][0] if fmts else 4)            # the first reader's requant shift of the concat
+    ps = [producer(g, x0, k, ci, shift - (max(c['w_fl']) - wf), w_fl=wf, relu=c['relu']) for k, (ci, wf) in enumerate(zip(c['C'], c['w_fl']))]
+    cat = g.concat(ps, label='cat')
+    if not fmts:
+        g.output(cat, as_float=c.get('as_float', False))
+        return [cat], [cat]
+    out = readers(g, cat, fmts)
+    g.output(out)
+    return [out], [cat]
+
+
+def _vec(g, x0, c):
+    """[C, 1, 1] tensors: the input's average pool (fraclen 14) -> producers that requantise it to unsigned fraclen 8 (shift 6) -> concat -> reader."""
+    p = g.avgpool_sum(x0)
+    ps = [producer(g, p, k, ci, 9, w_fl=5, relu=True, quant_input=True) for k, ci in enumerate(c['C'])]
+    cat = g.concat(ps, label='cat')
+    out = readers(g, cat, c['readers'])
+    g.output(out)
+    return [out], [cat]
+
+
+def _to_add(g, x0, c):
+    """concat(32, 32) joined with a 64-channel conv of the input: the join reads int32."""
+    ps = [producer(g, x0, k, 32, 9, w_fl=5, relu=True) for k in range(2)]
+    cat = g.concat(ps, label='cat')
+    other = producer(g, x0, 5, 64, 8, w_fl=4, relu=False)                  # fraclen 12 against 13: the join shifts it by 1
+    out = readers(g, g.add(cat, other, relu=True), [(4, False)])
+    g.output(out)
+    return [out], [cat]
+
+
+def _to_pool(g, x0, c):
+    """concat(32, 17) read by the average pool (int32; output 1) and by a 3 / 1 / 1 max-pool with one int8 reader (output 0)."""
+    ps = [producer(g, x0, k, ci, 9, w_fl=5, relu=True) for k, ci in enumerate(c['C'])]
+    cat = g.concat(ps, label='cat')
+    out = readers(g, g.maxpool(cat, 3, 1, 1), [(4, False)])
+    g.output(out)
+    pooled = g.avgpool_sum(cat)
+    g.output(pooled)
+    return [out, pooled], [cat]
+
+
+def _raw(g, x0, c):
+    """The net input itself (8 channels up to +-2^28 at fraclen 2) next to a conv of it at fraclen 9: nothing bounds the input, and its alignment
+    shift of 7 wraps and clamps."""
+    p = producer(g, x0, 0, 24, 5, w_fl=9, relu=False, in_fl=0, in_signed=True, quant_input=True)
+    cat = g.concat([x0, p], label='cat')
+    out = readers(g, cat, [(4, True)])
+    g.output(out)
+    return [out], [cat]
+
+
+def _nested(g, x0, c):
+    """DenseNet: 64 channels, then four times a 3x3 conv (32 outputs, fraclen 12) of the running concat (fraclen 13) appended to it.  The convs read
+    it at unsigned fraclen 4 and 3 in turn, so every inner concat is a source in two formats."""
+    run = producer(g, x0, 0, 64, 9, w_fl=5, relu=True)
+    cats = []
+    for k in range(4):
+        fl = 4 - (k & 1)
+        grow = producer(g, run, 1 + k, 32, 8, w_fl=12 - fl, relu=True, in_fl=fl, quant_input=True, kernel=3)
+        run = g.concat([run, grow], label=f'dense{k}')
+        cats.append(run)
+    out = readers(g, run, [(4, False)])
+    g.output(out)
+    return [out], cats
+
+
+def _shared(g, x0, c):
+    """concat(A, B) and concat(B, C): B is read by two concats, A also by a conv in another format (signed fraclen 3)."""
+    A, B, C = (producer(g, x0, k, 32, 9, w_fl=5, relu=False) for k in range(3))
+    c1, c2 = g.concat([A, B], label='cat1'), g.concat([B, C], label='cat2')
+    out = g.add(readers(g, c1, [(4, False)]), readers(g, c2, [(4, False)]))
+    side = g.conv(A, _w(95, (32, 32, 1, 1), 8.0), None, pad=0, groups=1, weight_fl=6, input_fl=3, input_signed=True, relu=False)
+    out = g.add(out, side)
+    g.output(out)
+    return [out], [c1, c2]
+
+
+def _inception(g, x0, c):
+    """Inception-3a on 192 input channels: 1x1 (64); 1x1 (96) -> 3x3 (128); 1x1 (16) -> 5x5 (32, a plain conv); max-pool 3 / 1 / 1 -> 1x1 (32)."""
+    b1 = producer(g, x0, 0, 64, 9, w_fl=5, relu=True)
+    b2 = producer(g, producer(g, x0, 1, 96, 9, w_fl=5, relu=True), 2, 128, 9, w_fl=9, relu=True, in_fl=4, quant_input=True, kernel=3)
+    b3 = producer(g, producer(g, x0, 3, 16, 9, w_fl=5, relu=True), 4, 32, 9, w_fl=9, relu=True, in_fl=4, quant_input=True, kernel=5)
+    b4 = producer(g, g.maxpool(x0, 3, 1, 1), 5, 32, 9, w_fl=5, relu=True)
+    cat = g.concat([b1, b2, b3, b4], label='inception_3a')
+    out = readers(g, cat, c['readers'])
+    g.output(out)
+    return [out], [cat]
+
+
+def aspp_head(g, t):
+    """DeepLab's ASPP without the image-pooling branch on tensor t: a 1x1 and three 3x3 at dilation 6 / 12 / 18, 64 outputs each, read at unsigned
+    fraclen 4 -> concat -> 1x1 projection to 64 (its int32 result is the head's output).  Returns (projection, concat)."""
+    bs = [producer(g, t, 0, 64, 5, w_fl=5, relu=True, in_fl=4, quant_input=True)]
+    bs += [producer(g, t, 1 + k, 64, 5, w_fl=5, relu=True, in_fl=4, quant_input=True, kernel=3, dilation=d) for k, d in enumerate((6, 12, 18))]
+    cat = g.concat(bs, label='aspp.cat')
+    return producer(g, cat, 6, 64, 9, w_fl=5, relu=True, in_fl=4, quant_input=True), cat
+
+
+def _gapneg(g, x0, c):
+    """Operands whose own shift is NEGATIVE: the producers read the input at lower fraclens (c['fmt']: (input_fl, weight_fl) per operand, input_fl 8 =
+    as it is), so that n_i = n - (out.fl - fl_i) < 0 for the operands below the reader's fraclen — their producers write through the left-shift branch."""
+    fls = [i + w for i, w in c['fmt']]
+    n = max(fls) - c['readers'][0][0]
+    ps = []
+    for k, (ci, (i, w)) in enumerate(zip(c['C'], c['fmt'])):
+        ni = n - (max(fls) - (i + w))
+        cin = g.v[x0][0].shape[1]
+        # 0 .. 255 >> (8 - i) in, times weights around +-2, summed over 8 channels: results that fill 8 bits once shifted by -ni
+        wt = _w(300 + k, (ci, cin, 1, 1), float(np.clip(2.0 ** (ni + (8 - i)) * 0.3, 0.5, 20.0)))
+        ps.append(g.conv(x0, wt, _b(310 + k, ci, 2.0 ** max(ni, 0) * 10, 2.0 ** max(ni, 0) * 20), pad=0, groups=1, weight_fl=w, input_fl=i, input_signed=False, relu=True,
+                         quant_input=i != X_FL))
+    cat = g.concat(ps, label='cat')
+    out = readers(g, cat, c['readers'])
+    g.output(out)
+    return [out], [cat]
+
+
+def _case(C, H, W, N, mode, aligned, build=_plain, **kw):
+    """mode / aligned: the expected token and kernel instance with option concat_i8 = 1, by hand."""
+    c = dict(C=list(C), H=H, W=W, N=N, mode=mode, aligned=aligned, build=build, w_fl=[5] * len(C), relu=True, readers=[(4, False)], cin=8, x_fl=X_FL)
+    c.update(kw)
+    return c
+
+
+I8, I32 = 'concat_i8:', 'concat_i32:'
+CASES = {
+    'aligned2': _case((32, 64), 8, 8, 2, I8, True),
+    'aligned5': _case((64,) * 5, 6, 6, 2, I8, True, relu=False, readers=[(4, True)]),
+    'k8': _case((16,) * 8, 4, 4, 1, I8, True),                                  # offsets multiples of 16, not of 32
+    'off8': _case((24, 40), 8, 8, 2, I8, False),
+    'bytes': _case((3, 5, 9), 5, 5, 3, I8, False, cin=3),                       # 17 real channels, 15 pad channels; 75 pixels
+    'shuffle': _case((58, 58), 7, 7, 3, I8, False),                             # 147 pixels; pad 12
+    'straddle': _case((17, 32, 15), 7, 7, 2, I8, False),
+    'vec': _case((40, 24), 7, 7, 4, I8, False, build=_vec),                     # the concat's map is 1 x 1: M = 4
+    # operand fraclens 14 / 11 / 8, the reader at unsigned fraclen 8: n = 6 and n_i = 6, 3, 0
+    'gap': _case((32, 32, 32), 8, 8, 2, I8, True, w_fl=[6, 3, 0], readers=[(8, False)]),
+    # operand fraclens 11 / 7 / 4, the reader at unsigned fraclen 8: n = 3 and n_i = 3, -1, -4 (0 < n, n_i < 0)
+    'gapneg': _case((32, 32, 32), 8, 8, 2, I8, True, build=_gapneg, fmt=[(8, 3), (5, 2), (4, 0)], readers=[(8, False)]),
+    # operand fraclens 8 / 6 / 4, the reader at fraclen 8: n = 0 and n_i = 0, -2, -4 (n <= 0: both sides shift left)
+    'gapneg0': _case((32, 32, 32), 8, 8, 2, I8, True, build=_gapneg, fmt=[(6, 2), (5, 1), (4, 0)], readers=[(8, False)]),
+    'twoforms': _case((32, 48), 8, 8, 2, I8, True, relu=False, readers=[(3, True), (4, False)]),
+    'threeforms': _case((32, 48), 8, 8, 2, I32, None, relu=False, readers=[(3, True), (4, False), (5, False)]),
+    'to_add': _case((32, 32), 8, 8, 2, I32, None, build=_to_add),
+    'to_out': _case((24, 40), 7, 7, 3, I32, None, readers=None),
+    'to_out_f32': _case((24, 40), 7, 7, 3, I32, None, readers=None, as_float=True),
+    'to_pool': _case((32, 17), 7, 7, 2, I32, None, build=_to_pool),
+    'raw': _case((8, 24), 6, 6, 2, I32, None, build=_raw, x_fl=2, raw=True),
+    'nested': _case((64, 32, 32, 32, 32), 8, 8, 2, I8, True, build=_nested),
+    'shared': _case((32, 32, 32), 8, 8, 2, I8, True, build=_shared),
+    'inception': _case((64, 128, 32, 32), 12, 12, 2, I8, True, build=_inception, cin=192),
+}
+I8_CASES = [k for k, c in CASES.items() if c['mode'] == I8]
+
+
+def make_input(name, n=None):
+    c = CASES[name]
+    shape = (n or c['N'], c['cin'], c['H'], c['W'])
+    if c.get('raw'):                                                           # up to +-2^28, and a band of small values
+        x = synth.rand_uniform_int(5, f'catx{name}', shape, -2 ** 28, 2 ** 28).astype(np.int64)
+        small = synth.rand_uniform_int(6, f'cats{name}', shape, -300, 300).astype(np.int64)
+        x = np.where(small % 3 == 0, small, x)
+        x.reshape(-1)[:4] = [2 ** 28, -2 ** 28, 2 ** 24, -2 ** 24]           # 2^24 << 7 = 2^31 wraps to -2^31, which the clamp moves
+        return x.astype(np.int32)
+    return synth.rand_uniform_int(5, f'catx{name}', shape, 0, 255).astype(np.int32)
+
+
+def build_graph(name, x, record=True):
+    """Returns (graph, output ids, concat ids)."""
+    c = CASES[name]
+    g = _Graph(x, c['x_fl'], record=record)
+    outs, cats = c['build'](g, next(iter(g.v)), c)
+    return g, outs, cats
+
+
+@functools.lru_cache(maxsize=None)
+def reference(name):
+    """(graph, output ids, concat ids) of the case over N + 1 images, evaluated on the reference alone, once; nothing may write into its arrays."""
+    return build_graph(name, make_input(name, CASES[name]['N'] + 1), record=False)
+
+
+def plan(name, x, max_batch=None, **opts):
+    g, outs, cats = build_graph(name, x)
+    for k, v in opts.items():
+        g.net.set_option(k, v)
+    g.net.finalize(max_batch or x.shape[0])
+    return g, outs, cats
+
+
+def concat_lines(net):
+    """[(launch index, plan token 'concat_i8:' / 'concat_i32:', kernel symbol)] of the handle's concat launches, in launch order."""
+    out = []
+    for i in range(net.num_launches):
+        tok = net.launch_info(i, 1)[0].split(':')[0] + ':'
+        if tok.startswith('concat_'):
+            out.append((i, tok, net.launch_kernel(i)))
+    return out
+
+
+def symbol(mode, aligned):
+    return 'f8::concat_i32_kernel' if mode == I32 else f'f8::concat_i8_kernel<{"true" if aligned else "false"}>'
+
+
+# ---- the walker of an imported graph (oracle.graph_forward knows no concat)
+def graph_forward(ig, x, input_fraclen=None):
+    V, layer = ig.solve_fraclens(input_fraclen)
+    t = {}
+    for i, o in enumerate(ig.ops):
+        if o.kind == 'input':
+            t[i] = np.ascontiguousarray(x, dtype=np.int32)
+        elif o.kind == 'conv':
+            s = t[o.src]
+            if o.shift is not None:
+                s = oracle.requant(s, layer[i][0], V[o.src], o.signed)
+            y = oracle.conv2d(s, dil_cases.stuffed(o.weight, o.dilation), o.bias, o.stride, o.pad, o.groups)
+            t[i] = oracle.relu(y) if o.relu else y
+        elif o.kind == 'add':
+            y, fl = oracle.add_align(t[o.src], t[o.src2], V[o.src], V[o.src2])
+            assert fl == V[i]
+            t[i] = oracle.relu(y) if o.relu else y
+        elif o.kind == 'maxpool':
+            t[i] = oracle.maxpool(t[o.src], o.kernel, o.stride, o.pad)
+        elif o.kind == 'concat':
+            t[i], fl = concat_align([t[s] for s in o.srcs], [V[s] for s in o.srcs])
+            assert fl == V[i] and [V[i] - V[s] for s in o.srcs] == list(o.shifts)
+        else:
+            raise ValueError(o.kind)
+    return t[ig.output]
+
+
+def int_graph(name):
+    """The case as an IntGraph, op for op what build_graph records (plain-conv / add / concat / maxpool cases whose first output is the only one)."""
+    from f8net_amd.onnx_import import IntGraph, IntOp
+    c = CASES[name]
+    ig = IntGraph(input_signed=False)
+    ig.ops.append(IntOp('input', shape=(c['cin'], c['H'], c['W'])))
+
+    class _Rec(_Graph):
+        def __init__(self, x, fl):
+            super().__init__(x, fl, record=False)
+            self.ids = {0: 0}
+
+        def conv(self, t, w, b, *, stride=1, pad, groups, weight_fl, input_fl, input_signed, relu, label=None, quant_input=True, dilation=1, w_eval=None):
+            o = super().conv(t, w, b, stride=stride, pad=pad, groups=groups, weight_fl=weight_fl, input_fl=input_fl, input_signed=input_signed, relu=relu,
+                             quant_input=quant_input, dilation=dilation)
+            ig.ops.append(IntOp('conv', src=self.ids[t], weight=np.asarray(w, np.int32), bias=np.zeros(w.shape[0], np.int32) if b is None else np.asarray(b, np.int32),
+                                stride=stride, pad=pad, groups=groups, kernel=w.shape[2], shift=(self.v[t][1] - input_fl) if quant_input else None,
+                                signed=input_signed, relu=relu, key=f'layer{len(ig.ops)}', dilation=dilation))
+            self.ids[o] = len(ig.ops) - 1
+            return o
+
+        def add(self, a, b, relu=False):
+            o = super().add(a, b, relu=relu)
+            fa, fb = self.v[a][1], self.v[b][1]
+            s, s2 = (a, b) if fa <= fb else (b, a)                    # src is the operand that shifts
+            ig.ops.append(IntOp('add', src=self.ids[s], src2=self.ids[s2], shift=abs(fa - fb), relu=relu, swap=s == b))
+            self.ids[o] = len(ig.ops) - 1
+            return o
+
+        def maxpool(self, t, k, stride, pad):
+            o = super().maxpool(t, k, stride, pad)
+            ig.ops.append(IntOp('maxpool', src=self.ids[t], kernel=k, stride=stride, pad=pad))
+            self.ids[o] = len(ig.ops) - 1
+            return o
+
+        def concat(self, ts, label=None):
+            o = super().concat(ts)
+            fl = self.v[o][1]
+            ig.ops.append(IntOp('concat', src=self.ids[ts[0]], srcs=[self.ids[t] for t in ts], shifts=[fl - self.v[t][1] for t in ts]))
+            self.ids[o] = len(ig.ops) - 1
+            return o
+
+    x = make_input(name)
+    g = _Rec(x, c['x_fl'])
+    outs, _ = c['build'](g, 0, c)
+    ig.output = g.ids[outs[0]]
+    ig.output_float = False
+    return ig, g, outs[0]
