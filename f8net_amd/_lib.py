@@ -50,6 +50,7 @@ SYMBOLS = [
     ('f8_net_conv_dilated', _i, [_vp, _i, ctypes.POINTER(ConvDesc), _i, _vp, _vp]),
     ('f8_net_add', _i, [_vp, _i, _i, _i]),
     ('f8_net_concat', _i, [_vp, ctypes.POINTER(ctypes.c_int), _i]),
+    ('f8_net_upsample', _i, [_vp, _i, _i, _i, _i]),
     ('f8_net_maxpool', _i, [_vp, _i, _i, _i, _i]),
     ('f8_net_avgpool_sum', _i, [_vp, _i, _i]),
     ('f8_net_linear', _i, [_vp, _i, ctypes.POINTER(LinearDesc), _vp, _vp]),

@@ -73,6 +73,7 @@ struct Options {
     int grouped = 0;             // grouped convs (1 < groups < cin): 0 = refused by f8_net_conv; 1 = accepted, on gconv3x3_kernel (f8_gconv.hip) where it applies and as the
                                  // dense expansion (the plain conv kernels over block-diagonal weights) elsewhere; 2 = accepted, always the dense expansion
     int concat_i8 = 1;           // f8_net_concat: 1 = the byte-gather mode where it is exact (every source written in the output's int8 formats, f8_concat.hip); 0 = always the int32 mode
+    int upsample_i8 = 1;         // f8_net_upsample, nearest: 1 = the byte-copy mode where the result is read in at most two int8 formats and by nothing else (f8_upsample.hip); 0 = always the int32 mode
     int tap_tiled = 1;           // network outputs 1 .. leave on tap_kernel (f8_tap.hip: walks the I32T blocks, every loaded byte used); 0: on output_kernel like output 0
     int check_input_range = 1;   // int32 inputs that are NARROWED to the head's 8-bit format (no requant) are range-checked on the device; f8_net_check reports
 };
@@ -200,6 +201,19 @@ struct ConcatArgs {
     const void* src[2][kMaxConcat];
     int32_t C[kMaxConcat], Cs_src[kMaxConcat], off[kMaxConcat], shl[kMaxConcat];   // real / padded channels of source i, its first output channel, its alignment shift
     int32_t K, M, Cs;                      // sources, pixels N * H * W, padded output channels (the real ones: off[K - 1] + C[K - 1])
+    int32_t* out32;
+    QuantOut q[2];
+};
+
+// Upsampling (f8_upsample.hip; f8_net_upsample): [C, Hs, Ws] -> [C, P, Q] = [C, Hs * sh, Ws * sw].  Mode i8 (upsample_i8_kernel, nearest only): src[k] is the
+// source in the int8 format of output form k (NHWC, Cs-byte rows), the launch copies bytes and only q[k].ptr is read.  Mode i32 (upsample_i32_kernel):
+// src[0] is the source's int32 form (I32T); nearest copies, bilinear (sh == sw == 1 << k) sums the four clamped neighbours with the integer weights of
+// f8net.h (the exact value times 4 s^2, wrapping); out32 and q[] as AddArgs.
+struct UpsampleArgs {
+    const void* src[2];
+    int32_t N, C, Cs, Hs, Ws, P, Q, sh, sw, k;           // images, real / padded channels, source map, output map, scales, bilinear: log2 of the scale
+    uint32_t mPQ, mQ, mSh, mSw, mWs, mVpp;               // magic divisors (make_magic): P * Q, Q, sh, sw, Ws, Cs / 16
+    int32_t s1PQ, s2PQ, s1Q, s2Q, s1Sh, s2Sh, s1Sw, s2Sw, s1Ws, s2Ws, s1Vpp, s2Vpp;
     int32_t* out32;
     QuantOut q[2];
 };
@@ -608,6 +622,9 @@ const char* input_kernel_name(int inst);
 int concat_inst(const ConcatArgs& a, bool i8);                     // f8_concat.hip.  0: concat_i32_kernel, 1: concat_i8_kernel<true> (16-byte vectors), 2: concat_i8_kernel<false>
 const char* concat_kernel_name(int inst);
 hipError_t launch_concat(const ConcatArgs& a, int inst, hipStream_t s);
+int upsample_inst(bool bilinear, bool i8);                         // f8_upsample.hip.  0: upsample_i8_kernel, 1: upsample_i32_kernel<false> (nearest), 2: upsample_i32_kernel<true> (bilinear)
+const char* upsample_kernel_name(int inst);
+hipError_t launch_upsample(const UpsampleArgs& a, int inst, hipStream_t s);
 hipError_t launch_input(const InArgs& a, int inst, hipStream_t s);
 const char* output_kernel_name();
 hipError_t launch_output(const OutArgs& a, hipStream_t s);

@@ -88,7 +88,7 @@ enum Role { R_NONE, R_B0, R_B2, R_B4, R_SC };
 // The chain launches: bottleneck stage (f8_chain.hip; the 7x7 stage over clusters, f8_cchain.hip), BasicBlocks (f8_bchain.hip), BasicBlocks of a 7x7 x 512
 // stage over clusters of eight workgroups (option fuse_bchain7, f8_bcchain.hip), inverted residuals (f8_irchain.hip).  Independent of the block kind.
 enum ChainKind { C_NONE, C_STAGE, C_BASIC, C_BASIC_CLUSTER, C_IR };
-enum NodeKind { N_INPUT, N_CONV, N_ADD, N_MAXPOOL, N_AVGPOOL, N_LINEAR, N_CONCAT };
+enum NodeKind { N_INPUT, N_CONV, N_ADD, N_MAXPOOL, N_AVGPOOL, N_LINEAR, N_CONCAT, N_UPSAMPLE };
 struct Node {
     int kind; int a = -1, b = -1; int out = -1;
     f8_conv_desc cd{};                 // conv / linear (as 1x1 conv)
@@ -101,6 +101,8 @@ struct Node {
     int shift = 0;                     // avgpool
     std::vector<int> srcs;             // concat: the operands in channel order (tensor ids; a = srcs[0])
     bool concat_i8 = false;            // concat, pass 2: the byte-gather mode (every source in the output's int8 formats); false: sources in int32
+    int up_mode = 0, up_sh = 1, up_sw = 1;      // upsample: F8_UP_NEAREST / F8_UP_BILINEAR, the scales
+    bool up_i8 = false;                // upsample, pass 2: the byte-copy mode (nearest, the source in the output's int8 formats); false: the source in int32
     // planning
     int fused_into = -1;               // add: conv node that carries it
     int fused_add = -1;                // conv: add node carried
@@ -122,7 +124,7 @@ struct Node {
     size_t rc_off = 0, cc_off = 0; int ncc = 0;      // border-class tables (0 = single class)
     ConvTile tile{};
 };
-enum StepKind { S_INPUT, S_CONV, S_DW, S_ADD, S_MAXPOOL, S_AVGPOOL, S_REQUANT, S_OUTPUT, S_FUSED, S_STEMPOOL, S_IR, S_P12, S_CHAIN, S_BCHAIN, S_HEAD2, S_IRCHAIN, S_DWS, S_DWS7, S_IRK, S_GCONV, S_CONCAT };
+enum StepKind { S_INPUT, S_CONV, S_DW, S_ADD, S_MAXPOOL, S_AVGPOOL, S_REQUANT, S_OUTPUT, S_FUSED, S_STEMPOOL, S_IR, S_P12, S_CHAIN, S_BCHAIN, S_HEAD2, S_IRCHAIN, S_DWS, S_DWS7, S_IRK, S_GCONV, S_CONCAT, S_UPSAMPLE };
 // The kernel of a step whose kind has several, chosen once by the step's emitter (pass 3); bind_step, run_step and f8_net_autotune switch on it.
 //   S_CONV:  conv_igemm (f8_kernels.hip), the LDS-patch 3x3 (f8_conv3x3.hip), conv1x1_wreg (f8_wreg.hip), conv1x1_wstat (f8_wstat.hip),
 //            conv3x3s2_wreg (f8_s2conv.hip), the 1x1 conv + average pool (f8_pool.hip), the classifier fc_dense (f8_fc.hip)
@@ -135,9 +137,9 @@ struct Step {
     int src_t = -1, src_f = -1;        // main input tensor / form
     int res_t = -1, res_f = -1;        // residual (conv) or second operand (add)
     int src2_t = -1, src2_f = -1;      // dual GEMM: input of the second conv
-    // S_CONCAT reads K tensors and keeps them HERE, with src_t = res_t = src2_t = -1: code that asks what a step reads (lifetimes: layout_arena; users of the
+    // S_CONCAT reads K tensors (S_UPSAMPLE: one, in up to two forms) and keeps them HERE, with src_t = res_t = src2_t = -1: code that asks what a step reads (lifetimes: layout_arena; users of the
     // network input: let_stem_read_input) must look at cat_t as well as the three *_t above; step_chunk / for_each_launch index tensors[src_t] only for S_FUSED
-    std::vector<int> cat_t, cat_f[2];  // S_CONCAT: the source tensors and their forms — i8 mode: cat_f[k] = the sources in the format of output form out.f8[k]; i32 mode: cat_f[0] = their int32 forms
+    std::vector<int> cat_t, cat_f[2];  // S_UPSAMPLE: the one source, forms as for S_CONCAT: the source tensors and their forms — i8 mode: cat_f[k] = the sources in the format of output form out.f8[k]; i32 mode: cat_f[0] = their int32 forms
     OutSel out;
     int acc_shl = 0, res_shl = 0, relu0 = 0, relu1 = 0;
     bool dense = false;
@@ -148,7 +150,7 @@ struct Step {
     double bytes_per_img = 0, bytes_const = 0, ops_per_img = 0;
     double valu_per_img = 0;           // ESSENTIAL vector lane-operations per image (f8_net_launch_valu): what the reference's semantics need once the MFMAs are done
     // the launcher's arguments as far as the plan decides them (bind_step); run_step copies them and adds what the run decides
-    std::variant<std::monostate, ConvArgs, StemPoolArgs, FusedArgs, ChainArgs, BChainArgs, BCChainArgs, IRArgs, IRKArgs, IRChainArgs, DwsArgs, Dws7Args, DwArgs, GConvArgs, AddArgs, PoolArgs, AvgArgs, OutArgs, ConcatArgs> args;
+    std::variant<std::monostate, ConvArgs, StemPoolArgs, FusedArgs, ChainArgs, BChainArgs, BCChainArgs, IRArgs, IRKArgs, IRChainArgs, DwsArgs, Dws7Args, DwArgs, GConvArgs, AddArgs, PoolArgs, AvgArgs, OutArgs, ConcatArgs, UpsampleArgs> args;
     int inst = 0;                      // the instance the launcher starts (the family's *_inst, f8_internal.h; bind_step)
     // S_CHAIN / S_BCHAIN: geometry, workgroups per image and resident per CU, the 7x7 cluster form (f8_cchain.hip)
     int C = 0, MID = 0, H = 0, W = 0, cin0 = 0, tiles = 0, wg_per_cu = 1; bool cluster = false;
@@ -285,6 +287,11 @@ static int64_t tensor_amax(f8_net* net, int t, int depth = 0) {
                 if (a < 0 || sa < 0 || sa > 31 || a > (cap >> sa)) { m = -1; break; }
                 m = std::max(m, a << sa);
             }
+        } else if (nd.kind == N_UPSAMPLE) {                  // nearest: the source's; bilinear: the weights of an output sum to 4 s^2, under the same cap
+            const int64_t a = tensor_amax(net, nd.a, depth + 1);
+            const int sa = T.fl - net->tensors[nd.a].fl;     // 0 / 2k + 2
+            constexpr int64_t cap = int64_t(1) << 40;
+            if (a >= 0 && sa >= 0 && sa <= 31 && a <= (cap >> sa)) m = a << sa;
         }
     }
     if (m > (int64_t(1) << 40)) m = -1;
@@ -388,6 +395,7 @@ static const OptKey kOptKeys[] = {
     {"tap_tiled", "F8_TAP_TILED", &Options::tap_tiled, 0, 1, true},
     {"grouped", "F8_GROUPED", &Options::grouped, 0, 2, true},
     {"concat_i8", "F8_CONCAT_I8", &Options::concat_i8, 0, 1, true},
+    {"upsample_i8", "F8_UPSAMPLE_I8", &Options::upsample_i8, 0, 1, true},
 };
 static const OptKey* find_opt(const char* key) {
     if (!key) return nullptr;
@@ -679,6 +687,36 @@ int f8_net_concat(f8_net* net, const int* srcs, int n) {
     const int t = new_tensor(net, C, net->tensors[srcs[0]].H, net->tensors[srcs[0]].W, fl, id);
     net->nodes[id].out = t;
     for (int i = 0; i < n; ++i) net->tensors[srcs[i]].consumers.push_back(id);
+    return t;
+}
+
+int f8_net_upsample(f8_net* net, int src, int mode, int scale_h, int scale_w) {
+    if (!net) return fail(F8_ERR_INVALID, "f8_net_upsample: null net");
+    if (net->finalized) return fail(F8_ERR_STATE, "f8_net_upsample: net already finalized");
+    if (const int rc = check_t(net, src, "f8_net_upsample")) return rc;
+    if (mode != F8_UP_NEAREST && mode != F8_UP_BILINEAR) return fail(F8_ERR_INVALID, "f8_net_upsample: unknown mode %d", mode);
+    if (scale_h < 1 || scale_w < 1 || (scale_h == 1 && scale_w == 1))
+        return fail(F8_ERR_INVALID, "f8_net_upsample: scales must be >= 1 and not both 1 (got %d, %d)", scale_h, scale_w);
+    const Tensor s = net->tensors[src];
+    int fl = s.fl;
+    if (mode == F8_UP_NEAREST) {
+        if (scale_h > 256 || scale_w > 256) return fail(F8_ERR_UNSUPPORTED, "f8_net_upsample: nearest scales above 256 are not built (got %d, %d)", scale_h, scale_w);
+    } else {
+        if (scale_h != scale_w || (scale_h != 2 && scale_h != 4 && scale_h != 8 && scale_h != 16))
+            return fail(F8_ERR_UNSUPPORTED, "f8_net_upsample: bilinear is built for equal scales of 2, 4, 8 or 16 (got %d, %d)", scale_h, scale_w);
+        int k = 0;
+        while ((1 << k) < scale_h) ++k;
+        fl = s.fl + 2 * k + 2;                                 // the weights of an output sum to 4 s^2 = 2^(2k + 2)
+        if (fl > 32) return fail(F8_ERR_INVALID, "f8_net_upsample: output fraclen %d > 32", fl);
+    }
+    if ((int64_t)s.H * scale_h > INT32_MAX / 4 || (int64_t)s.W * scale_w > INT32_MAX / 4 || (int64_t)s.H * scale_h * s.W * scale_w > INT32_MAX / 4)
+        return fail(F8_ERR_UNSUPPORTED, "f8_net_upsample: the %d x %d map times (%d, %d) exceeds 2 GiB per tensor", s.H, s.W, scale_h, scale_w);
+    Node nd; nd.kind = N_UPSAMPLE; nd.a = src; nd.up_mode = mode; nd.up_sh = scale_h; nd.up_sw = scale_w;
+    net->nodes.push_back(nd);
+    const int id = (int)net->nodes.size() - 1;
+    const int t = new_tensor(net, s.C, s.H * scale_h, s.W * scale_w, fl, id);
+    net->nodes[id].out = t;
+    net->tensors[src].consumers.push_back(id);
     return t;
 }
 
@@ -1859,6 +1897,19 @@ static void plan_tensor_forms(f8_net* net) {
                 }
                 break;
             }
+            case N_UPSAMPLE: {
+                // Mode.  upsample_nearest_i8: nearest, and the result exists in one or two int8 forms and nothing else (no int32 reader, no
+                // network output).  Replication commutes with every element-wise function, the requantisation among them, and the fraclen — so the shift — is the
+                // source's: the source is asked for the result's formats and the launch copies bytes.  No bound on the values is needed (the concat rule
+                // without its conditions (c) - (e)).  Otherwise the int32 mode: the source's int32 form, replicated / interpolated in the launch.
+                Tensor& o = T[nd.out];
+                int n8 = 0;
+                for (auto& F : o.forms) n8 += F.kind == FORM_I8;
+                nd.up_i8 = opt.upsample_i8 && nd.up_mode == F8_UP_NEAREST && n8 >= 1 && n8 <= 2 && (int)o.forms.size() == n8 && !is_output(net, nd.out);
+                if (!nd.up_i8) add_form(T[nd.a], FORM_I32, 0, 0);
+                else for (size_t f = 0; f < o.forms.size(); ++f) add_form(T[nd.a], FORM_I8, o.forms[f].n, o.forms[f].sgn);
+                break;
+            }
             default: break;
         }
     }
@@ -2418,6 +2469,34 @@ static int emit_concat(f8_net* net, int i, Step& st, std::vector<int>* extra) {
     return F8_OK;
 }
 
+static int emit_upsample(f8_net* net, int i, Step& st, std::vector<int>* extra) {
+    auto& T = net->tensors;
+    const Node& nd = net->nodes[i];
+    const Tensor& s = T[nd.a]; Tensor& o = T[nd.out];
+    st.kind = S_UPSAMPLE;
+    st.cat_t = {nd.a};
+    if (o.forms.empty()) add_form(o, FORM_I32, 0, 0);
+    select_outputs(net, nd.out, &st.out, extra);
+    const double ipx = (double)s.H * s.W, opx = (double)o.H * o.W;
+    const bool bil = nd.up_mode == F8_UP_BILINEAR;
+    if (nd.up_i8) {                                       // (pass 2: one or two int8 forms and no other)
+        for (int k = 0; k < 2; ++k) {
+            if (st.out.f8[k] < 0) continue;
+            const Form& F = o.forms[st.out.f8[k]];
+            const int f = find_form(s, FORM_I8, F.n, F.sgn);
+            if (f < 0) return fail(F8_ERR_STATE, "f8_net_finalize: planner bug: upsample source t%d lacks the output's int8 form", nd.a);
+            st.cat_f[k].push_back(f);
+        }
+        st.bytes_per_img = (ipx + opx) * o.C * out_forms8(st);      // every real byte read once and written once, per form
+    } else {
+        st.cat_f[0].push_back(find_form(s, FORM_I32, 0, 0));
+        st.bytes_per_img = ipx * o.C * 4 + out_bytes(st, o, opx);
+        st.valu_per_img = opx * o.C * ((bil ? 4 : 0) + 3 * out_forms8(st));      // bilinear: one multiply + three multiply-adds per value; 3 per int8 value produced
+    }
+    st.name = (bil ? "upsample_bilinear_i32:" : nd.up_i8 ? "upsample_nearest_i8:" : "upsample_nearest_i32:") + tname(net, nd.out);
+    return F8_OK;
+}
+
 // the int8 forms of tensor t beyond the two its producer writes: stand-alone requants of its int32 form
 static void emit_requants(f8_net* net, int t, const std::vector<int>& extra) {
     for (int f : extra) {
@@ -2483,6 +2562,7 @@ static int emit_steps(f8_net* net, int max_batch) {
             case N_MAXPOOL: rc = emit_maxpool(net, i, st, &extra); break;
             case N_AVGPOOL: rc = emit_avgpool(net, i, st, &extra); break;
             case N_CONCAT: rc = emit_concat(net, i, st, &extra); break;
+            case N_UPSAMPLE: rc = emit_upsample(net, i, st, &extra); break;
         }
         if (rc) return rc;
         net->steps.push_back(st);
@@ -3055,6 +3135,20 @@ static int bind_step(f8_net* net, Step& st) {
             snprintf(kb, sizeof kb, "%s", concat_kernel_name(st.inst = concat_inst(a, nd.concat_i8)));
             out_formats(a.q); st.args = a; break;
         }
+        case S_UPSAMPLE: {
+            const Tensor& sT = T[st.cat_t[0]]; const Tensor& oT = T[nd.out];
+            UpsampleArgs a{};
+            a.C = oT.C; a.Cs = oT.Cs; a.Hs = sT.H; a.Ws = sT.W; a.P = oT.H; a.Q = oT.W; a.sh = nd.up_sh; a.sw = nd.up_sw;
+            while (nd.up_mode == F8_UP_BILINEAR && (1 << a.k) < a.sh) ++a.k;
+            make_magic((uint32_t)(a.P * a.Q), &a.mPQ, &a.s1PQ, &a.s2PQ);
+            make_magic((uint32_t)a.Q, &a.mQ, &a.s1Q, &a.s2Q);
+            make_magic((uint32_t)a.sh, &a.mSh, &a.s1Sh, &a.s2Sh);
+            make_magic((uint32_t)a.sw, &a.mSw, &a.s1Sw, &a.s2Sw);
+            make_magic((uint32_t)a.Ws, &a.mWs, &a.s1Ws, &a.s2Ws);
+            make_magic((uint32_t)(a.Cs >> 4), &a.mVpp, &a.s1Vpp, &a.s2Vpp);
+            snprintf(kb, sizeof kb, "%s", upsample_kernel_name(st.inst = upsample_inst(nd.up_mode == F8_UP_BILINEAR, nd.up_i8)));
+            out_formats(a.q); st.args = a; break;
+        }
         case S_MAXPOOL: {
             const Tensor& sT = T[st.src_t]; const Form& sF = sT.forms[st.src_f];
             const Tensor& oT = T[nd.out];
@@ -3469,6 +3563,15 @@ static int run_step(const f8_net* net, const RunIO& io, const Step& st, int n0, 
             a.M = N * o.H * o.W;
             fill_out(&a.out32, a.q);
             e = launch_concat(a, st.inst, s);
+            break;
+        }
+        case S_UPSAMPLE: {
+            UpsampleArgs a = std::get<UpsampleArgs>(st.args);
+            for (int k = 0; k < 2; ++k)
+                if (!st.cat_f[k].empty()) a.src[k] = fp(T[st.cat_t[0]].forms[st.cat_f[k][0]]);
+            a.N = N;
+            fill_out(&a.out32, a.q);
+            e = launch_upsample(a, st.inst, s);
             break;
         }
         case S_MAXPOOL: {

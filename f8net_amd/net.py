@@ -102,6 +102,18 @@ class F8Net:
             self._L.f8_net_set_label(self._h, t, label.encode())
         return t
 
+    def upsample(self, src, scale, mode='nearest', label=None):
+        """Upsampling by integer scales (f8_net_upsample): `scale` is an int or (scale_h, scale_w); mode 'nearest' keeps the fraclen, 'bilinear'
+        (half-pixel centres, scale 2 / 4 / 8 / 16) yields the exact interpolated value times 4 scale^2 at fraclen + 2 log2(scale) + 2."""
+        sh, sw = (scale, scale) if isinstance(scale, int) else scale
+        modes = {'nearest': 0, 'bilinear': 1}
+        if mode not in modes:
+            raise ValueError(f"upsample mode {mode!r}: 'nearest' or 'bilinear'")
+        t = check(self._L.f8_net_upsample(self._h, src, modes[mode], int(sh), int(sw)))
+        if label:
+            self._L.f8_net_set_label(self._h, t, label.encode())
+        return t
+
     def maxpool(self, src, k=3, stride=2, pad=1, label=None):
         t = check(self._L.f8_net_maxpool(self._h, src, k, stride, pad))
         if label:

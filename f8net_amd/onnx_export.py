@@ -12,6 +12,8 @@ opset-11 vocabulary is written directly from the integer graph — per op the no
     head max-pool                  Cast(f32), MaxPool, Cast(i32)                     (fix_resnet.py:358-359)
     FXQAvgPool2d                   Cast(i64), ReduceSum(-1) x2, Cast(i32)            (fix_quant_ops.py:130-133)
     channel concatenation          [Pow/Cast/Mul per operand at a smaller fraction length,] Concat(axis=1)
+    upsampling, nearest            Resize(nearest, asymmetric, floor; scales [1, 1, sh, sw])
+    upsampling, bilinear           Cast(f32), Resize(linear, half_pixel; scales [1, 1, s, s]), Mul(4 s^2), Cast(i32)
     x.view(x.size(0), -1)          Shape, Gather, Unsqueeze, Concat, Reshape         (fix_resnet.py:371)
     classifier                     Gemm(transB=1), Cast(f32)                         (fix_resnet.py:383)
 
@@ -165,6 +167,13 @@ def export_graph(ig: IntGraph) -> bytes:
             y = w.cast(v, onnx_io.INT32)
         elif o.kind == 'concat':                                     # torch.cat(dim=1); `x << k` as in the residual join
             y = w.emit('Concat', [name[s] if k == 0 else w.emit('Mul', [name[s], w.pow2(k)]) for s, k in zip(o.srcs, o.shifts)], {'axis': 1})
+        elif o.kind == 'upsample':
+            roi, sc = w.const(np.zeros(0, np.float32), np.float32), w.const([1.0, 1.0, float(o.scale[0]), float(o.scale[1])], np.float32)
+            if o.mode == 'nearest':
+                y = w.emit('Resize', [name[o.src], roi, sc], {'coordinate_transformation_mode': b'asymmetric', 'mode': b'nearest', 'nearest_mode': b'floor'})
+            else:                                                    # the interpolated value times 4 s^2: integers again behind the Mul
+                v = w.emit('Resize', [w.cast(name[o.src], onnx_io.FLOAT), roi, sc], {'coordinate_transformation_mode': b'half_pixel', 'mode': b'linear'})
+                y = w.cast(w.emit('Mul', [v, w.const(float(4 * o.scale[0] * o.scale[1]), np.float32)]), onnx_io.INT32)
         elif o.kind == 'maxpool':
             v = w.emit('MaxPool', [w.cast(name[o.src], onnx_io.FLOAT)],
                        {'ceil_mode': 0, 'dilations': [1, 1], 'kernel_shape': [o.kernel] * 2, 'pads': [o.pad] * 4,

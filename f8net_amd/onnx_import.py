@@ -36,7 +36,7 @@ class OnnxImportError(ValueError):
 
 @dataclass
 class IntOp:
-    kind: str                      # input | conv | linear | add | maxpool | avgpool | concat
+    kind: str                      # input | conv | linear | add | maxpool | avgpool | concat | upsample
     src: int = -1                  # tensor id (index into IntGraph.ops)
     src2: int = -1                 # add: the operand that is NOT shifted
     weight: np.ndarray = None
@@ -54,6 +54,8 @@ class IntOp:
     dilation: int = 1              # conv: spacing of the kernel's taps (ONNX `dilations`, both equal)
     srcs: list = None              # concat: the operands in channel order (tensor ids)
     shifts: list = None            # concat: k_i of `srcs[i] << k_i`, the alignment to the largest fraclen (the smallest is 0)
+    mode: str = None               # upsample: 'nearest' | 'bilinear' (half-pixel centres; the result is the interpolated value times 4 scale^2)
+    scale: tuple = None            # upsample: (scale_h, scale_w)
 
 
 @dataclass
@@ -110,6 +112,10 @@ class IntGraph:
                     eq(t, s, k)
             elif o.kind == 'maxpool':
                 eq(t, o.src, 0)
+            elif o.kind == 'upsample':
+                eq(t, o.src, 0 if o.mode == 'nearest' else upsample_fl_gain(o.scale))
+                if o.mode != 'nearest':
+                    ge(ZERO, t, -32)                 # f8_net_upsample: the bound of the average pool
             elif o.kind == 'avgpool':
                 eq(t, o.src, AVGPOOL_SHIFT)
                 ge(ZERO, t, -32)                     # fix_quant_ops.py:129
@@ -177,12 +183,22 @@ class IntGraph:
                 ids[t] = net.concat([ids[s] for s in o.srcs])
             elif o.kind == 'maxpool':
                 ids[t] = net.maxpool(ids[o.src], o.kernel, o.stride, o.pad)
+            elif o.kind == 'upsample':
+                ids[t] = net.upsample(ids[o.src], tuple(o.scale), o.mode)
             elif o.kind == 'avgpool':
                 ids[t] = net.avgpool_sum(ids[o.src], AVGPOOL_SHIFT)
         net.output(ids[self.output], as_float=self.output_float)
         for k, v in (options or {}).items():
             net.set_option(k, v)
         return net.finalize(max_batch)
+
+
+def upsample_fl_gain(scale):
+    """2k + 2 for a bilinear upsample by scale (2^k, 2^k): its integer weights sum to 4 scale^2 = 2^(2k + 2) (include/f8net.h)."""
+    sh, sw = scale
+    if sh != sw or sh not in (2, 4, 8, 16):
+        raise OnnxImportError(f'bilinear upsample by {tuple(scale)}: only equal scales of 2, 4, 8 or 16')
+    return 2 * (sh.bit_length() - 1) + 2
 
 
 # ------------------------------------------------------------------------------ template recognition
@@ -248,6 +264,10 @@ def import_graph(model, input_signed=False) -> IntGraph:
     for nd in g.nodes:
         for s in nd.inputs:
             uses[s] = uses.get(s, 0) + 1
+    users = {}
+    for nd in g.nodes:
+        for s in nd.inputs:
+            users.setdefault(s, []).append(nd)
     ig = IntGraph(input_signed=bool(input_signed))
     ig.ops.append(IntOp('input', shape=tuple(idims[1:])))
     val = {iname: ('T', 0)}                          # ONNX value name -> expr | ('const', python number | ndarray)
@@ -320,6 +340,42 @@ def import_graph(model, input_signed=False) -> IntGraph:
                 raise OnnxImportError('Concat: every operand is scaled (the result takes the largest operand fraction length)')
             ig.ops.append(IntOp('concat', src=srcs[0], srcs=srcs, shifts=shifts))
             val[out] = ('T', len(ig.ops) - 1)
+        elif op == 'Resize':
+            # nearest: Resize(x, roi, [1, 1, sh, sw]; nearest / asymmetric / floor).  bilinear: Resize(linear, half_pixel) and the Mul by 4 s^2 behind
+            # it, which makes the values integers again — the pair is one op (the Mul branch below closes it)
+            e = val.get(nd.inputs[0], ('?',))
+            if e[0] != 'T':
+                raise OnnxImportError('Resize: the input is not a layer result')
+            if len(nd.inputs) > 3 and nd.inputs[3]:
+                raise OnnxImportError('Resize with a `sizes` input: only constant integer scales')
+            sc = val.get(nd.inputs[2]) if len(nd.inputs) > 2 else None
+            if sc is None or sc[0] != 'const':
+                raise OnnxImportError('Resize: the scales are not a constant')
+            sc = np.asarray(sc[1], np.float64).reshape(-1)
+            if sc.size != 4 or sc[0] != 1 or sc[1] != 1 or any(v != int(v) or v < 1 for v in sc[2:]):
+                raise OnnxImportError(f'Resize scales {sc.tolist()}: expected [1, 1, sh, sw] with integer sh, sw >= 1')
+            scale = (int(sc[2]), int(sc[3]))
+            mode = a.get('mode', b'nearest').decode()
+            ctm = a.get('coordinate_transformation_mode', b'half_pixel').decode()
+            if mode == 'nearest':
+                nm = a.get('nearest_mode', b'round_prefer_floor').decode()
+                if ctm != 'asymmetric' or nm != 'floor':
+                    raise OnnxImportError(f"Resize(nearest) with coordinate_transformation_mode {ctm!r}, nearest_mode {nm!r}: only 'asymmetric' / 'floor'")
+                ig.ops.append(IntOp('upsample', src=e[1], mode='nearest', scale=scale))
+                val[out] = ('T', len(ig.ops) - 1)
+            elif mode == 'linear':
+                if ctm not in ('half_pixel', 'pytorch_half_pixel'):
+                    raise OnnxImportError(f"Resize(linear) with coordinate_transformation_mode {ctm!r}: only 'half_pixel' / 'pytorch_half_pixel'")
+                gain = upsample_fl_gain(scale)
+                nxt, name = users.get(out, []), out
+                while len(nxt) == 1 and nxt[0].op == 'Cast':
+                    name = nxt[0].outputs[0]
+                    nxt = users.get(name, [])
+                if len(nxt) != 1 or nxt[0].op != 'Mul':
+                    raise OnnxImportError(f'Resize(linear) by {scale[0]} without the Mul by 2^{gain} behind it: its values are not integers')
+                val[out] = ('resize_lin', e[1], scale, gain)
+            else:
+                raise OnnxImportError(f'Resize mode {mode!r}: only nearest and linear')
         elif op in ('Shape', 'Gather', 'Unsqueeze', 'Concat'):
             val[out] = ('opaque',)                                 # the `x.view(x.size(0), -1)` plumbing before the FC
         elif op == 'Reshape':
@@ -333,6 +389,12 @@ def import_graph(model, input_signed=False) -> IntGraph:
                 val[out] = ('const', {'Add': cx + cy, 'Mul': cx * cy}.get(op))
                 if val[out][1] is None:
                     raise OnnxImportError(f'{op} of two constants')
+            elif is_const(y) and val.get(x, ('?',))[0] == 'resize_lin':
+                _, src, scale, gain = val[x]
+                if op != 'Mul' or const(y, op) != 1 << gain:
+                    raise OnnxImportError(f'Resize(linear) by {scale[0]} must be followed by a Mul by 2^{gain} = {1 << gain}')
+                ig.ops.append(IntOp('upsample', src=src, mode='bilinear', scale=scale))
+                val[out] = ('T', len(ig.ops) - 1)
             elif is_const(y):
                 tag = {'Add': 'addc', 'Mul': 'mul', 'Div': 'div', 'Mod': 'mod', 'Equal': 'eq'}[op]
                 val[out] = (tag, val[x], const(y, op))

@@ -157,6 +157,28 @@ int f8_net_add(f8_net* net, int a, int b, int relu);
 #define F8_MAX_CONCAT 8
 int f8_net_concat(f8_net* net, const int* srcs, int n);
 
+/* Upsampling (the top-down path of an FPN, a U-Net decoder, DeepLab's logits back at the input size, the broadcast of ASPP's image-pooling branch):
+ * out = [C, H * scale_h, W * scale_w] from src = [C, H, W].  Both modes are exact integer functions: no rounding, no real-valued scale.
+ *   F8_UP_NEAREST   1 <= scale_h, scale_w <= 256, not both 1.  out[c][P][Q] = x[c][P / scale_h][Q / scale_w] (integer division): torch's
+ *                   mode='nearest' for integer scales.  The fraclen is unchanged.  A [C, 1, 1] source with scale (H, W) is a broadcast.
+ *   F8_UP_BILINEAR  scale_h == scale_w == s = 2^k, k = 1 .. 4; half-pixel centres (torch's mode='bilinear', align_corners=False) scaled to integers.
+ *                   Per axis of n source values, output index o = s i + j, 0 <= j < s:
+ *                     j <  s / 2:  (s - 2j - 1) x[max(i - 1, 0)] + (s + 2j + 1) x[i]
+ *                     j >= s / 2:  (3s - 2j - 1) x[i] + (2j + 1 - s) x[min(i + 1, n - 1)]
+ *                   The weights of an axis sum to 2s; applied over H and over W every output is the exact interpolated value times 4 s^2 =
+ *                   2^(2k + 2), so out.fraclen = src.fraclen + 2k + 2.  All arithmetic modulo 2^32 (the int32 wrap of f8_net_avgpool_sum), no clamp,
+ *                   no rounding: a consumer with quant_input = 1 rounds once, as for any tensor.
+ * Returns the tensor id.  F8_ERR_INVALID: a bad tensor id, a scale < 1 or both scales 1, an unknown mode, bilinear with an output fraclen > 32 (the
+ * bound of f8_net_avgpool_sum); F8_ERR_UNSUPPORTED: a nearest scale > 256, bilinear with unequal scales or a scale outside {2, 4, 8, 16};
+ * F8_ERR_STATE after finalize.
+ * The plan runs it as one launch of f8_upsample.hip, its mode shown by its token: `upsample_nearest_i8:` — nearest, the result read in at most two
+ * int8 formats and by nothing else — has the source's producer write those formats and replicates bytes; `upsample_nearest_i32:` /
+ * `upsample_bilinear_i32:` read the source's int32 form (option upsample_i8 = 0: every nearest one).  Same values either way.
+ * A tensor read by an upsample exists in device memory: no fused block or chain launch keeps it on chip (it cuts a launch as an output tap does). */
+#define F8_UP_NEAREST  0
+#define F8_UP_BILINEAR 1
+int f8_net_upsample(f8_net* net, int src, int mode, int scale_h, int scale_w);
+
 /* Head max-pool nn.MaxPool2d(k, stride, pad) via the float detour (fix_resnet.py:358-359) or
  * FXQMaxPool2d (fix_quant_ops.py:150-157); exact integer max. */
 int f8_net_maxpool(f8_net* net, int src, int kernel, int stride, int pad);
@@ -317,7 +339,10 @@ int f8_net_check(f8_net* net);
  *               grouped conv.  Same values in both, bit for bit; depthwise convs keep their own rules and kernels whatever it says),
  *               concat_i8 (default 1: a concat whose result is read in at most two int8 formats and by nothing else, with values the planner can
  *               bound, runs f8::concat_i8_kernel on its operands' int8 forms, plan token concat_i8:; 0: every concat runs f8::concat_i32_kernel on
- *               their int32 forms, token concat_i32:.  Same values either way, bit for bit)
+ *               their int32 forms, token concat_i32:.  Same values either way, bit for bit),
+ *               upsample_i8 (default 1: a nearest upsample whose result is read in at most two int8 formats and by nothing else runs
+ *               f8::upsample_i8_kernel on its source's int8 forms, plan token upsample_nearest_i8:; 0: it runs f8::upsample_i32_kernel<false> on the
+ *               int32 form, token upsample_nearest_i32:.  Same values either way, bit for bit)
  *   scheduling: chunk56 / chunk28 / chunk14 (images per chunk of the fused blocks; -1 = derived from chunk_budget_mb, 0 = whole
  *               batch), chunk_budget_mb (memory-side cache a chunk's int32 stream may occupy), chunk_ds, chunk_opener,
  *               split_streams, graph, stagger, stagger_pipelined, stem_wpc, stem_grid_div (row-walking head on 1 / n of the CUs; 0 = by output form), check_device, check_input_range, pipeline_depth (2..4 runs in flight),

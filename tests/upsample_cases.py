@@ -1,0 +1,321 @@
+"""Case table, reference and graph builder of the tests of upsampling (f8_net_upsample / `F8Net.upsample`, f8_upsample.hip):
+tests/test_upsample_plan.py (acceptance, refusals, mode tokens, kernel symbols, forms, launch_info, fused nets, the ONNX round trip; no GPU) and
+tests/test_gpu_upsample.py (every case on both legs, bit for bit on the device).  No test functions here.
+
+The reference is numpy on int64, wrapped to int32 at the end: nearest is `np.repeat` along H and W; bilinear applies, per axis of n values and for
+output index o = s i + j (0 <= j < s), the integer weights of include/f8net.h
+    j <  s / 2:  (s - 2j - 1) x[max(i - 1, 0)] + (s + 2j + 1) x[i]
+    j >= s / 2:  (3s - 2j - 1) x[i] + (2j + 1 - s) x[min(i + 1, n - 1)]
+over H and then over W: the exact half-pixel interpolation times 4 s^2 = 2^(2k + 2), fraclen + 2k + 2.  `pin_to_torch` holds it against
+torch.nn.functional.interpolate in float64 with exact equality (tests/test_upsample_plan.py runs it on non-wrapping inputs).
+
+Unless a builder says otherwise a case is  input (8 channels, 0 .. 255, fraclen 8) -> a 1x1 producer conv that reads it as it is, C outputs at
+fraclen 13 -> upsample -> readers: one 32-output 1x1 conv per (input_fl, signed), summed (concat_cases.readers).
+
+The expected plan token of every case, on both legs of option upsample_i8, and the forms its launch writes are WRITTEN BY HAND (the rule:
+DESIGN.md 4.5j); nothing here asks the planner for them."""
+import functools
+
+import numpy as np
+
+import concat_cases as cc
+from concat_cases import FUSE_ALL, X_FL, producer, readers  # noqa: F401  (the tests take them from here)
+from f8net_amd import synth
+from f8net_amd.onnx_import import upsample_fl_gain
+from oracle import oracle
+
+I8, N32, B32 = 'upsample_nearest_i8:', 'upsample_nearest_i32:', 'upsample_bilinear_i32:'
+SYMBOL = {I8: 'f8::upsample_i8_kernel', N32: 'f8::upsample_i32_kernel<false>', B32: 'f8::upsample_i32_kernel<true>'}
+
+
+def wrap32(y):
+    return ((np.asarray(y, np.int64) + 2 ** 31) % 2 ** 32 - 2 ** 31).astype(np.int32)
+
+
+def nearest_exact(x, sh, sw):
+    return np.repeat(np.repeat(np.asarray(x, np.int64), sh, axis=2), sw, axis=3)
+
+
+def _bilinear_axis(x, s, axis):
+    n = x.shape[axis]
+    i0, i1, wl, wu = [], [], [], []
+    for o in range(s * n):
+        i, j = divmod(o, s)
+        if j < s // 2:
+            i0.append(max(i - 1, 0)), i1.append(i), wl.append(s - 2 * j - 1), wu.append(s + 2 * j + 1)
+        else:
+            i0.append(i), i1.append(min(i + 1, n - 1)), wl.append(3 * s - 2 * j - 1), wu.append(2 * j + 1 - s)
+    shape = [1] * x.ndim
+    shape[axis] = s * n
+    wl, wu = np.array(wl, np.int64).reshape(shape), np.array(wu, np.int64).reshape(shape)
+    assert ((wl + wu) == 2 * s).all() and (wl > 0).all() and (wu > 0).all()
+    return wl * np.take(x, i0, axis=axis) + wu * np.take(x, i1, axis=axis)
+
+
+def bilinear_exact(x, k):
+    """(N, C, H, W) integers -> the exact interpolated values times 2^(2k + 2), int64, not wrapped."""
+    x = np.asarray(x, np.int64)
+    return _bilinear_axis(_bilinear_axis(x, 1 << k, 2), 1 << k, 3)
+
+
+def upsample_ref(x, fl, scale, mode):
+    """-> (int32 values, fraclen)."""
+    sh, sw = (scale, scale) if isinstance(scale, int) else scale
+    if mode == 'nearest':
+        return wrap32(nearest_exact(x, sh, sw)), fl
+    k = sh.bit_length() - 1
+    assert mode == 'bilinear' and sh == sw == 1 << k and 1 <= k <= 4
+    assert upsample_fl_gain((sh, sw)) == 2 * k + 2
+    return wrap32(bilinear_exact(x, k)), fl + 2 * k + 2
+
+
+def pin_to_torch(x, k):
+    """bilinear_exact against torch in float64: exact equality (|x| 2^(2k + 2) stays far below 2^53)."""
+    import torch
+    import torch.nn.functional as F
+    want = F.interpolate(torch.from_numpy(np.asarray(x, np.float64)), scale_factor=1 << k, mode='bilinear', align_corners=False) * 2.0 ** (2 * k + 2)
+    got = bilinear_exact(x, k)
+    assert np.abs(got).max() < 2 ** 52
+    np.testing.assert_array_equal(got.astype(np.float64), want.numpy())
+
+
+class _Graph(cc._Graph):
+    """concat_cases._Graph with upsample."""
+
+    def upsample(self, t, scale, mode='nearest', label=None):
+        o = self._id(lambda: self.net.upsample(t, scale, mode, label=label))
+        self.v[o] = upsample_ref(self.v[t][0], self.v[t][1], scale, mode)
+        return o
+
+
+# ---- the builders.  Each returns (output tensor ids in output order, [upsample tensor ids])
+def _shift(c):
+    """The first reader's requant shift of the upsampled tensor, less what a bilinear upsample adds: what fills 8 bits at the producer."""
+    return 13 - (c['readers'][0][0] if c['readers'] else 4)
+
+
+def _plain(g, x0, c):
+    """producer -> upsample -> readers (or the upsample itself as an output, alone or next to a reader)."""
+    p = producer(g, x0, 0, c['C'], _shift(c), w_fl=5, relu=c['relu'])
+    up = g.upsample(p, c['scale'], c['mode'], label='up')
+    outs = []
+    if c['readers']:
+        outs.append(readers(g, up, c['readers']))
+        g.output(outs[0])
+    if c['out']:
+        outs.append(up)
+        g.output(up, as_float=c.get('as_float', False))
+    return outs, [up]
+
+
+def _coarse(g, x0, c):
+    """The coarse level of a two-level case: the input max-pooled by the case's scale (the fine map is the input's)."""
+    s = c['scale'] if isinstance(c['scale'], int) else c['scale'][0]
+    return g.maxpool(x0, s, s, 0)
+
+
+def _fpn(g, x0, c):
+    """FPN top-down step: a producer on the coarse level, upsampled, joined with a lateral 1x1 conv of the fine level (fraclen 12 against 13: the
+    join shifts it by 1), one int8 reader behind the join."""
+    top = producer(g, _coarse(g, x0, c), 0, c['C'], 9, w_fl=5, relu=True)
+    up = g.upsample(top, c['scale'], c['mode'], label='up')
+    lateral = producer(g, x0, 1, c['C'], 8, w_fl=4, relu=False)
+    out = readers(g, g.add(up, lateral, relu=False), [(4, False)])
+    g.output(out)
+    return [out], [up]
+
+
+def _unet(g, x0, c):
+    """U-Net decoder step: the upsampled coarse level concatenated with a skip (a producer on the fine level at the upsample's fraclen), one int8
+    reader behind the concat.  c['opts'] chooses the concat's mode; the byte-gather mode asks the upsample for the concat's int8 format."""
+    top = producer(g, _coarse(g, x0, c), 0, c['C'], 9, w_fl=5, relu=True)
+    up = g.upsample(top, c['scale'], c['mode'], label='up')
+    gain = g.v[up][1] - g.v[top][1]
+    skip = producer(g, x0, 1, 24, 9 + gain, w_fl=5 + gain, relu=True)
+    out = readers(g, g.concat([up, skip], label='cat'), [(4, False)])
+    g.output(out)
+    return [out], [up]
+
+
+def _wrap(g, x0, c):
+    """A 3x3 conv over 32 channels (0 .. 255) with weights 64 .. 127: accumulators around 2^22, interpolated at 16x = times 2^10: the exact sums
+    pass 2^31 and the result is their int32 wrap.  The result is the output."""
+    w = synth.rand_uniform_int(11, 'upwrapw', (c['C'], 32, 3, 3), 64, 127).astype(np.int32)
+    p = g.conv(x0, w, None, pad=1, groups=1, weight_fl=0, input_fl=X_FL, input_signed=False, relu=False, quant_input=False)
+    up = g.upsample(p, c['scale'], c['mode'], label='up')
+    g.output(up)
+    exact = bilinear_exact(g.v[p][0], 4)
+    assert (np.abs(exact) >= 2 ** 31).mean() > 0.25, 'the exact sums stay inside int32: the case shows nothing'
+    return [up], [up]
+
+
+def _case(C, H, W, mode, scale, tok, *, tok_off=None, forms=(0, 1), build=_plain, **kw):
+    """H x W: the SOURCE map.  tok / tok_off: the expected plan token with option upsample_i8 = 1 / 0; forms: (int32 forms, int8 forms) the launch
+    writes with upsample_i8 = 1 — all by hand."""
+    c = dict(C=C, H=H, W=W, N=2, mode=mode, scale=scale, tok=tok, tok_off=tok_off or (N32 if mode == 'nearest' else B32), forms=forms, build=build,
+             readers=[(4, False)], out=False, relu=True, cin=8, opts={})
+    c.update(kw)
+    return c
+
+
+U, S = (4, False), (3, True)
+CASES = {
+    # ---- nearest
+    'n_bcast7': _case(40, 1, 1, 'nearest', (7, 7), I8),                               # the ASPP broadcast; 49 pixels per image, two channel blocks
+    'n_bcast33': _case(32, 1, 1, 'nearest', (33, 33), I8),
+    'n_1x3': _case(8, 1, 3, 'nearest', (2, 2), I8),
+    'n_3x1_w4': _case(8, 3, 1, 'nearest', (1, 4), I8),
+    'n_2x2_h4': _case(64, 2, 2, 'nearest', (4, 1), I8),
+    'n_3x5_s35': _case(40, 3, 5, 'nearest', (3, 5), I8),
+    'n_3x5_two': _case(40, 3, 5, 'nearest', (2, 2), I8, forms=(0, 2), readers=[U, S], relu=False),     # 60 pixels per image
+    'n_7x7_three': _case(64, 7, 7, 'nearest', (2, 2), N32, forms=(1, 2), readers=[U, S, (5, False)], relu=False),      # a third format: int32 + `requant:`
+    'n_fpn': _case(40, 3, 5, 'nearest', (2, 2), N32, forms=(1, 0), build=_fpn),
+    'n_unet_i8': _case(40, 3, 5, 'nearest', (2, 2), I8, build=_unet),
+    'n_unet_i32': _case(40, 3, 5, 'nearest', (2, 2), N32, forms=(1, 0), build=_unet, opts={'concat_i8': 0}),
+    'n_out': _case(40, 3, 5, 'nearest', (2, 2), N32, forms=(1, 0), readers=None, out=True),
+    'n_out_f32': _case(8, 7, 7, 'nearest', (2, 2), N32, forms=(1, 0), readers=None, out=True, as_float=True),
+    'n_out_reader': _case(64, 2, 2, 'nearest', (2, 2), N32, forms=(1, 1), out=True),
+    # ---- bilinear (always the int32 mode)
+    'b_1x1_k1': _case(8, 1, 1, 'bilinear', 2, B32),                                    # a constant
+    'b_1x3_k2': _case(40, 1, 3, 'bilinear', 4, B32),
+    'b_3x1_k1': _case(8, 3, 1, 'bilinear', 2, B32),
+    'b_2x2_k3': _case(64, 2, 2, 'bilinear', 8, B32),
+    'b_3x5_k1': _case(40, 3, 5, 'bilinear', 2, B32),
+    'b_3x5_k4': _case(8, 3, 5, 'bilinear', 16, B32),
+    'b_7x7_two': _case(64, 7, 7, 'bilinear', 2, B32, forms=(0, 2), readers=[U, S], relu=False),
+    'b_7x7_three': _case(40, 7, 7, 'bilinear', 2, B32, forms=(1, 2), readers=[U, S, (5, False)], relu=False),
+    'b_fpn': _case(40, 3, 5, 'bilinear', 2, B32, forms=(1, 0), build=_fpn),
+    'b_unet_i8': _case(40, 3, 5, 'bilinear', 2, B32, build=_unet),
+    'b_unet_i32': _case(40, 3, 5, 'bilinear', 2, B32, forms=(1, 0), build=_unet, opts={'concat_i8': 0}),
+    'b_out': _case(40, 7, 7, 'bilinear', 4, B32, forms=(1, 0), readers=None, out=True),
+    'b_out_f32': _case(8, 3, 5, 'bilinear', 2, B32, forms=(1, 0), readers=None, out=True, as_float=True),
+    'b_out_reader': _case(64, 3, 5, 'bilinear', 2, B32, forms=(1, 1), out=True),
+    'b_wrap': _case(40, 3, 3, 'bilinear', 16, B32, forms=(1, 0), build=_wrap, cin=32),
+}
+
+
+def input_hw(c):
+    """The input's map: the source map, except where the case pools the input down to its coarse level first."""
+    if c['build'] in (_fpn, _unet):
+        s = c['scale'] if isinstance(c['scale'], int) else c['scale'][0]
+        return c['H'] * s, c['W'] * s
+    return c['H'], c['W']
+
+
+def make_input(name, n=None):
+    c = CASES[name]
+    return synth.rand_uniform_int(5, f'upx{name}', (n or c['N'], c['cin']) + input_hw(c), 0, 255).astype(np.int32)
+
+
+def build_graph(name, x, record=True):
+    """Returns (graph, output ids, upsample ids)."""
+    c = CASES[name]
+    g = _Graph(x, X_FL, record=record)
+    outs, ups = c['build'](g, next(iter(g.v)), c)
+    return g, outs, ups
+
+
+@functools.lru_cache(maxsize=None)
+def reference(name):
+    """(graph, output ids, upsample ids) of the case over N + 1 images, evaluated on the reference alone, once; nothing may write into its arrays."""
+    return build_graph(name, make_input(name, CASES[name]['N'] + 1), record=False)
+
+
+def plan(name, x, max_batch=None, **opts):
+    g, outs, ups = build_graph(name, x)
+    for k, v in dict(CASES[name]['opts'], **opts).items():
+        g.net.set_option(k, v)
+    g.net.finalize(max_batch or x.shape[0])
+    return g, outs, ups
+
+
+def upsample_lines(net):
+    """[(launch index, plan token, kernel symbol)] of the handle's upsample launches, in launch order."""
+    out = []
+    for i in range(net.num_launches):
+        tok = net.launch_info(i, 1)[0].split(':')[0] + ':'
+        if tok.startswith('upsample_'):
+            out.append((i, tok, net.launch_kernel(i)))
+    return out
+
+
+# ---- the walker of an imported graph (oracle.graph_forward knows neither concat nor upsample)
+def graph_forward(ig, x, input_fraclen=None):
+    import dil_cases
+    V, layer = ig.solve_fraclens(input_fraclen)
+    t = {}
+    for i, o in enumerate(ig.ops):
+        if o.kind == 'input':
+            t[i] = np.ascontiguousarray(x, dtype=np.int32)
+        elif o.kind == 'conv':
+            s = t[o.src]
+            if o.shift is not None:
+                s = oracle.requant(s, layer[i][0], V[o.src], o.signed)
+            y = oracle.conv2d(s, dil_cases.stuffed(o.weight, o.dilation), o.bias, o.stride, o.pad, o.groups)
+            t[i] = oracle.relu(y) if o.relu else y
+        elif o.kind == 'add':
+            y, fl = oracle.add_align(t[o.src], t[o.src2], V[o.src], V[o.src2])
+            assert fl == V[i]
+            t[i] = oracle.relu(y) if o.relu else y
+        elif o.kind == 'maxpool':
+            t[i] = oracle.maxpool(t[o.src], o.kernel, o.stride, o.pad)
+        elif o.kind == 'concat':
+            t[i], fl = cc.concat_align([t[s] for s in o.srcs], [V[s] for s in o.srcs])
+            assert fl == V[i]
+        elif o.kind == 'upsample':
+            t[i], fl = upsample_ref(t[o.src], V[o.src], tuple(o.scale), o.mode)
+            assert fl == V[i]
+        else:
+            raise ValueError(o.kind)
+    return t[ig.output]
+
+
+def int_graph(name):
+    """The case as an IntGraph, op for op what build_graph records (cases whose first output is the only one)."""
+    from f8net_amd.onnx_import import IntGraph, IntOp
+    c = CASES[name]
+    ig = IntGraph(input_signed=False)
+    ig.ops.append(IntOp('input', shape=(c['cin'],) + input_hw(c)))
+
+    class _Rec(_Graph):
+        def __init__(self, x, fl):
+            super().__init__(x, fl, record=False)
+            self.ids = {0: 0}
+
+        def _put(self, o, op):
+            ig.ops.append(op)
+            self.ids[o] = len(ig.ops) - 1
+            return o
+
+        def conv(self, t, w, b, *, stride=1, pad, groups, weight_fl, input_fl, input_signed, relu, label=None, quant_input=True, dilation=1, w_eval=None):
+            o = super().conv(t, w, b, stride=stride, pad=pad, groups=groups, weight_fl=weight_fl, input_fl=input_fl, input_signed=input_signed, relu=relu,
+                             quant_input=quant_input, dilation=dilation)
+            return self._put(o, IntOp('conv', src=self.ids[t], weight=np.asarray(w, np.int32),
+                                      bias=np.zeros(w.shape[0], np.int32) if b is None else np.asarray(b, np.int32), stride=stride, pad=pad, groups=groups,
+                                      kernel=w.shape[2], shift=(self.v[t][1] - input_fl) if quant_input else None, signed=input_signed, relu=relu,
+                                      key=f'layer{len(ig.ops)}', dilation=dilation))
+
+        def add(self, a, b, relu=False):
+            o = super().add(a, b, relu=relu)
+            fa, fb = self.v[a][1], self.v[b][1]
+            s, s2 = (a, b) if fa <= fb else (b, a)                    # src is the operand that shifts
+            return self._put(o, IntOp('add', src=self.ids[s], src2=self.ids[s2], shift=abs(fa - fb), relu=relu, swap=s == b))
+
+        def maxpool(self, t, k, stride, pad):
+            return self._put(super().maxpool(t, k, stride, pad), IntOp('maxpool', src=self.ids[t], kernel=k, stride=stride, pad=pad))
+
+        def concat(self, ts, label=None):
+            o = super().concat(ts)
+            fl = self.v[o][1]
+            return self._put(o, IntOp('concat', src=self.ids[ts[0]], srcs=[self.ids[t] for t in ts], shifts=[fl - self.v[t][1] for t in ts]))
+
+        def upsample(self, t, scale, mode='nearest', label=None):
+            sc = (scale, scale) if isinstance(scale, int) else tuple(scale)
+            return self._put(super().upsample(t, scale, mode), IntOp('upsample', src=self.ids[t], mode=mode, scale=sc))
+
+    x = make_input(name)
+    g = _Rec(x, X_FL)
+    outs, _ = c['build'](g, 0, c)
+    ig.output = g.ids[outs[0]]
+    ig.output_float = False
+    return ig, g, outs[0]
