@@ -48,6 +48,7 @@ SYMBOLS = [
     ('f8_net_input', _i, [_vp, _i, _i, _i, _i]),
     ('f8_net_conv', _i, [_vp, _i, ctypes.POINTER(ConvDesc), _vp, _vp]),
     ('f8_net_conv_dilated', _i, [_vp, _i, ctypes.POINTER(ConvDesc), _i, _vp, _vp]),
+    ('f8_net_conv_transpose', _i, [_vp, _i, ctypes.POINTER(ConvDesc), _i, _vp, _vp]),
     ('f8_net_add', _i, [_vp, _i, _i, _i]),
     ('f8_net_concat', _i, [_vp, ctypes.POINTER(ctypes.c_int), _i]),
     ('f8_net_upsample', _i, [_vp, _i, _i, _i, _i]),

@@ -218,6 +218,30 @@ struct UpsampleArgs {
     QuantOut q[2];
 };
 
+// Transposed convolution (f8_deconv.hip; f8_net_conv_transpose), stride 2 .. 4: [H, W] -> [P, Q] = [(H - 1) s - 2 pad + k + output_padding, ...].  The output
+// pixels of one PHASE (rh, rw) = ((oh + pad) % s, (ow + pad) % s) see the same kernel taps kh = rh + s th, th < Th, at the input rows ih = a - th
+// (oh = s a + rh - pad): one phase is one plain implicit GEMM over its sub-grid of A x Cn output pixels per image, K = Th * Tw * CK.
+constexpr int kMaxDeconvPhases = 16;       // stride <= 4
+struct DeconvPhase {
+    int32_t rh, rw;                        // the phase
+    int32_t a0, c0, A, Cn;                 // first row / column index (a, c) of its sub-grid, the sub-grid's rows / columns (0: the phase has no output pixel)
+    int32_t Th, Tw;                        // live taps per axis: ceil((k - rh) / s), ceil((k - rw) / s); 0: its outputs are the bias alone
+    uint32_t w_off;                        // byte offset of its packed weights [coutP][Th * Tw * CK] in MFMA-fragment order: [cout tile][K32 step][lane][16 B] (pack_deconv_weights)
+    uint32_t mAC, mC; int32_t s1AC, s2AC, s1C, s2C;   // magic numbers (fast_div) for / (A * Cn), / Cn
+};
+struct DeconvArgs {
+    const int8_t* x; uint32_t x_bytes;     // NHWC int8 [N][H][W][CK]
+    const int8_t* w; uint32_t w_bytes;     // the phases' weight matrices, one behind the other
+    const int32_t* bias;                   // [row classes * ncc][coutP] border-class bias table; ncc = 0: one class
+    const uint8_t* rowcls; const uint8_t* colcls; int32_t ncc;   // class of OUTPUT row oh / column ow: the set of kernel rows that meet an in-image input row
+    int32_t N, H, W, P, Q, CK, coutP, stride, pad, nph;
+    int32_t relu0;
+    int32_t* out32;
+    QuantOut q[2];
+    int32_t tiles;                         // pixel tiles (64 pixels: a wave's two MFMA tiles) of the largest phase at N images (set by the launcher)
+    DeconvPhase ph[kMaxDeconvPhases];
+};
+
 struct OutArgs {                           // NHWC int32 -> NCHW int32 / float32
     const int32_t* x; int32_t N, C, HW, Cs;
     void* out; int32_t as_float;
@@ -625,6 +649,9 @@ hipError_t launch_concat(const ConcatArgs& a, int inst, hipStream_t s);
 int upsample_inst(bool bilinear, bool i8);                         // f8_upsample.hip.  0: upsample_i8_kernel, 1: upsample_i32_kernel<false> (nearest), 2: upsample_i32_kernel<true> (bilinear)
 const char* upsample_kernel_name(int inst);
 hipError_t launch_upsample(const UpsampleArgs& a, int inst, hipStream_t s);
+int deconv_inst(const DeconvArgs& a);                              // f8_deconv.hip.  The cout tiles per wave: 2 (deconv_kernel<2>, coutP >= 64) or 1 (deconv_kernel<1>)
+const char* deconv_kernel_name(int inst);
+hipError_t launch_deconv(const DeconvArgs& a, int inst, hipStream_t s);
 hipError_t launch_input(const InArgs& a, int inst, hipStream_t s);
 const char* output_kernel_name();
 hipError_t launch_output(const OutArgs& a, hipStream_t s);

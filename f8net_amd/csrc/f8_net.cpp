@@ -88,12 +88,16 @@ enum Role { R_NONE, R_B0, R_B2, R_B4, R_SC };
 // The chain launches: bottleneck stage (f8_chain.hip; the 7x7 stage over clusters, f8_cchain.hip), BasicBlocks (f8_bchain.hip), BasicBlocks of a 7x7 x 512
 // stage over clusters of eight workgroups (option fuse_bchain7, f8_bcchain.hip), inverted residuals (f8_irchain.hip).  Independent of the block kind.
 enum ChainKind { C_NONE, C_STAGE, C_BASIC, C_BASIC_CLUSTER, C_IR };
-enum NodeKind { N_INPUT, N_CONV, N_ADD, N_MAXPOOL, N_AVGPOOL, N_LINEAR, N_CONCAT, N_UPSAMPLE };
+// N_DECONV (f8_net_conv_transpose at stride >= 2) is a kind of its own, not a flag on N_CONV: every matcher asks `kind == N_CONV` and so never sees it — a
+// launch of its own (f8_deconv.hip), no block, no chain, no join in its epilogue.  It READS like a conv: its source's int8 form in its consumer format.
+enum NodeKind { N_INPUT, N_CONV, N_ADD, N_MAXPOOL, N_AVGPOOL, N_LINEAR, N_CONCAT, N_UPSAMPLE, N_DECONV };
 struct Node {
     int kind; int a = -1, b = -1; int out = -1;
     f8_conv_desc cd{};                 // conv / linear (as 1x1 conv)
     int dil = 1;                       // dilation (f8_net_conv_dilated; 1 for kernel 1).  > 1: a launch of its own on conv_igemm_kernel / f8_dwk.hip — every matcher refuses it
-    std::vector<int8_t> w; std::vector<int32_t> bias;   // raw OIHW int8 + bias
+    std::vector<int8_t> w; std::vector<int32_t> bias;   // raw OIHW int8 + bias (N_DECONV: [cin][cout][k][k], nn.ConvTranspose2d's layout)
+    int out_pad = 0;                   // N_DECONV: output_padding
+    DeconvPhase dph[kMaxDeconvPhases]{};   // N_DECONV: the phase table (pack_deconv_weights; w_off relative to Node::w_off), cd.stride^2 entries
     int acc_ok = -1;                   // conv_acc_bounded(), cached
     int64_t acc_max = -2;              // conv_acc_max(), cached (-2: not computed yet)
     int relu = 0;                      // add
@@ -124,7 +128,7 @@ struct Node {
     size_t rc_off = 0, cc_off = 0; int ncc = 0;      // border-class tables (0 = single class)
     ConvTile tile{};
 };
-enum StepKind { S_INPUT, S_CONV, S_DW, S_ADD, S_MAXPOOL, S_AVGPOOL, S_REQUANT, S_OUTPUT, S_FUSED, S_STEMPOOL, S_IR, S_P12, S_CHAIN, S_BCHAIN, S_HEAD2, S_IRCHAIN, S_DWS, S_DWS7, S_IRK, S_GCONV, S_CONCAT, S_UPSAMPLE };
+enum StepKind { S_INPUT, S_CONV, S_DW, S_ADD, S_MAXPOOL, S_AVGPOOL, S_REQUANT, S_OUTPUT, S_FUSED, S_STEMPOOL, S_IR, S_P12, S_CHAIN, S_BCHAIN, S_HEAD2, S_IRCHAIN, S_DWS, S_DWS7, S_IRK, S_GCONV, S_CONCAT, S_UPSAMPLE, S_DECONV };
 // The kernel of a step whose kind has several, chosen once by the step's emitter (pass 3); bind_step, run_step and f8_net_autotune switch on it.
 //   S_CONV:  conv_igemm (f8_kernels.hip), the LDS-patch 3x3 (f8_conv3x3.hip), conv1x1_wreg (f8_wreg.hip), conv1x1_wstat (f8_wstat.hip),
 //            conv3x3s2_wreg (f8_s2conv.hip), the 1x1 conv + average pool (f8_pool.hip), the classifier fc_dense (f8_fc.hip)
@@ -150,7 +154,7 @@ struct Step {
     double bytes_per_img = 0, bytes_const = 0, ops_per_img = 0;
     double valu_per_img = 0;           // ESSENTIAL vector lane-operations per image (f8_net_launch_valu): what the reference's semantics need once the MFMAs are done
     // the launcher's arguments as far as the plan decides them (bind_step); run_step copies them and adds what the run decides
-    std::variant<std::monostate, ConvArgs, StemPoolArgs, FusedArgs, ChainArgs, BChainArgs, BCChainArgs, IRArgs, IRKArgs, IRChainArgs, DwsArgs, Dws7Args, DwArgs, GConvArgs, AddArgs, PoolArgs, AvgArgs, OutArgs, ConcatArgs, UpsampleArgs> args;
+    std::variant<std::monostate, ConvArgs, StemPoolArgs, FusedArgs, ChainArgs, BChainArgs, BCChainArgs, IRArgs, IRKArgs, IRChainArgs, DwsArgs, Dws7Args, DwArgs, GConvArgs, AddArgs, PoolArgs, AvgArgs, OutArgs, ConcatArgs, UpsampleArgs, DeconvArgs> args;
     int inst = 0;                      // the instance the launcher starts (the family's *_inst, f8_internal.h; bind_step)
     // S_CHAIN / S_BCHAIN: geometry, workgroups per image and resident per CU, the 7x7 cluster form (f8_cchain.hip)
     int C = 0, MID = 0, H = 0, W = 0, cin0 = 0, tiles = 0, wg_per_cu = 1; bool cluster = false;
@@ -242,10 +246,12 @@ static int64_t conv_acc_max(Node& nd) {
     if (nd.cd.cout > 0 && !nd.w.empty() && nd.w.size() % (size_t)nd.cd.cout == 0) {
         const size_t per = nd.w.size() / (size_t)nd.cd.cout;
         const int64_t xmax = (nd.cd.quant_input && nd.cd.input_signed) ? 127 : 255;
+        const size_t kk = (size_t)nd.cd.kernel * nd.cd.kernel;
         m = 0;
         for (int o = 0; o < nd.cd.cout; ++o) {
             int64_t s = 0;
-            for (size_t k = 0; k < per; ++k) { const int v = nd.w[(size_t)o * per + k]; s += v < 0 ? -v : v; }
+            // a transposed conv's weights are [cin][cout][k][k]; the sum over ALL taps bounds every phase, which sees a subset of them
+            for (size_t k = 0; k < per; ++k) { const int v = nd.kind == N_DECONV ? nd.w[((k / kk) * nd.cd.cout + o) * kk + k % kk] : nd.w[(size_t)o * per + k]; s += v < 0 ? -v : v; }
             const int64_t b = o < (int)nd.bias.size() ? (int64_t)nd.bias[o] : 0;
             m = std::max(m, s * xmax + (b < 0 ? -b : b));
         }
@@ -271,7 +277,7 @@ static int64_t tensor_amax(f8_net* net, int t, int depth = 0) {
     int64_t m = -1;
     if (T.prod >= 0) {
         Node& nd = net->nodes[T.prod];
-        if (nd.kind == N_CONV) m = conv_acc_max(nd);
+        if (nd.kind == N_CONV || nd.kind == N_DECONV) m = conv_acc_max(nd);
         else if (nd.kind == N_MAXPOOL) m = tensor_amax(net, nd.a, depth + 1);
         else if (nd.kind == N_ADD) {
             const int64_t a = tensor_amax(net, nd.a, depth + 1), b = tensor_amax(net, nd.b, depth + 1);
@@ -632,6 +638,60 @@ int f8_net_conv_dilated(f8_net* net, int src, const f8_conv_desc* desc, int dila
     return add_conv_node(net, src, *desc, dilation, w, b, N_CONV, "f8_net_conv_dilated");
 }
 
+int f8_net_conv_transpose(f8_net* net, int src, const f8_conv_desc* desc, int output_padding, const int32_t* w, const int32_t* b) {
+    const char* who = "f8_net_conv_transpose";
+    if (!desc) return fail(F8_ERR_INVALID, "%s: null desc", who);
+    const f8_conv_desc& d = *desc;
+    if (const int rc = check_t(net, src, who)) return rc;
+    const Tensor s = net->tensors[src];
+    if (d.cin != s.C) return fail(F8_ERR_INVALID, "%s: cin %d != source channels %d", who, d.cin, s.C);
+    if (d.kernel < 1 || d.stride < 1 || d.pad < 0 || d.cout < 1)
+        return fail(F8_ERR_INVALID, "%s: bad geometry (kernel %d, stride %d, pad %d, cout %d)", who, d.kernel, d.stride, d.pad, d.cout);
+    if (d.groups != 1) return fail(F8_ERR_UNSUPPORTED, "%s: groups %d: only groups == 1 is built", who, d.groups);
+    if (d.kernel > 8) return fail(F8_ERR_UNSUPPORTED, "%s: kernel %d > 8 is not built", who, d.kernel);
+    if (d.stride > 4) return fail(F8_ERR_UNSUPPORTED, "%s: stride %d > 4 is not built (kernel %d)", who, d.stride, d.kernel);
+    if (d.pad > d.kernel - 1) return fail(F8_ERR_UNSUPPORTED, "%s: pad %d > kernel - 1 = %d is not built", who, d.pad, d.kernel - 1);
+    if (output_padding < 0 || output_padding >= d.stride)
+        return fail(F8_ERR_INVALID, "%s: output_padding %d outside [0, stride %d)", who, output_padding, d.stride);
+    if (d.weight_fl < 0 || d.weight_fl > 31) return fail(F8_ERR_INVALID, "%s: bad weight_fl %d", who, d.weight_fl);
+    int n;
+    if (const int rc = consumer_format(s, d, &n, who)) return rc;
+    const int64_t P = (int64_t)(s.H - 1) * d.stride - 2 * d.pad + d.kernel + output_padding, Q = (int64_t)(s.W - 1) * d.stride - 2 * d.pad + d.kernel + output_padding;
+    if (P < 1 || Q < 1)
+        return fail(F8_ERR_INVALID, "%s: empty output %lld x %lld from a %d x %d map (kernel %d, stride %d, pad %d, output_padding %d)", who, (long long)P, (long long)Q,
+                    s.H, s.W, d.kernel, d.stride, d.pad, output_padding);
+    if (P > INT32_MAX / 4 || Q > INT32_MAX / 4 || P * Q > INT32_MAX / 4 || P * Q * round_up(d.cout, 32) > INT32_MAX / 4)
+        return fail(F8_ERR_UNSUPPORTED, "%s: the %lld x %lld x %d result exceeds 2 GiB per tensor", who, (long long)P, (long long)Q, d.cout);
+    if (!w) return fail(F8_ERR_INVALID, "%s: null weight", who);
+    const int k = d.kernel;
+    const size_t wn = (size_t)d.cin * d.cout * k * k;
+    for (size_t i = 0; i < wn; ++i)
+        if (w[i] < -128 || w[i] > 127) return fail(F8_ERR_INVALID, "%s: weight %d does not fit int8", who, w[i]);
+    if (d.stride == 1) {
+        // not a new op: the plain conv with pad' = k - 1 - pad over the weights flipped in both axes and swapped to [cout][cin][k][k]
+        std::vector<int32_t> wc(wn);
+        for (int ci = 0; ci < d.cin; ++ci)
+            for (int co = 0; co < d.cout; ++co)
+                for (int r = 0; r < k; ++r)
+                    for (int c = 0; c < k; ++c)
+                        wc[(((size_t)co * d.cin + ci) * k + (k - 1 - r)) * k + (k - 1 - c)] = w[(((size_t)ci * d.cout + co) * k + r) * k + c];
+        f8_conv_desc c = d;
+        c.pad = k - 1 - d.pad;
+        return add_conv_node(net, src, c, 1, wc.data(), b, N_CONV, who);
+    }
+    Node nd; nd.kind = N_DECONV; nd.a = src; nd.cd = d; nd.out_pad = output_padding;
+    nd.w.resize(wn);
+    for (size_t i = 0; i < wn; ++i) nd.w[i] = (int8_t)w[i];
+    nd.bias.assign(d.cout, 0);
+    if (b) for (int i = 0; i < d.cout; ++i) nd.bias[i] = b[i];
+    net->nodes.push_back(std::move(nd));
+    const int id = (int)net->nodes.size() - 1;
+    const int t = new_tensor(net, d.cout, (int)P, (int)Q, d.weight_fl + d.input_fl, id);
+    net->nodes[id].out = t;
+    net->tensors[src].consumers.push_back(id);
+    return t;
+}
+
 int f8_net_linear(f8_net* net, int src, const f8_linear_desc* d, const int32_t* w, const int32_t* b) {
     if (!d) return fail(F8_ERR_INVALID, "f8_net_linear: null desc");
     int rc = check_t(net, src, "f8_net_linear");
@@ -882,6 +942,100 @@ static void pack_conv_bias(f8_net* net, Node& nd, const std::vector<long long>& 
                 uint32_t b = (uint32_t)nd.bias[o];
                 if (!d.input_signed) b += (uint32_t)(128ll * sum);
                 bp[(rc * cmasks.size() + cc) * (size_t)nd.coutP + o] = (int32_t)b;
+            }
+    if (classes) {
+        nd.rc_off = round_up_z(net->wblob.size(), 256);
+        net->wblob.resize(nd.rc_off + rowcls.size(), 0);
+        memcpy(net->wblob.data() + nd.rc_off, rowcls.data(), rowcls.size());
+        nd.cc_off = round_up_z(net->wblob.size(), 256);
+        net->wblob.resize(nd.cc_off + colcls.size(), 0);
+        memcpy(net->wblob.data() + nd.cc_off, colcls.data(), colcls.size());
+    }
+}
+
+// A transposed conv's weights, biases and phase table.  Output phase (rh, rw) = ((oh + pad) % s, (ow + pad) % s) sees the kernel rows
+// kh = rh + s th, th < Th = ceil((k - rh) / s) — none where k <= rh — at the input row ih = a - th, oh = s a + rh - pad; its weights are one plain
+// GEMM operand [coutP][Th * Tw * CK], K = (th * Tw + tw) * CK + ci, stored in MFMA-fragment order (as pack_frag_weights: [cout tile of 32][K32 step]
+// [lane 0..63][16 B], lane l = row l & 31 of the tile, bytes [32 step + 16 (l >> 5), +16): one coalesced 1 KB per wave load), the phases one behind
+// the other from Node::w_off (DeconvPhase::w_off is relative to it; Node::ktot = the bytes per output channel summed over the phases = k * k * CK).
+// Bias: the border-class table of pack_conv_bias with the transposed conv's rule — the class of an OUTPUT row oh is the set of kernel rows kh with
+// oh + pad - kh = s ih for an in-image ih, and bias[rowclass * ncc + colclass][co] = b + 128 * (sum of w over that set x the column's set) for unsigned
+// (biased) inputs; an empty set leaves the bias alone.  Rows near either border miss taps even at pad 0, so unsigned inputs always have classes.
+static void pack_deconv_weights(f8_net* net, Node& nd) {
+    const f8_conv_desc& d = nd.cd;
+    const Tensor& src = net->tensors[nd.a]; const Tensor& dst = net->tensors[nd.out];
+    const int k = d.kernel, s = d.stride, CK = src.Cs;
+    nd.coutP = round_up(d.cout, 32);
+    nd.ck = CK; nd.ktot = k * k * CK;
+    nd.w_off = round_up_z(net->wblob.size(), 256);
+    net->wblob.resize(nd.w_off + (size_t)nd.coutP * nd.ktot, 0);
+    auto wraw = [&](int ci, int co, int r, int c) { return nd.w[(((size_t)ci * d.cout + co) * k + r) * k + c]; };
+    size_t off = 0;
+    for (int rh = 0; rh < s; ++rh)
+        for (int rw = 0; rw < s; ++rw) {
+            DeconvPhase& p = nd.dph[rh * s + rw];
+            p = DeconvPhase{};
+            p.rh = rh; p.rw = rw;
+            p.Th = rh < k ? (k - rh + s - 1) / s : 0; p.Tw = rw < k ? (k - rw + s - 1) / s : 0;
+            // the sub-grid: a >= a0 is the first index with oh = s a + rh - pad >= 0, and A of them stay below the output's height
+            auto grid = [&](int r, int n_out, int32_t* first, int32_t* count) {
+                *first = d.pad > r ? (d.pad - r + s - 1) / s : 0;
+                const int last = n_out - 1 + d.pad - r >= 0 ? (n_out - 1 + d.pad - r) / s : -1;
+                *count = std::max(0, last - *first + 1);
+            };
+            grid(rh, dst.H, &p.a0, &p.A);
+            grid(rw, dst.W, &p.c0, &p.Cn);
+            make_magic((uint32_t)std::max(1, p.A * p.Cn), &p.mAC, &p.s1AC, &p.s2AC);
+            make_magic((uint32_t)std::max(1, p.Cn), &p.mC, &p.s1C, &p.s2C);
+            p.w_off = (uint32_t)off;
+            const size_t kp = (size_t)p.Th * p.Tw * CK;
+            int8_t* wp = (int8_t*)net->wblob.data() + nd.w_off + off;
+            for (int co = 0; co < d.cout; ++co)
+                for (int th = 0; th < p.Th; ++th)
+                    for (int tw = 0; tw < p.Tw; ++tw)
+                        for (int ci = 0; ci < d.cin; ++ci) {
+                            const size_t kidx = ((size_t)th * p.Tw + tw) * CK + ci, nk = kp / 32;      // K32 step kidx / 32, lane half (kidx % 32) / 16
+                            wp[((((size_t)(co >> 5) * nk + kidx / 32) * 64) + ((kidx % 32) / 16) * 32 + (co & 31)) * 16 + kidx % 16] = wraw(ci, co, rh + s * th, rw + s * tw);
+                        }
+            off += (size_t)nd.coutP * kp;
+        }
+    // per-tap weight sums and the class tables
+    std::vector<long long> tapsum((size_t)d.cout * k * k, 0);
+    for (int ci = 0; ci < d.cin; ++ci)
+        for (int co = 0; co < d.cout; ++co)
+            for (int r = 0; r < k; ++r)
+                for (int c = 0; c < k; ++c) tapsum[((size_t)co * k + r) * k + c] += wraw(ci, co, r, c);
+    std::vector<uint32_t> rmasks, cmasks;
+    std::vector<uint8_t> rowcls(dst.H, 0), colcls(dst.W, 0);
+    const bool classes = !d.input_signed;
+    if (classes) {
+        auto classify = [&](int n_out, int n_in, std::vector<uint32_t>& masks, std::vector<uint8_t>& cls) {
+            for (int o = 0; o < n_out; ++o) {
+                uint32_t mk = 0;
+                for (int r = 0; r < k; ++r) { const int v = o + d.pad - r; if (v >= 0 && v % s == 0 && v / s < n_in) mk |= 1u << r; }
+                size_t id = 0;
+                while (id < masks.size() && masks[id] != mk) ++id;
+                if (id == masks.size()) masks.push_back(mk);
+                cls[o] = (uint8_t)id;
+            }
+        };
+        classify(dst.H, src.H, rmasks, rowcls);
+        classify(dst.W, src.W, cmasks, colcls);
+    } else {
+        rmasks.push_back(0); cmasks.push_back(0);                   // signed inputs: zero is zero, the bias is the bias
+    }
+    nd.ncc = classes ? (int)cmasks.size() : 0;
+    nd.b_off = round_up_z(net->wblob.size(), 256);
+    net->wblob.resize(nd.b_off + rmasks.size() * cmasks.size() * (size_t)nd.coutP * 4, 0);
+    int32_t* bp = (int32_t*)(net->wblob.data() + nd.b_off);
+    for (size_t rc = 0; rc < rmasks.size(); ++rc)
+        for (size_t cc = 0; cc < cmasks.size(); ++cc)
+            for (int o = 0; o < d.cout; ++o) {
+                long long sum = 0;
+                for (int r = 0; r < k; ++r)
+                    for (int c = 0; c < k; ++c)
+                        if (((rmasks[rc] >> r) & 1u) && ((cmasks[cc] >> c) & 1u)) sum += tapsum[((size_t)o * k + r) * k + c];
+                bp[(rc * cmasks.size() + cc) * (size_t)nd.coutP + o] = (int32_t)((uint32_t)nd.bias[o] + (uint32_t)(128ll * sum));
             }
     if (classes) {
         nd.rc_off = round_up_z(net->wblob.size(), 256);
@@ -1851,6 +2005,15 @@ static void plan_tensor_forms(f8_net* net) {
                 if (nd.fused_add >= 0 && nd.dual < 0 && bk != B_BASIC_OPENING && bk != B_BASIC_JOIN) add_form(stream(), FORM_I32, 0, 0);
                 break;
             }
+            case N_DECONV: {
+                // reads its source as a conv of its own does: the int8 form in its consumer format, written by the source's producer in its epilogue
+                // (a third format of one tensor: a requant: step from the int32 form, select_outputs).  No matcher counts it among a block's readers, so
+                // a source inside a would-be fused launch is no private intermediate and the launch is cut there, as by an output tap.
+                int n = 0;
+                consumer_format(T[nd.a], nd.cd, &n, "finalize");
+                add_form(T[nd.a], FORM_I8, n, nd.cd.input_signed ? 1 : 0);
+                break;
+            }
             case N_ADD:
                 if (nd.fused_into < 0) { add_form(T[nd.a], FORM_I32, 0, 0); add_form(T[nd.b], FORM_I32, 0, 0); }
                 break;
@@ -2379,6 +2542,28 @@ static int emit_gconv(f8_net* net, int i, Step& st, std::vector<int>* extra) {
     return F8_OK;
 }
 
+// a transposed conv (stride >= 2): always a launch of its own on deconv_kernel (f8_deconv.hip), no join
+static int emit_deconv(f8_net* net, int i, Step& st, std::vector<int>* extra) {
+    auto& T = net->tensors;
+    Node& nd = net->nodes[i];
+    const f8_conv_desc& d = nd.cd;
+    const Tensor& s = T[nd.a]; Tensor& o = T[nd.out];
+    st.kind = S_DECONV;
+    if (const int rc = conv_input_i8(net, nd, &st.src_t, &st.src_f)) return rc;
+    st.relu0 = d.relu;
+    pack_deconv_weights(net, nd);
+    if (o.forms.empty()) add_form(o, FORM_I32, 0, 0);
+    select_outputs(net, nd.out, &st.out, extra);
+    const double ipx = (double)s.H * s.W, opx = (double)o.H * o.W;
+    st.ops_per_img = 2.0 * ipx * d.kernel * d.kernel * d.cin * d.cout;      // every input pixel meets every tap once (what lands outside the output is cropped)
+    st.bytes_per_img = ipx * s.Cs + out_bytes(st, o, opx);                  // input once + the output forms
+    st.bytes_const = (double)nd.coutP * (nd.ktot + 4);
+    st.valu_per_img = 3.0 * opx * o.Cs * out_forms8(st);
+    char buf[64]; snprintf(buf, sizeof buf, "deconv%dx%ds%d:", d.kernel, d.kernel, d.stride);
+    st.name = buf + tname(net, nd.out);
+    return F8_OK;
+}
+
 // the launch of conv node i: the chain whose last block it hosts, else the block it hosts, else a conv of its own
 static int emit_conv_family(f8_net* net, int i, int max_batch, Step& st, std::vector<int>* extra) {
     static int (*const emit_chain_kind[])(f8_net*, int, Step&, std::vector<int>*) = {nullptr, emit_chain, emit_bchain, emit_bcchain, emit_irchain};   // by ChainKind
@@ -2563,6 +2748,7 @@ static int emit_steps(f8_net* net, int max_batch) {
             case N_AVGPOOL: rc = emit_avgpool(net, i, st, &extra); break;
             case N_CONCAT: rc = emit_concat(net, i, st, &extra); break;
             case N_UPSAMPLE: rc = emit_upsample(net, i, st, &extra); break;
+            case N_DECONV: rc = emit_deconv(net, i, st, &extra); break;
         }
         if (rc) return rc;
         net->steps.push_back(st);
@@ -3116,6 +3302,21 @@ static int bind_step(f8_net* net, Step& st) {
             gconv_kernel_name(kb, sizeof kb, a);                  // integer requantisation whatever requant_float says (as f8_dwk.hip)
             out_formats(a.q); st.args = a; break;
         }
+        case S_DECONV: {
+            const Tensor& sT = T[st.src_t];
+            const Tensor& oT = T[nd.out];
+            DeconvArgs a{};
+            a.w = W8(nd.w_off); a.w_bytes = (uint32_t)((size_t)nd.coutP * nd.ktot);
+            a.bias = B32(nd.b_off);
+            a.ncc = nd.ncc;
+            if (nd.ncc > 0) { a.rowcls = (const uint8_t*)W8(nd.rc_off); a.colcls = (const uint8_t*)W8(nd.cc_off); }
+            a.H = sT.H; a.W = sT.W; a.P = oT.H; a.Q = oT.W; a.CK = sT.Cs; a.coutP = nd.coutP; a.stride = nd.cd.stride; a.pad = nd.cd.pad;
+            a.nph = a.stride * a.stride;
+            for (int k = 0; k < a.nph; ++k) a.ph[k] = nd.dph[k];
+            a.relu0 = st.relu0;
+            snprintf(kb, sizeof kb, "%s", deconv_kernel_name(st.inst = deconv_inst(a)));      // integer requantisation whatever requant_float says (as f8_gconv.hip)
+            out_formats(a.q); st.args = a; break;
+        }
         case S_ADD: case S_REQUANT: {
             AddArgs a{};
             a.Cs = T[st.src_t].Cs; a.a_shl = st.acc_shl; a.b_shl = st.res_shl; a.relu = st.relu1;
@@ -3543,6 +3744,14 @@ static int run_step(const f8_net* net, const RunIO& io, const Step& st, int n0, 
             a.x = (const int8_t*)fp(sF); a.x_bytes = (uint32_t)(sF.bytes_per_img * N); a.N = N;
             fill_out(&a.out32, a.q);
             e = launch_gconv(a, s);
+            break;
+        }
+        case S_DECONV: {
+            const Form& sF = T[st.src_t].forms[st.src_f];
+            DeconvArgs a = std::get<DeconvArgs>(st.args);
+            a.x = (const int8_t*)fp(sF); a.x_bytes = (uint32_t)(sF.bytes_per_img * N); a.N = N;
+            fill_out(&a.out32, a.q);
+            e = launch_deconv(a, st.inst, s);
             break;
         }
         case S_ADD: case S_REQUANT: {
@@ -3993,7 +4202,7 @@ static int input_sign(const f8_net* net, const char* who) {
     int sgn = -1;
     for (int c : in.consumers) {
         const Node& nd = net->nodes[c];
-        if (nd.kind != N_CONV && nd.kind != N_LINEAR) return fail(F8_ERR_UNSUPPORTED, "%s: the input must feed convolutions", who);
+        if (nd.kind != N_CONV && nd.kind != N_LINEAR && nd.kind != N_DECONV) return fail(F8_ERR_UNSUPPORTED, "%s: the input must feed convolutions", who);
         if (sgn >= 0 && sgn != (nd.cd.input_signed ? 1 : 0)) return fail(F8_ERR_UNSUPPORTED, "%s: consumers disagree on signedness", who);
         sgn = nd.cd.input_signed ? 1 : 0;
     }

@@ -76,6 +76,23 @@ class F8Net:
             self._L.f8_net_set_label(self._h, t, label.encode())
         return t
 
+    def conv_transpose(self, src, weight, bias, *, stride, pad, output_padding=0, weight_fl, input_fl, input_signed,
+                       quant_input=True, relu=False, label=None):
+        """Transposed convolution (f8_net_conv_transpose): weight [cin, cout, k, k] as nn.ConvTranspose2d.weight; the result is
+        [(H - 1) stride - 2 pad + k + output_padding]^2 at fraclen weight_fl + input_fl.  stride 1 is recorded as the equivalent plain conv."""
+        w = _np_i32(weight)
+        cin, cout, k, k2 = w.shape
+        assert k == k2
+        d = ConvDesc(cin=cin, cout=cout, kernel=k, stride=stride, pad=pad, groups=1,
+                     weight_fl=int(weight_fl), input_fl=int(input_fl), input_signed=int(bool(input_signed)),
+                     quant_input=int(bool(quant_input)), relu=int(bool(relu)))
+        b = None if bias is None else _np_i32(bias)
+        t = check(self._L.f8_net_conv_transpose(self._h, src, ctypes.byref(d), int(output_padding), w.ctypes.data,
+                                                None if b is None else b.ctypes.data))
+        if label:
+            self._L.f8_net_set_label(self._h, t, label.encode())
+        return t
+
     def linear(self, src, weight, bias, *, weight_fl, input_fl, input_signed, quant_input=True, label=None):
         w = _np_i32(weight)
         d = LinearDesc(in_features=w.shape[1], out_features=w.shape[0], weight_fl=int(weight_fl),

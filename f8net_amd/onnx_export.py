@@ -8,6 +8,7 @@ opset-11 vocabulary is written directly from the integer graph — per op the no
                                    Clip(f32 bounds), Cast(i32)                      (fix_quant_ops.py:99-112)
     int_op_only_fix_quant, n <= 0  Pow/Cast/Mul, Clip, Cast(i32)                    (fix_quant_ops.py:105-112)
     conv / ReLU                    Conv(int32 W, B initializers), Relu, Cast(i32)
+    transposed conv / ReLU         ConvTranspose(int32 W [cin, cout, k, k], B; strides, pads, output_padding), Relu, Cast(i32)
     residual join                  Pow/Cast/Mul, Add, Clip(-+2^31 as f32), Cast(i32) [, Relu, Cast]   (fix_resnet.py:40-54,77)
     head max-pool                  Cast(f32), MaxPool, Cast(i32)                     (fix_resnet.py:358-359)
     FXQAvgPool2d                   Cast(i64), ReduceSum(-1) x2, Cast(i32)            (fix_quant_ops.py:130-133)
@@ -121,7 +122,7 @@ def export_graph(ig: IntGraph) -> bytes:
             name[t] = 'input'
             in_dims = ['batch_size'] + list(o.shape)
             continue
-        if o.kind in ('conv', 'linear'):
+        if o.kind in ('conv', 'deconv', 'linear'):
             s = name[o.src]
             if o.kind == 'linear':                                   # x.view(x.size(0), -1), fix_resnet.py:371
                 b0 = w.emit('Gather', [w.emit('Shape', [s]), w.const(0, np.int64)], {'axis': 0})
@@ -158,6 +159,9 @@ def export_graph(ig: IntGraph) -> bytes:
             if o.kind == 'conv':
                 y = w.emit('Conv', ins, {'dilations': [int(o.dilation)] * 2, 'group': int(o.groups), 'kernel_shape': [o.kernel] * 2,
                                          'pads': [o.pad] * 4, 'strides': [o.stride] * 2})
+            elif o.kind == 'deconv':
+                y = w.emit('ConvTranspose', ins, {'dilations': [1, 1], 'group': 1, 'kernel_shape': [o.kernel] * 2, 'output_padding': [int(o.output_padding)] * 2,
+                                                  'pads': [o.pad] * 4, 'strides': [o.stride] * 2})
             else:
                 y = w.emit('Gemm', ins, {'alpha': 1.0, 'beta': 1.0, 'transB': 1})
         elif o.kind == 'add':

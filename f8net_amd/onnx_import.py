@@ -36,7 +36,7 @@ class OnnxImportError(ValueError):
 
 @dataclass
 class IntOp:
-    kind: str                      # input | conv | linear | add | maxpool | avgpool | concat | upsample
+    kind: str                      # input | conv | deconv | linear | add | maxpool | avgpool | concat | upsample
     src: int = -1                  # tensor id (index into IntGraph.ops)
     src2: int = -1                 # add: the operand that is NOT shifted
     weight: np.ndarray = None
@@ -56,6 +56,7 @@ class IntOp:
     shifts: list = None            # concat: k_i of `srcs[i] << k_i`, the alignment to the largest fraclen (the smallest is 0)
     mode: str = None               # upsample: 'nearest' | 'bilinear' (half-pixel centres; the result is the interpolated value times 4 scale^2)
     scale: tuple = None            # upsample: (scale_h, scale_w)
+    output_padding: int = 0        # deconv (transposed conv; weight [cin, cout, k, k]): ONNX `output_padding`, both equal
 
 
 @dataclass
@@ -66,7 +67,7 @@ class IntGraph:
     input_signed: bool = False
 
     def layer_keys(self):
-        return [o.key for o in self.ops if o.kind in ('conv', 'linear')]
+        return [o.key for o in self.ops if o.kind in ('conv', 'deconv', 'linear')]
 
     # -- fraction lengths -------------------------------------------------------------------------------------------
     def solve_fraclens(self, input_fraclen=None):
@@ -92,7 +93,7 @@ class IntGraph:
                 if input_fraclen is None:
                     input_fraclen = 7 if self.input_signed else 8
                 eq(t, ZERO, input_fraclen)
-            elif o.kind in ('conv', 'linear'):
+            elif o.kind in ('conv', 'deconv', 'linear'):
                 lim = 7 if o.signed else 8
                 if o.shift is None:                  # head conv: i = V[src]
                     ge(o.src, ZERO, 0)
@@ -135,7 +136,7 @@ class IntGraph:
             raise OnnxImportError('no fraction-length assignment satisfies the shifts in this graph')
         layer = {}
         for t, o in enumerate(self.ops):
-            if o.kind in ('conv', 'linear'):
+            if o.kind in ('conv', 'deconv', 'linear'):
                 i = V[o.src] - (o.shift or 0)
                 layer[t] = (i, V[t] - i)
         return V[:n], layer
@@ -145,7 +146,7 @@ class IntGraph:
         _, layer = self.solve_fraclens(input_fraclen)
         sd = {}
         for t, o in enumerate(self.ops):
-            if o.kind in ('conv', 'linear'):
+            if o.kind in ('conv', 'deconv', 'linear'):
                 i, w = layer[t]
                 sd[o.key + '.weight'] = o.weight
                 sd[o.key + '.bias'] = o.bias
@@ -173,6 +174,11 @@ class IntGraph:
                 ids[t] = net.conv(ids[o.src], o.weight, o.bias, stride=o.stride, pad=o.pad, groups=o.groups,
                                   weight_fl=w, input_fl=i, input_signed=o.signed, quant_input=o.shift is not None,
                                   relu=o.relu, label=o.key, dilation=o.dilation)
+            elif o.kind == 'deconv':
+                i, w = layer[t]
+                ids[t] = net.conv_transpose(ids[o.src], o.weight, o.bias, stride=o.stride, pad=o.pad, output_padding=o.output_padding,
+                                            weight_fl=w, input_fl=i, input_signed=o.signed, quant_input=o.shift is not None,
+                                            relu=o.relu, label=o.key)
             elif o.kind == 'linear':
                 i, w = layer[t]
                 ids[t] = net.linear(ids[o.src], o.weight, o.bias, weight_fl=w, input_fl=i, input_signed=o.signed,
@@ -423,7 +429,7 @@ def import_graph(model, input_signed=False) -> IntGraph:
                 val[out] = ('clip', e, lo, hi)
         elif op == 'Relu':
             e = val[nd.inputs[0]]
-            if e[0] != 'T' or ig.ops[e[1]].kind not in ('conv', 'add') or uses.get(nd.inputs[0], 0) != 1:
+            if e[0] != 'T' or ig.ops[e[1]].kind not in ('conv', 'deconv', 'add') or uses.get(nd.inputs[0], 0) != 1:
                 raise OnnxImportError('Relu on something other than a single-use conv / join result')
             ig.ops[e[1]].relu = True                               # nn.ReLU(inplace=True) on the producer's tensor
             val[out] = e
@@ -440,6 +446,38 @@ def import_graph(model, input_signed=False) -> IntGraph:
                                 bias=None if b is None else np.array(b, np.int32), stride=st[0],
                                 pad=pads[0], groups=a.get('group', 1), kernel=k[0], shift=n, signed=signed,
                                 key=_layer_key(wname), dilation=int(dil[0])))
+            if n is None:
+                ig.ops[-1].signed = ig.input_signed
+            val[out] = ('T', len(ig.ops) - 1)
+        elif op == 'ConvTranspose':
+            # nn.ConvTranspose2d on int32: W [cin, cout, k, k]; one stride, one pad and one output_padding for both axes.  What f8_net_conv_transpose
+            # does not build is named, one error each
+            src, n, signed = requant_src(nd.inputs[0], 'ConvTranspose')
+            wname, w = init(nd.inputs[1], 'ConvTranspose weight')
+            b = init(nd.inputs[2], 'ConvTranspose bias')[1] if len(nd.inputs) > 2 else None
+            w = np.array(w, np.int32)
+            if w.ndim != 4:
+                raise OnnxImportError(f'ConvTranspose {wname}: weight of rank {w.ndim}, expected [cin, cout, k, k]')
+            k = list(a.get('kernel_shape', w.shape[2:]))
+            if len(k) != 2 or k[0] != k[1] or w.shape[2] != w.shape[3] or k[0] != w.shape[2]:
+                raise OnnxImportError(f'ConvTranspose {wname}: non-square kernel {k} (weight {tuple(w.shape)})')
+            ap = a.get('auto_pad', b'NOTSET')
+            if (ap.decode() if isinstance(ap, bytes) else ap) != 'NOTSET':
+                raise OnnxImportError(f'ConvTranspose {wname}: auto_pad {ap!r}: only explicit pads')
+            if 'output_shape' in a:
+                raise OnnxImportError(f'ConvTranspose {wname}: output_shape {list(a["output_shape"])}: only pads + output_padding')
+            if a.get('group', 1) != 1:
+                raise OnnxImportError(f'ConvTranspose {wname}: group {a.get("group")}: only group = 1')
+            dil = list(a.get('dilations', [1, 1]))
+            if any(d != 1 for d in dil):
+                raise OnnxImportError(f'ConvTranspose {wname}: dilations {dil}: only 1')
+            pads, st, opad = list(a.get('pads', [0, 0, 0, 0])), list(a.get('strides', [1, 1])), list(a.get('output_padding', [0, 0]))
+            if len(set(pads)) != 1:
+                raise OnnxImportError(f'ConvTranspose {wname}: asymmetric pads {pads}')
+            if st[0] != st[1] or opad[0] != opad[1]:
+                raise OnnxImportError(f'ConvTranspose {wname}: unequal strides {st} / output_padding {opad}')
+            ig.ops.append(IntOp('deconv', src=src, weight=w, bias=None if b is None else np.array(b, np.int32), stride=int(st[0]),
+                                pad=int(pads[0]), kernel=int(k[0]), shift=n, signed=signed, key=_layer_key(wname), output_padding=int(opad[0])))
             if n is None:
                 ig.ops[-1].signed = ig.input_signed
             val[out] = ('T', len(ig.ops) - 1)

@@ -101,6 +101,30 @@ class F8Conv2d(nn.Conv2d):
                                       self.input_symmetric, self.dilation[0])
 
 
+class F8ConvTranspose2d(nn.ConvTranspose2d):
+    """An integer `nn.ConvTranspose2d` in the manner of `int_conv` (the reference names a ReLUClipFXQConvTransposeBN, fix_quant_ops.py:9, and defines none)
+    with a HIP forward (`torch.ops.f8net.conv_transpose2d`): int32 `weight` [cin, cout, k, k], `bias`, buffers `weight_fraclen` / `input_fraclen`,
+    attribute `input_symmetric`, as F8Conv2d.  forward(x): x int32 NCHW holding input_fraclen-format 8-bit integers -> int32 NCHW."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, output_padding=0, input_symmetric=False):
+        super().__init__(in_channels, out_channels, kernel_size, stride=stride, padding=padding, output_padding=output_padding, bias=True)
+        self.weight.requires_grad_(False)
+        self.bias.requires_grad_(False)
+        self.weight.data = torch.zeros(self.weight.shape, dtype=torch.int32)
+        self.bias.data = torch.zeros(self.bias.shape, dtype=torch.int32)
+        self.register_buffer('weight_fraclen', torch.zeros((), dtype=torch.int32))
+        self.register_buffer('input_fraclen', torch.zeros(1, dtype=torch.int32))
+        self.input_symmetric = bool(input_symmetric)
+        self.int_op_only = True
+        self._fl = _Scalars()
+
+    def forward(self, x):
+        _require_dev_i32(x, 'F8ConvTranspose2d')
+        w_fl, in_fl = self._fl.get(self)
+        return torch.ops.f8net.conv_transpose2d(x, self.weight, self.bias, self.stride[0], self.padding[0], self.output_padding[0], w_fl, in_fl,
+                                                self.input_symmetric)
+
+
 class F8Linear(nn.Linear):
     """The integer `nn.Linear` of `int_fc` (fix_quant_ops.py:1165-1195) with a HIP forward (`torch.ops.f8net.linear`)."""
 

@@ -38,6 +38,7 @@ _DEF.define('requant(Tensor x, int fl, int input_fl, bool signed) -> Tensor')
 _DEF.define('relu_(Tensor(a!) x) -> Tensor(a!)')
 _DEF.define('add_align_(Tensor(a!) res, Tensor x, int res_fl, int x_fl) -> Tensor(a!)')
 _DEF.define('conv2d(Tensor x, Tensor weight, Tensor? bias, int stride, int pad, int groups, int weight_fl, int input_fl, bool input_signed, int dilation=1) -> Tensor')
+_DEF.define('conv_transpose2d(Tensor x, Tensor weight, Tensor? bias, int stride, int pad, int output_padding, int weight_fl, int input_fl, bool input_signed) -> Tensor')
 _DEF.define('linear(Tensor x, Tensor weight, Tensor? bias, int weight_fl, int input_fl, bool input_signed) -> Tensor')
 _DEF.define('avgpool_sum(Tensor x) -> Tensor')
 _DEF.define('maxpool(Tensor x, int k, int stride, int pad) -> Tensor')
@@ -186,6 +187,31 @@ def _conv2d(x, weight, bias, stride, pad, groups, weight_fl, input_fl, input_sig
     return net.run(x).view(N, weight.shape[0], P, Q)
 
 
+def _deconv_out(n, k, stride, pad, output_padding):
+    return (n - 1) * stride - 2 * pad + k + output_padding
+
+
+def _conv_transpose2d(x, weight, bias, stride, pad, output_padding, weight_fl, input_fl, input_signed):
+    """nn.ConvTranspose2d on int32 (weight [cin, cout, k, k]): one f8_net_conv_transpose launch behind the input launch."""
+    _i32(x, 'conv_transpose2d')
+    x = x.contiguous()
+    N, C, H, W = x.shape
+    key = ('deconv', x.device.index, C, H, W, id(weight), tuple(weight.shape), None if bias is None else id(bias), stride, pad, output_padding, weight_fl,
+           input_fl, bool(input_signed))
+
+    def build(n):
+        net = F8Net()
+        t = net.input(C, H, W, input_fl)
+        t = net.conv_transpose(t, _np(weight), _np(bias), stride=stride, pad=pad, output_padding=output_padding, weight_fl=weight_fl,
+                               input_fl=input_fl, input_signed=input_signed, quant_input=False, relu=False)
+        net.output(t, as_float=False)
+        return net.finalize(n)
+
+    net = _plans.get(key, (weight, bias), N, build)
+    k = weight.shape[2]
+    return net.run(x).view(N, weight.shape[1], _deconv_out(H, k, stride, pad, output_padding), _deconv_out(W, k, stride, pad, output_padding))
+
+
 def _linear(x, weight, bias, weight_fl, input_fl, input_signed):
     _i32(x, 'linear')
     N, C = x.shape[0], weight.shape[1]
@@ -264,7 +290,7 @@ def _net_forward_f32(images, handle, normalize):
 
 # ------------------------------------------------------------------------------------------ registration
 _CUDA = Library('f8net', 'IMPL', 'CUDA')
-for _n, _f in (('requant', _requant), ('relu_', _relu_), ('add_align_', _add_align_), ('conv2d', _conv2d), ('linear', _linear),
+for _n, _f in (('requant', _requant), ('relu_', _relu_), ('add_align_', _add_align_), ('conv2d', _conv2d), ('conv_transpose2d', _conv_transpose2d), ('linear', _linear),
                ('avgpool_sum', _avgpool_sum), ('maxpool', _maxpool), ('net_forward', _net_forward), ('net_forward_taps', _net_forward_taps),
                ('net_forward_f32', _net_forward_f32)):
     _CUDA.impl(_n, _f)
@@ -275,6 +301,8 @@ _META.impl('relu_', lambda x: x)
 _META.impl('add_align_', lambda res, x, res_fl, x_fl: res)
 _META.impl('conv2d', lambda x, w, b, stride, pad, groups, wfl, ifl, sgn, dilation=1: x.new_empty(
     (x.shape[0], w.shape[0], _conv_out(x.shape[2], w.shape[2], stride, pad, dilation), _conv_out(x.shape[3], w.shape[3], stride, pad, dilation))))
+_META.impl('conv_transpose2d', lambda x, w, b, stride, pad, opad, wfl, ifl, sgn: x.new_empty(
+    (x.shape[0], w.shape[1], _deconv_out(x.shape[2], w.shape[2], stride, pad, opad), _deconv_out(x.shape[3], w.shape[3], stride, pad, opad))))
 _META.impl('linear', lambda x, w, b, wfl, ifl, sgn: x.new_empty((x.shape[0], w.shape[0])))
 _META.impl('avgpool_sum', lambda x: x.new_empty((x.shape[0], x.shape[1])))
 _META.impl('maxpool', lambda x, k, stride, pad: x.new_empty(

@@ -141,6 +141,32 @@ int f8_net_conv(f8_net* net, int src, const f8_conv_desc* desc,
 int f8_net_conv_dilated(f8_net* net, int src, const f8_conv_desc* desc, int dilation,
                         const int32_t* weight_host, const int32_t* bias_host);
 
+/* Transposed convolution (the learned upsampler: nn.ConvTranspose2d(k=2, s=2) of a U-Net decoder, 4x4 / 2 / pad 1 of FCN, CenterNet and pose heads,
+ * 3x3 / 2 / pad 1 / output_padding 1 of encoder-decoders).  The reference names a ReLUClipFXQConvTransposeBN (fix_quant_ops.py:9) but defines no such
+ * class, so the integer semantics are fixed here: those of int_conv applied to nn.ConvTranspose2d.
+ * `desc` is the f8_conv_desc of f8_net_conv and every field means what it means there (quant_input, input_fl, input_signed, weight_fl, relu, kernel,
+ * stride, pad; groups must be 1).  weight: host int32 [cin, cout, k, k] — the layout of nn.ConvTranspose2d.weight and of ONNX ConvTranspose's W —
+ * values must fit int8; bias: host int32 [cout] at fraclen input_fl + weight_fl, or NULL.
+ * Result: [cout, P, Q] with P = (H - 1) stride - 2 pad + kernel + output_padding (Q alike from W), fraclen weight_fl + input_fl, and in wrapping
+ * int32 arithmetic, as for a conv,
+ *   out[n, co, oh, ow] = b[co] + sum x_q[n, ci, ih, iw] * w[ci, co, kh, kw]
+ *                        over ci, kh, kw with oh + pad - kh = stride * ih, 0 <= ih < H  and  ow + pad - kw = stride * iw, 0 <= iw < W
+ * where x_q is the source behind the consumer requantisation (quant_input) or the source itself; a ReLU follows when desc->relu is set.  The same
+ * function three ways: the scatter form (every input pixel adds x * w[.., kh, kw] at (stride ih - pad + kh, ..)), the per-phase gather above, and the
+ * plain conv with pad' = kernel - 1 - pad and flipped, in / out-swapped weights over the zero-stuffed input (stride - 1 zeros between pixels,
+ * output_padding zero rows / columns at the bottom / right) — all equal to torch.nn.functional.conv_transpose2d.
+ * Accepted: 1 <= kernel <= 8, 1 <= stride <= 4, 0 <= pad <= kernel - 1, 0 <= output_padding < stride, groups == 1.
+ * F8_ERR_INVALID: output_padding < 0 or >= stride, an empty output (P or Q < 1), a weight outside int8, cin != the source's channels, whatever the
+ * consumer format refuses (f8_net_conv); F8_ERR_UNSUPPORTED: kernel > 8, stride > 4, pad > kernel - 1, groups != 1, a result past the 2 GiB-per-tensor
+ * bound; F8_ERR_STATE after finalize.
+ * stride == 1 is not a new op: it is recorded as the equivalent plain conv node (flipped, swapped weights, pad' = kernel - 1 - pad) and plans, fuses
+ * and names itself as any f8_net_conv does.  stride >= 2 is one launch of f8::deconv_kernel<1 / 2> (f8_deconv.hip), plan token `deconv{k}x{k}s{s}:`; it joins
+ * no fused block or chain launch and carries no residual join (an f8_net_add whose later operand it produces stays an `add:` launch).  It reads its
+ * source's int8 form as a conv does, so a tensor it reads exists in device memory: no fused launch keeps it on chip (it cuts a launch as an output
+ * tap does). */
+int f8_net_conv_transpose(f8_net* net, int src, const f8_conv_desc* desc, int output_padding,
+                          const int32_t* weight_host, const int32_t* bias_host);
+
 /* Residual join of IntBlock.forward (fix_resnet.py:40-54 / :63-76) [+ post_relu :77]. */
 int f8_net_add(f8_net* net, int a, int b, int relu);
 
