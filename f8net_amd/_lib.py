@@ -54,10 +54,12 @@ SYMBOLS = [
     ('f8_net_upsample', _i, [_vp, _i, _i, _i, _i]),
     ('f8_net_maxpool', _i, [_vp, _i, _i, _i, _i]),
     ('f8_net_avgpool_sum', _i, [_vp, _i, _i]),
+    ('f8_net_avgpool_window', _i, [_vp, _i, _i, _i, _i, _i]),
     ('f8_net_linear', _i, [_vp, _i, ctypes.POINTER(LinearDesc), _vp, _vp]),
     ('f8_net_output', _i, [_vp, _i, _i]),
     ('f8_net_num_outputs', _i, [_vp]),
     ('f8_net_output_info', _i, [_vp, _i] + [ctypes.POINTER(_i)] * 5),
+    ('f8_net_tensor_info', _i, [_vp, _i] + [ctypes.POINTER(_i)] * 4),
     ('f8_net_set_output_buffers', _i, [_vp, ctypes.POINTER(_vp), _i]),
     ('f8_net_finalize', _i, [_vp, _i]),
     ('f8_net_describe', _sz, [_vp, ctypes.c_char_p, _sz]),

@@ -74,6 +74,8 @@ struct Options {
                                  // dense expansion (the plain conv kernels over block-diagonal weights) elsewhere; 2 = accepted, always the dense expansion
     int concat_i8 = 1;           // f8_net_concat: 1 = the byte-gather mode where it is exact (every source written in the output's int8 formats, f8_concat.hip); 0 = always the int32 mode
     int upsample_i8 = 1;         // f8_net_upsample, nearest: 1 = the byte-copy mode where the result is read in at most two int8 formats and by nothing else (f8_upsample.hip); 0 = always the int32 mode
+    int sumpool_wide = 1;        // f8_net_avgpool_window: 1 = sumpool_wide_kernel where sumpool_wide_rule says so (windows of 3 and more that do not overlap), else the block walker (f8_sumpool.hip);
+                                 // 0 = every pool on the walker; 2 = every pool with kernel >= 2 on the wide kernel (tests).  Same values on every leg
     int tap_tiled = 1;           // network outputs 1 .. leave on tap_kernel (f8_tap.hip: walks the I32T blocks, every loaded byte used); 0: on output_kernel like output 0
     int check_input_range = 1;   // int32 inputs that are NARROWED to the head's 8-bit format (no requant) are range-checked on the device; f8_net_check reports
 };
@@ -217,6 +219,24 @@ struct UpsampleArgs {
     int32_t* out32;
     QuantOut q[2];
 };
+
+// Windowed average pooling (f8_sumpool.hip; f8_net_avgpool_window): [C, H, W] -> [C, P, Q], each output the wrapping int32 sum of its k x k window's
+// in-image taps.  x is the source's int32 form (I32T); out32 and q[] as AddArgs.
+struct SumPoolArgs {
+    const int32_t* x;
+    int32_t N, C, Cs, H, W, P, Q, k, stride, pad;        // images, real / padded channels, source map, output map, window
+    int32_t lg;                                          // sumpool_wide_kernel: log2 of the lanes that share one (output pixel, 4 channels) item (sumpool_wide_lg)
+    uint32_t mPQ, mQ, mK, mCg;                           // magic divisors (make_magic): P * Q, Q, k, Cs / 4
+    int32_t s1PQ, s2PQ, s1Q, s2Q, s1K, s2K, s1Cg, s2Cg;
+    int32_t* out32;
+    QuantOut q[2];
+};
+// The walker / wide rule of option sumpool_wide = 1, MEASURED (profiles/sumpool_r12.md, tools/ab_avgpool.py): windows that do not overlap (stride >= kernel)
+// of this size and more run sumpool_wide_kernel — at 3x3 / 3 it takes 0.82 of the walker's time, at 4x4 / 4 0.38, at 2x2 / 2 1.3 - 2.1.  Overlapping
+// windows (stride < kernel) stay on the walker, whose neighbouring lanes share their taps through the cache: measured up to 7x7 / 1 (the wide kernel
+// 1.3 - 2.0 x its time); NOT measured above 7.
+constexpr int kSumpoolWideKernel = 3;
+inline bool sumpool_wide_rule(int kernel, int stride) { return kernel >= kSumpoolWideKernel && stride >= kernel; }
 
 // Transposed convolution (f8_deconv.hip; f8_net_conv_transpose), stride 2 .. 4: [H, W] -> [P, Q] = [(H - 1) s - 2 pad + k + output_padding, ...].  The output
 // pixels of one PHASE (rh, rw) = ((oh + pad) % s, (ow + pad) % s) see the same kernel taps kh = rh + s th, th < Th, at the input rows ih = a - th
@@ -652,6 +672,10 @@ hipError_t launch_upsample(const UpsampleArgs& a, int inst, hipStream_t s);
 int deconv_inst(const DeconvArgs& a);                              // f8_deconv.hip.  The cout tiles per wave: 2 (deconv_kernel<2>, coutP >= 64) or 1 (deconv_kernel<1>)
 const char* deconv_kernel_name(int inst);
 hipError_t launch_deconv(const DeconvArgs& a, int inst, hipStream_t s);
+int sumpool_inst(int k, bool wide);                                // f8_sumpool.hip.  0: sumpool_i32_kernel<0> (kernel size at run time), 2 / 3: sumpool_i32_kernel<2> / <3>, 4: sumpool_wide_kernel
+const char* sumpool_kernel_name(int inst);
+int sumpool_wide_lg(int k);
+hipError_t launch_sumpool(const SumPoolArgs& a, int inst, hipStream_t s);
 hipError_t launch_input(const InArgs& a, int inst, hipStream_t s);
 const char* output_kernel_name();
 hipError_t launch_output(const OutArgs& a, hipStream_t s);

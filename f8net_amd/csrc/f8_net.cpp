@@ -90,7 +90,9 @@ enum Role { R_NONE, R_B0, R_B2, R_B4, R_SC };
 enum ChainKind { C_NONE, C_STAGE, C_BASIC, C_BASIC_CLUSTER, C_IR };
 // N_DECONV (f8_net_conv_transpose at stride >= 2) is a kind of its own, not a flag on N_CONV: every matcher asks `kind == N_CONV` and so never sees it — a
 // launch of its own (f8_deconv.hip), no block, no chain, no join in its epilogue.  It READS like a conv: its source's int8 form in its consumer format.
-enum NodeKind { N_INPUT, N_CONV, N_ADD, N_MAXPOOL, N_AVGPOOL, N_LINEAR, N_CONCAT, N_UPSAMPLE, N_DECONV };
+// N_SUMPOOL (f8_net_avgpool_window, except the global window, which is N_AVGPOOL) is a kind of its own: no matcher counts it among a block's readers, so
+// its source exists in device memory and cuts a chain or fused block where an output tap does.  It reads its source's int32 form.
+enum NodeKind { N_INPUT, N_CONV, N_ADD, N_MAXPOOL, N_AVGPOOL, N_LINEAR, N_CONCAT, N_UPSAMPLE, N_DECONV, N_SUMPOOL };
 struct Node {
     int kind; int a = -1, b = -1; int out = -1;
     f8_conv_desc cd{};                 // conv / linear (as 1x1 conv)
@@ -106,6 +108,8 @@ struct Node {
     std::vector<int> srcs;             // concat: the operands in channel order (tensor ids; a = srcs[0])
     bool concat_i8 = false;            // concat, pass 2: the byte-gather mode (every source in the output's int8 formats); false: sources in int32
     int up_mode = 0, up_sh = 1, up_sw = 1;      // upsample: F8_UP_NEAREST / F8_UP_BILINEAR, the scales
+    int sum_k = 0, sum_stride = 0, sum_pad = 0;   // sumpool: the window (its fraclen shift is in the output tensor's fl alone)
+    bool sum_wide = false;             // sumpool, pass 2: sumpool_wide_kernel (option sumpool_wide); false: the block walker
     bool up_i8 = false;                // upsample, pass 2: the byte-copy mode (nearest, the source in the output's int8 formats); false: the source in int32
     // planning
     int fused_into = -1;               // add: conv node that carries it
@@ -128,7 +132,7 @@ struct Node {
     size_t rc_off = 0, cc_off = 0; int ncc = 0;      // border-class tables (0 = single class)
     ConvTile tile{};
 };
-enum StepKind { S_INPUT, S_CONV, S_DW, S_ADD, S_MAXPOOL, S_AVGPOOL, S_REQUANT, S_OUTPUT, S_FUSED, S_STEMPOOL, S_IR, S_P12, S_CHAIN, S_BCHAIN, S_HEAD2, S_IRCHAIN, S_DWS, S_DWS7, S_IRK, S_GCONV, S_CONCAT, S_UPSAMPLE, S_DECONV };
+enum StepKind { S_INPUT, S_CONV, S_DW, S_ADD, S_MAXPOOL, S_AVGPOOL, S_REQUANT, S_OUTPUT, S_FUSED, S_STEMPOOL, S_IR, S_P12, S_CHAIN, S_BCHAIN, S_HEAD2, S_IRCHAIN, S_DWS, S_DWS7, S_IRK, S_GCONV, S_CONCAT, S_UPSAMPLE, S_DECONV, S_SUMPOOL };
 // The kernel of a step whose kind has several, chosen once by the step's emitter (pass 3); bind_step, run_step and f8_net_autotune switch on it.
 //   S_CONV:  conv_igemm (f8_kernels.hip), the LDS-patch 3x3 (f8_conv3x3.hip), conv1x1_wreg (f8_wreg.hip), conv1x1_wstat (f8_wstat.hip),
 //            conv3x3s2_wreg (f8_s2conv.hip), the 1x1 conv + average pool (f8_pool.hip), the classifier fc_dense (f8_fc.hip)
@@ -154,7 +158,7 @@ struct Step {
     double bytes_per_img = 0, bytes_const = 0, ops_per_img = 0;
     double valu_per_img = 0;           // ESSENTIAL vector lane-operations per image (f8_net_launch_valu): what the reference's semantics need once the MFMAs are done
     // the launcher's arguments as far as the plan decides them (bind_step); run_step copies them and adds what the run decides
-    std::variant<std::monostate, ConvArgs, StemPoolArgs, FusedArgs, ChainArgs, BChainArgs, BCChainArgs, IRArgs, IRKArgs, IRChainArgs, DwsArgs, Dws7Args, DwArgs, GConvArgs, AddArgs, PoolArgs, AvgArgs, OutArgs, ConcatArgs, UpsampleArgs, DeconvArgs> args;
+    std::variant<std::monostate, ConvArgs, StemPoolArgs, FusedArgs, ChainArgs, BChainArgs, BCChainArgs, IRArgs, IRKArgs, IRChainArgs, DwsArgs, Dws7Args, DwArgs, GConvArgs, AddArgs, PoolArgs, AvgArgs, OutArgs, ConcatArgs, UpsampleArgs, DeconvArgs, SumPoolArgs> args;
     int inst = 0;                      // the instance the launcher starts (the family's *_inst, f8_internal.h; bind_step)
     // S_CHAIN / S_BCHAIN: geometry, workgroups per image and resident per CU, the 7x7 cluster form (f8_cchain.hip)
     int C = 0, MID = 0, H = 0, W = 0, cin0 = 0, tiles = 0, wg_per_cu = 1; bool cluster = false;
@@ -298,6 +302,11 @@ static int64_t tensor_amax(f8_net* net, int t, int depth = 0) {
             const int sa = T.fl - net->tensors[nd.a].fl;     // 0 / 2k + 2
             constexpr int64_t cap = int64_t(1) << 40;
             if (a >= 0 && sa >= 0 && sa <= 31 && a <= (cap >> sa)) m = a << sa;
+        } else if (nd.kind == N_SUMPOOL) {                   // at most kernel^2 taps of the source's bound, under the same cap
+            const int64_t a = tensor_amax(net, nd.a, depth + 1);
+            const int64_t kk = (int64_t)nd.sum_k * nd.sum_k;
+            constexpr int64_t cap = int64_t(1) << 40;
+            if (a >= 0 && a <= cap / kk) m = a * kk;
         }
     }
     if (m > (int64_t(1) << 40)) m = -1;
@@ -402,6 +411,7 @@ static const OptKey kOptKeys[] = {
     {"grouped", "F8_GROUPED", &Options::grouped, 0, 2, true},
     {"concat_i8", "F8_CONCAT_I8", &Options::concat_i8, 0, 1, true},
     {"upsample_i8", "F8_UPSAMPLE_I8", &Options::upsample_i8, 0, 1, true},
+    {"sumpool_wide", "F8_SUMPOOL_WIDE", &Options::sumpool_wide, 0, 2, true},
 };
 static const OptKey* find_opt(const char* key) {
     if (!key) return nullptr;
@@ -811,6 +821,32 @@ int f8_net_avgpool_sum(f8_net* net, int src, int shift) {
     return t;
 }
 
+int f8_net_avgpool_window(f8_net* net, int src, int kernel, int stride, int pad, int shift) {
+    if (!net) return fail(F8_ERR_INVALID, "f8_net_avgpool_window: null net");
+    if (net->finalized) return fail(F8_ERR_STATE, "f8_net_avgpool_window: net already finalized");
+    if (const int rc = check_t(net, src, "f8_net_avgpool_window")) return rc;
+    if (kernel < 1 || stride < 1 || pad < 0 || pad * 2 > kernel)
+        return fail(F8_ERR_INVALID, "f8_net_avgpool_window: bad geometry (kernel %d, stride %d, pad %d: kernel, stride >= 1 and 0 <= 2 pad <= kernel)", kernel, stride, pad);
+    if (kernel == 1 && stride == 1) return fail(F8_ERR_INVALID, "f8_net_avgpool_window: kernel 1 at stride 1 is the identity");
+    if (kernel > 64 || stride > 64) return fail(F8_ERR_UNSUPPORTED, "f8_net_avgpool_window: kernels and strides above 64 are not built (got %d, %d)", kernel, stride);
+    const Tensor s = net->tensors[src];
+    if (s.H + 2 * pad < kernel || s.W + 2 * pad < kernel)
+        return fail(F8_ERR_INVALID, "f8_net_avgpool_window: window %d larger than the padded %d x %d map", kernel, s.H + 2 * pad, s.W + 2 * pad);
+    if (shift < 0) return fail(F8_ERR_INVALID, "f8_net_avgpool_window: shift %d < 0", shift);
+    if (s.fl + shift > 32)   // fix_quant_ops.py:129 `assert output_fraclen <= 32`
+        return fail(F8_ERR_INVALID, "f8_net_avgpool_window: output fraclen %d > 32", s.fl + shift);
+    // the global window is not a new op: the node f8_net_avgpool_sum records, so it plans, fuses and names itself as before
+    if (pad == 0 && kernel == s.H && kernel == s.W) return f8_net_avgpool_sum(net, src, shift);
+    const int P = (s.H + 2 * pad - kernel) / stride + 1, Q = (s.W + 2 * pad - kernel) / stride + 1;
+    Node nd; nd.kind = N_SUMPOOL; nd.a = src; nd.sum_k = kernel; nd.sum_stride = stride; nd.sum_pad = pad;
+    net->nodes.push_back(nd);
+    const int id = (int)net->nodes.size() - 1;
+    const int t = new_tensor(net, s.C, P, Q, s.fl + shift, id);
+    net->nodes[id].out = t;
+    net->tensors[src].consumers.push_back(id);
+    return t;
+}
+
 int f8_net_output(f8_net* net, int src, int as_float) {
     int rc = check_t(net, src, "f8_net_output");
     if (rc) return rc;
@@ -821,6 +857,17 @@ int f8_net_output(f8_net* net, int src, int as_float) {
 }
 
 int f8_net_num_outputs(const f8_net* net) { return net ? (int)net->outs.size() : F8_ERR_INVALID; }
+
+int f8_net_tensor_info(const f8_net* net, int t, int* C, int* H, int* W, int* fraclen) {
+    if (!net) return fail(F8_ERR_INVALID, "f8_net_tensor_info: null net");
+    if (t < 0 || t >= (int)net->tensors.size()) return fail(F8_ERR_INVALID, "f8_net_tensor_info: tensor %d of %d", t, (int)net->tensors.size());
+    const Tensor& x = net->tensors[t];
+    if (C) *C = x.C;
+    if (H) *H = x.H;
+    if (W) *W = x.W;
+    if (fraclen) *fraclen = x.fl;
+    return F8_OK;
+}
 
 int f8_net_output_info(const f8_net* net, int k, int* C, int* H, int* W, int* fraclen, int* as_float) {
     if (!net) return fail(F8_ERR_INVALID, "f8_net_output_info: null net");
@@ -2060,6 +2107,12 @@ static void plan_tensor_forms(f8_net* net) {
                 }
                 break;
             }
+            case N_SUMPOOL:
+                // reads the source's int32 form, whatever reads the result.  No matcher counts it among a block's readers, so a source
+                // inside a would-be fused launch is no private intermediate and the launch is cut there, as by an output tap.  The kernel: option sumpool_wide.
+                add_form(T[nd.a], FORM_I32, 0, 0);
+                nd.sum_wide = opt.sumpool_wide == 2 ? nd.sum_k >= 2 : opt.sumpool_wide == 1 && sumpool_wide_rule(nd.sum_k, nd.sum_stride);
+                break;
             case N_UPSAMPLE: {
                 // Mode.  upsample_nearest_i8: nearest, and the result exists in one or two int8 forms and nothing else (no int32 reader, no
                 // network output).  Replication commutes with every element-wise function, the requantisation among them, and the fraclen — so the shift — is the
@@ -2682,6 +2735,23 @@ static int emit_upsample(f8_net* net, int i, Step& st, std::vector<int>* extra) 
     return F8_OK;
 }
 
+static int emit_sumpool(f8_net* net, int i, Step& st, std::vector<int>* extra) {
+    auto& T = net->tensors;
+    const Node& nd = net->nodes[i];
+    const Tensor& s = T[nd.a]; Tensor& o = T[nd.out];
+    st.kind = S_SUMPOOL;
+    st.src_t = nd.a; st.src_f = find_form(s, FORM_I32, 0, 0);
+    if (o.forms.empty()) add_form(o, FORM_I32, 0, 0);
+    select_outputs(net, nd.out, &st.out, extra);
+    const double opx = (double)o.H * o.W;
+    st.bytes_per_img = (double)s.H * s.W * s.Cs * 4 + out_bytes(st, o, opx);
+    st.valu_per_img = opx * o.C * (nd.sum_k * nd.sum_k - 1 + 3 * out_forms8(st));      // kernel^2 - 1 adds per value; 3 per int8 value produced
+    char tok[48];
+    snprintf(tok, sizeof tok, "sumpool%dx%ds%d:", nd.sum_k, nd.sum_k, nd.sum_stride);
+    st.name = tok + tname(net, nd.out);
+    return F8_OK;
+}
+
 // the int8 forms of tensor t beyond the two its producer writes: stand-alone requants of its int32 form
 static void emit_requants(f8_net* net, int t, const std::vector<int>& extra) {
     for (int f : extra) {
@@ -2749,6 +2819,7 @@ static int emit_steps(f8_net* net, int max_batch) {
             case N_CONCAT: rc = emit_concat(net, i, st, &extra); break;
             case N_UPSAMPLE: rc = emit_upsample(net, i, st, &extra); break;
             case N_DECONV: rc = emit_deconv(net, i, st, &extra); break;
+            case N_SUMPOOL: rc = emit_sumpool(net, i, st, &extra); break;
         }
         if (rc) return rc;
         net->steps.push_back(st);
@@ -3350,6 +3421,18 @@ static int bind_step(f8_net* net, Step& st) {
             snprintf(kb, sizeof kb, "%s", upsample_kernel_name(st.inst = upsample_inst(nd.up_mode == F8_UP_BILINEAR, nd.up_i8)));
             out_formats(a.q); st.args = a; break;
         }
+        case S_SUMPOOL: {
+            const Tensor& sT = T[st.src_t]; const Tensor& oT = T[nd.out];
+            SumPoolArgs a{};
+            a.C = oT.C; a.Cs = oT.Cs; a.H = sT.H; a.W = sT.W; a.P = oT.H; a.Q = oT.W; a.k = nd.sum_k; a.stride = nd.sum_stride; a.pad = nd.sum_pad;
+            a.lg = sumpool_wide_lg(a.k);
+            make_magic((uint32_t)(a.P * a.Q), &a.mPQ, &a.s1PQ, &a.s2PQ);
+            make_magic((uint32_t)a.Q, &a.mQ, &a.s1Q, &a.s2Q);
+            make_magic((uint32_t)a.k, &a.mK, &a.s1K, &a.s2K);
+            make_magic((uint32_t)(a.Cs >> 2), &a.mCg, &a.s1Cg, &a.s2Cg);
+            snprintf(kb, sizeof kb, "%s", sumpool_kernel_name(st.inst = sumpool_inst(a.k, nd.sum_wide)));
+            out_formats(a.q); st.args = a; break;
+        }
         case S_MAXPOOL: {
             const Tensor& sT = T[st.src_t]; const Form& sF = sT.forms[st.src_f];
             const Tensor& oT = T[nd.out];
@@ -3781,6 +3864,13 @@ static int run_step(const f8_net* net, const RunIO& io, const Step& st, int n0, 
             a.N = N;
             fill_out(&a.out32, a.q);
             e = launch_upsample(a, st.inst, s);
+            break;
+        }
+        case S_SUMPOOL: {
+            SumPoolArgs a = std::get<SumPoolArgs>(st.args);
+            a.x = (const int32_t*)fp(T[st.src_t].forms[st.src_f]); a.N = N;
+            fill_out(&a.out32, a.q);
+            e = launch_sumpool(a, st.inst, s);
             break;
         }
         case S_MAXPOOL: {

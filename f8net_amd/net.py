@@ -6,6 +6,7 @@ fix_mobilenet_v2.py:207-241, fix_mobilenet_v1.py:120-147) through the C ABI; the
 into fused HIP launches.  torch is used for device memory and streams only.
 """
 import ctypes
+import math
 import os
 
 import numpy as np
@@ -137,6 +138,30 @@ class F8Net:
             self._L.f8_net_set_label(self._h, t, label.encode())
         return t
 
+    def avgpool(self, src, kernel, stride=None, pad=0, shift=None, label=None):
+        """Windowed average pooling (f8_net_avgpool_window): the wrapping int32 SUM of each kernel x kernel window's in-image taps at fraclen + shift;
+        `stride` defaults to `kernel`, `shift` to the reference's round(log2(kernel^2)).  The global window (kernel == H == W, pad 0) is avgpool_sum."""
+        kernel = int(kernel)
+        stride = kernel if stride is None else int(stride)
+        if shift is None:
+            shift = int(round(math.log2(kernel * kernel))) if kernel >= 1 else 0
+        t = check(self._L.f8_net_avgpool_window(self._h, src, kernel, stride, int(pad), int(shift)))
+        if label:
+            self._L.f8_net_set_label(self._h, t, label.encode())
+        return t
+
+    def adaptive_avgpool(self, src, bins, shift=None, label=None):
+        """nn.AdaptiveAvgPool2d(bins) on a map whose sides are multiples of `bins` (kernel = stride = side / bins, which must be the same for both
+        sides: windows are square); any other map raises ValueError (uneven bins are not built)."""
+        _, h, w, _ = self.tensor_info(src)
+        bins = int(bins)
+        if bins < 1 or h % bins or w % bins or h // bins != w // bins:
+            raise ValueError(f'adaptive_avgpool: a {h} x {w} map does not split into {bins} x {bins} equal square windows')
+        k = h // bins
+        if k == 1:
+            raise ValueError(f'adaptive_avgpool: {bins} bins of a {h} x {w} map is the identity')
+        return self.avgpool(src, k, k, 0, shift, label)
+
     def avgpool_sum(self, src, shift=AVGPOOL_SHIFT, label=None):
         t = check(self._L.f8_net_avgpool_sum(self._h, src, shift))
         if label:
@@ -163,6 +188,12 @@ class F8Net:
         v = [ctypes.c_int(0) for _ in range(5)]
         check(self._L.f8_net_output_info(self._h, int(k), *[ctypes.byref(x) for x in v]))
         return tuple(x.value for x in v[:4]) + (bool(v[4].value),)
+
+    def tensor_info(self, t):
+        """(C, H, W, fraclen) of any recorded tensor (f8_net_tensor_info)."""
+        v = [ctypes.c_int(0) for _ in range(4)]
+        check(self._L.f8_net_tensor_info(self._h, int(t), *[ctypes.byref(x) for x in v]))
+        return tuple(x.value for x in v)
 
     # ---- introspection ----------------------------------------------------------------------
     def describe(self) -> str:

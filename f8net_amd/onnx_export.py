@@ -12,6 +12,7 @@ opset-11 vocabulary is written directly from the integer graph — per op the no
     residual join                  Pow/Cast/Mul, Add, Clip(-+2^31 as f32), Cast(i32) [, Relu, Cast]   (fix_resnet.py:40-54,77)
     head max-pool                  Cast(f32), MaxPool, Cast(i32)                     (fix_resnet.py:358-359)
     FXQAvgPool2d                   Cast(i64), ReduceSum(-1) x2, Cast(i32)            (fix_quant_ops.py:130-133)
+    windowed average pool          Cast(f32), AveragePool(count_include_pad=1, ceil_mode=0), Mul(k^2), Cast(i32)
     channel concatenation          [Pow/Cast/Mul per operand at a smaller fraction length,] Concat(axis=1)
     upsampling, nearest            Resize(nearest, asymmetric, floor; scales [1, 1, sh, sw])
     upsampling, bilinear           Cast(f32), Resize(linear, half_pixel; scales [1, 1, s, s]), Mul(4 s^2), Cast(i32)
@@ -183,6 +184,10 @@ def export_graph(ig: IntGraph) -> bytes:
                        {'ceil_mode': 0, 'dilations': [1, 1], 'kernel_shape': [o.kernel] * 2, 'pads': [o.pad] * 4,
                         'strides': [o.stride] * 2})
             y = w.cast(v, onnx_io.INT32)
+        elif o.kind == 'avgpool2d':                                  # the window's sum: the average times k^2, integers again behind the Mul
+            v = w.emit('AveragePool', [w.cast(name[o.src], onnx_io.FLOAT)],
+                       {'ceil_mode': 0, 'count_include_pad': 1, 'kernel_shape': [o.kernel] * 2, 'pads': [o.pad] * 4, 'strides': [o.stride] * 2})
+            y = w.cast(w.emit('Mul', [v, w.const(float(o.kernel * o.kernel), np.float32)]), onnx_io.INT32)
         elif o.kind == 'avgpool':
             v = w.cast(name[o.src], onnx_io.INT64)
             v = w.emit('ReduceSum', [v], {'axes': [-1], 'keepdims': 0})

@@ -36,7 +36,7 @@ class OnnxImportError(ValueError):
 
 @dataclass
 class IntOp:
-    kind: str                      # input | conv | deconv | linear | add | maxpool | avgpool | concat | upsample
+    kind: str                      # input | conv | deconv | linear | add | maxpool | avgpool | avgpool2d | concat | upsample
     src: int = -1                  # tensor id (index into IntGraph.ops)
     src2: int = -1                 # add: the operand that is NOT shifted
     weight: np.ndarray = None
@@ -45,7 +45,8 @@ class IntOp:
     pad: int = 0
     groups: int = 1
     kernel: int = 0
-    shift: int = None              # conv/linear: requant n (None = input already in format); add: k of `src << k`
+    shift: int = None              # conv/linear: requant n (None = input already in format); add: k of `src << k`; avgpool2d: what the window's sum adds
+                                   # to the fraction length (kernel, stride, pad: the window)
     signed: bool = False           # conv/linear: clamp range of the requant (+-127 vs 0..255)
     relu: bool = False
     swap: bool = False             # add: the shifted operand is the Add's second input (`res += x << k`) — cosmetic
@@ -117,6 +118,9 @@ class IntGraph:
                 eq(t, o.src, 0 if o.mode == 'nearest' else upsample_fl_gain(o.scale))
                 if o.mode != 'nearest':
                     ge(ZERO, t, -32)                 # f8_net_upsample: the bound of the average pool
+            elif o.kind == 'avgpool2d':
+                eq(t, o.src, o.shift)
+                ge(ZERO, t, -32)                     # f8_net_avgpool_window: the same bound
             elif o.kind == 'avgpool':
                 eq(t, o.src, AVGPOOL_SHIFT)
                 ge(ZERO, t, -32)                     # fix_quant_ops.py:129
@@ -191,12 +195,21 @@ class IntGraph:
                 ids[t] = net.maxpool(ids[o.src], o.kernel, o.stride, o.pad)
             elif o.kind == 'upsample':
                 ids[t] = net.upsample(ids[o.src], tuple(o.scale), o.mode)
+            elif o.kind == 'avgpool2d':
+                ids[t] = net.avgpool(ids[o.src], o.kernel, o.stride, o.pad, shift=o.shift)
             elif o.kind == 'avgpool':
                 ids[t] = net.avgpool_sum(ids[o.src], AVGPOOL_SHIFT)
         net.output(ids[self.output], as_float=self.output_float)
         for k, v in (options or {}).items():
             net.set_option(k, v)
         return net.finalize(max_batch)
+
+
+def avgpool2d_shift(kernel):
+    """FXQAvgPool2d(kernel).shiftnum = round(log2(kernel^2)) (fix_quant_ops.py:121-122): what a windowed average pool adds to the fraction length.
+    Nothing in a file carries it (the consumer's shift absorbs it); any value computes the same integers."""
+    import math
+    return int(round(math.log2(kernel * kernel)))
 
 
 def upsample_fl_gain(scale):
@@ -395,6 +408,12 @@ def import_graph(model, input_signed=False) -> IntGraph:
                 val[out] = ('const', {'Add': cx + cy, 'Mul': cx * cy}.get(op))
                 if val[out][1] is None:
                     raise OnnxImportError(f'{op} of two constants')
+            elif is_const(y) and val.get(x, ('?',))[0] == 'avgpool_win':
+                _, src, k, st, pad = val[x]
+                if op != 'Mul' or const(y, op) != k * k:
+                    raise OnnxImportError(f'AveragePool {k} x {k} must be followed by a Mul by {k}^2 = {k * k} (the window\'s sum)')
+                ig.ops.append(IntOp('avgpool2d', src=src, kernel=k, stride=st, pad=pad, shift=avgpool2d_shift(k)))
+                val[out] = ('T', len(ig.ops) - 1)
             elif is_const(y) and val.get(x, ('?',))[0] == 'resize_lin':
                 _, src, scale, gain = val[x]
                 if op != 'Mul' or const(y, op) != 1 << gain:
@@ -498,6 +517,34 @@ def import_graph(model, input_signed=False) -> IntGraph:
                 raise OnnxImportError('MaxPool: unsupported form')
             ig.ops.append(IntOp('maxpool', src=e[1], kernel=k[0], stride=st[0], pad=pads[0]))
             val[out] = ('T', len(ig.ops) - 1)
+        elif op == 'AveragePool':
+            # AveragePool(count_include_pad=1) and the Mul by k^2 behind it, which makes the values integers again (the window's sum): the pair is one
+            # op (the Mul branch above closes it).  What f8_net_avgpool_window does not build is named, one error each
+            e = val[nd.inputs[0]]
+            if e[0] != 'T':
+                raise OnnxImportError('AveragePool: the input is not a layer result')
+            ap = a.get('auto_pad', b'NOTSET')
+            if (ap.decode() if isinstance(ap, bytes) else ap) != 'NOTSET':
+                raise OnnxImportError(f'AveragePool: auto_pad {ap!r}: only explicit pads')
+            if a.get('ceil_mode', 0):
+                raise OnnxImportError('AveragePool: ceil_mode=1 is not built (only floor)')
+            k = list(a['kernel_shape'])
+            st, pads = list(a.get('strides', [1] * len(k))), list(a.get('pads', [0] * 2 * len(k)))
+            if len(k) != 2 or k[0] != k[1]:
+                raise OnnxImportError(f'AveragePool: non-square kernel {k}')
+            if len(st) != 2 or st[0] != st[1]:
+                raise OnnxImportError(f'AveragePool: non-square strides {st}')
+            if len(set(pads)) != 1:
+                raise OnnxImportError(f'AveragePool: asymmetric pads {pads}')
+            if not a.get('count_include_pad', 0) and pads[0] > 0:
+                raise OnnxImportError(f'AveragePool: count_include_pad=0 with pad {pads[0]} > 0: the divisor would vary over the border')
+            nxt, name = users.get(out, []), out
+            while len(nxt) == 1 and nxt[0].op == 'Cast':
+                name = nxt[0].outputs[0]
+                nxt = users.get(name, [])
+            if len(nxt) != 1 or nxt[0].op != 'Mul':
+                raise OnnxImportError(f'AveragePool {k[0]} x {k[0]} without the Mul by {k[0] * k[0]} behind it: its values are not integers')
+            val[out] = ('avgpool_win', e[1], int(k[0]), int(st[0]), int(pads[0]))
         elif op == 'ReduceSum':                                    # x.sum(-1).sum(-1), fix_quant_ops.py:130
             e = val[nd.inputs[0]]
             if a.get('axes') != [-1] or a.get('keepdims', 1) != 0:

@@ -164,6 +164,26 @@ class FXQAvgPool2d(nn.Module):
         return res
 
 
+class F8AvgPool2d(nn.Module):
+    """Windowed average pooling in FXQAvgPool2d's manner (fix_quant_ops.py:117-138, int branch, per window): the integer SUM of each kernel_size x
+    kernel_size window (a tap in the padding adds 0; count_include_pad=True's constant divisor is left to the next layer's weights) with a HIP forward
+    (`torch.ops.f8net.avgpool2d_sum`), fraclen += shiftnum = round(log2(kernel_size^2)).  `stride` defaults to `kernel_size`."""
+
+    def __init__(self, kernel_size, stride=None, padding=0):
+        super().__init__()
+        self.kernel_size, self.stride, self.padding = int(kernel_size), int(kernel_size if stride is None else stride), int(padding)
+        self.shiftnum = int(torch.round(torch.log2(torch.tensor(float(self.kernel_size ** 2)))).item())
+        self.int_op_only = True
+
+    def forward(self, x):
+        _require_dev_i32(x, 'F8AvgPool2d')
+        output_fraclen = x.output_fraclen + self.shiftnum
+        assert output_fraclen <= 32
+        res = torch.ops.f8net.avgpool2d_sum(x, self.kernel_size, self.stride, self.padding)
+        setattr(res, 'output_fraclen', output_fraclen)
+        return res
+
+
 class F8MaxPool2d(nn.Module):
     """Head max-pool (fix_resnet.py:358-359 float detour / FXQMaxPool2d): exact integer max."""
 

@@ -41,6 +41,7 @@ _DEF.define('conv2d(Tensor x, Tensor weight, Tensor? bias, int stride, int pad, 
 _DEF.define('conv_transpose2d(Tensor x, Tensor weight, Tensor? bias, int stride, int pad, int output_padding, int weight_fl, int input_fl, bool input_signed) -> Tensor')
 _DEF.define('linear(Tensor x, Tensor weight, Tensor? bias, int weight_fl, int input_fl, bool input_signed) -> Tensor')
 _DEF.define('avgpool_sum(Tensor x) -> Tensor')
+_DEF.define('avgpool2d_sum(Tensor x, int k, int stride, int pad) -> Tensor')
 _DEF.define('maxpool(Tensor x, int k, int stride, int pad) -> Tensor')
 _DEF.define('net_forward(Tensor x, int handle) -> Tensor')
 _DEF.define('net_forward_taps(Tensor x, int handle) -> Tensor[]')
@@ -243,6 +244,23 @@ def _avgpool_sum(x):
     return _plans.get(('avg', x.device.index, C, H, W), (), N, build).run(x)
 
 
+def _avgpool2d_sum(x, k, stride, pad):
+    """The wrapping int32 sum of every k x k window (f8_net_avgpool_window, shift 0): [N, C, H, W] -> [N, C, P, Q]."""
+    _i32(x, 'avgpool2d_sum')
+    x = x.contiguous()
+    N, C, H, W = x.shape
+
+    def build(n):
+        net = F8Net()
+        t = net.input(C, H, W, 0)
+        t = net.avgpool(t, k, stride, pad, shift=0)
+        net.output(t, as_float=False)
+        return net.finalize(n)
+
+    P, Q = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    return _plans.get(('avg2d', x.device.index, C, H, W, k, stride, pad), (), N, build).run(x).view(N, C, P, Q)
+
+
 def _maxpool(x, k, stride, pad):
     _i32(x, 'maxpool')
     x = x.contiguous()
@@ -291,7 +309,7 @@ def _net_forward_f32(images, handle, normalize):
 # ------------------------------------------------------------------------------------------ registration
 _CUDA = Library('f8net', 'IMPL', 'CUDA')
 for _n, _f in (('requant', _requant), ('relu_', _relu_), ('add_align_', _add_align_), ('conv2d', _conv2d), ('conv_transpose2d', _conv_transpose2d), ('linear', _linear),
-               ('avgpool_sum', _avgpool_sum), ('maxpool', _maxpool), ('net_forward', _net_forward), ('net_forward_taps', _net_forward_taps),
+               ('avgpool_sum', _avgpool_sum), ('avgpool2d_sum', _avgpool2d_sum), ('maxpool', _maxpool), ('net_forward', _net_forward), ('net_forward_taps', _net_forward_taps),
                ('net_forward_f32', _net_forward_f32)):
     _CUDA.impl(_n, _f)
 
@@ -305,6 +323,8 @@ _META.impl('conv_transpose2d', lambda x, w, b, stride, pad, opad, wfl, ifl, sgn:
     (x.shape[0], w.shape[1], _deconv_out(x.shape[2], w.shape[2], stride, pad, opad), _deconv_out(x.shape[3], w.shape[3], stride, pad, opad))))
 _META.impl('linear', lambda x, w, b, wfl, ifl, sgn: x.new_empty((x.shape[0], w.shape[0])))
 _META.impl('avgpool_sum', lambda x: x.new_empty((x.shape[0], x.shape[1])))
+_META.impl('avgpool2d_sum', lambda x, k, stride, pad: x.new_empty(
+    (x.shape[0], x.shape[1], (x.shape[2] + 2 * pad - k) // stride + 1, (x.shape[3] + 2 * pad - k) // stride + 1)))
 _META.impl('maxpool', lambda x, k, stride, pad: x.new_empty(
     (x.shape[0], x.shape[1], (x.shape[2] + 2 * pad - k) // stride + 1, (x.shape[3] + 2 * pad - k) // stride + 1)))
 _META.impl('net_forward', lambda x, handle: x.new_empty((x.shape[0], _nets[handle].out_elems),

@@ -213,6 +213,26 @@ int f8_net_maxpool(f8_net* net, int src, int kernel, int stride, int pad);
  * fraclen += shift (shiftnum = round(log2(kernel_size^2)) = 6 for the nets' FXQAvgPool2d(7)). */
 int f8_net_avgpool_sum(f8_net* net, int src, int shift);
 
+/* Windowed average pooling (DenseNet transitions, Inception's 3x3 / 1 / pad 1 branch, ResNet-D's shortcut, PSPNet's pyramid bins; ONNX AveragePool):
+ * FXQAvgPool2d's int branch (fix_quant_ops.py:117-138) applied per window — sum in integers, add `shift` to the fraclen, no division, no rounding.
+ * out = [C, P, Q] from src = [C, H, W], P = (H + 2 pad - kernel) / stride + 1 (floor), Q the same from W;
+ *   out[c][p][q] = sum over 0 <= r, s < kernel of x[c][p stride - pad + r][q stride - pad + s], over the taps inside the map: a tap outside adds 0
+ * (count_include_pad = True: the divisor kernel^2 is a constant; the real scale 2^shift / kernel^2 is folded into the neighbouring conv's weights by
+ * the exporter).  All arithmetic modulo 2^32 (the int32 wrap of f8_net_avgpool_sum), no clamp, no rounding, no ReLU.  out.fraclen = src.fraclen +
+ * shift; the reference's shift is round(log2(kernel^2)): 2 for 2x2 (an exact average), 3 for 3x3.
+ * Accepted: 1 <= kernel <= 64, 1 <= stride <= 64, 0 <= 2 pad <= kernel (f8_net_maxpool's rule), shift >= 0.
+ * Returns the tensor id.  F8_ERR_INVALID: a bad tensor id, a geometry outside the rule above, kernel == 1 with stride == 1 (the identity), P < 1 or
+ * Q < 1, shift < 0, src.fraclen + shift > 32 (the reference's assert); F8_ERR_UNSUPPORTED: kernel or stride above 64; F8_ERR_STATE after finalize.
+ * The GLOBAL window — kernel == H == W, pad == 0 — is not a new op: it records the node f8_net_avgpool_sum records and plans, fuses
+ * (`conv1x1+avgpool:`, the `...+avgpool` chain launches) and names itself (`avgpool_sum:`) exactly as that call.  A map that is not square, or whose
+ * side is not the kernel, stays windowed.
+ * The plan runs every other window as one launch of f8_sumpool.hip, token `sumpool{k}x{k}s{stride}:` + the tensor's name, on the source's int32 form:
+ * f8::sumpool_i32_kernel<2 / 3 / 0> (a lane per output pixel) or, for windows of 3 and more that do not overlap, f8::sumpool_wide_kernel (option sumpool_wide).  The result is
+ * written in int32 and / or up to two int8 formats; a third format is a `requant:` step.
+ * A tensor read by a windowed pool exists in device memory: no matcher counts the pool among a block's readers, so no fused block or chain launch keeps
+ * its source on chip (it cuts a launch as an output tap does). */
+int f8_net_avgpool_window(f8_net* net, int src, int kernel, int stride, int pad, int shift);
+
 /* Integer nn.Linear built by ReLUClipFXQLinear.int_fc (fix_quant_ops.py:1165-1195);
  * src must be [C,1,1]. weight: host int32 [out, in]; bias host int32 [out] or NULL. */
 int f8_net_linear(f8_net* net, int src, const f8_linear_desc* desc,
@@ -233,6 +253,9 @@ int f8_net_output(f8_net* net, int src, int as_float);
 int f8_net_num_outputs(const f8_net* net);
 /* Shape, fraclen and element type of output k (0 <= k < f8_net_num_outputs); any out-pointer may be NULL. */
 int f8_net_output_info(const f8_net* net, int k, int* C, int* H, int* W, int* fraclen, int* as_float);
+/* Shape and fraclen of any recorded tensor, before or after finalize (what F8Net.adaptive_avgpool sizes its windows from); NULL pointers are skipped.
+ * F8_ERR_INVALID: a bad tensor id. */
+int f8_net_tensor_info(const f8_net* net, int t, int* C, int* H, int* W, int* fraclen);
 
 /* Plans the graph for batches up to max_batch: fuses requant / ReLU / residual into producer
  * epilogues, picks kernels and tiles, packs weights (host side), lays out the arena.
@@ -368,7 +391,10 @@ int f8_net_check(f8_net* net);
  *               their int32 forms, token concat_i32:.  Same values either way, bit for bit),
  *               upsample_i8 (default 1: a nearest upsample whose result is read in at most two int8 formats and by nothing else runs
  *               f8::upsample_i8_kernel on its source's int8 forms, plan token upsample_nearest_i8:; 0: it runs f8::upsample_i32_kernel<false> on the
- *               int32 form, token upsample_nearest_i32:.  Same values either way, bit for bit)
+ *               int32 form, token upsample_nearest_i32:.  Same values either way, bit for bit),
+ *               sumpool_wide (default 1: a windowed average pool whose windows do not overlap (stride >= kernel) and whose kernel is at or above the
+ *               measured crossover, 3, runs f8::sumpool_wide_kernel — a group of lanes per output value —, every other f8::sumpool_i32_kernel<K>;
+ *               0: every pool runs the walker; 2: every pool with kernel >= 2 runs the wide kernel, for tests.  Same values on every leg, bit for bit)
  *   scheduling: chunk56 / chunk28 / chunk14 (images per chunk of the fused blocks; -1 = derived from chunk_budget_mb, 0 = whole
  *               batch), chunk_budget_mb (memory-side cache a chunk's int32 stream may occupy), chunk_ds, chunk_opener,
  *               split_streams, graph, stagger, stagger_pipelined, stem_wpc, stem_grid_div (row-walking head on 1 / n of the CUs; 0 = by output form), check_device, check_input_range, pipeline_depth (2..4 runs in flight),
