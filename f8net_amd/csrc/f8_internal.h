@@ -22,6 +22,7 @@ struct Options {
     int wstat = 1;               // weight-stationary 1x1 kernel (f8_wstat.hip) where a launch gives every workgroup >= wstat_min_tiles pixel tiles
     int wstat_min_tiles = 2;
     int wstat_fast = 1;          // 0: always the general epilogue (requant in either direction, explicit ReLU floor)
+    int wstat_grid_div = 0;      // tests: the weight-stationary 1x1 sizes its pixel groups for 1 / n of the CUs (long tile walks on small maps); 0 = all of them
     int s2wreg = 1;              // stride-2 3x3 convs of the stage-2 / stage-3 openers on conv3x3s2_wreg_kernel (f8_s2conv.hip)
     int wreg = 1;                // late 1x1 convs on conv1x1_wreg_kernel (weights straight to registers, f8_wreg.hip)
     int fuse_bchain = 2;         // consecutive BasicBlock identity blocks of a stage in ONE launch (f8_bchain.hip); 2: with the stage-opening block in front of them
@@ -594,7 +595,7 @@ bool conv1x1_wstat_supported(int k0, int k1, int coutP, bool has_res);
 int conv1x1_wstat_waves(int k0, int k1);
 int conv1x1_wstat_inst(const ConvArgs& a, bool res, bool out32, int nq, bool fast);   // fast: Options::wstat_fast
 int conv1x1_wstat_kernel_name(char* buf, size_t cap, const ConvArgs& a, int inst);
-hipError_t launch_conv1x1_wstat(const ConvArgs& a, int inst, int num_cu, hipStream_t s);
+hipError_t launch_conv1x1_wstat(const ConvArgs& a, int inst, int num_cu, int grid_div, hipStream_t s);   // grid_div: Options::wstat_grid_div
 // MobileNet-V2 inverted residual (f8_ir.hip): instance for the padded channel pair + a tile (R rows or G whole images) that fits LDS
 bool fused_ir_config(int cinS, int coutS, int H, int W, int stride, int* R, int* G);
 int fused_ir_inst(const IRArgs& a, int coutS);

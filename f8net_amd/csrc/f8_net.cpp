@@ -378,6 +378,7 @@ static const OptKey kOptKeys[] = {
     {"wstat", "F8_WSTAT", &Options::wstat, 0, 1, true},
     {"wstat_min_tiles", "F8_WSTAT_MIN_TILES", &Options::wstat_min_tiles, 0, 1 << 20, true},
     {"wstat_fast", "F8_WSTAT_FAST", &Options::wstat_fast, 0, 1, true},
+    {"wstat_grid_div", "F8_WSTAT_GRID_DIV", &Options::wstat_grid_div, 0, 32, false},
     {"patch3x3", "F8_PATCH3X3", &Options::patch3x3, 0, 1, true},
     {"dual_wide", "F8_DUAL_WIDE", &Options::dual_wide, 0, 1 << 30, true},
     {"deep_nk", "F8_DEEP_NK", &Options::deep_nk, 1, 1 << 20, true},
@@ -3732,7 +3733,7 @@ static int run_step(const f8_net* net, const RunIO& io, const Step& st, int n0, 
                 case V_FC: e = launch_fc_dense(a, (char*)io.out + (size_t)n0 * C * 4, C, net->outs[0].as_float, chain_err, net->epoch, s); break;
                 case V_POOL: e = launch_conv1x1_pool(a, s); break;
                 case V_S2WREG: e = launch_conv3x3s2_wreg(a, s); break;
-                case V_WSTAT: e = launch_conv1x1_wstat(a, st.inst, net->num_cu, s); break;
+                case V_WSTAT: e = launch_conv1x1_wstat(a, st.inst, net->num_cu, net->opt.wstat_grid_div, s); break;
                 case V_WREG: e = launch_conv1x1_wreg(a, s); break;
                 case V_PATCH3X3: e = launch_conv3x3_patch(a, nd.cd.cin, s); break;
                 default: e = launch_conv(a, nd.tile, st.inst, s);      // V_IGEMM

@@ -452,12 +452,13 @@ static hipError_t launch_wstat_f(const ConvArgs& a, int inst, int num_cu, hipStr
     return inst & kWstatFast ? launch_wstat_o<K0, K1, NW, RES, true>(a, num_cu, s) : launch_wstat_o<K0, K1, NW, RES, false>(a, num_cu, s);
 }
 
-hipError_t launch_conv1x1_wstat(const ConvArgs& a, int inst, int num_cu, hipStream_t s) {
+hipError_t launch_conv1x1_wstat(const ConvArgs& a, int inst, int num_cu, int grid_div, hipStream_t s) {
     const bool res = a.res != nullptr;
     const int k1 = a.x2 ? a.ktot2 : 0;
     if (res != ((inst & kWstatRes) != 0) || (a.out32 != nullptr) != ((inst & kWstatOut32) != 0) || (a.q[0].ptr ? 1 : 0) + (a.q[1].ptr ? 1 : 0) != inst >> 3)
         return hipErrorInvalidValue;
     if (num_cu <= 0) num_cu = 256;
+    if (grid_div > 0) num_cu = num_cu / grid_div > 1 ? num_cu / grid_div : 1;     // Options::wstat_grid_div: pixel groups for 1 / grid_div of the CUs
     if (k1 == 0 && !res && a.CK == 512) return launch_wstat_f<512, 0, 8, false>(a, inst, num_cu, s);
     if (k1 == 0 && !res && a.CK == 1024) return launch_wstat_f<1024, 0, 8, false>(a, inst, num_cu, s);
     if (k1 == 0 && res && a.CK == 512) return launch_wstat_f<512, 0, 8, true>(a, inst, num_cu, s);

@@ -397,7 +397,7 @@ int f8_net_check(f8_net* net);
  *               0: every pool runs the walker; 2: every pool with kernel >= 2 runs the wide kernel, for tests.  Same values on every leg, bit for bit)
  *   scheduling: chunk56 / chunk28 / chunk14 (images per chunk of the fused blocks; -1 = derived from chunk_budget_mb, 0 = whole
  *               batch), chunk_budget_mb (memory-side cache a chunk's int32 stream may occupy), chunk_ds, chunk_opener,
- *               split_streams, graph, stagger, stagger_pipelined, stem_wpc, stem_grid_div (row-walking head on 1 / n of the CUs; 0 = by output form), check_device, check_input_range, pipeline_depth (2..4 runs in flight),
+ *               split_streams, graph, stagger, stagger_pipelined, stem_wpc, stem_grid_div (row-walking head on 1 / n of the CUs; 0 = by output form), wstat_grid_div (0 .. 32, default 0, environment F8_WSTAT_GRID_DIV: f8::conv1x1_wstat_kernel sizes its pixel groups for 1 / n of the CUs, at least one — tests walk long tile rings on small maps; 0 = all of them; the plan and the values do not move), check_device, check_input_range, pipeline_depth (2..4 runs in flight),
  *               chain_timeout_ms (bound of a stage-chain launch's halo waits)
  *   read-only (f8_net_get_option): err_mirror (1 = after upload a page-locked host mirror of the chain error words exists: f8_net_run returns
  *               F8_ERR_HIP without issuing anything once a chain launch of an EARLIER run gave up waiting, until f8_net_check collects the error;

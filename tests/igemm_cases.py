@@ -75,13 +75,15 @@ def uniform_ld(bm, bn, bk):                                  # UNIFORM_LD of con
 # x_fl + pre.w_fl - in_fl).  join: None | 'in' | 'other'; o_fl: fraclen of `other` (its weights' is o_fl - x_fl); join_relu.  clamp: channel 5 of
 # the conv and of the other operand have zero weights and biases whose aligned sum is exactly 2^31, channel 9 biases that bring the sum above 2^30.
 # dual: {mid, stride}: input -> 1x1 / stride (c0 -> mid, ReLU) -> the conv under test (1x1, mid -> cout) + shortcut 1x1 / stride (c0 -> cout).
+# dual.host = 'shortcut': the shortcut behind the conv under test (it then hosts the pair's launch).  o_set {channel: value}: channels of `other`
+# with zero weights and that bias.
 # w_seed: another draw of the weights where the first left a liveness condition of test_igemm_plan.py unmet (eight output channels are few).
 # pool: None | ('max', k, stride, pad) | ('avg',) behind the result; readers [(fraclen, signed)]; out_i32.  shift: the right shift the spreads aim
 # at — weights' sigma and biases are scaled so that the accumulators spread over about 2^shift * [0, 255].
 def _case(k, cin, cout, tok, kernel, H=8, W=8, N=3, max_batch=None, stride=1, pad=0, why='', **kw):
     d = dict(k=k, cin=cin, cout=cout, H=H, W=W, N=N, max_batch=max_batch or N, stride=stride, pad=pad, groups=1, c0=None, x_fl=8, x_signed=False,
              in_fl=8, in_signed=False, w_fl=None, relu=True, pre=None, join=None, o_fl=None, join_relu=False, clamp=True, dual=None, pool=None,
-             readers=[(4, False)], out_i32=False, shift=9, opts={}, token=tok, kernel=kernel, extra_tokens=[], why=why, w_seed=0, w_mul=1.0, bias_big=False, spread=None, x_hi=None, bias_set={})
+             readers=[(4, False)], out_i32=False, shift=9, opts={}, token=tok, kernel=kernel, extra_tokens=[], why=why, w_seed=0, w_mul=1.0, bias_big=False, spread=None, x_hi=None, bias_set={}, o_set={})
     d.update(kw)
     if d['x_hi'] is None:
         d['x_hi'] = 127 if d['x_signed'] else 255
@@ -178,19 +180,31 @@ def build_graph(case, x):
         if c['clamp']:
             wo[5] = 0
             bo[5], bo[9] = big5 >> res_shl, big9 >> res_shl
+        for ch, v in c['o_set'].items():                           # channels of the other operand that are exactly v (zero weights)
+            wo[ch] = 0
+            bo[ch] = v
     if joined and c['clamp']:
         assert c['join'] != 'in' or c['pre'], 'the clamp construction needs a conv behind the other operand'
         w[5] = 0
         b[5], b[9] = big5 >> acc_shl, 2 ** 29 >> acc_shl
-    if c['join'] == 'other' or c['dual']:
-        other = g.conv(t0, wo, bo, stride=c['dual']['stride'] if c['dual'] else 1, pad=0, groups=1, weight_fl=o_fl - c['x_fl'], input_fl=c['x_fl'],
-                       input_signed=c['x_signed'], relu=False, quant_input=False, label='other')
+    def shortcut():
+        return g.conv(t0, wo, bo, stride=c['dual']['stride'] if c['dual'] else 1, pad=0, groups=1, weight_fl=o_fl - c['x_fl'], input_fl=c['x_fl'],
+                      input_signed=c['x_signed'], relu=False, quant_input=False, label='other')
+    # dual['host'] = 'shortcut' (tests/ostat_cases.py): the shortcut is added behind the conv under test and carries the join, as in a ResNet
+    host_sc = bool(c['dual']) and c['dual'].get('host') == 'shortcut'
+    if (c['join'] == 'other' or c['dual']) and not host_sc:
+        other = shortcut()
     with grouped_oracle():                                        # (oracle.conv2d per group where 1 < groups < cin)
         y = g.conv(src, w, b, stride=c['stride'], pad=c['pad'], groups=G, weight_fl=c['w_fl'], input_fl=c['in_fl'], input_signed=c['in_signed'],
                    relu=c['relu'], quant_input=not reads_input, label='under_test' if not reads_input else None)
     g.net._L.f8_net_set_label(g.net._h, y, b'ut')
-    t = g.add(y, other, relu=c['join_relu']) if other is not None else y
+    if host_sc:
+        other = shortcut()
+        t = g.add(other, y, relu=c['join_relu'])
+    else:
+        t = g.add(y, other, relu=c['join_relu']) if other is not None else y
     g.other, g.shl = other, (acc_shl, res_shl)                     # (for the liveness checks: the join's operand and align shifts)
+    g.weights = dict(ut=w, other=wo if (c['join'] == 'other' or c['dual']) else None)      # (... and the K slices of both products)
     if c['pool']:
         if c['pool'][0] == 'max':
             pk, ps, pp = c['pool'][1:4]
