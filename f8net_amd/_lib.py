@@ -52,6 +52,8 @@ SYMBOLS = [
     ('f8_net_add', _i, [_vp, _i, _i, _i]),
     ('f8_net_concat', _i, [_vp, ctypes.POINTER(ctypes.c_int), _i]),
     ('f8_net_upsample', _i, [_vp, _i, _i, _i, _i]),
+    ('f8_net_slice', _i, [_vp, _i, _i, _i]),
+    ('f8_net_channel_shuffle', _i, [_vp, _i, _i]),
     ('f8_net_maxpool', _i, [_vp, _i, _i, _i, _i]),
     ('f8_net_avgpool_sum', _i, [_vp, _i, _i]),
     ('f8_net_avgpool_window', _i, [_vp, _i, _i, _i, _i, _i]),

@@ -77,6 +77,8 @@ struct Options {
     int upsample_i8 = 1;         // f8_net_upsample, nearest: 1 = the byte-copy mode where the result is read in at most two int8 formats and by nothing else (f8_upsample.hip); 0 = always the int32 mode
     int sumpool_wide = 1;        // f8_net_avgpool_window: 1 = sumpool_wide_kernel where sumpool_wide_rule says so (windows of 3 and more that do not overlap), else the block walker (f8_sumpool.hip);
                                  // 0 = every pool on the walker; 2 = every pool with kernel >= 2 on the wide kernel (tests).  Same values on every leg
+    int chanmap_i8 = 1;          // f8_net_slice / f8_net_channel_shuffle: 1 = the byte-gather mode where the result is read in at most two int8 formats and by nothing else (f8_chanmap.hip); 0 = always the int32 mode
+    int fuse_shuffle = 1;        // a concat read by one i8-mode channel shuffle alone, `groups` operands of one width: 1 = one launch that reads the concat's operands (concat+shuffle{g}_i8:); 0 = two launches
     int tap_tiled = 1;           // network outputs 1 .. leave on tap_kernel (f8_tap.hip: walks the I32T blocks, every loaded byte used); 0: on output_kernel like output 0
     int check_input_range = 1;   // int32 inputs that are NARROWED to the head's 8-bit format (no requant) are range-checked on the device; f8_net_check reports
 };
@@ -238,6 +240,22 @@ struct SumPoolArgs {
 // 1.3 - 2.0 x its time); NOT measured above 7.
 constexpr int kSumpoolWideKernel = 3;
 inline bool sumpool_wide_rule(int kernel, int stride) { return kernel >= kSumpoolWideKernel && stride >= kernel; }
+
+// Channel slice and channel shuffle (f8_chanmap.hip; f8_net_slice, f8_net_channel_shuffle): pure channel gathers of one map, out[c] = src[first + c]
+// (groups == 0) or out[c] = src[(c % groups) * Cg + c / groups], Cg = C / groups.  The source is a TABLE of K entries: a slice has one (offset
+// `first`); a shuffle has one per group — stand-alone every entry points at the source with offset i * Cg, fused with its concat (concat+shuffle)
+// entry i is concat operand i with offset 0: the launches differ in nothing else.  Mode i8: src[k][i] is entry i in the int8 format of output form k
+// (NHWC, Cs_src[i]-byte rows), the launch moves bytes and only q[k].ptr / bias_xor are read.  Mode i32 (chanmap_i32_kernel, never fused): src[0][0] is the
+// source's int32 form (I32T); out32 and q[] as AddArgs.
+struct ChanMapArgs {
+    const void* src[2][kMaxConcat];
+    int32_t Cs_src[kMaxConcat], off[kMaxConcat];         // row stride (padded channels) of entry i, its first channel
+    int32_t K, groups, Cg;                               // table entries; 0 = slice, else the shuffle's groups (== K) and channels per group
+    int32_t M, C, Cs;                                    // pixels N * H * W, real / padded output channels
+    uint32_t mG; int32_t s1G, s2G;                       // magic divisor (make_magic): groups
+    int32_t* out32;
+    QuantOut q[2];
+};
 
 // Transposed convolution (f8_deconv.hip; f8_net_conv_transpose), stride 2 .. 4: [H, W] -> [P, Q] = [(H - 1) s - 2 pad + k + output_padding, ...].  The output
 // pixels of one PHASE (rh, rw) = ((oh + pad) % s, (ow + pad) % s) see the same kernel taps kh = rh + s th, th < Th, at the input rows ih = a - th
@@ -673,6 +691,9 @@ hipError_t launch_upsample(const UpsampleArgs& a, int inst, hipStream_t s);
 int deconv_inst(const DeconvArgs& a);                              // f8_deconv.hip.  The cout tiles per wave: 2 (deconv_kernel<2>, coutP >= 64) or 1 (deconv_kernel<1>)
 const char* deconv_kernel_name(int inst);
 hipError_t launch_deconv(const DeconvArgs& a, int inst, hipStream_t s);
+int chanmap_inst(const ChanMapArgs& a, bool i8);                   // f8_chanmap.hip.  0: chanmap_i32_kernel, 1 / 2: slice_i8_kernel<true> / <false>, 3 / 4 / 5: shuffle_i8_kernel<16> / <4> / <2>, 6: shuffle_i8_general_kernel
+const char* chanmap_kernel_name(int inst);
+hipError_t launch_chanmap(const ChanMapArgs& a, int inst, hipStream_t s);
 int sumpool_inst(int k, bool wide);                                // f8_sumpool.hip.  0: sumpool_i32_kernel<0> (kernel size at run time), 2 / 3: sumpool_i32_kernel<2> / <3>, 4: sumpool_wide_kernel
 const char* sumpool_kernel_name(int inst);
 int sumpool_wide_lg(int k);

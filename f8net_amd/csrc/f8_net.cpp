@@ -92,7 +92,9 @@ enum ChainKind { C_NONE, C_STAGE, C_BASIC, C_BASIC_CLUSTER, C_IR };
 // launch of its own (f8_deconv.hip), no block, no chain, no join in its epilogue.  It READS like a conv: its source's int8 form in its consumer format.
 // N_SUMPOOL (f8_net_avgpool_window, except the global window, which is N_AVGPOOL) is a kind of its own: no matcher counts it among a block's readers, so
 // its source exists in device memory and cuts a chain or fused block where an output tap does.  It reads its source's int32 form.
-enum NodeKind { N_INPUT, N_CONV, N_ADD, N_MAXPOOL, N_AVGPOOL, N_LINEAR, N_CONCAT, N_UPSAMPLE, N_DECONV, N_SUMPOOL };
+// N_SLICE / N_SHUFFLE (f8_net_slice, f8_net_channel_shuffle; f8_chanmap.hip) are kinds of their own for the same reason: their source exists in device
+// memory and cuts a chain or fused block where an output tap does.  Channel gathers without arithmetic; the mode rule of the nearest upsample.
+enum NodeKind { N_INPUT, N_CONV, N_ADD, N_MAXPOOL, N_AVGPOOL, N_LINEAR, N_CONCAT, N_UPSAMPLE, N_DECONV, N_SUMPOOL, N_SLICE, N_SHUFFLE };
 struct Node {
     int kind; int a = -1, b = -1; int out = -1;
     f8_conv_desc cd{};                 // conv / linear (as 1x1 conv)
@@ -110,6 +112,10 @@ struct Node {
     int up_mode = 0, up_sh = 1, up_sw = 1;      // upsample: F8_UP_NEAREST / F8_UP_BILINEAR, the scales
     int sum_k = 0, sum_stride = 0, sum_pad = 0;   // sumpool: the window (its fraclen shift is in the output tensor's fl alone)
     bool sum_wide = false;             // sumpool, pass 2: sumpool_wide_kernel (option sumpool_wide); false: the block walker
+    int cm_first = 0, cm_groups = 0;   // slice: the first source channel; shuffle: the groups
+    bool cm_i8 = false;                // slice / shuffle, pass 2: the byte-gather mode (the source in the output's int8 formats); false: the source in int32
+    int cm_cat = -1;                   // shuffle, pass 2: the concat node in front of it whose operands this launch reads itself (option fuse_shuffle), else -1
+    int cat_into = -1;                 // concat, pass 2: the shuffle node whose launch reads this concat's operands: no launch and no form of its own
     bool up_i8 = false;                // upsample, pass 2: the byte-copy mode (nearest, the source in the output's int8 formats); false: the source in int32
     // planning
     int fused_into = -1;               // add: conv node that carries it
@@ -132,7 +138,7 @@ struct Node {
     size_t rc_off = 0, cc_off = 0; int ncc = 0;      // border-class tables (0 = single class)
     ConvTile tile{};
 };
-enum StepKind { S_INPUT, S_CONV, S_DW, S_ADD, S_MAXPOOL, S_AVGPOOL, S_REQUANT, S_OUTPUT, S_FUSED, S_STEMPOOL, S_IR, S_P12, S_CHAIN, S_BCHAIN, S_HEAD2, S_IRCHAIN, S_DWS, S_DWS7, S_IRK, S_GCONV, S_CONCAT, S_UPSAMPLE, S_DECONV, S_SUMPOOL };
+enum StepKind { S_INPUT, S_CONV, S_DW, S_ADD, S_MAXPOOL, S_AVGPOOL, S_REQUANT, S_OUTPUT, S_FUSED, S_STEMPOOL, S_IR, S_P12, S_CHAIN, S_BCHAIN, S_HEAD2, S_IRCHAIN, S_DWS, S_DWS7, S_IRK, S_GCONV, S_CONCAT, S_UPSAMPLE, S_DECONV, S_SUMPOOL, S_CHANMAP };
 // The kernel of a step whose kind has several, chosen once by the step's emitter (pass 3); bind_step, run_step and f8_net_autotune switch on it.
 //   S_CONV:  conv_igemm (f8_kernels.hip), the LDS-patch 3x3 (f8_conv3x3.hip), conv1x1_wreg (f8_wreg.hip), conv1x1_wstat (f8_wstat.hip),
 //            conv3x3s2_wreg (f8_s2conv.hip), the 1x1 conv + average pool (f8_pool.hip), the classifier fc_dense (f8_fc.hip)
@@ -145,7 +151,7 @@ struct Step {
     int src_t = -1, src_f = -1;        // main input tensor / form
     int res_t = -1, res_f = -1;        // residual (conv) or second operand (add)
     int src2_t = -1, src2_f = -1;      // dual GEMM: input of the second conv
-    // S_CONCAT reads K tensors (S_UPSAMPLE: one, in up to two forms) and keeps them HERE, with src_t = res_t = src2_t = -1: code that asks what a step reads (lifetimes: layout_arena; users of the
+    // S_CONCAT reads K tensors (S_UPSAMPLE: one, in up to two forms; S_CHANMAP: one, or the operands of the concat it is fused with) and keeps them HERE, with src_t = res_t = src2_t = -1: code that asks what a step reads (lifetimes: layout_arena; users of the
     // network input: let_stem_read_input) must look at cat_t as well as the three *_t above; step_chunk / for_each_launch index tensors[src_t] only for S_FUSED
     std::vector<int> cat_t, cat_f[2];  // S_UPSAMPLE: the one source, forms as for S_CONCAT: the source tensors and their forms — i8 mode: cat_f[k] = the sources in the format of output form out.f8[k]; i32 mode: cat_f[0] = their int32 forms
     OutSel out;
@@ -158,7 +164,7 @@ struct Step {
     double bytes_per_img = 0, bytes_const = 0, ops_per_img = 0;
     double valu_per_img = 0;           // ESSENTIAL vector lane-operations per image (f8_net_launch_valu): what the reference's semantics need once the MFMAs are done
     // the launcher's arguments as far as the plan decides them (bind_step); run_step copies them and adds what the run decides
-    std::variant<std::monostate, ConvArgs, StemPoolArgs, FusedArgs, ChainArgs, BChainArgs, BCChainArgs, IRArgs, IRKArgs, IRChainArgs, DwsArgs, Dws7Args, DwArgs, GConvArgs, AddArgs, PoolArgs, AvgArgs, OutArgs, ConcatArgs, UpsampleArgs, DeconvArgs, SumPoolArgs> args;
+    std::variant<std::monostate, ConvArgs, StemPoolArgs, FusedArgs, ChainArgs, BChainArgs, BCChainArgs, IRArgs, IRKArgs, IRChainArgs, DwsArgs, Dws7Args, DwArgs, GConvArgs, AddArgs, PoolArgs, AvgArgs, OutArgs, ConcatArgs, UpsampleArgs, DeconvArgs, SumPoolArgs, ChanMapArgs> args;
     int inst = 0;                      // the instance the launcher starts (the family's *_inst, f8_internal.h; bind_step)
     // S_CHAIN / S_BCHAIN: geometry, workgroups per image and resident per CU, the 7x7 cluster form (f8_cchain.hip)
     int C = 0, MID = 0, H = 0, W = 0, cin0 = 0, tiles = 0, wg_per_cu = 1; bool cluster = false;
@@ -302,6 +308,8 @@ static int64_t tensor_amax(f8_net* net, int t, int depth = 0) {
             const int sa = T.fl - net->tensors[nd.a].fl;     // 0 / 2k + 2
             constexpr int64_t cap = int64_t(1) << 40;
             if (a >= 0 && sa >= 0 && sa <= 31 && a <= (cap >> sa)) m = a << sa;
+        } else if (nd.kind == N_SLICE || nd.kind == N_SHUFFLE) {      // a subset / a permutation of the source's values
+            m = tensor_amax(net, nd.a, depth + 1);
         } else if (nd.kind == N_SUMPOOL) {                   // at most kernel^2 taps of the source's bound, under the same cap
             const int64_t a = tensor_amax(net, nd.a, depth + 1);
             const int64_t kk = (int64_t)nd.sum_k * nd.sum_k;
@@ -413,6 +421,8 @@ static const OptKey kOptKeys[] = {
     {"concat_i8", "F8_CONCAT_I8", &Options::concat_i8, 0, 1, true},
     {"upsample_i8", "F8_UPSAMPLE_I8", &Options::upsample_i8, 0, 1, true},
     {"sumpool_wide", "F8_SUMPOOL_WIDE", &Options::sumpool_wide, 0, 2, true},
+    {"chanmap_i8", "F8_CHANMAP_I8", &Options::chanmap_i8, 0, 1, true},
+    {"fuse_shuffle", "F8_FUSE_SHUFFLE", &Options::fuse_shuffle, 0, 1, true},
 };
 static const OptKey* find_opt(const char* key) {
     if (!key) return nullptr;
@@ -786,6 +796,40 @@ int f8_net_upsample(f8_net* net, int src, int mode, int scale_h, int scale_w) {
     net->nodes.push_back(nd);
     const int id = (int)net->nodes.size() - 1;
     const int t = new_tensor(net, s.C, s.H * scale_h, s.W * scale_w, fl, id);
+    net->nodes[id].out = t;
+    net->tensors[src].consumers.push_back(id);
+    return t;
+}
+
+int f8_net_slice(f8_net* net, int src, int first, int channels) {
+    if (!net) return fail(F8_ERR_INVALID, "f8_net_slice: null net");
+    if (net->finalized) return fail(F8_ERR_STATE, "f8_net_slice: net already finalized");
+    if (const int rc = check_t(net, src, "f8_net_slice")) return rc;
+    const Tensor s = net->tensors[src];
+    if (first < 0 || channels < 1 || first > s.C || channels > s.C - first)
+        return fail(F8_ERR_INVALID, "f8_net_slice: channels [%d, %d + %d) outside the source's %d", first, first, channels, s.C);
+    if (channels == s.C) return fail(F8_ERR_INVALID, "f8_net_slice: the whole tensor (%d channels) is the identity: use the source", s.C);
+    Node nd; nd.kind = N_SLICE; nd.a = src; nd.cm_first = first;
+    net->nodes.push_back(nd);
+    const int id = (int)net->nodes.size() - 1;
+    const int t = new_tensor(net, channels, s.H, s.W, s.fl, id);
+    net->nodes[id].out = t;
+    net->tensors[src].consumers.push_back(id);
+    return t;
+}
+
+int f8_net_channel_shuffle(f8_net* net, int src, int groups) {
+    if (!net) return fail(F8_ERR_INVALID, "f8_net_channel_shuffle: null net");
+    if (net->finalized) return fail(F8_ERR_STATE, "f8_net_channel_shuffle: net already finalized");
+    if (const int rc = check_t(net, src, "f8_net_channel_shuffle")) return rc;
+    const Tensor s = net->tensors[src];
+    if (groups < 2 || s.C % groups) return fail(F8_ERR_INVALID, "f8_net_channel_shuffle: groups %d must be >= 2 and divide the %d channels", groups, s.C);
+    if (groups == s.C) return fail(F8_ERR_INVALID, "f8_net_channel_shuffle: groups == channels (%d) is the identity: use the source", s.C);
+    if (groups > F8_MAX_CONCAT) return fail(F8_ERR_UNSUPPORTED, "f8_net_channel_shuffle: at most %d groups (got %d)", F8_MAX_CONCAT, groups);
+    Node nd; nd.kind = N_SHUFFLE; nd.a = src; nd.cm_groups = groups;
+    net->nodes.push_back(nd);
+    const int id = (int)net->nodes.size() - 1;
+    const int t = new_tensor(net, s.C, s.H, s.W, s.fl, id);
     net->nodes[id].out = t;
     net->tensors[src].consumers.push_back(id);
     return t;
@@ -2087,6 +2131,7 @@ static void plan_tensor_forms(f8_net* net) {
                 if (nd.pool_host < 0) add_form(T[nd.a], FORM_I32, 0, 0);      // fused behind its conv (1i): the pool's input has no form
                 break;
             case N_CONCAT: {
+                if (nd.cat_into >= 0) break;                     // the shuffle behind it reads the operands itself and asked them for its forms (N_SHUFFLE below, a later node)
                 // Mode.  concat_i8: the output exists in one or two int8 forms and nothing else (no int32 reader, no network output), and
                 // requantising source i directly by n_i = n - (out.fl - fl_i) is the same function as aligning it and requantising by n: the aligned
                 // value neither wraps nor clamps (stream_bounded) and, for n > 0, the reference's `v + 2^(n-1)` stays below 2^31 on it.  Every source is
@@ -2114,6 +2159,40 @@ static void plan_tensor_forms(f8_net* net) {
                 add_form(T[nd.a], FORM_I32, 0, 0);
                 nd.sum_wide = opt.sumpool_wide == 2 ? nd.sum_k >= 2 : opt.sumpool_wide == 1 && sumpool_wide_rule(nd.sum_k, nd.sum_stride);
                 break;
+            case N_SLICE: case N_SHUFFLE: {
+                // Mode: the nearest-upsample rule.  i8: the result exists in one or two int8 forms and nothing else (no int32 reader, no
+                // network output).  A channel gather commutes with every element-wise function, the requantisation among them, and the fraclen is the
+                // source's: the source is asked for the result's formats and the launch moves bytes, with no bound on the values.  Otherwise the int32 mode.
+                Tensor& o = T[nd.out];
+                int n8 = 0;
+                for (auto& F : o.forms) n8 += F.kind == FORM_I8;
+                nd.cm_i8 = opt.chanmap_i8 && n8 >= 1 && n8 <= 2 && (int)o.forms.size() == n8 && !is_output(net, nd.out);
+                // concat -> shuffle in one launch (option fuse_shuffle): the concat is read by this shuffle alone, has `groups` operands of one width —
+                // group i of the shuffle is then operand i — and its own i8 conditions (c) - (e) of 4.5i hold for each of the shuffle's forms.  The
+                // operands are asked for FORM_I8(n_i, sgn) exactly as concat_i8 asks; the concat gets no form and no launch.
+                const Tensor& s = T[nd.a];
+                Node& cat = ND[s.prod];
+                if (nd.kind == N_SHUFFLE && nd.cm_i8 && opt.fuse_shuffle && cat.kind == N_CONCAT && s.consumers.size() == 1 && !is_output(net, nd.a) &&
+                    (int)cat.srcs.size() == nd.cm_groups && stream_bounded(net, nd.a)) {
+                    const int64_t amax = tensor_amax(net, nd.a);
+                    bool ok = true;
+                    for (int x : cat.srcs) ok = ok && T[x].C == o.C / nd.cm_groups;
+                    for (size_t f = 0; ok && f < o.forms.size(); ++f) {
+                        const int n = o.forms[f].n;
+                        if (n > 0 && amax + (int64_t(1) << (n - 1)) > INT32_MAX) ok = false;
+                        for (int x : cat.srcs) { const int ni = n - (s.fl - T[x].fl); if (ni < -31 || ni > 30) ok = false; }
+                    }
+                    if (ok) {
+                        nd.cm_cat = s.prod; cat.cat_into = i;
+                        for (int x : cat.srcs)
+                            for (size_t f = 0; f < o.forms.size(); ++f) add_form(T[x], FORM_I8, o.forms[f].n - (s.fl - T[x].fl), o.forms[f].sgn);
+                        break;
+                    }
+                }
+                if (!nd.cm_i8) add_form(T[nd.a], FORM_I32, 0, 0);
+                else for (size_t f = 0; f < o.forms.size(); ++f) add_form(T[nd.a], FORM_I8, o.forms[f].n, o.forms[f].sgn);
+                break;
+            }
             case N_UPSAMPLE: {
                 // Mode.  upsample_nearest_i8: nearest, and the result exists in one or two int8 forms and nothing else (no int32 reader, no
                 // network output).  Replication commutes with every element-wise function, the requantisation among them, and the fraclen — so the shift — is the
@@ -2736,6 +2815,40 @@ static int emit_upsample(f8_net* net, int i, Step& st, std::vector<int>* extra) 
     return F8_OK;
 }
 
+// slice / channel shuffle; a shuffle fused with its concat (Node::cm_cat) reads the concat's operands
+static int emit_chanmap(f8_net* net, int i, Step& st, std::vector<int>* extra) {
+    auto& T = net->tensors;
+    const Node& nd = net->nodes[i];
+    const Tensor& s = T[nd.a]; Tensor& o = T[nd.out];
+    const bool fused = nd.cm_cat >= 0;
+    st.kind = S_CHANMAP;
+    st.cat_t = fused ? net->nodes[nd.cm_cat].srcs : std::vector<int>{nd.a};
+    if (o.forms.empty()) add_form(o, FORM_I32, 0, 0);
+    select_outputs(net, nd.out, &st.out, extra);
+    const double px = (double)o.H * o.W;
+    if (nd.cm_i8) {                                       // (pass 2: one or two int8 forms and no other)
+        for (int k = 0; k < 2; ++k) {
+            if (st.out.f8[k] < 0) continue;
+            const Form& F = o.forms[st.out.f8[k]];
+            for (int x : st.cat_t) {
+                const int f = find_form(T[x], FORM_I8, F.n - (s.fl - T[x].fl), F.sgn);      // (stand-alone: x is the source, the shift is 0)
+                if (f < 0) return fail(F8_ERR_STATE, "f8_net_finalize: planner bug: slice / shuffle source t%d lacks the output's int8 form", x);
+                st.cat_f[k].push_back(f);
+            }
+        }
+        st.bytes_per_img = 2.0 * px * o.C * out_forms8(st);      // every real byte read once and written once, per form
+    } else {
+        st.cat_f[0].push_back(find_form(s, FORM_I32, 0, 0));
+        st.bytes_per_img = px * o.C * 4 + out_bytes(st, o, px);
+        st.valu_per_img = px * o.C * 3 * out_forms8(st);         // 3 per int8 value produced
+    }
+    char tok[48];
+    if (nd.kind == N_SLICE) snprintf(tok, sizeof tok, "slice_%s:", nd.cm_i8 ? "i8" : "i32");
+    else snprintf(tok, sizeof tok, "%sshuffle%d_%s:", fused ? "concat+" : "", nd.cm_groups, nd.cm_i8 ? "i8" : "i32");
+    st.name = tok + tname(net, nd.out);
+    return F8_OK;
+}
+
 static int emit_sumpool(f8_net* net, int i, Step& st, std::vector<int>* extra) {
     auto& T = net->tensors;
     const Node& nd = net->nodes[i];
@@ -2808,6 +2921,7 @@ static int emit_steps(f8_net* net, int max_batch) {
         if (nd.kind == N_CONV && nd.chain_into >= 0 && nd.chain_into != i) continue;      // runs inside the chain launch of a later block
         if (nd.kind == N_MAXPOOL && nd.sp_conv >= 0) continue;
         if (nd.kind == N_AVGPOOL && nd.pool_host >= 0) continue;     // runs in its conv's launch
+        if (nd.kind == N_CONCAT && nd.cat_into >= 0) continue;       // the shuffle behind it reads its operands
         Step st; st.node = i;
         std::vector<int> extra;
         int rc = F8_OK;
@@ -2821,6 +2935,7 @@ static int emit_steps(f8_net* net, int max_batch) {
             case N_UPSAMPLE: rc = emit_upsample(net, i, st, &extra); break;
             case N_DECONV: rc = emit_deconv(net, i, st, &extra); break;
             case N_SUMPOOL: rc = emit_sumpool(net, i, st, &extra); break;
+            case N_SLICE: case N_SHUFFLE: rc = emit_chanmap(net, i, st, &extra); break;
         }
         if (rc) return rc;
         net->steps.push_back(st);
@@ -3422,6 +3537,20 @@ static int bind_step(f8_net* net, Step& st) {
             snprintf(kb, sizeof kb, "%s", upsample_kernel_name(st.inst = upsample_inst(nd.up_mode == F8_UP_BILINEAR, nd.up_i8)));
             out_formats(a.q); st.args = a; break;
         }
+        case S_CHANMAP: {
+            const Tensor& oT = T[nd.out];
+            ChanMapArgs a{};
+            a.C = oT.C; a.Cs = oT.Cs; a.groups = nd.cm_groups; a.Cg = nd.cm_groups ? oT.C / nd.cm_groups : 0;
+            a.K = nd.kind == N_SLICE ? 1 : nd.cm_groups;
+            for (int i = 0; i < a.K; ++i) {                        // the table: the one source at offset first / i * Cg, or concat operand i at 0
+                const bool fused = nd.cm_cat >= 0;
+                a.Cs_src[i] = T[st.cat_t[fused ? i : 0]].Cs;
+                a.off[i] = nd.kind == N_SLICE ? nd.cm_first : fused ? 0 : i * a.Cg;
+            }
+            make_magic((uint32_t)std::max(a.groups, 1), &a.mG, &a.s1G, &a.s2G);
+            snprintf(kb, sizeof kb, "%s", chanmap_kernel_name(st.inst = chanmap_inst(a, nd.cm_i8)));
+            out_formats(a.q); st.args = a; break;
+        }
         case S_SUMPOOL: {
             const Tensor& sT = T[st.src_t]; const Tensor& oT = T[nd.out];
             SumPoolArgs a{};
@@ -3865,6 +3994,18 @@ static int run_step(const f8_net* net, const RunIO& io, const Step& st, int n0, 
             a.N = N;
             fill_out(&a.out32, a.q);
             e = launch_upsample(a, st.inst, s);
+            break;
+        }
+        case S_CHANMAP: {
+            ChanMapArgs a = std::get<ChanMapArgs>(st.args);
+            const bool one = st.cat_t.size() == 1;                   // stand-alone: every entry is the one source
+            for (int k = 0; k < 2; ++k)
+                if (!st.cat_f[k].empty())
+                    for (int i = 0; i < a.K; ++i) { const size_t j = one ? 0 : (size_t)i; a.src[k][i] = fp(T[st.cat_t[j]].forms[st.cat_f[k][j]]); }
+            const Tensor& o = T[st.out.t];
+            a.M = N * o.H * o.W;
+            fill_out(&a.out32, a.q);
+            e = launch_chanmap(a, st.inst, s);
             break;
         }
         case S_SUMPOOL: {

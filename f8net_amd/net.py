@@ -132,6 +132,28 @@ class F8Net:
             self._L.f8_net_set_label(self._h, t, label.encode())
         return t
 
+    def slice(self, src, start, stop, label=None):
+        """Channels [start, stop) of a tensor, `x[:, start:stop]` (f8_net_slice); map size and fraclen are the source's."""
+        t = check(self._L.f8_net_slice(self._h, src, int(start), int(stop) - int(start)))
+        if label:
+            self._L.f8_net_set_label(self._h, t, label.encode())
+        return t
+
+    def split(self, src, sizes, labels=None):
+        """torch.split(x, sizes, dim=1): one slice per entry of `sizes`, in channel order."""
+        out, first = [], 0
+        for k, n in enumerate(sizes):
+            out.append(self.slice(src, first, first + int(n), label=labels[k] if labels else None))
+            first += int(n)
+        return out
+
+    def channel_shuffle(self, src, groups, label=None):
+        """torch.nn.functional.channel_shuffle(x, groups) (f8_net_channel_shuffle); map size and fraclen are the source's."""
+        t = check(self._L.f8_net_channel_shuffle(self._h, src, int(groups)))
+        if label:
+            self._L.f8_net_set_label(self._h, t, label.encode())
+        return t
+
     def maxpool(self, src, k=3, stride=2, pad=1, label=None):
         t = check(self._L.f8_net_maxpool(self._h, src, k, stride, pad))
         if label:

@@ -14,6 +14,8 @@ opset-11 vocabulary is written directly from the integer graph — per op the no
     FXQAvgPool2d                   Cast(i64), ReduceSum(-1) x2, Cast(i32)            (fix_quant_ops.py:130-133)
     windowed average pool          Cast(f32), AveragePool(count_include_pad=1, ceil_mode=0), Mul(k^2), Cast(i32)
     channel concatenation          [Pow/Cast/Mul per operand at a smaller fraction length,] Concat(axis=1)
+    channel slice                  Slice(starts [a], ends [b], axes [1], steps [1])
+    channel shuffle                Reshape([-1, g, C / g, H, W]), Transpose(perm [0, 2, 1, 3, 4]), Reshape([-1, C, H, W])
     upsampling, nearest            Resize(nearest, asymmetric, floor; scales [1, 1, sh, sw])
     upsampling, bilinear           Cast(f32), Resize(linear, half_pixel; scales [1, 1, s, s]), Mul(4 s^2), Cast(i32)
     x.view(x.size(0), -1)          Shape, Gather, Unsqueeze, Concat, Reshape         (fix_resnet.py:371)
@@ -26,7 +28,7 @@ two requants of the max-pool result share a shift (ResNet-50 `stage_0_layer_0`: 
 import numpy as np
 
 from . import onnx_io, topology
-from .onnx_import import AVGPOOL_SHIFT, IntGraph, IntOp
+from .onnx_import import AVGPOOL_SHIFT, IntGraph, IntOp, tensor_shapes
 from .onnx_io import Node
 
 
@@ -172,6 +174,14 @@ def export_graph(ig: IntGraph) -> bytes:
             y = w.cast(v, onnx_io.INT32)
         elif o.kind == 'concat':                                     # torch.cat(dim=1); `x << k` as in the residual join
             y = w.emit('Concat', [name[s] if k == 0 else w.emit('Mul', [name[s], w.pow2(k)]) for s, k in zip(o.srcs, o.shifts)], {'axis': 1})
+        elif o.kind == 'slice':                                      # x[:, a:b]
+            y = w.emit('Slice', [name[o.src], w.const([o.first], np.int64), w.const([o.first + o.channels], np.int64), w.const([1], np.int64),
+                                 w.const([1], np.int64)])
+        elif o.kind == 'shuffle':                                    # x.view(N, g, C / g, H, W).transpose(1, 2).reshape(N, C, H, W)
+            C, H, W = tensor_shapes(ig.ops[:t + 1])[t]
+            v = w.emit('Reshape', [name[o.src], w.const([-1, o.groups, C // o.groups, H, W], np.int64)])
+            v = w.emit('Transpose', [v], {'perm': [0, 2, 1, 3, 4]})
+            y = w.emit('Reshape', [v, w.const([-1, C, H, W], np.int64)])
         elif o.kind == 'upsample':
             roi, sc = w.const(np.zeros(0, np.float32), np.float32), w.const([1.0, 1.0, float(o.scale[0]), float(o.scale[1])], np.float32)
             if o.mode == 'nearest':

@@ -36,7 +36,7 @@ class OnnxImportError(ValueError):
 
 @dataclass
 class IntOp:
-    kind: str                      # input | conv | deconv | linear | add | maxpool | avgpool | avgpool2d | concat | upsample
+    kind: str                      # input | conv | deconv | linear | add | maxpool | avgpool | avgpool2d | concat | upsample | slice | shuffle
     src: int = -1                  # tensor id (index into IntGraph.ops)
     src2: int = -1                 # add: the operand that is NOT shifted
     weight: np.ndarray = None
@@ -57,6 +57,8 @@ class IntOp:
     shifts: list = None            # concat: k_i of `srcs[i] << k_i`, the alignment to the largest fraclen (the smallest is 0)
     mode: str = None               # upsample: 'nearest' | 'bilinear' (half-pixel centres; the result is the interpolated value times 4 scale^2)
     scale: tuple = None            # upsample: (scale_h, scale_w)
+    first: int = 0                 # slice: the first channel
+    channels: int = 0              # slice: how many; shuffle: the groups are in `groups`
     output_padding: int = 0        # deconv (transposed conv; weight [cin, cout, k, k]): ONNX `output_padding`, both equal
 
 
@@ -112,7 +114,7 @@ class IntGraph:
             elif o.kind == 'concat':
                 for s, k in zip(o.srcs, o.shifts):
                     eq(t, s, k)
-            elif o.kind == 'maxpool':
+            elif o.kind in ('maxpool', 'slice', 'shuffle'):
                 eq(t, o.src, 0)
             elif o.kind == 'upsample':
                 eq(t, o.src, 0 if o.mode == 'nearest' else upsample_fl_gain(o.scale))
@@ -195,6 +197,10 @@ class IntGraph:
                 ids[t] = net.maxpool(ids[o.src], o.kernel, o.stride, o.pad)
             elif o.kind == 'upsample':
                 ids[t] = net.upsample(ids[o.src], tuple(o.scale), o.mode)
+            elif o.kind == 'slice':
+                ids[t] = net.slice(ids[o.src], o.first, o.first + o.channels)
+            elif o.kind == 'shuffle':
+                ids[t] = net.channel_shuffle(ids[o.src], o.groups)
             elif o.kind == 'avgpool2d':
                 ids[t] = net.avgpool(ids[o.src], o.kernel, o.stride, o.pad, shift=o.shift)
             elif o.kind == 'avgpool':
@@ -203,6 +209,36 @@ class IntGraph:
         for k, v in (options or {}).items():
             net.set_option(k, v)
         return net.finalize(max_batch)
+
+
+def tensor_shapes(ops):
+    """[(C, H, W)] of every tensor of a list of IntOps (the shuffle's Reshape and an equal Split need the channel count and the map)."""
+    out = []
+    for o in ops:
+        if o.kind == 'input':
+            out.append(tuple(o.shape))
+            continue
+        C, H, W = out[o.src]
+        if o.kind == 'conv':
+            k = o.dilation * (o.kernel - 1) + 1
+            out.append((o.weight.shape[0], (H + 2 * o.pad - k) // o.stride + 1, (W + 2 * o.pad - k) // o.stride + 1))
+        elif o.kind == 'deconv':
+            out.append((o.weight.shape[1], (H - 1) * o.stride - 2 * o.pad + o.kernel + o.output_padding, (W - 1) * o.stride - 2 * o.pad + o.kernel + o.output_padding))
+        elif o.kind == 'linear':
+            out.append((o.weight.shape[0], 1, 1))
+        elif o.kind == 'concat':
+            out.append((sum(out[s][0] for s in o.srcs), H, W))
+        elif o.kind in ('maxpool', 'avgpool2d'):
+            out.append((C, (H + 2 * o.pad - o.kernel) // o.stride + 1, (W + 2 * o.pad - o.kernel) // o.stride + 1))
+        elif o.kind == 'upsample':
+            out.append((C, H * o.scale[0], W * o.scale[1]))
+        elif o.kind == 'avgpool':
+            out.append((C, 1, 1))
+        elif o.kind == 'slice':
+            out.append((o.channels, H, W))
+        else:                                                        # add, shuffle
+            out.append((C, H, W))
+    return out
 
 
 def avgpool2d_shift(kernel):
@@ -319,6 +355,21 @@ def import_graph(model, input_signed=False) -> IntGraph:
     def is_const(name):
         return val.get(name, ('?',))[0] == 'const'
 
+    def int_list(name):
+        """The integers of a constant or initializer operand, or None when it is neither (or absent)."""
+        v = val.get(name) if name else None
+        if v is None or v[0] not in ('const', 'init'):
+            return None
+        a = np.asarray(v[1] if v[0] == 'const' else g.initializers[v[1]]).reshape(-1)
+        return [int(x) for x in a]
+
+    def slice_op(src, first, channels, what):
+        C = tensor_shapes(ig.ops)[src][0]
+        if first < 0 or channels < 1 or first + channels > C:
+            raise OnnxImportError(f'{what}: channels [{first}, {first + channels}) outside the tensor\'s {C}')
+        ig.ops.append(IntOp('slice', src=src, first=first, channels=channels))
+        return ('T', len(ig.ops) - 1)
+
     def requant_src(name, what):
         e = val.get(name)
         if e is None or e[0] in ('const', 'init', 'opaque'):
@@ -395,6 +446,64 @@ def import_graph(model, input_signed=False) -> IntGraph:
                 val[out] = ('resize_lin', e[1], scale, gain)
             else:
                 raise OnnxImportError(f'Resize mode {mode!r}: only nearest and linear')
+        elif op == 'Split' and val.get(nd.inputs[0], ('?',))[0] == 'T':
+            # torch.split / torch.chunk along C: one slice per output.  Opset 11 carries the sizes as the attribute `split`, opset 13 as a second input
+            src = val[nd.inputs[0]][1]
+            if a.get('axis', 0) not in (1, -3):
+                raise OnnxImportError(f'Split of an activation along axis {a.get("axis", 0)}: only the channel axis (1)')
+            sizes = a.get('split') or (int_list(nd.inputs[1]) if len(nd.inputs) > 1 else None)
+            C = tensor_shapes(ig.ops)[src][0]
+            if not sizes:
+                if C % len(nd.outputs):
+                    raise OnnxImportError(f'Split of {C} channels into {len(nd.outputs)} equal parts')
+                sizes = [C // len(nd.outputs)] * len(nd.outputs)
+            if len(sizes) != len(nd.outputs) or sum(sizes) != C:
+                raise OnnxImportError(f'Split sizes {list(sizes)} do not cover the {C} channels in {len(nd.outputs)} outputs')
+            first = 0
+            for o_name, n_ch in zip(nd.outputs, sizes):
+                val[o_name] = slice_op(src, first, int(n_ch), 'Split')
+                first += int(n_ch)
+        elif op == 'Slice' and val.get(nd.inputs[0], ('?',))[0] == 'T':
+            # x[:, a:b]: Slice(x, starts, ends, axes, steps) with constant operands, the channel axis, step 1
+            src = val[nd.inputs[0]][1]
+            starts, ends = int_list(nd.inputs[1]), int_list(nd.inputs[2])
+            axes = int_list(nd.inputs[3]) if len(nd.inputs) > 3 else None
+            steps = int_list(nd.inputs[4]) if len(nd.inputs) > 4 else [1]
+            if starts is None or ends is None or (len(nd.inputs) > 3 and nd.inputs[3] and axes is None) or steps is None:
+                raise OnnxImportError('Slice: starts / ends / axes / steps are not constants')
+            if axes is None or len(axes) != 1 or axes[0] not in (1, -3) or len(starts) != 1 or len(ends) != 1:
+                raise OnnxImportError(f'Slice of an activation along axes {axes}: only the channel axis (1)')
+            if steps != [1]:
+                raise OnnxImportError(f'Slice with steps {steps}: only step 1')
+            C = tensor_shapes(ig.ops)[src][0]
+            lo = starts[0] + C if starts[0] < 0 else starts[0]
+            hi = min(ends[0] + C if ends[0] < 0 else ends[0], C)     # (torch writes `x[:, a:]` with ends = INT64_MAX)
+            val[out] = slice_op(src, lo, hi - lo, 'Slice')
+        elif op == 'Transpose':
+            # the middle of torch's channel_shuffle: view(N, g, C / g, H, W).transpose(1, 2).reshape(N, C, H, W)
+            e = val.get(nd.inputs[0], ('?',))
+            if e[0] != 'reshape5':
+                raise OnnxImportError('Transpose of something other than an activation reshaped to [N, groups, C / groups, H, W]')
+            if list(a.get('perm', [])) != [0, 2, 1, 3, 4]:
+                raise OnnxImportError(f'Transpose with perm {list(a.get("perm", []))}: only [0, 2, 1, 3, 4] (the channel shuffle)')
+            val[out] = ('shuffle_t',) + e[1:]
+        elif op == 'Reshape' and val.get(nd.inputs[0], ('?',))[0] in ('T', 'shuffle_t') and int_list(nd.inputs[1]) is not None and \
+                len(int_list(nd.inputs[1])) in (4, 5):
+            e, shape = val[nd.inputs[0]], int_list(nd.inputs[1])
+            if e[0] == 'T':                                          # [N | 0 | -1, g, C / g, H, W]
+                C, H, W = tensor_shapes(ig.ops)[e[1]]
+                if len(shape) != 5:
+                    raise OnnxImportError(f'Reshape of an activation to {shape}: only [N, groups, C / groups, H, W] (the channel shuffle)')
+                _, gr, cg, h, w_ = shape
+                if gr < 1 or cg < 1 or gr * cg != C or (h, w_) != (H, W):
+                    raise OnnxImportError(f'Reshape of a [{C}, {H}, {W}] activation to {shape}: groups x (C / groups) must be {C} and the map {H} x {W}')
+                val[out] = ('reshape5', e[1], gr)
+            else:                                                    # back to [N | 0 | -1, C, H, W]
+                C, H, W = tensor_shapes(ig.ops)[e[1]]
+                if len(shape) != 4 or shape[1:] != [C, H, W]:
+                    raise OnnxImportError(f'Reshape behind the shuffle\'s Transpose to {shape}: expected [N, {C}, {H}, {W}]')
+                ig.ops.append(IntOp('shuffle', src=e[1], groups=e[2]))
+                val[out] = ('T', len(ig.ops) - 1)
         elif op in ('Shape', 'Gather', 'Unsqueeze', 'Concat'):
             val[out] = ('opaque',)                                 # the `x.view(x.size(0), -1)` plumbing before the FC
         elif op == 'Reshape':

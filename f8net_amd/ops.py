@@ -184,6 +184,23 @@ class F8AvgPool2d(nn.Module):
         return res
 
 
+class F8ChannelShuffle(nn.Module):
+    """nn.ChannelShuffle(groups) on int32 device tensors with a HIP forward (`torch.ops.f8net.channel_shuffle`): out[:, c] = x[:, (c % groups) *
+    (C / groups) + c / groups].  A permutation of channels: the fraclen is the input's."""
+
+    def __init__(self, groups):
+        super().__init__()
+        self.groups = int(groups)
+        self.int_op_only = True
+
+    def forward(self, x):
+        _require_dev_i32(x, 'F8ChannelShuffle')
+        res = torch.ops.f8net.channel_shuffle(x, self.groups)
+        if hasattr(x, 'output_fraclen'):
+            setattr(res, 'output_fraclen', x.output_fraclen)
+        return res
+
+
 class F8MaxPool2d(nn.Module):
     """Head max-pool (fix_resnet.py:358-359 float detour / FXQMaxPool2d): exact integer max."""
 

@@ -13,6 +13,7 @@ the dispatcher.
     f8net::linear(x, w, b, weight_fl, input_fl, input_signed)                         `self.classifier(x)`, int_fc :1165-1195
     f8net::avgpool_sum(x)                            FXQAvgPool2d int branch          fix_quant_ops.py:126-134
     f8net::maxpool(x, k, stride, pad)                head max-pool                    fix_resnet.py:358-359
+    f8net::channel_shuffle(x, groups)                torch.nn.functional.channel_shuffle on int32 (f8_net_channel_shuffle; no reference call site)
     f8net::net_forward(x, handle)                    IntModel.forward                 fix_resnet.py:352-383 (handle: register_net)
     f8net::net_forward_taps(x, handle)               ... of a net with further outputs (F8Net.output called more than once): all of them
     f8net::net_forward_f32(images, handle, normalize)  forward_loss input quantisation + IntModel.forward, fix_train.py:683-692
@@ -43,6 +44,7 @@ _DEF.define('linear(Tensor x, Tensor weight, Tensor? bias, int weight_fl, int in
 _DEF.define('avgpool_sum(Tensor x) -> Tensor')
 _DEF.define('avgpool2d_sum(Tensor x, int k, int stride, int pad) -> Tensor')
 _DEF.define('maxpool(Tensor x, int k, int stride, int pad) -> Tensor')
+_DEF.define('channel_shuffle(Tensor x, int groups) -> Tensor')
 _DEF.define('net_forward(Tensor x, int handle) -> Tensor')
 _DEF.define('net_forward_taps(Tensor x, int handle) -> Tensor[]')
 _DEF.define('net_forward_f32(Tensor images, int handle, bool normalize) -> Tensor')
@@ -277,6 +279,22 @@ def _maxpool(x, k, stride, pad):
     return _plans.get(('max', x.device.index, C, H, W, k, stride, pad), (), N, build).run(x).view(N, C, P, Q)
 
 
+def _channel_shuffle(x, groups):
+    """out[:, c] = x[:, (c % groups) * (C / groups) + c / groups] (f8_net_channel_shuffle): [N, C, H, W] -> [N, C, H, W]."""
+    _i32(x, 'channel_shuffle')
+    x = x.contiguous()
+    N, C, H, W = x.shape
+
+    def build(n):
+        net = F8Net()
+        t = net.input(C, H, W, 0)
+        t = net.channel_shuffle(t, groups)
+        net.output(t, as_float=False)
+        return net.finalize(n)
+
+    return _plans.get(('shuffle', x.device.index, C, H, W, groups), (), N, build).run(x).view(N, C, H, W)
+
+
 # ------------------------------------------------------------------------------------------ whole nets
 _nets = {}
 
@@ -309,7 +327,7 @@ def _net_forward_f32(images, handle, normalize):
 # ------------------------------------------------------------------------------------------ registration
 _CUDA = Library('f8net', 'IMPL', 'CUDA')
 for _n, _f in (('requant', _requant), ('relu_', _relu_), ('add_align_', _add_align_), ('conv2d', _conv2d), ('conv_transpose2d', _conv_transpose2d), ('linear', _linear),
-               ('avgpool_sum', _avgpool_sum), ('avgpool2d_sum', _avgpool2d_sum), ('maxpool', _maxpool), ('net_forward', _net_forward), ('net_forward_taps', _net_forward_taps),
+               ('avgpool_sum', _avgpool_sum), ('avgpool2d_sum', _avgpool2d_sum), ('maxpool', _maxpool), ('channel_shuffle', _channel_shuffle), ('net_forward', _net_forward), ('net_forward_taps', _net_forward_taps),
                ('net_forward_f32', _net_forward_f32)):
     _CUDA.impl(_n, _f)
 
@@ -327,6 +345,7 @@ _META.impl('avgpool2d_sum', lambda x, k, stride, pad: x.new_empty(
     (x.shape[0], x.shape[1], (x.shape[2] + 2 * pad - k) // stride + 1, (x.shape[3] + 2 * pad - k) // stride + 1)))
 _META.impl('maxpool', lambda x, k, stride, pad: x.new_empty(
     (x.shape[0], x.shape[1], (x.shape[2] + 2 * pad - k) // stride + 1, (x.shape[3] + 2 * pad - k) // stride + 1)))
+_META.impl('channel_shuffle', lambda x, groups: torch.empty_like(x))
 _META.impl('net_forward', lambda x, handle: x.new_empty((x.shape[0], _nets[handle].out_elems),
                                                         dtype=torch.float32 if _nets[handle].out_float else torch.int32))
 _META.impl('net_forward_taps', lambda x, handle: [x.new_empty((x.shape[0], _nets[handle].out_elems), dtype=torch.float32 if _nets[handle].out_float else torch.int32)] + [

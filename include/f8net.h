@@ -205,6 +205,23 @@ int f8_net_concat(f8_net* net, const int* srcs, int n);
 #define F8_UP_BILINEAR 1
 int f8_net_upsample(f8_net* net, int src, int mode, int scale_h, int scale_w);
 
+/* Channel slice and channel shuffle (the split and the shuffle of a ShuffleNet unit, torch.split / x[:, a:b] of a CSPNet, GhostNet or Res2Net block,
+ * a head that reads part of a tensor).  Both are pure channel gathers of one map: H, W and the fraclen are the source's, and there is no
+ * arithmetic at all — no shift, no clamp, no ReLU.
+ *   f8_net_slice            out = src[:, first : first + channels].
+ *   f8_net_channel_shuffle  torch.nn.functional.channel_shuffle: out[c] = src[(c % groups) * (C / groups) + c / groups].
+ * Both return the tensor id.  F8_ERR_INVALID: a bad tensor id; a slice with first < 0, channels < 1 or first + channels > C, or of the whole
+ * tensor (the identity); a shuffle with groups < 2, groups not dividing C, or groups == C (the identity).  F8_ERR_UNSUPPORTED: groups >
+ * F8_MAX_CONCAT (the launch's operand table).  F8_ERR_STATE after finalize.
+ * The plan runs each as one launch of f8_chanmap.hip, its mode shown by its token: `slice_i8:` / `shuffle{g}_i8:` — the result is read in at most
+ * two int8 formats and by nothing else — have the source's producer write those formats and move bytes; `slice_i32:` / `shuffle{g}_i32:` read the
+ * source's int32 form (option chanmap_i8 = 0: always).  A concat of `groups` operands of one width that an i8-mode shuffle alone reads emits no
+ * launch: the shuffle launch reads the operands, token `concat+shuffle{g}_i8:` (option fuse_shuffle = 0: two launches).  Same values in every case.
+ * A tensor read by a slice or a shuffle exists in device memory: no fused block or chain launch keeps it on chip (it cuts a launch as an output
+ * tap does). */
+int f8_net_slice(f8_net* net, int src, int first, int channels);
+int f8_net_channel_shuffle(f8_net* net, int src, int groups);
+
 /* Head max-pool nn.MaxPool2d(k, stride, pad) via the float detour (fix_resnet.py:358-359) or
  * FXQMaxPool2d (fix_quant_ops.py:150-157); exact integer max. */
 int f8_net_maxpool(f8_net* net, int src, int kernel, int stride, int pad);
@@ -394,7 +411,12 @@ int f8_net_check(f8_net* net);
  *               int32 form, token upsample_nearest_i32:.  Same values either way, bit for bit),
  *               sumpool_wide (default 1: a windowed average pool whose windows do not overlap (stride >= kernel) and whose kernel is at or above the
  *               measured crossover, 3, runs f8::sumpool_wide_kernel — a group of lanes per output value —, every other f8::sumpool_i32_kernel<K>;
- *               0: every pool runs the walker; 2: every pool with kernel >= 2 runs the wide kernel, for tests.  Same values on every leg, bit for bit)
+ *               0: every pool runs the walker; 2: every pool with kernel >= 2 runs the wide kernel, for tests.  Same values on every leg, bit for bit),
+ *               chanmap_i8 (default 1: a slice or channel shuffle whose result is read in at most two int8 formats and by nothing else moves bytes
+ *               of its source's int8 forms, plan tokens slice_i8: / shuffle{g}_i8:; 0: every one runs f8::chanmap_i32_kernel on the int32 form, tokens
+ *               slice_i32: / shuffle{g}_i32:.  Same values either way, bit for bit),
+ *               fuse_shuffle (default 1: a concat of `groups` operands of one width that only an i8-mode shuffle reads emits no launch; the shuffle
+ *               launch reads the operands, token concat+shuffle{g}_i8:; 0: two launches.  Same values either way, bit for bit)
  *   scheduling: chunk56 / chunk28 / chunk14 (images per chunk of the fused blocks; -1 = derived from chunk_budget_mb, 0 = whole
  *               batch), chunk_budget_mb (memory-side cache a chunk's int32 stream may occupy), chunk_ds, chunk_opener,
  *               split_streams, graph, stagger, stagger_pipelined, stem_wpc, stem_grid_div (row-walking head on 1 / n of the CUs; 0 = by output form), wstat_grid_div (0 .. 32, default 0, environment F8_WSTAT_GRID_DIV: f8::conv1x1_wstat_kernel sizes its pixel groups for 1 / n of the CUs, at least one — tests walk long tile rings on small maps; 0 = all of them; the plan and the values do not move), check_device, check_input_range, pipeline_depth (2..4 runs in flight),
