@@ -108,15 +108,13 @@ struct Node {
     int pk = 0, pstride = 0, ppad = 0; // maxpool
     int shift = 0;                     // avgpool
     std::vector<int> srcs;             // concat: the operands in channel order (tensor ids; a = srcs[0])
-    bool concat_i8 = false;            // concat, pass 2: the byte-gather mode (every source in the output's int8 formats); false: sources in int32
+    bool bytes_mode = false;           // concat / upsample / slice / shuffle, pass 2: the launch moves bytes, its sources are held in the output's int8 formats; false: sources in int32
     int up_mode = 0, up_sh = 1, up_sw = 1;      // upsample: F8_UP_NEAREST / F8_UP_BILINEAR, the scales
     int sum_k = 0, sum_stride = 0, sum_pad = 0;   // sumpool: the window (its fraclen shift is in the output tensor's fl alone)
     bool sum_wide = false;             // sumpool, pass 2: sumpool_wide_kernel (option sumpool_wide); false: the block walker
     int cm_first = 0, cm_groups = 0;   // slice: the first source channel; shuffle: the groups
-    bool cm_i8 = false;                // slice / shuffle, pass 2: the byte-gather mode (the source in the output's int8 formats); false: the source in int32
     int cm_cat = -1;                   // shuffle, pass 2: the concat node in front of it whose operands this launch reads itself (option fuse_shuffle), else -1
     int cat_into = -1;                 // concat, pass 2: the shuffle node whose launch reads this concat's operands: no launch and no form of its own
-    bool up_i8 = false;                // upsample, pass 2: the byte-copy mode (nearest, the source in the output's int8 formats); false: the source in int32
     // planning
     int fused_into = -1;               // add: conv node that carries it
     int fused_add = -1;                // conv: add node carried
@@ -151,9 +149,14 @@ struct Step {
     int src_t = -1, src_f = -1;        // main input tensor / form
     int res_t = -1, res_f = -1;        // residual (conv) or second operand (add)
     int src2_t = -1, src2_f = -1;      // dual GEMM: input of the second conv
-    // S_CONCAT reads K tensors (S_UPSAMPLE: one, in up to two forms; S_CHANMAP: one, or the operands of the concat it is fused with) and keeps them HERE, with src_t = res_t = src2_t = -1: code that asks what a step reads (lifetimes: layout_arena; users of the
-    // network input: let_stem_read_input) must look at cat_t as well as the three *_t above; step_chunk / for_each_launch index tensors[src_t] only for S_FUSED
-    std::vector<int> cat_t, cat_f[2];  // S_UPSAMPLE: the one source, forms as for S_CONCAT: the source tensors and their forms — i8 mode: cat_f[k] = the sources in the format of output form out.f8[k]; i32 mode: cat_f[0] = their int32 forms
+    // The gather steps keep what they read HERE, with src_t = res_t = src2_t = -1 (select_sources fills it, gather_sources reads it):
+    //   cat_t     the source tensors.  S_CONCAT: its K operands in channel order.  S_UPSAMPLE: the one source.  S_CHANMAP: the one source, or the operands
+    //             of the concat the shuffle is fused with (Node::cm_cat).
+    //   cat_f[k]  one form index per entry of cat_t.  Bytes mode (Node::bytes_mode): cat_f[k][j] = source j in the format of output form out.f8[k], empty
+    //             where out.f8[k] < 0.  Otherwise cat_f[0][j] = source j's int32 form and cat_f[1] is empty.
+    // Code that asks what a step reads must look at cat_t as well as the three *_t above: layout_arena (lifetimes) and let_stem_read_input (users of the
+    // network input) do.  step_chunk / for_each_launch index tensors[src_t] only for S_FUSED and need not.
+    std::vector<int> cat_t, cat_f[2];
     OutSel out;
     int acc_shl = 0, res_shl = 0, relu0 = 0, relu1 = 0;
     bool dense = false;
@@ -1281,6 +1284,11 @@ static void select_outputs(f8_net* net, int t, OutSel* o, std::vector<int>* extr
             else if (extra) extra->push_back((int)i);
         }
 }
+// ... for a launch of its own whose result nothing asked for in any form: it writes the int32 form
+static void select_outputs_or_i32(f8_net* net, int t, OutSel* o, std::vector<int>* extra) {
+    if (net->tensors[t].forms.empty()) add_form(net->tensors[t], FORM_I32, 0, 0);
+    select_outputs(net, t, o, extra);
+}
 
 // Essential vector work of a launch (VERDICT r5 #1b: the counters' SQ_INSTS_VALU x 64 divided by this = issued / essential): per value of the
 // reference's semantics, with the cheapest exact integer forms of f8_device.h —
@@ -2018,6 +2026,37 @@ static void plan_depthwise_separable_7x7(f8_net* net, int max_batch) {
 }
 
 // pass 2
+// The mode rule of the gathers — concat, nearest upsample, slice / shuffle.  Bytes mode: the result exists in one or two int8 forms
+// and nothing else (no int32 reader, no network output: int8_forms_only); the sources are then asked for the result's formats and the launch moves
+// bytes.  Otherwise the sources are read as int32 (ask_sources).  Replication and channel selection commute with every element-wise function, the
+// requantisation among them, so upsample and a stand-alone slice / shuffle need no more; a concat also aligns fraclens and needs requant_commutes.
+static bool int8_forms_only(const f8_net* net, int t) {
+    const Tensor& o = net->tensors[t];
+    int n8 = 0;
+    for (auto& F : o.forms) n8 += F.kind == FORM_I8;
+    return n8 >= 1 && n8 <= 2 && (int)o.forms.size() == n8 && !is_output(net, t);
+}
+// Conditions (c) - (e) of 4.5i: requantising operand i directly by n_i = n - (fl_ref - fl_i) is the same function as aligning it to fl_ref and
+// requantising by n, for every n of `forms`.  The aligned value neither wraps nor clamps (stream_bounded on tensor t, the concat's result), for n > 0
+// the reference's `v + 2^(n-1)` stays below 2^31 on it, and every n_i is a shift the kernels have (-31 .. 30).
+static bool requant_commutes(f8_net* net, const std::vector<int>& srcs, int t, const std::vector<Form>& forms) {
+    const int64_t amax = tensor_amax(net, t);
+    if (!stream_bounded(net, t)) return false;
+    for (const Form& F : forms) {
+        if (F.n > 0 && amax + (int64_t(1) << (F.n - 1)) > INT32_MAX) return false;
+        for (int x : srcs) { const int ni = F.n - (net->tensors[t].fl - net->tensors[x].fl); if (ni < -31 || ni > 30) return false; }
+    }
+    return true;
+}
+// asks every source for its int32 form or, in bytes mode, for `forms` (the result's) shifted by fl_ref - fl_i (0 for upsample and a stand-alone slice / shuffle)
+static void ask_sources(f8_net* net, const std::vector<int>& srcs, int fl_ref, const std::vector<Form>& forms, bool bytes_mode) {
+    for (int x : srcs) {
+        Tensor& s = net->tensors[x];
+        if (!bytes_mode) { add_form(s, FORM_I32, 0, 0); continue; }
+        for (const Form& F : forms) add_form(s, FORM_I8, F.n - (fl_ref - s.fl), F.sgn);
+    }
+}
+
 static void plan_tensor_forms(f8_net* net) {
     auto& T = net->tensors;
     auto& ND = net->nodes;
@@ -2132,25 +2171,11 @@ static void plan_tensor_forms(f8_net* net) {
                 break;
             case N_CONCAT: {
                 if (nd.cat_into >= 0) break;                     // the shuffle behind it reads the operands itself and asked them for its forms (N_SHUFFLE below, a later node)
-                // Mode.  concat_i8: the output exists in one or two int8 forms and nothing else (no int32 reader, no network output), and
-                // requantising source i directly by n_i = n - (out.fl - fl_i) is the same function as aligning it and requantising by n: the aligned
-                // value neither wraps nor clamps (stream_bounded) and, for n > 0, the reference's `v + 2^(n-1)` stays below 2^31 on it.  Every source is
-                // then asked for the output's formats and the launch copies bytes.  Otherwise concat_i32: the sources' int32 forms, aligned in the launch.
-                Tensor& o = T[nd.out];
-                const int64_t amax = tensor_amax(net, nd.out);
-                int n8 = 0;
-                for (auto& F : o.forms) n8 += F.kind == FORM_I8;
-                bool i8 = opt.concat_i8 && n8 >= 1 && n8 <= 2 && (int)o.forms.size() == n8 && !is_output(net, nd.out) && stream_bounded(net, nd.out);
-                for (size_t f = 0; i8 && f < o.forms.size(); ++f) {
-                    const int n = o.forms[f].n;
-                    if (n > 0 && amax + (int64_t(1) << (n - 1)) > INT32_MAX) i8 = false;
-                    for (int x : nd.srcs) { const int ni = n - (o.fl - T[x].fl); if (ni < -31 || ni > 30) i8 = false; }
-                }
-                nd.concat_i8 = i8;
-                for (int x : nd.srcs) {
-                    if (!i8) { add_form(T[x], FORM_I32, 0, 0); continue; }
-                    for (size_t f = 0; f < o.forms.size(); ++f) add_form(T[x], FORM_I8, o.forms[f].n - (o.fl - T[x].fl), o.forms[f].sgn);
-                }
+                // the mode rule with conditions (c) - (e); they are evaluated first, whatever the mode: that bounds the stream (tensor_amax caches) here
+                const Tensor& o = T[nd.out];
+                const bool exact = requant_commutes(net, nd.srcs, nd.out, o.forms);
+                nd.bytes_mode = opt.concat_i8 && int8_forms_only(net, nd.out) && exact;
+                ask_sources(net, nd.srcs, o.fl, o.forms, nd.bytes_mode);
                 break;
             }
             case N_SUMPOOL:
@@ -2160,50 +2185,25 @@ static void plan_tensor_forms(f8_net* net) {
                 nd.sum_wide = opt.sumpool_wide == 2 ? nd.sum_k >= 2 : opt.sumpool_wide == 1 && sumpool_wide_rule(nd.sum_k, nd.sum_stride);
                 break;
             case N_SLICE: case N_SHUFFLE: {
-                // Mode: the nearest-upsample rule.  i8: the result exists in one or two int8 forms and nothing else (no int32 reader, no
-                // network output).  A channel gather commutes with every element-wise function, the requantisation among them, and the fraclen is the
-                // source's: the source is asked for the result's formats and the launch moves bytes, with no bound on the values.  Otherwise the int32 mode.
-                Tensor& o = T[nd.out];
-                int n8 = 0;
-                for (auto& F : o.forms) n8 += F.kind == FORM_I8;
-                nd.cm_i8 = opt.chanmap_i8 && n8 >= 1 && n8 <= 2 && (int)o.forms.size() == n8 && !is_output(net, nd.out);
+                // the mode rule alone: the fraclen is the source's and no bound on the values is needed
+                const Tensor& o = T[nd.out];
+                nd.bytes_mode = opt.chanmap_i8 && int8_forms_only(net, nd.out);
                 // concat -> shuffle in one launch (option fuse_shuffle): the concat is read by this shuffle alone, has `groups` operands of one width —
-                // group i of the shuffle is then operand i — and its own i8 conditions (c) - (e) of 4.5i hold for each of the shuffle's forms.  The
-                // operands are asked for FORM_I8(n_i, sgn) exactly as concat_i8 asks; the concat gets no form and no launch.
+                // group i of the shuffle is then operand i — and its own conditions (c) - (e) hold for each of the shuffle's forms.  The operands are
+                // asked for the forms a concat in bytes mode asks for; the concat gets no form and no launch.
                 const Tensor& s = T[nd.a];
                 Node& cat = ND[s.prod];
-                if (nd.kind == N_SHUFFLE && nd.cm_i8 && opt.fuse_shuffle && cat.kind == N_CONCAT && s.consumers.size() == 1 && !is_output(net, nd.a) &&
-                    (int)cat.srcs.size() == nd.cm_groups && stream_bounded(net, nd.a)) {
-                    const int64_t amax = tensor_amax(net, nd.a);
-                    bool ok = true;
-                    for (int x : cat.srcs) ok = ok && T[x].C == o.C / nd.cm_groups;
-                    for (size_t f = 0; ok && f < o.forms.size(); ++f) {
-                        const int n = o.forms[f].n;
-                        if (n > 0 && amax + (int64_t(1) << (n - 1)) > INT32_MAX) ok = false;
-                        for (int x : cat.srcs) { const int ni = n - (s.fl - T[x].fl); if (ni < -31 || ni > 30) ok = false; }
-                    }
-                    if (ok) {
-                        nd.cm_cat = s.prod; cat.cat_into = i;
-                        for (int x : cat.srcs)
-                            for (size_t f = 0; f < o.forms.size(); ++f) add_form(T[x], FORM_I8, o.forms[f].n - (s.fl - T[x].fl), o.forms[f].sgn);
-                        break;
-                    }
-                }
-                if (!nd.cm_i8) add_form(T[nd.a], FORM_I32, 0, 0);
-                else for (size_t f = 0; f < o.forms.size(); ++f) add_form(T[nd.a], FORM_I8, o.forms[f].n, o.forms[f].sgn);
+                bool fuse = nd.kind == N_SHUFFLE && nd.bytes_mode && opt.fuse_shuffle && cat.kind == N_CONCAT && s.consumers.size() == 1 && !is_output(net, nd.a) &&
+                            (int)cat.srcs.size() == nd.cm_groups && requant_commutes(net, cat.srcs, nd.a, o.forms);
+                for (size_t k = 0; fuse && k < cat.srcs.size(); ++k) fuse = T[cat.srcs[k]].C == o.C / nd.cm_groups;
+                if (fuse) { nd.cm_cat = s.prod; cat.cat_into = i; }
+                ask_sources(net, nd.cm_cat >= 0 ? cat.srcs : std::vector<int>{nd.a}, s.fl, o.forms, nd.bytes_mode);
                 break;
             }
             case N_UPSAMPLE: {
-                // Mode.  upsample_nearest_i8: nearest, and the result exists in one or two int8 forms and nothing else (no int32 reader, no
-                // network output).  Replication commutes with every element-wise function, the requantisation among them, and the fraclen — so the shift — is the
-                // source's: the source is asked for the result's formats and the launch copies bytes.  No bound on the values is needed (the concat rule
-                // without its conditions (c) - (e)).  Otherwise the int32 mode: the source's int32 form, replicated / interpolated in the launch.
-                Tensor& o = T[nd.out];
-                int n8 = 0;
-                for (auto& F : o.forms) n8 += F.kind == FORM_I8;
-                nd.up_i8 = opt.upsample_i8 && nd.up_mode == F8_UP_NEAREST && n8 >= 1 && n8 <= 2 && (int)o.forms.size() == n8 && !is_output(net, nd.out);
-                if (!nd.up_i8) add_form(T[nd.a], FORM_I32, 0, 0);
-                else for (size_t f = 0; f < o.forms.size(); ++f) add_form(T[nd.a], FORM_I8, o.forms[f].n, o.forms[f].sgn);
+                // the mode rule alone, for nearest: the fraclen — so the shift — is the source's and no bound on the values is needed
+                nd.bytes_mode = opt.upsample_i8 && nd.up_mode == F8_UP_NEAREST && int8_forms_only(net, nd.out);
+                ask_sources(net, {nd.a}, T[nd.a].fl, T[nd.out].forms, nd.bytes_mode);
                 break;
             }
             default: break;
@@ -2685,8 +2685,7 @@ static int emit_deconv(f8_net* net, int i, Step& st, std::vector<int>* extra) {
     if (const int rc = conv_input_i8(net, nd, &st.src_t, &st.src_f)) return rc;
     st.relu0 = d.relu;
     pack_deconv_weights(net, nd);
-    if (o.forms.empty()) add_form(o, FORM_I32, 0, 0);
-    select_outputs(net, nd.out, &st.out, extra);
+    select_outputs_or_i32(net, nd.out, &st.out, extra);
     const double ipx = (double)s.H * s.W, opx = (double)o.H * o.W;
     st.ops_per_img = 2.0 * ipx * d.kernel * d.kernel * d.cin * d.cout;      // every input pixel meets every tap once (what lands outside the output is cropped)
     st.bytes_per_img = ipx * s.Cs + out_bytes(st, o, opx);                  // input once + the output forms
@@ -2738,8 +2737,7 @@ static int emit_maxpool(f8_net* net, int i, Step& st, std::vector<int>* extra) {
     st.src_t = nd.a;
     const bool i8 = (o.forms.size() == 1 && o.forms[0].kind == FORM_I8);
     st.src_f = i8 ? find_form(s, FORM_I8, o.forms[0].n, o.forms[0].sgn) : find_form(s, FORM_I32, 0, 0);
-    if (o.forms.empty()) add_form(o, FORM_I32, 0, 0);
-    select_outputs(net, nd.out, &st.out, extra);
+    select_outputs_or_i32(net, nd.out, &st.out, extra);
     st.name = std::string(i8 ? "maxpool_i8:" : "maxpool_i32:") + tname(net, nd.out);
     st.bytes_per_img = (double)s.H * s.W * s.Cs * (i8 ? 1 : 4) + out_bytes(st, o, (double)o.H * o.W);
     return F8_OK;
@@ -2751,103 +2749,89 @@ static int emit_avgpool(f8_net* net, int i, Step& st, std::vector<int>* extra) {
     const Tensor& s = T[nd.a]; Tensor& o = T[nd.out];
     st.kind = S_AVGPOOL;
     st.src_t = nd.a; st.src_f = find_form(s, FORM_I32, 0, 0);
-    if (o.forms.empty()) add_form(o, FORM_I32, 0, 0);
-    select_outputs(net, nd.out, &st.out, extra);
+    select_outputs_or_i32(net, nd.out, &st.out, extra);
     st.name = "avgpool_sum:" + tname(net, nd.out);
     st.bytes_per_img = (double)s.H * s.W * s.Cs * 4 + (double)o.Cs * 5;
     return F8_OK;
 }
 
-static int emit_concat(f8_net* net, int i, Step& st, std::vector<int>* extra) {
-    auto& T = net->tensors;
-    const Node& nd = net->nodes[i];
-    Tensor& o = T[nd.out];
-    st.kind = S_CONCAT;
-    st.cat_t = nd.srcs;
-    if (o.forms.empty()) add_form(o, FORM_I32, 0, 0);
-    select_outputs(net, nd.out, &st.out, extra);
-    const double px = (double)o.H * o.W;
-    if (nd.concat_i8) {                                   // (pass 2: one or two int8 forms and no other)
-        for (int k = 0; k < 2; ++k) {
-            if (st.out.f8[k] < 0) continue;
-            const Form& F = o.forms[st.out.f8[k]];
-            for (int x : nd.srcs) {
-                const int f = find_form(T[x], FORM_I8, F.n - (o.fl - T[x].fl), F.sgn);
-                if (f < 0) return fail(F8_ERR_STATE, "f8_net_finalize: planner bug: concat source t%d lacks the output's int8 form", x);
-                st.cat_f[k].push_back(f);
-            }
+// What a gather step reads (Step::cat_t / cat_f), st.out chosen: in bytes mode every source in the format of each int8 output form, shifted by
+// fl_ref - fl_i as pass 2 asked for it (ask_sources); else the sources' int32 forms.
+static int select_sources(f8_net* net, Step& st, const std::vector<int>& srcs, int fl_ref, bool bytes_mode, const char* op) {
+    const auto& T = net->tensors;
+    st.cat_t = srcs;
+    if (!bytes_mode)
+        for (int x : srcs) st.cat_f[0].push_back(find_form(T[x], FORM_I32, 0, 0));
+    for (int k = 0; bytes_mode && k < 2; ++k) {
+        if (st.out.f8[k] < 0) continue;
+        const Form& F = T[st.out.t].forms[st.out.f8[k]];
+        for (int x : srcs) {
+            const int f = find_form(T[x], FORM_I8, F.n - (fl_ref - T[x].fl), F.sgn);
+            if (f < 0) return fail(F8_ERR_STATE, "f8_net_finalize: planner bug: %s source t%d lacks the output's int8 form", op, x);
+            st.cat_f[k].push_back(f);
         }
+    }
+    return F8_OK;
+}
+
+static int emit_concat(f8_net* net, int i, Step& st, std::vector<int>* extra) {
+    const Node& nd = net->nodes[i];
+    const Tensor& o = net->tensors[nd.out];
+    st.kind = S_CONCAT;
+    select_outputs_or_i32(net, nd.out, &st.out, extra);
+    if (const int rc = select_sources(net, st, nd.srcs, o.fl, nd.bytes_mode, "concat")) return rc;
+    const double px = (double)o.H * o.W;
+    if (nd.bytes_mode) {
         st.bytes_per_img = 2.0 * px * o.C * out_forms8(st);      // every real byte read once and written once, per form
     } else {
-        for (int x : nd.srcs) st.cat_f[0].push_back(find_form(T[x], FORM_I32, 0, 0));
         st.bytes_per_img = px * o.C * 4 + out_bytes(st, o, px);
         st.valu_per_img = px * o.C * (2 + 3 * out_forms8(st));   // align + clamp per value, 3 per int8 value produced
     }
-    st.name = (nd.concat_i8 ? "concat_i8:" : "concat_i32:") + tname(net, nd.out);
+    st.name = (nd.bytes_mode ? "concat_i8:" : "concat_i32:") + tname(net, nd.out);
     return F8_OK;
 }
 
 static int emit_upsample(f8_net* net, int i, Step& st, std::vector<int>* extra) {
-    auto& T = net->tensors;
     const Node& nd = net->nodes[i];
-    const Tensor& s = T[nd.a]; Tensor& o = T[nd.out];
+    const Tensor& s = net->tensors[nd.a]; const Tensor& o = net->tensors[nd.out];
     st.kind = S_UPSAMPLE;
-    st.cat_t = {nd.a};
-    if (o.forms.empty()) add_form(o, FORM_I32, 0, 0);
-    select_outputs(net, nd.out, &st.out, extra);
+    select_outputs_or_i32(net, nd.out, &st.out, extra);
+    if (const int rc = select_sources(net, st, {nd.a}, s.fl, nd.bytes_mode, "upsample")) return rc;
     const double ipx = (double)s.H * s.W, opx = (double)o.H * o.W;
     const bool bil = nd.up_mode == F8_UP_BILINEAR;
-    if (nd.up_i8) {                                       // (pass 2: one or two int8 forms and no other)
-        for (int k = 0; k < 2; ++k) {
-            if (st.out.f8[k] < 0) continue;
-            const Form& F = o.forms[st.out.f8[k]];
-            const int f = find_form(s, FORM_I8, F.n, F.sgn);
-            if (f < 0) return fail(F8_ERR_STATE, "f8_net_finalize: planner bug: upsample source t%d lacks the output's int8 form", nd.a);
-            st.cat_f[k].push_back(f);
-        }
+    if (nd.bytes_mode) {
         st.bytes_per_img = (ipx + opx) * o.C * out_forms8(st);      // every real byte read once and written once, per form
     } else {
-        st.cat_f[0].push_back(find_form(s, FORM_I32, 0, 0));
         st.bytes_per_img = ipx * o.C * 4 + out_bytes(st, o, opx);
         st.valu_per_img = opx * o.C * ((bil ? 4 : 0) + 3 * out_forms8(st));      // bilinear: one multiply + three multiply-adds per value; 3 per int8 value produced
     }
-    st.name = (bil ? "upsample_bilinear_i32:" : nd.up_i8 ? "upsample_nearest_i8:" : "upsample_nearest_i32:") + tname(net, nd.out);
+    st.name = (bil ? "upsample_bilinear_i32:" : nd.bytes_mode ? "upsample_nearest_i8:" : "upsample_nearest_i32:") + tname(net, nd.out);
     return F8_OK;
 }
 
 // slice / channel shuffle; a shuffle fused with its concat (Node::cm_cat) reads the concat's operands
 static int emit_chanmap(f8_net* net, int i, Step& st, std::vector<int>* extra) {
-    auto& T = net->tensors;
     const Node& nd = net->nodes[i];
-    const Tensor& s = T[nd.a]; Tensor& o = T[nd.out];
+    const Tensor& o = net->tensors[nd.out];
     const bool fused = nd.cm_cat >= 0;
     st.kind = S_CHANMAP;
-    st.cat_t = fused ? net->nodes[nd.cm_cat].srcs : std::vector<int>{nd.a};
-    if (o.forms.empty()) add_form(o, FORM_I32, 0, 0);
-    select_outputs(net, nd.out, &st.out, extra);
+    select_outputs_or_i32(net, nd.out, &st.out, extra);
+    const std::vector<int> srcs = fused ? net->nodes[nd.cm_cat].srcs : std::vector<int>{nd.a};
+    if (const int rc = select_sources(net, st, srcs, net->tensors[nd.a].fl, nd.bytes_mode, "slice / shuffle")) return rc;
     const double px = (double)o.H * o.W;
-    if (nd.cm_i8) {                                       // (pass 2: one or two int8 forms and no other)
-        for (int k = 0; k < 2; ++k) {
-            if (st.out.f8[k] < 0) continue;
-            const Form& F = o.forms[st.out.f8[k]];
-            for (int x : st.cat_t) {
-                const int f = find_form(T[x], FORM_I8, F.n - (s.fl - T[x].fl), F.sgn);      // (stand-alone: x is the source, the shift is 0)
-                if (f < 0) return fail(F8_ERR_STATE, "f8_net_finalize: planner bug: slice / shuffle source t%d lacks the output's int8 form", x);
-                st.cat_f[k].push_back(f);
-            }
-        }
+    if (nd.bytes_mode) {
         st.bytes_per_img = 2.0 * px * o.C * out_forms8(st);      // every real byte read once and written once, per form
     } else {
-        st.cat_f[0].push_back(find_form(s, FORM_I32, 0, 0));
         st.bytes_per_img = px * o.C * 4 + out_bytes(st, o, px);
         st.valu_per_img = px * o.C * 3 * out_forms8(st);         // 3 per int8 value produced
     }
     char tok[48];
-    if (nd.kind == N_SLICE) snprintf(tok, sizeof tok, "slice_%s:", nd.cm_i8 ? "i8" : "i32");
-    else snprintf(tok, sizeof tok, "%sshuffle%d_%s:", fused ? "concat+" : "", nd.cm_groups, nd.cm_i8 ? "i8" : "i32");
+    if (nd.kind == N_SLICE) snprintf(tok, sizeof tok, "slice_%s:", nd.bytes_mode ? "i8" : "i32");
+    else snprintf(tok, sizeof tok, "%sshuffle%d_%s:", fused ? "concat+" : "", nd.cm_groups, nd.bytes_mode ? "i8" : "i32");
     st.name = tok + tname(net, nd.out);
     return F8_OK;
 }
+
 
 static int emit_sumpool(f8_net* net, int i, Step& st, std::vector<int>* extra) {
     auto& T = net->tensors;
@@ -2855,8 +2839,7 @@ static int emit_sumpool(f8_net* net, int i, Step& st, std::vector<int>* extra) {
     const Tensor& s = T[nd.a]; Tensor& o = T[nd.out];
     st.kind = S_SUMPOOL;
     st.src_t = nd.a; st.src_f = find_form(s, FORM_I32, 0, 0);
-    if (o.forms.empty()) add_form(o, FORM_I32, 0, 0);
-    select_outputs(net, nd.out, &st.out, extra);
+    select_outputs_or_i32(net, nd.out, &st.out, extra);
     const double opx = (double)o.H * o.W;
     st.bytes_per_img = (double)s.H * s.W * s.Cs * 4 + out_bytes(st, o, opx);
     st.valu_per_img = opx * o.C * (nd.sum_k * nd.sum_k - 1 + 3 * out_forms8(st));      // kernel^2 - 1 adds per value; 3 per int8 value produced
@@ -3520,7 +3503,7 @@ static int bind_step(f8_net* net, Step& st) {
                 a.C[i] = x.C; a.Cs_src[i] = x.Cs; a.off[i] = off; a.shl[i] = oT.fl - x.fl;
                 off += x.C;
             }
-            snprintf(kb, sizeof kb, "%s", concat_kernel_name(st.inst = concat_inst(a, nd.concat_i8)));
+            snprintf(kb, sizeof kb, "%s", concat_kernel_name(st.inst = concat_inst(a, nd.bytes_mode)));
             out_formats(a.q); st.args = a; break;
         }
         case S_UPSAMPLE: {
@@ -3534,7 +3517,7 @@ static int bind_step(f8_net* net, Step& st) {
             make_magic((uint32_t)a.sw, &a.mSw, &a.s1Sw, &a.s2Sw);
             make_magic((uint32_t)a.Ws, &a.mWs, &a.s1Ws, &a.s2Ws);
             make_magic((uint32_t)(a.Cs >> 4), &a.mVpp, &a.s1Vpp, &a.s2Vpp);
-            snprintf(kb, sizeof kb, "%s", upsample_kernel_name(st.inst = upsample_inst(nd.up_mode == F8_UP_BILINEAR, nd.up_i8)));
+            snprintf(kb, sizeof kb, "%s", upsample_kernel_name(st.inst = upsample_inst(nd.up_mode == F8_UP_BILINEAR, nd.bytes_mode)));
             out_formats(a.q); st.args = a; break;
         }
         case S_CHANMAP: {
@@ -3548,7 +3531,7 @@ static int bind_step(f8_net* net, Step& st) {
                 a.off[i] = nd.kind == N_SLICE ? nd.cm_first : fused ? 0 : i * a.Cg;
             }
             make_magic((uint32_t)std::max(a.groups, 1), &a.mG, &a.s1G, &a.s2G);
-            snprintf(kb, sizeof kb, "%s", chanmap_kernel_name(st.inst = chanmap_inst(a, nd.cm_i8)));
+            snprintf(kb, sizeof kb, "%s", chanmap_kernel_name(st.inst = chanmap_inst(a, nd.bytes_mode)));
             out_formats(a.q); st.args = a; break;
         }
         case S_SUMPOOL: {
@@ -3824,6 +3807,21 @@ static int run_step(const f8_net* net, const RunIO& io, const Step& st, int n0, 
         if (st.res_t >= 0) a.xr = (const int32_t*)fp(T[st.res_t].forms[st.res_f]);
         fill_out(&a.out32, a.q);
     };
+    // what a run adds to the arguments of a launch that reads one form of one tensor: the source, the batch, the output forms.  Returns the source's form.
+    auto src_io = [&](auto& a, int32_t** out32) -> const Form& {
+        const Form& sF = T[st.src_t].forms[st.src_f];
+        a.x = (decltype(a.x))fp(sF); a.N = N;
+        fill_out(out32, a.q);
+        return sF;
+    };
+    // the source pointers of a gather step (Step::cat_t / cat_f): slot(k, i) = entry i of the launch's table for output form k, `entries` of them — source i,
+    // or, where the step has a single source (upsample; a stand-alone slice / shuffle, whose table has one entry per group), that source for every entry
+    auto gather_sources = [&](int entries, auto&& slot) {
+        const bool one = st.cat_t.size() == 1;
+        for (int k = 0; k < 2; ++k)
+            if (!st.cat_f[k].empty())
+                for (int i = 0; i < entries; ++i) { const size_t j = one ? 0 : (size_t)i; slot(k, i) = fp(T[st.cat_t[j]].forms[st.cat_f[k][j]]); }
+    };
     char* const chain = net->d_chain ? net->d_chain + (size_t)part * net->chain_stride : nullptr;
     const uint32_t* chain_err = chain ? (const uint32_t*)chain + kChainErrWord : nullptr;
     auto chain_scratch = [&](ChainSync& cs) {
@@ -3930,43 +3928,18 @@ static int run_step(const f8_net* net, const RunIO& io, const Step& st, int n0, 
         case S_IR: { IRArgs a = std::get<IRArgs>(st.args); ir_io(a); e = launch_fused_ir(a, T[st.src_t].Cs, nd.coutP, st.inst, s); break; }
         case S_IRK: { IRKArgs a = std::get<IRKArgs>(st.args); ir_io(a); e = launch_fused_irk(a, st.inst, s); break; }
         case S_IRCHAIN: { IRChainArgs a = std::get<IRChainArgs>(st.args); ir_io(a); e = launch_irchain(a, st.inst, s); break; }
-        case S_DWS: {
-            DwsArgs a = std::get<DwsArgs>(st.args);
-            a.x = (const int8_t*)fp(T[st.src_t].forms[st.src_f]); a.N = N;
-            { int32_t* none = nullptr; fill_out(&none, a.q); }
-            e = launch_dws(a, st.inst, s);
-            break;
-        }
-        case S_DWS7: {
-            Dws7Args a = std::get<Dws7Args>(st.args);
-            a.x = (const int8_t*)fp(T[st.src_t].forms[st.src_f]); a.N = N;
-            fill_out(&a.out32, a.q);
-            e = launch_dws7(a, st.inst, net->num_cu, s);
-            break;
-        }
+        case S_DWS: { DwsArgs a = std::get<DwsArgs>(st.args); int32_t* none = nullptr; src_io(a, &none); e = launch_dws(a, st.inst, s); break; }
+        case S_DWS7: { Dws7Args a = std::get<Dws7Args>(st.args); src_io(a, &a.out32); e = launch_dws7(a, st.inst, net->num_cu, s); break; }
         case S_DW: {
-            DwArgs a = std::get<DwArgs>(st.args);
-            a.x = (const int8_t*)fp(T[st.src_t].forms[st.src_f]); a.N = N;
-            fill_out(&a.out32, a.q);
+            DwArgs a = std::get<DwArgs>(st.args); src_io(a, &a.out32);
             e = (a.k == 3 && a.pad == 1 && a.dil == 1) ? launch_dwconv(a, st.inst, s) : launch_dwk(a, st.inst, s);      // (general depthwise: f8_dwk.hip)
             break;
         }
-        case S_GCONV: {
-            const Form& sF = T[st.src_t].forms[st.src_f];
-            GConvArgs a = std::get<GConvArgs>(st.args);
-            a.x = (const int8_t*)fp(sF); a.x_bytes = (uint32_t)(sF.bytes_per_img * N); a.N = N;
-            fill_out(&a.out32, a.q);
-            e = launch_gconv(a, s);
-            break;
-        }
-        case S_DECONV: {
-            const Form& sF = T[st.src_t].forms[st.src_f];
-            DeconvArgs a = std::get<DeconvArgs>(st.args);
-            a.x = (const int8_t*)fp(sF); a.x_bytes = (uint32_t)(sF.bytes_per_img * N); a.N = N;
-            fill_out(&a.out32, a.q);
-            e = launch_deconv(a, st.inst, s);
-            break;
-        }
+        case S_GCONV: { GConvArgs a = std::get<GConvArgs>(st.args); a.x_bytes = (uint32_t)(src_io(a, &a.out32).bytes_per_img * N); e = launch_gconv(a, s); break; }
+        case S_DECONV: { DeconvArgs a = std::get<DeconvArgs>(st.args); a.x_bytes = (uint32_t)(src_io(a, &a.out32).bytes_per_img * N); e = launch_deconv(a, st.inst, s); break; }
+        case S_SUMPOOL: { SumPoolArgs a = std::get<SumPoolArgs>(st.args); src_io(a, &a.out32); e = launch_sumpool(a, st.inst, s); break; }
+        case S_MAXPOOL: { PoolArgs a = std::get<PoolArgs>(st.args); src_io(a, &a.out32); e = launch_maxpool(a, st.inst, s); break; }
+        case S_AVGPOOL: { AvgArgs a = std::get<AvgArgs>(st.args); src_io(a, &a.out32); e = launch_avgpool(a, s); break; }
         case S_ADD: case S_REQUANT: {
             const Tensor& sT = T[st.src_t];
             AddArgs a = std::get<AddArgs>(st.args);
@@ -3979,18 +3952,15 @@ static int run_step(const f8_net* net, const RunIO& io, const Step& st, int n0, 
         }
         case S_CONCAT: {
             ConcatArgs a = std::get<ConcatArgs>(st.args);
-            for (int k = 0; k < 2; ++k)
-                for (size_t j = 0; j < st.cat_f[k].size(); ++j) a.src[k][j] = fp(T[st.cat_t[j]].forms[st.cat_f[k][j]]);
-            const Tensor& o = T[st.out.t];
-            a.M = N * o.H * o.W;
+            gather_sources(a.K, [&](int k, int i) -> const void*& { return a.src[k][i]; });
+            a.M = N * T[st.out.t].H * T[st.out.t].W;
             fill_out(&a.out32, a.q);
             e = launch_concat(a, st.inst, s);
             break;
         }
         case S_UPSAMPLE: {
             UpsampleArgs a = std::get<UpsampleArgs>(st.args);
-            for (int k = 0; k < 2; ++k)
-                if (!st.cat_f[k].empty()) a.src[k] = fp(T[st.cat_t[0]].forms[st.cat_f[k][0]]);
+            gather_sources(1, [&](int k, int) -> const void*& { return a.src[k]; });
             a.N = N;
             fill_out(&a.out32, a.q);
             e = launch_upsample(a, st.inst, s);
@@ -3998,35 +3968,10 @@ static int run_step(const f8_net* net, const RunIO& io, const Step& st, int n0, 
         }
         case S_CHANMAP: {
             ChanMapArgs a = std::get<ChanMapArgs>(st.args);
-            const bool one = st.cat_t.size() == 1;                   // stand-alone: every entry is the one source
-            for (int k = 0; k < 2; ++k)
-                if (!st.cat_f[k].empty())
-                    for (int i = 0; i < a.K; ++i) { const size_t j = one ? 0 : (size_t)i; a.src[k][i] = fp(T[st.cat_t[j]].forms[st.cat_f[k][j]]); }
-            const Tensor& o = T[st.out.t];
-            a.M = N * o.H * o.W;
+            gather_sources(a.K, [&](int k, int i) -> const void*& { return a.src[k][i]; });
+            a.M = N * T[st.out.t].H * T[st.out.t].W;
             fill_out(&a.out32, a.q);
             e = launch_chanmap(a, st.inst, s);
-            break;
-        }
-        case S_SUMPOOL: {
-            SumPoolArgs a = std::get<SumPoolArgs>(st.args);
-            a.x = (const int32_t*)fp(T[st.src_t].forms[st.src_f]); a.N = N;
-            fill_out(&a.out32, a.q);
-            e = launch_sumpool(a, st.inst, s);
-            break;
-        }
-        case S_MAXPOOL: {
-            PoolArgs a = std::get<PoolArgs>(st.args);
-            a.x = fp(T[st.src_t].forms[st.src_f]); a.N = N;
-            fill_out(&a.out32, a.q);
-            e = launch_maxpool(a, st.inst, s);
-            break;
-        }
-        case S_AVGPOOL: {
-            AvgArgs a = std::get<AvgArgs>(st.args);
-            a.x = (const int32_t*)fp(T[st.src_t].forms[st.src_f]); a.N = N;
-            fill_out(&a.out32, a.q);
-            e = launch_avgpool(a, s);
             break;
         }
         case S_OUTPUT: {

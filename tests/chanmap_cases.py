@@ -20,8 +20,10 @@ import functools
 import numpy as np
 
 import concat_cases as cc
+import graph_cases
 from concat_cases import FUSE_ALL, X_FL, producer, readers  # noqa: F401  (the tests take FUSE_ALL from here)
 from f8net_amd import synth
+from f8net_amd.onnx_import import IntOp
 from ir_cases import _b, _w
 from oracle import oracle
 
@@ -285,12 +287,7 @@ def plan(name, x, max_batch=None, **opts):
 
 def lines(net):
     """[(launch index, plan token, kernel symbol)] of the handle's slice, shuffle and concat launches, in launch order."""
-    out = []
-    for i in range(net.num_launches):
-        tok = net.launch_info(i, 1)[0].split(':')[0] + ':'
-        if tok.startswith(('slice_', 'shuffle', 'concat')):
-            out.append((i, tok, net.launch_kernel(i)))
-    return out
+    return graph_cases.launch_lines(net, ('slice_', 'shuffle', 'concat'))
 
 
 def expected(name, **opts):
@@ -352,49 +349,22 @@ def stage_input(n=None):
     return synth.rand_uniform_int(5, 'cmstage', (n or STAGE['N'], STAGE['cin'], STAGE['H'], STAGE['W']), 0, 255).astype(np.int32)
 
 
+class Recorder(graph_cases.Recorder, _Graph):
+    def slice(self, t, start, stop, label=None):
+        return self._put(super().slice(t, start, stop), IntOp('slice', src=self.ids[t], first=start, channels=stop - start))
+
+    def channel_shuffle(self, t, groups, label=None):
+        return self._put(super().channel_shuffle(t, groups), IntOp('shuffle', src=self.ids[t], groups=groups))
+
+    def avgpool_sum(self, t, shift=oracle.AVGPOOL_SHIFT):
+        return self._put(super().avgpool_sum(t, shift), IntOp('avgpool', src=self.ids[t]))
+
+    def linear(self, t, w, b, *, weight_fl, input_fl, input_signed, label=None):
+        o = super().linear(t, w, b, weight_fl=weight_fl, input_fl=input_fl, input_signed=input_signed)
+        return self._put(o, IntOp('linear', src=self.ids[t], weight=np.asarray(w, np.int32), bias=np.asarray(b, np.int32),
+                                  shift=self.v[t][1] - input_fl, signed=input_signed, key='fc'))
+
+
 def stage_int_graph():
     """The stage as an IntGraph, op for op what shufflenet_stage records.  Returns (IntGraph, reference graph, output id)."""
-    from f8net_amd.onnx_import import IntGraph, IntOp
-    ig = IntGraph(input_signed=False)
-    ig.ops.append(IntOp('input', shape=(STAGE['cin'], STAGE['H'], STAGE['W'])))
-
-    class _Rec(_Graph):
-        def __init__(self, x, fl):
-            super().__init__(x, fl, record=False)
-            self.ids = {0: 0}
-
-        def _note(self, o, op):
-            ig.ops.append(op)
-            self.ids[o] = len(ig.ops) - 1
-            return o
-
-        def conv(self, t, w, b, *, stride=1, pad, groups, weight_fl, input_fl, input_signed, relu, label=None, quant_input=True, dilation=1, w_eval=None):
-            o = super().conv(t, w, b, stride=stride, pad=pad, groups=groups, weight_fl=weight_fl, input_fl=input_fl, input_signed=input_signed, relu=relu,
-                             quant_input=quant_input, dilation=dilation)
-            return self._note(o, IntOp('conv', src=self.ids[t], weight=np.asarray(w, np.int32), bias=np.asarray(b, np.int32), stride=stride, pad=pad,
-                                       groups=groups, kernel=w.shape[2], shift=(self.v[t][1] - input_fl) if quant_input else None, signed=input_signed,
-                                       relu=relu, key=f'layer{len(ig.ops)}', dilation=dilation))
-
-        def concat(self, ts, label=None):
-            o = super().concat(ts)
-            return self._note(o, IntOp('concat', src=self.ids[ts[0]], srcs=[self.ids[t] for t in ts], shifts=[self.v[o][1] - self.v[t][1] for t in ts]))
-
-        def slice(self, t, start, stop, label=None):
-            return self._note(super().slice(t, start, stop), IntOp('slice', src=self.ids[t], first=start, channels=stop - start))
-
-        def channel_shuffle(self, t, groups, label=None):
-            return self._note(super().channel_shuffle(t, groups), IntOp('shuffle', src=self.ids[t], groups=groups))
-
-        def avgpool_sum(self, t, shift=oracle.AVGPOOL_SHIFT):
-            return self._note(super().avgpool_sum(t, shift), IntOp('avgpool', src=self.ids[t]))
-
-        def linear(self, t, w, b, *, weight_fl, input_fl, input_signed, label=None):
-            o = super().linear(t, w, b, weight_fl=weight_fl, input_fl=input_fl, input_signed=input_signed)
-            return self._note(o, IntOp('linear', src=self.ids[t], weight=np.asarray(w, np.int32), bias=np.asarray(b, np.int32),
-                                       shift=self.v[t][1] - input_fl, signed=input_signed, key='fc'))
-
-    g = _Rec(stage_input(), STAGE['x_fl'])
-    out, _ = shufflenet_stage(g, 0)
-    ig.output = g.ids[out]
-    ig.output_float = False
-    return ig, g, out
+    return graph_cases.record_int_graph(Recorder, stage_input(), STAGE['x_fl'], lambda g, x0: shufflenet_stage(g, x0)[0])

@@ -4,8 +4,8 @@ tests/test_gpu_concat.py (every case on both legs, bit for bit on the device).  
 
 The reference.  `concat_align(xs, fls)`: the result's fraclen is the largest operand fraclen and operand i contributes what the residual join's
 alignment makes of it next to a zero partner, `oracle.add_align(zeros, x_i, out_fl, fl_i)` — shift left with the int32 wrap, clamp to
-+-(2^31 - 1) — so nothing of that arithmetic is restated here; then `np.concatenate` along C.  `oracle/` stays as it is: `graph_forward` below walks
-an imported ONNX graph, handles `concat` itself and hands every other op kind to the oracle's op-level functions.
++-(2^31 - 1) — so nothing of that arithmetic is restated here; then `np.concatenate` along C.  `oracle/` stays as it is: graph_cases.graph_forward
+walks an imported ONNX graph, handles `concat` with `concat_align` and hands every other op kind to the oracle's op-level functions.
 
 Unless a builder says otherwise a case is  input (8 channels, 0 .. 255, fraclen 8) -> K 1x1 producer convs that read it as it is, couts C_i, weight
 fraclens chosen to give the stated output fraclens -> concat -> readers: one 32-output 1x1 conv per (input_fl, signed), summed (as dil_cases).
@@ -17,8 +17,10 @@ import functools
 import numpy as np
 
 import dil_cases
+import graph_cases
 from dil_cases import FUSE_ALL  # noqa: F401  (the tests take it from here)
 from f8net_amd import synth
+from graph_cases import graph_forward, launch_lines  # noqa: F401  (the walker of an imported graph: the tests take it from here)
 from ir_cases import _b, _w
 from oracle import oracle
 
@@ -293,90 +295,18 @@ def plan(name, x, max_batch=None, **opts):
 
 def concat_lines(net):
     """[(launch index, plan token 'concat_i8:' / 'concat_i32:', kernel symbol)] of the handle's concat launches, in launch order."""
-    out = []
-    for i in range(net.num_launches):
-        tok = net.launch_info(i, 1)[0].split(':')[0] + ':'
-        if tok.startswith('concat_'):
-            out.append((i, tok, net.launch_kernel(i)))
-    return out
+    return launch_lines(net, 'concat_')
 
 
 def symbol(mode, aligned):
     return 'f8::concat_i32_kernel' if mode == I32 else f'f8::concat_i8_kernel<{"true" if aligned else "false"}>'
 
 
-# ---- the walker of an imported graph (oracle.graph_forward knows no concat)
-def graph_forward(ig, x, input_fraclen=None):
-    V, layer = ig.solve_fraclens(input_fraclen)
-    t = {}
-    for i, o in enumerate(ig.ops):
-        if o.kind == 'input':
-            t[i] = np.ascontiguousarray(x, dtype=np.int32)
-        elif o.kind == 'conv':
-            s = t[o.src]
-            if o.shift is not None:
-                s = oracle.requant(s, layer[i][0], V[o.src], o.signed)
-            y = oracle.conv2d(s, dil_cases.stuffed(o.weight, o.dilation), o.bias, o.stride, o.pad, o.groups)
-            t[i] = oracle.relu(y) if o.relu else y
-        elif o.kind == 'add':
-            y, fl = oracle.add_align(t[o.src], t[o.src2], V[o.src], V[o.src2])
-            assert fl == V[i]
-            t[i] = oracle.relu(y) if o.relu else y
-        elif o.kind == 'maxpool':
-            t[i] = oracle.maxpool(t[o.src], o.kernel, o.stride, o.pad)
-        elif o.kind == 'concat':
-            t[i], fl = concat_align([t[s] for s in o.srcs], [V[s] for s in o.srcs])
-            assert fl == V[i] and [V[i] - V[s] for s in o.srcs] == list(o.shifts)
-        else:
-            raise ValueError(o.kind)
-    return t[ig.output]
+class Recorder(graph_cases.Recorder, _Graph):
+    pass
 
 
 def int_graph(name):
     """The case as an IntGraph, op for op what build_graph records (plain-conv / add / concat / maxpool cases whose first output is the only one)."""
-    from f8net_amd.onnx_import import IntGraph, IntOp
     c = CASES[name]
-    ig = IntGraph(input_signed=False)
-    ig.ops.append(IntOp('input', shape=(c['cin'], c['H'], c['W'])))
-
-    class _Rec(_Graph):
-        def __init__(self, x, fl):
-            super().__init__(x, fl, record=False)
-            self.ids = {0: 0}
-
-        def conv(self, t, w, b, *, stride=1, pad, groups, weight_fl, input_fl, input_signed, relu, label=None, quant_input=True, dilation=1, w_eval=None):
-            o = super().conv(t, w, b, stride=stride, pad=pad, groups=groups, weight_fl=weight_fl, input_fl=input_fl, input_signed=input_signed, relu=relu,
-                             quant_input=quant_input, dilation=dilation)
-            ig.ops.append(IntOp('conv', src=self.ids[t], weight=np.asarray(w, np.int32), bias=np.zeros(w.shape[0], np.int32) if b is None else np.asarray(b, np.int32),
-                                stride=stride, pad=pad, groups=groups, kernel=w.shape[2], shift=(self.v[t][1] - input_fl) if quant_input else None,
-                                signed=input_signed, relu=relu, key=f'layer{len(ig.ops)}', dilation=dilation))
-            self.ids[o] = len(ig.ops) - 1
-            return o
-
-        def add(self, a, b, relu=False):
-            o = super().add(a, b, relu=relu)
-            fa, fb = self.v[a][1], self.v[b][1]
-            s, s2 = (a, b) if fa <= fb else (b, a)                    # src is the operand that shifts
-            ig.ops.append(IntOp('add', src=self.ids[s], src2=self.ids[s2], shift=abs(fa - fb), relu=relu, swap=s == b))
-            self.ids[o] = len(ig.ops) - 1
-            return o
-
-        def maxpool(self, t, k, stride, pad):
-            o = super().maxpool(t, k, stride, pad)
-            ig.ops.append(IntOp('maxpool', src=self.ids[t], kernel=k, stride=stride, pad=pad))
-            self.ids[o] = len(ig.ops) - 1
-            return o
-
-        def concat(self, ts, label=None):
-            o = super().concat(ts)
-            fl = self.v[o][1]
-            ig.ops.append(IntOp('concat', src=self.ids[ts[0]], srcs=[self.ids[t] for t in ts], shifts=[fl - self.v[t][1] for t in ts]))
-            self.ids[o] = len(ig.ops) - 1
-            return o
-
-    x = make_input(name)
-    g = _Rec(x, c['x_fl'])
-    outs, _ = c['build'](g, 0, c)
-    ig.output = g.ids[outs[0]]
-    ig.output_float = False
-    return ig, g, outs[0]
+    return graph_cases.record_int_graph(Recorder, make_input(name), c['x_fl'], lambda g, x0: c['build'](g, x0, c)[0][0])

@@ -19,8 +19,10 @@ import functools
 import numpy as np
 
 import concat_cases as cc
+import graph_cases
 from concat_cases import FUSE_ALL, X_FL, producer, readers  # noqa: F401  (the tests take them from here)
 from f8net_amd import synth
+from graph_cases import graph_forward, launch_lines  # noqa: F401  (the walker of an imported graph: the tests take it from here)
 from f8net_amd.onnx_import import upsample_fl_gain
 from oracle import oracle
 
@@ -231,91 +233,14 @@ def plan(name, x, max_batch=None, **opts):
 
 def upsample_lines(net):
     """[(launch index, plan token, kernel symbol)] of the handle's upsample launches, in launch order."""
-    out = []
-    for i in range(net.num_launches):
-        tok = net.launch_info(i, 1)[0].split(':')[0] + ':'
-        if tok.startswith('upsample_'):
-            out.append((i, tok, net.launch_kernel(i)))
-    return out
+    return launch_lines(net, 'upsample_')
 
 
-# ---- the walker of an imported graph (oracle.graph_forward knows neither concat nor upsample)
-def graph_forward(ig, x, input_fraclen=None):
-    import dil_cases
-    V, layer = ig.solve_fraclens(input_fraclen)
-    t = {}
-    for i, o in enumerate(ig.ops):
-        if o.kind == 'input':
-            t[i] = np.ascontiguousarray(x, dtype=np.int32)
-        elif o.kind == 'conv':
-            s = t[o.src]
-            if o.shift is not None:
-                s = oracle.requant(s, layer[i][0], V[o.src], o.signed)
-            y = oracle.conv2d(s, dil_cases.stuffed(o.weight, o.dilation), o.bias, o.stride, o.pad, o.groups)
-            t[i] = oracle.relu(y) if o.relu else y
-        elif o.kind == 'add':
-            y, fl = oracle.add_align(t[o.src], t[o.src2], V[o.src], V[o.src2])
-            assert fl == V[i]
-            t[i] = oracle.relu(y) if o.relu else y
-        elif o.kind == 'maxpool':
-            t[i] = oracle.maxpool(t[o.src], o.kernel, o.stride, o.pad)
-        elif o.kind == 'concat':
-            t[i], fl = cc.concat_align([t[s] for s in o.srcs], [V[s] for s in o.srcs])
-            assert fl == V[i]
-        elif o.kind == 'upsample':
-            t[i], fl = upsample_ref(t[o.src], V[o.src], tuple(o.scale), o.mode)
-            assert fl == V[i]
-        else:
-            raise ValueError(o.kind)
-    return t[ig.output]
+class Recorder(graph_cases.Recorder, _Graph):
+    pass
 
 
 def int_graph(name):
     """The case as an IntGraph, op for op what build_graph records (cases whose first output is the only one)."""
-    from f8net_amd.onnx_import import IntGraph, IntOp
     c = CASES[name]
-    ig = IntGraph(input_signed=False)
-    ig.ops.append(IntOp('input', shape=(c['cin'],) + input_hw(c)))
-
-    class _Rec(_Graph):
-        def __init__(self, x, fl):
-            super().__init__(x, fl, record=False)
-            self.ids = {0: 0}
-
-        def _put(self, o, op):
-            ig.ops.append(op)
-            self.ids[o] = len(ig.ops) - 1
-            return o
-
-        def conv(self, t, w, b, *, stride=1, pad, groups, weight_fl, input_fl, input_signed, relu, label=None, quant_input=True, dilation=1, w_eval=None):
-            o = super().conv(t, w, b, stride=stride, pad=pad, groups=groups, weight_fl=weight_fl, input_fl=input_fl, input_signed=input_signed, relu=relu,
-                             quant_input=quant_input, dilation=dilation)
-            return self._put(o, IntOp('conv', src=self.ids[t], weight=np.asarray(w, np.int32),
-                                      bias=np.zeros(w.shape[0], np.int32) if b is None else np.asarray(b, np.int32), stride=stride, pad=pad, groups=groups,
-                                      kernel=w.shape[2], shift=(self.v[t][1] - input_fl) if quant_input else None, signed=input_signed, relu=relu,
-                                      key=f'layer{len(ig.ops)}', dilation=dilation))
-
-        def add(self, a, b, relu=False):
-            o = super().add(a, b, relu=relu)
-            fa, fb = self.v[a][1], self.v[b][1]
-            s, s2 = (a, b) if fa <= fb else (b, a)                    # src is the operand that shifts
-            return self._put(o, IntOp('add', src=self.ids[s], src2=self.ids[s2], shift=abs(fa - fb), relu=relu, swap=s == b))
-
-        def maxpool(self, t, k, stride, pad):
-            return self._put(super().maxpool(t, k, stride, pad), IntOp('maxpool', src=self.ids[t], kernel=k, stride=stride, pad=pad))
-
-        def concat(self, ts, label=None):
-            o = super().concat(ts)
-            fl = self.v[o][1]
-            return self._put(o, IntOp('concat', src=self.ids[ts[0]], srcs=[self.ids[t] for t in ts], shifts=[fl - self.v[t][1] for t in ts]))
-
-        def upsample(self, t, scale, mode='nearest', label=None):
-            sc = (scale, scale) if isinstance(scale, int) else tuple(scale)
-            return self._put(super().upsample(t, scale, mode), IntOp('upsample', src=self.ids[t], mode=mode, scale=sc))
-
-    x = make_input(name)
-    g = _Rec(x, X_FL)
-    outs, _ = c['build'](g, 0, c)
-    ig.output = g.ids[outs[0]]
-    ig.output_float = False
-    return ig, g, outs[0]
+    return graph_cases.record_int_graph(Recorder, make_input(name), X_FL, lambda g, x0: c['build'](g, x0, c)[0][0])

@@ -10,6 +10,10 @@ on the library before and after it and comparing the two outputs with `diff` (F8
 Per configuration, through the public C ABI only: describe, arena_bytes, weight_bytes, num_launches, and for every launch
 launch_info, launch_valu, launch_kernel, launch_grid (num_cu 0, 256, 64) and step_launches at N = 1 and N = max batch; num_parts.
 A finalize that fails prints its status and message instead.  `--full` prints every query instead of the digest (to see WHAT moved).
+
+`--cases` digests the op cases of tests/*_cases.py instead (concat, upsample, slice / shuffle, windowed pool, transposed conv: ops no shipped net
+has), each at its default options and on the other legs of the options that steer it.  tests/golden/plan_digest_cases.txt holds that output of the
+library before the gathers' planner code was folded; tests/test_plan_digest_cases.py compares.
 """
 import argparse
 import hashlib
@@ -115,13 +119,46 @@ def plan_lines(job):
     return lines
 
 
+# --cases: the op-case modules of tests/ (none of the shipped nets has a concat, upsample, slice, shuffle, windowed pool or transposed conv) and
+# the options that steer their plans; each module has make_input(name) and plan(name, x, max_batch=None, **opts)
+CASE_MODULES = {'concat_cases': ['concat_i8'], 'upsample_cases': ['upsample_i8', 'concat_i8'], 'chanmap_cases': ['chanmap_i8', 'fuse_shuffle', 'concat_i8'],
+                'avgpool_cases': ['sumpool_wide', 'upsample_i8', 'concat_i8'], 'deconv_cases': ['concat_i8']}
+
+
+def case_lines(full=False, only=''):
+    """One line per (module, case, option set): the default plan, then each steering option alone at its other values."""
+    import importlib
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tests'))
+    lines = []
+    for mod, keys in CASE_MODULES.items():
+        m = importlib.import_module(mod)
+        for name, c in m.CASES.items():
+            x = m.make_input(name, 1)                              # one image records the graph; the plan is made for the case's batch
+            dflt = m.plan(name, x, c['N'])[0].net
+            sets = [('default', {})] + [(f'{k}={v}', {k: v}) for k in keys for v in range(LATER[k][0], LATER[k][1] + 1) if v != dflt.get_option(k)]
+            for sname, opts in sets:
+                head = f'{mod}.{name} bs={c["N"]} [{sname}]'
+                if only and only not in head:
+                    continue
+                net = m.plan(name, x, c['N'], **opts)[0].net
+                q = queries(net, c['N'])
+                lines.append(f'{head} launches={net.num_launches} arena={net.arena_bytes} sha256={hashlib.sha256(chr(10).join(q).encode()).hexdigest()[:24]}')
+                if full:
+                    lines += ['    ' + l for l in '\n'.join(q).split('\n')]
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('--jobs', type=int, default=min(8, os.cpu_count() or 1))
     ap.add_argument('--arch', action='append', help='only these architectures')
     ap.add_argument('--only', default='', help='only the option sets whose name contains this')
     ap.add_argument('--full', action='store_true', help='print every query under its configuration')
+    ap.add_argument('--cases', action='store_true', help="the op cases of tests/*_cases.py instead of the shipped nets (--only: part of a line's head)")
     args = ap.parse_args()
+    if args.cases:
+        print('\n'.join(case_lines(args.full, args.only)))
+        return
     jobs = [(a, hw, bs, args.full, args.only) for a, hw in [(a, 224) for a in ARCHS] + EXTRA_SIZES for bs in BATCHES
             if not args.arch or a in args.arch]
     with ProcessPoolExecutor(args.jobs) as ex:
