@@ -225,7 +225,7 @@ bcchain_kernel(const BCChainArgs a) {
                 mfma_operands_read();
             }
             if (tid < 64) bias_lds[64 + tid] = B.bb[c * 64 + tid];
-            write_zeros(FAST ? 0x80808080u : B.xor1);
+            write_zeros(FAST ? 0x80808080u : B.r1.bias_xor);
             {   // mid0 of the group (NHWC in HBM) -> LDS in fragment order: fragment e = (pixel tile e / KK, K32 step e % KK), one gather per fragment
                 const __amdgpu_buffer_rsrc_t rm = __builtin_amdgcn_make_buffer_rsrc((void*)a.m0in, 0, (unsigned)(npix * C), 0x00020000);
 #pragma unroll
@@ -323,7 +323,7 @@ bcchain_kernel(const BCChainArgs a) {
             if (jt_ok) {
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
-                    const v4i o = quant_tile16<FAST>(res[i], BN.nq, FAST ? 0 : BN.loq, FAST ? 255 : BN.hiq, FAST ? 0x80808080u : BN.xorq);
+                    const v4i o = quant_tile16<FAST>(res[i], BN.rq.n, FAST ? 0 : BN.rq.lo, FAST ? 255 : BN.rq.hi, FAST ? 0x80808080u : BN.rq.bias_xor);
                     __builtin_amdgcn_raw_buffer_store_b128(o, rxc, l16, Cfg::OFF_X8 + (jt * KK + c * 2 + i) * 1024, 17);
                 }
             }
@@ -339,7 +339,7 @@ bcchain_kernel(const BCChainArgs a) {
             // ---- this block's biases -> LDS (the previous ones were last read before the barrier inside publish())
             if (tid < 64) bias_lds[tid] = B.ba[c * 64 + tid];
             else if (tid < 128) bias_lds[tid] = B.bb[c * 64 + tid - 64];
-            write_zeros(FAST ? 0x80808080u : B.xorq);
+            write_zeros(FAST ? 0x80808080u : B.rq.bias_xor);
             wait_all();                                         // x8 of the whole cluster is in memory
 
             // =============================== PA: mid[64 c ..] = requant(relu(Wa . x8 + ba))
@@ -354,13 +354,13 @@ bcchain_kernel(const BCChainArgs a) {
                         if constexpr (!FAST)
 #pragma unroll
                             for (int r = 0; r < 16; ++r) y[i][r] = max(y[i][r], floor0);
-                        const v4i o = quant_tile16<FAST>(y[i], B.n1, FAST ? 0 : B.lo1, FAST ? 255 : B.hi1, FAST ? 0x80808080u : B.xor1);
+                        const v4i o = quant_tile16<FAST>(y[i], B.r1.n, FAST ? 0 : B.r1.lo, FAST ? 255 : B.r1.hi, FAST ? 0x80808080u : B.r1.bias_xor);
                         __builtin_amdgcn_raw_buffer_store_b128(o, rxc, l16, Cfg::OFF_MID + (jt * KK + c * 2 + i) * 1024, 17);
                     }
                 }
                 publish();
             }
-            write_zeros(FAST ? 0x80808080u : B.xor1);          // (the barrier inside publish() is behind every read of the K halves' exchange)
+            write_zeros(FAST ? 0x80808080u : B.r1.bias_xor);          // (the barrier inside publish() is behind every read of the K halves' exchange)
             wait_all();                                         // mid of the whole cluster is in memory
 
             // =============================== PB: stream' = clamp(((Wb . mid + bb) << acc_shl) + (stream << res_shl)) [ReLU]
@@ -392,11 +392,11 @@ size_t bcchain_xchg_bytes() { return kBCChainXchgBytes; }
 int bcchain_inst(const BCChainArgs& a, bool q8) {          // bchain_fast's rule; its float-converter choice (1) runs the integer instance here
     for (int k = 0; k < a.nblk; ++k) {
         const BChainBlk& B = a.blk[k];
-        if (!(B.relu_a && B.relu1 && B.n1 > 0 && B.n1 <= 30 && B.lo1 == 0)) return 0;
+        if (!(B.relu_a && B.relu1 && B.r1.u8_shr())) return 0;
         if (k == 0 && a.tail) continue;                               // opening block: its input arrives as int8, its join shifts either operand
-        if (!(B.nq > 0 && B.nq <= 30 && B.loq == 0 && B.res_shl == 0)) return 0;
+        if (!(B.rq.u8_shr() && B.res_shl == 0)) return 0;
     }
-    if (q8 && !(a.q[0].n > 0 && a.q[0].n <= 30 && a.q[0].lo == 0)) return 0;
+    if (q8 && !a.q[0].u8_shr()) return 0;
     return 2;
 }
 int bcchain_kernel_name(char* buf, size_t cap, int inst) { return snprintf(buf, cap, "f8::bcchain_kernel<%d>", inst != 0 ? 2 : 0); }

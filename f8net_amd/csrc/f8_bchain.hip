@@ -242,7 +242,7 @@ bchain_kernel(const BChainArgs a) {
         const int m_tile = (n * H + p0) * W;
         const BChainBlk& B0 = a.blk[0];
         auto fill_patchX = [&] {   // patchX <- biased zero (border; the interior is written before it is read)
-            const unsigned zq = FAST ? 0x80808080u : a.blk[DS && a.nblk > 1 ? 1 : 0].xorq;
+            const unsigned zq = FAST ? 0x80808080u : a.blk[DS && a.nblk > 1 ? 1 : 0].rq.bias_xor;
             const v4i zx = {(int)zq, (int)zq, (int)zq, (int)zq};
             for (int o = tid * 16; o < Cfg::PATCH_BYTES; o += NT * 16) *(v4i*)(patchX + o) = zx;
         };
@@ -266,7 +266,7 @@ bchain_kernel(const BChainArgs a) {
 #pragma unroll
             for (int j = 0; j < NPW; ++j) {
                 const int pix = bpix[j], pr = pix / W, pc = pix - pr * W;
-                const v4i o = quant_tile16<FAST>(res[j], B0.nq, FAST ? 0 : B0.loq, FAST ? 255 : B0.hiq, FAST ? 0x80808080u : B0.xorq);
+                const v4i o = quant_tile16<FAST>(res[j], B0.rq.n, FAST ? 0 : B0.rq.lo, FAST ? 255 : B0.rq.hi, FAST ? 0x80808080u : B0.rq.bias_xor);
                 if (pix < npx) *(v4i*)(patchX + ((pr + 1) * PW + pc + 1) * CS + ct * 32 + lh * 16) = o;
             }
             __syncthreads();
@@ -275,7 +275,7 @@ bchain_kernel(const BChainArgs a) {
             constexpr int CPI = Cfg::CIN / 16, RCHI = 2 * W * CPI, NPC = Cfg::PRI * RCHI, PER = (NPC + NT - 1) / NT;
             const int8_t* const xin = a.x8in + (size_t)n * (2 * H) * (2 * W) * Cfg::CIN;
             const int r0 = 2 * p0 - 1, nr = 2 * rows + 1;
-            const v4i zi = {(int)B0.xorq, (int)B0.xorq, (int)B0.xorq, (int)B0.xorq};
+            const v4i zi = {(int)B0.rq.bias_xor, (int)B0.rq.bias_xor, (int)B0.rq.bias_xor, (int)B0.rq.bias_xor};
             int t3 = tid; asm volatile("" : "+v"(t3));
             v4i v[PER];
 #pragma unroll
@@ -306,13 +306,13 @@ bchain_kernel(const BChainArgs a) {
             const BChainBlk& B = a.blk[b];
             const bool last = b + 1 == a.nblk;
             const BChainBlk& BN = a.blk[last ? b : b + 1];
-            const int n1 = B.n1, acc_shl = B.acc_shl, res_shl = B.res_shl;
-            const int lo1 = FAST ? 0 : B.lo1, hi1 = FAST ? 255 : B.hi1;
-            const unsigned xor1 = FAST ? 0x80808080u : B.xor1;
+            const int n1 = B.r1.n, acc_shl = B.acc_shl, res_shl = B.res_shl;
+            const int lo1 = FAST ? 0 : B.r1.lo, hi1 = FAST ? 255 : B.r1.hi;
+            const unsigned xor1 = FAST ? 0x80808080u : B.r1.bias_xor;
             const int relu_a = FAST ? 1 : B.relu_a, relu1 = FAST ? 1 : B.relu1;
-            const int nq = last ? a.q[0].n : BN.nq;
-            const int loq = FAST ? 0 : (last ? a.q[0].lo : BN.loq), hiq = FAST ? 255 : (last ? a.q[0].hi : BN.hiq);
-            const unsigned xorq = FAST ? 0x80808080u : (last ? a.q[0].bias_xor : BN.xorq);
+            const int nq = last ? a.q[0].n : BN.rq.n;
+            const int loq = FAST ? 0 : (last ? a.q[0].lo : BN.rq.lo), hiq = FAST ? 255 : (last ? a.q[0].hi : BN.rq.hi);
+            const unsigned xorq = FAST ? 0x80808080u : (last ? a.q[0].bias_xor : BN.rq.bias_xor);
             const int* const bl = bias_lds + b * 2 * C;
 
             {   // ============ first conv: mid = requant(relu(conv3x3(x8) + ba)) -> patchM interior
@@ -458,15 +458,15 @@ int bchain_fast(const BChainArgs& a, bool ds, bool q8) {
     bool f16 = true;
     for (int k = 0; k < a.nblk; ++k) {
         const BChainBlk& B = a.blk[k];
-        if (!(B.relu_a && B.relu1 && B.n1 > 0 && B.n1 <= 30 && B.lo1 == 0)) return 0;
-        f16 = f16 && B.n1 <= kRequantU8MaxShift;
+        if (!(B.relu_a && B.relu1 && B.r1.u8_shr())) return 0;
+        f16 = f16 && B.r1.u8_float();
         if (k == 0 && ds) continue;                          // opening block: its input arrives as int8, its join shifts either operand
-        if (!(B.nq > 0 && B.nq <= 30 && B.loq == 0 && B.res_shl == 0)) return 0;
-        f16 = f16 && B.nq <= kRequantU8MaxShift;
+        if (!(B.rq.u8_shr() && B.res_shl == 0)) return 0;
+        f16 = f16 && B.rq.u8_float();
     }
     if (q8) {
-        if (!(a.q[0].n > 0 && a.q[0].n <= 30 && a.q[0].lo == 0)) return 0;
-        f16 = f16 && a.q[0].n <= kRequantU8MaxShift;
+        if (!a.q[0].u8_shr()) return 0;
+        f16 = f16 && a.q[0].u8_float();
     }
     return (a.rq_int || !a.acc_ok || !a.stream_ok || !f16) ? 2 : 1;
 }

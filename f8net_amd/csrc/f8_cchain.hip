@@ -222,7 +222,7 @@ cchain_kernel(const ChainArgs a) {
             for (int j = 0; j < NPT; ++j) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) res[j][r] = max(res[j][r], floor1);
-                const v4i o = quant_tile16<F8_CC_QI(FAST, F8_CC_Q_TAIL)>(res[j], B1.nq, FAST ? 0 : B1.loq, FAST ? 255 : B1.hiq, FAST ? 0x80808080u : B1.xorq);
+                const v4i o = quant_tile16<F8_CC_QI(FAST, F8_CC_Q_TAIL)>(res[j], B1.rq.n, FAST ? 0 : B1.rq.lo, FAST ? 255 : B1.rq.hi, FAST ? 0x80808080u : B1.rq.bias_xor);
                 __builtin_amdgcn_raw_buffer_store_b128(o, rxc, l16, (j * NK1 + ct) * 1024, 17);
             }
             publish();
@@ -243,7 +243,7 @@ cchain_kernel(const ChainArgs a) {
             }
 #pragma unroll
             for (int j = 0; j < NPT; ++j) {
-                const v4i o = quant_tile16<FAST>(res[j], B0.nq, FAST ? 0 : B0.loq, FAST ? 255 : B0.hiq, FAST ? 0x80808080u : B0.xorq);
+                const v4i o = quant_tile16<FAST>(res[j], B0.rq.n, FAST ? 0 : B0.rq.lo, FAST ? 255 : B0.rq.hi, FAST ? 0x80808080u : B0.rq.bias_xor);
                 __builtin_amdgcn_raw_buffer_store_b128(o, rxc, l16, (j * NK1 + ct) * 1024, 17);
             }
             publish();
@@ -254,12 +254,12 @@ cchain_kernel(const ChainArgs a) {
             const ChainBlk& B = a.blk[b];
             const bool last = b + 1 == a.nblk;
             const ChainBlk& BN = a.blk[last ? b : b + 1];
-            const int n1 = B.n1, n2 = B.n2, acc_shl = B.acc_shl, res_shl = B.res_shl;
-            const int lo1 = FAST ? 0 : B.lo1, hi1 = FAST ? 255 : B.hi1, lo2 = FAST ? 0 : B.lo2, hi2 = FAST ? 255 : B.hi2;
-            const unsigned xor1 = FAST ? 0x80808080u : B.xor1, xor2 = FAST ? 0x80808080u : B.xor2;
+            const int n1 = B.r1.n, n2 = B.r2.n, acc_shl = B.acc_shl, res_shl = B.res_shl;
+            const int lo1 = FAST ? 0 : B.r1.lo, hi1 = FAST ? 255 : B.r1.hi, lo2 = FAST ? 0 : B.r2.lo, hi2 = FAST ? 255 : B.r2.hi;
+            const unsigned xor1 = FAST ? 0x80808080u : B.r1.bias_xor, xor2 = FAST ? 0x80808080u : B.r2.bias_xor;
             const int relu_a = FAST ? 1 : B.relu_a, relu_b = FAST ? 1 : B.relu_b, relu1 = FAST ? 1 : B.relu1;
-            const int nq = BN.nq, loq = FAST ? 0 : BN.loq, hiq = FAST ? 255 : BN.hiq;
-            const unsigned xorq = FAST ? 0x80808080u : BN.xorq;
+            const int nq = BN.rq.n, loq = FAST ? 0 : BN.rq.lo, hiq = FAST ? 255 : BN.rq.hi;
+            const unsigned xorq = FAST ? 0x80808080u : BN.rq.bias_xor;
 
             // ---- this block's biases -> LDS (read from P1's epilogue on; the previous block's were last read at the top of its P3)
             {

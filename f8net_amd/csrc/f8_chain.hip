@@ -384,7 +384,7 @@ chain_kernel(const ChainArgs a) {
             for (int pt = 0; pt < NPT; ++pt)
 #pragma unroll
                 for (int i = 0; i < CTW; ++i)
-                    *(v4i*)(x8 + xlane + pt * 32 * XS + (wave * CTW + i) * 32) = quant_tile16<FAST>(res[pt][i], B0.nq, FAST ? 0 : B0.loq, FAST ? 255 : B0.hiq, FAST ? 0x80808080u : B0.xorq);
+                    *(v4i*)(x8 + xlane + pt * 32 * XS + (wave * CTW + i) * 32) = quant_tile16<FAST>(res[pt][i], B0.rq.n, FAST ? 0 : B0.rq.lo, FAST ? 255 : B0.rq.hi, FAST ? 0x80808080u : B0.rq.bias_xor);
         } else {
             int bv0[NBI];
             if constexpr (BROT) bias_fetch(0, bv0);
@@ -420,16 +420,16 @@ chain_kernel(const ChainArgs a) {
                 const ChainBlk& BN = a.blk[last ? b : b + 1];
                 const int8_t* const pw0 = B.w0; const int8_t* const pw2 = B.w2; const int8_t* const pw4 = B.w4; const int8_t* const pwsc = B.wsc;
                 const int8_t* const pw0n = BN.w0;
-                const int n1 = B.n1, n2 = B.n2, acc_shl = B.acc_shl, res_shl = B.res_shl;
-                const int lo1 = FAST ? 0 : B.lo1, hi1 = FAST ? 255 : B.hi1, lo2 = FAST ? 0 : B.lo2, hi2 = FAST ? 255 : B.hi2;
+                const int n1 = B.r1.n, n2 = B.r2.n, acc_shl = B.acc_shl, res_shl = B.res_shl;
+                const int lo1 = FAST ? 0 : B.r1.lo, hi1 = FAST ? 255 : B.r1.hi, lo2 = FAST ? 0 : B.r2.lo, hi2 = FAST ? 255 : B.r2.hi;
                 // (FAST: the constant lives in a scalar register — as a 32-bit literal every v_xor_b32 is an 8-byte instruction, 3.6 instead of 2.3 cycles: ubench_bank)
                 const unsigned kx = FAST ? (unsigned)opaque((int)0x80808080u) : 0u;
-                const unsigned xor1 = FAST ? kx : B.xor1, xor2 = FAST ? kx : B.xor2;
+                const unsigned xor1 = FAST ? kx : B.r1.bias_xor, xor2 = FAST ? kx : B.r2.bias_xor;
                 const int relu_a = FAST ? 1 : B.relu_a, relu_b = FAST ? 1 : B.relu_b, relu1 = FAST ? 1 : B.relu1;
                 // format of the int8 copy of the block's output in LDS: the next block's body.0 input, or the first int8 form of the stage output
-                const int nq = last ? a.q[0].n : BN.nq;
-                const int loq = FAST ? 0 : (last ? a.q[0].lo : BN.loq), hiq = FAST ? 255 : (last ? a.q[0].hi : BN.hiq);
-                const unsigned xorq = FAST ? kx : (last ? a.q[0].bias_xor : BN.xorq);
+                const int nq = last ? a.q[0].n : BN.rq.n;
+                const int loq = FAST ? 0 : (last ? a.q[0].lo : BN.rq.lo), hiq = FAST ? 255 : (last ? a.q[0].hi : BN.rq.hi);
+                const unsigned xorq = FAST ? kx : (last ? a.q[0].bias_xor : BN.rq.bias_xor);
 
                 // this wave's P3 weights (WSTAT): requested when P2's K loop is over, so they travel during its epilogue
                 constexpr int K0 = DSB ? KS : 0, KT = KK + K0;  // opening block: the shortcut's K steps come first
@@ -1013,13 +1013,13 @@ int chain_fast(const ChainArgs& a, unsigned shortcut_blocks, bool q8) {
     bool f16 = true;
     for (int k = 0; k < a.nblk; ++k) {
         const ChainBlk& B = a.blk[k];
-        if (!(B.relu_a && B.relu_b && B.relu1 && B.n1 > 0 && B.n2 > 0 && B.nq > 0 && B.n1 <= 30 && B.n2 <= 30 && B.nq <= 30 && B.lo1 == 0 && B.lo2 == 0 && B.loq == 0)) return 0;
+        if (!(B.relu_a && B.relu_b && B.relu1 && B.r1.u8_shr() && B.r2.u8_shr() && B.rq.u8_shr())) return 0;
         if (!(shortcut_blocks >> k & 1u) && B.res_shl != 0) return 0;
-        f16 = f16 && B.n1 <= kRequantU8MaxShift && B.n2 <= kRequantU8MaxShift && B.nq <= kRequantU8MaxShift;
+        f16 = f16 && B.r1.u8_float() && B.r2.u8_float() && B.rq.u8_float();
     }
     if (q8) {
-        if (!(a.q[0].n > 0 && a.q[0].n <= 30 && a.q[0].lo == 0)) return 0;
-        f16 = f16 && a.q[0].n <= kRequantU8MaxShift;
+        if (!a.q[0].u8_shr()) return 0;
+        f16 = f16 && a.q[0].u8_float();
     }
     return (a.rq_int || !a.acc_ok || !a.stream_ok || !f16) ? 2 : 1;
 }

@@ -123,7 +123,7 @@ __global__ void __launch_bounds__(256) shuffle_i8_general_kernel(const ChanMapAr
     for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
         const unsigned m = (unsigned)(idx / vpp);
         const int c = (int)(idx - (size_t)m * vpp) << 2;
-        int qo = (int)fast_div((unsigned)c, a.mG, a.s1G, a.s2G), r = c - qo * a.groups;
+        int qo = (int)fast_div((unsigned)c, a.dG), r = c - qo * a.groups;
         unsigned w[2] = {a.q[0].bias_xor, a.q[1].bias_xor};
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -174,7 +174,7 @@ __global__ void __launch_bounds__(256) chanmap_i32_kernel(const ChanMapArgs a) {
                     y[0] = t.x; y[1] = t.y; y[2] = t.z; y[3] = t.w;
                 }
             } else {
-                int qo = (int)fast_div((unsigned)c, a.mG, a.s1G, a.s2G), r = c - qo * a.groups;      // (slice: unused)
+                int qo = (int)fast_div((unsigned)c, a.dG), r = c - qo * a.groups;      // (slice: unused)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const int sc = a.groups ? r * a.Cg + qo : first + c + e;
@@ -189,8 +189,7 @@ __global__ void __launch_bounds__(256) chanmap_i32_kernel(const ChanMapArgs a) {
             for (int k = 0; k < 2; ++k)
                 if (a.q[k].ptr)
                     *(unsigned*)(a.q[k].ptr + (size_t)m * a.Cs + c) =
-                        pack4(requant1(y[0], a.q[k].n, a.q[k].lo, a.q[k].hi), requant1(y[1], a.q[k].n, a.q[k].lo, a.q[k].hi),
-                              requant1(y[2], a.q[k].n, a.q[k].lo, a.q[k].hi), requant1(y[3], a.q[k].n, a.q[k].lo, a.q[k].hi)) ^ a.q[k].bias_xor;
+                        requant_pack4(y[0], y[1], y[2], y[3], a.q[k]);
         }
     }
 }

@@ -103,8 +103,7 @@ __global__ void __launch_bounds__(256) concat_i32_kernel(const ConcatArgs a) {
         for (int k = 0; k < 2; ++k)
             if (a.q[k].ptr)
                 *(unsigned*)(a.q[k].ptr + (size_t)m * a.Cs + c) =
-                    pack4(requant1(y[0], a.q[k].n, a.q[k].lo, a.q[k].hi), requant1(y[1], a.q[k].n, a.q[k].lo, a.q[k].hi),
-                          requant1(y[2], a.q[k].n, a.q[k].lo, a.q[k].hi), requant1(y[3], a.q[k].n, a.q[k].lo, a.q[k].hi)) ^ a.q[k].bias_xor;
+                    requant_pack4(y[0], y[1], y[2], y[3], a.q[k]);
     }
 }
 

@@ -60,9 +60,9 @@ __global__ void __launch_bounds__(256) deconv_kernel(const DeconvArgs a) {
         const int mp = tile * 64 + p * 32 + l31;
         live[p] = mp < Mph;
         const int mc = live[p] ? mp : Mph - 1;
-        n[p] = (int)fast_div((unsigned)mc, ph.mAC, ph.s1AC, ph.s2AC);
+        n[p] = (int)fast_div((unsigned)mc, ph.dAC);
         const int rem = mc - n[p] * AC;
-        const int ai = (int)fast_div((unsigned)rem, ph.mC, ph.s1C, ph.s2C);
+        const int ai = (int)fast_div((unsigned)rem, ph.dC);
         pa[p] = ph.a0 + ai; pc[p] = ph.c0 + (rem - ai * ph.Cn);
     }
 
@@ -156,8 +156,7 @@ __global__ void __launch_bounds__(256) deconv_kernel(const DeconvArgs a) {
                 unsigned d[4];
 #pragma unroll
                 for (int g = 0; g < 4; ++g)
-                    d[g] = pack4(requant1(y[g][0], a.q[k].n, a.q[k].lo, a.q[k].hi), requant1(y[g][1], a.q[k].n, a.q[k].lo, a.q[k].hi),
-                                 requant1(y[g][2], a.q[k].n, a.q[k].lo, a.q[k].hi), requant1(y[g][3], a.q[k].n, a.q[k].lo, a.q[k].hi)) ^ a.q[k].bias_xor;
+                    d[g] = requant_pack4(y[g][0], y[g][1], y[g][2], y[g][3], a.q[k]);
                 // lane half 0 collects channels 0 .. 15 of its pixel, half 1 channels 16 .. 31: one 16-byte store per lane
                 auto s0 = __builtin_amdgcn_permlane32_swap(d[0], d[2], false, false);
                 auto s1 = __builtin_amdgcn_permlane32_swap(d[1], d[3], false, false);

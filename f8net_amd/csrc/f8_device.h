@@ -53,8 +53,7 @@ __device__ __forceinline__ int requant1(int v, int n, int lo, int hi) {
 // that rounding did, because n <= 16), v_mul_f32 by 2^-n (exact), v_cvt_pk_u8_f32 (round to nearest EVEN, saturate to [0, 255], insert into
 // byte k of the dword).  Compared on the device with the integer form for EVERY int32 value and every n in 1 .. 16: identical
 // (tools/ubench/cvt_u8_probe.hip, tests/test_gpu_requant_probe.py; n >= 17 differs from 2^24 on, as predicted) — the hosts select the
-// instances that use this only when every shift involved is in 1 .. 16 (kRequantU8MaxShift).
-constexpr int kRequantU8MaxShift = 16;
+// instances that use this only when every shift involved is in 1 .. 16 (Requant::u8_float, kRequantU8MaxShift: f8_internal.h).
 // The float forms rely on ROUND-TO-NEAREST-EVEN in v_cvt_pk_u8_f32 (and v_cvt_f32_i32 above 2^24): that is the power-on state of the MODE register
 // and what HIP launches kernels with, but nothing else in the program states it — every kernel that instantiates a float form states it itself,
 // first thing (s_setreg_imm32_b32 hwreg(HW_REG_MODE, 0, 4) = 0: FP_ROUND single / double = nearest even).
@@ -87,10 +86,10 @@ __device__ __forceinline__ unsigned requant_u8x4_int(int a, int b, int c, int d,
 }
 
 // q = n / d for a divisor known on the host: q = (t + ((n - t) >> sh1)) >> sh2, t = mulhi(n, magic)
-// (round-up method, exact for every 32-bit n; host: f8_net.cpp make_magic)
-__device__ __forceinline__ unsigned fast_div(unsigned n, unsigned magic, int sh1, int sh2) {
-    const unsigned t = __umulhi(n, magic);
-    return (t + ((n - t) >> sh1)) >> sh2;
+// (round-up method, exact for every 32-bit n; host: fast_divisor, f8_internal.h)
+__device__ __forceinline__ unsigned fast_div(unsigned n, const FastDiv d) {
+    const unsigned t = __umulhi(n, d.m);
+    return (t + ((n - t) >> d.s1)) >> d.s2;
 }
 
 // low bytes of four values -> one dword (a = byte 0): three v_perm_b32 instead of and / and / and / shift-or x3
@@ -98,6 +97,10 @@ __device__ __forceinline__ unsigned pack4(int a, int b, int c, int d) {
     const unsigned lo = __builtin_amdgcn_perm((unsigned)b, (unsigned)a, 0x0c0c0400u);   // {a.b0, b.b0, 0, 0}
     const unsigned hi = __builtin_amdgcn_perm((unsigned)d, (unsigned)c, 0x0c0c0400u);   // {c.b0, d.b0, 0, 0}
     return __builtin_amdgcn_perm(hi, lo, 0x05040100u);                                    // {lo.b0, lo.b1, hi.b0, hi.b1}
+}
+// four values -> one dword in the format r, storage bias included: the general epilogue (a ReLU floor is the caller's: it passes max(x, floor))
+__device__ __forceinline__ unsigned requant_pack4(int a, int b, int c, int d, const Requant& r) {
+    return pack4(requant1(a, r.n, r.lo, r.hi), requant1(b, r.n, r.lo, r.hi), requant1(c, r.n, r.lo, r.hi), requant1(d, r.n, r.lo, r.hi)) ^ r.bias_xor;
 }
 
 // The same function — ReLU -> unsigned 8-bit, right shift n >= 1 — by compile-time choice of arithmetic.  RQ == 1: the float-converter form
@@ -118,6 +121,39 @@ __device__ __forceinline__ unsigned requant_u8x4_sel(int a, int b, int c, int d,
 __device__ __forceinline__ size_t i32t_index(int m, int c, int Cs) {
     return ((size_t)(m >> 5) * (size_t)(Cs >> 5) + (size_t)(c >> 5)) * 1024u +
            (size_t)(((((c & 31) >> 3) * 64 + ((c >> 2) & 1) * 32 + (m & 31)) << 2) + (c & 3));
+}
+
+// 16 accumulators of a lane (y[0 .. 15]: a v16i or an array) -> 16 bytes in the format r, by the cheapest exact form (wave-uniform branches); the halves of
+// a wave swap so that lane (pixel, half) holds channels 16 half .. 16 half + 15 of the 32-channel tile.  The row-walking heads' epilogue (f8_stem.hip, f8_head_dws.hip).
+template <class Y>
+__device__ __forceinline__ v4i quant_lane16(const Y& y, const Requant& r, bool acc_ok) {
+    const int n = r.n, lo = r.lo, hi = r.hi;
+    const unsigned x_or = r.bias_xor;
+    unsigned d[4];
+    if (acc_ok && r.u8_float()) {                    // the usual case with requant_float = 1 and bounded accumulators: three VALU operations per value
+        const float sc = requant_u8_scale(n);
+#pragma unroll
+        for (int g = 0; g < 4; ++g) d[g] = requant_u8x4(y[4 * g], y[4 * g + 1], y[4 * g + 2], y[4 * g + 3], sc) ^ x_or;
+    } else if (r.u8_shr()) {                         // the same case on INTEGER instructions (option requant_float = 0, the default, or an accumulator the planner
+                                                     // cannot bound): v_bfe_u32, v_add3_u32, v_ashr_pk_u8_i32: 2 3/4 per value, exact for every int32
+#pragma unroll
+        for (int g = 0; g < 4; ++g) d[g] = requant_u8x4_int(y[4 * g], y[4 * g + 1], y[4 * g + 2], y[4 * g + 3], n) ^ x_or;
+    } else if (n > 0) {                              // another right shift: four
+        const unsigned hf = 1u << (n - 1);
+#pragma unroll
+        for (int g = 0; g < 4; ++g) d[g] = pack4(requant_shr(y[4 * g], n, hf, 0u, lo, hi), requant_shr(y[4 * g + 1], n, hf, 0u, lo, hi),
+                                                 requant_shr(y[4 * g + 2], n, hf, 0u, lo, hi), requant_shr(y[4 * g + 3], n, hf, 0u, lo, hi)) ^ x_or;
+    } else {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) d[g] = requant_pack4(y[4 * g], y[4 * g + 1], y[4 * g + 2], y[4 * g + 3], r);
+    }
+    auto s0 = __builtin_amdgcn_permlane32_swap(d[0], d[2], false, false);
+    auto s1 = __builtin_amdgcn_permlane32_swap(d[1], d[3], false, false);
+    const v4i o = {(int)s0[0], (int)s0[1], (int)s1[0], (int)s1[1]};
+    return o;
+}
+__device__ __forceinline__ int dpp_next_lane(int v) {   // lane i <- lane i + 1 (across the 16-lane DPP rows; lane 63 keeps its value)
+    return __builtin_amdgcn_update_dpp(v, v, 0x130 /* wave_shl:1 */, 0xf, 0xf, false);
 }
 
 __device__ __forceinline__ int clamp_sym31(int v) {   // clamp_(max=2^31-1, min=-(2^31-1))

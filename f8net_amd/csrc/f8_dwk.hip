@@ -79,8 +79,7 @@ __global__ void __launch_bounds__(256) dwconvk_kernel(const DwArgs a) {
         for (int k = 0; k < 2; ++k)
             if (a.q[k].ptr)
                 *(unsigned*)(a.q[k].ptr + o) =
-                    pack4(requant1(acc[0], a.q[k].n, a.q[k].lo, a.q[k].hi), requant1(acc[1], a.q[k].n, a.q[k].lo, a.q[k].hi),
-                          requant1(acc[2], a.q[k].n, a.q[k].lo, a.q[k].hi), requant1(acc[3], a.q[k].n, a.q[k].lo, a.q[k].hi)) ^ a.q[k].bias_xor;
+                    requant_pack4(acc[0], acc[1], acc[2], acc[3], a.q[k]);
     }
 }
 
@@ -165,8 +164,7 @@ __global__ void __launch_bounds__(256) dwconvk_dot4_kernel(const DwArgs a) {
         for (int f = 0; f < 2; ++f)
             if (a.q[f].ptr)
                 *(unsigned*)(a.q[f].ptr + o) =
-                    pack4(requant1(acc[j][0], a.q[f].n, a.q[f].lo, a.q[f].hi), requant1(acc[j][1], a.q[f].n, a.q[f].lo, a.q[f].hi),
-                          requant1(acc[j][2], a.q[f].n, a.q[f].lo, a.q[f].hi), requant1(acc[j][3], a.q[f].n, a.q[f].lo, a.q[f].hi)) ^ a.q[f].bias_xor;
+                    requant_pack4(acc[j][0], acc[j][1], acc[j][2], acc[j][3], a.q[f]);
     }
 }
 
@@ -241,8 +239,7 @@ __global__ void __launch_bounds__(256) dwconv3x3_dil_dot4_kernel(const DwArgs a)
         for (int f = 0; f < 2; ++f)
             if (a.q[f].ptr)
                 *(unsigned*)(a.q[f].ptr + o) =
-                    pack4(requant1(acc[j][0], a.q[f].n, a.q[f].lo, a.q[f].hi), requant1(acc[j][1], a.q[f].n, a.q[f].lo, a.q[f].hi),
-                          requant1(acc[j][2], a.q[f].n, a.q[f].lo, a.q[f].hi), requant1(acc[j][3], a.q[f].n, a.q[f].lo, a.q[f].hi)) ^ a.q[f].bias_xor;
+                    requant_pack4(acc[j][0], acc[j][1], acc[j][2], acc[j][3], a.q[f]);
     }
 }
 

@@ -109,8 +109,7 @@ __global__ void __launch_bounds__(256, S == 1 ? 4 : 3) dwconv3x3_mma_kernel(cons
                 const int floor0 = a.relu0 ? 0 : INT32_MIN;
 #pragma unroll
                 for (int g = 0; g < 4; ++g)
-                    d[g] = pack4(requant1(max(acc[4 * g], floor0), a.q[k].n, a.q[k].lo, a.q[k].hi), requant1(max(acc[4 * g + 1], floor0), a.q[k].n, a.q[k].lo, a.q[k].hi),
-                                 requant1(max(acc[4 * g + 2], floor0), a.q[k].n, a.q[k].lo, a.q[k].hi), requant1(max(acc[4 * g + 3], floor0), a.q[k].n, a.q[k].lo, a.q[k].hi)) ^ a.q[k].bias_xor;
+                    d[g] = requant_pack4(max(acc[4 * g], floor0), max(acc[4 * g + 1], floor0), max(acc[4 * g + 2], floor0), max(acc[4 * g + 3], floor0), a.q[k]);
             }
             auto s0 = __builtin_amdgcn_permlane32_swap(d[0], d[2], false, false);
             auto s1 = __builtin_amdgcn_permlane32_swap(d[1], d[3], false, false);
@@ -175,8 +174,8 @@ int dwconv_mma_inst(const DwArgs& a, bool out32, int nq, int N) {
           (a.stride == 1 ? (a.P == a.H && a.Q == a.W) : (a.H == 2 * a.P && a.W == 2 * a.Q)) && (size_t)N * a.H * a.W * a.Cs < 0x7fffffffull)) return -1;
     int fq = a.relu0 != 0 ? ((a.acc_ok != 0 && !a.rq_int) ? 1 : 2) : 0;      // 1: float converter; 2: integer form of the same requantisation
     for (int k = 0; k < nq; ++k) {
-        if (!(a.q[k].n > 0 && a.q[k].n <= 30 && a.q[k].lo == 0 && a.q[k].hi == 255 && a.q[k].bias_xor == 0x80808080u)) fq = 0;
-        else if (fq == 1 && a.q[k].n > kRequantU8MaxShift) fq = 2;
+        if (!a.q[k].u8_shr()) fq = 0;
+        else if (fq == 1 && !a.q[k].u8_float()) fq = 2;
     }
     return fq | (a.Q >= DW_SW ? 1 : 2) << 2;
 }

@@ -47,7 +47,7 @@ __global__ void __launch_bounds__(DWS_NW * 64) dws_kernel(const DwsArgs a) {
         const DwsSrc src{a.x, a.wd, a.bd, a.N, a.H, a.W, a.Cin, a.in_signed};
         const int cts = a.Cin >> 5, strips = (a.Q + VW - 1) / VW;
         const int u = SUBS == 2 ? l31 & 15 : l31;
-        const float sc1 = FQ == 1 ? requant_u8_scale(a.n1) : 0.0f;
+        const float sc1 = FQ == 1 ? requant_u8_scale(a.r1.n) : 0.0f;
         (void)sc1;
         for (int it = wave; it < strips * cts; it += DWS_NW) {      // channel tile fastest: the waves read the same pixels' other channels
             const int ct = it % cts, q0 = (it / cts) * VW;
@@ -57,9 +57,8 @@ __global__ void __launch_bounds__(DWS_NW * 64) dws_kernel(const DwsArgs a) {
                 unsigned d[4];
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
-                    if constexpr (FQ) d[g] = requant_u8x4_sel<FQ == 2 ? 2 : 1>(acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3], a.n1, sc1) ^ 0x80808080u;
-                    else d[g] = pack4(requant1(max(acc[4 * g], 0), a.n1, a.lo1, a.hi1), requant1(max(acc[4 * g + 1], 0), a.n1, a.lo1, a.hi1),
-                                      requant1(max(acc[4 * g + 2], 0), a.n1, a.lo1, a.hi1), requant1(max(acc[4 * g + 3], 0), a.n1, a.lo1, a.hi1)) ^ a.xor1;
+                    if constexpr (FQ) d[g] = requant_u8x4_sel<FQ == 2 ? 2 : 1>(acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3], a.r1.n, sc1) ^ 0x80808080u;
+                    else d[g] = requant_pack4(max(acc[4 * g], 0), max(acc[4 * g + 1], 0), max(acc[4 * g + 2], 0), max(acc[4 * g + 3], 0), a.r1);
                 }
                 auto s0 = __builtin_amdgcn_permlane32_swap(d[0], d[2], false, false);
                 auto s1 = __builtin_amdgcn_permlane32_swap(d[1], d[3], false, false);
@@ -135,8 +134,7 @@ __global__ void __launch_bounds__(DWS_NW * 64) dws_kernel(const DwsArgs a) {
                     } else {
 #pragma unroll
                         for (int g = 0; g < 4; ++g)
-                            d[g] = pack4(requant1(max(acc[t][4 * g], floor0), a.q[k].n, a.q[k].lo, a.q[k].hi), requant1(max(acc[t][4 * g + 1], floor0), a.q[k].n, a.q[k].lo, a.q[k].hi),
-                                         requant1(max(acc[t][4 * g + 2], floor0), a.q[k].n, a.q[k].lo, a.q[k].hi), requant1(max(acc[t][4 * g + 3], floor0), a.q[k].n, a.q[k].lo, a.q[k].hi)) ^ a.q[k].bias_xor;
+                            d[g] = requant_pack4(max(acc[t][4 * g], floor0), max(acc[t][4 * g + 1], floor0), max(acc[t][4 * g + 2], floor0), max(acc[t][4 * g + 3], floor0), a.q[k]);
                     }
                     auto s0 = __builtin_amdgcn_permlane32_swap(d[0], d[2], false, false);
                     auto s1 = __builtin_amdgcn_permlane32_swap(d[1], d[3], false, false);
@@ -180,11 +178,10 @@ bool dws_supported(int cinS, int coutS, int H, int W, int stride, int imgs, int*
 
 // FQ (see the kernel) | sub-rows << 2
 int dws_inst(const DwsArgs& a, int nq) {
-    int fq = (a.relu0 && nq > 0 && a.n1 > 0 && a.n1 <= 30 && a.lo1 == 0 && a.hi1 == 255 && a.xor1 == 0x80808080u) ?
-             ((a.acc_ok && !a.rq_int && a.n1 <= kRequantU8MaxShift) ? 1 : 2) : 0;
+    int fq = (a.relu0 && nq > 0 && a.r1.u8_shr()) ? ((a.acc_ok && !a.rq_int && a.r1.u8_float()) ? 1 : 2) : 0;
     for (int k = 0; k < nq && fq; ++k) {
-        if (!(a.q[k].n > 0 && a.q[k].n <= 30 && a.q[k].lo == 0 && a.q[k].hi == 255 && a.q[k].bias_xor == 0x80808080u)) fq = 0;
-        else if (fq == 1 && a.q[k].n > kRequantU8MaxShift) fq = 2;
+        if (!a.q[k].u8_shr()) fq = 0;
+        else if (fq == 1 && !a.q[k].u8_float()) fq = 2;
     }
     return fq | (a.Q >= DWS_SW ? 1 : 2) << 2;
 }

@@ -59,7 +59,7 @@ __global__ void __launch_bounds__(D7_NW * 64) dws7_kernel(const Dws7Args a) {
     {
         const int cgs = a.Cin >> 4;
         const unsigned padv = a.in_signed ? 0u : 0x80808080u;
-        const float sc1 = FQ == 1 ? requant_u8_scale(a.n1) : 0.0f;
+        const float sc1 = FQ == 1 ? requant_u8_scale(a.r1.n) : 0.0f;
         (void)sc1;
         for (int idx = tid; idx < npx * cgs; idx += D7_NW * 64) {
             const int px = idx / cgs, cg = idx - px * cgs, c = cg << 4;
@@ -98,9 +98,8 @@ __global__ void __launch_bounds__(D7_NW * 64) dws7_kernel(const Dws7Args a) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
                     acc[e] = (int)((unsigned)acc[e] + (unsigned)((int)(signed char)(t8 >> (8 * e)) * (int)(signed char)(wC >> (8 * e))));
-                if constexpr (FQ) o[k] = requant_u8x4_sel<FQ == 2 ? 2 : 1>(acc[0], acc[1], acc[2], acc[3], a.n1, sc1) ^ 0x80808080u;
-                else o[k] = pack4(requant1(max(acc[0], 0), a.n1, a.lo1, a.hi1), requant1(max(acc[1], 0), a.n1, a.lo1, a.hi1),
-                                  requant1(max(acc[2], 0), a.n1, a.lo1, a.hi1), requant1(max(acc[3], 0), a.n1, a.lo1, a.hi1)) ^ a.xor1;
+                if constexpr (FQ) o[k] = requant_u8x4_sel<FQ == 2 ? 2 : 1>(acc[0], acc[1], acc[2], acc[3], a.r1.n, sc1) ^ 0x80808080u;
+                else o[k] = requant_pack4(max(acc[0], 0), max(acc[1], 0), max(acc[2], 0), max(acc[3], 0), a.r1);
             }
             const v4i ov = {(int)o[0], (int)o[1], (int)o[2], (int)o[3]};
             *(v4i*)(mid + (cg >> 1) * plane + px * 32 + (cg & 1) * 16) = ov;
@@ -192,8 +191,7 @@ __global__ void __launch_bounds__(D7_NW * 64) dws7_kernel(const Dws7Args a) {
                         } else {
 #pragma unroll
                             for (int g = 0; g < 4; ++g)
-                                d[g] = pack4(requant1(max(acc[t][4 * g], floor0), a.q[k].n, a.q[k].lo, a.q[k].hi), requant1(max(acc[t][4 * g + 1], floor0), a.q[k].n, a.q[k].lo, a.q[k].hi),
-                                             requant1(max(acc[t][4 * g + 2], floor0), a.q[k].n, a.q[k].lo, a.q[k].hi), requant1(max(acc[t][4 * g + 3], floor0), a.q[k].n, a.q[k].lo, a.q[k].hi)) ^ a.q[k].bias_xor;
+                                d[g] = requant_pack4(max(acc[t][4 * g], floor0), max(acc[t][4 * g + 1], floor0), max(acc[t][4 * g + 2], floor0), max(acc[t][4 * g + 3], floor0), a.q[k]);
                         }
                         auto s0 = __builtin_amdgcn_permlane32_swap(d[0], d[2], false, false);
                         auto s1 = __builtin_amdgcn_permlane32_swap(d[1], d[3], false, false);
@@ -221,8 +219,7 @@ __global__ void __launch_bounds__(D7_NW * 64) dws7_kernel(const Dws7Args a) {
             for (int k = 0; k < 2; ++k)
                 if (a.q[k].ptr)
                     *(unsigned*)(a.q[k].ptr + (size_t)n * a.Cout + c) =
-                        pack4(requant1(v.x, a.q[k].n, a.q[k].lo, a.q[k].hi), requant1(v.y, a.q[k].n, a.q[k].lo, a.q[k].hi),
-                              requant1(v.z, a.q[k].n, a.q[k].lo, a.q[k].hi), requant1(v.w, a.q[k].n, a.q[k].lo, a.q[k].hi)) ^ a.q[k].bias_xor;
+                        requant_pack4(v.x, v.y, v.z, v.w, a.q[k]);
         }
     }
 }
@@ -255,11 +252,10 @@ int dws7_slices(int groups, int nco, int cus) {
 
 // FQ (see the kernel).  With the pool only the depthwise requantisation is in it: the pooled values take the general form.
 int dws7_inst(const Dws7Args& a, int nq) {
-    int fq = (a.relu0 && (a.pool || nq > 0) && a.n1 > 0 && a.n1 <= 30 && a.lo1 == 0 && a.hi1 == 255 && a.xor1 == 0x80808080u) ?
-             ((a.acc_ok && !a.rq_int && a.n1 <= kRequantU8MaxShift) ? 1 : 2) : 0;
+    int fq = (a.relu0 && (a.pool || nq > 0) && a.r1.u8_shr()) ? ((a.acc_ok && !a.rq_int && a.r1.u8_float()) ? 1 : 2) : 0;
     for (int k = 0; k < nq && fq && !a.pool; ++k) {
-        if (!(a.q[k].n > 0 && a.q[k].n <= 30 && a.q[k].lo == 0 && a.q[k].hi == 255 && a.q[k].bias_xor == 0x80808080u)) fq = 0;
-        else if (fq == 1 && a.q[k].n > kRequantU8MaxShift) fq = 2;
+        if (!a.q[k].u8_shr()) fq = 0;
+        else if (fq == 1 && !a.q[k].u8_float()) fq = 2;
     }
     return fq;
 }

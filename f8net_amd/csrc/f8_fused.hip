@@ -125,7 +125,7 @@ fused_bottleneck_kernel(const FusedArgs a) {   // MID <= 128: <= 128 VGPRs so th
 #endif
     // ---- patch <- biased zero everywhere (border and out-of-image rows keep it); ALLW: after P1 (its stages lie over the patch)
     auto zero_patch = [&]() {
-        const unsigned z = a.xor1;
+        const unsigned z = a.r1.bias_xor;
         const v4i zv = {(int)z, (int)z, (int)z, (int)z};
         for (int o = tid * 16; o < PATCH_BYTES; o += 512 * 16) *(v4i*)(patch + o) = zv;
     };
@@ -409,8 +409,8 @@ fused_bottleneck_kernel(const FusedArgs a) {   // MID <= 128: <= 128 VGPRs so th
                 for (int g = 0; g < 4; ++g) {
                     int y[4];
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) y[e] = requant1(max(acc[j][i][4 * g + e], floor0), a.n1, a.lo1, a.hi1);
-                    d[g] = pack4(y[0], y[1], y[2], y[3]) ^ a.xor1;
+                    for (int e = 0; e < 4; ++e) y[e] = max(acc[j][i][4 * g + e], floor0);
+                    d[g] = requant_pack4(y[0], y[1], y[2], y[3], a.r1);
                 }
                 auto s0 = __builtin_amdgcn_permlane32_swap(d[0], d[2], false, false);
                 auto s1 = __builtin_amdgcn_permlane32_swap(d[1], d[3], false, false);
@@ -610,8 +610,8 @@ fused_bottleneck_kernel(const FusedArgs a) {   // MID <= 128: <= 128 VGPRs so th
             for (int g = 0; g < 4; ++g) {
                 int y[4];
 #pragma unroll
-                for (int e = 0; e < 4; ++e) y[e] = requant1(max(acc[i][4 * g + e], floor0), a.n2, a.lo2, a.hi2);
-                d[g] = pack4(y[0], y[1], y[2], y[3]) ^ a.xor2;
+                for (int e = 0; e < 4; ++e) y[e] = max(acc[i][4 * g + e], floor0);
+                d[g] = requant_pack4(y[0], y[1], y[2], y[3], a.r2);
             }
             auto s0 = __builtin_amdgcn_permlane32_swap(d[0], d[2], false, false);
             auto s1 = __builtin_amdgcn_permlane32_swap(d[1], d[3], false, false);
@@ -749,8 +749,7 @@ fused_bottleneck_kernel(const FusedArgs a) {   // MID <= 128: <= 128 VGPRs so th
                 unsigned d[4];
 #pragma unroll
                 for (int g = 0; g < 4; ++g)
-                    d[g] = pack4(requant1(y[g][0], a.q[k].n, a.q[k].lo, a.q[k].hi), requant1(y[g][1], a.q[k].n, a.q[k].lo, a.q[k].hi),
-                                 requant1(y[g][2], a.q[k].n, a.q[k].lo, a.q[k].hi), requant1(y[g][3], a.q[k].n, a.q[k].lo, a.q[k].hi)) ^ a.q[k].bias_xor;
+                    d[g] = requant_pack4(y[g][0], y[g][1], y[g][2], y[g][3], a.q[k]);
                 auto s0 = __builtin_amdgcn_permlane32_swap(d[0], d[2], false, false);
                 auto s1 = __builtin_amdgcn_permlane32_swap(d[1], d[3], false, false);
 #ifdef F8_ABL_NOSTORE8_ALL
@@ -840,8 +839,7 @@ fused_bottleneck_kernel(const FusedArgs a) {   // MID <= 128: <= 128 VGPRs so th
                 unsigned d[4];
 #pragma unroll
                 for (int g = 0; g < 4; ++g)
-                    d[g] = pack4(requant1(y[g][0], a.q[kq].n, a.q[kq].lo, a.q[kq].hi), requant1(y[g][1], a.q[kq].n, a.q[kq].lo, a.q[kq].hi),
-                                 requant1(y[g][2], a.q[kq].n, a.q[kq].lo, a.q[kq].hi), requant1(y[g][3], a.q[kq].n, a.q[kq].lo, a.q[kq].hi)) ^ a.q[kq].bias_xor;
+                    d[g] = requant_pack4(y[g][0], y[g][1], y[g][2], y[g][3], a.q[kq]);
                 auto s0 = __builtin_amdgcn_permlane32_swap(d[0], d[2], false, false);
                 auto s1 = __builtin_amdgcn_permlane32_swap(d[1], d[3], false, false);
 #if defined(F8_ABL_P3_NOSTORE) || defined(F8_ABL_P3_NOSTORE8)

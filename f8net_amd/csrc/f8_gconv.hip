@@ -56,8 +56,8 @@ __global__ void __launch_bounds__(256) gconv3x3_kernel(const GConvArgs a) {
     for (int i = 0; i * 256 + wave * 64 < slots; ++i) {         // wave-uniform bound
         const int s = i * 256 + tid;
         const int ppx = s >> 3, chunk = (s & 7) ^ SW::f(ppx);
-        const int img = (int)fast_div((unsigned)ppx, a.mIPP, a.s1IPP, a.s2IPP), rem = ppx - img * IMG_PP;
-        const int pr = (int)fast_div((unsigned)rem, a.mPW, a.s1PW, a.s2PW), pc = rem - pr * a.PW;
+        const int img = (int)fast_div((unsigned)ppx, a.dIPP), rem = ppx - img * IMG_PP;
+        const int pr = (int)fast_div((unsigned)rem, a.dPW), pc = rem - pr * a.PW;
         const int h = h0 + pr, w = w0 + pc, n = n0 + img, cb = quad * 128 + chunk * 16;
         const bool ok = s < slots && (unsigned)h < (unsigned)a.H && (unsigned)w < (unsigned)a.W && n < a.N && cb < a.Cs;
         const unsigned off = ok ? (unsigned)(((n * a.H + h) * a.W + w) * a.Cs + cb) : kOOB;
@@ -84,8 +84,8 @@ __global__ void __launch_bounds__(256) gconv3x3_kernel(const GConvArgs a) {
         // output pixel of this lane inside the tile (padding lanes: the tile's last pixel, result unused)
         const int op = pt * 32 + l31;
         const int oc = op < out_px ? op : out_px - 1;
-        const int img = (int)fast_div((unsigned)oc, a.mRTW, a.s1RTW, a.s2RTW), orem = oc - img * RTW;
-        const int orow = (int)fast_div((unsigned)orem, a.mTW, a.s1TW, a.s2TW), ocol = orem - orow * a.TW;
+        const int img = (int)fast_div((unsigned)oc, a.dRTW), orem = oc - img * RTW;
+        const int orow = (int)fast_div((unsigned)orem, a.dTW), ocol = orem - orow * a.TW;
         const int bpx = img * IMG_PP + orow * S * a.PW + ocol * S;              // patch pixel of tap (0, 0)
         const int n = n0 + img, p = p0 + orow, q = q0 + ocol;
         const bool ok = op < out_px && n < a.N && p < a.P && q < a.Q;           // (edge tiles: rows / columns / images past the map / batch)
@@ -124,8 +124,7 @@ __global__ void __launch_bounds__(256) gconv3x3_kernel(const GConvArgs a) {
             unsigned d[4];
 #pragma unroll
             for (int g = 0; g < 4; ++g)
-                d[g] = pack4(requant1(y[g][0], a.q[k].n, a.q[k].lo, a.q[k].hi), requant1(y[g][1], a.q[k].n, a.q[k].lo, a.q[k].hi),
-                             requant1(y[g][2], a.q[k].n, a.q[k].lo, a.q[k].hi), requant1(y[g][3], a.q[k].n, a.q[k].lo, a.q[k].hi)) ^ a.q[k].bias_xor;
+                d[g] = requant_pack4(y[g][0], y[g][1], y[g][2], y[g][3], a.q[k]);
             // lane half 0 collects channels 0 .. 15 of its pixel, half 1 channels 16 .. 31: one 16-byte store per lane
             auto s0 = __builtin_amdgcn_permlane32_swap(d[0], d[2], false, false);
             auto s1 = __builtin_amdgcn_permlane32_swap(d[1], d[3], false, false);

@@ -29,41 +29,13 @@ constexpr int SW = 28;                              // output columns per strip 
 constexpr int RBK = 14;                             // output rows per band (2 * 14 + 5 = 33 input rows)
 constexpr int RB_ROWS = 35;                         // rows of a patch buffer (the geometry of f8_stem.hip's buffers)
 
-__device__ __forceinline__ int dpp_next_lane(int v) {   // lane i <- lane i + 1 (across the 16-lane DPP rows; lane 63 keeps its value)
-    return __builtin_amdgcn_update_dpp(v, v, 0x130 /* wave_shl:1 */, 0xf, 0xf, false);
-}
-// 16 accumulators of a lane -> 16 bytes in one reader format (f8_stem.hip stem_quant16: the same four forms)
-__device__ __forceinline__ v4i head_quant16(const v16i& y, int n, int lo, int hi, unsigned x_or, bool acc_ok) {
-    unsigned d[4];
-    if (acc_ok && n > 0 && n <= kRequantU8MaxShift && lo == 0 && hi == 255) {   // unsigned 8-bit through the float converter (requant_float = 1, bounded accumulators)
-        const float sc = requant_u8_scale(n);
-#pragma unroll
-        for (int g = 0; g < 4; ++g) d[g] = requant_u8x4(y[4 * g], y[4 * g + 1], y[4 * g + 2], y[4 * g + 3], sc) ^ x_or;
-    } else if (n > 0 && n <= 30 && lo == 0 && hi == 255) {   // the same on integer instructions: exact for every int32
-#pragma unroll
-        for (int g = 0; g < 4; ++g) d[g] = requant_u8x4_int(y[4 * g], y[4 * g + 1], y[4 * g + 2], y[4 * g + 3], n) ^ x_or;
-    } else if (n > 0) {                              // another right shift
-        const unsigned hf = 1u << (n - 1);
-#pragma unroll
-        for (int g = 0; g < 4; ++g) d[g] = pack4(requant_shr(y[4 * g], n, hf, 0u, lo, hi), requant_shr(y[4 * g + 1], n, hf, 0u, lo, hi),
-                                                 requant_shr(y[4 * g + 2], n, hf, 0u, lo, hi), requant_shr(y[4 * g + 3], n, hf, 0u, lo, hi)) ^ x_or;
-    } else {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) d[g] = pack4(requant1(y[4 * g], n, lo, hi), requant1(y[4 * g + 1], n, lo, hi), requant1(y[4 * g + 2], n, lo, hi),
-                                                 requant1(y[4 * g + 3], n, lo, hi)) ^ x_or;
-    }
-    auto s0 = __builtin_amdgcn_permlane32_swap(d[0], d[2], false, false);
-    auto s1 = __builtin_amdgcn_permlane32_swap(d[1], d[3], false, false);
-    const v4i o = {(int)s0[0], (int)s0[1], (int)s1[0], (int)s1[1]};
-    return o;                                        // lane (pixel, half): channels 16 half .. 16 half + 15 of the 32-channel tile
-}
 }
 
 // KIND: the run's raw input (0 int32, 1 fp32, 2 uint8 planes; -1: the haloed NHWC4 copy); NT: 32-channel output tiles of the 1x1
 template <int KIND, int NT>
 __global__ void __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3, 3))) head_dws_kernel(const StemPoolArgs a) {
     extern __shared__ __attribute__((aligned(16))) char lds[];      // 2 x [RB_ROWS][PWB pixels][4 B] (patch column pc = input column pc - 5) | 128 biases | u8 table
-    set_fp_round_nearest_even();                                    // head_quant16 / quant_row may take the float-converter form (f8_device.h)
+    set_fp_round_nearest_even();                                    // quant_lane16 / quant_row may take the float-converter form (f8_device.h)
     const int tid = threadIdx.x;
     const int lane = tid & 63, l31 = lane & 31, lh = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // 0 .. 7 compute, 8 .. 11 loaders
@@ -305,7 +277,7 @@ __global__ void __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3, 3))
 #pragma unroll
                                 for (int q = 0; q < 16; ++q) y[q] = max(y[q], 0);
                             }
-                            const v4i v = head_quant16(y, a.q[k].n, a.q[k].lo, a.q[k].hi, a.q[k].bias_xor, !rqi);
+                            const v4i v = quant_lane16(y, a.q[k], !rqi);
                             if (lane_out) *(v4i*)(a.q[k].ptr + m * (32 * NT) + t * 32 + lh * 16) = v;
                         }
                 R0 = R1; R1 = R2;

@@ -85,13 +85,35 @@ struct Options {
 void options_from_env(Options* o);                       // f8_net.cpp
 int* option_slot(Options* o, const char* key);            // nullptr: unknown key
 
-// One requantised int8 output of an epilogue: int_op_only_fix_quant with n = src_fl - dst_fl.
-struct QuantOut {
-    int8_t* ptr;      // NHWC int8, row stride ld (bytes); nullptr = absent
+// The largest right shift at which the float-converter requantisation is exact (requant_u8x4, f8_device.h)
+constexpr int kRequantU8MaxShift = 16;
+
+// One requantisation target format: int_op_only_fix_quant with n = src_fl - dst_fl.  Every Requant is made by of().
+struct Requant {
     int32_t n;        // shift (> 0 right with round-half-even, <= 0 left)
     int32_t lo, hi;   // clamp bounds: [-127,127] or [0,255]
     uint32_t bias_xor; // 0x80808080 for unsigned formats (stored biased: x ^ 0x80), 0 for signed
+    static Requant of(int n, bool sgn) { return sgn ? Requant{n, -127, 127, 0u} : Requant{n, 0, 255, 0x80808080u}; }
+    // THE fast-instance rule: unsigned 8-bit by a right shift of 1 .. 30 — behind a ReLU (each *_inst / *_fast adds that and what else is its own)
+    // this is what the FAST / FQ instances compute (requant_u8x4_int, f8_device.h).  Since of() is the only maker, lo == 0 alone (what the stage-chain
+    // families used to test) and the full clamp / bias test are the same condition: every family states this one.
+    __host__ __device__ bool u8_shr() const { return n > 0 && n <= 30 && lo == 0 && hi == 255 && bias_xor == 0x80808080u; }
+    // ... and the float converter is exact for it: u8_shr() with the tighter bound, spelled out (one range test on the device)
+    __host__ __device__ bool u8_float() const { return n > 0 && n <= kRequantU8MaxShift && lo == 0 && hi == 255 && bias_xor == 0x80808080u; }
 };
+// One requantised int8 output of an epilogue: a Requant with a pointer.  The pointer stands IN FRONT of the format, hence as a base of its own: that is the
+// kernel-argument layout the stage-chain kernels were built with; behind the format, their SGPR spill counts and scratch sizes move.
+struct QuantPtr { int8_t* ptr; };      // NHWC int8, row stride ld (bytes); nullptr = absent
+struct QuantOut : QuantPtr, Requant {};
+
+// A divisor known at finalize: n / d == (t + ((n - t) >> s1)) >> s2, t = high32(n * m); exact for every 32-bit n (Granlund-Montgomery round-up
+// method, branch-free form).  Device side: fast_div (f8_device.h).
+struct FastDiv { uint32_t m; int32_t s1, s2; };
+inline FastDiv fast_divisor(uint32_t d) {                 // d >= 1
+    int l = 0;
+    while ((1ull << l) < d) ++l;                       // l = ceil(log2 d)
+    return {(uint32_t)(((1ull << 32) * ((1ull << l) - d)) / d + 1), l < 1 ? l : 1, l > 1 ? l - 1 : 0};
+}
 
 // Implicit-GEMM int8 convolution / linear on v_mfma_i32_32x32x32_i8.
 //   D[cout][pixel] = sum_k W[cout][k] * (X[pixel][k] ^ xor_mask)   (+ offset-corrected bias)
@@ -104,7 +126,7 @@ struct ConvArgs {
     int32_t ncc;                           // 0: single class (no padding, or signed input)
     int32_t M;                             // N*P*Q output pixels
     int32_t PQ, Q;
-    uint32_t mPQ, mQ; int32_t s1PQ, s2PQ, s1Q, s2Q;   // magic numbers for m / PQ and rem / Q (fast_div)
+    FastDiv dPQ, dQ;                       // m / PQ and rem / Q
     int32_t sN, sP, sQ;                    // input byte strides: per image, per output row, per output col
     int32_t origin;                        // byte offset of tap (0,0) at p=q=0 (negative with padding)
     int32_t H, W, stride, pad, kh, kw;
@@ -159,8 +181,7 @@ struct GConvArgs {
     int32_t R, TW, G;                      // a workgroup's tile: R output rows x TW output columns of G images (gconv_tile; G > 1: whole images)
     int32_t tiles_r, tiles_c;              // tiles per image
     int32_t PR, PW;                        // its haloed input patch, pixels per image: (R - 1) stride + 3 rows of (TW - 1) stride + 3
-    // magic numbers (fast_div) for / (PR * PW), / PW, / (R * TW), / TW: [magic, sh1, sh2]
-    uint32_t mIPP, mPW, mRTW, mTW; int32_t s1IPP, s2IPP, s1PW, s2PW, s1RTW, s2RTW, s1TW, s2TW;
+    FastDiv dIPP, dPW, dRTW, dTW;          // / (PR * PW), / PW, / (R * TW), / TW
     int32_t relu0;
     int32_t* out32;
     QuantOut q[2];
@@ -217,8 +238,7 @@ struct ConcatArgs {
 struct UpsampleArgs {
     const void* src[2];
     int32_t N, C, Cs, Hs, Ws, P, Q, sh, sw, k;           // images, real / padded channels, source map, output map, scales, bilinear: log2 of the scale
-    uint32_t mPQ, mQ, mSh, mSw, mWs, mVpp;               // magic divisors (make_magic): P * Q, Q, sh, sw, Ws, Cs / 16
-    int32_t s1PQ, s2PQ, s1Q, s2Q, s1Sh, s2Sh, s1Sw, s2Sw, s1Ws, s2Ws, s1Vpp, s2Vpp;
+    FastDiv dPQ, dQ, dSh, dSw, dWs, dVpp;                // / (P * Q), / Q, / sh, / sw, / Ws, / (Cs / 16)
     int32_t* out32;
     QuantOut q[2];
 };
@@ -229,8 +249,7 @@ struct SumPoolArgs {
     const int32_t* x;
     int32_t N, C, Cs, H, W, P, Q, k, stride, pad;        // images, real / padded channels, source map, output map, window
     int32_t lg;                                          // sumpool_wide_kernel: log2 of the lanes that share one (output pixel, 4 channels) item (sumpool_wide_lg)
-    uint32_t mPQ, mQ, mK, mCg;                           // magic divisors (make_magic): P * Q, Q, k, Cs / 4
-    int32_t s1PQ, s2PQ, s1Q, s2Q, s1K, s2K, s1Cg, s2Cg;
+    FastDiv dPQ, dQ, dK, dCg;                            // / (P * Q), / Q, / k, / (Cs / 4)
     int32_t* out32;
     QuantOut q[2];
 };
@@ -252,7 +271,7 @@ struct ChanMapArgs {
     int32_t Cs_src[kMaxConcat], off[kMaxConcat];         // row stride (padded channels) of entry i, its first channel
     int32_t K, groups, Cg;                               // table entries; 0 = slice, else the shuffle's groups (== K) and channels per group
     int32_t M, C, Cs;                                    // pixels N * H * W, real / padded output channels
-    uint32_t mG; int32_t s1G, s2G;                       // magic divisor (make_magic): groups
+    FastDiv dG;                                          // / groups
     int32_t* out32;
     QuantOut q[2];
 };
@@ -266,7 +285,7 @@ struct DeconvPhase {
     int32_t a0, c0, A, Cn;                 // first row / column index (a, c) of its sub-grid, the sub-grid's rows / columns (0: the phase has no output pixel)
     int32_t Th, Tw;                        // live taps per axis: ceil((k - rh) / s), ceil((k - rw) / s); 0: its outputs are the bias alone
     uint32_t w_off;                        // byte offset of its packed weights [coutP][Th * Tw * CK] in MFMA-fragment order: [cout tile][K32 step][lane][16 B] (pack_deconv_weights)
-    uint32_t mAC, mC; int32_t s1AC, s2AC, s1C, s2C;   // magic numbers (fast_div) for / (A * Cn), / Cn
+    FastDiv dAC, dC;                       // / (A * Cn), / Cn
 };
 struct DeconvArgs {
     const int8_t* x; uint32_t x_bytes;     // NHWC int8 [N][H][W][CK]
@@ -296,8 +315,8 @@ struct FusedArgs {
     // DS variant (wsc != nullptr): the join's other operand is the shortcut conv Wsc[COUT][C] . x (+ bsc) instead of xr
     const int8_t* wsc; uint32_t wsc_bytes; const int32_t* bsc; int32_t COUT;
     int32_t N, H, W, C, MID, R, tiles_per_img;
-    int32_t n1, lo1, hi1; uint32_t xor1;   // requant body.0 output -> body.2 input format
-    int32_t n2, lo2, hi2; uint32_t xor2;   // requant body.2 output -> body.4 input format
+    Requant r1;                            // requant body.0 output -> body.2 input format
+    Requant r2;                            // requant body.2 output -> body.4 input format
     int32_t relu_a, relu_b;                // ReLU after body.0 / body.2
     int32_t acc_shl, res_shl, relu1;       // residual join
     int32_t* out32; QuantOut q[2];
@@ -313,9 +332,9 @@ struct FusedArgs {
 struct ChainBlk {
     const int8_t* w0; const int8_t* w2; const int8_t* w4; const int8_t* wsc;     // wsc / bsc: stage-opening block only (1x1 shortcut conv)
     const int32_t* b0; const int32_t* b2; const int32_t* b4; const int32_t* bsc;  // offset-corrected, single class
-    int32_t nq, loq, hiq; uint32_t xorq;   // requant block input (int32 stream) -> body.0's input format
-    int32_t n1, lo1, hi1; uint32_t xor1;   // requant body.0 output -> body.2 input format
-    int32_t n2, lo2, hi2; uint32_t xor2;   // requant body.2 output -> body.4 input format
+    Requant rq;                            // requant block input (int32 stream) -> body.0's input format
+    Requant r1;                            // requant body.0 output -> body.2 input format
+    Requant r2;                            // requant body.2 output -> body.4 input format
     int32_t relu_a, relu_b, relu1;         // ReLU after body.0 / body.2 / the join
     int32_t acc_shl, res_shl;              // residual join: (conv << acc_shl) + (other << res_shl)
 };
@@ -360,8 +379,8 @@ constexpr size_t kChainXchgBytes = (size_t)512 * 2 * 2 * 3584;
 struct BChainBlk {
     const int8_t* wa; const int8_t* wb;    // first / second 3x3
     const int32_t* ba; const int32_t* bb;  // offset-corrected, single class (the LDS patches carry a biased-zero border)
-    int32_t nq, loq, hiq; uint32_t xorq;   // requant block input (int32 stream) -> the first conv's input format
-    int32_t n1, lo1, hi1; uint32_t xor1;   // requant first conv output -> second conv's input format
+    Requant rq;                            // requant block input (int32 stream) -> the first conv's input format
+    Requant r1;                            // requant first conv output -> second conv's input format
     int32_t relu_a, relu1;                 // ReLU after the first conv / after the join
     int32_t acc_shl, res_shl;              // join: (conv << acc_shl) + (stream << res_shl)
 };
@@ -408,14 +427,18 @@ struct IRArgs {
     const int8_t* wd4; const int32_t* bd4; // depthwise: dot4 image [E32/4][36 B], bias (+128*sum(w) for unsigned inputs) [E32]
     const int8_t* w4; const int32_t* b4;   // project [COUT_S][E32], offset-corrected bias [COUT_S]
     int32_t N, H, W, Ho, Wo, stride, R, G, tiles_per_img, E32;
+    // The two inner formats stay LOOSE fields here and in IRKArgs (r1() / r2() read them as records): as nested Requant members, whatever the kernels'
+    // spelling, the SGPR spill count of one generic instance here and two of fused_irk_kernel moves (profiles/argrec_kernel_resources.md)
     int32_t n1, lo1, hi1; uint32_t xor1;   // requant expand output -> depthwise input format
     int32_t n2, lo2, hi2; uint32_t xor2;   // requant depthwise output -> project input format
+    Requant r1() const { return {n1, lo1, hi1, xor1}; }
+    Requant r2() const { return {n2, lo2, hi2, xor2}; }
+    void set_r(const Requant& f1, const Requant& f2) { n1 = f1.n; lo1 = f1.lo; hi1 = f1.hi; xor1 = f1.bias_xor; n2 = f2.n; lo2 = f2.lo; hi2 = f2.hi; xor2 = f2.bias_xor; }
     int32_t relu_a, relu_b, relu0;         // ReLU after expand / depthwise / project
     int32_t acc_shl, res_shl, relu1;       // residual join
     int32_t* out32; QuantOut q[2];
     int32_t xp, off_patch, off_mid2, off_w;   // LDS layout (filled by launch_fused_ir)
-    // magic numbers (fast_div) for / W, / (H*W), / Wo, / (R*Wo): [magic, sh1, sh2]
-    uint32_t mW, mHW, mWo, mRWo; int32_t s1W, s2W, s1HW, s2HW, s1Wo, s2Wo, s1RWo, s2RWo;
+    FastDiv dW, dHW, dWo, dRWo;            // / W, / (H*W), / Wo, / (R*Wo)
 };
 
 // One launch for an inverted-residual block around a depthwise K x K, K = 5 / 7, pad K / 2 (f8_irk.hip): IRArgs with run-time channel counts.
@@ -427,15 +450,17 @@ struct IRKArgs {
     const int8_t* w4; const int32_t* b4;   // project [cout][E32], offset-corrected bias [cout]
     int32_t K, cin, cout;                  // depthwise kernel size; channel counts padded to 32
     int32_t N, H, W, Ho, Wo, stride, R, G, tiles_per_img, E32;   // R output rows per tile (tiles_per_img = ceil(Ho / R)) or G whole images (irk_config)
-    int32_t n1, lo1, hi1; uint32_t xor1;   // requant expand output -> depthwise input format (xor1 is also the patch's pad value)
+    int32_t n1, lo1, hi1; uint32_t xor1;   // requant expand output -> depthwise input format (xor1 is also the patch's pad value); loose: see IRArgs
     int32_t n2, lo2, hi2; uint32_t xor2;   // requant depthwise output -> project input format
+    Requant r1() const { return {n1, lo1, hi1, xor1}; }
+    Requant r2() const { return {n2, lo2, hi2, xor2}; }
+    void set_r(const Requant& f1, const Requant& f2) { n1 = f1.n; lo1 = f1.lo; hi1 = f1.hi; xor1 = f1.bias_xor; n2 = f2.n; lo2 = f2.lo; hi2 = f2.hi; xor2 = f2.bias_xor; }
     int32_t relu_a, relu_b, relu0;         // ReLU after expand / depthwise / project
     int32_t acc_shl, res_shl, relu1;       // residual join
     int32_t* out32; QuantOut q[2];
     int32_t xp, off_patch, off_mid2, off_w;   // LDS layout (filled by launch_fused_irk)
     int32_t QS;                            // P2 items per output row: ceil(Wo / 4)
-    // magic numbers (fast_div) for / W, / (H*W), / Wo, / (R*Wo), / QS, / (R*QS): [magic, sh1, sh2]
-    uint32_t mW, mHW, mWo, mRWo, mQS, mRQS; int32_t s1W, s2W, s1HW, s2HW, s1Wo, s2Wo, s1RWo, s2RWo, s1QS, s2QS, s1RQS, s2RQS;
+    FastDiv dW, dHW, dWo, dRWo, dQS, dRQS; // / W, / (H*W), / Wo, / (R*Wo), / QS, / (R*QS)
 };
 
 // One launch for a run of consecutive stride-1 inverted-residual blocks on one map, one workgroup per image (f8_irchain.hip): the int8 block
@@ -445,12 +470,12 @@ struct IRChainBlk {
     const int8_t* wd4; const int32_t* bd4; // depthwise: dot4 image [E32/4][36 B], bias (+128*sum(w) for unsigned inputs) [E32]
     const int8_t* w4; const int32_t* b4;   // project [cout][E32], offset-corrected bias [cout]
     int32_t cin, cout, E32;
-    int32_t n1, lo1, hi1; uint32_t xor1;   // requant expand output -> depthwise input format
-    int32_t n2, lo2, hi2; uint32_t xor2;   // requant depthwise output -> project input format
+    Requant r1;                            // requant expand output -> depthwise input format
+    Requant r2;                            // requant depthwise output -> project input format
     int32_t relu_a, relu_b, relu0;         // ReLU after expand / depthwise / project
     int32_t res;                           // the block joins its input (int32 stream): (acc << acc_shl) + (stream << res_shl), clamp, ReLU relu1
     int32_t acc_shl, res_shl, relu1;
-    int32_t nq, loq, hiq; uint32_t xorq;   // requant block output -> the NEXT block's expand input format (all blocks but the last)
+    Requant rq;                            // requant block output -> the NEXT block's expand input format (all blocks but the last)
     int32_t keep;                          // the next block joins this block's output: it stays in LDS as int32
 };
 constexpr int kIRChainMaxBlocks = 8;
@@ -462,7 +487,7 @@ struct IRChainArgs {
     const int32_t* xr;                     // ... int32 I32T, when blk[0].res
     int32_t N, H, W;
     int32_t* out32; QuantOut q[2];         // forms of the last block's output
-    uint32_t mW; int32_t s1W, s2W;         // magic numbers (fast_div) for / W
+    FastDiv dW;                            // / W
     int32_t xp, off_strm, off_patch, off_mid2, off_w;   // LDS layout (filled by launch_irchain)
 };
 
@@ -474,7 +499,7 @@ struct DwsArgs {
     int32_t N, H, W, P, Q, Cin, Cout, stride;   // H, W: input map; P, Q: output map; channel counts padded to 32
     int32_t R, tiles_per_img, px32;        // output rows per tile (dws_supported); tiles per image and the tile's padded pixel count (launch_dws)
     int32_t in_signed;                     // the depthwise conv reads a signed format (zero padding = 0, else the biased zero)
-    int32_t n1, lo1, hi1; uint32_t xor1;   // requant depthwise output (behind its ReLU) -> the 1x1's input format
+    Requant r1;                            // requant depthwise output (behind its ReLU) -> the 1x1's input format
     int32_t relu0;                         // ReLU after the 1x1
     QuantOut q[2];
     int32_t acc_ok, rq_int;                // both convs' accumulators bounded (conv_acc_bounded) / Options::requant_float == 0 (see DwArgs)
@@ -489,7 +514,7 @@ struct Dws7Args {
     int32_t N, H, W, Cin, Cout, stride;    // H, W: input map (7 * stride); channel counts padded to 32
     int32_t I, Z, px32;                    // images per workgroup (dws7_supported); slices of the output tiles and the mid tile's padded pixel count (launch_dws7)
     int32_t in_signed;                     // the depthwise conv reads a signed format (zero padding = 0, else the biased zero)
-    int32_t n1, lo1, hi1; uint32_t xor1;   // requant depthwise output (behind its ReLU) -> the 1x1's input format
+    Requant r1;                            // requant depthwise output (behind its ReLU) -> the 1x1's input format
     int32_t relu0;                         // ReLU after the 1x1
     int32_t pool;                          // the outputs are the forms of the block output SUMMED over its 49 pixels: out32 (I32T, one pixel per image), q (int8 [N][Cout])
     int32_t* out32;

@@ -81,15 +81,15 @@ __global__ void __launch_bounds__(NW * 64, (COUT_S <= 64 ? 4 : COUT_S <= 96 ? 3 
     // pixel index -> (image g, row, column) without hardware division (host magic numbers).  Row tiles (G == 1) have g == 0;
     // whole-image tiles (G > 1) have nvr == H.
     auto split_in = [&](int px, int& g, int& vr, int& c) {
-        g = a.G > 1 ? (int)fast_div((unsigned)px, a.mHW, a.s1HW, a.s2HW) : 0;
+        g = a.G > 1 ? (int)fast_div((unsigned)px, a.dHW) : 0;
         const int r = px - g * nvr * W;
-        vr = (int)fast_div((unsigned)r, a.mW, a.s1W, a.s2W);
+        vr = (int)fast_div((unsigned)r, a.dW);
         c = r - vr * W;
     };
     auto split_out = [&](int op, int& g, int& orow, int& ocol) {
-        g = a.G > 1 ? (int)fast_div((unsigned)op, a.mRWo, a.s1RWo, a.s2RWo) : 0;
+        g = a.G > 1 ? (int)fast_div((unsigned)op, a.dRWo) : 0;
         const int r = op - g * RWo;
-        orow = (int)fast_div((unsigned)r, a.mWo, a.s1Wo, a.s2Wo);
+        orow = (int)fast_div((unsigned)r, a.dWo);
         ocol = r - orow * Wo;
     };
 
@@ -395,8 +395,7 @@ __global__ void __launch_bounds__(NW * 64, (COUT_S <= 64 ? 4 : COUT_S <= 96 ? 3 
             unsigned d[4];
 #pragma unroll
             for (int gq = 0; gq < 4; ++gq)
-                d[gq] = pack4(requant1(y[gq][0], a.q[k].n, a.q[k].lo, a.q[k].hi), requant1(y[gq][1], a.q[k].n, a.q[k].lo, a.q[k].hi),
-                              requant1(y[gq][2], a.q[k].n, a.q[k].lo, a.q[k].hi), requant1(y[gq][3], a.q[k].n, a.q[k].lo, a.q[k].hi)) ^ a.q[k].bias_xor;
+                d[gq] = requant_pack4(y[gq][0], y[gq][1], y[gq][2], y[gq][3], a.q[k]);
             auto s0 = __builtin_amdgcn_permlane32_swap(d[0], d[2], false, false);
             auto s1 = __builtin_amdgcn_permlane32_swap(d[1], d[3], false, false);
             if (ok) {
@@ -473,9 +472,8 @@ static hipError_t launch_ir_t(const IRArgs& a, int lds, hipStream_t s) {
 // FQ: ReLU + right shift into unsigned 8-bit after the expand AND the depthwise conv (the VALU depthwise path keeps its general epilogue)
 // 1: through the float converter (bounded accumulators, shifts <= 16); 2: the integer form (option requant_float = 0, or where 1 is not provably exact)
 int fused_ir_inst(const IRArgs& a, int coutS) {
-    const bool fqf = a.relu_a && a.relu_b && a.n1 > 0 && a.n2 > 0 && a.n1 <= 30 && a.n2 <= 30 && a.lo1 == 0 && a.lo2 == 0 && a.hi1 == 255 && a.hi2 == 255 &&
-                     a.xor1 == 0x80808080u && a.xor2 == 0x80808080u && coutS <= 96;
-    return !fqf ? 0 : ((a.rq_int || !a.acc_ok || a.n1 > kRequantU8MaxShift || a.n2 > kRequantU8MaxShift) ? 2 : 1);
+    const bool fqf = a.relu_a && a.relu_b && a.r1().u8_shr() && a.r2().u8_shr() && coutS <= 96;
+    return !fqf ? 0 : ((a.rq_int || !a.acc_ok || !a.r1().u8_float() || !a.r2().u8_float()) ? 2 : 1);
 }
 
 int fused_ir_kernel_name(char* buf, size_t cap, int cinS, int coutS, int inst) {

@@ -55,7 +55,7 @@ __global__ void __launch_bounds__(NW * 64, 1) irchain_kernel(const IRChainArgs a
     const int mid_ct = xp * 32;                            // ... of mid2
     const int n0 = blockIdx.x;
     auto split_px = [&](int px, int& r, int& c) {
-        r = (int)fast_div((unsigned)px, a.mW, a.s1W, a.s2W);
+        r = (int)fast_div((unsigned)px, a.dW);
         c = px - r * W;
     };
 
@@ -73,7 +73,7 @@ __global__ void __launch_bounds__(NW * 64, 1) irchain_kernel(const IRChainArgs a
         const v4i zv = {(int)xor1, (int)xor1, (int)xor1, (int)xor1};
         for (int o = tid * 16; o < 2 * pct; o += NT * 16) *(v4i*)(patch + o) = zv;
     };
-    fill_border(a.blk[0].xor1);
+    fill_border(a.blk[0].r1.bias_xor);
     if (a.blk[0].res) {                                    // ---- block 0 joins the int32 input: I32T -> strm (accumulator layout)
         const int n = (a.blk[0].cin >> 5) * npt * 256;
         for (int i = tid; i < n; i += NT) {
@@ -138,8 +138,8 @@ __global__ void __launch_bounds__(NW * 64, 1) irchain_kernel(const IRChainArgs a
             const bool ok = opx < HW;
             const int m = n0 * HW + (ok ? opx : 0);
             const int floor0 = vgpr(B.relu0 ? 0 : INT32_MIN), floor1 = vgpr(B.relu1 ? 0 : -2147483647);
-            const int acc_shl = vgpr(B.acc_shl), res_shl = vgpr(B.res_shl), loq = vgpr(B.loq), hiq = vgpr(B.hiq);
-            const unsigned xorq = (unsigned)vgpr((int)B.xorq);
+            const int acc_shl = vgpr(B.acc_shl), res_shl = vgpr(B.res_shl), loq = vgpr(B.rq.lo), hiq = vgpr(B.rq.hi);
+            const unsigned xorq = (unsigned)vgpr((int)B.rq.bias_xor);
     #pragma unroll
             for (int jj = 0; jj < NJ; ++jj) {
                 const int j = ch + nch * jj;
@@ -167,8 +167,8 @@ __global__ void __launch_bounds__(NW * 64, 1) irchain_kernel(const IRChainArgs a
                     unsigned d[4];
     #pragma unroll
                     for (int gq = 0; gq < 4; ++gq)
-                        d[gq] = pack4(requant1(y[gq][0], B.nq, loq, hiq), requant1(y[gq][1], B.nq, loq, hiq),
-                                      requant1(y[gq][2], B.nq, loq, hiq), requant1(y[gq][3], B.nq, loq, hiq)) ^ xorq;
+                        d[gq] = pack4(requant1(y[gq][0], B.rq.n, loq, hiq), requant1(y[gq][1], B.rq.n, loq, hiq),
+                                      requant1(y[gq][2], B.rq.n, loq, hiq), requant1(y[gq][3], B.rq.n, loq, hiq)) ^ xorq;
                     auto s0 = __builtin_amdgcn_permlane32_swap(d[0], d[2], false, false);
                     auto s1 = __builtin_amdgcn_permlane32_swap(d[1], d[3], false, false);
                     if (ok) *(v4i*)(X + ((size_t)j * xp + opx) * 32 + lh * 16) = v4i{(int)s0[0], (int)s0[1], (int)s1[0], (int)s1[1]};
@@ -186,8 +186,7 @@ __global__ void __launch_bounds__(NW * 64, 1) irchain_kernel(const IRChainArgs a
                     unsigned d[4];
     #pragma unroll
                     for (int gq = 0; gq < 4; ++gq)
-                        d[gq] = pack4(requant1(y[gq][0], Q.n, Q.lo, Q.hi), requant1(y[gq][1], Q.n, Q.lo, Q.hi),
-                                      requant1(y[gq][2], Q.n, Q.lo, Q.hi), requant1(y[gq][3], Q.n, Q.lo, Q.hi)) ^ Q.bias_xor;
+                        d[gq] = requant_pack4(y[gq][0], y[gq][1], y[gq][2], y[gq][3], Q);
                     auto s0 = __builtin_amdgcn_permlane32_swap(d[0], d[2], false, false);
                     auto s1 = __builtin_amdgcn_permlane32_swap(d[1], d[3], false, false);
                     if (ok) *(v4i*)(Q.ptr + (size_t)m * cout + cot + 16 * lh) = v4i{(int)s0[0], (int)s0[1], (int)s1[0], (int)s1[1]};
@@ -202,10 +201,10 @@ __global__ void __launch_bounds__(NW * 64, 1) irchain_kernel(const IRChainArgs a
         const int nchunk = (B.E32 + 63) >> 6;
         // the generic instance's inner requantisations (FQ == 0) / the float converter's scales (FQ == 1)
         [[maybe_unused]] const int floor_a = vgpr(B.relu_a ? 0 : INT32_MIN), floor_b = vgpr(B.relu_b ? 0 : INT32_MIN);
-        [[maybe_unused]] const int lo1 = vgpr(B.lo1), hi1 = vgpr(B.hi1), lo2 = vgpr(B.lo2), hi2 = vgpr(B.hi2);
-        [[maybe_unused]] const unsigned xor1 = (unsigned)vgpr((int)B.xor1), xor2 = (unsigned)vgpr((int)B.xor2);
-        [[maybe_unused]] const float sc1 = FQ == 1 ? requant_u8_scale(B.n1) : 0.0f, sc2 = FQ == 1 ? requant_u8_scale(B.n2) : 0.0f;
-        if (k > 0) fill_border(B.xor1);                    // (the previous block's last P2 is behind a barrier)
+        [[maybe_unused]] const int lo1 = vgpr(B.r1.lo), hi1 = vgpr(B.r1.hi), lo2 = vgpr(B.r2.lo), hi2 = vgpr(B.r2.hi);
+        [[maybe_unused]] const unsigned xor1 = (unsigned)vgpr((int)B.r1.bias_xor), xor2 = (unsigned)vgpr((int)B.r2.bias_xor);
+        [[maybe_unused]] const float sc1 = FQ == 1 ? requant_u8_scale(B.r1.n) : 0.0f, sc2 = FQ == 1 ? requant_u8_scale(B.r2.n) : 0.0f;
+        if (k > 0) fill_border(B.r1.bias_xor);                    // (the previous block's last P2 is behind a barrier)
 #pragma unroll
         for (int jj = 0; jj < NJ; ++jj)
 #pragma unroll
@@ -242,12 +241,12 @@ __global__ void __launch_bounds__(NW * 64, 1) irchain_kernel(const IRChainArgs a
 #pragma unroll
                 for (int gq = 0; gq < 4; ++gq) {
                     if constexpr (FQ) {
-                        d[gq] = requant_u8x4_sel<FQ == 2 ? 2 : 1>(acc[4 * gq], acc[4 * gq + 1], acc[4 * gq + 2], acc[4 * gq + 3], B.n1, sc1) ^ 0x80808080u;
+                        d[gq] = requant_u8x4_sel<FQ == 2 ? 2 : 1>(acc[4 * gq], acc[4 * gq + 1], acc[4 * gq + 2], acc[4 * gq + 3], B.r1.n, sc1) ^ 0x80808080u;
                     } else {
                         const v4i bv = *(const v4i*)(wb + off_b0 + (i * 32 + 8 * gq + 4 * lh) * 4);
                         int y[4];
 #pragma unroll
-                        for (int q = 0; q < 4; ++q) y[q] = requant1(max((int)((unsigned)acc[4 * gq + q] + (unsigned)bv[q]), floor_a), B.n1, lo1, hi1);
+                        for (int q = 0; q < 4; ++q) y[q] = requant1(max((int)((unsigned)acc[4 * gq + q] + (unsigned)bv[q]), floor_a), B.r1.n, lo1, hi1);
                         d[gq] = pack4(y[0], y[1], y[2], y[3]) ^ xor1;
                     }
                 }
@@ -299,10 +298,10 @@ __global__ void __launch_bounds__(NW * 64, 1) irchain_kernel(const IRChainArgs a
 #pragma unroll
                 for (int gq = 0; gq < 4; ++gq) {
                     if constexpr (FQ)
-                        d[gq] = requant_u8x4_sel<FQ == 2 ? 2 : 1>(acc2[4 * gq], acc2[4 * gq + 1], acc2[4 * gq + 2], acc2[4 * gq + 3], B.n2, sc2) ^ 0x80808080u;
+                        d[gq] = requant_u8x4_sel<FQ == 2 ? 2 : 1>(acc2[4 * gq], acc2[4 * gq + 1], acc2[4 * gq + 2], acc2[4 * gq + 3], B.r2.n, sc2) ^ 0x80808080u;
                     else
-                        d[gq] = pack4(requant1(max(acc2[4 * gq], floor_b), B.n2, lo2, hi2), requant1(max(acc2[4 * gq + 1], floor_b), B.n2, lo2, hi2),
-                                      requant1(max(acc2[4 * gq + 2], floor_b), B.n2, lo2, hi2), requant1(max(acc2[4 * gq + 3], floor_b), B.n2, lo2, hi2)) ^ xor2;
+                        d[gq] = pack4(requant1(max(acc2[4 * gq], floor_b), B.r2.n, lo2, hi2), requant1(max(acc2[4 * gq + 1], floor_b), B.r2.n, lo2, hi2),
+                                      requant1(max(acc2[4 * gq + 2], floor_b), B.r2.n, lo2, hi2), requant1(max(acc2[4 * gq + 3], floor_b), B.r2.n, lo2, hi2)) ^ xor2;
                 }
                 auto s0 = __builtin_amdgcn_permlane32_swap(d[0], d[2], false, false);
                 auto s1 = __builtin_amdgcn_permlane32_swap(d[1], d[3], false, false);
@@ -378,9 +377,8 @@ int irchain_inst(const IRChainArgs& a) {
     int cin_max = 0, cout_max = 0;
     for (int k = 0; k < a.nblk; ++k) {
         const IRChainBlk& B = a.blk[k];
-        fqf = fqf && B.relu_a && B.relu_b && B.n1 > 0 && B.n2 > 0 && B.n1 <= 30 && B.n2 <= 30 && B.lo1 == 0 && B.lo2 == 0 && B.hi1 == 255 && B.hi2 == 255 &&
-              B.xor1 == 0x80808080u && B.xor2 == 0x80808080u;
-        small = small && B.n1 <= kRequantU8MaxShift && B.n2 <= kRequantU8MaxShift;
+        fqf = fqf && B.relu_a && B.relu_b && B.r1.u8_shr() && B.r2.u8_shr();
+        small = small && B.r1.u8_float() && B.r2.u8_float();
         cin_max = cin_max > B.cin ? cin_max : B.cin; cout_max = cout_max > B.cout ? cout_max : B.cout;
     }
     const int fq = !fqf ? 0 : ((a.rq_int || !a.acc_ok || !small) ? 2 : 1);

@@ -144,15 +144,15 @@ __global__ void __launch_bounds__(IRK_NT, 2) fused_irk_kernel(const IRKArgs a) {
     // pixel index -> (image g, row, column) without hardware division (host magic numbers).  Row tiles (G == 1) have g == 0;
     // whole-image tiles (G > 1) have nvr == H.
     auto split_in = [&](int px, int& g, int& vr, int& c) {
-        g = a.G > 1 ? (int)fast_div((unsigned)px, a.mHW, a.s1HW, a.s2HW) : 0;
+        g = a.G > 1 ? (int)fast_div((unsigned)px, a.dHW) : 0;
         const int r = px - g * nvr * W;
-        vr = (int)fast_div((unsigned)r, a.mW, a.s1W, a.s2W);
+        vr = (int)fast_div((unsigned)r, a.dW);
         c = r - vr * W;
     };
     auto split_out = [&](int op, int& g, int& orow, int& ocol) {
-        g = a.G > 1 ? (int)fast_div((unsigned)op, a.mRWo, a.s1RWo, a.s2RWo) : 0;
+        g = a.G > 1 ? (int)fast_div((unsigned)op, a.dRWo) : 0;
         const int r = op - g * RWo;
-        orow = (int)fast_div((unsigned)r, a.mWo, a.s1Wo, a.s2Wo);
+        orow = (int)fast_div((unsigned)r, a.dWo);
         ocol = r - orow * Wo;
     };
 
@@ -290,9 +290,9 @@ __global__ void __launch_bounds__(IRK_NT, 2) fused_irk_kernel(const IRKArgs a) {
                 int rest = it >> 3;
                 const int ct = rest >= npg ? 1 : 0;
                 rest -= ct * npg;
-                const int g = a.G > 1 ? (int)fast_div((unsigned)rest, a.mRQS, a.s1RQS, a.s2RQS) : 0;
+                const int g = a.G > 1 ? (int)fast_div((unsigned)rest, a.dRQS) : 0;
                 const int r2 = rest - g * RQS;
-                const int orow = (int)fast_div((unsigned)r2, a.mQS, a.s1QS, a.s2QS);
+                const int orow = (int)fast_div((unsigned)r2, a.dQS);
                 const int q0 = (r2 - orow * QS) * IRK_PIX;
                 const char* pp = patch + (size_t)ct * pct + (size_t)((g * PR + orow * s) * PW + q0 * s) * 32 + cq * 4;
                 const unsigned* wq = (const unsigned*)(wb + OFF_DW) + (ct * 8 + cq) * (K * GK * 4);
@@ -363,8 +363,7 @@ __global__ void __launch_bounds__(IRK_NT, 2) fused_irk_kernel(const IRKArgs a) {
             unsigned d[4];
 #pragma unroll
             for (int gq = 0; gq < 4; ++gq)
-                d[gq] = pack4(requant1(y[gq][0], a.q[k].n, a.q[k].lo, a.q[k].hi), requant1(y[gq][1], a.q[k].n, a.q[k].lo, a.q[k].hi),
-                              requant1(y[gq][2], a.q[k].n, a.q[k].lo, a.q[k].hi), requant1(y[gq][3], a.q[k].n, a.q[k].lo, a.q[k].hi)) ^ a.q[k].bias_xor;
+                d[gq] = requant_pack4(y[gq][0], y[gq][1], y[gq][2], y[gq][3], a.q[k]);
             auto s0 = __builtin_amdgcn_permlane32_swap(d[0], d[2], false, false);
             auto s1 = __builtin_amdgcn_permlane32_swap(d[1], d[3], false, false);
             if (ok) {
@@ -438,9 +437,7 @@ static hipError_t launch_irk_t(const IRKArgs& a, int lds, hipStream_t s) {
 // 2: ReLU + right shift into unsigned 8-bit after the expand AND the depthwise conv, in integer operations (whatever requant_float says: the
 // general depthwise launches have no float-converter form either); 0: any format
 int irk_inst(const IRKArgs& a) {
-    const bool fq = a.relu_a && a.relu_b && a.n1 > 0 && a.n2 > 0 && a.n1 <= 30 && a.n2 <= 30 && a.lo1 == 0 && a.lo2 == 0 && a.hi1 == 255 && a.hi2 == 255 &&
-                    a.xor1 == 0x80808080u && a.xor2 == 0x80808080u;
-    return fq ? 2 : 0;
+    return (a.relu_a && a.relu_b && a.r1().u8_shr() && a.r2().u8_shr()) ? 2 : 0;
 }
 
 int irk_kernel_name(char* buf, size_t cap, int K, int coutS, int inst) {

@@ -37,8 +37,8 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, v16i (&acc)[TCO
         // border class of this lane's pixel (which taps fell outside the image)
         const int32_t* bias = a.bias;
         if (a.ncc > 0 && ok) {
-            const int n = (int)fast_div((unsigned)m, a.mPQ, a.s1PQ, a.s2PQ), rem = m - n * a.PQ;
-            const int p = (int)fast_div((unsigned)rem, a.mQ, a.s1Q, a.s2Q), q = rem - p * a.Q;
+            const int n = (int)fast_div((unsigned)m, a.dPQ), rem = m - n * a.PQ;
+            const int p = (int)fast_div((unsigned)rem, a.dQ), q = rem - p * a.Q;
             bias += (size_t)((int)a.rowcls[p] * a.ncc + (int)a.colcls[q]) * (size_t)a.coutP;
         }
 #pragma unroll
@@ -181,8 +181,8 @@ __global__ void __launch_bounds__(256, BM * BN >= 128 * 128 ? (DUAL ? 2 : HAS_RE
         xh0[i] = xw0[i] = -(1 << 24);
         xbase[i] = kOOB;
         if (idx < XCH && m < a.M) {
-            const int n = (int)fast_div((unsigned)m, a.mPQ, a.s1PQ, a.s2PQ), rem = m - n * a.PQ;
-            const int p = (int)fast_div((unsigned)rem, a.mQ, a.s1Q, a.s2Q), q = rem - p * a.Q;
+            const int n = (int)fast_div((unsigned)m, a.dPQ), rem = m - n * a.PQ;
+            const int p = (int)fast_div((unsigned)rem, a.dQ), q = rem - p * a.Q;
             xbase[i] = (unsigned)(n * a.sN + p * a.sP + q * a.sQ + a.origin + chunk * 16);
             xh0[i] = p * a.stride - a.pad;
             xw0[i] = q * a.stride - a.pad;
@@ -208,8 +208,8 @@ __global__ void __launch_bounds__(256, BM * BN >= 128 * 128 ? (DUAL ? 2 : HAS_RE
             const int m = m0 + row;
             xbase2[i] = kOOB;
             if (idx < XCH && m < a.M) {
-                const int n = (int)fast_div((unsigned)m, a.mPQ, a.s1PQ, a.s2PQ), rem = m - n * a.PQ;
-                const int p = (int)fast_div((unsigned)rem, a.mQ, a.s1Q, a.s2Q), q = rem - p * a.Q;
+                const int n = (int)fast_div((unsigned)m, a.dPQ), rem = m - n * a.PQ;
+                const int p = (int)fast_div((unsigned)rem, a.dQ), q = rem - p * a.Q;
                 xbase2[i] = (unsigned)(n * a.sN2 + p * a.sP2 + q * a.sQ2 + chunk * 16);
             }
         }
@@ -466,8 +466,7 @@ __global__ void __launch_bounds__(256) dwconv3x3_kernel(const DwArgs a) {
         for (int k = 0; k < 2; ++k)
             if (a.q[k].ptr)
                 *(unsigned*)(a.q[k].ptr + o) =
-                    pack4(requant1(acc[0], a.q[k].n, a.q[k].lo, a.q[k].hi), requant1(acc[1], a.q[k].n, a.q[k].lo, a.q[k].hi),
-                          requant1(acc[2], a.q[k].n, a.q[k].lo, a.q[k].hi), requant1(acc[3], a.q[k].n, a.q[k].lo, a.q[k].hi)) ^ a.q[k].bias_xor;
+                    requant_pack4(acc[0], acc[1], acc[2], acc[3], a.q[k]);
     }
 }
 
@@ -551,8 +550,7 @@ __global__ void __launch_bounds__(256) dwconv3x3_dot4_kernel(const DwArgs a) {
 #pragma unroll
             for (int f = 0; f < 2; ++f)
                 if (a.q[f].ptr)
-                    outw[j][f][k] = pack4(requant1(acc[0], a.q[f].n, a.q[f].lo, a.q[f].hi), requant1(acc[1], a.q[f].n, a.q[f].lo, a.q[f].hi),
-                                          requant1(acc[2], a.q[f].n, a.q[f].lo, a.q[f].hi), requant1(acc[3], a.q[f].n, a.q[f].lo, a.q[f].hi)) ^ a.q[f].bias_xor;
+                    outw[j][f][k] = requant_pack4(acc[0], acc[1], acc[2], acc[3], a.q[f]);
         }
     }
 #pragma unroll
@@ -616,8 +614,7 @@ __global__ void __launch_bounds__(256) maxpool_kernel(const PoolArgs a) {
             for (int k = 0; k < 2; ++k)
                 if (a.q[k].ptr)
                     *(unsigned*)(a.q[k].ptr + o) =
-                        pack4(requant1(mx[0], a.q[k].n, a.q[k].lo, a.q[k].hi), requant1(mx[1], a.q[k].n, a.q[k].lo, a.q[k].hi),
-                              requant1(mx[2], a.q[k].n, a.q[k].lo, a.q[k].hi), requant1(mx[3], a.q[k].n, a.q[k].lo, a.q[k].hi)) ^ a.q[k].bias_xor;
+                        requant_pack4(mx[0], mx[1], mx[2], mx[3], a.q[k]);
         }
     }
 }
@@ -693,8 +690,7 @@ __global__ void __launch_bounds__(256) avgpool_kernel(const AvgArgs a) {
     for (int k = 0; k < 2; ++k)
         if (a.q[k].ptr)
             *(unsigned*)(a.q[k].ptr + o) =
-                pack4(requant1((int)t[0], a.q[k].n, a.q[k].lo, a.q[k].hi), requant1((int)t[1], a.q[k].n, a.q[k].lo, a.q[k].hi),
-                      requant1((int)t[2], a.q[k].n, a.q[k].lo, a.q[k].hi), requant1((int)t[3], a.q[k].n, a.q[k].lo, a.q[k].hi)) ^ a.q[k].bias_xor;
+                requant_pack4((int)t[0], (int)t[1], (int)t[2], (int)t[3], a.q[k]);
 }
 
 // Stand-alone residual join (only when it cannot ride in a conv epilogue) and stand-alone requant
@@ -720,8 +716,7 @@ __global__ void __launch_bounds__(256) add_kernel(const AddArgs a) {
         for (int k = 0; k < 2; ++k)
             if (a.q[k].ptr)
                 *(unsigned*)(a.q[k].ptr + (size_t)m * a.Cs + c) =
-                    pack4(requant1(y[0], a.q[k].n, a.q[k].lo, a.q[k].hi), requant1(y[1], a.q[k].n, a.q[k].lo, a.q[k].hi),
-                          requant1(y[2], a.q[k].n, a.q[k].lo, a.q[k].hi), requant1(y[3], a.q[k].n, a.q[k].lo, a.q[k].hi)) ^ a.q[k].bias_xor;
+                    requant_pack4(y[0], y[1], y[2], y[3], a.q[k]);
     }
 }
 

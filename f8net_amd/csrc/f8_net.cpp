@@ -336,23 +336,9 @@ int consumer_format(const Tensor& src, const f8_conv_desc& d, int* n, const char
     return 0;
 }
 
-// round-up magic for unsigned division by d >= 1:  n / d == (t + ((n - t) >> sh1)) >> sh2,
-// t = mulhi(n, magic); exact for all 32-bit n (Granlund-Montgomery, branch-free form)
-void make_magic(uint32_t d, uint32_t* magic, int32_t* sh1, int32_t* sh2) {
-    int l = 0;
-    while ((1ull << l) < d) ++l;                       // l = ceil(log2 d)
-    *magic = (uint32_t)(((1ull << 32) * ((1ull << l) - d)) / d + 1);
-    *sh1 = l < 1 ? l : 1;
-    *sh2 = l > 1 ? l - 1 : 0;
-}
-
 int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
 
-void set_q(QuantOut& q, const Form& f) {      // the format of an int8 output (its pointer: run_step)
-    q.n = f.n;
-    q.lo = f.sgn ? -127 : 0; q.hi = f.sgn ? 127 : 255;
-    q.bias_xor = f.sgn ? 0u : 0x80808080u;      // unsigned int8 tensors are stored biased (x ^ 0x80)
-}
+void set_q(QuantOut& q, const Form& f) { static_cast<Requant&>(q) = Requant::of(f.n, f.sgn); }   // the format of an int8 output (its pointer: run_step)
 
 }  // namespace
 
@@ -1080,8 +1066,8 @@ static void pack_deconv_weights(f8_net* net, Node& nd) {
             };
             grid(rh, dst.H, &p.a0, &p.A);
             grid(rw, dst.W, &p.c0, &p.Cn);
-            make_magic((uint32_t)std::max(1, p.A * p.Cn), &p.mAC, &p.s1AC, &p.s2AC);
-            make_magic((uint32_t)std::max(1, p.Cn), &p.mC, &p.s1C, &p.s2C);
+            p.dAC = fast_divisor((uint32_t)std::max(1, p.A * p.Cn));
+            p.dC = fast_divisor((uint32_t)std::max(1, p.Cn));
             p.w_off = (uint32_t)off;
             const size_t kp = (size_t)p.Th * p.Tw * CK;
             int8_t* wp = (int8_t*)net->wblob.data() + nd.w_off + off;
@@ -3055,7 +3041,7 @@ static int layout_arena(f8_net* net, int max_batch) {
 }
 
 // ------------------------------------------------------------------------------ bind
-// Fills st.args with every launch argument the plan decides: geometry, magic divisors, consumer formats, ReLU flags, join shifts, the bounds
+// Fills st.args with every launch argument the plan decides: geometry, divisors (FastDiv), consumer formats (Requant), ReLU flags, join shifts, the bounds
 // of the float requantisation, output formats; chooses the instance the launcher starts (st.inst: the family's *_inst, f8_internal.h) and
 // names it (st.kernel).  Weight pointers are set once the weights are on the device (f8_net_upload binds again).  What a run decides is run_step's.
 static int bind_step(f8_net* net, Step& st) {
@@ -3065,12 +3051,11 @@ static int bind_step(f8_net* net, Step& st) {
     auto W8 = [&](size_t off) { return net->d_w ? (const int8_t*)(net->d_w + off) : nullptr; };
     auto B32 = [&](size_t off) { return (const int32_t*)W8(off); };
     // the int8 input format of conv c: shift from its source tensor, clamp bounds, storage bias (unsigned formats are stored x ^ 0x80)
-    auto fmt = [&](const Node& c, int32_t* n, int32_t* lo = nullptr, int32_t* hi = nullptr, uint32_t* x_or = nullptr) {
+    auto fmt = [&](const Node& c) {
         int v = 0;
         const int r = consumer_format(T[c.a], c.cd, &v, "finalize");
         if (!rc) rc = r;
-        *n = v;
-        if (lo) { *lo = c.cd.input_signed ? -127 : 0; *hi = c.cd.input_signed ? 127 : 255; *x_or = c.cd.input_signed ? 0u : 0x80808080u; }
+        return Requant::of(v, c.cd.input_signed != 0);
     };
     auto out_formats = [&](QuantOut q[2]) {
         if (st.out.t < 0 || st.dense) return;
@@ -3087,14 +3072,13 @@ static int bind_step(f8_net* net, Step& st) {
         a.wd4 = W8(nb.rc_off); a.bd4 = B32(nb.cc_off);           // the depthwise conv's dot4 image; bias + 128 * sum(w) for unsigned inputs
         a.w4 = W8(nd.w_off); a.b4 = B32(nd.b_off);
         a.H = x.H; a.W = x.W; a.Ho = oT.H; a.Wo = oT.W; a.stride = nb.cd.stride; a.R = r.R; a.G = r.G; a.E32 = na.coutP;
-        fmt(nb, &a.n1, &a.lo1, &a.hi1, &a.xor1);
-        fmt(nd, &a.n2, &a.lo2, &a.hi2, &a.xor2);
+        a.set_r(fmt(nb), fmt(nd));
         a.relu_a = na.cd.relu; a.relu_b = nb.cd.relu; a.relu0 = st.relu0;
         a.acc_shl = st.acc_shl; a.res_shl = st.res_shl; a.relu1 = st.relu1;
-        make_magic((uint32_t)x.W, &a.mW, &a.s1W, &a.s2W);
-        make_magic((uint32_t)(x.H * x.W), &a.mHW, &a.s1HW, &a.s2HW);
-        make_magic((uint32_t)oT.W, &a.mWo, &a.s1Wo, &a.s2Wo);
-        make_magic((uint32_t)(r.R * oT.W), &a.mRWo, &a.s1RWo, &a.s2RWo);
+        a.dW = fast_divisor((uint32_t)x.W);
+        a.dHW = fast_divisor((uint32_t)(x.H * x.W));
+        a.dWo = fast_divisor((uint32_t)oT.W);
+        a.dRWo = fast_divisor((uint32_t)(r.R * oT.W));
         out_formats(a.q);
     };
     // ... DwsArgs and Dws7Args (depthwise nb -> 1x1 nd over block input x); the depthwise weights are each case's own image
@@ -3102,7 +3086,7 @@ static int bind_step(f8_net* net, Step& st) {
         a.w1 = W8(nd.wf_off); a.b1 = B32(nd.b_off);
         a.H = x.H; a.W = x.W; a.Cin = x.Cs; a.Cout = nd.coutP; a.stride = nb.cd.stride;
         a.in_signed = nb.cd.input_signed;
-        fmt(nd, &a.n1, &a.lo1, &a.hi1, &a.xor1);
+        a.r1 = fmt(nd);
         a.relu0 = st.relu0;
         a.acc_ok = conv_acc_bounded(nb) && conv_acc_bounded(nd); a.rq_int = rq_int;
         out_formats(a.q);
@@ -3111,8 +3095,8 @@ static int bind_step(f8_net* net, Step& st) {
     auto bind_basic_block = [&](BChainBlk& B, const Node& hk, const Node& c1, const Node& c2) {
         B.wa = W8(c1.wf_off); B.wb = W8(c2.wf_off);
         B.ba = B32(c1.b_off); B.bb = B32(c2.b_off);
-        fmt(c1, &B.nq, &B.loq, &B.hiq, &B.xorq);
-        fmt(c2, &B.n1, &B.lo1, &B.hi1, &B.xor1);
+        B.rq = fmt(c1);
+        B.r1 = fmt(c2);
         B.relu_a = c1.cd.relu; B.relu1 = ND[hk.fused_add].relu;
     };
     char kb[192] = "";
@@ -3131,8 +3115,8 @@ static int bind_step(f8_net* net, Step& st) {
             a.w = W8(nd.w_off); a.w_bytes = (uint32_t)((size_t)nd.coutP * nd.ktot);
             a.bias = B32(nd.b_off);
             a.PQ = oT.H * oT.W; a.Q = oT.W;
-            make_magic((uint32_t)a.PQ, &a.mPQ, &a.s1PQ, &a.s2PQ);
-            make_magic((uint32_t)a.Q, &a.mQ, &a.s1Q, &a.s2Q);
+            a.dPQ = fast_divisor((uint32_t)a.PQ);
+            a.dQ = fast_divisor((uint32_t)a.Q);
             a.stride = d.stride; a.kh = d.kernel; a.CK = nd.ck; a.ktot = nd.ktot; a.coutP = nd.coutP;
             a.ncc = nd.ncc;
             if (nd.ncc > 0) { a.rowcls = (const uint8_t*)W8(nd.rc_off); a.colcls = (const uint8_t*)W8(nd.cc_off); }
@@ -3186,11 +3170,11 @@ static int bind_step(f8_net* net, Step& st) {
                 a.relu1 = nd.cd.relu ? 1 : 0; a.Cs = oT.Cs;
                 a.wd = W8(hb.w_off); a.bd = B32(hb.cc_off);
                 a.w1 = W8(nd.w_off); a.b1 = B32(nd.b_off);
-                fmt(hb, &a.na); fmt(nd, &a.nb);
+                a.na = fmt(hb).n; a.nb = fmt(nd).n;
                 a.Pc = oT.H; a.Qc = oT.W; a.P = oT.H; a.Q = oT.W;
                 a.relu0 = 1;
                 a.acc_ok = conv_acc_bounded(hc) && conv_acc_bounded(hb) && conv_acc_bounded(nd); a.rq_int = rq_int || !a.acc_ok;
-                a.rC = sT.C; a.rH = sT.H; a.rW = sT.W; a.xor8 = sF.sgn ? 0u : 0x80808080u;
+                a.rC = sT.C; a.rH = sT.H; a.rW = sT.W; a.xor8 = Requant::of(0, sF.sgn).bias_xor;
             } else {
                 const Tensor& cT = T[nd.out]; const Tensor& oT = T[ND[nd.sp_pool].out];
                 a.Pc = cT.H; a.Qc = cT.W; a.P = oT.H; a.Q = oT.W;
@@ -3218,8 +3202,8 @@ static int bind_step(f8_net* net, Step& st) {
             }
             a.H = x.H; a.W = x.W; a.C = na.cd.cin; a.MID = na.cd.cout; a.R = r.R;
             a.tiles_per_img = opener ? (x.H / 2) / r.R : (x.H + r.R - 1) / r.R;
-            fmt(nb, &a.n1, &a.lo1, &a.hi1, &a.xor1);
-            fmt(ng, &a.n2, &a.lo2, &a.hi2, &a.xor2);
+            a.r1 = fmt(nb);
+            a.r2 = fmt(ng);
             a.relu_a = na.cd.relu; a.relu_b = nb.cd.relu;
             a.acc_shl = st.acc_shl; a.res_shl = st.res_shl; a.relu1 = st.relu1;
             out_formats(a.q);
@@ -3237,13 +3221,13 @@ static int bind_step(f8_net* net, Step& st) {
             a.w2 = W8(w2); a.w2_bytes = (uint32_t)((size_t)nd.coutP * nd.ktot);
             a.b0 = B32(na.b_off); a.b2 = B32(nd.b_off);
             a.H = x.H; a.W = x.W; a.C = na.cd.cin; a.MID = na.cd.cout;
-            fmt(nd, &a.n1, &a.lo1, &a.hi1, &a.xor1);
+            a.r1 = fmt(nd);
             a.relu_a = na.cd.relu; a.relu_b = nd.cd.relu;
             out_formats(a.q);
             if (opener) {                                 // body.0 + body.2 of a stride-2 opening block on f8_opener.hip (P12); q[0] = mid2
                 a.COUT = 4 * na.cd.cout; a.R = nd.blk.R;
                 a.tiles_per_img = (x.H / 2 + a.R - 1) / a.R;
-                a.n2 = a.q[0].n; a.lo2 = a.q[0].lo; a.hi2 = a.q[0].hi; a.xor2 = a.q[0].bias_xor;      // mid2's one form = body.4's input format
+                a.r2 = a.q[0];                                // mid2's one form = body.4's input format
                 a.stride2 = 1; a.p12only = 1; a.acc_ok = conv_acc_bounded(na) && conv_acc_bounded(nd); a.rq_int = rq_int;
                 fused_opener_kernel_name(kb, sizeof kb, a, st.inst = fused_opener_inst(a, opt.opener_stg));
             } else fused_p12_kernel_name(kb, sizeof kb, a);
@@ -3265,7 +3249,7 @@ static int bind_step(f8_net* net, Step& st) {
                 // identity: (body.4 << acc_shl) + (block input << res_shl); opening block: (shortcut << acc_shl) + (body.4 << res_shl)
                 join_shifts(T[hh.out].fl - (r.sc >= 0 ? T[ng.out].fl : T[ND[r.b0].a].fl), &B.acc_shl, &B.res_shl);
                 if (r.b0 < 0) {                                 // only the join of a stride-2 opening block (tail: always the first block)
-                    B.nq = B.n1 = B.n2 = 1; B.hiq = B.hi1 = B.hi2 = 255; B.xorq = B.xor1 = B.xor2 = 0x80808080u;     // (unused: no body.0 / body.2 here)
+                    B.rq = B.r1 = B.r2 = Requant::of(1, false);    // (unused: no body.0 / body.2 here)
                     B.relu_a = B.relu_b = 1;
                     a.acc_ok = 1; a.stream_ok = stream_bounded(net, ND[hh.fused_add].out) ? 1 : 0; a.rq_int = rq_int;
                     continue;
@@ -3273,9 +3257,9 @@ static int bind_step(f8_net* net, Step& st) {
                 Node& na = ND[r.b0]; Node& nb = ND[r.b2];
                 B.w0 = W8(na.wf_off); B.w2 = W8(nb.wf_off);
                 B.b0 = B32(na.b_off); B.b2 = B32(nb.b_off);
-                fmt(na, &B.nq, &B.loq, &B.hiq, &B.xorq);
-                fmt(nb, &B.n1, &B.lo1, &B.hi1, &B.xor1);
-                fmt(ng, &B.n2, &B.lo2, &B.hi2, &B.xor2);
+                B.rq = fmt(na);
+                B.r1 = fmt(nb);
+                B.r2 = fmt(ng);
                 B.relu_a = na.cd.relu; B.relu_b = nb.cd.relu;
                 if (k == 0) { a.acc_ok = 1; a.rq_int = rq_int; a.stream_ok = (r.sc >= 0 || stream_bounded(net, na.a)) ? 1 : 0; }   // identity first block: the stream it reads
                 a.acc_ok = a.acc_ok && conv_acc_bounded(na) && conv_acc_bounded(nb);
@@ -3311,7 +3295,7 @@ static int bind_step(f8_net* net, Step& st) {
                 BChainBlk& B = a.blk[k];
                 if (r.sc >= 0) {                                // the opening block's join: (body.2 << acc_shl) + (shortcut << res_shl)
                     B.wb = W8(c2.wf_off); B.bb = B32(c2.b_off);
-                    fmt(c2, &B.n1, &B.lo1, &B.hi1, &B.xor1);
+                    B.r1 = fmt(c2);
                     B.relu1 = ND[hk.fused_add].relu;
                     a.tail = 1; a.wsc = W8(hk.wf_off); a.bsc = B32(hk.b_off);
                     B.relu_a = ND[T[c2.a].prod].cd.relu;        // (body.0's ReLU: mid0's format)
@@ -3375,8 +3359,8 @@ static int bind_step(f8_net* net, Step& st) {
             a.K = ND[nd.blk.b2].cd.kernel; a.cin = x.Cs; a.cout = nd.coutP;
             a.tiles_per_img = (oT.H + a.R - 1) / a.R;
             a.QS = (oT.W + 3) / 4;
-            make_magic((uint32_t)a.QS, &a.mQS, &a.s1QS, &a.s2QS);
-            make_magic((uint32_t)(a.R * a.QS), &a.mRQS, &a.s1RQS, &a.s2RQS);
+            a.dQS = fast_divisor((uint32_t)a.QS);
+            a.dRQS = fast_divisor((uint32_t)(a.R * a.QS));
             irk_kernel_name(kb, sizeof kb, a.K, a.cout, st.inst = irk_inst(a));      // integer requantisation whatever requant_float says (as f8_dwk.hip)
             st.args = a; break;
         }
@@ -3394,21 +3378,21 @@ static int bind_step(f8_net* net, Step& st) {
                 B.wd4 = W8(nb.rc_off); B.bd4 = B32(nb.cc_off);
                 B.w4 = W8(c.w_off); B.b4 = B32(c.b_off);
                 B.cin = T[na.a].Cs; B.cout = c.coutP; B.E32 = na.coutP;
-                fmt(nb, &B.n1, &B.lo1, &B.hi1, &B.xor1);
-                fmt(c, &B.n2, &B.lo2, &B.hi2, &B.xor2);
+                B.r1 = fmt(nb);
+                B.r2 = fmt(c);
                 B.relu_a = na.cd.relu; B.relu_b = nb.cd.relu; B.relu0 = c.cd.relu;
                 if (c.fused_add >= 0) {                         // (project << acc_shl) + (block input << res_shl)
                     B.res = 1; B.relu1 = ND[c.fused_add].relu;
                     join_shifts(T[c.out].fl - T[na.a].fl, &B.acc_shl, &B.res_shl);
                 }
                 if (k + 1 < a.nblk) {
-                    fmt(ND[ND[ch[k + 1]].blk.b0], &B.nq, &B.loq, &B.hiq, &B.xorq);
+                    B.rq = fmt(ND[ND[ch[k + 1]].blk.b0]);
                     B.keep = ND[ch[k + 1]].fused_add >= 0;
                 }
                 a.acc_ok = a.acc_ok && conv_acc_bounded(na) && conv_acc_bounded(nb);
             }
             a.H = x.H; a.W = x.W;
-            make_magic((uint32_t)x.W, &a.mW, &a.s1W, &a.s2W);
+            a.dW = fast_divisor((uint32_t)x.W);
             out_formats(a.q);
             st.inst = irchain_inst(a);
             irchain_kernel_name(kb, sizeof kb, st.inst);
@@ -3464,10 +3448,10 @@ static int bind_step(f8_net* net, Step& st) {
             gconv_tile(a.P, a.Q, a.stride, &a.R, &a.TW, &a.G);
             a.tiles_r = (a.P + a.R - 1) / a.R; a.tiles_c = (a.Q + a.TW - 1) / a.TW;
             a.PR = (a.R - 1) * a.stride + 3; a.PW = (a.TW - 1) * a.stride + 3;
-            make_magic((uint32_t)(a.PR * a.PW), &a.mIPP, &a.s1IPP, &a.s2IPP);
-            make_magic((uint32_t)a.PW, &a.mPW, &a.s1PW, &a.s2PW);
-            make_magic((uint32_t)(a.R * a.TW), &a.mRTW, &a.s1RTW, &a.s2RTW);
-            make_magic((uint32_t)a.TW, &a.mTW, &a.s1TW, &a.s2TW);
+            a.dIPP = fast_divisor((uint32_t)(a.PR * a.PW));
+            a.dPW = fast_divisor((uint32_t)a.PW);
+            a.dRTW = fast_divisor((uint32_t)(a.R * a.TW));
+            a.dTW = fast_divisor((uint32_t)a.TW);
             a.relu0 = st.relu0;
             gconv_kernel_name(kb, sizeof kb, a);                  // integer requantisation whatever requant_float says (as f8_dwk.hip)
             out_formats(a.q); st.args = a; break;
@@ -3511,12 +3495,12 @@ static int bind_step(f8_net* net, Step& st) {
             UpsampleArgs a{};
             a.C = oT.C; a.Cs = oT.Cs; a.Hs = sT.H; a.Ws = sT.W; a.P = oT.H; a.Q = oT.W; a.sh = nd.up_sh; a.sw = nd.up_sw;
             while (nd.up_mode == F8_UP_BILINEAR && (1 << a.k) < a.sh) ++a.k;
-            make_magic((uint32_t)(a.P * a.Q), &a.mPQ, &a.s1PQ, &a.s2PQ);
-            make_magic((uint32_t)a.Q, &a.mQ, &a.s1Q, &a.s2Q);
-            make_magic((uint32_t)a.sh, &a.mSh, &a.s1Sh, &a.s2Sh);
-            make_magic((uint32_t)a.sw, &a.mSw, &a.s1Sw, &a.s2Sw);
-            make_magic((uint32_t)a.Ws, &a.mWs, &a.s1Ws, &a.s2Ws);
-            make_magic((uint32_t)(a.Cs >> 4), &a.mVpp, &a.s1Vpp, &a.s2Vpp);
+            a.dPQ = fast_divisor((uint32_t)(a.P * a.Q));
+            a.dQ = fast_divisor((uint32_t)a.Q);
+            a.dSh = fast_divisor((uint32_t)a.sh);
+            a.dSw = fast_divisor((uint32_t)a.sw);
+            a.dWs = fast_divisor((uint32_t)a.Ws);
+            a.dVpp = fast_divisor((uint32_t)(a.Cs >> 4));
             snprintf(kb, sizeof kb, "%s", upsample_kernel_name(st.inst = upsample_inst(nd.up_mode == F8_UP_BILINEAR, nd.bytes_mode)));
             out_formats(a.q); st.args = a; break;
         }
@@ -3530,7 +3514,7 @@ static int bind_step(f8_net* net, Step& st) {
                 a.Cs_src[i] = T[st.cat_t[fused ? i : 0]].Cs;
                 a.off[i] = nd.kind == N_SLICE ? nd.cm_first : fused ? 0 : i * a.Cg;
             }
-            make_magic((uint32_t)std::max(a.groups, 1), &a.mG, &a.s1G, &a.s2G);
+            a.dG = fast_divisor((uint32_t)std::max(a.groups, 1));
             snprintf(kb, sizeof kb, "%s", chanmap_kernel_name(st.inst = chanmap_inst(a, nd.bytes_mode)));
             out_formats(a.q); st.args = a; break;
         }
@@ -3539,10 +3523,10 @@ static int bind_step(f8_net* net, Step& st) {
             SumPoolArgs a{};
             a.C = oT.C; a.Cs = oT.Cs; a.H = sT.H; a.W = sT.W; a.P = oT.H; a.Q = oT.W; a.k = nd.sum_k; a.stride = nd.sum_stride; a.pad = nd.sum_pad;
             a.lg = sumpool_wide_lg(a.k);
-            make_magic((uint32_t)(a.P * a.Q), &a.mPQ, &a.s1PQ, &a.s2PQ);
-            make_magic((uint32_t)a.Q, &a.mQ, &a.s1Q, &a.s2Q);
-            make_magic((uint32_t)a.k, &a.mK, &a.s1K, &a.s2K);
-            make_magic((uint32_t)(a.Cs >> 2), &a.mCg, &a.s1Cg, &a.s2Cg);
+            a.dPQ = fast_divisor((uint32_t)(a.P * a.Q));
+            a.dQ = fast_divisor((uint32_t)a.Q);
+            a.dK = fast_divisor((uint32_t)a.k);
+            a.dCg = fast_divisor((uint32_t)(a.Cs >> 2));
             snprintf(kb, sizeof kb, "%s", sumpool_kernel_name(st.inst = sumpool_inst(a.k, nd.sum_wide)));
             out_formats(a.q); st.args = a; break;
         }
@@ -3774,7 +3758,7 @@ extern "C++" template <class A>
 static void bind_raw_common(A& a, const f8_net* net, const RunIO& io, size_t off, int sgn) {
     if (io.kind == RunIO::F32) { a.xf = (const float*)io.in + off; a.scale = io.scale; a.qlo = io.lo; a.qhi = io.hi; }
     else if (io.kind != RunIO::I32) { a.xu8 = (const uint8_t*)io.in + off; memcpy(a.lut, io.lut, sizeof a.lut); }
-    else if (net->opt.check_input_range && sgn >= 0) { a.err = net->d_err; a.chk_lo = sgn ? -127 : 0; a.chk_hi = sgn ? 127 : 255; }
+    else if (net->opt.check_input_range && sgn >= 0) { a.err = net->d_err; const Requant f = Requant::of(0, sgn != 0); a.chk_lo = f.lo; a.chk_hi = f.hi; }
 }
 static void bind_raw_input(InArgs& a, const f8_net* net, const RunIO& io, size_t off, int sgn) {
     a.u8_nhwc = io.kind == RunIO::U8_NHWC; if (io.kind == RunIO::I32) a.x = (const int32_t*)io.in + off;
@@ -3840,9 +3824,9 @@ static int run_step(const f8_net* net, const RunIO& io, const Step& st, int n0, 
             InArgs a{}; a.N = N; a.C = o.C; a.H = o.H; a.W = o.W;
             int narrow = -1;                                                   // sign of the head format (an 8-bit form without a requant)
             for (auto& F : o.forms) {
-                if (F.kind == FORM_I8) { if (F.n == 0) { a.out8 = (int8_t*)fp(F); a.Cs8 = o.Cs; if (!F.sgn) a.xor8 = 0x80808080u; narrow = F.sgn; } }
+                if (F.kind == FORM_I8) { if (F.n == 0) { a.out8 = (int8_t*)fp(F); a.Cs8 = o.Cs; a.xor8 |= Requant::of(0, F.sgn).bias_xor; narrow = F.sgn; } }
                 else if (F.kind == FORM_I32) { a.out32 = (int32_t*)fp(F); a.Cs32 = o.Cs; }
-                else { a.stem = (int8_t*)fp(F); a.Hp = F.Hp; a.Wp = F.Wp; a.pad = F.pad; if (!F.sgn) a.xor8 = 0x80808080u; narrow = F.sgn; }
+                else { a.stem = (int8_t*)fp(F); a.Hp = F.Hp; a.Wp = F.Wp; a.pad = F.pad; a.xor8 |= Requant::of(0, F.sgn).bias_xor; narrow = F.sgn; }
             }
             bind_raw_input(a, net, io, (size_t)n0 * o.C * o.H * o.W, narrow);
             e = launch_input(a, st.inst, s);
@@ -3874,7 +3858,7 @@ static int run_step(const f8_net* net, const RunIO& io, const Step& st, int n0, 
             if (st.kind == S_STEMPOOL) a.wpc = net->opt.stem_wpc;
             a.grid_div = net->opt.stem_grid_div;
             if (reads_raw_input(st, io)) {                               // the raw network input, read by this launch (the input step launches nothing)
-                a.rC = sT.C; a.rH = sT.H; a.rW = sT.W; a.xor8 = sF.sgn ? 0u : 0x80808080u;
+                a.rC = sT.C; a.rH = sT.H; a.rW = sT.W; a.xor8 = Requant::of(0, sF.sgn).bias_xor;
                 bind_raw_input(a, net, io, (size_t)n0 * sT.C * sT.H * sT.W, sF.sgn ? 1 : 0);
             }
             fill_out(&a.out32, a.q);

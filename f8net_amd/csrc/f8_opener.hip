@@ -132,7 +132,7 @@ fused_opener_kernel(const FusedArgs a) {
     }
     // ---- patch border = biased zero: column 0 (input column -1) of every row; row 0 when it lies above the image
     {
-        const unsigned z = a.xor1;
+        const unsigned z = a.r1.bias_xor;
         const v4i zv = {(int)z, (int)z, (int)z, (int)z};
         if (tid < PR * (MID / 16)) *(v4i*)(patch + (tid / (MID / 16)) * PW * MID + (tid % (MID / 16)) * 16) = zv;
         if (p0 == 0)
@@ -270,7 +270,7 @@ fused_opener_kernel(const FusedArgs a) {
         for (int k = 0; k < NS2 - 1; ++k) issue_w2(k, k);
 
         const int floor0 = a.relu_a ? 0 : INT32_MIN;
-        const float sc1 = FQ == 1 ? requant_u8_scale(a.n1) : 0.0f;
+        const float sc1 = FQ == 1 ? requant_u8_scale(a.r1.n) : 0.0f;
         (void)floor0; (void)sc1;
 #pragma unroll
         for (int j = 0; j < NP1W; ++j) {
@@ -285,13 +285,13 @@ fused_opener_kernel(const FusedArgs a) {
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     if constexpr (FQ != 0) {
-                        d[g] = requant_u8x4_sel<FQ == 2 ? 2 : 1>(acc[j][i][4 * g], acc[j][i][4 * g + 1], acc[j][i][4 * g + 2], acc[j][i][4 * g + 3], a.n1, sc1) ^ 0x80808080u;
+                        d[g] = requant_u8x4_sel<FQ == 2 ? 2 : 1>(acc[j][i][4 * g], acc[j][i][4 * g + 1], acc[j][i][4 * g + 2], acc[j][i][4 * g + 3], a.r1.n, sc1) ^ 0x80808080u;
                     } else {
                         const v4i bv = *(const v4i*)(bias_lds + ct * 32 + 8 * g + 4 * lh);
                         int y[4];
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) y[e] = requant1(max((int)((unsigned)acc[j][i][4 * g + e] + (unsigned)bv[e]), floor0), a.n1, a.lo1, a.hi1);
-                        d[g] = pack4(y[0], y[1], y[2], y[3]) ^ a.xor1;
+                        for (int e = 0; e < 4; ++e) y[e] = max((int)((unsigned)acc[j][i][4 * g + e] + (unsigned)bv[e]), floor0);
+                        d[g] = requant_pack4(y[0], y[1], y[2], y[3], a.r1);
                     }
                 }
                 auto s0 = __builtin_amdgcn_permlane32_swap(d[0], d[2], false, false);
@@ -358,7 +358,7 @@ fused_opener_kernel(const FusedArgs a) {
         }
 
         const int floor0 = a.relu_b ? 0 : INT32_MIN;
-        const float sc2 = FQ == 1 ? requant_u8_scale(a.n2) : 0.0f;
+        const float sc2 = FQ == 1 ? requant_u8_scale(a.r2.n) : 0.0f;
         (void)floor0; (void)sc2;
 #pragma unroll
         for (int i = 0; i < CMW; ++i) {
@@ -367,12 +367,12 @@ fused_opener_kernel(const FusedArgs a) {
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 if constexpr (FQ != 0) {
-                    d[g] = requant_u8x4_sel<FQ == 2 ? 2 : 1>(acc[i][4 * g], acc[i][4 * g + 1], acc[i][4 * g + 2], acc[i][4 * g + 3], a.n2, sc2) ^ 0x80808080u;
+                    d[g] = requant_u8x4_sel<FQ == 2 ? 2 : 1>(acc[i][4 * g], acc[i][4 * g + 1], acc[i][4 * g + 2], acc[i][4 * g + 3], a.r2.n, sc2) ^ 0x80808080u;
                 } else {
                     int y[4];
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) y[e] = requant1(max(acc[i][4 * g + e], floor0), a.n2, a.lo2, a.hi2);
-                    d[g] = pack4(y[0], y[1], y[2], y[3]) ^ a.xor2;
+                    for (int e = 0; e < 4; ++e) y[e] = max(acc[i][4 * g + e], floor0);
+                    d[g] = requant_pack4(y[0], y[1], y[2], y[3], a.r2);
                 }
             }
             auto s0 = __builtin_amdgcn_permlane32_swap(d[0], d[2], false, false);
@@ -465,8 +465,7 @@ fused_opener_kernel(const FusedArgs a) {
                 unsigned d[4];
 #pragma unroll
                 for (int g = 0; g < 4; ++g)
-                    d[g] = pack4(requant1(y[g][0], a.q[k].n, a.q[k].lo, a.q[k].hi), requant1(y[g][1], a.q[k].n, a.q[k].lo, a.q[k].hi),
-                                 requant1(y[g][2], a.q[k].n, a.q[k].lo, a.q[k].hi), requant1(y[g][3], a.q[k].n, a.q[k].lo, a.q[k].hi)) ^ a.q[k].bias_xor;
+                    d[g] = requant_pack4(y[g][0], y[g][1], y[g][2], y[g][3], a.q[k]);
                 auto s0 = __builtin_amdgcn_permlane32_swap(d[0], d[2], false, false);
                 auto s1 = __builtin_amdgcn_permlane32_swap(d[1], d[3], false, false);
                 const v4i o = {(int)s0[0], (int)s0[1], (int)s1[0], (int)s1[1]};
@@ -532,12 +531,11 @@ static hipError_t launch_opener_t(const FusedArgs& a, hipStream_t s) {
 // after both convs (1: float converter where it is provably exact, 2: integer form, 0: the general epilogues).
 int fused_opener_inst(const FusedArgs& a, bool stg) {
     if (!a.p12only) return stg ? 1 : 0;
-    const bool fqf = a.relu_a && a.relu_b && a.n1 > 0 && a.n2 > 0 && a.n1 <= 30 && a.n2 <= 30 && a.lo1 == 0 && a.lo2 == 0 && a.hi1 == 255 && a.hi2 == 255 &&
-                     a.xor1 == 0x80808080u && a.xor2 == 0x80808080u;
+    const bool fqf = a.relu_a && a.relu_b && a.r1.u8_shr() && a.r2.u8_shr();
 #ifndef F8_OPENER_FQ
 #define F8_OPENER_FQ 1             // 0 (tuning builds): the general epilogues
 #endif
-    return (!fqf || !F8_OPENER_FQ) ? 0 : ((a.rq_int || !a.acc_ok || a.n1 > kRequantU8MaxShift || a.n2 > kRequantU8MaxShift) ? 2 : 1);
+    return (!fqf || !F8_OPENER_FQ) ? 0 : ((a.rq_int || !a.acc_ok || !a.r1.u8_float() || !a.r2.u8_float()) ? 2 : 1);
 }
 
 int fused_opener_kernel_name(char* buf, size_t cap, const FusedArgs& a, int inst) {

@@ -112,7 +112,7 @@ fused_p12_kernel(const FusedArgs a) {
     issue_x(1);
     __builtin_amdgcn_sched_barrier(0);                   // the counted waits of P1 need the weight loads younger than these DMAs
     {   // patch <- biased zero (the border keeps it; P1 writes the 49 interior entries)
-        const v4i zv = {(int)a.xor1, (int)a.xor1, (int)a.xor1, (int)a.xor1};
+        const v4i zv = {(int)a.r1.bias_xor, (int)a.r1.bias_xor, (int)a.r1.bias_xor, (int)a.r1.bias_xor};
         for (int o = tid * 16; o < PW * PW * MID; o += 512 * 16) *(v4i*)(patch + o) = zv;
     }
 
@@ -189,8 +189,8 @@ fused_p12_kernel(const FusedArgs a) {
                     const v4i bv = *(const v4i*)(bias_lds + ct * 32 + 8 * g + 4 * lh);
                     int y[4];
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) y[e] = requant1(max((int)((unsigned)acc[j][i][4 * g + e] + (unsigned)bv[e]), floor0), a.n1, a.lo1, a.hi1);
-                    d[g] = pack4(y[0], y[1], y[2], y[3]) ^ a.xor1;
+                    for (int e = 0; e < 4; ++e) y[e] = max((int)((unsigned)acc[j][i][4 * g + e] + (unsigned)bv[e]), floor0);
+                    d[g] = requant_pack4(y[0], y[1], y[2], y[3], a.r1);
                 }
                 auto s0 = __builtin_amdgcn_permlane32_swap(d[0], d[2], false, false);
                 auto s1 = __builtin_amdgcn_permlane32_swap(d[1], d[3], false, false);
@@ -265,8 +265,7 @@ fused_p12_kernel(const FusedArgs a) {
                 unsigned d[4];
 #pragma unroll
                 for (int g = 0; g < 4; ++g)
-                    d[g] = pack4(requant1(max(acc[j][4 * g + 0], floor0), a.q[k].n, a.q[k].lo, a.q[k].hi), requant1(max(acc[j][4 * g + 1], floor0), a.q[k].n, a.q[k].lo, a.q[k].hi),
-                                 requant1(max(acc[j][4 * g + 2], floor0), a.q[k].n, a.q[k].lo, a.q[k].hi), requant1(max(acc[j][4 * g + 3], floor0), a.q[k].n, a.q[k].lo, a.q[k].hi)) ^ a.q[k].bias_xor;
+                    d[g] = requant_pack4(max(acc[j][4 * g + 0], floor0), max(acc[j][4 * g + 1], floor0), max(acc[j][4 * g + 2], floor0), max(acc[j][4 * g + 3], floor0), a.q[k]);
                 auto s0 = __builtin_amdgcn_permlane32_swap(d[0], d[2], false, false);
                 auto s1 = __builtin_amdgcn_permlane32_swap(d[1], d[3], false, false);
                 if (ok) {

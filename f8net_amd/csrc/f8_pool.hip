@@ -104,8 +104,7 @@ __global__ void __launch_bounds__(512) conv1x1_pool_kernel(const ConvArgs a) {
                 for (int k = 0; k < 2; ++k)
                     if (a.q[k].ptr)
                         *(unsigned*)(a.q[k].ptr + (size_t)n * a.coutP + c) =
-                            pack4(requant1((int)tot[4 * g], a.q[k].n, a.q[k].lo, a.q[k].hi), requant1((int)tot[4 * g + 1], a.q[k].n, a.q[k].lo, a.q[k].hi),
-                                  requant1((int)tot[4 * g + 2], a.q[k].n, a.q[k].lo, a.q[k].hi), requant1((int)tot[4 * g + 3], a.q[k].n, a.q[k].lo, a.q[k].hi)) ^ a.q[k].bias_xor;
+                            requant_pack4((int)tot[4 * g], (int)tot[4 * g + 1], (int)tot[4 * g + 2], (int)tot[4 * g + 3], a.q[k]);
             }
         }
         store_x(lds + (cur ^ 1) * (64 * XS), xr);                 // the other buffer: its last readers passed the previous barrier

@@ -170,8 +170,7 @@ __global__ void __launch_bounds__(512) conv3x3s2_wreg_kernel(const ConvArgs a, c
             unsigned d[4];
 #pragma unroll
             for (int g = 0; g < 4; ++g)
-                d[g] = pack4(requant1(max(acc[j][4 * g + 0], floor0), a.q[k].n, a.q[k].lo, a.q[k].hi), requant1(max(acc[j][4 * g + 1], floor0), a.q[k].n, a.q[k].lo, a.q[k].hi),
-                             requant1(max(acc[j][4 * g + 2], floor0), a.q[k].n, a.q[k].lo, a.q[k].hi), requant1(max(acc[j][4 * g + 3], floor0), a.q[k].n, a.q[k].lo, a.q[k].hi)) ^ a.q[k].bias_xor;
+                d[g] = requant_pack4(max(acc[j][4 * g + 0], floor0), max(acc[j][4 * g + 1], floor0), max(acc[j][4 * g + 2], floor0), max(acc[j][4 * g + 3], floor0), a.q[k]);
             auto s0 = __builtin_amdgcn_permlane32_swap(d[0], d[2], false, false);
             auto s1 = __builtin_amdgcn_permlane32_swap(d[1], d[3], false, false);
             if (gpx[j] >= 0) {

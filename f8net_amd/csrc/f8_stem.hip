@@ -230,8 +230,7 @@ __global__ void __launch_bounds__(512) stem_pool_kernel(const StemPoolArgs a) {
                 for (int k = 0; k < 2; ++k)
                     if (a.q[k].ptr)
                         *(unsigned*)(a.q[k].ptr + (size_t)m * 64 + c) =
-                            pack4(requant1(mx[0], a.q[k].n, a.q[k].lo, a.q[k].hi), requant1(mx[1], a.q[k].n, a.q[k].lo, a.q[k].hi),
-                                  requant1(mx[2], a.q[k].n, a.q[k].lo, a.q[k].hi), requant1(mx[3], a.q[k].n, a.q[k].lo, a.q[k].hi)) ^ a.q[k].bias_xor;
+                            requant_pack4(mx[0], mx[1], mx[2], mx[3], a.q[k]);
             }
         }
         // the next iteration's first barrier separates these ct reads from the next epilogue's ct writes
@@ -278,36 +277,6 @@ constexpr int SW = 28;                              // pooled columns per strip 
 constexpr int RB_ROWS = 4 * RB + 7;                 // input rows of a band
 constexpr int H2_RB = 14;                           // MobileNet-V2 head: output rows per band (2 * 14 + 5 = 33 input rows)
 
-__device__ __forceinline__ int dpp_next_lane(int v) {   // lane i <- lane i + 1 (across the 16-lane DPP rows; lane 63 keeps its value)
-    return __builtin_amdgcn_update_dpp(v, v, 0x130 /* wave_shl:1 */, 0xf, 0xf, false);
-}
-template <class Y>
-__device__ __forceinline__ v4i stem_quant16(const Y& y, int n, int lo, int hi, unsigned x_or, bool acc_ok) {
-    unsigned d[4];
-    if (acc_ok && n > 0 && n <= kRequantU8MaxShift && lo == 0 && hi == 255) {   // the usual case: unsigned 8-bit, three VALU operations per value (wave-uniform branch)
-        const float sc = requant_u8_scale(n);
-#pragma unroll
-        for (int g = 0; g < 4; ++g) d[g] = requant_u8x4(y[4 * g], y[4 * g + 1], y[4 * g + 2], y[4 * g + 3], sc) ^ x_or;
-    } else if (n > 0 && n <= 30 && lo == 0 && hi == 255) {   // the same case on INTEGER instructions (option requant_float = 0 — the default since round 5 — or an
-                                                     // accumulator the planner cannot bound): v_bfe_u32, v_add3_u32, v_ashr_pk_u8_i32: 2 3/4 per value, exact for every int32.
-                                                     // (Round 5: the integer default used to fall through to the general form below, 4 3/4 per value.)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) d[g] = requant_u8x4_int(y[4 * g], y[4 * g + 1], y[4 * g + 2], y[4 * g + 3], n) ^ x_or;
-    } else if (n > 0) {                              // another right shift: four
-        const unsigned hf = 1u << (n - 1);
-#pragma unroll
-        for (int g = 0; g < 4; ++g) d[g] = pack4(requant_shr(y[4 * g], n, hf, 0u, lo, hi), requant_shr(y[4 * g + 1], n, hf, 0u, lo, hi),
-                                                 requant_shr(y[4 * g + 2], n, hf, 0u, lo, hi), requant_shr(y[4 * g + 3], n, hf, 0u, lo, hi)) ^ x_or;
-    } else {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) d[g] = pack4(requant1(y[4 * g], n, lo, hi), requant1(y[4 * g + 1], n, lo, hi), requant1(y[4 * g + 2], n, lo, hi),
-                                                 requant1(y[4 * g + 3], n, lo, hi)) ^ x_or;
-    }
-    auto s0 = __builtin_amdgcn_permlane32_swap(d[0], d[2], false, false);
-    auto s1 = __builtin_amdgcn_permlane32_swap(d[1], d[3], false, false);
-    const v4i o = {(int)s0[0], (int)s0[1], (int)s1[0], (int)s1[1]};
-    return o;                                        // lane (pixel, half): channels 16 half .. 16 half + 15 of the 32-channel tile
-}
 }
 
 // H2: the same skeleton (loader waves, double-buffered patch, persistent bands) with a different body for the compute waves: the
@@ -315,7 +284,7 @@ __device__ __forceinline__ v4i stem_quant16(const Y& y, int n, int lo, int hi, u
 template <int KIND, bool H2 = false>
 __global__ void __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3, 3))) stem_rows_kernel(const StemPoolArgs a) {
     extern __shared__ __attribute__((aligned(16))) char lds[];      // 2 x [RB_ROWS][PWB pixels][4 B] (patch column pc = input column pc - 5) | 64 biases
-    set_fp_round_nearest_even();                                    // stem_quant16 / quant_row may take the float-converter form (f8_device.h)
+    set_fp_round_nearest_even();                                    // quant_lane16 / quant_row may take the float-converter form (f8_device.h)
     const int tid = threadIdx.x;
     const int lane = tid & 63, l31 = lane & 31, lh = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // 0 .. 7 compute, 8 .. 11 loaders
@@ -550,7 +519,7 @@ __global__ void __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3, 3))
 #pragma unroll
                     for (int k = 0; k < 2; ++k)
                         if (a.q[k].ptr) {
-                            const v4i v = stem_quant16(acc1, a.q[k].n, a.q[k].lo, a.q[k].hi, a.q[k].bias_xor, !rqi);
+                            const v4i v = quant_lane16(acc1, a.q[k], !rqi);
                             if (lane_out) *(v4i*)(a.q[k].ptr + m * 32 + lh * 16) = v;
                         }
                     R0 = R1; R1 = R2;
@@ -690,7 +659,7 @@ __global__ void __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3, 3))
 #pragma unroll
                 for (int k = 0; k < 2; ++k)
                     if (a.q[k].ptr) {
-                        const v4i v = stem_quant16(pm, a.q[k].n, a.q[k].lo, a.q[k].hi, a.q[k].bias_xor, a.acc_ok != 0 && a.rq_int == 0);
+                        const v4i v = quant_lane16(pm, a.q[k], a.acc_ok != 0 && a.rq_int == 0);
                         if (lane_out && (F8_STEM_ABL != 4 || v[0] == 0x12345678)) *(v4i*)(a.q[k].ptr + (size_t)m * 64 + half * 32 + lh * 16) = v;
                     }
             }

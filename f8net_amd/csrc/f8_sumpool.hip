@@ -22,8 +22,7 @@ __device__ __forceinline__ void sumpool_store8(const SumPoolArgs& a, size_t off,
     for (int k = 0; k < 2; ++k)
         if (a.q[k].ptr)
             *(unsigned*)(a.q[k].ptr + off) =
-                pack4(requant1((int)y[0], a.q[k].n, a.q[k].lo, a.q[k].hi), requant1((int)y[1], a.q[k].n, a.q[k].lo, a.q[k].hi),
-                      requant1((int)y[2], a.q[k].n, a.q[k].lo, a.q[k].hi), requant1((int)y[3], a.q[k].n, a.q[k].lo, a.q[k].hi)) ^ a.q[k].bias_xor;
+                requant_pack4((int)y[0], (int)y[1], (int)y[2], (int)y[3], a.q[k]);
 }
 
 // Walks the OUTPUT's 4 KB I32T blocks (32 pixels x 32 channels), one wave per block as upsample_i32_kernel / tap_kernel do: lane = output pixel
@@ -45,8 +44,8 @@ __global__ void __launch_bounds__(256) sumpool_i32_kernel(const SumPoolArgs a) {
         const unsigned pb = b / cbs, cb = b - pb * cbs;
         const unsigned m = pb * 32u + (lane & 31u);
         if (m >= M) continue;
-        const unsigned n = fast_div(m, a.mPQ, a.s1PQ, a.s2PQ), pq = m - n * PQ;
-        const unsigned p = fast_div(pq, a.mQ, a.s1Q, a.s2Q), q = pq - p * (unsigned)a.Q;
+        const unsigned n = fast_div(m, a.dPQ), pq = m - n * PQ;
+        const unsigned p = fast_div(pq, a.dQ), q = pq - p * (unsigned)a.Q;
         const int c0 = (int)(cb * 32u + 4u * (lane >> 5));
         const int h0 = (int)p * a.stride - a.pad, w0 = (int)q * a.stride - a.pad;
         const int row0 = (int)n * a.H;                                // first source row of the image
@@ -97,15 +96,15 @@ __global__ void __launch_bounds__(256) sumpool_wide_kernel(const SumPoolArgs a) 
     const unsigned kk = (unsigned)(a.k * a.k);
     const unsigned step = (gridDim.x * 256u) >> a.lg;
     for (unsigned item = (blockIdx.x * 256u + threadIdx.x) >> a.lg; item < items; item += step) {
-        const unsigned m = fast_div(item, a.mCg, a.s1Cg, a.s2Cg), cg = item - m * cgs;
-        const unsigned n = fast_div(m, a.mPQ, a.s1PQ, a.s2PQ), pq = m - n * PQ;
-        const unsigned p = fast_div(pq, a.mQ, a.s1Q, a.s2Q), q = pq - p * (unsigned)a.Q;
+        const unsigned m = fast_div(item, a.dCg), cg = item - m * cgs;
+        const unsigned n = fast_div(m, a.dPQ), pq = m - n * PQ;
+        const unsigned p = fast_div(pq, a.dQ), q = pq - p * (unsigned)a.Q;
         const int c = (int)(cg << 2);
         const int h0 = (int)p * a.stride - a.pad, w0 = (int)q * a.stride - a.pad;
         const int row0 = (int)n * a.H;
         unsigned y[4] = {0u, 0u, 0u, 0u};
         for (unsigned t = j; t < kk; t += G) {
-            const unsigned r = fast_div(t, a.mK, a.s1K, a.s2K), s = t - r * (unsigned)a.k;
+            const unsigned r = fast_div(t, a.dK), s = t - r * (unsigned)a.k;
             const int h = h0 + (int)r, w = w0 + (int)s;
             if ((unsigned)h >= (unsigned)a.H || (unsigned)w >= (unsigned)a.W) continue;    // outside the map: contributes 0
             const v4i v = *(const v4i*)(a.x + i32t_index((row0 + h) * a.W + w, c, a.Cs));

@@ -23,9 +23,9 @@ __global__ void __launch_bounds__(256) upsample_i8_kernel(const UpsampleArgs a) 
     const unsigned vpp = (unsigned)a.Cs >> 4;                        // vectors per pixel
     const unsigned total = (unsigned)a.N * (unsigned)a.P * (unsigned)a.Ws * vpp;      // <= output bytes / 16 < 2^27 (f8_net_finalize: a form stays below 2 GiB)
     for (unsigned idx = blockIdx.x * 256u + threadIdx.x; idx < total; idx += gridDim.x * 256u) {
-        const unsigned r = fast_div(idx, a.mVpp, a.s1Vpp, a.s2Vpp), v = idx - r * vpp;
-        const unsigned row = fast_div(r, a.mWs, a.s1Ws, a.s2Ws), j = r - row * (unsigned)a.Ws;      // row = n * P + p
-        const unsigned srow = fast_div(row, a.mSh, a.s1Sh, a.s2Sh);                                  // n * Hs + p / sh (P = Hs * sh)
+        const unsigned r = fast_div(idx, a.dVpp), v = idx - r * vpp;
+        const unsigned row = fast_div(r, a.dWs), j = r - row * (unsigned)a.Ws;      // row = n * P + p
+        const unsigned srow = fast_div(row, a.dSh);                                  // n * Hs + p / sh (P = Hs * sh)
         const size_t so = ((size_t)srow * a.Ws + j) * a.Cs + v * 16u;
         const size_t dst = ((size_t)row * a.Q + (size_t)j * a.sw) * a.Cs + v * 16u;
 #pragma unroll
@@ -56,8 +56,8 @@ __global__ void __launch_bounds__(256) upsample_i32_kernel(const UpsampleArgs a)
         const unsigned pb = b / cbs, cb = b - pb * cbs;
         const unsigned m = pb * 32u + (lane & 31u);
         if (m >= M) continue;
-        const unsigned n = fast_div(m, a.mPQ, a.s1PQ, a.s2PQ), pq = m - n * PQ;
-        const unsigned p = fast_div(pq, a.mQ, a.s1Q, a.s2Q), q = pq - p * (unsigned)a.Q;
+        const unsigned n = fast_div(m, a.dPQ), pq = m - n * PQ;
+        const unsigned p = fast_div(pq, a.dQ), q = pq - p * (unsigned)a.Q;
         const int c0 = (int)(cb * 32u + 4u * (lane >> 5));
         const int base = (int)n * a.Hs;                               // first source row of the image
         int m00, m01 = 0, m10 = 0, m11 = 0;                           // source pixels (rows i0 / i1, columns j0 / j1)
@@ -74,7 +74,7 @@ __global__ void __launch_bounds__(256) upsample_i32_kernel(const UpsampleArgs a)
             m10 = (base + i1) * a.Ws + j0; m11 = (base + i1) * a.Ws + j1;
             w00 = wl * vl; w01 = wl * vu; w10 = wu * vl; w11 = wu * vu;
         } else {
-            const unsigned i = fast_div(p, a.mSh, a.s1Sh, a.s2Sh), ii = fast_div(q, a.mSw, a.s1Sw, a.s2Sw);
+            const unsigned i = fast_div(p, a.dSh), ii = fast_div(q, a.dSw);
             m00 = (base + (int)i) * a.Ws + (int)ii;
         }
         v4i* const o32 = a.out32 ? (v4i*)(a.out32 + (size_t)b * 1024u) + lane : nullptr;

@@ -115,8 +115,8 @@ __global__ void __launch_bounds__(NW * 64) conv1x1_wstat_kernel(const ConvArgs a
 #pragma unroll
                 for (int i = 0; i < L; ++i) {
                     const unsigned m = (unsigned)tile * 32u + drow[p0 + i];
-                    const unsigned n = fast_div(m, a.mPQ, a.s1PQ, a.s2PQ), rem = m - n * (unsigned)a.PQ;
-                    const unsigned pr = fast_div(rem, a.mQ, a.s1Q, a.s2Q), q = rem - pr * (unsigned)a.Q;
+                    const unsigned n = fast_div(m, a.dPQ), rem = m - n * (unsigned)a.PQ;
+                    const unsigned pr = fast_div(rem, a.dQ), q = rem - pr * (unsigned)a.Q;
                     const unsigned o = n * (unsigned)sN + pr * (unsigned)sP + q * (unsigned)sQ + dconst[p0 + i];
                     doff[p0 + i] = m < (unsigned)a.M ? o : kOOB;
                 }

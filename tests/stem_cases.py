@@ -325,7 +325,7 @@ def _epi(readers=(_U,), shift=9, **kw):
 
 
 TABLE_C = {}
-for _rq in (0, 1):                                               # first / second branch of stem_quant16: float converter (requant_float 1, shift <= 16) / integer
+for _rq in (0, 1):                                               # first / second branch of quant_lane16 (f8_device.h): float converter (requant_float 1, shift <= 16) / integer
     TABLE_C[f'c_u_shift1_rq{_rq}'] = _epi([(7, False)], shift=1, opts={'requant_float': _rq})
     TABLE_C[f'c_u_shift9_rq{_rq}'] = _epi(opts={'requant_float': _rq})
     TABLE_C[f'c_u_shift16_rq{_rq}'] = _epi(shift=16, opts={'requant_float': _rq})

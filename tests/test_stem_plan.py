@@ -88,7 +88,7 @@ def test_support_boundaries_one_step_either_side():
 
 def test_bias_next_to_int32_max_keeps_the_plan():
     """An accumulator the planner cannot bound (acc_ok = 0) moves nothing the plan shows — the kernel names carry no template arguments and
-    describe() no requantisation form; stem_quant16 takes its integer branch on the launch argument.  What this pins on the CPU: the cases that aim
+    describe() no requantisation form; quant_lane16 takes its integer branch on the launch argument.  What this pins on the CPU: the cases that aim
     at it do hold accumulators next to both ends of int32, and plan the fused launch under requant_float = 1.  The device test decides the rest: the
     converter form is exact only up to kAccLimit, so a launch that took it would differ from the oracle there."""
     for name in ('c_bias_big_rq1', 'c_bias_big_rq0', 'c_h2_bias_big_head', 'c_h2_bias_big_dw'):
@@ -173,7 +173,7 @@ def test_liveness_on_the_oracle(name):
 
 
 def test_tables_cover_what_they_name():
-    """Table B: the issue's widths and heights of each kernel; table C: the four branches of stem_quant16 by their conditions."""
+    """Table B: the issue's widths and heights of each kernel; table C: the four branches of quant_lane16 by their conditions."""
     rows = {sc.pooled_hw(c) for n, c in sc.TABLE_B.items() if c['kernel'] == 'rows' and c['entry'] == 'i32'}
     assert rows == {(1, 2), (2, 27), (3, 28), (7, 29), (8, 30), (9, 55), (15, 56), (25, 25)}
     assert {c['entry'] for n, c in sc.TABLE_B.items() if sc.pooled_hw(c) == (5, 6)} == {'halo', 'nhwc', 'cin1', 'cin4'}

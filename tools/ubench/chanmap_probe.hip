@@ -44,14 +44,8 @@ static long run(int groups, int first, int channels, int C, const char** kernel)
         a.Cs_src[i] = Cs_src; a.off[i] = groups ? i * a.Cg : first;
         a.src[0][i] = d_src[0]; a.src[1][i] = d_src[1];
     }
-    {   // make_magic(groups) of f8_net.cpp
-        const uint32_t d = groups ? (uint32_t)groups : 1u;
-        int l = 0;
-        while ((1ull << l) < d) ++l;
-        a.mG = (uint32_t)(((1ull << 32) * ((1ull << l) - d)) / d + 1); a.s1G = l < 1 ? l : 1; a.s2G = l > 1 ? l - 1 : 0;
-    }
-    a.q[0].ptr = (int8_t*)d_out[0]; a.q[0].bias_xor = 0x80808080u; a.q[0].lo = 0; a.q[0].hi = 255;
-    a.q[1].ptr = (int8_t*)d_out[1]; a.q[1].bias_xor = 0u; a.q[1].lo = -127; a.q[1].hi = 127;
+    a.dG = f8::fast_divisor(groups ? (uint32_t)groups : 1u);
+    for (int k = 0; k < 2; ++k) { static_cast<f8::Requant&>(a.q[k]) = f8::Requant::of(0, k == 1); a.q[k].ptr = (int8_t*)d_out[k]; }   // form 0 unsigned (stored biased), form 1 signed
     const int inst = f8::chanmap_inst(a, true);
     *kernel = f8::chanmap_kernel_name(inst);
     HIP_OK(f8::launch_chanmap(a, inst, nullptr));
