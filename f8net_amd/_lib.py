@@ -29,6 +29,10 @@ class LinearDesc(ctypes.Structure):
                 ('in_features', 'out_features', 'weight_fl', 'input_fl', 'input_signed', 'quant_input')]
 
 
+class MulDesc(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ('a_fl', 'a_signed', 'b_fl', 'b_signed', 'relu')]
+
+
 _lib = None
 
 # every symbol include/f8net.h declares: (name, restype, argtypes)
@@ -54,6 +58,8 @@ SYMBOLS = [
     ('f8_net_upsample', _i, [_vp, _i, _i, _i, _i]),
     ('f8_net_slice', _i, [_vp, _i, _i, _i]),
     ('f8_net_channel_shuffle', _i, [_vp, _i, _i]),
+    ('f8_net_mul', _i, [_vp, _i, _i, ctypes.POINTER(MulDesc)]),
+    ('f8_net_hard_gate', _i, [_vp, _i]),
     ('f8_net_maxpool', _i, [_vp, _i, _i, _i, _i]),
     ('f8_net_avgpool_sum', _i, [_vp, _i, _i]),
     ('f8_net_avgpool_window', _i, [_vp, _i, _i, _i, _i, _i]),

@@ -79,6 +79,7 @@ struct Options {
                                  // 0 = every pool on the walker; 2 = every pool with kernel >= 2 on the wide kernel (tests).  Same values on every leg
     int chanmap_i8 = 1;          // f8_net_slice / f8_net_channel_shuffle: 1 = the byte-gather mode where the result is read in at most two int8 formats and by nothing else (f8_chanmap.hip); 0 = always the int32 mode
     int fuse_shuffle = 1;        // a concat read by one i8-mode channel shuffle alone, `groups` operands of one width: 1 = one launch that reads the concat's operands (concat+shuffle{g}_i8:); 0 = two launches
+    int fuse_hgate = 1;          // a hard gate read by the b operand of one mul alone: 1 = no launch of its own, the mul launch reads the gate's int32 source (hgate+mul_*: / hgate+chmul_*:, f8_mul.hip); 0 = two launches
     int tap_tiled = 1;           // network outputs 1 .. leave on tap_kernel (f8_tap.hip: walks the I32T blocks, every loaded byte used); 0: on output_kernel like output 0
     int check_input_range = 1;   // int32 inputs that are NARROWED to the head's 8-bit format (no requant) are range-checked on the device; f8_net_check reports
 };
@@ -272,6 +273,24 @@ struct ChanMapArgs {
     int32_t K, groups, Cg;                               // table entries; 0 = slice, else the shuffle's groups (== K) and channels per group
     int32_t M, C, Cs;                                    // pixels N * H * W, real / padded output channels
     FastDiv dG;                                          // / groups
+    int32_t* out32;
+    QuantOut q[2];
+};
+
+// Fixed-point multiply and hard gate (f8_mul.hip; f8_net_mul, f8_net_hard_gate).  out = A * B per element (bcast == 0: b has a's shape) or
+// out[pixel m][c] = A[m][c] * B[image m / HW][c] (bcast == 1: b is [C, 1, 1]); `a` is operand a in the int8 format ra (NHWC, Cs-byte rows; the shift
+// of ra is the producer's business: only ra.bias_xor and the sign ra.lo < 0 are read).  gate == 0: `b` is operand b in the int8 format rb, likewise.
+// gate == 1 (a hard gate fused into the launch): `b` is the GATE's SOURCE in int32 (I32T; bcast: one pixel per image), the launch computes
+// clamp(x, -lim, lim) + lim and requantises it by rb (shift, clamp) itself.  relu: max(., 0) on the product.  out32 (I32T) and q[] as AddArgs.
+// The stand-alone hard gate (hgate_kernel) uses the same record: `b` is its int32 source, lim its 3 * 2^fl, a is unused.
+struct MulArgs {
+    const int8_t* a; const void* b;
+    int32_t M, C, Cs;                                    // pixels N * H * W, real / padded channels (b's rows have the same Cs)
+    int32_t HW; FastDiv dHW;                             // bcast: pixels per image, pixel -> image
+    FastDiv dVpp;                                        // mul_i8_kernel: / (Cs / V), the vectors of a pixel (V = mul_vector_bytes of the instance)
+    int32_t bcast, gate, relu;
+    int32_t lim;                                         // gate: 3 * 2^fl of the gate's source
+    Requant ra, rb;                                      // the operand formats (Requant::of)
     int32_t* out32;
     QuantOut q[2];
 };
@@ -719,6 +738,10 @@ hipError_t launch_deconv(const DeconvArgs& a, int inst, hipStream_t s);
 int chanmap_inst(const ChanMapArgs& a, bool i8);                   // f8_chanmap.hip.  0: chanmap_i32_kernel, 1 / 2: slice_i8_kernel<true> / <false>, 3 / 4 / 5: shuffle_i8_kernel<16> / <4> / <2>, 6: shuffle_i8_general_kernel
 const char* chanmap_kernel_name(int inst);
 hipError_t launch_chanmap(const ChanMapArgs& a, int inst, hipStream_t s);
+int mul_inst(const MulArgs& a, int mode);                          // f8_mul.hip.  mode 0: the stand-alone hard gate, 1: a mul that writes the int32 form, 2: int8 outputs only.  0: hgate_kernel; 1 .. 4: mul_i32_kernel<BCAST, GATE> = <0,0> <0,1> <1,0> <1,1>; 5 .. 10: mul_i8_kernel<BCAST, GATE, V> = <0,0,16> <0,0,4> <1,0,16> <1,0,4> <1,1,16> <1,1,4>
+const char* mul_kernel_name(int inst);
+int mul_vector_bytes(int inst);                                    // bytes of one operand a lane of the instance owns per step (16 / 4)
+hipError_t launch_mul(const MulArgs& a, int inst, hipStream_t s);
 int sumpool_inst(int k, bool wide);                                // f8_sumpool.hip.  0: sumpool_i32_kernel<0> (kernel size at run time), 2 / 3: sumpool_i32_kernel<2> / <3>, 4: sumpool_wide_kernel
 const char* sumpool_kernel_name(int inst);
 int sumpool_wide_lg(int k);

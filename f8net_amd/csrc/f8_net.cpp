@@ -94,7 +94,9 @@ enum ChainKind { C_NONE, C_STAGE, C_BASIC, C_BASIC_CLUSTER, C_IR };
 // its source exists in device memory and cuts a chain or fused block where an output tap does.  It reads its source's int32 form.
 // N_SLICE / N_SHUFFLE (f8_net_slice, f8_net_channel_shuffle; f8_chanmap.hip) are kinds of their own for the same reason: their source exists in device
 // memory and cuts a chain or fused block where an output tap does.  Channel gathers without arithmetic; the mode rule of the nearest upsample.
-enum NodeKind { N_INPUT, N_CONV, N_ADD, N_MAXPOOL, N_AVGPOOL, N_LINEAR, N_CONCAT, N_UPSAMPLE, N_DECONV, N_SUMPOOL, N_SLICE, N_SHUFFLE };
+// N_MUL / N_HGATE (f8_net_mul, f8_net_hard_gate; f8_mul.hip) likewise: a mul READS like a conv — each operand's int8 form in the mul's format for it, written
+// by the operand's producer — and a hard gate reads its source's int32 form; no matcher counts either among a block's readers.
+enum NodeKind { N_INPUT, N_CONV, N_ADD, N_MAXPOOL, N_AVGPOOL, N_LINEAR, N_CONCAT, N_UPSAMPLE, N_DECONV, N_SUMPOOL, N_SLICE, N_SHUFFLE, N_MUL, N_HGATE };
 struct Node {
     int kind; int a = -1, b = -1; int out = -1;
     f8_conv_desc cd{};                 // conv / linear (as 1x1 conv)
@@ -114,6 +116,9 @@ struct Node {
     bool sum_wide = false;             // sumpool, pass 2: sumpool_wide_kernel (option sumpool_wide); false: the block walker
     int cm_first = 0, cm_groups = 0;   // slice: the first source channel; shuffle: the groups
     int cm_cat = -1;                   // shuffle, pass 2: the concat node in front of it whose operands this launch reads itself (option fuse_shuffle), else -1
+    f8_mul_desc md{};                  // mul: the operand formats and the ReLU (operands a, b)
+    int mul_gate = -1;                 // mul, pass 2: the hard-gate node that produces b and runs inside this launch (option fuse_hgate), else -1
+    int gate_into = -1;                // hard gate, pass 2: the mul node whose launch applies it: no launch and no form of its own
     int cat_into = -1;                 // concat, pass 2: the shuffle node whose launch reads this concat's operands: no launch and no form of its own
     // planning
     int fused_into = -1;               // add: conv node that carries it
@@ -136,7 +141,7 @@ struct Node {
     size_t rc_off = 0, cc_off = 0; int ncc = 0;      // border-class tables (0 = single class)
     ConvTile tile{};
 };
-enum StepKind { S_INPUT, S_CONV, S_DW, S_ADD, S_MAXPOOL, S_AVGPOOL, S_REQUANT, S_OUTPUT, S_FUSED, S_STEMPOOL, S_IR, S_P12, S_CHAIN, S_BCHAIN, S_HEAD2, S_IRCHAIN, S_DWS, S_DWS7, S_IRK, S_GCONV, S_CONCAT, S_UPSAMPLE, S_DECONV, S_SUMPOOL, S_CHANMAP };
+enum StepKind { S_INPUT, S_CONV, S_DW, S_ADD, S_MAXPOOL, S_AVGPOOL, S_REQUANT, S_OUTPUT, S_FUSED, S_STEMPOOL, S_IR, S_P12, S_CHAIN, S_BCHAIN, S_HEAD2, S_IRCHAIN, S_DWS, S_DWS7, S_IRK, S_GCONV, S_CONCAT, S_UPSAMPLE, S_DECONV, S_SUMPOOL, S_CHANMAP, S_MUL, S_HGATE };
 // The kernel of a step whose kind has several, chosen once by the step's emitter (pass 3); bind_step, run_step and f8_net_autotune switch on it.
 //   S_CONV:  conv_igemm (f8_kernels.hip), the LDS-patch 3x3 (f8_conv3x3.hip), conv1x1_wreg (f8_wreg.hip), conv1x1_wstat (f8_wstat.hip),
 //            conv3x3s2_wreg (f8_s2conv.hip), the 1x1 conv + average pool (f8_pool.hip), the classifier fc_dense (f8_fc.hip)
@@ -167,7 +172,7 @@ struct Step {
     double bytes_per_img = 0, bytes_const = 0, ops_per_img = 0;
     double valu_per_img = 0;           // ESSENTIAL vector lane-operations per image (f8_net_launch_valu): what the reference's semantics need once the MFMAs are done
     // the launcher's arguments as far as the plan decides them (bind_step); run_step copies them and adds what the run decides
-    std::variant<std::monostate, ConvArgs, StemPoolArgs, FusedArgs, ChainArgs, BChainArgs, BCChainArgs, IRArgs, IRKArgs, IRChainArgs, DwsArgs, Dws7Args, DwArgs, GConvArgs, AddArgs, PoolArgs, AvgArgs, OutArgs, ConcatArgs, UpsampleArgs, DeconvArgs, SumPoolArgs, ChanMapArgs> args;
+    std::variant<std::monostate, ConvArgs, StemPoolArgs, FusedArgs, ChainArgs, BChainArgs, BCChainArgs, IRArgs, IRKArgs, IRChainArgs, DwsArgs, Dws7Args, DwArgs, GConvArgs, AddArgs, PoolArgs, AvgArgs, OutArgs, ConcatArgs, UpsampleArgs, DeconvArgs, SumPoolArgs, ChanMapArgs, MulArgs> args;
     int inst = 0;                      // the instance the launcher starts (the family's *_inst, f8_internal.h; bind_step)
     // S_CHAIN / S_BCHAIN: geometry, workgroups per image and resident per CU, the 7x7 cluster form (f8_cchain.hip)
     int C = 0, MID = 0, H = 0, W = 0, cin0 = 0, tiles = 0, wg_per_cu = 1; bool cluster = false;
@@ -313,6 +318,10 @@ static int64_t tensor_amax(f8_net* net, int t, int depth = 0) {
             if (a >= 0 && sa >= 0 && sa <= 31 && a <= (cap >> sa)) m = a << sa;
         } else if (nd.kind == N_SLICE || nd.kind == N_SHUFFLE) {      // a subset / a permutation of the source's values
             m = tensor_amax(net, nd.a, depth + 1);
+        } else if (nd.kind == N_MUL) {                       // the product of the two formats' clamp bounds
+            m = (int64_t)(nd.md.a_signed ? 127 : 255) * (nd.md.b_signed ? 127 : 255);
+        } else if (nd.kind == N_HGATE) {                     // 0 .. 6 * 2^fl (fl <= 28: f8_net_hard_gate)
+            m = int64_t(6) << T.fl;
         } else if (nd.kind == N_SUMPOOL) {                   // at most kernel^2 taps of the source's bound, under the same cap
             const int64_t a = tensor_amax(net, nd.a, depth + 1);
             const int64_t kk = (int64_t)nd.sum_k * nd.sum_k;
@@ -412,6 +421,7 @@ static const OptKey kOptKeys[] = {
     {"sumpool_wide", "F8_SUMPOOL_WIDE", &Options::sumpool_wide, 0, 2, true},
     {"chanmap_i8", "F8_CHANMAP_I8", &Options::chanmap_i8, 0, 1, true},
     {"fuse_shuffle", "F8_FUSE_SHUFFLE", &Options::fuse_shuffle, 0, 1, true},
+    {"fuse_hgate", "F8_FUSE_HGATE", &Options::fuse_hgate, 0, 1, true},
 };
 static const OptKey* find_opt(const char* key) {
     if (!key) return nullptr;
@@ -816,6 +826,49 @@ int f8_net_channel_shuffle(f8_net* net, int src, int groups) {
     if (groups == s.C) return fail(F8_ERR_INVALID, "f8_net_channel_shuffle: groups == channels (%d) is the identity: use the source", s.C);
     if (groups > F8_MAX_CONCAT) return fail(F8_ERR_UNSUPPORTED, "f8_net_channel_shuffle: at most %d groups (got %d)", F8_MAX_CONCAT, groups);
     Node nd; nd.kind = N_SHUFFLE; nd.a = src; nd.cm_groups = groups;
+    net->nodes.push_back(nd);
+    const int id = (int)net->nodes.size() - 1;
+    const int t = new_tensor(net, s.C, s.H, s.W, s.fl, id);
+    net->nodes[id].out = t;
+    net->tensors[src].consumers.push_back(id);
+    return t;
+}
+
+int f8_net_mul(f8_net* net, int a, int b, const f8_mul_desc* desc) {
+    if (!net) return fail(F8_ERR_INVALID, "f8_net_mul: null net");
+    if (net->finalized) return fail(F8_ERR_STATE, "f8_net_mul: net already finalized");
+    if (!desc) return fail(F8_ERR_INVALID, "f8_net_mul: null desc");
+    if (const int rc = check_t(net, a, "f8_net_mul")) return rc;
+    if (const int rc = check_t(net, b, "f8_net_mul")) return rc;
+    const Tensor A = net->tensors[a], B = net->tensors[b];
+    const bool same = B.C == A.C && B.H == A.H && B.W == A.W, gate = B.C == A.C && B.H == 1 && B.W == 1;
+    if (!same && !gate)
+        return fail(F8_ERR_INVALID, "f8_net_mul: b is [%d, %d, %d]: neither a's shape [%d, %d, %d] nor [%d, 1, 1]", B.C, B.H, B.W, A.C, A.H, A.W, A.C);
+    // the operand formats are consumer formats: the conv's limits and shift range (consumer_format)
+    f8_conv_desc fa{}, fb{};
+    fa.input_fl = desc->a_fl; fa.input_signed = desc->a_signed != 0; fa.quant_input = 1;
+    fb.input_fl = desc->b_fl; fb.input_signed = desc->b_signed != 0; fb.quant_input = 1;
+    int n = 0;
+    if (const int rc = consumer_format(A, fa, &n, "f8_net_mul (a)")) return rc;
+    if (const int rc = consumer_format(B, fb, &n, "f8_net_mul (b)")) return rc;
+    Node nd; nd.kind = N_MUL; nd.a = a; nd.b = b; nd.md = *desc;
+    nd.md.a_signed = desc->a_signed != 0; nd.md.b_signed = desc->b_signed != 0; nd.md.relu = desc->relu != 0;
+    net->nodes.push_back(nd);
+    const int id = (int)net->nodes.size() - 1;
+    const int t = new_tensor(net, A.C, A.H, A.W, desc->a_fl + desc->b_fl, id);
+    net->nodes[id].out = t;
+    net->tensors[a].consumers.push_back(id);
+    net->tensors[b].consumers.push_back(id);      // (a == b: twice — two reads)
+    return t;
+}
+
+int f8_net_hard_gate(f8_net* net, int src) {
+    if (!net) return fail(F8_ERR_INVALID, "f8_net_hard_gate: null net");
+    if (net->finalized) return fail(F8_ERR_STATE, "f8_net_hard_gate: net already finalized");
+    if (const int rc = check_t(net, src, "f8_net_hard_gate")) return rc;
+    const Tensor s = net->tensors[src];
+    if (s.fl < 0 || s.fl > 28) return fail(F8_ERR_INVALID, "f8_net_hard_gate: source fraclen %d outside [0, 28] (6 * 2^fl must fit int32)", s.fl);
+    Node nd; nd.kind = N_HGATE; nd.a = src;
     net->nodes.push_back(nd);
     const int id = (int)net->nodes.size() - 1;
     const int t = new_tensor(net, s.C, s.H, s.W, s.fl, id);
@@ -2186,6 +2239,24 @@ static void plan_tensor_forms(f8_net* net) {
                 ask_sources(net, nd.cm_cat >= 0 ? cat.srcs : std::vector<int>{nd.a}, s.fl, o.forms, nd.bytes_mode);
                 break;
             }
+            case N_MUL: {
+                // reads like a conv with quant_input = 1: each operand's int8 form in the mul's format for it, written by the operand's producer (a == b in two
+                // formats: two forms of one tensor; a third format on a tensor: a requant: step, select_outputs).  A hard gate that only this mul's b operand
+                // reads (option fuse_hgate) runs inside the launch, which then reads the GATE's source in int32; the gate gets no form and no launch.
+                Tensor& A = T[nd.a]; Tensor& B = T[nd.b];
+                add_form(A, FORM_I8, A.fl - nd.md.a_fl, nd.md.a_signed);
+                Node& gp = ND[B.prod];
+                if (opt.fuse_hgate && gp.kind == N_HGATE && B.consumers.size() == 1 && nd.a != nd.b && !is_output(net, nd.b)) {
+                    nd.mul_gate = B.prod; gp.gate_into = i;
+                    add_form(T[gp.a], FORM_I32, 0, 0);
+                } else {
+                    add_form(B, FORM_I8, B.fl - nd.md.b_fl, nd.md.b_signed);
+                }
+                break;
+            }
+            case N_HGATE:
+                if (nd.gate_into < 0) add_form(T[nd.a], FORM_I32, 0, 0);      // (fused: the mul, a later node, asked the source already)
+                break;
             case N_UPSAMPLE: {
                 // the mode rule alone, for nearest: the fraclen — so the shift — is the source's and no bound on the values is needed
                 nd.bytes_mode = opt.upsample_i8 && nd.up_mode == F8_UP_NEAREST && int8_forms_only(net, nd.out);
@@ -2819,6 +2890,43 @@ static int emit_chanmap(f8_net* net, int i, Step& st, std::vector<int>* extra) {
 }
 
 
+// f8_net_mul; a hard gate fused into it (Node::mul_gate) makes the launch read the gate's int32 source as its b
+static int emit_mul(f8_net* net, int i, Step& st, std::vector<int>* extra) {
+    auto& T = net->tensors;
+    const Node& nd = net->nodes[i];
+    const Tensor& A = T[nd.a]; const Tensor& B = T[nd.b]; const Tensor& o = T[nd.out];
+    const bool fused = nd.mul_gate >= 0, bcast = B.H * B.W != A.H * A.W;
+    st.kind = S_MUL;
+    st.src_t = nd.a; st.src_f = find_form(A, FORM_I8, A.fl - nd.md.a_fl, nd.md.a_signed);
+    if (fused) { st.res_t = net->nodes[nd.mul_gate].a; st.res_f = find_form(T[st.res_t], FORM_I32, 0, 0); }
+    else { st.res_t = nd.b; st.res_f = find_form(B, FORM_I8, B.fl - nd.md.b_fl, nd.md.b_signed); }
+    if (st.src_f < 0 || st.res_f < 0) return fail(F8_ERR_STATE, "f8_net_finalize: planner bug: an operand of mul t%d lacks its form", nd.out);
+    st.relu1 = nd.md.relu;
+    select_outputs_or_i32(net, nd.out, &st.out, extra);
+    const double px = (double)o.H * o.W, bpx = (double)B.H * B.W;
+    st.bytes_per_img = px * o.C + bpx * o.C * (fused ? 4 : 1) + px * o.C * ((st.out.f32 >= 0 ? 4 : 0) + out_forms8(st));      // real bytes, each once
+    st.valu_per_img = px * o.C * (1 + (nd.md.relu ? 1 : 0) + 3 * out_forms8(st)) + (fused ? bpx * o.C * 5 : 0);      // the multiply, the ReLU, 3 per int8 value produced; a fused gate: clamp + offset + 3
+    char tok[48];
+    snprintf(tok, sizeof tok, "%s%s_%s:", fused ? "hgate+" : "", bcast ? "chmul" : "mul", st.out.f32 >= 0 ? "i32" : "i8");
+    st.name = tok + tname(net, nd.out);
+    return F8_OK;
+}
+
+// f8_net_hard_gate as a launch of its own
+static int emit_hgate(f8_net* net, int i, Step& st, std::vector<int>* extra) {
+    auto& T = net->tensors;
+    const Node& nd = net->nodes[i];
+    const Tensor& s = T[nd.a]; const Tensor& o = T[nd.out];
+    st.kind = S_HGATE;
+    st.src_t = nd.a; st.src_f = find_form(s, FORM_I32, 0, 0);
+    select_outputs_or_i32(net, nd.out, &st.out, extra);
+    const double px = (double)o.H * o.W;
+    st.bytes_per_img = px * o.C * (4 + (st.out.f32 >= 0 ? 4 : 0) + out_forms8(st));
+    st.valu_per_img = px * o.C * (2 + 3 * out_forms8(st));      // clamp + offset; 3 per int8 value produced
+    st.name = "hgate:" + tname(net, nd.out);
+    return F8_OK;
+}
+
 static int emit_sumpool(f8_net* net, int i, Step& st, std::vector<int>* extra) {
     auto& T = net->tensors;
     const Node& nd = net->nodes[i];
@@ -2891,6 +2999,7 @@ static int emit_steps(f8_net* net, int max_batch) {
         if (nd.kind == N_MAXPOOL && nd.sp_conv >= 0) continue;
         if (nd.kind == N_AVGPOOL && nd.pool_host >= 0) continue;     // runs in its conv's launch
         if (nd.kind == N_CONCAT && nd.cat_into >= 0) continue;       // the shuffle behind it reads its operands
+        if (nd.kind == N_HGATE && nd.gate_into >= 0) continue;       // the mul behind it applies it
         Step st; st.node = i;
         std::vector<int> extra;
         int rc = F8_OK;
@@ -2905,6 +3014,8 @@ static int emit_steps(f8_net* net, int max_batch) {
             case N_DECONV: rc = emit_deconv(net, i, st, &extra); break;
             case N_SUMPOOL: rc = emit_sumpool(net, i, st, &extra); break;
             case N_SLICE: case N_SHUFFLE: rc = emit_chanmap(net, i, st, &extra); break;
+            case N_MUL: rc = emit_mul(net, i, st, &extra); break;
+            case N_HGATE: rc = emit_hgate(net, i, st, &extra); break;
         }
         if (rc) return rc;
         net->steps.push_back(st);
@@ -3518,6 +3629,26 @@ static int bind_step(f8_net* net, Step& st) {
             snprintf(kb, sizeof kb, "%s", chanmap_kernel_name(st.inst = chanmap_inst(a, nd.bytes_mode)));
             out_formats(a.q); st.args = a; break;
         }
+        case S_MUL: case S_HGATE: {
+            const Tensor& oT = T[nd.out];
+            MulArgs a{};
+            a.C = oT.C; a.Cs = oT.Cs;
+            if (st.kind == S_HGATE) {
+                a.lim = 3 << oT.fl;
+                st.inst = mul_inst(a, 0);
+            } else {
+                const Tensor& bT = T[nd.b];
+                a.HW = oT.H * oT.W; a.dHW = fast_divisor((uint32_t)a.HW);
+                a.bcast = bT.H * bT.W != a.HW; a.gate = nd.mul_gate >= 0; a.relu = st.relu1;
+                if (a.gate) a.lim = 3 << bT.fl;
+                a.ra = Requant::of(T[nd.a].fl - nd.md.a_fl, nd.md.a_signed != 0);
+                a.rb = Requant::of(bT.fl - nd.md.b_fl, nd.md.b_signed != 0);
+                st.inst = mul_inst(a, out32 ? 1 : 2);
+                a.dVpp = fast_divisor((uint32_t)(a.Cs / mul_vector_bytes(st.inst)));
+            }
+            snprintf(kb, sizeof kb, "%s", mul_kernel_name(st.inst));
+            out_formats(a.q); st.args = a; break;
+        }
         case S_SUMPOOL: {
             const Tensor& sT = T[st.src_t]; const Tensor& oT = T[nd.out];
             SumPoolArgs a{};
@@ -3956,6 +4087,16 @@ static int run_step(const f8_net* net, const RunIO& io, const Step& st, int n0, 
             a.M = N * T[st.out.t].H * T[st.out.t].W;
             fill_out(&a.out32, a.q);
             e = launch_chanmap(a, st.inst, s);
+            break;
+        }
+        case S_MUL: case S_HGATE: {
+            MulArgs a = std::get<MulArgs>(st.args);
+            const Tensor& o = T[st.out.t];
+            if (st.kind == S_MUL) { a.a = (const int8_t*)fp(T[st.src_t].forms[st.src_f]); a.b = fp(T[st.res_t].forms[st.res_f]); }
+            else a.b = fp(T[st.src_t].forms[st.src_f]);
+            a.M = N * o.H * o.W;
+            fill_out(&a.out32, a.q);
+            e = launch_mul(a, st.inst, s);
             break;
         }
         case S_OUTPUT: {

@@ -12,7 +12,7 @@ import os
 import numpy as np
 
 from . import _lib, topology
-from ._lib import ConvDesc, LinearDesc, check
+from ._lib import ConvDesc, LinearDesc, MulDesc, check
 
 AVGPOOL_SHIFT = 6   # FXQAvgPool2d(7).shiftnum = round(log2(49)), fix_quant_ops.py:121-122
 
@@ -153,6 +153,27 @@ class F8Net:
         if label:
             self._L.f8_net_set_label(self._h, t, label.encode())
         return t
+
+    def mul(self, a, b, *, a_fl, a_signed, b_fl, b_signed=False, relu=False, label=None):
+        """Fixed-point product of two activations (f8_net_mul): a requantised to (a_fl, a_signed) times b requantised to (b_fl, b_signed), at fraclen
+        a_fl + b_fl.  b has a's shape (element-wise) or is [C, 1, 1] (a per-image channel gate: the scale of a squeeze-and-excitation block)."""
+        d = MulDesc(a_fl=int(a_fl), a_signed=int(bool(a_signed)), b_fl=int(b_fl), b_signed=int(bool(b_signed)), relu=int(bool(relu)))
+        t = check(self._L.f8_net_mul(self._h, a, b, ctypes.byref(d)))
+        if label:
+            self._L.f8_net_set_label(self._h, t, label.encode())
+        return t
+
+    def hard_gate(self, src, label=None):
+        """relu6(x + 3) in fixed point (f8_net_hard_gate): clamp(x, -3 * 2^fl, 3 * 2^fl) + 3 * 2^fl at the source's fraclen — the numerator of
+        hard-sigmoid; its 1 / 6 is a constant real scale for the exporter to fold into the next conv's weights."""
+        t = check(self._L.f8_net_hard_gate(self._h, src))
+        if label:
+            self._L.f8_net_set_label(self._h, t, label.encode())
+        return t
+
+    def hard_swish(self, src, *, x_fl, x_signed, g_fl, label=None):
+        """x * relu6(x + 3) (six times hard-swish): mul(src, hard_gate(src)) with x read at (x_fl, x_signed) and the gate, 0 .. 6, at unsigned g_fl."""
+        return self.mul(src, self.hard_gate(src), a_fl=x_fl, a_signed=x_signed, b_fl=g_fl, b_signed=False, label=label)
 
     def maxpool(self, src, k=3, stride=2, pad=1, label=None):
         t = check(self._L.f8_net_maxpool(self._h, src, k, stride, pad))

@@ -16,6 +16,8 @@ opset-11 vocabulary is written directly from the integer graph — per op the no
     channel concatenation          [Pow/Cast/Mul per operand at a smaller fraction length,] Concat(axis=1)
     channel slice                  Slice(starts [a], ends [b], axes [1], steps [1])
     channel shuffle                Reshape([-1, g, C / g, H, W]), Transpose(perm [0, 2, 1, 3, 4]), Reshape([-1, C, H, W])
+    fixed-point product            the requant of each operand as in front of a conv, [Unsqueeze(axes [2, 3]) of a [N, C] gate vector,] Mul [, Relu]
+    hard gate relu6(x + 3)         Clip(x, -3 * 2^fl, 3 * 2^fl), Add(3 * 2^fl)
     upsampling, nearest            Resize(nearest, asymmetric, floor; scales [1, 1, sh, sw])
     upsampling, bilinear           Cast(f32), Resize(linear, half_pixel; scales [1, 1, s, s]), Mul(4 s^2), Cast(i32)
     x.view(x.size(0), -1)          Shape, Gather, Unsqueeze, Concat, Reshape         (fix_resnet.py:371)
@@ -114,12 +116,28 @@ class _Writer:
         return self.cast(self.emit('Pow', [self.const(2.0, np.float32), e]), onnx_io.INT32)
 
 
+def _requant(w, s, n, signed):
+    """int_op_only_fix_quant of value s by shift n as the tracer writes it (the conv branch of export_graph keeps its own copy: it merges two
+    requants of a max-pool result).  Returns the int32 value."""
+    lo, hi = (-127.0, 127.0) if signed else (0.0, 255.0)
+    if n > 0:
+        h = 1 << (n - 1)
+        a = w.emit('Add', [s, w.const(h, np.int32)])
+        m = w.emit('Mod', [s, w.const(1 << n, np.int32)], {'fmod': 0})
+        e = w.emit('Equal', [w.cast(m, onnx_io.INT64), w.const(h, np.int64)])
+        v = w.emit('Where', [e, w.emit('Mul', [w.emit('Div', [a, w.pow2(n + 1)]), w.pow2(1)]), w.emit('Div', [a, w.pow2(n)])])
+    else:
+        v = w.emit('Mul', [s, w.pow2(-n)])
+    return w.cast(w.emit('Clip', [v, w.const(lo, np.float32), w.const(hi, np.float32)]), onnx_io.INT32)
+
+
 def export_graph(ig: IntGraph) -> bytes:
     """IntGraph -> serialized ModelProto."""
     w = _Writer()
     inits = {}
     name = {}
     shared = {}
+    flat = set()                                                     # tensors the file holds as [N, C]: a Gemm's result and what follows it element-wise
     for t, o in enumerate(ig.ops):
         if o.kind == 'input':
             name[t] = 'input'
@@ -167,11 +185,26 @@ def export_graph(ig: IntGraph) -> bytes:
                                                   'pads': [o.pad] * 4, 'strides': [o.stride] * 2})
             else:
                 y = w.emit('Gemm', ins, {'alpha': 1.0, 'beta': 1.0, 'transB': 1})
+                flat.add(t)
         elif o.kind == 'add':
             m = w.emit('Mul', [name[o.src], w.pow2(o.shift)])
             v = w.emit('Add', [name[o.src2], m] if o.swap else [m, name[o.src2]])   # `res += x`: res first
             v = w.emit('Clip', [v, w.const(-2147483647.0, np.float32), w.const(2147483647.0, np.float32)])
             y = w.cast(v, onnx_io.INT32)
+        elif o.kind == 'hgate':                                      # relu6(x + 3) at fraction length fl = o.shift: clamp first, then the offset
+            lim = 3 << o.shift
+            v = w.emit('Clip', [name[o.src], w.const(float(-lim), np.float32), w.const(float(lim), np.float32)])
+            y = w.emit('Add', [w.cast(v, onnx_io.INT32), w.const(lim, np.int32)])
+            if o.src in flat:
+                flat.add(t)
+        elif o.kind == 'mul':
+            A = _requant(w, name[o.src], o.shifts[0], o.signed)
+            B = _requant(w, name[o.src2], o.shifts[1], o.signed2)
+            if o.src2 in flat and o.src not in flat:
+                B = w.emit('Unsqueeze', [B], {'axes': [2, 3]})
+            y = w.emit('Mul', [A, B])
+            if o.src in flat:
+                flat.add(t)
         elif o.kind == 'concat':                                     # torch.cat(dim=1); `x << k` as in the residual join
             y = w.emit('Concat', [name[s] if k == 0 else w.emit('Mul', [name[s], w.pow2(k)]) for s, k in zip(o.srcs, o.shifts)], {'axis': 1})
         elif o.kind == 'slice':                                      # x[:, a:b]
@@ -203,6 +236,7 @@ def export_graph(ig: IntGraph) -> bytes:
             v = w.emit('ReduceSum', [v], {'axes': [-1], 'keepdims': 0})
             v = w.emit('ReduceSum', [v], {'axes': [-1], 'keepdims': 0})
             y = w.cast(v, onnx_io.INT32)
+            flat.add(t)
         else:
             raise ValueError(o.kind)
         if o.relu:

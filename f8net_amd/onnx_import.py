@@ -36,9 +36,9 @@ class OnnxImportError(ValueError):
 
 @dataclass
 class IntOp:
-    kind: str                      # input | conv | deconv | linear | add | maxpool | avgpool | avgpool2d | concat | upsample | slice | shuffle
+    kind: str                      # input | conv | deconv | linear | add | maxpool | avgpool | avgpool2d | concat | upsample | slice | shuffle | mul | hgate
     src: int = -1                  # tensor id (index into IntGraph.ops)
-    src2: int = -1                 # add: the operand that is NOT shifted
+    src2: int = -1                 # add: the operand that is NOT shifted; mul: operand b (of src's shape, or [C, 1, 1])
     weight: np.ndarray = None
     bias: np.ndarray = None
     stride: int = 1
@@ -47,14 +47,17 @@ class IntOp:
     kernel: int = 0
     shift: int = None              # conv/linear: requant n (None = input already in format); add: k of `src << k`; avgpool2d: what the window's sum adds
                                    # to the fraction length (kernel, stride, pad: the window)
-    signed: bool = False           # conv/linear: clamp range of the requant (+-127 vs 0..255)
+                                   # hgate: the source's fraction length fl itself (the file holds 3 * 2^fl); mul: unused (`shifts`)
+    signed: bool = False           # conv/linear: clamp range of the requant (+-127 vs 0..255); mul: of operand a
+    signed2: bool = False          # mul: clamp range of operand b's requant
     relu: bool = False
     swap: bool = False             # add: the shifted operand is the Add's second input (`res += x << k`) — cosmetic
     key: str = ''                  # state_dict key of the layer ('head.0', 'stage_0_layer_0.body.0', ...)
     shape: tuple = None            # input: (C, H, W)
     dilation: int = 1              # conv: spacing of the kernel's taps (ONNX `dilations`, both equal)
     srcs: list = None              # concat: the operands in channel order (tensor ids)
-    shifts: list = None            # concat: k_i of `srcs[i] << k_i`, the alignment to the largest fraclen (the smallest is 0)
+    shifts: list = None            # concat: k_i of `srcs[i] << k_i`, the alignment to the largest fraclen (the smallest is 0); mul: [n_a, n_b], the requant
+                                   # shifts of the two operands
     mode: str = None               # upsample: 'nearest' | 'bilinear' (half-pixel centres; the result is the interpolated value times 4 scale^2)
     scale: tuple = None            # upsample: (scale_h, scale_w)
     first: int = 0                 # slice: the first channel
@@ -116,6 +119,26 @@ class IntGraph:
                     eq(t, s, k)
             elif o.kind in ('maxpool', 'slice', 'shuffle'):
                 eq(t, o.src, 0)
+            elif o.kind == 'hgate':                  # 3 * 2^fl is a constant of the graph: the source's fraction length is pinned absolutely
+                if not 0 <= o.shift <= 28:
+                    raise OnnxImportError(f'hard gate at fraction length {o.shift}: outside 0 .. 28 (f8_net_hard_gate)')
+                eq(o.src, ZERO, o.shift)
+                eq(t, o.src, 0)
+            elif o.kind == 'mul':
+                # V[t] = a_fl + b_fl is a sum of two unknowns, no difference constraint — unless b's format is anchored: b is a hard gate's result, whose
+                # fraction length is a constant, so b_fl is one and V[t] = V[a] - n_a + b_fl
+                g = self.ops[o.src2]
+                if g.kind != 'hgate':
+                    raise OnnxImportError('Mul of two activations whose second operand is not a hard gate\'s result: its format is not anchored, so the '
+                                          'product\'s fraction length (a sum of two unknowns) is no difference constraint')
+                n_a, n_b = o.shifts
+                b_fl = g.shift - n_b
+                if not 0 <= b_fl <= (7 if o.signed2 else 8):
+                    raise OnnxImportError(f'Mul: the gate operand\'s format fraction length {b_fl} is outside the 8-bit formats')
+                lim = 7 if o.signed else 8
+                ge(o.src, ZERO, n_a)                 # a_fl = V[a] - n_a >= 0
+                ge(ZERO, o.src, -(n_a + lim))
+                eq(t, o.src, b_fl - n_a)
             elif o.kind == 'upsample':
                 eq(t, o.src, 0 if o.mode == 'nearest' else upsample_fl_gain(o.scale))
                 if o.mode != 'nearest':
@@ -201,6 +224,11 @@ class IntGraph:
                 ids[t] = net.slice(ids[o.src], o.first, o.first + o.channels)
             elif o.kind == 'shuffle':
                 ids[t] = net.channel_shuffle(ids[o.src], o.groups)
+            elif o.kind == 'hgate':
+                ids[t] = net.hard_gate(ids[o.src])
+            elif o.kind == 'mul':
+                ids[t] = net.mul(ids[o.src], ids[o.src2], a_fl=V[o.src] - o.shifts[0], a_signed=o.signed, b_fl=V[o.src2] - o.shifts[1],
+                                 b_signed=o.signed2, relu=o.relu)
             elif o.kind == 'avgpool2d':
                 ids[t] = net.avgpool(ids[o.src], o.kernel, o.stride, o.pad, shift=o.shift)
             elif o.kind == 'avgpool':
@@ -236,7 +264,7 @@ def tensor_shapes(ops):
             out.append((C, 1, 1))
         elif o.kind == 'slice':
             out.append((o.channels, H, W))
-        else:                                                        # add, shuffle
+        else:                                                        # add, shuffle, hgate, mul (operand a's shape)
             out.append((C, H, W))
     return out
 
@@ -504,6 +532,8 @@ def import_graph(model, input_signed=False) -> IntGraph:
                     raise OnnxImportError(f'Reshape behind the shuffle\'s Transpose to {shape}: expected [N, {C}, {H}, {W}]')
                 ig.ops.append(IntOp('shuffle', src=e[1], groups=e[2]))
                 val[out] = ('T', len(ig.ops) - 1)
+        elif op == 'Unsqueeze' and val.get(nd.inputs[0], ('?',))[0] in ('T', 'clip'):
+            val[out] = val[nd.inputs[0]]                           # a [N, C] gate vector lifted to [N, C, 1, 1] in front of a Mul: no arithmetic
         elif op in ('Shape', 'Gather', 'Unsqueeze', 'Concat'):
             val[out] = ('opaque',)                                 # the `x.view(x.size(0), -1)` plumbing before the FC
         elif op == 'Reshape':
@@ -529,11 +559,33 @@ def import_graph(model, input_signed=False) -> IntGraph:
                     raise OnnxImportError(f'Resize(linear) by {scale[0]} must be followed by a Mul by 2^{gain} = {1 << gain}')
                 ig.ops.append(IntOp('upsample', src=src, mode='bilinear', scale=scale))
                 val[out] = ('T', len(ig.ops) - 1)
+            elif is_const(y) and op == 'Add' and val.get(x, ('?',))[0] == 'clip' and val[x][1][0] == 'T':
+                # the hard gate relu6(x + 3) in fixed point: Clip(x, -3 * 2^fl, 3 * 2^fl) then Add(3 * 2^fl)
+                _, e, lo, hi = val[x]
+                c = const(y, 'Add')
+                if not (-lo == hi == c):
+                    raise OnnxImportError(f'Clip [{lo}, {hi}] + {c} of an activation: a hard gate needs equal constants (Clip(x, -L, L) + L)')
+                if hi <= 0 or hi % 3 or (hi // 3) & (hi // 3 - 1):
+                    raise OnnxImportError(f'Clip(x, -{hi}, {hi}) + {hi} of an activation: a hard gate\'s constant is 3 * 2^fl, {hi} is not')
+                ig.ops.append(IntOp('hgate', src=e[1], shift=(hi // 3).bit_length() - 1))
+                val[out] = ('T', len(ig.ops) - 1)
             elif is_const(y):
                 tag = {'Add': 'addc', 'Mul': 'mul', 'Div': 'div', 'Mod': 'mod', 'Equal': 'eq'}[op]
                 val[out] = (tag, val[x], const(y, op))
             elif op == 'Add':
                 val[out] = ('add', val[x], val[y])
+            elif op == 'Mul':
+                # the product of two activations, each behind its requantisation; the one that reads a hard gate's result is operand b
+                ra, rb = requant_src(x, 'Mul'), requant_src(y, 'Mul')
+                if ra[1] is None or rb[1] is None:
+                    raise OnnxImportError('Mul of two activations that are not both requantised to 8-bit formats')
+                if ig.ops[rb[0]].kind != 'hgate' and ig.ops[ra[0]].kind == 'hgate':
+                    ra, rb = rb, ra
+                if ig.ops[rb[0]].kind != 'hgate':
+                    raise OnnxImportError('Mul of two activations of which none is a hard gate\'s result: no operand format is anchored, so the '
+                                          'product\'s fraction length cannot be solved (only x * hard_gate(.) is imported)')
+                ig.ops.append(IntOp('mul', src=ra[0], src2=rb[0], shifts=[ra[1], rb[1]], signed=ra[2], signed2=rb[2]))
+                val[out] = ('T', len(ig.ops) - 1)
             else:
                 raise OnnxImportError(f'{op} of two activations')
         elif op == 'Where':
@@ -557,7 +609,7 @@ def import_graph(model, input_signed=False) -> IntGraph:
                 val[out] = ('clip', e, lo, hi)
         elif op == 'Relu':
             e = val[nd.inputs[0]]
-            if e[0] != 'T' or ig.ops[e[1]].kind not in ('conv', 'deconv', 'add') or uses.get(nd.inputs[0], 0) != 1:
+            if e[0] != 'T' or ig.ops[e[1]].kind not in ('conv', 'deconv', 'add', 'mul') or uses.get(nd.inputs[0], 0) != 1:
                 raise OnnxImportError('Relu on something other than a single-use conv / join result')
             ig.ops[e[1]].relu = True                               # nn.ReLU(inplace=True) on the producer's tensor
             val[out] = e

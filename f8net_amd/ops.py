@@ -201,6 +201,43 @@ class F8ChannelShuffle(nn.Module):
         return res
 
 
+class F8HardSwish(nn.Module):
+    """Six times nn.Hardswish on int32 device tensors with a HIP forward (`torch.ops.f8net.mul_q` with the hard gate on its own operand):
+    x_q * relu6(x + 3) with x_q = x requantised to (x_fl, x_signed) and the gate, 0 .. 6, requantised to unsigned g_fl; the result's fraclen is
+    x_fl + g_fl.  The 1 / 6 is a constant real scale: fold it into the next layer's weights."""
+
+    def __init__(self, x_fl, x_signed=True, g_fl=5):
+        super().__init__()
+        self.x_fl, self.x_signed, self.g_fl = int(x_fl), bool(x_signed), int(g_fl)
+        self.int_op_only = True
+
+    def forward(self, x):
+        _require_dev_i32(x, 'F8HardSwish')
+        fl = x.output_fraclen
+        res = torch.ops.f8net.mul_q(x, x, fl, fl, self.x_fl, self.x_signed, self.g_fl, False, True, False)
+        setattr(res, 'output_fraclen', self.x_fl + self.g_fl)
+        return res
+
+
+class F8ChannelGate(nn.Module):
+    """The scale of a squeeze-and-excitation block with a hard-sigmoid gate, times 6: x_q * relu6(s + 3) broadcast over H x W, x [N, C, H, W]
+    requantised to (x_fl, x_signed), s [N, C, 1, 1] the second FC's result, its gate requantised to unsigned g_fl (`torch.ops.f8net.mul_q`).
+    The result's fraclen is x_fl + g_fl; the 1 / 6 is left to the next layer's weights."""
+
+    def __init__(self, x_fl, x_signed=False, g_fl=5):
+        super().__init__()
+        self.x_fl, self.x_signed, self.g_fl = int(x_fl), bool(x_signed), int(g_fl)
+        self.int_op_only = True
+
+    def forward(self, x, s):
+        _require_dev_i32(x, 'F8ChannelGate')
+        _require_dev_i32(s, 'F8ChannelGate')
+        s4 = s.reshape(s.shape[0], s.shape[1], 1, 1)
+        res = torch.ops.f8net.mul_q(x, s4, x.output_fraclen, s.output_fraclen, self.x_fl, self.x_signed, self.g_fl, False, True, False)
+        setattr(res, 'output_fraclen', self.x_fl + self.g_fl)
+        return res
+
+
 class F8MaxPool2d(nn.Module):
     """Head max-pool (fix_resnet.py:358-359 float detour / FXQMaxPool2d): exact integer max."""
 

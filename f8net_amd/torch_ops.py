@@ -14,6 +14,9 @@ the dispatcher.
     f8net::avgpool_sum(x)                            FXQAvgPool2d int branch          fix_quant_ops.py:126-134
     f8net::maxpool(x, k, stride, pad)                head max-pool                    fix_resnet.py:358-359
     f8net::channel_shuffle(x, groups)                torch.nn.functional.channel_shuffle on int32 (f8_net_channel_shuffle; no reference call site)
+    f8net::mul_q(a, b, a_src_fl, b_src_fl, a_fl, a_signed, b_fl, b_signed, hard_gate_b, relu)
+                                                     requant(a) * requant(b), b of a's shape or [N, C, 1, 1]; hard_gate_b: b is relu6(b + 3) in fixed point
+                                                     first (f8_net_mul, f8_net_hard_gate; no reference call site)
     f8net::net_forward(x, handle)                    IntModel.forward                 fix_resnet.py:352-383 (handle: register_net)
     f8net::net_forward_taps(x, handle)               ... of a net with further outputs (F8Net.output called more than once): all of them
     f8net::net_forward_f32(images, handle, normalize)  forward_loss input quantisation + IntModel.forward, fix_train.py:683-692
@@ -45,6 +48,7 @@ _DEF.define('avgpool_sum(Tensor x) -> Tensor')
 _DEF.define('avgpool2d_sum(Tensor x, int k, int stride, int pad) -> Tensor')
 _DEF.define('maxpool(Tensor x, int k, int stride, int pad) -> Tensor')
 _DEF.define('channel_shuffle(Tensor x, int groups) -> Tensor')
+_DEF.define('mul_q(Tensor a, Tensor b, int a_src_fl, int b_src_fl, int a_fl, bool a_signed, int b_fl, bool b_signed, bool hard_gate_b, bool relu) -> Tensor')
 _DEF.define('net_forward(Tensor x, int handle) -> Tensor')
 _DEF.define('net_forward_taps(Tensor x, int handle) -> Tensor[]')
 _DEF.define('net_forward_f32(Tensor images, int handle, bool normalize) -> Tensor')
@@ -295,6 +299,65 @@ def _channel_shuffle(x, groups):
     return _plans.get(('shuffle', x.device.index, C, H, W, groups), (), N, build).run(x).view(N, C, H, W)
 
 
+def _mul_q(a, b, a_src_fl, b_src_fl, a_fl, a_signed, b_fl, b_signed, hard_gate_b, relu):
+    """int_op_only_fix_quant(a, 8, a_fl, a_src_fl, a_signed) * int_op_only_fix_quant(b', 8, b_fl, b_src_fl, b_signed) with b' = b, or
+    clamp(b, -3 * 2^b_src_fl, 3 * 2^b_src_fl) + 3 * 2^b_src_fl when hard_gate_b (f8_net_mul / f8_net_hard_gate): [N, C, H, W] x ([N, C, H, W] |
+    [N, C, 1, 1]) -> [N, C, H, W] at fraclen a_fl + b_fl.  `b is a` with hard_gate_b is hard-swish times 6.
+    A planned net has one input, so the two operands enter as the channels of one tensor at one fraction length F and leave it through two slices
+    (a gate vector: through a 1 x 1 window at stride max(H, W), which also lifts its fraction length).  Only the SHIFTS a_src_fl - a_fl and
+    b_src_fl - b_fl and the gate's 3 * 2^b_src_fl enter the values, so the formats are declared relative to F; operand fraction lengths so far apart
+    that no F keeps both declared formats inside 0 .. 8 (7 signed) raise ValueError, as do gate vectors on maps wider than 64."""
+    _i32(a, 'mul_q')
+    _i32(b, 'mul_q')
+    same = b is a or (b.data_ptr() == a.data_ptr() and b.shape == a.shape)
+    a = a.contiguous()
+    N, C, H, W = a.shape
+    bcast = tuple(b.shape[2:]) == (1, 1) and (H, W) != (1, 1)
+    if tuple(b.shape) != ((N, C, 1, 1) if bcast else (N, C, H, W)):
+        raise ValueError(f'mul_q: b is {tuple(b.shape)}: neither a\'s shape {tuple(a.shape)} nor [{N}, {C}, 1, 1]')
+    n_a, n_b = a_src_fl - a_fl, b_src_fl - b_fl
+    lim_a, lim_b = (7 if a_signed else 8), (7 if b_signed else 8)
+    lift = 0                                                        # what the gate vector's window adds to F
+    if hard_gate_b and not bcast:
+        F = b_src_fl
+    elif hard_gate_b:
+        F = max(n_a, 0)
+        lift = b_src_fl - F
+    else:
+        F = max(n_a, 0) if bcast else max(n_a, n_b, 0)
+        lift = max(0, n_b - F) if bcast else 0
+    fa, fb = F - n_a, F + lift - n_b
+    if not (0 <= fa <= lim_a and 0 <= fb <= lim_b and lift >= 0 and 0 <= F <= 28) or (bcast and max(H, W) > 64):
+        raise ValueError(f'mul_q: shifts {n_a} / {n_b} (hard_gate_b={bool(hard_gate_b)}) on a {H} x {W} map fit no common input fraction length')
+    fmt = dict(a_fl=fa, a_signed=a_signed, b_fl=fb, b_signed=b_signed, relu=relu)
+
+    def build(n):
+        net = F8Net()
+        if same:
+            t = net.input(C, H, W, F)
+            ta = tb = t
+        else:
+            t = net.input(2 * C, H, W, F)
+            ta, tb = net.slice(t, 0, C), net.slice(t, C, 2 * C)
+            if bcast:                                               # pixel (0, 0) of b's channels is the vector
+                tb = net.avgpool(tb, 1, max(H, W), 0, shift=lift)
+        if hard_gate_b:
+            tb = net.hard_gate(tb)
+        net.output(net.mul(ta, tb, **fmt), as_float=False)
+        return net.finalize(n)
+
+    if same:
+        x = a
+    elif bcast:
+        x = a.new_zeros((N, 2 * C, H, W))
+        x[:, :C] = a
+        x[:, C:, 0, 0] = b.reshape(N, C)
+    else:
+        x = torch.cat([a, b.contiguous()], dim=1)
+    key = ('mul', a.device.index, C, H, W, same, bcast, F, lift, fa, bool(a_signed), fb, bool(b_signed), bool(hard_gate_b), bool(relu))
+    return _plans.get(key, (), N, build).run(x).view(N, C, H, W)
+
+
 # ------------------------------------------------------------------------------------------ whole nets
 _nets = {}
 
@@ -327,7 +390,7 @@ def _net_forward_f32(images, handle, normalize):
 # ------------------------------------------------------------------------------------------ registration
 _CUDA = Library('f8net', 'IMPL', 'CUDA')
 for _n, _f in (('requant', _requant), ('relu_', _relu_), ('add_align_', _add_align_), ('conv2d', _conv2d), ('conv_transpose2d', _conv_transpose2d), ('linear', _linear),
-               ('avgpool_sum', _avgpool_sum), ('avgpool2d_sum', _avgpool2d_sum), ('maxpool', _maxpool), ('channel_shuffle', _channel_shuffle), ('net_forward', _net_forward), ('net_forward_taps', _net_forward_taps),
+               ('avgpool_sum', _avgpool_sum), ('avgpool2d_sum', _avgpool2d_sum), ('maxpool', _maxpool), ('channel_shuffle', _channel_shuffle), ('mul_q', _mul_q), ('net_forward', _net_forward), ('net_forward_taps', _net_forward_taps),
                ('net_forward_f32', _net_forward_f32)):
     _CUDA.impl(_n, _f)
 
@@ -346,6 +409,7 @@ _META.impl('avgpool2d_sum', lambda x, k, stride, pad: x.new_empty(
 _META.impl('maxpool', lambda x, k, stride, pad: x.new_empty(
     (x.shape[0], x.shape[1], (x.shape[2] + 2 * pad - k) // stride + 1, (x.shape[3] + 2 * pad - k) // stride + 1)))
 _META.impl('channel_shuffle', lambda x, groups: torch.empty_like(x))
+_META.impl('mul_q', lambda a, b, a_src_fl, b_src_fl, a_fl, a_signed, b_fl, b_signed, hard_gate_b, relu: torch.empty_like(a))
 _META.impl('net_forward', lambda x, handle: x.new_empty((x.shape[0], _nets[handle].out_elems),
                                                         dtype=torch.float32 if _nets[handle].out_float else torch.int32))
 _META.impl('net_forward_taps', lambda x, handle: [x.new_empty((x.shape[0], _nets[handle].out_elems), dtype=torch.float32 if _nets[handle].out_float else torch.int32)] + [

@@ -222,6 +222,42 @@ int f8_net_upsample(f8_net* net, int src, int mode, int scale_h, int scale_w);
 int f8_net_slice(f8_net* net, int src, int first, int channels);
 int f8_net_channel_shuffle(f8_net* net, int src, int groups);
 
+/* Fixed-point multiply of two activations and the hard gate (the scale of a squeeze-and-excitation block: SENet / SE-ResNet, MobileNet-V3, MnasNet-A1,
+ * RegNetY, GhostNet; hard-swish: MobileNet-V3, LCNet).  The reference defines no such class; the semantics are fixed here in its own terms
+ * (int_op_only_fix_quant, fix_quant_ops.py:91-112, on each operand; format x format -> int32, the fraction lengths add).
+ *   f8_net_mul        out[n, c, h, w] = A[n, c, h, w] * B[n, c, h, w]   (b has the shape of a: element-wise, plan sub-kind "mul"), or
+ *                     out[n, c, h, w] = A[n, c, h, w] * B[n, c, 0, 0]   (b is [a.C, 1, 1]: a per-image channel gate broadcast over H x W, "chmul")
+ *                     with A = int_op_only_fix_quant(a, 8, a_fl, a.fraclen, a_signed) and B the same from b: the round-half-even shift and the clamp
+ *                     to +-127 / 0 .. 255 every conv consumer applies.  |out| <= 255 * 255, so nothing wraps.  desc->relu: max(., 0) on the product.
+ *                     out.fraclen = a_fl + b_fl, the shape is a's.  a == b is allowed: the square, in one format or in two.
+ *                     Format limits are the conv's: 0 <= fl <= 8 unsigned, 0 <= fl <= 7 signed; the requant shift src.fraclen - fl lies in -31 .. 30.
+ *   f8_net_hard_gate  relu6(x + 3), the numerator of hard-sigmoid, exact in fixed point:
+ *                     out = clamp(x, -3 * 2^fl, +3 * 2^fl) + 3 * 2^fl,  fl = src.fraclen; shape and fraclen are the source's.  The clamp comes first, so
+ *                     no int32 input overflows: INT32_MIN gives 0, INT32_MAX gives 6 * 2^fl.
+ *                     The constant 1 / 6 of hard-sigmoid / hard-swish is applied NOWHERE: like the kernel^2 of f8_net_avgpool_window it is a constant
+ *                     real scale that the exporter folds into the next conv's weights.
+ * Compositions: the hard-sigmoid SE gate is f8_net_mul(x, f8_net_hard_gate(fc2)) with b = [C, 1, 1]; hard-swish is f8_net_mul(x, f8_net_hard_gate(x));
+ * ReLU-gated or plain products are f8_net_mul alone.
+ * Both return the tensor id.  F8_ERR_INVALID: a bad tensor id, a null desc, b neither of a's shape nor [a.C, 1, 1], a format outside the limits above,
+ * a shift outside -31 .. 30; f8_net_hard_gate on a source with fraclen > 28 (6 * 2^fl must fit int32) or < 0.  F8_ERR_STATE after finalize.
+ * NOT built: a true sigmoid (no fixed-point function; a 256-entry table op would be one), a [1, H, W] spatial broadcast, exporter support from float models.
+ * The plan (f8_mul.hip).  A mul reads int8: it registers (a_fl, a_signed) on a and (b_fl, b_signed) on b exactly as a conv with quant_input = 1
+ * registers its format, the producers write the forms (a third format of one tensor: a `requant:` step).  One launch, its mode shown by the token:
+ * `mul_i8:` / `chmul_i8:` — the result is read in at most two int8 formats and by nothing else — writes those formats only; `mul_i32:` / `chmul_i32:`
+ * writes the int32 form (a join, a pool, an output, a third format) and up to two int8 forms.  The product is bounded by 2^16: no proof about values
+ * is needed.  A hard gate alone is one launch `hgate:` on its source's int32 form.  A hard gate whose ONLY reader is the b operand of one mul emits
+ * no launch: the mul launch reads the gate's source in int32 and applies clamp, offset and requantisation itself, tokens `hgate+mul_i8:`,
+ * `hgate+chmul_i8:` and the `_i32` pair (option fuse_hgate = 0: two launches).  Same values in every case.
+ * A tensor read by a mul or a hard gate exists in device memory: no matcher counts them among a block's readers, so no fused block or chain launch
+ * keeps it on chip (it cuts a launch as an output tap does). */
+typedef struct f8_mul_desc {
+    int32_t a_fl, a_signed;   /* format a is requantised to: int_op_only_fix_quant(a, 8, a_fl, a.fraclen, a_signed) */
+    int32_t b_fl, b_signed;   /* the same for b */
+    int32_t relu;             /* max(., 0) on the product */
+} f8_mul_desc;
+int f8_net_mul(f8_net* net, int a, int b, const f8_mul_desc* desc);
+int f8_net_hard_gate(f8_net* net, int src);
+
 /* Head max-pool nn.MaxPool2d(k, stride, pad) via the float detour (fix_resnet.py:358-359) or
  * FXQMaxPool2d (fix_quant_ops.py:150-157); exact integer max. */
 int f8_net_maxpool(f8_net* net, int src, int kernel, int stride, int pad);
@@ -416,7 +452,9 @@ int f8_net_check(f8_net* net);
  *               of its source's int8 forms, plan tokens slice_i8: / shuffle{g}_i8:; 0: every one runs f8::chanmap_i32_kernel on the int32 form, tokens
  *               slice_i32: / shuffle{g}_i32:.  Same values either way, bit for bit),
  *               fuse_shuffle (default 1: a concat of `groups` operands of one width that only an i8-mode shuffle reads emits no launch; the shuffle
- *               launch reads the operands, token concat+shuffle{g}_i8:; 0: two launches.  Same values either way, bit for bit)
+ *               launch reads the operands, token concat+shuffle{g}_i8:; 0: two launches.  Same values either way, bit for bit),
+ *               fuse_hgate (default 1: a hard gate whose only reader is the b operand of one f8_net_mul emits no launch; the mul launch reads the gate's
+ *               source in int32, tokens hgate+mul_*: / hgate+chmul_*:; 0: an hgate: launch and the mul launch.  Same values either way, bit for bit)
  *   scheduling: chunk56 / chunk28 / chunk14 (images per chunk of the fused blocks; -1 = derived from chunk_budget_mb, 0 = whole
  *               batch), chunk_budget_mb (memory-side cache a chunk's int32 stream may occupy), chunk_ds, chunk_opener,
  *               split_streams, graph, stagger, stagger_pipelined, stem_wpc, stem_grid_div (row-walking head on 1 / n of the CUs; 0 = by output form), wstat_grid_div (0 .. 32, default 0, environment F8_WSTAT_GRID_DIV: f8::conv1x1_wstat_kernel sizes its pixel groups for 1 / n of the CUs, at least one — tests walk long tile rings on small maps; 0 = all of them; the plan and the values do not move), check_device, check_input_range, pipeline_depth (2..4 runs in flight),
