@@ -33,6 +33,10 @@ class MulDesc(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ('a_fl', 'a_signed', 'b_fl', 'b_signed', 'relu')]
 
 
+class TableDesc(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ('in_fl', 'in_signed', 'out_fl')]
+
+
 _lib = None
 
 # every symbol include/f8net.h declares: (name, restype, argtypes)
@@ -60,6 +64,7 @@ SYMBOLS = [
     ('f8_net_channel_shuffle', _i, [_vp, _i, _i]),
     ('f8_net_mul', _i, [_vp, _i, _i, ctypes.POINTER(MulDesc)]),
     ('f8_net_hard_gate', _i, [_vp, _i]),
+    ('f8_net_table', _i, [_vp, _i, ctypes.POINTER(TableDesc), ctypes.POINTER(ctypes.c_int32)]),
     ('f8_net_maxpool', _i, [_vp, _i, _i, _i, _i]),
     ('f8_net_avgpool_sum', _i, [_vp, _i, _i]),
     ('f8_net_avgpool_window', _i, [_vp, _i, _i, _i, _i, _i]),

@@ -80,6 +80,8 @@ struct Options {
     int chanmap_i8 = 1;          // f8_net_slice / f8_net_channel_shuffle: 1 = the byte-gather mode where the result is read in at most two int8 formats and by nothing else (f8_chanmap.hip); 0 = always the int32 mode
     int fuse_shuffle = 1;        // a concat read by one i8-mode channel shuffle alone, `groups` operands of one width: 1 = one launch that reads the concat's operands (concat+shuffle{g}_i8:); 0 = two launches
     int fuse_hgate = 1;          // a hard gate read by the b operand of one mul alone: 1 = no launch of its own, the mul launch reads the gate's int32 source (hgate+mul_*: / hgate+chmul_*:, f8_mul.hip); 0 = two launches
+    int table_i8 = 1;            // f8_net_table: 1 = the byte-gather mode where the result is read in at most two int8 formats and by nothing else (table_i8:, f8_table.hip); 0 = always table_i32:
+    int fuse_table = 1;          // a table read by the b operand of one broadcast mul alone: 1 = no launch of its own where the map has fewer than 2^20 values an image (the measured rule, fuse_table_rule in f8_net.cpp), the mul launch looks b up itself (table+chmul_*:, f8_table.hip); 2 = always; 0 = two launches
     int tap_tiled = 1;           // network outputs 1 .. leave on tap_kernel (f8_tap.hip: walks the I32T blocks, every loaded byte used); 0: on output_kernel like output 0
     int check_input_range = 1;   // int32 inputs that are NARROWED to the head's 8-bit format (no requant) are range-checked on the device; f8_net_check reports
 };
@@ -294,6 +296,24 @@ struct MulArgs {
     int32_t* out32;
     QuantOut q[2];
 };
+
+// The 256-entry table op (f8_table.hip; f8_net_table).  `src` is the source in the int8 format the table is indexed in (NHWC, Cs-byte rows, written
+// by the source's producer); the stored byte ^ 0x80 is the index u for either sign of that format (unsigned: u = q; signed: u = q + 128).
+//   table_i8_kernel     out form k byte = bt[k][u]: 256 bytes per output form, composed on the host (entry requantised to the form, storage bias folded in)
+//   table_i32_kernel    out = t32[u] (the caller's 256 entries), written as int32 (I32T) and requantised to q[] as AddArgs
+// Pad channels [C, Cs) of every output are the format's zero whatever the source's pad bytes hold.
+struct TableArgs {
+    const int8_t* src;
+    int32_t M, C, Cs;                                    // pixels N * H * W, real / padded channels (source and result alike)
+    FastDiv dVpp;                                        // table_i8_kernel: / (Cs / V), the vectors of a pixel
+    const int32_t* t32;                                  // table_i32_kernel: the entries
+    const uint8_t* bt[2];                                // table_i8_kernel: the composed byte table of q[k]
+    int32_t* out32;
+    QuantOut q[2];
+};
+// A table fused into the broadcast mul that reads it (table_chmul_*_kernel, f8_table.hip): m is the mul's record with gate == 0, bcast == 1 and
+// m.b = the TABLE's source in its int8 index format (N rows of Cs bytes); bt is the byte table composed for the mul's format of b (m.rb).
+struct TableMulArgs { MulArgs m; const uint8_t* bt; };
 
 // Transposed convolution (f8_deconv.hip; f8_net_conv_transpose), stride 2 .. 4: [H, W] -> [P, Q] = [(H - 1) s - 2 pad + k + output_padding, ...].  The output
 // pixels of one PHASE (rh, rw) = ((oh + pad) % s, (ow + pad) % s) see the same kernel taps kh = rh + s th, th < Th, at the input rows ih = a - th
@@ -742,6 +762,13 @@ int mul_inst(const MulArgs& a, int mode);                          // f8_mul.hip
 const char* mul_kernel_name(int inst);
 int mul_vector_bytes(int inst);                                    // bytes of one operand a lane of the instance owns per step (16 / 4)
 hipError_t launch_mul(const MulArgs& a, int inst, hipStream_t s);
+constexpr int kTableReplicas = 1;                                  // copies of a byte table in LDS, lane l reads copy l % R (measured, profiles/table_r15.md: 1 is as fast as or faster than 4 and 16 on every shape)
+int table_inst(const TableArgs& a, bool i8);                       // f8_table.hip.  0: table_i32_kernel, 1 / 2: table_i8_kernel<16, R> / <4, R>
+const char* table_kernel_name(int inst);
+hipError_t launch_table(const TableArgs& a, int inst, hipStream_t s);
+int table_mul_inst(const TableMulArgs& a, bool i8);                // 0: table_chmul_i32_kernel, 1 / 2: table_chmul_i8_kernel<16> / <4>
+const char* table_mul_kernel_name(int inst);
+hipError_t launch_table_mul(const TableMulArgs& a, int inst, hipStream_t s);
 int sumpool_inst(int k, bool wide);                                // f8_sumpool.hip.  0: sumpool_i32_kernel<0> (kernel size at run time), 2 / 3: sumpool_i32_kernel<2> / <3>, 4: sumpool_wide_kernel
 const char* sumpool_kernel_name(int inst);
 int sumpool_wide_lg(int k);

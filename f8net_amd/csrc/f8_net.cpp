@@ -96,7 +96,8 @@ enum ChainKind { C_NONE, C_STAGE, C_BASIC, C_BASIC_CLUSTER, C_IR };
 // memory and cuts a chain or fused block where an output tap does.  Channel gathers without arithmetic; the mode rule of the nearest upsample.
 // N_MUL / N_HGATE (f8_net_mul, f8_net_hard_gate; f8_mul.hip) likewise: a mul READS like a conv — each operand's int8 form in the mul's format for it, written
 // by the operand's producer — and a hard gate reads its source's int32 form; no matcher counts either among a block's readers.
-enum NodeKind { N_INPUT, N_CONV, N_ADD, N_MAXPOOL, N_AVGPOOL, N_LINEAR, N_CONCAT, N_UPSAMPLE, N_DECONV, N_SUMPOOL, N_SLICE, N_SHUFFLE, N_MUL, N_HGATE };
+// N_TABLE (f8_net_table; f8_table.hip) reads like a conv too — its source's int8 form in the format the table is indexed in — and cuts likewise.
+enum NodeKind { N_INPUT, N_CONV, N_ADD, N_MAXPOOL, N_AVGPOOL, N_LINEAR, N_CONCAT, N_UPSAMPLE, N_DECONV, N_SUMPOOL, N_SLICE, N_SHUFFLE, N_MUL, N_HGATE, N_TABLE };
 struct Node {
     int kind; int a = -1, b = -1; int out = -1;
     f8_conv_desc cd{};                 // conv / linear (as 1x1 conv)
@@ -119,6 +120,11 @@ struct Node {
     f8_mul_desc md{};                  // mul: the operand formats and the ReLU (operands a, b)
     int mul_gate = -1;                 // mul, pass 2: the hard-gate node that produces b and runs inside this launch (option fuse_hgate), else -1
     int gate_into = -1;                // hard gate, pass 2: the mul node whose launch applies it: no launch and no form of its own
+    f8_table_desc td{};                // table: the index format and the entries' fraclen
+    std::vector<int32_t> table;        // table: the 256 entries, copied at the call
+    int mul_table = -1;                // mul, pass 2: the table node that produces b and is looked up inside this launch (option fuse_table), else -1
+    int tab_into = -1;                 // table, pass 2: the mul node whose launch looks it up: no launch and no form of its own
+    size_t tab_off = 0;                // table / a mul with mul_table, pass 3: its device tables in the weight image (int32 entries, or 256 bytes per int8 form)
     int cat_into = -1;                 // concat, pass 2: the shuffle node whose launch reads this concat's operands: no launch and no form of its own
     // planning
     int fused_into = -1;               // add: conv node that carries it
@@ -141,7 +147,7 @@ struct Node {
     size_t rc_off = 0, cc_off = 0; int ncc = 0;      // border-class tables (0 = single class)
     ConvTile tile{};
 };
-enum StepKind { S_INPUT, S_CONV, S_DW, S_ADD, S_MAXPOOL, S_AVGPOOL, S_REQUANT, S_OUTPUT, S_FUSED, S_STEMPOOL, S_IR, S_P12, S_CHAIN, S_BCHAIN, S_HEAD2, S_IRCHAIN, S_DWS, S_DWS7, S_IRK, S_GCONV, S_CONCAT, S_UPSAMPLE, S_DECONV, S_SUMPOOL, S_CHANMAP, S_MUL, S_HGATE };
+enum StepKind { S_INPUT, S_CONV, S_DW, S_ADD, S_MAXPOOL, S_AVGPOOL, S_REQUANT, S_OUTPUT, S_FUSED, S_STEMPOOL, S_IR, S_P12, S_CHAIN, S_BCHAIN, S_HEAD2, S_IRCHAIN, S_DWS, S_DWS7, S_IRK, S_GCONV, S_CONCAT, S_UPSAMPLE, S_DECONV, S_SUMPOOL, S_CHANMAP, S_MUL, S_HGATE, S_TABLE };
 // The kernel of a step whose kind has several, chosen once by the step's emitter (pass 3); bind_step, run_step and f8_net_autotune switch on it.
 //   S_CONV:  conv_igemm (f8_kernels.hip), the LDS-patch 3x3 (f8_conv3x3.hip), conv1x1_wreg (f8_wreg.hip), conv1x1_wstat (f8_wstat.hip),
 //            conv3x3s2_wreg (f8_s2conv.hip), the 1x1 conv + average pool (f8_pool.hip), the classifier fc_dense (f8_fc.hip)
@@ -172,7 +178,7 @@ struct Step {
     double bytes_per_img = 0, bytes_const = 0, ops_per_img = 0;
     double valu_per_img = 0;           // ESSENTIAL vector lane-operations per image (f8_net_launch_valu): what the reference's semantics need once the MFMAs are done
     // the launcher's arguments as far as the plan decides them (bind_step); run_step copies them and adds what the run decides
-    std::variant<std::monostate, ConvArgs, StemPoolArgs, FusedArgs, ChainArgs, BChainArgs, BCChainArgs, IRArgs, IRKArgs, IRChainArgs, DwsArgs, Dws7Args, DwArgs, GConvArgs, AddArgs, PoolArgs, AvgArgs, OutArgs, ConcatArgs, UpsampleArgs, DeconvArgs, SumPoolArgs, ChanMapArgs, MulArgs> args;
+    std::variant<std::monostate, ConvArgs, StemPoolArgs, FusedArgs, ChainArgs, BChainArgs, BCChainArgs, IRArgs, IRKArgs, IRChainArgs, DwsArgs, Dws7Args, DwArgs, GConvArgs, AddArgs, PoolArgs, AvgArgs, OutArgs, ConcatArgs, UpsampleArgs, DeconvArgs, SumPoolArgs, ChanMapArgs, MulArgs, TableArgs, TableMulArgs> args;
     int inst = 0;                      // the instance the launcher starts (the family's *_inst, f8_internal.h; bind_step)
     // S_CHAIN / S_BCHAIN: geometry, workgroups per image and resident per CU, the 7x7 cluster form (f8_cchain.hip)
     int C = 0, MID = 0, H = 0, W = 0, cin0 = 0, tiles = 0, wg_per_cu = 1; bool cluster = false;
@@ -288,6 +294,7 @@ static bool conv_acc_bounded(Node& nd) {
 // shifted sum of its operands' — which makes the int32 residual STREAM of a ResNet stage a bounded quantity: real nets sit at 2^20 .. 2^27.  -1 =
 // unknown or beyond 2^40 (the network input, pooled sums).  The chain launches requantise the stream through the float converter only below
 // kAccLimit (ChainArgs::stream_ok); beyond it `v + 2^(n-1)` may wrap as the reference's int32 add does, and the integer instances run.
+int64_t table_amax(const int32_t table[256], bool sgn);      // (the table op's host side, below)
 static int64_t tensor_amax(f8_net* net, int t, int depth = 0) {
     if (t < 0 || t >= (int)net->tensors.size() || depth > 256) return -1;
     Tensor& T = net->tensors[t];
@@ -322,6 +329,8 @@ static int64_t tensor_amax(f8_net* net, int t, int depth = 0) {
             m = (int64_t)(nd.md.a_signed ? 127 : 255) * (nd.md.b_signed ? 127 : 255);
         } else if (nd.kind == N_HGATE) {                     // 0 .. 6 * 2^fl (fl <= 28: f8_net_hard_gate)
             m = int64_t(6) << T.fl;
+        } else if (nd.kind == N_TABLE) {                     // the reachable entries
+            m = table_amax(nd.table.data(), nd.td.in_signed != 0);
         } else if (nd.kind == N_SUMPOOL) {                   // at most kernel^2 taps of the source's bound, under the same cap
             const int64_t a = tensor_amax(net, nd.a, depth + 1);
             const int64_t kk = (int64_t)nd.sum_k * nd.sum_k;
@@ -333,6 +342,28 @@ static int64_t tensor_amax(f8_net* net, int t, int depth = 0) {
     T.amax = m;
     return m;
 }
+// ---- the host side of the table op (f8_net_table)
+// int_op_only_fix_quant on one value in the library's integer form — requant1 of f8_device.h, the reference's int32 wrap of `v + 2^(n-1)` included
+int requant_host(int32_t v, const Requant& r) {
+    const int n = r.n, shr = n > 0 ? n : 0, shl = n > 0 ? 0 : -n;
+    const uint32_t hm1 = n > 0 ? (1u << (n - 1)) - 1u : 0u;
+    const uint32_t odd = n > 0 ? ((uint32_t)v >> n) & 1u : 0u;
+    const uint32_t t = (shl >= 32 ? 0u : (uint32_t)v << shl) + hm1 + odd;
+    const int64_t q = (int64_t)(int32_t)t >> shr;       // (arithmetic: int32_t -> int64_t sign-extends, >> of a negative int64 is arithmetic on every compiler this builds with)
+    return (int)std::min<int64_t>(std::max<int64_t>(q, r.lo), r.hi);
+}
+// The byte table of one int8 form of a table's result: bt[u] = the stored byte of requant(table[u], r), u = stored source byte ^ 0x80 (0 .. 255 =
+// the unsigned index, or the signed index + 128: the entries' own order for either sign).
+void compose_byte_table(const int32_t table[256], const Requant& r, uint8_t bt[256]) {
+    for (int u = 0; u < 256; ++u) bt[u] = (uint8_t)((uint32_t)requant_host(table[u], r) ^ (r.bias_xor & 0xffu));
+}
+// max |entry| over the entries an index can reach: all 256 unsigned, 1 .. 255 signed (index -128 never occurs)
+int64_t table_amax(const int32_t table[256], bool sgn) {
+    int64_t m = 0;
+    for (int u = sgn ? 1 : 0; u < 256; ++u) m = std::max<int64_t>(m, std::llabs((int64_t)table[u]));
+    return m;
+}
+
 static bool stream_bounded(f8_net* net, int t) { const int64_t m = tensor_amax(net, t); return m >= 0 && m <= kAccLimit; }
 
 // shift / clamp of a consumer's int_op_only_fix_quant; validates what the reference asserts
@@ -422,6 +453,8 @@ static const OptKey kOptKeys[] = {
     {"chanmap_i8", "F8_CHANMAP_I8", &Options::chanmap_i8, 0, 1, true},
     {"fuse_shuffle", "F8_FUSE_SHUFFLE", &Options::fuse_shuffle, 0, 1, true},
     {"fuse_hgate", "F8_FUSE_HGATE", &Options::fuse_hgate, 0, 1, true},
+    {"table_i8", "F8_TABLE_I8", &Options::table_i8, 0, 1, true},
+    {"fuse_table", "F8_FUSE_TABLE", &Options::fuse_table, 0, 2, true},
 };
 static const OptKey* find_opt(const char* key) {
     if (!key) return nullptr;
@@ -872,6 +905,31 @@ int f8_net_hard_gate(f8_net* net, int src) {
     net->nodes.push_back(nd);
     const int id = (int)net->nodes.size() - 1;
     const int t = new_tensor(net, s.C, s.H, s.W, s.fl, id);
+    net->nodes[id].out = t;
+    net->tensors[src].consumers.push_back(id);
+    return t;
+}
+
+int f8_net_table(f8_net* net, int src, const f8_table_desc* desc, const int32_t table_host[256]) {
+    if (!net) return fail(F8_ERR_INVALID, "f8_net_table: null net");
+    if (net->finalized) return fail(F8_ERR_STATE, "f8_net_table: net already finalized");
+    if (!desc) return fail(F8_ERR_INVALID, "f8_net_table: null desc");
+    if (!table_host) return fail(F8_ERR_INVALID, "f8_net_table: null table");
+    if (const int rc = check_t(net, src, "f8_net_table")) return rc;
+    const Tensor s = net->tensors[src];
+    // the index format is a consumer format: the conv's limits and shift range (consumer_format)
+    f8_conv_desc f{};
+    f.input_fl = desc->in_fl; f.input_signed = desc->in_signed != 0; f.quant_input = 1;
+    int n = 0;
+    if (const int rc = consumer_format(s, f, &n, "f8_net_table")) return rc;
+    if (desc->out_fl < 0 || desc->out_fl > 38)
+        return fail(F8_ERR_INVALID, "f8_net_table: out_fl %d outside [0, 38] (beyond 38 no 8-bit format reads it: the shift would exceed 30)", desc->out_fl);
+    Node nd; nd.kind = N_TABLE; nd.a = src; nd.td = *desc;
+    nd.td.in_signed = desc->in_signed != 0;
+    nd.table.assign(table_host, table_host + 256);
+    net->nodes.push_back(std::move(nd));
+    const int id = (int)net->nodes.size() - 1;
+    const int t = new_tensor(net, s.C, s.H, s.W, desc->out_fl, id);
     net->nodes[id].out = t;
     net->tensors[src].consumers.push_back(id);
     return t;
@@ -2096,6 +2154,11 @@ static void ask_sources(f8_net* net, const std::vector<int>& srcs, int fl_ref, c
     }
 }
 
+// Option fuse_table.  1: the measured rule (profiles/table_r15.md, batch 128, EfficientNet-B0's shapes): the fused launch is 1.07 - 1.59 x faster than
+// the two launches on every shape up to 144 x 56 x 56 = 451 584 values an image and slower (0.96 x) on the one above, 96 x 112 x 112 = 1 204 224 —
+// so it fuses below 2^20 values an image.  2: always (what the measurement ran).  0: never.
+static bool fuse_table_rule(int opt, const Tensor& a) { return opt == 2 || (opt == 1 && (int64_t)a.C * a.H * a.W < (int64_t(1) << 20)); }
+
 static void plan_tensor_forms(f8_net* net) {
     auto& T = net->tensors;
     auto& ND = net->nodes;
@@ -2249,6 +2312,11 @@ static void plan_tensor_forms(f8_net* net) {
                 if (opt.fuse_hgate && gp.kind == N_HGATE && B.consumers.size() == 1 && nd.a != nd.b && !is_output(net, nd.b)) {
                     nd.mul_gate = B.prod; gp.gate_into = i;
                     add_form(T[gp.a], FORM_I32, 0, 0);
+                } else if (fuse_table_rule(opt.fuse_table, A) && gp.kind == N_TABLE && B.consumers.size() == 1 && !is_output(net, nd.b) && B.H * B.W == 1 && A.H * A.W > 1) {
+                    // a table that only this BROADCAST mul's b operand reads (the sigmoid SE gate): the launch reads the table's source bytes and looks
+                    // them up in a byte table composed for (b_fl, b_signed); the table gets no form and no launch
+                    nd.mul_table = B.prod; gp.tab_into = i;
+                    add_form(T[gp.a], FORM_I8, T[gp.a].fl - gp.td.in_fl, gp.td.in_signed);
                 } else {
                     add_form(B, FORM_I8, B.fl - nd.md.b_fl, nd.md.b_signed);
                 }
@@ -2256,6 +2324,13 @@ static void plan_tensor_forms(f8_net* net) {
             }
             case N_HGATE:
                 if (nd.gate_into < 0) add_form(T[nd.a], FORM_I32, 0, 0);      // (fused: the mul, a later node, asked the source already)
+                break;
+            case N_TABLE:
+                // reads like a conv with quant_input = 1: the source's int8 form in the index format, written by the source's producer.  The mode rule of
+                // the gathers: bytes where the result exists in one or two int8 forms and nothing else.  No bound on values is needed: the entries are known.
+                if (nd.tab_into >= 0) break;                                  // (fused: the mul, a later node, asked the source already)
+                add_form(T[nd.a], FORM_I8, T[nd.a].fl - nd.td.in_fl, nd.td.in_signed);
+                nd.bytes_mode = opt.table_i8 && int8_forms_only(net, nd.out);
                 break;
             case N_UPSAMPLE: {
                 // the mode rule alone, for nearest: the fraclen — so the shift — is the source's and no bound on the values is needed
@@ -2890,15 +2965,29 @@ static int emit_chanmap(f8_net* net, int i, Step& st, std::vector<int>* extra) {
 }
 
 
+// 256 bytes per int8 output form of `forms8` appended to the weight image: the entries requantised to each form (compose_byte_table).  Returns the offset.
+static size_t pack_byte_tables(f8_net* net, const std::vector<int32_t>& table, const Requant* r, int nr) {
+    const size_t off = round_up_z(net->wblob.size(), 256);
+    net->wblob.resize(off + 256 * (size_t)std::max(nr, 1), 0);
+    for (int k = 0; k < nr; ++k) compose_byte_table(table.data(), r[k], net->wblob.data() + off + 256 * (size_t)k);
+    return off;
+}
+
 // f8_net_mul; a hard gate fused into it (Node::mul_gate) makes the launch read the gate's int32 source as its b
 static int emit_mul(f8_net* net, int i, Step& st, std::vector<int>* extra) {
     auto& T = net->tensors;
     const Node& nd = net->nodes[i];
     const Tensor& A = T[nd.a]; const Tensor& B = T[nd.b]; const Tensor& o = T[nd.out];
-    const bool fused = nd.mul_gate >= 0, bcast = B.H * B.W != A.H * A.W;
+    const bool fused = nd.mul_gate >= 0, bcast = B.H * B.W != A.H * A.W, tab = nd.mul_table >= 0;
     st.kind = S_MUL;
     st.src_t = nd.a; st.src_f = find_form(A, FORM_I8, A.fl - nd.md.a_fl, nd.md.a_signed);
     if (fused) { st.res_t = net->nodes[nd.mul_gate].a; st.res_f = find_form(T[st.res_t], FORM_I32, 0, 0); }
+    else if (tab) {
+        const Node& tn = net->nodes[nd.mul_table];
+        st.res_t = tn.a; st.res_f = find_form(T[tn.a], FORM_I8, T[tn.a].fl - tn.td.in_fl, tn.td.in_signed);
+        const Requant rb = Requant::of(B.fl - nd.md.b_fl, nd.md.b_signed != 0);
+        net->nodes[i].tab_off = pack_byte_tables(net, tn.table, &rb, 1);
+    }
     else { st.res_t = nd.b; st.res_f = find_form(B, FORM_I8, B.fl - nd.md.b_fl, nd.md.b_signed); }
     if (st.src_f < 0 || st.res_f < 0) return fail(F8_ERR_STATE, "f8_net_finalize: planner bug: an operand of mul t%d lacks its form", nd.out);
     st.relu1 = nd.md.relu;
@@ -2907,8 +2996,44 @@ static int emit_mul(f8_net* net, int i, Step& st, std::vector<int>* extra) {
     st.bytes_per_img = px * o.C + bpx * o.C * (fused ? 4 : 1) + px * o.C * ((st.out.f32 >= 0 ? 4 : 0) + out_forms8(st));      // real bytes, each once
     st.valu_per_img = px * o.C * (1 + (nd.md.relu ? 1 : 0) + 3 * out_forms8(st)) + (fused ? bpx * o.C * 5 : 0);      // the multiply, the ReLU, 3 per int8 value produced; a fused gate: clamp + offset + 3
     char tok[48];
-    snprintf(tok, sizeof tok, "%s%s_%s:", fused ? "hgate+" : "", bcast ? "chmul" : "mul", st.out.f32 >= 0 ? "i32" : "i8");
+    snprintf(tok, sizeof tok, "%s%s_%s:", fused ? "hgate+" : tab ? "table+" : "", bcast ? "chmul" : "mul", st.out.f32 >= 0 ? "i32" : "i8");
     st.name = tok + tname(net, nd.out);
+    return F8_OK;
+}
+
+// The int8 output forms of a table_i8: launch in the order their byte tables lie in the weight image: slot j of the image belongs to output k = slot_k[j]
+// (emit_table composes in this order, bind_step pairs pointer and format by it: TableArgs::bt[k] goes with q[k])
+static int table_slots(const OutSel& o, int slot_k[2]) {
+    int n = 0;
+    for (int k = 0; k < 2; ++k) if (o.f8[k] >= 0) slot_k[n++] = k;
+    return n;
+}
+
+// f8_net_table as a launch of its own
+static int emit_table(f8_net* net, int i, Step& st, std::vector<int>* extra) {
+    auto& T = net->tensors;
+    Node& nd = net->nodes[i];
+    const Tensor& s = T[nd.a]; const Tensor& o = T[nd.out];
+    st.kind = S_TABLE;
+    st.src_t = nd.a; st.src_f = find_form(s, FORM_I8, s.fl - nd.td.in_fl, nd.td.in_signed);
+    if (st.src_f < 0) return fail(F8_ERR_STATE, "f8_net_finalize: planner bug: the source of table t%d lacks its form", nd.out);
+    select_outputs_or_i32(net, nd.out, &st.out, extra);
+    const bool i8 = nd.bytes_mode && st.out.f32 < 0;
+    if (i8) {
+        Requant r[2]; int slot_k[2];
+        const int nr = table_slots(st.out, slot_k);
+        for (int j = 0; j < nr; ++j) { const Form& F = o.forms[st.out.f8[slot_k[j]]]; r[j] = Requant::of(F.n, F.sgn != 0); }
+        nd.tab_off = pack_byte_tables(net, nd.table, r, nr);
+    } else {
+        nd.tab_off = round_up_z(net->wblob.size(), 256);
+        net->wblob.resize(nd.tab_off + 1024, 0);
+        memcpy(net->wblob.data() + nd.tab_off, nd.table.data(), 1024);
+    }
+    const double px = (double)o.H * o.W;
+    st.bytes_per_img = px * o.C * (1 + (st.out.f32 >= 0 ? 4 : 0) + out_forms8(st));
+    st.bytes_const = i8 ? 256 * out_forms8(st) : 1024;
+    st.valu_per_img = i8 ? 0 : px * o.C * 3 * out_forms8(st);      // bytes mode: a gather, no arithmetic; else 3 per int8 value produced
+    st.name = (i8 ? "table_i8:" : "table_i32:") + tname(net, nd.out);
     return F8_OK;
 }
 
@@ -3000,6 +3125,7 @@ static int emit_steps(f8_net* net, int max_batch) {
         if (nd.kind == N_AVGPOOL && nd.pool_host >= 0) continue;     // runs in its conv's launch
         if (nd.kind == N_CONCAT && nd.cat_into >= 0) continue;       // the shuffle behind it reads its operands
         if (nd.kind == N_HGATE && nd.gate_into >= 0) continue;       // the mul behind it applies it
+        if (nd.kind == N_TABLE && nd.tab_into >= 0) continue;        // the mul behind it looks it up
         Step st; st.node = i;
         std::vector<int> extra;
         int rc = F8_OK;
@@ -3016,6 +3142,7 @@ static int emit_steps(f8_net* net, int max_batch) {
             case N_SLICE: case N_SHUFFLE: rc = emit_chanmap(net, i, st, &extra); break;
             case N_MUL: rc = emit_mul(net, i, st, &extra); break;
             case N_HGATE: rc = emit_hgate(net, i, st, &extra); break;
+            case N_TABLE: rc = emit_table(net, i, st, &extra); break;
         }
         if (rc) return rc;
         net->steps.push_back(st);
@@ -3643,10 +3770,34 @@ static int bind_step(f8_net* net, Step& st) {
                 if (a.gate) a.lim = 3 << bT.fl;
                 a.ra = Requant::of(T[nd.a].fl - nd.md.a_fl, nd.md.a_signed != 0);
                 a.rb = Requant::of(bT.fl - nd.md.b_fl, nd.md.b_signed != 0);
+                if (nd.mul_table >= 0) {                             // b is looked up in the launch (f8_table.hip): the mul's record and the byte table
+                    TableMulArgs ta{};
+                    ta.bt = (const uint8_t*)W8(nd.tab_off);
+                    st.inst = table_mul_inst(TableMulArgs{a, nullptr}, !out32);
+                    a.dVpp = fast_divisor((uint32_t)(a.Cs / (st.inst == 1 ? 16 : 4)));
+                    ta.m = a;
+                    snprintf(kb, sizeof kb, "%s", table_mul_kernel_name(st.inst));
+                    out_formats(ta.m.q); st.args = ta; break;
+                }
                 st.inst = mul_inst(a, out32 ? 1 : 2);
                 a.dVpp = fast_divisor((uint32_t)(a.Cs / mul_vector_bytes(st.inst)));
             }
             snprintf(kb, sizeof kb, "%s", mul_kernel_name(st.inst));
+            out_formats(a.q); st.args = a; break;
+        }
+        case S_TABLE: {
+            const Tensor& oT = T[nd.out];
+            TableArgs a{};
+            a.C = oT.C; a.Cs = oT.Cs;
+            const bool i8 = nd.bytes_mode && !out32;
+            if (i8) {
+                int slot_k[2];
+                const int nr = table_slots(st.out, slot_k);      // (out_formats below sets q[k] from the same st.out.f8[k])
+                for (int j = 0; j < nr; ++j) a.bt[slot_k[j]] = (const uint8_t*)W8(nd.tab_off + 256 * (size_t)j);
+            } else a.t32 = B32(nd.tab_off);
+            st.inst = table_inst(a, i8);
+            a.dVpp = fast_divisor((uint32_t)(a.Cs / (st.inst == 1 ? 16 : 4)));
+            snprintf(kb, sizeof kb, "%s", table_kernel_name(st.inst));
             out_formats(a.q); st.args = a; break;
         }
         case S_SUMPOOL: {
@@ -4089,7 +4240,25 @@ static int run_step(const f8_net* net, const RunIO& io, const Step& st, int n0, 
             e = launch_chanmap(a, st.inst, s);
             break;
         }
+        case S_TABLE: {
+            TableArgs a = std::get<TableArgs>(st.args);
+            const Tensor& o = T[st.out.t];
+            a.src = (const int8_t*)fp(T[st.src_t].forms[st.src_f]);
+            a.M = N * o.H * o.W;
+            fill_out(&a.out32, a.q);
+            e = launch_table(a, st.inst, s);
+            break;
+        }
         case S_MUL: case S_HGATE: {
+            if (std::holds_alternative<TableMulArgs>(st.args)) {
+                TableMulArgs a = std::get<TableMulArgs>(st.args);
+                const Tensor& o = T[st.out.t];
+                a.m.a = (const int8_t*)fp(T[st.src_t].forms[st.src_f]); a.m.b = fp(T[st.res_t].forms[st.res_f]);
+                a.m.M = N * o.H * o.W;
+                fill_out(&a.m.out32, a.m.q);
+                e = launch_table_mul(a, st.inst, s);
+                break;
+            }
             MulArgs a = std::get<MulArgs>(st.args);
             const Tensor& o = T[st.out.t];
             if (st.kind == S_MUL) { a.a = (const int8_t*)fp(T[st.src_t].forms[st.src_f]); a.b = fp(T[st.res_t].forms[st.res_f]); }

@@ -11,8 +11,8 @@ import os
 
 import numpy as np
 
-from . import _lib, topology
-from ._lib import ConvDesc, LinearDesc, MulDesc, check
+from . import _lib, tables, topology
+from ._lib import ConvDesc, LinearDesc, MulDesc, TableDesc, check
 
 AVGPOOL_SHIFT = 6   # FXQAvgPool2d(7).shiftnum = round(log2(49)), fix_quant_ops.py:121-122
 
@@ -174,6 +174,27 @@ class F8Net:
     def hard_swish(self, src, *, x_fl, x_signed, g_fl, label=None):
         """x * relu6(x + 3) (six times hard-swish): mul(src, hard_gate(src)) with x read at (x_fl, x_signed) and the gate, 0 .. 6, at unsigned g_fl."""
         return self.mul(src, self.hard_gate(src), a_fl=x_fl, a_signed=x_signed, b_fl=g_fl, b_signed=False, label=label)
+
+    def table(self, src, table, *, in_fl, in_signed, out_fl, label=None):
+        """Any pointwise function as a 256-entry table (f8_net_table): src requantised to (in_fl, in_signed) gives q; the result is table[q] (unsigned)
+        or table[q + 128] (signed), int32 at fraclen out_fl.  `table`: 256 int32 entries (f8net_amd.tables builds them)."""
+        tab = np.ascontiguousarray(np.asarray(table).reshape(-1), dtype=np.int32)
+        if tab.size != 256 or not np.array_equal(tab, np.asarray(table).reshape(-1)):
+            raise ValueError('table: 256 int32 entries')
+        d = TableDesc(in_fl=int(in_fl), in_signed=int(bool(in_signed)), out_fl=int(out_fl))
+        t = check(self._L.f8_net_table(self._h, src, ctypes.byref(d), tab.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
+        if label:
+            self._L.f8_net_set_label(self._h, t, label.encode())
+        return t
+
+    def sigmoid(self, src, *, in_fl, in_signed, out_fl, label=None):
+        return self.table(src, tables.sigmoid(in_fl, in_signed, out_fl), in_fl=in_fl, in_signed=in_signed, out_fl=out_fl, label=label)
+
+    def swish(self, src, *, in_fl, in_signed, out_fl, label=None):
+        return self.table(src, tables.swish(in_fl, in_signed, out_fl), in_fl=in_fl, in_signed=in_signed, out_fl=out_fl, label=label)
+
+    def tanh(self, src, *, in_fl, in_signed, out_fl, label=None):
+        return self.table(src, tables.tanh(in_fl, in_signed, out_fl), in_fl=in_fl, in_signed=in_signed, out_fl=out_fl, label=label)
 
     def maxpool(self, src, k=3, stride=2, pad=1, label=None):
         t = check(self._L.f8_net_maxpool(self._h, src, k, stride, pad))

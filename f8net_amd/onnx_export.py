@@ -18,6 +18,8 @@ opset-11 vocabulary is written directly from the integer graph — per op the no
     channel shuffle                Reshape([-1, g, C / g, H, W]), Transpose(perm [0, 2, 1, 3, 4]), Reshape([-1, C, H, W])
     fixed-point product            the requant of each operand as in front of a conv, [Unsqueeze(axes [2, 3]) of a [N, C] gate vector,] Mul [, Relu]
     hard gate relu6(x + 3)         Clip(x, -3 * 2^fl, 3 * 2^fl), Add(3 * 2^fl)
+    256-entry table                the requant of the source as in front of a conv, [Add(128) for a signed index,] Gather(axis=0) on a 256-entry int32
+                                   initializer named `table_<t>.in_fl_<i>.out_fl_<o>` (the name carries the two fraction lengths)
     upsampling, nearest            Resize(nearest, asymmetric, floor; scales [1, 1, sh, sw])
     upsampling, bilinear           Cast(f32), Resize(linear, half_pixel; scales [1, 1, s, s]), Mul(4 s^2), Cast(i32)
     x.view(x.size(0), -1)          Shape, Gather, Unsqueeze, Concat, Reshape         (fix_resnet.py:371)
@@ -195,6 +197,15 @@ def export_graph(ig: IntGraph) -> bytes:
             lim = 3 << o.shift
             v = w.emit('Clip', [name[o.src], w.const(float(-lim), np.float32), w.const(float(lim), np.float32)])
             y = w.emit('Add', [w.cast(v, onnx_io.INT32), w.const(lim, np.int32)])
+            if o.src in flat:
+                flat.add(t)
+        elif o.kind == 'table':
+            A = _requant(w, name[o.src], o.shift, o.signed)
+            if o.signed:
+                A = w.emit('Add', [A, w.const(128, np.int32)])
+            key = f'table_{t}.in_fl_{int(o.in_fl)}.out_fl_{int(o.out_fl)}'
+            inits[key] = np.ascontiguousarray(np.asarray(o.table).reshape(256), dtype=np.int32)
+            y = w.emit('Gather', [key, A], {'axis': 0})
             if o.src in flat:
                 flat.add(t)
         elif o.kind == 'mul':

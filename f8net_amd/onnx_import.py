@@ -18,6 +18,7 @@ picks the least assignment that satisfies the reference's asserts (0 <= input_fr
 fix_quant_ops.py:91-98) — any assignment with the same shifts computes the same integers, and the logits the
 reference returns are raw integers (`.float()` without rescaling, fix_resnet.py:383).
 """
+import re
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -36,7 +37,7 @@ class OnnxImportError(ValueError):
 
 @dataclass
 class IntOp:
-    kind: str                      # input | conv | deconv | linear | add | maxpool | avgpool | avgpool2d | concat | upsample | slice | shuffle | mul | hgate
+    kind: str                      # input | conv | deconv | linear | add | maxpool | avgpool | avgpool2d | concat | upsample | slice | shuffle | mul | hgate | table
     src: int = -1                  # tensor id (index into IntGraph.ops)
     src2: int = -1                 # add: the operand that is NOT shifted; mul: operand b (of src's shape, or [C, 1, 1])
     weight: np.ndarray = None
@@ -50,6 +51,9 @@ class IntOp:
                                    # hgate: the source's fraction length fl itself (the file holds 3 * 2^fl); mul: unused (`shifts`)
     signed: bool = False           # conv/linear: clamp range of the requant (+-127 vs 0..255); mul: of operand a
     signed2: bool = False          # mul: clamp range of operand b's requant
+    table: np.ndarray = None       # table: the 256 int32 entries (f8_net_table); `shift` is the requant n of the source, `signed` its clamp range
+    in_fl: int = None              # table: the fraction length of the index format — with `shift` it pins the SOURCE's fraction length absolutely (in_fl + shift),
+    out_fl: int = None             # table: ... and of the entries = of the result, pinned absolutely: the entries are constants of the graph, as a hard gate's 3 * 2^fl
     relu: bool = False
     swap: bool = False             # add: the shifted operand is the Add's second input (`res += x << k`) — cosmetic
     key: str = ''                  # state_dict key of the layer ('head.0', 'stage_0_layer_0.body.0', ...)
@@ -124,15 +128,22 @@ class IntGraph:
                     raise OnnxImportError(f'hard gate at fraction length {o.shift}: outside 0 .. 28 (f8_net_hard_gate)')
                 eq(o.src, ZERO, o.shift)
                 eq(t, o.src, 0)
+            elif o.kind == 'table':                  # the entries are constants of the graph: both fraction lengths are pinned absolutely
+                if not 0 <= o.in_fl <= (7 if o.signed else 8):
+                    raise OnnxImportError(f'table: index format fraction length {o.in_fl} outside the 8-bit formats')
+                if not 0 <= o.out_fl <= 38:
+                    raise OnnxImportError(f'table: result fraction length {o.out_fl} outside 0 .. 38 (f8_net_table)')
+                eq(o.src, ZERO, o.in_fl + o.shift)
+                eq(t, ZERO, o.out_fl)
             elif o.kind == 'mul':
                 # V[t] = a_fl + b_fl is a sum of two unknowns, no difference constraint — unless b's format is anchored: b is a hard gate's result, whose
                 # fraction length is a constant, so b_fl is one and V[t] = V[a] - n_a + b_fl
                 g = self.ops[o.src2]
-                if g.kind != 'hgate':
+                if g.kind not in ('hgate', 'table'):
                     raise OnnxImportError('Mul of two activations whose second operand is not a hard gate\'s result: its format is not anchored, so the '
                                           'product\'s fraction length (a sum of two unknowns) is no difference constraint')
                 n_a, n_b = o.shifts
-                b_fl = g.shift - n_b
+                b_fl = (g.shift if g.kind == 'hgate' else g.out_fl) - n_b      # (a table's result is anchored as a gate's: out_fl is a constant)
                 if not 0 <= b_fl <= (7 if o.signed2 else 8):
                     raise OnnxImportError(f'Mul: the gate operand\'s format fraction length {b_fl} is outside the 8-bit formats')
                 lim = 7 if o.signed else 8
@@ -226,6 +237,8 @@ class IntGraph:
                 ids[t] = net.channel_shuffle(ids[o.src], o.groups)
             elif o.kind == 'hgate':
                 ids[t] = net.hard_gate(ids[o.src])
+            elif o.kind == 'table':
+                ids[t] = net.table(ids[o.src], o.table, in_fl=o.in_fl, in_signed=o.signed, out_fl=o.out_fl)
             elif o.kind == 'mul':
                 ids[t] = net.mul(ids[o.src], ids[o.src2], a_fl=V[o.src] - o.shifts[0], a_signed=o.signed, b_fl=V[o.src2] - o.shifts[1],
                                  b_signed=o.signed2, relu=o.relu)
@@ -534,6 +547,32 @@ def import_graph(model, input_signed=False) -> IntGraph:
                 val[out] = ('T', len(ig.ops) - 1)
         elif op == 'Unsqueeze' and val.get(nd.inputs[0], ('?',))[0] in ('T', 'clip'):
             val[out] = val[nd.inputs[0]]                           # a [N, C] gate vector lifted to [N, C, 1, 1] in front of a Mul: no arithmetic
+        elif op == 'Gather' and val.get(nd.inputs[0], ('?',))[0] in ('init', 'T', 'clip'):
+            # the table op: Gather(axis = 0) on a 256-entry int32 initializer, indexed by a requantised activation (+ 128 for a signed format).  The
+            # initializer's NAME carries the two fraction lengths nothing else in the file states: `<any>.in_fl_<i>.out_fl_<o>` (onnx_export writes it)
+            axis = a.get('axis', 0)
+            if val[nd.inputs[0]][0] != 'init':
+                raise OnnxImportError(f'Gather of an activation (axis {axis}): only a table lookup, Gather(table initializer, index), is imported')
+            key, arr = init(nd.inputs[0], 'Gather')
+            arr = np.asarray(arr)
+            if axis != 0:
+                raise OnnxImportError(f'Gather on initializer {key!r} along axis {axis}: a table lookup gathers along axis 0')
+            if arr.shape != (256,) or arr.dtype != np.int32:
+                raise OnnxImportError(f'Gather on initializer {key!r} of shape {tuple(arr.shape)} and type {arr.dtype}: a table is 256 int32 entries')
+            m = re.fullmatch(r'.*\.in_fl_(\d+)\.out_fl_(\d+)', key)
+            if not m:
+                raise OnnxImportError(f'Gather on initializer {key!r}: the name does not end in .in_fl_<i>.out_fl_<o>, so the table\'s fraction lengths are unknown')
+            e = val.get(nd.inputs[1], ('?',))
+            offset = 0
+            if e[0] == 'addc':
+                offset, e = e[2], e[1]
+            if e[0] != 'clip':
+                raise OnnxImportError('Gather index is not a requantised activation (Clip to an 8-bit format [, Add 128])')
+            src, n, signed = _match_requant(e)
+            if offset != (128 if signed else 0):
+                raise OnnxImportError(f'Gather index offset {offset} on a {"signed" if signed else "unsigned"} index: expected {128 if signed else 0}')
+            ig.ops.append(IntOp('table', src=src, shift=n, signed=signed, table=arr.copy(), in_fl=int(m.group(1)), out_fl=int(m.group(2))))
+            val[out] = ('T', len(ig.ops) - 1)
         elif op in ('Shape', 'Gather', 'Unsqueeze', 'Concat'):
             val[out] = ('opaque',)                                 # the `x.view(x.size(0), -1)` plumbing before the FC
         elif op == 'Reshape':
@@ -579,9 +618,9 @@ def import_graph(model, input_signed=False) -> IntGraph:
                 ra, rb = requant_src(x, 'Mul'), requant_src(y, 'Mul')
                 if ra[1] is None or rb[1] is None:
                     raise OnnxImportError('Mul of two activations that are not both requantised to 8-bit formats')
-                if ig.ops[rb[0]].kind != 'hgate' and ig.ops[ra[0]].kind == 'hgate':
+                if ig.ops[rb[0]].kind not in ('hgate', 'table') and ig.ops[ra[0]].kind in ('hgate', 'table'):
                     ra, rb = rb, ra
-                if ig.ops[rb[0]].kind != 'hgate':
+                if ig.ops[rb[0]].kind not in ('hgate', 'table'):
                     raise OnnxImportError('Mul of two activations of which none is a hard gate\'s result: no operand format is anchored, so the '
                                           'product\'s fraction length cannot be solved (only x * hard_gate(.) is imported)')
                 ig.ops.append(IntOp('mul', src=ra[0], src2=rb[0], shifts=[ra[1], rb[1]], signed=ra[2], signed2=rb[2]))

@@ -12,6 +12,7 @@ performance path is the fused whole-net plan in `f8net_amd.net` / `f8net_amd.int
 import torch
 import torch.nn as nn
 
+from . import tables
 from . import torch_ops  # noqa: F401  (registers torch.ops.f8net.*; every function below goes through the dispatcher)
 
 
@@ -236,6 +237,37 @@ class F8ChannelGate(nn.Module):
         res = torch.ops.f8net.mul_q(x, s4, x.output_fraclen, s.output_fraclen, self.x_fl, self.x_signed, self.g_fl, False, True, False)
         setattr(res, 'output_fraclen', self.x_fl + self.g_fl)
         return res
+
+
+class F8Table(nn.Module):
+    """Any pointwise function on int32 device tensors with a HIP forward (`torch.ops.f8net.table_q`, f8_net_table): x requantised to
+    (in_fl, in_signed) indexes `table` (256 int32 entries: f8net_amd.tables.from_function and friends); the result's fraclen is out_fl."""
+
+    def __init__(self, table, in_fl, in_signed, out_fl):
+        super().__init__()
+        self.register_buffer('table', torch.as_tensor(table, dtype=torch.int32).reshape(256).clone())
+        self.in_fl, self.in_signed, self.out_fl = int(in_fl), bool(in_signed), int(out_fl)
+        self.int_op_only = True
+
+    def forward(self, x):
+        _require_dev_i32(x, type(self).__name__)
+        res = torch.ops.f8net.table_q(x, self.table, x.output_fraclen, self.in_fl, self.in_signed, self.out_fl)
+        setattr(res, 'output_fraclen', self.out_fl)
+        return res
+
+
+class F8Sigmoid(F8Table):
+    """nn.Sigmoid of x read at (in_fl, in_signed), rounded half to even to fraclen out_fl."""
+
+    def __init__(self, in_fl, in_signed=True, out_fl=12):
+        super().__init__(tables.sigmoid(in_fl, in_signed, out_fl), in_fl, in_signed, out_fl)
+
+
+class F8Swish(F8Table):
+    """nn.SiLU of x read at (in_fl, in_signed), rounded half to even to fraclen out_fl."""
+
+    def __init__(self, in_fl, in_signed=True, out_fl=8):
+        super().__init__(tables.swish(in_fl, in_signed, out_fl), in_fl, in_signed, out_fl)
 
 
 class F8MaxPool2d(nn.Module):

@@ -17,6 +17,9 @@ the dispatcher.
     f8net::mul_q(a, b, a_src_fl, b_src_fl, a_fl, a_signed, b_fl, b_signed, hard_gate_b, relu)
                                                      requant(a) * requant(b), b of a's shape or [N, C, 1, 1]; hard_gate_b: b is relu6(b + 3) in fixed point
                                                      first (f8_net_mul, f8_net_hard_gate; no reference call site)
+    f8net::table_q(x, table, src_fl, in_fl, in_signed, out_fl)
+                                                     table[requant(x) (+ 128 signed)]: any pointwise function as 256 int32 entries (f8_net_table;
+                                                     f8net_amd.tables builds sigmoid, swish, tanh, ...; no reference call site)
     f8net::net_forward(x, handle)                    IntModel.forward                 fix_resnet.py:352-383 (handle: register_net)
     f8net::net_forward_taps(x, handle)               ... of a net with further outputs (F8Net.output called more than once): all of them
     f8net::net_forward_f32(images, handle, normalize)  forward_loss input quantisation + IntModel.forward, fix_train.py:683-692
@@ -49,6 +52,7 @@ _DEF.define('avgpool2d_sum(Tensor x, int k, int stride, int pad) -> Tensor')
 _DEF.define('maxpool(Tensor x, int k, int stride, int pad) -> Tensor')
 _DEF.define('channel_shuffle(Tensor x, int groups) -> Tensor')
 _DEF.define('mul_q(Tensor a, Tensor b, int a_src_fl, int b_src_fl, int a_fl, bool a_signed, int b_fl, bool b_signed, bool hard_gate_b, bool relu) -> Tensor')
+_DEF.define('table_q(Tensor x, Tensor table, int src_fl, int in_fl, bool in_signed, int out_fl) -> Tensor')
 _DEF.define('net_forward(Tensor x, int handle) -> Tensor')
 _DEF.define('net_forward_taps(Tensor x, int handle) -> Tensor[]')
 _DEF.define('net_forward_f32(Tensor images, int handle, bool normalize) -> Tensor')
@@ -358,6 +362,34 @@ def _mul_q(a, b, a_src_fl, b_src_fl, a_fl, a_signed, b_fl, b_signed, hard_gate_b
     return _plans.get(key, (), N, build).run(x).view(N, C, H, W)
 
 
+def _table_q(x, table, src_fl, in_fl, in_signed, out_fl):
+    """table[int_op_only_fix_quant(x, 8, in_fl, src_fl, in_signed) (+ 128 for a signed format)] (f8_net_table): x int32 [N, C, H, W] at fraction length
+    src_fl, `table` 256 int32 entries (any device), the result int32 of x's shape at fraction length out_fl.  Only the SHIFT src_fl - in_fl enters the
+    values, so the planned net declares its input at max(shift, 0) and the index format relative to it; a shift below -8 (-7 signed) fits no 8-bit
+    format and raises ValueError.  The plan is cached per shape and formats and snapshots the table as a conv's plan snapshots its weights: one plan per
+    key, rebuilt when another table tensor arrives or this one is edited in place (identity and version are checked; the plan cache is an LRU of bounded
+    size), and the table is read back from the device only when a plan is built.  Keep the table tensor alive between calls (ops.F8Table does)."""
+    _i32(x, 'table_q')
+    _i32(table, 'table_q')
+    if table.numel() != 256:
+        raise ValueError(f'table_q: the table has {table.numel()} entries, not 256')
+    x = x.contiguous()
+    N, C, H, W = x.shape
+    n = src_fl - in_fl
+    F = max(n, 0)
+    if not (0 <= F - n <= (7 if in_signed else 8) and n <= 30):
+        raise ValueError(f'table_q: shift {n} ({"signed" if in_signed else "unsigned"}) fits no 8-bit index format')
+    def build(k):
+        tab = table.detach().cpu().numpy().reshape(256).copy()
+        net = F8Net()
+        t = net.input(C, H, W, F)
+        net.output(net.table(t, tab, in_fl=F - n, in_signed=in_signed, out_fl=out_fl), as_float=False)
+        return net.finalize(k)
+
+    key = ('table', x.device.index, C, H, W, n, bool(in_signed), int(out_fl))
+    return _plans.get(key, (table,), N, build).run(x).view(N, C, H, W)
+
+
 # ------------------------------------------------------------------------------------------ whole nets
 _nets = {}
 
@@ -390,7 +422,7 @@ def _net_forward_f32(images, handle, normalize):
 # ------------------------------------------------------------------------------------------ registration
 _CUDA = Library('f8net', 'IMPL', 'CUDA')
 for _n, _f in (('requant', _requant), ('relu_', _relu_), ('add_align_', _add_align_), ('conv2d', _conv2d), ('conv_transpose2d', _conv_transpose2d), ('linear', _linear),
-               ('avgpool_sum', _avgpool_sum), ('avgpool2d_sum', _avgpool2d_sum), ('maxpool', _maxpool), ('channel_shuffle', _channel_shuffle), ('mul_q', _mul_q), ('net_forward', _net_forward), ('net_forward_taps', _net_forward_taps),
+               ('avgpool_sum', _avgpool_sum), ('avgpool2d_sum', _avgpool2d_sum), ('maxpool', _maxpool), ('channel_shuffle', _channel_shuffle), ('mul_q', _mul_q), ('table_q', _table_q), ('net_forward', _net_forward), ('net_forward_taps', _net_forward_taps),
                ('net_forward_f32', _net_forward_f32)):
     _CUDA.impl(_n, _f)
 
@@ -410,6 +442,7 @@ _META.impl('maxpool', lambda x, k, stride, pad: x.new_empty(
     (x.shape[0], x.shape[1], (x.shape[2] + 2 * pad - k) // stride + 1, (x.shape[3] + 2 * pad - k) // stride + 1)))
 _META.impl('channel_shuffle', lambda x, groups: torch.empty_like(x))
 _META.impl('mul_q', lambda a, b, a_src_fl, b_src_fl, a_fl, a_signed, b_fl, b_signed, hard_gate_b, relu: torch.empty_like(a))
+_META.impl('table_q', lambda x, table, src_fl, in_fl, in_signed, out_fl: torch.empty_like(x))
 _META.impl('net_forward', lambda x, handle: x.new_empty((x.shape[0], _nets[handle].out_elems),
                                                         dtype=torch.float32 if _nets[handle].out_float else torch.int32))
 _META.impl('net_forward_taps', lambda x, handle: [x.new_empty((x.shape[0], _nets[handle].out_elems), dtype=torch.float32 if _nets[handle].out_float else torch.int32)] + [

@@ -240,7 +240,7 @@ int f8_net_channel_shuffle(f8_net* net, int src, int groups);
  * ReLU-gated or plain products are f8_net_mul alone.
  * Both return the tensor id.  F8_ERR_INVALID: a bad tensor id, a null desc, b neither of a's shape nor [a.C, 1, 1], a format outside the limits above,
  * a shift outside -31 .. 30; f8_net_hard_gate on a source with fraclen > 28 (6 * 2^fl must fit int32) or < 0.  F8_ERR_STATE after finalize.
- * NOT built: a true sigmoid (no fixed-point function; a 256-entry table op would be one), a [1, H, W] spatial broadcast, exporter support from float models.
+ * NOT built: a [1, H, W] spatial broadcast, exporter support from float models.  (A true sigmoid is f8_net_table, below.)
  * The plan (f8_mul.hip).  A mul reads int8: it registers (a_fl, a_signed) on a and (b_fl, b_signed) on b exactly as a conv with quant_input = 1
  * registers its format, the producers write the forms (a third format of one tensor: a `requant:` step).  One launch, its mode shown by the token:
  * `mul_i8:` / `chmul_i8:` — the result is read in at most two int8 formats and by nothing else — writes those formats only; `mul_i32:` / `chmul_i32:`
@@ -257,6 +257,39 @@ typedef struct f8_mul_desc {
 } f8_mul_desc;
 int f8_net_mul(f8_net* net, int a, int b, const f8_mul_desc* desc);
 int f8_net_hard_gate(f8_net* net, int src);
+
+/* The 256-entry table op: ANY pointwise function of an 8-bit fixed-point activation — a true sigmoid (SENet, SE-ResNet, RegNetY, EfficientNet gates;
+ * pose and detection heads), swish / SiLU, Mish, GELU, leaky ReLU, tanh.  Every activation a consumer reads here is an 8-bit fixed-point value, so a
+ * function of it IS a table of 256 entries, exact but for the rounding of the entries.  The reference defines no such class; the semantics are fixed
+ * here in its own terms (int_op_only_fix_quant, fix_quant_ops.py:91-112, on the source):
+ *   q   = int_op_only_fix_quant(src, 8, in_fl, src.fraclen, in_signed): the round-half-even shift and the clamp every conv consumer and f8_net_mul
+ *         apply: 0 .. 255 unsigned, -127 .. 127 signed;
+ *   out = table[q] for an unsigned format, table[q + 128] for a signed one (entry 0 of a signed table is never read).
+ * The shape is the source's, out.fraclen = out_fl; no further rounding, clamp or ReLU: the entries are any int32.  The 256 entries are copied at the call.
+ * Format limits are the mul's (the conv's): 0 <= in_fl <= 8 unsigned, 0 <= in_fl <= 7 signed; the shift src.fraclen - in_fl lies in -31 .. 30.
+ * 0 <= out_fl <= 38: beyond 38 no 8-bit format could read the result (its shift would exceed 30).
+ * Returns the tensor id.  F8_ERR_INVALID: a null desc or table, a bad tensor id, a format or shift outside the limits, out_fl outside 0 .. 38.
+ * F8_ERR_STATE after finalize.  (f8net_amd/tables.py builds the entries of sigmoid, tanh, swish, mish, gelu, leaky_relu, hard_sigmoid.)
+ * The plan (f8_table.hip).  A table reads int8: it registers (in_fl, in_signed) on its source as a conv with quant_input = 1 does, the producer writes
+ * the form (a third format of one tensor: a `requant:` step).  Its value bound is the largest magnitude among the reachable entries.  One launch, its
+ * mode by the gathers' rule, shown by the token:
+ *   `table_i8:`   the result is read in at most two int8 formats and by nothing else.  At finalize the host composes one 256-BYTE table per format —
+ *                 entry i = the requantisation of table[i] to that format, storage bias folded in — and the launch only moves bytes.
+ *   `table_i32:`  a join, a pool, an output or a third format needs the int32 form: the launch writes it and up to two int8 forms (option table_i8 = 0:
+ *                 every table runs this kernel; it then writes the int32 form only where something needs it).
+ *   `table+chmul_i8:` / `table+chmul_i32:`   the sigmoid SE gate: a table that ONLY the b operand of one broadcast f8_net_mul reads, and that is no
+ *                 output, emits no launch; the mul launch reads the table's source bytes and looks them up in a byte table composed for
+ *                 (b_fl, b_signed) (option fuse_table: 1, the default, where the map has fewer than 2^20 values an image — the fused
+ *                 launch measured slower above —, 2 always, 0 never: two launches).  Same values in every case, bit for bit.
+ * The device tables live in the weight image f8_net_upload moves.  A tensor read by a table exists in device memory: no matcher counts the table among
+ * a block's readers, so it cuts a chain or fused block where an output tap does.
+ * NOT built: the table fused into its producer's epilogue, per-channel tables (PReLU), an element-wise table+mul (swish is itself one table),
+ * exporter support from float models. */
+typedef struct f8_table_desc {
+    int32_t in_fl, in_signed;   /* format the source is read in: int_op_only_fix_quant(src, 8, in_fl, src.fraclen, in_signed) */
+    int32_t out_fl;             /* fraction length of the entries = of the result */
+} f8_table_desc;
+int f8_net_table(f8_net* net, int src, const f8_table_desc* desc, const int32_t table_host[256]);
 
 /* Head max-pool nn.MaxPool2d(k, stride, pad) via the float detour (fix_resnet.py:358-359) or
  * FXQMaxPool2d (fix_quant_ops.py:150-157); exact integer max. */
@@ -454,7 +487,13 @@ int f8_net_check(f8_net* net);
  *               fuse_shuffle (default 1: a concat of `groups` operands of one width that only an i8-mode shuffle reads emits no launch; the shuffle
  *               launch reads the operands, token concat+shuffle{g}_i8:; 0: two launches.  Same values either way, bit for bit),
  *               fuse_hgate (default 1: a hard gate whose only reader is the b operand of one f8_net_mul emits no launch; the mul launch reads the gate's
- *               source in int32, tokens hgate+mul_*: / hgate+chmul_*:; 0: an hgate: launch and the mul launch.  Same values either way, bit for bit)
+ *               source in int32, tokens hgate+mul_*: / hgate+chmul_*:; 0: an hgate: launch and the mul launch.  Same values either way, bit for bit),
+ *               table_i8 (default 1: an f8_net_table whose result is read in at most two int8 formats and by nothing else gathers bytes from host-composed
+ *               byte tables, token table_i8:; 0: every one runs the int32-mode kernel, token table_i32: — it reads the int32 entries and requantises on
+ *               the device, and writes the int32 form only where something needs it.  Same values either way, bit for bit),
+ *               fuse_table (default 1: a table whose only reader is the b operand of one broadcast f8_net_mul emits no launch where the map has fewer
+ *               than 2^20 values an image — the measured rule, profiles/table_r15.md —, tokens table+chmul_*:; 2: on every size; 0: a table_*: launch
+ *               and the mul launch.  Same values in every case, bit for bit)
  *   scheduling: chunk56 / chunk28 / chunk14 (images per chunk of the fused blocks; -1 = derived from chunk_budget_mb, 0 = whole
  *               batch), chunk_budget_mb (memory-side cache a chunk's int32 stream may occupy), chunk_ds, chunk_opener,
  *               split_streams, graph, stagger, stagger_pipelined, stem_wpc, stem_grid_div (row-walking head on 1 / n of the CUs; 0 = by output form), wstat_grid_div (0 .. 32, default 0, environment F8_WSTAT_GRID_DIV: f8::conv1x1_wstat_kernel sizes its pixel groups for 1 / n of the CUs, at least one — tests walk long tile rings on small maps; 0 = all of them; the plan and the values do not move), check_device, check_input_range, pipeline_depth (2..4 runs in flight),
