@@ -3,7 +3,7 @@ tests/test_avgpool_plan.py (acceptance, refusals, tokens, kernel symbols on the 
 the ONNX round trip; no GPU) and tests/test_gpu_avgpool.py (every case on every leg, bit for bit on the device).  No test functions here.
 
 The reference is numpy on int64 over the zero-padded input: the k x k strided slices summed, wrapped to int32 at the end (`sumpool_exact`,
-`sumpool_ref`); the fraclen grows by `shift`, by default the reference's round(log2(k^2)).  `pin_to_torch` holds it with exact equality against
+`sumpool_ref` of tests/ref_ops.py); the fraclen grows by `shift`, by default the reference's round(log2(k^2)).  `pin_to_torch` holds it with exact equality against
 F.avg_pool2d(float64, count_include_pad=True, divisor_override=1) — the divisor 1, not "the average times k^2": sum / 9 * 9 is not exact in floating
 point — and `pin_to_oracle` against the oracle's depthwise conv with all-ones weights on 8-bit inputs, where the two definitions coincide.
 
@@ -12,20 +12,17 @@ fraclen 13 -> pool -> readers: one 32-output 1x1 conv per (input_fl, signed), su
 
 The expected plan token of every case, the kernel symbol on each leg and the forms its launch writes are WRITTEN BY HAND (the rule: DESIGN.md
 4.5l); nothing here asks the planner for them."""
-import functools
-import math
+import sys
 
 import numpy as np
 
 import graph_cases
-import upsample_cases as uc
 from concat_cases import FUSE_ALL, X_FL, producer, readers  # noqa: F401  (the tests take them from here)
 from f8net_amd import synth
-from f8net_amd.onnx_import import IntOp
-from graph_cases import graph_forward, launch_lines  # noqa: F401  (the walker of an imported graph: the tests take it from here)
+from graph_cases import launch_lines
 from ir_cases import _b, _w
 from oracle import oracle
-from upsample_cases import wrap32
+from ref_ops import default_shift, sumpool_exact, sumpool_ref
 
 # option sumpool_wide = 1: windows of this size and more that do not overlap (stride >= kernel) run the wide kernel (sumpool_wide_rule, f8_internal.h;
 # measured: profiles/sumpool_r12.md) — by hand
@@ -33,32 +30,8 @@ WIDE_FROM = 3
 GLOBAL = 'avgpool_sum:'
 
 
-def default_shift(k):
-    return int(round(math.log2(k * k)))
-
-
 def out_size(n, k, stride, pad):
     return (n + 2 * pad - k) // stride + 1
-
-
-def sumpool_exact(x, k, stride, pad):
-    """(N, C, H, W) integers -> the window sums over the zero-padded map, int64, not wrapped."""
-    x = np.asarray(x, np.int64)
-    N, C, H, W = x.shape
-    P, Q = out_size(H, k, stride, pad), out_size(W, k, stride, pad)
-    assert P >= 1 and Q >= 1
-    xp = np.zeros((N, C, H + 2 * pad, W + 2 * pad), np.int64)
-    xp[:, :, pad:pad + H, pad:pad + W] = x
-    y = np.zeros((N, C, P, Q), np.int64)
-    for r in range(k):
-        for s in range(k):
-            y += xp[:, :, r:r + (P - 1) * stride + 1:stride, s:s + (Q - 1) * stride + 1:stride]
-    return y
-
-
-def sumpool_ref(x, fl, k, stride, pad, shift=None):
-    """-> (int32 values, fraclen)."""
-    return wrap32(sumpool_exact(x, k, stride, pad)), fl + (default_shift(k) if shift is None else shift)
 
 
 def pin_to_torch(x, k, stride, pad):
@@ -78,22 +51,6 @@ def pin_to_oracle(x, k, stride, pad):
     C = x.shape[1]
     want = oracle.conv2d(x, np.ones((C, 1, k, k), np.int32), None, stride, pad, C)
     np.testing.assert_array_equal(sumpool_ref(x, 0, k, stride, pad)[0], want)
-
-
-class _Graph(uc._Graph):
-    """upsample_cases._Graph (concat, the pools, upsample) with the windowed average pool."""
-
-    def avgpool(self, t, k, stride=None, pad=0, shift=None, label=None):
-        stride = k if stride is None else stride
-        o = self._id(lambda: self.net.avgpool(t, k, stride, pad, shift, label=label))
-        self.v[o] = sumpool_ref(self.v[t][0], self.v[t][1], k, stride, pad, shift)
-        return o
-
-    def adaptive_avgpool(self, t, bins, label=None):
-        k = self.v[t][0].shape[2] // bins
-        o = self._id(lambda: self.net.adaptive_avgpool(t, bins, label=label))
-        self.v[o] = sumpool_ref(self.v[t][0], self.v[t][1], k, k, 0)
-        return o
 
 
 # ---- the builders.  Each returns (output tensor ids in output order, [pool tensor ids])
@@ -285,41 +242,9 @@ def make_input(name, n=None):
     return synth.rand_uniform_int(5, f'poolx{name}', (n or c['N'], c['cin'], c['H'], c['W']), 0, 255).astype(np.int32)
 
 
-def build_graph(name, x, record=True):
-    """Returns (graph, output ids, pool ids)."""
-    c = CASES[name]
-    g = _Graph(x, X_FL, record=record)
-    outs, pools = c['build'](g, next(iter(g.v)), c)
-    return g, outs, pools
-
-
-@functools.lru_cache(maxsize=None)
-def reference(name):
-    """(graph, output ids, pool ids) of the case over N + 1 images, evaluated on the reference alone, once; nothing may write into its arrays."""
-    return build_graph(name, make_input(name, CASES[name]['N'] + 1), record=False)
-
-
-def plan(name, x, max_batch=None, **opts):
-    g, outs, pools = build_graph(name, x)
-    for k, v in dict(CASES[name]['opts'], **opts).items():
-        g.net.set_option(k, v)
-    g.net.finalize(max_batch or x.shape[0])
-    return g, outs, pools
-
-
 def pool_lines(net):
     """[(launch index, plan token, kernel symbol)] of the handle's windowed-pool launches, in launch order."""
     return launch_lines(net, 'sumpool')
 
 
-class Recorder(graph_cases.Recorder, _Graph):
-    def avgpool(self, t, k, stride=None, pad=0, shift=None, label=None):
-        stride = k if stride is None else stride
-        return self._put(super().avgpool(t, k, stride, pad, shift),
-                         IntOp('avgpool2d', src=self.ids[t], kernel=k, stride=stride, pad=pad, shift=default_shift(k) if shift is None else shift))
-
-
-def int_graph(name):
-    """The case as an IntGraph, op for op what build_graph records (cases whose first output is the only one)."""
-    c = CASES[name]
-    return graph_cases.record_int_graph(Recorder, make_input(name), X_FL, lambda g, x0: c['build'](g, x0, c)[0][0])
+graph_cases.bind_cases(sys.modules[__name__])      # build_graph, reference, plan, int_graph

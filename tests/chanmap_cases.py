@@ -3,10 +3,10 @@
 fused launches, ONNX, the host code under the sanitizers; no GPU) and tests/test_gpu_chanmap.py (every case on both legs, bit for bit on the device).
 No test functions here.
 
-The reference is numpy fancy indexing on the int32 tensors the graph builder carries (concat_cases._Graph, which evaluates every other op with the
-oracle): `channel_shuffle(x, g) = x[:, (c % g) * (C / g) + c / g]`, `channel_slice(x, a, n) = x[:, a : a + n]`; test_chanmap_plan.py pins both to
+The reference is numpy fancy indexing on the int32 tensors the reference graph carries (tests/ref_ops.py):
+`channel_shuffle(x, g) = x[:, (c % g) * (C / g) + c / g]`, `channel_slice(x, a, n) = x[:, a : a + n]`; test_chanmap_plan.py pins both to
 torch.nn.functional.channel_shuffle / torch.split for every (C, groups) and (first, channels) of the table.  A concat in front of a shuffle is
-concat_cases.concat_align.
+ref_ops.concat_align.
 
 Unless a builder says otherwise a case is  input (8 channels, 0 .. 255, fraclen 8) -> one 1x1 producer conv per source, random weights (no two
 channels carry the same values) -> the op -> readers: one 32-output 1x1 conv per (input_fl, signed), summed.  Maps are 7 x 7 at N = 3 (147 pixels:
@@ -15,55 +15,15 @@ a ragged I32T block), one 9 x 11, one [C, 1, 1] at N = 2.
 The expected plan tokens and kernel symbols of every case — `exp`: option chanmap_i8 = 1 (the default plan, also with every fusing pass on), `exp0`:
 chanmap_i8 = 0, `nofuse`: fuse_shuffle = 0 — are WRITTEN BY HAND in launch order, the concat launches among them (the rule: DESIGN.md 4.5m); nothing
 here asks the planner for them."""
-import functools
+import sys
 
 import numpy as np
 
-import concat_cases as cc
 import graph_cases
 from concat_cases import FUSE_ALL, X_FL, producer, readers  # noqa: F401  (the tests take FUSE_ALL from here)
 from f8net_amd import synth
-from f8net_amd.onnx_import import IntOp
 from ir_cases import _b, _w
-from oracle import oracle
-
-
-def shuffle_index(C, groups):
-    c = np.arange(C)
-    return (c % groups) * (C // groups) + c // groups
-
-
-def channel_shuffle(x, groups):
-    return x[:, shuffle_index(x.shape[1], groups)]
-
-
-def channel_slice(x, first, channels):
-    return x[:, np.arange(first, first + channels)]
-
-
-class _Graph(cc._Graph):
-    """concat_cases._Graph with slice, split, channel_shuffle and the classifier."""
-
-    def slice(self, t, start, stop, label=None):
-        o = self._id(lambda: self.net.slice(t, start, stop, label=label))
-        self.v[o] = (channel_slice(self.v[t][0], start, stop - start), self.v[t][1])
-        return o
-
-    def split(self, t, sizes):
-        firsts = np.cumsum([0] + list(sizes))
-        return [self.slice(t, int(a), int(a + n)) for a, n in zip(firsts, sizes)]
-
-    def channel_shuffle(self, t, groups, label=None):
-        o = self._id(lambda: self.net.channel_shuffle(t, groups, label=label))
-        self.v[o] = (channel_shuffle(self.v[t][0], groups), self.v[t][1])
-        return o
-
-    def linear(self, t, w, b, *, weight_fl, input_fl, input_signed, label=None):
-        o = self._id(lambda: self.net.linear(t, w, b, weight_fl=weight_fl, input_fl=input_fl, input_signed=input_signed, quant_input=True, label=label))
-        x, fl = self.v[t]
-        y = oracle.linear(oracle.requant(x.reshape(x.shape[0], -1), input_fl, fl, input_signed), w, b)
-        self.v[o] = (y.reshape(y.shape[0], y.shape[1], 1, 1), input_fl + weight_fl)
-        return o
+from refgraph import record_int_graph
 
 
 # ---- the builders.  Each returns (output tensor ids in output order, [slice / shuffle tensor ids in launch order])
@@ -263,28 +223,6 @@ def make_input(name, n=None):
     return synth.rand_uniform_int(5, f'cmx{name}', shape, 0, 255).astype(np.int32)
 
 
-def build_graph(name, x, record=True):
-    """Returns (graph, output ids, slice / shuffle tensor ids)."""
-    c = CASES[name]
-    g = _Graph(x, c['x_fl'], record=record)
-    outs, ops = c['build'](g, next(iter(g.v)), c)
-    return g, outs, ops
-
-
-@functools.lru_cache(maxsize=None)
-def reference(name):
-    """(graph, output ids, op ids) of the case over N + 1 images, evaluated on the reference alone, once; nothing may write into its arrays."""
-    return build_graph(name, make_input(name, CASES[name]['N'] + 1), record=False)
-
-
-def plan(name, x, max_batch=None, **opts):
-    g, outs, ops = build_graph(name, x)
-    for k, v in opts.items():
-        g.net.set_option(k, v)
-    g.net.finalize(max_batch or x.shape[0])
-    return g, outs, ops
-
-
 def lines(net):
     """[(launch index, plan token, kernel symbol)] of the handle's slice, shuffle and concat launches, in launch order."""
     return graph_cases.launch_lines(net, ('slice_', 'shuffle', 'concat'))
@@ -349,22 +287,9 @@ def stage_input(n=None):
     return synth.rand_uniform_int(5, 'cmstage', (n or STAGE['N'], STAGE['cin'], STAGE['H'], STAGE['W']), 0, 255).astype(np.int32)
 
 
-class Recorder(graph_cases.Recorder, _Graph):
-    def slice(self, t, start, stop, label=None):
-        return self._put(super().slice(t, start, stop), IntOp('slice', src=self.ids[t], first=start, channels=stop - start))
-
-    def channel_shuffle(self, t, groups, label=None):
-        return self._put(super().channel_shuffle(t, groups), IntOp('shuffle', src=self.ids[t], groups=groups))
-
-    def avgpool_sum(self, t, shift=oracle.AVGPOOL_SHIFT):
-        return self._put(super().avgpool_sum(t, shift), IntOp('avgpool', src=self.ids[t]))
-
-    def linear(self, t, w, b, *, weight_fl, input_fl, input_signed, label=None):
-        o = super().linear(t, w, b, weight_fl=weight_fl, input_fl=input_fl, input_signed=input_signed)
-        return self._put(o, IntOp('linear', src=self.ids[t], weight=np.asarray(w, np.int32), bias=np.asarray(b, np.int32),
-                                  shift=self.v[t][1] - input_fl, signed=input_signed, key='fc'))
-
-
 def stage_int_graph():
     """The stage as an IntGraph, op for op what shufflenet_stage records.  Returns (IntGraph, reference graph, output id)."""
-    return graph_cases.record_int_graph(Recorder, stage_input(), STAGE['x_fl'], lambda g, x0: shufflenet_stage(g, x0)[0])
+    return record_int_graph(stage_input(), STAGE['x_fl'], lambda g, x0: shufflenet_stage(g, x0)[0])
+
+
+graph_cases.bind_cases(sys.modules[__name__])      # build_graph, reference, plan, int_graph

@@ -2,80 +2,27 @@
 tests/test_concat_plan.py (acceptance, refusals, mode tokens, kernel symbols, forms, launch_info, fused nets, the ONNX round trip; no GPU) and
 tests/test_gpu_concat.py (every case on both legs, bit for bit on the device).  No test functions here.
 
-The reference.  `concat_align(xs, fls)`: the result's fraclen is the largest operand fraclen and operand i contributes what the residual join's
-alignment makes of it next to a zero partner, `oracle.add_align(zeros, x_i, out_fl, fl_i)` — shift left with the int32 wrap, clamp to
-+-(2^31 - 1) — so nothing of that arithmetic is restated here; then `np.concatenate` along C.  `oracle/` stays as it is: graph_cases.graph_forward
-walks an imported ONNX graph, handles `concat` with `concat_align` and hands every other op kind to the oracle's op-level functions.
+The reference.  `ref_ops.concat_align(xs, fls)`: the result's fraclen is the largest operand fraclen and operand i contributes what the residual
+join's alignment makes of it next to a zero partner, `oracle.add_align(zeros, x_i, out_fl, fl_i)` — shift left with the int32 wrap, clamp to
++-(2^31 - 1) — so nothing of that arithmetic is restated here; then `np.concatenate` along C.  `oracle/` stays as it is: refgraph.graph_forward
+walks an imported ONNX graph with the same function.
 
 Unless a builder says otherwise a case is  input (8 channels, 0 .. 255, fraclen 8) -> K 1x1 producer convs that read it as it is, couts C_i, weight
 fraclens chosen to give the stated output fraclens -> concat -> readers: one 32-output 1x1 conv per (input_fl, signed), summed (as dil_cases).
 
 The expected mode token and the ALIGNED flag of the kernel symbol of every case are WRITTEN BY HAND (the rule: DESIGN.md 4.5i); nothing here asks
 the planner for them."""
-import functools
+import sys
 
 import numpy as np
 
-import dil_cases
 import graph_cases
 from dil_cases import FUSE_ALL  # noqa: F401  (the tests take it from here)
 from f8net_amd import synth
-from graph_cases import graph_forward, launch_lines  # noqa: F401  (the walker of an imported graph: the tests take it from here)
+from graph_cases import launch_lines
 from ir_cases import _b, _w
-from oracle import oracle
 
 X_FL = 8
-
-
-def concat_align(xs, fls):
-    """[(N, C_i, H, W) int32], [fraclen_i] -> (concatenation at the largest fraclen, that fraclen)."""
-    fl = max(fls)
-    parts = []
-    for x, f in zip(xs, fls):
-        y, got = oracle.add_align(np.zeros_like(x), x, fl, f)
-        assert got == fl
-        parts.append(y)
-    return np.concatenate(parts, axis=1), fl
-
-
-class _Graph(dil_cases._Graph):
-    """ir_cases._Graph (through dil_cases: `dilation=`, record=False) with concat and the two pools."""
-
-    def conv(self, t, w, b, *, dilation=1, pad, stride=1, **kw):
-        """A 3x3 at dilation d, pad d, stride 1 on a map of at most m + 1 pixels a side, m < d: the taps further than m from the centre only ever
-        meet padding, so the stuffed (2d + 1)-square kernel cropped to its central (2m + 1) square, at pad m, is the same conv (ASPP's d = 18 on a
-        6 x 6 map: 11 x 11 taps instead of 37 x 37 for the reference to walk)."""
-        x, fl = self.v[t]
-        d, m = dilation, max(x.shape[2], x.shape[3]) - 1
-        if not (d > 1 and w.shape[2] == 3 and pad == d and stride == 1 and m < d and kw['groups'] == 1 and kw.get('quant_input', True)):
-            return super().conv(t, w, b, dilation=dilation, pad=pad, stride=stride, **kw)
-        o = self._id(lambda: self.net.conv(t, w, b, stride=1, pad=pad, groups=1, weight_fl=kw['weight_fl'], input_fl=kw['input_fl'],
-                                           input_signed=kw['input_signed'], quant_input=True, relu=kw['relu'], dilation=d))
-        xq = oracle.requant(x, kw['input_fl'], fl, kw['input_signed'])
-        y = oracle.conv2d(xq, np.ascontiguousarray(dil_cases.stuffed(w, d)[:, :, d - m:d + m + 1, d - m:d + m + 1]), b, 1, m, 1)
-        self.raw[o] = y
-        self.v[o] = (oracle.relu(y) if kw['relu'] else y, kw['input_fl'] + kw['weight_fl'])
-        return o
-
-    def concat(self, ts, label=None):
-        o = self._id(lambda: self.net.concat(ts, label=label))
-        self.v[o] = concat_align([self.v[t][0] for t in ts], [self.v[t][1] for t in ts])
-        return o
-
-    def maxpool(self, t, k, stride, pad):
-        o = self._id(lambda: self.net.maxpool(t, k, stride, pad))
-        self.v[o] = (oracle.maxpool(self.v[t][0], k, stride, pad), self.v[t][1])
-        return o
-
-    def avgpool_sum(self, t, shift=oracle.AVGPOOL_SHIFT):
-        o = self._id(lambda: self.net.avgpool_sum(t, shift))
-        y = oracle.avgpool_sum(self.v[t][0])
-        self.v[o] = (y.reshape(y.shape[0], y.shape[1], 1, 1), self.v[t][1] + shift)
-        return o
-
-    def output(self, t, as_float=False):
-        if self.record:
-            self.net.output(t, as_float=as_float)
 
 
 def producer(g, t, k, cout, n, *, w_fl, relu, in_fl=X_FL, in_signed=False, quant_input=False, kernel=1, seed=0, dilation=1):
@@ -271,28 +218,6 @@ def make_input(name, n=None):
     return synth.rand_uniform_int(5, f'catx{name}', shape, 0, 255).astype(np.int32)
 
 
-def build_graph(name, x, record=True):
-    """Returns (graph, output ids, concat ids)."""
-    c = CASES[name]
-    g = _Graph(x, c['x_fl'], record=record)
-    outs, cats = c['build'](g, next(iter(g.v)), c)
-    return g, outs, cats
-
-
-@functools.lru_cache(maxsize=None)
-def reference(name):
-    """(graph, output ids, concat ids) of the case over N + 1 images, evaluated on the reference alone, once; nothing may write into its arrays."""
-    return build_graph(name, make_input(name, CASES[name]['N'] + 1), record=False)
-
-
-def plan(name, x, max_batch=None, **opts):
-    g, outs, cats = build_graph(name, x)
-    for k, v in opts.items():
-        g.net.set_option(k, v)
-    g.net.finalize(max_batch or x.shape[0])
-    return g, outs, cats
-
-
 def concat_lines(net):
     """[(launch index, plan token 'concat_i8:' / 'concat_i32:', kernel symbol)] of the handle's concat launches, in launch order."""
     return launch_lines(net, 'concat_')
@@ -302,11 +227,4 @@ def symbol(mode, aligned):
     return 'f8::concat_i32_kernel' if mode == I32 else f'f8::concat_i8_kernel<{"true" if aligned else "false"}>'
 
 
-class Recorder(graph_cases.Recorder, _Graph):
-    pass
-
-
-def int_graph(name):
-    """The case as an IntGraph, op for op what build_graph records (plain-conv / add / concat / maxpool cases whose first output is the only one)."""
-    c = CASES[name]
-    return graph_cases.record_int_graph(Recorder, make_input(name), c['x_fl'], lambda g, x0: c['build'](g, x0, c)[0][0])
+graph_cases.bind_cases(sys.modules[__name__])      # build_graph, reference, plan, int_graph

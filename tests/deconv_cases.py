@@ -2,7 +2,7 @@
 tests/test_deconv_plan.py (acceptance, refusals, tokens, kernel symbols, forms, launch_info, the tap-cut comparison, ONNX / IntGraph round trips, tap
 liveness; no GPU) and tests/test_gpu_deconv.py (every case bit for bit on the device).  No test functions here.
 
-The reference is numpy on int64 in the SCATTER form, wrapped to int32 at the end: every input pixel (ih, iw) adds x[ci] * w[ci, co, kh, kw] at
+The reference (ref_ops.deconv_exact / deconv_ref) is numpy on int64 in the SCATTER form, wrapped to int32 at the end: every input pixel (ih, iw) adds x[ci] * w[ci, co, kh, kw] at
 (s ih + kh, s iw + kw) of the full (H - 1) s + k + output_padding square, of which the output is the window [pad, pad + P).  It is pinned two ways
 (tests/test_deconv_plan.py): to torch.nn.functional.conv_transpose2d in float64 with exact equality (`pin_to_torch`), and to `oracle.conv2d` over the
 zero-stuffed input with flipped, in / out-swapped weights at pad' = k - 1 - pad (`pin_to_oracle`).
@@ -13,18 +13,17 @@ fraclen 13 [ReLU] -> the transposed conv, which requantises them to unsigned fra
 (cin channels, 0 .. 255 at fraclen 8) as it is, no requantisation.
 
 The expected plan token, kernel symbol and the forms the launch writes are WRITTEN BY HAND; nothing here asks the planner for them."""
-import functools
+import sys
 
 import numpy as np
 
 import graph_cases
-import upsample_cases as uc
 from concat_cases import FUSE_ALL, X_FL, producer, readers  # noqa: F401  (the tests take them from here)
 from f8net_amd import synth
-from f8net_amd.onnx_import import IntOp
-from graph_cases import graph_forward, launch_lines  # noqa: F401  (the walker of an imported graph: the tests take it from here)
+from graph_cases import launch_lines
 from ir_cases import _b, _w
 from oracle import oracle
+from ref_ops import deconv_exact, deconv_ref
 
 
 def symbol(cout):
@@ -32,32 +31,8 @@ def symbol(cout):
     return 'f8::deconv_kernel<2>' if cout > 32 else 'f8::deconv_kernel<1>'
 
 
-wrap32 = uc.wrap32
-
-
 def out_size(n, k, s, pad, op):
     return (n - 1) * s - 2 * pad + k + op
-
-
-def deconv_exact(x, w, b, s, pad, op):
-    """(N, cin, H, W) integers, w [cin, cout, k, k], b [cout] or None -> int64 (N, cout, P, Q), not wrapped.  The scatter form."""
-    x, w = np.asarray(x, np.int64), np.asarray(w, np.int64)
-    N, cin, H, W = x.shape
-    cout, k = w.shape[1], w.shape[2]
-    full = np.zeros((N, cout, (H - 1) * s + k + op, (W - 1) * s + k + op), np.int64)
-    for kh in range(k):
-        for kw in range(k):
-            full[:, :, kh:kh + (H - 1) * s + 1:s, kw:kw + (W - 1) * s + 1:s] += np.einsum('nchw,cd->ndhw', x, w[:, :, kh, kw])
-    P, Q = out_size(H, k, s, pad, op), out_size(W, k, s, pad, op)
-    y = full[:, :, pad:pad + P, pad:pad + Q]
-    assert y.shape[2:] == (P, Q)
-    if b is not None:
-        y = y + np.asarray(b, np.int64).reshape(1, -1, 1, 1)
-    return y
-
-
-def deconv_ref(x, w, b, s, pad, op):
-    return wrap32(deconv_exact(x, w, b, s, pad, op))
 
 
 def stuffed_input(x, s, op):
@@ -87,24 +62,6 @@ def pin_to_oracle(x, w, b, s, pad, op):
     k = w.shape[2]
     want = oracle.conv2d(stuffed_input(np.asarray(x, np.int32), s, op), conv_weights(w).astype(np.int32), b, 1, k - 1 - pad, 1)
     np.testing.assert_array_equal(deconv_ref(x, w, b, s, pad, op), want)
-
-
-class _Graph(uc._Graph):
-    """upsample_cases._Graph with conv_transpose.  w_eval: other weights for the reference only (the liveness check zeroes one tap)."""
-
-    def conv_transpose(self, t, w, b, *, stride, pad, output_padding=0, weight_fl, input_fl, input_signed, relu, quant_input=True, label=None, w_eval=None):
-        o = self._id(lambda: self.net.conv_transpose(t, w, b, stride=stride, pad=pad, output_padding=output_padding, weight_fl=weight_fl, input_fl=input_fl,
-                                                     input_signed=input_signed, quant_input=quant_input, relu=relu, label=label))
-        x, fl = self.v[t]
-        if quant_input:
-            xq = oracle.requant(x, input_fl, fl, input_signed)
-        else:
-            assert fl == input_fl and x.min() >= (-127 if input_signed else 0) and x.max() <= (127 if input_signed else 255)
-            xq = x
-        y = deconv_ref(xq, w if w_eval is None else w_eval, b, stride, pad, output_padding)
-        self.raw[o] = y
-        self.v[o] = (oracle.relu(y) if relu else y, input_fl + weight_fl)
-        return o
 
 
 # ---- weights.  Accumulators around 2^6 x 100, which a reader's shift of 6 (fraclen 10 -> 4) turns into 8 bits
@@ -241,28 +198,6 @@ def make_input(name, n=None):
     return synth.rand_uniform_int(5, f'dcx{name}', (n or c['N'], input_channels(c)) + input_hw(c), 0, 255).astype(np.int32)
 
 
-def build_graph(name, x, record=True, w_eval=None):
-    """Returns (graph, output ids, transposed conv ids)."""
-    c = CASES[name]
-    g = _Graph(x, X_FL, record=record)
-    outs, ups = c['build'](g, next(iter(g.v)), c, w_eval)
-    return g, outs, ups
-
-
-@functools.lru_cache(maxsize=None)
-def reference(name):
-    """(graph, output ids, transposed conv ids) of the case over N images, evaluated on the reference alone, once; nothing may write into its arrays."""
-    return build_graph(name, make_input(name), record=False)
-
-
-def plan(name, x, max_batch=None, **opts):
-    g, outs, ups = build_graph(name, x)
-    for k, v in dict(CASES[name]['opts'], **opts).items():
-        g.net.set_option(k, v)
-    g.net.finalize(max_batch or x.shape[0])
-    return g, outs, ups
-
-
 def deconv_lines(net, label='up'):
     """[(launch index, plan token, kernel symbol)] of the launches that write the tensor labelled `label`, in launch order."""
     return [ln for ln in launch_lines(net, label=label) if ln[1] not in ('output:', 'tap:', 'requant:')]
@@ -278,16 +213,5 @@ def check_lines(c, lines, describe=''):
         assert tok.startswith(c['tok']) and sym.startswith('f8::conv') and 'deconv' not in tok + sym, describe
 
 
-class Recorder(graph_cases.Recorder, _Graph):
-    def conv_transpose(self, t, w, b, *, stride, pad, output_padding=0, weight_fl, input_fl, input_signed, relu, quant_input=True, label=None, w_eval=None):
-        o = super().conv_transpose(t, w, b, stride=stride, pad=pad, output_padding=output_padding, weight_fl=weight_fl, input_fl=input_fl,
-                                   input_signed=input_signed, relu=relu, quant_input=quant_input)
-        return self._put(o, IntOp('deconv', src=self.ids[t], weight=np.asarray(w, np.int32), bias=np.asarray(b, np.int32), stride=stride, pad=pad,
-                                  kernel=w.shape[2], shift=(self.v[t][1] - input_fl) if quant_input else None, signed=input_signed, relu=relu,
-                                  key=label or f'layer{len(self.ig.ops)}', output_padding=output_padding))
-
-
-def int_graph(name):
-    """The case as an IntGraph, op for op what build_graph records (cases whose first output is the only one)."""
-    c = CASES[name]
-    return graph_cases.record_int_graph(Recorder, make_input(name), X_FL, lambda g, x0: c['build'](g, x0, c, None)[0][0])
+# (the reference runs over N images and the handle is planned for N: no spare image)
+graph_cases.bind_cases(sys.modules[__name__], spare_image=False)      # build_graph(..., w_eval=None), reference, plan, int_graph

@@ -3,7 +3,8 @@
 (every case bit for bit on the device).  No test functions here.
 
 The reference.  `oracle.conv2d` has no dilation and stays as it is, but it takes any kernel size: a dilated K x K conv equals the plain
-(d (K - 1) + 1)-square conv whose weights are zero except at [::d, ::d], with the same stride, pad and groups — `stuffed(w, d)`.  That is also what a
+(d (K - 1) + 1)-square conv whose weights are zero except at [::d, ::d], with the same stride, pad and groups — `ref_ops.stuffed(w, d)`, which
+RefGraph.conv and refgraph.graph_forward evaluate a dilated conv with.  That is also what a
 user of the library could do before this entry point existed.  test_dilated_plan.py pins the stuffed integer conv to
 torch.nn.functional.conv2d(float64, dilation=d), which is exact here (|acc| << 2^53).
 
@@ -19,75 +20,19 @@ import functools
 
 import numpy as np
 
-import gconv_cases
-import ir_cases
 from f8net_amd import synth
 from ir_cases import PIPELINED_CASE as _IR_PIPELINED
 from ir_cases import _b, _w
-from oracle import oracle
+from ref_ops import stuffed
+from refgraph import RefGraph
 
 # every fusing pass of the planner switched on (the options that are off by default among them)
 FUSE_ALL = dict(fuse_blocks=1, fuse_ds=1, fuse_opener=1, fuse_chain=1, fuse_chain7=1, fuse_tail=1, fuse_p12=1, fuse_bchain=2, fuse_bchain7=2, fuse_ir=2,
                 fuse_irchain=1, fuse_irk=1, fuse_dws=1, fuse_dws7=1, fuse_head2=1, fuse_head_dws=1, fuse_pool=1, fuse_dual=1, fuse_stem=1)
 
 
-def stuffed(w, d):
-    """[cout, cin / groups, K, K] -> the zero-stuffed [cout, cin / groups, d (K - 1) + 1, ...] kernel of the same conv at dilation 1."""
-    w = np.asarray(w)
-    if d == 1 or w.shape[2] == 1:
-        return w
-    K = w.shape[2]
-    E = d * (K - 1) + 1
-    s = np.zeros(w.shape[:2] + (E, E), w.dtype)
-    s[:, :, ::d, ::d] = w
-    return s
-
-
 def out_size(n, k, stride, pad, d):
     return (n + 2 * pad - d * (k - 1) - 1) // stride + 1
-
-
-class _Graph(ir_cases._Graph):
-    """ir_cases._Graph whose conv takes `dilation=` and evaluates with the stuffed weights (grouped convs: per group, gconv_cases.grouped_conv2d).
-    record=False: only the reference is evaluated, no handle is touched (tensor ids are counted here)."""
-
-    def __init__(self, x, x_fl, grouped=None, record=True):
-        self.record = record
-        if record:
-            super().__init__(x, x_fl)
-            if grouped is not None:
-                self.net.set_option('grouped', grouped)
-        else:
-            self.net, self.v, self.taps, self.raw, self._n = None, {0: (x, x_fl)}, [], {}, 0
-
-    def _id(self, make):
-        if self.record:
-            return make()
-        self._n += 1
-        return self._n
-
-    def conv(self, t, w, b, *, stride=1, pad, groups, weight_fl, input_fl, input_signed, relu, label=None, quant_input=True, dilation=1, w_eval=None):
-        """w_eval: other weights for the reference only (the liveness checks zero the outer taps)."""
-        o = self._id(lambda: self.net.conv(t, w, b, stride=stride, pad=pad, groups=groups, weight_fl=weight_fl, input_fl=input_fl,
-                                           input_signed=input_signed, quant_input=quant_input, relu=relu, dilation=dilation))
-        x, fl = self.v[t]
-        if quant_input:
-            xq = oracle.requant(x, input_fl, fl, input_signed)
-        else:
-            assert fl == input_fl and x.min() >= (-127 if input_signed else 0) and x.max() <= (127 if input_signed else 255)
-            xq = x
-        if label:
-            self.taps.append((label, xq, input_signed))
-        y = gconv_cases.grouped_conv2d(xq, stuffed(w if w_eval is None else w_eval, dilation), b, stride, pad, groups)
-        self.raw[o] = y
-        self.v[o] = (oracle.relu(y) if relu else y, input_fl + weight_fl)
-        return o
-
-    def add(self, a, b, relu=False):
-        o = self._id(lambda: self.net.add(a, b, relu=relu))
-        y, fl = oracle.add_align(self.v[a][0], self.v[b][0], self.v[a][1], self.v[b][1])
-        self.v[o] = (oracle.relu(y) if relu else y, fl)
-        return o
 
 
 # A case.  kind: 'plain' (groups 1), 'dw' (groups = C = cout) or 'grouped' (C in groups of cg).  Geometry of the dilated 3x3: H x W map, dilation d,
@@ -129,7 +74,7 @@ def biases(c, seed=40):
 def build_graph(case, x, record=True, centre=False):
     """Returns (graph, output tensor, [tensor ids of the dilated convs]).  centre: the reference runs with every tap but the centre zeroed."""
     c = case
-    g = _Graph(x, c['in_fl'], grouped=c['opts'].get('grouped', 1) if c['kind'] == 'grouped' else None, record=record)
+    g = RefGraph(x, c['in_fl'], grouped=c['opts'].get('grouped', 1) if c['kind'] == 'grouped' else None, record=record)
     t = next(iter(g.v))
     G = groups_of(c)
     w = weights(c)
@@ -356,14 +301,3 @@ def stuffed_twin(spec, params):
             params[c.key + '.weight'] = stuffed(np.asarray(params[c.key + '.weight']), c.dilation)
             c.k, c.dilation = c.dilation * (c.k - 1) + 1, 1
     return spec, params
-
-
-def stuffed_graph(ig):
-    """An IntGraph's twin for oracle.graph_forward: dilated conv ops stuffed the same way."""
-    import copy
-    ig = copy.deepcopy(ig)
-    for o in ig.ops:
-        if o.kind == 'conv' and o.dilation > 1:
-            o.weight = stuffed(o.weight, o.dilation)
-            o.kernel, o.dilation = o.dilation * (o.kernel - 1) + 1, 1
-    return ig

@@ -17,7 +17,8 @@ import numpy as np
 
 from f8net_amd import synth
 from ir_cases import PIPELINED_CASE as _IR_PIPELINED
-from ir_cases import _Graph, _b, _w
+from ir_cases import _b, _w
+from refgraph import RefGraph
 
 DW_SW = 28                                              # f8_dwmma.hip: output columns per strip, rows per band (8 below 4096 wave items)
 DW_BAND = 14
@@ -55,7 +56,7 @@ def out_hw(case):
 def build_graph(case, x):
     """Returns (graph, output tensor, [depthwise tensor ids])."""
     c = case
-    g = _Graph(x, c['in_fl'])
+    g = RefGraph(x, c['in_fl'])
     t = next(iter(g.v))
     C = c['C']
     bd = _b(40, C, c['b_sig'], c['b_mean'])

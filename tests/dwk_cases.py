@@ -15,7 +15,8 @@ import numpy as np
 
 from f8net_amd import synth
 from ir_cases import PIPELINED_CASE as _IR_PIPELINED
-from ir_cases import _Graph, _b, _w
+from ir_cases import _b, _w
+from refgraph import RefGraph
 
 PIX = 4                                                 # f8_dwk.hip DWK_PIX: output pixels per thread of the dot4 kernel
 
@@ -56,7 +57,7 @@ def _dw_weight(seed, C, K, sig):
 def build_graph(case, x):
     """Returns (graph, output tensor, [depthwise tensor ids])."""
     c = case
-    g = _Graph(x, c['in_fl'])
+    g = RefGraph(x, c['in_fl'])
     t = next(iter(g.v))
     C, K = c['C'], c['K']
     bd = _b(40, C, c['b_sig'], c['b_mean'])

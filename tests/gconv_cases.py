@@ -3,8 +3,9 @@
 test functions here.
 
 The reference.  `oracle.conv2d` refuses these groups (it is the reference's depthwise / plain conv) and stays as it is.  Wrapping int32 arithmetic
-is order-free, so a grouped conv is the oracle applied per group and concatenated along the channels: `grouped_conv2d`.  `grouped_oracle()` points
-`oracle.oracle.conv2d` at it for the time of a `graph_forward` / `net_forward`; `_Graph.conv` of this module does the same per conv.
+is order-free, so a grouped conv is the oracle applied per group and concatenated along the channels: `ref_ops.grouped_conv2d`, which RefGraph.conv
+evaluates every conv with.  `grouped_oracle()` points `oracle.oracle.conv2d` at it for the time of an `oracle.graph_forward` / `net_forward`: the
+whole-net walkers are the oracle's own and look the name up at call time.
 
 Every op-level graph is  input -> grouped K x K (the conv under test; it reads the net input as it is, quant_input = False) -> output, where the
 output is the grouped conv's int32 result itself (readers=None) or the sum of one 32-output 1x1 reader per (fraclen, signed) — plus the int32
@@ -19,49 +20,23 @@ import contextlib
 
 import numpy as np
 
-import ir_cases
 from f8net_amd import synth
 from ir_cases import PIPELINED_CASE as _IR_PIPELINED
 from ir_cases import _b, _w
 from oracle import oracle
-
-_oracle_conv2d = oracle.conv2d
-
-
-def grouped_conv2d(x, w, b, stride, pad, groups=1):
-    """oracle.conv2d for any groups: 1 < groups < cin is the oracle per group, concatenated along the channels."""
-    cin = x.shape[1]
-    if groups == 1 or groups == cin:
-        return _oracle_conv2d(x, w, b, stride, pad, groups)
-    cg, kg = cin // groups, w.shape[0] // groups
-    assert cg * groups == cin and kg * groups == w.shape[0] and w.shape[1] == cg
-    x, w = np.asarray(x), np.asarray(w)
-    return np.concatenate([_oracle_conv2d(np.ascontiguousarray(x[:, g * cg:(g + 1) * cg]), np.ascontiguousarray(w[g * kg:(g + 1) * kg]),
-                                          None if b is None else np.ascontiguousarray(np.asarray(b)[g * kg:(g + 1) * kg]), stride, pad, 1)
-                           for g in range(groups)], axis=1)
+from ref_ops import grouped_conv2d
+from refgraph import RefGraph
 
 
 @contextlib.contextmanager
 def grouped_oracle():
     """`oracle.oracle.conv2d` = grouped_conv2d while the block runs (graph_forward / net_forward look the name up at call time)."""
+    plain = oracle.conv2d
     oracle.conv2d = grouped_conv2d
     try:
         yield
     finally:
-        oracle.conv2d = _oracle_conv2d
-
-
-class _Graph(ir_cases._Graph):
-    """ir_cases._Graph on a handle that accepts grouped convs (option grouped = leg), evaluated with grouped_conv2d."""
-
-    def __init__(self, x, x_fl, grouped=1):
-        super().__init__(x, x_fl)
-        if grouped is not None:
-            self.net.set_option('grouped', grouped)
-
-    def conv(self, *a, **kw):
-        with grouped_oracle():
-            return super().conv(*a, **kw)
+        oracle.conv2d = plain
 
 
 def kernel(stride):
@@ -108,7 +83,7 @@ def biases(case, seed=40):
 def build_graph(case, x, leg=1):
     """Returns (graph, output tensor, [grouped conv tensor ids])."""
     c = case
-    g = _Graph(x, c['in_fl'], leg)
+    g = RefGraph(x, c['in_fl'], grouped=leg)
     t = next(iter(g.v))
     C, G = c['C'], c['C'] // c['cg']
     d = g.conv(t, weights(c), biases(c), stride=c['stride'], pad=c['pad'], groups=G, weight_fl=c['w_fl'], input_fl=c['in_fl'],

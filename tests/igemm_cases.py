@@ -21,9 +21,8 @@ On an 8 x 8 map that is: max_batch 3 (the three images of a run) -> 128x32 (cout
 import numpy as np
 
 from f8net_amd import synth
-from gconv_cases import grouped_oracle
-from ir_cases import _Graph, _b, _w
-from oracle import oracle
+from ir_cases import _b, _w
+from refgraph import RefGraph
 
 BASE_OPTS = dict(wstat=0, wreg=0, s2wreg=0, patch3x3=0, fuse_blocks=0, fuse_pool=0)
 SHALLOW, DEEP = 1 << 20, 1                                   # deep_nk: no K loop is long enough / every one is
@@ -123,7 +122,7 @@ def _lg(v):
 def build_graph(case, x):
     """Returns (graph, [output tensors], tensor id of the conv under test, tensor id of what leaves the launch (the join's result))."""
     c = case
-    g = _Graph(x, c['x_fl'])
+    g = RefGraph(x, c['x_fl'])
     for key, v in dict(BASE_OPTS, **c['opts']).items():           # (before the ops: `grouped` decides what the builder accepts)
         g.net.set_option(key, v)
     t0 = next(iter(g.v))
@@ -194,9 +193,8 @@ def build_graph(case, x):
     host_sc = bool(c['dual']) and c['dual'].get('host') == 'shortcut'
     if (c['join'] == 'other' or c['dual']) and not host_sc:
         other = shortcut()
-    with grouped_oracle():                                        # (oracle.conv2d per group where 1 < groups < cin)
-        y = g.conv(src, w, b, stride=c['stride'], pad=c['pad'], groups=G, weight_fl=c['w_fl'], input_fl=c['in_fl'], input_signed=c['in_signed'],
-                   relu=c['relu'], quant_input=not reads_input, label='under_test' if not reads_input else None)
+    y = g.conv(src, w, b, stride=c['stride'], pad=c['pad'], groups=G, weight_fl=c['w_fl'], input_fl=c['in_fl'], input_signed=c['in_signed'],
+               relu=c['relu'], quant_input=not reads_input, label='under_test' if not reads_input else None)
     g.net._L.f8_net_set_label(g.net._h, y, b'ut')
     if host_sc:
         other = shortcut()
@@ -208,17 +206,12 @@ def build_graph(case, x):
     if c['pool']:
         if c['pool'][0] == 'max':
             pk, ps, pp = c['pool'][1:4]
-            o = g.net.maxpool(t, pk, ps, pp)
-            g.v[o] = (oracle.maxpool(g.v[t][0], pk, ps, pp), g.v[t][1])
+            o = g.maxpool(t, pk, ps, pp)
         else:
-            o = g.net.avgpool_sum(t, oracle.AVGPOOL_SHIFT)
-            v = oracle.avgpool_sum(g.v[t][0])
-            g.v[o] = (v.reshape(v.shape + (1, 1)), g.v[t][1] + oracle.AVGPOOL_SHIFT)
+            o = g.avgpool_sum(t)
         pooled = o
         if c['pool'][-1] == 'twice':                              # the sum of two max-pools: a join no conv epilogue can carry
-            o2 = g.net.maxpool(t, pk, ps, pp)
-            g.v[o2] = g.v[o]
-            pooled = g.add(o, o2)
+            pooled = g.add(o, g.maxpool(t, pk, ps, pp))
     else:
         pooled = t
     outs = []

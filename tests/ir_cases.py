@@ -10,7 +10,7 @@ ir_nw of f8_ir.hip; nothing here asks the planner for them."""
 import numpy as np
 
 from f8net_amd import synth
-from oracle import oracle
+from refgraph import RefGraph
 
 INT32_MIN_CLAMP = -(2 ** 31 - 1)
 
@@ -21,40 +21,6 @@ def _w(seed, shape, sig):
 
 def _b(seed, n, sig, mean=0.0):
     return np.clip(synth.rand_normal_int(seed, f'b{n}', (n,), sig) + int(mean), -2 ** 30, 2 ** 30).astype(np.int32)
-
-
-class _Graph:
-    """Records each op into an F8Net and evaluates it with the oracle's op-level functions (value, fraclen) at the same time.  `taps` keeps
-    what the liveness checks look at: (label, the int8 tensor a conv reads, signed) and `raw` the conv results before their ReLU."""
-
-    def __init__(self, x, x_fl):
-        from f8net_amd.net import F8Net
-        self.net = F8Net()
-        self.v = {self.net.input(x.shape[1], x.shape[2], x.shape[3], x_fl): (x, x_fl)}
-        self.taps = []
-        self.raw = {}
-
-    def conv(self, t, w, b, *, stride=1, pad, groups, weight_fl, input_fl, input_signed, relu, label=None, quant_input=True):
-        o = self.net.conv(t, w, b, stride=stride, pad=pad, groups=groups, weight_fl=weight_fl, input_fl=input_fl, input_signed=input_signed,
-                          quant_input=quant_input, relu=relu)
-        x, fl = self.v[t]
-        if quant_input:
-            xq = oracle.requant(x, input_fl, fl, input_signed)
-        else:                                                    # the conv reads its input as it is: already 8 bits in its own format
-            assert fl == input_fl and x.min() >= (-127 if input_signed else 0) and x.max() <= (127 if input_signed else 255)
-            xq = x
-        if label:
-            self.taps.append((label, xq, input_signed))
-        y = oracle.conv2d(xq, w, b, stride, pad, groups)
-        self.raw[o] = y
-        self.v[o] = (oracle.relu(y) if relu else y, input_fl + weight_fl)
-        return o
-
-    def add(self, a, b, relu=False):
-        o = self.net.add(a, b, relu=relu)
-        y, fl = oracle.add_align(self.v[a][0], self.v[b][0], self.v[a][1], self.v[b][1])
-        self.v[o] = (oracle.relu(y) if relu else y, fl)
-        return o
 
 
 # A block.  Formats: in_fl / in_signed (what the expand conv reads), w_fl (expand weights), dw_in_fl / dw_signed, dw_w_fl, pw_in_fl / pw_signed,
@@ -81,7 +47,7 @@ X_FL = 5
 def build_graph(case, x):
     """Returns (graph, output tensor, per-block tensor ids [(expand, depthwise, project, block output)])."""
     blocks = case['blocks']
-    g = _Graph(x, X_FL)
+    g = RefGraph(x, X_FL)
     t = next(iter(g.v))
     c0 = blocks[0]['cin']
     # the pre conv's result is requantised by a shift of 7 whatever the first block's input format is

@@ -17,7 +17,8 @@ import numpy as np
 
 from f8net_amd import synth
 from ir_cases import PIPELINED_CASE as _IR_PIPELINED
-from ir_cases import X_FL, _blk, _Graph, _b, _w
+from ir_cases import X_FL, _blk, _b, _w
+from refgraph import RefGraph
 
 INT32_MIN_CLAMP = -(2 ** 31 - 1)
 
@@ -29,7 +30,7 @@ def _kblk(K, cin, cout, E, stride=1, **kw):
 def build_graph(case, x):
     """Returns (graph, output tensor, per-block tensor ids [(expand, depthwise, project, block output)])."""
     blocks = case['blocks']
-    g = _Graph(x, X_FL)
+    g = RefGraph(x, X_FL)
     t = next(iter(g.v))
     c0 = blocks[0]['cin']
     bpre = _b(2, c0, 300.0)

@@ -3,7 +3,7 @@
 symbols, launch_info, where the ops cut fused launches, ONNX, the host code under the sanitizers; no GPU) and tests/test_gpu_mul.py (every case bit
 for bit on the device, on the default plan, with every fusing pass on and with fuse_hgate = 0).  No test functions here.
 
-The references, in numpy int64 on the int32 tensors the graph builder carries (concat_cases._Graph evaluates every other op with the oracle):
+The references (tests/ref_ops.py), in numpy int64 on the int32 tensors the reference graph carries:
     mul_ref       oracle.requant(a, a_fl, fl_a, a_signed) * oracle.requant(b, b_fl, fl_b, b_signed), b broadcast over H x W where it is [C, 1, 1],
                   max(., 0) where relu is set, wrapped to int32 (|product| <= 255 * 255: the wrap never acts)
     hard_gate_ref np.clip(x, -3 * 2^fl, 3 * 2^fl) + 3 * 2^fl
@@ -15,69 +15,15 @@ N = 2; C in {8, 20, 48, 64}: the 4-byte instance with its end mask, the 16-byte 
 
 The expected plan tokens and kernel symbols of every case — `exp`: the default plan (also with every fusing pass on), `nofuse`: fuse_hgate = 0 — are
 WRITTEN BY HAND in launch order, the requant: steps of the op's result among them (the rule: DESIGN.md 4.5n); nothing here asks the planner for them."""
-import functools
+import sys
 
 import numpy as np
 
-import concat_cases as cc
 import graph_cases
 from concat_cases import FUSE_ALL, X_FL, producer, readers  # noqa: F401  (the tests take FUSE_ALL from here)
 from f8net_amd import synth
 from ir_cases import _b, _w
-from oracle import oracle
-
-
-def _wrap32(y):
-    return ((np.asarray(y, np.int64) + 2 ** 31) % 2 ** 32 - 2 ** 31).astype(np.int32)
-
-
-def mul_operands(a, fl_a, b, fl_b, a_fl, a_signed, b_fl, b_signed):
-    """(A, B): the two operands in the mul's formats, int64."""
-    return (oracle.requant(a, a_fl, fl_a, a_signed).astype(np.int64), oracle.requant(b, b_fl, fl_b, b_signed).astype(np.int64))
-
-
-def mul_ref(a, fl_a, b, fl_b, *, a_fl, a_signed, b_fl, b_signed=False, relu=False):
-    """-> (product int32 in a's shape, fraclen a_fl + b_fl); b has a's shape or is [N, C, 1, 1]."""
-    A, B = mul_operands(a, fl_a, b, fl_b, a_fl, a_signed, b_fl, b_signed)
-    y = A * B                                                     # (numpy broadcasts [N, C, 1, 1] over H x W)
-    if relu:
-        y = np.maximum(y, 0)
-    return _wrap32(y), a_fl + b_fl
-
-
-def hard_gate_ref(x, fl):
-    lim = 3 * 2 ** fl
-    return _wrap32(np.clip(np.asarray(x, np.int64), -lim, lim) + lim)
-
-
-class _Graph(cc._Graph):
-    """concat_cases._Graph with mul, hard_gate, hard_swish and the classifier.  `ops[o]` keeps (A, B) of every mul for the case builders' checks."""
-
-    def __init__(self, x, x_fl, record=True):
-        super().__init__(x, x_fl, record=record)
-        self.ops = {}
-
-    def mul(self, a, b, *, a_fl, a_signed, b_fl, b_signed=False, relu=False, label=None):
-        o = self._id(lambda: self.net.mul(a, b, a_fl=a_fl, a_signed=a_signed, b_fl=b_fl, b_signed=b_signed, relu=relu, label=label))
-        (xa, fa), (xb, fb) = self.v[a], self.v[b]
-        self.ops[o] = mul_operands(xa, fa, xb, fb, a_fl, a_signed, b_fl, b_signed)
-        self.v[o] = mul_ref(xa, fa, xb, fb, a_fl=a_fl, a_signed=a_signed, b_fl=b_fl, b_signed=b_signed, relu=relu)
-        return o
-
-    def hard_gate(self, t, label=None):
-        o = self._id(lambda: self.net.hard_gate(t, label=label))
-        self.v[o] = (hard_gate_ref(self.v[t][0], self.v[t][1]), self.v[t][1])
-        return o
-
-    def hard_swish(self, t, *, x_fl, x_signed, g_fl, label=None):
-        return self.mul(t, self.hard_gate(t), a_fl=x_fl, a_signed=x_signed, b_fl=g_fl, b_signed=False, label=label)
-
-    def linear(self, t, w, b, *, weight_fl, input_fl, input_signed, label=None):
-        o = self._id(lambda: self.net.linear(t, w, b, weight_fl=weight_fl, input_fl=input_fl, input_signed=input_signed, quant_input=True, label=label))
-        x, fl = self.v[t]
-        y = oracle.linear(oracle.requant(x.reshape(x.shape[0], -1), input_fl, fl, input_signed), w, b)
-        self.v[o] = (y.reshape(y.shape[0], y.shape[1], 1, 1), input_fl + weight_fl)
-        return o
+from refgraph import record_int_graph
 
 
 # ---- the builders.  Each returns (output tensor ids in output order, [mul / hard-gate tensor ids in launch order])
@@ -246,24 +192,13 @@ def make_input(name, n=None):
     return synth.rand_uniform_int(5, f'mx{name}', shape, 0, 255).astype(np.int32)
 
 
-def build_graph(name, x, record=True):
-    """Returns (graph, output ids, mul / hard-gate tensor ids)."""
-    c = CASES[name]
-    g = _Graph(x, c['x_fl'], record=record)
-    outs, ops = c['build'](g, next(iter(g.v)), c)
-    return g, outs, ops
-
-
 def _has_ties(y, n):
     return n > 0 and bool(np.any((np.asarray(y, np.int64) & ((1 << n) - 1)) == (1 << (n - 1))))
 
 
-@functools.lru_cache(maxsize=None)
-def reference(name):
-    """(graph, output ids, op ids) of the case over N + 1 images, evaluated on the reference alone, once; nothing may write into its arrays.
-    Asserts what the table promises about the DATA: the extreme operand pairs occur, a right-shifting reader meets exact ties, values vary."""
+def _check_data(name, g, outs, ops):
+    """What the table promises about the DATA of reference(name): the extreme operand pairs occur, a right-shifting reader meets exact ties, values vary."""
     c = CASES[name]
-    g, outs, ops = build_graph(name, make_input(name, c['N'] + 1), record=False)
     y, fl = g.v[ops[-1]]
     assert np.unique(y).size > 5, name
     for (A, B) in g.ops.values():
@@ -272,15 +207,9 @@ def reference(name):
     for rfl, _ in c['readers'] or []:
         if fl - rfl > 0 and not c.get('join'):
             assert _has_ties(y, fl - rfl), (name, fl, rfl)
-    return g, outs, ops
 
 
-def plan(name, x, max_batch=None, **opts):
-    g, outs, ops = build_graph(name, x)
-    for k, v in opts.items():
-        g.net.set_option(k, v)
-    g.net.finalize(max_batch or x.shape[0])
-    return g, outs, ops
+graph_cases.bind_cases(sys.modules[__name__], check_data=_check_data)      # build_graph, reference (asserts _check_data), plan, int_graph
 
 
 def lines(net):
@@ -366,32 +295,6 @@ def se_input(n=None):
     return synth.rand_uniform_int(5, 'senet', (n or SE['N'], SE['cin'], SE['H'], SE['W']), 0, 255).astype(np.int32)
 
 
-class Recorder(graph_cases.Recorder, _Graph):
-    def __init__(self, x, fl, ig):
-        graph_cases.Recorder.__init__(self, x, fl, ig)
-        self.ops = {}
-
-    def mul(self, a, b, *, a_fl, a_signed, b_fl, b_signed=False, relu=False, label=None):
-        from f8net_amd.onnx_import import IntOp
-        o = super().mul(a, b, a_fl=a_fl, a_signed=a_signed, b_fl=b_fl, b_signed=b_signed, relu=relu)
-        return self._put(o, IntOp('mul', src=self.ids[a], src2=self.ids[b], shifts=[self.v[a][1] - a_fl, self.v[b][1] - b_fl], signed=a_signed,
-                                  signed2=b_signed, relu=relu))
-
-    def hard_gate(self, t, label=None):
-        from f8net_amd.onnx_import import IntOp
-        return self._put(super().hard_gate(t), IntOp('hgate', src=self.ids[t], shift=self.v[t][1]))
-
-    def avgpool_sum(self, t, shift=oracle.AVGPOOL_SHIFT):
-        from f8net_amd.onnx_import import IntOp
-        return self._put(super().avgpool_sum(t, shift), IntOp('avgpool', src=self.ids[t]))
-
-    def linear(self, t, w, b, *, weight_fl, input_fl, input_signed, label=None):
-        from f8net_amd.onnx_import import IntOp
-        o = super().linear(t, w, b, weight_fl=weight_fl, input_fl=input_fl, input_signed=input_signed)
-        return self._put(o, IntOp('linear', src=self.ids[t], weight=np.asarray(w, np.int32), bias=np.asarray(b, np.int32),
-                                  shift=self.v[t][1] - input_fl, signed=input_signed, key=label or f'fc{len(self.ig.ops)}'))
-
-
 def se_int_graph(seen=None):
     """se_net as an IntGraph, op for op what se_net records.  Returns (IntGraph, reference graph, output id)."""
-    return graph_cases.record_int_graph(Recorder, se_input(), SE['x_fl'], lambda g, x0: se_net(g, x0, seen))
+    return record_int_graph(se_input(), SE['x_fl'], lambda g, x0: se_net(g, x0, seen))

@@ -23,8 +23,9 @@ import numpy as np
 
 from f8net_amd import synth
 from igemm_cases import _sig
-from ir_cases import _Graph, _b, _w
+from ir_cases import _b, _w
 from oracle import oracle
+from refgraph import RefGraph
 
 TOKEN = {'resnet': 'stem7x7s2+maxpool3x3s2:', 'h2': 'head3x3s2+dw3x3+1x1:'}
 KERNEL = {'tile': 'f8::stem_pool_kernel', 'rows': 'f8::stem_rows_kernel', 'h2': 'f8::stem_rows_kernel'}
@@ -34,15 +35,6 @@ RAW_PLAN = {'i32': True, 'f32': True, 'u8': True, 'halo': False, 'nhwc': True, '
 KIND = {'i32': 0, 'f32': 1, 'u8': 2, 'halo': -1, 'nhwc': -1, 'cin1': -1, 'cin4': -1}                             # the template argument the run selects
 MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
 INT32_LIM = 2 ** 31 - 2 ** 24                                    # biases stay this far inside int32: 147 products of 8 bits are below 2^23
-
-
-class Graph(_Graph):
-    """ir_cases._Graph with the max-pool the ResNet form needs."""
-
-    def maxpool(self, t, k=3, stride=2, pad=1):
-        o = self.net.maxpool(t, k, stride, pad)
-        self.v[o] = (oracle.maxpool(self.v[t][0], k, stride, pad), self.v[t][1])
-        return o
 
 
 # ---- entries: the format of the head input each one implies, and the images
@@ -135,7 +127,7 @@ def _readers(g, t, cin, readers):
 def build_graph(case, x):
     """Returns (graph, [output tensors], ids): ids names the tensors the liveness checks look at ('conv', 'pool' | 'head', 'dw', 'pw')."""
     c = case
-    g = Graph(x, c['x_fl'])
+    g = RefGraph(x, c['x_fl'])
     for key, v in c['opts'].items():
         g.net.set_option(key, v)
     t0 = next(iter(g.v))

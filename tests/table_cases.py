@@ -3,7 +3,7 @@ f8_table.hip): tests/test_table_plan.py (the tables against their definition, ac
 launches, the host code under the sanitizers; no GPU) and tests/test_gpu_table.py (every case bit for bit on the device, on the default plan, with
 every fusing pass on, with table_i8 = 0 and with fuse_table = 0).  No test functions here.
 
-The reference, in numpy on the int32 tensors the graph builder carries (mul_cases._Graph evaluates every other op with the oracle):
+The reference (tests/ref_ops.py), in numpy on the int32 tensors the reference graph carries:
     table_ref     table[oracle.requant(x, in_fl, fl, in_signed) + (128 if in_signed else 0)]
 
 Two families of cases.
@@ -21,7 +21,7 @@ C in {8, 20, 48, 64}: the masked 4-byte instance, the 16-byte instance, a ragged
 
 The expected plan tokens and kernel symbols of every case — `exp`: the default plan (also with every fusing pass on), `nofuse`: fuse_table = 0; with
 table_i8 = 0 every `table_i8:` of either list is `table_i32:` on f8::table_i32_kernel — are WRITTEN BY HAND in launch order."""
-import functools
+import sys
 
 import numpy as np
 
@@ -29,33 +29,9 @@ import graph_cases
 import mul_cases as mc
 from concat_cases import FUSE_ALL, X_FL, readers  # noqa: F401  (the tests take FUSE_ALL from here)
 from f8net_amd import synth, tables
-from oracle import oracle
+from refgraph import record_int_graph
 
 INT32_MIN, INT32_MAX = -2 ** 31, 2 ** 31 - 1
-
-
-def table_index(x, fl, *, in_fl, in_signed):
-    """q: the source in the table's index format, int64."""
-    return oracle.requant(x, in_fl, fl, in_signed).astype(np.int64)
-
-
-def table_ref(x, fl, table, *, in_fl, in_signed):
-    return np.asarray(table, np.int32)[table_index(x, fl, in_fl=in_fl, in_signed=in_signed) + (128 if in_signed else 0)]
-
-
-class _Graph(mc._Graph):
-    """mul_cases._Graph with table.  `idx[o]` keeps q of every table for the case builders' checks."""
-
-    def __init__(self, x, x_fl, record=True):
-        super().__init__(x, x_fl, record=record)
-        self.idx, self.srcv = {}, {}
-
-    def table(self, t, table, *, in_fl, in_signed, out_fl, label=None):
-        o = self._id(lambda: self.net.table(t, table, in_fl=in_fl, in_signed=in_signed, out_fl=out_fl, label=label))
-        x, fl = self.srcv[o] = self.v[t]
-        self.idx[o] = table_index(x, fl, in_fl=in_fl, in_signed=in_signed)
-        self.v[o] = (table_ref(x, fl, table, in_fl=in_fl, in_signed=in_signed), out_fl)
-        return o
 
 
 # ---- the tables
@@ -162,25 +138,14 @@ def make_input(name, n=None):
     return x
 
 
-def build_graph(name, x, record=True):
-    """Returns (graph, output ids, table / mul tensor ids)."""
-    c = CASES[name]
-    g = _Graph(x, c['x_fl'], record=record)
-    outs, ops = c['build'](g, next(iter(g.v)), c)
-    return g, outs, ops
-
-
 def reachable(in_signed):
     return set(range(-127, 128)) if in_signed else set(range(256))
 
 
-@functools.lru_cache(maxsize=None)
-def reference(name):
-    """(graph, output ids, op ids) of the case over N + 1 images, evaluated on the reference alone, once; nothing may write into its arrays.
-    Asserts what the module text promises about the DATA of a table-alone case: every reachable index occurs within the first N images AND within
-    the first N - 1 (the two batch sizes the device runs), the source meets exact ties of the index shift and both clamps."""
+def _check_data(name, g, outs, ops):
+    """What the module text promises about the DATA of reference(name) of a table-alone case: every reachable index occurs within the first N images
+    AND within the first N - 1 (the two batch sizes the device runs), the source meets exact ties of the index shift and both clamps."""
     c = CASES[name]
-    g, outs, ops = build_graph(name, make_input(name, c['N'] + 1), record=False)
     assert np.unique(g.v[ops[-1]][0]).size > 5, name
     if c['build'] is _tab:
         (q,) = g.idx.values()
@@ -191,15 +156,9 @@ def reference(name):
         assert sh == 5 and mc._has_ties(src, sh), name
         lo, hi = (-127, 127) if c['in'][1] else (0, 255)
         assert (np.asarray(src, np.int64) >> sh).max() > hi and ((np.asarray(src, np.int64) >> sh).min() < lo or not c['in'][1]), name
-    return g, outs, ops
 
 
-def plan(name, x, max_batch=None, **opts):
-    g, outs, ops = build_graph(name, x)
-    for k, v in opts.items():
-        g.net.set_option(k, v)
-    g.net.finalize(max_batch or x.shape[0])
-    return g, outs, ops
+graph_cases.bind_cases(sys.modules[__name__], check_data=_check_data)      # build_graph, reference (asserts _check_data), plan, int_graph
 
 
 def lines(net):
@@ -262,19 +221,9 @@ def mbconv_input(n=None):
     return synth.rand_uniform_int(5, 'mbconv', (n or MBCONV['N'], MBCONV['cin'], MBCONV['H'], MBCONV['W']), 0, 255).astype(np.int32)
 
 
-class Recorder(mc.Recorder, _Graph):
-    """mul_cases.Recorder with table: every op also goes into an IntGraph."""
-
-    def table(self, t, table, *, in_fl, in_signed, out_fl, label=None):
-        from f8net_amd.onnx_import import IntOp
-        o = super().table(t, table, in_fl=in_fl, in_signed=in_signed, out_fl=out_fl)
-        return self._put(o, IntOp('table', src=self.ids[t], shift=self.v[t][1] - in_fl, signed=in_signed, table=np.asarray(table, np.int32).copy(),
-                                  in_fl=in_fl, out_fl=out_fl))
-
-
 def mbconv_int_graph():
     """mbconv_block as an IntGraph, op for op what mbconv_block records.  Returns (IntGraph, reference graph, output id)."""
-    return graph_cases.record_int_graph(Recorder, mbconv_input(), MBCONV['x_fl'], lambda g, x0: mbconv_block(g, x0)[0])
+    return record_int_graph(mbconv_input(), MBCONV['x_fl'], lambda g, x0: mbconv_block(g, x0)[0])
 
 
 def unsigned_int_graph():
@@ -285,4 +234,4 @@ def unsigned_int_graph():
         out = mc._cv(g, s, 1, 32, 6, relu=False, in_fl=7, in_signed=False, label='tail')                          # fraclen 6 read at 7: a left shift
         g.output(out)
         return out
-    return graph_cases.record_int_graph(Recorder, mc.se_input(), X_FL, build)
+    return record_int_graph(mc.se_input(), X_FL, build)

@@ -5,20 +5,17 @@ hand, where a pool cuts the fused launches of ResNet-50 and MobileNet-V2 (exactl
 float64 and to the oracle's depthwise conv, adaptive_avgpool, ONNX AveragePool in both directions with its refusals, the torch op's meta shape, the
 option key, the shipped nets' plan digests, and examples/avgpool_host.c with the host code under ASan / UBSan as a stand-alone program.
 tests/test_gpu_avgpool.py runs every case on the device."""
-import glob
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 import avgpool_cases as ac
+import ref_ops
 from f8net_amd import onnx_export, onnx_import, onnx_io, synth, topology
 from f8net_amd._lib import F8Error, lib
 from f8net_amd.net import F8Net, build_net, record_net
+from graph_cases import plan_digest_tool, same_ops, sanitized_host_program, shipped_digest_membership
+from refgraph import RefGraph, graph_forward
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INVALID, UNSUPPORTED, STATE = -1, -2, -5
 
 
@@ -50,10 +47,10 @@ def test_acceptance_shape_and_fraclen(k, s, pad, shift, shape):
 
 
 def test_default_shift_is_the_references():
-    assert [ac.default_shift(k) for k in (1, 2, 3, 4, 5, 6, 7, 8, 15, 30, 64)] == [0, 2, 3, 4, 5, 5, 6, 6, 8, 10, 12]
+    assert [ref_ops.default_shift(k) for k in (1, 2, 3, 4, 5, 6, 7, 8, 15, 30, 64)] == [0, 2, 3, 4, 5, 5, 6, 6, 8, 10, 12]
     import torch
     for k in (2, 3, 5, 7, 11, 15):                                 # FXQAvgPool2d.__init__ (fix_quant_ops.py:121-122)
-        assert ac.default_shift(k) == int(torch.round(torch.log2(torch.tensor(float(k ** 2)))).item())
+        assert ref_ops.default_shift(k) == int(torch.round(torch.log2(torch.tensor(float(k ** 2)))).item())
 
 
 @pytest.mark.parametrize('what, status, match', [
@@ -205,7 +202,7 @@ def test_small_nets_plan(name):
     build, _, pools = ac.NETS[name]
     x = ac.net_input(name)
     for opts in ({}, ac.FUSE_ALL):
-        g = ac._Graph(x, ac.X_FL)
+        g = RefGraph(x, ac.X_FL)
         build(g, next(iter(g.v)))
         for k, v in opts.items():
             g.net.set_option(k, v)
@@ -226,8 +223,8 @@ def test_reference_is_torch_float64_with_divisor_1(hw):
             continue
         ac.pin_to_torch(x, k, s, pad)
         ac.pin_to_oracle(small, k, s, pad)
-        y, fl = ac.sumpool_ref(x.astype(np.int32), 5, k, s, pad)
-        assert fl == 5 + ac.default_shift(k) and y.dtype == np.int32 and y.shape == (2, 3, ac.out_size(hw[0], k, s, pad), ac.out_size(hw[1], k, s, pad))
+        y, fl = ref_ops.sumpool_ref(x.astype(np.int32), 5, k, s, pad)
+        assert fl == 5 + ref_ops.default_shift(k) and y.dtype == np.int32 and y.shape == (2, 3, ac.out_size(hw[0], k, s, pad), ac.out_size(hw[1], k, s, pad))
 
 
 def test_the_issues_six_geometries_on_7x9():
@@ -240,9 +237,9 @@ def test_wrap_case_leaves_the_int32_range_before_wrapping():
     c = ac.CASES['w_wrap']
     ref, _, (pl,) = ac.reference('w_wrap')
     src = next(v for t, (v, fl) in ref.v.items() if t not in (0, pl))
-    exact = ac.sumpool_exact(src, c['k'], c['s'], c['pad'])
+    exact = ref_ops.sumpool_exact(src, c['k'], c['s'], c['pad'])
     assert (np.abs(exact) >= 2 ** 31).sum() > 1000 and (exact != ref.v[pl][0]).sum() > 1000
-    np.testing.assert_array_equal(ref.v[pl][0], ac.wrap32(exact))
+    np.testing.assert_array_equal(ref.v[pl][0], ref_ops.wrap32(exact))
 
 
 # ---- adaptive pooling
@@ -264,19 +261,6 @@ def test_adaptive_avgpool_on_the_psp_bins():
 
 
 # ---- ONNX
-def _same_ops(a, b):
-    assert len(a.ops) == len(b.ops) and a.output == b.output and a.output_float == b.output_float
-    for p, q in zip(a.ops, b.ops):
-        for f in ('kind', 'src', 'src2', 'stride', 'pad', 'groups', 'kernel', 'shift', 'signed', 'relu', 'dilation', 'srcs', 'shifts', 'shape', 'mode', 'scale'):
-            if p.kind == 'concat' and f == 'src2':
-                continue
-            assert getattr(p, f) == getattr(q, f), (p.kind, f, getattr(p, f), getattr(q, f))
-        for f in ('weight', 'bias'):
-            assert (getattr(p, f) is None) == (getattr(q, f) is None)
-            if getattr(p, f) is not None:
-                np.testing.assert_array_equal(getattr(p, f), getattr(q, f))
-
-
 def _plan_but_labels(net):
     """Per launch (plan token, kernel symbol, bytes, the forms and epilogue flags describe() prints): the plan, but for the tensor labels."""
     text = [l.split()[2:] for l in net.describe().splitlines() if l.strip() and l.split()[0].isdigit()]
@@ -295,10 +279,10 @@ def test_onnx_round_trip(name):
         (1, 0, [c['k']] * 2, [c['s']] * 2, [c['pad']] * 4)
     (mul,) = [n for n in nodes if n.op == 'Mul' and n.inputs[0] == ap.outputs[0]]
     back = onnx_import.import_graph(data)
-    _same_ops(ig, back)
+    same_ops(ig, back)
     assert back.solve_fraclens(ac.X_FL) == ig.solve_fraclens(ac.X_FL)
     x = ac.make_input(name)
-    np.testing.assert_array_equal(ac.graph_forward(back, x, ac.X_FL), g.v[out][0])      # the walker against _Graph's reference
+    np.testing.assert_array_equal(graph_forward(back, x, ac.X_FL), g.v[out][0])      # the walker against RefGraph's values
     net = back.build_net(3, input_fraclen=ac.X_FL, options=c['opts'])
     direct, _, _ = ac.plan(name, x)
     assert [(t, k) for _, t, k in ac.pool_lines(net)] == ([] if c['forms'] is None else [(ac.token(c), ac.symbol(c, 1))])
@@ -351,7 +335,7 @@ def test_onnx_import_refusals(name, edit, match):
 
 def test_onnx_count_include_pad_0_without_padding_is_accepted():
     ig, _, _ = ac.int_graph('g_2s2_7x9')
-    _same_ops(ig, onnx_import.import_graph(_model('g_2s2_7x9', _set('count_include_pad', 0))))
+    same_ops(ig, onnx_import.import_graph(_model('g_2s2_7x9', _set('count_include_pad', 0))))
 
 
 def test_onnx_reduce_sum_pair_stays_the_global_pool():
@@ -408,37 +392,19 @@ def test_plan_digests_of_the_shipped_nets_are_the_parents():
     """tools/plan_digest.py's DEFAULT option column (tests/golden/plan_digest_default.txt, recorded before f8_net_concat existed) at batch 128 for the
     nets whose tail is the global pool in its three plans (a launch of its own, fused behind a conv, the end of a chain): f8_net_avgpool_window
     changes no matcher, and its option key moves no shipped plan.  (tests/test_concat_plan.py plans the whole column.)"""
-    sys.path.insert(0, os.path.join(ROOT, 'tools'))
-    import plan_digest
-    want = open(os.path.join(ROOT, 'tests', 'golden', 'plan_digest_default.txt')).read().splitlines()
+    plan_digest = plan_digest_tool()
     assert plan_digest.LATER['sumpool_wide'] == (0, 2)
     jobs = [(a, 224, 128, False, 'default') for a in plan_digest.ARCHS if a in ('resnet18', 'resnet50', 'mobilenet_v1', 'mobilenet_v2')]
     assert len(jobs) == 4
-    for job in jobs:
-        (line,) = plan_digest.plan_lines(job)
-        assert line in want, line
+    shipped_digest_membership(jobs)
 
 
 # ---- host code under the sanitizers
-def test_host_code_under_asan_and_ubsan(tmp_path):
+def test_host_code_under_asan_and_ubsan():
     """examples/avgpool_host.c records a DenseNet transition and a PSP pyramid (bins 1 / 2 / 3 / 6 -> 1x1 -> nearest upsample -> concat) through the C
     ABI, walks every refusal, finalizes, describes and destroys.  f8_net.cpp's host side is compiled with AddressSanitizer and
     UndefinedBehaviorSanitizer and linked with the library's other objects into that stand-alone program."""
-    hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-    objs = [o for o in sorted(glob.glob(os.path.join(ROOT, 'build', 'f8_*.o'))) if os.path.basename(o) != 'f8_net.o']
-    assert os.path.exists(hipcc) and len(objs) >= 29, 'build libf8net.so first (__graft_entry__.build()): its objects are linked here'
-    san = ['-fsanitize=address,undefined', '-fno-sanitize-recover=undefined']
-    net_o, host_o, exe = str(tmp_path / 'f8_net_san.o'), str(tmp_path / 'avgpool_host.o'), str(tmp_path / 'avgpool_host')
-    subprocess.check_call([hipcc, '--offload-arch=gfx950', '-O1', '-g', '-std=c++17', '-fPIC'] + [a for s in san for a in ('-Xarch_host', s)] +
-                          ['-x', 'hip', '-c', os.path.join(ROOT, 'f8net_amd', 'csrc', 'f8_net.cpp'), '-o', net_o])
-    subprocess.check_call(['gcc', '-std=c99', '-pedantic', '-Wall', '-Wextra', '-Werror', '-I' + os.path.join(ROOT, 'include')] + san +
-                          ['-c', os.path.join(ROOT, 'examples', 'avgpool_host.c'), '-o', host_o])
-    subprocess.check_call([hipcc, '--offload-arch=gfx950'] + san + [host_o, net_o] + objs + ['-o', exe])
-    env = dict(os.environ, LD_LIBRARY_PATH='/opt/rocm/lib:' + os.environ.get('LD_LIBRARY_PATH', ''), ASAN_OPTIONS='detect_leaks=1')
-    r = subprocess.run([exe], text=True, capture_output=True, env=env)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert 'runtime error' not in r.stderr and 'AddressSanitizer' not in r.stderr, r.stderr
-    out = r.stdout
+    out = sanitized_host_program('avgpool_host.c')
     assert out.rstrip().endswith('ok')
     assert out.count('sumpool2x2s2:transition.pool') == 1 and out.count('avgpool_sum:psp.pool1') == 1
     assert all(out.count(f'sumpool{k}x{k}s{k}:psp.pool{b}') == 1 for k, b in ((6, 2), (4, 3), (2, 6)))

@@ -4,21 +4,18 @@ pass on and with fuse_shuffle = 0 — written by hand there —, launch_info / l
 MobileNet-V2 (exactly where an output tap does), ONNX Split / Slice / Reshape-Transpose-Reshape in both directions and the import refusals, the
 shipped nets' default plans against the recorded digests, and the host code under AddressSanitizer / UndefinedBehaviorSanitizer as a stand-alone
 program.  tests/test_gpu_chanmap.py runs every case on the device."""
-import glob
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 import torch
 
 import chanmap_cases as cm
+import ref_ops
 from f8net_amd import onnx_export, onnx_import, onnx_io, synth, topology
 from f8net_amd._lib import F8Error
 from f8net_amd.net import F8Net, build_net, record_net
+from graph_cases import all_shipped_jobs, plan_digest_tool, same_ops, sanitized_host_program, shipped_digest_membership
+from refgraph import graph_forward
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INVALID, UNSUPPORTED, STATE = -1, -2, -5
 
 
@@ -96,21 +93,20 @@ def test_options():
         for bad in (-1, 2):
             with pytest.raises(F8Error):
                 net.set_option(key, bad)
-    sys.path.insert(0, os.path.join(ROOT, 'tools'))
-    import plan_digest
-    assert plan_digest.LATER['chanmap_i8'] == (0, 1) and plan_digest.LATER['fuse_shuffle'] == (0, 1)
+    later = plan_digest_tool().LATER
+    assert later['chanmap_i8'] == (0, 1) and later['fuse_shuffle'] == (0, 1)
 
 
 # ---- the reference
 @pytest.mark.parametrize('groups, C', cm.SHUFFLES)
 def test_shuffle_reference_is_torchs(groups, C):
     x = np.random.default_rng(C * 10 + groups).integers(-2 ** 31, 2 ** 31, (2, C, 3, 2), dtype=np.int64).astype(np.int32)
-    y = cm.channel_shuffle(x, groups)
+    y = ref_ops.channel_shuffle(x, groups)
     np.testing.assert_array_equal(y, torch.nn.functional.channel_shuffle(torch.from_numpy(x), groups).numpy())
-    assert sorted(cm.shuffle_index(C, groups).tolist()) == list(range(C))
+    assert sorted(ref_ops.shuffle_index(C, groups).tolist()) == list(range(C))
     assert not np.array_equal(y, x)
     if groups != C // groups:                                      # (4, 16) is its own inverse; every other entry tells the transpose done the wrong way round
-        assert not np.array_equal(y, cm.channel_shuffle(x, C // groups))
+        assert not np.array_equal(y, ref_ops.channel_shuffle(x, C // groups))
 
 
 @pytest.mark.parametrize('first, channels, C', cm.SLICES)
@@ -118,8 +114,8 @@ def test_slice_reference_is_torchs(first, channels, C):
     x = np.random.default_rng(C * 100 + first).integers(-2 ** 31, 2 ** 31, (2, C, 3, 2), dtype=np.int64).astype(np.int32)
     sizes = [s for s in (first, channels, C - first - channels) if s]
     parts = torch.split(torch.from_numpy(x), sizes, dim=1)
-    np.testing.assert_array_equal(cm.channel_slice(x, first, channels), parts[1 if first else 0].numpy())
-    np.testing.assert_array_equal(cm.channel_slice(x, first, channels), x[:, first:first + channels])
+    np.testing.assert_array_equal(ref_ops.channel_slice(x, first, channels), parts[1 if first else 0].numpy())
+    np.testing.assert_array_equal(ref_ops.channel_slice(x, first, channels), x[:, first:first + channels])
 
 
 @pytest.mark.parametrize('name', sorted(cm.CASES))
@@ -138,10 +134,10 @@ def test_the_reference_of_every_case_carries_values(name):
     if c['build'] in (cm._shuffle, cm._shuffle_join, cm._shuffle_input, cm._cat_shuffle):
         (t,) = ops
         y, g = ref.v[t][0], c['groups']
-        src = cm.channel_shuffle(y, y.shape[1] // g)               # the inverse permutation gives the source back
+        src = ref_ops.channel_shuffle(y, y.shape[1] // g)               # the inverse permutation gives the source back
         assert not np.array_equal(y, src)
         if g != y.shape[1] // g:
-            assert not np.array_equal(y, cm.channel_shuffle(src, y.shape[1] // g))
+            assert not np.array_equal(y, ref_ops.channel_shuffle(src, y.shape[1] // g))
 
 
 # ---- tokens and kernels
@@ -225,22 +221,6 @@ def test_the_op_cuts_the_chain_where_a_tap_does(arch, name, op):
 
 
 # ---- ONNX
-FIELDS = ('kind', 'src', 'src2', 'stride', 'pad', 'groups', 'kernel', 'shift', 'signed', 'relu', 'dilation', 'srcs', 'shifts', 'shape', 'first', 'channels')
-
-
-def _same_ops(a, b):
-    assert len(a.ops) == len(b.ops) and a.output == b.output and a.output_float == b.output_float
-    for p, q in zip(a.ops, b.ops):
-        for f in FIELDS:
-            if p.kind == 'concat' and f == 'src2':
-                continue
-            assert getattr(p, f) == getattr(q, f), (p.kind, f, getattr(p, f), getattr(q, f))
-        for f in ('weight', 'bias'):
-            assert (getattr(p, f) is None) == (getattr(q, f) is None)
-            if getattr(p, f) is not None:
-                np.testing.assert_array_equal(getattr(p, f), getattr(q, f))
-
-
 def test_onnx_round_trip_of_the_stage():
     ig, g, out = cm.stage_int_graph()
     assert [o.kind for o in ig.ops].count('slice') == 4 and [o.kind for o in ig.ops].count('shuffle') == 3
@@ -248,8 +228,10 @@ def test_onnx_round_trip_of_the_stage():
     nodes = onnx_io.load_graph(data).nodes
     assert sum(n.op == 'Slice' for n in nodes) == 4 and sum(n.op == 'Transpose' for n in nodes) == 3
     back = onnx_import.import_graph(data)
-    _same_ops(ig, back)
+    same_ops(ig, back)
     assert back.solve_fraclens(cm.X_FL) == ig.solve_fraclens(cm.X_FL)
+    x = cm.stage_input()
+    np.testing.assert_array_equal(graph_forward(back, x, cm.X_FL), g.v[out][0])      # the walker against RefGraph's values
     net = back.build_net(2, input_fraclen=cm.X_FL)
     assert [t for _, t, _ in cm.lines(net)] == ['concat+shuffle2_i8:', 'slice_i8:', 'slice_i8:'] * 2 + ['concat+shuffle2_i8:']
 
@@ -292,7 +274,7 @@ def _stage_model(edit=None, torch_style=True):
 def test_onnx_split_and_the_reshape_transpose_reshape_triple_import_as_slices_and_shuffles():
     ig, g = _stage_model()
     assert sum(n.op == 'Split' for n in g.nodes) == 2 and not any(n.op == 'Slice' for n in g.nodes)
-    _same_ops(ig, onnx_import.import_graph(onnx_io.model_proto(g)))
+    same_ops(ig, onnx_import.import_graph(onnx_io.model_proto(g)))
 
 
 def test_onnx_split_without_sizes_is_an_equal_split():
@@ -301,7 +283,7 @@ def test_onnx_split_without_sizes_is_an_equal_split():
             if n.op == 'Split':
                 del n.attrs['split']
     ig, g = _stage_model(edit)
-    _same_ops(ig, onnx_import.import_graph(onnx_io.model_proto(g)))
+    same_ops(ig, onnx_import.import_graph(onnx_io.model_proto(g)))
 
 
 def test_the_classifiers_reshape_stays_plumbing():
@@ -344,41 +326,21 @@ def test_a_shipped_net_exports_and_imports_as_before():
     ig = onnx_export.graph_from_params(spec, synth.make_params(spec, seed=5), 64)
     back = onnx_import.import_graph(onnx_export.export_graph(ig))
     assert all(o.kind not in ('slice', 'shuffle') for o in back.ops)
-    _same_ops(ig, back)
+    same_ops(ig, back)
 
 
 # ---- the shipped nets plan as before
 def test_plan_digests_of_the_shipped_nets_are_the_recorded_ones():
     """tools/plan_digest.py's DEFAULT option column: the lines recorded before these entry points existed (tests/golden/plan_digest_default.txt), of
     which a subset is planned here.  The other option sets of the tool's matrix are not checked by the suite."""
-    sys.path.insert(0, os.path.join(ROOT, 'tools'))
-    import plan_digest
-    want = open(os.path.join(ROOT, 'tests', 'golden', 'plan_digest_default.txt')).read().splitlines()
-    jobs = [(a, 224, bs, False, 'default') for a in plan_digest.ARCHS for bs in (2, 128)] + [(a, hw, 128, False, 'default') for a, hw in plan_digest.EXTRA_SIZES]
-    for job in jobs:
-        (line,) = plan_digest.plan_lines(job)
-        assert line in want, line
+    shipped_digest_membership(all_shipped_jobs())
 
 
 # ---- host code under the sanitizers
-def test_host_code_under_asan_and_ubsan(tmp_path):
+def test_host_code_under_asan_and_ubsan():
     """examples/shuffle_host.c records `unit`, `unequal` and `output` through the C ABI, finalizes, describes and destroys them.  f8_net.cpp's host side
     is compiled with AddressSanitizer and UndefinedBehaviorSanitizer and linked with the library's other objects into that stand-alone program."""
-    hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-    objs = [o for o in sorted(glob.glob(os.path.join(ROOT, 'build', 'f8_*.o'))) if os.path.basename(o) != 'f8_net.o']
-    assert os.path.exists(hipcc) and len(objs) >= 30, 'build libf8net.so first (__graft_entry__.build()): its objects are linked here'
-    san = ['-fsanitize=address,undefined', '-fno-sanitize-recover=undefined']
-    net_o, host_o, exe = str(tmp_path / 'f8_net_san.o'), str(tmp_path / 'shuffle_host.o'), str(tmp_path / 'shuffle_host')
-    subprocess.check_call([hipcc, '--offload-arch=gfx950', '-O1', '-g', '-std=c++17', '-fPIC'] + [a for s in san for a in ('-Xarch_host', s)] +
-                          ['-x', 'hip', '-c', os.path.join(ROOT, 'f8net_amd', 'csrc', 'f8_net.cpp'), '-o', net_o])
-    subprocess.check_call(['gcc', '-std=c99', '-pedantic', '-Wall', '-Wextra', '-Werror', '-I' + os.path.join(ROOT, 'include')] + san +
-                          ['-c', os.path.join(ROOT, 'examples', 'shuffle_host.c'), '-o', host_o])
-    subprocess.check_call([hipcc, '--offload-arch=gfx950'] + san + [host_o, net_o] + objs + ['-o', exe])
-    env = dict(os.environ, LD_LIBRARY_PATH='/opt/rocm/lib:' + os.environ.get('LD_LIBRARY_PATH', ''), ASAN_OPTIONS='detect_leaks=1')
-    r = subprocess.run([exe], text=True, capture_output=True, env=env)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert 'runtime error' not in r.stderr and 'AddressSanitizer' not in r.stderr, r.stderr
-    out = r.stdout
+    out = sanitized_host_program('shuffle_host.c')
     assert out.rstrip().endswith('ok')
     assert out.count('slice_i8:') == 2 and out.count('concat+shuffle2_i8:') == 1 and out.count('concat_i8:') == 1
     assert out.count('shuffle2_i8:') == 2 and out.count('shuffle3_i32:') == 1

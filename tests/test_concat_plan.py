@@ -3,22 +3,18 @@ tests/concat_cases.py plans — written by hand there —, the forms of an i8-mo
 ResNet-50 and MobileNet-V2 (exactly where an output tap does), the ONNX Concat in both directions, the shipped nets' plans against the digests of
 the library before this entry point existed, and the host code under AddressSanitizer / UndefinedBehaviorSanitizer as a stand-alone program.
 tests/test_gpu_concat.py runs every case on the device."""
-import glob
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 import concat_cases as cc
-import dil_cases
 from f8net_amd import onnx_export, onnx_import, onnx_io, synth, topology
 from f8net_amd._lib import F8Error
 from f8net_amd.net import F8Net, build_net, record_net
+from graph_cases import all_shipped_jobs, same_ops, sanitized_host_program, shipped_digest_membership
 from oracle import oracle
+from ref_ops import stuffed
+from refgraph import RefGraph, graph_forward
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INVALID, UNSUPPORTED, STATE = -1, -2, -5
 
 
@@ -180,30 +176,17 @@ def test_a_concat_cuts_the_chain_where_a_tap_does(arch, pair):
 
 
 # ---- ONNX
-def _same_ops(a, b):
-    assert len(a.ops) == len(b.ops) and a.output == b.output and a.output_float == b.output_float
-    for p, q in zip(a.ops, b.ops):
-        for f in ('kind', 'src', 'src2', 'stride', 'pad', 'groups', 'kernel', 'shift', 'signed', 'relu', 'dilation', 'srcs', 'shifts', 'shape'):
-            if p.kind == 'concat' and f == 'src2':
-                continue
-            assert getattr(p, f) == getattr(q, f), (p.kind, f, getattr(p, f), getattr(q, f))
-        for f in ('weight', 'bias'):
-            assert (getattr(p, f) is None) == (getattr(q, f) is None)
-            if getattr(p, f) is not None:
-                np.testing.assert_array_equal(getattr(p, f), getattr(q, f))
-
-
 @pytest.mark.parametrize('name', ['gap', 'nested', 'inception'])
 def test_onnx_round_trip(name):
     ig, g, out = cc.int_graph(name)
     assert sum(o.kind == 'concat' for o in ig.ops) == len(cc.reference(name)[2])
     back = onnx_import.import_graph(onnx_export.export_graph(ig))
-    _same_ops(ig, back)
+    same_ops(ig, back)
     assert back.solve_fraclens(cc.X_FL) == ig.solve_fraclens(cc.X_FL)
     if name == 'gap':
         assert [o.shifts for o in back.ops if o.kind == 'concat'] == [[0, 3, 6]]
     x = cc.make_input(name)
-    np.testing.assert_array_equal(cc.graph_forward(back, x, cc.X_FL), g.v[out][0])      # the walker against _Graph's reference
+    np.testing.assert_array_equal(graph_forward(back, x, cc.X_FL), g.v[out][0])      # the walker against RefGraph's values
     net = back.build_net(2, input_fraclen=cc.X_FL)
     c = cc.CASES[name]
     assert {(t, k) for _, t, k in cc.concat_lines(net)} == {(c['mode'], cc.symbol(c['mode'], c['aligned']))}
@@ -225,7 +208,7 @@ def test_onnx_concat_on_another_axis_is_refused(axis):
 
 def test_onnx_concat_axis_minus_3_is_the_channel_axis():
     ig, _, _ = cc.int_graph('gap')
-    _same_ops(ig, onnx_import.import_graph(_concat_model(lambda g, cat: cat.attrs.__setitem__('axis', -3))))
+    same_ops(ig, onnx_import.import_graph(_concat_model(lambda g, cat: cat.attrs.__setitem__('axis', -3))))
 
 
 def test_onnx_concat_operand_scaled_by_three_is_refused():
@@ -245,20 +228,20 @@ def test_a_shipped_net_exports_and_imports_as_before():
     assert sum(n.op == 'Concat' for n in onnx_io.load_graph(data).nodes) == 1
     back = onnx_import.import_graph(data)
     assert all(o.kind != 'concat' for o in back.ops)
-    _same_ops(ig, back)
+    same_ops(ig, back)
 
 
 def test_cropped_stuffed_kernel_is_the_same_conv():
-    """The identity concat_cases._Graph.conv evaluates ASPP's large dilations with, on the graph of two such convs and their concat as the handle records it."""
+    """The identity RefGraph.conv evaluates ASPP's large dilations with, on the graph of two such convs and their concat as the handle records it."""
     x = synth.rand_uniform_int(3, 'cropx', (2, 4, 5, 6), 0, 255).astype(np.int32)
-    g = cc._Graph(x, 8)
+    g = RefGraph(x, 8)
     ws = [synth.rand_uniform_int(4 + d, 'cropw', (16, 4, 3, 3), -127, 127).astype(np.int32) for d in (7, 9)]
     os_ = [g.conv(0, w, None, pad=d, groups=1, weight_fl=5, input_fl=8, input_signed=False, relu=False, quant_input=True, dilation=d) for w, d in zip(ws, (7, 9))]
     cat = g.concat(os_)
     g.output(cat)
     g.net.finalize(2)
     assert [n.split(':')[0] for n in _names(g.net)][1:4] == ['conv3x3s1d7_t128x32x32', 'conv3x3s1d9_t128x32x32', 'concat_i32']
-    want = [oracle.conv2d(x, dil_cases.stuffed(w, d), None, 1, d, 1) for w, d in zip(ws, (7, 9))]
+    want = [oracle.conv2d(x, stuffed(w, d), None, 1, d, 1) for w, d in zip(ws, (7, 9))]
     np.testing.assert_array_equal(g.v[cat][0], np.concatenate(want, axis=1))
 
 
@@ -266,35 +249,13 @@ def test_cropped_stuffed_kernel_is_the_same_conv():
 def test_plan_digests_of_the_shipped_nets_are_the_parents():
     """tools/plan_digest.py's DEFAULT option column only: the lines recorded from the library before f8_net_concat existed
     (tests/golden/plan_digest_default.txt), of which a subset is planned here.  The other option sets of the tool's matrix are not checked by the suite."""
-    sys.path.insert(0, os.path.join(ROOT, 'tools'))
-    import plan_digest
-    want = open(os.path.join(ROOT, 'tests', 'golden', 'plan_digest_default.txt')).read().splitlines()
-    assert len(want) == (len(plan_digest.ARCHS) + len(plan_digest.EXTRA_SIZES)) * len(plan_digest.BATCHES)
-    # (the file holds the whole default column; planned here: every net at 224 x 224 for 2 and 128 images, the extra sizes for 128)
-    jobs = [(a, 224, bs, False, 'default') for a in plan_digest.ARCHS for bs in (2, 128)] + [(a, hw, 128, False, 'default') for a, hw in plan_digest.EXTRA_SIZES]
-    for job in jobs:
-        (line,) = plan_digest.plan_lines(job)
-        assert line in want, line
+    shipped_digest_membership(all_shipped_jobs())
 
 
 # ---- host code under the sanitizers
-def test_host_code_under_asan_and_ubsan(tmp_path):
+def test_host_code_under_asan_and_ubsan():
     """examples/concat_host.c records `bytes`, `raw` and `nested` through the C ABI, finalizes, describes and destroys them.  f8_net.cpp's host side is
     compiled with AddressSanitizer and UndefinedBehaviorSanitizer and linked with the library's other objects into that stand-alone program."""
-    hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-    objs = [o for o in sorted(glob.glob(os.path.join(ROOT, 'build', 'f8_*.o'))) if os.path.basename(o) != 'f8_net.o']
-    assert os.path.exists(hipcc) and len(objs) >= 26, 'build libf8net.so first (__graft_entry__.build()): its objects are linked here'
-    san = ['-fsanitize=address,undefined', '-fno-sanitize-recover=undefined']
-    net_o, host_o, exe = str(tmp_path / 'f8_net_san.o'), str(tmp_path / 'concat_host.o'), str(tmp_path / 'concat_host')
-    subprocess.check_call([hipcc, '--offload-arch=gfx950', '-O1', '-g', '-std=c++17', '-fPIC'] + [a for s in san for a in ('-Xarch_host', s)] +
-                          ['-x', 'hip', '-c', os.path.join(ROOT, 'f8net_amd', 'csrc', 'f8_net.cpp'), '-o', net_o])
-    subprocess.check_call(['gcc', '-std=c99', '-pedantic', '-Wall', '-Wextra', '-Werror', '-I' + os.path.join(ROOT, 'include')] + san +
-                          ['-c', os.path.join(ROOT, 'examples', 'concat_host.c'), '-o', host_o])
-    subprocess.check_call([hipcc, '--offload-arch=gfx950'] + san + [host_o, net_o] + objs + ['-o', exe])
-    env = dict(os.environ, LD_LIBRARY_PATH='/opt/rocm/lib:' + os.environ.get('LD_LIBRARY_PATH', ''), ASAN_OPTIONS='detect_leaks=1')
-    r = subprocess.run([exe], text=True, capture_output=True, env=env)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert 'runtime error' not in r.stderr and 'AddressSanitizer' not in r.stderr, r.stderr
-    out = r.stdout
+    out = sanitized_host_program('concat_host.c')
     assert out.rstrip().endswith('ok')
     assert out.count('concat_i8:') == 5 and out.count('concat_i32:') == 1

@@ -4,21 +4,19 @@ transposed conv cuts the fused launches of ResNet-50 (exactly where an output ta
 errors, the reference pinned to torch in float64 and to the oracle's conv over the zero-stuffed input for 314 geometries, the liveness of every
 kernel tap of every case, the default plan digests of the shipped nets, the host code under the sanitizers as a stand-alone C program.
 tests/test_gpu_deconv.py runs every case on the device."""
-import glob
 import itertools
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import deconv_cases as dc
+import ref_ops
 from f8net_amd import onnx_export, onnx_import, onnx_io, synth, topology
 from f8net_amd._lib import ConvDesc, F8Error, lib
 from f8net_amd.net import F8Net, build_net, record_net
+from graph_cases import all_shipped_jobs, same_ops, sanitized_host_program, shipped_digest_membership
+from refgraph import graph_forward
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INVALID, UNSUPPORTED, STATE = -1, -2, -5
 
 
@@ -204,19 +202,6 @@ def test_a_transposed_conv_cuts_the_chain_where_a_tap_does(signed, in_fl):
 
 
 # ---- ONNX and IntGraph
-def _same_ops(a, b):
-    assert len(a.ops) == len(b.ops) and a.output == b.output and a.output_float == b.output_float
-    for p, q in zip(a.ops, b.ops):
-        for f in ('kind', 'src', 'src2', 'stride', 'pad', 'groups', 'kernel', 'shift', 'signed', 'relu', 'dilation', 'srcs', 'shifts', 'shape', 'output_padding', 'key'):
-            if p.kind == 'concat' and f == 'src2':
-                continue
-            assert getattr(p, f) == getattr(q, f), (p.kind, f, getattr(p, f), getattr(q, f))
-        for f in ('weight', 'bias'):
-            assert (getattr(p, f) is None) == (getattr(q, f) is None)
-            if getattr(p, f) is not None:
-                np.testing.assert_array_equal(getattr(p, f), getattr(q, f))
-
-
 @pytest.mark.parametrize('name', ['g_2200', 'g_5321', 'g_7231', 'e_1201', 's_3110', 'f_fcn', 'f_unet_i8'])
 def test_onnx_and_intgraph_round_trip(name):
     c = dc.CASES[name]
@@ -229,10 +214,10 @@ def test_onnx_and_intgraph_round_trip(name):
     assert (list(ct.attrs['strides']), list(ct.attrs['pads']), list(ct.attrs['output_padding']), list(ct.attrs['kernel_shape']), ct.attrs['group'],
             list(ct.attrs['dilations'])) == ([c['s']] * 2, [c['pad']] * 4, [c['op']] * 2, [c['k']] * 2, 1, [1, 1])
     back = onnx_import.import_graph(data)
-    _same_ops(ig, back)
+    same_ops(ig, back)
     assert back.solve_fraclens(dc.X_FL) == ig.solve_fraclens(dc.X_FL)
     x = dc.make_input(name)
-    np.testing.assert_array_equal(dc.graph_forward(back, x, dc.X_FL), g.v[out][0])      # the walker against _Graph's reference
+    np.testing.assert_array_equal(graph_forward(back, x, dc.X_FL), g.v[out][0])      # the walker against RefGraph's values
     net = back.build_net(2, input_fraclen=dc.X_FL)
     dc.check_lines(c, dc.deconv_lines(net), net.describe())
 
@@ -300,9 +285,9 @@ def test_wrap_cases_leave_the_int32_range_before_wrapping():
         ref, _, (up,) = dc.reference(name)
         w, b = dc.weights(c)
         src = ref.v[0][0] if c['src'] == 'input' else oracle_requant(ref, up)
-        exact = dc.deconv_exact(src, w, b, c['s'], c['pad'], c['op'])
+        exact = ref_ops.deconv_exact(src, w, b, c['s'], c['pad'], c['op'])
         assert (np.abs(exact) >= 2 ** 31).sum() > 100 and (exact != ref.v[up][0]).sum() > 100
-        np.testing.assert_array_equal(ref.v[up][0], dc.wrap32(exact))
+        np.testing.assert_array_equal(ref.v[up][0], ref_ops.wrap32(exact))
 
 
 def oracle_requant(ref, up):
@@ -330,34 +315,14 @@ def test_every_kernel_tap_of_every_case_is_live(name):
 def test_plan_digests_of_the_shipped_nets_are_the_parents():
     """tools/plan_digest.py's DEFAULT option column (tests/golden/plan_digest_default.txt, recorded before f8_net_concat existed), the subset
     tests/test_concat_plan.py plans: f8_net_conv_transpose adds no option key and changes no matcher."""
-    sys.path.insert(0, os.path.join(ROOT, 'tools'))
-    import plan_digest
-    want = open(os.path.join(ROOT, 'tests', 'golden', 'plan_digest_default.txt')).read().splitlines()
-    jobs = [(a, 224, bs, False, 'default') for a in plan_digest.ARCHS for bs in (2, 128)] + [(a, hw, 128, False, 'default') for a, hw in plan_digest.EXTRA_SIZES]
-    for job in jobs:
-        (line,) = plan_digest.plan_lines(job)
-        assert line in want, line
+    shipped_digest_membership(all_shipped_jobs())
 
 
 # ---- host code under the sanitizers
-def test_host_code_under_asan_and_ubsan(tmp_path):
+def test_host_code_under_asan_and_ubsan():
     """examples/deconv_host.c records a U-Net step (conv / 2 -> conv -> deconv 2x2 / 2 -> concat with the skip -> conv) and every phase shape of the
     packer through the C ABI, walks the refusals, finalizes, describes and destroys.  f8_net.cpp's host side is compiled with AddressSanitizer and
     UndefinedBehaviorSanitizer and linked with the library's other objects into that stand-alone program."""
-    hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-    objs = [o for o in sorted(glob.glob(os.path.join(ROOT, 'build', 'f8_*.o'))) if os.path.basename(o) != 'f8_net.o']
-    assert os.path.exists(hipcc) and len(objs) >= 28, 'build libf8net.so first (__graft_entry__.build()): its objects are linked here'
-    san = ['-fsanitize=address,undefined', '-fno-sanitize-recover=undefined']
-    net_o, host_o, exe = str(tmp_path / 'f8_net_san.o'), str(tmp_path / 'deconv_host.o'), str(tmp_path / 'deconv_host')
-    subprocess.check_call([hipcc, '--offload-arch=gfx950', '-O1', '-g', '-std=c++17', '-fPIC'] + [a for s in san for a in ('-Xarch_host', s)] +
-                          ['-x', 'hip', '-c', os.path.join(ROOT, 'f8net_amd', 'csrc', 'f8_net.cpp'), '-o', net_o])
-    subprocess.check_call(['gcc', '-std=c99', '-pedantic', '-Wall', '-Wextra', '-Werror', '-I' + os.path.join(ROOT, 'include')] + san +
-                          ['-c', os.path.join(ROOT, 'examples', 'deconv_host.c'), '-o', host_o])
-    subprocess.check_call([hipcc, '--offload-arch=gfx950'] + san + [host_o, net_o] + objs + ['-o', exe])
-    env = dict(os.environ, LD_LIBRARY_PATH='/opt/rocm/lib:' + os.environ.get('LD_LIBRARY_PATH', ''), ASAN_OPTIONS='detect_leaks=1')
-    r = subprocess.run([exe], text=True, capture_output=True, env=env)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert 'runtime error' not in r.stderr and 'AddressSanitizer' not in r.stderr, r.stderr
-    out = r.stdout
+    out = sanitized_host_program('deconv_host.c')
     assert out.rstrip().endswith('ok')
     assert out.count('deconv2x2s2:') == 1 and out.count('concat_i8:') == 1 and out.count('deconv') >= 5

@@ -15,6 +15,8 @@ import dil_cases
 from f8net_amd import _lib, onnx_export, onnx_import, onnx_io, synth, topology
 from f8net_amd.net import F8Net, build_net, record_net
 from oracle import oracle
+from ref_ops import stuffed
+from refgraph import graph_forward
 
 F8_ERR_INVALID, F8_ERR_UNSUPPORTED = -1, -2
 ALL = dil_cases.ALL
@@ -29,7 +31,7 @@ def test_the_stuffed_integer_conv_is_torchs_float64_dilated_conv(d, stride, pad,
     x = synth.rand_uniform_int(1, f'pin_x{d}{stride}{pad}', (2, C, 11, 13), 0, 255).astype(np.int32)
     w = synth.rand_uniform_int(2, f'pin_w{d}{groups}', (C, C // groups, 3, 3), -127, 127).astype(np.int32)
     b = synth.rand_normal_int(3, 'pin_b', (C,), 3e5).astype(np.int32)
-    got = oracle.conv2d(x, dil_cases.stuffed(w, d), b, stride, pad, groups)
+    got = oracle.conv2d(x, stuffed(w, d), b, stride, pad, groups)
     want = torch.nn.functional.conv2d(torch.from_numpy(x).double(), torch.from_numpy(w).double(), torch.from_numpy(b).double(), stride=stride, padding=pad,
                                       dilation=d, groups=groups).numpy()
     assert got.shape == want.shape == (2, C, dil_cases.out_size(11, 3, stride, pad, d), dil_cases.out_size(13, 3, stride, pad, d))
@@ -196,7 +198,7 @@ def test_bias_classes_of_the_case_whose_rows_lose_both_outer_taps():
                  relu=False, dilation=4)
     net.output(t, as_float=False)
     net.finalize(1)
-    want = oracle.conv2d(np.ones((1, 32, 7, 7), np.int32), dil_cases.stuffed(np.ones((32, 32, 3, 3), np.int32), 4), None, 1, 4, 1)
+    want = oracle.conv2d(np.ones((1, 32, 7, 7), np.int32), stuffed(np.ones((32, 32, 3, 3), np.int32), 4), None, 1, 4, 1)
     rows = [2, 2, 2, 1, 2, 2, 2]                                     # in-image taps of an output row / column
     assert (want[0, 0] == 32 * np.outer(rows, rows)).all()
     # the weight image grows by the eight further bias vectors (32 int32 each) and the two class tables, against the one vector of a signed input
@@ -324,7 +326,7 @@ def test_the_onnx_round_trip_preserves_dilation():
     a, b = ig.build_net(2), back.build_net(2)
     assert a.describe() == b.describe() and 'dwconv3x3s1d2:' in a.describe()
     x = synth.rand_uniform_int(6, 'onnx_x', (1, 3, 64, 64), 0, 255).astype(np.int32)
-    np.testing.assert_array_equal(oracle.graph_forward(dil_cases.stuffed_graph(back), x), oracle.graph_forward(dil_cases.stuffed_graph(ig), x))
+    np.testing.assert_array_equal(graph_forward(back, x), graph_forward(ig, x))
     # unequal dilations are refused
     bad = onnx_io.load_graph(model)
     next(n for n in bad.nodes if n.op == 'Conv' and tuple(n.attrs['dilations']) == (2, 2)).attrs['dilations'] = [2, 1]

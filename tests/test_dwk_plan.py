@@ -13,8 +13,9 @@ import dw_cases
 import dwk_cases
 from f8net_amd import _lib
 from f8net_amd.net import F8Net
-from ir_cases import _Graph, _b, _w
+from ir_cases import _b, _w
 from oracle import oracle
+from refgraph import RefGraph
 
 ALL = dict(dwk_cases.CASES, max_batch=dwk_cases.MAX_BATCH_CASE, pipelined=dwk_cases.PIPELINED_CASE)
 F8_ERR_UNSUPPORTED = -2
@@ -107,7 +108,7 @@ def test_3x3_pad_1_plans_as_before(name, dwk_dot4):
 def _inverted_residual(K):
     """input -> pre 1x1 -> [1x1 expand + ReLU -> K x K / 1 depthwise + ReLU -> 1x1 project] + the block input -> output"""
     x = np.zeros((2, 32, 14, 14), np.int32)
-    g = _Graph(x, 4)
+    g = RefGraph(x, 4)
     t = next(iter(g.v))
     kw = dict(groups=1, pad=0, weight_fl=6, input_signed=False)
     pre = g.conv(t, _w(1, (32, 32, 1, 1), 8.0), _b(2, 32, 64.0), input_fl=4, relu=False, quant_input=False, **kw)

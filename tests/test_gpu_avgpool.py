@@ -12,10 +12,13 @@ import torch
 
 import avgpool_cases as ac
 import f8net_amd.torch_ops  # noqa: F401  (registers torch.ops.f8net)
+import ref_ops
 from avgpool_cases import producer
 from f8net_amd import onnx_export, onnx_import, synth, topology
 from f8net_amd.net import record_net
+from graph_cases import run_case
 from oracle import oracle
+from refgraph import RefGraph, record_int_graph
 
 pytestmark = pytest.mark.gpu
 
@@ -26,44 +29,24 @@ def dev():
     return torch.device('cuda:0')
 
 
-def _outputs(got, n, wants):
-    got = got if isinstance(got, tuple) else (got,)
-    assert len(got) == len(wants)
-    return [y.cpu().numpy().reshape((n,) + w.shape[1:]) for y, w in zip(got, wants)]
-
-
 def _expect(name, leg):
     c = ac.CASES[name]
     return [] if c['forms'] is None else [(ac.token(c), ac.symbol(c, leg))]
 
 
-def _run(name, dev, **opts):
-    c = ac.CASES[name]
-    N = c['N']
-    ref, routs, _ = ac.reference(name)                             # over N + 1 images
-    wants = [ref.v[o][0] for o in routs]
-    x = ac.make_input(name, N + 1)
-    g, outs, _ = ac.plan(name, x, max_batch=N + 1, **opts)
-    assert [(t, k) for _, t, k in ac.pool_lines(g.net)] == _expect(name, opts.get('sumpool_wide', 1)), g.net.describe()
-    xt = torch.from_numpy(x).to(dev)
-    for n in (N, N - 1):
-        got = _outputs(g.net.run(xt[:n]), n, wants)
-        for k, (y, w) in enumerate(zip(got, wants)):
-            if c.get('as_float') and k == len(wants) - 1:
-                w = w.astype(np.float32)
-            np.testing.assert_array_equal(y, w[:n], err_msg=f'{name} {opts} n={n} output {k}')
-    g.net.check()
+def _check_plan(net, name, opts):
+    assert [(t, k) for _, t, k in ac.pool_lines(net)] == _expect(name, opts.get('sumpool_wide', 1)), net.describe()
 
 
 @pytest.mark.parametrize('leg', [0, 1, 2])
 @pytest.mark.parametrize('name', sorted(ac.CASES))
 def test_every_case_on_every_leg(name, leg, dev):
-    _run(name, dev, sumpool_wide=leg)
+    run_case(ac, name, dev, _check_plan, float_last_only=True, sumpool_wide=leg)
 
 
 @pytest.mark.parametrize('name', sorted(ac.CASES))
 def test_every_case_with_all_fusions(name, dev):
-    _run(name, dev, **ac.FUSE_ALL)
+    run_case(ac, name, dev, _check_plan, float_last_only=True, **ac.FUSE_ALL)
 
 
 @pytest.mark.parametrize('name', ['g_3s1p1_5x7', 'g_15s15_15x30'])
@@ -107,7 +90,7 @@ def test_profiled_run_times_the_pool_launch(dev):
 @pytest.mark.parametrize('k, s, pad, hw', [(2, 2, 0, (7, 9)), (3, 1, 1, (5, 7)), (4, 2, 2, (8, 10)), (15, 15, 0, (15, 30)), (6, 6, 0, (6, 6))])
 def test_torch_op_on_a_device_tensor(k, s, pad, hw, dev):
     x = synth.rand_uniform_int(21, f'op{k}{s}{pad}', (3, 40) + hw, -2 ** 27, 2 ** 27).astype(np.int32)
-    want, _ = ac.sumpool_ref(x, 0, k, s, pad)
+    want, _ = ref_ops.sumpool_ref(x, 0, k, s, pad)
     got = torch.ops.f8net.avgpool2d_sum(torch.from_numpy(x).to(dev), k, s, pad)
     assert got.dtype == torch.int32 and tuple(got.shape) == want.shape
     np.testing.assert_array_equal(got.cpu().numpy(), want)
@@ -122,7 +105,7 @@ def test_module_carries_the_output_fraclen(dev):
         assert m.shiftnum == sh
         y = m(xt)
         assert y.output_fraclen == 5 + sh
-        np.testing.assert_array_equal(y.cpu().numpy(), ac.sumpool_ref(x, 0, k, s, pad)[0])
+        np.testing.assert_array_equal(y.cpu().numpy(), ref_ops.sumpool_ref(x, 0, k, s, pad)[0])
 
 
 # ---- nets
@@ -130,7 +113,7 @@ def _check_graph(build, x, dev, option_sets=(None, ac.FUSE_ALL), pools=None):
     """build(g) -> output ids; records into a fresh net per option set, runs, compares every output with the graph's own reference."""
     xt = torch.from_numpy(x).to(dev)
     for options in option_sets:
-        g = ac._Graph(x, ac.X_FL)
+        g = RefGraph(x, ac.X_FL)
         outs = build(g, next(iter(g.v)))
         for k, v in (options or {}).items():
             g.net.set_option(k, v)
@@ -139,19 +122,17 @@ def _check_graph(build, x, dev, option_sets=(None, ac.FUSE_ALL), pools=None):
             assert [t for _, t, _ in ac.pool_lines(g.net)] == pools, g.net.describe()
         wants = [g.v[o][0] for o in outs]
         assert all(np.unique(w).size > 50 for w in wants)
-        for y, w in zip(_outputs(g.net.run(xt), x.shape[0], wants), wants):
-            np.testing.assert_array_equal(y, w, err_msg=f'{options}')
+        got = g.net.run(xt)
+        got = got if isinstance(got, tuple) else (got,)
+        assert len(got) == len(wants)
+        for y, w in zip(got, wants):
+            np.testing.assert_array_equal(y.cpu().numpy().reshape(w.shape), w, err_msg=f'{options}')
         g.net.check()
 
 
 def test_densenet_block_transition_block_imported_from_onnx(dev):
-    from f8net_amd.onnx_import import IntGraph, IntOp
     x = ac.net_input('densenet')
-    ig = IntGraph(input_signed=False)
-    ig.ops.append(IntOp('input', shape=x.shape[1:]))
-    g = ac.Recorder(x, ac.X_FL, ig)
-    (out,) = ac.net_densenet(g, 0)
-    ig.output, ig.output_float = g.ids[out], False
+    ig, g, out = record_int_graph(x, ac.X_FL, lambda g, x0: ac.net_densenet(g, x0)[0])
     back = onnx_import.import_graph(onnx_export.export_graph(ig))
     assert [(o.kernel, o.stride, o.pad, o.shift) for o in back.ops if o.kind == 'avgpool2d'] == [(2, 2, 0, 2)]
     want = g.v[out][0]
@@ -169,15 +150,6 @@ def test_small_nets(name, dev):
     """Inception-3a with its average-pool branch, a ResNet-D stride-2 opener (pooled shortcut -> 1x1 -> join), the DenseNet graph recorded directly."""
     build, _, pools = ac.NETS[name]
     _check_graph(build, ac.net_input(name), dev, pools=pools)
-
-
-def _tapped_graph(net, seen):
-    """An avgpool_cases._Graph that records into `net` and starts from the tapped tensors {block name: (values, fraclen)} of the oracle's walk."""
-    first = next(iter(seen.values()))
-    g = ac._Graph(first[0], first[1], record=False)
-    g.record, g.net = True, net
-    g.v = {net.tap_ids[k]: v for k, v in seen.items()}
-    return g
 
 
 @functools.lru_cache(maxsize=None)
@@ -203,7 +175,7 @@ def test_pool_of_a_block_output_inside_a_stage_chain_on_resnet50(dev):
     xt = torch.from_numpy(x).to(dev)
     for options in (None, ac.FUSE_ALL):
         net = record_net(spec, params, 64, options=options)
-        g = _tapped_graph(net, seen)
+        g = RefGraph.on(net, {net.tap_ids[k]: v for k, v in seen.items()})
         pl = g.avgpool(net.tap_ids[name], 2, label='pool')
         assert net.output(pl, as_float=False) == 1
         for k, v in (options or {}).items():
@@ -228,7 +200,7 @@ def test_psp_head_on_resnet50_os8(dev):
     xt = torch.from_numpy(x).to(dev)
     for options in (None, ac.FUSE_ALL):
         net = record_net(spec, params, 96, options=options)
-        g = _tapped_graph(net, seen)
+        g = RefGraph.on(net, {net.tap_ids[k]: v for k, v in seen.items()})
         t = net.tap_ids[last]
         bs = [t]
         for b, bins in enumerate((1, 2, 3, 6)):

@@ -10,6 +10,8 @@ import torch
 
 import chanmap_cases as cm
 from f8net_amd import onnx_export, onnx_import, ops
+from graph_cases import run_case
+from refgraph import RefGraph
 
 pytestmark = pytest.mark.gpu
 
@@ -20,44 +22,24 @@ def dev():
     return torch.device('cuda:0')
 
 
-def _outputs(got, n, wants):
-    got = got if isinstance(got, tuple) else (got,)
-    assert len(got) == len(wants)
-    return [y.cpu().numpy().reshape((n,) + w.shape[1:]) for y, w in zip(got, wants)]
-
-
-def _run(name, dev, **opts):
-    c = cm.CASES[name]
-    N = c['N']
-    ref, routs, _ = cm.reference(name)                             # over N + 1 images
-    wants = [ref.v[o][0] for o in routs]
-    x = cm.make_input(name, N + 1)
-    g, outs, _ = cm.plan(name, x, max_batch=N + 1, **opts)
-    assert [(t, k) for _, t, k in cm.lines(g.net)] == cm.expected(name, **opts), g.net.describe()
-    xt = torch.from_numpy(x).to(dev)
-    for n in (N, N - 1):
-        got = _outputs(g.net.run(xt[:n]), n, wants)
-        for k, (y, w) in enumerate(zip(got, wants)):
-            if c.get('as_float'):
-                w = w.astype(np.float32)
-            np.testing.assert_array_equal(y, w[:n], err_msg=f'{name} {opts} n={n} output {k}')
-    g.net.check()
+def _check_plan(net, name, opts):
+    assert [(t, k) for _, t, k in cm.lines(net)] == cm.expected(name, **opts), net.describe()
 
 
 @pytest.mark.parametrize('i8', [1, 0])
 @pytest.mark.parametrize('name', sorted(cm.CASES))
 def test_every_case_on_both_legs(name, i8, dev):
-    _run(name, dev, chanmap_i8=i8)
+    run_case(cm, name, dev, _check_plan, chanmap_i8=i8)
 
 
 @pytest.mark.parametrize('name', sorted(cm.CASES))
 def test_every_case_with_all_fusions(name, dev):
-    _run(name, dev, **cm.FUSE_ALL)
+    run_case(cm, name, dev, _check_plan, **cm.FUSE_ALL)
 
 
 @pytest.mark.parametrize('name', cm.FUSED)
 def test_fused_cases_as_two_launches(name, dev):
-    _run(name, dev, fuse_shuffle=0)
+    run_case(cm, name, dev, _check_plan, fuse_shuffle=0)
 
 
 @pytest.mark.parametrize('name', ['f_58_gap', 'sl_49_15'])
@@ -105,7 +87,7 @@ STAGE_I32 = [('concat_i32:', cm.C32), ('shuffle2_i32:', cm.K32)] + ([('slice_i32
 
 @pytest.fixture(scope='module')
 def stage_reference():
-    g = cm._Graph(cm.stage_input(), cm.X_FL, record=False)
+    g = RefGraph(cm.stage_input(), cm.X_FL, record=False)
     out, shuffles = cm.shufflenet_stage(g, 0)
     assert np.unique(g.v[out][0]).size > 10 and all(np.unique(g.v[s][0]).size > 100 for s in shuffles)
     return g.v[out][0]
@@ -115,7 +97,7 @@ def stage_reference():
 def test_shufflenet_v2_stage(leg, stage_reference, dev):
     """Every unit of the stage plans one concat+shuffle2_i8: launch (by hand: operands of 58 channels at offset 0 — the V = 2 instance)."""
     x = cm.stage_input()
-    g = cm._Graph(x, cm.X_FL)
+    g = RefGraph(x, cm.X_FL)
     out, _ = cm.shufflenet_stage(g, next(iter(g.v)))
     for k, v in {'i8': {}, 'i32': dict(chanmap_i8=0), 'all_fusions': cm.FUSE_ALL}[leg].items():
         g.net.set_option(k, v)

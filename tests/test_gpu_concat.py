@@ -10,7 +10,9 @@ import torch
 import concat_cases as cc
 from f8net_amd import onnx_export, onnx_import, synth, topology
 from f8net_amd.net import build_net, record_net
+from graph_cases import run_case
 from oracle import oracle
+from refgraph import RefGraph
 
 pytestmark = pytest.mark.gpu
 
@@ -21,42 +23,21 @@ def dev():
     return torch.device('cuda:0')
 
 
-def _outputs(got, n, wants):
-    got = got if isinstance(got, tuple) else (got,)
-    assert len(got) == len(wants)
-    return [y.cpu().numpy().reshape((n,) + w.shape[1:]) for y, w in zip(got, wants)]
-
-
-def _run(name, dev, **opts):
+def _check_plan(net, name, opts):
     c = cc.CASES[name]
-    N = c['N']
-    ref, routs, _ = cc.reference(name)                             # over N + 1 images
-    wants = [ref.v[o][0] for o in routs]
-    x = cc.make_input(name, N + 1)
-    g, outs, _ = cc.plan(name, x, max_batch=N + 1, **opts)
     i8 = opts.get('concat_i8', 1)
-    assert all(tok == (c['mode'] if i8 else cc.I32) for _, tok, _ in cc.concat_lines(g.net)), g.net.describe()
-    xt = torch.from_numpy(x).to(dev)
-    for n in (N, N - 1):
-        if n < 1:
-            continue
-        got = _outputs(g.net.run(xt[:n]), n, wants)
-        for k, (y, w) in enumerate(zip(got, wants)):
-            if c.get('as_float'):
-                w = w.astype(np.float32)
-            np.testing.assert_array_equal(y, w[:n], err_msg=f'{name} {opts} n={n} output {k}')
-    g.net.check()
+    assert all(tok == (c['mode'] if i8 else cc.I32) for _, tok, _ in cc.concat_lines(net)), net.describe()
 
 
 @pytest.mark.parametrize('i8', [1, 0])
 @pytest.mark.parametrize('name', sorted(cc.CASES))
 def test_every_case_on_both_legs(name, i8, dev):
-    _run(name, dev, concat_i8=i8)
+    run_case(cc, name, dev, _check_plan, concat_i8=i8)
 
 
 @pytest.mark.parametrize('name', sorted(cc.CASES))
 def test_every_case_with_all_fusions(name, dev):
-    _run(name, dev, **cc.FUSE_ALL)
+    run_case(cc, name, dev, _check_plan, **cc.FUSE_ALL)
 
 
 @pytest.mark.parametrize('name', ['straddle', 'nested'])
@@ -113,9 +94,8 @@ def test_aspp_head_on_resnet50_os16(dev):
         plain = build_net(spec, params, 2, hw=96, options=options).run(xt).cpu().numpy()
         np.testing.assert_array_equal(plain, logits, err_msg=str(options))
         net = record_net(spec, params, 96, options=options)
-        g = cc._Graph(seen[last][0], seen[last][1], record=False)
-        g.record, g.net, t = True, net, net.tap_ids[last]
-        g.v = {t: seen[last]}
+        t = net.tap_ids[last]
+        g = RefGraph.on(net, {t: seen[last]})
         proj, cat = cc.aspp_head(g, t)
         assert net.output(proj, as_float=False) == 1
         for k, v in (options or {}).items():

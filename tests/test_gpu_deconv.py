@@ -8,9 +8,12 @@ import pytest
 import torch
 
 import deconv_cases as dc
+import ref_ops
 from f8net_amd import onnx_export, onnx_import, ops, synth, topology
 from f8net_amd.net import record_net
+from graph_cases import run_case
 from oracle import oracle
+from refgraph import RefGraph
 
 pytestmark = pytest.mark.gpu
 
@@ -21,28 +24,13 @@ def dev():
     return torch.device('cuda:0')
 
 
-def _outputs(got, n, wants):
-    got = got if isinstance(got, tuple) else (got,)
-    assert len(got) == len(wants)
-    return [y.cpu().numpy().reshape((n,) + w.shape[1:]) for y, w in zip(got, wants)]
+def _check_plan(net, name, opts):
+    dc.check_lines(dc.CASES[name], dc.deconv_lines(net), net.describe())
 
 
 def _run(name, dev, **opts):
-    c = dc.CASES[name]
-    N = c['N']
-    ref, routs, _ = dc.reference(name)
-    wants = [ref.v[o][0] for o in routs]
-    x = dc.make_input(name)
-    g, outs, _ = dc.plan(name, x, **opts)
-    dc.check_lines(c, dc.deconv_lines(g.net), g.net.describe())
-    xt = torch.from_numpy(x).to(dev)
-    for n in (N, N - 1):
-        got = _outputs(g.net.run(xt[:n]), n, wants)
-        for k, (y, w) in enumerate(zip(got, wants)):
-            if c.get('as_float') and k == len(wants) - 1:
-                w = w.astype(np.float32)
-            np.testing.assert_array_equal(y, w[:n], err_msg=f'{name} {opts} n={n} output {k}')
-    g.net.check()
+    """(the reference runs over N images and the handle is planned for N: no spare image)"""
+    run_case(dc, name, dev, _check_plan, spare_image=False, float_last_only=True, **opts)
 
 
 @pytest.mark.parametrize('name', sorted(dc.CASES))
@@ -124,18 +112,9 @@ def test_op_level_drop_in(k, s, pad, op, cin, cout, hw, signed, dev):
     m.input_fraclen.fill_(4)
     m = m.to(dev)
     got = m(torch.from_numpy(x).to(dev))
-    want = dc.deconv_ref(x, w, b, s, pad, op)
+    want = ref_ops.deconv_ref(x, w, b, s, pad, op)
     assert tuple(got.shape) == want.shape
     np.testing.assert_array_equal(got.cpu().numpy(), want)
-
-
-def _tapped_graph(net, seen):
-    """A deconv_cases._Graph that records into `net` and starts from the tapped tensors {block name: (values, fraclen)} of the oracle's walk."""
-    first = next(iter(seen.values()))
-    g = dc._Graph(first[0], first[1], record=False)
-    g.record, g.net = True, net
-    g.v = {net.tap_ids[k]: v for k, v in seen.items()}
-    return g
 
 
 def _up(g, t, k, s, pad, cout, seed, label, relu=True, in_fl=4):
@@ -151,7 +130,7 @@ def test_small_unet(dev):
     concatenated with enc1 -> 3x3 -> deconv 2x2 / 2 to 16 channels, concatenated with a 3x3 of the input -> 1x1 to 5 classes: the output."""
     x = synth.rand_uniform_int(7, 'unetx', (2, 8, 64, 64), 0, 255).astype(np.int32)
     for options in (None, dc.FUSE_ALL):
-        g = dc._Graph(x, dc.X_FL)
+        g = RefGraph(x, dc.X_FL)
         x0 = next(iter(g.v))
 
         def conv3(t, k, cout, stride, first=False, w_fl=5):
@@ -195,7 +174,7 @@ def test_fcn_head_on_tapped_resnet18_stages(dev):
     xt = torch.from_numpy(x).to(dev)
     for options in (None, dc.FUSE_ALL):
         net = record_net(spec, params, 64, options=options)
-        g = _tapped_graph(net, seen)
+        g = RefGraph.on(net, {net.tap_ids[k]: v for k, v in seen.items()})
         # score convs first, so that each join's later producer is the transposed conv: the joins stay add: launches
         sc = [dc.producer(g, net.tap_ids[n], k, 21, 9, w_fl=6, relu=False, in_fl=4, quant_input=True) for k, n in enumerate(names)]      # fraclen 10
         up = _up(g, sc[2], 4, 2, 1, 21, 90, 'up32', relu=False, in_fl=4)

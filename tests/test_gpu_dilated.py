@@ -11,6 +11,8 @@ import dil_cases
 from f8net_amd import onnx_export, synth, topology
 from f8net_amd.net import build_net
 from oracle import oracle
+from ref_ops import stuffed
+from refgraph import graph_forward
 
 pytestmark = pytest.mark.gpu
 
@@ -142,7 +144,7 @@ def test_op_level_conv2d(dev, C, G, stride, d, pad):
     conv.weight_fraclen.fill_(6)
     xt = torch.from_numpy(x).to(dev)
     got = conv(xt).cpu().numpy()
-    want = oracle.conv2d(x, dil_cases.stuffed(w, d), b, stride, pad, G)
+    want = oracle.conv2d(x, stuffed(w, d), b, stride, pad, G)
     assert got.shape == want.shape
     np.testing.assert_array_equal(got, want)
     meta = torch.ops.f8net.conv2d(xt.to('meta'), conv.weight.to('meta'), conv.bias.to('meta'), stride, pad, G, 6, 5, False, d)
@@ -160,10 +162,10 @@ def _net_case(arch, dev, hw=64, seed=31):
 
 
 def test_an_intgraph_with_dilated_convs(dev):
-    """mobilenet_v2_os16 recorded as an IntGraph (what the ONNX importer hands to build_net), against graph_forward on the stuffed twin."""
+    """mobilenet_v2_os16 recorded as an IntGraph (what the ONNX importer hands to build_net), against refgraph.graph_forward."""
     spec, params, x, _ = _net_case('mobilenet_v2_os16', dev)
     ig = onnx_export.graph_from_params(spec, params, 64)
-    want = oracle.graph_forward(dil_cases.stuffed_graph(ig), x)
+    want = graph_forward(ig, x)
     assert np.unique(want).size > 8
     net = ig.build_net(2)
     assert 'dwconv3x3s1d2:' in net.describe()

@@ -8,7 +8,9 @@ import pytest
 import torch
 
 from f8net_amd import synth, topology
+from ir_cases import _b, _w
 from oracle import oracle
+from refgraph import RefGraph
 
 pytestmark = pytest.mark.gpu
 
@@ -27,37 +29,6 @@ def _dws_symbols(net):
     return [net.launch_kernel(i) for i in range(net.num_launches) if net.launch_info(i, 1)[0].startswith('fused_dws:')]
 
 
-def _w(seed, shape, sig):
-    return np.clip(synth.rand_normal_int(seed, f'w{shape}', shape, sig), -127, 127).astype(np.int32)
-
-
-def _b(seed, n, sig):
-    return np.clip(synth.rand_normal_int(seed, f'b{n}', (n,), sig), -2 ** 30, 2 ** 30).astype(np.int32)
-
-
-class _Graph:
-    """Records each op into an F8Net and evaluates it with the oracle's op-level functions (value, fraclen) at the same time."""
-
-    def __init__(self, x, x_fl):
-        from f8net_amd.net import F8Net
-        self.net = F8Net()
-        self.v = {self.net.input(x.shape[1], x.shape[2], x.shape[3], x_fl): (x, x_fl)}
-
-    def conv(self, t, w, b, *, stride=1, pad, groups, weight_fl, input_fl, input_signed, relu):
-        o = self.net.conv(t, w, b, stride=stride, pad=pad, groups=groups, weight_fl=weight_fl, input_fl=input_fl, input_signed=input_signed,
-                          quant_input=True, relu=relu)
-        x, fl = self.v[t]
-        y = oracle.conv2d(oracle.requant(x, input_fl, fl, input_signed), w, b, stride, pad, groups)
-        self.v[o] = (oracle.relu(y) if relu else y, input_fl + weight_fl)
-        return o
-
-    def add(self, a, b, relu=False):
-        o = self.net.add(a, b, relu=relu)
-        y, fl = oracle.add_align(self.v[a][0], self.v[b][0], self.v[a][1], self.v[b][1])
-        self.v[o] = (oracle.relu(y) if relu else y, fl)
-        return o
-
-
 # A block: cin, cout, stride; dw_in_fl (the depthwise conv's unsigned input format), dw_w_fl / pw_in_fl: the mid requantisation shifts right by
 # dw_in_fl + dw_w_fl - pw_in_fl; pw_w_fl and the readers' formats: the output shifts by pw_in_fl + pw_w_fl - reader fl.  *_sig / *_bsig: weight
 # and bias spreads (small weights for a shift of 1, large biases for a shift of 16: the values stay inside 8 bits without saturating everywhere).
@@ -72,7 +43,7 @@ def _blk(cin, cout, stride=1, **kw):
 
 def _graph(blocks, readers, x):
     """input -> pre 1x1 (ReLU) -> blocks -> one 1x1 reader per (fl, signed) of `readers`, summed: the int32 net output."""
-    g = _Graph(x, 6)
+    g = RefGraph(x, 6)
     t = next(iter(g.v))
     c0 = blocks[0]['cin']
     t = g.conv(t, _w(1, (c0, c0, 1, 1), 12.0 * (32.0 / c0) ** 0.5), _b(2, c0, 300.0), pad=0, groups=1, weight_fl=blocks[0]['dw_in_fl'], input_fl=6,

@@ -12,6 +12,7 @@ from f8net_amd import synth, topology
 from f8net_amd.net import build_net
 from f8net_amd.onnx_import import IntGraph, IntOp
 from oracle import oracle
+from ref_ops import grouped_conv2d
 
 pytestmark = pytest.mark.gpu
 
@@ -138,7 +139,7 @@ def test_op_level_conv2d(dev, C, G, stride):
     conv.input_fraclen.fill_(5)
     conv.weight_fraclen.fill_(6)
     got = conv(torch.from_numpy(x).to(dev)).cpu().numpy()
-    want = gconv_cases.grouped_conv2d(x, w, b, stride, 1, G)
+    want = grouped_conv2d(x, w, b, stride, 1, G)
     assert got.shape == want.shape
     np.testing.assert_array_equal(got, want)
 

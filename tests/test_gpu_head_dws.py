@@ -8,7 +8,9 @@ import pytest
 import torch
 
 from f8net_amd import synth, topology
+from ir_cases import _b, _w
 from oracle import oracle
+from refgraph import RefGraph
 
 pytestmark = pytest.mark.gpu
 
@@ -25,37 +27,6 @@ def _fused(net):
     return [i for i in range(net.num_launches) if net.launch_info(i, 1)[0].startswith(FUSED)]
 
 
-def _w(seed, shape, sig):
-    return np.clip(synth.rand_normal_int(seed, f'w{shape}', shape, sig), -127, 127).astype(np.int32)
-
-
-def _b(seed, n, sig):
-    return np.clip(synth.rand_normal_int(seed, f'b{n}', (n,), sig), -2 ** 30, 2 ** 30).astype(np.int32)
-
-
-class _Graph:
-    """Records each op into an F8Net and evaluates it with the oracle's op-level functions (value, fraclen) at the same time."""
-
-    def __init__(self, x, x_fl):
-        from f8net_amd.net import F8Net
-        self.net = F8Net()
-        self.v = {self.net.input(x.shape[1], x.shape[2], x.shape[3], x_fl): (x, x_fl)}
-
-    def conv(self, t, w, b, *, stride=1, pad, groups, weight_fl, input_fl, input_signed, relu):
-        o = self.net.conv(t, w, b, stride=stride, pad=pad, groups=groups, weight_fl=weight_fl, input_fl=input_fl, input_signed=input_signed,
-                          quant_input=True, relu=relu)
-        x, fl = self.v[t]
-        y = oracle.conv2d(oracle.requant(x, input_fl, fl, input_signed), w, b, stride, pad, groups)
-        self.v[o] = (oracle.relu(y) if relu else y, input_fl + weight_fl)
-        return o
-
-    def add(self, a, b, relu=False):
-        o = self.net.add(a, b, relu=relu)
-        y, fl = oracle.add_align(self.v[a][0], self.v[b][0], self.v[a][1], self.v[b][1])
-        self.v[o] = (oracle.relu(y) if relu else y, fl)
-        return o
-
-
 # Formats: the input is fraclen 8 unsigned (pixel values 0 .. 255) or fraclen 6 signed; head weights fraclen 6 -> the depthwise conv's unsigned
 # fraclen-6 input is a right shift by 8 (6); depthwise weights fraclen 6 -> the 1x1's unsigned fraclen-6 input: a shift by 6; 1x1 weights fraclen 6
 # -> a reader of fraclen f shifts by 12 - f.  Weight and bias spreads keep the 8-bit values spread over their range without saturating everywhere.
@@ -63,7 +34,7 @@ def _graph(x, x_signed, cout, relu, readers, big):
     """raw input -> 3x3 / 2 head conv (ReLU) -> depthwise 3x3 (ReLU) -> 1x1 [ReLU] -> one 32-output 1x1 reader per (fl, signed), summed (int32)."""
     cin = x.shape[1]
     x_fl = 6 if x_signed else 8
-    g = _Graph(x, x_fl)
+    g = RefGraph(x, x_fl)
     t = next(iter(g.v))
     bd, bp = _b(40, 32, 2.0 ** 9), _b(60, cout, 2.0 ** 11)
     if big:                                                         # next to 2^31: `v + 2^(n-1)` wraps in the reference's int32 arithmetic

@@ -7,7 +7,9 @@ import pytest
 import torch
 
 from f8net_amd import synth, topology
+from ir_cases import _w
 from oracle import oracle
+from refgraph import RefGraph
 
 pytestmark = pytest.mark.gpu
 
@@ -116,40 +118,13 @@ def test_bench_schedule_and_ragged_batches(rq, dev):
 
 
 # ---- F8Net graphs of chained blocks in corner formats, against the CPU oracle (op by op) and the same graph planned without the chain
-def _w(seed, shape, sig):
-    return np.clip(synth.rand_normal_int(seed, f'w{shape}', shape, sig), -127, 127).astype(np.int32)
-
-
-class _Graph:
-    """Records each op into an F8Net and evaluates it with the oracle's op-level functions (value, fraclen) at the same time."""
-
-    def __init__(self, x, x_fl):
-        from f8net_amd.net import F8Net
-        self.net = F8Net()
-        self.v = {self.net.input(x.shape[1], x.shape[2], x.shape[3], x_fl): (x, x_fl)}
-
-    def conv(self, t, w, b, *, pad, groups, weight_fl, input_fl, input_signed, relu):
-        o = self.net.conv(t, w, b, stride=1, pad=pad, groups=groups, weight_fl=weight_fl, input_fl=input_fl, input_signed=input_signed,
-                          quant_input=True, relu=relu)
-        x, fl = self.v[t]
-        y = oracle.conv2d(oracle.requant(x, input_fl, fl, input_signed), w, b, 1, pad, groups)
-        self.v[o] = (oracle.relu(y) if relu else y, input_fl + weight_fl)
-        return o
-
-    def add(self, a, b, relu=False):
-        o = self.net.add(a, b, relu=relu)
-        y, fl = oracle.add_align(self.v[a][0], self.v[b][0], self.v[a][1], self.v[b][1])
-        self.v[o] = (oracle.relu(y) if relu else y, fl)
-        return o
-
-
 def _block_graph(case, x):
     """case: (blocks, x_fl, tail_fls).  blocks: dicts cin, cout, E, in_fl / in_signed (expand input), w_fl (expand weights), dw_in_fl, dw_w_fl,
     pw_in_fl, pw_w_fl (default w_fl), res, join_relu, bias_big (expand biases next to 2^31), pw_sig (project weights), zero_ch {channel: project
     bias of an output channel whose project weights are zero}.  tail_fls: 1x1 convs that read the last block's output as int8 in these formats
     (a 32-channel output is also joined as int32)."""
     blocks, x_fl, tail_fls = case
-    g = _Graph(x, x_fl)
+    g = RefGraph(x, x_fl)
     t = next(iter(g.v))
     c0 = blocks[0]['cin']
     t = g.conv(t, _w(1, (c0, c0, 1, 1), 12.0), synth.rand_normal_int(2, 'pb', (c0,), 300.0).astype(np.int32), pad=0, groups=1,

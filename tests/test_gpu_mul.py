@@ -8,7 +8,11 @@ import pytest
 import torch
 
 import mul_cases as mc
+import ref_ops
 from f8net_amd import ops  # (registers torch.ops.f8net)
+from graph_cases import run_case, se_branch_on_resnet50_stage
+from ir_cases import _b, _w
+from refgraph import RefGraph
 
 pytestmark = pytest.mark.gpu
 
@@ -19,41 +23,23 @@ def dev():
     return torch.device('cuda:0')
 
 
-def _outputs(got, n, wants):
-    got = got if isinstance(got, tuple) else (got,)
-    assert len(got) == len(wants)
-    return [y.cpu().numpy().reshape((n,) + w.shape[1:]) for y, w in zip(got, wants)]
-
-
-def _run(name, dev, **opts):
-    c = mc.CASES[name]
-    N = c['N']
-    ref, routs, _ = mc.reference(name)                             # over N + 1 images
-    wants = [ref.v[o][0] for o in routs]
-    x = mc.make_input(name, N + 1)
-    g, outs, _ = mc.plan(name, x, max_batch=N + 1, **opts)
-    assert [(t, k) for _, t, k in mc.lines(g.net)] == mc.expected(name, **opts), g.net.describe()
-    xt = torch.from_numpy(x).to(dev)
-    for n in (N, N - 1):
-        got = _outputs(g.net.run(xt[:n]), n, wants)
-        for k, (y, w) in enumerate(zip(got, wants)):
-            np.testing.assert_array_equal(y, w[:n], err_msg=f'{name} {opts} n={n} output {k}')
-    g.net.check()
+def _check_plan(net, name, opts):
+    assert [(t, k) for _, t, k in mc.lines(net)] == mc.expected(name, **opts), net.describe()
 
 
 @pytest.mark.parametrize('name', sorted(mc.CASES))
 def test_every_case_on_the_default_plan(name, dev):
-    _run(name, dev)
+    run_case(mc, name, dev, _check_plan)
 
 
 @pytest.mark.parametrize('name', sorted(mc.CASES))
 def test_every_case_with_all_fusions(name, dev):
-    _run(name, dev, **mc.FUSE_ALL)
+    run_case(mc, name, dev, _check_plan, **mc.FUSE_ALL)
 
 
 @pytest.mark.parametrize('name', mc.FUSED)
 def test_fused_gates_as_two_launches(name, dev):
-    _run(name, dev, fuse_hgate=0)
+    run_case(mc, name, dev, _check_plan, fuse_hgate=0)
 
 
 @pytest.mark.parametrize('name', ['se_20', 'hsw_64'])
@@ -86,7 +72,7 @@ LEGS = {'default': {}, 'all_fusions': mc.FUSE_ALL, 'two_launches': dict(fuse_hga
 
 @pytest.fixture(scope='module')
 def mbv3_reference():
-    g = mc._Graph(mc.mbv3_input(), mc.X_FL, record=False)
+    g = RefGraph(mc.mbv3_input(), mc.X_FL, record=False)
     out, ops = mc.mbv3_block(g, 0)
     assert np.unique(g.v[out][0]).size > 100 and all(np.unique(g.v[t][0]).size > 20 for t in ops)
     return g.v[out][0]
@@ -97,7 +83,7 @@ def test_mobilenet_v3_block(leg, mbv3_reference, dev):
     """1x1 expand + hard-swish, depthwise 5x5 + hard-swish, SE with a hard-sigmoid gate, 1x1 project, join: three fused gate launches by hand
     (mc.MBV3_TOKENS), six launches with fuse_hgate = 0."""
     x = mc.mbv3_input()
-    g = mc._Graph(x, mc.X_FL)
+    g = RefGraph(x, mc.X_FL)
     mc.mbv3_block(g, next(iter(g.v)))
     for k, v in LEGS[leg].items():
         g.net.set_option(k, v)
@@ -127,40 +113,11 @@ def test_se_scale_of_a_block_output_inside_a_stage_chain_on_resnet50(dev):
     """ResNet-50 at 64 x 64: stage_1_layer_1's output (512 x 8 x 8) sits in the middle of what the stage chain runs as one launch.  An SE branch with a
     hard-sigmoid gate reads it — avgpool_sum, linear, hard gate, channel gate: the scaled map is output 1 — so the launch is cut there.  The logits
     stay the plain net's."""
-    import dil_cases
-    from f8net_amd import synth, topology
-    from f8net_amd.net import record_net
-    from ir_cases import _b, _w
-    from oracle import oracle
-    name = 'stage_1_layer_1'
-    spec = topology.get('resnet50')
-    params = synth.make_params(spec, seed=17)
-    x, x_fl = synth.make_input(spec, params, 2, 64, seed=3)
-    seen = {}
-    tspec, tparams = dil_cases.stuffed_twin(spec, params)
-    logits = oracle.net_forward(tspec, tparams, x, x_fl, tap=lambda k, v, fl: seen.__setitem__(k, (v.copy(), fl)) if k == name else None)
-    assert seen[name][0].shape[1:] == (512, 8, 8)
-    xt = torch.from_numpy(x).to(dev)
-    for options in (None, mc.FUSE_ALL):
-        net = record_net(spec, params, 64, options=options)
-        g = mc._Graph(seen[name][0], seen[name][1], record=False)
-        g.record, g.net = True, net
-        src = net.tap_ids[name]
-        g.v = {src: seen[name]}
-        assert seen[name][1] == 10                                 # the map at fraclen 10, values up to 2^20: read at unsigned fraclen 0; its pool at fraclen 16
+    def branch(g, src):                                            # the map is read at unsigned fraclen 0; its pool is at fraclen 16
         v = g.linear(g.avgpool_sum(src), _w(71, (512, 512), 3.0), _b(72, 512, 2.0 ** 11), weight_fl=12, input_fl=0, input_signed=False, label='se.fc')
-        s = g.mul(src, g.hard_gate(v), a_fl=0, a_signed=False, b_fl=5, label='se.scale')
-        assert net.output(s, as_float=False) == 1
-        for k, val in (options or {}).items():
-            net.set_option(k, val)
-        net.finalize(2)
-        assert [(t, k) for _, t, k in mc.lines(net)] == [('hgate+chmul_i32:', mc.W11)], net.describe()
-        want = g.v[s][0]
-        assert np.unique(want).size > 100 and np.unique(g.v[v][0]).size > 100
-        got, scaled = net.run(xt)
-        net.check()
-        np.testing.assert_array_equal(got.cpu().numpy(), logits, err_msg=f'logits {options}')
-        np.testing.assert_array_equal(scaled.cpu().numpy().reshape(want.shape), want, err_msg=f'scaled map {options}')
+        assert np.unique(g.v[v][0]).size > 100
+        return g.mul(src, g.hard_gate(v), a_fl=0, a_signed=False, b_fl=5, label='se.scale')
+    se_branch_on_resnet50_stage(dev, branch, ('hgate+chmul_i32:', mc.W11), lines=mc.lines)
 
 
 # ---- torch
@@ -180,8 +137,8 @@ def test_torch_mul_q_against_the_reference(C, H, W, bcast, gate, a, b, relu, dev
     fa, fb = 13, 12
     xa = _rand(C * 7 + H, (3, C, H, W), -2 ** 16, 2 ** 16, dev)
     xb = _rand(C * 11 + W, (3, C, 1, 1) if bcast else (3, C, H, W), -2 ** 15, 2 ** 15, dev)
-    b_ref = mc.hard_gate_ref(xb.cpu().numpy(), fb) if gate else xb.cpu().numpy()
-    want, fl = mc.mul_ref(xa.cpu().numpy(), fa, b_ref, fb, a_fl=a[0], a_signed=a[1], b_fl=b[0], b_signed=b[1], relu=relu)
+    b_ref = ref_ops.hard_gate_ref(xb.cpu().numpy(), fb) if gate else xb.cpu().numpy()
+    want, fl = ref_ops.mul_ref(xa.cpu().numpy(), fa, b_ref, fb, a_fl=a[0], a_signed=a[1], b_fl=b[0], b_signed=b[1], relu=relu)
     got = torch.ops.f8net.mul_q(xa, xb, fa, fb, a[0], a[1], b[0], b[1], gate, relu)
     assert got.dtype == torch.int32 and got.shape == xa.shape and np.unique(want).size > 50
     np.testing.assert_array_equal(got.cpu().numpy(), want)
@@ -193,13 +150,13 @@ def test_hard_swish_and_channel_gate_modules(dev):
     x = _rand(5, (3, 48, 7, 7), -6 * 2 ** fl, 6 * 2 ** fl, dev)
     x.output_fraclen = fl
     y = ops.F8HardSwish(x_fl=4, x_signed=True, g_fl=5)(x)
-    want, out_fl = mc.mul_ref(x.cpu().numpy(), fl, mc.hard_gate_ref(x.cpu().numpy(), fl), fl, a_fl=4, a_signed=True, b_fl=5, b_signed=False)
+    want, out_fl = ref_ops.mul_ref(x.cpu().numpy(), fl, ref_ops.hard_gate_ref(x.cpu().numpy(), fl), fl, a_fl=4, a_signed=True, b_fl=5, b_signed=False)
     np.testing.assert_array_equal(y.cpu().numpy(), want)
     assert y.output_fraclen == out_fl == 9
     s = _rand(6, (3, 48), -5 * 2 ** 9, 5 * 2 ** 9, dev)
     s.output_fraclen = 9
     z = ops.F8ChannelGate(x_fl=4, x_signed=True, g_fl=5)(x, s)
-    gate = mc.hard_gate_ref(s.cpu().numpy().reshape(3, 48, 1, 1), 9)
-    want, out_fl = mc.mul_ref(x.cpu().numpy(), fl, gate, 9, a_fl=4, a_signed=True, b_fl=5, b_signed=False)
+    gate = ref_ops.hard_gate_ref(s.cpu().numpy().reshape(3, 48, 1, 1), 9)
+    want, out_fl = ref_ops.mul_ref(x.cpu().numpy(), fl, gate, 9, a_fl=4, a_signed=True, b_fl=5, b_signed=False)
     np.testing.assert_array_equal(z.cpu().numpy(), want)
     assert z.output_fraclen == out_fl

@@ -15,6 +15,7 @@ from f8net_amd.net import F8Net, build_net
 from oracle import oracle
 
 import outputs_cases as oc
+from refgraph import RefGraph
 
 
 @pytest.fixture(scope='module')
@@ -80,56 +81,22 @@ def test_tap_kernel_corners(dev, side, N, C, as_float, tap_tiled):
 
 
 # ------------------------------------------------------------------------------------------ several taps at once
-class _Graph:
-    """Records each op into an F8Net and evaluates it with the oracle's op-level functions (value, fraclen) at the same time."""
-
-    def __init__(self, x, x_fl):
-        self.net = F8Net()
-        self.v = {self.net.input(x.shape[1], x.shape[2], x.shape[3], x_fl): (x, x_fl)}
-
-    def conv(self, t, w, b, *, pad, weight_fl, input_fl, input_signed, relu):
-        o = self.net.conv(t, w, b, stride=1, pad=pad, groups=1, weight_fl=weight_fl, input_fl=input_fl, input_signed=input_signed, quant_input=True, relu=relu)
-        x, fl = self.v[t]
-        y = oracle.conv2d(oracle.requant(x, input_fl, fl, input_signed), w, b, 1, pad, 1)
-        self.v[o] = (oracle.relu(y) if relu else y, input_fl + weight_fl)
-        return o
-
-    def add(self, a, b, relu):
-        o = self.net.add(a, b, relu=relu)
-        y, fl = oracle.add_align(self.v[a][0], self.v[b][0], self.v[a][1], self.v[b][1])
-        self.v[o] = (oracle.relu(y) if relu else y, fl)
-        return o
-
-    def avgpool(self, t):
-        o = self.net.avgpool_sum(t, 6)
-        x, fl = self.v[t]
-        self.v[o] = (oracle.avgpool_sum(x)[:, :, None, None], fl + 6)
-        return o
-
-    def linear(self, t, w, b, *, weight_fl, input_fl):
-        o = self.net.linear(t, w, b, weight_fl=weight_fl, input_fl=input_fl, input_signed=False)
-        x, fl = self.v[t]
-        y = oracle.linear(oracle.requant(x.reshape(x.shape[0], -1), input_fl, fl, False), w, b)
-        self.v[o] = (y[:, :, None, None], input_fl + weight_fl)
-        return o
-
-
 def _residual_net(x, taps):
     """input -> 3x3 conv, ReLU -> two residual blocks (3x3, ReLU, 1x1, join, ReLU) -> average pool -> linear = output 0 (int32);
     taps: indices into [first block's 3x3 conv, second block's join, pooled vector]."""
     C = 64
     w = lambda k, shape, sig: np.clip(synth.rand_normal_int(20 + k, f'rw{k}', shape, sig), -127, 127).astype(np.int32)
     b = lambda k, n, sig: synth.rand_normal_int(40 + k, f'rb{k}', (n,), sig).astype(np.int32)
-    g = _Graph(x, 6)
-    t = g.conv(next(iter(g.v)), w(0, (C, x.shape[1], 3, 3), 20.0), b(0, C, 2.0 ** 10), pad=1, weight_fl=6, input_fl=6, input_signed=True, relu=True)
+    g = RefGraph(x, 6)
+    t = g.conv(next(iter(g.v)), w(0, (C, x.shape[1], 3, 3), 20.0), b(0, C, 2.0 ** 10), pad=1, groups=1, weight_fl=6, input_fl=6, input_signed=True, relu=True)
     cand = []
     for k in range(2):
-        a = g.conv(t, w(1 + 2 * k, (C, C, 3, 3), 8.0), b(1 + 2 * k, C, 2.0 ** 10), pad=1, weight_fl=6, input_fl=4, input_signed=False, relu=True)
-        p = g.conv(a, w(2 + 2 * k, (C, C, 1, 1), 12.0), b(2 + 2 * k, C, 2.0 ** 10), pad=0, weight_fl=7, input_fl=5, input_signed=False, relu=False)
+        a = g.conv(t, w(1 + 2 * k, (C, C, 3, 3), 8.0), b(1 + 2 * k, C, 2.0 ** 10), pad=1, groups=1, weight_fl=6, input_fl=4, input_signed=False, relu=True)
+        p = g.conv(a, w(2 + 2 * k, (C, C, 1, 1), 12.0), b(2 + 2 * k, C, 2.0 ** 10), pad=0, groups=1, weight_fl=7, input_fl=5, input_signed=False, relu=False)
         t = g.add(p, t, relu=True)
         cand.append((a, t))
-    pooled = g.avgpool(t)
-    out = g.linear(pooled, w(9, (10, C), 30.0), b(9, 10, 2.0 ** 12), weight_fl=6, input_fl=3)
+    pooled = g.avgpool_sum(t)
+    out = g.linear(pooled, w(9, (10, C), 30.0), b(9, 10, 2.0 ** 12), weight_fl=6, input_fl=3, input_signed=False)
     g.net.output(out, as_float=False)
     ids = [cand[0][0], cand[1][1], pooled]
     for k in taps:

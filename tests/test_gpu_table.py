@@ -7,8 +7,12 @@ import numpy as np
 import pytest
 import torch
 
+import ref_ops
 import table_cases as tc
 from f8net_amd import ops, tables  # (ops registers torch.ops.f8net)
+from graph_cases import run_case, se_branch_on_resnet50_stage
+from ir_cases import _b, _w
+from refgraph import RefGraph
 
 pytestmark = pytest.mark.gpu
 
@@ -19,46 +23,28 @@ def dev():
     return torch.device('cuda:0')
 
 
-def _outputs(got, n, wants):
-    got = got if isinstance(got, tuple) else (got,)
-    assert len(got) == len(wants)
-    return [y.cpu().numpy().reshape((n,) + w.shape[1:]) for y, w in zip(got, wants)]
-
-
-def _run(name, dev, **opts):
-    c = tc.CASES[name]
-    N = c['N']
-    ref, routs, _ = tc.reference(name)                             # over N + 1 images
-    wants = [ref.v[o][0] for o in routs]
-    x = tc.make_input(name, N + 1)
-    g, outs, _ = tc.plan(name, x, max_batch=N + 1, **opts)
-    assert [(t, k) for _, t, k in tc.lines(g.net)] == tc.expected(name, **opts), g.net.describe()
-    xt = torch.from_numpy(x).to(dev)
-    for n in (N, N - 1):
-        got = _outputs(g.net.run(xt[:n]), n, wants)
-        for k, (y, w) in enumerate(zip(got, wants)):
-            np.testing.assert_array_equal(y, w[:n], err_msg=f'{name} {opts} n={n} output {k}')
-    g.net.check()
+def _check_plan(net, name, opts):
+    assert [(t, k) for _, t, k in tc.lines(net)] == tc.expected(name, **opts), net.describe()
 
 
 @pytest.mark.parametrize('name', sorted(tc.CASES))
 def test_every_case_on_the_default_plan(name, dev):
-    _run(name, dev)
+    run_case(tc, name, dev, _check_plan)
 
 
 @pytest.mark.parametrize('name', sorted(tc.CASES))
 def test_every_case_with_all_fusions(name, dev):
-    _run(name, dev, **tc.FUSE_ALL)
+    run_case(tc, name, dev, _check_plan, **tc.FUSE_ALL)
 
 
 @pytest.mark.parametrize('name', sorted(tc.CASES))
 def test_every_case_in_int32_mode(name, dev):
-    _run(name, dev, table_i8=0)
+    run_case(tc, name, dev, _check_plan, table_i8=0)
 
 
 @pytest.mark.parametrize('name', tc.FUSED)
 def test_fused_gates_as_two_launches(name, dev):
-    _run(name, dev, fuse_table=0)
+    run_case(tc, name, dev, _check_plan, fuse_table=0)
 
 
 # ---- an EfficientNet MBConv block, a sigmoid SE block on a ResNet-50 stage
@@ -67,7 +53,7 @@ LEGS = {'default': {}, 'all_fusions': tc.FUSE_ALL, 'int32_mode': dict(table_i8=0
 
 @pytest.fixture(scope='module')
 def mbconv_reference():
-    g = tc._Graph(tc.mbconv_input(), tc.X_FL, record=False)
+    g = RefGraph(tc.mbconv_input(), tc.X_FL, record=False)
     out, ops = tc.mbconv_block(g, 0)
     assert np.unique(g.v[out][0]).size > 100 and all(np.unique(g.v[t][0]).size > 10 for t in ops)
     return g.v[out][0]
@@ -78,7 +64,7 @@ def test_efficientnet_mbconv_block(leg, mbconv_reference, dev):
     """1x1 expand + swish, depthwise 5x5 + swish, SE (pool, linear, swish, linear, sigmoid, channel gate), 1x1 project, join: the SE gate plans
     table+chmul_i8: (tc.MBCONV_TOKENS, by hand), two launches with fuse_table = 0."""
     x = tc.mbconv_input()
-    g = tc._Graph(x, tc.X_FL)
+    g = RefGraph(x, tc.X_FL)
     tc.mbconv_block(g, next(iter(g.v)))
     for k, v in LEGS[leg].items():
         g.net.set_option(k, v)
@@ -108,41 +94,12 @@ def test_sigmoid_se_branch_inside_a_stage_chain_on_resnet50(dev):
     """ResNet-50 at 64 x 64: stage_1_layer_1's output (512 x 8 x 8) sits in the middle of what the stage chain runs as one launch.  An SE branch with a
     sigmoid gate reads it — avgpool_sum, linear, sigmoid table, channel gate: the scaled map is output 1 — so the launch is cut there.  The logits stay
     the plain net's."""
-    import dil_cases
-    from f8net_amd import synth, tables, topology
-    from f8net_amd.net import record_net
-    from ir_cases import _b, _w
-    from oracle import oracle
-    name = 'stage_1_layer_1'
-    spec = topology.get('resnet50')
-    params = synth.make_params(spec, seed=17)
-    x, x_fl = synth.make_input(spec, params, 2, 64, seed=3)
-    seen = {}
-    tspec, tparams = dil_cases.stuffed_twin(spec, params)
-    logits = oracle.net_forward(tspec, tparams, x, x_fl, tap=lambda k, v, fl: seen.__setitem__(k, (v.copy(), fl)) if k == name else None)
-    assert seen[name][0].shape[1:] == (512, 8, 8)
-    xt = torch.from_numpy(x).to(dev)
-    for options in (None, tc.FUSE_ALL):
-        net = record_net(spec, params, 64, options=options)
-        g = tc._Graph(seen[name][0], seen[name][1], record=False)
-        g.record, g.net = True, net
-        src = net.tap_ids[name]
-        g.v = {src: seen[name]}
-        assert seen[name][1] == 10                                 # the map at fraclen 10, values up to 2^20: read at unsigned fraclen 0; its pool at fraclen 16
+    def branch(g, src):                                            # the map is read at unsigned fraclen 0; its pool is at fraclen 16
         v = g.linear(g.avgpool_sum(src), _w(71, (512, 512), 3.0), _b(72, 512, 2.0 ** 11), weight_fl=12, input_fl=0, input_signed=False, label='se.fc')
         gate = g.table(v, tables.sigmoid(4, True, 12), in_fl=4, in_signed=True, out_fl=12, label='se.gate')      # fraclen 12 read at +-8
-        s = g.mul(src, gate, a_fl=0, a_signed=False, b_fl=8, label='se.scale')
-        assert net.output(s, as_float=False) == 1
-        for k, val in (options or {}).items():
-            net.set_option(k, val)
-        net.finalize(2)
-        assert [(t, k) for _, t, k in tc.lines(net)] == [('table+chmul_i32:', tc.F32)], net.describe()
-        want = g.v[s][0]
-        assert np.unique(want).size > 100 and np.unique(g.v[gate][0]).size > 50
-        got, scaled = net.run(xt)
-        net.check()
-        np.testing.assert_array_equal(got.cpu().numpy(), logits, err_msg=f'logits {options}')
-        np.testing.assert_array_equal(scaled.cpu().numpy().reshape(want.shape), want, err_msg=f'scaled map {options}')
+        assert np.unique(g.v[gate][0]).size > 50
+        return g.mul(src, gate, a_fl=0, a_signed=False, b_fl=8, label='se.scale')
+    se_branch_on_resnet50_stage(dev, branch, ('table+chmul_i32:', tc.F32), lines=tc.lines)
 
 
 # ---- torch
@@ -161,7 +118,7 @@ def test_torch_table_q_against_the_reference(C, H, W, src_fl, in_fl, in_signed, 
     out_fl = 30 if kind == 'rnd' else 10
     table = (np.random.default_rng(C).integers(-2 ** 31, 2 ** 31, 256, dtype=np.int64).astype(np.int32) if kind == 'rnd'
              else getattr(tables, kind)(in_fl, in_signed, out_fl))
-    want = tc.table_ref(x.cpu().numpy(), src_fl, table, in_fl=in_fl, in_signed=in_signed)
+    want = ref_ops.table_ref(x.cpu().numpy(), src_fl, table, in_fl=in_fl, in_signed=in_signed)
     got = torch.ops.f8net.table_q(x, torch.from_numpy(table), src_fl, in_fl, in_signed, out_fl)
     assert got.dtype == torch.int32 and got.shape == x.shape and np.unique(want).size > (50 if kind == 'rnd' else 10)
     np.testing.assert_array_equal(got.cpu().numpy(), want)
@@ -175,6 +132,6 @@ def test_sigmoid_and_swish_modules(dev):
     for mod, table, out_fl in ((ops.F8Sigmoid(4, True, 12).to(dev), tables.sigmoid(4, True, 12), 12), (ops.F8Swish(4, True, 8).to(dev), tables.swish(4, True, 8), 8),
                                (ops.F8Table(tables.tanh(5, True, 7), 5, True, 7).to(dev), tables.tanh(5, True, 7), 7)):
         y = mod(x)
-        want = tc.table_ref(x.cpu().numpy(), fl, table, in_fl=mod.in_fl, in_signed=True)
+        want = ref_ops.table_ref(x.cpu().numpy(), fl, table, in_fl=mod.in_fl, in_signed=True)
         np.testing.assert_array_equal(y.cpu().numpy(), want)
         assert y.output_fraclen == out_fl and np.unique(want).size > 50

@@ -12,7 +12,9 @@ import concat_cases as cc
 import upsample_cases as uc
 from f8net_amd import onnx_export, onnx_import, synth, topology
 from f8net_amd.net import record_net
+from graph_cases import run_case
 from oracle import oracle
+from refgraph import RefGraph
 
 pytestmark = pytest.mark.gpu
 
@@ -23,40 +25,21 @@ def dev():
     return torch.device('cuda:0')
 
 
-def _outputs(got, n, wants):
-    got = got if isinstance(got, tuple) else (got,)
-    assert len(got) == len(wants)
-    return [y.cpu().numpy().reshape((n,) + w.shape[1:]) for y, w in zip(got, wants)]
-
-
-def _run(name, dev, **opts):
+def _check_plan(net, name, opts):
     c = uc.CASES[name]
-    N = c['N']
-    ref, routs, _ = uc.reference(name)                             # over N + 1 images
-    wants = [ref.v[o][0] for o in routs]
-    x = uc.make_input(name, N + 1)
-    g, outs, _ = uc.plan(name, x, max_batch=N + 1, **opts)
     tok = c['tok'] if opts.get('upsample_i8', 1) else c['tok_off']
-    assert [(t, k) for _, t, k in uc.upsample_lines(g.net)] == [(tok, uc.SYMBOL[tok])], g.net.describe()
-    xt = torch.from_numpy(x).to(dev)
-    for n in (N, N - 1):
-        got = _outputs(g.net.run(xt[:n]), n, wants)
-        for k, (y, w) in enumerate(zip(got, wants)):
-            if c.get('as_float'):
-                w = w.astype(np.float32)
-            np.testing.assert_array_equal(y, w[:n], err_msg=f'{name} {opts} n={n} output {k}')
-    g.net.check()
+    assert [(t, k) for _, t, k in uc.upsample_lines(net)] == [(tok, uc.SYMBOL[tok])], net.describe()
 
 
 @pytest.mark.parametrize('i8', [1, 0])
 @pytest.mark.parametrize('name', sorted(uc.CASES))
 def test_every_case_on_both_legs(name, i8, dev):
-    _run(name, dev, upsample_i8=i8)
+    run_case(uc, name, dev, _check_plan, upsample_i8=i8)
 
 
 @pytest.mark.parametrize('name', sorted(uc.CASES))
 def test_every_case_with_all_fusions(name, dev):
-    _run(name, dev, **uc.FUSE_ALL)
+    run_case(uc, name, dev, _check_plan, **uc.FUSE_ALL)
 
 
 @pytest.mark.parametrize('name', ['n_3x5_two', 'b_3x5_k1'])
@@ -96,15 +79,6 @@ def test_profiled_run_times_the_upsample_launch(dev):
     g.net.check()
 
 
-def _tapped_graph(net, seen):
-    """An upsample_cases._Graph that records into `net` and starts from the tapped tensors {block name: (values, fraclen)} of the oracle's walk."""
-    first = next(iter(seen.values()))
-    g = uc._Graph(first[0], first[1], record=False)
-    g.record, g.net = True, net
-    g.v = {net.tap_ids[k]: v for k, v in seen.items()}
-    return g
-
-
 def test_deeplabv3_head_on_resnet50_os16(dev):
     """resnet50_os16 at 96 x 96 (stage 3 on a 6 x 6 map) with a whole DeepLabV3 head on the stage-3 output: the four ASPP conv branches of
     concat_cases.aspp_head, the image-pooling branch (average pool -> 1x1 conv -> nearest (6, 6): the broadcast), concat, projection, a 1x1
@@ -121,7 +95,7 @@ def test_deeplabv3_head_on_resnet50_os16(dev):
     xt = torch.from_numpy(x).to(dev)
     for options in (None, uc.FUSE_ALL):
         net = record_net(spec, params, 96, options=options)
-        g = _tapped_graph(net, seen)
+        g = RefGraph.on(net, {net.tap_ids[k]: v for k, v in seen.items()})
         t = net.tap_ids[last]
         bs = [uc.producer(g, t, 0, 64, 5, w_fl=5, relu=True, in_fl=4, quant_input=True)]
         bs += [uc.producer(g, t, 1 + k, 64, 5, w_fl=5, relu=True, in_fl=4, quant_input=True, kernel=3, dilation=d) for k, d in enumerate((6, 12, 18))]
@@ -160,7 +134,7 @@ def test_fpn_top_down_step_on_resnet50(dev):
     xt = torch.from_numpy(x).to(dev)
     for options in (None, uc.FUSE_ALL):
         net = record_net(spec, params, 64, options=options)
-        g = _tapped_graph(net, seen)
+        g = RefGraph.on(net, {net.tap_ids[k]: v for k, v in seen.items()})
         top = uc.producer(g, net.tap_ids[c4], 0, 64, 9, w_fl=5, relu=False, in_fl=4, quant_input=True)
         up = g.upsample(top, 2, 'nearest', label='p4.up')
         lateral = uc.producer(g, net.tap_ids[c3], 1, 64, 8, w_fl=4, relu=False, in_fl=4, quant_input=True)

@@ -4,24 +4,21 @@ fusing pass on and with fuse_hgate = 0, written by hand there —, launch_info /
 where the ops cut the fused launches of ResNet-50 and MobileNet-V2 (exactly where an output tap does), the IntOp round trip through ONNX with the
 exported file evaluated by the oracle's ONNX walker, the importer's refusals, the shipped nets' default plans against the recorded digests, and the
 host code under AddressSanitizer / UndefinedBehaviorSanitizer as a stand-alone program.  tests/test_gpu_mul.py runs every case on the device."""
-import glob
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
 import mul_cases as mc
+import ref_ops
 from f8net_amd import onnx_export, onnx_import, onnx_io, synth, topology
 from f8net_amd._lib import F8Error
 from f8net_amd.net import F8Net, build_net, record_net
 from f8net_amd.onnx_import import IntGraph, IntOp, OnnxImportError
+from graph_cases import all_shipped_jobs, plan_digest_tool, same_ops, sanitized_host_program, shipped_digest_membership
 from oracle import onnx_eval
+from refgraph import RefGraph, graph_forward
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INVALID, STATE = -1, -5
 
 
@@ -49,10 +46,10 @@ def test_mul_reference_is_the_real_product(a, b):
     for shape in ((2, 5, 3, 4), (2, 5, 1, 1)):
         xb = rng.integers(-2 ** 10, 2 ** 10, shape, dtype=np.int64).astype(np.int32)
         fa, fb = a[0] + 3, b[0] + 2
-        A, B = mc.mul_operands(xa, fa, xb, fb, a[0], a[1], b[0], b[1])
+        A, B = ref_ops.mul_operands(xa, fa, xb, fb, a[0], a[1], b[0], b[1])
         assert A.min() >= (-127 if a[1] else 0) and A.max() <= (127 if a[1] else 255) and np.unique(A).size > 20
         for relu in (False, True):
-            y, fl = mc.mul_ref(xa, fa, xb, fb, a_fl=a[0], a_signed=a[1], b_fl=b[0], b_signed=b[1], relu=relu)
+            y, fl = ref_ops.mul_ref(xa, fa, xb, fb, a_fl=a[0], a_signed=a[1], b_fl=b[0], b_signed=b[1], relu=relu)
             assert fl == a[0] + b[0] and y.dtype == np.int32 and y.shape == xa.shape
             want = torch.from_numpy(A).double() / 2 ** a[0] * (torch.from_numpy(B).double() / 2 ** b[0])
             if relu:
@@ -64,7 +61,7 @@ def test_mul_reference_is_the_real_product(a, b):
 def test_hard_gate_reference_is_relu6_of_x_plus_3(fl):
     x = np.random.default_rng(fl).integers(-5 * 2 ** fl - 3, 5 * 2 ** fl + 3, 4000, dtype=np.int64)
     x = np.concatenate([x, [-2 ** 31, 2 ** 31 - 1, 3 * 2 ** fl, -3 * 2 ** fl, 3 * 2 ** fl + 1, -3 * 2 ** fl - 1, 0]]).astype(np.int32)
-    g = mc.hard_gate_ref(x, fl)
+    g = ref_ops.hard_gate_ref(x, fl)
     xr = torch.from_numpy(x).double() / 2 ** fl
     assert torch.equal(torch.from_numpy(g).double() / 2 ** fl, F.relu6(xr + 3))
     assert torch.equal(torch.from_numpy(g).double() / 2 ** fl, F.hardsigmoid(xr) * 6) or fl > 20      # (hardsigmoid divides and multiplies back: exact on small fraclens)
@@ -76,7 +73,7 @@ def test_hard_swish_reference_is_six_times_torchs():
     here the gate is read at its full fraclen (no rounding) and x at a format that holds it exactly."""
     fl = 4
     x = np.arange(-127, 128, dtype=np.int32).reshape(1, 5, 51, 1)                 # every signed 8-bit value at fraclen 4: -7.9 .. 7.9
-    y, out_fl = mc.mul_ref(x, fl, mc.hard_gate_ref(x, fl), fl, a_fl=fl, a_signed=True, b_fl=fl, b_signed=False)
+    y, out_fl = ref_ops.mul_ref(x, fl, ref_ops.hard_gate_ref(x, fl), fl, a_fl=fl, a_signed=True, b_fl=fl, b_signed=False)
     xr = torch.from_numpy(x).double() / 2 ** fl
     want = xr * F.relu6(xr + 3)
     assert torch.equal(torch.from_numpy(y).double() / 2 ** out_fl, want)
@@ -157,9 +154,7 @@ def test_option():
     for bad in (-1, 2):
         with pytest.raises(F8Error):
             net.set_option('fuse_hgate', bad)
-    sys.path.insert(0, os.path.join(ROOT, 'tools'))
-    import plan_digest
-    assert plan_digest.LATER['fuse_hgate'] == (0, 1)
+    assert plan_digest_tool().LATER['fuse_hgate'] == (0, 1)
 
 
 # ---- tokens and kernels
@@ -300,7 +295,7 @@ def test_tokens_of_the_mobilenet_v3_block_and_the_se_net():
     for build, x, fl, tokens, nofuse in ((lambda g, x0: mc.mbv3_block(g, x0)[0], mc.mbv3_input(), mc.X_FL, mc.MBV3_TOKENS, mc.MBV3_NOFUSE),
                                          (mc.se_net, mc.se_input(), mc.X_FL, mc.SE_TOKENS, None)):
         for opts in ({}, mc.FUSE_ALL, dict(fuse_hgate=0)):
-            g = mc._Graph(x, fl)
+            g = RefGraph(x, fl)
             build(g, next(iter(g.v)))
             for k, v in opts.items():
                 g.net.set_option(k, v)
@@ -315,20 +310,6 @@ def test_tokens_of_the_mobilenet_v3_block_and_the_se_net():
 
 
 # ---- ONNX
-FIELDS = ('kind', 'src', 'src2', 'stride', 'pad', 'groups', 'kernel', 'shift', 'signed', 'signed2', 'relu', 'dilation', 'srcs', 'shifts', 'shape')
-
-
-def _same_ops(a, b):
-    assert len(a.ops) == len(b.ops) and a.output == b.output and a.output_float == b.output_float
-    for p, q in zip(a.ops, b.ops):
-        for f in FIELDS:
-            assert getattr(p, f) == getattr(q, f), (p.kind, f, getattr(p, f), getattr(q, f))
-        for f in ('weight', 'bias'):
-            assert (getattr(p, f) is None) == (getattr(q, f) is None)
-            if getattr(p, f) is not None:
-                np.testing.assert_array_equal(getattr(p, f), getattr(q, f))
-
-
 def test_onnx_round_trip_of_the_se_net_and_the_file_evaluates_to_the_reference():
     seen = {}
     ig, g, out = mc.se_int_graph(seen)
@@ -338,8 +319,10 @@ def test_onnx_round_trip_of_the_se_net_and_the_file_evaluates_to_the_reference()
     graph = onnx_io.load_graph(data)
     assert sum(n.op == 'Unsqueeze' and n.attrs.get('axes') == [2, 3] for n in graph.nodes) == 1      # the [N, C] gate in front of its Mul
     back = onnx_import.import_graph(data)
-    _same_ops(ig, back)
+    same_ops(ig, back)
     assert back.solve_fraclens(mc.X_FL) == ig.solve_fraclens(mc.X_FL)
+    x = mc.se_input()
+    np.testing.assert_array_equal(graph_forward(back, x, mc.X_FL), g.v[out][0])      # the walker against RefGraph's values
     V, _ = ig.solve_fraclens(mc.X_FL)
     gates = [t for t, o in enumerate(ig.ops) if o.kind == 'hgate']
     assert [V[t] for t in gates] == [ig.ops[t].shift for t in gates] == [9, 9]      # pinned absolutely
@@ -413,41 +396,21 @@ def test_a_shipped_net_exports_and_imports_as_before():
     ig = onnx_export.graph_from_params(spec, synth.make_params(spec, seed=5), 64)
     back = onnx_import.import_graph(onnx_export.export_graph(ig))
     assert all(o.kind not in ('mul', 'hgate') for o in back.ops)
-    _same_ops(ig, back)
+    same_ops(ig, back)
 
 
 # ---- the shipped nets plan as before
 def test_plan_digests_of_the_shipped_nets_are_the_recorded_ones():
     """tools/plan_digest.py's DEFAULT option column: the lines recorded before these entry points existed (tests/golden/plan_digest_default.txt), of
     which a subset is planned here; and the op cases' digests (tests/golden/plan_digest_cases.txt): the tool's case modules are the ones they were."""
-    sys.path.insert(0, os.path.join(ROOT, 'tools'))
-    import plan_digest
-    assert 'mul_cases' not in plan_digest.CASE_MODULES
-    want = open(os.path.join(ROOT, 'tests', 'golden', 'plan_digest_default.txt')).read().splitlines()
-    jobs = [(a, 224, bs, False, 'default') for a in plan_digest.ARCHS for bs in (2, 128)] + [(a, hw, 128, False, 'default') for a, hw in plan_digest.EXTRA_SIZES]
-    for job in jobs:
-        (line,) = plan_digest.plan_lines(job)
-        assert line in want, line
+    assert 'mul_cases' not in plan_digest_tool().CASE_MODULES
+    shipped_digest_membership(all_shipped_jobs())
 
 
 # ---- host code under the sanitizers
-def test_host_code_under_asan_and_ubsan(tmp_path):
+def test_host_code_under_asan_and_ubsan():
     """examples/se_host.c records `se`, `hswish` and `shared` through the C ABI, finalizes, describes and destroys them.  f8_net.cpp's host side
     is compiled with AddressSanitizer and UndefinedBehaviorSanitizer and linked with the library's other objects into that stand-alone program."""
-    hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-    objs = [o for o in sorted(glob.glob(os.path.join(ROOT, 'build', 'f8_*.o'))) if os.path.basename(o) != 'f8_net.o']
-    assert os.path.exists(hipcc) and len(objs) >= 31, 'build libf8net.so first (__graft_entry__.build()): its objects are linked here'
-    san = ['-fsanitize=address,undefined', '-fno-sanitize-recover=undefined']
-    net_o, host_o, exe = str(tmp_path / 'f8_net_san.o'), str(tmp_path / 'se_host.o'), str(tmp_path / 'se_host')
-    subprocess.check_call([hipcc, '--offload-arch=gfx950', '-O1', '-g', '-std=c++17', '-fPIC'] + [a for s in san for a in ('-Xarch_host', s)] +
-                          ['-x', 'hip', '-c', os.path.join(ROOT, 'f8net_amd', 'csrc', 'f8_net.cpp'), '-o', net_o])
-    subprocess.check_call(['gcc', '-std=c99', '-pedantic', '-Wall', '-Wextra', '-Werror', '-I' + os.path.join(ROOT, 'include')] + san +
-                          ['-c', os.path.join(ROOT, 'examples', 'se_host.c'), '-o', host_o])
-    subprocess.check_call([hipcc, '--offload-arch=gfx950'] + san + [host_o, net_o] + objs + ['-o', exe])
-    env = dict(os.environ, LD_LIBRARY_PATH='/opt/rocm/lib:' + os.environ.get('LD_LIBRARY_PATH', ''), ASAN_OPTIONS='detect_leaks=1')
-    r = subprocess.run([exe], text=True, capture_output=True, env=env)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert 'runtime error' not in r.stderr and 'AddressSanitizer' not in r.stderr, r.stderr
-    out = r.stdout
+    out = sanitized_host_program('se_host.c')
     assert out.rstrip().endswith('ok')
     assert out.count('hgate+chmul_i8:') == 1 and out.count('hgate+mul_i32:') == 1 and out.count('hgate:') == 1 and out.count(' chmul_i8:') == 1

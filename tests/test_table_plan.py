@@ -4,25 +4,23 @@ fuse_table = 0, written by hand there —, the host-composed byte tables' effect
 the op cuts the fused launches of ResNet-50 and MobileNet-V2 (exactly where an output tap does), the shipped nets' default plans against the
 recorded digests, and the host code — table composition, value bound, argument checks — under AddressSanitizer / UndefinedBehaviorSanitizer as a
 stand-alone program.  tests/test_gpu_table.py runs every case on the device."""
-import glob
-import os
-import subprocess
-
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
-import table_cases as tc
 import mul_cases as mc
+import ref_ops
+import table_cases as tc
 from f8net_amd import onnx_export, onnx_import, onnx_io, synth, tables, topology
 from f8net_amd._lib import F8Error
 from f8net_amd.net import F8Net, build_net, record_net
 from f8net_amd.onnx_import import OnnxImportError
+from graph_cases import all_shipped_jobs, plan_digest_tool, same_ops, sanitized_host_program, shipped_digest_membership
 from oracle import onnx_eval
 from oracle import oracle
+from refgraph import RefGraph, graph_forward
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INVALID, STATE = -1, -5
 FORMATS = [(8, False), (5, False), (0, False), (7, True), (4, True), (0, True)]
 
@@ -91,7 +89,7 @@ def test_reference_indexes_by_the_requantised_source(in_fl, in_signed):
     fl = in_fl + 3
     x = rng.integers(-2 ** 11, 2 ** 11, (2, 5, 3, 40), dtype=np.int64).astype(np.int32)
     table = rng.integers(-2 ** 31, 2 ** 31, 256, dtype=np.int64).astype(np.int32)
-    y = tc.table_ref(x, fl, table, in_fl=in_fl, in_signed=in_signed)
+    y = ref_ops.table_ref(x, fl, table, in_fl=in_fl, in_signed=in_signed)
     q = oracle.requant_py(x, in_fl, fl, in_signed)                                     # the second, independent statement of the shift
     want = np.array([table[v + 128] if in_signed else table[v] for v in q.reshape(-1).tolist()], np.int32).reshape(x.shape)
     assert np.array_equal(y, want) and y.dtype == np.int32
@@ -171,7 +169,7 @@ def test_null_desc_and_null_table_through_the_raw_abi():
     assert L.f8_net_table(net._h, a, ctypes.byref(d), tab) >= 0
 
 
-def test_options(monkeypatch):
+def test_options():
     net = F8Net()
     for key, hi in (('table_i8', 1), ('fuse_table', 2)):
         assert net.get_option(key) == 1
@@ -181,9 +179,8 @@ def test_options(monkeypatch):
         for bad in (-1, hi + 1):
             with pytest.raises(F8Error):
                 net.set_option(key, bad)
-    monkeypatch.syspath_prepend(os.path.join(ROOT, 'tools'))
-    import plan_digest
-    assert plan_digest.LATER['table_i8'] == (0, 1) and plan_digest.LATER['fuse_table'] == (0, 2)
+    later = plan_digest_tool().LATER
+    assert later['table_i8'] == (0, 1) and later['fuse_table'] == (0, 2)
 
 
 def test_the_torch_op_has_a_meta_impl_and_refuses_what_no_format_holds():
@@ -224,7 +221,7 @@ def test_tokens_and_kernels_of_every_case(name):
 
 def test_tokens_of_the_mbconv_block():
     for opts in ({}, tc.FUSE_ALL, dict(table_i8=0), dict(fuse_table=0)):
-        g = tc._Graph(tc.mbconv_input(), tc.X_FL)
+        g = RefGraph(tc.mbconv_input(), tc.X_FL)
         tc.mbconv_block(g, next(iter(g.v)))
         for k, v in opts.items():
             g.net.set_option(k, v)
@@ -351,58 +348,24 @@ def test_the_op_cuts_the_chain_where_a_tap_does(arch, name, op):
 
 
 # ---- the shipped nets plan as before
-def test_plan_digests_of_the_shipped_nets_are_the_recorded_ones(monkeypatch):
+def test_plan_digests_of_the_shipped_nets_are_the_recorded_ones():
     """tools/plan_digest.py's DEFAULT option column of a subset of the jobs: each planned line must be one of the recorded lines
     (tests/golden/plan_digest_default.txt).  Membership, not file equality: tests/test_plan_digest.py compares the whole file and the whole matrix."""
-    monkeypatch.syspath_prepend(os.path.join(ROOT, 'tools'))
-    import plan_digest
-    assert 'table_cases' not in plan_digest.CASE_MODULES
-    want = open(os.path.join(ROOT, 'tests', 'golden', 'plan_digest_default.txt')).read().splitlines()
-    jobs = [(a, 224, bs, False, 'default') for a in plan_digest.ARCHS for bs in (2, 128)] + [(a, hw, 128, False, 'default') for a, hw in plan_digest.EXTRA_SIZES]
-    for job in jobs:
-        (line,) = plan_digest.plan_lines(job)
-        assert line in want, line
+    assert 'table_cases' not in plan_digest_tool().CASE_MODULES
+    shipped_digest_membership(all_shipped_jobs())
 
 
 # ---- host code under the sanitizers
-def test_host_code_under_asan_and_ubsan(tmp_path):
+def test_host_code_under_asan_and_ubsan():
     """examples/table_host.c records `se`, `extreme` and `output` through the C ABI — argument checks, the value bound, byte tables composed from
     INT32_MIN / INT32_MAX entries by right and left shifts — finalizes, describes and destroys them.  f8_net.cpp's host side is compiled with
     AddressSanitizer and UndefinedBehaviorSanitizer and linked with the library's other objects into that stand-alone program."""
-    hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-    objs = [o for o in sorted(glob.glob(os.path.join(ROOT, 'build', 'f8_*.o'))) if os.path.basename(o) != 'f8_net.o']
-    assert os.path.exists(hipcc) and len(objs) >= 32, 'build libf8net.so first (__graft_entry__.build()): its objects are linked here'
-    san = ['-fsanitize=address,undefined', '-fno-sanitize-recover=undefined']
-    net_o, host_o, exe = str(tmp_path / 'f8_net_san.o'), str(tmp_path / 'table_host.o'), str(tmp_path / 'table_host')
-    subprocess.check_call([hipcc, '--offload-arch=gfx950', '-O1', '-g', '-std=c++17', '-fPIC'] + [a for s in san for a in ('-Xarch_host', s)] +
-                          ['-x', 'hip', '-c', os.path.join(ROOT, 'f8net_amd', 'csrc', 'f8_net.cpp'), '-o', net_o])
-    subprocess.check_call(['gcc', '-std=c99', '-pedantic', '-Wall', '-Wextra', '-Werror', '-I' + os.path.join(ROOT, 'include')] + san +
-                          ['-c', os.path.join(ROOT, 'examples', 'table_host.c'), '-o', host_o])
-    subprocess.check_call([hipcc, '--offload-arch=gfx950'] + san + [host_o, net_o] + objs + ['-lm', '-o', exe])
-    env = dict(os.environ, LD_LIBRARY_PATH='/opt/rocm/lib:' + os.environ.get('LD_LIBRARY_PATH', ''), ASAN_OPTIONS='detect_leaks=1')
-    r = subprocess.run([exe], text=True, capture_output=True, env=env)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert 'runtime error' not in r.stderr and 'AddressSanitizer' not in r.stderr, r.stderr
-    out = r.stdout
+    out = sanitized_host_program('table_host.c', libs=['-lm'])
     assert out.rstrip().endswith('ok')
     assert out.count('table+chmul_i8:') == 1 and out.count(' table_i8:') == 2 and out.count(' table_i32:') == 1 and out.count('requant:') == 1
 
 
 # ---- IntOp(kind='table'), the fraction-length solver's pins, ONNX in both directions
-FIELDS = ('kind', 'src', 'src2', 'stride', 'pad', 'groups', 'kernel', 'shift', 'signed', 'signed2', 'relu', 'dilation', 'srcs', 'shifts', 'shape', 'in_fl', 'out_fl')
-
-
-def _same_ops(a, b):
-    assert len(a.ops) == len(b.ops) and a.output == b.output and a.output_float == b.output_float
-    for p, q in zip(a.ops, b.ops):
-        for f in FIELDS:
-            assert getattr(p, f) == getattr(q, f), (p.kind, f, getattr(p, f), getattr(q, f))
-        for f in ('weight', 'bias', 'table'):
-            assert (getattr(p, f) is None) == (getattr(q, f) is None)
-            if getattr(p, f) is not None:
-                np.testing.assert_array_equal(getattr(p, f), getattr(q, f))
-
-
 def test_onnx_round_trip_of_the_mbconv_block():
     """Export: per table the mul's requant subgraph, Add(128) for the signed index, Gather(axis=0) on a 256-entry int32 initializer; the importer maps
     each back to ONE op, and the imported graph plans the tokens of the recorded one (the sigmoid gate anchors the channel gate's b as a hard gate does)."""
@@ -416,8 +379,10 @@ def test_onnx_round_trip_of_the_mbconv_block():
         arr = graph.initializers[n.inputs[0]]
         assert arr.shape == (256,) and arr.dtype == np.int32
     back = onnx_import.import_graph(data)
-    _same_ops(ig, back)
+    same_ops(ig, back)
     assert back.solve_fraclens(tc.X_FL) == ig.solve_fraclens(tc.X_FL)
+    x = tc.mbconv_input()
+    np.testing.assert_array_equal(graph_forward(back, x, tc.X_FL), g.v[out][0])      # the walker against RefGraph's values
     net = back.build_net(2, input_fraclen=tc.X_FL)
     assert [(t, k) for _, t, k in tc.lines(net)] == tc.MBCONV_TOKENS, net.describe()
 
@@ -432,7 +397,9 @@ def test_onnx_file_with_an_unsigned_index_evaluates_to_the_reference():
     producer = {n.outputs[0]: n for n in graph.nodes}
     assert producer[gather.inputs[1]].op == 'Cast'                                     # straight from the requant's Clip / Cast: no Add(128)
     back = onnx_import.import_graph(data)
-    _same_ops(ig, back)
+    same_ops(ig, back)
+    x = mc.se_input()
+    np.testing.assert_array_equal(graph_forward(back, x, tc.X_FL), g.v[out][0])      # the walker against RefGraph's values
     want = g.v[out][0]
     assert np.unique(want).size > 100 and all(v[0].min() >= 0 for k, v in g.v.items() if k != out)
     y = onnx_eval.run(graph, mc.se_input())
@@ -522,4 +489,4 @@ def test_a_shipped_net_exports_and_imports_as_before():
     ig = onnx_export.graph_from_params(spec, synth.make_params(spec, seed=5), 64)
     back = onnx_import.import_graph(onnx_export.export_graph(ig))
     assert all(o.kind != 'table' for o in back.ops)
-    _same_ops(ig, back)
+    same_ops(ig, back)

@@ -5,10 +5,13 @@ its refusals, the reference pinned to torch in float64, the option key.  tests/t
 import numpy as np
 import pytest
 
+import ref_ops
 import upsample_cases as uc
 from f8net_amd import onnx_export, onnx_import, onnx_io, synth, topology
 from f8net_amd._lib import F8Error
 from f8net_amd.net import F8Net, build_net, record_net
+from graph_cases import same_ops
+from refgraph import graph_forward
 
 INVALID, UNSUPPORTED, STATE = -1, -2, -5
 
@@ -162,19 +165,6 @@ def test_an_upsample_cuts_the_chain_where_a_tap_does(arch, name, mode):
 
 
 # ---- ONNX
-def _same_ops(a, b):
-    assert len(a.ops) == len(b.ops) and a.output == b.output and a.output_float == b.output_float
-    for p, q in zip(a.ops, b.ops):
-        for f in ('kind', 'src', 'src2', 'stride', 'pad', 'groups', 'kernel', 'shift', 'signed', 'relu', 'dilation', 'srcs', 'shifts', 'shape', 'mode', 'scale'):
-            if p.kind == 'concat' and f == 'src2':
-                continue
-            assert getattr(p, f) == getattr(q, f), (p.kind, f, getattr(p, f), getattr(q, f))
-        for f in ('weight', 'bias'):
-            assert (getattr(p, f) is None) == (getattr(q, f) is None)
-            if getattr(p, f) is not None:
-                np.testing.assert_array_equal(getattr(p, f), getattr(q, f))
-
-
 @pytest.mark.parametrize('name', ['n_3x5_s35', 'n_unet_i8', 'b_3x5_k4', 'b_fpn'])
 def test_onnx_round_trip(name):
     c = uc.CASES[name]
@@ -187,10 +177,10 @@ def test_onnx_round_trip(name):
     else:
         assert (rs.attrs['mode'], rs.attrs['coordinate_transformation_mode']) == (b'linear', b'half_pixel')
     back = onnx_import.import_graph(data)
-    _same_ops(ig, back)
+    same_ops(ig, back)
     assert back.solve_fraclens(uc.X_FL) == ig.solve_fraclens(uc.X_FL)
     x = uc.make_input(name)
-    np.testing.assert_array_equal(uc.graph_forward(back, x, uc.X_FL), g.v[out][0])      # the walker against _Graph's reference
+    np.testing.assert_array_equal(graph_forward(back, x, uc.X_FL), g.v[out][0])      # the walker against RefGraph's values
     net = back.build_net(2, input_fraclen=uc.X_FL)
     assert [(t, k) for _, t, k in uc.upsample_lines(net)] == [(c['tok'], uc.SYMBOL[c['tok']])]
 
@@ -245,7 +235,7 @@ def test_onnx_import_refusals(name, edit, match):
 
 def test_onnx_pytorch_half_pixel_is_accepted():
     ig, _, _ = uc.int_graph('b_3x5_k1')
-    _same_ops(ig, onnx_import.import_graph(_model('b_3x5_k1', lambda g, rs: rs.attrs.__setitem__('coordinate_transformation_mode', b'pytorch_half_pixel'))))
+    same_ops(ig, onnx_import.import_graph(_model('b_3x5_k1', lambda g, rs: rs.attrs.__setitem__('coordinate_transformation_mode', b'pytorch_half_pixel'))))
 
 
 # ---- the reference
@@ -254,15 +244,15 @@ def test_onnx_pytorch_half_pixel_is_accepted():
 def test_bilinear_reference_is_torch_float64_times_4s2(k, hw):
     x = synth.rand_uniform_int(9, f'pin{k}{hw}', (2, 3) + hw, -2 ** 30, 2 ** 30)
     uc.pin_to_torch(x, k)
-    y, fl = uc.upsample_ref(x.astype(np.int32), 5, 1 << k, 'bilinear')
+    y, fl = ref_ops.upsample_ref(x.astype(np.int32), 5, 1 << k, 'bilinear')
     assert fl == 5 + 2 * k + 2 and y.dtype == np.int32 and y.shape == (2, 3, hw[0] << k, hw[1] << k)
-    np.testing.assert_array_equal(y, uc.wrap32(uc.bilinear_exact(x, k)))
+    np.testing.assert_array_equal(y, ref_ops.wrap32(ref_ops.bilinear_exact(x, k)))
 
 
 def test_nearest_reference_is_torch_nearest():
     import torch
     x = synth.rand_uniform_int(9, 'pinn', (2, 3, 3, 5), -2 ** 31, 2 ** 31 - 1).astype(np.int32)
-    y, fl = uc.upsample_ref(x, 5, (3, 2), 'nearest')
+    y, fl = ref_ops.upsample_ref(x, 5, (3, 2), 'nearest')
     want = torch.nn.functional.interpolate(torch.from_numpy(x.astype(np.float64)), scale_factor=(3, 2), mode='nearest').numpy()
     assert fl == 5
     np.testing.assert_array_equal(y.astype(np.float64), want)
@@ -271,9 +261,9 @@ def test_nearest_reference_is_torch_nearest():
 def test_wrap_case_leaves_the_int32_range_before_wrapping():
     ref, _, (up,) = uc.reference('b_wrap')
     g, _, _ = uc.build_graph('b_wrap', uc.make_input('b_wrap', uc.CASES['b_wrap']['N'] + 1), record=False)     # (the builder asserts it as well)
-    exact = uc.bilinear_exact(next(v for t, (v, fl) in ref.v.items() if t not in (0, up)), 4)
+    exact = ref_ops.bilinear_exact(next(v for t, (v, fl) in ref.v.items() if t not in (0, up)), 4)
     assert (np.abs(exact) >= 2 ** 31).sum() > 1000 and (exact != ref.v[up][0]).sum() > 1000
-    np.testing.assert_array_equal(ref.v[up][0], uc.wrap32(exact))
+    np.testing.assert_array_equal(ref.v[up][0], ref_ops.wrap32(exact))
 
 
 # ---- the option key

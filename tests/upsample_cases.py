@@ -2,7 +2,7 @@
 tests/test_upsample_plan.py (acceptance, refusals, mode tokens, kernel symbols, forms, launch_info, fused nets, the ONNX round trip; no GPU) and
 tests/test_gpu_upsample.py (every case on both legs, bit for bit on the device).  No test functions here.
 
-The reference is numpy on int64, wrapped to int32 at the end: nearest is `np.repeat` along H and W; bilinear applies, per axis of n values and for
+The reference (ref_ops.upsample_ref) is numpy on int64, wrapped to int32 at the end: nearest is `np.repeat` along H and W; bilinear applies, per axis of n values and for
 output index o = s i + j (0 <= j < s), the integer weights of include/f8net.h
     j <  s / 2:  (s - 2j - 1) x[max(i - 1, 0)] + (s + 2j + 1) x[i]
     j >= s / 2:  (3s - 2j - 1) x[i] + (2j + 1 - s) x[min(i + 1, n - 1)]
@@ -14,61 +14,18 @@ fraclen 13 -> upsample -> readers: one 32-output 1x1 conv per (input_fl, signed)
 
 The expected plan token of every case, on both legs of option upsample_i8, and the forms its launch writes are WRITTEN BY HAND (the rule:
 DESIGN.md 4.5j); nothing here asks the planner for them."""
-import functools
+import sys
 
 import numpy as np
 
-import concat_cases as cc
 import graph_cases
 from concat_cases import FUSE_ALL, X_FL, producer, readers  # noqa: F401  (the tests take them from here)
 from f8net_amd import synth
-from graph_cases import graph_forward, launch_lines  # noqa: F401  (the walker of an imported graph: the tests take it from here)
-from f8net_amd.onnx_import import upsample_fl_gain
-from oracle import oracle
+from graph_cases import launch_lines
+from ref_ops import bilinear_exact
 
 I8, N32, B32 = 'upsample_nearest_i8:', 'upsample_nearest_i32:', 'upsample_bilinear_i32:'
 SYMBOL = {I8: 'f8::upsample_i8_kernel', N32: 'f8::upsample_i32_kernel<false>', B32: 'f8::upsample_i32_kernel<true>'}
-
-
-def wrap32(y):
-    return ((np.asarray(y, np.int64) + 2 ** 31) % 2 ** 32 - 2 ** 31).astype(np.int32)
-
-
-def nearest_exact(x, sh, sw):
-    return np.repeat(np.repeat(np.asarray(x, np.int64), sh, axis=2), sw, axis=3)
-
-
-def _bilinear_axis(x, s, axis):
-    n = x.shape[axis]
-    i0, i1, wl, wu = [], [], [], []
-    for o in range(s * n):
-        i, j = divmod(o, s)
-        if j < s // 2:
-            i0.append(max(i - 1, 0)), i1.append(i), wl.append(s - 2 * j - 1), wu.append(s + 2 * j + 1)
-        else:
-            i0.append(i), i1.append(min(i + 1, n - 1)), wl.append(3 * s - 2 * j - 1), wu.append(2 * j + 1 - s)
-    shape = [1] * x.ndim
-    shape[axis] = s * n
-    wl, wu = np.array(wl, np.int64).reshape(shape), np.array(wu, np.int64).reshape(shape)
-    assert ((wl + wu) == 2 * s).all() and (wl > 0).all() and (wu > 0).all()
-    return wl * np.take(x, i0, axis=axis) + wu * np.take(x, i1, axis=axis)
-
-
-def bilinear_exact(x, k):
-    """(N, C, H, W) integers -> the exact interpolated values times 2^(2k + 2), int64, not wrapped."""
-    x = np.asarray(x, np.int64)
-    return _bilinear_axis(_bilinear_axis(x, 1 << k, 2), 1 << k, 3)
-
-
-def upsample_ref(x, fl, scale, mode):
-    """-> (int32 values, fraclen)."""
-    sh, sw = (scale, scale) if isinstance(scale, int) else scale
-    if mode == 'nearest':
-        return wrap32(nearest_exact(x, sh, sw)), fl
-    k = sh.bit_length() - 1
-    assert mode == 'bilinear' and sh == sw == 1 << k and 1 <= k <= 4
-    assert upsample_fl_gain((sh, sw)) == 2 * k + 2
-    return wrap32(bilinear_exact(x, k)), fl + 2 * k + 2
 
 
 def pin_to_torch(x, k):
@@ -79,15 +36,6 @@ def pin_to_torch(x, k):
     got = bilinear_exact(x, k)
     assert np.abs(got).max() < 2 ** 52
     np.testing.assert_array_equal(got.astype(np.float64), want.numpy())
-
-
-class _Graph(cc._Graph):
-    """concat_cases._Graph with upsample."""
-
-    def upsample(self, t, scale, mode='nearest', label=None):
-        o = self._id(lambda: self.net.upsample(t, scale, mode, label=label))
-        self.v[o] = upsample_ref(self.v[t][0], self.v[t][1], scale, mode)
-        return o
 
 
 # ---- the builders.  Each returns (output tensor ids in output order, [upsample tensor ids])
@@ -209,38 +157,9 @@ def make_input(name, n=None):
     return synth.rand_uniform_int(5, f'upx{name}', (n or c['N'], c['cin']) + input_hw(c), 0, 255).astype(np.int32)
 
 
-def build_graph(name, x, record=True):
-    """Returns (graph, output ids, upsample ids)."""
-    c = CASES[name]
-    g = _Graph(x, X_FL, record=record)
-    outs, ups = c['build'](g, next(iter(g.v)), c)
-    return g, outs, ups
-
-
-@functools.lru_cache(maxsize=None)
-def reference(name):
-    """(graph, output ids, upsample ids) of the case over N + 1 images, evaluated on the reference alone, once; nothing may write into its arrays."""
-    return build_graph(name, make_input(name, CASES[name]['N'] + 1), record=False)
-
-
-def plan(name, x, max_batch=None, **opts):
-    g, outs, ups = build_graph(name, x)
-    for k, v in dict(CASES[name]['opts'], **opts).items():
-        g.net.set_option(k, v)
-    g.net.finalize(max_batch or x.shape[0])
-    return g, outs, ups
-
-
 def upsample_lines(net):
     """[(launch index, plan token, kernel symbol)] of the handle's upsample launches, in launch order."""
     return launch_lines(net, 'upsample_')
 
 
-class Recorder(graph_cases.Recorder, _Graph):
-    pass
-
-
-def int_graph(name):
-    """The case as an IntGraph, op for op what build_graph records (cases whose first output is the only one)."""
-    c = CASES[name]
-    return graph_cases.record_int_graph(Recorder, make_input(name), X_FL, lambda g, x0: c['build'](g, x0, c)[0][0])
+graph_cases.bind_cases(sys.modules[__name__])      # build_graph, reference, plan, int_graph
