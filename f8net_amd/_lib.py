@@ -70,6 +70,8 @@ SYMBOLS = [
     ('f8_net_avgpool_window', _i, [_vp, _i, _i, _i, _i, _i]),
     ('f8_net_linear', _i, [_vp, _i, ctypes.POINTER(LinearDesc), _vp, _vp]),
     ('f8_net_output', _i, [_vp, _i, _i]),
+    ('f8_net_output_argmax', _i, [_vp, _i, _i]),
+    ('f8_net_output_kind', _i, [_vp, _i]),
     ('f8_net_num_outputs', _i, [_vp]),
     ('f8_net_output_info', _i, [_vp, _i] + [ctypes.POINTER(_i)] * 5),
     ('f8_net_tensor_info', _i, [_vp, _i] + [ctypes.POINTER(_i)] * 4),

@@ -82,6 +82,7 @@ struct Options {
     int fuse_hgate = 1;          // a hard gate read by the b operand of one mul alone: 1 = no launch of its own, the mul launch reads the gate's int32 source (hgate+mul_*: / hgate+chmul_*:, f8_mul.hip); 0 = two launches
     int table_i8 = 1;            // f8_net_table: 1 = the byte-gather mode where the result is read in at most two int8 formats and by nothing else (table_i8:, f8_table.hip); 0 = always table_i32:
     int fuse_table = 1;          // a table read by the b operand of one broadcast mul alone: 1 = no launch of its own where the map has fewer than 2^20 values an image (the measured rule, fuse_table_rule in f8_net.cpp), the mul launch looks b up itself (table+chmul_*:, f8_table.hip); 2 = always; 0 = two launches
+    int fuse_argmax = 1;         // an argmax output on an upsample's result that nothing else reads: 1 = one launch that interpolates and reduces in registers, the upsampled tensor in no form (upsample_*+argmax_*:, f8_argmax.hip); 0 = the upsample launch and an argmax_*: launch
     int tap_tiled = 1;           // network outputs 1 .. leave on tap_kernel (f8_tap.hip: walks the I32T blocks, every loaded byte used); 0: on output_kernel like output 0
     int check_input_range = 1;   // int32 inputs that are NARROWED to the head's 8-bit format (no requant) are range-checked on the device; f8_net_check reports
 };
@@ -343,6 +344,18 @@ struct OutArgs {                           // NHWC int32 -> NCHW int32 / float32
     const int32_t* x; int32_t N, C, HW, Cs;
     void* out; int32_t as_float;
     const uint32_t* err; uint32_t epoch;   // the run's stage-chain error word (or nullptr) and tag: when the word carries THIS run's tag, the outputs are poisoned (NaN / INT32_MIN)
+};
+
+// Channel argmax as a network output (f8_argmax.hip; f8_net_output_argmax): out[n, p, q] = the smallest c with the largest x[n, c, p, q], uint8 or int32
+// [N, P, Q] in the caller's buffer.  argmax_i32t_kernel: x is the marked tensor's int32 form (I32T), [C, P, Q]; only N, C, Cs, P, Q are read.
+// upsample_argmax_kernel (option fuse_argmax): x is the int32 form of the SOURCE [C, Hs, Ws] of the upsample that produces the marked tensor, which
+// exists in no form; scales, k and the divisors as UpsampleArgs.
+struct ArgmaxArgs {
+    const int32_t* x;
+    int32_t N, C, Cs, Hs, Ws, P, Q, sh, sw, k;           // images, real / padded channels, source map, output map, scales, bilinear: log2 of the scale
+    FastDiv dSh, dSw, dQ4, dP;                           // / sh, / sw, / ceil(Q / 4), / P
+    void* out;                                           // the caller's buffer from this sub-batch's first image on
+    const uint32_t* err; uint32_t epoch;                 // as OutArgs: when the word carries THIS run's tag the map is poisoned (255 / INT32_MIN)
 };
 
 // One launch for a ResNet bottleneck identity block (f8_fused.hip).
@@ -778,6 +791,9 @@ const char* output_kernel_name();
 hipError_t launch_output(const OutArgs& a, hipStream_t s);
 const char* tap_kernel_name(int as_float);                       // f8_tap.hip: the same conversion, one wave per 4 KB block of the I32T source
 hipError_t launch_tap(const OutArgs& a, hipStream_t s);
+int argmax_inst(bool fused, bool bilinear, int index_bytes);     // f8_argmax.hip.  0 / 1: argmax_i32t_kernel<1> / <4>; 2 / 3: upsample_argmax_kernel<false, 1> / <false, 4>; 4 / 5: upsample_argmax_kernel<true, 1> / <true, 4>
+const char* argmax_kernel_name(int inst);
+hipError_t launch_argmax(const ArgmaxArgs& a, int inst, hipStream_t s);
 hipError_t launch_quantize_input(const float* x, int32_t* y, size_t n, float scale, int lo, int hi, hipStream_t s);
 struct TopkKs { int k[8]; };                // the k list travels by value in the kernel arguments
 hipError_t launch_topk_correct(const float* logits, const int64_t* target, int N, int C, TopkKs ks, int nk, float* correct, hipStream_t s);

@@ -125,6 +125,7 @@ struct Node {
     int mul_table = -1;                // mul, pass 2: the table node that produces b and is looked up inside this launch (option fuse_table), else -1
     int tab_into = -1;                 // table, pass 2: the mul node whose launch looks it up: no launch and no form of its own
     size_t tab_off = 0;                // table / a mul with mul_table, pass 3: its device tables in the weight image (int32 entries, or 256 bytes per int8 form)
+    int argmax_k = -1;                 // upsample, pass 2: the argmax output whose launch interpolates this node's result itself (option fuse_argmax): no launch and no form of its own, else -1
     int cat_into = -1;                 // concat, pass 2: the shuffle node whose launch reads this concat's operands: no launch and no form of its own
     // planning
     int fused_into = -1;               // add: conv node that carries it
@@ -147,7 +148,7 @@ struct Node {
     size_t rc_off = 0, cc_off = 0; int ncc = 0;      // border-class tables (0 = single class)
     ConvTile tile{};
 };
-enum StepKind { S_INPUT, S_CONV, S_DW, S_ADD, S_MAXPOOL, S_AVGPOOL, S_REQUANT, S_OUTPUT, S_FUSED, S_STEMPOOL, S_IR, S_P12, S_CHAIN, S_BCHAIN, S_HEAD2, S_IRCHAIN, S_DWS, S_DWS7, S_IRK, S_GCONV, S_CONCAT, S_UPSAMPLE, S_DECONV, S_SUMPOOL, S_CHANMAP, S_MUL, S_HGATE, S_TABLE };
+enum StepKind { S_INPUT, S_CONV, S_DW, S_ADD, S_MAXPOOL, S_AVGPOOL, S_REQUANT, S_OUTPUT, S_FUSED, S_STEMPOOL, S_IR, S_P12, S_CHAIN, S_BCHAIN, S_HEAD2, S_IRCHAIN, S_DWS, S_DWS7, S_IRK, S_GCONV, S_CONCAT, S_UPSAMPLE, S_DECONV, S_SUMPOOL, S_CHANMAP, S_MUL, S_HGATE, S_TABLE, S_ARGMAX };
 // The kernel of a step whose kind has several, chosen once by the step's emitter (pass 3); bind_step, run_step and f8_net_autotune switch on it.
 //   S_CONV:  conv_igemm (f8_kernels.hip), the LDS-patch 3x3 (f8_conv3x3.hip), conv1x1_wreg (f8_wreg.hip), conv1x1_wstat (f8_wstat.hip),
 //            conv3x3s2_wreg (f8_s2conv.hip), the 1x1 conv + average pool (f8_pool.hip), the classifier fc_dense (f8_fc.hip)
@@ -171,14 +172,14 @@ struct Step {
     OutSel out;
     int acc_shl = 0, res_shl = 0, relu0 = 0, relu1 = 0;
     bool dense = false;
-    int out_k = 0;                     // S_OUTPUT: the network output it copies out (0: into the run's output_dev, k >= 1: into buffer k of f8_net_set_output_buffers)
+    int out_k = 0;                     // S_OUTPUT / S_ARGMAX: the network output it writes (0: into the run's output_dev, k >= 1: into buffer k of f8_net_set_output_buffers)
     bool raw_input = false;            // S_INPUT: its work is done by the stem launch (S_STEMPOOL with the same flag) unless the run's input is uint8 NHWC
     std::string name;
     std::string kernel;                // device symbol as rocprofv3 prints it: of the instance bind_step chose (the launch family's *_kernel_name)
     double bytes_per_img = 0, bytes_const = 0, ops_per_img = 0;
     double valu_per_img = 0;           // ESSENTIAL vector lane-operations per image (f8_net_launch_valu): what the reference's semantics need once the MFMAs are done
     // the launcher's arguments as far as the plan decides them (bind_step); run_step copies them and adds what the run decides
-    std::variant<std::monostate, ConvArgs, StemPoolArgs, FusedArgs, ChainArgs, BChainArgs, BCChainArgs, IRArgs, IRKArgs, IRChainArgs, DwsArgs, Dws7Args, DwArgs, GConvArgs, AddArgs, PoolArgs, AvgArgs, OutArgs, ConcatArgs, UpsampleArgs, DeconvArgs, SumPoolArgs, ChanMapArgs, MulArgs, TableArgs, TableMulArgs> args;
+    std::variant<std::monostate, ConvArgs, StemPoolArgs, FusedArgs, ChainArgs, BChainArgs, BCChainArgs, IRArgs, IRKArgs, IRChainArgs, DwsArgs, Dws7Args, DwArgs, GConvArgs, AddArgs, PoolArgs, AvgArgs, OutArgs, ConcatArgs, UpsampleArgs, ArgmaxArgs, DeconvArgs, SumPoolArgs, ChanMapArgs, MulArgs, TableArgs, TableMulArgs> args;
     int inst = 0;                      // the instance the launcher starts (the family's *_inst, f8_internal.h; bind_step)
     // S_CHAIN / S_BCHAIN: geometry, workgroups per image and resident per CU, the 7x7 cluster form (f8_cchain.hip)
     int C = 0, MID = 0, H = 0, W = 0, cin0 = 0, tiles = 0, wg_per_cu = 1; bool cluster = false;
@@ -189,7 +190,7 @@ struct Step {
 struct f8_net {
     std::vector<Tensor> tensors;
     std::vector<Node> nodes;
-    struct Output { int t; int as_float; };
+    struct Output { int t; int as_float; int idx = 0; };      // idx: 0 = the tensor's values (f8_net_output); F8_IDX_U8 / F8_IDX_I32 = its channel argmax in elements of that many bytes (f8_net_output_argmax)
     std::vector<Output> outs;          // the network outputs in the order of the f8_net_output calls; [0] is the one f8_net_run's output_dev receives
     void* out_bufs[F8_MAX_OUTPUTS - 1] = {};   // caller buffers of outputs 1 .. (f8_net_set_output_buffers): one-shot, consumed by the next run (begin_run)
     bool out_bufs_set = false;
@@ -225,12 +226,18 @@ struct f8_net {
 
 namespace {
 
-// index of tensor t among the network outputs, -1: none.  Every output exists in HBM as int32: no fused launch keeps it on chip.
+// index of tensor t among the network outputs as a VALUE output (f8_net_output), -1: none.  Every output exists in HBM as int32: no fused launch keeps it on chip.
 int output_index(const f8_net* net, int t) {
-    for (size_t k = 0; k < net->outs.size(); ++k) if (net->outs[k].t == t) return (int)k;
+    for (size_t k = 0; k < net->outs.size(); ++k) if (net->outs[k].t == t && !net->outs[k].idx) return (int)k;
     return -1;
 }
-bool is_output(const f8_net* net, int t) { return output_index(net, t) >= 0; }
+// ... as an argmax output (f8_net_output_argmax); a tensor may carry one mark of each kind
+int argmax_index(const f8_net* net, int t) {
+    for (size_t k = 0; k < net->outs.size(); ++k) if (net->outs[k].t == t && net->outs[k].idx) return (int)k;
+    return -1;
+}
+// either mark: what every matcher asks — the tensor leaves the net, so it exists in device memory and cuts a fused launch
+bool is_output(const f8_net* net, int t) { return output_index(net, t) >= 0 || argmax_index(net, t) >= 0; }
 
 int add_form(Tensor& t, int kind, int n, int sgn) {
     for (size_t i = 0; i < t.forms.size(); ++i)
@@ -455,6 +462,7 @@ static const OptKey kOptKeys[] = {
     {"fuse_hgate", "F8_FUSE_HGATE", &Options::fuse_hgate, 0, 1, true},
     {"table_i8", "F8_TABLE_I8", &Options::table_i8, 0, 1, true},
     {"fuse_table", "F8_FUSE_TABLE", &Options::fuse_table, 0, 2, true},
+    {"fuse_argmax", "F8_FUSE_ARGMAX", &Options::fuse_argmax, 0, 1, true},
 };
 static const OptKey* find_opt(const char* key) {
     if (!key) return nullptr;
@@ -995,10 +1003,30 @@ int f8_net_avgpool_window(f8_net* net, int src, int kernel, int stride, int pad,
 int f8_net_output(f8_net* net, int src, int as_float) {
     int rc = check_t(net, src, "f8_net_output");
     if (rc) return rc;
-    if (is_output(net, src)) return fail(F8_ERR_INVALID, "f8_net_output: tensor %d is already output %d", src, output_index(net, src));
+    if (output_index(net, src) >= 0) return fail(F8_ERR_INVALID, "f8_net_output: tensor %d is already output %d", src, output_index(net, src));
     if ((int)net->outs.size() >= F8_MAX_OUTPUTS) return fail(F8_ERR_UNSUPPORTED, "f8_net_output: at most %d outputs per net", F8_MAX_OUTPUTS);
     net->outs.push_back({src, as_float ? 1 : 0});
     return (int)net->outs.size() - 1;
+}
+
+int f8_net_output_argmax(f8_net* net, int src, int index_bytes) {
+    int rc = check_t(net, src, "f8_net_output_argmax");
+    if (rc) return rc;
+    if (index_bytes != F8_IDX_U8 && index_bytes != F8_IDX_I32) return fail(F8_ERR_INVALID, "f8_net_output_argmax: index_bytes %d (F8_IDX_U8 or F8_IDX_I32)", index_bytes);
+    const Tensor& s = net->tensors[src];
+    if (s.C < 2) return fail(F8_ERR_INVALID, "f8_net_output_argmax: tensor %d has %d channel(s): the argmax needs at least 2", src, s.C);
+    if (argmax_index(net, src) >= 0) return fail(F8_ERR_INVALID, "f8_net_output_argmax: tensor %d is already argmax output %d", src, argmax_index(net, src));
+    if (index_bytes == F8_IDX_U8 && s.C > 255) return fail(F8_ERR_UNSUPPORTED, "f8_net_output_argmax: %d channels do not fit uint8 indices (255 is the poison value): use F8_IDX_I32", s.C);
+    if ((int)net->outs.size() >= F8_MAX_OUTPUTS) return fail(F8_ERR_UNSUPPORTED, "f8_net_output_argmax: at most %d outputs per net", F8_MAX_OUTPUTS);
+    net->outs.push_back({src, 0, index_bytes});
+    return (int)net->outs.size() - 1;
+}
+
+int f8_net_output_kind(const f8_net* net, int k) {
+    if (!net) return fail(F8_ERR_INVALID, "f8_net_output_kind: null net");
+    if (k < 0 || k >= (int)net->outs.size()) return fail(F8_ERR_INVALID, "f8_net_output_kind: output %d of %d", k, (int)net->outs.size());
+    const auto& o = net->outs[k];
+    return o.idx == F8_IDX_U8 ? 2 : o.idx == F8_IDX_I32 ? 3 : o.as_float ? 1 : 0;
 }
 
 int f8_net_num_outputs(const f8_net* net) { return net ? (int)net->outs.size() : F8_ERR_INVALID; }
@@ -1018,10 +1046,11 @@ int f8_net_output_info(const f8_net* net, int k, int* C, int* H, int* W, int* fr
     if (!net) return fail(F8_ERR_INVALID, "f8_net_output_info: null net");
     if (k < 0 || k >= (int)net->outs.size()) return fail(F8_ERR_INVALID, "f8_net_output_info: output %d of %d", k, (int)net->outs.size());
     const Tensor& t = net->tensors[net->outs[k].t];
-    if (C) *C = t.C;
+    const bool amax = net->outs[k].idx != 0;           // a class map: one channel of indices, no fraclen
+    if (C) *C = amax ? 1 : t.C;
     if (H) *H = t.H;
     if (W) *W = t.W;
-    if (fraclen) *fraclen = t.fl;
+    if (fraclen) *fraclen = amax ? 0 : t.fl;
     if (as_float) *as_float = net->outs[k].as_float;
     return F8_OK;
 }
@@ -2159,23 +2188,37 @@ static void ask_sources(f8_net* net, const std::vector<int>& srcs, int fl_ref, c
 // so it fuses below 2^20 values an image.  2: always (what the measurement ran).  0: never.
 static bool fuse_table_rule(int opt, const Tensor& a) { return opt == 2 || (opt == 1 && (int64_t)a.C * a.H * a.W < (int64_t(1) << 20)); }
 
-static void plan_tensor_forms(f8_net* net) {
+static void plan_tensor_forms(f8_net* net, int max_batch) {
     auto& T = net->tensors;
     auto& ND = net->nodes;
     const int nn = (int)ND.size();
     const Options& opt = net->opt;
     // ---- 2. which forms does each tensor need?  (reverse order: consumers before producers)
-    {
+    if (!net->outs[0].idx) {
         const int out0 = net->outs[0].t;
         Tensor& O = T[out0];
         const Node& p = ND[O.prod];
         // the classifier (a linear / 1x1 conv on a 1x1 map that nothing else reads) writes the caller's buffer itself: no int32 form
+        // (an argmax output on the same tensor reads the int32 form: the classifier then writes that, and the output launch copies it out)
         const Tensor& ps = T[p.a >= 0 ? p.a : out0];
         O.dense_out = opt.fuse_fc && (p.kind == N_LINEAR || p.kind == N_CONV) && p.cd.kernel == 1 && p.cd.stride == 1 && p.cd.pad == 0 && p.cd.groups == 1 &&
                       O.H == 1 && O.W == 1 && ps.H == 1 && ps.W == 1 && O.consumers.empty() && p.fused_add < 0 && p.absorbed_by < 0 && !p.cd.relu &&
-                      fc_dense_supported(ps.Cs, round_up(p.cd.cout, 32));
+                      fc_dense_supported(ps.Cs, round_up(p.cd.cout, 32)) && argmax_index(net, out0) < 0;
         if (!O.dense_out) add_form(O, FORM_I32, 0, 0);
-        for (size_t k = 1; k < net->outs.size(); ++k) add_form(T[net->outs[k].t], FORM_I32, 0, 0);      // the copy-out launch reads the int32 form
+    }
+    for (size_t k = 0; k < net->outs.size(); ++k) {
+        const int t = net->outs[k].t;
+        if (!net->outs[k].idx) { if (k >= 1) add_form(T[t], FORM_I32, 0, 0); continue; }      // the copy-out launch reads the int32 form
+        // An argmax output.  On an upsample's result that NOTHING else reads — no consumer, no value output — the argmax launch interpolates per output
+        // pixel itself (option fuse_argmax): the upsample emits no launch, its result gets no form, its source is read in int32.  Its items
+        // are indexed in 32 bits: the launch stays below 2^31 output pixels.  Otherwise the launch reads the marked tensor's int32 form, as a tap does.
+        Node& p = ND[T[t].prod];
+        if (opt.fuse_argmax && p.kind == N_UPSAMPLE && T[t].consumers.empty() && output_index(net, t) < 0 && (int64_t)max_batch * T[t].H * T[t].W < (int64_t(1) << 31)) {
+            p.argmax_k = (int)k;
+            add_form(T[p.a], FORM_I32, 0, 0);
+        } else {
+            add_form(T[t], FORM_I32, 0, 0);
+        }
     }
     for (int i = nn - 1; i >= 0; --i) {
         Node& nd = ND[i];
@@ -2333,6 +2376,7 @@ static void plan_tensor_forms(f8_net* net) {
                 nd.bytes_mode = opt.table_i8 && int8_forms_only(net, nd.out);
                 break;
             case N_UPSAMPLE: {
+                if (nd.argmax_k >= 0) break;                                  // (fused: the argmax output asked the source for its int32 form above)
                 // the mode rule alone, for nearest: the fraclen — so the shift — is the source's and no bound on the values is needed
                 nd.bytes_mode = opt.upsample_i8 && nd.up_mode == F8_UP_NEAREST && int8_forms_only(net, nd.out);
                 ask_sources(net, {nd.a}, T[nd.a].fl, T[nd.out].forms, nd.bytes_mode);
@@ -3093,6 +3137,25 @@ static void emit_output(f8_net* net, int k = 0) {
     net->steps.push_back(st);
 }
 
+// The launch of argmax output k (f8_argmax.hip), directly behind the producer of what it reads.  up < 0: it reads the marked tensor's int32 form.  up >= 0: the
+// upsample node that produces the marked tensor and runs inside this launch (Node::argmax_k): it reads the upsample's SOURCE in int32 and stands in the
+// upsample's place in the plan.  It writes no tensor (st.out.t < 0), only the caller's buffer.
+static void emit_argmax(f8_net* net, int k, int up) {
+    const int t = net->outs[k].t, ib = net->outs[k].idx;
+    const Tensor& o = net->tensors[t];
+    const Node* u = up >= 0 ? &net->nodes[up] : nullptr;
+    const int src = u ? u->a : t;
+    const Tensor& x = net->tensors[src];
+    Step st; st.kind = S_ARGMAX; st.node = u ? up : o.prod; st.out_k = k;
+    st.src_t = src; st.src_f = find_form(x, FORM_I32, 0, 0);
+    const bool bil = u && u->up_mode == F8_UP_BILINEAR;
+    st.name = std::string(u ? (bil ? "upsample_bilinear+" : "upsample_nearest+") : "") + (ib == F8_IDX_U8 ? "argmax_u8:" : "argmax_i32:") + tname(net, t);
+    const double opx = (double)o.H * o.W;
+    st.bytes_per_img = (double)x.H * x.W * x.Cs * 4 + opx * ib;      // the source's blocks once (the fused launch re-reads them from cache), one index per pixel
+    st.valu_per_img = opx * o.C * ((bil ? 4 : 0) + 3);               // bilinear: one multiply + three multiply-adds per value; compare, select the maximum, select the index
+    net->steps.push_back(st);
+}
+
 // the fused stem launch can read the raw input itself: the input step then launches nothing (run_step)
 static void let_stem_read_input(f8_net* net) {
     for (auto& st : net->steps) {
@@ -3115,9 +3178,11 @@ static void let_stem_read_input(f8_net* net) {
 
 static int emit_steps(f8_net* net, int max_batch) {
     net->steps.clear();
-    int taps = 0;
+    int taps = 0, amaxes = 0, want_taps = 0, want_amaxes = 0;
+    for (size_t k = 0; k < net->outs.size(); ++k) { want_amaxes += net->outs[k].idx != 0; want_taps += k >= 1 && !net->outs[k].idx; }
     for (int i = 0; i < (int)net->nodes.size(); ++i) {
         const Node& nd = net->nodes[i];
+        if (nd.kind == N_UPSAMPLE && nd.argmax_k >= 0) { emit_argmax(net, nd.argmax_k, i); ++amaxes; continue; }      // the argmax launch interpolates itself
         if (nd.kind == N_ADD && nd.fused_into >= 0) continue;
         if (nd.kind == N_CONV && (nd.absorbed_by >= 0 || nd.dual_host >= 0)) continue;
         if (nd.kind == N_CONV && nd.chain_into >= 0 && nd.chain_into != i) continue;      // runs inside the chain launch of a later block
@@ -3151,9 +3216,12 @@ static int emit_steps(f8_net* net, int max_batch) {
         // again, and the arena reuses its space (at the end of the plan every tapped map would stay allocated through the whole run)
         const int k = output_index(net, st.out.t);
         if (k >= 1) { emit_output(net, k); ++taps; }
+        // ... and so does an argmax output, whatever its index (output 0 included: it has no copy-out launch at the end of the plan)
+        const int ka = st.out.t >= 0 ? argmax_index(net, st.out.t) : -1;
+        if (ka >= 0) { emit_argmax(net, ka, -1); ++amaxes; }
     }
-    if (taps != (int)net->outs.size() - 1) return fail(F8_ERR_UNSUPPORTED, "f8_net_finalize: an output tensor is written by no launch of the plan");
-    emit_output(net);
+    if (taps != want_taps || amaxes != want_amaxes) return fail(F8_ERR_UNSUPPORTED, "f8_net_finalize: an output tensor is written by no launch of the plan");
+    if (!net->outs[0].idx) emit_output(net);
     let_stem_read_input(net);
     return F8_OK;
 }
@@ -3836,6 +3904,20 @@ static int bind_step(f8_net* net, Step& st) {
             snprintf(kb, sizeof kb, "%s", st.inst ? tap_kernel_name(a.as_float) : output_kernel_name());
             st.args = a; break;
         }
+        case S_ARGMAX: {
+            const Tensor& sT = T[st.src_t]; const Tensor& oT = T[net->outs[st.out_k].t];
+            const bool fused = nd.kind == N_UPSAMPLE && nd.argmax_k == st.out_k;      // st.node: the upsample inside the launch, else the marked tensor's producer
+            ArgmaxArgs a{};
+            a.C = oT.C; a.Cs = sT.Cs; a.Hs = sT.H; a.Ws = sT.W; a.P = oT.H; a.Q = oT.W;
+            a.sh = fused ? nd.up_sh : 1; a.sw = fused ? nd.up_sw : 1;
+            while (fused && nd.up_mode == F8_UP_BILINEAR && (1 << a.k) < a.sh) ++a.k;
+            a.dSh = fast_divisor((uint32_t)a.sh);
+            a.dSw = fast_divisor((uint32_t)a.sw);
+            a.dQ4 = fast_divisor((uint32_t)((a.Q + 3) >> 2));
+            a.dP = fast_divisor((uint32_t)a.P);
+            snprintf(kb, sizeof kb, "%s", argmax_kernel_name(st.inst = argmax_inst(fused, fused && nd.up_mode == F8_UP_BILINEAR, net->outs[st.out_k].idx)));
+            st.args = a; break;
+        }
     }
     st.kernel = kb;
     return rc;
@@ -3861,7 +3943,7 @@ int f8_net_finalize(f8_net* net, int max_batch) {
     plan_depthwise_separable(net, max_batch);       // 1j: MobileNet-V1 depthwise-separable blocks in one launch (option fuse_dws)
     plan_depthwise_separable_7x7(net, max_batch);   // 1k: ... those on 7 x 7 output maps, and the average pool behind the last (option fuse_dws7)
     if (net->plan_bug >= 0) return fail(F8_ERR_STATE, "f8_net_finalize: planner bug: two fused launches claim conv node %d", net->plan_bug);
-    plan_tensor_forms(net);                         // 2:  which forms of each tensor exist in HBM
+    plan_tensor_forms(net, max_batch);              // 2:  which forms of each tensor exist in HBM
     int rc = emit_steps(net, max_batch);            // 3:  the launches, packed weights, algorithmic bytes / ops
     if (rc) return rc;
     if ((rc = layout_arena(net, max_batch))) return rc;   // 4: lifetimes, first-fit arena
@@ -3893,11 +3975,11 @@ size_t f8_net_describe(const f8_net* net, char* buf, size_t cap) {
 int f8_net_num_launches(const f8_net* net) { return (net && net->finalized) ? (int)net->steps.size() : F8_ERR_STATE; }
 size_t f8_net_arena_bytes(const f8_net* net) { return net ? net->arena_bytes : 0; }
 size_t f8_net_weight_bytes(const f8_net* net) { return net ? net->wblob.size() : 0; }
-int f8_net_output_fraclen(const f8_net* net) { return (net && !net->outs.empty()) ? net->tensors[net->outs[0].t].fl : F8_ERR_STATE; }
+int f8_net_output_fraclen(const f8_net* net) { return (net && !net->outs.empty()) ? (net->outs[0].idx ? 0 : net->tensors[net->outs[0].t].fl) : F8_ERR_STATE; }
 size_t f8_net_output_elems(const f8_net* net) {
     if (!net || net->outs.empty()) return 0;
     const Tensor& t = net->tensors[net->outs[0].t];
-    return (size_t)t.C * t.H * t.W;
+    return (size_t)(net->outs[0].idx ? 1 : t.C) * t.H * t.W;
 }
 
 int f8_net_launch_info(const f8_net* net, int i, int N, char* name, size_t name_cap, double* alg_bytes, double* alg_ops) {
@@ -4274,6 +4356,15 @@ static int run_step(const f8_net* net, const RunIO& io, const Step& st, int n0, 
             char* const buf = st.out_k ? (char*)io.bufs[st.out_k - 1] : (char*)io.out;
             a.out = buf + (size_t)n0 * a.C * a.HW * 4; a.err = chain_err; a.epoch = net->epoch;
             e = st.inst ? launch_tap(a, s) : launch_output(a, s);
+            break;
+        }
+        case S_ARGMAX: {
+            ArgmaxArgs a = std::get<ArgmaxArgs>(st.args);
+            a.x = (const int32_t*)fp(T[st.src_t].forms[st.src_f]); a.N = N;
+            char* const buf = st.out_k ? (char*)io.bufs[st.out_k - 1] : (char*)io.out;
+            a.out = buf + (size_t)n0 * a.P * a.Q * net->outs[st.out_k].idx;      // the sub-batch's first image: elements of index_bytes, not of 4
+            a.err = chain_err; a.epoch = net->epoch;
+            e = launch_argmax(a, st.inst, s);
             break;
         }
     }

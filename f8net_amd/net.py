@@ -44,6 +44,7 @@ class F8Net:
         self.out_float = True
         self.in_shape = None
         self.outputs = []       # after finalize: (C, H, W, fraclen, as_float) of every output, in the order of the output() calls
+        self.output_kinds = []  # after finalize, parallel to `outputs`: 0 int32 values, 1 float32 values, 2 argmax as uint8, 3 argmax as int32 (f8_net_output_kind)
         self.tap_ids = {}       # record_net: name -> tensor id of everything `taps=` accepts
         self.taps = ()          # record_net: the names marked as outputs 1 .., in that order
 
@@ -240,12 +241,40 @@ class F8Net:
             self.out_float = bool(as_float)
         return k
 
+    def output_argmax(self, src, dtype='u8'):
+        """Marks the channel argmax of tensor `src` as a network output (f8_net_output_argmax) and returns its index: the class map [N, H, W] of a
+        segmentation head ([N] for a [C, 1, 1] tensor: the predicted class), the smallest index winning a tie.  dtype 'u8' (at most 255 channels;
+        255 is the poison value) or 'i32'.  The tensor may be a value output as well (output())."""
+        sizes = {'u8': 1, 'i32': 4}
+        if dtype not in sizes:
+            raise ValueError(f"output_argmax dtype {dtype!r}: 'u8' or 'i32'")
+        k = check(self._L.f8_net_output_argmax(self._h, src, sizes[dtype]))
+        if k == 0:
+            self.out_float = False
+        return k
+
     def finalize(self, max_batch):
         check(self._L.f8_net_finalize(self._h, int(max_batch)))
         self.max_batch = int(max_batch)
         self.out_elems = int(self._L.f8_net_output_elems(self._h))
         self.outputs = [self.output_info(k) for k in range(check(self._L.f8_net_num_outputs(self._h)))]
+        self.output_kinds = [check(self._L.f8_net_output_kind(self._h, k)) for k in range(len(self.outputs))]
         return self
+
+    def _out_dtype(self, k):
+        """torch dtype of output k's buffer."""
+        import torch
+        return (torch.int32, torch.float32, torch.uint8, torch.int32)[self.output_kinds[k]]
+
+    def _output0(self, N, device, out):
+        """Output 0's buffer [N, out_elems] (a class map as output 0: [N, H * W]); allocated when `out` is None, checked when it is a class map."""
+        import torch
+        dt = self._out_dtype(0)
+        if out is None:
+            return torch.empty((N, self.out_elems), dtype=dt, device=device)
+        if self.output_kinds[0] >= 2 and (out.device != device or out.dtype != dt or not out.is_contiguous() or out.numel() != N * self.out_elems):
+            raise ValueError(f'F8Net: out= must be a contiguous {dt} tensor of [{N},{self.out_elems}] on {device} (output 0 is a class map)')
+        return out
 
     def output_info(self, k):
         """(C, H, W, fraclen, as_float) of output k (f8_net_output_info)."""
@@ -345,22 +374,24 @@ class F8Net:
 
     def _output_buffers(self, N, device, outs):
         """Hands the buffers of outputs 1 .. to the next run (f8_net_set_output_buffers; allocated when `outs` is None) and returns them
-        shaped [N, C, H, W].  A single-output net has none."""
+        shaped [N, C, H, W] — a class map (output_argmax): [N, H, W], uint8 or int32.  A single-output net has none."""
         import torch
         extra = self.outputs[1:]
         if not extra:
             if outs:
                 raise ValueError('F8Net: outs= given, but the net has a single output')
             return []
+        shapes = [(N, H, W) if kind >= 2 else (N, C, H, W) for (C, H, W, _, _), kind in zip(extra, self.output_kinds[1:])]
+        dtypes = [self._out_dtype(k) for k in range(1, len(self.outputs))]
         if outs is None:
-            outs = [torch.empty((N, C, H, W), dtype=torch.float32 if f else torch.int32, device=device) for C, H, W, _, f in extra]
+            outs = [torch.empty(shape, dtype=dt, device=device) for shape, dt in zip(shapes, dtypes)]
         if len(outs) != len(extra):
             raise ValueError(f'F8Net: {len(outs)} buffers for outputs 1 .. {len(extra)}')
         res = []
-        for o, (C, H, W, _, f) in zip(outs, extra):
-            if o.device != device or o.dtype != (torch.float32 if f else torch.int32) or not o.is_contiguous() or o.numel() != N * C * H * W:
-                raise ValueError(f'F8Net: an output buffer must be a contiguous {"float32" if f else "int32"} tensor of [{N},{C},{H},{W}] on {device}')
-            res.append(o.view(N, C, H, W))
+        for o, shape, dt in zip(outs, shapes, dtypes):
+            if o.device != device or o.dtype != dt or not o.is_contiguous() or o.numel() != math.prod(shape):
+                raise ValueError(f'F8Net: an output buffer must be a contiguous {str(dt).replace("torch.", "")} tensor of {list(shape)} on {device}')
+            res.append(o.view(shape))
         ptrs = (ctypes.c_void_p * len(res))(*[o.data_ptr() for o in res])
         check(self._L.f8_net_set_output_buffers(self._h, ptrs, len(res)))
         return res
@@ -372,9 +403,7 @@ class F8Net:
         import torch
         self._check_input(x)
         N = x.shape[0]
-        if out is None:
-            out = torch.empty((N, self.out_elems), dtype=torch.float32 if self.out_float else torch.int32,
-                              device=x.device)
+        out = self._output0(N, x.device, out)
         stream = torch.cuda.current_stream(x.device).cuda_stream
         with torch.cuda.device(x.device):
             outs = self._output_buffers(N, x.device, outs)      # (may raise: before the one-shot event is armed)
@@ -415,9 +444,7 @@ class F8Net:
         N = images.shape[0]
         if not (1 <= N <= self.max_batch):
             raise ValueError(f'F8Net.run_f32: batch {N} outside [1,{self.max_batch}]')
-        if out is None:
-            out = torch.empty((N, self.out_elems), dtype=torch.float32 if self.out_float else torch.int32,
-                              device=images.device)
+        out = self._output0(N, images.device, out)
         stream = torch.cuda.current_stream(images.device).cuda_stream
         with torch.cuda.device(images.device):
             outs = self._output_buffers(N, images.device, outs)
@@ -441,8 +468,7 @@ class F8Net:
         N = images.shape[0]
         if not (1 <= N <= self.max_batch):
             raise ValueError(f'F8Net.run_u8: batch {N} outside [1,{self.max_batch}]')
-        if out is None:
-            out = torch.empty((N, self.out_elems), dtype=torch.float32 if self.out_float else torch.int32, device=images.device)
+        out = self._output0(N, images.device, out)
         m = (ctypes.c_float * 3)(*[float(v) for v in mean]) if mean is not None else None
         s = (ctypes.c_float * 3)(*[float(v) for v in std]) if std is not None else None
         stream = torch.cuda.current_stream(images.device).cuda_stream
@@ -458,9 +484,7 @@ class F8Net:
         import torch
         self._check_input(x)
         N = x.shape[0]
-        if out is None:
-            out = torch.empty((N, self.out_elems), dtype=torch.float32 if self.out_float else torch.int32,
-                              device=x.device)
+        out = self._output0(N, x.device, out)
         n = self.num_launches
         ms = (ctypes.c_float * n)()
         stream = torch.cuda.current_stream(x.device).cuda_stream

@@ -24,6 +24,7 @@ opset-11 vocabulary is written directly from the integer graph — per op the no
     upsampling, bilinear           Cast(f32), Resize(linear, half_pixel; scales [1, 1, s, s]), Mul(4 s^2), Cast(i32)
     x.view(x.size(0), -1)          Shape, Gather, Unsqueeze, Concat, Reshape         (fix_resnet.py:371)
     classifier                     Gemm(transB=1), Cast(f32)                         (fix_resnet.py:383)
+    class map (output_argmax)      ArgMax(axis=1, keepdims=0, select_last_index=0), Cast(u8 | i32): the graph's last nodes, in place of the output's Cast
 
 Input `input` int32 [batch_size, C, H, W], output `output` float32 [batch_size, classes], dynamic batch axis, initializers
 named by state_dict key — as in the reference's files, including the tracer's merging of the identical arithmetic when
@@ -253,11 +254,18 @@ def export_graph(ig: IntGraph) -> bytes:
         if o.relu:
             y = w.cast(w.emit('Relu', [y]), onnx_io.INT32)
         name[t] = y
-    w.cast(name[ig.output], onnx_io.FLOAT if ig.output_float else onnx_io.INT32)
+    if ig.output_argmax:                                             # the class map: ArgMax over the channels (int64), cast to the index type
+        if ig.output_argmax not in ('u8', 'i32'):
+            raise ValueError(f"IntGraph.output_argmax {ig.output_argmax!r}: None, 'u8' or 'i32'")
+        out_type = onnx_io.UINT8 if ig.output_argmax == 'u8' else onnx_io.INT32
+        w.cast(w.emit('ArgMax', [name[ig.output]], {'axis': 1, 'keepdims': 0, 'select_last_index': 0}), out_type)
+    else:
+        out_type = onnx_io.FLOAT if ig.output_float else onnx_io.INT32
+        w.cast(name[ig.output], out_type)
     w.nodes[-1].outputs[0] = 'output'
-    classes = ig.ops[ig.output].weight.shape[0] if ig.ops[ig.output].kind == 'linear' else '?'
+    classes = ig.ops[ig.output].weight.shape[0] if ig.ops[ig.output].kind == 'linear' and not ig.output_argmax else '?'
     g = onnx_io.Graph(w.nodes, inits, [('input', onnx_io.INT32, in_dims)],
-                      [('output', onnx_io.FLOAT if ig.output_float else onnx_io.INT32, ['batch_size', classes])],
+                      [('output', out_type, ['batch_size', classes])],
                       opset=11, producer='f8net_amd', name='main_graph')
     return onnx_io.model_proto(g)
 

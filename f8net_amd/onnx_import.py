@@ -75,6 +75,7 @@ class IntGraph:
     output: int = -1
     output_float: bool = True
     input_signed: bool = False
+    output_argmax: str = None      # None | 'u8' | 'i32': the graph's result is the channel argmax of tensor `output` (F8Net.output_argmax) in that index type
 
     def layer_keys(self):
         return [o.key for o in self.ops if o.kind in ('conv', 'deconv', 'linear')]
@@ -246,7 +247,10 @@ class IntGraph:
                 ids[t] = net.avgpool(ids[o.src], o.kernel, o.stride, o.pad, shift=o.shift)
             elif o.kind == 'avgpool':
                 ids[t] = net.avgpool_sum(ids[o.src], AVGPOOL_SHIFT)
-        net.output(ids[self.output], as_float=self.output_float)
+        if self.output_argmax:
+            net.output_argmax(ids[self.output], self.output_argmax)
+        else:
+            net.output(ids[self.output], as_float=self.output_float)
         for k, v in (options or {}).items():
             net.set_option(k, v)
         return net.finalize(max_batch)
@@ -425,6 +429,28 @@ def import_graph(model, input_signed=False) -> IntGraph:
             val[out] = ('const', a['value'])
         elif op == 'Identity':
             val[out] = val[nd.inputs[0]]
+        elif op == 'ArgMax':
+            # The class map: ArgMax over the channels as the graph's LAST node, alone (int64, returned as int32) or followed by one Cast to UINT8 / INT32 /
+            # INT64 that is the output.  It is an output kind of the library, not a tensor: nothing else may read it.
+            e = val.get(nd.inputs[0])
+            if e is None or e[0] != 'T':
+                raise OnnxImportError('ArgMax: its input is not a layer result')
+            if a.get('axis', 0) != 1:
+                raise OnnxImportError(f'ArgMax: axis {a.get("axis", 0)}; only the channel argmax (axis=1) is built')
+            if a.get('select_last_index', 0) != 0:
+                raise OnnxImportError('ArgMax: select_last_index=1; the smallest index wins a tie here')
+            nxt = users.get(out, [])
+            last = out == g.outputs[0][0] and not nxt
+            cast = len(nxt) == 1 and nxt[0].op == 'Cast' and nxt[0].outputs[0] == g.outputs[0][0] and not users.get(nxt[0].outputs[0])
+            if not (last or cast):
+                raise OnnxImportError('ArgMax: its result feeds something other than the graph output (a class map is an output, not a tensor)')
+            val[out] = ('argmax', e[1], 'i32')
+        elif op in ('TopK', 'Softmax'):
+            raise OnnxImportError(f'{op}: not built (top-k maps and softmax / confidence outputs; ArgMax(axis=1) is)')
+        elif op == 'Cast' and val.get(nd.inputs[0], ('?',))[0] == 'argmax':
+            if a['to'] not in (onnx_io.UINT8, onnx_io.INT32, onnx_io.INT64):
+                raise OnnxImportError(f'Cast of an ArgMax to ONNX type {a["to"]}: UINT8, INT32 or INT64 (returned as int32)')
+            val[out] = ('argmax', val[nd.inputs[0]][1], 'u8' if a['to'] == onnx_io.UINT8 else 'i32')
         elif op == 'Cast':
             v = val[nd.inputs[0]]
             val[out] = v                                           # integer-valued throughout: casts carry no arithmetic
@@ -759,6 +785,9 @@ def import_graph(model, input_signed=False) -> IntGraph:
         else:
             raise OnnxImportError(f'unsupported ONNX op {op}')
     e = val.get(g.outputs[0][0])
+    if e is not None and e[0] == 'argmax':
+        ig.output, ig.output_argmax, ig.output_float = e[1], e[2], False
+        return ig
     if e is None or e[0] != 'T':
         raise OnnxImportError('graph output is not a layer result')
     ig.output = e[1]

@@ -185,6 +185,22 @@ class F8AvgPool2d(nn.Module):
         return res
 
 
+class F8ArgMax(nn.Module):
+    """torch.argmax(x, dim=1) on int32 device tensors with a HIP forward (`torch.ops.f8net.argmax_channels`): the class map [N, H, W] of logits
+    [N, C, H, W], the smallest index winning a tie.  dtype 'u8' (at most 255 channels) or 'i32'."""
+
+    def __init__(self, dtype='u8'):
+        super().__init__()
+        if dtype not in ('u8', 'i32'):
+            raise ValueError(f"F8ArgMax dtype {dtype!r}: 'u8' or 'i32'")
+        self.u8 = dtype == 'u8'
+        self.int_op_only = True
+
+    def forward(self, x):
+        _require_dev_i32(x, 'F8ArgMax')
+        return torch.ops.f8net.argmax_channels(x, self.u8)
+
+
 class F8ChannelShuffle(nn.Module):
     """nn.ChannelShuffle(groups) on int32 device tensors with a HIP forward (`torch.ops.f8net.channel_shuffle`): out[:, c] = x[:, (c % groups) *
     (C / groups) + c / groups].  A permutation of channels: the fraclen is the input's."""

@@ -20,6 +20,8 @@ the dispatcher.
     f8net::table_q(x, table, src_fl, in_fl, in_signed, out_fl)
                                                      table[requant(x) (+ 128 signed)]: any pointwise function as 256 int32 entries (f8_net_table;
                                                      f8net_amd.tables builds sigmoid, swish, tanh, ...; no reference call site)
+    f8net::argmax_channels(x, u8)                    the smallest channel index of the largest value per pixel, [N, C, H, W] -> [N, H, W] uint8 (u8, at most
+                                                     255 channels) or int32 (f8_net_output_argmax; the reference's forward_loss takes topk of the logits)
     f8net::net_forward(x, handle)                    IntModel.forward                 fix_resnet.py:352-383 (handle: register_net)
     f8net::net_forward_taps(x, handle)               ... of a net with further outputs (F8Net.output called more than once): all of them
     f8net::net_forward_f32(images, handle, normalize)  forward_loss input quantisation + IntModel.forward, fix_train.py:683-692
@@ -53,6 +55,7 @@ _DEF.define('maxpool(Tensor x, int k, int stride, int pad) -> Tensor')
 _DEF.define('channel_shuffle(Tensor x, int groups) -> Tensor')
 _DEF.define('mul_q(Tensor a, Tensor b, int a_src_fl, int b_src_fl, int a_fl, bool a_signed, int b_fl, bool b_signed, bool hard_gate_b, bool relu) -> Tensor')
 _DEF.define('table_q(Tensor x, Tensor table, int src_fl, int in_fl, bool in_signed, int out_fl) -> Tensor')
+_DEF.define('argmax_channels(Tensor x, bool u8) -> Tensor')
 _DEF.define('net_forward(Tensor x, int handle) -> Tensor')
 _DEF.define('net_forward_taps(Tensor x, int handle) -> Tensor[]')
 _DEF.define('net_forward_f32(Tensor images, int handle, bool normalize) -> Tensor')
@@ -390,6 +393,21 @@ def _table_q(x, table, src_fl, in_fl, in_signed, out_fl):
     return _plans.get(key, (table,), N, build).run(x).view(N, C, H, W)
 
 
+def _argmax_channels(x, u8):
+    """The class map of int32 logits (f8_net_output_argmax on the input of a one-launch net): out[n, h, w] = the smallest c with the largest
+    x[n, c, h, w], signed compare.  [N, C, H, W] -> [N, H, W], uint8 (u8: C <= 255, else the library's F8_ERR_UNSUPPORTED) or int32; C >= 2."""
+    _i32(x, 'argmax_channels')
+    x = x.contiguous()
+    N, C, H, W = x.shape
+
+    def build(n):
+        net = F8Net()
+        net.output_argmax(net.input(C, H, W, 0), 'u8' if u8 else 'i32')
+        return net.finalize(n)
+
+    return _plans.get(('argmax', x.device.index, C, H, W, bool(u8)), (), N, build).run(x).view(N, H, W)
+
+
 # ------------------------------------------------------------------------------------------ whole nets
 _nets = {}
 
@@ -422,7 +440,7 @@ def _net_forward_f32(images, handle, normalize):
 # ------------------------------------------------------------------------------------------ registration
 _CUDA = Library('f8net', 'IMPL', 'CUDA')
 for _n, _f in (('requant', _requant), ('relu_', _relu_), ('add_align_', _add_align_), ('conv2d', _conv2d), ('conv_transpose2d', _conv_transpose2d), ('linear', _linear),
-               ('avgpool_sum', _avgpool_sum), ('avgpool2d_sum', _avgpool2d_sum), ('maxpool', _maxpool), ('channel_shuffle', _channel_shuffle), ('mul_q', _mul_q), ('table_q', _table_q), ('net_forward', _net_forward), ('net_forward_taps', _net_forward_taps),
+               ('avgpool_sum', _avgpool_sum), ('avgpool2d_sum', _avgpool2d_sum), ('maxpool', _maxpool), ('channel_shuffle', _channel_shuffle), ('mul_q', _mul_q), ('table_q', _table_q), ('argmax_channels', _argmax_channels), ('net_forward', _net_forward), ('net_forward_taps', _net_forward_taps),
                ('net_forward_f32', _net_forward_f32)):
     _CUDA.impl(_n, _f)
 
@@ -443,9 +461,11 @@ _META.impl('maxpool', lambda x, k, stride, pad: x.new_empty(
 _META.impl('channel_shuffle', lambda x, groups: torch.empty_like(x))
 _META.impl('mul_q', lambda a, b, a_src_fl, b_src_fl, a_fl, a_signed, b_fl, b_signed, hard_gate_b, relu: torch.empty_like(a))
 _META.impl('table_q', lambda x, table, src_fl, in_fl, in_signed, out_fl: torch.empty_like(x))
-_META.impl('net_forward', lambda x, handle: x.new_empty((x.shape[0], _nets[handle].out_elems),
-                                                        dtype=torch.float32 if _nets[handle].out_float else torch.int32))
-_META.impl('net_forward_taps', lambda x, handle: [x.new_empty((x.shape[0], _nets[handle].out_elems), dtype=torch.float32 if _nets[handle].out_float else torch.int32)] + [
-    x.new_empty((x.shape[0], C, H, W), dtype=torch.float32 if f else torch.int32) for C, H, W, _, f in _nets[handle].outputs[1:]])
+_META.impl('argmax_channels', lambda x, u8: x.new_empty((x.shape[0], x.shape[2], x.shape[3]), dtype=torch.uint8 if u8 else torch.int32))
+_KIND_DTYPE = (torch.int32, torch.float32, torch.uint8, torch.int32)      # F8Net.output_kinds: int32 / float32 values, a class map as uint8 / int32 ([N, H, W])
+_META.impl('net_forward', lambda x, handle: x.new_empty((x.shape[0], _nets[handle].out_elems), dtype=_KIND_DTYPE[_nets[handle].output_kinds[0]]))
+_META.impl('net_forward_taps', lambda x, handle: [x.new_empty((x.shape[0], _nets[handle].out_elems), dtype=_KIND_DTYPE[_nets[handle].output_kinds[0]])] + [
+    x.new_empty((x.shape[0], H, W) if kind >= 2 else (x.shape[0], C, H, W), dtype=_KIND_DTYPE[kind])
+    for (C, H, W, _, _), kind in zip(_nets[handle].outputs[1:], _nets[handle].output_kinds[1:])])
 _META.impl('net_forward_f32', lambda x, handle, normalize: x.new_empty((x.shape[0], _nets[handle].out_elems),
                                                                       dtype=torch.float32 if _nets[handle].out_float else torch.int32))

@@ -327,7 +327,7 @@ int f8_net_linear(f8_net* net, int src, const f8_linear_desc* desc,
 /* Marks `src` as a network output; may be called up to F8_MAX_OUTPUTS times before f8_net_finalize, on any tensor of the graph
  * (a stage output for a detection head, the pooled vector in front of the classifier, any conv's result for a comparison with
  * the reference).  Returns the output's index: 0 for the first call (the same value as F8_OK), 1, 2, ... for the next ones.
- * F8_ERR_INVALID for a tensor that is an output already, F8_ERR_UNSUPPORTED for one output too many, F8_ERR_STATE after finalize.
+ * F8_ERR_INVALID for a tensor that is an output of this kind already (its argmax may be one as well: f8_net_output_argmax), F8_ERR_UNSUPPORTED for one output too many, F8_ERR_STATE after finalize.
  * as_float != 0: float32 (the `.float()` of fix_resnet.py:383), else int32; every output has its own.  Layout NCHW [N,C,H,W]
  * ([N,C] for pooled / linear results).  Output 0 is what the `output_dev` of the run entries receives; the others go to the
  * buffers of f8_net_set_output_buffers.  Every output exists in device memory as int32: a fused launch that would keep the
@@ -335,6 +335,33 @@ int f8_net_linear(f8_net* net, int src, const f8_linear_desc* desc,
  * pool out of the launch in front of it), and each further output adds one copy-out launch directly behind its producer. */
 #define F8_MAX_OUTPUTS 8
 int f8_net_output(f8_net* net, int src, int as_float);
+/* Channel argmax as an output kind: the class map of a segmentation net, the predicted class of a classifier.
+ *   out[n, h, w] = the smallest c in 0 .. C - 1 for which src[n, c, h, w] is maximal.
+ * The compare is over the int32 values the tensor holds — signed, after any wrap its producer defines (a bilinear upsample wraps modulo 2^32) —, the
+ * smallest index wins a tie (numpy.argmax(axis=1); torch.argmax(dim=1) as documented), and the fraclen plays no part.
+ * The result is [N, H, W] ([N] for a [C, 1, 1] tensor) of uint8_t (index_bytes = F8_IDX_U8) or int32_t (F8_IDX_I32; an ONNX int64 ArgMax is returned as
+ * int32).  It is an OUTPUT, not a tensor: it has no id, nothing in the net can read it, and it counts towards F8_MAX_OUTPUTS.  Returns the output's
+ * index as f8_net_output does; output 0 goes to `output_dev`, later ones to the buffers of f8_net_set_output_buffers, densely packed in their element
+ * type.  A tensor may carry one f8_net_output mark and one f8_net_output_argmax mark: logits and classes side by side.
+ * Rules: C >= 2; F8_IDX_U8 needs C <= 255 (index 255 is then never a class: it is the poison value); F8_IDX_I32 takes any C.
+ * F8_ERR_INVALID: a bad tensor id, C < 2, index_bytes neither constant, a second argmax mark on one tensor; F8_ERR_UNSUPPORTED: F8_IDX_U8 with C > 255,
+ * one output too many; F8_ERR_STATE after finalize.
+ * f8_net_output_info on such an output reports C = 1, the map's H and W, fraclen 0 and as_float = 0; f8_net_output_elems is H * W when it is output 0;
+ * f8_net_output_kind tells the element type of any output.
+ * Poison: a chain launch of the same run that gave up a halo wait (f8_net_check) turns the class map into 255 (uint8) or INT32_MIN (int32), as the value
+ * outputs turn into NaN / INT32_MIN.
+ * The plan: one launch of f8_argmax.hip directly behind its producer, as an output tap.  Token `argmax_u8:` / `argmax_i32:` — f8::argmax_i32t_kernel reads
+ * the marked tensor's int32 form, which therefore exists in device memory: a chain or fused block is cut there exactly where an output tap cuts it, and a
+ * classifier whose result is marked writes its int32 form, not the caller's buffer.  Tokens `upsample_bilinear+argmax_u8:`, `upsample_nearest+argmax_u8:`
+ * and the `_i32` pair (option fuse_argmax) — the marked tensor is the result of an f8_net_upsample that NOTHING else reads (no consumer, no value output):
+ * the upsample emits no launch and its result exists in no form; f8::upsample_argmax_kernel reads the upsample's SOURCE in int32 and interpolates per
+ * output pixel with the weights and the wrapping arithmetic of the upsample launch, then takes the argmax of the wrapped values: bit for bit the two launches.
+ * NOT built: top-k maps, softmax / confidence outputs, the argmax fused into a conv or deconv epilogue, align_corners. */
+#define F8_IDX_U8  1
+#define F8_IDX_I32 4
+int f8_net_output_argmax(f8_net* net, int src, int index_bytes);
+/* Element type of output k: 0 int32 values, 1 float32 values, 2 argmax as uint8, 3 argmax as int32.  F8_ERR_INVALID: k out of range. */
+int f8_net_output_kind(const f8_net* net, int k);
 /* Number of outputs marked so far. */
 int f8_net_num_outputs(const f8_net* net);
 /* Shape, fraclen and element type of output k (0 <= k < f8_net_num_outputs); any out-pointer may be NULL. */
@@ -493,7 +520,10 @@ int f8_net_check(f8_net* net);
  *               the device, and writes the int32 form only where something needs it.  Same values either way, bit for bit),
  *               fuse_table (default 1: a table whose only reader is the b operand of one broadcast f8_net_mul emits no launch where the map has fewer
  *               than 2^20 values an image — the measured rule, profiles/table_r15.md —, tokens table+chmul_*:; 2: on every size; 0: a table_*: launch
- *               and the mul launch.  Same values in every case, bit for bit)
+ *               and the mul launch.  Same values in every case, bit for bit),
+ *               fuse_argmax (default 1: an f8_net_output_argmax on the result of an f8_net_upsample that nothing else reads is ONE launch that interpolates
+ *               and reduces in registers, tokens upsample_bilinear+argmax_*: / upsample_nearest+argmax_*:, the upsampled tensor in no form; 0: the
+ *               upsample launch and an argmax_*: launch.  Same class map either way, bit for bit)
  *   scheduling: chunk56 / chunk28 / chunk14 (images per chunk of the fused blocks; -1 = derived from chunk_budget_mb, 0 = whole
  *               batch), chunk_budget_mb (memory-side cache a chunk's int32 stream may occupy), chunk_ds, chunk_opener,
  *               split_streams, graph, stagger, stagger_pipelined, stem_wpc, stem_grid_div (row-walking head on 1 / n of the CUs; 0 = by output form), wstat_grid_div (0 .. 32, default 0, environment F8_WSTAT_GRID_DIV: f8::conv1x1_wstat_kernel sizes its pixel groups for 1 / n of the CUs, at least one — tests walk long tile rings on small maps; 0 = all of them; the plan and the values do not move), check_device, check_input_range, pipeline_depth (2..4 runs in flight),
