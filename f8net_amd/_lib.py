@@ -62,6 +62,8 @@ SYMBOLS = [
     ('f8_net_upsample', _i, [_vp, _i, _i, _i, _i]),
     ('f8_net_slice', _i, [_vp, _i, _i, _i]),
     ('f8_net_channel_shuffle', _i, [_vp, _i, _i]),
+    ('f8_net_depth_to_space', _i, [_vp, _i, _i, _i]),
+    ('f8_net_space_to_depth', _i, [_vp, _i, _i, _i]),
     ('f8_net_mul', _i, [_vp, _i, _i, ctypes.POINTER(MulDesc)]),
     ('f8_net_hard_gate', _i, [_vp, _i]),
     ('f8_net_table', _i, [_vp, _i, ctypes.POINTER(TableDesc), ctypes.POINTER(ctypes.c_int32)]),

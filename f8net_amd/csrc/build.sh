@@ -36,20 +36,23 @@ $HIPCC $FLAGS -c f8_upsample.hip -o ../../build/f8_upsample.o 2> ../../build/f8_
 $HIPCC $FLAGS -c f8_deconv.hip -o ../../build/f8_deconv.o 2> ../../build/f8_deconv.log &
 $HIPCC $FLAGS -c f8_sumpool.hip -o ../../build/f8_sumpool.o 2> ../../build/f8_sumpool.log &
 $HIPCC $FLAGS -c f8_chanmap.hip -o ../../build/f8_chanmap.o 2> ../../build/f8_chanmap.log &
+$HIPCC $FLAGS -c f8_pixmap.hip -o ../../build/f8_pixmap.o 2> ../../build/f8_pixmap.log &
 $HIPCC $FLAGS -c f8_mul.hip -o ../../build/f8_mul.o 2> ../../build/f8_mul.log &
 $HIPCC $FLAGS -c f8_table.hip -o ../../build/f8_table.o 2> ../../build/f8_table.log &
 $HIPCC $FLAGS -c f8_argmax.hip -o ../../build/f8_argmax.o 2> ../../build/f8_argmax.log &
 $HIPCC $FLAGS -x hip -c f8_net.cpp -o ../../build/f8_net.o 2> ../../build/f8_net.log &
 wait
-for f in f8_kernels f8_fused f8_conv3x3 f8_stem f8_opener f8_ir f8_irk f8_irchain f8_p12 f8_wreg f8_wstat f8_s2conv f8_fc f8_chain f8_cchain f8_bchain f8_bcchain f8_dwmma f8_dwk f8_gconv f8_dws f8_dws7 f8_head_dws f8_pool f8_tap f8_concat f8_upsample f8_deconv f8_sumpool f8_chanmap f8_mul f8_table f8_argmax f8_net; do grep -E "error|warning:" ../../build/$f.log | grep -v Rpass || true; done
+for f in f8_kernels f8_fused f8_conv3x3 f8_stem f8_opener f8_ir f8_irk f8_irchain f8_p12 f8_wreg f8_wstat f8_s2conv f8_fc f8_chain f8_cchain f8_bchain f8_bcchain f8_dwmma f8_dwk f8_gconv f8_dws f8_dws7 f8_head_dws f8_pool f8_tap f8_concat f8_upsample f8_deconv f8_sumpool f8_chanmap f8_pixmap f8_mul f8_table f8_argmax f8_net; do grep -E "error|warning:" ../../build/$f.log | grep -v Rpass || true; done
 # a failed compile leaves the previous object in place: the link below would silently ship stale code
 if grep -lE "(^|[^a-z])error( generated|:)" ../../build/f8_*.log; then echo "ERROR: compile errors (logs above)"; exit 1; fi
-$HIPCC --offload-arch=gfx950 -shared -fPIC ../../build/f8_kernels.o ../../build/f8_fused.o ../../build/f8_conv3x3.o ../../build/f8_stem.o ../../build/f8_opener.o ../../build/f8_ir.o ../../build/f8_irk.o ../../build/f8_irchain.o ../../build/f8_p12.o ../../build/f8_wreg.o ../../build/f8_wstat.o ../../build/f8_s2conv.o ../../build/f8_fc.o ../../build/f8_chain.o ../../build/f8_cchain.o ../../build/f8_bchain.o ../../build/f8_bcchain.o ../../build/f8_dwmma.o ../../build/f8_dwk.o ../../build/f8_gconv.o ../../build/f8_dws.o ../../build/f8_dws7.o ../../build/f8_head_dws.o ../../build/f8_pool.o ../../build/f8_tap.o ../../build/f8_concat.o ../../build/f8_upsample.o ../../build/f8_deconv.o ../../build/f8_sumpool.o ../../build/f8_chanmap.o ../../build/f8_mul.o ../../build/f8_table.o ../../build/f8_argmax.o ../../build/f8_net.o -o $OUT
+$HIPCC --offload-arch=gfx950 -shared -fPIC ../../build/f8_kernels.o ../../build/f8_fused.o ../../build/f8_conv3x3.o ../../build/f8_stem.o ../../build/f8_opener.o ../../build/f8_ir.o ../../build/f8_irk.o ../../build/f8_irchain.o ../../build/f8_p12.o ../../build/f8_wreg.o ../../build/f8_wstat.o ../../build/f8_s2conv.o ../../build/f8_fc.o ../../build/f8_chain.o ../../build/f8_cchain.o ../../build/f8_bchain.o ../../build/f8_bcchain.o ../../build/f8_dwmma.o ../../build/f8_dwk.o ../../build/f8_gconv.o ../../build/f8_dws.o ../../build/f8_dws7.o ../../build/f8_head_dws.o ../../build/f8_pool.o ../../build/f8_tap.o ../../build/f8_concat.o ../../build/f8_upsample.o ../../build/f8_deconv.o ../../build/f8_sumpool.o ../../build/f8_chanmap.o ../../build/f8_pixmap.o ../../build/f8_mul.o ../../build/f8_table.o ../../build/f8_argmax.o ../../build/f8_net.o -o $OUT
 echo "built $(readlink -f $OUT)"
 # device probe of the float requantisation (f8_device.h requant_u8x4): a stand-alone binary, run by tests/test_gpu_requant_probe.py
 $HIPCC --offload-arch=gfx950 -O2 ../../tools/ubench/cvt_u8_probe.hip -o ../../tools/ubench/cvt_u8_probe.bin 2> ../../build/cvt_u8_probe.log || { echo "ERROR: cvt_u8_probe"; exit 1; }
 # device probe of the slice / shuffle byte kernels on sources with poisoned pad bytes (it includes f8_chanmap.hip): run by tests/test_gpu_chanmap_probe.py
 $HIPCC --offload-arch=gfx950 -O2 -std=c++17 ../../tools/ubench/chanmap_probe.hip -o ../../tools/ubench/chanmap_probe.bin 2> ../../build/chanmap_probe.log || { echo "ERROR: chanmap_probe"; exit 1; }
+# device probe of the depth_to_space / space_to_depth byte kernels on sources with poisoned pad bytes and guarded destinations, and the measurement of tools/ab_pixmap.py (it includes f8_pixmap.hip): run by tests/test_gpu_pixmap_probe.py
+$HIPCC --offload-arch=gfx950 -O2 -std=c++17 ../../tools/ubench/pixmap_probe.hip -o ../../tools/ubench/pixmap_probe.bin 2> ../../build/pixmap_probe.log || { echo "ERROR: pixmap_probe"; exit 1; }
 # device probe of the multiply byte kernels on operands with poisoned pad bytes (it includes f8_mul.hip): run by tests/test_gpu_mul_probe.py
 $HIPCC --offload-arch=gfx950 -O2 -std=c++17 ../../tools/ubench/mul_probe.hip -o ../../tools/ubench/mul_probe.bin 2> ../../build/mul_probe.log || { echo "ERROR: mul_probe"; exit 1; }
 # device probe of the table byte kernels on sources with poisoned pad bytes, and the replica measurement of tools/ab_table.py (it includes f8_table.hip): run by tests/test_gpu_table_probe.py

@@ -79,6 +79,7 @@ struct Options {
                                  // 0 = every pool on the walker; 2 = every pool with kernel >= 2 on the wide kernel (tests).  Same values on every leg
     int chanmap_i8 = 1;          // f8_net_slice / f8_net_channel_shuffle: 1 = the byte-gather mode where the result is read in at most two int8 formats and by nothing else (f8_chanmap.hip); 0 = always the int32 mode
     int fuse_shuffle = 1;        // a concat read by one i8-mode channel shuffle alone, `groups` operands of one width: 1 = one launch that reads the concat's operands (concat+shuffle{g}_i8:); 0 = two launches
+    int pixmap_i8 = 1;           // f8_net_depth_to_space / f8_net_space_to_depth: 1 = the byte-gather mode where the result is read in at most two int8 formats and by nothing else (f8_pixmap.hip); 0 = always the int32 mode
     int fuse_hgate = 1;          // a hard gate read by the b operand of one mul alone: 1 = no launch of its own, the mul launch reads the gate's int32 source (hgate+mul_*: / hgate+chmul_*:, f8_mul.hip); 0 = two launches
     int table_i8 = 1;            // f8_net_table: 1 = the byte-gather mode where the result is read in at most two int8 formats and by nothing else (table_i8:, f8_table.hip); 0 = always table_i32:
     int fuse_table = 1;          // a table read by the b operand of one broadcast mul alone: 1 = no launch of its own where the map has fewer than 2^20 values an image (the measured rule, fuse_table_rule in f8_net.cpp), the mul launch looks b up itself (table+chmul_*:, f8_table.hip); 2 = always; 0 = two launches
@@ -276,6 +277,21 @@ struct ChanMapArgs {
     int32_t K, groups, Cg;                               // table entries; 0 = slice, else the shuffle's groups (== K) and channels per group
     int32_t M, C, Cs;                                    // pixels N * H * W, real / padded output channels
     FastDiv dG;                                          // / groups
+    int32_t* out32;
+    QuantOut q[2];
+};
+
+// Depth-to-space and space-to-depth (f8_pixmap.hip; f8_net_depth_to_space, f8_net_space_to_depth): pure gathers between the channel axis and r x r
+// pixel blocks of one map, the formulas of include/f8net.h.  (C, Cs, P, Q) are the OUTPUT's real / padded channels and map, (Csrc, Cs_src, Hs, Ws) the
+// source's: s2d == 0: Csrc == C r^2, P == Hs r, Q == Ws r; s2d == 1: C == Csrc r^2, Hs == P r, Ws == Q r.  Mode i8: src[k] is the source in the int8
+// format of output form k (NHWC, Cs_src-byte rows), the launch moves bytes and only q[k].ptr / bias_xor are read.  Mode i32 (pixmap_i32_kernel): src[0]
+// is the source's int32 form (I32T); out32 and q[] as AddArgs.
+struct PixMapArgs {
+    const void* src[2];
+    int32_t N, C, Cs, P, Q;                              // images, the output's real / padded channels and map
+    int32_t Csrc, Cs_src, Hs, Ws;                        // the source's real / padded channels and map
+    int32_t r, s2d, crd;                                 // block; 0 = depth_to_space, 1 = space_to_depth; 0 = F8_ORDER_DCR, 1 = F8_ORDER_CRD
+    FastDiv dPQ, dQ, dHsWs, dWs, dR, dRR, dC;            // / (P * Q), / Q, / (Hs * Ws), / Ws, / r, / r^2, / Csrc (space_to_depth in DCR order: channel -> block)
     int32_t* out32;
     QuantOut q[2];
 };
@@ -771,6 +787,9 @@ hipError_t launch_deconv(const DeconvArgs& a, int inst, hipStream_t s);
 int chanmap_inst(const ChanMapArgs& a, bool i8);                   // f8_chanmap.hip.  0: chanmap_i32_kernel, 1 / 2: slice_i8_kernel<true> / <false>, 3 / 4 / 5: shuffle_i8_kernel<16> / <4> / <2>, 6: shuffle_i8_general_kernel
 const char* chanmap_kernel_name(int inst);
 hipError_t launch_chanmap(const ChanMapArgs& a, int inst, hipStream_t s);
+int pixmap_inst(const PixMapArgs& a, bool i8);                     // f8_pixmap.hip.  0: pixmap_i32_kernel, 1: pixmap_run_i8_kernel (DCR order, runs of a multiple of 16 channels), 2: pixmap_i8_general_kernel, 3 / 4: pixmap_crd2_i8_kernel<false> / <true> (CRD order, r = 2, a multiple of 4 channels; depth_to_space / space_to_depth)
+const char* pixmap_kernel_name(int inst);
+hipError_t launch_pixmap(const PixMapArgs& a, int inst, hipStream_t s);
 int mul_inst(const MulArgs& a, int mode);                          // f8_mul.hip.  mode 0: the stand-alone hard gate, 1: a mul that writes the int32 form, 2: int8 outputs only.  0: hgate_kernel; 1 .. 4: mul_i32_kernel<BCAST, GATE> = <0,0> <0,1> <1,0> <1,1>; 5 .. 10: mul_i8_kernel<BCAST, GATE, V> = <0,0,16> <0,0,4> <1,0,16> <1,0,4> <1,1,16> <1,1,4>
 const char* mul_kernel_name(int inst);
 int mul_vector_bytes(int inst);                                    // bytes of one operand a lane of the instance owns per step (16 / 4)

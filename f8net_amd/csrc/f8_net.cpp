@@ -97,7 +97,8 @@ enum ChainKind { C_NONE, C_STAGE, C_BASIC, C_BASIC_CLUSTER, C_IR };
 // N_MUL / N_HGATE (f8_net_mul, f8_net_hard_gate; f8_mul.hip) likewise: a mul READS like a conv — each operand's int8 form in the mul's format for it, written
 // by the operand's producer — and a hard gate reads its source's int32 form; no matcher counts either among a block's readers.
 // N_TABLE (f8_net_table; f8_table.hip) reads like a conv too — its source's int8 form in the format the table is indexed in — and cuts likewise.
-enum NodeKind { N_INPUT, N_CONV, N_ADD, N_MAXPOOL, N_AVGPOOL, N_LINEAR, N_CONCAT, N_UPSAMPLE, N_DECONV, N_SUMPOOL, N_SLICE, N_SHUFFLE, N_MUL, N_HGATE, N_TABLE };
+// N_D2S / N_S2D (f8_net_depth_to_space, f8_net_space_to_depth; f8_pixmap.hip) are gathers like N_SLICE / N_SHUFFLE, with their mode rule, and cut likewise.
+enum NodeKind { N_INPUT, N_CONV, N_ADD, N_MAXPOOL, N_AVGPOOL, N_LINEAR, N_CONCAT, N_UPSAMPLE, N_DECONV, N_SUMPOOL, N_SLICE, N_SHUFFLE, N_MUL, N_HGATE, N_TABLE, N_D2S, N_S2D };
 struct Node {
     int kind; int a = -1, b = -1; int out = -1;
     f8_conv_desc cd{};                 // conv / linear (as 1x1 conv)
@@ -111,11 +112,12 @@ struct Node {
     int pk = 0, pstride = 0, ppad = 0; // maxpool
     int shift = 0;                     // avgpool
     std::vector<int> srcs;             // concat: the operands in channel order (tensor ids; a = srcs[0])
-    bool bytes_mode = false;           // concat / upsample / slice / shuffle, pass 2: the launch moves bytes, its sources are held in the output's int8 formats; false: sources in int32
+    bool bytes_mode = false;           // concat / upsample / slice / shuffle / depth_to_space / space_to_depth, pass 2: the launch moves bytes, its sources are held in the output's int8 formats; false: sources in int32
     int up_mode = 0, up_sh = 1, up_sw = 1;      // upsample: F8_UP_NEAREST / F8_UP_BILINEAR, the scales
     int sum_k = 0, sum_stride = 0, sum_pad = 0;   // sumpool: the window (its fraclen shift is in the output tensor's fl alone)
     bool sum_wide = false;             // sumpool, pass 2: sumpool_wide_kernel (option sumpool_wide); false: the block walker
     int cm_first = 0, cm_groups = 0;   // slice: the first source channel; shuffle: the groups
+    int pm_block = 0, pm_order = 0;    // depth_to_space / space_to_depth: the block r and F8_ORDER_DCR / F8_ORDER_CRD
     int cm_cat = -1;                   // shuffle, pass 2: the concat node in front of it whose operands this launch reads itself (option fuse_shuffle), else -1
     f8_mul_desc md{};                  // mul: the operand formats and the ReLU (operands a, b)
     int mul_gate = -1;                 // mul, pass 2: the hard-gate node that produces b and runs inside this launch (option fuse_hgate), else -1
@@ -148,7 +150,7 @@ struct Node {
     size_t rc_off = 0, cc_off = 0; int ncc = 0;      // border-class tables (0 = single class)
     ConvTile tile{};
 };
-enum StepKind { S_INPUT, S_CONV, S_DW, S_ADD, S_MAXPOOL, S_AVGPOOL, S_REQUANT, S_OUTPUT, S_FUSED, S_STEMPOOL, S_IR, S_P12, S_CHAIN, S_BCHAIN, S_HEAD2, S_IRCHAIN, S_DWS, S_DWS7, S_IRK, S_GCONV, S_CONCAT, S_UPSAMPLE, S_DECONV, S_SUMPOOL, S_CHANMAP, S_MUL, S_HGATE, S_TABLE, S_ARGMAX };
+enum StepKind { S_INPUT, S_CONV, S_DW, S_ADD, S_MAXPOOL, S_AVGPOOL, S_REQUANT, S_OUTPUT, S_FUSED, S_STEMPOOL, S_IR, S_P12, S_CHAIN, S_BCHAIN, S_HEAD2, S_IRCHAIN, S_DWS, S_DWS7, S_IRK, S_GCONV, S_CONCAT, S_UPSAMPLE, S_DECONV, S_SUMPOOL, S_CHANMAP, S_MUL, S_HGATE, S_TABLE, S_ARGMAX, S_PIXMAP };
 // The kernel of a step whose kind has several, chosen once by the step's emitter (pass 3); bind_step, run_step and f8_net_autotune switch on it.
 //   S_CONV:  conv_igemm (f8_kernels.hip), the LDS-patch 3x3 (f8_conv3x3.hip), conv1x1_wreg (f8_wreg.hip), conv1x1_wstat (f8_wstat.hip),
 //            conv3x3s2_wreg (f8_s2conv.hip), the 1x1 conv + average pool (f8_pool.hip), the classifier fc_dense (f8_fc.hip)
@@ -162,7 +164,7 @@ struct Step {
     int res_t = -1, res_f = -1;        // residual (conv) or second operand (add)
     int src2_t = -1, src2_f = -1;      // dual GEMM: input of the second conv
     // The gather steps keep what they read HERE, with src_t = res_t = src2_t = -1 (select_sources fills it, gather_sources reads it):
-    //   cat_t     the source tensors.  S_CONCAT: its K operands in channel order.  S_UPSAMPLE: the one source.  S_CHANMAP: the one source, or the operands
+    //   cat_t     the source tensors.  S_CONCAT: its K operands in channel order.  S_UPSAMPLE / S_PIXMAP: the one source.  S_CHANMAP: the one source, or the operands
     //             of the concat the shuffle is fused with (Node::cm_cat).
     //   cat_f[k]  one form index per entry of cat_t.  Bytes mode (Node::bytes_mode): cat_f[k][j] = source j in the format of output form out.f8[k], empty
     //             where out.f8[k] < 0.  Otherwise cat_f[0][j] = source j's int32 form and cat_f[1] is empty.
@@ -179,7 +181,7 @@ struct Step {
     double bytes_per_img = 0, bytes_const = 0, ops_per_img = 0;
     double valu_per_img = 0;           // ESSENTIAL vector lane-operations per image (f8_net_launch_valu): what the reference's semantics need once the MFMAs are done
     // the launcher's arguments as far as the plan decides them (bind_step); run_step copies them and adds what the run decides
-    std::variant<std::monostate, ConvArgs, StemPoolArgs, FusedArgs, ChainArgs, BChainArgs, BCChainArgs, IRArgs, IRKArgs, IRChainArgs, DwsArgs, Dws7Args, DwArgs, GConvArgs, AddArgs, PoolArgs, AvgArgs, OutArgs, ConcatArgs, UpsampleArgs, ArgmaxArgs, DeconvArgs, SumPoolArgs, ChanMapArgs, MulArgs, TableArgs, TableMulArgs> args;
+    std::variant<std::monostate, ConvArgs, StemPoolArgs, FusedArgs, ChainArgs, BChainArgs, BCChainArgs, IRArgs, IRKArgs, IRChainArgs, DwsArgs, Dws7Args, DwArgs, GConvArgs, AddArgs, PoolArgs, AvgArgs, OutArgs, ConcatArgs, UpsampleArgs, ArgmaxArgs, DeconvArgs, SumPoolArgs, ChanMapArgs, PixMapArgs, MulArgs, TableArgs, TableMulArgs> args;
     int inst = 0;                      // the instance the launcher starts (the family's *_inst, f8_internal.h; bind_step)
     // S_CHAIN / S_BCHAIN: geometry, workgroups per image and resident per CU, the 7x7 cluster form (f8_cchain.hip)
     int C = 0, MID = 0, H = 0, W = 0, cin0 = 0, tiles = 0, wg_per_cu = 1; bool cluster = false;
@@ -330,7 +332,7 @@ static int64_t tensor_amax(f8_net* net, int t, int depth = 0) {
             const int sa = T.fl - net->tensors[nd.a].fl;     // 0 / 2k + 2
             constexpr int64_t cap = int64_t(1) << 40;
             if (a >= 0 && sa >= 0 && sa <= 31 && a <= (cap >> sa)) m = a << sa;
-        } else if (nd.kind == N_SLICE || nd.kind == N_SHUFFLE) {      // a subset / a permutation of the source's values
+        } else if (nd.kind == N_SLICE || nd.kind == N_SHUFFLE || nd.kind == N_D2S || nd.kind == N_S2D) {      // a subset / a permutation of the source's values
             m = tensor_amax(net, nd.a, depth + 1);
         } else if (nd.kind == N_MUL) {                       // the product of the two formats' clamp bounds
             m = (int64_t)(nd.md.a_signed ? 127 : 255) * (nd.md.b_signed ? 127 : 255);
@@ -459,6 +461,7 @@ static const OptKey kOptKeys[] = {
     {"sumpool_wide", "F8_SUMPOOL_WIDE", &Options::sumpool_wide, 0, 2, true},
     {"chanmap_i8", "F8_CHANMAP_I8", &Options::chanmap_i8, 0, 1, true},
     {"fuse_shuffle", "F8_FUSE_SHUFFLE", &Options::fuse_shuffle, 0, 1, true},
+    {"pixmap_i8", "F8_PIXMAP_I8", &Options::pixmap_i8, 0, 1, true},
     {"fuse_hgate", "F8_FUSE_HGATE", &Options::fuse_hgate, 0, 1, true},
     {"table_i8", "F8_TABLE_I8", &Options::table_i8, 0, 1, true},
     {"fuse_table", "F8_FUSE_TABLE", &Options::fuse_table, 0, 2, true},
@@ -874,6 +877,34 @@ int f8_net_channel_shuffle(f8_net* net, int src, int groups) {
     net->tensors[src].consumers.push_back(id);
     return t;
 }
+
+// depth_to_space (s2d == 0) / space_to_depth (s2d == 1): the checks and the node
+static int add_pixmap(f8_net* net, int src, int block, int order, bool s2d) {
+    const char* fn = s2d ? "f8_net_space_to_depth" : "f8_net_depth_to_space";
+    if (!net) return fail(F8_ERR_INVALID, "%s: null net", fn);
+    if (net->finalized) return fail(F8_ERR_STATE, "%s: net already finalized", fn);
+    if (const int rc = check_t(net, src, fn)) return rc;
+    if (block < 2) return fail(F8_ERR_INVALID, "%s: block %d must be >= 2", fn, block);
+    if (order != F8_ORDER_DCR && order != F8_ORDER_CRD) return fail(F8_ERR_INVALID, "%s: unknown order %d", fn, order);
+    if (block > 16) return fail(F8_ERR_UNSUPPORTED, "%s: blocks above 16 are not built (got %d)", fn, block);
+    const Tensor s = net->tensors[src];
+    const int rr = block * block;
+    if (!s2d && s.C % rr) return fail(F8_ERR_INVALID, "%s: the %d channels are no multiple of block^2 = %d", fn, s.C, rr);
+    if (s2d && (s.H % block || s.W % block)) return fail(F8_ERR_INVALID, "%s: the %d x %d map is no multiple of block %d", fn, s.H, s.W, block);
+    const int64_t C = s2d ? (int64_t)s.C * rr : s.C / rr, H = s2d ? s.H / block : (int64_t)s.H * block, W = s2d ? s.W / block : (int64_t)s.W * block;
+    // the bound of f8_net_upsample on the map, and the result's padded int32 rows below 2 GiB an image
+    if (H > INT32_MAX / 4 || W > INT32_MAX / 4 || H * W > INT32_MAX / 4 || C > INT32_MAX / 4 || H * W * ((C + 31) / 32 * 32) > INT32_MAX / 4)
+        return fail(F8_ERR_UNSUPPORTED, "%s: the result [%lld, %lld, %lld] exceeds 2 GiB per tensor", fn, (long long)C, (long long)H, (long long)W);
+    Node nd; nd.kind = s2d ? N_S2D : N_D2S; nd.a = src; nd.pm_block = block; nd.pm_order = order;
+    net->nodes.push_back(nd);
+    const int id = (int)net->nodes.size() - 1;
+    const int t = new_tensor(net, (int)C, (int)H, (int)W, s.fl, id);
+    net->nodes[id].out = t;
+    net->tensors[src].consumers.push_back(id);
+    return t;
+}
+int f8_net_depth_to_space(f8_net* net, int src, int block, int order) { return add_pixmap(net, src, block, order, false); }
+int f8_net_space_to_depth(f8_net* net, int src, int block, int order) { return add_pixmap(net, src, block, order, true); }
 
 int f8_net_mul(f8_net* net, int a, int b, const f8_mul_desc* desc) {
     if (!net) return fail(F8_ERR_INVALID, "f8_net_mul: null net");
@@ -2152,7 +2183,7 @@ static void plan_depthwise_separable_7x7(f8_net* net, int max_batch) {
 }
 
 // pass 2
-// The mode rule of the gathers — concat, nearest upsample, slice / shuffle.  Bytes mode: the result exists in one or two int8 forms
+// The mode rule of the gathers — concat, nearest upsample, slice / shuffle, depth_to_space / space_to_depth.  Bytes mode: the result exists in one or two int8 forms
 // and nothing else (no int32 reader, no network output: int8_forms_only); the sources are then asked for the result's formats and the launch moves
 // bytes.  Otherwise the sources are read as int32 (ask_sources).  Replication and channel selection commute with every element-wise function, the
 // requantisation among them, so upsample and a stand-alone slice / shuffle need no more; a concat also aligns fraclens and needs requant_commutes.
@@ -2345,6 +2376,11 @@ static void plan_tensor_forms(f8_net* net, int max_batch) {
                 ask_sources(net, nd.cm_cat >= 0 ? cat.srcs : std::vector<int>{nd.a}, s.fl, o.forms, nd.bytes_mode);
                 break;
             }
+            case N_D2S: case N_S2D:
+                // the mode rule alone, as a stand-alone slice / shuffle: a permutation of the source's values at the source's fraclen
+                nd.bytes_mode = opt.pixmap_i8 && int8_forms_only(net, nd.out);
+                ask_sources(net, {nd.a}, T[nd.a].fl, T[nd.out].forms, nd.bytes_mode);
+                break;
             case N_MUL: {
                 // reads like a conv with quant_input = 1: each operand's int8 form in the mul's format for it, written by the operand's producer (a == b in two
                 // formats: two forms of one tensor; a third format on a tensor: a requant: step, select_outputs).  A hard gate that only this mul's b operand
@@ -3008,6 +3044,25 @@ static int emit_chanmap(f8_net* net, int i, Step& st, std::vector<int>* extra) {
     return F8_OK;
 }
 
+// depth_to_space / space_to_depth
+static int emit_pixmap(f8_net* net, int i, Step& st, std::vector<int>* extra) {
+    const Node& nd = net->nodes[i];
+    const Tensor& o = net->tensors[nd.out];
+    st.kind = S_PIXMAP;
+    select_outputs_or_i32(net, nd.out, &st.out, extra);
+    if (const int rc = select_sources(net, st, {nd.a}, net->tensors[nd.a].fl, nd.bytes_mode, "depth_to_space / space_to_depth")) return rc;
+    const double px = (double)o.H * o.W;
+    if (nd.bytes_mode) {
+        st.bytes_per_img = 2.0 * px * o.C * out_forms8(st);      // every real byte read once and written once, per form
+    } else {
+        st.bytes_per_img = px * o.C * 4 + out_bytes(st, o, px);
+        st.valu_per_img = px * o.C * 3 * out_forms8(st);         // 3 per int8 value produced
+    }
+    char tok[48];
+    snprintf(tok, sizeof tok, "%s%d%s_%s:", nd.kind == N_S2D ? "s2d" : "d2s", nd.pm_block, nd.pm_order == F8_ORDER_CRD ? "crd" : "dcr", nd.bytes_mode ? "i8" : "i32");
+    st.name = tok + tname(net, nd.out);
+    return F8_OK;
+}
 
 // 256 bytes per int8 output form of `forms8` appended to the weight image: the entries requantised to each form (compose_byte_table).  Returns the offset.
 static size_t pack_byte_tables(f8_net* net, const std::vector<int32_t>& table, const Requant* r, int nr) {
@@ -3205,6 +3260,7 @@ static int emit_steps(f8_net* net, int max_batch) {
             case N_DECONV: rc = emit_deconv(net, i, st, &extra); break;
             case N_SUMPOOL: rc = emit_sumpool(net, i, st, &extra); break;
             case N_SLICE: case N_SHUFFLE: rc = emit_chanmap(net, i, st, &extra); break;
+            case N_D2S: case N_S2D: rc = emit_pixmap(net, i, st, &extra); break;
             case N_MUL: rc = emit_mul(net, i, st, &extra); break;
             case N_HGATE: rc = emit_hgate(net, i, st, &extra); break;
             case N_TABLE: rc = emit_table(net, i, st, &extra); break;
@@ -3824,6 +3880,21 @@ static int bind_step(f8_net* net, Step& st) {
             snprintf(kb, sizeof kb, "%s", chanmap_kernel_name(st.inst = chanmap_inst(a, nd.bytes_mode)));
             out_formats(a.q); st.args = a; break;
         }
+        case S_PIXMAP: {
+            const Tensor& sT = T[st.cat_t[0]]; const Tensor& oT = T[nd.out];
+            PixMapArgs a{};
+            a.C = oT.C; a.Cs = oT.Cs; a.P = oT.H; a.Q = oT.W; a.Csrc = sT.C; a.Cs_src = sT.Cs; a.Hs = sT.H; a.Ws = sT.W;
+            a.r = nd.pm_block; a.s2d = nd.kind == N_S2D; a.crd = nd.pm_order == F8_ORDER_CRD;
+            a.dPQ = fast_divisor((uint32_t)(a.P * a.Q));
+            a.dQ = fast_divisor((uint32_t)a.Q);
+            a.dHsWs = fast_divisor((uint32_t)(a.Hs * a.Ws));
+            a.dWs = fast_divisor((uint32_t)a.Ws);
+            a.dR = fast_divisor((uint32_t)a.r);
+            a.dRR = fast_divisor((uint32_t)(a.r * a.r));
+            a.dC = fast_divisor((uint32_t)a.Csrc);
+            snprintf(kb, sizeof kb, "%s", pixmap_kernel_name(st.inst = pixmap_inst(a, nd.bytes_mode)));
+            out_formats(a.q); st.args = a; break;
+        }
         case S_MUL: case S_HGATE: {
             const Tensor& oT = T[nd.out];
             MulArgs a{};
@@ -4320,6 +4391,14 @@ static int run_step(const f8_net* net, const RunIO& io, const Step& st, int n0, 
             a.M = N * T[st.out.t].H * T[st.out.t].W;
             fill_out(&a.out32, a.q);
             e = launch_chanmap(a, st.inst, s);
+            break;
+        }
+        case S_PIXMAP: {
+            PixMapArgs a = std::get<PixMapArgs>(st.args);
+            gather_sources(1, [&](int k, int) -> const void*& { return a.src[k]; });
+            a.N = N;
+            fill_out(&a.out32, a.q);
+            e = launch_pixmap(a, st.inst, s);
             break;
         }
         case S_TABLE: {

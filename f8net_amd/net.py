@@ -155,6 +155,33 @@ class F8Net:
             self._L.f8_net_set_label(self._h, t, label.encode())
         return t
 
+    def _pixmap(self, fn, src, block, order, label):
+        orders = {'dcr': 0, 'crd': 1}
+        if order not in orders:
+            raise ValueError(f"order {order!r}: 'crd' or 'dcr'")
+        t = check(fn(self._h, src, int(block), orders[order]))
+        if label:
+            self._L.f8_net_set_label(self._h, t, label.encode())
+        return t
+
+    def depth_to_space(self, src, block, order='crd', label=None):
+        """[C r^2, H, W] -> [C, H r, W r], r = block (f8_net_depth_to_space).  order 'crd': torch.nn.functional.pixel_shuffle / ONNX DepthToSpace
+        mode="CRD"; 'dcr': ONNX DepthToSpace's default mode.  The fraclen is the source's."""
+        return self._pixmap(self._L.f8_net_depth_to_space, src, block, order, label)
+
+    def space_to_depth(self, src, block, order='crd', label=None):
+        """[C, H r, W r] -> [C r^2, H, W], r = block, the inverse of depth_to_space for each order (f8_net_space_to_depth).  order 'crd':
+        torch.nn.functional.pixel_unshuffle; 'dcr': ONNX SpaceToDepth, TResNet's stem.  The fraclen is the source's."""
+        return self._pixmap(self._L.f8_net_space_to_depth, src, block, order, label)
+
+    def pixel_shuffle(self, src, r, label=None):
+        """torch.nn.functional.pixel_shuffle(x, r): depth_to_space in CRD order."""
+        return self.depth_to_space(src, r, 'crd', label)
+
+    def pixel_unshuffle(self, src, r, label=None):
+        """torch.nn.functional.pixel_unshuffle(x, r): space_to_depth in CRD order."""
+        return self.space_to_depth(src, r, 'crd', label)
+
     def mul(self, a, b, *, a_fl, a_signed, b_fl, b_signed=False, relu=False, label=None):
         """Fixed-point product of two activations (f8_net_mul): a requantised to (a_fl, a_signed) times b requantised to (b_fl, b_signed), at fraclen
         a_fl + b_fl.  b has a's shape (element-wise) or is [C, 1, 1] (a per-image channel gate: the scale of a squeeze-and-excitation block)."""

@@ -16,6 +16,9 @@ opset-11 vocabulary is written directly from the integer graph — per op the no
     channel concatenation          [Pow/Cast/Mul per operand at a smaller fraction length,] Concat(axis=1)
     channel slice                  Slice(starts [a], ends [b], axes [1], steps [1])
     channel shuffle                Reshape([-1, g, C / g, H, W]), Transpose(perm [0, 2, 1, 3, 4]), Reshape([-1, C, H, W])
+    depth_to_space                 DepthToSpace(blocksize, mode DCR | CRD)
+    space_to_depth, DCR            SpaceToDepth(blocksize)
+    space_to_depth, CRD            Reshape([-1, C, H / r, r, W / r, r]), Transpose(perm [0, 1, 3, 5, 2, 4]), Reshape([-1, C r^2, H / r, W / r])  (torch's pixel_unshuffle)
     fixed-point product            the requant of each operand as in front of a conv, [Unsqueeze(axes [2, 3]) of a [N, C] gate vector,] Mul [, Relu]
     hard gate relu6(x + 3)         Clip(x, -3 * 2^fl, 3 * 2^fl), Add(3 * 2^fl)
     256-entry table                the requant of the source as in front of a conv, [Add(128) for a signed index,] Gather(axis=0) on a 256-entry int32
@@ -226,6 +229,16 @@ def export_graph(ig: IntGraph) -> bytes:
             C, H, W = tensor_shapes(ig.ops[:t + 1])[t]
             v = w.emit('Reshape', [name[o.src], w.const([-1, o.groups, C // o.groups, H, W], np.int64)])
             v = w.emit('Transpose', [v], {'perm': [0, 2, 1, 3, 4]})
+            y = w.emit('Reshape', [v, w.const([-1, C, H, W], np.int64)])
+        elif o.kind == 'd2s':
+            y = w.emit('DepthToSpace', [name[o.src]], {'blocksize': int(o.block), 'mode': o.order.upper().encode()})
+        elif o.kind == 's2d' and o.order == 'dcr':
+            y = w.emit('SpaceToDepth', [name[o.src]], {'blocksize': int(o.block)})
+        elif o.kind == 's2d':                                        # x.view(N, C, H / r, r, W / r, r).permute(0, 1, 3, 5, 2, 4).reshape(N, C r^2, H / r, W / r)
+            C, H, W = tensor_shapes(ig.ops[:t + 1])[t]
+            r = int(o.block)
+            v = w.emit('Reshape', [name[o.src], w.const([-1, C // (r * r), H, r, W, r], np.int64)])
+            v = w.emit('Transpose', [v], {'perm': [0, 1, 3, 5, 2, 4]})
             y = w.emit('Reshape', [v, w.const([-1, C, H, W], np.int64)])
         elif o.kind == 'upsample':
             roi, sc = w.const(np.zeros(0, np.float32), np.float32), w.const([1.0, 1.0, float(o.scale[0]), float(o.scale[1])], np.float32)

@@ -37,7 +37,7 @@ class OnnxImportError(ValueError):
 
 @dataclass
 class IntOp:
-    kind: str                      # input | conv | deconv | linear | add | maxpool | avgpool | avgpool2d | concat | upsample | slice | shuffle | mul | hgate | table
+    kind: str                      # input | conv | deconv | linear | add | maxpool | avgpool | avgpool2d | concat | upsample | slice | shuffle | d2s | s2d | mul | hgate | table
     src: int = -1                  # tensor id (index into IntGraph.ops)
     src2: int = -1                 # add: the operand that is NOT shifted; mul: operand b (of src's shape, or [C, 1, 1])
     weight: np.ndarray = None
@@ -66,6 +66,8 @@ class IntOp:
     scale: tuple = None            # upsample: (scale_h, scale_w)
     first: int = 0                 # slice: the first channel
     channels: int = 0              # slice: how many; shuffle: the groups are in `groups`
+    block: int = 0                 # d2s / s2d (depth_to_space / space_to_depth): the block size r
+    order: str = None              # d2s / s2d: 'crd' | 'dcr' (include/f8net.h)
     output_padding: int = 0        # deconv (transposed conv; weight [cin, cout, k, k]): ONNX `output_padding`, both equal
 
 
@@ -122,7 +124,7 @@ class IntGraph:
             elif o.kind == 'concat':
                 for s, k in zip(o.srcs, o.shifts):
                     eq(t, s, k)
-            elif o.kind in ('maxpool', 'slice', 'shuffle'):
+            elif o.kind in ('maxpool', 'slice', 'shuffle', 'd2s', 's2d'):
                 eq(t, o.src, 0)
             elif o.kind == 'hgate':                  # 3 * 2^fl is a constant of the graph: the source's fraction length is pinned absolutely
                 if not 0 <= o.shift <= 28:
@@ -236,6 +238,10 @@ class IntGraph:
                 ids[t] = net.slice(ids[o.src], o.first, o.first + o.channels)
             elif o.kind == 'shuffle':
                 ids[t] = net.channel_shuffle(ids[o.src], o.groups)
+            elif o.kind == 'd2s':
+                ids[t] = net.depth_to_space(ids[o.src], o.block, o.order)
+            elif o.kind == 's2d':
+                ids[t] = net.space_to_depth(ids[o.src], o.block, o.order)
             elif o.kind == 'hgate':
                 ids[t] = net.hard_gate(ids[o.src])
             elif o.kind == 'table':
@@ -281,6 +287,10 @@ def tensor_shapes(ops):
             out.append((C, 1, 1))
         elif o.kind == 'slice':
             out.append((o.channels, H, W))
+        elif o.kind == 'd2s':
+            out.append((C // o.block ** 2, H * o.block, W * o.block))
+        elif o.kind == 's2d':
+            out.append((C * o.block ** 2, H // o.block, W // o.block))
         else:                                                        # add, shuffle, hgate, mul (operand a's shape)
             out.append((C, H, W))
     return out
@@ -549,11 +559,35 @@ def import_graph(model, input_signed=False) -> IntGraph:
         elif op == 'Transpose':
             # the middle of torch's channel_shuffle: view(N, g, C / g, H, W).transpose(1, 2).reshape(N, C, H, W)
             e = val.get(nd.inputs[0], ('?',))
-            if e[0] != 'reshape5':
-                raise OnnxImportError('Transpose of something other than an activation reshaped to [N, groups, C / groups, H, W]')
-            if list(a.get('perm', [])) != [0, 2, 1, 3, 4]:
+            if e[0] == 'reshape6':                                   # the middle of torch's pixel_unshuffle: view(N, C, H / r, r, W / r, r).permute(0, 1, 3, 5, 2, 4)
+                if list(a.get('perm', [])) != [0, 1, 3, 5, 2, 4]:
+                    raise OnnxImportError(f'Transpose of a 6-D view with perm {list(a.get("perm", []))}: only [0, 1, 3, 5, 2, 4] (space_to_depth in CRD order)')
+                val[out] = ('s2d_t',) + e[1:]
+            elif e[0] != 'reshape5':
+                raise OnnxImportError('Transpose of something other than an activation reshaped to [N, groups, C / groups, H, W] or [N, C, H / r, r, W / r, r] '
+                                      'by a Reshape with a constant shape')
+            elif list(a.get('perm', [])) != [0, 2, 1, 3, 4]:
                 raise OnnxImportError(f'Transpose with perm {list(a.get("perm", []))}: only [0, 2, 1, 3, 4] (the channel shuffle)')
-            val[out] = ('shuffle_t',) + e[1:]
+            else:
+                val[out] = ('shuffle_t',) + e[1:]
+        elif op == 'Reshape' and val.get(nd.inputs[0], ('?',))[0] == 's2d_t':      # back to [N | 0 | -1, C r^2, H / r, W / r]
+            e, shape = val[nd.inputs[0]], int_list(nd.inputs[1])
+            C, H, W = tensor_shapes(ig.ops)[e[1]]
+            r = e[2]
+            if shape is None:
+                raise OnnxImportError('Reshape behind the space_to_depth Transpose: its shape is missing or not a constant')
+            if len(shape) != 4 or shape[1:] != [C * r * r, H // r, W // r]:
+                raise OnnxImportError(f'Reshape behind the space_to_depth Transpose to {shape}: expected [N, {C * r * r}, {H // r}, {W // r}]')
+            ig.ops.append(IntOp('s2d', src=e[1], block=r, order='crd'))
+            val[out] = ('T', len(ig.ops) - 1)
+        elif op == 'Reshape' and val.get(nd.inputs[0], ('?',))[0] == 'T' and int_list(nd.inputs[1]) is not None and len(int_list(nd.inputs[1])) == 6:
+            # the head of torch's pixel_unshuffle: view(N, C, H / r, r, W / r, r)
+            e, shape = val[nd.inputs[0]], int_list(nd.inputs[1])
+            C, H, W = tensor_shapes(ig.ops)[e[1]]
+            _, c6, h, ri, w_, rj = shape
+            if c6 != C or ri < 2 or ri != rj or h * ri != H or w_ * rj != W:
+                raise OnnxImportError(f'Reshape of a [{C}, {H}, {W}] activation to {shape}: a 6-D view must factor the map as [N, {C}, H / r, r, W / r, r]')
+            val[out] = ('reshape6', e[1], ri)
         elif op == 'Reshape' and val.get(nd.inputs[0], ('?',))[0] in ('T', 'shuffle_t') and int_list(nd.inputs[1]) is not None and \
                 len(int_list(nd.inputs[1])) in (4, 5):
             e, shape = val[nd.inputs[0]], int_list(nd.inputs[1])
@@ -571,6 +605,22 @@ def import_graph(model, input_signed=False) -> IntGraph:
                     raise OnnxImportError(f'Reshape behind the shuffle\'s Transpose to {shape}: expected [N, {C}, {H}, {W}]')
                 ig.ops.append(IntOp('shuffle', src=e[1], groups=e[2]))
                 val[out] = ('T', len(ig.ops) - 1)
+        elif op in ('DepthToSpace', 'SpaceToDepth') and val.get(nd.inputs[0], ('?',))[0] == 'T':
+            src = val[nd.inputs[0]][1]
+            C, H, W = tensor_shapes(ig.ops)[src]
+            r = int(a.get('blocksize', 0))
+            mode = a.get('mode', b'DCR')
+            mode = (mode.decode() if isinstance(mode, bytes) else str(mode)) if op == 'DepthToSpace' else 'DCR'
+            if mode not in ('DCR', 'CRD'):
+                raise OnnxImportError(f'DepthToSpace mode {mode!r}: only DCR and CRD')
+            if r < 2 or r > 16:
+                raise OnnxImportError(f'{op} blocksize {r}: outside 2 .. 16 (f8_net_depth_to_space)')
+            if op == 'DepthToSpace' and C % (r * r):
+                raise OnnxImportError(f'DepthToSpace blocksize {r} on {C} channels: no multiple of {r * r}')
+            if op == 'SpaceToDepth' and (H % r or W % r):
+                raise OnnxImportError(f'SpaceToDepth blocksize {r} on a {H} x {W} map: no multiple of {r}')
+            ig.ops.append(IntOp('d2s' if op == 'DepthToSpace' else 's2d', src=src, block=r, order=mode.lower()))
+            val[out] = ('T', len(ig.ops) - 1)
         elif op == 'Unsqueeze' and val.get(nd.inputs[0], ('?',))[0] in ('T', 'clip'):
             val[out] = val[nd.inputs[0]]                           # a [N, C] gate vector lifted to [N, C, 1, 1] in front of a Mul: no arithmetic
         elif op == 'Gather' and val.get(nd.inputs[0], ('?',))[0] in ('init', 'T', 'clip'):

@@ -218,6 +218,40 @@ class F8ChannelShuffle(nn.Module):
         return res
 
 
+class F8PixelShuffle(nn.Module):
+    """nn.PixelShuffle(r) on int32 device tensors with a HIP forward (`torch.ops.f8net.depth_to_space`, order 'crd'): [N, C r^2, H, W] ->
+    [N, C, H r, W r].  A rearrangement of values: the fraclen is the input's."""
+
+    def __init__(self, upscale_factor):
+        super().__init__()
+        self.upscale_factor = int(upscale_factor)
+        self.int_op_only = True
+
+    def forward(self, x):
+        _require_dev_i32(x, 'F8PixelShuffle')
+        res = torch.ops.f8net.depth_to_space(x, self.upscale_factor, 'crd')
+        if hasattr(x, 'output_fraclen'):
+            setattr(res, 'output_fraclen', x.output_fraclen)
+        return res
+
+
+class F8PixelUnshuffle(nn.Module):
+    """nn.PixelUnshuffle(r) on int32 device tensors with a HIP forward (`torch.ops.f8net.space_to_depth`, order 'crd'): [N, C, H r, W r] ->
+    [N, C r^2, H, W].  A rearrangement of values: the fraclen is the input's."""
+
+    def __init__(self, downscale_factor):
+        super().__init__()
+        self.downscale_factor = int(downscale_factor)
+        self.int_op_only = True
+
+    def forward(self, x):
+        _require_dev_i32(x, 'F8PixelUnshuffle')
+        res = torch.ops.f8net.space_to_depth(x, self.downscale_factor, 'crd')
+        if hasattr(x, 'output_fraclen'):
+            setattr(res, 'output_fraclen', x.output_fraclen)
+        return res
+
+
 class F8HardSwish(nn.Module):
     """Six times nn.Hardswish on int32 device tensors with a HIP forward (`torch.ops.f8net.mul_q` with the hard gate on its own operand):
     x_q * relu6(x + 3) with x_q = x requantised to (x_fl, x_signed) and the gate, 0 .. 6, requantised to unsigned g_fl; the result's fraclen is

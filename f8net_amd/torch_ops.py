@@ -14,6 +14,9 @@ the dispatcher.
     f8net::avgpool_sum(x)                            FXQAvgPool2d int branch          fix_quant_ops.py:126-134
     f8net::maxpool(x, k, stride, pad)                head max-pool                    fix_resnet.py:358-359
     f8net::channel_shuffle(x, groups)                torch.nn.functional.channel_shuffle on int32 (f8_net_channel_shuffle; no reference call site)
+    f8net::depth_to_space(x, block, order)           [N, C r^2, H, W] -> [N, C, H r, W r]; order 'crd' = torch.nn.functional.pixel_shuffle, 'dcr' = ONNX
+                                                     DepthToSpace's default (f8_net_depth_to_space; no reference call site)
+    f8net::space_to_depth(x, block, order)           the inverse; 'crd' = pixel_unshuffle, 'dcr' = ONNX SpaceToDepth (f8_net_space_to_depth)
     f8net::mul_q(a, b, a_src_fl, b_src_fl, a_fl, a_signed, b_fl, b_signed, hard_gate_b, relu)
                                                      requant(a) * requant(b), b of a's shape or [N, C, 1, 1]; hard_gate_b: b is relu6(b + 3) in fixed point
                                                      first (f8_net_mul, f8_net_hard_gate; no reference call site)
@@ -53,6 +56,8 @@ _DEF.define('avgpool_sum(Tensor x) -> Tensor')
 _DEF.define('avgpool2d_sum(Tensor x, int k, int stride, int pad) -> Tensor')
 _DEF.define('maxpool(Tensor x, int k, int stride, int pad) -> Tensor')
 _DEF.define('channel_shuffle(Tensor x, int groups) -> Tensor')
+_DEF.define('depth_to_space(Tensor x, int block, str order) -> Tensor')
+_DEF.define('space_to_depth(Tensor x, int block, str order) -> Tensor')
 _DEF.define('mul_q(Tensor a, Tensor b, int a_src_fl, int b_src_fl, int a_fl, bool a_signed, int b_fl, bool b_signed, bool hard_gate_b, bool relu) -> Tensor')
 _DEF.define('table_q(Tensor x, Tensor table, int src_fl, int in_fl, bool in_signed, int out_fl) -> Tensor')
 _DEF.define('argmax_channels(Tensor x, bool u8) -> Tensor')
@@ -306,6 +311,50 @@ def _channel_shuffle(x, groups):
     return _plans.get(('shuffle', x.device.index, C, H, W, groups), (), N, build).run(x).view(N, C, H, W)
 
 
+def _pixmap_shape(x, block, order, s2d):
+    """The result's [N, C, H, W]; the refusals of f8_net_depth_to_space / f8_net_space_to_depth as ValueError (the meta impl has no handle to ask)."""
+    N, C, H, W = x.shape
+    r = int(block)
+    if order not in ('crd', 'dcr'):
+        raise ValueError(f"order {order!r}: 'crd' or 'dcr'")
+    if r < 2 or r > 16:
+        raise ValueError(f'block {r}: 2 .. 16')
+    if s2d:
+        if H % r or W % r:
+            raise ValueError(f'space_to_depth: the {H} x {W} map is no multiple of block {r}')
+        return N, C * r * r, H // r, W // r
+    if C % (r * r):
+        raise ValueError(f'depth_to_space: the {C} channels are no multiple of block^2 = {r * r}')
+    return N, C // (r * r), H * r, W * r
+
+
+def _pixmap(x, block, order, s2d):
+    who = 'space_to_depth' if s2d else 'depth_to_space'
+    _i32(x, who)
+    x = x.contiguous()
+    N, C, H, W = x.shape
+    shape = _pixmap_shape(x, block, order, s2d)
+
+    def build(n):
+        net = F8Net()
+        t = net.input(C, H, W, 0)
+        t = net.space_to_depth(t, block, order) if s2d else net.depth_to_space(t, block, order)
+        net.output(t, as_float=False)
+        return net.finalize(n)
+
+    return _plans.get((who, x.device.index, C, H, W, int(block), order), (), N, build).run(x).view(shape)
+
+
+def _depth_to_space(x, block, order):
+    """f8_net_depth_to_space: [N, C r^2, H, W] -> [N, C, H r, W r]; order 'crd' is torch.nn.functional.pixel_shuffle."""
+    return _pixmap(x, block, order, False)
+
+
+def _space_to_depth(x, block, order):
+    """f8_net_space_to_depth: [N, C, H r, W r] -> [N, C r^2, H, W]; order 'crd' is torch.nn.functional.pixel_unshuffle."""
+    return _pixmap(x, block, order, True)
+
+
 def _mul_q(a, b, a_src_fl, b_src_fl, a_fl, a_signed, b_fl, b_signed, hard_gate_b, relu):
     """int_op_only_fix_quant(a, 8, a_fl, a_src_fl, a_signed) * int_op_only_fix_quant(b', 8, b_fl, b_src_fl, b_signed) with b' = b, or
     clamp(b, -3 * 2^b_src_fl, 3 * 2^b_src_fl) + 3 * 2^b_src_fl when hard_gate_b (f8_net_mul / f8_net_hard_gate): [N, C, H, W] x ([N, C, H, W] |
@@ -440,7 +489,7 @@ def _net_forward_f32(images, handle, normalize):
 # ------------------------------------------------------------------------------------------ registration
 _CUDA = Library('f8net', 'IMPL', 'CUDA')
 for _n, _f in (('requant', _requant), ('relu_', _relu_), ('add_align_', _add_align_), ('conv2d', _conv2d), ('conv_transpose2d', _conv_transpose2d), ('linear', _linear),
-               ('avgpool_sum', _avgpool_sum), ('avgpool2d_sum', _avgpool2d_sum), ('maxpool', _maxpool), ('channel_shuffle', _channel_shuffle), ('mul_q', _mul_q), ('table_q', _table_q), ('argmax_channels', _argmax_channels), ('net_forward', _net_forward), ('net_forward_taps', _net_forward_taps),
+               ('avgpool_sum', _avgpool_sum), ('avgpool2d_sum', _avgpool2d_sum), ('maxpool', _maxpool), ('channel_shuffle', _channel_shuffle), ('depth_to_space', _depth_to_space), ('space_to_depth', _space_to_depth), ('mul_q', _mul_q), ('table_q', _table_q), ('argmax_channels', _argmax_channels), ('net_forward', _net_forward), ('net_forward_taps', _net_forward_taps),
                ('net_forward_f32', _net_forward_f32)):
     _CUDA.impl(_n, _f)
 
@@ -459,6 +508,8 @@ _META.impl('avgpool2d_sum', lambda x, k, stride, pad: x.new_empty(
 _META.impl('maxpool', lambda x, k, stride, pad: x.new_empty(
     (x.shape[0], x.shape[1], (x.shape[2] + 2 * pad - k) // stride + 1, (x.shape[3] + 2 * pad - k) // stride + 1)))
 _META.impl('channel_shuffle', lambda x, groups: torch.empty_like(x))
+_META.impl('depth_to_space', lambda x, block, order: x.new_empty(_pixmap_shape(x, block, order, False)))
+_META.impl('space_to_depth', lambda x, block, order: x.new_empty(_pixmap_shape(x, block, order, True)))
 _META.impl('mul_q', lambda a, b, a_src_fl, b_src_fl, a_fl, a_signed, b_fl, b_signed, hard_gate_b, relu: torch.empty_like(a))
 _META.impl('table_q', lambda x, table, src_fl, in_fl, in_signed, out_fl: torch.empty_like(x))
 _META.impl('argmax_channels', lambda x, u8: x.new_empty((x.shape[0], x.shape[2], x.shape[3]), dtype=torch.uint8 if u8 else torch.int32))

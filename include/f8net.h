@@ -222,6 +222,26 @@ int f8_net_upsample(f8_net* net, int src, int mode, int scale_h, int scale_w);
 int f8_net_slice(f8_net* net, int src, int first, int channels);
 int f8_net_channel_shuffle(f8_net* net, int src, int groups);
 
+/* Depth-to-space and space-to-depth (nn.PixelShuffle of ESPCN / EDSR / Real-ESRGAN and of a Dense Upsampling Convolution head; nn.PixelUnshuffle,
+ * TResNet's SpaceToDepth stem, YOLO's reorg / Focus).  Both move values between the channel axis and the spatial axes of one map in square blocks
+ * of r = block pixels a side; there is no arithmetic at all — no shift, no clamp, no ReLU — and the fraclen is the source's.
+ *   f8_net_depth_to_space   [C r^2, H, W] -> [C, H r, W r].
+ *                           F8_ORDER_CRD: out[n, c, h r + i, w r + j] = src[n, c r^2 + i r + j, h, w]     (torch pixel_shuffle, ONNX mode="CRD")
+ *                           F8_ORDER_DCR: out[n, c, h r + i, w r + j] = src[n, (i r + j) C + c, h, w]     (ONNX DepthToSpace's default mode)
+ *   f8_net_space_to_depth   [C, H r, W r] -> [C r^2, H, W], the exact inverse of the above for each order: CRD is torch pixel_unshuffle, DCR is ONNX
+ *                           SpaceToDepth and TResNet's stem.
+ * Both return the tensor id.  F8_ERR_INVALID: a bad tensor id, block < 2, an order other than the two, C not a multiple of r^2 (depth_to_space), H or
+ * W not a multiple of r (space_to_depth).  F8_ERR_UNSUPPORTED: block > 16, a result beyond the 2 GiB per tensor of the other ops.  F8_ERR_STATE
+ * after finalize.  Only square blocks.
+ * The plan runs each as one launch of f8_pixmap.hip, its mode shown by its token: `d2s{r}{crd|dcr}_i8:` / `s2d{r}{crd|dcr}_i8:` — the result is read
+ * in at most two int8 formats and by nothing else — have the source's producer write those formats and move bytes; `..._i32:` read the source's
+ * int32 form (option pixmap_i8 = 0: always).  Same values either way.  A tensor read by one of them exists in device memory: no fused block or
+ * chain launch keeps it on chip (it cuts a launch as an output tap does). */
+#define F8_ORDER_DCR 0   /* ONNX DepthToSpace mode="DCR" (its default), ONNX SpaceToDepth, TResNet */
+#define F8_ORDER_CRD 1   /* ONNX DepthToSpace mode="CRD" = torch pixel_shuffle / pixel_unshuffle    */
+int f8_net_depth_to_space(f8_net* net, int src, int block, int order);
+int f8_net_space_to_depth(f8_net* net, int src, int block, int order);
+
 /* Fixed-point multiply of two activations and the hard gate (the scale of a squeeze-and-excitation block: SENet / SE-ResNet, MobileNet-V3, MnasNet-A1,
  * RegNetY, GhostNet; hard-swish: MobileNet-V3, LCNet).  The reference defines no such class; the semantics are fixed here in its own terms
  * (int_op_only_fix_quant, fix_quant_ops.py:91-112, on each operand; format x format -> int32, the fraction lengths add).
@@ -513,6 +533,9 @@ int f8_net_check(f8_net* net);
  *               slice_i32: / shuffle{g}_i32:.  Same values either way, bit for bit),
  *               fuse_shuffle (default 1: a concat of `groups` operands of one width that only an i8-mode shuffle reads emits no launch; the shuffle
  *               launch reads the operands, token concat+shuffle{g}_i8:; 0: two launches.  Same values either way, bit for bit),
+ *               pixmap_i8 (default 1: a depth_to_space or space_to_depth whose result is read in at most two int8 formats and by nothing else moves
+ *               bytes of its source's int8 forms, plan tokens d2s{r}{crd|dcr}_i8: / s2d{r}{crd|dcr}_i8:; 0: every one runs f8::pixmap_i32_kernel on the
+ *               int32 form, tokens ..._i32:.  Same values either way, bit for bit),
  *               fuse_hgate (default 1: a hard gate whose only reader is the b operand of one f8_net_mul emits no launch; the mul launch reads the gate's
  *               source in int32, tokens hgate+mul_*: / hgate+chmul_*:; 0: an hgate: launch and the mul launch.  Same values either way, bit for bit),
  *               table_i8 (default 1: an f8_net_table whose result is read in at most two int8 formats and by nothing else gathers bytes from host-composed

@@ -41,7 +41,7 @@ PLANNING = {
 }
 # keys added after the digest's matrix was fixed: each alone at every value, appended behind the matrix and only where the library under
 # test knows the key — so a parent library yields exactly its old lines and the lines of a new key are additions (never part of the random mixes)
-LATER = {'fuse_irk': (0, 1), 'grouped': (0, 2), 'igemm_tile': (0, 4), 'concat_i8': (0, 1), 'upsample_i8': (0, 1), 'sumpool_wide': (0, 2), 'chanmap_i8': (0, 1), 'fuse_shuffle': (0, 1), 'fuse_hgate': (0, 1), 'table_i8': (0, 1), 'fuse_table': (0, 2)}
+LATER = {'fuse_irk': (0, 1), 'grouped': (0, 2), 'igemm_tile': (0, 4), 'concat_i8': (0, 1), 'upsample_i8': (0, 1), 'sumpool_wide': (0, 2), 'chanmap_i8': (0, 1), 'fuse_shuffle': (0, 1), 'pixmap_i8': (0, 1), 'fuse_hgate': (0, 1), 'table_i8': (0, 1), 'fuse_table': (0, 2)}
 
 
 def option_sets(defaults):
