@@ -24,6 +24,11 @@ class ConvDesc(ctypes.Structure):
                  'input_signed', 'quant_input', 'relu')]
 
 
+class ConvGeom(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in
+                ('kh', 'kw', 'stride_h', 'stride_w', 'pad_top', 'pad_left', 'pad_bottom', 'pad_right', 'dilation')]
+
+
 class LinearDesc(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in
                 ('in_features', 'out_features', 'weight_fl', 'input_fl', 'input_signed', 'quant_input')]
@@ -56,6 +61,7 @@ SYMBOLS = [
     ('f8_net_input', _i, [_vp, _i, _i, _i, _i]),
     ('f8_net_conv', _i, [_vp, _i, ctypes.POINTER(ConvDesc), _vp, _vp]),
     ('f8_net_conv_dilated', _i, [_vp, _i, ctypes.POINTER(ConvDesc), _i, _vp, _vp]),
+    ('f8_net_conv_rect', _i, [_vp, _i, ctypes.POINTER(ConvDesc), ctypes.POINTER(ConvGeom), _vp, _vp]),
     ('f8_net_conv_transpose', _i, [_vp, _i, ctypes.POINTER(ConvDesc), _i, _vp, _vp]),
     ('f8_net_add', _i, [_vp, _i, _i, _i]),
     ('f8_net_concat', _i, [_vp, ctypes.POINTER(ctypes.c_int), _i]),

@@ -24,6 +24,9 @@
 //                                 residue class mod d — and walks the six columns q - pad, q - pad + d, .. q - pad + 5d once; each transposed column feeds
 //                                 up to three pixels: 18 loads, 48 v_perm_b32 and 48 dot4 for 4 x 4 output values (144 multiply-adds).  A row is cut into
 //                                 min(d, Q) residues x ceil(ceil(Q / d) / DWK_PIX) groups; pixels at or beyond Q are computed and not stored.
+//   dwstrip_dot4_kernel<NW>       int8 forms only, the strips 1 x k / k x 1 of f8_net_conv_rect (3 <= k <= 31) at stride 1, both orientations in one kernel:
+//                                 see the comment in front of it.  Strips at stride 2, with an int32 form or under dwk_dot4 = 0 run dwconvk_kernel, whose
+//                                 tap loops are per axis (DwArgs::k rows behind the top pad, DwArgs::kw columns behind pad_w).
 #include "f8_device.h"
 #include <algorithm>
 
@@ -50,16 +53,16 @@ __global__ void __launch_bounds__(256) dwconvk_kernel(const DwArgs a) {
             const v4i b = *(const v4i*)(a.bias + c);
             acc[0] = b.x; acc[1] = b.y; acc[2] = b.z; acc[3] = b.w;
         }
-        const int h0 = p * a.stride - a.pad, w0 = q * a.stride - a.pad;
+        const int h0 = p * a.stride - a.pad, w0 = q * a.stride - a.pad_w;      // (per axis: k rows behind the top pad, kw columns behind the left pad)
         const unsigned in_xor = SIGNED_IN ? 0u : 0x80808080u;   // unsigned tensors are stored biased
         for (int r = 0; r < a.k; ++r) {
             const int h = h0 + r * a.dil;
             if ((unsigned)h >= (unsigned)a.H) continue;
-            for (int s = 0; s < a.k; ++s) {
+            for (int s = 0; s < a.kw; ++s) {
                 const int w = w0 + s * a.dil;
                 if ((unsigned)w >= (unsigned)a.W) continue;
                 const unsigned xv = *(const unsigned*)(a.x + (((size_t)n * a.H + h) * a.W + w) * a.Cs + c) ^ in_xor;
-                const unsigned wv = *(const unsigned*)(a.w + (size_t)(r * a.k + s) * a.Cs + c);
+                const unsigned wv = *(const unsigned*)(a.w + (size_t)(r * a.kw + s) * a.Cs + c);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const int xe = SIGNED_IN ? (int)(signed char)(xv >> (8 * e)) : (int)((xv >> (8 * e)) & 0xffu);
@@ -243,22 +246,125 @@ __global__ void __launch_bounds__(256) dwconv3x3_dil_dot4_kernel(const DwArgs a)
     }
 }
 
+// Depthwise strips 1 x k / k x 1 at stride 1 (f8_net_conv_rect), int8 forms only, on v_dot4_i32_i8: ONE kernel for both orientations — the strip axis is a
+// run-time byte step between successive taps and successive outputs (Cs for 1 x k, W * Cs for k x 1).  One thread = 4 channels x DWS_RUN consecutive
+// outputs o0 .. o0 + DWS_RUN - 1 along the strip.  It loads the DWS_RUN / 4 + NW - 1 groups of four input positions from i0 = o0 - pad on, once (a position
+// outside the image: the biased zero), byte-transposes each group with the 8 v_perm_b32 of dwconvk_dot4_kernel — one dword per channel, byte b = position
+// i0 + 4 g + b — and accumulates output j, whose window starts at byte j % 4 of group j / 4, against weight image j % 4 of pack_dwk_weights: the k taps
+// shifted by that many bytes and zero-filled, NW = ceil((k + 3) / 4) dwords per channel.  The data is transposed once and never re-aligned; the phases are
+// compile-time (o0 is a multiple of DWS_RUN).  Per output value of one channel: NW dot4 instead of k multiplies; per run (DWS_RUN + 4 NW - 4) / 4 group
+// loads instead of k loads per output.  Lanes run over channel quads first, then over the other axis' pixels (k x 1) or the runs (1 x k): either
+// orientation reads whole rows of Cs bytes.  NW is the only template parameter: one instance serves four kernel sizes (4 NW - 6 .. 4 NW - 3).
+namespace {
+constexpr int DWS_RUN = 8;                          // consecutive outputs along the strip per thread
+}
+template <int NW>
+__global__ void __launch_bounds__(256) dwstrip_dot4_kernel(const DwArgs a) {
+    constexpr int RUN = DWS_RUN, NG = RUN / 4 + NW - 1;      // groups of four input positions
+    const bool vert = a.kw == 1;                     // k x 1: the strip runs down the rows
+    const int cgs = a.Cs >> 2;                       // 4-channel quads
+    const int LO = vert ? a.P : a.Q, LI = vert ? a.H : a.W;      // outputs / inputs along the strip
+    const int B = vert ? a.Q : a.P;                  // pixels on the other axis (the same in and out: kernel 1, no pad)
+    const int RUNS = (LO + RUN - 1) / RUN;
+    const size_t total = (size_t)a.N * RUNS * B * cgs;
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    const int cg = (int)(idx % cgs);
+    size_t st = idx / cgs;
+    int run, b;
+    if (vert) { b = (int)(st % B); st /= B; run = (int)(st % RUNS); st /= RUNS; }
+    else { run = (int)(st % RUNS); st /= RUNS; b = (int)(st % B); st /= B; }
+    const int n = (int)st;
+    const int c = cg << 2, o0 = run * RUN;
+    const int i0 = o0 - (vert ? a.pad : a.pad_w);
+    const size_t istep = vert ? (size_t)a.W * a.Cs : (size_t)a.Cs, ibstep = vert ? (size_t)a.Cs : (size_t)a.W * a.Cs;
+    const size_t ostep = vert ? (size_t)a.Q * a.Cs : (size_t)a.Cs, obstep = vert ? (size_t)a.Cs : (size_t)a.Q * a.Cs;
+    const unsigned padv = a.in_signed ? 0u : 0x80808080u;
+    const int8_t* const xb = a.x + (size_t)n * a.H * a.W * a.Cs + (size_t)b * ibstep + c;
+
+    unsigned col[NG][4];                             // [group][channel]: bytes = the group's four positions
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+        unsigned t[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int i = i0 + 4 * g + j;
+            unsigned v = padv;
+            if ((unsigned)i < (unsigned)LI) v = *(const unsigned*)(xb + (size_t)i * istep);
+            t[j] = v;
+        }
+        const unsigned lo01 = __builtin_amdgcn_perm(t[1], t[0], 0x05010400u), hi01 = __builtin_amdgcn_perm(t[1], t[0], 0x07030602u);
+        const unsigned lo23 = __builtin_amdgcn_perm(t[3], t[2], 0x05010400u), hi23 = __builtin_amdgcn_perm(t[3], t[2], 0x07030602u);
+        col[g][0] = __builtin_amdgcn_perm(lo23, lo01, 0x05040100u); col[g][1] = __builtin_amdgcn_perm(lo23, lo01, 0x07060302u);
+        col[g][2] = __builtin_amdgcn_perm(hi23, hi01, 0x05040100u); col[g][3] = __builtin_amdgcn_perm(hi23, hi01, 0x07060302u);
+    }
+    const v4i bv = *(const v4i*)(a.bias + c);
+    const unsigned* const wq = (const unsigned*)a.w + (size_t)cg * (4 * NW * 4);      // [phase][dword][channel]
+    const int floor0 = a.relu0 ? 0 : INT32_MIN;
+    int8_t* const q0 = a.q[0].ptr, * const q1 = a.q[1].ptr;
+    const size_t ob = ((size_t)n * a.P * a.Q) * a.Cs + (size_t)b * obstep + c;
+#pragma unroll
+    for (int ph = 0; ph < 4; ++ph) {
+        v4i wv[NW];
+#pragma unroll
+        for (int m = 0; m < NW; ++m) wv[m] = *(const v4i*)(wq + (ph * NW + m) * 4);
+#pragma unroll
+        for (int jj = 0; jj < RUN / 4; ++jj) {
+            int acc0 = bv.x, acc1 = bv.y, acc2 = bv.z, acc3 = bv.w;
+#pragma unroll
+            for (int m = 0; m < NW; ++m) {
+                acc0 = __builtin_amdgcn_sdot4((int)col[jj + m][0], wv[m].x, acc0, false);
+                acc1 = __builtin_amdgcn_sdot4((int)col[jj + m][1], wv[m].y, acc1, false);
+                acc2 = __builtin_amdgcn_sdot4((int)col[jj + m][2], wv[m].z, acc2, false);
+                acc3 = __builtin_amdgcn_sdot4((int)col[jj + m][3], wv[m].w, acc3, false);
+            }
+            const int o = o0 + 4 * jj + ph;
+            if (o >= LO) continue;
+            acc0 = max(acc0, floor0); acc1 = max(acc1, floor0); acc2 = max(acc2, floor0); acc3 = max(acc3, floor0);
+            const size_t off = ob + (size_t)o * ostep;
+            if (q0) *(unsigned*)(q0 + off) = requant_pack4(acc0, acc1, acc2, acc3, a.q[0]);
+            if (q1) *(unsigned*)(q1 + off) = requant_pack4(acc0, acc1, acc2, acc3, a.q[1]);
+        }
+    }
+}
+
 // General depthwise: the v_dot4 kernels for int8-only launches (Options::dwk_dot4), else the generic one.  A dilated conv (3x3 only) has its dot4
 // kernel — instance 2 — at stride 1, exactly where dwconvk_dot4_kernel<3, 1> runs the undilated one.
 int dwk_inst(const DwArgs& a, bool out32, bool dot4) {
+    if (a.kw != a.k) return dot4 && !out32 && a.stride == 1 && a.dil == 1 && (a.k == 1 || a.kw == 1) ? 3 : 0;      // a strip: instance 3, dwstrip_dot4_kernel
     if (a.dil > 1) return dot4 && !out32 && a.k == 3 && a.stride == 1 ? 2 : 0;
     return dot4 && !out32 && (a.k == 3 || a.k == 5 || a.k == 7) && (a.stride == 1 || a.stride == 2) ? 1 : 0;
 }
 
 int dwk_kernel_name(char* buf, size_t cap, const DwArgs& a, int inst) {
     if (inst == 2) return snprintf(buf, cap, "f8::dwconv3x3_dil_dot4_kernel");
+    if (inst == 3) return snprintf(buf, cap, "f8::dwstrip_dot4_kernel<%d>", (std::max(a.k, a.kw) + 6) / 4);
     if (inst) return snprintf(buf, cap, "f8::dwconvk_dot4_kernel<%d, %d>", a.k, a.stride);
     return snprintf(buf, cap, "f8::dwconvk_kernel<%s>", a.in_signed ? "true" : "false");
 }
 
 hipError_t launch_dwk(const DwArgs& a, int inst, hipStream_t s) {
-    if (a.k < 1 || a.dil < 1 || a.pad < 0 || a.pad > (a.dil > 1 ? a.dil : a.k / 2) || (a.dil > 1 && a.k != 3)) return hipErrorInvalidValue;
-    if ((inst == 2) != (a.dil > 1 && inst != 0)) return hipErrorInvalidValue;      // a dot4 instance: 2 for a dilated conv and only for one
+    if (a.kw != a.k) {                                    // a strip 1 x k / k x 1: pads below k on its axis, none on the other; instance 3 or the generic kernel
+        const int k = std::max(a.k, a.kw);
+        if (std::min(a.k, a.kw) != 1 || k < 3 || k > 31 || a.dil != 1 || a.pad < 0 || a.pad >= a.k || a.pad_w < 0 || a.pad_w >= a.kw || (inst != 0 && inst != 3))
+            return hipErrorInvalidValue;
+        if (inst == 3) {
+            const bool vert = a.kw == 1;
+            if (a.out32 || !a.w4 || a.stride != 1 || (vert ? a.Q != a.W : a.P != a.H)) return hipErrorInvalidValue;      // (the other axis: the same pixels in and out)
+            const size_t work = (size_t)a.N * (((vert ? a.P : a.Q) + DWS_RUN - 1) / DWS_RUN) * (vert ? a.Q : a.P) * (a.Cs >> 2);
+            const unsigned grid = (unsigned)((work + 255) / 256);
+            DwArgs b = a; b.w = a.w4; b.bias = a.bias4;
+            switch ((k + 6) / 4) {
+#define F8_DWS(NW_) case NW_: hipLaunchKernelGGL((dwstrip_dot4_kernel<NW_>), dim3(grid), dim3(256), 0, s, b); return hipGetLastError();
+                F8_DWS(2) F8_DWS(3) F8_DWS(4) F8_DWS(5) F8_DWS(6) F8_DWS(7) F8_DWS(8) F8_DWS(9)
+#undef F8_DWS
+            }
+            return hipErrorInvalidValue;
+        }
+    } else {
+        if (a.k < 1 || a.dil < 1 || a.pad < 0 || a.pad > (a.dil > 1 ? a.dil : a.k / 2) || (a.dil > 1 && a.k != 3) || a.pad_w != a.pad) return hipErrorInvalidValue;
+        if ((inst == 2) != (a.dil > 1 && inst != 0)) return hipErrorInvalidValue;      // a dot4 instance: 2 for a dilated conv and only for one
+    }
     if (inst == 2) {
         if (a.out32 || !a.w4 || a.stride != 1) return hipErrorInvalidValue;
         const int DR = std::min(a.dil, a.Q), NG = ((a.Q + a.dil - 1) / a.dil + DWK_PIX - 1) / DWK_PIX;

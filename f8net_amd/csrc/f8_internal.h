@@ -154,6 +154,11 @@ struct ConvArgs {
     int32_t sN2, sP2, sQ2, ktot2;          // input byte strides of x2 (per image / output row / output col), its K
     void* trace;                           // tuning builds (F8_TRACE) only; nullptr otherwise
     int32_t dil, kwd;                      // conv_igemm_kernel only: dilation (1: none) and kw * dil — its K loop steps the tap coordinates by dil and wraps the column at kwd
+    // conv_igemm_kernel only: the column axis of a rectangular conv (f8_net_conv_rect).  `stride` and `pad` are then the rows' stride and TOP pad, these the
+    // columns' stride and LEFT pad; pad_far = the larger of the bottom / right pads, which no coordinate needs: it only decides, with the other two, whether
+    // any tap can leave the image (padded()).  A square conv: stride_w = stride, pad_w = pad_far = pad.  The stem path: pad = pad_w = pad_far = 0.
+    int32_t stride_w, pad_w, pad_far;
+    bool padded() const { return pad > 0 || pad_w > 0 || pad_far > 0; }
 };
 
 // Depthwise K x K (groups == C), NHWC int8 in, VALU.  3x3 / pad 1: the launchers of f8_kernels.hip / f8_dwmma.hip, which never read `k`;
@@ -163,6 +168,7 @@ struct DwArgs {
     const int32_t* bias;                   // [Cs]
     const int8_t* w4; const int32_t* bias4; // dot4 kernels, bias + 128*sum(w) for unsigned inputs.  3x3 / pad 1: [Cs/4][9] tap-transposed dwords;
                                            // general: [Cs/4][k columns][ceil(k / 4) row groups][4 channels] dwords, byte j = row 4g + j (0 beyond k)
+                                           // a strip (kw != k): [Cs/4][4 phases][ceil((k + 3) / 4)][4 channels] dwords, the taps shifted by `phase` bytes
     int32_t N, H, W, P, Q, Cs, stride, pad;
     int32_t in_signed;
     int32_t relu0;
@@ -174,6 +180,8 @@ struct DwArgs {
     int32_t rq_int;                        // Options::requant_float == 0: integer requantisation only
     int32_t k;                             // kernel size; read by the general depthwise kernels only (f8_dwk.hip)
     int32_t dil;                           // ... and the dilation (1: none; > 1 only with k == 3)
+    int32_t kw, pad_w;                     // ... and the columns' kernel size and leading pad: k and pad are the rows' (kernel height, top pad).  A square conv:
+                                           // kw = k, pad_w = pad; a strip (f8_net_conv_rect): one of k / kw is 1.  The 3x3 launchers never read them.
 };
 
 // Grouped 3x3 (f8_gconv.hip): cin == cout, cg = C / groups divides 32, stride 1 / 2, pad 0 / 1.  The kernel sees 32-channel slices only.

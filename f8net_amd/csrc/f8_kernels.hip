@@ -185,7 +185,7 @@ __global__ void __launch_bounds__(256, BM * BN >= 128 * 128 ? (DUAL ? 2 : HAS_RE
             const int p = (int)fast_div((unsigned)rem, a.dQ), q = rem - p * a.Q;
             xbase[i] = (unsigned)(n * a.sN + p * a.sP + q * a.sQ + a.origin + chunk * 16);
             xh0[i] = p * a.stride - a.pad;
-            xw0[i] = q * a.stride - a.pad;
+            xw0[i] = q * a.stride_w - a.pad_w;     // (the columns of a rectangular conv have a stride and a leading pad of their own)
         }
     }
 #pragma unroll
@@ -933,7 +933,7 @@ int conv_inst(const ConvArgs& a, const ConvTile& t, bool res, bool dual, int dee
 
 int conv_kernel_name(char* buf, size_t cap, const ConvArgs& a, const ConvTile& t, int inst) {
     const int wpx = conv_wpx(t.bm, t.bn), dual = inst & kConvDual;
-    return snprintf(buf, cap, "f8::conv_igemm_kernel<%d, %d, %d, %d, %d, %s, %s, %d, %s>", t.bm, t.bn, t.bk, wpx, 4 / wpx, a.pad > 0 ? "true" : "false",
+    return snprintf(buf, cap, "f8::conv_igemm_kernel<%d, %d, %d, %d, %d, %s, %s, %d, %s>", t.bm, t.bn, t.bk, wpx, 4 / wpx, a.padded() ? "true" : "false",
                     (inst & kConvRes) || dual ? "true" : "false", inst & kConvDeep ? conv_deep_stages(t.bm, t.bn, t.bk) : kConvStages, dual ? "true" : "false");
 }
 
@@ -951,7 +951,7 @@ template <int BM, int BN, int BK, int WPX, int WCO>
 static hipError_t launch_conv_t(const ConvArgs& a, int inst, int grid, hipStream_t s) {
     constexpr int ST = kConvStages, DST = conv_deep_stages(BM, BN, BK);
     static_assert(ST * (BM + BN) * BK <= 65536, "static LDS");
-    const bool pad = a.pad > 0, res = inst & kConvRes, deep = inst & kConvDeep;
+    const bool pad = a.padded(), res = inst & kConvRes, deep = inst & kConvDeep;
     if (res != (a.res != nullptr) || ((inst & kConvDual) != 0) != (a.x2 != nullptr)) return hipErrorInvalidValue;
     if (a.x2) {   // dual GEMM (downsample join): 1x1 / no padding; 64-wide cout tiles, or 128x128 for the wide late stages
         if constexpr (BK == 64 && (BN == 64 || (BN == 128 && BM == 128))) {

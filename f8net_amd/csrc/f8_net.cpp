@@ -103,6 +103,8 @@ struct Node {
     int kind; int a = -1, b = -1; int out = -1;
     f8_conv_desc cd{};                 // conv / linear (as 1x1 conv)
     int dil = 1;                       // dilation (f8_net_conv_dilated; 1 for kernel 1).  > 1: a launch of its own on conv_igemm_kernel / f8_dwk.hip — every matcher refuses it
+    bool rect = false;                 // f8_net_conv_rect with a geometry that is not square + symmetric: cd.kernel / stride / pad are 0 — no matcher, stem or
+    f8_conv_geom rg{};                 // LDS-patch / register-weight variant takes it — and the geometry is rg (geom_of); a launch of its own as a dilated conv
     std::vector<int8_t> w; std::vector<int32_t> bias;   // raw OIHW int8 + bias (N_DECONV: [cin][cout][k][k], nn.ConvTranspose2d's layout)
     int out_pad = 0;                   // N_DECONV: output_padding
     DeconvPhase dph[kMaxDeconvPhases]{};   // N_DECONV: the phase table (pack_deconv_weights; w_off relative to Node::w_off), cd.stride^2 entries
@@ -150,6 +152,13 @@ struct Node {
     size_t rc_off = 0, cc_off = 0; int ncc = 0;      // border-class tables (0 = single class)
     ConvTile tile{};
 };
+// The per-axis geometry of a conv node: a rectangular node's own, else the square one of its desc.  What packs, counts, names and binds a conv of its own
+// reads this; the matchers read cd, where a rectangular node shows kernel 0.
+static f8_conv_geom geom_of(const Node& n) {
+    if (n.rect) return n.rg;
+    const f8_conv_desc& d = n.cd;
+    return f8_conv_geom{d.kernel, d.kernel, d.stride, d.stride, d.pad, d.pad, d.pad, d.pad, n.dil};
+}
 enum StepKind { S_INPUT, S_CONV, S_DW, S_ADD, S_MAXPOOL, S_AVGPOOL, S_REQUANT, S_OUTPUT, S_FUSED, S_STEMPOOL, S_IR, S_P12, S_CHAIN, S_BCHAIN, S_HEAD2, S_IRCHAIN, S_DWS, S_DWS7, S_IRK, S_GCONV, S_CONCAT, S_UPSAMPLE, S_DECONV, S_SUMPOOL, S_CHANMAP, S_MUL, S_HGATE, S_TABLE, S_ARGMAX, S_PIXMAP };
 // The kernel of a step whose kind has several, chosen once by the step's emitter (pass 3); bind_step, run_step and f8_net_autotune switch on it.
 //   S_CONV:  conv_igemm (f8_kernels.hip), the LDS-patch 3x3 (f8_conv3x3.hip), conv1x1_wreg (f8_wreg.hip), conv1x1_wstat (f8_wstat.hip),
@@ -641,6 +650,8 @@ int f8_net_input(f8_net* net, int C, int H, int W, int fraclen) {
     return t;
 }
 
+static int push_conv_node(f8_net* net, int src, const f8_conv_desc& d, int dil, const f8_conv_geom* rg, int P, int Q, const int32_t* w, const int32_t* b,
+                          int kind, const char* who);
 static int add_conv_node(f8_net* net, int src, const f8_conv_desc& d, int dil, const int32_t* w, const int32_t* b,
                          int kind, const char* who) {
     int rc = check_t(net, src, who);
@@ -674,9 +685,16 @@ static int add_conv_node(f8_net* net, int src, const f8_conv_desc& d, int dil, c
                     s.H + 2 * d.pad, s.W + 2 * d.pad, d.pad);
     }
     const int P = (s.H + 2 * d.pad - ext) / d.stride + 1, Q = (s.W + 2 * d.pad - ext) / d.stride + 1;
+    return push_conv_node(net, src, d, dil, nullptr, P, Q, w, b, kind, who);
+}
+
+// records a validated conv: the node (rg: the geometry of a rectangular one, else null), its copied weights and its [cout, P, Q] result
+static int push_conv_node(f8_net* net, int src, const f8_conv_desc& d, int dil, const f8_conv_geom* rg, int P, int Q, const int32_t* w, const int32_t* b,
+                          int kind, const char* who) {
     if (!w) return fail(F8_ERR_INVALID, "%s: null weight", who);
     Node nd; nd.kind = kind; nd.a = src; nd.cd = d; nd.dil = dil;
-    const size_t wn = (size_t)d.cout * (d.cin / d.groups) * d.kernel * d.kernel;
+    if (rg) { nd.rect = true; nd.rg = *rg; }
+    const size_t wn = (size_t)d.cout * (d.cin / d.groups) * (rg ? rg->kh * rg->kw : d.kernel * d.kernel);
     nd.w.resize(wn);
     for (size_t i = 0; i < wn; ++i) {
         if (w[i] < -128 || w[i] > 127) return fail(F8_ERR_INVALID, "%s: weight %d does not fit int8", who, w[i]);
@@ -700,6 +718,52 @@ int f8_net_conv(f8_net* net, int src, const f8_conv_desc* desc, const int32_t* w
 int f8_net_conv_dilated(f8_net* net, int src, const f8_conv_desc* desc, int dilation, const int32_t* w, const int32_t* b) {
     if (!desc) return fail(F8_ERR_INVALID, "f8_net_conv_dilated: null desc");
     return add_conv_node(net, src, *desc, dilation, w, b, N_CONV, "f8_net_conv_dilated");
+}
+
+int f8_net_conv_rect(f8_net* net, int src, const f8_conv_desc* desc, const f8_conv_geom* geom, const int32_t* w, const int32_t* b) {
+    const char* who = "f8_net_conv_rect";
+    if (!desc) return fail(F8_ERR_INVALID, "%s: null desc", who);
+    if (!geom) return fail(F8_ERR_INVALID, "%s: null geom", who);
+    if (const int rc = check_t(net, src, who)) return rc;
+    f8_conv_desc d = *desc;
+    f8_conv_geom g = *geom;
+    if (d.kernel || d.stride || d.pad)
+        return fail(F8_ERR_INVALID, "%s: desc kernel %d, stride %d, pad %d must be 0: the geometry comes from geom", who, d.kernel, d.stride, d.pad);
+    char gs[192];
+    snprintf(gs, sizeof gs, "kernel %d x %d, stride (%d, %d), pads (top %d, left %d, bottom %d, right %d), dilation %d", g.kh, g.kw, g.stride_h, g.stride_w,
+             g.pad_top, g.pad_left, g.pad_bottom, g.pad_right, g.dilation);
+    if (g.kh < 1 || g.kw < 1 || g.kh > 31 || g.kw > 31) return fail(F8_ERR_INVALID, "%s: kernel sides must be 1 .. 31 (%s)", who, gs);
+    if (g.stride_h < 1 || g.stride_w < 1) return fail(F8_ERR_INVALID, "%s: strides must be >= 1 (%s)", who, gs);
+    if (g.pad_top < 0 || g.pad_left < 0 || g.pad_bottom < 0 || g.pad_right < 0) return fail(F8_ERR_INVALID, "%s: pads must be >= 0 (%s)", who, gs);
+    if (g.dilation < 1) return fail(F8_ERR_INVALID, "%s: dilation %d < 1 (%s)", who, g.dilation, gs);
+    // square and symmetric: the node f8_net_conv_dilated records, with its rules and messages
+    if (g.kh == g.kw && g.stride_h == g.stride_w && g.pad_top == g.pad_left && g.pad_top == g.pad_bottom && g.pad_top == g.pad_right) {
+        d.kernel = g.kh; d.stride = g.stride_h; d.pad = g.pad_top;
+        return add_conv_node(net, src, d, g.dilation, w, b, N_CONV, who);
+    }
+    if (g.dilation > 64) return fail(F8_ERR_UNSUPPORTED, "%s: dilation %d > 64 is not built (%s)", who, g.dilation, gs);
+    if (g.kh == 1 && g.kw == 1) g.dilation = 1;    // no second tap: the same conv
+    const Tensor& s = net->tensors[src];
+    if (d.cin != s.C) return fail(F8_ERR_INVALID, "%s: cin %d != source channels %d", who, d.cin, s.C);
+    if (d.cout < 1) return fail(F8_ERR_INVALID, "%s: cout %d < 1", who, d.cout);
+    const int eh = g.dilation * (g.kh - 1) + 1, ew = g.dilation * (g.kw - 1) + 1;      // the kernel's extent on the input, per axis
+    if (g.pad_top >= eh || g.pad_bottom >= eh || g.pad_left >= ew || g.pad_right >= ew)
+        return fail(F8_ERR_INVALID, "%s: a pad exceeds its axis' extent - 1 (%d rows, %d columns; %s)", who, eh - 1, ew - 1, gs);
+    if (d.groups > 1 && d.groups < d.cin) return fail(F8_ERR_UNSUPPORTED, "%s: grouped rectangular convs are not built (groups %d of cin %d; %s)", who, d.groups, d.cin, gs);
+    if (!(d.groups == 1 || (d.groups == d.cin && d.cout == d.cin))) return fail(F8_ERR_UNSUPPORTED, "%s: groups must be 1 or cin (depthwise)", who);
+    if (d.groups != 1) {
+        const int k = std::max(g.kh, g.kw);
+        const bool strip = std::min(g.kh, g.kw) == 1 && k >= 3 && g.dilation == 1 && g.stride_h == g.stride_w && g.stride_h <= 2;
+        if (!strip)
+            return fail(F8_ERR_UNSUPPORTED, "%s: rectangular depthwise is built for strips only: 1 x k or k x 1 with 3 <= k <= 31, dilation 1, one stride of 1 or 2 (got %s)", who, gs);
+    }
+    if (d.weight_fl < 0 || d.weight_fl > 31) return fail(F8_ERR_INVALID, "%s: bad weight_fl", who);
+    int n;
+    if (const int rc = consumer_format(s, d, &n, who)) return rc;
+    const int Hp = s.H + g.pad_top + g.pad_bottom, Wp = s.W + g.pad_left + g.pad_right;
+    if (Hp < eh || Wp < ew)
+        return fail(F8_ERR_INVALID, "%s: empty output: the kernel spans %d x %d pixels, the padded input is %d x %d (%s)", who, eh, ew, Hp, Wp, gs);
+    return push_conv_node(net, src, d, g.dilation, &g, (Hp - eh) / g.stride_h + 1, (Wp - ew) / g.stride_w + 1, w, b, N_CONV, who);
 }
 
 int f8_net_conv_transpose(f8_net* net, int src, const f8_conv_desc* desc, int output_padding, const int32_t* w, const int32_t* b) {
@@ -1125,28 +1189,29 @@ static void pack_conv_weights(f8_net* net, Node& nd) {
     // other weight of its row stays zero (block-diagonal), and its tap sums run over those cin / groups weights.
     const f8_conv_desc& d = nd.cd;
     const Tensor& src = net->tensors[nd.a];
-    const int k = d.kernel;
+    const f8_conv_geom g = geom_of(nd);
+    const int kh = g.kh, kw = g.kw;              // (a rectangular conv: taps (r, s) of kh rows x kw columns, [coutP][(r * kw + s) * Cs + c]; never the stem)
     const int cg = d.cin / d.groups, kg = d.cout / d.groups;
     nd.coutP = round_up(d.cout, 32);
-    if (nd.stem) { nd.ck = 32; nd.ktot = k * 32; }
-    else { nd.ck = src.Cs; nd.ktot = k * k * src.Cs; }
+    if (nd.stem) { nd.ck = 32; nd.ktot = kh * 32; }
+    else { nd.ck = src.Cs; nd.ktot = kh * kw * src.Cs; }
     nd.w_off = round_up_z(net->wblob.size(), 256);
     const size_t wbytes = (size_t)nd.coutP * nd.ktot;
     net->wblob.resize(nd.w_off + wbytes, 0);
     // per-tap weight sums
-    std::vector<long long> tapsum((size_t)d.cout * k * k, 0);
+    std::vector<long long> tapsum((size_t)d.cout * kh * kw, 0);
     {
         int8_t* wp = (int8_t*)net->wblob.data() + nd.w_off;
         for (int o = 0; o < d.cout; ++o)
             for (int ci = 0; ci < cg; ++ci)
-                for (int r = 0; r < k; ++r)
-                    for (int s = 0; s < k; ++s) {
-                        const int8_t v = nd.w[(((size_t)o * cg + ci) * k + r) * k + s];
+                for (int r = 0; r < kh; ++r)
+                    for (int s = 0; s < kw; ++s) {
+                        const int8_t v = nd.w[(((size_t)o * cg + ci) * kh + r) * kw + s];
                         const int c = (o / kg) * cg + ci;       // the input channel (groups == 1: ci)
-                        tapsum[((size_t)o * k + r) * k + s] += v;
+                        tapsum[((size_t)o * kh + r) * kw + s] += v;
                         size_t idx;
                         if (nd.stem) idx = (size_t)o * nd.ktot + (size_t)r * 32 + (size_t)s * 4 + c;
-                        else idx = (size_t)o * nd.ktot + ((size_t)(r * k + s)) * src.Cs + c;
+                        else idx = (size_t)o * nd.ktot + ((size_t)(r * kw + s)) * src.Cs + c;
                         wp[idx] = v;
                     }
     }
@@ -1154,30 +1219,32 @@ static void pack_conv_weights(f8_net* net, Node& nd) {
 }
 
 // The border-class bias table of a conv whose weights are packed (nd.coutP set): bias[rowclass * ncc + colclass][coutP] and the class of every output
-// row / column (pack_conv_weights); tapsum[cout][k][k] = the sum over the input channels of each tap's weights.
+// row / column (pack_conv_weights); tapsum[cout][kh][kw] = the sum over the input channels of each tap's weights.  Each axis is classified with its own
+// kernel size, stride and LEADING pad (geom_of); a trailing pad shows only in the number of outputs and in which of them lose taps.
 static void pack_conv_bias(f8_net* net, Node& nd, const std::vector<long long>& tapsum) {
     const f8_conv_desc& d = nd.cd;
     const Tensor& src = net->tensors[nd.a]; const Tensor& dst = net->tensors[nd.out];
-    const int k = d.kernel;
+    const f8_conv_geom g = geom_of(nd);
+    const int kh = g.kh, kw = g.kw;
     // classes
     std::vector<uint32_t> rmasks, cmasks;
     std::vector<uint8_t> rowcls(dst.H, 0), colcls(dst.W, 0);
-    const bool classes = !d.input_signed && d.pad > 0 && !nd.stem && !nd.no_classes;
+    const bool classes = !d.input_signed && (g.pad_top > 0 || g.pad_left > 0 || g.pad_bottom > 0 || g.pad_right > 0) && !nd.stem && !nd.no_classes;
     if (classes) {
-        auto classify = [&](int n_out, int n_in, std::vector<uint32_t>& masks, std::vector<uint8_t>& cls) {
+        auto classify = [&](int n_out, int n_in, int k, int stride, int pad, std::vector<uint32_t>& masks, std::vector<uint8_t>& cls) {
             for (int p = 0; p < n_out; ++p) {
                 uint32_t mk = 0;
-                for (int r = 0; r < k; ++r) { const int h = p * d.stride - d.pad + r * nd.dil; if (h >= 0 && h < n_in) mk |= 1u << r; }
+                for (int r = 0; r < k; ++r) { const int h = p * stride - pad + r * nd.dil; if (h >= 0 && h < n_in) mk |= 1u << r; }
                 size_t id = 0;
                 while (id < masks.size() && masks[id] != mk) ++id;
                 if (id == masks.size()) masks.push_back(mk);
                 cls[p] = (uint8_t)id;
             }
         };
-        classify(dst.H, src.H, rmasks, rowcls);
-        classify(dst.W, src.W, cmasks, colcls);
+        classify(dst.H, src.H, kh, g.stride_h, g.pad_top, rmasks, rowcls);
+        classify(dst.W, src.W, kw, g.stride_w, g.pad_left, cmasks, colcls);
     } else {
-        rmasks.push_back((1u << k) - 1); cmasks.push_back((1u << k) - 1);
+        rmasks.push_back((1u << kh) - 1); cmasks.push_back((1u << kw) - 1);
     }
     nd.ncc = classes ? (int)cmasks.size() : 0;
     const size_t ncls = rmasks.size() * cmasks.size();
@@ -1188,9 +1255,9 @@ static void pack_conv_bias(f8_net* net, Node& nd, const std::vector<long long>& 
         for (size_t cc = 0; cc < cmasks.size(); ++cc)
             for (int o = 0; o < d.cout; ++o) {
                 long long sum = 0;
-                for (int r = 0; r < k; ++r)
-                    for (int s = 0; s < k; ++s)
-                        if (((rmasks[rc] >> r) & 1u) && ((cmasks[cc] >> s) & 1u)) sum += tapsum[((size_t)o * k + r) * k + s];
+                for (int r = 0; r < kh; ++r)
+                    for (int s = 0; s < kw; ++s)
+                        if (((rmasks[rc] >> r) & 1u) && ((cmasks[cc] >> s) & 1u)) sum += tapsum[((size_t)o * kh + r) * kw + s];
                 uint32_t b = (uint32_t)nd.bias[o];
                 if (!d.input_signed) b += (uint32_t)(128ll * sum);
                 bp[(rc * cmasks.size() + cc) * (size_t)nd.coutP + o] = (int32_t)b;
@@ -1366,12 +1433,17 @@ static bool dw_general(const Node& n) { const f8_conv_desc& d = n.cd; return d.g
 static void pack_dwk_weights(f8_net* net, Node& nd) {
     const f8_conv_desc& d = nd.cd;
     const Tensor& src = net->tensors[nd.a];
-    const int K = d.kernel, G = (K + 3) / 4;
+    const f8_conv_geom g = geom_of(nd);
+    const int KH = g.kh, KW = g.kw, K = std::max(KH, KW), G = (K + 3) / 4;
+    // a strip (f8_net_conv_rect: 1 x K or K x 1): image (1) is [KH * KW][Cs]; image (2) is dwstrip_dot4_kernel's — [Cs / 4][4 phases][NW = ceil((K + 3) / 4)]
+    // [4 channels] dwords, byte b of dword (quad, ph, m, e) = tap 4 m + b - ph of channel 4 quad + e, 0 outside 0 .. K - 1: the K taps shifted by ph bytes
+    const int NW = (K + 3 + 3) / 4;
+    const size_t w4_bytes = nd.rect ? (size_t)(src.Cs / 4) * 4 * NW * 16 : (size_t)(src.Cs / 4) * K * G * 16;
     nd.coutP = src.Cs; nd.ck = 0; nd.ktot = 0;
     nd.w_off = round_up_z(net->wblob.size(), 256);
-    nd.b_off = round_up_z(nd.w_off + (size_t)K * K * src.Cs, 256);
+    nd.b_off = round_up_z(nd.w_off + (size_t)KH * KW * src.Cs, 256);
     nd.rc_off = round_up_z(nd.b_off + (size_t)src.Cs * 4, 256);                    // dot4 weights
-    nd.cc_off = round_up_z(nd.rc_off + (size_t)(src.Cs / 4) * K * G * 16, 256);    // dot4 bias
+    nd.cc_off = round_up_z(nd.rc_off + w4_bytes, 256);                             // dot4 bias
     net->wblob.resize(nd.cc_off + (size_t)src.Cs * 4, 0);
     int8_t* wp = (int8_t*)net->wblob.data() + nd.w_off;
     int32_t* bp = (int32_t*)(net->wblob.data() + nd.b_off);
@@ -1379,12 +1451,15 @@ static void pack_dwk_weights(f8_net* net, Node& nd) {
     int32_t* b4 = (int32_t*)(net->wblob.data() + nd.cc_off);
     for (int c = 0; c < d.cout; ++c) {
         long long sum = 0;
-        for (int r = 0; r < K; ++r)
-            for (int s = 0; s < K; ++s) {
-                const int8_t v = nd.w[((size_t)c * K + r) * K + s];
-                wp[(size_t)(r * K + s) * src.Cs + c] = v;
+        for (int r = 0; r < KH; ++r)
+            for (int s = 0; s < KW; ++s) {
+                const int8_t v = nd.w[((size_t)c * KH + r) * KW + s];
+                wp[(size_t)(r * KW + s) * src.Cs + c] = v;
                 sum += v;
-                w4[((((size_t)(c / 4) * K + s) * G + r / 4) * 4 + c % 4) * 4 + r % 4] = v;
+                if (!nd.rect) { w4[((((size_t)(c / 4) * K + s) * G + r / 4) * 4 + c % 4) * 4 + r % 4] = v; continue; }
+                const int t = r + s;                            // the tap along the strip (one of r, s is 0)
+                for (int ph = 0; ph < 4; ++ph)
+                    w4[((((size_t)(c / 4) * 4 + ph) * NW + (t + ph) / 4) * 4 + c % 4) * 4 + (t + ph) % 4] = v;
             }
         bp[c] = nd.bias[c];
         uint32_t b = (uint32_t)nd.bias[c];
@@ -1465,6 +1540,15 @@ static void label_conv_step(f8_net* net, Step& st, const Node& nd) {
     const std::string key = nd.dual >= 0 ? tname(net, net->nodes[nd.dual].out) + "+" + tname(net, nd.out) : tname(net, nd.out);
     char buf[160], dl[16] = "";                  // d<D> behind the stride of a dilated conv
     if (nd.dil > 1) snprintf(dl, sizeof dl, "d%d", nd.dil);
+    if (nd.rect) {                               // conv1x7s1_..., conv3x5s2x1_... where the strides differ; dwconv1x21s1:
+        const f8_conv_geom& g = nd.rg;
+        char ss[24];
+        if (g.stride_h == g.stride_w) snprintf(ss, sizeof ss, "%d", g.stride_h); else snprintf(ss, sizeof ss, "%dx%d", g.stride_h, g.stride_w);
+        if (nd.depthwise) snprintf(buf, sizeof buf, "dwconv%dx%ds%s:%s", g.kh, g.kw, ss, key.c_str());
+        else snprintf(buf, sizeof buf, "conv%dx%ds%s%s_t%dx%dx%d%s:%s", g.kh, g.kw, ss, dl, nd.tile.bm, nd.tile.bn, nd.tile.bk, res ? "_res" : "", key.c_str());
+        st.name = buf;
+        return;
+    }
     switch (st.variant) {
         case V_FC: st.name = "linear_dense:" + key; return;
         case V_POOL: st.name = (res ? "conv1x1_res+avgpool:" : "conv1x1+avgpool:") + key; return;
@@ -2295,7 +2379,7 @@ static void plan_tensor_forms(f8_net* net, int max_batch) {
                     default: in_launch = false;                  // a conv of its own; B_JOIN: the shortcut and body.4 read their int8 inputs from HBM
                 }
                 if (in_launch) break;
-                nd.stem = !nd.depthwise && !nd.grouped && nd.cd.cin <= 4 && ND[s.prod].kind == N_INPUT && nd.cd.kernel <= 8 && nd.dil == 1 &&
+                nd.stem = !nd.depthwise && !nd.grouped && nd.cd.cin <= 4 && ND[s.prod].kind == N_INPUT && nd.cd.kernel <= 8 && nd.dil == 1 && !nd.rect &&
                           s.consumers.size() == 1 && !is_output(net, nd.a) && n == 0;
                 if (nd.stem) {
                     const int Q = T[nd.out].W;
@@ -2329,7 +2413,7 @@ static void plan_tensor_forms(f8_net* net, int max_batch) {
                 if (!o.forms.empty() && T[nd.a].consumers.size() == 1 && !is_output(net, nd.a)) {
                     // ResNet head: 7x7/2 stem conv + this pool in one launch (the conv output never leaves LDS)
                     Node& c = ND[T[nd.a].prod];
-                    if (c.kind == N_CONV && c.cd.groups == 1 && c.dil == 1 && c.fused_add < 0 && ND[T[c.a].prod].kind == N_INPUT && T[c.a].consumers.size() == 1 &&
+                    if (c.kind == N_CONV && c.cd.groups == 1 && c.dil == 1 && !c.rect && c.fused_add < 0 && ND[T[c.a].prod].kind == N_INPUT && T[c.a].consumers.size() == 1 &&
                         !is_output(net, c.a) && (!c.cd.quant_input || T[c.a].fl == c.cd.input_fl) && opt.fuse_stem &&
                         stem_pool_supported(c.cd.cin, c.cd.cout, c.cd.kernel, c.cd.stride, c.cd.pad, nd.pk, nd.pstride, nd.ppad, o.H, o.W, opt.stem_rows, T[c.a].H, T[c.a].W)) {
                         c.sp_pool = i; nd.sp_conv = T[nd.a].prod;
@@ -2444,13 +2528,15 @@ static int join_output(const f8_net* net, const Node& c, Step& st) {
 }
 // bytes of a conv's packed weights + bias (depthwise: K * K taps + 4 bytes of bias per channel; grouped: the weights of the groups, not the zeros between them)
 static double weight_bytes(const f8_net* net, const Node& c) {
-    if (c.grouped) return (double)c.cd.cout * ((c.cd.cin / c.cd.groups) * c.cd.kernel * c.cd.kernel + 4);
-    return c.depthwise ? (double)net->tensors[c.a].Cs * (c.cd.kernel * c.cd.kernel + 4) : (double)c.coutP * (c.ktot + 4);
+    const f8_conv_geom g = geom_of(c);
+    if (c.grouped) return (double)c.cd.cout * ((c.cd.cin / c.cd.groups) * g.kh * g.kw + 4);
+    return c.depthwise ? (double)net->tensors[c.a].Cs * (g.kh * g.kw + 4) : (double)c.coutP * (c.ktot + 4);
 }
 // multiply-adds x 2 of a conv per image
 static double conv_ops(const f8_net* net, const Node& c) {
     const Tensor& o = net->tensors[c.out];
-    return 2.0 * o.H * o.W * c.cd.cout * (c.cd.cin / c.cd.groups) * c.cd.kernel * c.cd.kernel;
+    const f8_conv_geom g = geom_of(c);           // (a rectangular conv: its kh x kw real taps)
+    return 2.0 * o.H * o.W * c.cd.cout * (c.cd.cin / c.cd.groups) * g.kh * g.kw;
 }
 // bytes per image a step writes: its output forms over px pixels of map o
 static double out_bytes(const Step& st, const Tensor& o, double px) { return px * o.Cs * ((st.out.f32 >= 0 ? 4 : 0) + out_forms8(st)); }
@@ -2762,7 +2848,7 @@ static Variant conv_variant(const f8_net* net, const Node& nd, const Step& st, i
     if (st.dense) return V_FC;                   // the classifier: logits straight into the caller's buffer (f8_fc.hip)
     if (nd.pool >= 0) return V_POOL;             // ... and the average pool behind the last 1x1 conv (1i)
     const bool plain = !nd.stem && d.groups == 1;
-    if (nd.dil > 1) return V_IGEMM;              // a dilated conv: conv_igemm_kernel walks its taps at any spacing, the LDS-patch / register-weight 3x3 kernels do not
+    if (nd.dil > 1 || nd.rect) return V_IGEMM;   // a dilated or rectangular conv: conv_igemm_kernel walks its taps at any spacing, the LDS-patch / register-weight 3x3 kernels do not
     // the stride-2 3x3 of a late stage-opening block, int8 outputs only: input patch in LDS, weights straight to registers
     if (opt.s2wreg && plain && d.kernel == 3 && d.stride == 2 && d.pad == 1 && nd.fused_add < 0 && nd.dual < 0 && st.out.f32 < 0 && nd.ck == d.cin &&
         s.H == 2 * o.H && s.W == 2 * o.W && conv3x3s2_wreg_supported(nd.ck, o.H, o.W, nd.coutP)) return V_S2WREG;
@@ -2849,7 +2935,7 @@ static int emit_conv(f8_net* net, int i, int max_batch, Step& st, std::vector<in
     if (g) b += (double)T[g->a].H * T[g->a].W * T[g->a].Cs;
     if (st.dense) b += (double)d.cout * 4;
     st.bytes_per_img = b + out_bytes(st, o, outpix);
-    st.valu_per_img = ((st.res_t >= 0 || g) ? 2.0 * opix * o.C : 0.0) + (nd.pool >= 0 ? opix * o.C : 0.0) + 3.0 * outpix * o.Cs * out_forms8(st) + (nd.depthwise ? (double)(d.kernel * d.kernel) * opix * d.cout / 4.0 : 0.0);   // (a VALU depthwise conv: one v_dot4 per four taps)
+    st.valu_per_img = ((st.res_t >= 0 || g) ? 2.0 * opix * o.C : 0.0) + (nd.pool >= 0 ? opix * o.C : 0.0) + 3.0 * outpix * o.Cs * out_forms8(st) + (nd.depthwise ? (double)(geom_of(nd).kh * geom_of(nd).kw) * opix * d.cout / 4.0 : 0.0);   // (a VALU depthwise conv: one v_dot4 per four taps)
     st.bytes_const = weight_bytes(net, nd) + (g ? weight_bytes(net, *g) : 0.0);
     label_conv_step(net, st, nd);
     if (reads_frag_weights(st.variant)) pack_frag_weights(net, nd);
@@ -3479,7 +3565,8 @@ static int bind_step(f8_net* net, Step& st) {
             a.PQ = oT.H * oT.W; a.Q = oT.W;
             a.dPQ = fast_divisor((uint32_t)a.PQ);
             a.dQ = fast_divisor((uint32_t)a.Q);
-            a.stride = d.stride; a.kh = d.kernel; a.CK = nd.ck; a.ktot = nd.ktot; a.coutP = nd.coutP;
+            const f8_conv_geom g = geom_of(nd);           // per axis: the rows by (stride, pad), the columns by (stride_w, pad_w)
+            a.stride = g.stride_h; a.stride_w = g.stride_w; a.kh = g.kh; a.CK = nd.ck; a.ktot = nd.ktot; a.coutP = nd.coutP;
             a.ncc = nd.ncc;
             if (nd.ncc > 0) { a.rowcls = (const uint8_t*)W8(nd.rc_off); a.colcls = (const uint8_t*)W8(nd.cc_off); }
             if (nd.stem) {
@@ -3487,8 +3574,9 @@ static int bind_step(f8_net* net, Step& st) {
                 a.origin = 0; a.H = sF.Hp; a.W = sF.Wp; a.pad = 0; a.kw = 1;
                 a.tapH = sF.Wp * 4; a.tapW = 0;
             } else {
-                a.sN = sT.H * sT.W * sT.Cs; a.sP = d.stride * sT.W * sT.Cs; a.sQ = d.stride * sT.Cs;
-                a.origin = -(d.pad * sT.W + d.pad) * sT.Cs; a.H = sT.H; a.W = sT.W; a.pad = d.pad; a.kw = d.kernel;
+                a.sN = sT.H * sT.W * sT.Cs; a.sP = g.stride_h * sT.W * sT.Cs; a.sQ = g.stride_w * sT.Cs;
+                a.origin = -(g.pad_top * sT.W + g.pad_left) * sT.Cs; a.H = sT.H; a.W = sT.W; a.pad = g.pad_top; a.pad_w = g.pad_left; a.kw = g.kw;
+                a.pad_far = std::max(g.pad_bottom, g.pad_right);
                 a.tapH = sT.W * sT.Cs; a.tapW = sT.Cs;
             }
             a.dil = nd.stem ? 1 : nd.dil; a.kwd = a.kw * a.dil;     // (conv_igemm_kernel carries its tap coordinates pre-dilated; every other variant is undilated)
@@ -3786,9 +3874,10 @@ static int bind_step(f8_net* net, Step& st) {
             DwArgs a{};
             a.w = W8(nd.w_off); a.bias = B32(nd.b_off);
             a.w4 = W8(nd.rc_off); a.bias4 = B32(nd.cc_off);
-            a.H = sT.H; a.W = sT.W; a.P = oT.H; a.Q = oT.W; a.Cs = sT.Cs; a.stride = nd.cd.stride; a.pad = nd.cd.pad;
+            const f8_conv_geom g = geom_of(nd);           // (a strip: one stride for both axes, the leading pad of each)
+            a.H = sT.H; a.W = sT.W; a.P = oT.H; a.Q = oT.W; a.Cs = sT.Cs; a.stride = g.stride_h; a.pad = g.pad_top; a.pad_w = g.pad_left;
             a.in_signed = nd.cd.input_signed; a.relu0 = st.relu0; a.acc_ok = conv_acc_bounded(nd); a.rq_int = rq_int;
-            a.k = nd.cd.kernel; a.dil = nd.dil;
+            a.k = g.kh; a.kw = g.kw; a.dil = nd.dil;
             out_formats(a.q);
             if (dw_general(nd)) {                                 // f8_dwk.hip: integer requantisation (requant1) whatever requant_float says
                 st.inst = dwk_inst(a, out32, opt.dwk_dot4);
@@ -4351,7 +4440,7 @@ static int run_step(const f8_net* net, const RunIO& io, const Step& st, int n0, 
         case S_DWS7: { Dws7Args a = std::get<Dws7Args>(st.args); src_io(a, &a.out32); e = launch_dws7(a, st.inst, net->num_cu, s); break; }
         case S_DW: {
             DwArgs a = std::get<DwArgs>(st.args); src_io(a, &a.out32);
-            e = (a.k == 3 && a.pad == 1 && a.dil == 1) ? launch_dwconv(a, st.inst, s) : launch_dwk(a, st.inst, s);      // (general depthwise: f8_dwk.hip)
+            e = (a.k == 3 && a.kw == 3 && a.pad == 1 && a.dil == 1) ? launch_dwconv(a, st.inst, s) : launch_dwk(a, st.inst, s);      // (general depthwise: f8_dwk.hip)
             break;
         }
         case S_GCONV: { GConvArgs a = std::get<GConvArgs>(st.args); a.x_bytes = (uint32_t)(src_io(a, &a.out32).bytes_per_img * N); e = launch_gconv(a, s); break; }

@@ -12,7 +12,7 @@ import os
 import numpy as np
 
 from . import _lib, tables, topology
-from ._lib import ConvDesc, LinearDesc, MulDesc, TableDesc, check
+from ._lib import ConvDesc, ConvGeom, LinearDesc, MulDesc, TableDesc, check
 
 AVGPOOL_SHIFT = 6   # FXQAvgPool2d(7).shiftnum = round(log2(49)), fix_quant_ops.py:121-122
 
@@ -29,6 +29,24 @@ def accept_grouped(net, convs, options=None):
         net.set_option('grouped', options['grouped'])
     elif 'F8_GROUPED' not in os.environ and any(1 < g < cin for cin, g in convs):
         net.set_option('grouped', 1)
+
+
+def conv_pair(v):
+    """An int or a pair as (h, w)."""
+    if isinstance(v, (tuple, list)):
+        h, w = v
+        return int(h), int(w)
+    return int(v), int(v)
+
+
+def conv_pads(pad):
+    """An int, (ph, pw) or (top, left, bottom, right) as (top, left, bottom, right) — the order of ONNX `pads`."""
+    if isinstance(pad, (tuple, list)):
+        if len(pad) == 2:
+            return int(pad[0]), int(pad[1]), int(pad[0]), int(pad[1])
+        t, l, b, r = pad
+        return int(t), int(l), int(b), int(r)
+    return (int(pad),) * 4
 
 
 class F8Net:
@@ -60,15 +78,24 @@ class F8Net:
 
     def conv(self, src, weight, bias, *, stride, pad, groups, weight_fl, input_fl, input_signed,
              quant_input=True, relu=False, label=None, dilation=1):
-        """dilation: the spacing of the kernel's taps (f8_net_conv_dilated); the weights stay the k x k real taps."""
+        """dilation: the spacing of the kernel's taps (f8_net_conv_dilated); the weights stay the real taps.
+        weight may be [cout, cin_g, kh, kw]; stride an int or (sh, sw); pad an int, (ph, pw) or (top, left, bottom, right).  Anything square and symmetric
+        goes through f8_net_conv / f8_net_conv_dilated as ever; everything else is f8_net_conv_rect."""
         w = _np_i32(weight)
-        cout, cin_g, k, k2 = w.shape
-        assert k == k2
-        d = ConvDesc(cin=cin_g * groups, cout=cout, kernel=k, stride=stride, pad=pad, groups=groups,
+        cout, cin_g, kh, kw = w.shape
+        sh, sw = conv_pair(stride)
+        pads = conv_pads(pad)
+        square = kh == kw and sh == sw and len(set(pads)) == 1
+        d = ConvDesc(cin=cin_g * groups, cout=cout, kernel=kh if square else 0, stride=sh if square else 0, pad=pads[0] if square else 0, groups=groups,
                      weight_fl=int(weight_fl), input_fl=int(input_fl), input_signed=int(bool(input_signed)),
                      quant_input=int(bool(quant_input)), relu=int(bool(relu)))
         b = None if bias is None else _np_i32(bias)
-        if dilation != 1:
+        if not square:
+            g = ConvGeom(kh=kh, kw=kw, stride_h=sh, stride_w=sw, pad_top=pads[0], pad_left=pads[1], pad_bottom=pads[2], pad_right=pads[3],
+                         dilation=int(dilation))
+            t = check(self._L.f8_net_conv_rect(self._h, src, ctypes.byref(d), ctypes.byref(g), w.ctypes.data,
+                                               None if b is None else b.ctypes.data))
+        elif dilation != 1:
             t = check(self._L.f8_net_conv_dilated(self._h, src, ctypes.byref(d), int(dilation), w.ctypes.data,
                                                   None if b is None else b.ctypes.data))
         else:

@@ -184,8 +184,9 @@ def export_graph(ig: IntGraph) -> bytes:
                 inits[o.key + '.bias'] = o.bias
                 ins.append(o.key + '.bias')
             if o.kind == 'conv':
-                y = w.emit('Conv', ins, {'dilations': [int(o.dilation)] * 2, 'group': int(o.groups), 'kernel_shape': [o.kernel] * 2,
-                                         'pads': [o.pad] * 4, 'strides': [o.stride] * 2})
+                kh, kw, sh, sw, pt, pl, pb, pr = o.conv_geometry()     # (pads: [top, left, bottom, right]; an axis of one tap has dilation 1)
+                y = w.emit('Conv', ins, {'dilations': [int(o.dilation) if kh > 1 else 1, int(o.dilation) if kw > 1 else 1], 'group': int(o.groups),
+                                         'kernel_shape': [kh, kw], 'pads': [pt, pl, pb, pr], 'strides': [sh, sw]})
             elif o.kind == 'deconv':
                 y = w.emit('ConvTranspose', ins, {'dilations': [1, 1], 'group': 1, 'kernel_shape': [o.kernel] * 2, 'output_padding': [int(o.output_padding)] * 2,
                                                   'pads': [o.pad] * 4, 'strides': [o.stride] * 2})

@@ -69,6 +69,12 @@ class IntOp:
     block: int = 0                 # d2s / s2d (depth_to_space / space_to_depth): the block size r
     order: str = None              # d2s / s2d: 'crd' | 'dcr' (include/f8net.h)
     output_padding: int = 0        # deconv (transposed conv; weight [cin, cout, k, k]): ONNX `output_padding`, both equal
+    rect: tuple = None             # conv: None for a square kernel with one stride and one pad (`kernel`, `stride`, `pad`); else the rectangular geometry
+                                   # (kh, kw, stride_h, stride_w, pad_top, pad_left, pad_bottom, pad_right) of f8_net_conv_rect, and those three are 0
+
+    def conv_geometry(self):
+        """(kh, kw, stride_h, stride_w, top, left, bottom, right) of a conv, rectangular or not."""
+        return tuple(self.rect) if self.rect else (self.kernel, self.kernel, self.stride, self.stride) + (self.pad,) * 4
 
 
 @dataclass
@@ -214,7 +220,8 @@ class IntGraph:
                 ids[t] = net.input(C, H, W, V[t])
             elif o.kind == 'conv':
                 i, w = layer[t]
-                ids[t] = net.conv(ids[o.src], o.weight, o.bias, stride=o.stride, pad=o.pad, groups=o.groups,
+                g = o.conv_geometry()
+                ids[t] = net.conv(ids[o.src], o.weight, o.bias, stride=g[2:4] if o.rect else o.stride, pad=g[4:] if o.rect else o.pad, groups=o.groups,
                                   weight_fl=w, input_fl=i, input_signed=o.signed, quant_input=o.shift is not None,
                                   relu=o.relu, label=o.key, dilation=o.dilation)
             elif o.kind == 'deconv':
@@ -262,6 +269,26 @@ class IntGraph:
         return net.finalize(max_batch)
 
 
+def _check_rect(wname, rect, dil, groups, cin):
+    """What f8_net_conv_rect refuses, as an OnnxImportError that says which (include/f8net.h)."""
+    kh, kw, sh, sw, pt, pl, pb, pr = rect
+    what = f'kernel {kh}x{kw}, strides ({sh}, {sw}), pads [{pt}, {pl}, {pb}, {pr}], dilation {dil}'
+    if not (1 <= kh <= 31 and 1 <= kw <= 31):
+        raise OnnxImportError(f'Conv {wname}: rectangular kernel sides must be 1 .. 31 ({what})')
+    if not 1 <= dil <= 64:
+        raise OnnxImportError(f'Conv {wname}: dilation must be 1 .. 64 ({what})')
+    eh, ew = dil * (kh - 1) + 1, dil * (kw - 1) + 1
+    if pt >= eh or pb >= eh or pl >= ew or pr >= ew:
+        raise OnnxImportError(f'Conv {wname}: a pad exceeds its axis\' extent - 1 = {eh - 1} rows / {ew - 1} columns ({what})')
+    if 1 < groups < cin:
+        raise OnnxImportError(f'Conv {wname}: grouped rectangular convs are not built (group {groups} of {cin} channels; {what})')
+    if groups == cin and groups > 1:
+        k = max(kh, kw)
+        if not (min(kh, kw) == 1 and k >= 3 and dil == 1 and sh == sw and sh <= 2):
+            raise OnnxImportError(f'Conv {wname}: rectangular depthwise convs are built for strips only: 1xk / kx1, 3 <= k <= 31, dilation 1, one '
+                                  f'stride of 1 or 2 ({what})')
+
+
 def tensor_shapes(ops):
     """[(C, H, W)] of every tensor of a list of IntOps (the shuffle's Reshape and an equal Split need the channel count and the map)."""
     out = []
@@ -271,8 +298,8 @@ def tensor_shapes(ops):
             continue
         C, H, W = out[o.src]
         if o.kind == 'conv':
-            k = o.dilation * (o.kernel - 1) + 1
-            out.append((o.weight.shape[0], (H + 2 * o.pad - k) // o.stride + 1, (W + 2 * o.pad - k) // o.stride + 1))
+            kh, kw, sh, sw, pt, pl, pb, pr = o.conv_geometry()
+            out.append((o.weight.shape[0], (H + pt + pb - o.dilation * (kh - 1) - 1) // sh + 1, (W + pl + pr - o.dilation * (kw - 1) - 1) // sw + 1))
         elif o.kind == 'deconv':
             out.append((o.weight.shape[1], (H - 1) * o.stride - 2 * o.pad + o.kernel + o.output_padding, (W - 1) * o.stride - 2 * o.pad + o.kernel + o.output_padding))
         elif o.kind == 'linear':
@@ -732,15 +759,29 @@ def import_graph(model, input_signed=False) -> IntGraph:
             src, n, signed = requant_src(nd.inputs[0], 'Conv')
             wname, w = init(nd.inputs[1], 'Conv weight')
             b = init(nd.inputs[2], 'Conv bias')[1] if len(nd.inputs) > 2 else None
-            k = a['kernel_shape']
-            pads, st = a.get('pads', [0, 0, 0, 0]), a.get('strides', [1, 1])
-            dil = list(a.get('dilations', [1, 1]))
-            if k[0] != k[1] or len(set(pads)) != 1 or st[0] != st[1] or len(set(dil)) != 1 or dil[0] < 1:
-                raise OnnxImportError(f'Conv {wname}: only square kernels / symmetric pads / equal dilations (got dilations {dil})')
-            ig.ops.append(IntOp('conv', src=src, weight=np.array(w, np.int32),
-                                bias=None if b is None else np.array(b, np.int32), stride=st[0],
-                                pad=pads[0], groups=a.get('group', 1), kernel=k[0], shift=n, signed=signed,
-                                key=_layer_key(wname), dilation=int(dil[0])))
+            w = np.array(w, np.int32)
+            ap = a.get('auto_pad', b'NOTSET')
+            if ap not in (b'NOTSET', 'NOTSET'):
+                raise OnnxImportError(f'Conv {wname}: auto_pad {ap!r}: only explicit pads')
+            k = [int(v) for v in a.get('kernel_shape', w.shape[2:])]
+            pads, st = [int(v) for v in a.get('pads', [0, 0, 0, 0])], [int(v) for v in a.get('strides', [1, 1])]
+            dil = [int(v) for v in a.get('dilations', [1, 1])]
+            if len(k) != 2 or len(pads) != 4 or len(st) != 2 or len(dil) != 2:
+                raise OnnxImportError(f'Conv {wname}: only 2-D convs (kernel_shape {k}, pads {pads}, strides {st}, dilations {dil})')
+            # one dilation for both axes (f8_net_conv_rect): the axes whose kernel is > 1 must agree; an axis of one tap has no spacing ([d, 1] on a 3x1 is d)
+            live = sorted({d for d, kk in zip(dil, k) if kk > 1})
+            if len(live) > 1 or min(dil) < 1:
+                raise OnnxImportError(f'Conv {wname}: only equal dilations on the axes with more than one tap (got dilations {dil}, kernel {k})')
+            d1 = live[0] if live else 1
+            groups = int(a.get('group', 1))
+            if k[0] == k[1] and len(set(pads)) == 1 and st[0] == st[1]:
+                geo = dict(stride=st[0], pad=pads[0], kernel=k[0])
+            else:                                                   # ONNX pads: [top, left, bottom, right]
+                geo = dict(stride=0, pad=0, kernel=0, rect=(k[0], k[1], st[0], st[1], pads[0], pads[1], pads[2], pads[3]))
+                _check_rect(wname, geo['rect'], d1, groups, w.shape[1] * groups)
+            ig.ops.append(IntOp('conv', src=src, weight=w,
+                                bias=None if b is None else np.array(b, np.int32), groups=groups, shift=n, signed=signed,
+                                key=_layer_key(wname), dilation=d1, **geo))
             if n is None:
                 ig.ops[-1].signed = ig.input_signed
             val[out] = ('T', len(ig.ops) - 1)

@@ -98,8 +98,17 @@ class F8Conv2d(nn.Conv2d):
     def forward(self, x):
         _require_dev_i32(x, 'F8Conv2d')
         w_fl, in_fl = self._fl.get(self)
-        return torch.ops.f8net.conv2d(x, self.weight, self.bias, self.stride[0], self.padding[0], self.groups, w_fl, in_fl,
-                                      self.input_symmetric, self.dilation[0])
+        kh, kw = self.kernel_size
+        if kh == kw and self.stride[0] == self.stride[1] and self.padding[0] == self.padding[1] and self.dilation[0] == self.dilation[1]:
+            return torch.ops.f8net.conv2d(x, self.weight, self.bias, self.stride[0], self.padding[0], self.groups, w_fl, in_fl,
+                                          self.input_symmetric, self.dilation[0])
+        # nn.Conv2d's tuple kernel_size / stride / padding / dilation (f8_net_conv_rect): one dilation for the axes with more than one tap
+        dil = {d for d, k in zip(self.dilation, self.kernel_size) if k > 1}
+        if len(dil) > 1:
+            raise ValueError(f'F8Conv2d: dilation {self.dilation} on kernel {self.kernel_size}: only equal dilations on the axes with more than one tap')
+        ph, pw = self.padding
+        return torch.ops.f8net.conv2d_rect(x, self.weight, self.bias, list(self.stride), [ph, pw, ph, pw], self.groups, w_fl, in_fl,
+                                           self.input_symmetric, dil.pop() if dil else 1)
 
 
 class F8ConvTranspose2d(nn.ConvTranspose2d):

@@ -10,6 +10,7 @@ the dispatcher.
     f8net::relu_(x)                                  nn.ReLU(inplace) on int32        fix_resnet.py:39,77
     f8net::add_align_(res, x, res_fl, x_fl)          residual align-add-clamp         fix_resnet.py:40-54
     f8net::conv2d(x, w, b, stride, pad, groups, weight_fl, input_fl, input_signed, dilation=1)    `layer_(res)`, int nn.Conv2d of int_conv :680-714
+    f8net::conv2d_rect(x, w, b, stride[2], pads[4], groups, weight_fl, input_fl, input_signed, dilation=1)    the same with a kh x kw kernel, (sh, sw), (top, left, bottom, right)
     f8net::linear(x, w, b, weight_fl, input_fl, input_signed)                         `self.classifier(x)`, int_fc :1165-1195
     f8net::avgpool_sum(x)                            FXQAvgPool2d int branch          fix_quant_ops.py:126-134
     f8net::maxpool(x, k, stride, pad)                head max-pool                    fix_resnet.py:358-359
@@ -50,6 +51,7 @@ _DEF.define('requant(Tensor x, int fl, int input_fl, bool signed) -> Tensor')
 _DEF.define('relu_(Tensor(a!) x) -> Tensor(a!)')
 _DEF.define('add_align_(Tensor(a!) res, Tensor x, int res_fl, int x_fl) -> Tensor(a!)')
 _DEF.define('conv2d(Tensor x, Tensor weight, Tensor? bias, int stride, int pad, int groups, int weight_fl, int input_fl, bool input_signed, int dilation=1) -> Tensor')
+_DEF.define('conv2d_rect(Tensor x, Tensor weight, Tensor? bias, int[2] stride, int[4] pads, int groups, int weight_fl, int input_fl, bool input_signed, int dilation=1) -> Tensor')
 _DEF.define('conv_transpose2d(Tensor x, Tensor weight, Tensor? bias, int stride, int pad, int output_padding, int weight_fl, int input_fl, bool input_signed) -> Tensor')
 _DEF.define('linear(Tensor x, Tensor weight, Tensor? bias, int weight_fl, int input_fl, bool input_signed) -> Tensor')
 _DEF.define('avgpool_sum(Tensor x) -> Tensor')
@@ -203,6 +205,32 @@ def _conv2d(x, weight, bias, stride, pad, groups, weight_fl, input_fl, input_sig
     net = _plans.get(key, (weight, bias), N, build)
     k = weight.shape[2]
     P, Q = _conv_out(H, k, stride, pad, dilation), _conv_out(W, k, stride, pad, dilation)
+    return net.run(x).view(N, weight.shape[0], P, Q)
+
+
+def _rect_out(n, k, stride, pad0, pad1, dilation):
+    return (n + pad0 + pad1 - dilation * (k - 1) - 1) // stride + 1
+
+
+def _conv2d_rect(x, weight, bias, stride, pads, groups, weight_fl, input_fl, input_signed, dilation=1):
+    """nn.Conv2d with tuple arguments behind an explicit zero pad (f8_net_conv_rect): stride (sh, sw), pads (top, left, bottom, right)."""
+    _i32(x, 'conv2d_rect')
+    x = x.contiguous()
+    N, C, H, W = x.shape
+    stride, pads = tuple(int(v) for v in stride), tuple(int(v) for v in pads)
+    key = ('conv_rect', x.device.index, C, H, W, id(weight), tuple(weight.shape), None if bias is None else id(bias), stride, pads, groups, weight_fl, input_fl,
+           bool(input_signed), dilation)
+
+    def build(n):
+        net = F8Net()
+        t = net.input(C, H, W, input_fl)
+        t = net.conv(t, _np(weight), _np(bias), stride=stride, pad=pads, groups=groups, weight_fl=weight_fl, input_fl=input_fl,
+                     input_signed=input_signed, quant_input=False, relu=False, dilation=dilation)
+        net.output(t, as_float=False)
+        return net.finalize(n)
+
+    net = _plans.get(key, (weight, bias), N, build)
+    P, Q = _rect_out(H, weight.shape[2], stride[0], pads[0], pads[2], dilation), _rect_out(W, weight.shape[3], stride[1], pads[1], pads[3], dilation)
     return net.run(x).view(N, weight.shape[0], P, Q)
 
 
@@ -488,7 +516,7 @@ def _net_forward_f32(images, handle, normalize):
 
 # ------------------------------------------------------------------------------------------ registration
 _CUDA = Library('f8net', 'IMPL', 'CUDA')
-for _n, _f in (('requant', _requant), ('relu_', _relu_), ('add_align_', _add_align_), ('conv2d', _conv2d), ('conv_transpose2d', _conv_transpose2d), ('linear', _linear),
+for _n, _f in (('requant', _requant), ('relu_', _relu_), ('add_align_', _add_align_), ('conv2d', _conv2d), ('conv2d_rect', _conv2d_rect), ('conv_transpose2d', _conv_transpose2d), ('linear', _linear),
                ('avgpool_sum', _avgpool_sum), ('avgpool2d_sum', _avgpool2d_sum), ('maxpool', _maxpool), ('channel_shuffle', _channel_shuffle), ('depth_to_space', _depth_to_space), ('space_to_depth', _space_to_depth), ('mul_q', _mul_q), ('table_q', _table_q), ('argmax_channels', _argmax_channels), ('net_forward', _net_forward), ('net_forward_taps', _net_forward_taps),
                ('net_forward_f32', _net_forward_f32)):
     _CUDA.impl(_n, _f)
@@ -499,6 +527,9 @@ _META.impl('relu_', lambda x: x)
 _META.impl('add_align_', lambda res, x, res_fl, x_fl: res)
 _META.impl('conv2d', lambda x, w, b, stride, pad, groups, wfl, ifl, sgn, dilation=1: x.new_empty(
     (x.shape[0], w.shape[0], _conv_out(x.shape[2], w.shape[2], stride, pad, dilation), _conv_out(x.shape[3], w.shape[3], stride, pad, dilation))))
+_META.impl('conv2d_rect', lambda x, w, b, stride, pads, groups, wfl, ifl, sgn, dilation=1: x.new_empty(
+    (x.shape[0], w.shape[0], _rect_out(x.shape[2], w.shape[2], stride[0], pads[0], pads[2], dilation),
+     _rect_out(x.shape[3], w.shape[3], stride[1], pads[1], pads[3], dilation))))
 _META.impl('conv_transpose2d', lambda x, w, b, stride, pad, opad, wfl, ifl, sgn: x.new_empty(
     (x.shape[0], w.shape[1], _deconv_out(x.shape[2], w.shape[2], stride, pad, opad), _deconv_out(x.shape[3], w.shape[3], stride, pad, opad))))
 _META.impl('linear', lambda x, w, b, wfl, ifl, sgn: x.new_empty((x.shape[0], w.shape[0])))

@@ -96,7 +96,7 @@ typedef struct f8_net f8_net;
 
 typedef struct f8_conv_desc {
     int32_t cin, cout;
-    int32_t kernel;        /* square kernels: 1, 3, 7 in the reference nets */
+    int32_t kernel;        /* square kernels: 1, 3, 7 in the reference nets (rectangular ones, per-axis strides and pads: f8_net_conv_rect) */
     int32_t stride, pad;
     int32_t groups;        /* 1 or cin (depthwise, cout == cin) — fix_quant_ops.py:373-390.  Depthwise: kernel 3, 5 or 7,
                               stride 1 or 2, 0 <= pad <= kernel / 2; anything else depthwise is F8_ERR_UNSUPPORTED.
@@ -140,6 +140,37 @@ int f8_net_conv(f8_net* net, int src, const f8_conv_desc* desc,
  * F8_ERR_INVALID: dilation < 1, or an empty output; F8_ERR_UNSUPPORTED: dilation > 64, or a depthwise kernel of 5 / 7 with dilation > 1. */
 int f8_net_conv_dilated(f8_net* net, int src, const f8_conv_desc* desc, int dilation,
                         const int32_t* weight_host, const int32_t* bias_host);
+
+/* The same conv with a rectangular kernel, a stride per axis and four pads (nn.Conv2d with tuple kernel_size / stride / dilation behind an explicit
+ * zero pad; ONNX Conv with kernel_shape, strides and pads = [top, left, bottom, right]): the 1x7 / 7x1 of Inception-v3, the 3x1 / 1x3 (dilated) of
+ * ERFNet, the depthwise 1xk / kx1 strips of SegNeXt, the SAME padding (0, 0, 1, 1) of TF-derived stride-2 convs.
+ * `desc` means what it means for f8_net_conv, but its `kernel`, `stride` and `pad` must be 0 (F8_ERR_INVALID): the geometry comes from `geom` only.
+ * weight: host int32 [cout, cin/groups, kh, kw] (int8 values), the kh x kw real taps; bias as f8_net_conv.
+ * Result: [cout, P, Q], P = (H + pad_top + pad_bottom - dilation (kh - 1) - 1) / stride_h + 1 (floor), Q alike from W, pad_left / pad_right, kw and
+ * stride_w; fraclen weight_fl + input_fl.  In wrapping int32 arithmetic
+ *   out[n, co, p, q] = b[co] + sum x_q[n, ci, p stride_h - pad_top + dilation r, q stride_w - pad_left + dilation s] * w[co, ci, r, s]
+ * over ci of the group, r < kh, s < kw, a tap outside the image reading 0; x_q, relu and the bias as f8_net_conv.
+ * Not a new op where it is square: kh == kw, stride_h == stride_w and four equal pads record exactly the node f8_net_conv_dilated records (the same
+ * plan, tokens, fusions and kernels); kh == kw == 1 normalises the dilation to 1.
+ * Accepted, plain (groups == 1): 1 <= kh, kw <= 31, strides >= 1, 1 <= dilation <= 64, each pad from 0 to its axis' extent - 1 (extent =
+ * dilation (k - 1) + 1: a 1-wide axis takes no pad), a non-empty output.  One launch of conv_igemm_kernel that may carry the residual join, as a
+ * dilated conv: `conv1x7s1_t64x64x64[_res]:`, `conv3x1s1d2_...:`, `conv3x5s2x1_...:` where the strides differ.  It joins no fused block or chain.
+ * Accepted, depthwise (groups == cin == cout): strips only — one of kh / kw is 1, the other k with 3 <= k <= 31 —, dilation 1, stride 1 or 2 (the
+ * same on both axes), pads <= k - 1 on the strip axis and 0 on the unit axis: `dwconv1x21s1:` / `dwconv21x1s1:` (f8_dwk.hip: dwstrip_dot4_kernel for
+ * int8-only results at stride 1 under option dwk_dot4, else dwconvk_kernel).
+ * F8_ERR_UNSUPPORTED (the message names the geometry): every other depthwise rectangle (kh, kw both > 1 and unequal, a dilated strip, per-axis
+ * strides), grouped rectangular convs (1 < groups < cin, whatever option `grouped` says).  F8_ERR_INVALID: a null desc / geom, desc->kernel / stride /
+ * pad != 0, a kernel, stride, pad or dilation outside the rules above, an empty output.  F8_ERR_STATE after finalize.
+ * Not built: rectangular pools and transposed convs; grouped rectangular convs; general kh x kw, dilated or per-axis-strided depthwise convs; a
+ * fused 1xk -> kx1 pair; an LDS-patch kernel for strips. */
+typedef struct f8_conv_geom {
+    int32_t kh, kw;
+    int32_t stride_h, stride_w;
+    int32_t pad_top, pad_left, pad_bottom, pad_right;
+    int32_t dilation;      /* one spacing for both axes, as f8_net_conv_dilated */
+} f8_conv_geom;
+int f8_net_conv_rect(f8_net* net, int src, const f8_conv_desc* desc, const f8_conv_geom* geom,
+                     const int32_t* weight_host, const int32_t* bias_host);
 
 /* Transposed convolution (the learned upsampler: nn.ConvTranspose2d(k=2, s=2) of a U-Net decoder, 4x4 / 2 / pad 1 of FCN, CenterNet and pose heads,
  * 3x3 / 2 / pad 1 / output_padding 1 of encoder-decoders).  The reference names a ReLUClipFXQConvTransposeBN (fix_quant_ops.py:9) but defines no such
