@@ -73,6 +73,8 @@ struct Options {
                                  // float converter (v_cvt_f32_i32, v_mul_f32 by 2^-n, v_cvt_pk_u8_f32: exact where planned, f8_device.h)
     int grouped = 0;             // grouped convs (1 < groups < cin): 0 = refused by f8_net_conv; 1 = accepted, on gconv3x3_kernel (f8_gconv.hip) where it applies and as the
                                  // dense expansion (the plain conv kernels over block-diagonal weights) elsewhere; 2 = accepted, always the dense expansion
+    int gconv_wide = 0;          // with grouped = 1: 1 = grouped 3x3 convs of group width cg in {24, 40, 48, 56, 64} (cin == cout, stride 1 / 2, pad 0 / 1) on gconvw3x3_kernel
+                                 // (f8_gconvw.hip, gconvw3x3s<S>:); 0 (default, until it is measured): the dense expansion, as before the kernel existed
     int concat_i8 = 1;           // f8_net_concat: 1 = the byte-gather mode where it is exact (every source written in the output's int8 formats, f8_concat.hip); 0 = always the int32 mode
     int upsample_i8 = 1;         // f8_net_upsample, nearest: 1 = the byte-copy mode where the result is read in at most two int8 formats and by nothing else (f8_upsample.hip); 0 = always the int32 mode
     int sumpool_wide = 1;        // f8_net_avgpool_window: 1 = sumpool_wide_kernel where sumpool_wide_rule says so (windows of 3 and more that do not overlap), else the block walker (f8_sumpool.hip);
@@ -198,6 +200,13 @@ struct GConvArgs {
     int32_t relu0;
     int32_t* out32;
     QuantOut q[2];
+};
+// Grouped 3x3 for group widths cg in {24, 40, 48, 56, 64} (f8_gconvw.hip): GConvArgs' fields with their meaning, the tile included, and the units.
+// A unit = one group x one 32-output subtile of it (KS = ceil(cg / 32) subtiles and K32 steps per tap); a workgroup runs four consecutive units.
+struct GConvWArgs : GConvArgs {            // w: [units][9 taps][KS ksteps][64 lanes][16 B], zero rows / input channels past the group (pack_gconvw_weights)
+    int32_t cg, groups;                    // channels per group; groups (C = groups * cg <= Cs)
+    int32_t units;                         // groups * KS, plus one all-zero unit for the padded channels C .. Cs - 1 where Cs > C
+    int32_t nch;                           // 16-byte chunks of a workgroup's input span that meet a weight: ceil((4 / KS) cg / 16)
 };
 
 struct PoolArgs {                          // max-pool, NHWC
@@ -770,6 +779,9 @@ hipError_t launch_dwk(const DwArgs& a, int inst, hipStream_t s);
 void gconv_tile(int P, int Q, int stride, int* R, int* TW, int* G);
 int gconv_kernel_name(char* buf, size_t cap, const GConvArgs& a);
 hipError_t launch_gconv(const GConvArgs& a, hipStream_t s);
+// grouped 3x3 for group widths 24 .. 64 on the group-aligned MFMA kernel (f8_gconvw.hip); the tile is gconv_tile's
+int gconvw_kernel_name(char* buf, size_t cap, const GConvWArgs& a);
+hipError_t launch_gconvw(const GConvWArgs& a, hipStream_t s);
 int maxpool_inst(const PoolArgs& a);
 const char* maxpool_kernel_name(int inst);
 hipError_t launch_maxpool(const PoolArgs& a, int inst, hipStream_t s);

@@ -159,7 +159,7 @@ static f8_conv_geom geom_of(const Node& n) {
     const f8_conv_desc& d = n.cd;
     return f8_conv_geom{d.kernel, d.kernel, d.stride, d.stride, d.pad, d.pad, d.pad, d.pad, n.dil};
 }
-enum StepKind { S_INPUT, S_CONV, S_DW, S_ADD, S_MAXPOOL, S_AVGPOOL, S_REQUANT, S_OUTPUT, S_FUSED, S_STEMPOOL, S_IR, S_P12, S_CHAIN, S_BCHAIN, S_HEAD2, S_IRCHAIN, S_DWS, S_DWS7, S_IRK, S_GCONV, S_CONCAT, S_UPSAMPLE, S_DECONV, S_SUMPOOL, S_CHANMAP, S_MUL, S_HGATE, S_TABLE, S_ARGMAX, S_PIXMAP };
+enum StepKind { S_INPUT, S_CONV, S_DW, S_ADD, S_MAXPOOL, S_AVGPOOL, S_REQUANT, S_OUTPUT, S_FUSED, S_STEMPOOL, S_IR, S_P12, S_CHAIN, S_BCHAIN, S_HEAD2, S_IRCHAIN, S_DWS, S_DWS7, S_IRK, S_GCONV, S_CONCAT, S_UPSAMPLE, S_DECONV, S_SUMPOOL, S_CHANMAP, S_MUL, S_HGATE, S_TABLE, S_ARGMAX, S_PIXMAP, S_GCONVW };
 // The kernel of a step whose kind has several, chosen once by the step's emitter (pass 3); bind_step, run_step and f8_net_autotune switch on it.
 //   S_CONV:  conv_igemm (f8_kernels.hip), the LDS-patch 3x3 (f8_conv3x3.hip), conv1x1_wreg (f8_wreg.hip), conv1x1_wstat (f8_wstat.hip),
 //            conv3x3s2_wreg (f8_s2conv.hip), the 1x1 conv + average pool (f8_pool.hip), the classifier fc_dense (f8_fc.hip)
@@ -190,7 +190,7 @@ struct Step {
     double bytes_per_img = 0, bytes_const = 0, ops_per_img = 0;
     double valu_per_img = 0;           // ESSENTIAL vector lane-operations per image (f8_net_launch_valu): what the reference's semantics need once the MFMAs are done
     // the launcher's arguments as far as the plan decides them (bind_step); run_step copies them and adds what the run decides
-    std::variant<std::monostate, ConvArgs, StemPoolArgs, FusedArgs, ChainArgs, BChainArgs, BCChainArgs, IRArgs, IRKArgs, IRChainArgs, DwsArgs, Dws7Args, DwArgs, GConvArgs, AddArgs, PoolArgs, AvgArgs, OutArgs, ConcatArgs, UpsampleArgs, ArgmaxArgs, DeconvArgs, SumPoolArgs, ChanMapArgs, PixMapArgs, MulArgs, TableArgs, TableMulArgs> args;
+    std::variant<std::monostate, ConvArgs, StemPoolArgs, FusedArgs, ChainArgs, BChainArgs, BCChainArgs, IRArgs, IRKArgs, IRChainArgs, DwsArgs, Dws7Args, DwArgs, GConvArgs, GConvWArgs, AddArgs, PoolArgs, AvgArgs, OutArgs, ConcatArgs, UpsampleArgs, ArgmaxArgs, DeconvArgs, SumPoolArgs, ChanMapArgs, PixMapArgs, MulArgs, TableArgs, TableMulArgs> args;
     int inst = 0;                      // the instance the launcher starts (the family's *_inst, f8_internal.h; bind_step)
     // S_CHAIN / S_BCHAIN: geometry, workgroups per image and resident per CU, the 7x7 cluster form (f8_cchain.hip)
     int C = 0, MID = 0, H = 0, W = 0, cin0 = 0, tiles = 0, wg_per_cu = 1; bool cluster = false;
@@ -465,6 +465,7 @@ static const OptKey kOptKeys[] = {
     {"whole_batch_launches", "F8_WHOLE_BATCH_LAUNCHES", &Options::whole_batch_launches, 0, 1, true},
     {"tap_tiled", "F8_TAP_TILED", &Options::tap_tiled, 0, 1, true},
     {"grouped", "F8_GROUPED", &Options::grouped, 0, 2, true},
+    {"gconv_wide", "F8_GCONV_WIDE", &Options::gconv_wide, 0, 1, true},
     {"concat_i8", "F8_CONCAT_I8", &Options::concat_i8, 0, 1, true},
     {"upsample_i8", "F8_UPSAMPLE_I8", &Options::upsample_i8, 0, 1, true},
     {"sumpool_wide", "F8_SUMPOOL_WIDE", &Options::sumpool_wide, 0, 2, true},
@@ -1491,6 +1492,36 @@ static void pack_gconv_weights(f8_net* net, Node& nd) {
                 wp[(((size_t)(o >> 5) * 9 + t) * 64 + lane) * 16 + (c & 15)] = v;
             }
         }
+    pack_conv_bias(net, nd, tapsum);
+}
+
+// A grouped 3x3 on gconvw3x3_kernel (f8_gconvw.hip; gconvw_kernel_applies: cin == cout, cg in {24, 40, 48, 56, 64}).  A UNIT is one group g x one
+// subtile j of its outputs: rows i < live = min(32, cg - 32 j) are output channels g cg + 32 j + i, K index kk < cg is input channel g cg + kk, over
+// KS = ceil(cg / 32) K32 steps per tap; every other row and K byte stays zero, so the kernel needs no notion of groups.  Fragment order
+// [unit][tap][kstep][lane][16 B], the lane <-> (row, K half) map of pack_gconv_weights.  Where Cs > C one more unit of zeros follows the last group:
+// it writes the padded channels C .. Cs - 1 as zero accumulator + zero bias.  The bias table is pack_conv_weights'.
+static int gconvw_units(const f8_conv_desc& d, int Cs) { return d.groups * ((d.cin / d.groups + 31) / 32) + (Cs > d.cout ? 1 : 0); }
+static void pack_gconvw_weights(f8_net* net, Node& nd) {
+    const f8_conv_desc& d = nd.cd;
+    const Tensor& src = net->tensors[nd.a];
+    const int cg = d.cin / d.groups, KS = (cg + 31) / 32;
+    nd.coutP = src.Cs; nd.ck = 32 * KS; nd.ktot = 9 * 32 * KS;
+    nd.w_off = round_up_z(net->wblob.size(), 256);
+    net->wblob.resize(nd.w_off + (size_t)gconvw_units(d, src.Cs) * 9 * KS * 1024, 0);
+    std::vector<long long> tapsum((size_t)d.cout * 9, 0);
+    int8_t* wp = (int8_t*)net->wblob.data() + nd.w_off;
+    for (int o = 0; o < d.cout; ++o) {
+        const int g = o / cg, i = o % cg;                       // row i & 31 of unit g KS + i / 32
+        const size_t unit = (size_t)g * KS + i / 32;
+        for (int kk = 0; kk < cg; ++kk) {
+            const int lane = (i & 31) + 32 * ((kk & 31) >> 4);
+            for (int t = 0; t < 9; ++t) {
+                const int8_t v = nd.w[((size_t)o * cg + kk) * 9 + t];
+                tapsum[(size_t)o * 9 + t] += v;
+                wp[((((unit * 9 + t) * KS + kk / 32) * 64) + lane) * 16 + (kk & 15)] = v;
+            }
+        }
+    }
     pack_conv_bias(net, nd, tapsum);
 }
 
@@ -2952,23 +2983,31 @@ static bool gconv_kernel_applies(const Options& opt, const Node& n) {
     const int cg = d.cin / d.groups;
     return opt.grouped == 1 && d.kernel == 3 && n.dil == 1 && (d.stride == 1 || d.stride == 2) && d.pad <= 1 && d.cin == d.cout && cg >= 2 && cg <= 32 && 32 % cg == 0;
 }
-// a grouped 3x3 on the slice-diagonal kernel: always a launch of its own, no join
-static int emit_gconv(f8_net* net, int i, Step& st, std::vector<int>* extra) {
+// ... and which run on gconvw3x3_kernel (f8_gconvw.hip) under grouped = 1 with option gconv_wide = 1: the same geometry at the group widths a 32-channel
+// slice cannot hold.  NOT measured against the expansion yet — hence the option, default 0.
+static bool gconvw_kernel_applies(const Options& opt, const Node& n) {
+    const f8_conv_desc& d = n.cd;
+    const int cg = d.cin / d.groups;
+    return opt.grouped == 1 && opt.gconv_wide == 1 && d.kernel == 3 && n.dil == 1 && (d.stride == 1 || d.stride == 2) && d.pad <= 1 && d.cin == d.cout &&
+           (cg == 24 || cg == 40 || cg == 48 || cg == 56 || cg == 64);
+}
+// a grouped 3x3 on the slice-diagonal kernel or (wide) the group-aligned one: always a launch of its own, no join
+static int emit_gconv(f8_net* net, int i, Step& st, std::vector<int>* extra, bool wide) {
     auto& T = net->tensors;
     Node& nd = net->nodes[i];
     const f8_conv_desc& d = nd.cd;
     const Tensor& s = T[nd.a]; const Tensor& o = T[nd.out];
-    st.kind = S_GCONV;
+    st.kind = wide ? S_GCONVW : S_GCONV;
     if (const int rc = conv_input_i8(net, nd, &st.src_t, &st.src_f)) return rc;
     st.relu0 = d.relu;
-    pack_gconv_weights(net, nd);
+    if (wide) pack_gconvw_weights(net, nd); else pack_gconv_weights(net, nd);
     select_outputs(net, nd.out, &st.out, extra);
     const double opix = (double)o.H * o.W;
     st.ops_per_img = conv_ops(net, nd);
     st.bytes_per_img = (double)s.H * s.W * s.Cs + out_bytes(st, o, opix);
     st.bytes_const = weight_bytes(net, nd);
     st.valu_per_img = 3.0 * opix * o.Cs * out_forms8(st);
-    char buf[64]; snprintf(buf, sizeof buf, "gconv3x3s%d:", d.stride);
+    char buf[64]; snprintf(buf, sizeof buf, wide ? "gconvw3x3s%d:" : "gconv3x3s%d:", d.stride);
     st.name = buf + tname(net, nd.out);
     return F8_OK;
 }
@@ -3007,7 +3046,8 @@ static int emit_conv_family(f8_net* net, int i, int max_batch, Step& st, std::ve
         case B_IR: case B_IRK: return emit_ir(net, i, st, extra);
         case B_DWS: return emit_dws(net, i, st, extra);
         default:
-            if (nd.grouped && gconv_kernel_applies(net->opt, nd)) return emit_gconv(net, i, st, extra);
+            if (nd.grouped && gconv_kernel_applies(net->opt, nd)) return emit_gconv(net, i, st, extra, false);
+            if (nd.grouped && gconvw_kernel_applies(net->opt, nd)) return emit_gconv(net, i, st, extra, true);
             return emit_conv(net, i, max_batch, st, extra);
     }
 }
@@ -3888,10 +3928,11 @@ static int bind_step(f8_net* net, Step& st) {
             }
             st.args = a; break;
         }
-        case S_GCONV: {
+        case S_GCONV: case S_GCONVW: {
             const Tensor& sT = T[st.src_t];
             const Tensor& oT = T[nd.out];
-            GConvArgs a{};
+            GConvWArgs wa{};
+            GConvArgs& a = wa;
             a.w = W8(nd.w_off); a.bias = B32(nd.b_off);
             a.ncc = nd.ncc;
             if (nd.ncc > 0) { a.rowcls = (const uint8_t*)W8(nd.rc_off); a.colcls = (const uint8_t*)W8(nd.cc_off); }
@@ -3904,8 +3945,13 @@ static int bind_step(f8_net* net, Step& st) {
             a.dRTW = fast_divisor((uint32_t)(a.R * a.TW));
             a.dTW = fast_divisor((uint32_t)a.TW);
             a.relu0 = st.relu0;
-            gconv_kernel_name(kb, sizeof kb, a);                  // integer requantisation whatever requant_float says (as f8_dwk.hip)
-            out_formats(a.q); st.args = a; break;
+            out_formats(a.q);                                     // integer requantisation whatever requant_float says (as f8_dwk.hip)
+            if (st.kind == S_GCONV) { gconv_kernel_name(kb, sizeof kb, a); st.args = a; break; }
+            wa.groups = nd.cd.groups; wa.cg = nd.cd.cin / nd.cd.groups;
+            wa.units = gconvw_units(nd.cd, sT.Cs);
+            wa.nch = (4 / ((wa.cg + 31) / 32) * wa.cg + 15) / 16;
+            gconvw_kernel_name(kb, sizeof kb, wa);
+            st.args = wa; break;
         }
         case S_DECONV: {
             const Tensor& sT = T[st.src_t];
@@ -4444,6 +4490,7 @@ static int run_step(const f8_net* net, const RunIO& io, const Step& st, int n0, 
             break;
         }
         case S_GCONV: { GConvArgs a = std::get<GConvArgs>(st.args); a.x_bytes = (uint32_t)(src_io(a, &a.out32).bytes_per_img * N); e = launch_gconv(a, s); break; }
+        case S_GCONVW: { GConvWArgs a = std::get<GConvWArgs>(st.args); a.x_bytes = (uint32_t)(src_io(a, &a.out32).bytes_per_img * N); e = launch_gconvw(a, s); break; }
         case S_DECONV: { DeconvArgs a = std::get<DeconvArgs>(st.args); a.x_bytes = (uint32_t)(src_io(a, &a.out32).bytes_per_img * N); e = launch_deconv(a, st.inst, s); break; }
         case S_SUMPOOL: { SumPoolArgs a = std::get<SumPoolArgs>(st.args); src_io(a, &a.out32); e = launch_sumpool(a, st.inst, s); break; }
         case S_MAXPOOL: { PoolArgs a = std::get<PoolArgs>(st.args); src_io(a, &a.out32); e = launch_maxpool(a, st.inst, s); break; }

@@ -550,6 +550,10 @@ int f8_net_check(f8_net* net);
  *               every other grouped conv runs as the DENSE EXPANSION, the plain conv kernels over block-diagonal weights, plan token
  *               gconv{k}x{k}s{S}_dense:; 2: accepted, always the dense expansion.  Set it before the f8_net_conv call that adds the
  *               grouped conv.  Same values in both, bit for bit; depthwise convs keep their own rules and kernels whatever it says),
+ *               gconv_wide (default 0; environment F8_GCONV_WIDE.  With grouped = 1: 1 = the same geometry — kernel 3, stride 1 / 2, pad 0 / 1,
+ *               dilation 1, cin == cout — at cin / groups in {24, 40, 48, 56, 64} runs f8::gconvw3x3_kernel<S, KS>, f8_gconvw.hip, plan token
+ *               gconvw3x3s{S}:, in place of the dense expansion; 0: every plan, token and kernel as without the key.  Nothing sets it unasked:
+ *               build_net / IntGraph.build_net forward an `options` entry.  Same values either way, bit for bit; grouped = 2 ignores it),
  *               concat_i8 (default 1: a concat whose result is read in at most two int8 formats and by nothing else, with values the planner can
  *               bound, runs f8::concat_i8_kernel on its operands' int8 forms, plan token concat_i8:; 0: every concat runs f8::concat_i32_kernel on
  *               their int32 forms, token concat_i32:.  Same values either way, bit for bit),
