@@ -75,6 +75,8 @@ struct Options {
                                  // dense expansion (the plain conv kernels over block-diagonal weights) elsewhere; 2 = accepted, always the dense expansion
     int gconv_wide = 0;          // with grouped = 1: 1 = grouped 3x3 convs of group width cg in {24, 40, 48, 56, 64} (cin == cout, stride 1 / 2, pad 0 / 1) on gconvw3x3_kernel
                                  // (f8_gconvw.hip, gconvw3x3s<S>:); 0 (default, until it is measured): the dense expansion, as before the kernel existed
+    int gconv_xwide = 0;         // with grouped = 1: 1 = grouped 3x3 convs of group width cg = 72 .. 256, a multiple of 8 (cin == cout, groups >= 2, stride 1 / 2, pad 0 / 1) on
+                                 // gconvx3x3_kernel (f8_gconvx.hip, gconvx3x3s<S>:); 0 (default): the dense expansion, as before the kernel existed
     int concat_i8 = 1;           // f8_net_concat: 1 = the byte-gather mode where it is exact (every source written in the output's int8 formats, f8_concat.hip); 0 = always the int32 mode
     int upsample_i8 = 1;         // f8_net_upsample, nearest: 1 = the byte-copy mode where the result is read in at most two int8 formats and by nothing else (f8_upsample.hip); 0 = always the int32 mode
     int sumpool_wide = 1;        // f8_net_avgpool_window: 1 = sumpool_wide_kernel where sumpool_wide_rule says so (windows of 3 and more that do not overlap), else the block walker (f8_sumpool.hip);
@@ -207,6 +209,16 @@ struct GConvWArgs : GConvArgs {            // w: [units][9 taps][KS ksteps][64 l
     int32_t cg, groups;                    // channels per group; groups (C = groups * cg <= Cs)
     int32_t units;                         // groups * KS, plus one all-zero unit for the padded channels C .. Cs - 1 where Cs > C
     int32_t nch;                           // 16-byte chunks of a workgroup's input span that meet a weight: ceil((4 / KS) cg / 16)
+};
+// Grouped 3x3 for group widths cg = 72 .. 256, a multiple of 8 (f8_gconvx.hip): GConvArgs' fields with their meaning (the tile is gconvx_tile's), the
+// units of GConvWArgs in the same packed order, streamed: a workgroup runs ONE group's KS subtiles over its tile, accumulators stationary.
+struct GConvXArgs : GConvArgs {            // w: [groups (+ 1 pad unit)][KS subtiles][9 taps][KS ksteps][64 lanes][16 B] (pack_gconvw_weights)
+    int32_t cg, groups;                    // channels per group; groups (C = groups * cg <= Cs)
+    int32_t units;                         // groups * KS, plus one all-zero unit for the padded channels C .. Cs - 1 where Cs > C
+    int32_t ks;                            // KS = ceil(cg / 32): subtiles of a group, K32 steps per tap
+    int32_t pitch;                         // bytes of a patch pixel in LDS: 32 KS + 16 (gconvx_pitch)
+    int32_t psplit, ipg;                   // a subtile's pixel groups are dealt to the waves in psplit parts of ipg = ceil(groups of the tile / psplit) <= 8
+    FastDiv dCH;                           // / (pitch / 16)
 };
 
 struct PoolArgs {                          // max-pool, NHWC
@@ -782,6 +794,11 @@ hipError_t launch_gconv(const GConvArgs& a, hipStream_t s);
 // grouped 3x3 for group widths 24 .. 64 on the group-aligned MFMA kernel (f8_gconvw.hip); the tile is gconv_tile's
 int gconvw_kernel_name(char* buf, size_t cap, const GConvWArgs& a);
 hipError_t launch_gconvw(const GConvWArgs& a, hipStream_t s);
+// grouped 3x3 for group widths 72 .. 256 on the weight-streaming MFMA kernel (f8_gconvx.hip), and its pitch-aware tile
+int gconvx_pitch(int cg);
+void gconvx_tile(int P, int Q, int stride, int cg, int* R, int* TW, int* G, int* psplit);
+int gconvx_kernel_name(char* buf, size_t cap, const GConvXArgs& a);
+hipError_t launch_gconvx(const GConvXArgs& a, hipStream_t s);
 int maxpool_inst(const PoolArgs& a);
 const char* maxpool_kernel_name(int inst);
 hipError_t launch_maxpool(const PoolArgs& a, int inst, hipStream_t s);

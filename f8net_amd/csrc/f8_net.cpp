@@ -159,7 +159,7 @@ static f8_conv_geom geom_of(const Node& n) {
     const f8_conv_desc& d = n.cd;
     return f8_conv_geom{d.kernel, d.kernel, d.stride, d.stride, d.pad, d.pad, d.pad, d.pad, n.dil};
 }
-enum StepKind { S_INPUT, S_CONV, S_DW, S_ADD, S_MAXPOOL, S_AVGPOOL, S_REQUANT, S_OUTPUT, S_FUSED, S_STEMPOOL, S_IR, S_P12, S_CHAIN, S_BCHAIN, S_HEAD2, S_IRCHAIN, S_DWS, S_DWS7, S_IRK, S_GCONV, S_CONCAT, S_UPSAMPLE, S_DECONV, S_SUMPOOL, S_CHANMAP, S_MUL, S_HGATE, S_TABLE, S_ARGMAX, S_PIXMAP, S_GCONVW };
+enum StepKind { S_INPUT, S_CONV, S_DW, S_ADD, S_MAXPOOL, S_AVGPOOL, S_REQUANT, S_OUTPUT, S_FUSED, S_STEMPOOL, S_IR, S_P12, S_CHAIN, S_BCHAIN, S_HEAD2, S_IRCHAIN, S_DWS, S_DWS7, S_IRK, S_GCONV, S_CONCAT, S_UPSAMPLE, S_DECONV, S_SUMPOOL, S_CHANMAP, S_MUL, S_HGATE, S_TABLE, S_ARGMAX, S_PIXMAP, S_GCONVW, S_GCONVX };
 // The kernel of a step whose kind has several, chosen once by the step's emitter (pass 3); bind_step, run_step and f8_net_autotune switch on it.
 //   S_CONV:  conv_igemm (f8_kernels.hip), the LDS-patch 3x3 (f8_conv3x3.hip), conv1x1_wreg (f8_wreg.hip), conv1x1_wstat (f8_wstat.hip),
 //            conv3x3s2_wreg (f8_s2conv.hip), the 1x1 conv + average pool (f8_pool.hip), the classifier fc_dense (f8_fc.hip)
@@ -190,7 +190,7 @@ struct Step {
     double bytes_per_img = 0, bytes_const = 0, ops_per_img = 0;
     double valu_per_img = 0;           // ESSENTIAL vector lane-operations per image (f8_net_launch_valu): what the reference's semantics need once the MFMAs are done
     // the launcher's arguments as far as the plan decides them (bind_step); run_step copies them and adds what the run decides
-    std::variant<std::monostate, ConvArgs, StemPoolArgs, FusedArgs, ChainArgs, BChainArgs, BCChainArgs, IRArgs, IRKArgs, IRChainArgs, DwsArgs, Dws7Args, DwArgs, GConvArgs, GConvWArgs, AddArgs, PoolArgs, AvgArgs, OutArgs, ConcatArgs, UpsampleArgs, ArgmaxArgs, DeconvArgs, SumPoolArgs, ChanMapArgs, PixMapArgs, MulArgs, TableArgs, TableMulArgs> args;
+    std::variant<std::monostate, ConvArgs, StemPoolArgs, FusedArgs, ChainArgs, BChainArgs, BCChainArgs, IRArgs, IRKArgs, IRChainArgs, DwsArgs, Dws7Args, DwArgs, GConvArgs, GConvWArgs, GConvXArgs, AddArgs, PoolArgs, AvgArgs, OutArgs, ConcatArgs, UpsampleArgs, ArgmaxArgs, DeconvArgs, SumPoolArgs, ChanMapArgs, PixMapArgs, MulArgs, TableArgs, TableMulArgs> args;
     int inst = 0;                      // the instance the launcher starts (the family's *_inst, f8_internal.h; bind_step)
     // S_CHAIN / S_BCHAIN: geometry, workgroups per image and resident per CU, the 7x7 cluster form (f8_cchain.hip)
     int C = 0, MID = 0, H = 0, W = 0, cin0 = 0, tiles = 0, wg_per_cu = 1; bool cluster = false;
@@ -466,6 +466,7 @@ static const OptKey kOptKeys[] = {
     {"tap_tiled", "F8_TAP_TILED", &Options::tap_tiled, 0, 1, true},
     {"grouped", "F8_GROUPED", &Options::grouped, 0, 2, true},
     {"gconv_wide", "F8_GCONV_WIDE", &Options::gconv_wide, 0, 1, true},
+    {"gconv_xwide", "F8_GCONV_XWIDE", &Options::gconv_xwide, 0, 1, true},
     {"concat_i8", "F8_CONCAT_I8", &Options::concat_i8, 0, 1, true},
     {"upsample_i8", "F8_UPSAMPLE_I8", &Options::upsample_i8, 0, 1, true},
     {"sumpool_wide", "F8_SUMPOOL_WIDE", &Options::sumpool_wide, 0, 2, true},
@@ -2991,13 +2992,27 @@ static bool gconvw_kernel_applies(const Options& opt, const Node& n) {
     return opt.grouped == 1 && opt.gconv_wide == 1 && d.kernel == 3 && n.dil == 1 && (d.stride == 1 || d.stride == 2) && d.pad <= 1 && d.cin == d.cout &&
            (cg == 24 || cg == 40 || cg == 48 || cg == 56 || cg == 64);
 }
-// a grouped 3x3 on the slice-diagonal kernel or (wide) the group-aligned one: always a launch of its own, no join
-static int emit_gconv(f8_net* net, int i, Step& st, std::vector<int>* extra, bool wide) {
+// ... and which run on gconvx3x3_kernel (f8_gconvx.hip) under grouped = 1 with option gconv_xwide = 1: the same geometry at group widths 72 .. 256 (a
+// multiple of 8), where a group is a GEMM of its own and the weights are streamed.  Default 0, as gconv_wide (second addendum).
+// MEASURED SLOWER, kept on the expansion: two groups at stride 2 on a map of more than one tile (128 output pixels) — 240 x 56 x 56 / 2 at cg 120: 160 against
+// 99 us (profiles/gconv_xwide_r20.md): the expansion only doubles the work there, and the kernel's row tiles re-read their stride-2 patch rows.
+static bool gconvx_kernel_applies(const f8_net* net, const Node& n) {
+    const Options& opt = net->opt;
+    const f8_conv_desc& d = n.cd;
+    const Tensor& o = net->tensors[n.out];
+    const int cg = d.cin / d.groups;
+    return opt.grouped == 1 && opt.gconv_xwide == 1 && d.kernel == 3 && n.dil == 1 && (d.stride == 1 || d.stride == 2) && d.pad <= 1 && d.cin == d.cout &&
+           d.groups >= 2 && cg % 8 == 0 && cg >= 72 && cg <= 256 && !(d.groups == 2 && d.stride == 2 && o.H * o.W > 128);
+}
+// a grouped 3x3 on the slice-diagonal kernel (S_GCONV), the group-aligned one (S_GCONVW) or the weight-streaming one (S_GCONVX, which reads S_GCONVW's packed
+// weights): always a launch of its own, no join
+static int emit_gconv(f8_net* net, int i, Step& st, std::vector<int>* extra, StepKind kind) {
+    const bool wide = kind != S_GCONV;
     auto& T = net->tensors;
     Node& nd = net->nodes[i];
     const f8_conv_desc& d = nd.cd;
     const Tensor& s = T[nd.a]; const Tensor& o = T[nd.out];
-    st.kind = wide ? S_GCONVW : S_GCONV;
+    st.kind = kind;
     if (const int rc = conv_input_i8(net, nd, &st.src_t, &st.src_f)) return rc;
     st.relu0 = d.relu;
     if (wide) pack_gconvw_weights(net, nd); else pack_gconv_weights(net, nd);
@@ -3007,7 +3022,7 @@ static int emit_gconv(f8_net* net, int i, Step& st, std::vector<int>* extra, boo
     st.bytes_per_img = (double)s.H * s.W * s.Cs + out_bytes(st, o, opix);
     st.bytes_const = weight_bytes(net, nd);
     st.valu_per_img = 3.0 * opix * o.Cs * out_forms8(st);
-    char buf[64]; snprintf(buf, sizeof buf, wide ? "gconvw3x3s%d:" : "gconv3x3s%d:", d.stride);
+    char buf[64]; snprintf(buf, sizeof buf, kind == S_GCONVX ? "gconvx3x3s%d:" : wide ? "gconvw3x3s%d:" : "gconv3x3s%d:", d.stride);
     st.name = buf + tname(net, nd.out);
     return F8_OK;
 }
@@ -3046,8 +3061,9 @@ static int emit_conv_family(f8_net* net, int i, int max_batch, Step& st, std::ve
         case B_IR: case B_IRK: return emit_ir(net, i, st, extra);
         case B_DWS: return emit_dws(net, i, st, extra);
         default:
-            if (nd.grouped && gconv_kernel_applies(net->opt, nd)) return emit_gconv(net, i, st, extra, false);
-            if (nd.grouped && gconvw_kernel_applies(net->opt, nd)) return emit_gconv(net, i, st, extra, true);
+            if (nd.grouped && gconv_kernel_applies(net->opt, nd)) return emit_gconv(net, i, st, extra, S_GCONV);
+            if (nd.grouped && gconvw_kernel_applies(net->opt, nd)) return emit_gconv(net, i, st, extra, S_GCONVW);
+            if (nd.grouped && gconvx_kernel_applies(net, nd)) return emit_gconv(net, i, st, extra, S_GCONVX);
             return emit_conv(net, i, max_batch, st, extra);
     }
 }
@@ -3928,16 +3944,19 @@ static int bind_step(f8_net* net, Step& st) {
             }
             st.args = a; break;
         }
-        case S_GCONV: case S_GCONVW: {
+        case S_GCONV: case S_GCONVW: case S_GCONVX: {
             const Tensor& sT = T[st.src_t];
             const Tensor& oT = T[nd.out];
             GConvWArgs wa{};
-            GConvArgs& a = wa;
+            GConvXArgs xa{};
+            GConvArgs& a = st.kind == S_GCONVX ? (GConvArgs&)xa : wa;
+            const int cg = nd.cd.cin / nd.cd.groups;
             a.w = W8(nd.w_off); a.bias = B32(nd.b_off);
             a.ncc = nd.ncc;
             if (nd.ncc > 0) { a.rowcls = (const uint8_t*)W8(nd.rc_off); a.colcls = (const uint8_t*)W8(nd.cc_off); }
             a.H = sT.H; a.W = sT.W; a.P = oT.H; a.Q = oT.W; a.Cs = sT.Cs; a.stride = nd.cd.stride; a.pad = nd.cd.pad;
-            gconv_tile(a.P, a.Q, a.stride, &a.R, &a.TW, &a.G);
+            if (st.kind == S_GCONVX) gconvx_tile(a.P, a.Q, a.stride, cg, &a.R, &a.TW, &a.G, &xa.psplit);
+            else gconv_tile(a.P, a.Q, a.stride, &a.R, &a.TW, &a.G);
             a.tiles_r = (a.P + a.R - 1) / a.R; a.tiles_c = (a.Q + a.TW - 1) / a.TW;
             a.PR = (a.R - 1) * a.stride + 3; a.PW = (a.TW - 1) * a.stride + 3;
             a.dIPP = fast_divisor((uint32_t)(a.PR * a.PW));
@@ -3947,7 +3966,16 @@ static int bind_step(f8_net* net, Step& st) {
             a.relu0 = st.relu0;
             out_formats(a.q);                                     // integer requantisation whatever requant_float says (as f8_dwk.hip)
             if (st.kind == S_GCONV) { gconv_kernel_name(kb, sizeof kb, a); st.args = a; break; }
-            wa.groups = nd.cd.groups; wa.cg = nd.cd.cin / nd.cd.groups;
+            if (st.kind == S_GCONVX) {
+                xa.groups = nd.cd.groups; xa.cg = cg; xa.ks = (cg + 31) / 32;
+                xa.units = gconvw_units(nd.cd, sT.Cs);
+                xa.pitch = gconvx_pitch(cg);
+                xa.dCH = fast_divisor((uint32_t)(xa.pitch / 16));
+                xa.ipg = ((a.G * a.R * a.TW + 31) / 32 + xa.psplit - 1) / xa.psplit;
+                gconvx_kernel_name(kb, sizeof kb, xa);
+                st.args = xa; break;
+            }
+            wa.groups = nd.cd.groups; wa.cg = cg;
             wa.units = gconvw_units(nd.cd, sT.Cs);
             wa.nch = (4 / ((wa.cg + 31) / 32) * wa.cg + 15) / 16;
             gconvw_kernel_name(kb, sizeof kb, wa);
@@ -4491,6 +4519,7 @@ static int run_step(const f8_net* net, const RunIO& io, const Step& st, int n0, 
         }
         case S_GCONV: { GConvArgs a = std::get<GConvArgs>(st.args); a.x_bytes = (uint32_t)(src_io(a, &a.out32).bytes_per_img * N); e = launch_gconv(a, s); break; }
         case S_GCONVW: { GConvWArgs a = std::get<GConvWArgs>(st.args); a.x_bytes = (uint32_t)(src_io(a, &a.out32).bytes_per_img * N); e = launch_gconvw(a, s); break; }
+        case S_GCONVX: { GConvXArgs a = std::get<GConvXArgs>(st.args); a.x_bytes = (uint32_t)(src_io(a, &a.out32).bytes_per_img * N); e = launch_gconvx(a, s); break; }
         case S_DECONV: { DeconvArgs a = std::get<DeconvArgs>(st.args); a.x_bytes = (uint32_t)(src_io(a, &a.out32).bytes_per_img * N); e = launch_deconv(a, st.inst, s); break; }
         case S_SUMPOOL: { SumPoolArgs a = std::get<SumPoolArgs>(st.args); src_io(a, &a.out32); e = launch_sumpool(a, st.inst, s); break; }
         case S_MAXPOOL: { PoolArgs a = std::get<PoolArgs>(st.args); src_io(a, &a.out32); e = launch_maxpool(a, st.inst, s); break; }

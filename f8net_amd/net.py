@@ -25,9 +25,11 @@ def accept_grouped(net, convs, options=None):
     """The raw builder refuses grouped convs (1 < groups < cin) unless the handle's option `grouped` says otherwise, and the option must be set
     before the conv is added.  The high-level entry points call this before they record: a value the caller gave (options, or F8_GROUPED in the
     environment) is applied as it is; with none, `grouped` becomes 1 when one of `convs` — (cin, groups) pairs — is grouped.  A `gconv_wide` key of
-    `options` (group widths 24 .. 64 on the group-aligned kernel) is forwarded the same way; nothing sets it unasked."""
-    if options and 'gconv_wide' in options:
-        net.set_option('gconv_wide', options['gconv_wide'])
+    `options` (group widths 24 .. 64 on the group-aligned kernel) and a `gconv_xwide` key (72 .. 256 on the weight-streaming kernel) are forwarded the same
+    way; nothing sets them unasked."""
+    for key in ('gconv_wide', 'gconv_xwide'):
+        if options and key in options:
+            net.set_option(key, options[key])
     if options and 'grouped' in options:
         net.set_option('grouped', options['grouped'])
     elif 'F8_GROUPED' not in os.environ and any(1 < g < cin for cin, g in convs):
@@ -569,7 +571,7 @@ def build_net(spec: topology.NetSpec, params: dict, max_batch: int, hw: int = 22
 
 def record_net(spec: topology.NetSpec, params: dict, hw: int = 224, input_fraclen=None, taps=(), options=None) -> F8Net:
     """The recording half of build_net: the graph is in the handle, not yet planned (set planning options, then finalize).
-    options: only its `grouped` and `gconv_wide` keys are read here — grouped convs are accepted while they are recorded (accept_grouped).
+    options: only its `grouped`, `gconv_wide` and `gconv_xwide` keys are read here — grouped convs are accepted while they are recorded (accept_grouped).
 
     taps: names of further tensors to return, marked as int32 outputs 1, 2, ... in the order given (output 0 stays the float
     logits).  A name is a block name (`stage_1_layer_3`: the block's output tensor, whether or not the block ends in a join), a

@@ -554,6 +554,11 @@ int f8_net_check(f8_net* net);
  *               dilation 1, cin == cout — at cin / groups in {24, 40, 48, 56, 64} runs f8::gconvw3x3_kernel<S, KS>, f8_gconvw.hip, plan token
  *               gconvw3x3s{S}:, in place of the dense expansion; 0: every plan, token and kernel as without the key.  Nothing sets it unasked:
  *               build_net / IntGraph.build_net forward an `options` entry.  Same values either way, bit for bit; grouped = 2 ignores it),
+ *               gconv_xwide (default 0; environment F8_GCONV_XWIDE.  With grouped = 1: 1 = that geometry at cin / groups = 72 .. 256, a multiple of 8,
+ *               groups >= 2, runs f8::gconvx3x3_kernel<S, NPG>, f8_gconvx.hip, plan token gconvx3x3s{S}:, in place of the dense expansion — except two
+ *               groups at stride 2 on a map of more than 128 output pixels, measured slower; 0: every plan, token and kernel as without the key.
+ *               Nothing sets it unasked; forwarded like gconv_wide.  Same values either way, bit for bit; grouped = 2 ignores it.  Out of scope:
+ *               cin != cout, other group widths, kernel sizes, dilation, a join in the epilogue),
  *               concat_i8 (default 1: a concat whose result is read in at most two int8 formats and by nothing else, with values the planner can
  *               bound, runs f8::concat_i8_kernel on its operands' int8 forms, plan token concat_i8:; 0: every concat runs f8::concat_i32_kernel on
  *               their int32 forms, token concat_i32:.  Same values either way, bit for bit),
