@@ -5,7 +5,8 @@
  *            -> one hgate+chmul_i8: launch (the gate emits none)
  *   hswish   hard-swish of a conv result that is also a network output        -> hgate+mul_i32:
  *   shared   a hard gate read by the channel gate AND by a conv: not fusable  -> hgate: then chmul_i8:
- * and walks the refusals of both entry points.  tests/test_mul_plan.py builds the library's host code with AddressSanitizer and
+ * and walks the refusals of both entry points.  With the switch --fuse-se the se graph sets option fuse_se = 1: avgpool_sum and the
+ * two FCs plan as ONE avgpool+fc+fc: launch (tests/test_se_plan.py runs it so).  tests/test_mul_plan.py builds the library's host code with AddressSanitizer and
  * UndefinedBehaviorSanitizer and runs this program against it. */
 #include <stdio.h>
 #include <stdlib.h>
@@ -59,13 +60,15 @@ static int finish(f8_net* net, const char* what) {
     return 0;
 }
 
-int main(void) {
+int main(int argc, char** argv) {
+    const int fuse_se = argc > 1 && !strcmp(argv[1], "--fuse-se");
     int x, src, other, pool, f1, f2, gate, m, k, deep;
     f8_mul_desc d;
     f8_net* net;
 
     net = f8_net_create();                                   /* se */
     if (!net) return 1;
+    if (fuse_se) CHECK(f8_net_set_option(net, "fuse_se", 1));
     CHECK(x = f8_net_input(net, 8, 7, 7, 8));
     CHECK(src = conv(net, x, 8, 48, 5, 8, 0, 0, 1));                     /* fraclen 13 */
     CHECK(other = conv(net, x, 8, 24, 5, 8, 0, 0, 1));
@@ -86,7 +89,8 @@ int main(void) {
     d = fmt(4, 0, -1, 0, 0);
     EXPECT(f8_net_mul(net, src, gate, &d), F8_ERR_INVALID);
     EXPECT(f8_net_hard_gate(net, 99), F8_ERR_INVALID);
-    CHECK(deep = fc(net, pool, 48, 16, 31, 0, 0));                       /* fraclen 31 */
+    CHECK(deep = f8_net_avgpool_sum(net, other, 6));                     /* (a pool of its own: the se branch's keeps fc1 as its only reader) */
+    CHECK(deep = fc(net, deep, 24, 16, 31, 0, 0));                       /* fraclen 31 */
     EXPECT(f8_net_hard_gate(net, deep), F8_ERR_INVALID);                 /* 6 * 2^31 does not fit */
     d = fmt(4, 0, 5, 0, 0);
     CHECK(m = f8_net_mul(net, src, gate, &d));

@@ -88,6 +88,8 @@ struct Options {
     int table_i8 = 1;            // f8_net_table: 1 = the byte-gather mode where the result is read in at most two int8 formats and by nothing else (table_i8:, f8_table.hip); 0 = always table_i32:
     int fuse_table = 1;          // a table read by the b operand of one broadcast mul alone: 1 = no launch of its own where the map has fewer than 2^20 values an image (the measured rule, fuse_table_rule in f8_net.cpp), the mul launch looks b up itself (table+chmul_*:, f8_table.hip); 2 = always; 0 = two launches
     int fuse_argmax = 1;         // an argmax output on an upsample's result that nothing else reads: 1 = one launch that interpolates and reduces in registers, the upsampled tensor in no form (upsample_*+argmax_*:, f8_argmax.hip); 0 = the upsample launch and an argmax_*: launch
+    int fuse_se = 0;             // the squeeze path of an SE branch — avgpool_sum -> linear / 1x1 conv -> linear / 1x1 conv, the first two results private — in ONE launch, one
+                                 // workgroup per image (avgpool+fc+fc:, f8_se.hip): 1 = where both layers together are at most 2^17 multiply-adds an image (the measured rule, fuse_se_rule in f8_net.cpp); 2 = every match; 0 (default): the three launches
     int tap_tiled = 1;           // network outputs 1 .. leave on tap_kernel (f8_tap.hip: walks the I32T blocks, every loaded byte used); 0: on output_kernel like output 0
     int check_input_range = 1;   // int32 inputs that are NARROWED to the head's 8-bit format (no requant) are range-checked on the device; f8_net_check reports
 };
@@ -360,6 +362,25 @@ struct TableArgs {
 // A table fused into the broadcast mul that reads it (table_chmul_*_kernel, f8_table.hip): m is the mul's record with gate == 0, bcast == 1 and
 // m.b = the TABLE's source in its int8 index format (N rows of Cs bytes); bt is the byte table composed for the mul's format of b (m.rb).
 struct TableMulArgs { MulArgs m; const uint8_t* bt; };
+
+// The squeeze path of an SE branch in one launch (f8_se.hip; option fuse_se): out = fc2(fc1(sum over the map's pixels of x)), one workgroup per image.
+// A layer: `w` is pack_se_weights' image (f8_net.cpp) in the order its mapping reads — klanes != 0: [coutP][Kp] int8 rows; else K-major [Kp / 4][coutP]
+// dwords —, zero beyond K and cout; bias[coutP] is offset-corrected (+ 128 sum(w) for an unsigned, biased-stored input); rq requantises the layer's
+// int32 input (the pooled sum / fc1's result) to its int8 input format.
+constexpr int kSeMaxC = 4096, kSeMaxMid = 1024;          // the block's limits: channels of the map (and of fc2's result), fc1's outputs
+struct SELayer {
+    const int8_t* w; const int32_t* bias;
+    int32_t K, Kp, cout, coutP;                          // inputs, padded to 16; outputs, padded to 32
+    int32_t klanes, relu;                                // the mapping (se_klanes); ReLU on the result (a 1x1 conv node's)
+    Requant rq;
+};
+struct SEArgs {
+    const int32_t* x;                                    // the map's int32 form (I32T), pixels n * HW .. of image n
+    int32_t N, HW, C, Cs;                                // images, pixels per image, real / padded channels of the map
+    SELayer l1, l2;
+    int32_t* out32;                                      // fc2's result: I32T, one pixel per image, l2.coutP channels
+    QuantOut q[2];                                       // ... and its int8 forms [N][l2.coutP]
+};
 
 // Transposed convolution (f8_deconv.hip; f8_net_conv_transpose), stride 2 .. 4: [H, W] -> [P, Q] = [(H - 1) s - 2 pad + k + output_padding, ...].  The output
 // pixels of one PHASE (rh, rw) = ((oh + pad) % s, (ow + pad) % s) see the same kernel taps kh = rh + s th, th < Th, at the input rows ih = a - th
@@ -842,6 +863,10 @@ int sumpool_inst(int k, bool wide);                                // f8_sumpool
 const char* sumpool_kernel_name(int inst);
 int sumpool_wide_lg(int k);
 hipError_t launch_sumpool(const SumPoolArgs& a, int inst, hipStream_t s);
+bool se_klanes(int cin, int cout);                                 // f8_se.hip.  The mapping of a layer: true = K over lanes (cout <= cin), false = outputs over lanes
+int se_inst(const SEArgs& a);                                      // 2 * l1.klanes + l2.klanes: se_kernel<K1, K2>
+const char* se_kernel_name(int inst);
+hipError_t launch_se(const SEArgs& a, int inst, hipStream_t s);
 hipError_t launch_input(const InArgs& a, int inst, hipStream_t s);
 const char* output_kernel_name();
 hipError_t launch_output(const OutArgs& a, hipStream_t s);

@@ -82,7 +82,9 @@ struct Tensor {
 //   B_HEAD2         MobileNet-V2 head launch (f8_stem.hip, H2): 3x3 / 2 head conv, depthwise, host = the 1x1
 //   B_DWS           depthwise-separable block (option fuse_dws, f8_dws.hip; R rows per tile): body.0 = the depthwise 3x3, host = the 1x1;
 //                   I7 > 0: the form for a 7 x 7 output map (option fuse_dws7, f8_dws7.hip; I7 images per workgroup), the same block to every pass
-enum BlockKind { B_NONE, B_BOTTLENECK, B_OPENING, B_JOIN, B_P12, B_BASIC, B_BASIC_OPENING, B_BASIC_JOIN, B_IR, B_HEAD2, B_DWS, B_IRK };
+//   B_SE            the squeeze path of an SE branch (option fuse_se, f8_se.hip): body.0 = fc1, host = fc2 (linears or 1x1 convs on [C, 1, 1]); the average
+//                   pool in front of fc1 is linked as the 1x1 conv + pool launch links its pool (Node::se_pool / se_host)
+enum BlockKind { B_NONE, B_BOTTLENECK, B_OPENING, B_JOIN, B_P12, B_BASIC, B_BASIC_OPENING, B_BASIC_JOIN, B_IR, B_HEAD2, B_DWS, B_IRK, B_SE };
 struct Block { BlockKind kind = B_NONE; int b0 = -1, b2 = -1, b4 = -1, sc = -1; bool s2 = false; int R = 0, G = 0, I7 = 0; };
 enum Role { R_NONE, R_B0, R_B2, R_B4, R_SC };
 // The chain launches: bottleneck stage (f8_chain.hip; the 7x7 stage over clusters, f8_cchain.hip), BasicBlocks (f8_bchain.hip), BasicBlocks of a 7x7 x 512
@@ -140,6 +142,7 @@ struct Node {
     Block blk;                         // the fused block this conv hosts (B_NONE: none)
     int sp_pool = -1, sp_conv = -1;      // stem conv <-> max-pool fused into one launch (f8_stem.hip)
     int pool = -1, pool_host = -1;       // 1x1 conv (hosting its residual join or not) <-> the average pool behind it, one launch (f8_pool.hip)
+    int se_pool = -1, se_host = -1;      // fc2 of a B_SE block <-> the average pool IN FRONT of its fc1, summed in the launch (f8_se.hip)
     int chain_into = -1;               // host of a block that runs inside a chain launch: the host of the chain's LAST block
     std::vector<int> chain;            // host of the last block of a chain: the hosts of all its blocks, in order
     ChainKind chain_kind = C_NONE;     // ... and the launch it is
@@ -159,7 +162,7 @@ static f8_conv_geom geom_of(const Node& n) {
     const f8_conv_desc& d = n.cd;
     return f8_conv_geom{d.kernel, d.kernel, d.stride, d.stride, d.pad, d.pad, d.pad, d.pad, n.dil};
 }
-enum StepKind { S_INPUT, S_CONV, S_DW, S_ADD, S_MAXPOOL, S_AVGPOOL, S_REQUANT, S_OUTPUT, S_FUSED, S_STEMPOOL, S_IR, S_P12, S_CHAIN, S_BCHAIN, S_HEAD2, S_IRCHAIN, S_DWS, S_DWS7, S_IRK, S_GCONV, S_CONCAT, S_UPSAMPLE, S_DECONV, S_SUMPOOL, S_CHANMAP, S_MUL, S_HGATE, S_TABLE, S_ARGMAX, S_PIXMAP, S_GCONVW, S_GCONVX };
+enum StepKind { S_INPUT, S_CONV, S_DW, S_ADD, S_MAXPOOL, S_AVGPOOL, S_REQUANT, S_OUTPUT, S_FUSED, S_STEMPOOL, S_IR, S_P12, S_CHAIN, S_BCHAIN, S_HEAD2, S_IRCHAIN, S_DWS, S_DWS7, S_IRK, S_GCONV, S_CONCAT, S_UPSAMPLE, S_DECONV, S_SUMPOOL, S_CHANMAP, S_MUL, S_HGATE, S_TABLE, S_ARGMAX, S_PIXMAP, S_GCONVW, S_GCONVX, S_SE };
 // The kernel of a step whose kind has several, chosen once by the step's emitter (pass 3); bind_step, run_step and f8_net_autotune switch on it.
 //   S_CONV:  conv_igemm (f8_kernels.hip), the LDS-patch 3x3 (f8_conv3x3.hip), conv1x1_wreg (f8_wreg.hip), conv1x1_wstat (f8_wstat.hip),
 //            conv3x3s2_wreg (f8_s2conv.hip), the 1x1 conv + average pool (f8_pool.hip), the classifier fc_dense (f8_fc.hip)
@@ -190,7 +193,7 @@ struct Step {
     double bytes_per_img = 0, bytes_const = 0, ops_per_img = 0;
     double valu_per_img = 0;           // ESSENTIAL vector lane-operations per image (f8_net_launch_valu): what the reference's semantics need once the MFMAs are done
     // the launcher's arguments as far as the plan decides them (bind_step); run_step copies them and adds what the run decides
-    std::variant<std::monostate, ConvArgs, StemPoolArgs, FusedArgs, ChainArgs, BChainArgs, BCChainArgs, IRArgs, IRKArgs, IRChainArgs, DwsArgs, Dws7Args, DwArgs, GConvArgs, GConvWArgs, GConvXArgs, AddArgs, PoolArgs, AvgArgs, OutArgs, ConcatArgs, UpsampleArgs, ArgmaxArgs, DeconvArgs, SumPoolArgs, ChanMapArgs, PixMapArgs, MulArgs, TableArgs, TableMulArgs> args;
+    std::variant<std::monostate, ConvArgs, StemPoolArgs, FusedArgs, ChainArgs, BChainArgs, BCChainArgs, IRArgs, IRKArgs, IRChainArgs, DwsArgs, Dws7Args, DwArgs, GConvArgs, GConvWArgs, GConvXArgs, AddArgs, PoolArgs, AvgArgs, OutArgs, ConcatArgs, UpsampleArgs, ArgmaxArgs, DeconvArgs, SumPoolArgs, ChanMapArgs, PixMapArgs, MulArgs, TableArgs, TableMulArgs, SEArgs> args;
     int inst = 0;                      // the instance the launcher starts (the family's *_inst, f8_internal.h; bind_step)
     // S_CHAIN / S_BCHAIN: geometry, workgroups per image and resident per CU, the 7x7 cluster form (f8_cchain.hip)
     int C = 0, MID = 0, H = 0, W = 0, cin0 = 0, tiles = 0, wg_per_cu = 1; bool cluster = false;
@@ -477,6 +480,7 @@ static const OptKey kOptKeys[] = {
     {"table_i8", "F8_TABLE_I8", &Options::table_i8, 0, 1, true},
     {"fuse_table", "F8_FUSE_TABLE", &Options::fuse_table, 0, 2, true},
     {"fuse_argmax", "F8_FUSE_ARGMAX", &Options::fuse_argmax, 0, 1, true},
+    {"fuse_se", "F8_FUSE_SE", &Options::fuse_se, 0, 2, true},
 };
 static const OptKey* find_opt(const char* key) {
     if (!key) return nullptr;
@@ -1526,6 +1530,30 @@ static void pack_gconvw_weights(f8_net* net, Node& nd) {
     pack_conv_bias(net, nd, tapsum);
 }
 
+// The images of one layer of a B_SE block (f8_se.hip): K = cin padded to 16 bytes, cout padded to 32, zero weights beyond either.  klanes: [coutP][Kp] int8
+// rows (K over lanes); else K-major [Kp / 4][coutP] dwords, byte j of dword (k4, o) = w[o][4 k4 + j] (outputs over lanes).  Bias [coutP]: + 128 sum(w) for an
+// unsigned input, stored biased, as pack_conv_bias (one class: a [C, 1, 1] map has no border).
+static void pack_se_weights(f8_net* net, Node& nd, bool klanes) {
+    const f8_conv_desc& d = nd.cd;
+    nd.coutP = round_up(d.cout, 32);
+    nd.ck = nd.ktot = round_up(d.cin, 16);
+    nd.w_off = round_up_z(net->wblob.size(), 256);
+    net->wblob.resize(nd.w_off + (size_t)nd.coutP * nd.ktot, 0);
+    nd.b_off = round_up_z(net->wblob.size(), 256);
+    net->wblob.resize(nd.b_off + (size_t)nd.coutP * 4, 0);
+    int8_t* const wp = (int8_t*)net->wblob.data() + nd.w_off;
+    int32_t* const bp = (int32_t*)(net->wblob.data() + nd.b_off);
+    for (int o = 0; o < d.cout; ++o) {
+        long long sum = 0;
+        for (int k = 0; k < d.cin; ++k) {
+            const int8_t v = nd.w[(size_t)o * d.cin + k];
+            sum += v;
+            wp[klanes ? (size_t)o * nd.ktot + k : ((size_t)(k >> 2) * nd.coutP + o) * 4 + (k & 3)] = v;
+        }
+        bp[o] = (int32_t)((uint32_t)nd.bias[o] + (d.input_signed ? 0u : (uint32_t)(128ll * sum)));
+    }
+}
+
 static std::string tname(const f8_net* net, int t) {
     const Tensor& T = net->tensors[t];
     if (!T.label.empty()) return T.label;
@@ -2298,6 +2326,44 @@ static void plan_depthwise_separable_7x7(f8_net* net, int max_batch) {
     }
 }
 
+// a fully connected layer of an SE branch: a linear, or the 1x1 conv on a [C, 1, 1] map that ONNX import and torchvision-style blocks arrive with; it
+// requantises its input and is linked to nothing (no join, dual GEMM, pool, fused launch)
+static bool se_fc_node(const f8_net* net, int i) {
+    const Node& n = net->nodes[i];
+    const Tensor& s = net->tensors[n.a];
+    return (n.kind == N_LINEAR || (plain_conv(n, 1, 1, 0) && !n.rect)) && s.H == 1 && s.W == 1 && n.cd.quant_input && n.fused_add < 0 && n.dual < 0 &&
+           n.pool < 0 && n.sp_pool < 0 && !claimed(net, i);
+}
+
+// Option fuse_se.  1: the measured rule (profiles/se_r21.md, batch 128, the SE shapes of MobileNet-V3-Large and EfficientNet-B0): every workgroup of the
+// fused launch streams both weight sets whole, so it is 1.13 - 13 x faster than the three launches on every shape up to 480 / 120 = 115 200
+// multiply-adds an image and slower (0.85 - 0.64 x) from 672 / 168 = 225 792 on — it fuses up to 2^17.  2: every match (what the measurement ran).  0: never.
+static bool fuse_se_rule(int opt, const Node& f1, const Node& f2) {
+    return opt == 2 || (opt == 1 && (int64_t)f1.cd.cin * f1.cd.cout + (int64_t)f2.cd.cin * f2.cd.cout <= (int64_t(1) << 17));
+}
+
+// pass 1l
+static void plan_squeeze_excite(f8_net* net) {
+    auto& T = net->tensors;
+    auto& ND = net->nodes;
+    const int nn = (int)ND.size();
+    // ---- 1l. the squeeze path of an SE branch (option fuse_se): avgpool_sum -> fc1 -> fc2, the pooled vector and fc1's result read by nobody else and no
+    //          network output  ->  ONE launch hosted by fc2 (f8_se.hip), one workgroup per image; neither intermediate exists in any form.  fc2's readers
+    //          are whatever they are: the launch writes its int32 and / or int8 forms as a conv launch does.  The limits are the kernel's LDS arrays.
+    //          The last of the passes 1x: whatever an earlier one claimed (the 1x1 conv + average pool of 1i among them) stays what it is.
+    for (int i = 0; net->opt.fuse_se && i < nn; ++i) {
+        if (!se_fc_node(net, i) || is_output(net, ND[i].out)) continue;
+        const int f1 = private_producer(net, ND[i].a);
+        if (f1 < 0 || !se_fc_node(net, f1)) continue;
+        const int pi = private_producer(net, ND[f1].a);
+        if (pi < 0 || ND[pi].kind != N_AVGPOOL || ND[pi].pool_host >= 0) continue;
+        if (T[ND[pi].a].C > kSeMaxC || ND[f1].cd.cout > kSeMaxMid || ND[i].cd.cout > kSeMaxC) continue;
+        if (!fuse_se_rule(net->opt.fuse_se, ND[f1], ND[i])) continue;                  // wide layers keep their three launches under the rule
+        set_block(net, i, Block{B_SE, f1, -1, i, -1});
+        ND[i].se_pool = pi; ND[pi].se_host = i;
+    }
+}
+
 // pass 2
 // The mode rule of the gathers — concat, nearest upsample, slice / shuffle, depth_to_space / space_to_depth.  Bytes mode: the result exists in one or two int8 forms
 // and nothing else (no int32 reader, no network output: int8_forms_only); the sources are then asked for the result's formats and the launch moves
@@ -2388,6 +2454,7 @@ static void plan_tensor_forms(f8_net* net, int max_batch) {
                     case B_P12: in_launch = role == R_B2; break;
                     case B_HEAD2: in_launch = role != R_B0; break;
                     case B_DWS: in_launch = role == R_B4; break;      // (the depthwise conv reads the block input from HBM)
+                    case B_SE: break;                            // fc1 reads the pooled sum, fc2 fc1's result: both in LDS (the pool, an earlier node, asks the map for its int32 form)
                     case B_BASIC_JOIN:                           // (cluster launch: body.0's int8 output in HBM)
                         if (role == R_B2) add_form(s, FORM_I8, n, nd.cd.input_signed ? 1 : 0);
                         [[fallthrough]];
@@ -2872,6 +2939,28 @@ static int emit_dws(f8_net* net, int i, Step& st, std::vector<int>* extra) {
     return F8_OK;
 }
 
+// The squeeze path of an SE branch (B_SE, pass 1l): node i is fc2; the launch reads the int32 form of the map the pool sums and writes fc2's forms
+static int emit_se(f8_net* net, int i, Step& st, std::vector<int>* extra) {
+    auto& T = net->tensors; auto& ND = net->nodes;
+    Node& f2 = ND[i]; Node& f1 = ND[f2.blk.b0];
+    const Node& p = ND[f2.se_pool];
+    const Tensor& x = T[p.a];
+    st.kind = S_SE;
+    st.src_t = p.a; st.src_f = find_form(x, FORM_I32, 0, 0);
+    st.relu0 = f2.cd.relu;
+    pack_se_weights(net, f1, se_klanes(f1.cd.cin, f1.cd.cout));
+    pack_se_weights(net, f2, se_klanes(f2.cd.cin, f2.cd.cout));
+    select_outputs_or_i32(net, f2.out, &st.out, extra);
+    const Tensor& o = T[f2.out];
+    const double px = (double)x.H * x.W;
+    st.bytes_per_img = px * x.Cs * 4 + out_bytes(st, o, 1.0);                  // the map once at 4 B / value, the output forms
+    st.bytes_const = weight_bytes(net, f1) + weight_bytes(net, f2);            // both weight sets
+    st.ops_per_img = 2.0 * ((double)f1.cd.cin * f1.cd.cout + (double)f2.cd.cin * f2.cd.cout);
+    st.valu_per_img = px * x.C + 3.0 * (f1.cd.cin + f2.cd.cin) + 3.0 * o.Cs * out_forms8(st);      // one add per map value, the two requantisations, the output forms
+    st.name = "avgpool+fc+fc:" + tname(net, f2.out);
+    return F8_OK;
+}
+
 // The kernel of a plain conv step (not depthwise), once its inputs and outputs are known; the first that applies, in this order.
 static Variant conv_variant(const f8_net* net, const Node& nd, const Step& st, int max_batch) {
     const Options& opt = net->opt;
@@ -3060,6 +3149,7 @@ static int emit_conv_family(f8_net* net, int i, int max_batch, Step& st, std::ve
         case B_P12: return emit_p12(net, i, st, extra);
         case B_IR: case B_IRK: return emit_ir(net, i, st, extra);
         case B_DWS: return emit_dws(net, i, st, extra);
+        case B_SE: return emit_se(net, i, st, extra);
         default:
             if (nd.grouped && gconv_kernel_applies(net->opt, nd)) return emit_gconv(net, i, st, extra, S_GCONV);
             if (nd.grouped && gconvw_kernel_applies(net->opt, nd)) return emit_gconv(net, i, st, extra, S_GCONVW);
@@ -3385,6 +3475,8 @@ static int emit_steps(f8_net* net, int max_batch) {
         if (nd.kind == N_CONV && nd.chain_into >= 0 && nd.chain_into != i) continue;      // runs inside the chain launch of a later block
         if (nd.kind == N_MAXPOOL && nd.sp_conv >= 0) continue;
         if (nd.kind == N_AVGPOOL && nd.pool_host >= 0) continue;     // runs in its conv's launch
+        if (nd.kind == N_AVGPOOL && nd.se_host >= 0) continue;       // summed in the SE launch hosted by fc2 (f8_se.hip)
+        if (nd.kind == N_LINEAR && nd.absorbed_by >= 0) continue;    // fc1 of a B_SE block (the only block a linear is a member of)
         if (nd.kind == N_CONCAT && nd.cat_into >= 0) continue;       // the shuffle behind it reads its operands
         if (nd.kind == N_HGATE && nd.gate_into >= 0) continue;       // the mul behind it applies it
         if (nd.kind == N_TABLE && nd.tab_into >= 0) continue;        // the mul behind it looks it up
@@ -4123,6 +4215,20 @@ static int bind_step(f8_net* net, Step& st) {
             snprintf(kb, sizeof kb, "%s", maxpool_kernel_name(st.inst = maxpool_inst(a)));
             out_formats(a.q); st.args = a; break;
         }
+        case S_SE: {
+            const Tensor& sT = T[st.src_t];
+            SEArgs a{};
+            a.HW = sT.H * sT.W; a.C = sT.C; a.Cs = sT.Cs;
+            auto layer = [&](SELayer& L, const Node& c) {
+                L.w = W8(c.w_off); L.bias = B32(c.b_off);
+                L.K = c.cd.cin; L.Kp = c.ktot; L.cout = c.cd.cout; L.coutP = c.coutP;
+                L.klanes = se_klanes(c.cd.cin, c.cd.cout); L.relu = c.cd.relu;
+                L.rq = fmt(c);
+            };
+            layer(a.l1, ND[nd.blk.b0]); layer(a.l2, nd);
+            snprintf(kb, sizeof kb, "%s", se_kernel_name(st.inst = se_inst(a)));
+            out_formats(a.q); st.args = a; break;
+        }
         case S_AVGPOOL: {
             const Tensor& sT = T[st.src_t];
             AvgArgs a{};
@@ -4176,6 +4282,7 @@ int f8_net_finalize(f8_net* net, int max_batch) {
     plan_last_conv_and_pool(net);                   // 1i: the last 1x1 conv + the average pool
     plan_depthwise_separable(net, max_batch);       // 1j: MobileNet-V1 depthwise-separable blocks in one launch (option fuse_dws)
     plan_depthwise_separable_7x7(net, max_batch);   // 1k: ... those on 7 x 7 output maps, and the average pool behind the last (option fuse_dws7)
+    plan_squeeze_excite(net);                       // 1l: avgpool_sum -> fc -> fc of an SE branch in one launch (option fuse_se)
     if (net->plan_bug >= 0) return fail(F8_ERR_STATE, "f8_net_finalize: planner bug: two fused launches claim conv node %d", net->plan_bug);
     plan_tensor_forms(net, max_batch);              // 2:  which forms of each tensor exist in HBM
     int rc = emit_steps(net, max_batch);            // 3:  the launches, packed weights, algorithmic bytes / ops
@@ -4524,6 +4631,7 @@ static int run_step(const f8_net* net, const RunIO& io, const Step& st, int n0, 
         case S_SUMPOOL: { SumPoolArgs a = std::get<SumPoolArgs>(st.args); src_io(a, &a.out32); e = launch_sumpool(a, st.inst, s); break; }
         case S_MAXPOOL: { PoolArgs a = std::get<PoolArgs>(st.args); src_io(a, &a.out32); e = launch_maxpool(a, st.inst, s); break; }
         case S_AVGPOOL: { AvgArgs a = std::get<AvgArgs>(st.args); src_io(a, &a.out32); e = launch_avgpool(a, s); break; }
+        case S_SE: { SEArgs a = std::get<SEArgs>(st.args); src_io(a, &a.out32); e = launch_se(a, st.inst, s); break; }
         case S_ADD: case S_REQUANT: {
             const Tensor& sT = T[st.src_t];
             AddArgs a = std::get<AddArgs>(st.args);

@@ -586,7 +586,16 @@ int f8_net_check(f8_net* net);
  *               and the mul launch.  Same values in every case, bit for bit),
  *               fuse_argmax (default 1: an f8_net_output_argmax on the result of an f8_net_upsample that nothing else reads is ONE launch that interpolates
  *               and reduces in registers, tokens upsample_bilinear+argmax_*: / upsample_nearest+argmax_*:, the upsampled tensor in no form; 0: the
- *               upsample launch and an argmax_*: launch.  Same class map either way, bit for bit)
+ *               upsample launch and an argmax_*: launch.  Same class map either way, bit for bit),
+ *               fuse_se (0 .. 2, default 0, environment F8_FUSE_SE: 1 or 2 = the squeeze path of a squeeze-and-excitation branch is ONE launch, plan token
+ *               avgpool+fc+fc:, kernel f8::se_kernel<..> (one workgroup per image).  The match: an f8_net_avgpool_sum (or the global window of
+ *               f8_net_avgpool_window) on [C, H, W], C <= 4096, that is no output and read by fc1 alone; fc1 an f8_net_linear — or a 1x1 / stride 1 /
+ *               pad 0 / groups 1 f8_net_conv on [C, 1, 1], its ReLU honoured — with quant_input = 1, at most 1024 outputs, no output, read by fc2
+ *               alone; fc2 the same kind of node with at most 4096 outputs and no output mark, whatever reads it: the launch writes its int32 form
+ *               and / or up to two int8 forms, as a conv launch does.  The pooled vector and fc1's result exist in no form.  Whatever does not match
+ *               keeps its three launches (avgpool_sum: and two conv launches).  Same values either way, bit for bit.  Measured, profiles/se_r21.md: faster on ten of
+ *               thirteen SE shapes of MobileNet-V3-Large / EfficientNet-B0, slower where the two layers hold 250 KB of weights and more.  Hence 1 = the measured rule:
+ *               a match whose two layers together exceed 2^17 multiply-adds an image (C mid + mid C) keeps its three launches; 2 = every match)
  *   scheduling: chunk56 / chunk28 / chunk14 (images per chunk of the fused blocks; -1 = derived from chunk_budget_mb, 0 = whole
  *               batch), chunk_budget_mb (memory-side cache a chunk's int32 stream may occupy), chunk_ds, chunk_opener,
  *               split_streams, graph, stagger, stagger_pipelined, stem_wpc, stem_grid_div (row-walking head on 1 / n of the CUs; 0 = by output form), wstat_grid_div (0 .. 32, default 0, environment F8_WSTAT_GRID_DIV: f8::conv1x1_wstat_kernel sizes its pixel groups for 1 / n of the CUs, at least one — tests walk long tile rings on small maps; 0 = all of them; the plan and the values do not move), check_device, check_input_range, pipeline_depth (2..4 runs in flight),
