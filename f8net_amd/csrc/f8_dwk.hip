@@ -1,13 +1,15 @@
-// f8_dwk.hip — general depthwise convolution (gfx950): square kernels 3 / 5 / 7, stride 1 / 2, any pad up to K / 2, and the 3x3 at dilation d > 1
-// (pad up to d) — everything depthwise that is not the undilated 3x3 / pad 1 of f8_kernels.hip / f8_dwmma.hip, which keeps its own kernels.  VALU; a
-// launch of its own (S_DW, f8_net.cpp).
+// f8_dwk.hip — general depthwise convolution (gfx950): square kernels 3 / 5 / 7 (and 8 .. 31 under option dw_large), stride 1 / 2, any pad up to K / 2, and the
+// 3x3 at dilation d > 1 (pad up to d) — everything depthwise that is not the undilated 3x3 / pad 1 of f8_kernels.hip / f8_dwmma.hip, which keeps its own
+// kernels.  VALU, but for kernels 8 .. 31 at stride 1, which have the MFMA kernel of f8_dwlk.hip (instances 4 / 5 of the launcher below); a launch of its own
+// (S_DW, f8_net.cpp).
 //
 // All kernels work in the stored domain of the 3x3 kernels: NHWC int8 with channel stride Cs (a multiple of 32); unsigned tensors are stored
 // biased (x ^ 0x80); wrapping int32 accumulation; optional ReLU floor; up to two int8 forms (QuantOut) and / or the tiled int32 form.
 //
 //   dwconvk_kernel<SIGNED_IN>     K, stride, pad, dilation at run time; one thread = one output pixel x 4 channels; bytes extracted and multiplied one by
 //                                 one (unsigned inputs as unsigned bytes: out-of-image taps are skipped, plain bias).  Writes any form.  The
-//                                 correctness anchor, and what runs when a launch writes the int32 form or option dwk_dot4 is 0.
+//                                 correctness anchor, and what runs when a launch writes the int32 form or option dwk_dot4 is 0; kernels 8 .. 31 at stride 2,
+//                                 with an int32 form, under dw_large = 2 or where dwlk_rule keeps them off dwlk_kernel.
 //   dwconvk_dot4_kernel<K, S>     int8 forms only, on v_dot4_i32_i8.  One thread = 4 channels (one dword per tap) x DWK_PIX adjacent output pixels
 //                                 of one row.  A dot4 reduces over four ROWS of one input column: the thread walks the (DWK_PIX - 1) * S + K input
 //                                 columns of its pixels once, loads the K dwords of a column, byte-transposes rows 4g .. 4g + 3 into one dword per
@@ -330,13 +332,15 @@ __global__ void __launch_bounds__(256) dwstrip_dot4_kernel(const DwArgs a) {
 
 // General depthwise: the v_dot4 kernels for int8-only launches (Options::dwk_dot4), else the generic one.  A dilated conv (3x3 only) has its dot4
 // kernel — instance 2 — at stride 1, exactly where dwconvk_dot4_kernel<3, 1> runs the undilated one.
-int dwk_inst(const DwArgs& a, bool out32, bool dot4) {
+int dwk_inst(const DwArgs& a, bool out32, int nq, bool dot4, bool large) {
+    if (a.kw == a.k && a.k >= 8) return large && !out32 && nq >= 1 && a.stride == 1 && a.dil == 1 && dwlk_rule(a, nq) ? 3 + nq : 0;      // f8_dwlk.hip: 4 / 5
     if (a.kw != a.k) return dot4 && !out32 && a.stride == 1 && a.dil == 1 && (a.k == 1 || a.kw == 1) ? 3 : 0;      // a strip: instance 3, dwstrip_dot4_kernel
     if (a.dil > 1) return dot4 && !out32 && a.k == 3 && a.stride == 1 ? 2 : 0;
     return dot4 && !out32 && (a.k == 3 || a.k == 5 || a.k == 7) && (a.stride == 1 || a.stride == 2) ? 1 : 0;
 }
 
 int dwk_kernel_name(char* buf, size_t cap, const DwArgs& a, int inst) {
+    if (inst >= 4) return dwlk_kernel_name(buf, cap, a, inst - 3);
     if (inst == 2) return snprintf(buf, cap, "f8::dwconv3x3_dil_dot4_kernel");
     if (inst == 3) return snprintf(buf, cap, "f8::dwstrip_dot4_kernel<%d>", (std::max(a.k, a.kw) + 6) / 4);
     if (inst) return snprintf(buf, cap, "f8::dwconvk_dot4_kernel<%d, %d>", a.k, a.stride);
@@ -344,6 +348,7 @@ int dwk_kernel_name(char* buf, size_t cap, const DwArgs& a, int inst) {
 }
 
 hipError_t launch_dwk(const DwArgs& a, int inst, hipStream_t s) {
+    if (inst >= 4) return launch_dwlk(a, inst - 3, s);
     if (a.kw != a.k) {                                    // a strip 1 x k / k x 1: pads below k on its axis, none on the other; instance 3 or the generic kernel
         const int k = std::max(a.k, a.kw);
         if (std::min(a.k, a.kw) != 1 || k < 3 || k > 31 || a.dil != 1 || a.pad < 0 || a.pad >= a.k || a.pad_w < 0 || a.pad_w >= a.kw || (inst != 0 && inst != 3))

@@ -73,6 +73,8 @@ struct Options {
                                  // float converter (v_cvt_f32_i32, v_mul_f32 by 2^-n, v_cvt_pk_u8_f32: exact where planned, f8_device.h)
     int grouped = 0;             // grouped convs (1 < groups < cin): 0 = refused by f8_net_conv; 1 = accepted, on gconv3x3_kernel (f8_gconv.hip) where it applies and as the
                                  // dense expansion (the plain conv kernels over block-diagonal weights) elsewhere; 2 = accepted, always the dense expansion
+    int dw_large = 0;            // depthwise convs of kernel 8 .. 31 (stride 1 / 2, pad 0 .. kernel / 2): 0 = refused by f8_net_conv; 1 = accepted, on dwlk_kernel (f8_dwlk.hip) where
+                                 // dwlk_rule says so (stride 1, int8 forms only) and on dwconvk_kernel elsewhere; 2 = accepted, always dwconvk_kernel
     int gconv_wide = 0;          // with grouped = 1: 1 = grouped 3x3 convs of group width cg in {24, 40, 48, 56, 64} (cin == cout, stride 1 / 2, pad 0 / 1) on gconvw3x3_kernel
                                  // (f8_gconvw.hip, gconvw3x3s<S>:); 0 (default, until it is measured): the dense expansion, as before the kernel existed
     int gconv_xwide = 0;         // with grouped = 1: 1 = grouped 3x3 convs of group width cg = 72 .. 256, a multiple of 8 (cin == cout, groups >= 2, stride 1 / 2, pad 0 / 1) on
@@ -168,13 +170,15 @@ struct ConvArgs {
 };
 
 // Depthwise K x K (groups == C), NHWC int8 in, VALU.  3x3 / pad 1: the launchers of f8_kernels.hip / f8_dwmma.hip, which never read `k`;
-// every other accepted geometry (k 3 / 5 / 7, pad <= k / 2; k 3 at dilation dil > 1, pad <= dil: "general depthwise"): f8_dwk.hip, with the images of pack_dwk_weights.
+// every other accepted geometry (k 3 / 5 / 7 and — option dw_large — 8 .. 31, pad <= k / 2; k 3 at dilation dil > 1, pad <= dil: "general depthwise"): f8_dwk.hip and
+// f8_dwlk.hip, with the images of pack_dwk_weights.
 struct DwArgs {
     const int8_t* x; const int8_t* w;      // w: [k * k][Cs] tap-major
     const int32_t* bias;                   // [Cs]
     const int8_t* w4; const int32_t* bias4; // dot4 kernels, bias + 128*sum(w) for unsigned inputs.  3x3 / pad 1: [Cs/4][9] tap-transposed dwords;
                                            // general: [Cs/4][k columns][ceil(k / 4) row groups][4 channels] dwords, byte j = row 4g + j (0 beyond k)
                                            // a strip (kw != k): [Cs/4][4 phases][ceil((k + 3) / 4)][4 channels] dwords, the taps shifted by `phase` bytes
+                                           // k >= 8: DwlkArgs::w
     int32_t N, H, W, P, Q, Cs, stride, pad;
     int32_t in_signed;
     int32_t relu0;
@@ -188,6 +192,21 @@ struct DwArgs {
     int32_t dil;                           // ... and the dilation (1: none; > 1 only with k == 3)
     int32_t kw, pad_w;                     // ... and the columns' kernel size and leading pad: k and pad are the rows' (kernel height, top pad).  A square conv:
                                            // kw = k, pad_w = pad; a strip (f8_net_conv_rect): one of k / kw is 1.  The 3x3 launchers never read them.
+};
+
+// Large depthwise K x K, K = 8 .. 31, stride 1, on the Toeplitz MFMA kernel (f8_dwlk.hip): made from a DwArgs by its launcher (dwlk_geom), never stored in a plan.
+constexpr int DWLK_ROWB = 96;              // bytes of one byte-shifted copy of a zero-extended weight row: Z[0 .. 94] = 31 zeros, the K taps, zeros (pack_dwk_weights)
+struct DwlkArgs {
+    const int8_t* x; const int8_t* w;      // w: [Cs][K rows][4 copies][DWLK_ROWB]: byte u of copy ph = Z[u + ph]
+    const int32_t* bias;                   // [Cs], + 128 * sum(w) for unsigned inputs
+    int32_t N, H, W, P, Q, Cs, k, pad;
+    int32_t in_signed, relu0;
+    QuantOut q[2];
+    int32_t CG, TC;                        // a workgroup's channels (32 / 16) and column tiles of 32 outputs (1 / 2)
+    int32_t RS, G, IR;                     // output rows per image slot (32 / 16), image slots stacked in the 32 rows of a tile, input rows per slot RS + K - 1
+    int32_t pitch, opitch;                 // bytes of a staged input row (32 (TC + 1) + 16) and of an output-tile row (32 TC CG + 16)
+    int32_t lds_in, lds_out;               // bytes of the staged input tile and of ONE form's output tile
+    int32_t tiles_r, tiles_c;              // row tiles (1 when G > 1) and column tiles of 32 TC per image
 };
 
 // Grouped 3x3 (f8_gconv.hip): cin == cout, cg = C / groups divides 32, stride 1 / 2, pad 0 / 1.  The kernel sees 32-channel slices only.
@@ -804,10 +823,15 @@ int dwconv_inst(const DwArgs& a, bool out32, int nq, bool mma, bool dot4, int ma
 int dwconv_kernel_name(char* buf, size_t cap, const DwArgs& a, int inst);
 hipError_t launch_dwconv(const DwArgs& a, int inst, hipStream_t s);
 // general depthwise (f8_dwk.hip): every accepted depthwise geometry but the undilated 3x3 / pad 1.  inst 1: dwconvk_dot4_kernel<k, stride> (int8 outputs only,
-// Options::dwk_dot4), 2: dwconv3x3_dil_dot4_kernel (the same, 3x3 at dilation > 1, stride 1), 0: dwconvk_kernel<in_signed>
-int dwk_inst(const DwArgs& a, bool out32, bool dot4);
+// Options::dwk_dot4), 2: dwconv3x3_dil_dot4_kernel (the same, 3x3 at dilation > 1, stride 1), 3: dwstrip_dot4_kernel (strips), 4 / 5: dwlk_kernel (f8_dwlk.hip: k 8 .. 31 at
+// stride 1, nq = 1 / 2 int8 outputs and no int32 one, Options::dw_large == 1 — `large`), 0: dwconvk_kernel<in_signed>
+int dwk_inst(const DwArgs& a, bool out32, int nq, bool dot4, bool large);
 int dwk_kernel_name(char* buf, size_t cap, const DwArgs& a, int inst);
 hipError_t launch_dwk(const DwArgs& a, int inst, hipStream_t s);
+bool dwlk_geom(const DwArgs& a, int nq, DwlkArgs* g);           // f8_dwlk.hip: the tile of a large depthwise launch that writes nq int8 forms; false: none fits
+bool dwlk_rule(const DwArgs& a, int nq);                        // ... and where option dw_large = 1 plans it
+int dwlk_kernel_name(char* buf, size_t cap, const DwArgs& a, int nq);
+hipError_t launch_dwlk(const DwArgs& a, int nq, hipStream_t s);
 // grouped 3x3 on the slice-diagonal MFMA kernel (f8_gconv.hip): the tile of a P x Q output map (R rows x TW columns, or G whole images)
 void gconv_tile(int P, int Q, int stride, int* R, int* TW, int* G);
 int gconv_kernel_name(char* buf, size_t cap, const GConvArgs& a);

@@ -468,6 +468,7 @@ static const OptKey kOptKeys[] = {
     {"whole_batch_launches", "F8_WHOLE_BATCH_LAUNCHES", &Options::whole_batch_launches, 0, 1, true},
     {"tap_tiled", "F8_TAP_TILED", &Options::tap_tiled, 0, 1, true},
     {"grouped", "F8_GROUPED", &Options::grouped, 0, 2, true},
+    {"dw_large", "F8_DW_LARGE", &Options::dw_large, 0, 2, true},
     {"gconv_wide", "F8_GCONV_WIDE", &Options::gconv_wide, 0, 1, true},
     {"gconv_xwide", "F8_GCONV_XWIDE", &Options::gconv_xwide, 0, 1, true},
     {"concat_i8", "F8_CONCAT_I8", &Options::concat_i8, 0, 1, true},
@@ -674,9 +675,11 @@ static int add_conv_node(f8_net* net, int src, const f8_conv_desc& d, int dil, c
         if (d.cin % d.groups || d.cout % d.groups) return fail(F8_ERR_INVALID, "%s: groups %d must divide cin %d and cout %d", who, d.groups, d.cin, d.cout);
     } else if (!(d.groups == 1 || (d.groups == d.cin && d.cout == d.cin)))
         return fail(F8_ERR_UNSUPPORTED, "%s: groups must be 1 or cin (depthwise)", who);
-    if (d.groups != 1 && !grouped && dil == 1 && !((d.kernel == 3 || d.kernel == 5 || d.kernel == 7) && d.stride <= 2 && d.pad <= d.kernel / 2))
-        return fail(F8_ERR_UNSUPPORTED, "%s: depthwise is built for kernel 3, 5 or 7, stride 1 or 2, pad 0 .. kernel / 2 (got kernel %d, stride %d, pad %d)",
-                    who, d.kernel, d.stride, d.pad);
+    // large depthwise kernels (8 .. 31) are opt-in at the builder too (option dw_large): dwlk_kernel (f8_dwlk.hip) or the generic kernel of f8_dwk.hip
+    const bool dw_k = d.kernel == 3 || d.kernel == 5 || d.kernel == 7 || (net->opt.dw_large >= 1 && d.kernel >= 8 && d.kernel <= 31);
+    if (d.groups != 1 && !grouped && dil == 1 && !(dw_k && d.stride <= 2 && d.pad <= d.kernel / 2))
+        return fail(F8_ERR_UNSUPPORTED, "%s: depthwise is built for kernel 3, 5 or 7%s, stride 1 or 2, pad 0 .. kernel / 2 (got kernel %d, stride %d, pad %d)",
+                    who, net->opt.dw_large >= 1 ? " and (option dw_large) 8 .. 31" : "", d.kernel, d.stride, d.pad);
     if (d.groups != 1 && !grouped && dil > 1 && !(d.kernel == 3 && d.stride <= 2 && d.pad <= dil))
         return fail(F8_ERR_UNSUPPORTED, "%s: dilated depthwise is built for kernel 3, stride 1 or 2, pad 0 .. dilation (got kernel %d, stride %d, pad %d, dilation %d)",
                     who, d.kernel, d.stride, d.pad, dil);
@@ -1426,7 +1429,7 @@ static void pack_dw_weights(f8_net* net, Node& nd) {
     }
 }
 
-// "General depthwise": every accepted depthwise conv that is not 3x3 / pad 1 (kernel 3 / 5 / 7, stride 1 / 2, pad 0 .. kernel / 2; add_conv_node).  One pass
+// "General depthwise": every accepted depthwise conv that is not 3x3 / pad 1 (kernel 3 / 5 / 7 and, option dw_large, 8 .. 31, stride 1 / 2, pad 0 .. kernel / 2; add_conv_node).  One pass
 // of the planner fuses one — 1e3, option fuse_irk: kernel 5 / 7 with pad kernel / 2 inside an inverted residual —; every other matcher asks for kernel 3
 // and pad 1, so anywhere else it is a launch of its own on the kernels of f8_dwk.hip.
 static bool dw_general(const Node& n) { const f8_conv_desc& d = n.cd; return d.groups != 1 && d.groups == d.cin && !(d.kernel == 3 && d.pad == 1 && n.dil == 1); }
@@ -1444,7 +1447,11 @@ static void pack_dwk_weights(f8_net* net, Node& nd) {
     // a strip (f8_net_conv_rect: 1 x K or K x 1): image (1) is [KH * KW][Cs]; image (2) is dwstrip_dot4_kernel's — [Cs / 4][4 phases][NW = ceil((K + 3) / 4)]
     // [4 channels] dwords, byte b of dword (quad, ph, m, e) = tap 4 m + b - ph of channel 4 quad + e, 0 outside 0 .. K - 1: the K taps shifted by ph bytes
     const int NW = (K + 3 + 3) / 4;
-    const size_t w4_bytes = nd.rect ? (size_t)(src.Cs / 4) * 4 * NW * 16 : (size_t)(src.Cs / 4) * K * G * 16;
+    // a large square kernel (8 .. 31, option dw_large): image (2) is dwlk_kernel's (f8_dwlk.hip) — [Cs][K rows][4 copies][DWLK_ROWB] bytes: byte u of copy ph of
+    // (channel, row r) = Z[u + ph], Z the zero-extended weight row with Z[31 + s] = w[r][s].  A lane's 16 consecutive bytes of Z from any t0 on are then four
+    // ALIGNED dwords of copy t0 & 3 (the strips' byte-shifted copies, a whole band long).
+    const bool large = !nd.rect && K >= 8;
+    const size_t w4_bytes = nd.rect ? (size_t)(src.Cs / 4) * 4 * NW * 16 : large ? (size_t)src.Cs * K * 4 * DWLK_ROWB : (size_t)(src.Cs / 4) * K * G * 16;
     nd.coutP = src.Cs; nd.ck = 0; nd.ktot = 0;
     nd.w_off = round_up_z(net->wblob.size(), 256);
     nd.b_off = round_up_z(nd.w_off + (size_t)KH * KW * src.Cs, 256);
@@ -1462,6 +1469,11 @@ static void pack_dwk_weights(f8_net* net, Node& nd) {
                 const int8_t v = nd.w[((size_t)c * KH + r) * KW + s];
                 wp[(size_t)(r * KW + s) * src.Cs + c] = v;
                 sum += v;
+                if (large) {
+                    for (int ph = 0; ph < 4; ++ph)
+                        if (31 + s - ph >= 0) w4[(((size_t)c * K + r) * 4 + ph) * DWLK_ROWB + 31 + s - ph] = v;
+                    continue;
+                }
                 if (!nd.rect) { w4[((((size_t)(c / 4) * K + s) * G + r / 4) * 4 + c % 4) * 4 + r % 4] = v; continue; }
                 const int t = r + s;                            // the tap along the strip (one of r, s is 0)
                 for (int ph = 0; ph < 4; ++ph)
@@ -4028,7 +4040,7 @@ static int bind_step(f8_net* net, Step& st) {
             a.k = g.kh; a.kw = g.kw; a.dil = nd.dil;
             out_formats(a.q);
             if (dw_general(nd)) {                                 // f8_dwk.hip: integer requantisation (requant1) whatever requant_float says
-                st.inst = dwk_inst(a, out32, opt.dwk_dot4);
+                st.inst = dwk_inst(a, out32, nq, opt.dwk_dot4, opt.dw_large == 1);
                 dwk_kernel_name(kb, sizeof kb, a, st.inst);
             } else {
                 st.inst = dwconv_inst(a, out32, nq, opt.dw_mma, opt.dw_dot4, net->max_batch);     // (the MMA kernel's index bound at the largest launch)

@@ -98,8 +98,10 @@ typedef struct f8_conv_desc {
     int32_t cin, cout;
     int32_t kernel;        /* square kernels: 1, 3, 7 in the reference nets (rectangular ones, per-axis strides and pads: f8_net_conv_rect) */
     int32_t stride, pad;
-    int32_t groups;        /* 1 or cin (depthwise, cout == cin) — fix_quant_ops.py:373-390.  Depthwise: kernel 3, 5 or 7,
-                              stride 1 or 2, 0 <= pad <= kernel / 2; anything else depthwise is F8_ERR_UNSUPPORTED.
+    int32_t groups;        /* 1 or cin (depthwise, cout == cin) — fix_quant_ops.py:373-390.  Depthwise: kernel 3, 5 or 7 — and
+                              8 .. 31 on a handle whose option `dw_large` is 1 or 2, set BEFORE this call (1: f8::dwlk_kernel where
+                              it applies, 2: always f8::dwconvk_kernel; the kernel may exceed the unpadded map) —, stride 1 or 2,
+                              0 <= pad <= kernel / 2; anything else depthwise is F8_ERR_UNSUPPORTED.
                               1 < groups < cin (grouped, the int nn.Conv2d of fix_quant_ops.py:680-714): F8_ERR_UNSUPPORTED unless the
                               handle's option `grouped` is 1 or 2, set BEFORE this call; then any geometry a plain conv takes, and
                               groups must divide cin and cout (F8_ERR_INVALID) */
@@ -595,7 +597,12 @@ int f8_net_check(f8_net* net);
  *               and / or up to two int8 forms, as a conv launch does.  The pooled vector and fc1's result exist in no form.  Whatever does not match
  *               keeps its three launches (avgpool_sum: and two conv launches).  Same values either way, bit for bit.  Measured, profiles/se_r21.md: faster on ten of
  *               thirteen SE shapes of MobileNet-V3-Large / EfficientNet-B0, slower where the two layers hold 250 KB of weights and more.  Hence 1 = the measured rule:
- *               a match whose two layers together exceed 2^17 multiply-adds an image (C mid + mid C) keeps its three launches; 2 = every match)
+ *               a match whose two layers together exceed 2^17 multiply-adds an image (C mid + mid C) keeps its three launches; 2 = every match,
+ *               dw_large (0 .. 2, default 0, environment F8_DW_LARGE; read by f8_net_conv, so set it BEFORE the conv is added: 0 = a depthwise conv of kernel
+ *               8 .. 31 is F8_ERR_UNSUPPORTED, as every other depthwise kernel but 3, 5 and 7; 1 = accepted (stride 1 or 2, 0 <= pad <= kernel / 2, dilation 1),
+ *               plan token dwconv{K}x{K}s{S}:, on f8::dwlk_kernel<TC> (the Toeplitz MFMA kernel, f8_dwlk.hip) at stride 1 with int8 forms only and an output
+ *               map of more than 8 rows and columns — the measured rule, profiles/dwlk_r22.md — and on f8::dwconvk_kernel elsewhere; 2 = accepted, always
+ *               f8::dwconvk_kernel.  Same values either way, bit for bit)
  *   scheduling: chunk56 / chunk28 / chunk14 (images per chunk of the fused blocks; -1 = derived from chunk_budget_mb, 0 = whole
  *               batch), chunk_budget_mb (memory-side cache a chunk's int32 stream may occupy), chunk_ds, chunk_opener,
  *               split_streams, graph, stagger, stagger_pipelined, stem_wpc, stem_grid_div (row-walking head on 1 / n of the CUs; 0 = by output form), wstat_grid_div (0 .. 32, default 0, environment F8_WSTAT_GRID_DIV: f8::conv1x1_wstat_kernel sizes its pixel groups for 1 / n of the CUs, at least one — tests walk long tile rings on small maps; 0 = all of them; the plan and the values do not move), check_device, check_input_range, pipeline_depth (2..4 runs in flight),
