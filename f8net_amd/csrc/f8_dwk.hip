@@ -1,6 +1,6 @@
 // f8_dwk.hip — general depthwise convolution (gfx950): square kernels 3 / 5 / 7 (and 8 .. 31 under option dw_large), stride 1 / 2, any pad up to K / 2, and the
-// 3x3 at dilation d > 1 (pad up to d) — everything depthwise that is not the undilated 3x3 / pad 1 of f8_kernels.hip / f8_dwmma.hip, which keeps its own
-// kernels.  VALU, but for kernels 8 .. 31 at stride 1, which have the MFMA kernel of f8_dwlk.hip (instances 4 / 5 of the launcher below); a launch of its own
+// 3x3 at dilation d > 1 (pad up to d; option dw_dilated: 5x5 / 7x7 too, pad up to d * (K / 2)) — everything depthwise that is not the undilated 3x3 / pad 1
+// of f8_kernels.hip / f8_dwmma.hip, which keeps its own kernels.  VALU, but for kernels 8 .. 31 at stride 1, which have the MFMA kernel of f8_dwlk.hip (instances 4 / 5 of the launcher below); a launch of its own
 // (S_DW, f8_net.cpp).
 //
 // All kernels work in the stored domain of the 3x3 kernels: NHWC int8 with channel stride Cs (a multiple of 32); unsigned tensors are stored
@@ -26,6 +26,8 @@
 //                                 residue class mod d — and walks the six columns q - pad, q - pad + d, .. q - pad + 5d once; each transposed column feeds
 //                                 up to three pixels: 18 loads, 48 v_perm_b32 and 48 dot4 for 4 x 4 output values (144 multiply-adds).  A row is cut into
 //                                 min(d, Q) residues x ceil(ceil(Q / d) / DWK_PIX) groups; pixels at or beyond Q are computed and not stored.
+//   dwconvk_dil_dot4_kernel<K, ROWS>  int8 forms only, 5x5 / 7x7 at run-time dilation d > 1, stride 1 (option dw_dilated = 1): residue classes in BOTH axes and two
+//                                 weight images a byte apart — see the comment in front of it.
 //   dwstrip_dot4_kernel<NW>       int8 forms only, the strips 1 x k / k x 1 of f8_net_conv_rect (3 <= k <= 31) at stride 1, both orientations in one kernel:
 //                                 see the comment in front of it.  Strips at stride 2, with an int32 form or under dwk_dot4 = 0 run dwconvk_kernel, whose
 //                                 tap loops are per axis (DwArgs::k rows behind the top pad, DwArgs::kw columns behind pad_w).
@@ -248,6 +250,129 @@ __global__ void __launch_bounds__(256) dwconv3x3_dil_dot4_kernel(const DwArgs a)
     }
 }
 
+// Depthwise 5x5 / 7x7 at run-time dilation d > 1, stride 1, int8 forms only (option dw_dilated = 1).  The column ownership of dwconv3x3_dil_dot4_kernel with the
+// pre-shifted weight images of dwstrip_dot4_kernel, turned to the rows: one thread = 4 channels x DWK_PIX output pixels q = res + d (DWK_PIX g + j) of one column
+// residue class mod d x ROWS output rows p, p + d of one ROW residue class.  It walks its DWK_PIX + K - 1 input columns q0 - pad + cc d once; per column it loads
+// the NR = K + ROWS - 1 rows p - pad + r d (one dword = 4 channels each; outside the image: the biased zero) and byte-transposes them in groups of four LOADED
+// rows into one dword per channel.  Output row p meets weight image 0 (byte j of group g = kernel row 4 g + j), output row p + d image 1 (kernel row
+// 4 g + j - 1; 0 outside 0 .. K - 1): the two rows share every load and every transpose, and each transposed column feeds every pixel whose window holds it.
+// NR is 5 .. 8, so there are always two groups; the last one holds 1 (K 5, ROWS 1: three shifts), 2 (K 5, ROWS 2: two v_perm_b32 and two shifts), 3 or 4 rows
+// (K 7: the eight v_perm_b32) — slots past the loaded rows meet zero weights and may hold anything.  Per column and pixel: 8 dot4 per output row.
+// Weights: pack_dwk_weights' image [Cs / 4][K columns][2 images][2 groups][4 channels] dwords; ROWS = 1 reads image 0 only.  Threads run over channel quads
+// first, then column residues, pixel groups, row units (ROWS = 1: the P rows; ROWS = 2: min(d, P) row residues x ceil(ceil(P / d) / 2) pairs) and images;
+// pixels and rows at or beyond Q / P are computed and not stored, empty residue classes get no thread.
+template <int K, int ROWS>
+__global__ void __launch_bounds__(256) dwconvk_dil_dot4_kernel(const DwArgs a) {
+    constexpr int PIX = DWK_PIX, NCOL = PIX + K - 1;                                 // the pixels' columns: q0 - pad + cc * dil
+    constexpr int NR = K + ROWS - 1;                                                 // loaded rows of a column
+    constexpr int G = (NR + 3) / 4, LAST = NR - 4 * (G - 1);                         // groups of four loaded rows; rows of the last one
+    static_assert((K == 5 || K == 7) && (ROWS == 1 || ROWS == 2) && G == 2, "K is 5 or 7: two groups");
+    const int d = a.dil;
+    const int cgs = a.Cs >> 2;                       // 4-channel quads
+    const int DR = min(d, a.Q);                      // column residue classes that hold a pixel
+    const int NG = ((a.Q + d - 1) / d + PIX - 1) / PIX;
+    const int RR = ROWS == 1 ? 1 : min(d, a.P);      // row residue classes that hold a row ...
+    const int NM = ROWS == 1 ? a.P : ((a.P + d - 1) / d + 1) / 2;      // ... and the row pairs of one (ROWS = 1: the rows themselves)
+    const size_t total = (size_t)a.N * NM * RR * NG * DR * cgs;
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    const int cg = (int)(idx % cgs);
+    size_t st = idx / cgs;
+    const int res = (int)(st % DR); st /= DR;
+    const int g = (int)(st % NG); st /= NG;
+    const int rr = (int)(st % RR); st /= RR;
+    const int m = (int)(st % NM);
+    const int n = (int)(st / NM);
+    const int c = cg << 2, q0 = g * PIX * d + res, p0 = ROWS == 1 ? m : rr + 2 * d * m;
+    const unsigned padv = a.in_signed ? 0u : 0x80808080u;
+    const int h0 = p0 - a.pad, w0 = q0 - a.pad;
+    const unsigned* const wq = (const unsigned*)a.w + (size_t)cg * (K * 2 * G * 4);   // [column][image][group][channel]
+
+    int acc[ROWS][PIX][4];
+    {
+        const v4i bv = *(const v4i*)(a.bias + c);
+#pragma unroll
+        for (int i = 0; i < ROWS; ++i)
+#pragma unroll
+            for (int j = 0; j < PIX; ++j) { acc[i][j][0] = bv.x; acc[i][j][1] = bv.y; acc[i][j][2] = bv.z; acc[i][j][3] = bv.w; }
+    }
+    const int8_t* const xn = a.x + (size_t)n * a.H * a.W * a.Cs + c;
+#pragma unroll
+    for (int cc = 0; cc < NCOL; ++cc) {
+        const int w = w0 + cc * d;
+        const bool wok = (unsigned)w < (unsigned)a.W;
+        unsigned t[4 * G];                            // loaded rows 0 .. NR - 1 of this column, 4 channels each
+#pragma unroll
+        for (int r = 0; r < NR; ++r) {
+            const int h = h0 + r * d;
+            unsigned v = padv;
+            if (wok && (unsigned)h < (unsigned)a.H) v = *(const unsigned*)(xn + ((size_t)h * a.W + w) * a.Cs);
+            t[r] = v;
+        }
+        unsigned col[G][4];                           // [row group][channel]: bytes = the group's four loaded rows
+#pragma unroll
+        for (int gg = 0; gg < G; ++gg) {
+            const unsigned t0 = t[4 * gg];
+            if (gg == G - 1 && LAST == 1) {           // one row: byte 0
+                col[gg][0] = t0; col[gg][1] = t0 >> 8; col[gg][2] = t0 >> 16; col[gg][3] = t0 >> 24;
+            } else if (gg == G - 1 && LAST == 2) {    // two rows: bytes 0, 1
+                const unsigned lo01 = __builtin_amdgcn_perm(t[4 * gg + 1], t0, 0x05010400u), hi01 = __builtin_amdgcn_perm(t[4 * gg + 1], t0, 0x07030602u);
+                col[gg][0] = lo01; col[gg][1] = lo01 >> 16; col[gg][2] = hi01; col[gg][3] = hi01 >> 16;
+            } else {
+                const unsigned t1 = t[4 * gg + 1], t2 = t[4 * gg + 2];
+                const unsigned t3 = (gg == G - 1 && LAST == 3) ? t2 : t[4 * gg + 3];     // (three rows: slot 3 meets a zero weight)
+                const unsigned lo01 = __builtin_amdgcn_perm(t1, t0, 0x05010400u), hi01 = __builtin_amdgcn_perm(t1, t0, 0x07030602u);
+                const unsigned lo23 = __builtin_amdgcn_perm(t3, t2, 0x05010400u), hi23 = __builtin_amdgcn_perm(t3, t2, 0x07030602u);
+                col[gg][0] = __builtin_amdgcn_perm(lo23, lo01, 0x05040100u); col[gg][1] = __builtin_amdgcn_perm(lo23, lo01, 0x07060302u);
+                col[gg][2] = __builtin_amdgcn_perm(hi23, hi01, 0x05040100u); col[gg][3] = __builtin_amdgcn_perm(hi23, hi01, 0x07060302u);
+            }
+        }
+        // every pixel j whose window holds column cc: kernel column s = cc - j; output row i against image i
+#pragma unroll
+        for (int j = 0; j < PIX; ++j) {
+            const int s = cc - j;
+            if (s < 0 || s >= K) continue;
+#pragma unroll
+            for (int i = 0; i < ROWS; ++i)
+#pragma unroll
+                for (int gg = 0; gg < G; ++gg) {
+                    const v4i wv = *(const v4i*)(wq + ((s * 2 + i) * G + gg) * 4);
+                    acc[i][j][0] = __builtin_amdgcn_sdot4((int)col[gg][0], wv.x, acc[i][j][0], false);
+                    acc[i][j][1] = __builtin_amdgcn_sdot4((int)col[gg][1], wv.y, acc[i][j][1], false);
+                    acc[i][j][2] = __builtin_amdgcn_sdot4((int)col[gg][2], wv.z, acc[i][j][2], false);
+                    acc[i][j][3] = __builtin_amdgcn_sdot4((int)col[gg][3], wv.w, acc[i][j][3], false);
+                }
+        }
+    }
+    const int floor0 = a.relu0 ? 0 : INT32_MIN;
+#pragma unroll
+    for (int i = 0; i < ROWS; ++i) {
+        const int p = p0 + i * d;
+        if (p >= a.P) continue;
+#pragma unroll
+        for (int j = 0; j < PIX; ++j) {
+            const int q = q0 + j * d;
+            if (q >= a.Q) continue;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc[i][j][e] = max(acc[i][j][e], floor0);
+            const size_t o = ((((size_t)n * a.P + p) * a.Q + q)) * a.Cs + c;
+#pragma unroll
+            for (int f = 0; f < 2; ++f)
+                if (a.q[f].ptr)
+                    *(unsigned*)(a.q[f].ptr + o) =
+                        requant_pack4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3], a.q[f]);
+        }
+    }
+}
+
+// How many output rows a thread of dwconvk_dil_dot4_kernel owns where option dw_dilated = 1 plans it.  rows: Options::dwdil_rows (0 = the measured rule, 1 / 2 =
+// that many: the A/B of tools/ab_dwdil.py).  The rule is ONE row everywhere: ROWS = 2 halves the loads and permutes per output value but keeps both weight
+// images and 32 accumulators in registers — 228 (K 5) / 256 (K 7) VGPRs against 109 / 148 — and lost on all ten shapes of profiles/dwdil_r23.md, by 1.12 .. 1.24x
+// at K 5 and 1.8 .. 2.2x at K 7.  ROWS = 1 beat dwconvk_kernel on every one of them (1.03x on 512 x 7^2, 1.8 .. 5.1x elsewhere), so no shape is kept off the kernel.
+static int dwdil_rows(const DwArgs&, int rows) {
+    return rows ? rows : 1;
+}
+
 // Depthwise strips 1 x k / k x 1 at stride 1 (f8_net_conv_rect), int8 forms only, on v_dot4_i32_i8: ONE kernel for both orientations — the strip axis is a
 // run-time byte step between successive taps and successive outputs (Cs for 1 x k, W * Cs for k x 1).  One thread = 4 channels x DWS_RUN consecutive
 // outputs o0 .. o0 + DWS_RUN - 1 along the strip.  It loads the DWS_RUN / 4 + NW - 1 groups of four input positions from i0 = o0 - pad on, once (a position
@@ -331,15 +456,18 @@ __global__ void __launch_bounds__(256) dwstrip_dot4_kernel(const DwArgs a) {
 }
 
 // General depthwise: the v_dot4 kernels for int8-only launches (Options::dwk_dot4), else the generic one.  A dilated conv (3x3 only) has its dot4
-// kernel — instance 2 — at stride 1, exactly where dwconvk_dot4_kernel<3, 1> runs the undilated one.
-int dwk_inst(const DwArgs& a, bool out32, int nq, bool dot4, bool large) {
+// kernel — instance 2 — at stride 1, exactly where dwconvk_dot4_kernel<3, 1> runs the undilated one; a dilated 5x5 / 7x7 (option dw_dilated) has instances
+// 6 / 7 — dwconvk_dil_dot4_kernel<K, 1 / 2> — there when dilk says so (0: dw_dilated is not 1; else 1 + Options::dwdil_rows).
+int dwk_inst(const DwArgs& a, bool out32, int nq, bool dot4, bool large, int dilk) {
     if (a.kw == a.k && a.k >= 8) return large && !out32 && nq >= 1 && a.stride == 1 && a.dil == 1 && dwlk_rule(a, nq) ? 3 + nq : 0;      // f8_dwlk.hip: 4 / 5
     if (a.kw != a.k) return dot4 && !out32 && a.stride == 1 && a.dil == 1 && (a.k == 1 || a.kw == 1) ? 3 : 0;      // a strip: instance 3, dwstrip_dot4_kernel
-    if (a.dil > 1) return dot4 && !out32 && a.k == 3 && a.stride == 1 ? 2 : 0;
+    if (a.dil > 1 && a.k != 3) return dot4 && !out32 && dilk && a.stride == 1 ? 5 + dwdil_rows(a, dilk - 1) : 0;
+    if (a.dil > 1) return dot4 && !out32 && a.stride == 1 ? 2 : 0;
     return dot4 && !out32 && (a.k == 3 || a.k == 5 || a.k == 7) && (a.stride == 1 || a.stride == 2) ? 1 : 0;
 }
 
 int dwk_kernel_name(char* buf, size_t cap, const DwArgs& a, int inst) {
+    if (inst >= 6) return snprintf(buf, cap, "f8::dwconvk_dil_dot4_kernel<%d, %d>", a.k, inst - 5);
     if (inst >= 4) return dwlk_kernel_name(buf, cap, a, inst - 3);
     if (inst == 2) return snprintf(buf, cap, "f8::dwconv3x3_dil_dot4_kernel");
     if (inst == 3) return snprintf(buf, cap, "f8::dwstrip_dot4_kernel<%d>", (std::max(a.k, a.kw) + 6) / 4);
@@ -348,7 +476,7 @@ int dwk_kernel_name(char* buf, size_t cap, const DwArgs& a, int inst) {
 }
 
 hipError_t launch_dwk(const DwArgs& a, int inst, hipStream_t s) {
-    if (inst >= 4) return launch_dwlk(a, inst - 3, s);
+    if (inst >= 4 && inst <= 5) return launch_dwlk(a, inst - 3, s);
     if (a.kw != a.k) {                                    // a strip 1 x k / k x 1: pads below k on its axis, none on the other; instance 3 or the generic kernel
         const int k = std::max(a.k, a.kw);
         if (std::min(a.k, a.kw) != 1 || k < 3 || k > 31 || a.dil != 1 || a.pad < 0 || a.pad >= a.k || a.pad_w < 0 || a.pad_w >= a.kw || (inst != 0 && inst != 3))
@@ -367,8 +495,22 @@ hipError_t launch_dwk(const DwArgs& a, int inst, hipStream_t s) {
             return hipErrorInvalidValue;
         }
     } else {
-        if (a.k < 1 || a.dil < 1 || a.pad < 0 || a.pad > (a.dil > 1 ? a.dil : a.k / 2) || (a.dil > 1 && a.k != 3) || a.pad_w != a.pad) return hipErrorInvalidValue;
-        if ((inst == 2) != (a.dil > 1 && inst != 0)) return hipErrorInvalidValue;      // a dot4 instance: 2 for a dilated conv and only for one
+        if (a.k < 1 || a.dil < 1 || a.pad < 0 || a.pad > a.dil * (a.k / 2) || (a.dil > 1 && a.k != 3 && a.k != 5 && a.k != 7) || a.pad_w != a.pad) return hipErrorInvalidValue;
+        const bool dil_inst = inst == 2 || inst == 6 || inst == 7;
+        if (dil_inst != (a.dil > 1 && inst != 0) || (dil_inst && (inst == 2) != (a.k == 3))) return hipErrorInvalidValue;      // a dot4 instance: 2 (3x3) / 6, 7 (5x5, 7x7) for a dilated conv and only for one
+    }
+    if (inst >= 6) {
+        if (a.out32 || !a.w4 || a.stride != 1) return hipErrorInvalidValue;
+        const int rows = inst - 5, d = a.dil;
+        const int DR = std::min(d, a.Q), NG = ((a.Q + d - 1) / d + DWK_PIX - 1) / DWK_PIX;
+        const int RU = rows == 1 ? a.P : std::min(d, a.P) * (((a.P + d - 1) / d + 1) / 2);
+        const size_t work = (size_t)a.N * RU * NG * DR * (a.Cs >> 2);
+        const unsigned grid = (unsigned)((work + 255) / 256);
+        DwArgs b = a; b.w = a.w4; b.bias = a.bias4;
+#define F8_DWD(K_, R_) if (a.k == K_ && rows == R_) { hipLaunchKernelGGL((dwconvk_dil_dot4_kernel<K_, R_>), dim3(grid), dim3(256), 0, s, b); return hipGetLastError(); }
+        F8_DWD(5, 1) F8_DWD(5, 2) F8_DWD(7, 1) F8_DWD(7, 2)
+#undef F8_DWD
+        return hipErrorInvalidValue;
     }
     if (inst == 2) {
         if (a.out32 || !a.w4 || a.stride != 1) return hipErrorInvalidValue;

@@ -75,6 +75,10 @@ struct Options {
                                  // dense expansion (the plain conv kernels over block-diagonal weights) elsewhere; 2 = accepted, always the dense expansion
     int dw_large = 0;            // depthwise convs of kernel 8 .. 31 (stride 1 / 2, pad 0 .. kernel / 2): 0 = refused by f8_net_conv; 1 = accepted, on dwlk_kernel (f8_dwlk.hip) where
                                  // dwlk_rule says so (stride 1, int8 forms only) and on dwconvk_kernel elsewhere; 2 = accepted, always dwconvk_kernel
+    int dw_dilated = 0;          // depthwise 5x5 / 7x7 at dilation 2 .. 64 (stride 1 / 2, pad 0 .. dilation * (kernel / 2)): 0 = refused by f8_net_conv_dilated; 1 = accepted, on
+                                 // dwconvk_dil_dot4_kernel (f8_dwk.hip) at stride 1 with int8 forms only (and dwk_dot4 = 1) and on dwconvk_kernel elsewhere; 2 = accepted, always dwconvk_kernel
+    int dwdil_rows = 0;          // with dw_dilated = 1: output rows a thread of dwconvk_dil_dot4_kernel owns: 0 = the measured rule (1 everywhere: dwdil_rows, f8_dwk.hip),
+                                 // 1 / 2 = that many everywhere (the A/B of tools/ab_dwdil.py; same values either way)
     int gconv_wide = 0;          // with grouped = 1: 1 = grouped 3x3 convs of group width cg in {24, 40, 48, 56, 64} (cin == cout, stride 1 / 2, pad 0 / 1) on gconvw3x3_kernel
                                  // (f8_gconvw.hip, gconvw3x3s<S>:); 0 (default, until it is measured): the dense expansion, as before the kernel existed
     int gconv_xwide = 0;         // with grouped = 1: 1 = grouped 3x3 convs of group width cg = 72 .. 256, a multiple of 8 (cin == cout, groups >= 2, stride 1 / 2, pad 0 / 1) on
@@ -170,7 +174,7 @@ struct ConvArgs {
 };
 
 // Depthwise K x K (groups == C), NHWC int8 in, VALU.  3x3 / pad 1: the launchers of f8_kernels.hip / f8_dwmma.hip, which never read `k`;
-// every other accepted geometry (k 3 / 5 / 7 and — option dw_large — 8 .. 31, pad <= k / 2; k 3 at dilation dil > 1, pad <= dil: "general depthwise"): f8_dwk.hip and
+// every other accepted geometry (k 3 / 5 / 7 and — option dw_large — 8 .. 31, pad <= k / 2; k 3 and — option dw_dilated — 5 / 7 at dilation dil > 1, pad <= dil * (k / 2): "general depthwise"): f8_dwk.hip and
 // f8_dwlk.hip, with the images of pack_dwk_weights.
 struct DwArgs {
     const int8_t* x; const int8_t* w;      // w: [k * k][Cs] tap-major
@@ -179,6 +183,7 @@ struct DwArgs {
                                            // general: [Cs/4][k columns][ceil(k / 4) row groups][4 channels] dwords, byte j = row 4g + j (0 beyond k)
                                            // a strip (kw != k): [Cs/4][4 phases][ceil((k + 3) / 4)][4 channels] dwords, the taps shifted by `phase` bytes
                                            // k >= 8: DwlkArgs::w
+                                           // k 5 / 7 at dil > 1: [Cs/4][k columns][2 images][2 groups][4 channels] dwords, byte j = row 4g + j - image (0 outside 0 .. k - 1)
     int32_t N, H, W, P, Q, Cs, stride, pad;
     int32_t in_signed;
     int32_t relu0;
@@ -824,8 +829,9 @@ int dwconv_kernel_name(char* buf, size_t cap, const DwArgs& a, int inst);
 hipError_t launch_dwconv(const DwArgs& a, int inst, hipStream_t s);
 // general depthwise (f8_dwk.hip): every accepted depthwise geometry but the undilated 3x3 / pad 1.  inst 1: dwconvk_dot4_kernel<k, stride> (int8 outputs only,
 // Options::dwk_dot4), 2: dwconv3x3_dil_dot4_kernel (the same, 3x3 at dilation > 1, stride 1), 3: dwstrip_dot4_kernel (strips), 4 / 5: dwlk_kernel (f8_dwlk.hip: k 8 .. 31 at
-// stride 1, nq = 1 / 2 int8 outputs and no int32 one, Options::dw_large == 1 — `large`), 0: dwconvk_kernel<in_signed>
-int dwk_inst(const DwArgs& a, bool out32, int nq, bool dot4, bool large);
+// stride 1, nq = 1 / 2 int8 outputs and no int32 one, Options::dw_large == 1 — `large`), 6 / 7: dwconvk_dil_dot4_kernel<k, 1 / 2> (k 5 / 7 at dilation > 1, stride 1, int8 outputs only, dilk != 0: 0 unless Options::dw_dilated == 1,
+// else 1 + Options::dwdil_rows), 0: dwconvk_kernel<in_signed>
+int dwk_inst(const DwArgs& a, bool out32, int nq, bool dot4, bool large, int dilk);
 int dwk_kernel_name(char* buf, size_t cap, const DwArgs& a, int inst);
 hipError_t launch_dwk(const DwArgs& a, int inst, hipStream_t s);
 bool dwlk_geom(const DwArgs& a, int nq, DwlkArgs* g);           // f8_dwlk.hip: the tile of a large depthwise launch that writes nq int8 forms; false: none fits

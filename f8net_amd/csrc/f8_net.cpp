@@ -469,6 +469,8 @@ static const OptKey kOptKeys[] = {
     {"tap_tiled", "F8_TAP_TILED", &Options::tap_tiled, 0, 1, true},
     {"grouped", "F8_GROUPED", &Options::grouped, 0, 2, true},
     {"dw_large", "F8_DW_LARGE", &Options::dw_large, 0, 2, true},
+    {"dw_dilated", "F8_DW_DILATED", &Options::dw_dilated, 0, 2, true},
+    {"dwdil_rows", "F8_DWDIL_ROWS", &Options::dwdil_rows, 0, 2, true},
     {"gconv_wide", "F8_GCONV_WIDE", &Options::gconv_wide, 0, 1, true},
     {"gconv_xwide", "F8_GCONV_XWIDE", &Options::gconv_xwide, 0, 1, true},
     {"concat_i8", "F8_CONCAT_I8", &Options::concat_i8, 0, 1, true},
@@ -680,9 +682,16 @@ static int add_conv_node(f8_net* net, int src, const f8_conv_desc& d, int dil, c
     if (d.groups != 1 && !grouped && dil == 1 && !(dw_k && d.stride <= 2 && d.pad <= d.kernel / 2))
         return fail(F8_ERR_UNSUPPORTED, "%s: depthwise is built for kernel 3, 5 or 7%s, stride 1 or 2, pad 0 .. kernel / 2 (got kernel %d, stride %d, pad %d)",
                     who, net->opt.dw_large >= 1 ? " and (option dw_large) 8 .. 31" : "", d.kernel, d.stride, d.pad);
-    if (d.groups != 1 && !grouped && dil > 1 && !(d.kernel == 3 && d.stride <= 2 && d.pad <= dil))
+    // ... and so are dilated 5x5 / 7x7 depthwise convs (option dw_dilated): dwconvk_dil_dot4_kernel or the generic kernel of f8_dwk.hip.  pad <= dilation * (kernel / 2)
+    // is the 3x3 rule (pad <= dilation) for any kernel: a window keeps its centre tap inside the image
+    const bool dil_k = d.kernel == 3 || (net->opt.dw_dilated >= 1 && (d.kernel == 5 || d.kernel == 7));
+    if (d.groups != 1 && !grouped && dil > 1 && !(dil_k && d.stride <= 2 && d.pad <= dil * (d.kernel / 2))) {
+        if (net->opt.dw_dilated >= 1)
+            return fail(F8_ERR_UNSUPPORTED, "%s: dilated depthwise is built for kernel 3 and (option dw_dilated) 5 or 7, stride 1 or 2, pad 0 .. dilation * (kernel / 2) "
+                        "(got kernel %d, stride %d, pad %d, dilation %d)", who, d.kernel, d.stride, d.pad, dil);
         return fail(F8_ERR_UNSUPPORTED, "%s: dilated depthwise is built for kernel 3, stride 1 or 2, pad 0 .. dilation (got kernel %d, stride %d, pad %d, dilation %d)",
                     who, d.kernel, d.stride, d.pad, dil);
+    }
     if (d.weight_fl < 0 || d.weight_fl > 31) return fail(F8_ERR_INVALID, "%s: bad weight_fl", who);
     int n;
     rc = consumer_format(s, d, &n, who);
@@ -1429,7 +1438,7 @@ static void pack_dw_weights(f8_net* net, Node& nd) {
     }
 }
 
-// "General depthwise": every accepted depthwise conv that is not 3x3 / pad 1 (kernel 3 / 5 / 7 and, option dw_large, 8 .. 31, stride 1 / 2, pad 0 .. kernel / 2; add_conv_node).  One pass
+// "General depthwise": every accepted depthwise conv that is not 3x3 / pad 1 (kernel 3 / 5 / 7 and, option dw_large, 8 .. 31, stride 1 / 2, pad 0 .. kernel / 2; 3 and, option dw_dilated, 5 / 7 at dilation d > 1, pad 0 .. d * (kernel / 2); add_conv_node).  One pass
 // of the planner fuses one — 1e3, option fuse_irk: kernel 5 / 7 with pad kernel / 2 inside an inverted residual —; every other matcher asks for kernel 3
 // and pad 1, so anywhere else it is a launch of its own on the kernels of f8_dwk.hip.
 static bool dw_general(const Node& n) { const f8_conv_desc& d = n.cd; return d.groups != 1 && d.groups == d.cin && !(d.kernel == 3 && d.pad == 1 && n.dil == 1); }
@@ -1451,7 +1460,11 @@ static void pack_dwk_weights(f8_net* net, Node& nd) {
     // (channel, row r) = Z[u + ph], Z the zero-extended weight row with Z[31 + s] = w[r][s].  A lane's 16 consecutive bytes of Z from any t0 on are then four
     // ALIGNED dwords of copy t0 & 3 (the strips' byte-shifted copies, a whole band long).
     const bool large = !nd.rect && K >= 8;
-    const size_t w4_bytes = nd.rect ? (size_t)(src.Cs / 4) * 4 * NW * 16 : large ? (size_t)src.Cs * K * 4 * DWLK_ROWB : (size_t)(src.Cs / 4) * K * G * 16;
+    // a dilated 5x5 / 7x7 (option dw_dilated): image (2) is dwconvk_dil_dot4_kernel's — [Cs / 4][K columns][2 images][2 groups][4 channels] dwords: byte j of dword
+    // (quad, s, i, g, e) = the weight of channel 4 quad + e at row 4 g + j - i, column s, 0 outside rows 0 .. K - 1.  Image 0 meets the thread's first output row,
+    // image 1 — the same taps one byte on — its second, one dilation step below (K + 1 <= 8 loaded rows: two groups either way)
+    const bool dilk = !nd.rect && nd.dil > 1 && (K == 5 || K == 7);
+    const size_t w4_bytes = nd.rect ? (size_t)(src.Cs / 4) * 4 * NW * 16 : large ? (size_t)src.Cs * K * 4 * DWLK_ROWB : (size_t)(src.Cs / 4) * K * (dilk ? 4 : G) * 16;
     nd.coutP = src.Cs; nd.ck = 0; nd.ktot = 0;
     nd.w_off = round_up_z(net->wblob.size(), 256);
     nd.b_off = round_up_z(nd.w_off + (size_t)KH * KW * src.Cs, 256);
@@ -1472,6 +1485,11 @@ static void pack_dwk_weights(f8_net* net, Node& nd) {
                 if (large) {
                     for (int ph = 0; ph < 4; ++ph)
                         if (31 + s - ph >= 0) w4[(((size_t)c * K + r) * 4 + ph) * DWLK_ROWB + 31 + s - ph] = v;
+                    continue;
+                }
+                if (dilk) {
+                    for (int i = 0; i < 2; ++i)
+                        w4[(((((size_t)(c / 4) * K + s) * 2 + i) * 2 + (r + i) / 4) * 4 + c % 4) * 4 + (r + i) % 4] = v;
                     continue;
                 }
                 if (!nd.rect) { w4[((((size_t)(c / 4) * K + s) * G + r / 4) * 4 + c % 4) * 4 + r % 4] = v; continue; }
@@ -4040,7 +4058,7 @@ static int bind_step(f8_net* net, Step& st) {
             a.k = g.kh; a.kw = g.kw; a.dil = nd.dil;
             out_formats(a.q);
             if (dw_general(nd)) {                                 // f8_dwk.hip: integer requantisation (requant1) whatever requant_float says
-                st.inst = dwk_inst(a, out32, nq, opt.dwk_dot4, opt.dw_large == 1);
+                st.inst = dwk_inst(a, out32, nq, opt.dwk_dot4, opt.dw_large == 1, opt.dw_dilated == 1 ? 1 + opt.dwdil_rows : 0);
                 dwk_kernel_name(kb, sizeof kb, a, st.inst);
             } else {
                 st.inst = dwconv_inst(a, out32, nq, opt.dw_mma, opt.dw_dot4, net->max_batch);     // (the MMA kernel's index bound at the largest launch)

@@ -24,12 +24,13 @@ def _np_i32(a):
 def accept_grouped(net, convs, options=None):
     """The raw builder refuses grouped convs (1 < groups < cin) unless the handle's option `grouped` says otherwise, and the option must be set
     before the conv is added.  The high-level entry points call this before they record: a value the caller gave (options, or F8_GROUPED in the
-    environment) is applied as it is; with none, `grouped` becomes 1 when one of `convs` — (cin, groups) or (cin, groups, kernel) — is grouped.  A
+    environment) is applied as it is; with none, `grouped` becomes 1 when one of `convs` — (cin, groups[, kernel[, dilation]]) — is grouped.  A
     `gconv_wide` key of `options` (group widths 24 .. 64 on the group-aligned kernel) and a `gconv_xwide` key (72 .. 256 on the weight-streaming kernel) are
     forwarded the same way; nothing sets them unasked.
 
     Large depthwise kernels (groups == cin, square kernel 8 .. 31) are opt-in the same way through option `dw_large` (environment F8_DW_LARGE): a value
-    the caller gave is applied as it is; with none, `dw_large` becomes 1 when one of `convs` names such a kernel."""
+    the caller gave is applied as it is; with none, `dw_large` becomes 1 when one of `convs` names such a kernel.  Dilated depthwise 5x5 / 7x7 convs
+    (dilation > 1) likewise through option `dw_dilated` (environment F8_DW_DILATED)."""
     for key in ('gconv_wide', 'gconv_xwide'):
         if options and key in options:
             net.set_option(key, options[key])
@@ -41,6 +42,10 @@ def accept_grouped(net, convs, options=None):
         net.set_option('dw_large', options['dw_large'])
     elif 'F8_DW_LARGE' not in os.environ and any(len(c) > 2 and c[1] == c[0] > 1 and 8 <= c[2] <= 31 for c in convs):
         net.set_option('dw_large', 1)
+    if options and 'dw_dilated' in options:
+        net.set_option('dw_dilated', options['dw_dilated'])
+    elif 'F8_DW_DILATED' not in os.environ and any(len(c) > 3 and c[1] == c[0] > 1 and c[2] in (5, 7) and c[3] > 1 for c in convs):
+        net.set_option('dw_dilated', 1)
 
 
 def conv_pair(v):
@@ -578,8 +583,8 @@ def build_net(spec: topology.NetSpec, params: dict, max_batch: int, hw: int = 22
 
 def record_net(spec: topology.NetSpec, params: dict, hw: int = 224, input_fraclen=None, taps=(), options=None) -> F8Net:
     """The recording half of build_net: the graph is in the handle, not yet planned (set planning options, then finalize).
-    options: only its `grouped`, `gconv_wide`, `gconv_xwide` and `dw_large` keys are read here — grouped convs and large depthwise kernels are accepted while
-    they are recorded (accept_grouped).
+    options: only its `grouped`, `gconv_wide`, `gconv_xwide`, `dw_large` and `dw_dilated` keys are read here — grouped convs, large depthwise
+    kernels and dilated depthwise 5x5 / 7x7 convs are accepted while they are recorded (accept_grouped).
 
     taps: names of further tensors to return, marked as int32 outputs 1, 2, ... in the order given (output 0 stays the float
     logits).  A name is a block name (`stage_1_layer_3`: the block's output tensor, whether or not the block ends in a join), a
@@ -590,7 +595,7 @@ def record_net(spec: topology.NetSpec, params: dict, hw: int = 224, input_fracle
     that can be tapped is kept as `net.tap_ids`, the names given as `net.taps`."""
     params = {k: (v.detach().cpu().numpy() if hasattr(v, 'detach') else np.asarray(v)) for k, v in params.items()}
     net = F8Net()
-    accept_grouped(net, [(c.cin, c.groups, c.k) for c in spec.convs()], options)
+    accept_grouped(net, [(c.cin, c.groups, c.k, c.dilation) for c in spec.convs()], options)
     head_in_fl = _fl(params, spec.head.key, 'input_fraclen')
     if input_fraclen is None:
         input_fraclen = head_in_fl if spec.normalize else 8     # fix_train.py:683-692

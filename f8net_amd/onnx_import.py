@@ -210,7 +210,7 @@ class IntGraph:
         from .net import F8Net, accept_grouped
         V, layer = self.solve_fraclens(input_fraclen)
         net = F8Net()
-        accept_grouped(net, [(o.weight.shape[1] * o.groups, o.groups, o.weight.shape[2] if o.weight.shape[2] == o.weight.shape[3] else 0)
+        accept_grouped(net, [(o.weight.shape[1] * o.groups, o.groups, o.weight.shape[2] if o.weight.shape[2] == o.weight.shape[3] else 0, o.dilation)
                              for o in self.ops if o.kind == 'conv'], options)
         ids = {}
         for t, o in enumerate(self.ops):

@@ -195,7 +195,7 @@ def _conv2d(x, weight, bias, stride, pad, groups, weight_fl, input_fl, input_sig
 
     def build(n):
         net = F8Net()
-        accept_grouped(net, [(C, groups, weight.shape[2] if weight.shape[2] == weight.shape[3] else 0)])
+        accept_grouped(net, [(C, groups, weight.shape[2] if weight.shape[2] == weight.shape[3] else 0, dilation)])
         t = net.input(C, H, W, input_fl)
         t = net.conv(t, _np(weight), _np(bias), stride=stride, pad=pad, groups=groups, weight_fl=weight_fl, input_fl=input_fl,
                      input_signed=input_signed, quant_input=False, relu=False, dilation=dilation)

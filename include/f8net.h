@@ -137,9 +137,12 @@ int f8_net_conv(f8_net* net, int src, const f8_conv_desc* desc,
  * output size (H + 2 pad - dilation (kernel - 1) - 1) / stride + 1; weights as f8_net_conv ([cout, cin/groups, k, k], the k x k real taps).
  * f8_net_conv is the dilation == 1 call of this function.  Accepted for 1 <= dilation <= 64: plain convs (groups == 1) of any geometry
  * f8_net_conv takes (kernel == 1: dilation is normalised to 1), on conv_igemm_kernel, a launch of its own (conv3x3s1d2_t128x64x64[_res]:) that may
- * carry the residual join; depthwise convs of kernel 3 with pad <= dilation, stride 1 / 2 (dwconv3x3s1d2:, f8_dwk.hip); grouped convs on a handle
+ * carry the residual join; depthwise convs of kernel 3 with pad <= dilation, stride 1 / 2 (dwconv3x3s1d2:, f8_dwk.hip) — and, on a handle whose option
+ * `dw_dilated` is 1 or 2, set BEFORE this call, of kernel 5 or 7 with 2 <= dilation <= 64, stride 1 / 2, pad <= dilation * (kernel / 2)
+ * (dwconv5x5s1d2:; f8_net_conv_rect's square and symmetric route likewise) —; grouped convs on a handle
  * with option grouped >= 1, always as the dense expansion (gconv3x3s1d2_dense:).  A dilated conv joins no fused block or chain launch.
- * F8_ERR_INVALID: dilation < 1, or an empty output; F8_ERR_UNSUPPORTED: dilation > 64, or a depthwise kernel of 5 / 7 with dilation > 1. */
+ * F8_ERR_INVALID: dilation < 1, or an empty output; F8_ERR_UNSUPPORTED: dilation > 64, a depthwise kernel of 5 / 7 with dilation > 1 while option
+ * dw_dilated is 0, and with it on a depthwise kernel of 8 .. 31, a stride above 2 or a larger pad at dilation > 1. */
 int f8_net_conv_dilated(f8_net* net, int src, const f8_conv_desc* desc, int dilation,
                         const int32_t* weight_host, const int32_t* bias_host);
 
@@ -602,7 +605,13 @@ int f8_net_check(f8_net* net);
  *               8 .. 31 is F8_ERR_UNSUPPORTED, as every other depthwise kernel but 3, 5 and 7; 1 = accepted (stride 1 or 2, 0 <= pad <= kernel / 2, dilation 1),
  *               plan token dwconv{K}x{K}s{S}:, on f8::dwlk_kernel<TC> (the Toeplitz MFMA kernel, f8_dwlk.hip) at stride 1 with int8 forms only and an output
  *               map of more than 8 rows and columns — the measured rule, profiles/dwlk_r22.md — and on f8::dwconvk_kernel elsewhere; 2 = accepted, always
- *               f8::dwconvk_kernel.  Same values either way, bit for bit)
+ *               f8::dwconvk_kernel.  Same values either way, bit for bit),
+ *               dw_dilated (0 .. 2, default 0, environment F8_DW_DILATED; read by f8_net_conv_dilated, so set it BEFORE the conv is added: 0 = a depthwise conv of
+ *               kernel 5 / 7 at dilation > 1 is F8_ERR_UNSUPPORTED; 1 = accepted (2 <= dilation <= 64, stride 1 or 2, 0 <= pad <= dilation * (kernel / 2)), plan
+ *               token dwconv{K}x{K}s{S}d{D}:, on f8::dwconvk_dil_dot4_kernel<K, ROWS> (f8_dwk.hip) at stride 1 with int8 forms only and dwk_dot4 = 1, on
+ *               f8::dwconvk_kernel elsewhere; 2 = accepted, always f8::dwconvk_kernel.  Same values either way, bit for bit),
+ *               dwdil_rows (0 .. 2, default 0, environment F8_DWDIL_ROWS; read at finalize: output rows a thread of f8::dwconvk_dil_dot4_kernel owns, 0 = the
+ *               measured rule — 1 everywhere, profiles/dwdil_r23.md —, 1 / 2 = that many everywhere; the A/B switch of tools/ab_dwdil.py.  Same values)
  *   scheduling: chunk56 / chunk28 / chunk14 (images per chunk of the fused blocks; -1 = derived from chunk_budget_mb, 0 = whole
  *               batch), chunk_budget_mb (memory-side cache a chunk's int32 stream may occupy), chunk_ds, chunk_opener,
  *               split_streams, graph, stagger, stagger_pipelined, stem_wpc, stem_grid_div (row-walking head on 1 / n of the CUs; 0 = by output form), wstat_grid_div (0 .. 32, default 0, environment F8_WSTAT_GRID_DIV: f8::conv1x1_wstat_kernel sizes its pixel groups for 1 / n of the CUs, at least one — tests walk long tile rings on small maps; 0 = all of them; the plan and the values do not move), check_device, check_input_range, pipeline_depth (2..4 runs in flight),
