@@ -83,6 +83,9 @@ struct Options {
                                  // (f8_gconvw.hip, gconvw3x3s<S>:); 0 (default, until it is measured): the dense expansion, as before the kernel existed
     int gconv_xwide = 0;         // with grouped = 1: 1 = grouped 3x3 convs of group width cg = 72 .. 256, a multiple of 8 (cin == cout, groups >= 2, stride 1 / 2, pad 0 / 1) on
                                  // gconvx3x3_kernel (f8_gconvx.hip, gconvx3x3s<S>:); 0 (default): the dense expansion, as before the kernel existed
+    int gconv_pw = 0;            // with grouped = 1: grouped 1x1 convs (stride 1, pad 0, cin / groups and cout / groups multiples of 4, cin / groups <= 512; an int32 output form only where
+                                 // cout / groups is a multiple of 8; cin != cout allowed) on gconvp1x1_kernel (f8_gconvp.hip, gconvp1x1s1:): 1 = where gconvp_rule says so, 2 = every shape of
+                                 // the set; 0 (default): the dense expansion, as before the kernel existed
     int concat_i8 = 1;           // f8_net_concat: 1 = the byte-gather mode where it is exact (every source written in the output's int8 formats, f8_concat.hip); 0 = always the int32 mode
     int upsample_i8 = 1;         // f8_net_upsample, nearest: 1 = the byte-copy mode where the result is read in at most two int8 formats and by nothing else (f8_upsample.hip); 0 = always the int32 mode
     int sumpool_wide = 1;        // f8_net_avgpool_window: 1 = sumpool_wide_kernel where sumpool_wide_rule says so (windows of 3 and more that do not overlap), else the block walker (f8_sumpool.hip);
@@ -245,6 +248,23 @@ struct GConvXArgs : GConvArgs {            // w: [groups (+ 1 pad unit)][KS subt
     int32_t pitch;                         // bytes of a patch pixel in LDS: 32 KS + 16 (gconvx_pitch)
     int32_t psplit, ipg;                   // a subtile's pixel groups are dealt to the waves in psplit parts of ipg = ceil(groups of the tile / psplit) <= 8
     FastDiv dCH;                           // / (pitch / 16)
+};
+// Grouped 1x1 / stride 1 / pad 0 over flat pixels (f8_gconvp.hip): cgi = cin / groups input and cgo = cout / groups output channels a group, both multiples
+// of 4, cin != cout allowed.  A unit = one group x one 32-output subtile; a workgroup runs TP pixels x GS whole groups (gconvp_plan).
+struct GConvPArgs {
+    const int8_t* x; uint32_t x_bytes;     // NHWC int8 [N H W][Ci]
+    const int8_t* w;                       // [groups * nsub (+ 1 pad unit)][ks ksteps][64 lanes][16 B], zero rows / K bytes past the group (pack_gconvp_weights)
+    const int32_t* bias;                   // [Co], + 128 * sum(w) for unsigned inputs: one class (no padding)
+    int32_t N, HW;                         // images of the run, pixels of a map: the kernel sees M = N * HW flat pixel rows
+    int32_t Ci, Co;                        // row strides (bytes / elements) of the input and of the outputs: cin and cout rounded up to 32
+    int32_t cgi, cgo, groups, cout;        // cout = groups * cgo <= Co
+    int32_t ks, nsub;                      // ceil(cgi / 32) K32 steps; ceil(cgo / 32) subtiles a group
+    int32_t GS, nspan;                     // groups a workgroup; workgroups a pixel tile: ceil(groups / GS)
+    int32_t TP, pitch;                     // pixels a tile (a multiple of 32); bytes of a pixel in LDS: GS * 32 * ks + 16
+    FastDiv dCHS, dGSL;                    // / (slots a pixel), / (slots a group): slots of 16 bytes where cgi % 8 == 0, else of 4
+    int32_t relu0;
+    int32_t* out32;
+    QuantOut q[2];
 };
 
 struct PoolArgs {                          // max-pool, NHWC
@@ -850,6 +870,11 @@ int gconvx_pitch(int cg);
 void gconvx_tile(int P, int Q, int stride, int cg, int* R, int* TW, int* G, int* psplit);
 int gconvx_kernel_name(char* buf, size_t cap, const GConvXArgs& a);
 hipError_t launch_gconvx(const GConvXArgs& a, hipStream_t s);
+// grouped 1x1 (cin != cout allowed) on the group-aligned flat-pixel MFMA kernel (f8_gconvp.hip): its geometry for M pixels, and where option gconv_pw = 1 plans it
+void gconvp_plan(int groups, int cgi, int cgo, long M, int* GS, int* TP, int* pitch);
+bool gconvp_rule(int groups, int cgi, int cgo);
+int gconvp_kernel_name(char* buf, size_t cap, const GConvPArgs& a);
+hipError_t launch_gconvp(const GConvPArgs& a, hipStream_t s);
 int maxpool_inst(const PoolArgs& a);
 const char* maxpool_kernel_name(int inst);
 hipError_t launch_maxpool(const PoolArgs& a, int inst, hipStream_t s);

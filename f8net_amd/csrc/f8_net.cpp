@@ -162,7 +162,7 @@ static f8_conv_geom geom_of(const Node& n) {
     const f8_conv_desc& d = n.cd;
     return f8_conv_geom{d.kernel, d.kernel, d.stride, d.stride, d.pad, d.pad, d.pad, d.pad, n.dil};
 }
-enum StepKind { S_INPUT, S_CONV, S_DW, S_ADD, S_MAXPOOL, S_AVGPOOL, S_REQUANT, S_OUTPUT, S_FUSED, S_STEMPOOL, S_IR, S_P12, S_CHAIN, S_BCHAIN, S_HEAD2, S_IRCHAIN, S_DWS, S_DWS7, S_IRK, S_GCONV, S_CONCAT, S_UPSAMPLE, S_DECONV, S_SUMPOOL, S_CHANMAP, S_MUL, S_HGATE, S_TABLE, S_ARGMAX, S_PIXMAP, S_GCONVW, S_GCONVX, S_SE };
+enum StepKind { S_INPUT, S_CONV, S_DW, S_ADD, S_MAXPOOL, S_AVGPOOL, S_REQUANT, S_OUTPUT, S_FUSED, S_STEMPOOL, S_IR, S_P12, S_CHAIN, S_BCHAIN, S_HEAD2, S_IRCHAIN, S_DWS, S_DWS7, S_IRK, S_GCONV, S_CONCAT, S_UPSAMPLE, S_DECONV, S_SUMPOOL, S_CHANMAP, S_MUL, S_HGATE, S_TABLE, S_ARGMAX, S_PIXMAP, S_GCONVW, S_GCONVX, S_SE, S_GCONVP };
 // The kernel of a step whose kind has several, chosen once by the step's emitter (pass 3); bind_step, run_step and f8_net_autotune switch on it.
 //   S_CONV:  conv_igemm (f8_kernels.hip), the LDS-patch 3x3 (f8_conv3x3.hip), conv1x1_wreg (f8_wreg.hip), conv1x1_wstat (f8_wstat.hip),
 //            conv3x3s2_wreg (f8_s2conv.hip), the 1x1 conv + average pool (f8_pool.hip), the classifier fc_dense (f8_fc.hip)
@@ -193,7 +193,7 @@ struct Step {
     double bytes_per_img = 0, bytes_const = 0, ops_per_img = 0;
     double valu_per_img = 0;           // ESSENTIAL vector lane-operations per image (f8_net_launch_valu): what the reference's semantics need once the MFMAs are done
     // the launcher's arguments as far as the plan decides them (bind_step); run_step copies them and adds what the run decides
-    std::variant<std::monostate, ConvArgs, StemPoolArgs, FusedArgs, ChainArgs, BChainArgs, BCChainArgs, IRArgs, IRKArgs, IRChainArgs, DwsArgs, Dws7Args, DwArgs, GConvArgs, GConvWArgs, GConvXArgs, AddArgs, PoolArgs, AvgArgs, OutArgs, ConcatArgs, UpsampleArgs, ArgmaxArgs, DeconvArgs, SumPoolArgs, ChanMapArgs, PixMapArgs, MulArgs, TableArgs, TableMulArgs, SEArgs> args;
+    std::variant<std::monostate, ConvArgs, StemPoolArgs, FusedArgs, ChainArgs, BChainArgs, BCChainArgs, IRArgs, IRKArgs, IRChainArgs, DwsArgs, Dws7Args, DwArgs, GConvArgs, GConvWArgs, GConvXArgs, GConvPArgs, AddArgs, PoolArgs, AvgArgs, OutArgs, ConcatArgs, UpsampleArgs, ArgmaxArgs, DeconvArgs, SumPoolArgs, ChanMapArgs, PixMapArgs, MulArgs, TableArgs, TableMulArgs, SEArgs> args;
     int inst = 0;                      // the instance the launcher starts (the family's *_inst, f8_internal.h; bind_step)
     // S_CHAIN / S_BCHAIN: geometry, workgroups per image and resident per CU, the 7x7 cluster form (f8_cchain.hip)
     int C = 0, MID = 0, H = 0, W = 0, cin0 = 0, tiles = 0, wg_per_cu = 1; bool cluster = false;
@@ -473,6 +473,7 @@ static const OptKey kOptKeys[] = {
     {"dwdil_rows", "F8_DWDIL_ROWS", &Options::dwdil_rows, 0, 2, true},
     {"gconv_wide", "F8_GCONV_WIDE", &Options::gconv_wide, 0, 1, true},
     {"gconv_xwide", "F8_GCONV_XWIDE", &Options::gconv_xwide, 0, 1, true},
+    {"gconv_pw", "F8_GCONV_PW", &Options::gconv_pw, 0, 2, true},
     {"concat_i8", "F8_CONCAT_I8", &Options::concat_i8, 0, 1, true},
     {"upsample_i8", "F8_UPSAMPLE_I8", &Options::upsample_i8, 0, 1, true},
     {"sumpool_wide", "F8_SUMPOOL_WIDE", &Options::sumpool_wide, 0, 2, true},
@@ -1555,6 +1556,31 @@ static void pack_gconvw_weights(f8_net* net, Node& nd) {
                 tapsum[(size_t)o * 9 + t] += v;
                 wp[((((unit * 9 + t) * KS + kk / 32) * 64) + lane) * 16 + (kk & 15)] = v;
             }
+        }
+    }
+    pack_conv_bias(net, nd, tapsum);
+}
+
+// A grouped 1x1 on gconvp1x1_kernel (f8_gconvp.hip; gconvp_kernel_applies: cgi = cin / groups and cgo = cout / groups multiples of 4, cin != cout allowed).  A
+// UNIT is one group g x one subtile j of its cgo outputs: rows i < live = min(32, cgo - 32 j) are output channels g cgo + 32 j + i, K index kk < cgi is input
+// channel g cgi + kk, over KS = ceil(cgi / 32) K32 steps; every other row and K byte stays zero.  Fragment order [unit][kstep][lane][16 B], the lane <->
+// (row, K half) map of pack_gconv_weights.  Where the outputs' Cs > cout one more unit of zeros follows the last group.  The bias is pack_conv_bias' with one
+// class (no padding): [Cs of the outputs], + 128 * sum(w) for an unsigned input.
+static void pack_gconvp_weights(f8_net* net, Node& nd) {
+    const f8_conv_desc& d = nd.cd;
+    const int cgi = d.cin / d.groups, cgo = d.cout / d.groups, KS = (cgi + 31) / 32, nsub = (cgo + 31) / 32;
+    nd.coutP = round_up(d.cout, 32); nd.ck = 32 * KS; nd.ktot = 32 * KS;
+    nd.w_off = round_up_z(net->wblob.size(), 256);
+    net->wblob.resize(nd.w_off + (size_t)(d.groups * nsub + (nd.coutP > d.cout ? 1 : 0)) * KS * 1024, 0);
+    std::vector<long long> tapsum((size_t)d.cout, 0);
+    int8_t* wp = (int8_t*)net->wblob.data() + nd.w_off;
+    for (int o = 0; o < d.cout; ++o) {
+        const int g = o / cgo, i = o % cgo;                     // row i & 31 of unit g nsub + i / 32
+        const size_t unit = (size_t)g * nsub + i / 32;
+        for (int kk = 0; kk < cgi; ++kk) {
+            const int8_t v = nd.w[(size_t)o * cgi + kk];
+            tapsum[o] += v;
+            wp[((unit * KS + kk / 32) * 64 + (i & 31) + 32 * ((kk & 31) >> 4)) * 16 + (kk & 15)] = v;
         }
     }
     pack_conv_bias(net, nd, tapsum);
@@ -3123,6 +3149,41 @@ static bool gconvx_kernel_applies(const f8_net* net, const Node& n) {
     return opt.grouped == 1 && opt.gconv_xwide == 1 && d.kernel == 3 && n.dil == 1 && (d.stride == 1 || d.stride == 2) && d.pad <= 1 && d.cin == d.cout &&
            d.groups >= 2 && cg % 8 == 0 && cg >= 72 && cg <= 256 && !(d.groups == 2 && d.stride == 2 && o.H * o.W > 128);
 }
+// ... and which grouped 1x1 convs run on gconvp1x1_kernel (f8_gconvp.hip) under grouped = 1 with option gconv_pw >= 1: stride 1, pad 0, both group widths
+// multiples of 4, cgi <= 512, cin and cout otherwise unrelated.  The tiled int32 form is written per 8-channel group: a conv whose result is wanted in int32
+// (asked for, or read in more than two int8 formats: select_outputs) is in the set only where cgo is a multiple of 8.  gconv_pw = 1 adds gconvp_rule, the
+// measured rule (f8_gconvp.hip: 8 or more groups, cgi >= 48, cin x cout >= 2^17 — three of 19 measured shapes, profiles/gconv_pw_r24.md); 2 takes every shape of the set.  Default 0, as gconv_wide.
+static bool gconvp_kernel_applies(const f8_net* net, const Node& n) {
+    const Options& opt = net->opt;
+    const f8_conv_desc& d = n.cd;
+    if (opt.grouped != 1 || opt.gconv_pw < 1 || n.rect || d.kernel != 1 || n.dil != 1 || d.stride != 1 || d.pad != 0 || d.groups < 2 || d.groups >= d.cin) return false;
+    const int cgi = d.cin / d.groups, cgo = d.cout / d.groups;
+    if (cgi % 4 || cgo % 4 || cgi < 4 || cgi > 512 || cgo < 4) return false;
+    const Tensor& o = net->tensors[n.out];
+    int n8 = 0;
+    for (const Form& F : o.forms) n8 += F.kind == FORM_I8;
+    if ((n8 > 2 || find_form(o, FORM_I32, 0, 0) >= 0) && cgo % 8) return false;
+    return opt.gconv_pw == 2 || gconvp_rule(d.groups, cgi, cgo);
+}
+// a grouped 1x1 on the flat-pixel kernel: always a launch of its own, no join.  Counts: the grouped work, the input once + the output forms, the groups' weights
+static int emit_gconvp(f8_net* net, int i, Step& st, std::vector<int>* extra) {
+    auto& T = net->tensors;
+    Node& nd = net->nodes[i];
+    const Tensor& s = T[nd.a]; const Tensor& o = T[nd.out];
+    st.kind = S_GCONVP;
+    if (const int rc = conv_input_i8(net, nd, &st.src_t, &st.src_f)) return rc;
+    st.relu0 = nd.cd.relu;
+    pack_gconvp_weights(net, nd);
+    select_outputs(net, nd.out, &st.out, extra);
+    const double opix = (double)o.H * o.W;
+    st.ops_per_img = conv_ops(net, nd);
+    st.bytes_per_img = opix * s.Cs + out_bytes(st, o, opix);
+    st.bytes_const = weight_bytes(net, nd);
+    st.valu_per_img = 3.0 * opix * o.Cs * out_forms8(st);
+    st.name = "gconvp1x1s1:" + tname(net, nd.out);
+    return F8_OK;
+}
+
 // a grouped 3x3 on the slice-diagonal kernel (S_GCONV), the group-aligned one (S_GCONVW) or the weight-streaming one (S_GCONVX, which reads S_GCONVW's packed
 // weights): always a launch of its own, no join
 static int emit_gconv(f8_net* net, int i, Step& st, std::vector<int>* extra, StepKind kind) {
@@ -3184,6 +3245,7 @@ static int emit_conv_family(f8_net* net, int i, int max_batch, Step& st, std::ve
             if (nd.grouped && gconv_kernel_applies(net->opt, nd)) return emit_gconv(net, i, st, extra, S_GCONV);
             if (nd.grouped && gconvw_kernel_applies(net->opt, nd)) return emit_gconv(net, i, st, extra, S_GCONVW);
             if (nd.grouped && gconvx_kernel_applies(net, nd)) return emit_gconv(net, i, st, extra, S_GCONVX);
+            if (nd.grouped && gconvp_kernel_applies(net, nd)) return emit_gconvp(net, i, st, extra);
             return emit_conv(net, i, max_batch, st, extra);
     }
 }
@@ -4103,6 +4165,23 @@ static int bind_step(f8_net* net, Step& st) {
             gconvw_kernel_name(kb, sizeof kb, wa);
             st.args = wa; break;
         }
+        case S_GCONVP: {
+            const Tensor& sT = T[st.src_t];
+            const Tensor& oT = T[nd.out];
+            GConvPArgs a{};
+            a.w = W8(nd.w_off); a.bias = B32(nd.b_off);
+            a.HW = oT.H * oT.W; a.Ci = sT.Cs; a.Co = oT.Cs;
+            a.groups = nd.cd.groups; a.cgi = nd.cd.cin / a.groups; a.cgo = nd.cd.cout / a.groups; a.cout = nd.cd.cout;
+            a.ks = (a.cgi + 31) / 32; a.nsub = (a.cgo + 31) / 32;
+            gconvp_plan(a.groups, a.cgi, a.cgo, (long)(opt.whole_batch_launches ? net->max_batch : std::max(1, net->max_batch / opt.split)) * a.HW, &a.GS, &a.TP, &a.pitch);      // (the tile for the largest launch)
+            a.nspan = (a.groups + a.GS - 1) / a.GS;
+            const int sb = a.cgi % 8 ? 4 : 16;
+            a.dCHS = fast_divisor((uint32_t)(a.pitch / sb)); a.dGSL = fast_divisor((uint32_t)(32 * a.ks / sb));
+            a.relu0 = st.relu0;
+            out_formats(a.q);                                     // integer requantisation whatever requant_float says (as f8_gconvw.hip)
+            gconvp_kernel_name(kb, sizeof kb, a);
+            st.args = a; break;
+        }
         case S_DECONV: {
             const Tensor& sT = T[st.src_t];
             const Tensor& oT = T[nd.out];
@@ -4657,6 +4736,7 @@ static int run_step(const f8_net* net, const RunIO& io, const Step& st, int n0, 
         case S_GCONV: { GConvArgs a = std::get<GConvArgs>(st.args); a.x_bytes = (uint32_t)(src_io(a, &a.out32).bytes_per_img * N); e = launch_gconv(a, s); break; }
         case S_GCONVW: { GConvWArgs a = std::get<GConvWArgs>(st.args); a.x_bytes = (uint32_t)(src_io(a, &a.out32).bytes_per_img * N); e = launch_gconvw(a, s); break; }
         case S_GCONVX: { GConvXArgs a = std::get<GConvXArgs>(st.args); a.x_bytes = (uint32_t)(src_io(a, &a.out32).bytes_per_img * N); e = launch_gconvx(a, s); break; }
+        case S_GCONVP: { GConvPArgs a = std::get<GConvPArgs>(st.args); a.x_bytes = (uint32_t)(src_io(a, &a.out32).bytes_per_img * N); e = launch_gconvp(a, s); break; }
         case S_DECONV: { DeconvArgs a = std::get<DeconvArgs>(st.args); a.x_bytes = (uint32_t)(src_io(a, &a.out32).bytes_per_img * N); e = launch_deconv(a, st.inst, s); break; }
         case S_SUMPOOL: { SumPoolArgs a = std::get<SumPoolArgs>(st.args); src_io(a, &a.out32); e = launch_sumpool(a, st.inst, s); break; }
         case S_MAXPOOL: { PoolArgs a = std::get<PoolArgs>(st.args); src_io(a, &a.out32); e = launch_maxpool(a, st.inst, s); break; }

@@ -25,13 +25,13 @@ def accept_grouped(net, convs, options=None):
     """The raw builder refuses grouped convs (1 < groups < cin) unless the handle's option `grouped` says otherwise, and the option must be set
     before the conv is added.  The high-level entry points call this before they record: a value the caller gave (options, or F8_GROUPED in the
     environment) is applied as it is; with none, `grouped` becomes 1 when one of `convs` — (cin, groups[, kernel[, dilation]]) — is grouped.  A
-    `gconv_wide` key of `options` (group widths 24 .. 64 on the group-aligned kernel) and a `gconv_xwide` key (72 .. 256 on the weight-streaming kernel) are
-    forwarded the same way; nothing sets them unasked.
+    `gconv_wide` key of `options` (group widths 24 .. 64 on the group-aligned kernel) and a `gconv_xwide` key (72 .. 256 on the weight-streaming kernel) and a
+    `gconv_pw` key (grouped 1x1 convs, cin != cout allowed, on the group-aligned flat-pixel kernel) are forwarded the same way; nothing sets them unasked.
 
     Large depthwise kernels (groups == cin, square kernel 8 .. 31) are opt-in the same way through option `dw_large` (environment F8_DW_LARGE): a value
     the caller gave is applied as it is; with none, `dw_large` becomes 1 when one of `convs` names such a kernel.  Dilated depthwise 5x5 / 7x7 convs
     (dilation > 1) likewise through option `dw_dilated` (environment F8_DW_DILATED)."""
-    for key in ('gconv_wide', 'gconv_xwide'):
+    for key in ('gconv_wide', 'gconv_xwide', 'gconv_pw'):
         if options and key in options:
             net.set_option(key, options[key])
     if options and 'grouped' in options:
@@ -583,7 +583,7 @@ def build_net(spec: topology.NetSpec, params: dict, max_batch: int, hw: int = 22
 
 def record_net(spec: topology.NetSpec, params: dict, hw: int = 224, input_fraclen=None, taps=(), options=None) -> F8Net:
     """The recording half of build_net: the graph is in the handle, not yet planned (set planning options, then finalize).
-    options: only its `grouped`, `gconv_wide`, `gconv_xwide`, `dw_large` and `dw_dilated` keys are read here — grouped convs, large depthwise
+    options: only its `grouped`, `gconv_wide`, `gconv_xwide`, `gconv_pw`, `dw_large` and `dw_dilated` keys are read here — grouped convs, large depthwise
     kernels and dilated depthwise 5x5 / 7x7 convs are accepted while they are recorded (accept_grouped).
 
     taps: names of further tensors to return, marked as int32 outputs 1, 2, ... in the order given (output 0 stays the float

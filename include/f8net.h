@@ -564,6 +564,12 @@ int f8_net_check(f8_net* net);
  *               groups at stride 2 on a map of more than 128 output pixels, measured slower; 0: every plan, token and kernel as without the key.
  *               Nothing sets it unasked; forwarded like gconv_wide.  Same values either way, bit for bit; grouped = 2 ignores it.  Out of scope:
  *               cin != cout, other group widths, kernel sizes, dilation, a join in the epilogue),
+ *               gconv_pw (default 0; environment F8_GCONV_PW.  With grouped = 1: a grouped 1x1 conv — stride 1, pad 0, cin / groups and cout / groups
+ *               multiples of 4, cin / groups <= 512, cin != cout allowed; where its result is wanted in int32, cout / groups a multiple of 8 — runs
+ *               f8::gconvp1x1_kernel<SB, KSM>, f8_gconvp.hip, plan token gconvp1x1s1:, in place of the dense expansion: 2 = every such conv, 1 = those the
+ *               measured rule names (8 or more groups, cin / groups >= 48, cin x cout >= 2^17); 0: every plan, token and kernel as without the key.  Nothing
+ *               sets it unasked; forwarded like gconv_wide.  Same values either way, bit for bit; grouped = 2 ignores it.  Out of scope: stride 2, other
+ *               group widths, a join in the epilogue),
  *               concat_i8 (default 1: a concat whose result is read in at most two int8 formats and by nothing else, with values the planner can
  *               bound, runs f8::concat_i8_kernel on its operands' int8 forms, plan token concat_i8:; 0: every concat runs f8::concat_i32_kernel on
  *               their int32 forms, token concat_i32:.  Same values either way, bit for bit),
