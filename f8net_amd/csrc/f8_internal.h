@@ -79,6 +79,8 @@ struct Options {
                                  // dwconvk_dil_dot4_kernel (f8_dwk.hip) at stride 1 with int8 forms only (and dwk_dot4 = 1) and on dwconvk_kernel elsewhere; 2 = accepted, always dwconvk_kernel
     int dwdil_rows = 0;          // with dw_dilated = 1: output rows a thread of dwconvk_dil_dot4_kernel owns: 0 = the measured rule (1 everywhere: dwdil_rows, f8_dwk.hip),
                                  // 1 / 2 = that many everywhere (the A/B of tools/ab_dwdil.py; same values either way)
+    int dw_deconv = 0;           // depthwise transposed convs (groups == cin == cout, kernel 1 .. 16, stride 2 .. 8, pad 0 .. kernel - 1): 0 = refused by f8_net_conv_transpose; 1 = accepted, on
+                                 // dwdeconv_dot4_kernel (f8_dwdeconv.hip) with int8 forms only, ceil(kernel / stride) <= 4 (and dwk_dot4 = 1) and on dwdeconv_kernel elsewhere; 2 = accepted, always dwdeconv_kernel
     int gconv_wide = 0;          // with grouped = 1: 1 = grouped 3x3 convs of group width cg in {24, 40, 48, 56, 64} (cin == cout, stride 1 / 2, pad 0 / 1) on gconvw3x3_kernel
                                  // (f8_gconvw.hip, gconvw3x3s<S>:); 0 (default, until it is measured): the dense expansion, as before the kernel existed
     int gconv_xwide = 0;         // with grouped = 1: 1 = grouped 3x3 convs of group width cg = 72 .. 256, a multiple of 8 (cin == cout, groups >= 2, stride 1 / 2, pad 0 / 1) on
@@ -448,6 +450,21 @@ struct DeconvArgs {
     QuantOut q[2];
     int32_t tiles;                         // pixel tiles (64 pixels: a wave's two MFMA tiles) of the largest phase at N images (set by the launcher)
     DeconvPhase ph[kMaxDeconvPhases];
+};
+
+// Depthwise transposed convolution (f8_dwdeconv.hip; f8_net_conv_transpose with groups == cin == cout under option dw_deconv), kernel 1 .. 16, stride 2 .. 8,
+// NHWC int8 in, VALU, with the images of pack_dwdeconv_weights.  T = ceil(k / stride) taps per axis and phase.
+struct DwDeconvArgs {
+    const int8_t* x; const int8_t* w;      // w: [k * k][Cs] tap-major (dwdeconv_kernel)
+    const int32_t* bias;                   // [Cs]
+    const int8_t* w4;                      // dwdeconv_dot4_kernel (T <= 4): [stride^2 phases][T columns][Cs / 4][4 channels] dwords, byte j of (rh * stride + rw, tw, quad, e) =
+                                           // w[4 quad + e][rh + stride * j][rw + stride * tw], 0 where that kernel row or column is >= k
+    const int32_t* bias4;                  // ... and [stride^2 phases][Cs]: bias + 128 * (the sum of the phase's taps) for unsigned inputs
+    int32_t N, H, W, P, Q, Cs, k, stride, pad;
+    int32_t in_signed;
+    int32_t relu0;
+    int32_t* out32;
+    QuantOut q[2];
 };
 
 struct OutArgs {                           // NHWC int32 -> NCHW int32 / float32
@@ -897,6 +914,11 @@ hipError_t launch_upsample(const UpsampleArgs& a, int inst, hipStream_t s);
 int deconv_inst(const DeconvArgs& a);                              // f8_deconv.hip.  The cout tiles per wave: 2 (deconv_kernel<2>, coutP >= 64) or 1 (deconv_kernel<1>)
 const char* deconv_kernel_name(int inst);
 hipError_t launch_deconv(const DeconvArgs& a, int inst, hipStream_t s);
+// f8_dwdeconv.hip.  0: dwdeconv_kernel<in_signed>; T = ceil(k / stride) = 1 .. 4: dwdeconv_dot4_kernel<T> (nq = 1 / 2 int8 outputs and no int32 one, `dot4` = Options::dwk_dot4,
+// `mode` = Options::dw_deconv == 1, dwdeconv_rule)
+int dwdeconv_inst(const DwDeconvArgs& a, bool out32, int nq, bool dot4, int mode);
+int dwdeconv_kernel_name(char* buf, size_t cap, const DwDeconvArgs& a, int inst);
+hipError_t launch_dwdeconv(const DwDeconvArgs& a, int inst, hipStream_t s);
 int chanmap_inst(const ChanMapArgs& a, bool i8);                   // f8_chanmap.hip.  0: chanmap_i32_kernel, 1 / 2: slice_i8_kernel<true> / <false>, 3 / 4 / 5: shuffle_i8_kernel<16> / <4> / <2>, 6: shuffle_i8_general_kernel
 const char* chanmap_kernel_name(int inst);
 hipError_t launch_chanmap(const ChanMapArgs& a, int inst, hipStream_t s);

@@ -162,7 +162,7 @@ static f8_conv_geom geom_of(const Node& n) {
     const f8_conv_desc& d = n.cd;
     return f8_conv_geom{d.kernel, d.kernel, d.stride, d.stride, d.pad, d.pad, d.pad, d.pad, n.dil};
 }
-enum StepKind { S_INPUT, S_CONV, S_DW, S_ADD, S_MAXPOOL, S_AVGPOOL, S_REQUANT, S_OUTPUT, S_FUSED, S_STEMPOOL, S_IR, S_P12, S_CHAIN, S_BCHAIN, S_HEAD2, S_IRCHAIN, S_DWS, S_DWS7, S_IRK, S_GCONV, S_CONCAT, S_UPSAMPLE, S_DECONV, S_SUMPOOL, S_CHANMAP, S_MUL, S_HGATE, S_TABLE, S_ARGMAX, S_PIXMAP, S_GCONVW, S_GCONVX, S_SE, S_GCONVP };
+enum StepKind { S_INPUT, S_CONV, S_DW, S_ADD, S_MAXPOOL, S_AVGPOOL, S_REQUANT, S_OUTPUT, S_FUSED, S_STEMPOOL, S_IR, S_P12, S_CHAIN, S_BCHAIN, S_HEAD2, S_IRCHAIN, S_DWS, S_DWS7, S_IRK, S_GCONV, S_CONCAT, S_UPSAMPLE, S_DECONV, S_SUMPOOL, S_CHANMAP, S_MUL, S_HGATE, S_TABLE, S_ARGMAX, S_PIXMAP, S_GCONVW, S_GCONVX, S_SE, S_GCONVP, S_DWDECONV };
 // The kernel of a step whose kind has several, chosen once by the step's emitter (pass 3); bind_step, run_step and f8_net_autotune switch on it.
 //   S_CONV:  conv_igemm (f8_kernels.hip), the LDS-patch 3x3 (f8_conv3x3.hip), conv1x1_wreg (f8_wreg.hip), conv1x1_wstat (f8_wstat.hip),
 //            conv3x3s2_wreg (f8_s2conv.hip), the 1x1 conv + average pool (f8_pool.hip), the classifier fc_dense (f8_fc.hip)
@@ -193,7 +193,7 @@ struct Step {
     double bytes_per_img = 0, bytes_const = 0, ops_per_img = 0;
     double valu_per_img = 0;           // ESSENTIAL vector lane-operations per image (f8_net_launch_valu): what the reference's semantics need once the MFMAs are done
     // the launcher's arguments as far as the plan decides them (bind_step); run_step copies them and adds what the run decides
-    std::variant<std::monostate, ConvArgs, StemPoolArgs, FusedArgs, ChainArgs, BChainArgs, BCChainArgs, IRArgs, IRKArgs, IRChainArgs, DwsArgs, Dws7Args, DwArgs, GConvArgs, GConvWArgs, GConvXArgs, GConvPArgs, AddArgs, PoolArgs, AvgArgs, OutArgs, ConcatArgs, UpsampleArgs, ArgmaxArgs, DeconvArgs, SumPoolArgs, ChanMapArgs, PixMapArgs, MulArgs, TableArgs, TableMulArgs, SEArgs> args;
+    std::variant<std::monostate, ConvArgs, StemPoolArgs, FusedArgs, ChainArgs, BChainArgs, BCChainArgs, IRArgs, IRKArgs, IRChainArgs, DwsArgs, Dws7Args, DwArgs, GConvArgs, GConvWArgs, GConvXArgs, GConvPArgs, AddArgs, PoolArgs, AvgArgs, OutArgs, ConcatArgs, UpsampleArgs, ArgmaxArgs, DeconvArgs, DwDeconvArgs, SumPoolArgs, ChanMapArgs, PixMapArgs, MulArgs, TableArgs, TableMulArgs, SEArgs> args;
     int inst = 0;                      // the instance the launcher starts (the family's *_inst, f8_internal.h; bind_step)
     // S_CHAIN / S_BCHAIN: geometry, workgroups per image and resident per CU, the 7x7 cluster form (f8_cchain.hip)
     int C = 0, MID = 0, H = 0, W = 0, cin0 = 0, tiles = 0, wg_per_cu = 1; bool cluster = false;
@@ -295,8 +295,8 @@ static int64_t conv_acc_max(Node& nd) {
         m = 0;
         for (int o = 0; o < nd.cd.cout; ++o) {
             int64_t s = 0;
-            // a transposed conv's weights are [cin][cout][k][k]; the sum over ALL taps bounds every phase, which sees a subset of them
-            for (size_t k = 0; k < per; ++k) { const int v = nd.kind == N_DECONV ? nd.w[((k / kk) * nd.cd.cout + o) * kk + k % kk] : nd.w[(size_t)o * per + k]; s += v < 0 ? -v : v; }
+            // a transposed conv's weights are [cin][cout][k][k]; the sum over ALL taps bounds every phase, which sees a subset of them (a depthwise one's: [C][1][k][k], as a conv's)
+            for (size_t k = 0; k < per; ++k) { const int v = nd.kind == N_DECONV && nd.cd.groups == 1 ? nd.w[((k / kk) * nd.cd.cout + o) * kk + k % kk] : nd.w[(size_t)o * per + k]; s += v < 0 ? -v : v; }
             const int64_t b = o < (int)nd.bias.size() ? (int64_t)nd.bias[o] : 0;
             m = std::max(m, s * xmax + (b < 0 ? -b : b));
         }
@@ -471,6 +471,7 @@ static const OptKey kOptKeys[] = {
     {"dw_large", "F8_DW_LARGE", &Options::dw_large, 0, 2, true},
     {"dw_dilated", "F8_DW_DILATED", &Options::dw_dilated, 0, 2, true},
     {"dwdil_rows", "F8_DWDIL_ROWS", &Options::dwdil_rows, 0, 2, true},
+    {"dw_deconv", "F8_DW_DECONV", &Options::dw_deconv, 0, 2, true},
     {"gconv_wide", "F8_GCONV_WIDE", &Options::gconv_wide, 0, 1, true},
     {"gconv_xwide", "F8_GCONV_XWIDE", &Options::gconv_xwide, 0, 1, true},
     {"gconv_pw", "F8_GCONV_PW", &Options::gconv_pw, 0, 2, true},
@@ -794,9 +795,13 @@ int f8_net_conv_transpose(f8_net* net, int src, const f8_conv_desc* desc, int ou
     if (d.cin != s.C) return fail(F8_ERR_INVALID, "%s: cin %d != source channels %d", who, d.cin, s.C);
     if (d.kernel < 1 || d.stride < 1 || d.pad < 0 || d.cout < 1)
         return fail(F8_ERR_INVALID, "%s: bad geometry (kernel %d, stride %d, pad %d, cout %d)", who, d.kernel, d.stride, d.pad, d.cout);
-    if (d.groups != 1) return fail(F8_ERR_UNSUPPORTED, "%s: groups %d: only groups == 1 is built", who, d.groups);
-    if (d.kernel > 8) return fail(F8_ERR_UNSUPPORTED, "%s: kernel %d > 8 is not built", who, d.kernel);
-    if (d.stride > 4) return fail(F8_ERR_UNSUPPORTED, "%s: stride %d > 4 is not built (kernel %d)", who, d.stride, d.kernel);
+    // depthwise (groups == cin == cout; weights [C][1][k][k]) under option dw_deconv: kernel 1 .. 16, stride 2 .. 8 on the kernels of f8_dwdeconv.hip; stride 1 is the
+    // flipped depthwise conv.  Every other groups != 1 is refused as ever, and with the option 0 so is this one, in the same words.
+    const bool dw = net->opt.dw_deconv >= 1 && d.groups != 1 && d.groups == d.cin && d.cout == d.cin;
+    if (d.groups != 1 && !dw) return fail(F8_ERR_UNSUPPORTED, "%s: groups %d: only groups == 1 is built", who, d.groups);
+    const int kmax = dw ? 16 : 8, smax = dw ? 8 : 4;
+    if (d.kernel > kmax) return fail(F8_ERR_UNSUPPORTED, "%s: kernel %d > %d is not built", who, d.kernel, kmax);
+    if (d.stride > smax) return fail(F8_ERR_UNSUPPORTED, "%s: stride %d > %d is not built (kernel %d)", who, d.stride, smax, d.kernel);
     if (d.pad > d.kernel - 1) return fail(F8_ERR_UNSUPPORTED, "%s: pad %d > kernel - 1 = %d is not built", who, d.pad, d.kernel - 1);
     if (output_padding < 0 || output_padding >= d.stride)
         return fail(F8_ERR_INVALID, "%s: output_padding %d outside [0, stride %d)", who, output_padding, d.stride);
@@ -811,9 +816,19 @@ int f8_net_conv_transpose(f8_net* net, int src, const f8_conv_desc* desc, int ou
         return fail(F8_ERR_UNSUPPORTED, "%s: the %lld x %lld x %d result exceeds 2 GiB per tensor", who, (long long)P, (long long)Q, d.cout);
     if (!w) return fail(F8_ERR_INVALID, "%s: null weight", who);
     const int k = d.kernel;
-    const size_t wn = (size_t)d.cin * d.cout * k * k;
+    const size_t wn = (size_t)d.cin * (dw ? 1 : d.cout) * k * k;
     for (size_t i = 0; i < wn; ++i)
         if (w[i] < -128 || w[i] > 127) return fail(F8_ERR_INVALID, "%s: weight %d does not fit int8", who, w[i]);
+    if (d.stride == 1 && dw) {
+        // the depthwise conv with pad' = k - 1 - pad over the weights flipped in both axes ([C][1][k][k] either way): add_conv_node's rules and refusals
+        std::vector<int32_t> wc(wn);
+        for (int c = 0; c < d.cin; ++c)
+            for (int r = 0; r < k; ++r)
+                for (int q = 0; q < k; ++q) wc[((size_t)c * k + (k - 1 - r)) * k + (k - 1 - q)] = w[((size_t)c * k + r) * k + q];
+        f8_conv_desc c = d;
+        c.pad = k - 1 - d.pad;
+        return add_conv_node(net, src, c, 1, wc.data(), b, N_CONV, who);
+    }
     if (d.stride == 1) {
         // not a new op: the plain conv with pad' = k - 1 - pad over the weights flipped in both axes and swapped to [cout][cin][k][k]
         std::vector<int32_t> wc(wn);
@@ -1436,6 +1451,49 @@ static void pack_dw_weights(f8_net* net, Node& nd) {
         uint32_t b = (uint32_t)nd.bias[c];
         if (!d.input_signed) b += (uint32_t)(128ll * sum);
         b4[c] = (int32_t)b;
+    }
+}
+
+// The images of a depthwise transposed conv (f8_dwdeconv.hip; raw weights [C][1][k][k]), at the four offsets of pack_dwk_weights:
+//  (1) [k * k][Cs] tap-major + plain bias                                   — dwdeconv_kernel
+//  (2) where T = ceil(k / s) <= 4: [s^2 phases][T columns][Cs / 4][4 channels] dwords for dwdeconv_dot4_kernel: byte j of dword (rh s + rw, tw, quad, e) = the
+//      weight of channel 4 quad + e at kernel row rh + s j, column rw + s tw — 0 where that row or column is >= k, whose slots of a dot4 may then hold any
+//      byte —, and the per-phase bias [s^2][Cs]: bias + 128 * (the sum of the phase's taps) when the input is unsigned (stored biased; the kernel replaces
+//      out-of-image taps by the biased zero).  A phase without a tap (k <= rh or k <= rw) keeps zero weights and the plain bias.
+static void pack_dwdeconv_weights(f8_net* net, Node& nd) {
+    const f8_conv_desc& d = nd.cd;
+    const Tensor& src = net->tensors[nd.a];
+    const int k = d.kernel, s = d.stride, T = (k + s - 1) / s, Cs = src.Cs;
+    const bool dot4 = T <= 4;
+    nd.coutP = Cs; nd.ck = 0; nd.ktot = 0;
+    nd.w_off = round_up_z(net->wblob.size(), 256);
+    nd.b_off = round_up_z(nd.w_off + (size_t)k * k * Cs, 256);
+    nd.rc_off = round_up_z(nd.b_off + (size_t)Cs * 4, 256);                                       // dot4 weights
+    nd.cc_off = round_up_z(nd.rc_off + (dot4 ? (size_t)s * s * T * Cs * 4 : 0), 256);             // dot4 bias
+    net->wblob.resize(nd.cc_off + (dot4 ? (size_t)s * s * Cs * 4 : 0), 0);
+    int8_t* wp = (int8_t*)net->wblob.data() + nd.w_off;
+    int32_t* bp = (int32_t*)(net->wblob.data() + nd.b_off);
+    int8_t* w4 = (int8_t*)net->wblob.data() + nd.rc_off;
+    int32_t* b4 = (int32_t*)(net->wblob.data() + nd.cc_off);
+    for (int c = 0; c < d.cout; ++c) {
+        bp[c] = nd.bias[c];
+        for (int r = 0; r < k; ++r)
+            for (int q = 0; q < k; ++q) wp[(size_t)(r * k + q) * Cs + c] = nd.w[((size_t)c * k + r) * k + q];
+        if (!dot4) continue;
+        for (int rh = 0; rh < s; ++rh)
+            for (int rw = 0; rw < s; ++rw) {
+                const int ph = rh * s + rw;
+                long long sum = 0;
+                for (int j = 0; rh + s * j < k; ++j)
+                    for (int tw = 0; rw + s * tw < k; ++tw) {
+                        const int8_t v = nd.w[((size_t)c * k + rh + s * j) * k + rw + s * tw];
+                        w4[((((size_t)ph * T + tw) * (Cs / 4) + c / 4) * 4 + c % 4) * 4 + j] = v;
+                        sum += v;
+                    }
+                uint32_t b = (uint32_t)nd.bias[c];
+                if (!d.input_signed) b += (uint32_t)(128ll * sum);
+                b4[(size_t)ph * Cs + c] = (int32_t)b;
+            }
     }
 }
 
@@ -3213,6 +3271,21 @@ static int emit_deconv(f8_net* net, int i, Step& st, std::vector<int>* extra) {
     Node& nd = net->nodes[i];
     const f8_conv_desc& d = nd.cd;
     const Tensor& s = T[nd.a]; Tensor& o = T[nd.out];
+    if (d.groups != 1) {                            // depthwise (option dw_deconv): a launch of its own on the kernels of f8_dwdeconv.hip
+        st.kind = S_DWDECONV;
+        if (const int rc = conv_input_i8(net, nd, &st.src_t, &st.src_f)) return rc;
+        st.relu0 = d.relu;
+        pack_dwdeconv_weights(net, nd);
+        select_outputs_or_i32(net, nd.out, &st.out, extra);
+        const double ipx = (double)s.H * s.W, opx = (double)o.H * o.W;
+        st.ops_per_img = 2.0 * ipx * d.kernel * d.kernel * d.cin;               // every input pixel meets every tap of its channel once
+        st.bytes_per_img = ipx * s.Cs + out_bytes(st, o, opx);
+        st.bytes_const = (double)s.Cs * (d.kernel * d.kernel + 4);
+        st.valu_per_img = 3.0 * opx * o.Cs * out_forms8(st);
+        char buf[64]; snprintf(buf, sizeof buf, "dwdeconv%dx%ds%d:", d.kernel, d.kernel, d.stride);
+        st.name = buf + tname(net, nd.out);
+        return F8_OK;
+    }
     st.kind = S_DECONV;
     if (const int rc = conv_input_i8(net, nd, &st.src_t, &st.src_f)) return rc;
     st.relu0 = d.relu;
@@ -4197,6 +4270,18 @@ static int bind_step(f8_net* net, Step& st) {
             snprintf(kb, sizeof kb, "%s", deconv_kernel_name(st.inst = deconv_inst(a)));      // integer requantisation whatever requant_float says (as f8_gconv.hip)
             out_formats(a.q); st.args = a; break;
         }
+        case S_DWDECONV: {
+            const Tensor& sT = T[st.src_t];
+            const Tensor& oT = T[nd.out];
+            DwDeconvArgs a{};
+            a.w = W8(nd.w_off); a.bias = B32(nd.b_off);
+            a.w4 = W8(nd.rc_off); a.bias4 = B32(nd.cc_off);
+            a.H = sT.H; a.W = sT.W; a.P = oT.H; a.Q = oT.W; a.Cs = sT.Cs; a.k = nd.cd.kernel; a.stride = nd.cd.stride; a.pad = nd.cd.pad;
+            a.in_signed = nd.cd.input_signed; a.relu0 = st.relu0;
+            out_formats(a.q);                                     // integer requantisation whatever requant_float says (as f8_dwk.hip)
+            dwdeconv_kernel_name(kb, sizeof kb, a, st.inst = dwdeconv_inst(a, out32, nq, opt.dwk_dot4, opt.dw_deconv));
+            st.args = a; break;
+        }
         case S_ADD: case S_REQUANT: {
             AddArgs a{};
             a.Cs = T[st.src_t].Cs; a.a_shl = st.acc_shl; a.b_shl = st.res_shl; a.relu = st.relu1;
@@ -4738,6 +4823,7 @@ static int run_step(const f8_net* net, const RunIO& io, const Step& st, int n0, 
         case S_GCONVX: { GConvXArgs a = std::get<GConvXArgs>(st.args); a.x_bytes = (uint32_t)(src_io(a, &a.out32).bytes_per_img * N); e = launch_gconvx(a, s); break; }
         case S_GCONVP: { GConvPArgs a = std::get<GConvPArgs>(st.args); a.x_bytes = (uint32_t)(src_io(a, &a.out32).bytes_per_img * N); e = launch_gconvp(a, s); break; }
         case S_DECONV: { DeconvArgs a = std::get<DeconvArgs>(st.args); a.x_bytes = (uint32_t)(src_io(a, &a.out32).bytes_per_img * N); e = launch_deconv(a, st.inst, s); break; }
+        case S_DWDECONV: { DwDeconvArgs a = std::get<DwDeconvArgs>(st.args); src_io(a, &a.out32); e = launch_dwdeconv(a, st.inst, s); break; }
         case S_SUMPOOL: { SumPoolArgs a = std::get<SumPoolArgs>(st.args); src_io(a, &a.out32); e = launch_sumpool(a, st.inst, s); break; }
         case S_MAXPOOL: { PoolArgs a = std::get<PoolArgs>(st.args); src_io(a, &a.out32); e = launch_maxpool(a, st.inst, s); break; }
         case S_AVGPOOL: { AvgArgs a = std::get<AvgArgs>(st.args); src_io(a, &a.out32); e = launch_avgpool(a, s); break; }

@@ -48,6 +48,15 @@ def accept_grouped(net, convs, options=None):
         net.set_option('dw_dilated', 1)
 
 
+def accept_dw_deconv(net, deconvs, options=None):
+    """Depthwise transposed convs (groups == cin == cout) are opt-in at the raw builder through option `dw_deconv` (environment F8_DW_DECONV), set before the
+    op is added: a value the caller gave is applied as it is; with none, `dw_deconv` becomes 1 when one of `deconvs` — (cin, groups) — is depthwise."""
+    if options and 'dw_deconv' in options:
+        net.set_option('dw_deconv', options['dw_deconv'])
+    elif 'F8_DW_DECONV' not in os.environ and any(g == c > 1 for c, g in deconvs):
+        net.set_option('dw_deconv', 1)
+
+
 def conv_pair(v):
     """An int or a pair as (h, w)."""
     if isinstance(v, (tuple, list)):
@@ -123,13 +132,14 @@ class F8Net:
         return t
 
     def conv_transpose(self, src, weight, bias, *, stride, pad, output_padding=0, weight_fl, input_fl, input_signed,
-                       quant_input=True, relu=False, label=None):
-        """Transposed convolution (f8_net_conv_transpose): weight [cin, cout, k, k] as nn.ConvTranspose2d.weight; the result is
-        [(H - 1) stride - 2 pad + k + output_padding]^2 at fraclen weight_fl + input_fl.  stride 1 is recorded as the equivalent plain conv."""
+                       quant_input=True, relu=False, label=None, groups=1):
+        """Transposed convolution (f8_net_conv_transpose): weight [cin, cout / groups, k, k] as nn.ConvTranspose2d.weight; the result is
+        [(H - 1) stride - 2 pad + k + output_padding]^2 at fraclen weight_fl + input_fl.  stride 1 is recorded as the equivalent plain conv.
+        groups: 1, or cin (depthwise, weight [cin, 1, k, k]) on a handle whose option `dw_deconv` is set."""
         w = _np_i32(weight)
-        cin, cout, k, k2 = w.shape
+        cin, cout_g, k, k2 = w.shape
         assert k == k2
-        d = ConvDesc(cin=cin, cout=cout, kernel=k, stride=stride, pad=pad, groups=1,
+        d = ConvDesc(cin=cin, cout=cout_g * groups, kernel=k, stride=stride, pad=pad, groups=groups,
                      weight_fl=int(weight_fl), input_fl=int(input_fl), input_signed=int(bool(input_signed)),
                      quant_input=int(bool(quant_input)), relu=int(bool(relu)))
         b = None if bias is None else _np_i32(bias)

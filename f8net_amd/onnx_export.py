@@ -8,7 +8,7 @@ opset-11 vocabulary is written directly from the integer graph — per op the no
                                    Clip(f32 bounds), Cast(i32)                      (fix_quant_ops.py:99-112)
     int_op_only_fix_quant, n <= 0  Pow/Cast/Mul, Clip, Cast(i32)                    (fix_quant_ops.py:105-112)
     conv / ReLU                    Conv(int32 W, B initializers), Relu, Cast(i32)
-    transposed conv / ReLU         ConvTranspose(int32 W [cin, cout, k, k], B; strides, pads, output_padding), Relu, Cast(i32)
+    transposed conv / ReLU         ConvTranspose(int32 W [cin, cout / group, k, k], B; strides, pads, output_padding, group 1 or cin), Relu, Cast(i32)
     residual join                  Pow/Cast/Mul, Add, Clip(-+2^31 as f32), Cast(i32) [, Relu, Cast]   (fix_resnet.py:40-54,77)
     head max-pool                  Cast(f32), MaxPool, Cast(i32)                     (fix_resnet.py:358-359)
     FXQAvgPool2d                   Cast(i64), ReduceSum(-1) x2, Cast(i32)            (fix_quant_ops.py:130-133)
@@ -188,7 +188,7 @@ def export_graph(ig: IntGraph) -> bytes:
                 y = w.emit('Conv', ins, {'dilations': [int(o.dilation) if kh > 1 else 1, int(o.dilation) if kw > 1 else 1], 'group': int(o.groups),
                                          'kernel_shape': [kh, kw], 'pads': [pt, pl, pb, pr], 'strides': [sh, sw]})
             elif o.kind == 'deconv':
-                y = w.emit('ConvTranspose', ins, {'dilations': [1, 1], 'group': 1, 'kernel_shape': [o.kernel] * 2, 'output_padding': [int(o.output_padding)] * 2,
+                y = w.emit('ConvTranspose', ins, {'dilations': [1, 1], 'group': int(o.groups), 'kernel_shape': [o.kernel] * 2, 'output_padding': [int(o.output_padding)] * 2,
                                                   'pads': [o.pad] * 4, 'strides': [o.stride] * 2})
             else:
                 y = w.emit('Gemm', ins, {'alpha': 1.0, 'beta': 1.0, 'transB': 1})

@@ -68,7 +68,7 @@ class IntOp:
     channels: int = 0              # slice: how many; shuffle: the groups are in `groups`
     block: int = 0                 # d2s / s2d (depth_to_space / space_to_depth): the block size r
     order: str = None              # d2s / s2d: 'crd' | 'dcr' (include/f8net.h)
-    output_padding: int = 0        # deconv (transposed conv; weight [cin, cout, k, k]): ONNX `output_padding`, both equal
+    output_padding: int = 0        # deconv (transposed conv; weight [cin, cout / groups, k, k], `groups` 1 or cin): ONNX `output_padding`, both equal
     rect: tuple = None             # conv: None for a square kernel with one stride and one pad (`kernel`, `stride`, `pad`); else the rectangular geometry
                                    # (kh, kw, stride_h, stride_w, pad_top, pad_left, pad_bottom, pad_right) of f8_net_conv_rect, and those three are 0
 
@@ -207,11 +207,12 @@ class IntGraph:
     def build_net(self, max_batch, hw=None, input_fraclen=None, options=None):
         """Record the graph through libf8net.so's builder and plan it (f8_net_finalize).
         options: {key: value} for f8_net_set_option, applied before planning (as net.build_net's)."""
-        from .net import F8Net, accept_grouped
+        from .net import F8Net, accept_dw_deconv, accept_grouped
         V, layer = self.solve_fraclens(input_fraclen)
         net = F8Net()
         accept_grouped(net, [(o.weight.shape[1] * o.groups, o.groups, o.weight.shape[2] if o.weight.shape[2] == o.weight.shape[3] else 0, o.dilation)
                              for o in self.ops if o.kind == 'conv'], options)
+        accept_dw_deconv(net, [(o.weight.shape[0], o.groups) for o in self.ops if o.kind == 'deconv'], options)
         ids = {}
         for t, o in enumerate(self.ops):
             if o.kind == 'input':
@@ -229,7 +230,7 @@ class IntGraph:
                 i, w = layer[t]
                 ids[t] = net.conv_transpose(ids[o.src], o.weight, o.bias, stride=o.stride, pad=o.pad, output_padding=o.output_padding,
                                             weight_fl=w, input_fl=i, input_signed=o.signed, quant_input=o.shift is not None,
-                                            relu=o.relu, label=o.key)
+                                            relu=o.relu, label=o.key, groups=o.groups)
             elif o.kind == 'linear':
                 i, w = layer[t]
                 ids[t] = net.linear(ids[o.src], o.weight, o.bias, weight_fl=w, input_fl=i, input_signed=o.signed,
@@ -302,7 +303,7 @@ def tensor_shapes(ops):
             kh, kw, sh, sw, pt, pl, pb, pr = o.conv_geometry()
             out.append((o.weight.shape[0], (H + pt + pb - o.dilation * (kh - 1) - 1) // sh + 1, (W + pl + pr - o.dilation * (kw - 1) - 1) // sw + 1))
         elif o.kind == 'deconv':
-            out.append((o.weight.shape[1], (H - 1) * o.stride - 2 * o.pad + o.kernel + o.output_padding, (W - 1) * o.stride - 2 * o.pad + o.kernel + o.output_padding))
+            out.append((o.weight.shape[1] * o.groups, (H - 1) * o.stride - 2 * o.pad + o.kernel + o.output_padding, (W - 1) * o.stride - 2 * o.pad + o.kernel + o.output_padding))
         elif o.kind == 'linear':
             out.append((o.weight.shape[0], 1, 1))
         elif o.kind == 'concat':
@@ -803,8 +804,9 @@ def import_graph(model, input_signed=False) -> IntGraph:
                 raise OnnxImportError(f'ConvTranspose {wname}: auto_pad {ap!r}: only explicit pads')
             if 'output_shape' in a:
                 raise OnnxImportError(f'ConvTranspose {wname}: output_shape {list(a["output_shape"])}: only pads + output_padding')
-            if a.get('group', 1) != 1:
-                raise OnnxImportError(f'ConvTranspose {wname}: group {a.get("group")}: only group = 1')
+            group = int(a.get('group', 1))
+            if group != 1 and not (group == w.shape[0] and w.shape[1] == 1):      # depthwise: W [C, 1, k, k] (option dw_deconv; build_net sets it)
+                raise OnnxImportError(f'ConvTranspose {wname}: group {group}: only group = 1 or group = cin = cout (depthwise)')
             dil = list(a.get('dilations', [1, 1]))
             if any(d != 1 for d in dil):
                 raise OnnxImportError(f'ConvTranspose {wname}: dilations {dil}: only 1')
@@ -814,7 +816,7 @@ def import_graph(model, input_signed=False) -> IntGraph:
             if st[0] != st[1] or opad[0] != opad[1]:
                 raise OnnxImportError(f'ConvTranspose {wname}: unequal strides {st} / output_padding {opad}')
             ig.ops.append(IntOp('deconv', src=src, weight=w, bias=None if b is None else np.array(b, np.int32), stride=int(st[0]),
-                                pad=int(pads[0]), kernel=int(k[0]), shift=n, signed=signed, key=_layer_key(wname), output_padding=int(opad[0])))
+                                pad=int(pads[0]), kernel=int(k[0]), shift=n, signed=signed, key=_layer_key(wname), output_padding=int(opad[0]), groups=group))
             if n is None:
                 ig.ops[-1].signed = ig.input_signed
             val[out] = ('T', len(ig.ops) - 1)

@@ -113,11 +113,11 @@ class F8Conv2d(nn.Conv2d):
 
 class F8ConvTranspose2d(nn.ConvTranspose2d):
     """An integer `nn.ConvTranspose2d` in the manner of `int_conv` (the reference names a ReLUClipFXQConvTransposeBN, fix_quant_ops.py:9, and defines none)
-    with a HIP forward (`torch.ops.f8net.conv_transpose2d`): int32 `weight` [cin, cout, k, k], `bias`, buffers `weight_fraclen` / `input_fraclen`,
-    attribute `input_symmetric`, as F8Conv2d.  forward(x): x int32 NCHW holding input_fraclen-format 8-bit integers -> int32 NCHW."""
+    with a HIP forward (`torch.ops.f8net.conv_transpose2d`): int32 `weight` [cin, cout / groups, k, k], `bias`, buffers `weight_fraclen` / `input_fraclen`,
+    attribute `input_symmetric`, as F8Conv2d.  groups: 1, or in_channels = out_channels (depthwise; the op sets the handle's option dw_deconv itself).  forward(x): x int32 NCHW holding input_fraclen-format 8-bit integers -> int32 NCHW."""
 
-    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, output_padding=0, input_symmetric=False):
-        super().__init__(in_channels, out_channels, kernel_size, stride=stride, padding=padding, output_padding=output_padding, bias=True)
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, output_padding=0, input_symmetric=False, groups=1):
+        super().__init__(in_channels, out_channels, kernel_size, stride=stride, padding=padding, output_padding=output_padding, groups=groups, bias=True)
         self.weight.requires_grad_(False)
         self.bias.requires_grad_(False)
         self.weight.data = torch.zeros(self.weight.shape, dtype=torch.int32)
@@ -132,7 +132,7 @@ class F8ConvTranspose2d(nn.ConvTranspose2d):
         _require_dev_i32(x, 'F8ConvTranspose2d')
         w_fl, in_fl = self._fl.get(self)
         return torch.ops.f8net.conv_transpose2d(x, self.weight, self.bias, self.stride[0], self.padding[0], self.output_padding[0], w_fl, in_fl,
-                                                self.input_symmetric)
+                                                self.input_symmetric, self.groups)
 
 
 class F8Linear(nn.Linear):

@@ -44,7 +44,7 @@ from torch.library import Library
 
 from . import _lib
 from ._lib import check
-from .net import F8Net, accept_grouped
+from .net import F8Net, accept_dw_deconv, accept_grouped
 
 _DEF = Library('f8net', 'DEF')
 _DEF.define('requant(Tensor x, int fl, int input_fl, bool signed) -> Tensor')
@@ -52,7 +52,7 @@ _DEF.define('relu_(Tensor(a!) x) -> Tensor(a!)')
 _DEF.define('add_align_(Tensor(a!) res, Tensor x, int res_fl, int x_fl) -> Tensor(a!)')
 _DEF.define('conv2d(Tensor x, Tensor weight, Tensor? bias, int stride, int pad, int groups, int weight_fl, int input_fl, bool input_signed, int dilation=1) -> Tensor')
 _DEF.define('conv2d_rect(Tensor x, Tensor weight, Tensor? bias, int[2] stride, int[4] pads, int groups, int weight_fl, int input_fl, bool input_signed, int dilation=1) -> Tensor')
-_DEF.define('conv_transpose2d(Tensor x, Tensor weight, Tensor? bias, int stride, int pad, int output_padding, int weight_fl, int input_fl, bool input_signed) -> Tensor')
+_DEF.define('conv_transpose2d(Tensor x, Tensor weight, Tensor? bias, int stride, int pad, int output_padding, int weight_fl, int input_fl, bool input_signed, int groups=1) -> Tensor')
 _DEF.define('linear(Tensor x, Tensor weight, Tensor? bias, int weight_fl, int input_fl, bool input_signed) -> Tensor')
 _DEF.define('avgpool_sum(Tensor x) -> Tensor')
 _DEF.define('avgpool2d_sum(Tensor x, int k, int stride, int pad) -> Tensor')
@@ -238,25 +238,26 @@ def _deconv_out(n, k, stride, pad, output_padding):
     return (n - 1) * stride - 2 * pad + k + output_padding
 
 
-def _conv_transpose2d(x, weight, bias, stride, pad, output_padding, weight_fl, input_fl, input_signed):
-    """nn.ConvTranspose2d on int32 (weight [cin, cout, k, k]): one f8_net_conv_transpose launch behind the input launch."""
+def _conv_transpose2d(x, weight, bias, stride, pad, output_padding, weight_fl, input_fl, input_signed, groups=1):
+    """nn.ConvTranspose2d on int32 (weight [cin, cout / groups, k, k]; groups 1 or cin): one f8_net_conv_transpose launch behind the input launch."""
     _i32(x, 'conv_transpose2d')
     x = x.contiguous()
     N, C, H, W = x.shape
     key = ('deconv', x.device.index, C, H, W, id(weight), tuple(weight.shape), None if bias is None else id(bias), stride, pad, output_padding, weight_fl,
-           input_fl, bool(input_signed))
+           input_fl, bool(input_signed), groups)
 
     def build(n):
         net = F8Net()
+        accept_dw_deconv(net, [(C, groups)])
         t = net.input(C, H, W, input_fl)
         t = net.conv_transpose(t, _np(weight), _np(bias), stride=stride, pad=pad, output_padding=output_padding, weight_fl=weight_fl,
-                               input_fl=input_fl, input_signed=input_signed, quant_input=False, relu=False)
+                               input_fl=input_fl, input_signed=input_signed, quant_input=False, relu=False, groups=groups)
         net.output(t, as_float=False)
         return net.finalize(n)
 
     net = _plans.get(key, (weight, bias), N, build)
     k = weight.shape[2]
-    return net.run(x).view(N, weight.shape[1], _deconv_out(H, k, stride, pad, output_padding), _deconv_out(W, k, stride, pad, output_padding))
+    return net.run(x).view(N, weight.shape[1] * groups, _deconv_out(H, k, stride, pad, output_padding), _deconv_out(W, k, stride, pad, output_padding))
 
 
 def _linear(x, weight, bias, weight_fl, input_fl, input_signed):
@@ -530,8 +531,8 @@ _META.impl('conv2d', lambda x, w, b, stride, pad, groups, wfl, ifl, sgn, dilatio
 _META.impl('conv2d_rect', lambda x, w, b, stride, pads, groups, wfl, ifl, sgn, dilation=1: x.new_empty(
     (x.shape[0], w.shape[0], _rect_out(x.shape[2], w.shape[2], stride[0], pads[0], pads[2], dilation),
      _rect_out(x.shape[3], w.shape[3], stride[1], pads[1], pads[3], dilation))))
-_META.impl('conv_transpose2d', lambda x, w, b, stride, pad, opad, wfl, ifl, sgn: x.new_empty(
-    (x.shape[0], w.shape[1], _deconv_out(x.shape[2], w.shape[2], stride, pad, opad), _deconv_out(x.shape[3], w.shape[3], stride, pad, opad))))
+_META.impl('conv_transpose2d', lambda x, w, b, stride, pad, opad, wfl, ifl, sgn, groups=1: x.new_empty(
+    (x.shape[0], w.shape[1] * groups, _deconv_out(x.shape[2], w.shape[2], stride, pad, opad), _deconv_out(x.shape[3], w.shape[3], stride, pad, opad))))
 _META.impl('linear', lambda x, w, b, wfl, ifl, sgn: x.new_empty((x.shape[0], w.shape[0])))
 _META.impl('avgpool_sum', lambda x: x.new_empty((x.shape[0], x.shape[1])))
 _META.impl('avgpool2d_sum', lambda x, k, stride, pad: x.new_empty(

@@ -199,7 +199,14 @@ int f8_net_conv_rect(f8_net* net, int src, const f8_conv_desc* desc, const f8_co
  * and names itself as any f8_net_conv does.  stride >= 2 is one launch of f8::deconv_kernel<1 / 2> (f8_deconv.hip), plan token `deconv{k}x{k}s{s}:`; it joins
  * no fused block or chain launch and carries no residual join (an f8_net_add whose later operand it produces stays an `add:` launch).  It reads its
  * source's int8 form as a conv does, so a tensor it reads exists in device memory: no fused launch keeps it on chip (it cuts a launch as an output
- * tap does). */
+ * tap does).
+ * Depthwise (nn.ConvTranspose2d(C, C, k, stride, padding, output_padding, groups=C): DLA's IDAUp, bilinear-initialised per-class upsamplers): with option
+ * `dw_deconv` 1 or 2, set BEFORE this call, a desc with groups == cin == cout is accepted for 1 <= kernel <= 16, 2 <= stride <= 8, pad <= kernel - 1,
+ * output_padding < stride; weights [C, 1, k, k] as the module holds them, out[n, c, oh, ow] = b[c] + sum x_q[n, c, ih, iw] * w[c, 0, kh, kw] over the same
+ * taps.  One launch `dwdeconv{k}x{k}s{s}:` on f8::dwdeconv_dot4_kernel<T> (f8_dwdeconv.hip; T = ceil(kernel / stride) <= 4, int8 forms only, dw_deconv = 1
+ * and dwk_dot4 = 1) or f8::dwdeconv_kernel elsewhere.  Its stride 1 is recorded as the flipped depthwise conv and inherits f8_net_conv's rules for one
+ * (kernel 3 / 5 / 7 ..., pad' = kernel - 1 - pad).  1 < groups < cin, cout != cin and — with dw_deconv 0 — the depthwise form are F8_ERR_UNSUPPORTED
+ * ("groups N: only groups == 1 is built"); groups == 1 keeps its limits and its kernel whatever the option says. */
 int f8_net_conv_transpose(f8_net* net, int src, const f8_conv_desc* desc, int output_padding,
                           const int32_t* weight_host, const int32_t* bias_host);
 
@@ -617,7 +624,11 @@ int f8_net_check(f8_net* net);
  *               token dwconv{K}x{K}s{S}d{D}:, on f8::dwconvk_dil_dot4_kernel<K, ROWS> (f8_dwk.hip) at stride 1 with int8 forms only and dwk_dot4 = 1, on
  *               f8::dwconvk_kernel elsewhere; 2 = accepted, always f8::dwconvk_kernel.  Same values either way, bit for bit),
  *               dwdil_rows (0 .. 2, default 0, environment F8_DWDIL_ROWS; read at finalize: output rows a thread of f8::dwconvk_dil_dot4_kernel owns, 0 = the
- *               measured rule — 1 everywhere, profiles/dwdil_r23.md —, 1 / 2 = that many everywhere; the A/B switch of tools/ab_dwdil.py.  Same values)
+ *               measured rule — 1 everywhere, profiles/dwdil_r23.md —, 1 / 2 = that many everywhere; the A/B switch of tools/ab_dwdil.py.  Same values),
+ *               dw_deconv (0 .. 2, default 0, environment F8_DW_DECONV; read by f8_net_conv_transpose, so set it BEFORE the op is added: 0 = a depthwise
+ *               transposed conv is F8_ERR_UNSUPPORTED; 1 = accepted (groups == cin == cout, 1 <= kernel <= 16, 2 <= stride <= 8, pad <= kernel - 1), plan token
+ *               dwdeconv{k}x{k}s{s}:, on f8::dwdeconv_dot4_kernel<T> (f8_dwdeconv.hip) with int8 forms only, T = ceil(kernel / stride) <= 4 and dwk_dot4 = 1 — every
+ *               measured shape won there, profiles/dwdeconv_r25.md —, on f8::dwdeconv_kernel elsewhere; 2 = accepted, always f8::dwdeconv_kernel.  Same values)
  *   scheduling: chunk56 / chunk28 / chunk14 (images per chunk of the fused blocks; -1 = derived from chunk_budget_mb, 0 = whole
  *               batch), chunk_budget_mb (memory-side cache a chunk's int32 stream may occupy), chunk_ds, chunk_opener,
  *               split_streams, graph, stagger, stagger_pipelined, stem_wpc, stem_grid_div (row-walking head on 1 / n of the CUs; 0 = by output form), wstat_grid_div (0 .. 32, default 0, environment F8_WSTAT_GRID_DIV: f8::conv1x1_wstat_kernel sizes its pixel groups for 1 / n of the CUs, at least one — tests walk long tile rings on small maps; 0 = all of them; the plan and the values do not move), check_device, check_input_range, pipeline_depth (2..4 runs in flight),
