@@ -567,9 +567,10 @@ __global__ void __launch_bounds__(256) dwconv3x3_dot4_kernel(const DwArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// Max-pool (NHWC).  int32 input: exact max, then any of {int32, two requantised int8} outputs.
-// int8 input (already in the single consumer format; requant is monotone so pooling commutes with
-// it exactly): per-byte signed max — unsigned tensors are stored biased (x ^ 0x80), which preserves order.
+// Max-pool (NHWC), int32 input: exact max over the in-image taps, then any of {int32, two requantised int8} outputs.
+// An int8 input (already in the single consumer format; requant is monotone so pooling commutes with it exactly) is
+// maxpool_i8x16_kernel's below, the only int8 max-pool: every tensor's Cs is a multiple of 32 and f8_net_maxpool refuses
+// 2 * pad > k, so every int8 pool of a planned net is its (maxpool_inst).
 // ---------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) maxpool_kernel(const PoolArgs a) {
     const int cgs = a.Cs >> 2;
@@ -591,31 +592,19 @@ __global__ void __launch_bounds__(256) maxpool_kernel(const PoolArgs a) {
                 const int w = w0 + s;
                 if ((unsigned)w >= (unsigned)a.W) continue;
                 const int mi = (n * a.H + h) * a.W + w;
-                if (a.in_is_i8) {
-                    const unsigned xv = *(const unsigned*)((const int8_t*)a.x + (size_t)mi * a.Cs + c);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        mx[e] = max(mx[e], (int)(signed char)(xv >> (8 * e)));   // biased u8 keeps its order as s8
-                    }
-                } else {
-                    const v4i xv = *(const v4i*)((const int32_t*)a.x + i32t_index(mi, c, a.Cs));
-                    mx[0] = max(mx[0], xv.x); mx[1] = max(mx[1], xv.y);
-                    mx[2] = max(mx[2], xv.z); mx[3] = max(mx[3], xv.w);
-                }
+                const v4i xv = *(const v4i*)((const int32_t*)a.x + i32t_index(mi, c, a.Cs));
+                mx[0] = max(mx[0], xv.x); mx[1] = max(mx[1], xv.y);
+                mx[2] = max(mx[2], xv.z); mx[3] = max(mx[3], xv.w);
             }
         }
         const int mo = (n * a.P + p) * a.Q + q;
         const size_t o = (size_t)mo * a.Cs + c;
-        if (a.in_is_i8) {
-            *(unsigned*)(a.q[0].ptr + o) = pack4(mx[0], mx[1], mx[2], mx[3]);
-        } else {
-            if (a.out32) { v4i v = {mx[0], mx[1], mx[2], mx[3]}; *(v4i*)(a.out32 + i32t_index(mo, c, a.Cs)) = v; }
+        if (a.out32) { v4i v = {mx[0], mx[1], mx[2], mx[3]}; *(v4i*)(a.out32 + i32t_index(mo, c, a.Cs)) = v; }
 #pragma unroll
-            for (int k = 0; k < 2; ++k)
-                if (a.q[k].ptr)
-                    *(unsigned*)(a.q[k].ptr + o) =
-                        requant_pack4(mx[0], mx[1], mx[2], mx[3], a.q[k]);
-        }
+        for (int k = 0; k < 2; ++k)
+            if (a.q[k].ptr)
+                *(unsigned*)(a.q[k].ptr + o) =
+                    requant_pack4(mx[0], mx[1], mx[2], mx[3], a.q[k]);
     }
 }
 
@@ -1056,7 +1045,7 @@ hipError_t launch_dwconv(const DwArgs& a, int inst, hipStream_t s) {
     else hipLaunchKernelGGL(dwconv3x3_kernel<false>, dim3(grid_for(work)), dim3(256), 0, s, a);
     return hipGetLastError();
 }
-int maxpool_inst(const PoolArgs& a) { return a.in_is_i8 && (a.Cs & 15) == 0 && a.pad < a.k; }     // every window holds at least one in-image tap (pad < k)
+int maxpool_inst(const PoolArgs& a) { return a.in_is_i8 != 0; }     // (Cs % 32 == 0 and 2 * pad <= k: 16-byte groups, and every window holds an in-image tap)
 const char* maxpool_kernel_name(int inst) { return inst ? "f8::maxpool_i8x16_kernel" : "f8::maxpool_kernel"; }
 hipError_t launch_maxpool(const PoolArgs& a, int inst, hipStream_t s) {
     if (inst) {
