@@ -81,6 +81,10 @@ struct Options {
                                  // 1 / 2 = that many everywhere (the A/B of tools/ab_dwdil.py; same values either way)
     int dw_deconv = 0;           // depthwise transposed convs (groups == cin == cout, kernel 1 .. 16, stride 2 .. 8, pad 0 .. kernel - 1): 0 = refused by f8_net_conv_transpose; 1 = accepted, on
                                  // dwdeconv_dot4_kernel (f8_dwdeconv.hip) with int8 forms only, ceil(kernel / stride) <= 4 (and dwk_dot4 = 1) and on dwdeconv_kernel elsewhere; 2 = accepted, always dwdeconv_kernel
+    int maxpool_tile = 0;        // int8-mode max pools of stride 1, odd kernel 3 .. 13, pad kernel / 2: 0 = maxpool_i8x16_kernel (f8_kernels.hip), as ever; 1 = maxpool_tile_kernel<1>
+                                 // (f8_maxpool.hip) where maxpool_tile_rule keeps the shape; 2 = on it everywhere.  Same token (maxpool_i8:), same values
+    int fuse_spp = 0;            // 1 = a bytes-mode concat of a tensor x and one to three stride-1 max pools of it — side by side (SPP) or chained (SPPF), effective windows <= 13 —
+                                 // is ONE launch of maxpool_tile_kernel<LEVELS> that writes x and every level into its slice (spp{k1}_{k2}_{k3}+concat_i8:); 0 = the pools and the concat launch
     int gconv_wide = 0;          // with grouped = 1: 1 = grouped 3x3 convs of group width cg in {24, 40, 48, 56, 64} (cin == cout, stride 1 / 2, pad 0 / 1) on gconvw3x3_kernel
                                  // (f8_gconvw.hip, gconvw3x3s<S>:); 0 (default, until it is measured): the dense expansion, as before the kernel existed
     int gconv_xwide = 0;         // with grouped = 1: 1 = grouped 3x3 convs of group width cg = 72 .. 256, a multiple of 8 (cin == cout, groups >= 2, stride 1 / 2, pad 0 / 1) on
@@ -275,6 +279,22 @@ struct PoolArgs {                          // max-pool, NHWC
     int32_t* out32;
     QuantOut q[2];                         // when in_is_i8: q[0].ptr is the int8 output, no requant
 };
+
+// Stride-1 max pools on an LDS tile (f8_maxpool.hip; options maxpool_tile and fuse_spp): int8 in, int8 out, the output map is the input map.  Level l is a
+// window of 2 r[l] + 1 over level l - 1 (level -1 = x), stored at q[0].ptr + pixel * oCs + coff[l]; coff[3] >= 0: x itself is copied there.
+constexpr int kMaxpoolTilePatch = 24;      // the haloed patch is 24 x 24 pixels: a tile is (24 - 2 R)^2 output pixels
+struct MaxPoolTileArgs {
+    const int8_t* x;
+    int32_t N, H, W, Cs;                   // x: NHWC, Cs-byte pixels
+    int32_t R;                             // the halo: r[0] + .. + r[LEVELS - 1] <= 6
+    int32_t r[3]; uint32_t steps[3];       // per level: radius, and its doubling steps (maxpool_tile_steps)
+    int32_t oCs, coff[4];                  // output pixel pitch (bytes); first byte of level l in it; [3]: of x's copy, or -1
+    int32_t tiles_w, tiles_h;              // tiles per image: ceil(W / (24 - 2 R)), ceil(H / (24 - 2 R))
+    FastDiv dTW;                           // / tiles_w
+    QuantOut q[2];                         // q[0].ptr: the output (no requant: the values are x's)
+};
+// Where option maxpool_tile = 1 takes a stand-alone pool to the tile kernel, MEASURED (profiles/maxpool_tile_r26.md, batch 128): see f8_maxpool.hip's launcher.
+bool maxpool_tile_rule(int k, int H, int W, int Cs);
 
 struct AvgArgs {                           // FXQAvgPool2d sum over H*W, NHWC int32 in
     const int32_t* x; int32_t N, HW, Cs;
@@ -919,6 +939,9 @@ hipError_t launch_deconv(const DeconvArgs& a, int inst, hipStream_t s);
 int dwdeconv_inst(const DwDeconvArgs& a, bool out32, int nq, bool dot4, int mode);
 int dwdeconv_kernel_name(char* buf, size_t cap, const DwDeconvArgs& a, int inst);
 hipError_t launch_dwdeconv(const DwDeconvArgs& a, int inst, hipStream_t s);
+uint32_t maxpool_tile_steps(int w);                                // f8_maxpool.hip.  The instance of a launch is its LEVELS (1 .. 3): maxpool_tile_kernel<LEVELS>
+int maxpool_tile_kernel_name(char* buf, size_t cap, int levels);
+hipError_t launch_maxpool_tile(const MaxPoolTileArgs& a, int levels, hipStream_t s);
 int chanmap_inst(const ChanMapArgs& a, bool i8);                   // f8_chanmap.hip.  0: chanmap_i32_kernel, 1 / 2: slice_i8_kernel<true> / <false>, 3 / 4 / 5: shuffle_i8_kernel<16> / <4> / <2>, 6: shuffle_i8_general_kernel
 const char* chanmap_kernel_name(int inst);
 hipError_t launch_chanmap(const ChanMapArgs& a, int inst, hipStream_t s);

@@ -133,6 +133,11 @@ struct Node {
     size_t tab_off = 0;                // table / a mul with mul_table, pass 3: its device tables in the weight image (int32 entries, or 256 bytes per int8 form)
     int argmax_k = -1;                 // upsample, pass 2: the argmax output whose launch interpolates this node's result itself (option fuse_argmax): no launch and no form of its own, else -1
     int cat_into = -1;                 // concat, pass 2: the shuffle node whose launch reads this concat's operands: no launch and no form of its own
+    bool pool_tile = false;            // maxpool, pass 2: an int8-mode pool on maxpool_tile_kernel<1> (option maxpool_tile); false: maxpool_i8x16_kernel / maxpool_kernel
+    int spp_into = -1;                 // maxpool, pass 2: the concat node whose launch computes this pool (option fuse_spp): no launch and no form of its own
+    int spp_x = -1;                    // concat, pass 2: the pyramid's source tensor x — the launch is maxpool_tile_kernel<LEVELS> (option fuse_spp) —, else -1
+    std::vector<int> spp_pools;        // ... and its pool nodes, ascending effective window
+    std::vector<int> spp_k;            // ... and those windows (5, 9, 13)
     // planning
     int fused_into = -1;               // add: conv node that carries it
     int fused_add = -1;                // conv: add node carried
@@ -162,7 +167,7 @@ static f8_conv_geom geom_of(const Node& n) {
     const f8_conv_desc& d = n.cd;
     return f8_conv_geom{d.kernel, d.kernel, d.stride, d.stride, d.pad, d.pad, d.pad, d.pad, n.dil};
 }
-enum StepKind { S_INPUT, S_CONV, S_DW, S_ADD, S_MAXPOOL, S_AVGPOOL, S_REQUANT, S_OUTPUT, S_FUSED, S_STEMPOOL, S_IR, S_P12, S_CHAIN, S_BCHAIN, S_HEAD2, S_IRCHAIN, S_DWS, S_DWS7, S_IRK, S_GCONV, S_CONCAT, S_UPSAMPLE, S_DECONV, S_SUMPOOL, S_CHANMAP, S_MUL, S_HGATE, S_TABLE, S_ARGMAX, S_PIXMAP, S_GCONVW, S_GCONVX, S_SE, S_GCONVP, S_DWDECONV };
+enum StepKind { S_INPUT, S_CONV, S_DW, S_ADD, S_MAXPOOL, S_AVGPOOL, S_REQUANT, S_OUTPUT, S_FUSED, S_STEMPOOL, S_IR, S_P12, S_CHAIN, S_BCHAIN, S_HEAD2, S_IRCHAIN, S_DWS, S_DWS7, S_IRK, S_GCONV, S_CONCAT, S_UPSAMPLE, S_DECONV, S_SUMPOOL, S_CHANMAP, S_MUL, S_HGATE, S_TABLE, S_ARGMAX, S_PIXMAP, S_GCONVW, S_GCONVX, S_SE, S_GCONVP, S_DWDECONV, S_MAXPOOLT };
 // The kernel of a step whose kind has several, chosen once by the step's emitter (pass 3); bind_step, run_step and f8_net_autotune switch on it.
 //   S_CONV:  conv_igemm (f8_kernels.hip), the LDS-patch 3x3 (f8_conv3x3.hip), conv1x1_wreg (f8_wreg.hip), conv1x1_wstat (f8_wstat.hip),
 //            conv3x3s2_wreg (f8_s2conv.hip), the 1x1 conv + average pool (f8_pool.hip), the classifier fc_dense (f8_fc.hip)
@@ -193,7 +198,7 @@ struct Step {
     double bytes_per_img = 0, bytes_const = 0, ops_per_img = 0;
     double valu_per_img = 0;           // ESSENTIAL vector lane-operations per image (f8_net_launch_valu): what the reference's semantics need once the MFMAs are done
     // the launcher's arguments as far as the plan decides them (bind_step); run_step copies them and adds what the run decides
-    std::variant<std::monostate, ConvArgs, StemPoolArgs, FusedArgs, ChainArgs, BChainArgs, BCChainArgs, IRArgs, IRKArgs, IRChainArgs, DwsArgs, Dws7Args, DwArgs, GConvArgs, GConvWArgs, GConvXArgs, GConvPArgs, AddArgs, PoolArgs, AvgArgs, OutArgs, ConcatArgs, UpsampleArgs, ArgmaxArgs, DeconvArgs, DwDeconvArgs, SumPoolArgs, ChanMapArgs, PixMapArgs, MulArgs, TableArgs, TableMulArgs, SEArgs> args;
+    std::variant<std::monostate, ConvArgs, StemPoolArgs, FusedArgs, ChainArgs, BChainArgs, BCChainArgs, IRArgs, IRKArgs, IRChainArgs, DwsArgs, Dws7Args, DwArgs, GConvArgs, GConvWArgs, GConvXArgs, GConvPArgs, AddArgs, PoolArgs, AvgArgs, OutArgs, ConcatArgs, UpsampleArgs, ArgmaxArgs, DeconvArgs, DwDeconvArgs, MaxPoolTileArgs, SumPoolArgs, ChanMapArgs, PixMapArgs, MulArgs, TableArgs, TableMulArgs, SEArgs> args;
     int inst = 0;                      // the instance the launcher starts (the family's *_inst, f8_internal.h; bind_step)
     // S_CHAIN / S_BCHAIN: geometry, workgroups per image and resident per CU, the 7x7 cluster form (f8_cchain.hip)
     int C = 0, MID = 0, H = 0, W = 0, cin0 = 0, tiles = 0, wg_per_cu = 1; bool cluster = false;
@@ -486,6 +491,8 @@ static const OptKey kOptKeys[] = {
     {"fuse_table", "F8_FUSE_TABLE", &Options::fuse_table, 0, 2, true},
     {"fuse_argmax", "F8_FUSE_ARGMAX", &Options::fuse_argmax, 0, 1, true},
     {"fuse_se", "F8_FUSE_SE", &Options::fuse_se, 0, 2, true},
+    {"maxpool_tile", "F8_MAXPOOL_TILE", &Options::maxpool_tile, 0, 2, true},
+    {"fuse_spp", "F8_FUSE_SPP", &Options::fuse_spp, 0, 1, true},
 };
 static const OptKey* find_opt(const char* key) {
     if (!key) return nullptr;
@@ -2510,6 +2517,61 @@ static void ask_sources(f8_net* net, const std::vector<int>& srcs, int fl_ref, c
     }
 }
 
+// A max pool maxpool_tile_kernel (f8_maxpool.hip) computes: stride 1, odd kernel 3 .. 13, pad = kernel / 2 — the output map is the input map
+static bool spp_pool(const Node& p) { return p.kind == N_MAXPOOL && p.pstride == 1 && (p.pk & 1) && p.pk >= 3 && p.pk <= 13 && p.ppad == p.pk / 2; }
+// Option fuse_spp: is concat node i (bytes mode decided) spatial pyramid pooling — its operands, in any order, one tensor x and one to three such pools
+// that either all read x with distinct kernels (SPP) or form a chain p1 = pool(x), p2 = pool(p1), .. (SPPF), effective windows 1 + sum(k - 1) <= 13;
+// every pool read by the concat alone (in the chain: and by the next pool), none an output; the result in ONE int8 form; x at the concat's fraclen
+// with whole 32-channel rows (C == Cs: every slice then starts on a 16-byte boundary and the result has no pad channels to fill)?  Fills
+// Node::spp_x / spp_pools / spp_k.  Anything else keeps the pools' and the concat's own launches.
+static bool match_spp(f8_net* net, int i, int max_batch) {
+    auto& T = net->tensors; auto& ND = net->nodes;
+    Node& nd = ND[i];
+    const Tensor& o = T[nd.out];
+    const int K = (int)nd.srcs.size();
+    if (!nd.bytes_mode || o.forms.size() != 1 || K < 2 || K > 4 || max_batch > 65535) return false;
+    auto readers_ok = [&](const Node& p, int next) {             // the concat once, and `next` (a node id, or -1) once
+        const std::vector<int>& c = T[p.out].consumers;
+        if (is_output(net, p.out) || argmax_index(net, p.out) >= 0 || c.size() != (next >= 0 ? 2u : 1u)) return false;
+        return std::count(c.begin(), c.end(), i) == 1 && (next < 0 || std::count(c.begin(), c.end(), next) == 1);
+    };
+    for (int xi = 0; xi < K; ++xi) {
+        const int x = nd.srcs[xi];
+        if (T[x].C != T[x].Cs || T[x].fl != o.fl) continue;
+        std::vector<int> pools;                                   // the other operands' producers
+        for (int j = 0; j < K; ++j) if (j != xi) pools.push_back(T[nd.srcs[j]].prod);
+        bool all = true;
+        for (int p : pools) all = all && spp_pool(ND[p]);
+        if (!all) continue;
+        // SPP: every pool reads x; ascending kernels, all distinct
+        std::sort(pools.begin(), pools.end(), [&](int p, int q) { return ND[p].pk < ND[q].pk; });
+        bool spp = true;
+        for (size_t j = 0; j < pools.size(); ++j)
+            spp = spp && ND[pools[j]].a == x && readers_ok(ND[pools[j]], -1) && (j == 0 || ND[pools[j]].pk > ND[pools[j - 1]].pk);
+        std::vector<int> ks;
+        for (int p : pools) ks.push_back(ND[p].pk);
+        if (!spp) {
+            // SPPF: the chain from x
+            std::vector<int> chain; ks.clear();
+            int t = x, win = 1;
+            for (size_t j = 0; j < pools.size(); ++j) {
+                int nx = -1;
+                for (int p : pools) if (ND[p].a == t && std::find(chain.begin(), chain.end(), p) == chain.end()) { nx = p; break; }
+                if (nx < 0) break;
+                chain.push_back(nx); win += ND[nx].pk - 1; ks.push_back(win); t = ND[nx].out;
+            }
+            if (chain.size() != pools.size() || win > 13) continue;
+            bool ok = true;
+            for (size_t j = 0; j < chain.size(); ++j) ok = ok && readers_ok(ND[chain[j]], j + 1 < chain.size() ? chain[j + 1] : -1);
+            if (!ok) continue;
+            pools = chain;
+        }
+        nd.spp_x = x; nd.spp_pools = pools; nd.spp_k = ks;
+        return true;
+    }
+    return false;
+}
+
 // Option fuse_table.  1: the measured rule (profiles/table_r15.md, batch 128, EfficientNet-B0's shapes): the fused launch is 1.07 - 1.59 x faster than
 // the two launches on every shape up to 144 x 56 x 56 = 451 584 values an image and slower (0.96 x) on the one above, 96 x 112 x 112 = 1 204 224 —
 // so it fuses below 2^20 values an image.  2: always (what the measurement ran).  0: never.
@@ -2622,6 +2684,7 @@ static void plan_tensor_forms(f8_net* net, int max_batch) {
                 if (nd.fused_into < 0) { add_form(T[nd.a], FORM_I32, 0, 0); add_form(T[nd.b], FORM_I32, 0, 0); }
                 break;
             case N_MAXPOOL: {
+                if (nd.spp_into >= 0) break;                     // the concat behind it computes it and asked x for its form (N_CONCAT below, a later node)
                 Tensor& o = T[nd.out];
                 if (!o.forms.empty() && T[nd.a].consumers.size() == 1 && !is_output(net, nd.a)) {
                     // ResNet head: 7x7/2 stem conv + this pool in one launch (the conv output never leaves LDS)
@@ -2633,9 +2696,12 @@ static void plan_tensor_forms(f8_net* net, int max_batch) {
                         break;                                   // no HBM form of the conv output
                     }
                 }
-                if (o.forms.size() == 1 && o.forms[0].kind == FORM_I8)
+                if (o.forms.size() == 1 && o.forms[0].kind == FORM_I8) {
                     add_form(T[nd.a], FORM_I8, o.forms[0].n, o.forms[0].sgn);
-                else
+                    // option maxpool_tile: the stride-1 pools with the map kept on the LDS-tile kernel (f8_maxpool.hip)
+                    nd.pool_tile = spp_pool(nd) && max_batch <= 65535 &&
+                                   (opt.maxpool_tile == 2 || (opt.maxpool_tile == 1 && maxpool_tile_rule(nd.pk, o.H, o.W, o.Cs)));
+                } else
                     add_form(T[nd.a], FORM_I32, 0, 0);
                 break;
             }
@@ -2648,6 +2714,11 @@ static void plan_tensor_forms(f8_net* net, int max_batch) {
                 const Tensor& o = T[nd.out];
                 const bool exact = requant_commutes(net, nd.srcs, nd.out, o.forms);
                 nd.bytes_mode = opt.concat_i8 && int8_forms_only(net, nd.out) && exact;
+                if (opt.fuse_spp && match_spp(net, i, max_batch)) {      // the pyramid in one launch: only x is read, in the concat's format
+                    for (int p : nd.spp_pools) ND[p].spp_into = i;
+                    ask_sources(net, {nd.spp_x}, o.fl, o.forms, true);
+                    break;
+                }
                 ask_sources(net, nd.srcs, o.fl, o.forms, nd.bytes_mode);
                 break;
             }
@@ -3338,6 +3409,15 @@ static int emit_add(f8_net* net, int i, Step& st, std::vector<int>* extra) {
     return F8_OK;
 }
 
+// Essential vector work of maxpool_tile_kernel per image: level l (window k_l - k_{l-1} + 1 over the previous level) takes its doubling steps on each axis, a
+// packed 16-bit max covering two bytes: steps lane-operations per byte and level.  The xors, the even / odd split and the halo are what the ratio shows.
+static double tile_valu(const Tensor& x, const std::vector<int>& ks) {
+    double steps = 0;
+    int prev = 1;
+    for (int k : ks) { for (uint32_t s = maxpool_tile_steps(k - prev + 1); s; s >>= 4) steps += 1; prev = k; }
+    return (double)x.H * x.W * x.C * steps;
+}
+
 static int emit_maxpool(f8_net* net, int i, Step& st, std::vector<int>* extra) {
     auto& T = net->tensors;
     const Node& nd = net->nodes[i];
@@ -3349,6 +3429,28 @@ static int emit_maxpool(f8_net* net, int i, Step& st, std::vector<int>* extra) {
     select_outputs_or_i32(net, nd.out, &st.out, extra);
     st.name = std::string(i8 ? "maxpool_i8:" : "maxpool_i32:") + tname(net, nd.out);
     st.bytes_per_img = (double)s.H * s.W * s.Cs * (i8 ? 1 : 4) + out_bytes(st, o, (double)o.H * o.W);
+    if (nd.pool_tile) {                              // the same token and bytes on maxpool_tile_kernel<1>; its essential work: tile_valu
+        st.kind = S_MAXPOOLT;
+        st.valu_per_img = tile_valu(o, {nd.pk});
+    }
+    return F8_OK;
+}
+
+// The pyramid launch hosted by concat node i (match_spp): x in, x and every level out, each into its channel slice of the concat's result
+static int emit_spp(f8_net* net, int i, Step& st, std::vector<int>* extra) {
+    const Node& nd = net->nodes[i];
+    const Tensor& o = net->tensors[nd.out]; const Tensor& x = net->tensors[nd.spp_x];
+    st.kind = S_MAXPOOLT;
+    select_outputs(net, nd.out, &st.out, extra);
+    const Form& F = o.forms[st.out.f8[0]];
+    st.src_t = nd.spp_x; st.src_f = find_form(x, FORM_I8, F.n - (o.fl - x.fl), F.sgn);
+    if (st.src_f < 0) return fail(F8_ERR_STATE, "f8_net_finalize: planner bug: the pyramid's source t%d lacks the concat's int8 form", nd.spp_x);
+    const double px = (double)o.H * o.W;
+    st.bytes_per_img = px * (x.C + o.C);             // x read once, every real byte of the result written once
+    st.valu_per_img = tile_valu(x, nd.spp_k);
+    std::string tok = "spp";
+    for (size_t l = 0; l < nd.spp_k.size(); ++l) tok += (l ? "_" : "") + std::to_string(nd.spp_k[l]);
+    st.name = tok + "+concat_i8:" + tname(net, nd.out);
     return F8_OK;
 }
 
@@ -3639,6 +3741,7 @@ static int emit_steps(f8_net* net, int max_batch) {
         if (nd.kind == N_CONV && (nd.absorbed_by >= 0 || nd.dual_host >= 0)) continue;
         if (nd.kind == N_CONV && nd.chain_into >= 0 && nd.chain_into != i) continue;      // runs inside the chain launch of a later block
         if (nd.kind == N_MAXPOOL && nd.sp_conv >= 0) continue;
+        if (nd.kind == N_MAXPOOL && nd.spp_into >= 0) continue;      // a level of the pyramid launch its concat hosts
         if (nd.kind == N_AVGPOOL && nd.pool_host >= 0) continue;     // runs in its conv's launch
         if (nd.kind == N_AVGPOOL && nd.se_host >= 0) continue;       // summed in the SE launch hosted by fc2 (f8_se.hip)
         if (nd.kind == N_LINEAR && nd.absorbed_by >= 0) continue;    // fc1 of a B_SE block (the only block a linear is a member of)
@@ -3654,7 +3757,7 @@ static int emit_steps(f8_net* net, int max_batch) {
             case N_ADD: rc = emit_add(net, i, st, &extra); break;
             case N_MAXPOOL: rc = emit_maxpool(net, i, st, &extra); break;
             case N_AVGPOOL: rc = emit_avgpool(net, i, st, &extra); break;
-            case N_CONCAT: rc = emit_concat(net, i, st, &extra); break;
+            case N_CONCAT: rc = nd.spp_x >= 0 ? emit_spp(net, i, st, &extra) : emit_concat(net, i, st, &extra); break;
             case N_UPSAMPLE: rc = emit_upsample(net, i, st, &extra); break;
             case N_DECONV: rc = emit_deconv(net, i, st, &extra); break;
             case N_SUMPOOL: rc = emit_sumpool(net, i, st, &extra); break;
@@ -4409,6 +4512,24 @@ static int bind_step(f8_net* net, Step& st) {
             snprintf(kb, sizeof kb, "%s", maxpool_kernel_name(st.inst = maxpool_inst(a)));
             out_formats(a.q); st.args = a; break;
         }
+        case S_MAXPOOLT: {                           // a stand-alone pool (nd: N_MAXPOOL) or the pyramid its concat hosts (nd: N_CONCAT, match_spp)
+            const Tensor& sT = T[st.src_t]; const Tensor& oT = T[nd.out];
+            MaxPoolTileArgs a{};
+            a.H = sT.H; a.W = sT.W; a.Cs = sT.Cs; a.oCs = oT.Cs;
+            const std::vector<int> ks = nd.kind == N_MAXPOOL ? std::vector<int>{nd.pk} : nd.spp_k;
+            int prev = 1;
+            for (size_t l = 0; l < ks.size(); ++l) { a.r[l] = (ks[l] - prev) / 2; a.steps[l] = maxpool_tile_steps(ks[l] - prev + 1); a.R += a.r[l]; prev = ks[l]; }
+            a.coff[3] = -1;
+            for (int j = 0, off = 0; nd.kind == N_CONCAT && j < (int)nd.srcs.size(); off += T[nd.srcs[j++]].C) {
+                if (nd.srcs[j] == nd.spp_x) a.coff[3] = off;
+                for (size_t l = 0; l < ks.size(); ++l) if (nd.srcs[j] == ND[nd.spp_pools[l]].out) a.coff[l] = off;
+            }
+            const int tile = kMaxpoolTilePatch - 2 * a.R;
+            a.tiles_w = (a.W + tile - 1) / tile; a.tiles_h = (a.H + tile - 1) / tile;
+            a.dTW = fast_divisor((uint32_t)a.tiles_w);
+            maxpool_tile_kernel_name(kb, sizeof kb, st.inst = (int)ks.size());
+            out_formats(a.q); st.args = a; break;
+        }
         case S_SE: {
             const Tensor& sT = T[st.src_t];
             SEArgs a{};
@@ -4826,6 +4947,7 @@ static int run_step(const f8_net* net, const RunIO& io, const Step& st, int n0, 
         case S_DWDECONV: { DwDeconvArgs a = std::get<DwDeconvArgs>(st.args); src_io(a, &a.out32); e = launch_dwdeconv(a, st.inst, s); break; }
         case S_SUMPOOL: { SumPoolArgs a = std::get<SumPoolArgs>(st.args); src_io(a, &a.out32); e = launch_sumpool(a, st.inst, s); break; }
         case S_MAXPOOL: { PoolArgs a = std::get<PoolArgs>(st.args); src_io(a, &a.out32); e = launch_maxpool(a, st.inst, s); break; }
+        case S_MAXPOOLT: { MaxPoolTileArgs a = std::get<MaxPoolTileArgs>(st.args); int32_t* none = nullptr; src_io(a, &none); e = launch_maxpool_tile(a, st.inst, s); break; }
         case S_AVGPOOL: { AvgArgs a = std::get<AvgArgs>(st.args); src_io(a, &a.out32); e = launch_avgpool(a, s); break; }
         case S_SE: { SEArgs a = std::get<SEArgs>(st.args); src_io(a, &a.out32); e = launch_se(a, st.inst, s); break; }
         case S_ADD: case S_REQUANT: {

@@ -628,7 +628,15 @@ int f8_net_check(f8_net* net);
  *               dw_deconv (0 .. 2, default 0, environment F8_DW_DECONV; read by f8_net_conv_transpose, so set it BEFORE the op is added: 0 = a depthwise
  *               transposed conv is F8_ERR_UNSUPPORTED; 1 = accepted (groups == cin == cout, 1 <= kernel <= 16, 2 <= stride <= 8, pad <= kernel - 1), plan token
  *               dwdeconv{k}x{k}s{s}:, on f8::dwdeconv_dot4_kernel<T> (f8_dwdeconv.hip) with int8 forms only, T = ceil(kernel / stride) <= 4 and dwk_dot4 = 1 — every
- *               measured shape won there, profiles/dwdeconv_r25.md —, on f8::dwdeconv_kernel elsewhere; 2 = accepted, always f8::dwdeconv_kernel.  Same values)
+ *               measured shape won there, profiles/dwdeconv_r25.md —, on f8::dwdeconv_kernel elsewhere; 2 = accepted, always f8::dwdeconv_kernel.  Same values),
+ *               maxpool_tile (0 .. 2, default 0, environment F8_MAXPOOL_TILE: an f8_net_maxpool of stride 1, odd kernel 3 .. 13, pad kernel / 2 whose result exists in
+ *               one int8 form runs f8::maxpool_tile_kernel<1> (f8_maxpool.hip: row and column passes of running maxima over an LDS tile) — 2 = every such
+ *               pool, 1 = those the measured rule keeps (kernel >= 5 where the map fills 0.35 of its tiles, kernel 3 from 80 x 80 pixels on,
+ *               profiles/maxpool_tile_r26.md), 0 = f8::maxpool_i8x16_kernel as before.  Plan token maxpool_i8: either way.  Same values),
+ *               fuse_spp (0 / 1, default 0, environment F8_FUSE_SPP: 1 = an f8_net_concat whose operands, in any order, are a tensor x (channels a multiple
+ *               of 32) and one to three stride-1 max pools of it — side by side with distinct kernels (SPP) or chained (SPPF), effective windows <= 13, pad
+ *               kernel / 2, read by nothing else — and whose result exists in one int8 form is ONE launch of f8::maxpool_tile_kernel<LEVELS>, token
+ *               spp{k1}_{k2}_{k3}+concat_i8: — 1.24 - 2.59 x faster than the four launches at batch 128; anything else plans as with 0.  Same values)
  *   scheduling: chunk56 / chunk28 / chunk14 (images per chunk of the fused blocks; -1 = derived from chunk_budget_mb, 0 = whole
  *               batch), chunk_budget_mb (memory-side cache a chunk's int32 stream may occupy), chunk_ds, chunk_opener,
  *               split_streams, graph, stagger, stagger_pipelined, stem_wpc, stem_grid_div (row-walking head on 1 / n of the CUs; 0 = by output form), wstat_grid_div (0 .. 32, default 0, environment F8_WSTAT_GRID_DIV: f8::conv1x1_wstat_kernel sizes its pixel groups for 1 / n of the CUs, at least one — tests walk long tile rings on small maps; 0 = all of them; the plan and the values do not move), check_device, check_input_range, pipeline_depth (2..4 runs in flight),
